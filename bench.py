@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- trace cells/sec (and proofs/sec) of the MI355X STARK prover hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one complete prove() (commit trace -> quotient -> commit chunks -> open -> FRI ->
 queries -> proof on the host) of BASELINE.json configs[2]: the build-defined SynthMulAir-64 trace,
@@ -250,6 +250,25 @@ def _leaf_tree_bytes(N: int, w: int, qd: int, fri_leaves, tree_log: int) -> dict
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64 (exact for the u32 words the prover
+    computes), at most 64 MiB in all.  Returns the record's `dump_outputs` entry."""
+    import numpy as np
+
+    conv = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "bytes": total, "dtype": "float64",
+            "arrays": {name: list(a.shape) for name, a in conv.items()}}
+
+
 def _omp_set_threads(n: int):
     import ctypes
     try:
@@ -371,7 +390,7 @@ def fold_benchmark(args):
             ctx.check(l.ts_fri_fold_device(ctx.h, d_in.data_ptr(), h, bp, d_out.data_ptr()))
         fold()
         ctx.synchronize()
-        reps = max(args.steps, 10)
+        reps = args.steps
         ctx.set_kernel_timing(True)
         for _ in range(reps):
             fold()
@@ -403,7 +422,7 @@ def fold_benchmark(args):
                "sample": "oracle fold_matrix (C, one thread), best of 5 per size; value = the 2^22 row", "rows": crow}
     big = rows[-1]
     rec = {"metric": "fold_matrix on EF4 vectors (fri/benches/fold_even_odd.rs:14-46 sizes), input elements/sec at 2^22",
-           "value": big["elements_per_s_gpu"], "unit": "input elements/sec", "n_gpus": 1, "steps": max(args.steps, 10),
+           "value": big["elements_per_s_gpu"], "unit": "input elements/sec", "n_gpus": 1, "steps": args.steps,
            "warmup": 1, "ms_per_step": big["kernel_us"] * 1e-3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "u32", "data": "synthetic (uniform field elements, resident in HBM)",
            "config": {"workload": "fold_matrix, EF4 vectors of 2^12 .. 2^22 elements, one launch each"},
@@ -413,6 +432,11 @@ def fold_benchmark(args):
            "cpu_baseline": cpu, "rows": rows,
            "note": "below ~2^19 elements a launch is at the ~7 us floor HIP events see for any kernel; the prover "
                    "never launches such folds alone (rounds with <= 2^17 leaves fold inside k_fri_round / k_fri_tail)"}
+    if args.dump_outputs:
+        # the last timed step is the 2^22 fold: a fixed, seeded sample of its 2^21 output rows (EF4 each)
+        got = held[-1][1]
+        rows = np.sort(np.random.default_rng(7).choice(len(got), 1 << 18, replace=False))
+        rec["dump_outputs"] = dump_outputs(args.dump_outputs, {"fold_out_rows": rows, "fold_out": got[rows]})
     print(json.dumps(rec), flush=True)
 
 
@@ -619,12 +643,17 @@ def main():
     ap.add_argument("--windows", type=int, default=3,
                     help="timed windows of K steps each, back to back; `value` is the FIRST (the contract's "
                          "K steps), the others are reported as spread")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the proof's words; for "
+                         "--workload fold a seeded sample of the 2^22 fold's output) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     # ---- launch protocol (before anything imports torch or touches the GPU)
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if env_world is None and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     if env_world is not None and int(env_world) != args.gpus:
@@ -792,6 +821,8 @@ def main():
         def prove_one(i):
             last["proof"] = ts.prove_sharded(config, cair, ts.BfChallenger(), mats[i], pis, comm,
                                              trace_replicated=not sliced, local_quotient=localq)
+            if i == total - 1:  # the last timed step (--dump-outputs)
+                last["final"] = last["proof"]
     else:
         # one resident trace per step (prove() consumes it); beyond 100 GB of them (288 GB of HBM) the
         # trace of a step is generated on the device at the start of the step instead, inside the
@@ -812,8 +843,10 @@ def main():
             tg = time.perf_counter()
             start_gate()
             t0 = time.perf_counter()
-            last["proof"] = ts.prove(conf, ca, ts.BfChallenger(), m, pis)
+            last["proof"] = proof = ts.prove(conf, ca, ts.BfChallenger(), m, pis)
             lane_log[i % S].append((t0, time.perf_counter(), t0 - tg))  # ts_prove call, return, time held at the gate
+            if i == total - 1:  # the last timed step (--dump-outputs); lanes may return out of order
+                last["final"] = proof
             if pregen:
                 mats[i] = None  # the matrix handle is spent
 
@@ -863,7 +896,9 @@ def main():
             t_call = time.perf_counter()
             proof, st, wl = ts.prove_stream(stream_lanes, [mats[i] for i in idx], [i % S for i in idx], pis,
                                             gate_ms=stagger["ms"])
-            last["proof"] = proof
+            last["proof"] = proof  # the proof of the highest index
+            if first + count == total:  # the last timed step (--dump-outputs)
+                last["final"] = proof
             for k, i in enumerate(idx):  # the library's per-proof clock, on this process's time axis
                 lane_log[i % S].append((t_call + 1e-3 * st[k], t_call + 1e-3 * (st[k] + wl[k]), 0.0))
                 mats[i] = None
@@ -1135,6 +1170,8 @@ def main():
                       "self_launched": bool(os.environ.get("TS_BENCH_SELF_LAUNCHED"))},
             "shard_stages_ms_per_rank": shard_stages,
         }
+        if args.dump_outputs:  # a caller of prove() receives the proof's words
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, {"proof_words": last["final"].words})
     if env.rank == 0 and not args.headline_only:
         out.update(rank0_legs(ts, args, env, ctx, config, cair, lanes, S, pool if S > 1 else None, local_sync,
                               make_trace, pis, cfg, n, w, qd, res, sharded, start_gate, proof,

@@ -279,6 +279,25 @@ def test_dry_run_of_the_eight_gpu_lease():
     assert rec["wall_budget"]["elapsed_total_s"] < rec["wall_budget"]["limit_s"]
 
 
+def test_dump_outputs_writes_the_last_timed_proof(tmp_path):
+    """--dump-outputs DIR: the proof of the last timed step as DIR/proof_words.npy (float64), named in the
+    record; --steps K is the number of steps in the measured window."""
+    import json
+
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = _run_bench_stub_lib(["--gpus", "1", "--steps", "6", "--warmup", "2", "--headline-only",
+                             "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    _check_contract_line(rec, 1, 6)
+    words = np.load(out / "proof_words.npy")
+    assert words.dtype == np.float64 and (words == np.arange(64)).all()  # the stand-in library's proof
+    assert rec["dump_outputs"]["arrays"] == {"proof_words": [64]} and rec["dump_outputs"]["bytes"] == 64 * 8
+    assert sorted(os.listdir(out)) == ["proof_words.npy"]
+
+
 def test_dry_run_scale_n1_equals_bench_n1():
     """The driver's SCALE series starts at N = 1 with the same command as BENCH: the same line (metric,
     config, the rank-0 legs with roofline and cpu_baseline keys) whether launched plainly or as a
