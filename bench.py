@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- trace cells/sec (and proofs/sec) of the MI355X STARK prover hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one complete prove() (commit trace -> quotient -> commit chunks -> open -> FRI ->
 queries -> proof on the host) of BASELINE.json configs[2]: the build-defined SynthMulAir-64 trace,
 2^20 rows x 64 columns, log_blowup 2, 28 queries, 8 PoW bits, with the trace already resident in
 HBM when the timed region starts.
+
+A plain run does only what the headline needs: it sets up (contexts, lanes, the start gate's spacing,
+the priming probes), runs the W warm-up steps, times ONE window of K steps, writes --dump-outputs and
+prints the line.  `--full` adds everything else the benchmark measures or checks, as it always has:
+two more timed windows (the spread), the native verifier on the last timed proof, the rank-0 legs
+below, and for N > 1 the sharded blocks.
 
 N > 1: one rank per GPU.  Launched by `python -m torch.distributed.run` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment) the process IS a rank; launched as a plain command with
@@ -15,16 +21,16 @@ call -- relays rank 0's JSON line and propagates a non-zero exit.  A WORLD_SIZE 
 --gpus, or fewer visible devices than ranks, is an error, never a silent one-GPU run.
 By default every rank proves its own independent traces (proofs are independent objects: no
 data-path collective, weak scaling, `value` is the aggregate over ranks).  After that measurement
-every N > 1 run also proves BASELINE config 4 (2^22 x 64, log_blowup 4, 16 queries) as ONE proof
-sharded over the ranks (tap-stark_amd/csrc/sharded.cpp over the library's native RCCL communicator)
-and attaches it as `sharded_config4`.  `--mode sharded` makes the sharded proof the measured step
-itself (strong scaling, the latency mode; `--workload config4`).
+every N > 1 run with --full also proves BASELINE config 4 (2^22 x 64, log_blowup 4, 16 queries) as
+ONE proof sharded over the ranks (tap-stark_amd/csrc/sharded.cpp over the library's native RCCL
+communicator) and attaches it as `sharded_config4`.  `--mode sharded` makes the sharded proof the
+measured step itself (strong scaling, the latency mode; `--workload config4`).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus:
+Prints ONE JSON line on rank 0 with the driver's contract fields; with --full also:
   roofline     -- the dominant kernel's achieved algorithmic-bytes rate from HIP events recorded
                   around every launch on the library's own stream (a separate, untimed pass);
   cpu_baseline -- the CPU oracle (a port: the Rust reference cannot run here) on a bounded
-                  sample of the same workload, on this box's host cores.
+                  sample of the same workload, on the host's cores.
 """
 from __future__ import annotations
 
@@ -45,6 +51,7 @@ PLANNED_S = {"start-up (imports, rendezvous, context, AIR compile)": 40.0,
              "replicas: warm-up + timed windows": 10.0,
              "rank-0 legs (kernel timers, latency, h2d, clocks, cpu_baseline)": 100.0,
              "sharded_config4": 60.0, "sharded_config5": 60.0}
+PLAIN_PHASES = ("start-up (imports, rendezvous, context, AIR compile)", "replicas: warm-up + timed windows")
 _PHASES = []
 
 
@@ -52,12 +59,13 @@ def phase_done(name: str):
     _PHASES.append((name, time.perf_counter()))
 
 
-def wall_budget() -> dict:
+def wall_budget(full: bool = True) -> dict:
     el, t = {}, T_PROCESS_START
     for name, t1 in _PHASES:
         el[name] = round(t1 - t, 2)
         t = t1
-    return {"limit_s": WALL_LIMIT_S, "planned_s": PLANNED_S, "planned_total_s": sum(PLANNED_S.values()),
+    planned = PLANNED_S if full else {k: v for k, v in PLANNED_S.items() if k in PLAIN_PHASES}
+    return {"limit_s": WALL_LIMIT_S, "planned_s": planned, "planned_total_s": sum(planned.values()),
             "elapsed_s": el, "elapsed_total_s": round(time.perf_counter() - T_PROCESS_START, 2),
             "note": "sharded blocks: 2 variants each (replicated, localq), under a watchdog of "
                     "TS_BENCH_SHARD_TIMEOUT_S (default 200 s for both) that prints the record it has"}
@@ -362,7 +370,8 @@ def fold_benchmark(args):
     fold the prover runs) on EF4 vectors of those sizes, device-resident (ts_fri_fold_device ->
     k_fri_fold_pairs), timed with HIP events around every launch on the library's stream.  Bytes per fold:
     2h EF4 read + h EF4 written + h twiddles = 52 h.  cpu_baseline leg: the oracle's fold_matrix on one
-    host core beside it (and the check that the device result equals it)."""
+    host core beside it (and the check that the device result equals it).  A plain run times the 2^22
+    fold alone (the headline row, on the same input); --full adds the smaller sizes and the cpu_baseline leg."""
     import ctypes as C
 
     import numpy as np
@@ -381,7 +390,9 @@ def fold_benchmark(args):
     for log_size in (12, 14, 16, 18, 20, 22):  # the reference's sweep: elements of the INPUT vector
         n = 1 << log_size
         h = n // 2
-        vec = rng.integers(0, P, (n, 4), dtype=np.uint32)
+        vec = rng.integers(0, P, (n, 4), dtype=np.uint32)  # drawn at every size: the 2^22 input stays the same
+        if not args.full and log_size != 22:
+            continue
         d_in = torch.from_numpy(vec.view(np.int32)).to("cuda:0")
         d_out = torch.zeros((h, 4), dtype=torch.int32, device="cuda:0")
         torch.cuda.synchronize()
@@ -406,7 +417,7 @@ def fold_benchmark(args):
         held.append((vec, d_out.cpu().numpy().view(np.uint32)))
     # ---- cpu_baseline leg (the only place the oracle is touched): host timing + result check
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle_py as orc
         crow = []
         for r, (vec, got) in zip(rows, held):
@@ -425,7 +436,9 @@ def fold_benchmark(args):
            "value": big["elements_per_s_gpu"], "unit": "input elements/sec", "n_gpus": 1, "steps": args.steps,
            "warmup": 1, "ms_per_step": big["kernel_us"] * 1e-3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "u32", "data": "synthetic (uniform field elements, resident in HBM)",
-           "config": {"workload": "fold_matrix, EF4 vectors of 2^12 .. 2^22 elements, one launch each"},
+           "config": {"workload": "fold_matrix, EF4 vectors of " + ("2^12 .. 2^22 elements" if args.full else
+                                                                     "2^22 elements (--full: 2^12 .. 2^22)")
+                                  + ", one launch each"},
            "roofline": {"bound": "hbm", "kernel": big["kernel"], "achieved": big["GB_per_s"], "peak": HBM_PEAK / 1e9,
                         "unit": "GB/s", "frac": big["frac_of_8TBps"], "traffic": None,
                         "alg_bytes_per_launch": big["alg_bytes"], "avg_launch_ms": big["kernel_us"] * 1e-3},
@@ -625,11 +638,16 @@ def main():
     ap.add_argument("--log-n", type=int, default=None, help="default 20 (22 for config4)")
     ap.add_argument("--mode", default="replicas", choices=["replicas", "sharded"],
                     help="N > 1: independent proofs per GPU (default) or one proof over all GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: three timed windows, the verifier on the last timed "
+                         "proof, the roofline / latency / h2d / clock / cpu legs and, for N > 1, the sharded "
+                         "config-4 / config-5 blocks (a plain run times one window of K steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the roofline / latency / h2d / cpu legs (parameter sweeps)")
+                    help="with --full: skip the roofline / latency / h2d / cpu legs (parameter sweeps); "
+                         "a plain run never runs them")
     ap.add_argument("--no-sharded-block", action="store_true",
-                    help="N > 1: do not append the sharded config-4 / config-5 measurements")
+                    help="with --full, N > 1: do not append the sharded config-4 / config-5 measurements")
     ap.add_argument("--host-traces", action="store_true",
                     help="hand every step its trace as a HOST buffer (ts_matrix_upload inside the "
                          "timed region): the PCIe-inclusive rate, reported in DESIGN.md, never `value`")
@@ -640,13 +658,15 @@ def main():
                     help="minimum spacing between the starts of two proofs on one GPU, so that the lanes run in "
                          "complementary phases instead of lockstep (-1 = auto: a quarter of the time one "
                          "proof takes alone, measured before the run; 0 = off)")
-    ap.add_argument("--windows", type=int, default=3,
+    ap.add_argument("--windows", type=int, default=None,
                     help="timed windows of K steps each, back to back; `value` is the FIRST (the contract's "
-                         "K steps), the others are reported as spread")
+                         "K steps), the others are reported as spread (default 1; 3 with --full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (the proof's words; for "
                          "--workload fold a seeded sample of the 2^22 fold's output) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
 
     # ---- launch protocol (before anything imports torch or touches the GPU)
     env_world = os.environ.get("WORLD_SIZE")
@@ -686,7 +706,7 @@ def main():
     def emit(record: dict):
         sys.stdout.flush()
         if isinstance(record, dict) and "wall_budget" not in record:
-            record["wall_budget"] = wall_budget()
+            record["wall_budget"] = wall_budget(args.full)
         if isinstance(record, dict) and "headline_windows" in record:
             # the driver's record keeps the END of this line verbatim: the per-window table goes last
             record["headline_windows"] = record.pop("headline_windows")
@@ -702,8 +722,8 @@ def main():
                "windows_ms_per_step": res.get("windows_ms_per_step"),
                "data": "stub (TS_BENCH_STUB: launch / timing protocol only, no prover, no GPU)",
                "self_launched": bool(os.environ.get("TS_BENCH_SELF_LAUNCHED")),
-               "sharded_config4": {"skipped": "stub"} if env.world > 1 else None,
-               "sharded_config5": {"skipped": "stub"} if env.world > 1 else None}
+               "sharded_config4": {"skipped": "stub"} if env.world > 1 and args.full else None,
+               "sharded_config5": {"skipped": "stub"} if env.world > 1 and args.full else None}
         env.close()
         if env.rank == 0:
             emit(rec)
@@ -1037,7 +1057,8 @@ def main():
 
     phase_done("start-up (imports, rendezvous, context, AIR compile)")
     # clock / power sampler over the timed windows: a CHILD process (amdsmi only), so that it takes
-    # nothing from this process's interpreter lock; rank 0 only; TS_BENCH_SAMPLER=0 turns it off
+    # nothing from this process's interpreter lock; rank 0 only; TS_BENCH_SAMPLER=0 turns it off.  A plain run keeps
+    # it: the headline has always been timed with it running (same-box A/B: without it window 1 reads ~1 % faster)
     sampler = None
     if env.rank == 0 and os.environ.get("TS_BENCH_SAMPLER", "1") != "0":
         from tapstark_amd.benchutil import GpuSamplerProcess
@@ -1087,8 +1108,9 @@ def main():
         per_window.append(row)
     shard_stages = None
     if sharded:
-        import torch.distributed as dist
         res["steps_per_sec"] = n_groups * args.steps / res["elapsed_s"]
+    if sharded and args.full:
+        import torch.distributed as dist
         # one more proof with the stage timers on, on every rank: where a rank's time goes
         ctx.set_timing(True)
         prove_one(total)
@@ -1106,12 +1128,13 @@ def main():
         # the last proof of the timed region, checked after it (outside every timed window): the
         # product's native verifier (csrc/verifier.cpp, uni-stark/src/verifier.rs:19-161) must accept it
         import hashlib
-        verified = None
-        try:
-            ts.verify(ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(*cfg), ctx)), air, ts.BfChallenger(), proof, pis)
-            verified = True
-        except Exception as e:  # noqa: BLE001
-            verified = f"REJECTED: {e!r}"
+        verified = None  # --full only
+        if args.full:
+            try:
+                ts.verify(ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(*cfg), ctx)), air, ts.BfChallenger(), proof, pis)
+                verified = True
+            except Exception as e:  # noqa: BLE001
+                verified = f"REJECTED: {e!r}"
         out = {
             "metric": f"trace cells/sec (proofs/sec alongside), 2^{args.log_n}x{w} BabyBear trace",
             "value": res["value"], "unit": "trace cells/sec", "n_gpus": env.world,
@@ -1130,7 +1153,7 @@ def main():
                 "python_gc": "on (TS_BENCH_KEEP_GC=1)" if keep_gc else "disabled and frozen over priming + timed windows",
                 "note": "every timed window of K steps (value = the first); clock / power from an amdsmi child "
                         "process during the window; host gap = longest pause between a ts_prove returning and "
-                        "the next call on one lane; the sustained 160-step leg is clocks.prover_sustained"},
+                        "the next call on one lane; the sustained 160-step leg is clocks.prover_sustained (--full)"},
             "higher_is_better": True,
             "scaling": ("strong" if n_groups == 1 else "strong within a group, weak across groups")
                        if sharded else "weak", "vs_baseline": None,
@@ -1172,7 +1195,7 @@ def main():
         }
         if args.dump_outputs:  # a caller of prove() receives the proof's words
             out["dump_outputs"] = dump_outputs(args.dump_outputs, {"proof_words": last["final"].words})
-    if env.rank == 0 and not args.headline_only:
+    if env.rank == 0 and args.full and not args.headline_only:
         out.update(rank0_legs(ts, args, env, ctx, config, cair, lanes, S, pool if S > 1 else None, local_sync,
                               make_trace, pis, cfg, n, w, qd, res, sharded, start_gate, proof,
                               gate_ms=stagger["ms"], stream_ok=(not sharded and S > 1 and stream_ok)))
@@ -1187,11 +1210,12 @@ def main():
                                                         "socket_power_w_median": ps_["socket_power_w_median"]}
         except Exception:  # noqa: BLE001
             pass
-    phase_done("rank-0 legs (kernel timers, latency, h2d, clocks, cpu_baseline)")
+    if args.full:
+        phase_done("rank-0 legs (kernel timers, latency, h2d, clocks, cpu_baseline)")
 
     # ---- N > 1: BASELINE configs 4 and 5 as one sharded proof each, in the same lease
     wd = None
-    force_block = bool(os.environ.get("TS_BENCH_FORCE_SHARD_BLOCK")) and env.world == 1 and not sharded
+    force_block = bool(os.environ.get("TS_BENCH_FORCE_SHARD_BLOCK")) and env.world == 1 and not sharded and args.full
     if force_block:
         # Rehearsal of the N > 1 blocks' NATIVE-RCCL branch on a one-GPU box: a process group of one
         # nccl rank, so that the unique-id exchange, ts_comm_rccl_create, every variant and the gathers of
@@ -1201,7 +1225,7 @@ def main():
         dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29513", rank=0, world_size=1,
                                 device_id=torch.device("cuda", dev))
         env.dist, env.device = dist, f"cuda:{dev}"
-    if (env.world > 1 or force_block) and not sharded and not args.no_sharded_block:
+    if (env.world > 1 or force_block) and not sharded and args.full and not args.no_sharded_block:
         for c, _, _ in lanes[1:]:
             c.synchronize()
         mats = None

@@ -89,7 +89,7 @@ def test_bench_gpus_2_as_a_plain_command_launches_two_ranks():
     # says n_gpus = 2.  TS_BENCH_STUB replaces the prover by a sleep so that this runs without a GPU.
     import json
 
-    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1"], {})
+    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full"], {})
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec["n_gpus"] == 2 and rec["stub"] is True and rec["self_launched"] is True
@@ -153,10 +153,22 @@ def test_bench_under_torch_distributed_run():
 def test_stub_line_names_both_sharded_blocks():
     import json
 
-    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1"], {})
+    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full"], {})
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec["sharded_config4"] == {"skipped": "stub"} and rec["sharded_config5"] == {"skipped": "stub"}
+
+
+def test_plain_multi_gpu_run_times_one_window_and_no_sharded_block():
+    # a plain run (no --full) times the K steps once and leaves the sharded blocks out
+    import json
+
+    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1"], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 4 and len(rec["windows_ms_per_step"]) == 1
+    assert abs(rec["value"] - 2 * 4 / (rec["ms_per_step"] * 4e-3)) < 1e-6 * rec["value"]
+    assert rec["sharded_config4"] is None and rec["sharded_config5"] is None
 
 
 def test_collectives_table_from_stage_timings():
@@ -232,7 +244,7 @@ def _run_bench_stub_lib(args, extra_env=None, timeout=600, launcher=None):
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 
 
-def _check_contract_line(rec, n_gpus, steps):
+def _check_contract_line(rec, n_gpus, steps, windows=3):
     import math
 
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -247,7 +259,7 @@ def _check_contract_line(rec, n_gpus, steps):
     assert math.isclose(rec["value"], cells / (rec["ms_per_step"] * steps * 1e-3), rel_tol=1e-9)
     assert math.isclose(rec["proofs_per_sec"], n_gpus * steps / (rec["ms_per_step"] * steps * 1e-3), rel_tol=1e-9)
     assert math.isclose(rec["windows_ms_per_step"][0], rec["ms_per_step"], rel_tol=1e-3)
-    assert len(rec["windows"]) == len(rec["windows_ms_per_step"]) == 3
+    assert len(rec["windows"]) == len(rec["windows_ms_per_step"]) == windows
     assert rec["priming"]["probes_ms_per_step"], "the priming probes are on the record"
 
 
@@ -259,7 +271,7 @@ def test_dry_run_of_the_eight_gpu_lease():
     import json
 
     port = _free_port()
-    r = _run_bench_stub_lib(["--gpus", "8", "--steps", "8", "--warmup", "4"],
+    r = _run_bench_stub_lib(["--gpus", "8", "--steps", "8", "--warmup", "4", "--full"],
                             launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
                                       "8", "--master-addr", "127.0.0.1", "--master-port", str(port)], timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -287,11 +299,10 @@ def test_dump_outputs_writes_the_last_timed_proof(tmp_path):
     import numpy as np
 
     out = tmp_path / "dump"
-    r = _run_bench_stub_lib(["--gpus", "1", "--steps", "6", "--warmup", "2", "--headline-only",
-                             "--dump-outputs", str(out)])
+    r = _run_bench_stub_lib(["--gpus", "1", "--steps", "6", "--warmup", "2", "--dump-outputs", str(out)])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    _check_contract_line(rec, 1, 6)
+    _check_contract_line(rec, 1, 6, windows=1)
     words = np.load(out / "proof_words.npy")
     assert words.dtype == np.float64 and (words == np.arange(64)).all()  # the stand-in library's proof
     assert rec["dump_outputs"]["arrays"] == {"proof_words": [64]} and rec["dump_outputs"]["bytes"] == 64 * 8
@@ -304,11 +315,11 @@ def test_dry_run_scale_n1_equals_bench_n1():
     one-rank torch.distributed.run job."""
     import json
 
-    plain = _run_bench_stub_lib(["--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline"])
+    plain = _run_bench_stub_lib(["--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--full"])
     assert plain.returncode == 0, plain.stderr[-3000:]
     a = json.loads([l for l in plain.stdout.splitlines() if l.startswith("{")][-1])
     port = _free_port()
-    tr = _run_bench_stub_lib(["--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline"],
+    tr = _run_bench_stub_lib(["--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--full"],
                              launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
                                        "1", "--master-addr", "127.0.0.1", "--master-port", str(port)])
     assert tr.returncode == 0, tr.stderr[-3000:]
@@ -319,3 +330,27 @@ def test_dry_run_scale_n1_equals_bench_n1():
         assert "cpu_baseline" in rec and "stages_ms" in rec and rec["single_proof_latency_ms"] > 0
     strip = lambda c: {k: v for k, v in c.items() if k != "parallelism"}  # (it quotes the measured start spacing)
     assert a["metric"] == b["metric"] and strip(a["config"]) == strip(b["config"]) and set(a) == set(b)
+
+
+def test_plain_run_does_only_the_headline():
+    """Without --full: one timed window of K steps and the line; no verifier, rank-0 legs or cpu_baseline.
+    With --full the same command adds them (the line keeps every contract field either way)."""
+    import json
+
+    r = _run_bench_stub_lib(["--gpus", "1", "--steps", "6", "--warmup", "2"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    _check_contract_line(rec, 1, 6, windows=1)
+    assert rec["higher_is_better"] is True and rec["warmup"] >= 2
+    for key in ("roofline", "cpu_baseline", "stages_ms", "kernels", "single_proof_latency_ms", "clocks",
+                "matches_oracle", "sharded_config4"):
+        assert key not in rec, key
+    assert rec["timed_proof_verified"] is None
+    assert list(rec["wall_budget"]["elapsed_s"]) == ["start-up (imports, rendezvous, context, AIR compile)",
+                                                     "replicas: warm-up + timed windows"]
+    full = _run_bench_stub_lib(["--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"])
+    assert full.returncode == 0, full.stderr[-3000:]
+    f = json.loads([l for l in full.stdout.splitlines() if l.startswith("{")][-1])
+    _check_contract_line(f, 1, 6)
+    assert f["timed_proof_verified"] is True and "roofline" in f and "stages_ms" in f
+    assert {k for k in rec if k != "dump_outputs"} <= set(f)

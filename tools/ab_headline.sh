@@ -9,7 +9,7 @@ settings+=("$cur")
 for rep in 1 2; do
   for s in "${settings[@]}"; do
     set -- $s; name=$1; shift
-    env "$@" python bench.py --headline-only --no-cpu-baseline ${WORKLOAD:+--workload $WORKLOAD} 2>/dev/null | python -c "
+    env "$@" python bench.py --full --headline-only --no-cpu-baseline ${WORKLOAD:+--workload $WORKLOAD} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name', '$*', d['ms_per_step'], d['extra']['windows_ms_per_step'])"
   done

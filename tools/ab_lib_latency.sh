@@ -13,7 +13,7 @@ done
 for rep in 1 2; do
   for which in prev new; do
     if [ $which = prev ]; then export TS_LIB_PATH=$PREV; else unset TS_LIB_PATH; fi
-    timeout -k 10 200 python bench.py --headline-only --no-cpu-baseline 2>/dev/null | python -c "
+    timeout -k 10 200 python bench.py --full --headline-only --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$which headline', d['ms_per_step'], d['extra']['windows_ms_per_step'])" >> $L || exit 1
   done

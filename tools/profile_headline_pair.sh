@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-r05}/final
 mkdir -p $O
 cd $R
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_config3_k20.json 2> $O/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_config3_k20.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/kt_config3
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_config3 -o kt -- python3 $R/tools/prof_prove.py 10 config3 > $O/kt_config3.log 2>&1
