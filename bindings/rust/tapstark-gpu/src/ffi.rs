@@ -40,6 +40,30 @@ pub struct ts_shard_options {
     pub local_quotient: u32,
 }
 
+/// One statement of `ts_prove_batch`: inputs, then what the library writes back.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ts_batch_item {
+    pub struct_size: u32, // = size_of::<ts_batch_item>() (the library refuses the whole call otherwise)
+    pub lane: u32,
+    pub trace: *mut ts_matrix,   // device trace made on the lane's context (consumed) ...
+    pub host_trace: *const u32,  // ... or canonical row-major host values; exactly one is set
+    pub height: u64,
+    pub width: u32,
+    pub n_public: u32,
+    pub public_values: *const u32,
+    pub challenger: *const ts_challenger, // null = fresh; else cloned, never modified
+    pub proof_out: *mut u32,
+    pub cap_words: usize,
+    pub status: ts_status, // -1 = not attempted
+    pub n_words: usize,
+    pub proof_blake3: [u32; 8],
+    pub final_state: [u32; 34],
+    pub start_ms: f64,
+    pub wall_ms: f64,
+}
+pub const TS_BATCH_DIGEST: u32 = 1;
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct ts_rccl_info {
@@ -114,6 +138,9 @@ extern "C" {
     pub fn ts_prove(ctx: *mut ts_ctx, cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
                     trace: *mut ts_matrix, public_values: *const u32, n_public: u32, proof_out: *mut u32,
                     cap_words: usize, n_words_out: *mut usize) -> ts_status;
+    pub fn ts_prove_batch(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, n_lanes: u32,
+                          cfg: *const ts_fri_config, items: *mut ts_batch_item, n_items: u32, gate_ms: f64,
+                          flags: u32) -> ts_status;
     pub fn ts_prove_sharded(ctx: *mut ts_ctx, cfg: *const ts_fri_config, comm: *const ts_comm,
                             air: *const ts_air, chal: *mut ts_challenger, trace_rows: *mut ts_matrix,
                             public_values: *const u32, n_public: u32, options: *const ts_shard_options,

@@ -136,6 +136,84 @@ where
     proofs.into_inner().unwrap().into_iter().map(|p| p.expect("every proof index was taken")).collect()
 }
 
+/// One statement of `prove_gpu_batch`: the arguments of one reference `prove` call
+/// (uni-stark/src/prover.rs:25-39) and the lane that proves it.
+pub struct BatchStatement<'a> {
+    pub lane: usize,
+    pub trace: &'a RowMajorMatrix<Val>,
+    pub public_values: &'a [Val],
+    /// `None` = a fresh challenger; otherwise the library proves from a clone and leaves this one as it is
+    pub challenger: Option<&'a GpuChallenger>,
+}
+
+/// Why one statement of a batch has no proof: the item's `ts_status` (-1: not attempted, an earlier
+/// statement of its lane hit a device error), and the words it needed on `TS_ERR_BUFFER`.
+#[derive(Debug, Clone, Copy)]
+pub struct BatchError {
+    pub status: ts_status,
+    pub n_words: usize,
+}
+
+/// Many statements in ONE library call (`ts_prove_batch`): lane `l` is `lanes[l]` (its context and AIR; the AIRs
+/// may differ), one host thread per lane inside the library, each trace uploaded on its lane's stream just
+/// before its proof.  Every statement gets its own `Result`: a bad statement fails alone, a device error stops
+/// only its lane.  What `prove_gpu_stream` does with Rust threads, for hosts that prefer one call.
+pub fn prove_gpu_batch(fri: FriConfig, lanes: &[&CompiledAir<'_>], statements: &[BatchStatement<'_>],
+                       gate_ms: f64) -> Vec<Result<Proof, BatchError>> {
+    let ctxs: Vec<*mut ts_ctx> = lanes.iter().map(|a| a.ctx.raw).collect();
+    let airs: Vec<*const ts_air> = lanes.iter().map(|a| a.raw as *const ts_air).collect();
+    // the host buffers must stay untouched until the call returns: they live to the end of this function
+    let words: Vec<Vec<u32>> =
+        statements.iter().map(|s| s.trace.values.iter().map(|v| v.as_canonical_u32()).collect()).collect();
+    let pis: Vec<Vec<u32>> =
+        statements.iter().map(|s| s.public_values.iter().map(|v| v.as_canonical_u32()).collect()).collect();
+    let mut outs: Vec<Vec<u32>> = statements
+        .iter()
+        .map(|s| {
+            let lqd = lanes.get(s.lane).map_or(0, |a| a.log_quotient_degree);
+            vec![0u32; proof_capacity(&fri, s.trace.height(), s.trace.width(), 1 << lqd)]
+        })
+        .collect();
+    let mut items: Vec<ts_batch_item> = statements
+        .iter()
+        .enumerate()
+        .map(|(i, s)| ts_batch_item {
+            struct_size: core::mem::size_of::<ts_batch_item>() as u32,
+            lane: s.lane as u32,
+            trace: ptr::null_mut(),
+            host_trace: words[i].as_ptr(),
+            height: s.trace.height() as u64,
+            width: s.trace.width() as u32,
+            n_public: pis[i].len() as u32,
+            public_values: if pis[i].is_empty() { ptr::null() } else { pis[i].as_ptr() },
+            challenger: s.challenger.map_or(ptr::null(), |c| c.raw as *const ts_challenger),
+            proof_out: outs[i].as_mut_ptr(),
+            cap_words: outs[i].len(),
+            status: -1,
+            n_words: 0,
+            proof_blake3: [0; 8],
+            final_state: [0; 34],
+            start_ms: 0.0,
+            wall_ms: 0.0,
+        })
+        .collect();
+    let cfg = fri.raw();
+    let rc = unsafe {
+        ts_prove_batch(ctxs.as_ptr(), airs.as_ptr(), ctxs.len() as u32, &cfg, items.as_mut_ptr(),
+                       items.len() as u32, gate_ms, 0)
+    };
+    // a refused call (no lanes, an invalid FriConfig) writes no item: its status goes to every statement
+    let refused = rc != TS_OK && items.iter().all(|it| it.status == -1);
+    items
+        .iter()
+        .enumerate()
+        .map(|(i, it)| match it.status {
+            TS_OK => Ok(Proof::from_tspf(&outs[i][..it.n_words])),
+            status => Err(BatchError { status: if refused { rc } else { status }, n_words: it.n_words }),
+        })
+        .collect()
+}
+
 /// Form 2: the body of uni-stark/src/prover.rs:40-118 over the `Pcs` trait.
 pub fn prove_gpu_stepwise<A>(pcs: &GpuFriPcs<'_>, air: &A, challenger: &mut GpuChallenger,
                              trace: RowMajorMatrix<Val>, public_values: &Vec<Val>) -> Proof

@@ -346,6 +346,60 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
                           uint32_t* last_proof_out, size_t cap_words, size_t* n_words_out,
                           double* start_ms_out, double* wall_ms_out);
 
+/* Many statements in one call, every proof returned: n_items independent uni_stark::prove calls
+ * (uni-stark/src/prover.rs:25-39: each with its own trace, public values and challenger, each returning its
+ * proof) on n_lanes contexts of ONE device, one host thread per lane inside the call, as ts_prove_stream.
+ * Item i runs on lane items[i].lane with airs[lane] (lanes may carry different AIRs); a lane takes its
+ * items in index order.  Item i's proof words and final challenger state are those ts_prove gives for the
+ * same context, AIR, trace, public values and a clone of the same challenger.
+ *   trace / host_trace  exactly one is set.  `trace` must have been made on the lane's context and is
+ *                       consumed (each handle in at most one item).  `host_trace` (height x width canonical
+ *                       row-major values; height a power of two) is uploaded on the lane's own stream just
+ *                       before its proof, so that one lane's upload overlaps the others' proofs; pinned
+ *                       memory (ts_host_alloc) gets the full link rate.  THE HOST BUFFER MUST STAY UNTOUCHED
+ *                       UNTIL THE CALL RETURNS.
+ *   public_values       n_public values; n_public and the trace width must match airs[lane] (ts_air_info).
+ *   challenger          NULL = a fresh BfChallenger(Blake3, sample_ext) as ts_prove_stream uses; otherwise
+ *                       a CLONE of it is used and the caller's object is never modified (one object may
+ *                       serve several items; it must not change during the call).
+ *   proof_out           cap_words words; a finished proof is copied there at once (the library keeps at
+ *                       most one proof per lane).
+ * Outputs: status (-1 = not attempted), n_words (also on TS_ERR_BUFFER: the size needed), final_state (the
+ * ts_chal_state layout of the challenger after the proof), start_ms / wall_ms (relative to the call's
+ * start; the start is stamped inside the gate's critical section, so sorted starts are >= gate_ms apart),
+ * proof_blake3 (Blake3 of the proof words as little-endian bytes, computed on the lane thread, only with
+ * TS_BATCH_DIGEST in flags).
+ * Failures: a bad item (width or n_public not the AIR's, a consumed or repeated trace, both or neither
+ * trace source, lane >= n_lanes, a null buffer, a proof buffer too small) fails in its own status and the
+ * other items still run; TS_ERR_HIP / TS_ERR_OOM / TS_ERR_INVARIANT stop that item's lane (its later items
+ * stay at -1).  Returns TS_OK if every item is TS_OK, else the status of the lowest-index failed item;
+ * ts_last_error of the item's lane context holds the text.  Null arrays, n_lanes of 0 or > 64, an invalid
+ * cfg or any struct_size != sizeof(ts_batch_item) return TS_ERR_INVALID before any trace is consumed or any
+ * item written. */
+typedef struct {
+    uint32_t struct_size;            /* = sizeof(ts_batch_item): another layout refuses the whole call */
+    uint32_t lane;                   /* < n_lanes */
+    ts_matrix* trace;                /* device trace made on the lane's context (consumed) ... */
+    const uint32_t* host_trace;      /* ... OR canonical row-major host values, height x width */
+    uint64_t height;                 /* of host_trace */
+    uint32_t width;                  /* of host_trace */
+    uint32_t n_public;
+    const uint32_t* public_values;
+    const ts_challenger* challenger; /* NULL = fresh; else cloned, never modified */
+    uint32_t* proof_out;
+    size_t cap_words;
+    /* outputs */
+    ts_status status;
+    size_t n_words;
+    uint32_t proof_blake3[8];
+    uint32_t final_state[34];
+    double start_ms, wall_ms;
+} ts_batch_item;
+#define TS_BATCH_DIGEST 1u
+ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_t n_lanes,
+                         const ts_fri_config* cfg, ts_batch_item* items, uint32_t n_items, double gate_ms,
+                         uint32_t flags);
+
 /* prove() with the work of ONE proof split over comm->world ranks, one GPU each: rank g owns the
  * bit-reversed LDE rows [g N/G, (g+1) N/G) -- whole cosets, so world must be a power of two
  * <= 2^log_blowup (TS_ERR_UNSUPPORTED otherwise) -- with their Merkle sub-trees, FRI slabs and

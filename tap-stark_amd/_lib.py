@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "ts_pcs_data_info", "ts_pcs_data_matrix_info", "ts_pcs_data_digests", "ts_pcs_open_batch", "ts_pcs_data_free",
     "ts_quotient_chunks", "ts_pcs_open_reduce", "ts_pcs_open", "ts_pcs_verify", "ts_fri_prove", "ts_fri_verify", "ts_fri_fold", "ts_fri_fold_device", "ts_chal_new", "ts_chal_clone",
     "ts_chal_free", "ts_chal_observe", "ts_chal_observe_commitment", "ts_chal_sample",
-    "ts_chal_sample_bits", "ts_chal_check_witness", "ts_chal_grind", "ts_chal_state", "ts_prove", "ts_prove_stream", "ts_prove_sharded", "ts_verify", "ts_check_constraints",
+    "ts_chal_sample_bits", "ts_chal_check_witness", "ts_chal_grind", "ts_chal_state", "ts_prove", "ts_prove_stream", "ts_prove_batch", "ts_prove_sharded", "ts_verify", "ts_check_constraints",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -77,6 +77,18 @@ class ShardOptionsC(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_local_log", C.c_uint32), ("trace_replicated", C.c_uint32),
                 ("local_quotient", C.c_uint32)]
 
+
+class BatchItemC(C.Structure):
+    """``ts_batch_item`` (include/tapstark.h): one statement of ``ts_prove_batch``, inputs then outputs."""
+    _fields_ = [("struct_size", C.c_uint32), ("lane", C.c_uint32), ("trace", C.c_void_p),
+                ("host_trace", C.c_void_p), ("height", C.c_uint64), ("width", C.c_uint32),
+                ("n_public", C.c_uint32), ("public_values", C.c_void_p), ("challenger", C.c_void_p),
+                ("proof_out", C.c_void_p), ("cap_words", C.c_size_t),
+                ("status", C.c_int), ("n_words", C.c_size_t), ("proof_blake3", C.c_uint32 * 8),
+                ("final_state", C.c_uint32 * 34), ("start_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+BATCH_DIGEST = 1  # TS_BATCH_DIGEST
 
 _lib = None
 
@@ -173,6 +185,8 @@ def lib() -> C.CDLL:
                                       C.POINTER(C.c_void_p), u32p, C.c_uint32, u32p, C.c_uint32, C.c_double,
                                       u32p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]
+        l.ts_prove_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(FriConfigC),
+                                     C.POINTER(BatchItemC), C.c_uint32, C.c_double, C.c_uint32]
         l.ts_prove_sharded.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.POINTER(CommC), C.c_void_p,
                                        C.c_void_p, C.c_void_p, u32p, C.c_uint32,
                                        C.POINTER(ShardOptionsC), u32p, C.c_size_t,

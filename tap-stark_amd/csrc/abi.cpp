@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "abi_types.hpp"
+#include "blake3.hpp"
 #include "jit.hpp"
 
 // hiprtc's time grows faster than the program (a 4.6k-instruction program compiles in 14 s, an
@@ -1093,6 +1094,126 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
         if (last_proof[best].size() > cap_words) return TS_ERR_BUFFER;
         memcpy(last_proof_out, last_proof[best].data(), last_proof[best].size() * 4);
     }
+    return TS_OK;
+}
+
+// ------------------------------------------------------------------ prove_batch
+// ts_prove_stream's lane loop for n DISTINCT statements (uni-stark/src/prover.rs:25-39: each call has its own
+// trace, public values and challenger, and returns its proof): per-item inputs and outputs, host traces
+// uploaded on the lane's stream just before their proof, failures confined to the item (or, for a device
+// fault, to its lane).  ts_prove_stream itself is left as it was: bench.py drives it.
+ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_t n_lanes,
+                         const ts_fri_config* cfg, ts_batch_item* items, uint32_t n_items, double gate_ms,
+                         uint32_t flags) {
+    // whole-call refusals first: nothing is consumed or written before these pass
+    if (!ctxs || !airs || (!items && n_items) || n_lanes == 0 || n_lanes > 64) return TS_ERR_INVALID;
+    for (uint32_t l = 0; l < n_lanes; l++)
+        if (!ctxs[l] || !airs[l]) return TS_ERR_INVALID;
+    for (uint32_t i = 0; i < n_items; i++)
+        if (items[i].struct_size != sizeof(ts_batch_item)) return TS_ERR_INVALID;
+    ts::FriConfig fcfg;
+    try {
+        fcfg = load_cfg(cfg);
+    } catch (const ts::Error&) {
+        return TS_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < n_items; i++) {
+        ts_batch_item& it = items[i];
+        it.status = -1;
+        it.n_words = 0;
+        it.start_ms = it.wall_ms = 0;
+        memset(it.proof_blake3, 0, sizeof it.proof_blake3);
+        memset(it.final_state, 0, sizeof it.final_state);
+    }
+    // items no lane can take, or whose trace handle an earlier item already names (two lane threads would
+    // race for it), fail here
+    std::vector<std::pair<const ts_matrix*, uint32_t>> handles;
+    for (uint32_t i = 0; i < n_items; i++) {
+        if (items[i].lane >= n_lanes) items[i].status = TS_ERR_INVALID;
+        else if (items[i].trace) handles.emplace_back(items[i].trace, i);
+    }
+    std::sort(handles.begin(), handles.end());
+    for (size_t k = 1; k < handles.size(); k++)
+        if (handles[k].first == handles[k - 1].first) items[handles[k].second].status = TS_ERR_INVALID;
+
+    std::mutex gate_m;
+    double gate_last = -1e300;
+    const double gap = gate_ms > 0 ? gate_ms : 0;
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+    auto lane_main = [&](uint32_t l) {
+        ts_ctx* ctx = ctxs[l];
+        const ts_air* air = airs[l];
+        std::unique_ptr<ts::TwoAdicFriPcs> pcs;
+        for (uint32_t i = 0; i < n_items; i++) {
+            ts_batch_item& it = items[i];
+            if (it.lane != l || it.status != -1) continue;
+            it.status = guard(ctx, [&] {
+                const ts::AirProgram& prog = ready_prog(air);
+                TS_REQUIRE((it.trace != nullptr) != (it.host_trace != nullptr), ts::TS_ERR_INVALID,
+                           "prove_batch: exactly one of trace / host_trace must be set");
+                TS_REQUIRE(it.proof_out, ts::TS_ERR_INVALID, "prove_batch: null proof_out");
+                TS_REQUIRE(it.n_public == prog.n_public, ts::TS_ERR_INVALID,
+                           "prove_batch: n_public differs from the lane's AIR");
+                TS_REQUIRE(!it.n_public || it.public_values, ts::TS_ERR_INVALID, "prove_batch: null public values");
+                if (it.trace) {
+                    TS_REQUIRE(it.trace->m.buf.p, ts::TS_ERR_INVALID, "prove_batch: trace matrix was already consumed");
+                    TS_REQUIRE(it.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
+                               "prove_batch: trace was not made on the lane's context");
+                    TS_REQUIRE(it.trace->m.width == prog.width, ts::TS_ERR_INVALID,
+                               "prove_batch: trace width differs from the lane's AIR");
+                } else {
+                    TS_REQUIRE(it.height >= 1 && (it.height & (it.height - 1)) == 0 && it.height <= (1ull << 27),
+                               ts::TS_ERR_INVALID, "prove_batch: host trace height must be a power of two <= 2^27");
+                    TS_REQUIRE(it.width == prog.width, ts::TS_ERR_INVALID,
+                               "prove_batch: host trace width differs from the lane's AIR");
+                }
+                const std::vector<uint32_t> pis(it.public_values, it.public_values + it.n_public);
+                ts::BfChallenger chal = it.challenger ? it.challenger->c : ts::BfChallenger(0, true);
+                if (!pcs) pcs = std::make_unique<ts::TwoAdicFriPcs>(ctx->ctx, fcfg);
+                double t0;
+                if (gap > 0) {  // no two proofs start within gate_ms of each other; the stamp is taken INSIDE
+                    std::lock_guard<std::mutex> g(gate_m);
+                    for (;;) {
+                        const double wait = gate_last + gap - now_ms();
+                        if (wait <= 0) break;
+                        std::this_thread::sleep_for(std::chrono::microseconds((long)std::min(wait * 1e3, 200.0)));
+                    }
+                    t0 = gate_last = now_ms();
+                } else {
+                    t0 = now_ms();
+                }
+                ts::DeviceMatrix trace;
+                if (it.trace) {
+                    trace = std::move(it.trace->m);
+                } else {  // H2D on the lane's stream: ordered before the proof's kernels, no host wait here
+                    trace.buf = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)it.height * it.width);
+                    trace.height = it.height;
+                    trace.width = it.width;
+                    trace.layout = ts::DeviceMatrix::ROW_MAJOR;
+                    TS_HIP(hipMemcpyAsync(trace.buf.p, it.host_trace, (size_t)it.height * it.width * 4,
+                                          hipMemcpyHostToDevice, ctx->ctx.stream));
+                }
+                std::vector<uint32_t> proof = ts::prove(*pcs, prog, chal, std::move(trace), pis);
+                it.start_ms = t0;
+                it.wall_ms = now_ms() - t0;
+                chal.export_state(it.final_state);
+                it.n_words = proof.size();
+                TS_REQUIRE(proof.size() <= it.cap_words, ts::TS_ERR_BUFFER, "prove_batch: proof buffer too small");
+                memcpy(it.proof_out, proof.data(), proof.size() * 4);
+                if (flags & TS_BATCH_DIGEST)
+                    ts::b3::hash_stream([&](uint64_t k) { return proof[k]; }, proof.size(), it.proof_blake3);
+            });
+            // a device fault leaves the lane's context in doubt: its later items stay unattempted
+            if (it.status == TS_ERR_HIP || it.status == TS_ERR_OOM || it.status == TS_ERR_INVARIANT) break;
+        }
+    };
+    std::vector<std::thread> threads;
+    for (uint32_t l = 1; l < n_lanes; l++) threads.emplace_back(lane_main, l);
+    lane_main(0);
+    for (auto& t : threads) t.join();
+    for (uint32_t i = 0; i < n_items; i++)
+        if (items[i].status != TS_OK) return items[i].status;
     return TS_OK;
 }
 

@@ -788,6 +788,129 @@ def prove_stream(lanes, traces, lane_of, public_values, gate_ms: float = 0.0, wa
     return Proof(out[: n_words.value].copy()), st[:n], wl[:n]
 
 
+def _proof_capacity(n: int, w: int, log_quotient_degree: int, fri: FriConfig) -> int:
+    """Upper bound on the TSPF v1 words of one proof of an n x w trace (as ``prove`` sizes its buffer)."""
+    log_N = max(n, 1).bit_length() - 1 + fri.log_blowup
+    qd = 1 << log_quotient_degree
+    R = log_N - fri.log_blowup
+    Q = fri.num_queries
+    return 64 + 8 * w + 16 * qd + 8 * R + Q * (16 + w + 5 * qd + 2 * 8 * log_N + R * (9 + 8 * log_N))
+
+
+@dataclass
+class BatchResult:
+    """What ``prove_batch`` returns, one entry per item: ``proofs[i]`` is None unless ``status[i]`` is 0
+    (-1 = not attempted: an earlier item of its lane hit a device error); ``n_words[i]`` is also set on
+    TS_ERR_BUFFER; ``digests`` (n x 8 words: Blake3 of the proof words) only with ``digests=True``;
+    ``final_states`` (n x 34) is ``BfChallenger.state()`` of the challenger after the proof; ``rc`` is the
+    call's status (that of the lowest-index failed item); ``errors[i]`` the text of item i's lane context."""
+    rc: int
+    proofs: list
+    status: np.ndarray
+    n_words: np.ndarray
+    digests: np.ndarray | None
+    final_states: np.ndarray
+    start_ms: np.ndarray
+    wall_ms: np.ndarray
+    errors: list = field(default_factory=list)
+
+
+def _is_vector(v) -> bool:
+    return v.ndim == 1 if isinstance(v, np.ndarray) else all(np.isscalar(x) for x in v)
+
+
+def _per_item(value, n: int, is_single, what: str) -> list:
+    if value is None or is_single(value):
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError(f"prove_batch: {len(value)} {what} for {n} traces")
+    return value
+
+
+def prove_batch(lanes, traces, lane_of, public_values=None, challengers=None, gate_ms: float = 0.0,
+                digests: bool = False, check: bool = True, _struct_size: int | None = None,
+                _cap_words=None) -> BatchResult:
+    """``ts_prove_batch``: ``len(traces)`` distinct statements (reference uni-stark/src/prover.rs:25-39, one
+    call each) on the contexts of ``lanes`` = [(StarkConfig, CompiledAir), ...] (one context each, same device,
+    same FriConfig; the AIRs may differ), one host thread per lane inside the library, every proof returned.
+
+    ``traces[i]``: a ``DeviceMatrix`` made on lane ``lane_of[i]``'s context (consumed), a ``PinnedHostMatrix``
+    or an (h, w) uint32 array (uploaded on the lane's stream just before its proof).  ``public_values``: one
+    vector for every item or one per item; ``challengers``: None (a fresh ``BfChallenger()``), one
+    ``BfChallenger`` for every item or one (or None) per item -- a clone is used, the objects are not modified.
+    With ``check`` a failed item raises ``TsError`` once every item has run; otherwise see ``status``.
+    (``_struct_size`` / ``_cap_words``: test hooks -- another struct layout, per-item proof buffer sizes.)"""
+    n, n_l = len(traces), len(lanes)
+    lane_of = [int(x) for x in lane_of]
+    if len(lane_of) != n:
+        raise ValueError(f"prove_batch: {len(lane_of)} lane indices for {n} traces")
+    pis = [np.zeros(0, dtype=np.uint32) if p is None else _u32(p).reshape(-1)
+           for p in _per_item(public_values, n, _is_vector, "public-value vectors")]
+    chals = _per_item(challengers, n, lambda v: isinstance(v, BfChallenger), "challengers")
+    caps = _per_item(_cap_words, n, lambda v: isinstance(v, int), "buffer sizes")
+    if not lanes:
+        raise ValueError("prove_batch: no lanes")
+    l = _lib.lib()
+    fri = lanes[0][0].pcs.fri
+    cfg = fri._c()
+    ctxs = (C.c_void_p * n_l)(*[conf.pcs.ctx.h for conf, _ in lanes])
+    airs = (C.c_void_p * n_l)(*[a.h for _, a in lanes])
+    items = (_lib.BatchItemC * max(n, 1))()
+    keep, outs = [], []  # host buffers that must outlive the call
+    for i, t in enumerate(traces):
+        it = items[i]
+        it.struct_size = C.sizeof(_lib.BatchItemC) if _struct_size is None else _struct_size
+        it.lane = lane_of[i]
+        it.status = -1
+        if isinstance(t, DeviceMatrix):
+            it.trace = t.h
+            h, w = t.dims()
+        elif isinstance(t, PinnedHostMatrix):
+            it.host_trace = t.ptr
+            h, w = t.shape
+        else:
+            a = _u32(t)
+            if a.ndim != 2:
+                raise ValueError(f"prove_batch: trace {i} is not a 2-D array")
+            keep.append(a)
+            it.host_trace = a.ctypes.data
+            h, w = a.shape
+        it.height, it.width = h, w
+        it.n_public = len(pis[i])
+        it.public_values = pis[i].ctypes.data if len(pis[i]) else None
+        it.challenger = chals[i].h if chals[i] is not None else None
+        lqd = lanes[lane_of[i]][1].log_quotient_degree if 0 <= lane_of[i] < n_l else 0
+        cap = _proof_capacity(h, w, lqd, fri) if caps[i] is None else caps[i]
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        outs.append(out)
+        it.proof_out = out.ctypes.data
+        it.cap_words = cap
+    rc = l.ts_prove_batch(ctxs, airs, n_l, C.byref(cfg), items, n, float(gate_ms),
+                          _lib.BATCH_DIGEST if digests else 0)
+    status = np.array([items[i].status for i in range(n)], dtype=np.int32)
+    if rc and (status == -1).all():  # the whole call was refused: no item was touched
+        msg = "ts_prove_batch refused the call (null arrays, lane count, FriConfig or struct_size)"
+        raise _lib.TsError(rc, msg)
+    n_words = np.array([items[i].n_words for i in range(n)], dtype=np.int64)
+    errors = [None if s == 0 else (l.ts_last_error(lanes[lane_of[i]][0].pcs.ctx.h) or b"").decode()
+              if 0 <= lane_of[i] < n_l else f"lane {lane_of[i]} out of range" for i, s in enumerate(status)]
+    res = BatchResult(
+        rc=int(rc),
+        proofs=[Proof(outs[i][: n_words[i]].copy()) if status[i] == 0 else None for i in range(n)],
+        status=status, n_words=n_words,
+        digests=np.array([list(items[i].proof_blake3) for i in range(n)], dtype=np.uint32).reshape(n, 8)
+        if digests else None,
+        final_states=np.array([list(items[i].final_state) for i in range(n)], dtype=np.uint32).reshape(n, 34),
+        start_ms=np.array([items[i].start_ms for i in range(n)]),
+        wall_ms=np.array([items[i].wall_ms for i in range(n)]),
+        errors=errors)
+    if check and rc:
+        bad = next(i for i in range(n) if status[i] != 0)
+        raise _lib.TsError(int(status[bad]), f"item {bad}: {errors[bad] or 'not attempted'}")
+    return res
+
+
 def prove_sharded(config: StarkConfig, air, challenger: BfChallenger, trace_rows, public_values,
                   comm, min_local_log: int = 0, trace_replicated: bool = False,
                   local_quotient: bool = False, _options_struct_size: int | None = None) -> Proof:
