@@ -338,6 +338,11 @@ ts_status ts_comm_local_group_set_timeout(ts_comm_group* group, int seconds);
  * gate_ms of each other (0 = no gate; a quarter of one proof's solo time keeps the lanes in complementary
  * phases).  last_proof_out receives the proof of the highest index; start_ms_out / wall_ms_out (n_proofs each,
  * may be NULL): when each ts_prove-equivalent started, relative to the call's start, and how long it took.
+ * The start is stamped inside the gate's critical section, so sorted starts are >= gate_ms apart.
+ * Null arrays, n_lanes of 0 or > 64, one context on two lanes, lane_of[i] >= n_lanes or an invalid cfg
+ * return TS_ERR_INVALID before any lane starts.  A trace made on another context, or of another width than
+ * the lane's AIR, fails its lane with TS_ERR_INVALID and is not consumed.  A failing lane stops the others;
+ * the call returns the status of the lowest-index failed lane.
  * What a host with cheap threads does itself (examples/prove_stream.cpp); a host behind an interpreter
  * lock gets the loop without paying its lock per proof. */
 ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_t n_lanes,

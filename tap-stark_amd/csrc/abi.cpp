@@ -248,6 +248,115 @@ ts::FriConfig load_cfg(const ts_fri_config* cfg) {
     return f;
 }
 
+// ------------------------------------------------------------------ arguments of the prove / verify calls
+std::vector<uint32_t> public_inputs(const uint32_t* values, uint32_t n) {
+    std::vector<uint32_t> pis;
+    if (n) {
+        TS_REQUIRE(values, ts::TS_ERR_INVALID, "null public values");
+        pis.assign(values, values + n);
+    }
+    return pis;
+}
+
+// the trace is consumed, like the reference's moved RowMajorMatrix
+ts::DeviceMatrix take_trace(ts_matrix* trace) {
+    TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+    return std::move(trace->m);
+}
+
+// *n_words_out is set before the size check: a caller told TS_ERR_BUFFER learns the size it needs
+void copy_proof(const std::vector<uint32_t>& words, uint32_t* out, size_t cap, size_t* n_words_out) {
+    *n_words_out = words.size();
+    TS_REQUIRE(words.size() <= cap, ts::TS_ERR_BUFFER, "proof buffer too small");
+    memcpy(out, words.data(), words.size() * 4);
+}
+
+ts::TapLocks tap_locks(const uint8_t* bytes, const uint64_t* offsets, size_t n_scripts) {
+    ts::TapLocks locks;
+    locks.bytes = bytes;
+    locks.offsets = offsets;
+    locks.n_scripts = n_scripts;
+    return locks;
+}
+
+// a rank leaving the protocol on an error makes the peers' pending collectives fail instead of hang
+template <class F>
+auto abort_on_throw(const ts_comm& cb, F&& fn) -> decltype(fn()) {
+    try {
+        return fn();
+    } catch (...) {
+        if (cb.abort) cb.abort(cb.user);
+        throw;
+    }
+}
+
+// ------------------------------------------------------------------ lanes of ts_prove_stream / ts_prove_batch
+// The refusals every lane call shares, made before any lane starts: pointer comparisons only, so no context
+// is dereferenced.  A context on two lanes would have two threads driving one Context (pool, stream,
+// last_error).
+bool check_lanes(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_t n_lanes, const ts_fri_config* cfg,
+                 ts::FriConfig& fri) {
+    if (!ctxs || !airs || n_lanes == 0 || n_lanes > 64) return false;
+    for (uint32_t l = 0; l < n_lanes; l++) {
+        if (!ctxs[l] || !airs[l]) return false;
+        for (uint32_t k = 0; k < l; k++)
+            if (ctxs[k] == ctxs[l]) return false;
+    }
+    try {
+        fri = load_cfg(cfg);
+    } catch (const ts::Error&) {
+        return false;
+    }
+    return true;
+}
+
+// The call's clock and its start gate: no two proofs start within gap ms of each other.  enter() stamps the
+// start inside the critical section, so sorted stamps are at least gap apart.
+struct StartGate {
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    const double gap;
+    std::mutex m;
+    double last = -1e300;
+
+    explicit StartGate(double gate_ms) : gap(gate_ms > 0 ? gate_ms : 0) {}
+    double now_ms() const {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    double enter() {
+        if (gap <= 0) return now_ms();
+        std::lock_guard<std::mutex> g(m);
+        for (double wait; (wait = last + gap - now_ms()) > 0;)
+            std::this_thread::sleep_for(std::chrono::microseconds((long)std::min(wait * 1e3, 200.0)));
+        return last = now_ms();
+    }
+};
+
+// fn(l) for every lane: lanes 1 .. n_lanes-1 on threads of their own, lane 0 on the caller's.  If a thread
+// cannot be created, no further lane starts (lane 0 neither), the running ones finish and are joined, and
+// the call gets TS_ERR_OOM instead of an exception through the C ABI.
+template <class F>
+ts_status run_lanes(uint32_t n_lanes, const F& fn) {
+    std::vector<std::thread> threads;
+    ts_status st = TS_OK;
+    try {
+        threads.reserve(n_lanes - 1);
+        for (uint32_t l = 1; l < n_lanes; l++) threads.emplace_back(fn, l);
+    } catch (...) {  // std::system_error, std::bad_alloc
+        st = TS_ERR_OOM;
+    }
+    if (st == TS_OK) fn(0);
+    for (std::thread& t : threads) t.join();
+    return st;
+}
+
+// a lane's device trace: made on the lane's context, of the AIR's width and unconsumed, all checked before it
+// is moved out
+ts::DeviceMatrix lane_trace(ts_matrix* trace, ts_ctx* ctx, const ts::AirProgram& prog) {
+    TS_REQUIRE(trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "trace was not made on the lane's context");
+    TS_REQUIRE(trace->m.width == prog.width, ts::TS_ERR_INVALID, "trace width differs from the lane's AIR");
+    return take_trace(trace);
+}
+
 }  // namespace
 
 extern "C" {
@@ -315,9 +424,7 @@ ts_status ts_proof_from_postcard_v(const uint8_t* bytes, size_t n_bytes, int tsp
         std::vector<uint32_t> w;
         TS_REQUIRE(ts::postcard_to_tspf(bytes, n_bytes, w, tspf_version), ts::TS_ERR_INVALID,
                    "malformed postcard proof (or not of the TSPF version asked for)");
-        *n_words_out = w.size();
-        TS_REQUIRE(w.size() <= cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
-        memcpy(proof_out, w.data(), w.size() * 4);
+        copy_proof(w, proof_out, cap_words, n_words_out);
     });
 }
 
@@ -825,11 +932,7 @@ ts_status ts_quotient_chunks(ts_ctx* ctx, const ts_pcs_data* trace_data, uint32_
     return guard(ctx, [&] {
         ts_fri_config raw{log_blowup, 1, 0};
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));  // same [1, 8] bound as everywhere else
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         auto chunks = pcs.quotient_chunks(*trace_data->d, ready_prog(air), pis, load_ef(alpha));
         for (size_t c = 0; c < chunks.size(); c++) {
             auto m = std::make_unique<ts_matrix>();
@@ -889,11 +992,9 @@ ts_status ts_pcs_open(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal
         std::vector<ts::Ef> opened;
         std::vector<uint32_t> proof = pcs.open(rs, chal->c, opened);
         *n_opened_words = opened.size() * 4;
-        *n_proof_words = proof.size();
+        copy_proof(proof, proof_out, proof_cap_words, n_proof_words);
         TS_REQUIRE(opened.size() * 4 <= opened_cap_words, ts::TS_ERR_BUFFER, "opened-values buffer too small");
-        TS_REQUIRE(proof.size() <= proof_cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
         memcpy(opened_out, opened.data(), opened.size() * sizeof(ts::Ef));
-        memcpy(proof_out, proof.data(), proof.size() * 4);
     });
 }
 
@@ -920,9 +1021,7 @@ ts_status ts_fri_prove(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* cha
         ctx->ctx.sync();
         std::vector<uint32_t> pf;
         pcs.fri_prove(in, logs, chal->c, {}, pf, /*pass_through=*/true);
-        *n_words_out = pf.size();
-        TS_REQUIRE(pf.size() <= cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
-        memcpy(proof_out, pf.data(), pf.size() * 4);
+        copy_proof(pf, proof_out, cap_words, n_words_out);
     });
 }
 ts_status ts_fri_verify(const ts_fri_config* cfg, ts_challenger* chal, const uint32_t* proof,
@@ -1006,17 +1105,10 @@ ts_status ts_prove(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_
     *n_words_out = 0;
     return guard(ctx, [&] {
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
-        TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "prove: trace matrix was already consumed");
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        ts::DeviceMatrix m = take_trace(trace);
         ts::StageTimer t(&ctx->ctx, "prove");
-        std::vector<uint32_t> proof = ts::prove(pcs, ready_prog(air), chal->c, std::move(trace->m), pis);
-        *n_words_out = proof.size();
-        TS_REQUIRE(proof.size() <= cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
-        memcpy(proof_out, proof.data(), proof.size() * 4);
+        copy_proof(ts::prove(pcs, ready_prog(air), chal->c, std::move(m), pis), proof_out, cap_words, n_words_out);
     });
 }
 
@@ -1032,21 +1124,15 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
                           uint32_t n_proofs, const uint32_t* public_values, uint32_t n_public, double gate_ms,
                           uint32_t* last_proof_out, size_t cap_words, size_t* n_words_out,
                           double* start_ms_out, double* wall_ms_out) {
-    if (!ctxs || !airs || !traces || !lane_of || !n_words_out || n_lanes == 0 || n_lanes > 64) return TS_ERR_INVALID;
+    if (!traces || !lane_of || !n_words_out) return TS_ERR_INVALID;
     *n_words_out = 0;
-    for (uint32_t l = 0; l < n_lanes; l++)
-        if (!ctxs[l] || !airs[l]) return TS_ERR_INVALID;
+    ts::FriConfig fri;
+    if (!check_lanes(ctxs, airs, n_lanes, cfg, fri)) return TS_ERR_INVALID;
     for (uint32_t i = 0; i < n_proofs; i++)
         if (!traces[i] || lane_of[i] >= n_lanes) return TS_ERR_INVALID;
     if (n_public && !public_values) return TS_ERR_INVALID;
     const std::vector<uint32_t> pis(public_values, public_values + n_public);
-    struct Gate {
-        std::mutex m;
-        double last = -1e300, gap = 0;
-    } gate;
-    gate.gap = gate_ms > 0 ? gate_ms : 0;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+    StartGate gate(gate_ms);
     std::vector<ts_status> status(n_lanes, TS_OK);
     std::vector<std::vector<uint32_t>> last_proof(n_lanes);
     std::vector<uint32_t> last_index(n_lanes, 0);
@@ -1054,34 +1140,23 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
     auto lane_main = [&](uint32_t l) {
         ts_ctx* ctx = ctxs[l];
         status[l] = guard(ctx, [&] {
-            ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
+            ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
             for (uint32_t i = 0; i < n_proofs && !stop.load(); i++) {
                 if (lane_of[i] != l) continue;
-                TS_REQUIRE(traces[i]->m.buf.p, ts::TS_ERR_INVALID, "prove_stream: trace matrix was already consumed");
+                const ts::AirProgram& prog = ready_prog(airs[l]);
+                ts::DeviceMatrix trace = lane_trace(traces[i], ctx, prog);
                 ts::BfChallenger chal(0, true);  // a fresh challenger per proof, as prove() is handed
-                if (gate.gap > 0) {  // no two proofs start within gate_ms of each other
-                    std::lock_guard<std::mutex> g(gate.m);
-                    for (;;) {
-                        const double wait = gate.last + gate.gap - now_ms();
-                        if (wait <= 0) break;
-                        std::this_thread::sleep_for(std::chrono::microseconds((long)std::min(wait * 1e3, 200.0)));
-                    }
-                    gate.last = now_ms();
-                }
-                const double t0 = now_ms();
-                std::vector<uint32_t> proof = ts::prove(pcs, ready_prog(airs[l]), chal, std::move(traces[i]->m), pis);
+                const double t0 = gate.enter();
+                std::vector<uint32_t> proof = ts::prove(pcs, prog, chal, std::move(trace), pis);
                 if (start_ms_out) start_ms_out[i] = t0;
-                if (wall_ms_out) wall_ms_out[i] = now_ms() - t0;
+                if (wall_ms_out) wall_ms_out[i] = gate.now_ms() - t0;
                 last_proof[l] = std::move(proof);
                 last_index[l] = i;
             }
         });
         if (status[l] != TS_OK) stop = true;
     };
-    std::vector<std::thread> threads;
-    for (uint32_t l = 1; l < n_lanes; l++) threads.emplace_back(lane_main, l);
-    lane_main(0);
-    for (auto& t : threads) t.join();
+    if (run_lanes(n_lanes, lane_main) != TS_OK) return TS_ERR_OOM;
     for (uint32_t l = 0; l < n_lanes; l++)
         if (status[l] != TS_OK) return status[l];
     // the proof of the highest index goes back (every proof of a run is checked by the caller's tests, not here)
@@ -1101,22 +1176,15 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
 // ts_prove_stream's lane loop for n DISTINCT statements (uni-stark/src/prover.rs:25-39: each call has its own
 // trace, public values and challenger, and returns its proof): per-item inputs and outputs, host traces
 // uploaded on the lane's stream just before their proof, failures confined to the item (or, for a device
-// fault, to its lane).  ts_prove_stream itself is left as it was: bench.py drives it.
+// fault, to its lane).  The whole-call refusals, the start gate and the lane threads are shared with the stream.
 ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_t n_lanes,
                          const ts_fri_config* cfg, ts_batch_item* items, uint32_t n_items, double gate_ms,
                          uint32_t flags) {
     // whole-call refusals first: nothing is consumed or written before these pass
-    if (!ctxs || !airs || (!items && n_items) || n_lanes == 0 || n_lanes > 64) return TS_ERR_INVALID;
-    for (uint32_t l = 0; l < n_lanes; l++)
-        if (!ctxs[l] || !airs[l]) return TS_ERR_INVALID;
+    ts::FriConfig fri;
+    if ((!items && n_items) || !check_lanes(ctxs, airs, n_lanes, cfg, fri)) return TS_ERR_INVALID;
     for (uint32_t i = 0; i < n_items; i++)
         if (items[i].struct_size != sizeof(ts_batch_item)) return TS_ERR_INVALID;
-    ts::FriConfig fcfg;
-    try {
-        fcfg = load_cfg(cfg);
-    } catch (const ts::Error&) {
-        return TS_ERR_INVALID;
-    }
     for (uint32_t i = 0; i < n_items; i++) {
         ts_batch_item& it = items[i];
         it.status = -1;
@@ -1136,11 +1204,7 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
     for (size_t k = 1; k < handles.size(); k++)
         if (handles[k].first == handles[k - 1].first) items[handles[k].second].status = TS_ERR_INVALID;
 
-    std::mutex gate_m;
-    double gate_last = -1e300;
-    const double gap = gate_ms > 0 ? gate_ms : 0;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+    StartGate gate(gate_ms);
     auto lane_main = [&](uint32_t l) {
         ts_ctx* ctx = ctxs[l];
         const ts_air* air = airs[l];
@@ -1155,38 +1219,20 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
                 TS_REQUIRE(it.proof_out, ts::TS_ERR_INVALID, "prove_batch: null proof_out");
                 TS_REQUIRE(it.n_public == prog.n_public, ts::TS_ERR_INVALID,
                            "prove_batch: n_public differs from the lane's AIR");
-                TS_REQUIRE(!it.n_public || it.public_values, ts::TS_ERR_INVALID, "prove_batch: null public values");
+                const std::vector<uint32_t> pis = public_inputs(it.public_values, it.n_public);
+                ts::DeviceMatrix trace;
                 if (it.trace) {
-                    TS_REQUIRE(it.trace->m.buf.p, ts::TS_ERR_INVALID, "prove_batch: trace matrix was already consumed");
-                    TS_REQUIRE(it.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
-                               "prove_batch: trace was not made on the lane's context");
-                    TS_REQUIRE(it.trace->m.width == prog.width, ts::TS_ERR_INVALID,
-                               "prove_batch: trace width differs from the lane's AIR");
+                    trace = lane_trace(it.trace, ctx, prog);
                 } else {
                     TS_REQUIRE(it.height >= 1 && (it.height & (it.height - 1)) == 0 && it.height <= (1ull << 27),
                                ts::TS_ERR_INVALID, "prove_batch: host trace height must be a power of two <= 2^27");
                     TS_REQUIRE(it.width == prog.width, ts::TS_ERR_INVALID,
                                "prove_batch: host trace width differs from the lane's AIR");
                 }
-                const std::vector<uint32_t> pis(it.public_values, it.public_values + it.n_public);
                 ts::BfChallenger chal = it.challenger ? it.challenger->c : ts::BfChallenger(0, true);
-                if (!pcs) pcs = std::make_unique<ts::TwoAdicFriPcs>(ctx->ctx, fcfg);
-                double t0;
-                if (gap > 0) {  // no two proofs start within gate_ms of each other; the stamp is taken INSIDE
-                    std::lock_guard<std::mutex> g(gate_m);
-                    for (;;) {
-                        const double wait = gate_last + gap - now_ms();
-                        if (wait <= 0) break;
-                        std::this_thread::sleep_for(std::chrono::microseconds((long)std::min(wait * 1e3, 200.0)));
-                    }
-                    t0 = gate_last = now_ms();
-                } else {
-                    t0 = now_ms();
-                }
-                ts::DeviceMatrix trace;
-                if (it.trace) {
-                    trace = std::move(it.trace->m);
-                } else {  // H2D on the lane's stream: ordered before the proof's kernels, no host wait here
+                if (!pcs) pcs = std::make_unique<ts::TwoAdicFriPcs>(ctx->ctx, fri);
+                const double t0 = gate.enter();
+                if (!it.trace) {  // H2D on the lane's stream: ordered before the proof's kernels, no host wait here
                     trace.buf = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)it.height * it.width);
                     trace.height = it.height;
                     trace.width = it.width;
@@ -1196,11 +1242,9 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
                 }
                 std::vector<uint32_t> proof = ts::prove(*pcs, prog, chal, std::move(trace), pis);
                 it.start_ms = t0;
-                it.wall_ms = now_ms() - t0;
+                it.wall_ms = gate.now_ms() - t0;
                 chal.export_state(it.final_state);
-                it.n_words = proof.size();
-                TS_REQUIRE(proof.size() <= it.cap_words, ts::TS_ERR_BUFFER, "prove_batch: proof buffer too small");
-                memcpy(it.proof_out, proof.data(), proof.size() * 4);
+                copy_proof(proof, it.proof_out, it.cap_words, &it.n_words);
                 if (flags & TS_BATCH_DIGEST)
                     ts::b3::hash_stream([&](uint64_t k) { return proof[k]; }, proof.size(), it.proof_blake3);
             });
@@ -1208,10 +1252,7 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
             if (it.status == TS_ERR_HIP || it.status == TS_ERR_OOM || it.status == TS_ERR_INVARIANT) break;
         }
     };
-    std::vector<std::thread> threads;
-    for (uint32_t l = 1; l < n_lanes; l++) threads.emplace_back(lane_main, l);
-    lane_main(0);
-    for (auto& t : threads) t.join();
+    if (run_lanes(n_lanes, lane_main) != TS_OK) return TS_ERR_OOM;
     for (uint32_t i = 0; i < n_items; i++)
         if (items[i].status != TS_OK) return items[i].status;
     return TS_OK;
@@ -1243,12 +1284,7 @@ ts_status ts_prove_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_comm*
     *n_words_out = 0;
     return guard(ctx, [&] {
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
-        TS_REQUIRE(trace_rows->m.buf.p, ts::TS_ERR_INVALID, "prove: trace matrix was already consumed");
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts_comm cb = *comm;
         ts::Comm c = wrap_comm(cb);
         ts::ShardOptions opt;
@@ -1261,18 +1297,12 @@ ts_status ts_prove_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_comm*
         }
         if (options) opt.trace_replicated = options->trace_replicated != 0;
         if (options) opt.local_quotient = options->local_quotient != 0;
+        ts::DeviceMatrix m = take_trace(trace_rows);
         ts::StageTimer t(&ctx->ctx, "prove");
-        std::vector<uint32_t> proof;
-        try {
-            proof = ts::prove_sharded(pcs, c, ready_prog(air), chal->c, std::move(trace_rows->m), pis, opt);
-        } catch (...) {
-            // this rank is leaving the protocol: make the peers' pending collectives fail, not hang
-            if (cb.abort) cb.abort(cb.user);
-            throw;
-        }
-        *n_words_out = proof.size();
-        TS_REQUIRE(proof.size() <= cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
-        memcpy(proof_out, proof.data(), proof.size() * 4);
+        copy_proof(abort_on_throw(cb, [&] {
+                       return ts::prove_sharded(pcs, c, ready_prog(air), chal->c, std::move(m), pis, opt);
+                   }),
+                   proof_out, cap_words, n_words_out);
     });
 }
 
@@ -1286,21 +1316,12 @@ ts_status ts_prove_tap(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
     *n_words_out = 0;
     return guard(ctx, [&] {
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
-        TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "prove: trace matrix was already consumed");
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
-        ts::TapLocks locks;
-        locks.bytes = lock_scripts;
-        locks.offsets = lock_offsets;
-        locks.n_scripts = n_scripts;
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
+        ts::DeviceMatrix m = take_trace(trace);
         ts::StageTimer t(&ctx->ctx, "prove");
-        std::vector<uint32_t> proof = ts::prove_tap(pcs, ready_prog(air), chal->c, std::move(trace->m), pis, locks);
-        *n_words_out = proof.size();
-        TS_REQUIRE(proof.size() <= cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
-        memcpy(proof_out, proof.data(), proof.size() * 4);
+        copy_proof(ts::prove_tap(pcs, ready_prog(air), chal->c, std::move(m), pis, locks), proof_out, cap_words,
+                   n_words_out);
     });
 }
 
@@ -1314,29 +1335,16 @@ ts_status ts_prove_tap_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_c
     *n_words_out = 0;
     return guard(ctx, [&] {
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
-        TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "prove: trace matrix was already consumed");
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
-        ts::TapLocks locks;
-        locks.bytes = lock_scripts;
-        locks.offsets = lock_offsets;
-        locks.n_scripts = n_scripts;
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
         const ts_comm cb = *comm;
         ts::Comm c = wrap_comm(cb);
+        ts::DeviceMatrix m = take_trace(trace);
         ts::StageTimer t(&ctx->ctx, "prove");
-        std::vector<uint32_t> proof;
-        try {
-            proof = ts::prove_tap(pcs, ready_prog(air), chal->c, std::move(trace->m), pis, locks, &c);
-        } catch (...) {
-            if (cb.abort) cb.abort(cb.user);  // the peers' pending collectives fail instead of waiting
-            throw;
-        }
-        *n_words_out = proof.size();
-        TS_REQUIRE(proof.size() <= cap_words, ts::TS_ERR_BUFFER, "proof buffer too small");
-        memcpy(proof_out, proof.data(), proof.size() * 4);
+        copy_proof(abort_on_throw(cb, [&] {
+                       return ts::prove_tap(pcs, ready_prog(air), chal->c, std::move(m), pis, locks, &c);
+                   }),
+                   proof_out, cap_words, n_words_out);
     });
 }
 
@@ -1348,18 +1356,11 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
     *verdict = -1;
     return guard(nullptr, [&] {
         ts::FriConfig f = load_cfg(cfg);
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         for (size_t i = 0; i < n_scripts; i++)
             TS_REQUIRE(lock_offsets[i + 1] >= lock_offsets[i], ts::TS_ERR_INVALID, "bad lock script offsets");
-        ts::TapLocks locks;
-        locks.bytes = lock_scripts;
-        locks.offsets = lock_offsets;
-        locks.n_scripts = n_scripts;
-        *verdict = ts::verify_tap(f, air->prog, chal->c, proof, n_words, pis, locks);
+        *verdict = ts::verify_tap(f, air->prog, chal->c, proof, n_words, pis,
+                                  tap_locks(lock_scripts, lock_offsets, n_scripts));
     });
 }
 
@@ -1404,12 +1405,7 @@ ts_status ts_verify(const ts_fri_config* cfg, const ts_air* air, ts_challenger* 
     *verdict = -1;
     return guard(nullptr, [&] {
         ts::FriConfig f = load_cfg(cfg);
-        std::vector<uint32_t> pis;
-        if (n_public) {
-            TS_REQUIRE(public_values, ts::TS_ERR_INVALID, "null public values");
-            pis.assign(public_values, public_values + n_public);
-        }
-        *verdict = ts::verify(f, air->prog, chal->c, proof, n_words, pis);
+        *verdict = ts::verify(f, air->prog, chal->c, proof, n_words, public_inputs(public_values, n_public));
     });
 }
 

@@ -733,19 +733,7 @@ def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_valu
         air = CompiledAir(ctx, air_tape(air, len(pis)))
     if not isinstance(trace, DeviceMatrix):
         trace = DeviceMatrix.upload(ctx, trace)
-    n, w = trace.dims()
-    log_n = n.bit_length() - 1
-    log_N = log_n + pcs.fri.log_blowup
-    qd = 1 << air.log_quotient_degree
-    R = log_N - pcs.fri.log_blowup
-    Q = pcs.fri.num_queries
-    cap = (64 + 8 * w + 16 * qd + 8 * R
-           + Q * (16 + w + 5 * qd + 2 * 8 * log_N + R * (9 + 8 * log_N)))
-    # One output buffer per context, kept for its lifetime (a context is driven by one thread): no
-    # half-megabyte allocation, zero-fill and release per proof.
-    out = getattr(ctx, "_proof_buf", None)
-    if out is None or len(out) < cap:
-        out = ctx._proof_buf = np.zeros(cap, dtype=np.uint32)
+    out = _proof_buffer(ctx, _proof_capacity(*trace.dims(), air.log_quotient_degree, pcs.fri))
     n_words = C.c_size_t()
     cfg = pcs.fri._c()
     pis_p = _p(pis) if len(pis) else None
@@ -761,17 +749,14 @@ def prove_stream(lanes, traces, lane_of, public_values, gate_ms: float = 0.0, wa
     consumed) and a fresh challenger.  Returns (Proof of the highest index, start_ms array, wall_ms array)."""
     n_l, n = len(lanes), len(traces)
     l = _lib.lib()
-    ctxs = (C.c_void_p * n_l)(*[conf.pcs.ctx.h for conf, _ in lanes])
-    airs = (C.c_void_p * n_l)(*[a.h for _, a in lanes])
+    ctxs, airs, fri = _lane_arrays(lanes)
     mats = (C.c_void_p * max(n, 1))(*[t.h for t in traces])
     lo = _u32(lane_of)
     pis = _u32(public_values)
-    pcs = lanes[0][0].pcs
-    cfg = pcs.fri._c()
-    ctx0 = pcs.ctx
-    out = getattr(ctx0, "_proof_buf", None)
-    if out is None or len(out) < (1 << 20):
-        out = ctx0._proof_buf = np.zeros(1 << 20, dtype=np.uint32)
+    cfg = fri._c()
+    # sized for the proof that comes back: that of the highest index
+    cap = _proof_capacity(*traces[-1].dims(), _lane_lqd(lanes, lane_of[-1]), fri) if n else 1
+    out = _proof_buffer(lanes[0][0].pcs.ctx, cap)
     n_words = C.c_size_t()
     st = np.zeros(max(n, 1), dtype=np.float64)
     wl = np.zeros(max(n, 1), dtype=np.float64)
@@ -779,22 +764,47 @@ def prove_stream(lanes, traces, lane_of, public_values, gate_ms: float = 0.0, wa
     rc = l.ts_prove_stream(ctxs, airs, n_l, C.byref(cfg), mats, _p(lo), n, _p(pis) if len(pis) else None, len(pis),
                            float(gate_ms), _p(out), len(out), C.byref(n_words),
                            st.ctypes.data_as(dp) if want_times else None, wl.ctypes.data_as(dp) if want_times else None)
-    if rc:
-        for conf, _ in lanes:  # the failing lane's context holds the message
-            msg = (l.ts_last_error(conf.pcs.ctx.h) or b"").decode()
-            if msg:
-                raise _lib.TsError(rc, msg)
-        raise _lib.TsError(rc, "ts_prove_stream")
+    if rc:  # the failing lane's context holds the message
+        msg = next(filter(None, (_lane_error(lanes, k) for k in range(n_l))), "ts_prove_stream")
+        raise _lib.TsError(rc, msg)
     return Proof(out[: n_words.value].copy()), st[:n], wl[:n]
 
 
 def _proof_capacity(n: int, w: int, log_quotient_degree: int, fri: FriConfig) -> int:
-    """Upper bound on the TSPF v1 words of one proof of an n x w trace (as ``prove`` sizes its buffer)."""
+    """Upper bound on the TSPF v1 words of one proof of an n x w trace."""
     log_N = max(n, 1).bit_length() - 1 + fri.log_blowup
     qd = 1 << log_quotient_degree
     R = log_N - fri.log_blowup
     Q = fri.num_queries
     return 64 + 8 * w + 16 * qd + 8 * R + Q * (16 + w + 5 * qd + 2 * 8 * log_N + R * (9 + 8 * log_N))
+
+
+def _proof_buffer(ctx, cap: int) -> np.ndarray:
+    """One output buffer per context, kept for its lifetime (a context is driven by one thread): no
+    half-megabyte allocation, zero-fill and release per proof."""
+    out = getattr(ctx, "_proof_buf", None)
+    if out is None or len(out) < cap:
+        out = ctx._proof_buf = np.zeros(cap, dtype=np.uint32)
+    return out
+
+
+def _lane_arrays(lanes):
+    """The ``ctxs`` / ``airs`` arrays of a lane call and its FriConfig (that of lane 0: all lanes share it)."""
+    ctxs = (C.c_void_p * len(lanes))(*[conf.pcs.ctx.h for conf, _ in lanes])
+    airs = (C.c_void_p * len(lanes))(*[a.h for _, a in lanes])
+    return ctxs, airs, lanes[0][0].pcs.fri
+
+
+def _lane_lqd(lanes, lane: int) -> int:
+    """log_quotient_degree of a lane's AIR (0 for a lane index the library will refuse)."""
+    return lanes[lane][1].log_quotient_degree if 0 <= lane < len(lanes) else 0
+
+
+def _lane_error(lanes, lane: int) -> str:
+    """The error text of a lane's context ('' if it holds none)."""
+    if not 0 <= lane < len(lanes):
+        return f"lane {lane} out of range"
+    return (_lib.lib().ts_last_error(lanes[lane][0].pcs.ctx.h) or b"").decode()
 
 
 @dataclass
@@ -852,10 +862,8 @@ def prove_batch(lanes, traces, lane_of, public_values=None, challengers=None, ga
     if not lanes:
         raise ValueError("prove_batch: no lanes")
     l = _lib.lib()
-    fri = lanes[0][0].pcs.fri
+    ctxs, airs, fri = _lane_arrays(lanes)
     cfg = fri._c()
-    ctxs = (C.c_void_p * n_l)(*[conf.pcs.ctx.h for conf, _ in lanes])
-    airs = (C.c_void_p * n_l)(*[a.h for _, a in lanes])
     items = (_lib.BatchItemC * max(n, 1))()
     keep, outs = [], []  # host buffers that must outlive the call
     for i, t in enumerate(traces):
@@ -880,8 +888,7 @@ def prove_batch(lanes, traces, lane_of, public_values=None, challengers=None, ga
         it.n_public = len(pis[i])
         it.public_values = pis[i].ctypes.data if len(pis[i]) else None
         it.challenger = chals[i].h if chals[i] is not None else None
-        lqd = lanes[lane_of[i]][1].log_quotient_degree if 0 <= lane_of[i] < n_l else 0
-        cap = _proof_capacity(h, w, lqd, fri) if caps[i] is None else caps[i]
+        cap = _proof_capacity(h, w, _lane_lqd(lanes, lane_of[i]), fri) if caps[i] is None else caps[i]
         out = np.zeros(max(cap, 1), dtype=np.uint32)
         outs.append(out)
         it.proof_out = out.ctypes.data
@@ -890,11 +897,10 @@ def prove_batch(lanes, traces, lane_of, public_values=None, challengers=None, ga
                           _lib.BATCH_DIGEST if digests else 0)
     status = np.array([items[i].status for i in range(n)], dtype=np.int32)
     if rc and (status == -1).all():  # the whole call was refused: no item was touched
-        msg = "ts_prove_batch refused the call (null arrays, lane count, FriConfig or struct_size)"
+        msg = "ts_prove_batch refused the call (null arrays, lane count, a repeated context, FriConfig or struct_size)"
         raise _lib.TsError(rc, msg)
     n_words = np.array([items[i].n_words for i in range(n)], dtype=np.int64)
-    errors = [None if s == 0 else (l.ts_last_error(lanes[lane_of[i]][0].pcs.ctx.h) or b"").decode()
-              if 0 <= lane_of[i] < n_l else f"lane {lane_of[i]} out of range" for i, s in enumerate(status)]
+    errors = [None if s == 0 else _lane_error(lanes, lane_of[i]) for i, s in enumerate(status)]
     res = BatchResult(
         rc=int(rc),
         proofs=[Proof(outs[i][: n_words[i]].copy()) if status[i] == 0 else None for i in range(n)],
@@ -933,12 +939,7 @@ def prove_sharded(config: StarkConfig, air, challenger: BfChallenger, trace_rows
         trace_rows = DeviceMatrix.upload(ctx, trace_rows)
     n_loc, w = trace_rows.dims()
     n = n_loc if trace_replicated else n_loc * comm.world
-    log_N = n.bit_length() - 1 + pcs.fri.log_blowup
-    qd = 1 << air.log_quotient_degree
-    R = log_N - pcs.fri.log_blowup
-    Q = pcs.fri.num_queries
-    cap = (64 + 8 * w + 16 * qd + 8 * R
-           + Q * (16 + w + 5 * qd + 2 * 8 * log_N + R * (9 + 8 * log_N)))
+    cap = _proof_capacity(n, w, air.log_quotient_degree, pcs.fri)
     out = np.zeros(cap, dtype=np.uint32)
     n_words = C.c_size_t()
     cfg = pcs.fri._c()

@@ -1,6 +1,6 @@
 """CPU-side checks of ts_prove_batch (include/tapstark.h): the symbol, the refusals of a meaningless call
 (which return before any context is touched, so no GPU is needed), the ctypes layout of ts_batch_item and
-the Python wrapper's own argument checks."""
+the Python wrapper's own argument checks; and the same whole-call refusals of ts_prove_stream."""
 import ctypes as C
 import os
 import subprocess
@@ -29,14 +29,25 @@ def host_air(lib):
     return ts.CompiledAir(None, ts.air_tape(FibonacciAir(), 3))
 
 
-# a stand-in context: never dereferenced by the refusals below (they happen before any lane starts)
+# a stand-in context and trace: never dereferenced by the refusals below (they happen before any lane starts)
 _FAKE_CTX = C.create_string_buffer(64)
+_FAKE_TRACE = C.create_string_buffer(64)
 
 
 def _call(lib, ctxs, airs, n_lanes, items, n_items, cfg=(2, 28, 8)):
     cfg_c = _lib.FriConfigC(*cfg) if cfg is not None else None
     return lib.ts_prove_batch(ctxs, airs, n_lanes, C.byref(cfg_c) if cfg_c is not None else None,
                               items, n_items, 0.0, 0)
+
+
+def _stream(lib, ctxs, airs, n_lanes, lane_of, traces=True):
+    n = len(lane_of) if lane_of is not None else 1
+    mats = (C.c_void_p * n)(*([C.addressof(_FAKE_TRACE)] * n)) if traces else None
+    lo = (C.c_uint32 * n)(*lane_of) if lane_of is not None else None
+    cfg_c = _lib.FriConfigC(2, 28, 8)
+    n_words = C.c_size_t(12345)
+    return lib.ts_prove_stream(ctxs, airs, n_lanes, C.byref(cfg_c), mats, lo, n, None, 0, 0.0, None, 0,
+                               C.byref(n_words), None, None)
 
 
 def _lanes(host_air, n):
@@ -119,3 +130,27 @@ def test_wrapper_rejects_mismatched_lengths_before_the_library(monkeypatch):
         ts.prove_batch(lanes, traces, [0, 0, 0], public_values=[[0, 1, 2], [0, 1, 2]])
     with pytest.raises(ValueError, match="challengers"):
         ts.prove_batch(lanes, traces, [0, 0, 0], challengers=[None, None])
+
+
+def test_stream_refuses_before_any_lane_starts(lib, host_air):
+    ctxs, airs = _lanes(host_air, 65)
+    assert _stream(lib, None, airs, 1, [0]) == TS_ERR_INVALID
+    assert _stream(lib, ctxs, None, 1, [0]) == TS_ERR_INVALID
+    assert _stream(lib, ctxs, airs, 1, [0], traces=False) == TS_ERR_INVALID
+    assert _stream(lib, ctxs, airs, 1, None) == TS_ERR_INVALID
+    assert _stream(lib, ctxs, airs, 0, [0]) == TS_ERR_INVALID
+    assert _stream(lib, ctxs, airs, 65, [0]) == TS_ERR_INVALID
+    null_ctx = (C.c_void_p * 1)(None)
+    assert _stream(lib, null_ctx, airs, 1, [0]) == TS_ERR_INVALID
+    # a proof no lane can take refuses the whole call
+    assert _stream(lib, ctxs, airs, 1, [0, 1]) == TS_ERR_INVALID
+
+
+def test_one_context_on_two_lanes_refused(lib, host_air):
+    # two lane threads would drive one context: both calls refuse it before any lane starts
+    ctxs, airs = _lanes(host_air, 2)
+    assert _stream(lib, ctxs, airs, 2, [0, 1]) == TS_ERR_INVALID
+    items = (_lib.BatchItemC * 1)(_item(lane=5))
+    assert _call(lib, ctxs, airs, 2, items, 1) == TS_ERR_INVALID
+    assert items[0].status == 12345, "a refused call wrote an item"
+    assert _call(lib, ctxs, airs, 2, None, 0) == TS_ERR_INVALID
