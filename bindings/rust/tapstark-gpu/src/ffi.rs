@@ -12,6 +12,16 @@ pub const TS_OK: ts_status = 0;
 pub const TS_ERR_INVARIANT: ts_status = 5; // where the reference would have panicked
 pub const TS_ERR_BUFFER: ts_status = 6;
 
+/// `ts_air_options` (struct_size first): the segmented specialisation of `ts_air_compile_opts`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_air_options {
+    pub struct_size: u32,
+    pub segment_instr: u32,
+    pub jit_jobs: u32,
+    pub reserved: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct ts_fri_config {
@@ -107,6 +117,9 @@ extern "C" {
     pub fn ts_air_is_jit(air: *const ts_air) -> c_int;
     pub fn ts_air_jit_wait(ctx: *mut ts_ctx, air: *mut ts_air, state: *mut c_int, compile_seconds: *mut f64) -> ts_status;
     pub fn ts_air_program(air: *const ts_air, out: *mut u32, cap_words: usize, n_words: *mut usize) -> ts_status;
+    pub fn ts_air_compile_opts(ctx: *mut ts_ctx, tape: *const u32, n_words: usize, opt: *const ts_air_options,
+                               out: *mut *mut ts_air) -> ts_status;
+    pub fn ts_air_segment_plan(air: *const ts_air, out: *mut u32, cap_words: usize, n_words: *mut usize) -> ts_status;
 
     pub fn ts_pcs_commit(ctx: *mut ts_ctx, cfg: *const ts_fri_config, n_mats: u32,
                          evals: *const *mut ts_matrix, domain_shifts: *const u32, root_out: *mut u32,

@@ -143,7 +143,8 @@ ts_status ts_air_info(const ts_air* air, uint32_t* width, uint32_t* n_public,
  * directory) keeps the code objects across processes: a later ts_air_compile of the same AIR loads
  * instead of compiling. */
 int ts_air_is_jit(const ts_air* air);
-/* joins a background compilation; state: 0 none, 3 specialised kernel loaded, 4 compilation failed */
+/* joins a background compilation (every child of a segmented AIR); state: 0 none, 3 specialised kernel(s)
+ * loaded, 4 compilation failed */
 ts_status ts_air_jit_wait(ts_ctx* ctx, ts_air* air, int* state, double* compile_seconds);
 void ts_air_free(ts_ctx* ctx, ts_air* air);
 /* Inspection of what the tape was lowered to (none of these needs a GPU; `air` may be host-only).
@@ -159,6 +160,31 @@ void ts_air_free(ts_ctx* ctx, ts_air* air);
  * ts_air_jit_source: the HIP source (not NUL-terminated; *n_bytes set even on TS_ERR_BUFFER).
  * ts_air_jit_compile: that source through hiprtc for `arch` ("gfx950"); the code object and the
  *   compile time.  TS_ERR_UNSUPPORTED if hiprtc is missing or the compilation fails. */
+/* Segmented specialisation (opt-in).  A program longer than segment_instr lowered instructions is cut into
+ * segments of at most that many, each its own straight-line kernel; a computed value that crosses a cut goes
+ * through an explicit slab in device memory, the constraint sum as 8 more words.  Compile time grows with the
+ * program, not faster, and no kernel spills: each stays within 128 VGPRs.  Such an AIR is always compiled in
+ * the background by up to jit_jobs ts_jitc children (0 = up to 4; at most 8), one module each, while proofs
+ * run on the interpreter; ts_air_jit_wait joins them all, ts_air_free kills those still running, and
+ * TS_JIT_CACHE_DIR keeps every module under its own key.  It has no TS_JIT_MAX_INSTR ceiling but a cap of
+ * 2^20 lowered instructions (TS_ERR_INVALID above).  opt == NULL or segment_instr == 0 is ts_air_compile, and
+ * so is a program of at most segment_instr instructions.  struct_size must be sizeof(ts_air_options) and
+ * reserved 0 (else TS_ERR_INVALID).  ts_air_jit_source / ts_air_jit_compile of a segmented AIR give all its
+ * kernels in one module. */
+typedef struct ts_air_options {
+    uint32_t struct_size;   /* sizeof(ts_air_options) */
+    uint32_t segment_instr; /* 0 = as ts_air_compile; S > 0: programs longer than S are segmented */
+    uint32_t jit_jobs;      /* compiler children for one AIR; 0 = default */
+    uint32_t reserved;      /* must be 0 */
+} ts_air_options;
+ts_status ts_air_compile_opts(ts_ctx* ctx, const uint32_t* tape, size_t n_words, const ts_air_options* opt,
+                              ts_air** out);
+/* The plan of a segmented AIR: out = [slab_width, n_segments, then per segment: begin, end (lowered
+ * instructions, [begin, end)), n_in, n_out, pressure (most values its kernel holds at once), n_in x (defining
+ * instruction, slot), n_out x (defining instruction, slot)].  slab_width counts value slots only (the most
+ * values live across one cut).  TS_ERR_BUFFER with *n_words set if cap is short; TS_ERR_INVALID for an AIR
+ * that is not segmented. */
+ts_status ts_air_segment_plan(const ts_air* air, uint32_t* out, size_t cap_words, size_t* n_words);
 ts_status ts_air_program(const ts_air* air, uint32_t* out, size_t cap_words, size_t* n_words);
 ts_status ts_air_jit_source(const ts_air* air, char* buf, size_t cap, size_t* n_bytes);
 ts_status ts_air_jit_compile(const ts_air* air, const char* arch, void* code_out, size_t cap,

@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "ts_ctx_stream", "ts_ctx_set_timing", "ts_ctx_take_timings", "ts_ctx_set_replay", "ts_ctx_set_kernel_timing",
     "ts_ctx_take_kernel_timings", "ts_ctx_graph_stats", "ts_ctx_stat", "ts_matrix_upload",
     "ts_matrix_from_device", "ts_trace_fibonacci", "ts_trace_synth_mul", "ts_trace_synth_ext", "ts_matrix_dims", "ts_matrix_download", "ts_matrix_free",
-    "ts_air_compile", "ts_air_info", "ts_air_is_jit", "ts_air_jit_wait", "ts_air_free", "ts_air_program", "ts_air_jit_source", "ts_air_jit_compile", "ts_pcs_commit", "ts_mmcs_commit", "ts_pcs_data_lde",
+    "ts_air_compile", "ts_air_compile_opts", "ts_air_segment_plan", "ts_air_info", "ts_air_is_jit", "ts_air_jit_wait", "ts_air_free", "ts_air_program", "ts_air_jit_source", "ts_air_jit_compile", "ts_pcs_commit", "ts_mmcs_commit", "ts_pcs_data_lde",
     "ts_pcs_data_info", "ts_pcs_data_matrix_info", "ts_pcs_data_digests", "ts_pcs_open_batch", "ts_pcs_data_free",
     "ts_quotient_chunks", "ts_pcs_open_reduce", "ts_pcs_open", "ts_pcs_verify", "ts_fri_prove", "ts_fri_verify", "ts_fri_fold", "ts_fri_fold_device", "ts_chal_new", "ts_chal_clone",
     "ts_chal_free", "ts_chal_observe", "ts_chal_observe_commitment", "ts_chal_sample",
@@ -41,6 +41,12 @@ ABI_SYMBOLS = [
 
 STATUS = {0: "TS_OK", 1: "TS_ERR_INVALID", 2: "TS_ERR_HIP", 3: "TS_ERR_OOM",
           4: "TS_ERR_UNSUPPORTED", 5: "TS_ERR_INVARIANT", 6: "TS_ERR_BUFFER", 7: "TS_ERR_COMM"}
+
+
+class AirOptionsC(C.Structure):
+    """``ts_air_options`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("segment_instr", C.c_uint32), ("jit_jobs", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class TsError(RuntimeError):

@@ -1,6 +1,7 @@
 // extern "C" boundary (include/tapstark.h): plain pointers and sizes, status codes, no exceptions
 // across the ABI.
 #include <dlfcn.h>
+#include <errno.h>
 #include <signal.h>
 #include <spawn.h>
 #include <stdio.h>
@@ -29,6 +30,8 @@
 //                                               interpreter (a GPU path too) until the code object is
 //                                               ready, the next use loads it; ts_air_jit_wait joins;
 //   larger                                      interpreter only.
+// The segmented form (ts_air_compile_opts, air.cpp plan_segments) compiles linearly and has no such budget:
+// always in the background, its kernels split into up to J modules, one child each.
 // Both kernels compute the same words, so which one ran never shows in a proof.
 // A background compilation runs in a CHILD PROCESS (tap-stark_amd/jitc/ts_jitc.cpp, built beside the
 // library): hiprtc serialises compilations inside one process, cannot be interrupted, and a thread still
@@ -46,23 +49,59 @@ static std::string jitc_path() {
     return "ts_jitc";
 }
 
+// One compiler child per module.  `pid` stays set until the child has been reaped (or is known to have
+// ended when the host reaped it first), so a live child is always killed with its AIR.
 struct JitChild {
     pid_t pid = -1;
-    std::string dir, src, out, log, cache;
-    std::chrono::steady_clock::time_point t0;
-    void cleanup() {
-        for (const std::string& f : {src, out, out + ".part", log})
-            if (!f.empty()) (void)unlink(f.c_str());
-        if (!dir.empty()) (void)rmdir(dir.c_str());
-        dir.clear();
-    }
-    ~JitChild() {
-        if (pid > 0) {  // still compiling for an AIR nobody wants any more
-            (void)kill(pid, SIGKILL);
-            int st = 0;
-            (void)waitpid(pid, &st, 0);
+    bool done = false, ok = false;
+    std::string src, out, log, cache;
+    std::vector<char> code;  // the code object, once done and ok
+};
+static bool file_exists(const std::string& f) { return !f.empty() && access(f.c_str(), F_OK) == 0; }
+static bool read_all(const std::string& path, std::vector<char>& out) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    out.clear();
+    char buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + n);
+    fclose(f);
+    return true;
+}
+// waitpid without losing the child to EINTR; ECHILD (the host ignores SIGCHLD or reaped it with
+// waitpid(-1)) counts as ended only once ts_jitc's last file is there (it writes the log after the code
+// object, both by rename) or the pid is gone.  true once the child has ended; `st` is valid if `reaped`.
+static bool child_ended(JitChild& c, bool wait, bool& reaped, int& st) {
+    reaped = false;
+    for (;;) {
+        const pid_t r = waitpid(c.pid, &st, wait ? 0 : WNOHANG);
+        if (r == c.pid) {
+            reaped = true;
+            return true;
         }
-        cleanup();
+        if (r == 0) return false;
+        if (errno == EINTR) continue;
+        if (file_exists(c.log) || file_exists(c.out) || (kill(c.pid, 0) != 0 && errno == ESRCH)) return true;
+        if (!wait) return false;
+        std::this_thread::sleep_for(std::chrono::milliseconds(20));
+    }
+}
+struct JitJob {
+    std::string dir;
+    std::vector<JitChild> mods;
+    std::chrono::steady_clock::time_point t0;
+    ~JitJob() {
+        for (JitChild& c : mods) {
+            if (c.pid > 0) {  // still compiling for an AIR nobody wants any more
+                (void)kill(c.pid, SIGKILL);
+                int st = 0;
+                while (waitpid(c.pid, &st, 0) < 0 && errno == EINTR) {
+                }
+            }
+            for (const std::string& f : {c.src, c.out, c.out + ".part", c.log, c.log + ".part"})
+                if (!f.empty() && !dir.empty()) (void)unlink(f.c_str());
+        }
+        if (!dir.empty()) (void)rmdir(dir.c_str());
     }
 };
 
@@ -73,30 +112,98 @@ struct ts_air {
     int device = -1;  // the device the jit module was loaded on (-1: host-only AIR)
     enum { JIT_NONE = 0, JIT_COMPILING = 1, JIT_LOADED = 3, JIT_FAILED = 4 };
     int jit_state = JIT_NONE;
-    std::unique_ptr<JitChild> job;
+    std::unique_ptr<JitJob> job;
     double jit_seconds = 0;
     std::string arch;
     std::mutex poll_m;  // two threads proving with one ts_air: the adoption happens once
+    std::unique_ptr<ts::SegmentPlan> seg;  // set: the segmented form (ts_air_compile_opts)
+    uint32_t jit_jobs = 1;                 // modules (= compiler children) of the segmented form
+    std::unique_ptr<ts::JitKernelSet> kset;  // what prog.jit points at once published
 
+    std::vector<std::string> module_sources() const {
+        if (!seg) return {ts::jit_quotient_source(prog)};
+        return ts::jit_segment_sources(prog, *seg, jit_jobs);
+    }
+    std::vector<std::string> module_kernels(uint32_t j, uint32_t n_modules) const {
+        if (!seg) return {"k_quotient_jit"};
+        std::vector<std::string> names;
+        for (uint32_t k = ts::jit_segment_module_first(*seg, n_modules, j);
+             k < ts::jit_segment_module_first(*seg, n_modules, j + 1); k++)
+            names.push_back("k_quotient_seg" + std::to_string(k));
+        return names;
+    }
+    // loads every module on the AIR's device (the caller's device is restored) and publishes the set whole
+    bool publish(const std::vector<std::vector<char>>& codes, std::string& log) {
+        auto ks = std::make_unique<ts::JitKernelSet>();
+        ks->seg = seg.get();
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (device >= 0 && cur != device) (void)hipSetDevice(device);
+        bool ok = true;
+        for (uint32_t j = 0; ok && j < codes.size(); j++) {
+            void* mod = nullptr;
+            std::vector<void*> fns;
+            ok = ts::jit_load_module(codes[j], module_kernels(j, (uint32_t)codes.size()), mod, fns, log);
+            if (ok) {
+                ks->modules.push_back(mod);
+                ks->fns.insert(ks->fns.end(), fns.begin(), fns.end());
+            }
+        }
+        if (!ok)
+            for (void* m : ks->modules) (void)hipModuleUnload((hipModule_t)m);
+        if (device >= 0 && cur >= 0 && cur != device) (void)hipSetDevice(cur);
+        if (!ok) return false;
+        kset = std::move(ks);
+        prog.jit.publish(kset.get());
+        jit_state = JIT_LOADED;
+        return true;
+    }
     // a code object of this very source left by an earlier process (TS_JIT_CACHE_DIR): no compilation at all
     bool adopt_cached() {
         std::vector<char> code_obj;
         if (!ts::jit_cache_load(ts::jit_cache_path(ts::jit_quotient_source(prog), arch.c_str()), code_obj)) return false;
-        ts::JitKernel jk;
         std::string log;
-        if (!ts::jit_load_code(code_obj, jk, log)) return false;
-        prog.jit_module = jk.module;
-        prog.jit_fn = jk.fn;
-        jit_state = JIT_LOADED;
-        return true;
+        return publish({code_obj}, log);
     }
+    static pid_t spawn(const std::string& helper, const std::string& arch, const JitChild& c) {
+        char* argv[] = {const_cast<char*>(helper.c_str()), const_cast<char*>(arch.c_str()),
+                        const_cast<char*>(c.src.c_str()), const_cast<char*>(c.out.c_str()),
+                        const_cast<char*>(c.log.c_str()), nullptr};
+        // the child is a plain compiler run: nothing preloaded into the host (profilers, sanitizer runtimes)
+        // belongs in it
+        std::vector<char*> envp;
+        for (char** e = environ; e && *e; e++)
+            if (strncmp(*e, "LD_PRELOAD=", 11) != 0 && strncmp(*e, "HSA_TOOLS_LIB=", 14) != 0 &&
+                strncmp(*e, "ROCP_TOOL_", 10) != 0)
+                envp.push_back(*e);
+        envp.push_back(nullptr);
+        pid_t pid = -1;
+        return posix_spawn(&pid, helper.c_str(), nullptr, nullptr, argv, envp.data()) == 0 ? pid : -1;
+    }
+    // one child per module that the cache does not hold; with every module cached the set is published at once
     void start_background_jit() {
+        const std::vector<std::string> srcs = module_sources();
+        auto j = std::make_unique<JitJob>();
+        j->t0 = std::chrono::steady_clock::now();
+        j->mods.resize(srcs.size());
+        bool need_child = false;
+        for (size_t m = 0; m < srcs.size(); m++) {
+            JitChild& c = j->mods[m];
+            c.cache = ts::jit_cache_path(srcs[m], arch.c_str());
+            if (ts::jit_cache_load(c.cache, c.code)) c.done = c.ok = true;
+            else need_child = true;
+        }
+        if (!need_child) {
+            std::vector<std::vector<char>> codes;
+            for (JitChild& c : j->mods) codes.push_back(std::move(c.code));
+            if (!publish(codes, jit_log)) jit_state = JIT_FAILED;
+            return;
+        }
         const std::string helper = jitc_path();
         if (access(helper.c_str(), X_OK) != 0) {
             jit_log = "background specialisation needs the helper " + helper + " (not found): interpreter only";
             return;
         }
-        auto j = std::make_unique<JitChild>();
         const char* tmp = getenv("TMPDIR");
         std::string tmpl = std::string(tmp && *tmp ? tmp : "/tmp") + "/ts_jit_XXXXXX";
         std::vector<char> buf(tmpl.begin(), tmpl.end());
@@ -106,36 +213,27 @@ struct ts_air {
             return;
         }
         j->dir = buf.data();
-        j->src = j->dir + "/quotient_jit.hip";
-        j->out = j->dir + "/quotient_jit.co";
-        j->log = j->dir + "/log.txt";
-        const std::string src = ts::jit_quotient_source(prog);
-        j->cache = ts::jit_cache_path(src, arch.c_str());
-        FILE* f = fopen(j->src.c_str(), "wb");
-        if (!f || fwrite(src.data(), 1, src.size(), f) != src.size()) {
-            if (f) fclose(f);
-            jit_log = "cannot write the kernel source: interpreter only";
-            return;
+        for (size_t m = 0; m < srcs.size(); m++) {
+            JitChild& c = j->mods[m];
+            if (c.done) continue;
+            const std::string stem = j->dir + (seg ? "/quotient_seg" + std::to_string(m) : std::string("/quotient_jit"));
+            c.src = stem + ".hip";
+            c.out = stem + ".co";
+            c.log = seg ? stem + ".log" : j->dir + "/log.txt";
+            FILE* f = fopen(c.src.c_str(), "wb");
+            if (!f || fwrite(srcs[m].data(), 1, srcs[m].size(), f) != srcs[m].size()) {
+                if (f) fclose(f);
+                jit_log = "cannot write the kernel source: interpreter only";
+                return;  // ~JitJob kills the children already started
+            }
+            fclose(f);
+            c.pid = spawn(helper, arch, c);
+            if (c.pid <= 0) {
+                c.pid = -1;
+                jit_log = "posix_spawn of " + helper + " failed: interpreter only";
+                return;
+            }
         }
-        fclose(f);
-        char* argv[] = {const_cast<char*>(helper.c_str()), const_cast<char*>(arch.c_str()),
-                        const_cast<char*>(j->src.c_str()), const_cast<char*>(j->out.c_str()),
-                        const_cast<char*>(j->log.c_str()), nullptr};
-        // the child is a plain compiler run: nothing preloaded into the host (profilers, sanitizer runtimes)
-        // belongs in it
-        std::vector<char*> envp;
-        for (char** e = environ; e && *e; e++)
-            if (strncmp(*e, "LD_PRELOAD=", 11) != 0 && strncmp(*e, "HSA_TOOLS_LIB=", 14) != 0 &&
-                strncmp(*e, "ROCP_TOOL_", 10) != 0)
-                envp.push_back(*e);
-        envp.push_back(nullptr);
-        j->t0 = std::chrono::steady_clock::now();
-        pid_t pid = -1;
-        if (posix_spawn(&pid, helper.c_str(), nullptr, nullptr, argv, envp.data()) != 0) {
-            jit_log = "posix_spawn of " + helper + " failed: interpreter only";
-            return;
-        }
-        j->pid = pid;
         job = std::move(j);
         jit_state = JIT_COMPILING;
     }
@@ -143,54 +241,37 @@ struct ts_air {
     void poll_jit(bool wait) {
         std::lock_guard<std::mutex> pg(poll_m);
         if (!job) return;
-        int st = 0;
-        const pid_t r = waitpid(job->pid, &st, wait ? 0 : WNOHANG);
-        if (r == 0) return;  // still compiling
-        job->pid = -1;
+        for (JitChild& c : job->mods) {
+            if (c.done) continue;
+            bool reaped = false;
+            int st = 0;
+            if (!child_ended(c, wait, reaped, st)) return;  // still compiling
+            c.pid = -1;
+            c.done = true;
+            c.ok = (!reaped || (WIFEXITED(st) && WEXITSTATUS(st) == 0)) && read_all(c.out, c.code) && !c.code.empty();
+            if (c.ok) ts::jit_cache_store(c.cache, c.code);
+        }
         jit_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - job->t0).count();
-        std::vector<char> code_obj;
-        bool ok = r > 0 && WIFEXITED(st) && WEXITSTATUS(st) == 0;
-        if (ok) {
-            if (FILE* f = fopen(job->out.c_str(), "rb")) {
-                char buf[1 << 16];
-                size_t n;
-                while ((n = fread(buf, 1, sizeof buf, f)) > 0) code_obj.insert(code_obj.end(), buf, buf + n);
-                fclose(f);
+        std::vector<std::vector<char>> codes;
+        bool ok = true;
+        for (JitChild& c : job->mods) {
+            if (!c.ok && ok) {
+                std::vector<char> l;
+                if (read_all(c.log, l)) jit_log.assign(l.data(), std::min<size_t>(l.size(), 4096));
+                if (jit_log.empty()) jit_log = "the compiler child ended without a code object";
             }
-            ok = !code_obj.empty();
-            if (ok) ts::jit_cache_store(job->cache, code_obj);
+            ok = ok && c.ok;
+            codes.push_back(std::move(c.code));
         }
-        if (!ok) {
-            if (FILE* f = fopen(job->log.c_str(), "rb")) {
-                char buf[4096];
-                const size_t n = fread(buf, 1, sizeof buf, f);
-                jit_log.assign(buf, n);
-                fclose(f);
-            }
-            if (jit_log.empty()) jit_log = "the compiler child ended without a code object";
-        }
-        ts::JitKernel jk;
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (device >= 0 && cur != device) (void)hipSetDevice(device);  // the module belongs to the AIR's device
-        const bool loaded = ok && ts::jit_load_code(code_obj, jk, jit_log);
-        if (device >= 0 && cur >= 0 && cur != device) (void)hipSetDevice(cur);
-        if (loaded) {
-            prog.jit_module = jk.module;
-            prog.jit_fn = jk.fn;
-            jit_state = JIT_LOADED;
-        } else {
-            jit_state = JIT_FAILED;
-        }
+        if (!ok || !publish(codes, jit_log)) jit_state = JIT_FAILED;
         job.reset();
     }
     ~ts_air() {
         job.reset();
-        if (device >= 0 && prog.jit_module) (void)hipSetDevice(device);
-        ts::JitKernel jk;
-        jk.module = prog.jit_module;
-        jk.fn = prog.jit_fn;
-        ts::jit_release(jk);
+        if (kset) {
+            if (device >= 0) (void)hipSetDevice(device);
+            for (void* m : kset->modules) (void)hipModuleUnload((hipModule_t)m);
+        }
     }
 };
 // the program as the prover sees it, with a background specialisation adopted if it has finished
@@ -703,13 +784,29 @@ void ts_matrix_free(ts_ctx* ctx, ts_matrix* m) {
 }
 
 // ------------------------------------------------------------------ AIR
-ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out) {
+// segment_instr == 0: the monolithic route; S > 0 and a program longer than S: the segmented one
+static ts_status air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, uint32_t segment_instr,
+                             uint32_t jit_jobs, ts_air** out) {
     if (!out) return TS_ERR_INVALID;
     *out = nullptr;
+    auto env_or = [](const char* name, size_t dflt) {
+        const char* v = getenv(name);
+        return v && *v ? (size_t)strtoull(v, nullptr, 10) : dflt;
+    };
+    // segmented: the plan (host only).  The register budget keeps every segment kernel within 128 VGPRs
+    // (4 waves per SIMD) with no spill; TS_SEG_REGS overrides it for measurements.
+    auto plan = [&](ts_air& a) {
+        const size_t n_instr = a.prog.code.size() / 4;
+        if (segment_instr == 0 || n_instr <= segment_instr) return;
+        a.seg = std::make_unique<ts::SegmentPlan>(
+            ts::plan_segments(a.prog, segment_instr, (uint32_t)env_or("TS_SEG_REGS", 32)));
+        a.jit_jobs = std::min<uint32_t>(jit_jobs ? jit_jobs : 4, (uint32_t)a.seg->segs.size());
+    };
     if (!ctx) {  // host-only AIR (no GPU needed): usable by ts_verify
         return guard(nullptr, [&] {
             auto a = std::make_unique<ts_air>();
             a->prog = ts::compile_air(tape, n_words);
+            plan(*a);
             *out = a.release();
         });
     }
@@ -717,6 +814,7 @@ ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_a
         auto a = std::make_unique<ts_air>();
         a->device = ctx->ctx.device;
         a->prog = ts::compile_air(tape, n_words);
+        plan(*a);
         a->code = ts::DevBuf<uint32_t>(&ctx->ctx, std::max<size_t>(a->prog.code.size(), 4));
         if (!a->prog.code.empty())
             TS_HIP(hipMemcpyAsync(a->code.p, a->prog.code.data(), a->prog.code.size() * 4,
@@ -726,18 +824,19 @@ ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_a
         // specialise the quotient kernel for this AIR (the interpreter runs it otherwise)
         a->arch = ctx->ctx.arch_name;
         const size_t n_instr = a->prog.code.size() / 4;
-        auto env_or = [](const char* name, size_t dflt) {
-            const char* v = getenv(name);
-            return v && *v ? (size_t)strtoull(v, nullptr, 10) : dflt;
-        };
         if (getenv("TS_NO_JIT")) {
             a->jit_log = "disabled by TS_NO_JIT";
+        } else if (a->seg) {
+            a->start_background_jit();  // always in the background: J children, or the cache
         } else if (n_instr <= env_or("TS_JIT_SYNC_INSTR", 2048)) {
             ts::JitKernel jk;
             const auto t0 = std::chrono::steady_clock::now();
             if (ts::jit_compile_quotient(a->prog, a->arch.c_str(), jk, a->jit_log)) {
-                a->prog.jit_module = jk.module;
-                a->prog.jit_fn = jk.fn;
+                auto ks = std::make_unique<ts::JitKernelSet>();
+                ks->modules = {jk.module};
+                ks->fns = {jk.fn};
+                a->kset = std::move(ks);
+                a->prog.jit.publish(a->kset.get());
                 a->jit_state = ts_air::JIT_LOADED;
             } else {
                 a->jit_state = ts_air::JIT_FAILED;
@@ -751,13 +850,19 @@ ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_a
         *out = a.release();
     });
 }
+ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out) {
+    return air_compile(ctx, tape, n_words, 0, 0, out);
+}
+ts_status ts_air_compile_opts(ts_ctx* ctx, const uint32_t* tape, size_t n_words, const ts_air_options* opt,
+                              ts_air** out) {
+    if (opt && (opt->struct_size != sizeof(ts_air_options) || opt->reserved != 0)) return TS_ERR_INVALID;
+    return air_compile(ctx, tape, n_words, opt ? opt->segment_instr : 0, opt ? std::min(opt->jit_jobs, 8u) : 0, out);
+}
 int ts_air_is_jit(const ts_air* air) {
     if (!air) return 0;
-    if (air->device >= 0 && air->job) {
-        (void)hipSetDevice(air->device);
-        const_cast<ts_air*>(air)->poll_jit(false);
-    }
-    return air->prog.jit_fn ? 1 : 0;
+    ts_air* a = const_cast<ts_air*>(air);
+    if (a->device >= 0) a->poll_jit(false);  // takes poll_m before it looks at the job; restores the device
+    return a->prog.jit.load() ? 1 : 0;
 }
 ts_status ts_air_jit_wait(ts_ctx* ctx, ts_air* air, int* state, double* compile_seconds) {
     if (!ctx || !air) return TS_ERR_INVALID;
@@ -794,10 +899,25 @@ ts_status ts_air_program(const ts_air* air, uint32_t* out, size_t cap_words, siz
     std::copy(p.const_public_idx.begin(), p.const_public_idx.end(), out + 3 + p.code.size() + nc);
     return TS_OK;
 }
+ts_status ts_air_segment_plan(const ts_air* air, uint32_t* out, size_t cap_words, size_t* n_words) {
+    if (!air || !n_words || !air->seg) return TS_ERR_INVALID;
+    const ts::SegmentPlan& sp = *air->seg;
+    std::vector<uint32_t> w = {sp.slab_width, (uint32_t)sp.segs.size()};
+    for (const auto& sg : sp.segs) {
+        w.insert(w.end(), {sg.begin, sg.end, (uint32_t)sg.live_in.size(), (uint32_t)sg.live_out.size(), sg.pressure});
+        for (const auto& v : sg.live_in) w.insert(w.end(), {v.def, v.slot});
+        for (const auto& v : sg.live_out) w.insert(w.end(), {v.def, v.slot});
+    }
+    *n_words = w.size();
+    if (!out || cap_words < w.size()) return TS_ERR_BUFFER;
+    std::copy(w.begin(), w.end(), out);
+    return TS_OK;
+}
 ts_status ts_air_jit_source(const ts_air* air, char* buf, size_t cap, size_t* n_bytes) {
     if (!air || !n_bytes) return TS_ERR_INVALID;
     return guard(nullptr, [&] {
-        const std::string src = ts::jit_quotient_source(air->prog);
+        const std::string src = air->seg ? ts::jit_segment_sources(air->prog, *air->seg, 1)[0]
+                                         : ts::jit_quotient_source(air->prog);
         *n_bytes = src.size();
         TS_REQUIRE(buf && cap >= src.size(), ts::TS_ERR_BUFFER, "jit source buffer too small");
         memcpy(buf, src.data(), src.size());
@@ -810,7 +930,8 @@ ts_status ts_air_jit_compile(const ts_air* air, const char* arch, void* code_out
         std::vector<char> code;
         std::string log;
         const auto t0 = std::chrono::steady_clock::now();
-        const bool ok = ts::jit_compile_code(air->prog, arch, code, log);
+        const bool ok = air->seg ? ts::jit_compile_source(ts::jit_segment_sources(air->prog, *air->seg, 1)[0], arch, code, log)
+                                 : ts::jit_compile_code(air->prog, arch, code, log);
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         TS_REQUIRE(ok, ts::TS_ERR_UNSUPPORTED, ("hiprtc: " + log).c_str());
         *n_bytes = code.size();

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <map>
 #include <string>
+#include <vector>
 
 #include "bb.hpp"
 #include "context.hpp"
@@ -181,6 +182,141 @@ AirProgram compile_air(const uint32_t* tape, size_t n_words) {
     }
     p.n_regs = std::max(next_reg, 1u);
     return p;
+}
+
+// ---- segment plan ------------------------------------------------------------------------------
+namespace {
+bool is_leaf(uint32_t op) { return op == D_LOAD || op == D_CONST || op == D_SEL; }
+bool is_computed(uint32_t op) { return op == D_ADD || op == D_SUB || op == D_NEG || op == D_MUL; }
+}  // namespace
+
+SegmentPlan plan_segments(const AirProgram& p, uint32_t S, uint32_t reg_budget) {
+    const uint32_t n = (uint32_t)(p.code.size() / 4);
+    TS_REQUIRE(S >= 1 && reg_budget >= 4, TS_ERR_INVALID, "segment plan: bad size or budget");
+    TS_REQUIRE(n <= SEG_MAX_INSTR, TS_ERR_INVALID, "segmented AIR: program above 2^20 lowered instructions");
+    SegmentPlan plan;
+    auto op_of = [&](uint32_t i) { return p.code[4 * i]; };
+    // SSA view of the register program: the defining instruction of every operand
+    plan.opdef.assign(2 * (size_t)n, ~0u);
+    std::vector<uint32_t> cur(p.n_regs, ~0u), last_use(n, 0);
+    std::vector<uint8_t> used(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t op = op_of(i), dst = p.code[4 * i + 1], a = p.code[4 * i + 2], b = p.code[4 * i + 3];
+        const int nops = (op == D_ADD || op == D_SUB || op == D_MUL) ? 2 : (op == D_NEG || op == D_ASSERT) ? 1 : 0;
+        const uint32_t regs[2] = {a, b};
+        for (int k = 0; k < nops; k++) {
+            const uint32_t v = cur[regs[k]];
+            TS_REQUIRE(v != ~0u, TS_ERR_INVARIANT, "segment plan: read of an unwritten register");
+            plan.opdef[2 * (size_t)i + k] = v;
+            last_use[v] = i;
+            used[v] = 1;
+        }
+        if (op != D_ASSERT) cur[dst] = i;
+    }
+    // cross[c]: computed values defined before instruction c and used at or after it (a cut before c)
+    std::vector<int64_t> cross(n + 2, 0);
+    for (uint32_t v = 0; v < n; v++)
+        if (is_computed(op_of(v)) && used[v] && last_use[v] > v) {
+            cross[v + 1]++;
+            cross[last_use[v] + 1]--;
+        }
+    for (uint32_t c = 1; c <= n; c++) cross[c] += cross[c - 1];
+
+    // values held at once by the kernel of [b, e): a value defined there lives from its definition to its
+    // last use there; one from an earlier segment (a slot load or a re-emitted leaf) from its first to its
+    // last use there
+    std::vector<uint32_t> stamp(n, ~0u), first_in(n, 0), last_in(n, 0);
+    std::vector<int32_t> diff(S + 2, 0);
+    uint32_t epoch = 0;
+    // `outs`: live-outs of [b, e) whose store waits (SegmentPlan::Slot::at) hold their value until then
+    auto pressure = [&](uint32_t b, uint32_t e, const std::vector<SegmentPlan::Slot>* outs = nullptr) -> uint32_t {
+        epoch++;
+        std::vector<uint32_t> touched;
+        auto touch = [&](uint32_t v, uint32_t i) {
+            if (stamp[v] != epoch) {
+                stamp[v] = epoch;
+                first_in[v] = v >= b ? v : i;
+                touched.push_back(v);
+            }
+            last_in[v] = i;
+        };
+        for (uint32_t i = b; i < e; i++) {
+            for (int k = 0; k < 2; k++)
+                if (plan.opdef[2 * (size_t)i + k] != ~0u) touch(plan.opdef[2 * (size_t)i + k], i);
+            if (op_of(i) != D_ASSERT) touch(i, i);
+        }
+        if (outs)
+            for (const auto& o : *outs) last_in[o.def] = std::max(last_in[o.def], o.at);
+        std::fill(diff.begin(), diff.begin() + (e - b) + 2, 0);
+        for (uint32_t v : touched) {
+            diff[first_in[v] - b]++;
+            diff[last_in[v] - b + 1]--;
+        }
+        int32_t run = 0, mx = 0;
+        for (uint32_t i = 0; i < e - b; i++) mx = std::max(mx, run += diff[i]);
+        return (uint32_t)mx;
+    };
+
+    uint32_t b = 0;
+    while (b < n) {
+        // the longest segment within S and the register budget (pressure grows with the end)
+        uint32_t lo = b + 1, hi = std::min(n, b + S);
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo + 1) / 2;
+            if (pressure(b, mid) <= reg_budget) lo = mid; else hi = mid - 1;
+        }
+        uint32_t e = lo;
+        if (e < n) {  // cut at the fewest crossing values in the second half of the window (latest on a tie)
+            const uint32_t w0 = b + std::max(1u, (e - b) / 2);
+            uint32_t best = e;
+            for (uint32_t c = e; c >= w0; c--)
+                if (cross[c] < cross[best]) best = c;
+            e = best;
+        }
+        SegmentPlan::Segment sg;
+        sg.begin = b;
+        sg.end = e;
+        plan.segs.push_back(std::move(sg));
+        b = e;
+    }
+
+    // slots: a live-out takes a free slot, else the slot of a value that dies in this segment once that value
+    // has been loaded (the store then waits for the load), else a new one.  The width is the most values
+    // crossing any one cut: when a new slot is opened, every slot in use holds a value that crosses the next cut.
+    std::vector<uint32_t> slot_of(n, ~0u), free_slots;
+    for (size_t k = 0; k < plan.segs.size(); k++) {
+        SegmentPlan::Segment& sg = plan.segs[k];
+        epoch++;
+        std::vector<std::pair<uint32_t, uint32_t>> dying;  // (load position, slot)
+        for (uint32_t i = sg.begin; i < sg.end; i++)
+            for (int q = 0; q < 2; q++) {
+                const uint32_t v = plan.opdef[2 * (size_t)i + q];
+                if (v == ~0u || v >= sg.begin || !is_computed(op_of(v)) || stamp[v] == epoch) continue;
+                stamp[v] = epoch;
+                sg.live_in.push_back({v, slot_of[v], i});
+                if (last_use[v] < sg.end) dying.push_back({i, slot_of[v]});
+            }
+        size_t dn = 0;  // dying is in load order already
+        for (uint32_t v = sg.begin; v < sg.end; v++) {
+            if (!is_computed(op_of(v)) || !used[v] || last_use[v] < sg.end) continue;
+            while (dn < dying.size() && dying[dn].first <= v) free_slots.push_back(dying[dn++].second);
+            uint32_t slot, at = v;
+            if (!free_slots.empty()) {
+                slot = free_slots.back();
+                free_slots.pop_back();
+            } else if (dn < dying.size()) {
+                at = dying[dn].first;
+                slot = dying[dn++].second;
+            } else {
+                slot = plan.slab_width++;
+            }
+            slot_of[v] = slot;
+            sg.live_out.push_back({v, slot, at});
+        }
+        while (dn < dying.size()) free_slots.push_back(dying[dn++].second);
+        sg.pressure = pressure(sg.begin, sg.end, &sg.live_out);
+    }
+    return plan;
 }
 
 }  // namespace ts

@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <vector>
 
 namespace ts {
@@ -32,6 +33,29 @@ enum DevOp : uint32_t {
     D_ASSERT = 7,   // acc += reg[a] * alpha_pow[b]   (b = constraint index)
 };
 
+// The hiprtc-specialised quotient kernels of one AIR (jit.cpp), built whole and then published once
+// (AirProgram::jit).  fns.size() == 1 and seg == nullptr: the monolithic k_quotient_jit; otherwise one
+// k_quotient_seg<k> per segment of *seg, launched in order over a slab (quotient.hip).
+struct SegmentPlan;
+struct JitKernelSet {
+    std::vector<void*> modules;
+    std::vector<void*> fns;
+    const SegmentPlan* seg = nullptr;
+};
+// A pointer that copies by value: readers load it once per launch (acquire); the owner stores it once,
+// after the modules are loaded (release).
+struct KernelSetRef {
+    std::atomic<const JitKernelSet*> p{nullptr};
+    KernelSetRef() = default;
+    KernelSetRef(const KernelSetRef& o) : p(o.p.load(std::memory_order_acquire)) {}
+    KernelSetRef& operator=(const KernelSetRef& o) {
+        p.store(o.p.load(std::memory_order_acquire), std::memory_order_release);
+        return *this;
+    }
+    const JitKernelSet* load() const { return p.load(std::memory_order_acquire); }
+    void publish(const JitKernelSet* k) { p.store(k, std::memory_order_release); }
+};
+
 struct AirProgram {
     uint32_t width = 0;
     uint32_t n_public = 0;
@@ -45,12 +69,40 @@ struct AirProgram {
     std::vector<uint32_t> tape;             // the validated input (kept for the verifier side)
     // device copy of `code`, owned by the context that compiled it
     uint32_t* d_code = nullptr;
-    // hiprtc-specialised quotient kernel (jit.cpp); null => the interpreter in quotient.hip is used
-    void* jit_module = nullptr;
-    void* jit_fn = nullptr;
+    // hiprtc-specialised quotient kernel(s) (jit.cpp); null => the interpreter in quotient.hip is used
+    KernelSetRef jit;
 };
 
 // throws ts::Error(TS_ERR_INVALID) on a malformed tape
 AirProgram compile_air(const uint32_t* tape, size_t n_words);
+
+// ---- segmented specialisation (opt-in, ts_air_compile_opts): the lowered program cut into segments of at
+// most S instructions, each its own kernel.  A computed value (ADD/SUB/NEG/MUL) defined in one segment and
+// used in a later one crosses through a slot of an explicit slab in HBM, [slot][row of the tile]; leaves
+// (LOAD/CONST/SEL) are never slotted but re-emitted where they are used.  Values are named by the index of
+// the instruction that defines them.  The four EF4 accumulators of the ASSERT sum cross every cut too, as
+// 8 words (lo, hi of a0..a3, after lazy_fix) in slab rows [slab_width, slab_width + 8).
+constexpr uint32_t SEG_MAX_INSTR = 1u << 20;  // programs above this are refused (TS_ERR_INVALID)
+constexpr uint32_t SEG_ACC_SLOTS = 8;
+struct SegmentPlan {
+    struct Slot {
+        uint32_t def;   // defining instruction
+        uint32_t slot;
+        uint32_t at;    // live-out: stored right after instruction `at` (>= def: after the load of the slot's
+                        // previous owner in this segment); live-in: loaded right before instruction `at`
+                        // (its first use in the segment)
+    };
+    struct Segment {
+        uint32_t begin = 0, end = 0;  // [begin, end) in lowered instructions
+        std::vector<Slot> live_in, live_out;
+        uint32_t pressure = 0;        // most values held at once in the segment (the kernel's live set)
+    };
+    uint32_t slab_width = 0;  // value slots: the most values live across any one cut
+    std::vector<Segment> segs;
+    // per instruction: the defining instructions of its operands a and b (~0u: not a register operand)
+    std::vector<uint32_t> opdef;
+};
+// `reg_budget`: the most values one segment may hold at once; a segment is shortened below S to respect it
+SegmentPlan plan_segments(const AirProgram& p, uint32_t S, uint32_t reg_budget);
 
 }  // namespace ts

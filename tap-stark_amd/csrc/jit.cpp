@@ -13,6 +13,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <sstream>
 
 namespace ts {
@@ -145,6 +146,114 @@ std::string jit_quotient_source(const AirProgram& air) {
     return s.str();
 }
 
+// ---- segmented form (air.hpp SegmentPlan): one kernel per segment, values crossing a cut go through the
+// slab as S[slot * slab_rows] (one u32 per row of the tile: coalesced), the accumulators as 8 words after
+// lazy_fix.  Values are named v<defining instruction>; a value from an earlier segment is materialised right
+// before its first use here (a slab load, or the leaf itself re-emitted).
+const char* kSegHead = R"SRC(
+extern "C" __global__ void __launch_bounds__(256, 4)
+k_quotient_seg%u(const u32* __restrict__ lde, u64 col_stride, unsigned log_n, unsigned log_qd,
+               const u32* __restrict__ C, const u32* __restrict__ AP, const u32* __restrict__ isf,
+               const u32* __restrict__ isl, const u32* __restrict__ ist, QC qc, QO out,
+               u32 row_begin, u32 row_end, u32* __restrict__ slab, u32 slab_rows) {
+    const unsigned L = log_n + log_qd;
+    const u32 total = 1u << L;
+    const u32 t = blockIdx.x * 256u + threadIdx.x;
+    const u32 r = row_begin + t;
+    if (r >= row_end) return;
+    const u32 i = L ? (__brev(r) >> (32 - L)) : 0u;
+    const u32 i_next = (i + (1u << log_qd)) & (total - 1u);
+    const u32 r_next = L ? (__brev(i_next) >> (32 - L)) : 0u;
+    const u32* __restrict__ row0 = lde + r;
+    const u32* __restrict__ row1 = lde + r_next;
+    const u32 sel0 = isf[r], sel1 = isl[r], sel2 = ist[r];
+    u32* __restrict__ S = slab + t;
+)SRC";
+
+static std::string seg_kernel(const AirProgram& air, const SegmentPlan& plan, uint32_t k) {
+    const SegmentPlan::Segment& sg = plan.segs[k];
+    const bool last = k + 1 == plan.segs.size();
+    const uint32_t W = plan.slab_width;
+    char head[2048];
+    snprintf(head, sizeof head, kSegHead, k);
+    std::ostringstream s;
+    s << head;
+    auto sl = [&](uint32_t slot) { return "S[" + std::to_string(slot) + "ull * slab_rows]"; };
+    if (k == 0) {
+        s << "    u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;\n";
+    } else {
+        for (int q = 0; q < 4; q++)
+            s << "    u64 a" << q << " = (u64)" << sl(W + 2 * q) << " | ((u64)" << sl(W + 2 * q + 1) << " << 32);\n";
+    }
+    std::vector<uint32_t> slot_in(air.code.size() / 4, ~0u);
+    for (const auto& li : sg.live_in) slot_in[li.def] = li.slot;
+    std::vector<std::vector<const SegmentPlan::Slot*>> stores(sg.end - sg.begin);
+    for (const auto& lo : sg.live_out) stores[lo.at - sg.begin].push_back(&lo);
+    std::vector<uint8_t> have(air.code.size() / 4, 0);
+    auto leaf = [&](uint32_t v) {
+        const uint32_t op = air.code[4 * v], a = air.code[4 * v + 2], b = air.code[4 * v + 3];
+        if (op == D_LOAD) return "to_mont(row" + std::to_string(a) + "[" + std::to_string(b) + "ull * col_stride])";
+        if (op == D_CONST) return "C[" + std::to_string(a) + "]";
+        return "sel" + std::to_string(a);  // D_SEL
+    };
+    uint32_t n_assert = 0;
+    for (uint32_t pc = sg.begin; pc < sg.end; pc++) {
+        const uint32_t op = air.code[4 * pc];
+        const uint32_t va = plan.opdef[2 * (size_t)pc], vb = plan.opdef[2 * (size_t)pc + 1];
+        for (uint32_t v : {va, vb}) {
+            if (v == ~0u || v >= sg.begin || have[v]) continue;
+            have[v] = 1;
+            s << "    const u32 v" << v << " = " << (slot_in[v] != ~0u ? sl(slot_in[v]) : leaf(v)) << ";\n";
+        }
+        switch (op) {
+            case D_LOAD: case D_CONST: case D_SEL: s << "    const u32 v" << pc << " = " << leaf(pc) << ";\n"; break;
+            case D_ADD: s << "    const u32 v" << pc << " = add(v" << va << ", v" << vb << ");\n"; break;
+            case D_SUB: s << "    const u32 v" << pc << " = sub(v" << va << ", v" << vb << ");\n"; break;
+            case D_NEG: s << "    const u32 v" << pc << " = neg(v" << va << ");\n"; break;
+            case D_MUL: s << "    const u32 v" << pc << " = mont_mul(v" << va << ", v" << vb << ");\n"; break;
+            default: {  // D_ASSERT
+                const uint32_t b = air.code[4 * pc + 3];
+                s << "    a0 += (u64)v" << va << " * AP[" << 4 * b << "]; a1 += (u64)v" << va << " * AP[" << 4 * b + 1
+                  << "]; a2 += (u64)v" << va << " * AP[" << 4 * b + 2 << "]; a3 += (u64)v" << va << " * AP["
+                  << 4 * b + 3 << "];\n";
+                if (++n_assert % 2 == 0)
+                    s << "    a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);\n";
+                break;
+            }
+        }
+        for (const SegmentPlan::Slot* st : stores[pc - sg.begin]) s << "    " << sl(st->slot) << " = v" << st->def << ";\n";
+    }
+    if (last) {
+        s << kEpilogue;
+    } else {  // lazy_fix first: the next segment starts from the overflow invariant of a fresh sum
+        s << "    a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);\n";
+        for (int q = 0; q < 4; q++)
+            s << "    " << sl(W + 2 * q) << " = (u32)a" << q << "; " << sl(W + 2 * q + 1) << " = (u32)(a" << q
+              << " >> 32);\n";
+        s << "}\n";
+    }
+    return s.str();
+}
+
+uint32_t jit_segment_module_first(const SegmentPlan& plan, uint32_t n_modules, uint32_t j) {
+    const uint64_t K = plan.segs.size();
+    return (uint32_t)(K * j / n_modules);
+}
+
+std::vector<std::string> jit_segment_sources(const AirProgram& air, const SegmentPlan& plan, uint32_t n_modules) {
+    n_modules = std::max(1u, std::min<uint32_t>(n_modules, (uint32_t)plan.segs.size()));
+    const std::string pre(kPrelude);
+    const std::string helpers = pre.substr(0, pre.find("extern \"C\""));
+    std::vector<std::string> out;
+    for (uint32_t j = 0; j < n_modules; j++) {
+        std::string src = helpers;
+        for (uint32_t k = jit_segment_module_first(plan, n_modules, j); k < jit_segment_module_first(plan, n_modules, j + 1); k++)
+            src += seg_kernel(air, plan, k);
+        out.push_back(std::move(src));
+    }
+    return out;
+}
+
 // ---- optional on-disk cache of code objects (TS_JIT_CACHE_DIR): the reference pays for `Air::eval` once, at
 // build time; a prover process that restarts should not pay hiprtc again for an AIR it has compiled before.
 // Key: 128 bits of FNV-1a over (generator version, hiprtc version, arch, source).
@@ -250,6 +359,27 @@ bool jit_compile_quotient(const AirProgram& air, const char* arch, JitKernel& ou
     std::vector<char> code;
     if (!jit_compile_code(air, arch, code, log)) return false;
     return jit_load_code(code, out, log);
+}
+
+bool jit_load_module(const std::vector<char>& code, const std::vector<std::string>& names, void*& module,
+                     std::vector<void*>& fns, std::string& log) {
+    hipModule_t mod = nullptr;
+    if (hipModuleLoadData(&mod, code.data()) != hipSuccess) {
+        log += " hipModuleLoadData failed";
+        return false;
+    }
+    fns.clear();
+    for (const std::string& name : names) {
+        hipFunction_t fn = nullptr;
+        if (hipModuleGetFunction(&fn, mod, name.c_str()) != hipSuccess) {
+            (void)hipModuleUnload(mod);
+            log += " hipModuleGetFunction(" + name + ") failed";
+            return false;
+        }
+        fns.push_back(fn);
+    }
+    module = mod;
+    return true;
 }
 
 bool jit_load_code(const std::vector<char>& code, JitKernel& out, std::string& log) {

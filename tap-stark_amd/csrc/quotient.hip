@@ -246,16 +246,38 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
                "quotient: row range");
     const uint64_t total = row_end - row_begin;  // rows to do
     uint32_t rb = (uint32_t)row_begin, re = (uint32_t)row_end;
-    if (air.jit_fn) {
+    const JitKernelSet* ks = air.jit.load();  // once per launch: published whole (air.hpp KernelSetRef)
+    const uint32_t* lde_p = trace_lde.d;
+    uint64_t stride = trace_lde.col_stride;
+    QuotOut qo = out;
+    if (ks && !ks->seg) {
         // specialised straight-line kernel (jit.cpp); same arguments, same results
-        const uint32_t* lde_p = trace_lde.d;
-        uint64_t stride = trace_lde.col_stride;
-        QuotOut qo = out;
         void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont,
                         &is_first, &is_last, &is_transition, &qc, &qo, &rb, &re};
         KernelTimer kt(&ctx, "k_quotient_jit");
-        TS_HIP(hipModuleLaunchKernel((hipFunction_t)air.jit_fn, (unsigned)((total + 255) / 256), 1, 1,
+        TS_HIP(hipModuleLaunchKernel((hipFunction_t)ks->fns[0], (unsigned)((total + 255) / 256), 1, 1,
                                      256, 1, 1, 0, ctx.stream, args, nullptr));
+        return;
+    }
+    if (ks) {
+        // segmented kernels (jit.cpp jit_segment_sources): per tile of rows, segments 0..K-1 in stream order,
+        // values crossing a cut in a slab of [slab_width + 8][tile_rows] words from the context's pool
+        const uint64_t width = (uint64_t)ks->seg->slab_width + SEG_ACC_SLOTS;
+        const uint64_t slab_mb = [] { const char* e = getenv("TS_SEG_SLAB_MB"); return e && *e ? (uint64_t)atoi(e) : (uint64_t)4096; }();
+        uint64_t tile = std::max<uint64_t>(256, ((slab_mb << 18) / width) & ~(uint64_t)255);
+        tile = std::min<uint64_t>(tile, (total + 255) & ~(uint64_t)255);
+        DevBuf<uint32_t> slab(&ctx, (size_t)(width * tile));
+        uint32_t* slab_p = slab.p;
+        uint32_t slab_rows = (uint32_t)tile;
+        KernelTimer kt(&ctx, "k_quotient_seg");
+        for (uint64_t t0 = row_begin; t0 < row_end; t0 += tile) {
+            uint32_t tb = (uint32_t)t0, te = (uint32_t)std::min<uint64_t>(row_end, t0 + tile);
+            void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
+                            &is_last, &is_transition, &qc, &qo, &tb, &te, &slab_p, &slab_rows};
+            const unsigned grid = (unsigned)((te - tb + 255) / 256);
+            for (void* fn : ks->fns)
+                TS_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 256, 1, 1, 0, ctx.stream, args, nullptr));
+        }
         return;
     }
     const RegFilePlan pl = plan_reg_file(ctx, air.n_regs, total);

@@ -5,6 +5,9 @@
 // the GPU (hiprtc only).
 //
 //     ts_jitc <arch> <source.hip> <out.co> <log.txt>        exit 0 = code object written
+//
+// The log is written last, on every path (empty if the compiler said nothing), and like the code object by
+// rename: a parent that could not reap the child (ECHILD) takes the log's presence for "ended".
 #include <dlfcn.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,9 +27,12 @@ static bool read_file(const char* path, std::string& out) {
     return true;
 }
 static void write_file(const char* path, const void* p, size_t n) {
-    if (FILE* f = fopen(path, "wb")) {
+    // write beside, then rename: the reader never sees a partial file
+    const std::string tmp = std::string(path) + ".part";
+    if (FILE* f = fopen(tmp.c_str(), "wb")) {
         fwrite(p, 1, n, f);
         fclose(f);
+        (void)rename(tmp.c_str(), path);
     }
 }
 
@@ -68,18 +74,18 @@ int main(int argc, char** argv) {
     const int rc = compile(prog, 2, opts);
     size_t sz = 0;
     log_size(prog, &sz);
-    if (sz > 1) {
-        std::vector<char> log(sz);
-        get_log(prog, log.data());
-        write_file(log_path, log.data(), sz - 1);
+    std::vector<char> log(sz > 1 ? sz : 1);
+    if (sz > 1) get_log(prog, log.data());
+    const size_t log_n = sz > 1 ? sz - 1 : 0;
+    if (rc != 0) {
+        write_file(log_path, log.data(), log_n);
+        return 1;
     }
-    if (rc != 0) return 1;
     code_size(prog, &sz);
     std::vector<char> code(sz);
     get_code(prog, code.data());
-    // write beside, then rename: the reader never sees a partial file
-    const std::string tmp = std::string(out_path) + ".part";
-    write_file(tmp.c_str(), code.data(), sz);
-    return rename(tmp.c_str(), out_path) == 0 ? 0 : 1;
+    write_file(out_path, code.data(), sz);
+    write_file(log_path, log.data(), log_n);
+    return 0;
     // (no hiprtcDestroyProgram / dlclose: the process ends here)
 }

@@ -230,14 +230,23 @@ class DeviceMatrix:
 
 
 class CompiledAir:
-    """``ts_air``.  With ``ctx=None`` the AIR is host-only (degree rules, ``verify``): no GPU."""
+    """``ts_air``.  With ``ctx=None`` the AIR is host-only (degree rules, ``verify``): no GPU.
 
-    def __init__(self, ctx: "Context | None", tape):
+    ``segment_instr=S`` (``ts_air_compile_opts``): a program longer than S lowered instructions gets the
+    segmented specialisation, compiled in the background by up to ``jit_jobs`` children (default 4, at most
+    8); ``None`` or 0 is the default route."""
+
+    def __init__(self, ctx: "Context | None", tape, segment_instr: int | None = None, jit_jobs: int | None = None):
         self.ctx = ctx
         self._l = _lib.lib()
         self.tape = _u32(tape)
         h = C.c_void_p()
-        rc = self._l.ts_air_compile(ctx.h if ctx else None, _p(self.tape), len(self.tape), C.byref(h))
+        if segment_instr is None and jit_jobs is None:
+            rc = self._l.ts_air_compile(ctx.h if ctx else None, _p(self.tape), len(self.tape), C.byref(h))
+        else:
+            opt = _lib.AirOptionsC(C.sizeof(_lib.AirOptionsC), int(segment_instr or 0), int(jit_jobs or 0), 0)
+            rc = self._l.ts_air_compile_opts(ctx.h if ctx else None, _p(self.tape), len(self.tape), C.byref(opt),
+                                             C.byref(h))
         if rc:
             msg = self._l.ts_last_error(ctx.h if ctx else None) or b""
             raise _lib.TsError(rc, msg.decode())
@@ -278,6 +287,30 @@ class CompiledAir:
         code = out[3:3 + 4 * n_instr].reshape(n_instr, 4)
         consts = out[3 + 4 * n_instr:3 + 4 * n_instr + n_consts]
         return {"n_regs": n_regs, "code": code, "consts": consts, "const_public": out[3 + 4 * n_instr + n_consts:]}
+
+    def segment_plan(self) -> dict:
+        """The plan of a segmented AIR (``ts_air_segment_plan``): ``slab_width`` and ``segments``, each a dict
+        of ``begin``, ``end``, ``pressure``, ``live_in`` and ``live_out`` as lists of (defining instruction,
+        slot).  TsError(TS_ERR_INVALID) for an AIR that is not segmented."""
+        n = C.c_size_t()
+        rc = self._l.ts_air_segment_plan(self.h, None, 0, C.byref(n))
+        if rc != 6:  # TS_ERR_BUFFER, with the size
+            raise _lib.TsError(rc, "ts_air_segment_plan: not a segmented AIR")
+        out = np.zeros(n.value, dtype=np.uint32)
+        rc = self._l.ts_air_segment_plan(self.h, _p(out), len(out), C.byref(n))
+        if rc:
+            raise _lib.TsError(rc, "ts_air_segment_plan")
+        w = out.tolist()
+        segs, k = [], 2
+        for _ in range(w[1]):
+            b, e, n_in, n_out, pr = w[k:k + 5]
+            k += 5
+            li = [tuple(w[k + 2 * j:k + 2 * j + 2]) for j in range(n_in)]
+            k += 2 * n_in
+            lo = [tuple(w[k + 2 * j:k + 2 * j + 2]) for j in range(n_out)]
+            k += 2 * n_out
+            segs.append({"begin": b, "end": e, "pressure": pr, "live_in": li, "live_out": lo})
+        return {"slab_width": w[0], "segments": segs}
 
     def jit_source(self) -> str:
         n = C.c_size_t()
