@@ -77,13 +77,12 @@ ts_status ts_ctx_set_replay(ts_ctx* ctx, int mode);
  * (resolved lazily, no sync per kernel); take writes "kernel=launches:total_ms;..." */
 ts_status ts_ctx_set_kernel_timing(ts_ctx* ctx, int enabled);
 ts_status ts_ctx_take_kernel_timings(ts_ctx* ctx, char* buf, size_t cap);
-/* TS_FRI_GRAPH knob (the FRI commit phase, fri/src/prover.rs:93-141, replayed as a hipGraph):
- * out[0] = commit phases replayed from a graph, out[1] = captures abandoned for the eager path
- * (an allocation the pool could not serve inside the capture), out[2] = shapes whose block sizes
- * are known, out[3] = bytes the context's device pool holds.  Diagnostics only. */
+/* out[3] = bytes the context's device pool holds.  out[0..2] counted the FRI commit phase's replays
+ * from a hipGraph, a measurement option that has been retired: they are always 0, kept so that the
+ * layout does not change.  Diagnostics only. */
 ts_status ts_ctx_graph_stats(ts_ctx* ctx, uint64_t out[4]);
-/* One diagnostic counter of the context by index: 0-3 as ts_ctx_graph_stats; 4 = graph attempts the
- * pool could not reserve for (the phase ran eagerly); 5 = ts_prove_sharded calls whose local quotient
+/* One diagnostic counter of the context by index: 0-3 as ts_ctx_graph_stats; 4 = always 0 (it counted
+ * refused reservations of the retired graph replay); 5 = ts_prove_sharded calls whose local quotient
  * (ts_shard_options.local_quotient) was redone through the broadcast path because FRI's final
  * polynomial was not constant, i.e. the trace was invalid (fri/src/prover.rs:129-134).
  * 6 / 7 / 8 = proof-of-work witnesses (fri/src/prover.rs:43) taken from the device search after the

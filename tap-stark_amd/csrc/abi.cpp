@@ -587,9 +587,7 @@ ts_status ts_ctx_take_kernel_timings(ts_ctx* ctx, char* buf, size_t cap) {
 
 ts_status ts_ctx_graph_stats(ts_ctx* ctx, uint64_t out[4]) {
     if (!ctx || !out) return TS_ERR_INVALID;
-    out[0] = ctx->ctx.fri_graph_replays;
-    out[1] = ctx->ctx.fri_graph_fallbacks;
-    out[2] = ctx->ctx.fri_graph_sizes.size();
+    out[0] = out[1] = out[2] = 0;  // the retired FRI graph replay's counters
     out[3] = ctx->ctx.bytes_reserved;
     return TS_OK;
 }
@@ -597,11 +595,8 @@ ts_status ts_ctx_graph_stats(ts_ctx* ctx, uint64_t out[4]) {
 ts_status ts_ctx_stat(ts_ctx* ctx, int which, uint64_t* out) {
     if (!ctx || !out) return TS_ERR_INVALID;
     switch (which) {
-    case 0: *out = ctx->ctx.fri_graph_replays; break;
-    case 1: *out = ctx->ctx.fri_graph_fallbacks; break;
-    case 2: *out = ctx->ctx.fri_graph_sizes.size(); break;
+    case 0: case 1: case 2: case 4: *out = 0; break;  // the retired FRI graph replay's counters
     case 3: *out = ctx->ctx.bytes_reserved; break;
-    case 4: *out = ctx->ctx.fri_graph_reserve_failures; break;
     case 5: *out = ctx->ctx.local_quotient_fallbacks; break;
     case 6: *out = ctx->ctx.pow_hints_accepted; break;
     case 7: *out = ctx->ctx.pow_hints_rejected; break;

@@ -138,30 +138,10 @@ struct Context {
     // name -> (launch count, total ms)
     std::map<std::string, std::pair<uint64_t, double>> take_kernel_timings();
 
-    // TS_FRI_GRAPH (prover.cpp): the instantiated graph of the FRI commit phase, updated per proof.
-    // A stream capture must not reach hipMalloc / hipFree / a stream sync, so while `capturing`:
-    // alloc() only serves from the free list and throws CaptureMiss otherwise (no HIP call made);
-    // free() parks the block in `deferred_free` (it stays live: nothing captured has run yet, and a
-    // fallback to the eager path may need the buffer's contents); stage() throws CaptureMiss instead
-    // of wrapping its arena.  `alloc_log`, when set, records every rounded size alloc() hands out:
-    // the first (eager) proof of a shape records what the commit phase needs, reserve() then makes
-    // the free list hold all of it at once before a capture starts.
-    struct CaptureMiss {};
-    hipGraphExec_t fri_graph_exec = nullptr;
-    bool capturing = false;
-    std::vector<void*> deferred_free;
-    std::vector<size_t>* alloc_log = nullptr;
-    std::map<std::vector<uint32_t>, std::vector<size_t>> fri_graph_sizes;  // shape key -> block sizes
-    uint64_t fri_graph_replays = 0, fri_graph_fallbacks = 0;
-    uint64_t fri_graph_reserve_failures = 0;  // Context::reserve refused: the phase ran eagerly
     // fri_pow_witness (prover.cpp): witnesses taken from the device search after the host's one-step check,
     // device candidates the host refused (never expected), and searches run on the host
     uint64_t pow_hints_accepted = 0, pow_hints_rejected = 0, pow_host_grinds = 0;
     uint64_t local_quotient_fallbacks = 0;    // prove_sharded: local quotient -> broadcast path (invalid trace)
-    bool reserve(const std::vector<size_t>& sizes);
-    // ends the deferral: blocks in `revive` stay live (returned: which of them had been parked),
-    // every other parked block goes back to the free list
-    std::vector<void*> flush_deferred(const std::vector<void*>& revive);
 
     explicit Context(int dev);
     ~Context();
@@ -186,24 +166,8 @@ struct Context {
     void d2h_point(void* host_dst, const void* dev_src, size_t bytes);  // an async copy + sync
     void* pinned(size_t bytes);
     void ensure_twiddles(unsigned log_size);
-    // The host's wait for the stream: hipStreamSynchronize puts the thread to sleep on an interrupt after a
-    // short spin, and the wake-up is the OS scheduler's business -- tens of microseconds normally, milliseconds
-    // now and then.  TS_SYNC_SPIN=1 polls hipStreamQuery instead (the thread has nothing else to do during
-    // the 0.1-0.5 ms it waits for; one core per context is busy while a proof runs).
-    void sync() {
-        static const int spin = [] { const char* e = getenv("TS_SYNC_SPIN"); return e ? atoi(e) : 0; }();
-        if (!spin) {
-            TS_HIP(hipStreamSynchronize(stream));
-            return;
-        }
-        hipError_t e;
-        while ((e = hipStreamQuery(stream)) == hipErrorNotReady) {
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        TS_HIP(e);
-    }
+    // (polling hipStreamQuery instead was measured and made no difference: profiles/r06_sync_spin_ab.txt)
+    void sync() { TS_HIP(hipStreamSynchronize(stream)); }
 };
 
 // RAII device buffer from the context's pool
@@ -214,12 +178,6 @@ struct DevBuf {
     size_t n = 0;
     DevBuf() = default;
     DevBuf(Context* c, size_t count) : ctx(c), p(c->alloc_n<T>(count)), n(count) {}
-    // takes over a block that is still live in the context's pool (Context::flush_deferred)
-    static DevBuf adopt(Context* c, T* ptr, size_t count) {
-        DevBuf b;
-        b.ctx = c; b.p = ptr; b.n = count;
-        return b;
-    }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     DevBuf(DevBuf&& o) noexcept : ctx(o.ctx), p(o.p), n(o.n) { o.p = nullptr; }

@@ -16,7 +16,8 @@
 namespace ts {
 
 // ROWS rows per thread (r, r + height/ROWS, ...): independent Blake3 chains in one thread give the
-// scheduler something to overlap with each chain's long dependency path
+// scheduler something to overlap with each chain's long dependency path.  Only ROWS = 1 is launched
+// (2 measured no better); the parameter keeps the kernel's name, which the profile tools key on.
 template <int ROWS>
 __global__ void __launch_bounds__(256)
 k_leaf_hash(const uint32_t* const* __restrict__ cols, uint32_t total, uint64_t height,
@@ -110,20 +111,9 @@ void launch_leaf_hash(Context& ctx, const LeafMats& mats, uint64_t height, uint3
         TS_HIP(hipGetLastError());
         return;
     }
-    static const int rows_per_thread = [] {
-        const char* e = getenv("TS_LEAF_ROWS");
-        return e ? atoi(e) : 1;
-    }();
-    static const int strided = [] {
-        const char* e = getenv("TS_LEAF_STRIDED");
-        return e ? atoi(e) : 1;
-    }();
-    if (strided && mats.n_mats == 1 && mats.d[0] != nullptr && mats.total_width >= 1) {
+    if (mats.n_mats == 1 && mats.d[0] != nullptr && mats.total_width >= 1) {
         TS_LAUNCH(ctx, k_leaf_hash_strided, dim3((unsigned)((height + 255) / 256)), dim3(256), 0, mats.d[0],
                   mats.col_stride[0], mats.total_width / 16, mats.total_width % 16, height, digests);
-    } else if (rows_per_thread == 2 && height % 2 == 0 && height >= (1u << 16)) {
-        TS_LAUNCH(ctx, k_leaf_hash<2>, dim3((unsigned)((height / 2 + 255) / 256)), dim3(256), 0, mats.cols,
-                  mats.total_width, height, digests);
     } else {
         TS_LAUNCH(ctx, k_leaf_hash<1>, dim3((unsigned)((height + 255) / 256)), dim3(256), 0, mats.cols,
                   mats.total_width, height, digests);
@@ -153,7 +143,8 @@ void launch_leaf_hash_ef_pairs(Context& ctx, const uint32_t* vec, uint64_t n_row
 }
 
 // one level: parents[i] = Blake3(children[2i] || children[2i+1]); PAR parents per thread
-// (i, i + n/PAR, ...: independent chains, as in k_leaf_hash)
+// (i, i + n/PAR, ...: independent chains, as in k_leaf_hash).  Only PAR = 1 is launched: two parents
+// per thread measured no better inside whole proofs (3.32 vs 3.27-3.33 ms/step).
 template <int PAR>
 __global__ void __launch_bounds__(256)
 k_merkle_level(const uint4* __restrict__ children, uint4* __restrict__ parents, uint64_t n_parents) {
@@ -185,18 +176,8 @@ k_merkle_level(const uint4* __restrict__ children, uint4* __restrict__ parents, 
 // per C3 proof: the access pattern is not what holds these launches at 2.8 TB/s; most of the 27 per
 // proof are short levels of 2^16..2^18 parents whose time is launch and tail latency.)
 static void launch_level(Context& ctx, const uint32_t* children, uint32_t* parents, uint64_t n_parents) {
-    static const int par = [] {
-        // two parents per thread measured no better inside whole proofs (3.32 vs 3.27-3.33 ms/step);
-        // like TS_LEAF_ROWS this stays a knob for experiments
-        const char* e = getenv("TS_LEVEL_PAR");
-        return e ? atoi(e) : 1;
-    }();
-    if (par == 2 && n_parents >= (1u << 18) && n_parents % 2 == 0)
-        TS_LAUNCH(ctx, k_merkle_level<2>, dim3((unsigned)((n_parents / 2 + 255) / 256)), dim3(256), 0,
-                  reinterpret_cast<const uint4*>(children), reinterpret_cast<uint4*>(parents), n_parents);
-    else
-        TS_LAUNCH(ctx, k_merkle_level<1>, dim3((unsigned)((n_parents + 255) / 256)), dim3(256), 0,
-                  reinterpret_cast<const uint4*>(children), reinterpret_cast<uint4*>(parents), n_parents);
+    TS_LAUNCH(ctx, k_merkle_level<1>, dim3((unsigned)((n_parents + 255) / 256)), dim3(256), 0,
+              reinterpret_cast<const uint4*>(children), reinterpret_cast<uint4*>(parents), n_parents);
 }
 
 void launch_merkle_one_level(Context& ctx, const uint32_t* children, uint32_t* parents,

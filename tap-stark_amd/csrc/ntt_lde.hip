@@ -17,14 +17,14 @@
 // SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.33 / 0.50 / 0.40 for the three big kernels,
 // profiles/r03_config3_sq_counters.txt -- lanes 0 and 31 of every 32-element run met on one bank.)
 // Three kernels:
-//   k_intt_contig    stages log_n-1 .. sA of the inverse on 4096-element chunks   (only n > 4096)
+//   k_intt_contig    stages log_n-1 .. sA of the inverse on 2^LM-element chunks   (only n > 2^LM)
 //   k_lde_mid        the strided stages of the inverse (sA-1 .. 0), then for every coset: scale
 //                    coefficient k by s_beta^k / n and run the strided stages of the forward
 //                    transform, writing coset block beta -- the coefficients never touch HBM
-//   k_lde_fwd_contig stages sA .. log_n-1 of the forward transform, in place on 4096-element chunks
+//   k_lde_fwd_contig stages sA .. log_n-1 of the forward transform, in place on 2^LM-element chunks
 // For n <= 4096 k_lde_mid alone does everything.
 //
-// The contiguous chunk is 2^LM elements, LM = 12 by default.  For n = 2^21 and 2^22 it grows to
+// The contiguous chunk is 2^LM elements, LM = 12 except for n = 2^21 and 2^22, where it grows to
 // 2^13 / 2^14 (LM = log_n - 8) so that the strided pass keeps the shape it has at n = 2^20 -- 8
 // strided stages on 256-row x 128-byte tiles, two 512-thread workgroups per CU, one LDS round per
 // coset (PLAN 1) -- instead of 9 / 10 stages on tiles whose rows are 64 bytes wide and whose
@@ -32,11 +32,6 @@
 // busy 0.67 with 44 % of its wave-cycles parked at barriers and scale-table loads).  The extra one
 // or two stages go to the contiguous passes as radix-32 register rounds (13 = 5+4+4, 14 = 5+5+4):
 // still three LDS round trips per chunk.
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <initializer_list>
-
 #include "kernels.hpp"
 
 namespace ts {
@@ -152,35 +147,6 @@ __device__ __forceinline__ void radix_round(uint32_t* s, unsigned log_total, uns
         for (int q = 0; q < R; q++) s[addr[q]] = v[q];
     }
     __syncthreads();
-}
-
-// Last forward round of a strided tile: groups read from the LDS, results written straight to the
-// tile's positions in HBM (element e of the tile lives at o[((e >> log_T) << row_shift) + (e & mask)]),
-// (values stay in [0, 2p): the contiguous forward pass follows).  A group's elements are 2^LOG_DL >= 2^log_T apart... and consecutive lanes hold
-// consecutive `lo`, so every store instruction writes whole 2^log_T-word row pieces, exactly like the
-// copy loop it replaces; no barrier is needed after it.
-template <int K, int LOG_DL, int NTH>
-__device__ __forceinline__ void radix_round_fwd_to_global(const uint32_t* s, unsigned log_total,
-                                                          unsigned u0, const uint32_t* __restrict__ W,
-                                                          uint32_t* __restrict__ o, unsigned log_T,
-                                                          unsigned row_shift) {
-    constexpr int R = 1 << K;
-    const uint32_t n_groups = 1u << (log_total - K);
-    const uint32_t tmask = (1u << log_T) - 1;
-    for (uint32_t g = threadIdx.x; g < n_groups; g += NTH) {
-        const uint32_t lo = g & ((1u << LOG_DL) - 1);
-        const uint32_t hi = g >> LOG_DL;
-        const uint32_t base = (hi << (K + LOG_DL)) + lo;
-        uint32_t v[R];
-#pragma unroll
-        for (int q = 0; q < R; q++) v[q] = s[pad(base + ((uint32_t)q << LOG_DL))];
-        radix_butterflies<K, false, false>(v, 0, u0, 0, hi, W);
-#pragma unroll
-        for (int q = 0; q < R; q++) {
-            const uint32_t e = base + ((uint32_t)q << LOG_DL);
-            o[((uint64_t)(e >> log_T) << row_shift) + (e & tmask)] = v[q];  // lazy: k_lde_fwd_contig reads it next
-        }
-    }
 }
 
 template <bool INV, int NTH>
@@ -400,8 +366,7 @@ k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned l
 // each coset: scaled copy -> forward stages 0 .. log_len-1 -> block beta of `out`.
 // PLAN 0: generic (runtime round plan).  PLAN 1: log_len = 8, log_T = 5 (n = 2^(LM + 8): 2^20 with
 // 4096-element chunks, 2^21 / 2^22 with LM = 13 / 14): two radix-16 rounds with compile-time
-// distances 2^9 and 2^5.  PLAN 2: log_len = 10 (n = 2^22), rounds of 4, 3
-// and 3 stages with compile-time distances; TILE elements per workgroup (log_T = log2(TILE) - 10).
+// distances 2^9 and 2^5.
 template <int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, int LM = LOG_M>
 __global__ void __launch_bounds__(NTM)
 k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* __restrict__ out,
@@ -411,14 +376,9 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
           const uint32_t* __restrict__ evals2, const uint32_t* __restrict__ scale_b, uint32_t gw) {
     __shared__ uint32_t s[padded(TILE)];
     constexpr int PER_THREAD = TILE / NTM;
-    constexpr int LOG_TILE = TILE == 8192 ? 13 : (TILE == 16384 ? 14 : 15);
     if (PLAN == 1) {
         log_len = 8;
         log_T = 5;
-    }
-    if (PLAN == 2) {
-        log_len = 10;
-        log_T = LOG_TILE - 10;
     }
     // Tiles narrower than 128 B (log_T < 5) share every cache line they touch with their neighbours:
     // neighbouring tiles go to workgroups of the same XCD (ids 8 apart), whose L2 then merges the
@@ -436,22 +396,6 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
         bx = (blockIdx.x & 31) + 32 * (blockIdx.x / (32 * ncols));  // < 2^(LM - 5)
         col_id = (blockIdx.x >> 5) % ncols;
     }
-    if constexpr (PLAN == 2) {
-        // 1-D grid, n_tiles x ncols workgroups.  The scale table of this shape (n x 2^log_blowup
-        // words: 268 MB for 2^22 rows at log_blowup 4) no longer fits the Infinity Cache; with a
-        // (tiles, columns) grid every column swept the whole table from HBM (rocprofv3 FETCH_SIZE:
-        // 20.5 GB per proof against 1.2 GB of coefficients, profiles/r02_config4_pmc_traffic.json).
-        // Order: workgroup ids go round the 8 XCDs; XCD x owns a contiguous range of tile PAIRS and,
-        // for each pair, runs (tile 2p, col), (tile 2p+1, col) for all columns in turn -- the pair's
-        // 2 MB of table stay in that XCD's L2 for every column, and the two 64-byte halves of every
-        // output line (neighbouring tiles) are still written back to back on one XCD.
-        const uint32_t n_tiles = (uint32_t)(1u << LOG_M) >> log_T;
-        const uint32_t ncols = gridDim.x / n_tiles;
-        const uint32_t x = blockIdx.x & 7, k = blockIdx.x >> 3;
-        const uint32_t pair_local = k / (2 * ncols), r = k % (2 * ncols);
-        col_id = r >> 1;
-        bx = (x * (n_tiles >> 4) + pair_local) * 2 + (r & 1);
-    }
     const uint32_t j2_0 = bx << log_T;
     // a two-matrix launch (coset_lde: evals2): columns gw .. come from the second matrix and take its
     // coset's scale table; the output columns follow each other either way
@@ -460,7 +404,7 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
     const uint32_t* __restrict__ scale = col_id < gw ? scale_a : scale_b;
     const uint32_t total = 1u << (log_len + log_T);
     const uint32_t tmask = (1u << log_T) - 1;
-    if constexpr (PLAN == 1 || PLAN == 2) {
+    if constexpr (PLAN == 1) {
         // fixed shape: PER_THREAD loads issued back to back (the generic loop below is a run-time
         // loop whose iterations the compiler keeps in order: load, wait, LDS store)
         uint32_t t[PER_THREAD];
@@ -480,10 +424,6 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
         radix_round<4, true, 5, NTM>(s, 13, 4, 0, 0, Winv);
         // the last inverse round (distance 2^9) works on elements tid + 512 q: exactly the share of
         // the tile this thread keeps as coefficients, so it runs in registers (below)
-    } else if (PLAN == 2) {
-        radix_round<3, true, LOG_TILE - 10, NTM>(s, LOG_TILE, 7, 0, 0, Winv);
-        radix_round<3, true, LOG_TILE - 7, NTM>(s, LOG_TILE, 4, 0, 0, Winv);
-        // last inverse round: in registers, as in PLAN 1 (below)
     } else {
         tile_inverse_rt<NTM>(s, log_len, log_T, 0, 0, Winv);
     }
@@ -494,11 +434,11 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
         const uint32_t i = threadIdx.x + (uint32_t)k * NTM;
         coef[k] = i < total ? s[pad(i)] : 0u;
     }
-    // PLAN 1 / 2: the radix-16 round at the largest distance (TILE/16) has TILE/16 groups, GP =
+    // PLAN 1: the radix-16 round at the largest distance (TILE/16) has TILE/16 groups, GP =
     // PER_THREAD/16 per thread, and group j of a thread is {tid + (j + GP q) NTM : q < 16}: its own
     // coefficients coef[j + GP q].  That round therefore runs in registers on either side.
     constexpr int GP = PER_THREAD / 16;
-    if constexpr (PLAN == 1 || PLAN == 2) {
+    if constexpr (PLAN == 1) {
 #pragma unroll
         for (int j = 0; j < GP; j++) {
             uint32_t v[16];
@@ -533,28 +473,20 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
         const uint32_t beta = beta0 + bl;
         const uint32_t* sc = scale + ((uint64_t)beta << log_n);  // s_beta^k / n, one entry per coefficient
         __syncthreads();
-        if constexpr (PLAN == 1 || PLAN == 2) {
+        if constexpr (PLAN == 1) {
             // scaled coefficients and the first forward round (the thread's own elements) stay in
             // registers; LDS is written once, for the following rounds
-            constexpr unsigned LT = PLAN == 1 ? 5 : LOG_TILE - 10;
 #pragma unroll
             for (int j = 0; j < GP; j++) {
                 uint32_t v[16];
+                // (lazy product: the butterflies that follow take [0, 2p) -- two instructions fewer
+                // per coefficient and coset)
 #pragma unroll
-                for (int q = 0; q < 16; q++) {
-                    const uint32_t i = threadIdx.x + (uint32_t)(j + GP * q) * NTM;
-                    const uint32_t kk = ((i >> LT) << LM) + (i & ((1u << LT) - 1)) + j2_0;
-                    // (lazy product: the butterflies that follow take [0, 2p) -- two instructions fewer
-                    // per coefficient and coset)
-                    if constexpr (PREFETCH) v[q] = mont_mul_lazy(coef[j + GP * q], scv[q]);
-                    else v[q] = mont_mul_lazy(coef[j + GP * q], sc[kk]);
-                }
-                if constexpr (PREFETCH) {
-                    if (bl + 1 < n_cosets) {
-                        const uint32_t* nx = scp + ((uint64_t)(beta + 1) << log_n);
+                for (int q = 0; q < 16; q++) v[q] = mont_mul_lazy(coef[j + GP * q], scv[q]);
+                if (bl + 1 < n_cosets) {
+                    const uint32_t* nx = scp + ((uint64_t)(beta + 1) << log_n);
 #pragma unroll
-                        for (int q = 0; q < 16; q++) scv[q] = nx[(uint64_t)q * (NTM >> 5) << LM];
-                    }
+                    for (int q = 0; q < 16; q++) scv[q] = nx[(uint64_t)q * (NTM >> 5) << LM];
                 }
                 radix_butterflies<4, false, true>(v, 0, 0, 0, 0, W);
 #pragma unroll
@@ -562,25 +494,20 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
             }
             __syncthreads();
             uint32_t* og = out + (uint64_t)col_id * out_col_stride + ((uint64_t)bl << log_n) + j2_0;
-            if constexpr (PLAN == 1) {
-                // (writing this round's results straight to HBM, as PLAN 2 does below: round 2 it needed
-                // 137 VGPRs -- one workgroup per CU -- and ran 0.85 ms against 0.64; since the scale
-                // prefetch simplified the addressing it fits in 123 and runs 0.584-0.591 ms per proof
-                // against 0.588-0.601: within the noise of whole proofs, so the LDS round stays)
-                radix_round<4, false, 5, NTM>(s, 13, 4, 0, 0, W);
-                // lazy values: k_lde_fwd_contig reads them next.  Unrolled: 16 LDS reads in flight, then
-                // 16 stores whose addresses differ by constants (as a run-time loop each iteration
-                // cost 7 VALU instructions and waited for its own LDS read)
-                uint32_t t[PER_THREAD];
+            // (writing this round's results straight to HBM from registers: round 2 it needed 137 VGPRs
+            // -- one workgroup per CU -- and ran 0.85 ms against 0.64; since the scale prefetch
+            // simplified the addressing it fits in 123 and runs 0.584-0.591 ms per proof against
+            // 0.588-0.601: within the noise of whole proofs, so the LDS round stays)
+            radix_round<4, false, 5, NTM>(s, 13, 4, 0, 0, W);
+            // lazy values: k_lde_fwd_contig reads them next.  Unrolled: 16 LDS reads in flight, then
+            // 16 stores whose addresses differ by constants (as a run-time loop each iteration
+            // cost 7 VALU instructions and waited for its own LDS read)
+            uint32_t t[PER_THREAD];
 #pragma unroll
-                for (int k = 0; k < PER_THREAD; k++) t[k] = s[pad(threadIdx.x + (uint32_t)k * NTM)];
-                uint32_t* ot = og + ((uint64_t)(threadIdx.x >> 5) << LM) + (threadIdx.x & 31);
+            for (int k = 0; k < PER_THREAD; k++) t[k] = s[pad(threadIdx.x + (uint32_t)k * NTM)];
+            uint32_t* ot = og + ((uint64_t)(threadIdx.x >> 5) << LM) + (threadIdx.x & 31);
 #pragma unroll
-                for (int k = 0; k < PER_THREAD; k++) ot[(uint64_t)k * (NTM >> 5) << LM] = t[k];
-            } else {
-                radix_round<3, false, LOG_TILE - 7, NTM>(s, LOG_TILE, 4, 0, 0, W);
-                radix_round_fwd_to_global<3, LOG_TILE - 10, NTM>(s, LOG_TILE, 7, W, og, LOG_TILE - 10, LOG_M);
-            }
+            for (int k = 0; k < PER_THREAD; k++) ot[(uint64_t)k * (NTM >> 5) << LM] = t[k];
             continue;  // stored; the barrier at the top of the loop protects the LDS image
         } else {
 #pragma unroll
@@ -607,56 +534,15 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
 }
 
 // ------------------------------------------------------------------ host driver
-// Tuning knobs of the LDE plans (A/B measurements; the defaults are what the tables in DESIGN.md were
-// measured with).  Parsed ONCE per process, strictly: a value outside a knob's list is reported on
-// stderr and ignored, so a typo cannot silently select another plan.
-//   TS_LDE_LM=12                 n = 2^21 / 2^22 with the 4096-element chunk plans of round 2
-//   TS_LDE_NO_FUSED_TRANSPOSE=1  transpose without the fused first inverse round
-//   TS_LDE_TILE=0|8192|16384|32768, TS_LDE_THREADS=512|1024   PLAN 2 tile / workgroup (with TS_LDE_LM=12)
-//   TS_LDE_FWD_CPW=1|2|4         chunks per workgroup of the 16384-element forward pass
-struct LdeKnobs {
-    int lm = 0;                   // 0 = default plan choice
-    bool no_fused_transpose = false;
-    int plan2_tile = 16384, plan2_threads = 1024, fwd_cpw = 4;
-};
-static int knob_int(const char* name, int dflt, std::initializer_list<int> allowed) {
-    const char* e = getenv(name);
-    if (!e) return dflt;
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    bool ok = end != e && *end == 0;
-    bool listed = false;
-    for (int a : allowed) listed = listed || a == v;
-    if (!ok || !listed) {
-        fprintf(stderr, "tapstark: %s=%s ignored (allowed:", name, e);
-        for (int a : allowed) fprintf(stderr, " %d", a);
-        fprintf(stderr, "); using %d\n", dflt);
-        return dflt;
-    }
-    return (int)v;
-}
-static const LdeKnobs& lde_knobs() {
-    static const LdeKnobs k = [] {
-        LdeKnobs x;
-        x.lm = knob_int("TS_LDE_LM", 0, {12});
-        x.no_fused_transpose = knob_int("TS_LDE_NO_FUSED_TRANSPOSE", 0, {0, 1}) != 0;
-        x.plan2_tile = knob_int("TS_LDE_TILE", 16384, {0, 8192, 16384, 32768});
-        x.plan2_threads = knob_int("TS_LDE_THREADS", 1024, {512, 1024});
-        x.fwd_cpw = knob_int("TS_LDE_FWD_CPW", 4, {1, 2, 4});
-        return x;
-    }();
-    return k;
-}
-
 // chunk size of the contiguous passes: 2^12, or log_n - 8 for n = 2^21 / 2^22 (header comment).
 // The one place that decides it: the fused transpose and coset_lde both ask here.
 static unsigned lde_chunk_log(unsigned log_n) {
-    return ((log_n == 21 || log_n == 22) && lde_knobs().lm != 12) ? log_n - 8 : (unsigned)LOG_M;
+    return (log_n == 21 || log_n == 22) ? log_n - 8 : (unsigned)LOG_M;
 }
 
 bool launch_transpose_bitrev_r16(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_n, uint32_t w,
                                  uint64_t dst_col_stride, uint32_t src_width) {
-    if (lde_knobs().no_fused_transpose || w == 0 || log_n <= lde_chunk_log(log_n)) return false;  // no contiguous inverse pass to shorten
+    if (w == 0 || log_n <= lde_chunk_log(log_n)) return false;  // no contiguous inverse pass to shorten
     ctx.ensure_twiddles(log_n);
     TS_LAUNCH(ctx, k_transpose_bitrev_r16, dim3(1u << (log_n - 6), (w + 63) / 64), dim3(256), 0, src, dst, log_n, w,
               dst_col_stride, src_width ? src_width : w, (const uint32_t*)ctx.d_twiddle_inv);
@@ -685,16 +571,8 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
     const uint32_t* W = ctx.d_twiddle_fwd;
     const uint32_t* Winv = ctx.d_twiddle_inv;
     unsigned log_T = 0;
-    // PLAN 2 tile (TS_LDE_TILE).  Measured on 2^22 x 64, log_blowup 4 (ms per launch): generic 19.1,
-    // 8192 15.7, 16384 13.8, 32768 30.3 (one workgroup per CU); with the register-resident outer rounds
-    // and the last round stored straight to HBM 16384 went 13.8 -> 11.7, and to 11.1 with 1024 threads
-    // (TS_LDE_THREADS: 114 VGPRs, 16 waves per CU; 512 threads: 191 VGPRs, 8 waves)
-    const int plan2_tile = lde_knobs().plan2_tile, plan2_threads = lde_knobs().plan2_threads;
-    const bool plan2 = two_pass && sA == 10 && plan2_tile != 0;
-    if (two_pass && sA <= 13) {
+    if (two_pass && sA <= 13)
         while ((1u << (sA + log_T + 1)) <= (unsigned)TILE_ELEMS && log_T < 6) log_T++;
-        if (plan2) log_T = plan2_tile == 8192 ? 3 : (plan2_tile == 16384 ? 4 : 5);
-    }
 
     // per-coset scale table s_beta^k / n (cached per context: the trace's is the same every proof)
     const uint32_t n_cosets = 1u << log_blowup;
@@ -729,21 +607,13 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
         }
         StageTimer t_rest(&ctx, "lde: strided pass + forward NTT of the owned cosets");
         const dim3 grid(1u << (LM - log_T), ncols);
-        const dim3 grid1((1u << (LM - log_T)) * ncols);  // PLAN 1 / 2: 1-D, see the kernel
+        const dim3 grid1((1u << (LM - log_T)) * ncols);  // PLAN 1: 1-D, see the kernel
 #define TS_MID_ARGS                                                                            \
     (const uint32_t*)evals, in_col_stride, out, out_col_stride, log_n, sA, log_T, (unsigned)LM, \
         beta0, n_beta, W, Winv, scale, (const uint32_t*)evals2, scale2, gw
         if (!(ctx.lde_pass_mask & 2u)) {
         } else if (sA == 14)
             TS_LAUNCH(ctx, (k_lde_mid<0, 16384>), grid, dim3(NT_MID), 0, TS_MID_ARGS);
-        else if (plan2 && plan2_tile == 8192)
-            TS_LAUNCH(ctx, (k_lde_mid<2, 8192>), grid1, dim3(NT_MID), 0, TS_MID_ARGS);
-        else if (plan2 && plan2_tile == 16384 && plan2_threads == 1024)
-            TS_LAUNCH(ctx, (k_lde_mid<2, 16384, 1024>), grid1, dim3(1024), 0, TS_MID_ARGS);
-        else if (plan2 && plan2_tile == 16384)
-            TS_LAUNCH(ctx, (k_lde_mid<2, 16384>), grid1, dim3(NT_MID), 0, TS_MID_ARGS);
-        else if (plan2)
-            TS_LAUNCH(ctx, (k_lde_mid<2, 32768, 1024>), grid1, dim3(1024), 0, TS_MID_ARGS);
         else if (sA == 8 && log_T == 5 && LM == 12)
             TS_LAUNCH(ctx, k_lde_mid<1>, grid1, dim3(NT_MID), 0, TS_MID_ARGS);
         else if (sA == 8 && log_T == 5 && LM == 13)
@@ -753,19 +623,13 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
         else
             TS_LAUNCH(ctx, k_lde_mid<0>, grid, dim3(NT_MID), 0, TS_MID_ARGS);
         const dim3 gf(1u << sA, ncols, n_beta);
-        // chunks per workgroup of the 16384-element forward pass: measured 12.49 (1) / 13.34 (2: spills) /
-        // 12.22 ms (4) per proof
-        const int fwd_cpw = lde_knobs().fwd_cpw;
+        // 4 chunks per workgroup of the 16384-element forward pass: measured 12.22 ms per proof against
+        // 12.49 with 1 and 13.34 with 2 (spills)
         if (!(ctx.lde_pass_mask & 4u)) {
         } else if (LM == 12)
             TS_LAUNCH(ctx, k_lde_fwd_contig<12>, gf, dim3(chunk_threads(12)), 0, out, out_col_stride, log_n, W);
         else if (LM == 13)
             TS_LAUNCH(ctx, k_lde_fwd_contig<13>, gf, dim3(chunk_threads(13)), 0, out, out_col_stride, log_n, W);
-        else if (fwd_cpw == 1)
-            TS_LAUNCH(ctx, k_lde_fwd_contig<14>, gf, dim3(chunk_threads(14)), 0, out, out_col_stride, log_n, W);
-        else if (fwd_cpw == 2)
-            TS_LAUNCH(ctx, (k_lde_fwd_contig<14, 2>), dim3(gf.x / 2, gf.y, gf.z), dim3(chunk_threads(14)), 0, out,
-                      out_col_stride, log_n, W);
         else
             TS_LAUNCH(ctx, (k_lde_fwd_contig<14, 4>), dim3(gf.x / 4, gf.y, gf.z), dim3(chunk_threads(14)), 0, out,
                       out_col_stride, log_n, W);

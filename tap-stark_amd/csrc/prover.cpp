@@ -110,8 +110,6 @@ void mmcs_commit(Context& ctx, PcsData& data) {
                                  cm.d == first->d + (uint64_t)wsum * first->col_stride;
                     wsum += cm.width;
                 }
-            static const bool strided_knob = [] { const char* e = getenv("TS_LEAF_STRIDED"); return !e || atoi(e) != 0; }();
-            if (!strided_knob) upload_table();  // TS_LEAF_STRIDED=0 sends even one matrix through the table kernels
             if (first && contiguous && wsum >= 1 && wsum <= 256) {
                 lm.n_mats = 1;
                 lm.d[0] = first->d;
@@ -129,8 +127,7 @@ void mmcs_commit(Context& ctx, PcsData& data) {
         if (uniform) {  // leaves and every level in one launch (leaf_tree.hpp)
             // the kernel that makes the root writes it into the context's mailbox (host memory) as well:
             // no copy kernel between the tree and the host's next transcript step
-            static const bool no_mail = [] { const char* e = getenv("TS_NO_MAILBOX"); return e && atoi(e) != 0; }();
-            if (log_H >= 1 && !no_mail) mail = ctx.mailbox(8);
+            if (log_H >= 1) mail = ctx.mailbox(8);
             launch_commit_tree(ctx, group_mats(groups[0]), log_H, data.tree.p, nullptr, mail, nullptr);
         } else {
             group_leaves(groups[0], data.tree.p);
@@ -699,111 +696,7 @@ void TwoAdicFriPcs::fri_prove(std::vector<DevBuf<Ef>>& inputs, const std::vector
     {
         StageTimer t(&ctx, "FRI commit phase");
         fri_commit_begin(ctx, fri, log_max_height, challenger, st);
-        DevBuf<Ef> first = std::move(inputs[0]);
-        // TS_FRI_GRAPH=1 (measurement knob, DESIGN.md "hipGraph"): the commit phase -- the launch-bound
-        // loop of the path, ~20 dependent launches with no host interaction -- is captured into a
-        // hipGraph and replayed; the instantiated graph is kept per context and updated in place
-        // (hipGraphExecUpdate) when a proof of the same shape comes with other buffer addresses.
-        // A capture cannot hipMalloc, so: the first proof of a SHAPE (log_blowup + every input height:
-        // what the block sizes depend on) runs eagerly and records the sizes the phase allocates;
-        // before a capture the pool is made to hold all of them at once (Context::reserve); and an
-        // allocation that still misses inside the capture (Context::CaptureMiss: no HIP call was made)
-        // ends the capture and re-runs the phase eagerly from the untouched inputs.
-        // TS_FRI_GRAPH=2 skips the reservation: the test hook that exercises that fall-back; =3 treats the
-        // replay as failed after a good capture (instantiate / launch failure: the same fall-back).
-        const char* genv = getenv("TS_FRI_GRAPH");
-        const int want_graph = (genv && !ctx.timing && !ctx.kernel_timing) ? atoi(genv) : 0;
-        const uint64_t len0 = 1ull << log_max_height;
-        bool done = false;
-        if (want_graph) {
-            std::vector<uint32_t> key{fri.log_blowup};
-            for (unsigned l : log_lens) key.push_back(l);
-            auto known = ctx.fri_graph_sizes.find(key);
-            if (known == ctx.fri_graph_sizes.end()) {  // first proof of this shape: eager, recording
-                std::vector<size_t> sizes;
-                ctx.alloc_log = &sizes;
-                try {
-                    fri_commit_rounds(ctx, fri, std::move(first), len0, inputs, log_lens, 1, st);
-                } catch (...) {
-                    ctx.alloc_log = nullptr;
-                    throw;
-                }
-                ctx.alloc_log = nullptr;
-                ctx.fri_graph_sizes[key] = std::move(sizes);
-                done = true;
-            } else if (want_graph != 2 && !ctx.reserve(known->second)) {
-                ctx.fri_graph_reserve_failures++;  // hipMalloc refused the reservation: eager, and on the record
-            } else {
-                hipGraph_t g = nullptr;
-                bool miss = false;
-                TS_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeThreadLocal));
-                ctx.capturing = true;
-                try {
-                    fri_commit_rounds(ctx, fri, std::move(first), len0, inputs, log_lens, 1, st);
-                } catch (Context::CaptureMiss&) {
-                    miss = true;
-                } catch (...) {
-                    (void)hipStreamEndCapture(ctx.stream, &g);
-                    if (g) (void)hipGraphDestroy(g);
-                    ctx.capturing = false;
-                    ctx.flush_deferred({});
-                    throw;
-                }
-                const hipError_t ec = hipStreamEndCapture(ctx.stream, &g);
-                // Nothing captured has run yet.  A capture miss, a failed end-of-capture, and a graph
-                // that cannot be instantiated / updated / launched (e.g. out of memory on a new shape)
-                // all take the same way out: drop the graph and the half-built round state while frees
-                // are still parked, take the input vectors back (the rounds had moved some of them into
-                // the state), return every other parked block to the pool, then run eagerly.
-                bool replayed = false;
-                if (!miss && ec == hipSuccess) {
-                    bool ready = false;
-                    if (ctx.fri_graph_exec) {
-                        hipGraphNode_t err_node = nullptr;
-                        hipGraphExecUpdateResult res;
-                        ready = hipGraphExecUpdate(ctx.fri_graph_exec, g, &err_node, &res) == hipSuccess &&
-                                res == hipGraphExecUpdateSuccess;
-                        if (!ready) {
-                            (void)hipGetLastError();
-                            (void)hipGraphExecDestroy(ctx.fri_graph_exec);
-                            ctx.fri_graph_exec = nullptr;
-                        }
-                    }
-                    if (!ready) {
-                        ready = hipGraphInstantiate(&ctx.fri_graph_exec, g, nullptr, nullptr, 0) == hipSuccess;
-                        if (!ready) ctx.fri_graph_exec = nullptr;
-                    }
-                    // TS_FRI_GRAPH=3: the test hook for this branch (pretend the launch failed)
-                    if (ready && want_graph != 3)
-                        replayed = hipGraphLaunch(ctx.fri_graph_exec, ctx.stream) == hipSuccess;
-                }
-                if (g) (void)hipGraphDestroy(g);
-                if (replayed) {
-                    ctx.capturing = false;
-                    ctx.flush_deferred({});
-                    ctx.fri_graph_replays++;
-                    done = true;
-                } else {
-                    (void)hipGetLastError();
-                    st.rounds.clear();
-                    st.keep_vecs.clear();
-                    st.keep_trees.clear();
-                    std::vector<void*> mine;
-                    for (const Ef* q : in_ptr) mine.push_back(const_cast<Ef*>(q));
-                    ctx.capturing = false;
-                    const std::vector<void*> back = ctx.flush_deferred(mine);
-                    for (void* q : back)
-                        for (size_t k = 0; k < in_ptr.size(); k++)
-                            if (q == (const void*)in_ptr[k]) {
-                                DevBuf<Ef> b = DevBuf<Ef>::adopt(&ctx, static_cast<Ef*>(q), 1ull << log_lens[k]);
-                                if (k == 0) first = std::move(b);
-                                else inputs[k] = std::move(b);
-                            }
-                    ctx.fri_graph_fallbacks++;
-                }
-            }
-        }
-        if (!done) fri_commit_rounds(ctx, fri, std::move(first), len0, inputs, log_lens, 1, st);
+        fri_commit_rounds(ctx, fri, std::move(inputs[0]), 1ull << log_max_height, inputs, log_lens, 1, st);
         final_poly = fri_commit_finish(ctx, fri, challenger, st);
     }
     std::vector<FriRound>& rounds = st.rounds;

@@ -101,14 +101,16 @@ class Context:
         return out
 
     def graph_stats(self) -> dict:
-        """TS_FRI_GRAPH diagnostics (``ts_ctx_graph_stats``)."""
+        """``ts_ctx_graph_stats``: ``pool_bytes`` = bytes the device pool holds.  The other four counted
+        the retired hipGraph replay of the FRI commit phase and are always 0."""
         out = (C.c_uint64 * 4)()
         self.check(self._l.ts_ctx_graph_stats(self.h, out))
         return {"replays": int(out[0]), "fallbacks": int(out[1]), "shapes": int(out[2]),
                 "pool_bytes": int(out[3]), "reserve_failures": self.stat(4)}
 
     def stat(self, which: int) -> int:
-        """``ts_ctx_stat``: 0-3 as graph_stats, 4 graph reservations refused, 5 local-quotient fall-backs."""
+        """``ts_ctx_stat``: 3 pool bytes, 5 local-quotient fall-backs, 6-8 proof-of-work witness counters;
+        0, 1, 2 and 4 (the retired graph replay's counters) are always 0."""
         v = C.c_uint64()
         self.check(self._l.ts_ctx_stat(self.h, which, C.byref(v)))
         return int(v.value)

@@ -823,3 +823,34 @@ def test_prove_stream_is_prove_on_several_lanes(ctx, orc):
     # nothing to do is not an error
     proof, start, wall = ts.prove_stream(lanes, [], [], [])
     assert len(proof.words) == 0 and len(start) == 0
+
+
+@pytest.mark.parametrize("log_n", [16, 20])
+def test_one_context_alternating_shapes(ctx, log_n):
+    # config-3-shaped proofs, then config-2-shaped ones, then back, on ONE context (the same
+    # log_max_height and input count: round 3 once failed with TS_ERR_OOM at the first config-2-shaped
+    # proof after config-3-shaped ones), then another blowup on the same context.  Every proof equals
+    # the one from a fresh context.
+    ref_ctx = ts.Context(0)
+    fib = generate_fibonacci_trace(0, 1, 1 << log_n)
+    cases = [("mul64", SynthMulAir(64), generate_synth_mul_trace(1 << log_n), np.zeros(0, dtype=np.uint32)),
+             ("fib", FibonacciAir(), fib, fibonacci_public_values(fib))]
+    cfg = (2, 28, 8)
+    want = {}
+    for name, air, trace, pis in cases:
+        conf = ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(*cfg), ref_ctx))
+        want[name] = ts.prove(conf, air, ts.BfChallenger(), trace.copy(), pis).words
+    one = ts.Context(0)
+    conf = ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(*cfg), one))
+    for name, air, trace, pis in [cases[0]] * 3 + [cases[1]] * 3 + [cases[0]] * 2 + [cases[1]]:
+        got = ts.prove(conf, air, ts.BfChallenger(), trace.copy(), pis).words
+        assert len(got) == len(want[name]) and (got == want[name]).all(), f"{name}: proof differs"
+    air, trace = SynthMulAir(64), generate_synth_mul_trace(1 << 10)
+    pis = np.zeros(0, dtype=np.uint32)
+    w3 = ts.prove(ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(3, 9, 8), ref_ctx)), air, ts.BfChallenger(),
+                  trace.copy(), pis).words
+    conf3 = ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(3, 9, 8), one))
+    for _ in range(3):
+        assert (ts.prove(conf3, air, ts.BfChallenger(), trace.copy(), pis).words == w3).all()
+    one.close()
+    ref_ctx.close()

@@ -1,6 +1,6 @@
 """Single-proof latency (wall clock around ts_prove, one proof alone on the GPU) of configs 3 and 2: median / min /
-p90 / max of N proofs.  Settings that are read once per process (TS_SYNC_SPIN ...) are compared by running this
-in separate processes, alternating (tools/ab_sync_spin.sh).   python tools/latency_simple.py [n=40]"""
+p90 / max of N proofs.  Settings that are read once per process are compared by running this in separate
+processes, alternating.   python tools/latency_simple.py [n=40]"""
 import os
 import sys
 import time
@@ -31,4 +31,4 @@ for name in ("config3", "config2"):
         lat.append(1e3 * (time.perf_counter() - t0))
     lat.sort()
     out.append(f"{name}: median {lat[n // 2]:.3f} min {lat[0]:.3f} p90 {lat[int(0.9 * n)]:.3f} max {lat[-1]:.3f}")
-print(f"TS_SYNC_SPIN={os.environ.get('TS_SYNC_SPIN', '0')}  " + "   ".join(out), flush=True)
+print("   ".join(out), flush=True)

@@ -5,8 +5,7 @@
 # tools/profile_collect.py: bench lines (driver protocol for config 3; configs 2, 4, 5; the 2-rank
 # shared-GPU rehearsal of --gpus 2 with both sharded blocks), rocprofv3 kernel-trace stats for configs
 # 2-5, SQ counters and FETCH_SIZE / WRITE_SIZE passes for configs 3 and 4 (counters only, separate
-# passes), the turn-taking shard-stage tables of configs 4 and 5, the TS_FRI_GRAPH latency A/B, the
-# reference's fold benchmark.
+# passes), the turn-taking shard-stage tables of configs 4 and 5, the reference's fold benchmark.
 set -e
 set -o pipefail
 TAG=${1:-r06}
@@ -27,7 +26,6 @@ echo "benches done"
 python3 tools/shard_stages.py config4 8 > $O/config4_shard_stages.json 2>> $O/bench.err
 python3 tools/shard_stages.py config5 8 replicated localq > $O/config5_shard_stages.json 2>> $O/bench.err
 echo "shard stages done"
-{ python3 tools/latency.py; python3 tools/latency.py; } 2>> $O/bench.err | grep -v amdgpu.ids > $O/fri_hipgraph_latency.txt
 if [ -f tap-stark_amd/lib_diag/libtapstark_hip.so ]; then  # python -m tapstark_amd.build -DTS_TAIL_STAMPS
   TS_LIB_PATH=tap-stark_amd/lib_diag/libtapstark_hip.so python3 tools/tail_stamps.py 2>> $O/bench.err | grep -v amdgpu.ids > $O/chain_stamps.txt
 fi
