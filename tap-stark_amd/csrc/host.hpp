@@ -81,8 +81,17 @@ struct PcsData {
     DevBuf<const uint32_t*> col_table;  // one base pointer per column of the concatenated row
     bool col_table_uploaded = false;    // mmcs_commit uploads it only for the table-addressed leaf kernels
     uint32_t root[8] = {0};
+    // cols == nullptr unless the table was uploaded: readers of a strided-committed batch use d[] / col_stride
     LeafMats leaf_mats() const;
+    // the same with the table: uploads it (one copy on the stream) if nothing has yet
+    LeafMats leaf_mats_with_table(Context& ctx);
 };
+// base pointer of every column of `ldes` in commit order; height != 0: of the matrices of that height only
+std::vector<const uint32_t*> column_pointers(const std::vector<ColMat>& ldes, uint64_t height = 0);
+// The matrices of `height` lie back to back with one stride (lde_stage stores a batch that way), so ONE
+// matrix of the summed width describes them -- if that width is at most max_width (0: no limit; the
+// strided leaf kernels take rows of up to 256 elements).  False otherwise.
+bool columns_as_one_matrix(const std::vector<ColMat>& ldes, uint64_t height, uint32_t max_width, ColMat& one);
 
 unsigned log2_strict(uint64_t n);  // throws TS_ERR_INVALID unless n is a power of two
 

@@ -12,53 +12,9 @@
 
 #include <algorithm>
 
-#include "fri_internal.hpp"
+#include "prover_internal.hpp"
 
 namespace ts {
-
-// small uploads go through the context's page-locked arena: truly asynchronous, and the caller's
-// buffer (a stack temporary, a vector about to die) is free as soon as this returns
-// (uploads above 1 MiB -- lock-script tables, script blobs -- go straight from the caller's buffer,
-// which the caller keeps alive until its next blocking call)
-void h2d(Context& ctx, void* dst, const void* src, size_t bytes) {
-    if (!bytes) return;
-    const void* from = bytes <= (1u << 20) ? ctx.stage(src, bytes) : src;
-    TS_HIP(hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, ctx.stream));
-}
-void d2h_sync(Context& ctx, void* dst, const void* src, size_t bytes) {
-    if (bytes) TS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx.stream));
-    ctx.sync();
-}
-
-unsigned log2_strict(uint64_t n) {
-    unsigned k = 0;
-    while ((1ull << k) < n) k++;
-    TS_REQUIRE((1ull << k) == n, TS_ERR_INVALID, "height must be a power of two");
-    return k;
-}
-
-// canonical-domain EF helpers for the handful of host-side scalars
-Ef efc_mul(Ef a, Ef b) { return ef_mul(a, ef_to_mont(b)); }
-Ef efc_mul_base(Ef a, uint32_t b) { return ef_mul_base(a, to_mont(b)); }
-Ef efc_pow(Ef a, uint64_t e) { return ef_from_mont(ef_pow(ef_to_mont(a), e)); }
-Ef efc_one() { return Ef{{1, 0, 0, 0}}; }
-
-LeafMats PcsData::leaf_mats() const {
-    LeafMats lm;
-    memset(&lm, 0, sizeof lm);
-    lm.n_mats = (uint32_t)ldes.size();
-    for (size_t i = 0; i < ldes.size(); i++) {
-        lm.d[i] = ldes[i].d;
-        lm.col_stride[i] = ldes[i].col_stride;
-        lm.width[i] = ldes[i].width;
-        lm.row_shift[i] = (uint8_t)(log_height - log2_strict(ldes[i].height));
-        lm.total_width += ldes[i].width;
-    }
-    // the table is only uploaded when a leaf kernel addressed columns through it (mmcs_commit); readers
-    // of a strided-committed batch use d[] / col_stride and must not be handed uninitialised pointers
-    lm.cols = col_table_uploaded ? col_table.p : nullptr;
-    return lm;
-}
 
 // ------------------------------------------------------------------ BFMmcs::commit
 // basic/src/mmcs/bf_mmcs.rs:22-35 on matrices already resident (column-major): builds the Blake3
@@ -73,50 +29,32 @@ void mmcs_commit(Context& ctx, PcsData& data) {
         data.tree = DevBuf<uint32_t>(&ctx, merkle_total_digests(log_H) * 8);
         // column pointers grouped by height (tallest first), commit order inside a group
         std::vector<const uint32_t*> cols;
-        struct Group { uint64_t height; size_t first; uint32_t total; uint32_t n_mats; const ColMat* only; };
+        struct Group { uint64_t height; size_t first; uint32_t total; };
         std::vector<Group> groups;
         for (unsigned lh = log_H + 1; lh-- > 0;) {
-            Group g{1ull << lh, cols.size(), 0, 0, nullptr};
-            for (auto& cm : data.ldes)
-                if (cm.height == g.height) {
-                    for (uint32_t c = 0; c < cm.width; c++) cols.push_back(cm.d + (uint64_t)c * cm.col_stride);
-                    g.total += cm.width;
-                    g.n_mats++;
-                    g.only = &cm;
-                }
-            if (g.total) groups.push_back(g);
+            const std::vector<const uint32_t*> gc = column_pointers(data.ldes, 1ull << lh);
+            if (!gc.empty()) groups.push_back(Group{1ull << lh, cols.size(), (uint32_t)gc.size()});
+            cols.insert(cols.end(), gc.begin(), gc.end());
         }
         data.col_table = DevBuf<const uint32_t*>(&ctx, cols.size());
-        bool table_uploaded = false;
-        auto upload_table = [&] {  // only the leaf kernels that address columns through the table read it
-            if (!table_uploaded) h2d(ctx, data.col_table.p, cols.data(), cols.size() * sizeof(const uint32_t*));
-            table_uploaded = true;
-            data.col_table_uploaded = true;
-        };
+        data.col_table_uploaded = false;
         auto group_mats = [&](const Group& g) {
             LeafMats lm;
             memset(&lm, 0, sizeof lm);
             lm.cols = data.col_table.p + g.first;
             lm.total_width = g.total;
-            // one matrix -- or several lying back to back with one stride (commit() stores a batch of
-            // equal-height matrices that way) -- lets the leaf kernel address the columns by stride
-            const ColMat* first = nullptr;
-            bool contiguous = true;
-            uint32_t wsum = 0;
-            for (auto& cm : data.ldes)
-                if (cm.height == g.height) {
-                    if (!first) first = &cm;
-                    contiguous = contiguous && cm.col_stride == first->col_stride &&
-                                 cm.d == first->d + (uint64_t)wsum * first->col_stride;
-                    wsum += cm.width;
-                }
-            if (first && contiguous && wsum >= 1 && wsum <= 256) {
+            // one matrix -- or several lying back to back with one stride -- lets the leaf kernel address
+            // the columns by stride (rows of at most 256 elements)
+            ColMat one;
+            if (columns_as_one_matrix(data.ldes, g.height, 256, one)) {
                 lm.n_mats = 1;
-                lm.d[0] = first->d;
-                lm.col_stride[0] = first->col_stride;
-                lm.width[0] = wsum;
-            } else {
-                upload_table();  // pointer-table leaf kernels (several scattered matrices, rows wider than 256)
+                lm.d[0] = one.d;
+                lm.col_stride[0] = one.col_stride;
+                lm.width[0] = one.width;
+            } else if (!data.col_table_uploaded) {
+                // only the pointer-table leaf kernels (several scattered matrices, rows wider than 256) read it
+                h2d(ctx, data.col_table.p, cols.data(), cols.size() * sizeof(const uint32_t*));
+                data.col_table_uploaded = true;
             }
             return lm;
         };
@@ -160,100 +98,8 @@ void mmcs_commit(Context& ctx, PcsData& data) {
 // and the rows of the matrices of height h are compressed into the level that has h nodes.
 std::unique_ptr<PcsData> TwoAdicFriPcs::commit(std::vector<DeviceMatrix>& evals,
                                                const std::vector<uint32_t>& domain_shifts, bool build_tree) {
-    TS_REQUIRE(!evals.empty() && evals.size() <= (size_t)MAX_BATCH_MATS, TS_ERR_INVALID,
-               "commit: between 1 and MAX_BATCH_MATS (64) matrices per batch");
-    TS_REQUIRE(evals.size() == domain_shifts.size(), TS_ERR_INVALID, "commit: one domain per matrix");
-    uint64_t max_n = 0;
-    for (auto& m : evals) {
-        TS_REQUIRE(m.width >= 1 && m.buf.p, TS_ERR_INVALID, "commit: empty matrix");
-        log2_strict(m.height);
-        max_n = std::max(max_n, m.height);
-    }
-    const unsigned log_N = log2_strict(max_n) + fri_.log_blowup;
-    TS_REQUIRE(log_N <= 27, TS_ERR_INVALID, "commit: LDE larger than the two-adic subgroup");
-    ctx_.ensure_twiddles(std::max(1u, log_N));
-
     auto data = std::make_unique<PcsData>();
-    data->log_height = log_N;
-    {
-        StageTimer t(&ctx_, "coset_lde");
-        // A batch of equal-height matrices (the quotient chunks) gets ONE allocation, matrix after
-        // matrix: to the leaf hash and to the opening's dot products it is then a single matrix of
-        // the summed width (strided addressing, one launch) instead of a pointer table / a launch each.
-        bool same_height = evals.size() > 1;
-        size_t total_w = 0;
-        for (auto& m : evals) {
-            same_height = same_height && m.height == evals[0].height;
-            total_w += m.width;
-        }
-        DevBuf<uint32_t> batch;
-        if (same_height) batch = DevBuf<uint32_t>(&ctx_, total_w * (evals[0].height << fri_.log_blowup));
-        size_t batch_col = 0;
-        // exactly two column-major matrices of one shape (the two quotient chunks of a degree-3 AIR):
-        // ONE set of LDE launches for both (coset_lde: evals2) -- 8 columns instead of 4 twice
-        static const bool pair_knob = [] { const char* e = getenv("TS_LDE_PAIR"); return !e || atoi(e) != 0; }();
-        const bool pair = pair_knob && same_height && evals.size() == 2 && evals[0].width == evals[1].width &&
-                          evals[0].layout == DeviceMatrix::COL_MAJOR_BITREV &&
-                          evals[1].layout == DeviceMatrix::COL_MAJOR_BITREV;
-        if (pair) {
-            for (size_t i = 0; i < 2; i++)
-                TS_REQUIRE(domain_shifts[i] != 0 && domain_shifts[i] < P, TS_ERR_INVALID, "bad domain shift");
-            const uint64_t n = evals[0].height;
-            const unsigned log_n = log2_strict(n);
-            const uint64_t Ni = n << fri_.log_blowup;
-            const uint32_t w = evals[0].width;
-            // two_adic_pcs.rs:235: shift = Val::generator() / domain.shift
-            coset_lde(ctx_, evals[0].buf.p, n, 2 * w, log_n, fri_.log_blowup, mul(GENERATOR, inv_canon(domain_shifts[0])),
-                      batch.p, Ni, 0, 0, false, evals[1].buf.p, mul(GENERATOR, inv_canon(domain_shifts[1])), w);
-            for (size_t i = 0; i < 2; i++) {
-                ColMat cm;
-                cm.d = batch.p + i * (size_t)w * Ni;
-                cm.height = Ni;
-                cm.width = w;
-                cm.col_stride = Ni;
-                data->ldes.push_back(cm);
-            }
-            evals[0].buf.reset();  // consumed, both
-            evals[1].buf.reset();
-        }
-        for (size_t i = 0; i < (pair ? 0 : evals.size()); i++) {
-            DeviceMatrix& m = evals[i];
-            TS_REQUIRE(domain_shifts[i] != 0 && domain_shifts[i] < P, TS_ERR_INVALID, "bad domain shift");
-            const uint64_t n = m.height;
-            const unsigned log_n = log2_strict(n);
-            const uint64_t Ni = n << fri_.log_blowup;
-            DevBuf<uint32_t> colmajor;
-            uint32_t* ev = m.buf.p;
-            bool r16 = false;  // the transpose already ran the first round of the inverse transform
-            if (m.layout == DeviceMatrix::ROW_MAJOR) {
-                colmajor = DevBuf<uint32_t>(&ctx_, (size_t)m.width * n);
-                r16 = launch_transpose_bitrev_r16(ctx_, m.buf.p, colmajor.p, log_n, m.width, n);
-                if (!r16) launch_transpose_bitrev(ctx_, m.buf.p, colmajor.p, log_n, m.width, n);
-                ev = colmajor.p;
-            }
-            DevBuf<uint32_t> lde;
-            uint32_t* lde_p;
-            if (same_height) {
-                lde_p = batch.p + batch_col * Ni;
-                batch_col += m.width;
-            } else {
-                lde = DevBuf<uint32_t>(&ctx_, (size_t)m.width * Ni);
-                lde_p = lde.p;
-            }
-            // two_adic_pcs.rs:235: shift = Val::generator() / domain.shift
-            const uint32_t shift = mul(GENERATOR, inv_canon(domain_shifts[i]));
-            coset_lde(ctx_, ev, n, m.width, log_n, fri_.log_blowup, shift, lde_p, Ni, 0, 0, r16);
-            ColMat cm;
-            cm.d = lde_p;
-            cm.height = Ni;
-            cm.width = m.width;
-            cm.col_stride = Ni;
-            data->ldes.push_back(cm);
-            if (!same_height) data->lde_storage.push_back(std::move(lde));
-            m.buf.reset();  // consumed
-        }
-        if (same_height) data->lde_storage.push_back(std::move(batch));
-    }
+    lde_stage(ctx_, fri_, evals, domain_shifts, 0, 0, /*allow_pair=*/true, *data);
     if (build_tree) mmcs_commit(ctx_, *data);
     return data;
 }
@@ -317,14 +163,9 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
     }
     // alpha^(K-1-i): folder.rs:60-64 unrolled (acc = acc*alpha + c_i)
     const uint32_t K = air.n_constraints;
+    const std::vector<uint32_t> pw = alpha_powers_mont(alpha, K);
     std::vector<uint32_t> apow(std::max<size_t>(4 * (size_t)K, 4), 0);
-    {
-        Ef am = ef_to_mont(alpha), cur = ef_one_mont();
-        for (uint32_t i = 0; i < K; i++) {
-            memcpy(&apow[4 * (size_t)(K - 1 - i)], cur.c, 16);
-            cur = ef_mul(cur, am);
-        }
-    }
+    for (uint32_t i = 0; i < K; i++) memcpy(&apow[4 * (size_t)(K - 1 - i)], &pw[4 * (size_t)i], 16);
     // one upload for both (a small host-to-device copy is a launch of its own on the stream)
     consts.resize((consts.size() + 3) & ~(size_t)3, 0);  // the powers stay 16-byte aligned
     const size_t n_consts = consts.size();
@@ -396,13 +237,9 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         struct { Ef* p; } sums{reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw.size()))};
         BaryPending pend;  // the trace's partial sums and the chunks' are added up in one launch
         launch_bary_dots(ctx_, tr, log_n, weights.p, 2, sums.p, &pend);  // [col][point]
-        bool chunks_contiguous = true;  // commit() lays the chunk LDEs back to back
-        for (uint32_t c = 0; c < qd; c++)
-            chunks_contiguous = chunks_contiguous && quotient_data.ldes[c].col_stride == quotient_data.ldes[0].col_stride &&
-                                quotient_data.ldes[c].d == quotient_data.ldes[0].d + (uint64_t)4 * c * quotient_data.ldes[0].col_stride;
-        if (chunks_contiguous && qd > 1) {
-            ColMat all = quotient_data.ldes[0];
-            all.width = 4 * qd;
+        ColMat all;  // lde_stage lays the chunk LDEs back to back (no width limit: the dot products take any)
+        if (qd > 1 && columns_as_one_matrix(quotient_data.ldes, quotient_data.ldes[0].height, 0, all) &&
+            all.width == 4 * qd) {
             launch_bary_dots(ctx_, all, log_n, weights.p, 1, sums.p + 2 * w, &pend);
         } else {
             for (uint32_t c = 0; c < qd; c++)
@@ -413,15 +250,7 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         memcpy(raw.data(), sums.p, raw.size() * sizeof(Ef));
     }
     // p(z) = ((z/s)^n - 1)/n * sum_i p_i x_i/(z - x_i) on the coset s*H_n (s = 31 unless sharded)
-    const uint32_t gen_inv = inv_canon(coset_gen);
-    const uint32_t n_inv = inv_canon((uint32_t)(n % P));
-    Ef scale[2];
-    for (int p = 0; p < 2; p++) {
-        Ef u = efc_mul_base(p == 0 ? zeta : zeta_next, gen_inv);
-        Ef un = efc_pow(u, n);
-        un.c[0] = sub(un.c[0], 1);
-        scale[p] = efc_mul_base(un, n_inv);
-    }
+    const Ef scale[2] = {bary_scale(zeta, coset_gen, n), bary_scale(zeta_next, coset_gen, n)};
     opened_values.assign(2 * (size_t)w + 4 * (size_t)qd, ef_zero());
     for (uint32_t c = 0; c < w; c++) {
         opened_values[c] = efc_mul(raw[2 * c], scale[0]);          // trace_local
@@ -432,15 +261,8 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
     // ---- reduce (two_adic_pcs.rs:371-383)
     StageTimer t(&ctx_, "reduce rows");
     const uint32_t max_w = std::max(w, 4u);
-    std::vector<uint32_t> apow(4 * (size_t)max_w);
+    std::vector<uint32_t> apow = alpha_powers_mont(alpha, max_w);
     const Ef am = ef_to_mont(alpha);
-    {
-        Ef cur = ef_one_mont();
-        for (uint32_t i = 0; i < max_w; i++) {
-            memcpy(&apow[4 * (size_t)i], cur.c, 16);
-            cur = ef_mul(cur, am);
-        }
-    }
     // (uploaded below, together with the chunk weights: one copy on the stream instead of two)
     auto reduced_ys = [&](const Ef* ys, uint32_t width) {  // dot_product(alpha.powers(), ys), :372
         Ef acc = ef_zero();
@@ -796,45 +618,33 @@ void TwoAdicFriPcs::fri_prove(std::vector<DevBuf<Ef>>& inputs, const std::vector
     std::vector<uint32_t> g(std::max<size_t>(off, 1));
     d2h_sync(ctx, g.data(), d_out.p, off * 4);
 
-    // ---- FriProof (fri/src/proof.rs) in TSPF v1 order
-    pf.reserve(pf.size() + 16 + off + (size_t)Q * (8 + 2 * R + 4 * n_in_rounds));
-    auto push = [&](uint32_t v) { pf.push_back(v); };
-    auto push_n = [&](const uint32_t* p, size_t k) { pf.insert(pf.end(), p, p + k); };
-    push(R);
-    for (uint32_t r = 0; r < R; r++) push_n(rounds[r].root, 8);
-    push(Q);
+    // ---- FriProof (fri/src/proof.rs)
+    std::vector<ProofWriter::Batch> batches;
+    for (const PcsData* d : input_rounds) batches.push_back({&d->ldes, d->log_height});
+    std::vector<unsigned> round_depths;
+    for (auto& r : rounds) round_depths.push_back(r.log_leaves);
+    pf.reserve(pf.size() + 16 + 8 * (size_t)R +
+               (size_t)Q * ProofWriter::words_per_query(batches, round_depths, o_pass.size()));
+    ProofWriter pw(pf);
+    pw.begin_rounds(R);
+    for (uint32_t r = 0; r < R; r++) pw.commitment(rounds[r].root, 8);
+    pw.begin_queries(Q);
     for (uint32_t q = 0; q < Q; q++) {
-        if (pass_through) {  // fri.rs:109-118: [(log_height, value)] by descending height
-            push((uint32_t)in_ptr.size());
-            for (size_t k = 0; k < in_ptr.size(); k++) {
-                push(log_lens[k]);
-                const uint32_t half = (indices[q] >> (log_max_height - log_lens[k])) & 1;
-                push_n(&g[o_pass[k] + (size_t)q * 8 + 4 * half], 4);
-            }
-        } else {
-            push((uint32_t)n_in_rounds);  // input_proof: one BatchOpening per commit round
+        pw.begin_input_proof((uint32_t)(pass_through ? in_ptr.size() : n_in_rounds));
+        for (size_t k = 0; k < o_pass.size(); k++) {
+            const uint32_t half = (indices[q] >> (log_max_height - log_lens[k])) & 1;
+            pw.pass_through_value(log_lens[k], &g[o_pass[k] + (size_t)q * 8 + 4 * half]);
         }
         for (size_t k = 0; k < n_in_rounds; k++) {
-            const LeafMats& lm = lms[k];
-            push(lm.n_mats);
-            size_t c = o_rows[k] + (size_t)q * lm.total_width;
-            for (uint32_t i = 0; i < lm.n_mats; i++) {
-                push(lm.width[i]);
-                push_n(&g[c], lm.width[i]);
-                c += lm.width[i];
-            }
             const unsigned lh = input_rounds[k]->log_height;
-            push(lh);
-            push_n(&g[o_path[k] + (size_t)q * 8 * lh], 8 * (size_t)lh);
+            pw.batch_opening(input_rounds[k]->ldes, &g[o_rows[k] + (size_t)q * lms[k].total_width], lh,
+                             {{&g[o_path[k] + (size_t)q * 8 * lh], lh}});
         }
-        for (uint32_t r = 0; r < R; r++) {  // commit_phase_openings
-            push_n(&g[o_fvals[r] + (size_t)q * 8], 8);
-            push(rounds[r].log_leaves);
-            push_n(&g[o_fpath[r] + (size_t)q * 8 * rounds[r].log_leaves], 8 * (size_t)rounds[r].log_leaves);
-        }
+        for (uint32_t r = 0; r < R; r++)
+            pw.round_opening(&g[o_fvals[r] + (size_t)q * 8], rounds[r].log_leaves,
+                             {{&g[o_fpath[r] + (size_t)q * 8 * rounds[r].log_leaves], rounds[r].log_leaves}});
     }
-    push_n(final_poly.c, 4);
-    push(pow_witness);
+    pw.finish(final_poly, pow_witness);
 }
 
 // ------------------------------------------------------------------ Pcs::open, any shape
@@ -853,21 +663,13 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
         log_global_max = std::max(log_global_max, r.data->log_height);  // :319-326
     }
     ctx_.ensure_twiddles(std::max(1u, log_global_max));
-    std::vector<uint32_t> apow(4 * (size_t)max_w);
-    {
-        Ef cur = ef_one_mont();
-        for (uint32_t i = 0; i < max_w; i++) {
-            memcpy(&apow[4 * (size_t)i], cur.c, 16);
-            cur = ef_mul(cur, am);
-        }
-    }
+    const std::vector<uint32_t> apow = alpha_powers_mont(alpha, max_w);
     DevBuf<uint32_t> d_apow(&ctx_, apow.size());
     h2d(ctx_, d_apow.p, apow.data(), apow.size() * 4);
 
     opened_values.clear();
     DevBuf<Ef> ro[32];            // :331 reduced_openings by log_height
     uint64_t num_reduced[32] = {0};  // :332
-    const uint32_t gen_inv = inv_canon(GENERATOR);
     for (auto& r : rounds) {
         for (size_t mi = 0; mi < r.data->ldes.size(); mi++) {
             const ColMat& m = r.data->ldes[mi];
@@ -876,7 +678,6 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
             const unsigned log_n = log_h - fri_.log_blowup;
             const uint64_t n = 1ull << log_n;
             const uint32_t w = m.width;
-            const uint32_t n_inv = inv_canon((uint32_t)(n % P));
             const auto& pts = r.points[mi];
             for (size_t p0 = 0; p0 < pts.size(); p0 += 2) {
                 const uint32_t np = (uint32_t)std::min<size_t>(2, pts.size() - p0);
@@ -896,10 +697,7 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
                 memset(&a, 0, sizeof a);
                 a.n_points = np;
                 for (uint32_t p = 0; p < np; p++) {
-                    // p(z) = ((z/31)^n - 1)/n * sum_i p_i x_i/(z - x_i)
-                    Ef un = efc_pow(efc_mul_base(pts[p0 + p], gen_inv), n);
-                    un.c[0] = sub(un.c[0], 1);
-                    const Ef scale = efc_mul_base(un, n_inv);
+                    const Ef scale = bary_scale(pts[p0 + p], GENERATOR, n);  // the low coset: s = 31
                     Ef rys = ef_zero();  // :372 dot_product(alpha.powers(), ys)
                     for (uint32_t c = 0; c < w; c++) {
                         const Ef y = efc_mul(raw[(size_t)c * np + p], scale);
@@ -944,20 +742,8 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
 // ------------------------------------------------------------------ prove
 std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                             DeviceMatrix trace, const std::vector<uint32_t>& public_values) {
-    Context& ctx = pcs.ctx();
-    const FriConfig& fri = pcs.fri();
-    TS_REQUIRE(trace.width == air.width, TS_ERR_INVALID, "prove: trace width != AIR width");
-    TS_REQUIRE(public_values.size() == air.n_public, TS_ERR_INVALID,
-               "prove: wrong number of public values");
-    const uint64_t degree = trace.height;  // prover.rs:43-44
-    const unsigned log_degree = log2_strict(degree);
-    const unsigned lqd = air.log_quotient_degree;  // :46
-    const uint32_t qd = 1u << lqd;
-    const unsigned log_N = log_degree + fri.log_blowup;
-    const uint32_t w = air.width;
-    TS_REQUIRE(lqd <= fri.log_blowup, TS_ERR_INVARIANT,
-               "quotient domain larger than the committed LDE (log_quotient_degree > log_blowup)");
-    ctx.ensure_twiddles(std::max(1u, log_N));
+    const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
+    pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
 
     // :50-53 commit to trace data (natural domain: shift 1)
     std::vector<DeviceMatrix> tv;
@@ -968,13 +754,10 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
 
     // :65-80 quotient on the disjoint domain, flattened and split into qd chunks
     std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, public_values, alpha);
-    // split_domains (:80): chunk c lives on {log_n, shift = 31 * omega_{n*qd}^c}
-    std::vector<uint32_t> qshifts(qd);
-    const uint32_t gq = two_adic_generator(log_degree + lqd);
-    for (uint32_t c = 0; c < qd; c++) qshifts[c] = mul(GENERATOR, pow_canon(gq, c));
-    std::unique_ptr<PcsData> quotient_data = pcs.commit(chunks, qshifts);  // :82-83
-    challenger.observe_commitment(quotient_data->root);                    // :84
-    const Ef zeta = challenger.sample();                                   // :91
+    std::unique_ptr<PcsData> quotient_data =
+        pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));  // :80-83
+    challenger.observe_commitment(quotient_data->root);                             // :84
+    const Ef zeta = challenger.sample();                                            // :91
 
     // :94-104 open; two_adic_pcs.rs:312 batch-combination challenge first.  Same result as
     // pcs.open({trace: [zeta, zeta_next]}, {chunks: [zeta]}), through the one-pass reduce kernel.
@@ -983,18 +766,15 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
     std::vector<DevBuf<Ef>> inputs;
     inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened));
 
-    // ---- Proof (prover.rs:105-118) in TSPF v1 order
+    // ---- Proof (prover.rs:105-118), TSPF v1
     std::vector<uint32_t> pf;
     pf.reserve(64 + opened.size() * 4);
-    pf.push_back(TSPF_MAGIC);
-    pf.push_back(1);
-    pf.push_back(log_degree);
-    pf.push_back(w);
-    pf.push_back(qd);
-    pf.insert(pf.end(), trace_data->root, trace_data->root + 8);
-    pf.insert(pf.end(), quotient_data->root, quotient_data->root + 8);
-    for (auto& e : opened) pf.insert(pf.end(), e.c, e.c + 4);
-    pcs.fri_prove(inputs, {log_N}, challenger, {trace_data.get(), quotient_data.get()}, pf);
+    ProofWriter pw(pf);
+    pw.header(1, st.log_degree, st.w, st.qd, 0);
+    pw.commitment(trace_data->root, 8);
+    pw.commitment(quotient_data->root, 8);
+    pw.opened_values(opened);
+    pcs.fri_prove(inputs, {st.log_N}, challenger, {trace_data.get(), quotient_data.get()}, pf);
     return pf;
 }
 

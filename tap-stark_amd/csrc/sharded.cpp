@@ -20,7 +20,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "fri_internal.hpp"
+#include "prover_internal.hpp"
 
 namespace ts {
 
@@ -37,7 +37,6 @@ struct Shard {
 // what one rank keeps of a committed batch
 struct ShardedData {
     PcsData local;              // slab LDEs (height N/G) and the slab's Merkle tree
-    unsigned log_global = 0;    // log2 N
     std::vector<uint32_t> top;  // (2G-1) x 8 words: the G sub-roots, ..., the root
     uint32_t root[8];
 };
@@ -76,74 +75,12 @@ std::unique_ptr<ShardedData> commit_sharded(Shard& sh, std::vector<DeviceMatrix>
                                             const std::vector<uint32_t>& domain_shifts,
                                             const std::vector<uint32_t>* mix = nullptr, bool mix_local = false) {
     Context& ctx = sh.ctx;
-    TS_REQUIRE(!evals.empty() && evals.size() <= (size_t)MAX_BATCH_MATS, TS_ERR_INVALID,
-               "commit: between 1 and 16 matrices per batch");
-    const uint64_t n = evals[0].height;
-    const unsigned log_n = log2_strict(n);
-    const unsigned log_N = log_n + sh.fri.log_blowup;
-    TS_REQUIRE(log_N <= 27, TS_ERR_INVALID, "commit: LDE larger than the two-adic subgroup");
-    const uint64_t rows = (uint64_t)sh.cosets << log_n;  // slab height
-    const unsigned log_rows = log2_strict(rows);
-    ctx.ensure_twiddles(std::max(1u, log_N));
-
     auto data = std::make_unique<ShardedData>();
-    data->log_global = log_N;
     PcsData& loc = data->local;
-    loc.log_height = log_rows;
-    {
-        StageTimer t(&ctx, "coset_lde");
-        // a batch (the quotient chunks) in one allocation, matrix after matrix, as TwoAdicFriPcs::commit
-        // does: the slab's leaf hash then takes it as one strided matrix
-        size_t total_w = 0;
-        for (auto& m : evals) total_w += m.width;
-        DevBuf<uint32_t> batch;
-        if (evals.size() > 1) batch = DevBuf<uint32_t>(&ctx, total_w * rows);
-        size_t batch_col = 0;
-        for (size_t i = 0; i < evals.size(); i++) {
-            DeviceMatrix& m = evals[i];
-            TS_REQUIRE(m.height == n && m.width >= 1 && m.buf.p, TS_ERR_INVALID,
-                       "sharded commit: matrices of one height expected");
-            DevBuf<uint32_t> colmajor;
-            uint32_t* ev = m.buf.p;
-            struct { uint32_t* p; } lde{nullptr};
-            DevBuf<uint32_t> own;
-            if (batch.p) {
-                lde.p = batch.p + batch_col * rows;
-                batch_col += m.width;
-            } else {
-                own = DevBuf<uint32_t>(&ctx, (size_t)m.width * rows);
-                lde.p = own.p;
-            }
-            const uint32_t shift = mul(GENERATOR, inv_canon(domain_shifts[i]));  // two_adic_pcs.rs:235
-            // The inverse transform is replicated: every rank transposes and inverts every column, then
-            // runs the forward transforms of its own cosets.  (Rounds 2-4 carried an option that did the
-            // per-column part of the inverse for w/G columns per rank and all-gathered the
-            // half-transformed columns, SURVEY.md section 8(e) steps 1-2: it took 0.5 / 0.35 ms off the
-            // compute path of configs 4 / 5 at G = 8 and added 1.5 / 0.8 ms of bulk all-gathers by the link
-            // model -- removed in round 5, numbers in HISTORY.md.)
-            {
-                bool r16 = false;
-                if (m.layout == DeviceMatrix::ROW_MAJOR) {
-                    StageTimer t(&ctx, "lde: transpose (every column on every rank)");
-                    colmajor = DevBuf<uint32_t>(&ctx, (size_t)m.width * n);
-                    r16 = launch_transpose_bitrev_r16(ctx, m.buf.p, colmajor.p, log_n, m.width, n);
-                    if (!r16) launch_transpose_bitrev(ctx, m.buf.p, colmajor.p, log_n, m.width, n);
-                    ev = colmajor.p;
-                }
-                coset_lde(ctx, ev, n, m.width, log_n, sh.fri.log_blowup, shift, lde.p, rows, sh.beta0, sh.cosets,
-                          r16);
-            }
-            ColMat cm;
-            cm.d = lde.p;
-            cm.height = rows;
-            cm.width = m.width;
-            cm.col_stride = rows;
-            loc.ldes.push_back(cm);
-            if (own.p) loc.lde_storage.push_back(std::move(own));
-            m.buf.reset();  // consumed
-        }
-        if (batch.p) loc.lde_storage.push_back(std::move(batch));
-    }
+    // every rank extends every column, onto its own cosets only: no pair launch on a slab
+    lde_stage(ctx, sh.fri, evals, domain_shifts, sh.beta0, sh.cosets, /*allow_pair=*/false, loc);
+    const unsigned log_rows = loc.log_height;
+    const uint64_t rows = 1ull << log_rows;  // slab height
     if (mix) {
         StageTimer t(&ctx, "mix chunk LDEs (local quotient)");
         const uint32_t qd = (uint32_t)evals.size();
@@ -164,31 +101,20 @@ std::unique_ptr<ShardedData> commit_sharded(Shard& sh, std::vector<DeviceMatrix>
     {
         StageTimer t(&ctx, "merkle_commit");
         loc.tree = DevBuf<uint32_t>(&ctx, merkle_total_digests(log_rows) * 8);
-        std::vector<const uint32_t*> cols;
-        for (auto& cm : loc.ldes)
-            for (uint32_t c = 0; c < cm.width; c++) cols.push_back(cm.d + (uint64_t)c * cm.col_stride);
-        loc.col_table = DevBuf<const uint32_t*>(&ctx, cols.size());
-        h2d(ctx, loc.col_table.p, cols.data(), cols.size() * sizeof(const uint32_t*));
-        loc.col_table_uploaded = true;
-        LeafMats lm = loc.leaf_mats();
-        if (loc.ldes.size() > 1) {  // laid back to back above: one matrix of the summed width for the leaf hash
-            bool contiguous = true;
-            uint32_t wsum = 0;
-            for (auto& cm : loc.ldes) {
-                contiguous = contiguous && cm.col_stride == rows && cm.d == loc.ldes[0].d + (uint64_t)wsum * rows;
-                wsum += cm.width;
-            }
-            if (contiguous && wsum <= 256) {
-                lm.n_mats = 1;
-                lm.width[0] = wsum;
-            }
+        // the table always goes up here; laid back to back by lde_stage, the batch is one matrix of the
+        // summed width for the leaf hash
+        LeafMats lm = loc.leaf_mats_with_table(ctx);
+        ColMat one;
+        if (columns_as_one_matrix(loc.ldes, rows, 256, one)) {
+            lm.n_mats = 1;
+            lm.width[0] = one.width;
         }
         launch_commit_tree(ctx, lm, log_rows, loc.tree.p);  // leaves + the slab's sub-tree
         DevBuf<uint32_t> d_top(&ctx, 8 * (size_t)(2 * sh.G - 1));
         gather_top(sh, "commit sub-roots", loc.tree.p + 8 * (merkle_total_digests(log_rows) - 1), d_top.p,
                    nullptr, nullptr, nullptr);
         data->top.resize(8 * (size_t)(2 * sh.G - 1));
-        d2h_sync(ctx, data->top.data(), d_top.p, data->top.size() * 4);  // also covers `cols`
+        d2h_sync(ctx, data->top.data(), d_top.p, data->top.size() * 4);
         memcpy(data->root, &data->top[8 * (size_t)(2 * sh.G - 2)], 32);
         memcpy(loc.root, &data->top[8 * (size_t)sh.rank], 32);
     }
@@ -287,21 +213,14 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
                "cosets per rank); run independent proofs per GPU otherwise");
     Shard sh{ctx, fri, comm, G, (uint32_t)comm.rank, log2_strict(G), fri.blowup() / G,
              (uint32_t)comm.rank * (fri.blowup() / G)};
-    TS_REQUIRE(trace_rows.width == air.width, TS_ERR_INVALID, "prove: trace width != AIR width");
     TS_REQUIRE(trace_rows.layout == DeviceMatrix::ROW_MAJOR && trace_rows.buf.p, TS_ERR_INVALID,
                "prove_sharded: the trace slice must be an uploaded row-major matrix");
-    TS_REQUIRE(public_values.size() == air.n_public, TS_ERR_INVALID,
-               "prove: wrong number of public values");
-    const uint32_t w = air.width;
     const uint64_t degree = opt.trace_replicated ? trace_rows.height : trace_rows.height * G;  // prover.rs:43-44
-    const unsigned log_degree = log2_strict(degree);
-    const unsigned lqd = air.log_quotient_degree;
-    const uint32_t qd = 1u << lqd;
-    const unsigned log_N = log_degree + fri.log_blowup;
+    const Statement stm = check_statement(fri, air, trace_rows.width, degree, public_values.size());
+    const unsigned log_degree = stm.log_degree, lqd = stm.lqd, log_N = stm.log_N;
+    const uint32_t w = stm.w, qd = stm.qd;
     const uint64_t N = 1ull << log_N, n = degree;
     const uint64_t loc0 = N / G;  // slab height
-    TS_REQUIRE(lqd <= fri.log_blowup, TS_ERR_INVARIANT,
-               "quotient domain larger than the committed LDE (log_quotient_degree > log_blowup)");
     ctx.ensure_twiddles(std::max(1u, log_N));
     TwoAdicFriPcs::Slab slab;
     slab.row0 = (uint64_t)sh.rank * loc0;
@@ -340,8 +259,7 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
     auto rest = [&](bool local_quotient) -> std::vector<uint32_t> {
     // :65-80 the quotient domain is the first qd cosets: chunk c = coset bitrev(c), computed by the
     // rank that owns that coset, then broadcast (exchange 2)
-    std::vector<uint32_t> qshifts(qd);
-    const uint32_t gq = two_adic_generator(log_degree + lqd);
+    std::vector<uint32_t> qshifts;
     std::unique_ptr<ShardedData> quotient_data;
     if (local_quotient) {
         // every rank on its own cosets ("local quotient" above); with qd = 1 the values on the rank's
@@ -351,7 +269,7 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
         std::vector<DeviceMatrix> chunks = pcs.quotient_chunks_slab(trace_data->local.ldes[0], log_degree,
                                                                     TwoAdicFriPcs::Slab{}, air, public_values,
                                                                     alpha, s_g);
-        for (uint32_t c = 0; c < qd; c++) qshifts[c] = mul(s_g, pow_canon(gq, c));
+        qshifts = chunk_domain_shifts(s_g, log_degree, lqd);
         std::vector<uint32_t> mix;
         if (qd > 1) mix = chunk_mix_matrix(qd, log_degree, s_g);
         quotient_data = commit_sharded(sh, chunks, qshifts, qd > 1 ? &mix : nullptr, true);  // :82-83
@@ -365,7 +283,7 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
                 coll_broadcast(ctx, comm, "quotient chunk", chunks[c].buf.p, (size_t)n * 16, (int)owner);
             }
         }
-        for (uint32_t c = 0; c < qd; c++) qshifts[c] = mul(GENERATOR, pow_canon(gq, c));
+        qshifts = chunk_domain_shifts(GENERATOR, log_degree, lqd);
         quotient_data = commit_sharded(sh, chunks, qshifts);  // :82-83
     }
     challenger.observe_commitment(quotient_data->root);                                 // :84
@@ -464,13 +382,13 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
     const uint32_t n_own = (uint32_t)own.size();
     const ShardedData* in_rounds[2] = {trace_data.get(), quotient_data.get()};
     const unsigned log_loc0 = log2_strict(loc0);
-    // words of one answered query (the same for every query)
-    size_t wpq = 1;
-    for (auto* d : in_rounds) {
-        wpq += 1 + d->local.ldes.size() + 1 + 8 * (size_t)log_N;
-        for (auto& m : d->local.ldes) wpq += m.width;
-    }
-    for (uint32_t r = 0; r < R; r++) wpq += 8 + 1 + 8 * (size_t)(log_N - 1 - r);
+    // the sub-tree's siblings in the top levels are the same for every query of this rank
+    std::vector<uint32_t> in_top[2];
+    for (int k = 0; k < 2; k++) push_top_path(in_top[k], in_rounds[k]->top.data(), G, sh.rank);
+    std::vector<unsigned> round_depths(R);
+    for (uint32_t r = 0; r < R; r++) round_depths[r] = log_N - 1 - r;
+    const size_t wpq = ProofWriter::words_per_query(
+        {{&trace_data->local.ldes, log_N}, {&quotient_data->local.ldes, log_N}}, round_depths);
     std::vector<uint32_t> seg((size_t)Q * wpq, 0);
     if (n_own) {
         DevBuf<uint32_t> d_li(&ctx, n_own), d_gi(&ctx, n_own);
@@ -513,30 +431,20 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
         std::vector<uint32_t> g(std::max<size_t>(off, 1));
         d2h_sync(ctx, g.data(), d_out.p, off * 4);
 
-        std::vector<uint32_t> one;
+        std::vector<uint32_t> one, round_top;
+        ProofWriter pw(one);
         for (uint32_t j = 0; j < n_own; j++) {
             one.clear();
-            auto push = [&](uint32_t v) { one.push_back(v); };
-            auto push_n = [&](const uint32_t* p, size_t k) { one.insert(one.end(), p, p + k); };
-            push(2);  // input_proof: one BatchOpening per commit round (two_adic_pcs.rs:399-414)
-            for (int k = 0; k < 2; k++) {
-                push(lms[k].n_mats);
-                size_t c = o_rows[k] + (size_t)j * lms[k].total_width;
-                for (uint32_t i = 0; i < lms[k].n_mats; i++) {
-                    push(lms[k].width[i]);
-                    push_n(&g[c], lms[k].width[i]);
-                    c += lms[k].width[i];
-                }
-                push(log_N);
-                push_n(&g[o_path[k] + (size_t)j * 8 * log_loc0], 8 * (size_t)log_loc0);
-                push_top_path(one, in_rounds[k]->top.data(), G, sh.rank);
-            }
-            for (uint32_t r = 0; r < R; r++) {  // commit_phase_openings
+            pw.begin_input_proof(2);
+            for (int k = 0; k < 2; k++)
+                pw.batch_opening(in_rounds[k]->local.ldes, &g[o_rows[k] + (size_t)j * lms[k].total_width], log_N,
+                                 {{&g[o_path[k] + (size_t)j * 8 * log_loc0], log_loc0}, {in_top[k].data(), sh.log_G}});
+            for (uint32_t r = 0; r < R; r++) {
                 const unsigned ll = st.rounds[r].log_leaves;
-                push_n(&g[o_fvals[r] + (size_t)j * 8], 8);
-                push(log_N - 1 - r);
-                push_n(&g[o_fpath[r] + (size_t)j * 8 * ll], 8 * (size_t)ll);
-                if (r < R_sh) push_top_path(one, &tops[top_words * r], G, sh.rank);
+                round_top.clear();
+                if (r < R_sh) push_top_path(round_top, &tops[top_words * r], G, sh.rank);
+                pw.round_opening(&g[o_fvals[r] + (size_t)j * 8], log_N - 1 - r,
+                                 {{&g[o_fpath[r] + (size_t)j * 8 * ll], ll}, {round_top.data(), round_top.size() / 8}});
             }
             TS_REQUIRE(one.size() == wpq, TS_ERR_INVARIANT, "sharded query: segment size");
             memcpy(&seg[(size_t)own[j] * wpq], one.data(), wpq * 4);
@@ -551,27 +459,20 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
         d2h_sync(ctx, all_seg.data(), d_all.p, all_seg.size() * 4);
     }
 
-    // ---- Proof (uni-stark/src/prover.rs:105-118) in TSPF v1 order
+    // ---- Proof (uni-stark/src/prover.rs:105-118), TSPF v1
     std::vector<uint32_t> pf;
     pf.reserve(64 + opened.size() * 4 + 8 * (size_t)R + (size_t)Q * wpq);
-    pf.push_back(TSPF_MAGIC);
-    pf.push_back(1);
-    pf.push_back(log_degree);
-    pf.push_back(w);
-    pf.push_back(qd);
-    pf.insert(pf.end(), trace_data->root, trace_data->root + 8);
-    pf.insert(pf.end(), quotient_data->root, quotient_data->root + 8);
-    for (auto& e : opened) pf.insert(pf.end(), e.c, e.c + 4);
-    pf.push_back(R);
-    for (uint32_t r = 0; r < R; r++) pf.insert(pf.end(), st.rounds[r].root, st.rounds[r].root + 8);
-    pf.push_back(Q);
-    for (uint32_t q = 0; q < Q; q++) {
-        const size_t owner = indices[q] / loc0;
-        const uint32_t* s = &all_seg[(owner * Q + q) * wpq];
-        pf.insert(pf.end(), s, s + wpq);
-    }
-    pf.insert(pf.end(), final_poly.c, final_poly.c + 4);
-    pf.push_back(pow_witness);
+    ProofWriter pw(pf);
+    pw.header(1, log_degree, w, qd, 0);
+    pw.commitment(trace_data->root, 8);
+    pw.commitment(quotient_data->root, 8);
+    pw.opened_values(opened);
+    pw.begin_rounds(R);
+    for (uint32_t r = 0; r < R; r++) pw.commitment(st.rounds[r].root, 8);
+    pw.begin_queries(Q);
+    for (uint32_t q = 0; q < Q; q++)  // answered by the rank that owns the row
+        pw.words(&all_seg[((size_t)(indices[q] / loc0) * Q + q) * wpq], wpq);
+    pw.finish(final_poly, pow_witness);
     return pf;
     };  // rest
 

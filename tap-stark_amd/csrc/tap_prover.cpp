@@ -15,7 +15,7 @@
 
 #include <algorithm>
 
-#include "fri_internal.hpp"
+#include "prover_internal.hpp"
 #include "taptree.hpp"
 
 namespace ts {
@@ -76,16 +76,11 @@ TapCommit commit_trees(Context& ctx, const TreeShare& sh, const std::vector<cons
 
 TapCommit commit_columns(Context& ctx, const TreeShare& sh, const PcsData& data, const TapLocks& locks,
                          size_t& cursor) {
-    std::vector<const uint32_t*> cols;
-    std::vector<uint8_t> shifts;
-    for (auto& cm : data.ldes) {
+    for (auto& cm : data.ldes)
         TS_REQUIRE(cm.height == (1ull << data.log_height), TS_ERR_UNSUPPORTED,
                    "prove over taptrees: matrices of one height per commitment");
-        for (uint32_t c = 0; c < cm.width; c++) {
-            cols.push_back(cm.d + (uint64_t)c * cm.col_stride);
-            shifts.push_back(0);
-        }
-    }
+    const std::vector<const uint32_t*> cols = column_pointers(data.ldes);
+    const std::vector<uint8_t> shifts(cols.size(), 0);
     return commit_trees(ctx, sh, cols, shifts, 1, data.log_height, 1, locks, cursor);
 }
 
@@ -101,20 +96,14 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
                                 const TapLocks& locks, const Comm* comm) {
     Context& ctx = pcs.ctx();
     const FriConfig& fri = pcs.fri();
-    TS_REQUIRE(trace.width == air.width, TS_ERR_INVALID, "prove: trace width != AIR width");
-    TS_REQUIRE(public_values.size() == air.n_public, TS_ERR_INVALID, "prove: wrong number of public values");
+    const Statement st = check_statement(fri, air, trace.width, trace.height, public_values.size());
     TS_REQUIRE(locks.bytes && locks.offsets, TS_ERR_INVALID, "prove over taptrees: no lock-script table");
     TS_REQUIRE(!comm || (comm->world >= 1 && comm->rank >= 0 && comm->rank < comm->world), TS_ERR_INVALID,
                "prove over taptrees: bad communicator");
-    const uint32_t w = air.width, Q = fri.num_queries;
-    const uint64_t n = trace.height;
-    const unsigned log_n = log2_strict(n), lqd = air.log_quotient_degree;
-    const uint32_t qd = 1u << lqd;
-    const unsigned log_N = log_n + fri.log_blowup;
+    const uint32_t w = st.w, qd = st.qd, Q = fri.num_queries;
+    const unsigned log_n = st.log_degree, log_N = st.log_N;
     const uint64_t N = 1ull << log_N;
     const uint32_t R = log_N - fri.log_blowup;
-    TS_REQUIRE(lqd <= fri.log_blowup, TS_ERR_INVARIANT,
-               "quotient domain larger than the committed LDE (log_quotient_degree > log_blowup)");
     TS_REQUIRE(locks.n_scripts >= (size_t)Q * ((1 + w) + (1 + 4 * (size_t)qd) + 3 * (size_t)R), TS_ERR_INVALID,
                "prove over taptrees: the lock-script table is shorter than Q ((1+w) + (1+4 qd) + 3 log2(n))");
     const TreeShare sh(Q, comm && comm->world > 1 ? comm : nullptr);
@@ -130,10 +119,7 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
 
     // ---- :65-84 quotient chunks, their commitment, zeta
     std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, public_values, alpha);
-    std::vector<uint32_t> qshifts(qd);
-    const uint32_t gq = two_adic_generator(log_n + lqd);
-    for (uint32_t c = 0; c < qd; c++) qshifts[c] = mul(GENERATOR, pow_canon(gq, c));
-    std::unique_ptr<PcsData> quotient_data = pcs.commit(chunks, qshifts, false);
+    std::unique_ptr<PcsData> quotient_data = pcs.commit(chunks, chunk_domain_shifts(GENERATOR, log_n, st.lqd), false);
     TapCommit quotient_commit = commit_columns(ctx, sh, *quotient_data, locks, cursor);
     observe_roots(challenger, quotient_commit.roots);
     const Ef zeta = challenger.sample();
@@ -178,15 +164,12 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
     // ---- query phase :45-59: query q opens every commitment in tree q, i.e. on the rank that owns it
     std::vector<uint32_t> indices(Q);
     for (uint32_t q = 0; q < Q; q++) indices[q] = (uint32_t)challenger.sample_bits(log_N);
-    const PcsData* in_data[2] = {trace_data.get(), quotient_data.get()};
+    PcsData* in_data[2] = {trace_data.get(), quotient_data.get()};
     const TapCommit* in_commit[2] = {&trace_commit, &quotient_commit};
-    // words of one answered query (the same for every query)
-    size_t wpq = 1;
-    for (auto* d : in_data) {
-        wpq += 1 + d->ldes.size() + 1 + 8 * (size_t)log_N;
-        for (auto& cm : d->ldes) wpq += cm.width;
-    }
-    for (uint32_t r = 0; r < R; r++) wpq += 8 + 1 + 8 * (size_t)rounds[r].commit.log_height;
+    std::vector<unsigned> round_depths(R);
+    for (uint32_t r = 0; r < R; r++) round_depths[r] = rounds[r].commit.log_height;
+    const size_t wpq =
+        ProofWriter::words_per_query({{&trace_data->ldes, log_N}, {&quotient_data->ldes, log_N}}, round_depths);
     const uint32_t nq = sh.cnt;  // queries answered here: q0 .. q0 + nq - 1, in local trees 0 .. nq - 1
     std::vector<uint32_t> answers((size_t)(sh.comm ? sh.per : Q) * wpq, 0);
     if (nq) {
@@ -203,15 +186,11 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
         h2d(ctx, d_tree.p, tree_of.data(), nq * 4);
         h2d(ctx, d_idx64.p, idx64.data(), nq * 8);
         std::vector<std::vector<uint32_t>> in_rows(2), in_paths(2);
+        size_t row_w[2];
         for (int k = 0; k < 2; k++) {
-            LeafMats lm = in_data[k]->leaf_mats();
-            // leaf_mats() points at the Blake3 column table, which this flow never built
-            std::vector<const uint32_t*> cols;
-            for (auto& cm : in_data[k]->ldes)
-                for (uint32_t c = 0; c < cm.width; c++) cols.push_back(cm.d + (uint64_t)c * cm.col_stride);
-            DevBuf<const uint32_t*> d_cols(&ctx, cols.size());
-            h2d(ctx, d_cols.p, cols.data(), cols.size() * sizeof(const uint32_t*));
-            lm.cols = d_cols.p;
+            // the row gather reads the columns through the table, which this flow has not built so far
+            const LeafMats lm = in_data[k]->leaf_mats_with_table(ctx);
+            row_w[k] = lm.total_width;
             DevBuf<uint32_t> d_rows(&ctx, (size_t)nq * lm.total_width), d_path(&ctx, (size_t)nq * 8 * log_N);
             launch_gather_rows(ctx, lm, d_idx.p, nq, 0, d_rows.p);
             launch_tap_gather_paths(ctx, in_commit[k]->trees.p, 2 * N - 1, log_N, d_tree.p, d_idx64.p, nq, d_path.p);
@@ -241,33 +220,16 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
             ctx.sync();
         }
         std::vector<uint32_t> one;
+        ProofWriter pw(one, /*swap_path_bytes=*/true);  // state words -> bytes read little-endian
         for (uint32_t j = 0; j < nq; j++) {
             one.clear();
-            auto push = [&](uint32_t v) { one.push_back(v); };
-            auto push_n = [&](const uint32_t* p, size_t k) { one.insert(one.end(), p, p + k); };
-            auto push_path = [&](const uint32_t* state_words, size_t depth) {  // state words -> bytes read LE
-                for (size_t k = 0; k < 8 * depth; k++) one.push_back(__builtin_bswap32(state_words[k]));
-            };
-            push(2);  // input_proof: one BatchOpening per commit round (two_adic_pcs.rs:399-414)
-            for (int k = 0; k < 2; k++) {
-                const auto& ldes = in_data[k]->ldes;
-                size_t tw = 0;
-                for (auto& cm : ldes) tw += cm.width;
-                push((uint32_t)ldes.size());
-                size_t c = (size_t)j * tw;
-                for (auto& cm : ldes) {
-                    push(cm.width);
-                    push_n(&in_rows[k][c], cm.width);
-                    c += cm.width;
-                }
-                push(log_N);
-                push_path(&in_paths[k][(size_t)j * 8 * log_N], log_N);
-            }
-            for (uint32_t r = 0; r < R; r++) {  // commit_phase_openings
+            pw.begin_input_proof(2);
+            for (int k = 0; k < 2; k++)
+                pw.batch_opening(in_data[k]->ldes, &in_rows[k][j * row_w[k]], log_N,
+                                 {{&in_paths[k][(size_t)j * 8 * log_N], log_N}});
+            for (uint32_t r = 0; r < R; r++) {
                 const unsigned ll = rounds[r].commit.log_height;
-                push_n(&f_vals[r][(size_t)j * 8], 8);
-                push(ll);
-                push_path(ll ? &f_paths[r][(size_t)j * 8 * ll] : nullptr, ll);
+                pw.round_opening(&f_vals[r][(size_t)j * 8], ll, {{f_paths[r].data() + (size_t)j * 8 * ll, ll}});
             }
             TS_REQUIRE(one.size() == wpq, TS_ERR_INVARIANT, "taptree query: segment size");
             memcpy(&answers[(size_t)j * wpq], one.data(), wpq * 4);
@@ -284,23 +246,16 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
 
     // ---- Proof (uni-stark/src/prover.rs:105-118), TSPF v2
     std::vector<uint32_t> pf;
-    auto push = [&](uint32_t v) { pf.push_back(v); };
-    auto push_n = [&](const uint32_t* p, size_t k) { pf.insert(pf.end(), p, p + k); };
-    push(TSPF_MAGIC);
-    push(2);
-    push(log_n);
-    push(w);
-    push(qd);
-    push(Q);
-    push_n(trace_commit.roots.data(), trace_commit.roots.size());
-    push_n(quotient_commit.roots.data(), quotient_commit.roots.size());
-    for (auto& e : opened) push_n(e.c, 4);
-    push(R);
-    for (uint32_t r = 0; r < R; r++) push_n(rounds[r].commit.roots.data(), rounds[r].commit.roots.size());
-    push(Q);
-    push_n(answers.data(), (size_t)Q * wpq);  // query q sits at q: the ranks' ranges are contiguous
-    push_n(final_poly.c, 4);
-    push(pow_witness);
+    ProofWriter pw(pf);
+    pw.header(2, log_n, w, qd, Q);
+    pw.commitment(trace_commit.roots.data(), trace_commit.roots.size());
+    pw.commitment(quotient_commit.roots.data(), quotient_commit.roots.size());
+    pw.opened_values(opened);
+    pw.begin_rounds(R);
+    for (uint32_t r = 0; r < R; r++) pw.commitment(rounds[r].commit.roots.data(), rounds[r].commit.roots.size());
+    pw.begin_queries(Q);
+    pw.words(answers.data(), (size_t)Q * wpq);  // query q sits at q: the ranks' ranges are contiguous
+    pw.finish(final_poly, pow_witness);
     return pf;
 }
 

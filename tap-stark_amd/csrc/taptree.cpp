@@ -25,7 +25,7 @@
 #include <algorithm>
 
 #include "abi_types.hpp"
-#include "fri_internal.hpp"
+#include "prover_internal.hpp"
 #include "sha256.hpp"
 #include "taptree.hpp"
 
@@ -463,7 +463,6 @@ std::unique_ptr<TapMmcsData> tap_mmcs_commit(Context& ctx, std::vector<DeviceMat
     const uint64_t base = d->lock_offsets.front();
     for (auto& o : d->lock_offsets) o -= base;
 
-    std::vector<const uint32_t*> cols;
     std::vector<uint8_t> shifts;
     for (auto& m : inputs) {
         DevBuf<uint32_t> cmaj(&ctx, (size_t)m.height * m.width);
@@ -473,14 +472,12 @@ std::unique_ptr<TapMmcsData> tap_mmcs_commit(Context& ctx, std::vector<DeviceMat
         cm.height = m.height;
         cm.width = m.width;
         cm.col_stride = m.height;
-        for (uint32_t c = 0; c < m.width; c++) {
-            cols.push_back(cm.d + (uint64_t)c * cm.col_stride);
-            shifts.push_back((uint8_t)(d->log_height - log2_strict(m.height)));
-        }
+        shifts.insert(shifts.end(), m.width, (uint8_t)(d->log_height - log2_strict(m.height)));
         d->mats.push_back(cm);
         d->storage.push_back(std::move(cmaj));
         m.buf.reset();
     }
+    const std::vector<const uint32_t*> cols = column_pointers(d->mats);
     d->cols = DevBuf<const uint32_t*>(&ctx, cols.size());  // (kept for callers that walk the columns)
     h2d(ctx, d->cols.p, cols.data(), cols.size() * sizeof(const uint32_t*));
     TapLocks tl;

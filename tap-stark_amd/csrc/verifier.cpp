@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "blake3.hpp"
-#include "host.hpp"
+#include "prover_internal.hpp"
 
 namespace ts {
 
@@ -407,9 +407,7 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     if (rc) return rc;
 
     // ---- verifier.rs:103-132 quotient recombination
-    std::vector<uint32_t> shifts(qd);
-    const uint32_t gq = two_adic_generator(degree_bits + lqd);
-    for (uint32_t c = 0; c < qd; c++) shifts[c] = mul(GENERATOR, pow_canon(gq, c));
+    const std::vector<uint32_t> shifts = chunk_domain_shifts(GENERATOR, degree_bits, lqd);
     Ef quotient = ef_zero();
     for (uint32_t i = 0; i < qd; i++) {
         Ef zp = c_one();

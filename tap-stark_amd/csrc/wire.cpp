@@ -22,7 +22,7 @@
 
 #include <vector>
 
-#include "fri_internal.hpp"
+#include "prover_internal.hpp"
 
 namespace ts {
 
