@@ -1,14 +1,7 @@
 // extern "C" boundary (include/tapstark.h): plain pointers and sizes, status codes, no exceptions
 // across the ABI.
-#include <dlfcn.h>
-#include <errno.h>
-#include <signal.h>
-#include <spawn.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
-#include <sys/wait.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -23,263 +16,8 @@
 #include "blake3.hpp"
 #include "jit.hpp"
 
-// hiprtc's time grows faster than the program (a 4.6k-instruction program compiles in 14 s, an
-// 18.8k one in 146 s: profiles/r06_air_jit_compile.txt), so the specialisation has a budget:
-//   <= TS_JIT_SYNC_INSTR (default 2048, ~3 s)   compiled inside ts_air_compile, as before;
-//   <= TS_JIT_MAX_INSTR  (default 32768)        compiled by a child process (ts_jitc): proofs run on the
-//                                               interpreter (a GPU path too) until the code object is
-//                                               ready, the next use loads it; ts_air_jit_wait joins;
-//   larger                                      interpreter only.
-// The segmented form (ts_air_compile_opts, air.cpp plan_segments) compiles linearly and has no such budget:
-// always in the background, its kernels split into up to J modules, one child each.
-// Both kernels compute the same words, so which one ran never shows in a proof.
-// A background compilation runs in a CHILD PROCESS (tap-stark_amd/jitc/ts_jitc.cpp, built beside the
-// library): hiprtc serialises compilations inside one process, cannot be interrupted, and a thread still
-// inside it when the host exits meets the compiler's static destructors.  The child compiles beside the
-// prover and beside other children, is killed when its AIR is freed, and leaves nothing behind but a
-// code object in a private temporary directory.
-static std::string jitc_path() {
-    if (const char* e = getenv("TS_JITC_PATH")) return e;
-    Dl_info info;
-    if (dladdr((void*)&jitc_path, &info) && info.dli_fname) {
-        std::string p = info.dli_fname;
-        const size_t k = p.rfind('/');
-        return (k == std::string::npos ? std::string(".") : p.substr(0, k)) + "/ts_jitc";
-    }
-    return "ts_jitc";
-}
-
-// One compiler child per module.  `pid` stays set until the child has been reaped (or is known to have
-// ended when the host reaped it first), so a live child is always killed with its AIR.
-struct JitChild {
-    pid_t pid = -1;
-    bool done = false, ok = false;
-    std::string src, out, log, cache;
-    std::vector<char> code;  // the code object, once done and ok
-};
-static bool file_exists(const std::string& f) { return !f.empty() && access(f.c_str(), F_OK) == 0; }
-static bool read_all(const std::string& path, std::vector<char>& out) {
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    out.clear();
-    char buf[1 << 16];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + n);
-    fclose(f);
-    return true;
-}
-// waitpid without losing the child to EINTR; ECHILD (the host ignores SIGCHLD or reaped it with
-// waitpid(-1)) counts as ended only once ts_jitc's last file is there (it writes the log after the code
-// object, both by rename) or the pid is gone.  true once the child has ended; `st` is valid if `reaped`.
-static bool child_ended(JitChild& c, bool wait, bool& reaped, int& st) {
-    reaped = false;
-    for (;;) {
-        const pid_t r = waitpid(c.pid, &st, wait ? 0 : WNOHANG);
-        if (r == c.pid) {
-            reaped = true;
-            return true;
-        }
-        if (r == 0) return false;
-        if (errno == EINTR) continue;
-        if (file_exists(c.log) || file_exists(c.out) || (kill(c.pid, 0) != 0 && errno == ESRCH)) return true;
-        if (!wait) return false;
-        std::this_thread::sleep_for(std::chrono::milliseconds(20));
-    }
-}
-struct JitJob {
-    std::string dir;
-    std::vector<JitChild> mods;
-    std::chrono::steady_clock::time_point t0;
-    ~JitJob() {
-        for (JitChild& c : mods) {
-            if (c.pid > 0) {  // still compiling for an AIR nobody wants any more
-                (void)kill(c.pid, SIGKILL);
-                int st = 0;
-                while (waitpid(c.pid, &st, 0) < 0 && errno == EINTR) {
-                }
-            }
-            for (const std::string& f : {c.src, c.out, c.out + ".part", c.log, c.log + ".part"})
-                if (!f.empty() && !dir.empty()) (void)unlink(f.c_str());
-        }
-        if (!dir.empty()) (void)rmdir(dir.c_str());
-    }
-};
-
-struct ts_air {
-    ts::AirProgram prog;
-    ts::DevBuf<uint32_t> code;
-    std::string jit_log;
-    int device = -1;  // the device the jit module was loaded on (-1: host-only AIR)
-    enum { JIT_NONE = 0, JIT_COMPILING = 1, JIT_LOADED = 3, JIT_FAILED = 4 };
-    int jit_state = JIT_NONE;
-    std::unique_ptr<JitJob> job;
-    double jit_seconds = 0;
-    std::string arch;
-    std::mutex poll_m;  // two threads proving with one ts_air: the adoption happens once
-    std::unique_ptr<ts::SegmentPlan> seg;  // set: the segmented form (ts_air_compile_opts)
-    uint32_t jit_jobs = 1;                 // modules (= compiler children) of the segmented form
-    std::unique_ptr<ts::JitKernelSet> kset;  // what prog.jit points at once published
-
-    std::vector<std::string> module_sources() const {
-        if (!seg) return {ts::jit_quotient_source(prog)};
-        return ts::jit_segment_sources(prog, *seg, jit_jobs);
-    }
-    std::vector<std::string> module_kernels(uint32_t j, uint32_t n_modules) const {
-        if (!seg) return {"k_quotient_jit"};
-        std::vector<std::string> names;
-        for (uint32_t k = ts::jit_segment_module_first(*seg, n_modules, j);
-             k < ts::jit_segment_module_first(*seg, n_modules, j + 1); k++)
-            names.push_back("k_quotient_seg" + std::to_string(k));
-        return names;
-    }
-    // loads every module on the AIR's device (the caller's device is restored) and publishes the set whole
-    bool publish(const std::vector<std::vector<char>>& codes, std::string& log) {
-        auto ks = std::make_unique<ts::JitKernelSet>();
-        ks->seg = seg.get();
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (device >= 0 && cur != device) (void)hipSetDevice(device);
-        bool ok = true;
-        for (uint32_t j = 0; ok && j < codes.size(); j++) {
-            void* mod = nullptr;
-            std::vector<void*> fns;
-            ok = ts::jit_load_module(codes[j], module_kernels(j, (uint32_t)codes.size()), mod, fns, log);
-            if (ok) {
-                ks->modules.push_back(mod);
-                ks->fns.insert(ks->fns.end(), fns.begin(), fns.end());
-            }
-        }
-        if (!ok)
-            for (void* m : ks->modules) (void)hipModuleUnload((hipModule_t)m);
-        if (device >= 0 && cur >= 0 && cur != device) (void)hipSetDevice(cur);
-        if (!ok) return false;
-        kset = std::move(ks);
-        prog.jit.publish(kset.get());
-        jit_state = JIT_LOADED;
-        return true;
-    }
-    // a code object of this very source left by an earlier process (TS_JIT_CACHE_DIR): no compilation at all
-    bool adopt_cached() {
-        std::vector<char> code_obj;
-        if (!ts::jit_cache_load(ts::jit_cache_path(ts::jit_quotient_source(prog), arch.c_str()), code_obj)) return false;
-        std::string log;
-        return publish({code_obj}, log);
-    }
-    static pid_t spawn(const std::string& helper, const std::string& arch, const JitChild& c) {
-        char* argv[] = {const_cast<char*>(helper.c_str()), const_cast<char*>(arch.c_str()),
-                        const_cast<char*>(c.src.c_str()), const_cast<char*>(c.out.c_str()),
-                        const_cast<char*>(c.log.c_str()), nullptr};
-        // the child is a plain compiler run: nothing preloaded into the host (profilers, sanitizer runtimes)
-        // belongs in it
-        std::vector<char*> envp;
-        for (char** e = environ; e && *e; e++)
-            if (strncmp(*e, "LD_PRELOAD=", 11) != 0 && strncmp(*e, "HSA_TOOLS_LIB=", 14) != 0 &&
-                strncmp(*e, "ROCP_TOOL_", 10) != 0)
-                envp.push_back(*e);
-        envp.push_back(nullptr);
-        pid_t pid = -1;
-        return posix_spawn(&pid, helper.c_str(), nullptr, nullptr, argv, envp.data()) == 0 ? pid : -1;
-    }
-    // one child per module that the cache does not hold; with every module cached the set is published at once
-    void start_background_jit() {
-        const std::vector<std::string> srcs = module_sources();
-        auto j = std::make_unique<JitJob>();
-        j->t0 = std::chrono::steady_clock::now();
-        j->mods.resize(srcs.size());
-        bool need_child = false;
-        for (size_t m = 0; m < srcs.size(); m++) {
-            JitChild& c = j->mods[m];
-            c.cache = ts::jit_cache_path(srcs[m], arch.c_str());
-            if (ts::jit_cache_load(c.cache, c.code)) c.done = c.ok = true;
-            else need_child = true;
-        }
-        if (!need_child) {
-            std::vector<std::vector<char>> codes;
-            for (JitChild& c : j->mods) codes.push_back(std::move(c.code));
-            if (!publish(codes, jit_log)) jit_state = JIT_FAILED;
-            return;
-        }
-        const std::string helper = jitc_path();
-        if (access(helper.c_str(), X_OK) != 0) {
-            jit_log = "background specialisation needs the helper " + helper + " (not found): interpreter only";
-            return;
-        }
-        const char* tmp = getenv("TMPDIR");
-        std::string tmpl = std::string(tmp && *tmp ? tmp : "/tmp") + "/ts_jit_XXXXXX";
-        std::vector<char> buf(tmpl.begin(), tmpl.end());
-        buf.push_back(0);
-        if (!mkdtemp(buf.data())) {
-            jit_log = "mkdtemp failed: interpreter only";
-            return;
-        }
-        j->dir = buf.data();
-        for (size_t m = 0; m < srcs.size(); m++) {
-            JitChild& c = j->mods[m];
-            if (c.done) continue;
-            const std::string stem = j->dir + (seg ? "/quotient_seg" + std::to_string(m) : std::string("/quotient_jit"));
-            c.src = stem + ".hip";
-            c.out = stem + ".co";
-            c.log = seg ? stem + ".log" : j->dir + "/log.txt";
-            FILE* f = fopen(c.src.c_str(), "wb");
-            if (!f || fwrite(srcs[m].data(), 1, srcs[m].size(), f) != srcs[m].size()) {
-                if (f) fclose(f);
-                jit_log = "cannot write the kernel source: interpreter only";
-                return;  // ~JitJob kills the children already started
-            }
-            fclose(f);
-            c.pid = spawn(helper, arch, c);
-            if (c.pid <= 0) {
-                c.pid = -1;
-                jit_log = "posix_spawn of " + helper + " failed: interpreter only";
-                return;
-            }
-        }
-        job = std::move(j);
-        jit_state = JIT_COMPILING;
-    }
-    // called on the thread that drives the context: adopt a finished compilation
-    void poll_jit(bool wait) {
-        std::lock_guard<std::mutex> pg(poll_m);
-        if (!job) return;
-        for (JitChild& c : job->mods) {
-            if (c.done) continue;
-            bool reaped = false;
-            int st = 0;
-            if (!child_ended(c, wait, reaped, st)) return;  // still compiling
-            c.pid = -1;
-            c.done = true;
-            c.ok = (!reaped || (WIFEXITED(st) && WEXITSTATUS(st) == 0)) && read_all(c.out, c.code) && !c.code.empty();
-            if (c.ok) ts::jit_cache_store(c.cache, c.code);
-        }
-        jit_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - job->t0).count();
-        std::vector<std::vector<char>> codes;
-        bool ok = true;
-        for (JitChild& c : job->mods) {
-            if (!c.ok && ok) {
-                std::vector<char> l;
-                if (read_all(c.log, l)) jit_log.assign(l.data(), std::min<size_t>(l.size(), 4096));
-                if (jit_log.empty()) jit_log = "the compiler child ended without a code object";
-            }
-            ok = ok && c.ok;
-            codes.push_back(std::move(c.code));
-        }
-        if (!ok || !publish(codes, jit_log)) jit_state = JIT_FAILED;
-        job.reset();
-    }
-    ~ts_air() {
-        job.reset();
-        if (kset) {
-            if (device >= 0) (void)hipSetDevice(device);
-            for (void* m : kset->modules) (void)hipModuleUnload((hipModule_t)m);
-        }
-    }
-};
-// the program as the prover sees it, with a background specialisation adopted if it has finished
-static const ts::AirProgram& ready_prog(const ts_air* air) {
-    const_cast<ts_air*>(air)->poll_jit(false);
-    return air->prog;
-}
-extern char** environ;
+// the program as the prover sees it; the handle is const in the prove calls, adopting a finished specialisation is not
+static const ts::AirProgram& ready_prog(const ts_air* air) { return const_cast<ts_air*>(air)->a.ready(); }
 
 struct ts_challenger {
     ts::BfChallenger c;
@@ -611,67 +349,10 @@ ts_status ts_bench_alu(ts_ctx* ctx, int kind, double* units_per_second) {
     return guard(ctx, [&] { *units_per_second = ts::alu_ceiling(ctx->ctx, kind); });
 }
 
-// One stage of the path in a sustained loop on resident, arbitrary data (measurement aid; the values
-// are whatever the previous repetition left -- valid lazy-range field elements, never checked):
-//   stage 0: coset_lde of a 2^log_n x width matrix (all three NTT passes, every coset)
-//   stage 1: BFMmcs::commit's hashing of a 2^(log_n + log_blowup) x width matrix (leaves + tree)
-// Returns the mean time of a repetition from HIP events on the context's stream.
 ts_status ts_bench_stage(ts_ctx* ctx, int stage, unsigned log_n, uint32_t width, unsigned log_blowup,
                          uint32_t reps, double* ms_per_rep) {
     if (!ctx || !ms_per_rep) return TS_ERR_INVALID;
-    return guard(ctx, [&] {
-        ts::Context& c = ctx->ctx;
-        TS_REQUIRE(stage >= 0 && stage <= 4 && width >= 1 && width <= 256 && reps >= 1 && log_n >= 1 &&
-                       log_n + log_blowup <= 27,
-                   ts::TS_ERR_INVALID, "bench_stage: stage 0 .. 4, width 1..256, log_n + log_blowup <= 27");
-        // stages 2, 3, 4: ONE pass of the LDE alone (inverse contiguous / strided middle / forward
-        // contiguous; two-pass shapes only, log_n > 12), on whatever the buffers hold
-        struct MaskGuard {
-            ts::Context& c;
-            ~MaskGuard() { c.lde_pass_mask = 7; }
-        } guard_mask{c};
-        if (stage >= 2) {
-            TS_REQUIRE(log_n > 12, ts::TS_ERR_INVALID, "bench_stage: single LDE passes exist for log_n > 12 only");
-            c.lde_pass_mask = 1u << (stage - 2);
-        }
-        const bool is_lde = stage != 1;
-        const uint64_t n = 1ull << log_n, N = n << log_blowup;
-        c.ensure_twiddles(log_n + log_blowup);
-        ts::DevBuf<uint32_t> lde(&c, (size_t)width * N), in(&c, is_lde ? (size_t)width * n : 1);
-        TS_HIP(hipMemsetAsync(lde.p, 0x11, (size_t)width * N * 4, c.stream));  // 0x11111111 < p
-        if (is_lde) TS_HIP(hipMemsetAsync(in.p, 0x11, (size_t)width * n * 4, c.stream));
-        ts::DevBuf<uint32_t> tree(&c, stage == 1 ? ts::merkle_total_digests(log_n + log_blowup) * 8 : 1);
-        std::vector<const uint32_t*> cols(width);
-        for (uint32_t k = 0; k < width; k++) cols[k] = lde.p + (uint64_t)k * N;
-        ts::DevBuf<const uint32_t*> d_cols(&c, width);
-        TS_HIP(hipMemcpyAsync(d_cols.p, cols.data(), width * sizeof(const uint32_t*), hipMemcpyHostToDevice, c.stream));
-        c.sync();
-        ts::LeafMats lm;
-        memset(&lm, 0, sizeof lm);
-        lm.n_mats = 1;
-        lm.d[0] = lde.p;
-        lm.col_stride[0] = N;
-        lm.width[0] = width;
-        lm.total_width = width;
-        lm.cols = d_cols.p;
-        auto once = [&] {
-            if (is_lde) ts::coset_lde(c, in.p, n, width, log_n, log_blowup, ts::GENERATOR, lde.p, N);
-            else ts::launch_commit_tree(c, lm, log_n + log_blowup, tree.p);
-        };
-        once();  // tables, first-touch
-        hipEvent_t e0, e1;
-        TS_HIP(hipEventCreate(&e0));
-        TS_HIP(hipEventCreate(&e1));
-        TS_HIP(hipEventRecord(e0, c.stream));
-        for (uint32_t r = 0; r < reps; r++) once();
-        TS_HIP(hipEventRecord(e1, c.stream));
-        c.sync();
-        float ms = 0;
-        TS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        *ms_per_rep = (double)ms / reps;
-    });
+    return guard(ctx, [&] { *ms_per_rep = ts::bench_stage(ctx->ctx, stage, log_n, width, log_blowup, reps); });
 }
 
 // pinned host memory for traces handed over as host buffers (PCIe at full rate, truly async copies)
@@ -779,71 +460,12 @@ void ts_matrix_free(ts_ctx* ctx, ts_matrix* m) {
 }
 
 // ------------------------------------------------------------------ AIR
-// segment_instr == 0: the monolithic route; S > 0 and a program longer than S: the segmented one
+// ctx == NULL: a host-only AIR (no GPU needed), usable by ts_verify
 static ts_status air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, uint32_t segment_instr,
                              uint32_t jit_jobs, ts_air** out) {
     if (!out) return TS_ERR_INVALID;
     *out = nullptr;
-    auto env_or = [](const char* name, size_t dflt) {
-        const char* v = getenv(name);
-        return v && *v ? (size_t)strtoull(v, nullptr, 10) : dflt;
-    };
-    // segmented: the plan (host only).  The register budget keeps every segment kernel within 128 VGPRs
-    // (4 waves per SIMD) with no spill; TS_SEG_REGS overrides it for measurements.
-    auto plan = [&](ts_air& a) {
-        const size_t n_instr = a.prog.code.size() / 4;
-        if (segment_instr == 0 || n_instr <= segment_instr) return;
-        a.seg = std::make_unique<ts::SegmentPlan>(
-            ts::plan_segments(a.prog, segment_instr, (uint32_t)env_or("TS_SEG_REGS", 32)));
-        a.jit_jobs = std::min<uint32_t>(jit_jobs ? jit_jobs : 4, (uint32_t)a.seg->segs.size());
-    };
-    if (!ctx) {  // host-only AIR (no GPU needed): usable by ts_verify
-        return guard(nullptr, [&] {
-            auto a = std::make_unique<ts_air>();
-            a->prog = ts::compile_air(tape, n_words);
-            plan(*a);
-            *out = a.release();
-        });
-    }
-    return guard(ctx, [&] {
-        auto a = std::make_unique<ts_air>();
-        a->device = ctx->ctx.device;
-        a->prog = ts::compile_air(tape, n_words);
-        plan(*a);
-        a->code = ts::DevBuf<uint32_t>(&ctx->ctx, std::max<size_t>(a->prog.code.size(), 4));
-        if (!a->prog.code.empty())
-            TS_HIP(hipMemcpyAsync(a->code.p, a->prog.code.data(), a->prog.code.size() * 4,
-                                  hipMemcpyHostToDevice, ctx->ctx.stream));
-        ctx->ctx.sync();
-        a->prog.d_code = a->code.p;
-        // specialise the quotient kernel for this AIR (the interpreter runs it otherwise)
-        a->arch = ctx->ctx.arch_name;
-        const size_t n_instr = a->prog.code.size() / 4;
-        if (getenv("TS_NO_JIT")) {
-            a->jit_log = "disabled by TS_NO_JIT";
-        } else if (a->seg) {
-            a->start_background_jit();  // always in the background: J children, or the cache
-        } else if (n_instr <= env_or("TS_JIT_SYNC_INSTR", 2048)) {
-            ts::JitKernel jk;
-            const auto t0 = std::chrono::steady_clock::now();
-            if (ts::jit_compile_quotient(a->prog, a->arch.c_str(), jk, a->jit_log)) {
-                auto ks = std::make_unique<ts::JitKernelSet>();
-                ks->modules = {jk.module};
-                ks->fns = {jk.fn};
-                a->kset = std::move(ks);
-                a->prog.jit.publish(a->kset.get());
-                a->jit_state = ts_air::JIT_LOADED;
-            } else {
-                a->jit_state = ts_air::JIT_FAILED;
-            }
-            a->jit_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        } else if (n_instr <= env_or("TS_JIT_MAX_INSTR", 32768)) {
-            if (!a->adopt_cached()) a->start_background_jit();
-        } else {
-            a->jit_log = "program above TS_JIT_MAX_INSTR: interpreter only";
-        }
-        *out = a.release();
-    });
+    return guard(ctx, [&] { *out = new ts_air{{ctx ? &ctx->ctx : nullptr, tape, n_words, segment_instr, jit_jobs}}; });
 }
 ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out) {
     return air_compile(ctx, tape, n_words, 0, 0, out);
@@ -853,27 +475,22 @@ ts_status ts_air_compile_opts(ts_ctx* ctx, const uint32_t* tape, size_t n_words,
     if (opt && (opt->struct_size != sizeof(ts_air_options) || opt->reserved != 0)) return TS_ERR_INVALID;
     return air_compile(ctx, tape, n_words, opt ? opt->segment_instr : 0, opt ? std::min(opt->jit_jobs, 8u) : 0, out);
 }
-int ts_air_is_jit(const ts_air* air) {
-    if (!air) return 0;
-    ts_air* a = const_cast<ts_air*>(air);
-    if (a->device >= 0) a->poll_jit(false);  // takes poll_m before it looks at the job; restores the device
-    return a->prog.jit.load() ? 1 : 0;
-}
+int ts_air_is_jit(const ts_air* air) { return air && const_cast<ts_air*>(air)->a.is_specialised() ? 1 : 0; }
 ts_status ts_air_jit_wait(ts_ctx* ctx, ts_air* air, int* state, double* compile_seconds) {
     if (!ctx || !air) return TS_ERR_INVALID;
     return guard(ctx, [&] {
-        air->poll_jit(true);
-        if (state) *state = air->jit_state;
-        if (compile_seconds) *compile_seconds = air->jit_seconds;
+        const auto [st, seconds] = air->a.wait();
+        if (state) *state = st;
+        if (compile_seconds) *compile_seconds = seconds;
     });
 }
 ts_status ts_air_info(const ts_air* air, uint32_t* width, uint32_t* n_public,
                       uint32_t* max_constraint_degree, uint32_t* log_quotient_degree) {
     if (!air) return TS_ERR_INVALID;
-    if (width) *width = air->prog.width;
-    if (n_public) *n_public = air->prog.n_public;
-    if (max_constraint_degree) *max_constraint_degree = air->prog.max_degree;
-    if (log_quotient_degree) *log_quotient_degree = air->prog.log_quotient_degree;
+    if (width) *width = air->a.prog().width;
+    if (n_public) *n_public = air->a.prog().n_public;
+    if (max_constraint_degree) *max_constraint_degree = air->a.prog().max_degree;
+    if (log_quotient_degree) *log_quotient_degree = air->a.prog().log_quotient_degree;
     return TS_OK;
 }
 void ts_air_free(ts_ctx* ctx, ts_air* air) {
@@ -882,7 +499,7 @@ void ts_air_free(ts_ctx* ctx, ts_air* air) {
 }
 ts_status ts_air_program(const ts_air* air, uint32_t* out, size_t cap_words, size_t* n_words) {
     if (!air || !n_words) return TS_ERR_INVALID;
-    const ts::AirProgram& p = air->prog;
+    const ts::AirProgram& p = air->a.prog();
     const size_t nc = p.const_canonical.size();
     *n_words = 3 + p.code.size() + 2 * nc;
     if (!out || cap_words < *n_words) return TS_ERR_BUFFER;
@@ -895,8 +512,8 @@ ts_status ts_air_program(const ts_air* air, uint32_t* out, size_t cap_words, siz
     return TS_OK;
 }
 ts_status ts_air_segment_plan(const ts_air* air, uint32_t* out, size_t cap_words, size_t* n_words) {
-    if (!air || !n_words || !air->seg) return TS_ERR_INVALID;
-    const ts::SegmentPlan& sp = *air->seg;
+    if (!air || !n_words || !air->a.seg()) return TS_ERR_INVALID;
+    const ts::SegmentPlan& sp = *air->a.seg();
     std::vector<uint32_t> w = {sp.slab_width, (uint32_t)sp.segs.size()};
     for (const auto& sg : sp.segs) {
         w.insert(w.end(), {sg.begin, sg.end, (uint32_t)sg.live_in.size(), (uint32_t)sg.live_out.size(), sg.pressure});
@@ -911,8 +528,7 @@ ts_status ts_air_segment_plan(const ts_air* air, uint32_t* out, size_t cap_words
 ts_status ts_air_jit_source(const ts_air* air, char* buf, size_t cap, size_t* n_bytes) {
     if (!air || !n_bytes) return TS_ERR_INVALID;
     return guard(nullptr, [&] {
-        const std::string src = air->seg ? ts::jit_segment_sources(air->prog, *air->seg, 1)[0]
-                                         : ts::jit_quotient_source(air->prog);
+        const std::string src = air->a.source();
         *n_bytes = src.size();
         TS_REQUIRE(buf && cap >= src.size(), ts::TS_ERR_BUFFER, "jit source buffer too small");
         memcpy(buf, src.data(), src.size());
@@ -925,8 +541,7 @@ ts_status ts_air_jit_compile(const ts_air* air, const char* arch, void* code_out
         std::vector<char> code;
         std::string log;
         const auto t0 = std::chrono::steady_clock::now();
-        const bool ok = air->seg ? ts::jit_compile_source(ts::jit_segment_sources(air->prog, *air->seg, 1)[0], arch, code, log)
-                                 : ts::jit_compile_code(air->prog, arch, code, log);
+        const bool ok = ts::jit_compile_source(air->a.source(), arch, code, log);
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         TS_REQUIRE(ok, ts::TS_ERR_UNSUPPORTED, ("hiprtc: " + log).c_str());
         *n_bytes = code.size();
@@ -1475,7 +1090,7 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         for (size_t i = 0; i < n_scripts; i++)
             TS_REQUIRE(lock_offsets[i + 1] >= lock_offsets[i], ts::TS_ERR_INVALID, "bad lock script offsets");
-        *verdict = ts::verify_tap(f, air->prog, chal->c, proof, n_words, pis,
+        *verdict = ts::verify_tap(f, air->a.prog(), chal->c, proof, n_words, pis,
                                   tap_locks(lock_scripts, lock_offsets, n_scripts));
     });
 }
@@ -1487,7 +1102,7 @@ ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* 
     if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
     *first_violation = -1;
     return guard(ctx, [&] {
-        const ts::AirProgram& p = air->prog;
+        const ts::AirProgram& p = air->a.prog();
         TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
                    "check_constraints: needs an uploaded (row-major, unconsumed) trace");
         TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
@@ -1521,7 +1136,7 @@ ts_status ts_verify(const ts_fri_config* cfg, const ts_air* air, ts_challenger* 
     *verdict = -1;
     return guard(nullptr, [&] {
         ts::FriConfig f = load_cfg(cfg);
-        *verdict = ts::verify(f, air->prog, chal->c, proof, n_words, public_inputs(public_values, n_public));
+        *verdict = ts::verify(f, air->a.prog(), chal->c, proof, n_words, public_inputs(public_values, n_public));
     });
 }
 

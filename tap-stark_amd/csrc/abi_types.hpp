@@ -1,14 +1,19 @@
 // The opaque handle types of include/tapstark.h, shared by the translation units that implement
-// the C ABI (abi.cpp, taptree.cpp, comm.cpp).
+// the C ABI (abi.cpp, taptree.cpp, comm.cpp).  Each wraps the ts:: object that does the work; an AIR's is
+// ts::SpecialisedAir (air_spec.hpp).
 #pragma once
 #include <memory>
 
 #include "../../include/tapstark.h"
+#include "air_spec.hpp"
 #include "host.hpp"
 
 struct ts_ctx {
     ts::Context ctx;
     explicit ts_ctx(int dev) : ctx(dev) {}
+};
+struct ts_air {
+    ts::SpecialisedAir a;
 };
 struct ts_matrix {
     ts::DeviceMatrix m;

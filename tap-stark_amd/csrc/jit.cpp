@@ -283,16 +283,18 @@ std::string jit_cache_path(const std::string& src, const char* arch) {
     snprintf(name, sizeof name, "/q_%016llx%016llx_%s.co", (unsigned long long)h1, (unsigned long long)h2, arch);
     return std::string(dir) + name;
 }
-bool jit_cache_load(const std::string& path, std::vector<char>& code) {
-    if (path.empty()) return false;
+bool read_file(const std::string& path, std::vector<char>& out) {
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) return false;
-    code.clear();
+    out.clear();
     char buf[1 << 16];
     size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) code.insert(code.end(), buf, buf + n);
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + n);
     fclose(f);
-    return code.size() > 64 && memcmp(code.data(), "\177ELF", 4) == 0;
+    return true;
+}
+bool jit_cache_load(const std::string& path, std::vector<char>& code) {
+    return !path.empty() && read_file(path, code) && code.size() > 64 && memcmp(code.data(), "\177ELF", 4) == 0;
 }
 void jit_cache_store(const std::string& path, const std::vector<char>& code) {
     if (path.empty() || code.empty()) return;
@@ -302,10 +304,6 @@ void jit_cache_store(const std::string& path, const std::vector<char>& code) {
     const bool ok = fwrite(code.data(), 1, code.size(), f) == code.size();
     fclose(f);
     if (!ok || rename(tmp.c_str(), path.c_str()) != 0) (void)unlink(tmp.c_str());
-}
-
-bool jit_compile_code(const AirProgram& air, const char* arch, std::vector<char>& code, std::string& log) {
-    return jit_compile_source(jit_quotient_source(air), arch, code, log);
 }
 
 bool jit_compile_source(const std::string& src, const char* arch, std::vector<char>& code, std::string& log) {
@@ -351,58 +349,23 @@ bool jit_compile_source(const std::string& src, const char* arch, std::vector<ch
     return true;
 }
 
-bool jit_compile_quotient(const AirProgram& air, const char* arch, JitKernel& out, std::string& log) {
-    if (getenv("TS_NO_JIT")) {
-        log = "disabled by TS_NO_JIT";
-        return false;
-    }
-    std::vector<char> code;
-    if (!jit_compile_code(air, arch, code, log)) return false;
-    return jit_load_code(code, out, log);
-}
-
-bool jit_load_module(const std::vector<char>& code, const std::vector<std::string>& names, void*& module,
-                     std::vector<void*>& fns, std::string& log) {
+bool jit_load_module(const std::vector<char>& code, const std::vector<std::string>& names, JitKernelSet& set,
+                     std::string& log) {
     hipModule_t mod = nullptr;
     if (hipModuleLoadData(&mod, code.data()) != hipSuccess) {
         log += " hipModuleLoadData failed";
         return false;
     }
-    fns.clear();
+    set.modules.push_back(mod);
     for (const std::string& name : names) {
         hipFunction_t fn = nullptr;
         if (hipModuleGetFunction(&fn, mod, name.c_str()) != hipSuccess) {
-            (void)hipModuleUnload(mod);
             log += " hipModuleGetFunction(" + name + ") failed";
             return false;
         }
-        fns.push_back(fn);
+        set.fns.push_back(fn);
     }
-    module = mod;
     return true;
-}
-
-bool jit_load_code(const std::vector<char>& code, JitKernel& out, std::string& log) {
-    hipModule_t mod = nullptr;
-    if (hipModuleLoadData(&mod, code.data()) != hipSuccess) {
-        log += " hipModuleLoadData failed";
-        return false;
-    }
-    hipFunction_t fn = nullptr;
-    if (hipModuleGetFunction(&fn, mod, "k_quotient_jit") != hipSuccess) {
-        (void)hipModuleUnload(mod);
-        log += " hipModuleGetFunction failed";
-        return false;
-    }
-    out.module = mod;
-    out.fn = fn;
-    return true;
-}
-
-void jit_release(JitKernel& k) {
-    if (k.module) (void)hipModuleUnload((hipModule_t)k.module);
-    k.module = nullptr;
-    k.fn = nullptr;
 }
 
 }  // namespace ts

@@ -266,6 +266,9 @@ void launch_gather_queries(Context& ctx, const RowGatherJob* d_rows, uint32_t n_
 // ---- alubench.hip ---------------------------------------------------------------------------
 // whole-chip rate of NTT butterflies (kind 0) or Blake3 compressions (kind 1), no memory traffic
 double alu_ceiling(Context& ctx, int kind);
+// (prover_common.cpp) mean ms of one repetition of one stage of the path, on resident, arbitrary data:
+// stage 0 coset_lde of a 2^log_n x width matrix, 1 the commit hashing of its LDE, 2 .. 4 one LDE pass alone
+double bench_stage(Context& ctx, int stage, unsigned log_n, uint32_t width, unsigned log_blowup, uint32_t reps);
 
 // ---- tracegen.hip ----------------------------------------------------------------------------
 // row-major traces generated in place (no H2D): Fibonacci (uni-stark/tests/fib_air.rs:59-78) and the

@@ -292,4 +292,63 @@ void ProofWriter::finish(Ef final_poly, uint32_t pow_witness) {
     out_.push_back(pow_witness);
 }
 
+// ------------------------------------------------------------------ ts_bench_stage
+// One stage of the path in a sustained loop on resident, arbitrary data (measurement aid; the values
+// are whatever the previous repetition left -- valid lazy-range field elements, never checked):
+//   stage 0: coset_lde of a 2^log_n x width matrix (all three NTT passes, every coset)
+//   stage 1: BFMmcs::commit's hashing of a 2^(log_n + log_blowup) x width matrix (leaves + tree)
+// Returns the mean time of a repetition from HIP events on the context's stream.
+double bench_stage(Context& c, int stage, unsigned log_n, uint32_t width, unsigned log_blowup, uint32_t reps) {
+    TS_REQUIRE(stage >= 0 && stage <= 4 && width >= 1 && width <= 256 && reps >= 1 && log_n >= 1 &&
+                   log_n + log_blowup <= 27,
+               TS_ERR_INVALID, "bench_stage: stage 0 .. 4, width 1..256, log_n + log_blowup <= 27");
+    // stages 2, 3, 4: ONE pass of the LDE alone (inverse contiguous / strided middle / forward
+    // contiguous; two-pass shapes only, log_n > 12), on whatever the buffers hold
+    struct MaskGuard {
+        Context& c;
+        ~MaskGuard() { c.lde_pass_mask = 7; }
+    } guard_mask{c};
+    if (stage >= 2) {
+        TS_REQUIRE(log_n > 12, TS_ERR_INVALID, "bench_stage: single LDE passes exist for log_n > 12 only");
+        c.lde_pass_mask = 1u << (stage - 2);
+    }
+    const bool is_lde = stage != 1;
+    const uint64_t n = 1ull << log_n, N = n << log_blowup;
+    c.ensure_twiddles(log_n + log_blowup);
+    DevBuf<uint32_t> lde(&c, (size_t)width * N), in(&c, is_lde ? (size_t)width * n : 1);
+    TS_HIP(hipMemsetAsync(lde.p, 0x11, (size_t)width * N * 4, c.stream));  // 0x11111111 < p
+    if (is_lde) TS_HIP(hipMemsetAsync(in.p, 0x11, (size_t)width * n * 4, c.stream));
+    DevBuf<uint32_t> tree(&c, stage == 1 ? merkle_total_digests(log_n + log_blowup) * 8 : 1);
+    std::vector<const uint32_t*> cols(width);
+    for (uint32_t k = 0; k < width; k++) cols[k] = lde.p + (uint64_t)k * N;
+    DevBuf<const uint32_t*> d_cols(&c, width);
+    TS_HIP(hipMemcpyAsync(d_cols.p, cols.data(), width * sizeof(const uint32_t*), hipMemcpyHostToDevice, c.stream));
+    c.sync();
+    LeafMats lm;
+    memset(&lm, 0, sizeof lm);
+    lm.n_mats = 1;
+    lm.d[0] = lde.p;
+    lm.col_stride[0] = N;
+    lm.width[0] = width;
+    lm.total_width = width;
+    lm.cols = d_cols.p;
+    auto once = [&] {
+        if (is_lde) coset_lde(c, in.p, n, width, log_n, log_blowup, GENERATOR, lde.p, N);
+        else launch_commit_tree(c, lm, log_n + log_blowup, tree.p);
+    };
+    once();  // tables, first-touch
+    hipEvent_t e0, e1;
+    TS_HIP(hipEventCreate(&e0));
+    TS_HIP(hipEventCreate(&e1));
+    TS_HIP(hipEventRecord(e0, c.stream));
+    for (uint32_t r = 0; r < reps; r++) once();
+    TS_HIP(hipEventRecord(e1, c.stream));
+    c.sync();
+    float ms = 0;
+    TS_HIP(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return (double)ms / reps;
+}
+
 }  // namespace ts

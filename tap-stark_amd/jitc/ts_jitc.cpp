@@ -1,5 +1,5 @@
 // ts_jitc -- out-of-process hiprtc compilation for libtapstark_hip.so's background specialisation of
-// large AIRs (csrc/abi.cpp).  hiprtc serialises compilations inside one process and cannot be
+// large AIRs (csrc/air_spec.cpp).  hiprtc serialises compilations inside one process and cannot be
 // interrupted; a child process compiles beside the prover (and beside other children), can be killed
 // when its AIR is freed, and takes the compiler's global state with it when it ends.  It never touches
 // the GPU (hiprtc only).
