@@ -260,72 +260,6 @@ void launch_vec_add(Context& ctx, Ef* acc, const Ef* other, uint64_t n) {
     TS_HIP(hipGetLastError());
 }
 
-// ------------------------------------------------------------------ gathers
-// out[q][0..total_width) = row (indices[q] >> shift) of every matrix, concatenated
-__global__ void k_gather_rows(LeafMats mats, const uint32_t* __restrict__ indices, uint32_t n_idx,
-                              unsigned shift, uint32_t* __restrict__ out) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t total = mats.total_width;
-    if (t >= n_idx * total) return;
-    const uint32_t q = t / total;
-    uint32_t c = t % total;
-    uint32_t mi = 0;
-    while (c >= mats.width[mi]) {
-        c -= mats.width[mi];
-        mi++;
-    }
-    const uint64_t row = ((uint64_t)indices[q] >> shift) >> mats.row_shift[mi];
-    out[t] = mats.d[mi][(uint64_t)c * mats.col_stride[mi] + row];
-}
-void launch_gather_rows(Context& ctx, const LeafMats& mats, const uint32_t* d_indices,
-                        uint32_t n_idx, unsigned index_shift, uint32_t* out) {
-    const uint32_t total = n_idx * mats.total_width;
-    if (!total) return;
-    TS_LAUNCH(ctx, k_gather_rows, dim3((total + 255) / 256), dim3(256), 0, mats,
-                       d_indices, n_idx, index_shift, out);
-    TS_HIP(hipGetLastError());
-}
-
-// out[q][l][0..8) = sibling digest at level l of leaf (indices[q] >> shift)
-__global__ void k_gather_paths(const uint32_t* __restrict__ tree, unsigned log_leaves,
-                               const uint32_t* __restrict__ indices, uint32_t n_idx, unsigned shift,
-                               uint32_t* __restrict__ out) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_idx * log_leaves * 8) return;
-    const uint32_t word = t & 7;
-    const uint32_t l = (t >> 3) % log_leaves;
-    const uint32_t q = (t >> 3) / log_leaves;
-    const uint64_t leaf = indices[q] >> shift;
-    uint64_t off = 0;
-    for (unsigned k = 0; k < l; k++) off += (uint64_t)1 << (log_leaves - k);
-    const uint64_t node = off + ((leaf >> l) ^ 1);
-    out[t] = tree[8 * node + word];
-}
-void launch_gather_paths(Context& ctx, const uint32_t* tree, unsigned log_leaves,
-                         const uint32_t* d_indices, uint32_t n_idx, unsigned index_shift,
-                         uint32_t* out) {
-    const uint32_t total = n_idx * log_leaves * 8;
-    if (!total) return;
-    TS_LAUNCH(ctx, k_gather_paths, dim3((total + 255) / 256), dim3(256), 0, tree,
-                       log_leaves, d_indices, n_idx, index_shift, out);
-    TS_HIP(hipGetLastError());
-}
-
-// out[q][0..8) = (vec[2r], vec[2r+1]), r = indices[q] >> shift
-__global__ void k_gather_ef_pairs(const uint32_t* __restrict__ vec, const uint32_t* __restrict__ indices,
-                                  uint32_t n_idx, unsigned shift, uint32_t* __restrict__ out) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_idx * 8) return;
-    const uint64_t r = indices[t >> 3] >> shift;
-    out[t] = vec[8 * r + (t & 7)];
-}
-void launch_gather_ef_pairs(Context& ctx, const Ef* vec, const uint32_t* d_indices, uint32_t n_idx,
-                            unsigned index_shift, uint32_t* out) {
-    if (!n_idx) return;
-    TS_LAUNCH(ctx, k_gather_ef_pairs, dim3((n_idx * 8 + 255) / 256), dim3(256), 0, reinterpret_cast<const uint32_t*>(vec), d_indices, n_idx, index_shift, out);
-    TS_HIP(hipGetLastError());
-}
-
 // ------------------------------------------------------------------ device-side transcript
 // One round of fri/src/prover.rs:113-116 without a host round trip: observe the root that the
 // Merkle kernels just wrote, sample beta, leave both where the host will collect them later.
@@ -577,15 +511,10 @@ __device__ __forceinline__ void gather_desc(const FriGatherDesc d, const uint32_
         out[d.out_path + ((uint64_t)q * d.log_leaves + l) * 8 + word] = d.tree[8 * node + word];
     }
 }
-// every commit-phase opening of every query in one launch (bf_answer_query, fri/src/prover.rs:69-90):
-// blockIdx.y = round
-__global__ void k_gather_fri(const FriGatherDesc* __restrict__ descs, const uint32_t* __restrict__ indices,
-                             uint32_t n_idx, uint32_t* __restrict__ out) {
-    gather_desc(descs[blockIdx.y], indices, n_idx, out);
-}
 
-// The query phase of one proof in one launch (kernels.hpp): blockIdx.y < n_rows: the opened rows of
-// committed batch blockIdx.y (k_gather_rows' work, the matrix table read from device memory); then one
+// The query phase of one proof in one launch (kernels.hpp; bf_answer_query, fri/src/prover.rs:69-90):
+// blockIdx.y < n_rows: the opened rows of committed batch blockIdx.y, out[q][0..total_width) = row
+// (indices[q] >> shift) of every matrix, concatenated (the matrix table read from device memory); then one
 // descriptor each.
 __global__ void k_gather_queries(const RowGatherJob* __restrict__ rows, uint32_t n_rows,
                                  const FriGatherDesc* __restrict__ descs, const uint32_t* __restrict__ indices,
@@ -616,16 +545,6 @@ void launch_gather_queries(Context& ctx, const RowGatherJob* d_rows, uint32_t n_
     if (!per_q) return;
     TS_LAUNCH(ctx, k_gather_queries, dim3((n_idx * per_q + 255) / 256, n_rows + n_descs), dim3(256), 0, d_rows,
               n_rows, d_descs, d_indices, n_idx, out);
-    TS_HIP(hipGetLastError());
-}
-
-void launch_gather_fri(Context& ctx, const FriGatherDesc* d_descs, uint32_t n_rounds,
-                       uint32_t max_log_leaves, const uint32_t* d_indices, uint32_t n_idx,
-                       uint32_t* out) {
-    if (!n_rounds || !n_idx) return;
-    const uint32_t per_q = 8 + 8 * max_log_leaves;
-    TS_LAUNCH(ctx, k_gather_fri, dim3((n_idx * per_q + 255) / 256, n_rounds), dim3(256), 0, d_descs,
-              d_indices, n_idx, out);
     TS_HIP(hipGetLastError());
 }
 

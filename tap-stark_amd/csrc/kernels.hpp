@@ -228,15 +228,12 @@ void launch_fri_tail(Context& ctx, const Ef* in, uint32_t L0, uint32_t blowup, D
 // (beta_in != nullptr: `in` holds 2 L0 elements, the previous round's vector, and the kernel starts by
 // folding it with *beta_in)
 void launch_vec_add(Context& ctx, Ef* acc, const Ef* other, uint64_t n);
-// gathers: rows of column-major matrices and Merkle paths at given indices
-void launch_gather_rows(Context& ctx, const LeafMats& mats, const uint32_t* d_indices,
-                        uint32_t n_idx, unsigned index_shift, uint32_t* out);
-void launch_gather_paths(Context& ctx, const uint32_t* tree, unsigned log_leaves,
-                         const uint32_t* d_indices, uint32_t n_idx, unsigned index_shift,
-                         uint32_t* out);
-void launch_gather_ef_pairs(Context& ctx, const Ef* vec, const uint32_t* d_indices, uint32_t n_idx,
-                            unsigned index_shift, uint32_t* out);
-// all commit-phase openings in one launch: one descriptor per FRI round (device array)
+// The whole query phase of one proof in ONE launch (after the host's sync the stream is empty, and
+// every launch on an empty stream costs the ~4 us it takes to reach the GPU: five launches were 16 us
+// of a 3.4 ms proof); driven by QueryGather (prover_internal.hpp).  Row jobs: the opened rows of a committed
+// batch.  Descriptor jobs: per query the row of two values and its Merkle path (a FRI round opening), where
+// vec == nullptr means "path only" (the batch's Merkle path) and log_leaves == 0 "values only" (a pass-through
+// input).  Both tables are device arrays.
 struct FriGatherDesc {
     const uint32_t* vec;   // committed vector as words (8 per row)
     const uint32_t* tree;  // its Merkle tree
@@ -245,14 +242,6 @@ struct FriGatherDesc {
     uint64_t out_vals;     // word offset of [query][8] in `out`
     uint64_t out_path;     // word offset of [query][log_leaves][8] in `out`
 };
-void launch_gather_fri(Context& ctx, const FriGatherDesc* d_descs, uint32_t n_rounds,
-                       uint32_t max_log_leaves, const uint32_t* d_indices, uint32_t n_idx,
-                       uint32_t* out);
-// The whole query phase of one proof in ONE launch (after the host's sync the stream is empty, and
-// every launch on an empty stream costs the ~4 us it takes to reach the GPU: five launches were 16 us
-// of a 3.4 ms proof).  Row jobs: the opened rows of a committed batch (k_gather_rows' work); descriptor
-// jobs as above, where vec == nullptr means "path only" (the batch's Merkle path) and log_leaves == 0
-// "values only" (a pass-through input).  Both tables are device arrays.
 struct RowGatherJob {
     LeafMats mats;
     uint32_t shift;  // row = index >> shift (>> row_shift[i] per matrix)

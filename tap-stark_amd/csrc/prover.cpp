@@ -321,18 +321,12 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
 void TwoAdicFriPcs::open_batch(const PcsData& d, uint64_t index, std::vector<uint32_t>& rows,
                                std::vector<uint32_t>& path) {
     TS_REQUIRE(index < (1ull << d.log_height), TS_ERR_INVALID, "open_batch: index out of range");
-    LeafMats lm = d.leaf_mats();
-    DevBuf<uint32_t> d_idx(&ctx_, 1), d_rows(&ctx_, std::max(lm.total_width, 1u)),
-        d_path(&ctx_, std::max(8u * d.log_height, 8u));
-    uint32_t idx32 = (uint32_t)index;
-    h2d(ctx_, d_idx.p, &idx32, 4);
-    launch_gather_rows(ctx_, lm, d_idx.p, 1, 0, d_rows.p);
-    launch_gather_paths(ctx_, d.tree.p, d.log_height, d_idx.p, 1, 0, d_path.p);
-    rows.resize(lm.total_width);
-    path.resize(8 * (size_t)d.log_height);
-    if (!rows.empty()) TS_HIP(hipMemcpyAsync(rows.data(), d_rows.p, rows.size() * 4, hipMemcpyDeviceToHost, ctx_.stream));
-    if (!path.empty()) TS_HIP(hipMemcpyAsync(path.data(), d_path.p, path.size() * 4, hipMemcpyDeviceToHost, ctx_.stream));
-    ctx_.sync();
+    QueryGather qg(ctx_);
+    const unsigned li = qg.add_indices({(uint32_t)index});
+    const QueryGather::Slot o_rows = qg.add_rows(li, d.leaf_mats(), 0), o_path = qg.add_path(li, d.tree.p, d.log_height, 0);
+    qg.run();
+    rows.assign(qg.data(o_rows, 0), qg.data(o_rows, 0) + o_rows.words);
+    path.assign(qg.data(o_path, 0), qg.data(o_path, 0) + o_path.words);
 }
 
 // ------------------------------------------------------------------ bf_commit_phase
@@ -534,89 +528,29 @@ void TwoAdicFriPcs::fri_prove(std::vector<DevBuf<Ef>>& inputs, const std::vector
     // ---- query phase :45-59
     StageTimer tq(&ctx, "query phase");
     const uint32_t Q = fri.num_queries;
-    std::vector<uint32_t> indices(std::max(Q, 1u));
+    std::vector<uint32_t> indices(Q);
     for (uint32_t q = 0; q < Q; q++) indices[q] = (uint32_t)challenger.sample_bits(log_max_height);
-    // (uploaded below together with the FRI gather descriptors: one copy on the stream)
 
-    // gather everything into one buffer, one D2H
+    // The whole query phase is ONE upload, ONE launch and ONE D2H (QueryGather): the opened rows and the Merkle
+    // path of every committed batch (two_adic_pcs.rs:403-409: bits_reduced = log_global_max_height -
+    // log_max_height(batch)), bf_answer_query :69-90 for every commit round (index_i = index >> i >> 1) and
+    // the pass-through inputs (values only: the pair holding element index >> shift).
     const size_t n_in_rounds = input_rounds.size();
-    std::vector<LeafMats> lms(n_in_rounds);
-    std::vector<size_t> o_rows(n_in_rounds), o_path(n_in_rounds);
-    size_t off = 0;
+    QueryGather qg(ctx);
+    const unsigned li = qg.add_indices(indices);
+    std::vector<QueryGather::Slot> o_rows(n_in_rounds), o_path(n_in_rounds);
     for (size_t k = 0; k < n_in_rounds; k++) {
-        lms[k] = input_rounds[k]->leaf_mats();
-        o_rows[k] = off; off += (size_t)Q * lms[k].total_width;
-        o_path[k] = off; off += (size_t)Q * 8 * input_rounds[k]->log_height;
+        const unsigned lh = input_rounds[k]->log_height;
+        o_rows[k] = qg.add_rows(li, input_rounds[k]->leaf_mats(), log_max_height - lh);
+        o_path[k] = qg.add_path(li, input_rounds[k]->tree.p, lh, log_max_height - lh);
     }
-    std::vector<size_t> o_fvals(R), o_fpath(R);
-    for (uint32_t r = 0; r < R; r++) {
-        o_fvals[r] = off; off += (size_t)Q * 8;
-        o_fpath[r] = off; off += (size_t)Q * 8 * rounds[r].log_leaves;
-    }
-    std::vector<size_t> o_pass(pass_through ? in_ptr.size() : 0);
-    for (size_t k = 0; k < o_pass.size(); k++) {
-        o_pass[k] = off; off += (size_t)Q * 8;
-    }
-    // The whole query phase is ONE launch (launch_gather_queries): the opened rows of every committed batch
-    // (two_adic_pcs.rs:403-409: bits_reduced = log_global_max_height - log_max_height(batch)), and as
-    // descriptors the batches' Merkle paths (no values), bf_answer_query :69-90 for every commit round
-    // (index_i = index >> i >> 1) and the pass-through inputs (values only: the pair holding element
-    // index >> shift).
-    std::vector<RowGatherJob> rjobs(n_in_rounds);
-    uint32_t max_row_w = 0;
-    for (size_t k = 0; k < n_in_rounds; k++) {
-        rjobs[k].mats = lms[k];
-        rjobs[k].shift = log_max_height - input_rounds[k]->log_height;
-        rjobs[k].pad = 0;
-        rjobs[k].out = o_rows[k];
-        max_row_w = std::max(max_row_w, lms[k].total_width);
-    }
-    std::vector<FriGatherDesc> descs;
-    uint32_t max_ll = 0;
-    for (size_t k = 0; k < n_in_rounds; k++) {
-        FriGatherDesc d{};
-        d.vec = nullptr;
-        d.tree = input_rounds[k]->tree.p;
-        d.log_leaves = input_rounds[k]->log_height;
-        d.shift = log_max_height - input_rounds[k]->log_height;
-        d.out_path = o_path[k];
-        descs.push_back(d);
-        max_ll = std::max(max_ll, d.log_leaves);
-    }
-    for (uint32_t r = 0; r < R; r++) {
-        FriGatherDesc d{};
-        d.vec = reinterpret_cast<const uint32_t*>(rounds[r].vec);
-        d.tree = rounds[r].tree;
-        d.log_leaves = rounds[r].log_leaves;
-        d.shift = r + 1;
-        d.out_vals = o_fvals[r];
-        d.out_path = o_fpath[r];
-        descs.push_back(d);
-        max_ll = std::max(max_ll, d.log_leaves);
-    }
-    for (size_t k = 0; k < o_pass.size(); k++) {
-        FriGatherDesc d{};
-        d.vec = reinterpret_cast<const uint32_t*>(in_ptr[k]);
-        d.log_leaves = 0;
-        d.shift = log_max_height - log_lens[k] + 1;
-        d.out_vals = o_pass[k];
-        descs.push_back(d);
-    }
-    // row jobs, descriptors, then the indices, in ONE upload
-    const size_t b_rows = rjobs.size() * sizeof(RowGatherJob), b_descs = descs.size() * sizeof(FriGatherDesc);
-    static_assert(sizeof(RowGatherJob) % 8 == 0 && sizeof(FriGatherDesc) % 8 == 0, "tables stay 8-byte aligned");
-    std::vector<unsigned char> up(b_rows + b_descs + indices.size() * 4);
-    if (b_rows) memcpy(up.data(), rjobs.data(), b_rows);
-    if (b_descs) memcpy(up.data() + b_rows, descs.data(), b_descs);
-    memcpy(up.data() + b_rows + b_descs, indices.data(), indices.size() * 4);
-    DevBuf<unsigned char> d_up(&ctx, up.size());
-    h2d(ctx, d_up.p, up.data(), up.size());
-    DevBuf<uint32_t> d_out(&ctx, std::max<size_t>(off, 1));
-    launch_gather_queries(ctx, reinterpret_cast<const RowGatherJob*>(d_up.p), (uint32_t)rjobs.size(), max_row_w,
-                          reinterpret_cast<const FriGatherDesc*>(d_up.p + b_rows), (uint32_t)descs.size(), max_ll,
-                          reinterpret_cast<const uint32_t*>(d_up.p + b_rows + b_descs), Q, d_out.p);
-    std::vector<uint32_t> g(std::max<size_t>(off, 1));
-    d2h_sync(ctx, g.data(), d_out.p, off * 4);
+    std::vector<QueryGather::Opening> o_round(R);
+    for (uint32_t r = 0; r < R; r++)
+        o_round[r] = qg.add_round(li, rounds[r].vec, rounds[r].tree, rounds[r].log_leaves, r + 1);
+    std::vector<QueryGather::Slot> o_pass(pass_through ? in_ptr.size() : 0);
+    for (size_t k = 0; k < o_pass.size(); k++)
+        o_pass[k] = qg.add_values(li, in_ptr[k], log_max_height - log_lens[k] + 1);
+    qg.run();
 
     // ---- FriProof (fri/src/proof.rs)
     std::vector<ProofWriter::Batch> batches;
@@ -633,16 +567,15 @@ void TwoAdicFriPcs::fri_prove(std::vector<DevBuf<Ef>>& inputs, const std::vector
         pw.begin_input_proof((uint32_t)(pass_through ? in_ptr.size() : n_in_rounds));
         for (size_t k = 0; k < o_pass.size(); k++) {
             const uint32_t half = (indices[q] >> (log_max_height - log_lens[k])) & 1;
-            pw.pass_through_value(log_lens[k], &g[o_pass[k] + (size_t)q * 8 + 4 * half]);
+            pw.pass_through_value(log_lens[k], qg.data(o_pass[k], q) + 4 * half);
         }
         for (size_t k = 0; k < n_in_rounds; k++) {
             const unsigned lh = input_rounds[k]->log_height;
-            pw.batch_opening(input_rounds[k]->ldes, &g[o_rows[k] + (size_t)q * lms[k].total_width], lh,
-                             {{&g[o_path[k] + (size_t)q * 8 * lh], lh}});
+            pw.batch_opening(input_rounds[k]->ldes, qg.data(o_rows[k], q), lh, {{qg.data(o_path[k], q), lh}});
         }
         for (uint32_t r = 0; r < R; r++)
-            pw.round_opening(&g[o_fvals[r] + (size_t)q * 8], rounds[r].log_leaves,
-                             {{&g[o_fpath[r] + (size_t)q * 8 * rounds[r].log_leaves], rounds[r].log_leaves}});
+            pw.round_opening(qg.data(o_round[r].vals, q), rounds[r].log_leaves,
+                             {{qg.data(o_round[r].path, q), rounds[r].log_leaves}});
     }
     pw.finish(final_poly, pow_witness);
 }

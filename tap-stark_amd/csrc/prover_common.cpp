@@ -292,6 +292,97 @@ void ProofWriter::finish(Ef final_poly, uint32_t pow_witness) {
     out_.push_back(pow_witness);
 }
 
+// ------------------------------------------------------------------ the query-phase gather
+unsigned QueryGather::add_indices(const std::vector<uint32_t>& indices) {
+    lists_.emplace_back();
+    lists_.back().indices = indices;
+    return (unsigned)lists_.size() - 1;
+}
+
+// the one place that lays out the output buffer: job after job, [query][words of one answer] each
+QueryGather::Slot QueryGather::take(const List& l, size_t words_per_query) {
+    const Slot s{words_, words_per_query};
+    words_ += l.indices.size() * words_per_query;
+    return s;
+}
+
+QueryGather::Slot QueryGather::add_rows(unsigned list, const LeafMats& mats, unsigned shift) {
+    List& l = lists_.at(list);
+    const Slot s = take(l, mats.total_width);
+    RowGatherJob jb{};
+    jb.mats = mats;
+    jb.shift = shift;
+    jb.out = s.at;
+    l.rows.push_back(jb);
+    l.max_row_width = std::max(l.max_row_width, mats.total_width);
+    return s;
+}
+
+// kernels.hpp: vec == nullptr is "path only", log_leaves == 0 "values only"
+QueryGather::Opening QueryGather::add_desc(unsigned list, const Ef* vec, const uint32_t* tree, unsigned log_leaves,
+                                           unsigned shift) {
+    List& l = lists_.at(list);
+    FriGatherDesc d{};
+    d.vec = reinterpret_cast<const uint32_t*>(vec);
+    d.tree = tree;
+    d.log_leaves = log_leaves;
+    d.shift = shift;
+    Opening o;
+    if (vec) d.out_vals = (o.vals = take(l, 8)).at;
+    if (tree) d.out_path = (o.path = take(l, 8 * (size_t)log_leaves)).at;
+    l.descs.push_back(d);
+    l.max_log_leaves = std::max(l.max_log_leaves, d.log_leaves);
+    return o;
+}
+QueryGather::Slot QueryGather::add_path(unsigned list, const uint32_t* tree, unsigned log_leaves, unsigned shift) {
+    return add_desc(list, nullptr, tree, log_leaves, shift).path;
+}
+QueryGather::Opening QueryGather::add_round(unsigned list, const Ef* vec, const uint32_t* tree, unsigned log_leaves,
+                                            unsigned shift) {
+    return add_desc(list, vec, tree, log_leaves, shift);
+}
+QueryGather::Slot QueryGather::add_values(unsigned list, const Ef* vec, unsigned shift) {
+    return add_desc(list, vec, nullptr, 0, shift).vals;
+}
+
+void QueryGather::run() {
+    static_assert(sizeof(RowGatherJob) % 8 == 0 && sizeof(FriGatherDesc) % 8 == 0, "tables stay 8-byte aligned");
+    size_t b_rows = 0, b_descs = 0, b_idx = 0;
+    for (auto& l : lists_) {
+        b_rows += l.rows.size() * sizeof(RowGatherJob);
+        b_descs += l.descs.size() * sizeof(FriGatherDesc);
+        b_idx += l.indices.size() * 4;
+    }
+    if (!b_idx) return;
+    // every list's row jobs, then every list's descriptors, then the indices
+    std::vector<unsigned char> up(b_rows + b_descs + b_idx);
+    auto put = [](unsigned char*& at, const void* src, size_t bytes) {
+        if (bytes) memcpy(at, src, bytes);
+        at += bytes;
+    };
+    unsigned char *rows = up.data(), *descs = rows + b_rows, *idx = descs + b_descs;
+    for (auto& l : lists_) {
+        put(rows, l.rows.data(), l.rows.size() * sizeof(RowGatherJob));
+        put(descs, l.descs.data(), l.descs.size() * sizeof(FriGatherDesc));
+        put(idx, l.indices.data(), l.indices.size() * 4);
+    }
+    DevBuf<unsigned char> d_up(&ctx_, up.size());
+    h2d(ctx_, d_up.p, up.data(), up.size());
+    DevBuf<uint32_t> d_out(&ctx_, std::max<size_t>(words_, 1));
+    rows = d_up.p, descs = rows + b_rows, idx = descs + b_descs;
+    for (auto& l : lists_) {
+        launch_gather_queries(ctx_, reinterpret_cast<const RowGatherJob*>(rows), (uint32_t)l.rows.size(),
+                              l.max_row_width, reinterpret_cast<const FriGatherDesc*>(descs), (uint32_t)l.descs.size(),
+                              l.max_log_leaves, reinterpret_cast<const uint32_t*>(idx), (uint32_t)l.indices.size(),
+                              d_out.p);
+        rows += l.rows.size() * sizeof(RowGatherJob);
+        descs += l.descs.size() * sizeof(FriGatherDesc);
+        idx += l.indices.size() * 4;
+    }
+    out_.resize(words_);
+    d2h_sync(ctx_, out_.data(), d_out.p, words_ * 4);
+}
+
 // ------------------------------------------------------------------ ts_bench_stage
 // One stage of the path in a sustained loop on resident, arbitrary data (measurement aid; the values
 // are whatever the previous repetition left -- valid lazy-range field elements, never checked):

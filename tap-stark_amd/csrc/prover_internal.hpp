@@ -112,6 +112,45 @@ private:
     bool swap_;
 };
 
+// ---- the query-phase gather (bf_answer_query, fri/src/prover.rs:69-90, and open_input, two_adic_pcs.rs:
+// 399-414): everything between "the indices are sampled" and "the ProofWriter serialises the answers".
+// The caller registers index lists and adds jobs against them; every add returns the slot of its result
+// ([query of the list][words of one answer]) in the one output buffer.  run() then sends every row job,
+// descriptor and index in ONE upload, launches k_gather_queries once per index list and brings the answers
+// back in ONE D2H (it synchronises); data(slot, j) is the answer to query j of the job's list.
+// Row = index >> shift in every job.
+class QueryGather {
+public:
+    struct Slot { size_t at = 0, words = 0; };  // word offset in the output buffer, words per query
+    struct Opening { Slot vals, path; };
+    explicit QueryGather(Context& ctx) : ctx_(ctx) {}
+    unsigned add_indices(const std::vector<uint32_t>& indices);  // -> the list's number
+    // the opened rows of a committed batch: total_width words per query
+    Slot add_rows(unsigned list, const LeafMats& mats, unsigned shift);
+    // a Merkle path: 8 * log_leaves words per query
+    Slot add_path(unsigned list, const uint32_t* tree, unsigned log_leaves, unsigned shift);
+    // a FRI round opening: the row of two values (8 words per query) and its path
+    Opening add_round(unsigned list, const Ef* vec, const uint32_t* tree, unsigned log_leaves, unsigned shift);
+    // values only: the row of two values (8 words per query)
+    Slot add_values(unsigned list, const Ef* vec, unsigned shift);
+    void run();
+    const uint32_t* data(Slot s, size_t query) const { return out_.data() + s.at + query * s.words; }
+
+private:
+    struct List {
+        std::vector<uint32_t> indices;
+        std::vector<RowGatherJob> rows;
+        std::vector<FriGatherDesc> descs;
+        uint32_t max_row_width = 0, max_log_leaves = 0;
+    };
+    Slot take(const List& l, size_t words_per_query);
+    Opening add_desc(unsigned list, const Ef* vec, const uint32_t* tree, unsigned log_leaves, unsigned shift);
+    Context& ctx_;
+    std::vector<List> lists_;
+    std::vector<uint32_t> out_;
+    size_t words_ = 0;
+};
+
 // ---- small host helpers
 void h2d(Context& ctx, void* dst, const void* src, size_t bytes);
 void d2h_sync(Context& ctx, void* dst, const void* src, size_t bytes);

@@ -391,45 +391,20 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
         {{&trace_data->local.ldes, log_N}, {&quotient_data->local.ldes, log_N}}, round_depths);
     std::vector<uint32_t> seg((size_t)Q * wpq, 0);
     if (n_own) {
-        DevBuf<uint32_t> d_li(&ctx, n_own), d_gi(&ctx, n_own);
-        h2d(ctx, d_li.p, li.data(), n_own * 4);
-        h2d(ctx, d_gi.p, gi.data(), n_own * 4);
-        LeafMats lms[2];
-        size_t o_rows[2], o_path[2], off = 0;
+        // list 0, local indices: the slab batches' rows and sub-tree paths and the sharded rounds; list 1, global
+        // indices: the replicated rounds (bf_answer_query :69-90)
+        QueryGather qg(ctx);
+        const unsigned by_li = qg.add_indices(li), by_gi = qg.add_indices(gi);
+        QueryGather::Slot o_rows[2], o_path[2];
         for (int k = 0; k < 2; k++) {
-            lms[k] = in_rounds[k]->local.leaf_mats();
-            o_rows[k] = off; off += (size_t)n_own * lms[k].total_width;
-            o_path[k] = off; off += (size_t)n_own * 8 * log_loc0;
+            o_rows[k] = qg.add_rows(by_li, in_rounds[k]->local.leaf_mats(), 0);
+            o_path[k] = qg.add_path(by_li, in_rounds[k]->local.tree.p, log_loc0, 0);
         }
-        std::vector<size_t> o_fvals(R), o_fpath(R);
-        for (uint32_t r = 0; r < R; r++) {
-            o_fvals[r] = off; off += (size_t)n_own * 8;
-            o_fpath[r] = off; off += (size_t)n_own * 8 * st.rounds[r].log_leaves;
-        }
-        DevBuf<uint32_t> d_out(&ctx, std::max<size_t>(off, 1));
-        for (int k = 0; k < 2; k++) {
-            launch_gather_rows(ctx, lms[k], d_li.p, n_own, 0, d_out.p + o_rows[k]);
-            launch_gather_paths(ctx, in_rounds[k]->local.tree.p, log_loc0, d_li.p, n_own, 0,
-                                d_out.p + o_path[k]);
-        }
-        // bf_answer_query :69-90: sharded rounds by local index, replicated rounds by global index
-        std::vector<FriGatherDesc> descs(std::max(R, 1u));
-        uint32_t max_sh = 0, max_rep = 0;
-        for (uint32_t r = 0; r < R; r++) {
-            descs[r].vec = reinterpret_cast<const uint32_t*>(st.rounds[r].vec);
-            descs[r].tree = st.rounds[r].tree;
-            descs[r].log_leaves = st.rounds[r].log_leaves;
-            descs[r].shift = r + 1;
-            descs[r].out_vals = o_fvals[r];
-            descs[r].out_path = o_fpath[r];
-            (r < R_sh ? max_sh : max_rep) = std::max(r < R_sh ? max_sh : max_rep, st.rounds[r].log_leaves);
-        }
-        DevBuf<FriGatherDesc> d_descs(&ctx, descs.size());
-        h2d(ctx, d_descs.p, descs.data(), descs.size() * sizeof(FriGatherDesc));
-        launch_gather_fri(ctx, d_descs.p, R_sh, max_sh, d_li.p, n_own, d_out.p);
-        launch_gather_fri(ctx, d_descs.p + R_sh, R - R_sh, max_rep, d_gi.p, n_own, d_out.p);
-        std::vector<uint32_t> g(std::max<size_t>(off, 1));
-        d2h_sync(ctx, g.data(), d_out.p, off * 4);
+        std::vector<QueryGather::Opening> o_round(R);
+        for (uint32_t r = 0; r < R; r++)
+            o_round[r] = qg.add_round(r < R_sh ? by_li : by_gi, st.rounds[r].vec, st.rounds[r].tree,
+                                      st.rounds[r].log_leaves, r + 1);
+        qg.run();
 
         std::vector<uint32_t> one, round_top;
         ProofWriter pw(one);
@@ -437,14 +412,14 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
             one.clear();
             pw.begin_input_proof(2);
             for (int k = 0; k < 2; k++)
-                pw.batch_opening(in_rounds[k]->local.ldes, &g[o_rows[k] + (size_t)j * lms[k].total_width], log_N,
-                                 {{&g[o_path[k] + (size_t)j * 8 * log_loc0], log_loc0}, {in_top[k].data(), sh.log_G}});
+                pw.batch_opening(in_rounds[k]->local.ldes, qg.data(o_rows[k], j), log_N,
+                                 {{qg.data(o_path[k], j), log_loc0}, {in_top[k].data(), sh.log_G}});
             for (uint32_t r = 0; r < R; r++) {
                 const unsigned ll = st.rounds[r].log_leaves;
                 round_top.clear();
                 if (r < R_sh) push_top_path(round_top, &tops[top_words * r], G, sh.rank);
-                pw.round_opening(&g[o_fvals[r] + (size_t)j * 8], log_N - 1 - r,
-                                 {{&g[o_fpath[r] + (size_t)j * 8 * ll], ll}, {round_top.data(), round_top.size() / 8}});
+                pw.round_opening(qg.data(o_round[r].vals, j), log_N - 1 - r,
+                                 {{qg.data(o_round[r].path, j), ll}, {round_top.data(), round_top.size() / 8}});
             }
             TS_REQUIRE(one.size() == wpq, TS_ERR_INVARIANT, "sharded query: segment size");
             memcpy(&seg[(size_t)own[j] * wpq], one.data(), wpq * 4);

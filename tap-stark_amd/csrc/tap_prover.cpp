@@ -173,63 +173,50 @@ std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
     const uint32_t nq = sh.cnt;  // queries answered here: q0 .. q0 + nq - 1, in local trees 0 .. nq - 1
     std::vector<uint32_t> answers((size_t)(sh.comm ? sh.per : Q) * wpq, 0);
     if (nq) {
-        std::vector<uint32_t> tree_of(nq), idx32(nq);
-        std::vector<uint64_t> idx64(nq);
+        // rows and round values through the shared gather: one upload, one launch, and the one sync of this phase
+        const std::vector<uint32_t> idx(indices.begin() + sh.q0, indices.begin() + sh.q0 + nq);
+        QueryGather qg(ctx);
+        const unsigned li = qg.add_indices(idx);
+        QueryGather::Slot o_rows[2];
+        // (the row gather reads the columns through the table, which this flow has not built so far)
+        for (int k = 0; k < 2; k++) o_rows[k] = qg.add_rows(li, in_data[k]->leaf_mats_with_table(ctx), 0);
+        std::vector<QueryGather::Slot> o_vals(R);
+        for (uint32_t r = 0; r < R; r++) o_vals[r] = qg.add_values(li, rounds[r].vec.p, r + 1);
+        // The paths stay with launch_tap_gather_paths (its trees are addressed per query): the two input batches,
+        // then the rounds, launch after launch into one buffer.  Leaf indices from ONE uploaded table: row t =
+        // index >> t (row 0 for the batches; row r + 1 for round r, bf_answer_query :69-90: it opens row
+        // index >> r >> 1 of its h x 2 matrix, in tree q), then the local tree numbers.
+        const size_t n_tab = (size_t)(R + 1) * nq;
+        std::vector<uint64_t> tab(n_tab + (nq + 1) / 2);
+        uint32_t* tree_of = reinterpret_cast<uint32_t*>(&tab[n_tab]);
         for (uint32_t j = 0; j < nq; j++) {
+            for (uint32_t t = 0; t <= R; t++) tab[(size_t)t * nq + j] = idx[j] >> t;
             tree_of[j] = j;
-            idx32[j] = indices[sh.q0 + j];
-            idx64[j] = indices[sh.q0 + j];
         }
-        DevBuf<uint32_t> d_idx(&ctx, nq), d_tree(&ctx, nq);
-        DevBuf<uint64_t> d_idx64(&ctx, nq);
-        h2d(ctx, d_idx.p, idx32.data(), nq * 4);
-        h2d(ctx, d_tree.p, tree_of.data(), nq * 4);
-        h2d(ctx, d_idx64.p, idx64.data(), nq * 8);
-        std::vector<std::vector<uint32_t>> in_rows(2), in_paths(2);
-        size_t row_w[2];
-        for (int k = 0; k < 2; k++) {
-            // the row gather reads the columns through the table, which this flow has not built so far
-            const LeafMats lm = in_data[k]->leaf_mats_with_table(ctx);
-            row_w[k] = lm.total_width;
-            DevBuf<uint32_t> d_rows(&ctx, (size_t)nq * lm.total_width), d_path(&ctx, (size_t)nq * 8 * log_N);
-            launch_gather_rows(ctx, lm, d_idx.p, nq, 0, d_rows.p);
-            launch_tap_gather_paths(ctx, in_commit[k]->trees.p, 2 * N - 1, log_N, d_tree.p, d_idx64.p, nq, d_path.p);
-            in_rows[k].resize((size_t)nq * lm.total_width);
-            in_paths[k].resize((size_t)nq * 8 * log_N);
-            TS_HIP(hipMemcpyAsync(in_rows[k].data(), d_rows.p, in_rows[k].size() * 4, hipMemcpyDeviceToHost, ctx.stream));
-            d2h_sync(ctx, in_paths[k].data(), d_path.p, in_paths[k].size() * 4);
-        }
-        // bf_answer_query :69-90: round i opens row index >> i >> 1 of its h x 2 matrix, in tree q
-        std::vector<std::vector<uint32_t>> f_vals(R), f_paths(R);
-        for (uint32_t r = 0; r < R; r++) {
-            const unsigned ll = rounds[r].commit.log_height;
-            std::vector<uint64_t> ri(nq);
-            for (uint32_t j = 0; j < nq; j++) ri[j] = idx64[j] >> (r + 1);
-            std::vector<uint32_t> ri32(ri.begin(), ri.end());
-            DevBuf<uint64_t> d_ri(&ctx, nq);
-            DevBuf<uint32_t> d_ri32(&ctx, nq), d_vals(&ctx, (size_t)nq * 8),
-                d_path(&ctx, std::max<size_t>((size_t)nq * 8 * ll, 8));
-            h2d(ctx, d_ri.p, ri.data(), nq * 8);
-            h2d(ctx, d_ri32.p, ri32.data(), nq * 4);
-            launch_gather_ef_pairs(ctx, rounds[r].vec.p, d_ri32.p, nq, 0, d_vals.p);
-            launch_tap_gather_paths(ctx, rounds[r].commit.trees.p, (2ull << ll) - 1, ll, d_tree.p, d_ri.p, nq, d_path.p);
-            f_vals[r].resize((size_t)nq * 8);
-            f_paths[r].resize((size_t)nq * 8 * ll);
-            TS_HIP(hipMemcpyAsync(f_vals[r].data(), d_vals.p, f_vals[r].size() * 4, hipMemcpyDeviceToHost, ctx.stream));
-            if (ll) TS_HIP(hipMemcpyAsync(f_paths[r].data(), d_path.p, f_paths[r].size() * 4, hipMemcpyDeviceToHost, ctx.stream));
-            ctx.sync();
-        }
+        DevBuf<uint64_t> d_tab(&ctx, tab.size());
+        h2d(ctx, d_tab.p, tab.data(), tab.size() * 8);
+        std::vector<size_t> o_tpath(2 + R + 1, 0);  // [i]: where opening i's [query][depth][8] starts; last: the total
+        auto depth = [&](uint32_t i) { return i < 2 ? log_N : rounds[i - 2].commit.log_height; };
+        for (uint32_t i = 0; i < 2 + R; i++) o_tpath[i + 1] = o_tpath[i] + (size_t)nq * 8 * depth(i);
+        DevBuf<uint32_t> d_paths(&ctx, o_tpath.back());
+        for (uint32_t i = 0; i < 2 + R; i++)
+            launch_tap_gather_paths(ctx, i < 2 ? in_commit[i]->trees.p : rounds[i - 2].commit.trees.p,
+                                    (2ull << depth(i)) - 1, depth(i), reinterpret_cast<const uint32_t*>(d_tab.p + n_tab),
+                                    d_tab.p + (size_t)(i < 2 ? 0 : i - 1) * nq, nq, d_paths.p + o_tpath[i]);
+        std::vector<uint32_t> paths(o_tpath.back());
+        TS_HIP(hipMemcpyAsync(paths.data(), d_paths.p, paths.size() * 4, hipMemcpyDeviceToHost, ctx.stream));
+        qg.run();
         std::vector<uint32_t> one;
         ProofWriter pw(one, /*swap_path_bytes=*/true);  // state words -> bytes read little-endian
         for (uint32_t j = 0; j < nq; j++) {
             one.clear();
             pw.begin_input_proof(2);
             for (int k = 0; k < 2; k++)
-                pw.batch_opening(in_data[k]->ldes, &in_rows[k][j * row_w[k]], log_N,
-                                 {{&in_paths[k][(size_t)j * 8 * log_N], log_N}});
+                pw.batch_opening(in_data[k]->ldes, qg.data(o_rows[k], j), log_N,
+                                 {{&paths[o_tpath[k] + (size_t)j * 8 * log_N], log_N}});
             for (uint32_t r = 0; r < R; r++) {
                 const unsigned ll = rounds[r].commit.log_height;
-                pw.round_opening(&f_vals[r][(size_t)j * 8], ll, {{f_paths[r].data() + (size_t)j * 8 * ll, ll}});
+                pw.round_opening(qg.data(o_vals[r], j), ll, {{paths.data() + o_tpath[2 + r] + (size_t)j * 8 * ll, ll}});
             }
             TS_REQUIRE(one.size() == wpq, TS_ERR_INVARIANT, "taptree query: segment size");
             memcpy(&answers[(size_t)j * wpq], one.data(), wpq * 4);

@@ -204,6 +204,9 @@ LOCAL_CASES = [
     ("mul64", 11, (2, 28, 8), 4, 4, False),    # the headline config's FRI parameters over 4 ranks
     ("mul7", 22, (2, 7, 8), 4, 12, True),      # 2^22 rows: 16384-element NTT chunks, one coset per rank
     ("mul7", 21, (3, 7, 8), 4, 12, False),     # 2^21 rows: 8192-element chunks, two cosets per rank, row-sliced
+    # fewer queries than ranks: at least three (two) of the four ranks own no query and skip the gather
+    ("mul7", 9, (2, 1, 8), 4, 2, False),
+    ("mul64", 10, (2, 2, 8), 4, 4, False),
 ]
 
 
