@@ -116,6 +116,23 @@ TS_HD void hash64(const uint32_t m[16], uint32_t out[8]) {
     compress(out, m, 64, CHUNK_START | CHUNK_END | ROOT);
 }
 
+// Blake3 of exactly 32 bytes: the MMCS leaf of a row of two EF4 (the FRI commit-phase matrix), one
+// short block.  The ONE definition of that leaf: every kernel that hashes such a row calls this.
+TS_HD void hash_ef_pair(const Ef& a, const Ef& b, uint32_t out[8]) {
+    const uint32_t m[16] = {a.c[0], a.c[1], a.c[2], a.c[3], b.c[0], b.c[1], b.c[2], b.c[3], 0, 0, 0, 0, 0, 0, 0, 0};
+    iv(out);
+    compress(out, m, 32, CHUNK_START | CHUNK_END | ROOT);
+}
+
+#if defined(__HIPCC__)
+// a digest to its 32 bytes in a tree (8 consecutive words, 32-byte aligned): two 16-byte stores
+__device__ __forceinline__ void store_digest(uint32_t* at, const uint32_t cv[8]) {
+    uint4* o = reinterpret_cast<uint4*>(at);
+    o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+    o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+}
+#endif
+
 // parent node of the BLAKE3 tree: compress(IV, left cv || right cv, PARENT [| ROOT])
 TS_HD void parent_cv(const uint32_t l[8], const uint32_t r[8], bool root, uint32_t out[8]) {
     uint32_t m[16];

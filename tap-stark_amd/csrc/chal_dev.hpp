@@ -75,6 +75,21 @@ __device__ inline Ef dc_observe_root_and_sample(DevChallenger* c, const uint32_t
     }
     return r;
 }
+// The whole step on ONE lane (k_chal_round, k_shard_top): observe the root at `root`, sample, leave root
+// and challenge where the host collects them later.  The sponge runs on a copy in LDS (above).
+__device__ __forceinline__ void dc_round_one_lane(DevChallenger* ch, const uint32_t* root, uint32_t* root_out,
+                                                  Ef* beta_out) {
+    __shared__ DevChallenger lc;
+    uint32_t r[8];
+    for (int i = 0; i < 8; i++) {
+        r[i] = root[i];
+        root_out[i] = r[i];
+    }
+    dc_copy(&lc, ch);
+    const Ef beta = dc_observe_root_and_sample(&lc, r);
+    dc_copy(ch, &lc);
+    *reinterpret_cast<uint4*>(beta_out) = make_uint4(beta.c[0], beta.c[1], beta.c[2], beta.c[3]);
+}
 
 // Orders one wave's LDS stores before its later LDS loads by other lanes (lock-step lanes of one wave
 // need no s_barrier; the fences keep the compiler from moving the accesses across).

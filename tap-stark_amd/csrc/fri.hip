@@ -12,25 +12,15 @@
 #include "kernels.hpp"
 #include "merkle_tree.hpp"
 #include "leaf_tree.hpp"
+#include "leaves.hpp"
 
 namespace ts {
 
-__device__ __forceinline__ Ef load_ef(const Ef* p) {
-    uint4 v = *reinterpret_cast<const uint4*>(p);
-    return Ef{{v.x, v.y, v.z, v.w}};
-}
-__device__ __forceinline__ void store_ef(Ef* p, Ef e) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]);
-}
-
-constexpr uint32_t HALF_MONT = 0x07ffffffu;  // to_mont(2^-1)
-
-// out = (lo + hi)/2 + (lo - hi) * w * (beta/2);  w = g^-bitrev(i) (Montgomery base)
-__device__ __forceinline__ Ef fold_one(Ef lo, Ef hi, uint32_t w_mont, Ef half_beta_mont,
-                                       uint32_t half_mont) {
-    Ef s = ef_mul_base(ef_add(lo, hi), half_mont);
-    Ef d = ef_mul_base(ef_sub(lo, hi), w_mont);
-    return ef_add(s, ef_mul(d, half_beta_mont));
+// the smallest k with 2^k >= n (the launchers that need a power of two check 2^k == n themselves)
+static unsigned ceil_log2(uint64_t n) {
+    unsigned k = 0;
+    while ((1ull << k) < n) k++;
+    return k;
 }
 
 __global__ void __launch_bounds__(256)
@@ -40,7 +30,7 @@ k_fri_fold_pairs(const Ef* __restrict__ in, uint64_t h, const uint32_t* __restri
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // output pair index
     if (2 * j >= h) return;
     const uint32_t half_mont = HALF_MONT;
-    const Ef half_beta_mont = ef_mul_base(ef_to_mont(load_ef(beta_ptr)), half_mont);
+    const Ef half_beta_mont = half_beta_mont_of(beta_ptr);
     const uint64_t i0 = 2 * j, i1 = 2 * j + 1;
     Ef a = fold_one(load_ef(in + 2 * i0), load_ef(in + 2 * i0 + 1), Winv[h + i0], half_beta_mont,
                     half_mont);
@@ -49,14 +39,9 @@ k_fri_fold_pairs(const Ef* __restrict__ in, uint64_t h, const uint32_t* __restri
     store_ef(out + i0, a);
     store_ef(out + i1, b);
     if (next_digests) {
-        uint32_t m[16] = {a.c[0], a.c[1], a.c[2], a.c[3], b.c[0], b.c[1], b.c[2], b.c[3],
-                          0, 0, 0, 0, 0, 0, 0, 0};
         uint32_t cv[8];
-        b3::iv(cv);
-        b3::compress(cv, m, 32, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
-        uint4* o = reinterpret_cast<uint4*>(next_digests + 8 * j);
-        o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-        o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+        b3::hash_ef_pair(a, b, cv);
+        b3::store_digest(next_digests + 8 * j, cv);
     }
 }
 
@@ -66,7 +51,7 @@ __global__ void k_fri_fold_single(const Ef* __restrict__ in, uint64_t h,
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= h) return;
     const uint32_t half_mont = HALF_MONT;
-    const Ef half_beta_mont = ef_mul_base(ef_to_mont(load_ef(beta_ptr)), half_mont);
+    const Ef half_beta_mont = half_beta_mont_of(beta_ptr);
     store_ef(out + i, fold_one(load_ef(in + 2 * i), load_ef(in + 2 * i + 1), Winv[h + i],
                                half_beta_mont, half_mont));
 }
@@ -74,8 +59,7 @@ __global__ void k_fri_fold_single(const Ef* __restrict__ in, uint64_t h,
 void launch_fri_fold_dev(Context& ctx, const Ef* in, uint64_t h, const Ef* d_beta, Ef* out,
                          uint32_t* next_digests, uint64_t h_global, uint64_t row0) {
     if (h_global == 0) h_global = h;
-    unsigned log_h = 0;
-    while ((1ull << log_h) < h_global) log_h++;
+    const unsigned log_h = ceil_log2(h_global);
     TS_REQUIRE((1ull << log_h) == h_global && row0 + h <= h_global, TS_ERR_INVALID,
                "fri_fold: length not a power of two");
     ctx.ensure_twiddles(log_h + 1);
@@ -102,44 +86,18 @@ void launch_fri_fold(Context& ctx, const Ef* in, uint64_t h, Ef beta, Ef* out,
 }
 
 // ---- one commit-phase round in one launch (merkle_tree.hpp) ------------------------------------
-// leaf i of the round's matrix = (cur[2i], cur[2i+1]).  FOLD: cur is not in memory yet: it is the
-// fold of the previous round's vector with the challenge that round's kernel left in device memory
-// (cur[k] = fold(prev[2k], prev[2k+1])), computed, stored and hashed by the thread that owns the leaf.
+// leaves: fri_leaf_digest (leaves.hpp), with the fold of the previous round in it
 static_assert(FRI_ROUND_MAX_LOG == mt::MAX_LOG_TREE, "kernels.hpp and merkle_tree.hpp disagree");
 
+// the round kernel's leaf: as FriLeaf, with the halved challenge computed once per kernel
 template <bool FOLD>
-struct FriLeaves {
+struct FriRoundLeaf {
     const Ef* prev;
-    const uint32_t* tw;   // tw[k] = g^-bitrev(k), the twiddle of output k of the fold
+    const uint32_t* tw;
     Ef half_beta_mont;
     Ef* cur;
-    uint32_t* level0;     // the tree's leaf digests
-    __device__ __forceinline__ void fill(uint32_t* in, uint64_t node0, uint32_t count) {
-        for (uint32_t n = threadIdx.x; n < count; n += mt::NTH) {
-            const uint64_t i = node0 + n;
-            Ef a, b;
-            if (FOLD) {
-                a = fold_one(load_ef(prev + 4 * i), load_ef(prev + 4 * i + 1), tw[2 * i], half_beta_mont, HALF_MONT);
-                b = fold_one(load_ef(prev + 4 * i + 2), load_ef(prev + 4 * i + 3), tw[2 * i + 1], half_beta_mont,
-                             HALF_MONT);
-                store_ef(cur + 2 * i, a);
-                store_ef(cur + 2 * i + 1, b);
-            } else {
-                a = load_ef(cur + 2 * i);
-                b = load_ef(cur + 2 * i + 1);
-            }
-            uint32_t m[16] = {a.c[0], a.c[1], a.c[2], a.c[3], b.c[0], b.c[1], b.c[2], b.c[3],
-                              0, 0, 0, 0, 0, 0, 0, 0};
-            uint32_t cv[8];
-            b3::iv(cv);
-            b3::compress(cv, m, 32, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
-            uint4* o = reinterpret_cast<uint4*>(level0 + 8 * i);
-            o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-            o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
-#pragma unroll
-            for (int k = 0; k < 8; k++) in[k * mt::CH + n] = cv[k];
-        }
-        b3::lds_barrier();
+    __device__ __forceinline__ void digest(uint64_t i, uint32_t cv[8]) const {
+        fri_leaf_digest<FOLD>(prev, tw, half_beta_mont, cur, i, cv);
     }
 };
 
@@ -152,54 +110,19 @@ k_fri_round(const Ef* __restrict__ prev, const uint32_t* __restrict__ tw, const 
     __shared__ mt::Lds lds;
     __shared__ uint32_t s_last;
     const mt::Levels lv{tree, 0, (uint64_t)1 << log_leaves};
-    FriLeaves<FOLD> prod{prev, tw, ef_zero(), cur, tree};
-    if (FOLD) prod.half_beta_mont = ef_mul_base(ef_to_mont(load_ef(beta_prev)), HALF_MONT);
+    mt::T9::LeafNodes<FriRoundLeaf<FOLD>> prod{{prev, tw, ef_zero(), cur}, tree};
+    if (FOLD) prod.leaf.half_beta_mont = half_beta_mont_of(beta_prev);
     mt::T9::tree_body(lds, s_last, prod, lv, log_leaves, ticket, ch, root_out, beta_out);
 }
 
-// The same round for a TALL vector, through the leaf-tree kernel (leaf_tree.hpp): a lane folds and
-// hashes R leaves, the first log2(R) levels stay in its registers.  Before round 5 a round above
+// The same round for a TALL vector, through the leaf-tree kernel (leaf_tree.hpp, FriLeaf): a lane folds
+// and hashes R leaves, the first log2(R) levels stay in its registers.  Before round 5 a round above
 // 2^17 leaves was a fold launch, one launch per level and the tree launch.
-template <bool FOLD>
-struct FriLeaf {
-    const Ef* prev;
-    const uint32_t* tw;
-    const Ef* beta_prev;
-    Ef* cur;
-    static const char* name(int lr) {
-        static const char* const N[2][4] = {{"k_leaf_tree<0,fri_leaf>", "k_leaf_tree<1,fri_leaf>",
-                                             "k_leaf_tree<2,fri_leaf>", "k_leaf_tree<3,fri_leaf>"},
-                                            {"k_leaf_tree<0,fri_fold>", "k_leaf_tree<1,fri_fold>",
-                                             "k_leaf_tree<2,fri_fold>", "k_leaf_tree<3,fri_fold>"}};
-        return N[FOLD ? 1 : 0][lr];
-    }
-    __device__ __forceinline__ void digest(uint64_t i, uint32_t cv[8]) const {
-        Ef a, b;
-        if (FOLD) {
-            const Ef half_beta_mont = ef_mul_base(ef_to_mont(load_ef(beta_prev)), HALF_MONT);
-            a = fold_one(load_ef(prev + 4 * i), load_ef(prev + 4 * i + 1), tw[2 * i], half_beta_mont, HALF_MONT);
-            b = fold_one(load_ef(prev + 4 * i + 2), load_ef(prev + 4 * i + 3), tw[2 * i + 1], half_beta_mont,
-                         HALF_MONT);
-            store_ef(cur + 2 * i, a);
-            store_ef(cur + 2 * i + 1, b);
-        } else {
-            a = load_ef(cur + 2 * i);
-            b = load_ef(cur + 2 * i + 1);
-        }
-        const uint32_t m[16] = {a.c[0], a.c[1], a.c[2], a.c[3], b.c[0], b.c[1], b.c[2], b.c[3],
-                                0, 0, 0, 0, 0, 0, 0, 0};
-        b3::iv(cv);
-        b3::compress(cv, m, 32, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
-    }
-};
-
 bool launch_fri_round_tall(Context& ctx, const Ef* prev, const Ef* d_beta_prev, Ef* cur, uint64_t h,
                            uint32_t* tree, DevChallenger* ch, uint32_t* root_out, Ef* beta_out,
                            uint64_t h_global, uint64_t row0) {
     if (h_global == 0) h_global = h;
-    unsigned log_h = 0, log_hg = 0;
-    while ((1ull << log_h) < h) log_h++;
-    while ((1ull << log_hg) < h_global) log_hg++;
+    const unsigned log_h = ceil_log2(h), log_hg = ceil_log2(h_global);
     TS_REQUIRE((1ull << log_h) == h && (1ull << log_hg) == h_global && row0 + h <= h_global, TS_ERR_INVALID,
                "fri_round_tall: leaf counts must be powers of two");
     if (!leaf_tree_enabled(log_h)) {  // the round-4 path: fold (+ leaf digests), levels, tree
@@ -232,8 +155,7 @@ unsigned fri_round_max_log() {
 
 void launch_fri_round(Context& ctx, const Ef* prev, const Ef* d_beta_prev, Ef* cur, uint64_t h,
                       uint32_t* tree, DevChallenger* ch, uint32_t* root_out, Ef* beta_out) {
-    unsigned log_h = 0;
-    while ((1ull << log_h) < h) log_h++;
+    const unsigned log_h = ceil_log2(h);
     TS_REQUIRE((1ull << log_h) == h && log_h <= FRI_ROUND_MAX_LOG, TS_ERR_INVALID,
                "fri_round: leaf count not a power of two <= 2^22");
     const dim3 grid(1u << (log_h - mt::block_log(log_h)));
@@ -265,17 +187,7 @@ void launch_vec_add(Context& ctx, Ef* acc, const Ef* other, uint64_t n) {
 // Merkle kernels just wrote, sample beta, leave both where the host will collect them later.
 __global__ void k_chal_round(DevChallenger* __restrict__ ch, const uint32_t* __restrict__ root,
                              uint32_t* __restrict__ root_out, Ef* __restrict__ beta_out) {
-    __shared__ DevChallenger lc;
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint32_t r[8];
-    for (int i = 0; i < 8; i++) {
-        r[i] = root[i];
-        root_out[i] = r[i];
-    }
-    dc_copy(&lc, ch);
-    Ef beta = dc_observe_root_and_sample(&lc, r);
-    dc_copy(ch, &lc);
-    store_ef(beta_out, beta);
+    if (threadIdx.x == 0 && blockIdx.x == 0) dc_round_one_lane(ch, root, root_out, beta_out);
 }
 void launch_chal_round(Context& ctx, DevChallenger* ch, const uint32_t* root, uint32_t* root_out,
                        Ef* beta_out) {
@@ -379,7 +291,7 @@ k_fri_tail(const Ef* __restrict__ in, uint32_t L0, uint32_t blowup, DevChallenge
     if (beta_in != nullptr) {
         // `in` is the previous round's vector (2 L0 elements): its fold with that round's challenge is this
         // kernel's first vector (one launch less on the chain than a fold kernel in front)
-        const Ef hb = ef_mul_base(ef_to_mont(load_ef(beta_in)), HALF_MONT);
+        const Ef hb = half_beta_mont_of(beta_in);
         for (uint32_t i = threadIdx.x; i < L0; i += TAIL_NT)
             cur[i] = fold_one(load_ef(in + 2 * i), load_ef(in + 2 * i + 1), Winv[L0 + i], hb, HALF_MONT);
     } else {
@@ -483,8 +395,7 @@ void launch_fri_tail(Context& ctx, const Ef* in, uint32_t L0, uint32_t blowup, D
                      Ef* final_out, uint32_t pow_bits, uint32_t* pow_out, const Ef* beta_in) {
     TS_REQUIRE(pow_bits <= 31, TS_ERR_INVALID, "fri_tail: proof-of-work bits > 31");
     TS_REQUIRE(L0 <= (uint32_t)TAIL_MAX && L0 >= 1, TS_ERR_INVALID, "fri_tail: vector too long");
-    unsigned log_l = 0;
-    while ((1u << log_l) < L0) log_l++;
+    const unsigned log_l = ceil_log2(L0);
     ctx.ensure_twiddles(log_l + (beta_in ? 1 : 0) == 0 ? 1 : log_l + (beta_in ? 1 : 0));
     TS_LAUNCH(ctx, k_fri_tail, dim3(1), dim3(TAIL_NT), 0, in, L0, blowup, ch,
               (const uint32_t*)ctx.d_twiddle_inv, tail_vecs, tail_trees, roots_out, betas_out,

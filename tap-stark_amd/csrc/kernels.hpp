@@ -80,6 +80,10 @@ struct DevChallenger;
 bool launch_merkle_levels(Context& ctx, uint32_t* tree, unsigned log_leaves,
                           DevChallenger* ch = nullptr, uint32_t* root_out = nullptr,
                           Ef* beta_out = nullptr);
+// the whole-tree kernel on the levels from `first_level` up (first_level's nodes are in the tree; between
+// 2 and 2^22 of them): what launch_merkle_levels ends in, and the second launch of a tall leaf tree
+void launch_merkle_tree_from(Context& ctx, uint32_t* tree, unsigned log_leaves, unsigned first_level,
+                             DevChallenger* ch, uint32_t* root_out, Ef* beta_out);
 // Leaf digests AND every level in one launch where the shape allows (leaf_tree.hpp; 2^8 leaves and
 // up, rows of at most 256 elements; TS_LEAF_TREE=0 or another shape: launch_leaf_hash +
 // launch_merkle_levels).  Return value as launch_merkle_levels.

@@ -1,6 +1,7 @@
 // Leaves AND tree of a Merkle commitment in one launch (merkle_tree.hpp: leaf_tree_body): the kernel
 // template and its launcher, shared by merkle.hip (committed matrices) and fri.hip (commit-phase
-// rounds, with the fold in the leaf).  Device code; include from .hip files only.
+// rounds, with the fold in the leaf); the leaf kinds are in leaves.hpp.  Device code; include from
+// .hip files only.
 #pragma once
 #include <stdlib.h>
 
@@ -22,11 +23,6 @@ k_leaf_tree(Leaf leaf, uint32_t* __restrict__ tree, unsigned log_leaves, int fin
     const mt::Levels lv{tree, 0, (uint64_t)1 << log_leaves};
     mt::leaf_tree_body<LOG_R>(lds, s_last, leaf, lv, log_leaves, finish != 0, ticket, ch, root_out, beta_out);
 }
-
-// merkle.hip: the whole-tree kernel on the levels from `first_level` up (first_level's nodes are in
-// the tree); at most 2^MAX_LOG_TREE of them
-void launch_merkle_tree_from(Context& ctx, uint32_t* tree, unsigned log_leaves, unsigned first_level,
-                             DevChallenger* ch, uint32_t* root_out, Ef* beta_out);
 
 // Leaf digests and every level of a tree of 2^log_leaves >= 2^LEAF_TREE_MIN_LOG leaves.  One launch
 // while the workgroups leave at most 2^LEAF_TREE_MAX_LOG_SUB sub-roots (trees up to 2^16 .. 2^18
@@ -51,11 +47,10 @@ void launch_leaf_tree(Context& ctx, const Leaf& leaf, uint32_t* tree, unsigned l
     DevChallenger* kch = finish ? ch : nullptr;
     // (kernel timers: one name per leaf kind and R, Leaf::name(log_r))
 #define TS_LEAF_TREE_CASE(LR)                                                                              \
-    case LR: {                                                                                             \
-        ts::KernelTimer _kt(&ctx, Leaf::name(LR));                                                         \
-        hipLaunchKernelGGL((k_leaf_tree<LR, Leaf>), grid, block, 0, ctx.stream, leaf, tree, log_leaves,    \
-                           finish, ctx.ticket(), kch, root_out, beta_out);                                 \
-    } break;
+    case LR:                                                                                               \
+        TS_LAUNCH_NAMED(ctx, Leaf::name(LR), (k_leaf_tree<LR, Leaf>), grid, block, 0, leaf, tree,          \
+                        log_leaves, finish, ctx.ticket(), kch, root_out, beta_out);                        \
+        break;
     switch (log_r) {
         TS_LEAF_TREE_CASE(0)
         TS_LEAF_TREE_CASE(1)

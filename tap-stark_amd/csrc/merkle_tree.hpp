@@ -138,9 +138,7 @@ struct Tree {
                 b3::hash64(m, cv);
 #pragma unroll
                 for (int w = 0; w < 8; w++) dst[w * CH + i] = cv[w];
-                uint4* o = reinterpret_cast<uint4*>(out + 8 * i);
-                o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-                o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+                b3::store_digest(out + 8 * i, cv);
             }
         } else {
             const uint32_t j = threadIdx.x & 3;
@@ -308,6 +306,24 @@ struct Tree {
         }
     };
 
+    // first-level nodes that are leaf digests, made here: leaf.digest(row, cv) (leaves.hpp) for every node
+    // of the chunk, stored as level 0 (lv.off0 == 0) and written to the LDS image
+    template <class Leaf>
+    struct LeafNodes {
+        Leaf leaf;
+        uint32_t* level0;
+        __device__ __forceinline__ void fill(uint32_t* in, uint64_t node0, uint32_t count) {
+            for (uint32_t n = threadIdx.x; n < count; n += NTH) {
+                uint32_t cv[8];
+                leaf.digest(node0 + n, cv);
+                b3::store_digest(level0 + 8 * (node0 + n), cv);
+#pragma unroll
+                for (int k = 0; k < 8; k++) in[k * CH + n] = cv[k];
+            }
+            b3::lds_barrier();
+        }
+    };
+
     // Every workgroup fetches the transcript's 36 words at its start (one coalesced load that nobody
     // waits for): the workgroup that turns out to be the finisher has them in LDS when it gets there
     // instead of paying a global round trip at the very end of the dependency chain.  The previous
@@ -439,9 +455,7 @@ __device__ __forceinline__ void register_level(uint32_t (*D)[8], const Levels& l
 #pragma unroll
         for (int w = 0; w < 8; w++) D[m][w] = cv[w];
         const uint32_t k = ((uint32_t)(2 * m + (hi ? 1 : 0)) << S) + (tid & ((1u << S) - 1));
-        uint4* o = reinterpret_cast<uint4*>(lv.at(S + 1, (base + 256ull * k + tid) >> (S + 1)));
-        o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-        o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+        b3::store_digest(lv.at(S + 1, (base + 256ull * k + tid) >> (S + 1)), cv);
     }
 }
 
@@ -454,9 +468,7 @@ __device__ __forceinline__ void leaf_rows(Leaf& leaf, uint32_t (*D)[8], const Le
     if constexpr (K < R) {
         const uint64_t row = row0 + 256u * K;
         leaf.digest(row, D[K]);
-        uint4* o = reinterpret_cast<uint4*>(lv.at(0, row));
-        o[0] = make_uint4(D[K][0], D[K][1], D[K][2], D[K][3]);
-        o[1] = make_uint4(D[K][4], D[K][5], D[K][6], D[K][7]);
+        b3::store_digest(lv.at(0, row), D[K]);
         leaf_rows<K + 1, R>(leaf, D, lv, row0);
     }
 }
