@@ -87,7 +87,6 @@ void launch_fri_fold(Context& ctx, const Ef* in, uint64_t h, Ef beta, Ef* out,
 
 // ---- one commit-phase round in one launch (merkle_tree.hpp) ------------------------------------
 // leaves: fri_leaf_digest (leaves.hpp), with the fold of the previous round in it
-static_assert(FRI_ROUND_MAX_LOG == mt::MAX_LOG_TREE, "kernels.hpp and merkle_tree.hpp disagree");
 
 // the round kernel's leaf: as FriLeaf, with the halved challenge computed once per kernel
 template <bool FOLD>
@@ -115,59 +114,82 @@ k_fri_round(const Ef* __restrict__ prev, const uint32_t* __restrict__ tw, const 
     mt::T9::tree_body(lds, s_last, prod, lv, log_leaves, ticket, ch, root_out, beta_out);
 }
 
-// The same round for a TALL vector, through the leaf-tree kernel (leaf_tree.hpp, FriLeaf): a lane folds
-// and hashes R leaves, the first log2(R) levels stay in its registers.  Before round 5 a round above
-// 2^17 leaves was a fold launch, one launch per level and the tree launch.
-bool launch_fri_round_tall(Context& ctx, const Ef* prev, const Ef* d_beta_prev, Ef* cur, uint64_t h,
-                           uint32_t* tree, DevChallenger* ch, uint32_t* root_out, Ef* beta_out,
-                           uint64_t h_global, uint64_t row0) {
-    if (h_global == 0) h_global = h;
-    const unsigned log_h = ceil_log2(h), log_hg = ceil_log2(h_global);
-    TS_REQUIRE((1ull << log_h) == h && (1ull << log_hg) == h_global && row0 + h <= h_global, TS_ERR_INVALID,
-               "fri_round_tall: leaf counts must be powers of two");
-    if (!leaf_tree_enabled(log_h)) {  // the round-4 path: fold (+ leaf digests), levels, tree
-        if (prev != nullptr)
-            launch_fri_fold_dev(ctx, prev, 2 * h, d_beta_prev, cur, tree, 2 * h_global, 2 * row0);
-        else
-            launch_leaf_hash_ef_pairs(ctx, reinterpret_cast<const uint32_t*>(cur), h, tree);
-        return launch_merkle_levels(ctx, tree, log_h, ch, root_out, beta_out);
-    }
-    if (prev != nullptr) {
-        // the fold's output has 2 h_global elements (twiddles of order 4 h_global); this slab's first
-        // output is global element 2 row0
-        ctx.ensure_twiddles(log_hg + 2);
-        launch_leaf_tree(ctx, FriLeaf<true>{prev, ctx.d_twiddle_inv + 2 * h_global + 2 * row0, d_beta_prev, cur},
-                         tree, log_h, ch, root_out, beta_out);
-    } else {
-        launch_leaf_tree(ctx, FriLeaf<false>{nullptr, nullptr, nullptr, cur}, tree, log_h, ch, root_out, beta_out);
-    }
-    return ch != nullptr;
+// ------------------------------------------------------------------ device-side transcript
+// One round of fri/src/prover.rs:113-116 without a host round trip: observe the root that the
+// Merkle kernels just wrote, sample beta, leave both where the host will collect them later.
+__global__ void k_chal_round(DevChallenger* __restrict__ ch, const uint32_t* __restrict__ root,
+                             uint32_t* __restrict__ root_out, Ef* __restrict__ beta_out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) dc_round_one_lane(ch, root, root_out, beta_out);
 }
 
-unsigned fri_round_max_log() {
+// ---- the launcher of a commit-phase round: the one place that chooses the engine ----------------
+// commit rounds up to this many levels take k_fri_round (TS_FRI_ROUND_LOG; 0: never)
+static unsigned fri_round_max_log() {
     static const unsigned v = [] {
         const char* e = getenv("TS_FRI_ROUND_LOG");  // 0: never; up to 22
         const int x = e ? atoi(e) : 17;
-        return (unsigned)(x < 0 ? 0 : x > (int)FRI_ROUND_MAX_LOG ? (int)FRI_ROUND_MAX_LOG : x);
+        return (unsigned)(x < 0 ? 0 : x > (int)mt::MAX_LOG_TREE ? (int)mt::MAX_LOG_TREE : x);
     }();
     return v;
 }
 
-void launch_fri_round(Context& ctx, const Ef* prev, const Ef* d_beta_prev, Ef* cur, uint64_t h,
-                      uint32_t* tree, DevChallenger* ch, uint32_t* root_out, Ef* beta_out) {
-    const unsigned log_h = ceil_log2(h);
-    TS_REQUIRE((1ull << log_h) == h && log_h <= FRI_ROUND_MAX_LOG, TS_ERR_INVALID,
-               "fri_round: leaf count not a power of two <= 2^22");
+// k_fri_round: leaves, tree and the transcript step of a whole vector of at most 2^22 leaves in one launch
+static void launch_fri_round(Context& ctx, const FriRoundLaunch& r, unsigned log_h) {
+    TS_REQUIRE(log_h <= mt::MAX_LOG_TREE, TS_ERR_INVALID, "fri_round: leaf count not a power of two <= 2^22");
     const dim3 grid(1u << (log_h - mt::block_log(log_h)));
-    if (prev != nullptr) {
+    if (r.prev != nullptr) {
         ctx.ensure_twiddles(log_h + 2);  // the fold's output has 2h elements: twiddles of order 4h
-        TS_LAUNCH(ctx, k_fri_round<true>, grid, dim3(mt::NTH), 0, prev, ctx.d_twiddle_inv + 2 * h, d_beta_prev,
-                  cur, tree, log_h, ctx.ticket(), ch, root_out, beta_out);
+        TS_LAUNCH(ctx, k_fri_round<true>, grid, dim3(mt::NTH), 0, r.prev, ctx.d_twiddle_inv + 2 * r.h, r.d_beta_prev,
+                  r.cur, r.tree, log_h, ctx.ticket(), r.ch, r.root_out, r.beta_out);
     } else {
-        TS_LAUNCH(ctx, k_fri_round<false>, grid, dim3(mt::NTH), 0, prev, (const uint32_t*)nullptr,
-                  (const Ef*)nullptr, cur, tree, log_h, ctx.ticket(), ch, root_out, beta_out);
+        TS_LAUNCH(ctx, k_fri_round<false>, grid, dim3(mt::NTH), 0, r.prev, (const uint32_t*)nullptr,
+                  (const Ef*)nullptr, r.cur, r.tree, log_h, ctx.ticket(), r.ch, r.root_out, r.beta_out);
     }
     TS_HIP(hipGetLastError());
+}
+
+// A whole-vector round with a transcript step of at most 2^TS_FRI_ROUND_LOG leaves: k_fri_round.  Every other
+// round -- taller ones, and the sub-tree of a slab (ch == nullptr; one-rank sharded runs included), whose
+// transcript step belongs to the top kernel -- goes through the leaf-tree kernel (leaf_tree.hpp, FriLeaf: a lane
+// folds and hashes R leaves, the first log2(R) levels stay in its registers; one launch from 2^8 to 2^22 leaves),
+// or, with TS_LEAF_TREE=0 or below 2^8 leaves, through a fold / leaf launch, the level launches and the tree launch.
+void launch_fri_commit_round(Context& ctx, const FriRoundLaunch& r) {
+    const uint64_t h = r.h, h_global = r.h_global ? r.h_global : r.h, row0 = r.row0;
+    const unsigned log_h = ceil_log2(h), log_hg = ceil_log2(h_global);
+    TS_REQUIRE((1ull << log_h) == h && (1ull << log_hg) == h_global && row0 + h <= h_global, TS_ERR_INVALID,
+               "fri_commit_round: leaf counts must be powers of two");
+    TS_REQUIRE(r.ch == nullptr || h == h_global, TS_ERR_INVALID,
+               "fri_commit_round: the root of a slab's sub-tree is not the round's root");
+    if (r.ch != nullptr && fri_round_max_log() != 0 && log_h <= fri_round_max_log())
+        return launch_fri_round(ctx, r, log_h);
+    if (leaf_tree_enabled(log_h)) {
+        if (r.prev != nullptr) {
+            // the fold's output has 2 h_global elements (twiddles of order 4 h_global); this slab's first
+            // output is global element 2 row0
+            ctx.ensure_twiddles(log_hg + 2);
+            const uint32_t* tw = ctx.d_twiddle_inv + 2 * h_global + 2 * row0;
+            launch_leaf_tree(ctx, FriLeaf<true>{r.prev, tw, r.d_beta_prev, r.cur}, r.tree, log_h, r.ch, r.root_out,
+                             r.beta_out);
+        } else {
+            launch_leaf_tree(ctx, FriLeaf<false>{nullptr, nullptr, nullptr, r.cur}, r.tree, log_h, r.ch, r.root_out,
+                             r.beta_out);
+        }
+        return;
+    }
+    if (r.prev != nullptr)
+        launch_fri_fold_dev(ctx, r.prev, 2 * h, r.d_beta_prev, r.cur, r.tree, 2 * h_global, 2 * row0);
+    else
+        launch_leaf_hash_ef_pairs(ctx, reinterpret_cast<const uint32_t*>(r.cur), h, r.tree);
+    const bool stepped = launch_merkle_levels(ctx, r.tree, log_h, r.ch, r.root_out, r.beta_out);
+    // No tree kernel ran, so none took the transcript step: the tree is its single leaf.  A whole-vector round
+    // of one leaf is a vector of two values that is still longer than the blowup, i.e. log_blowup = 0, which
+    // the C ABI refuses (abi.cpp load_cfg: log_blowup in [1, 8]).  So this is not reachable through the ABI or
+    // the bindings above it: only a C++ caller of TwoAdicFriPcs with log_blowup = 0 gets here, and only under
+    // TS_FRI_ROUND_LOG=0 (a one-leaf round is within every other setting of it and went to k_fri_round above).
+    if (r.ch != nullptr && !stepped) {
+        TS_LAUNCH(ctx, k_chal_round, dim3(1), dim3(64), 0, r.ch, r.tree, r.root_out, r.beta_out);
+        TS_HIP(hipGetLastError());
+    }
 }
 
 // acc[i] += other[i]   (reference fri/src/prover.rs:124-126)
@@ -179,19 +201,6 @@ __global__ void k_vec_add(Ef* __restrict__ acc, const Ef* __restrict__ other, ui
 void launch_vec_add(Context& ctx, Ef* acc, const Ef* other, uint64_t n) {
     TS_LAUNCH(ctx, k_vec_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, acc,
                        other, n);
-    TS_HIP(hipGetLastError());
-}
-
-// ------------------------------------------------------------------ device-side transcript
-// One round of fri/src/prover.rs:113-116 without a host round trip: observe the root that the
-// Merkle kernels just wrote, sample beta, leave both where the host will collect them later.
-__global__ void k_chal_round(DevChallenger* __restrict__ ch, const uint32_t* __restrict__ root,
-                             uint32_t* __restrict__ root_out, Ef* __restrict__ beta_out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) dc_round_one_lane(ch, root, root_out, beta_out);
-}
-void launch_chal_round(Context& ctx, DevChallenger* ch, const uint32_t* root, uint32_t* root_out,
-                       Ef* beta_out) {
-    TS_LAUNCH(ctx, k_chal_round, dim3(1), dim3(64), 0, ch, root, root_out, beta_out);
     TS_HIP(hipGetLastError());
 }
 

@@ -86,13 +86,10 @@ void launch_merkle_tree_from(Context& ctx, uint32_t* tree, unsigned log_leaves, 
                              DevChallenger* ch, uint32_t* root_out, Ef* beta_out);
 // Leaf digests AND every level in one launch where the shape allows (leaf_tree.hpp; 2^8 leaves and
 // up, rows of at most 256 elements; TS_LEAF_TREE=0 or another shape: launch_leaf_hash +
-// launch_merkle_levels).  Return value as launch_merkle_levels.
+// launch_merkle_levels).  root_out != nullptr: the kernel that makes the root writes it there as well.
 bool leaf_tree_enabled(unsigned log_leaves);
-bool launch_commit_tree(Context& ctx, const LeafMats& mats, unsigned log_leaves, uint32_t* tree,
-                        DevChallenger* ch = nullptr, uint32_t* root_out = nullptr, Ef* beta_out = nullptr);
-bool launch_commit_tree_ef_pairs(Context& ctx, const uint32_t* vec, unsigned log_leaves, uint32_t* tree,
-                                 DevChallenger* ch = nullptr, uint32_t* root_out = nullptr,
-                                 Ef* beta_out = nullptr);
+void launch_commit_tree(Context& ctx, const LeafMats& mats, unsigned log_leaves, uint32_t* tree,
+                        uint32_t* root_out = nullptr);
 // mixed-height batches: one level at a time, with the digests of the rows of the matrices whose
 // height equals the level's node count compressed into the nodes (node = Blake3(node || inj))
 // sharded trees: the G sub-tree roots (gathered, rank order) -> the log2(G) top levels.  `top`
@@ -194,31 +191,32 @@ void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
 // If next_digests != nullptr (h >= 2) also writes the h/2 leaf digests of the next round.
 void launch_fri_fold(Context& ctx, const Ef* in, uint64_t h, Ef beta_canonical, Ef* out,
                      uint32_t* next_digests);
-// same with beta read from device memory (written by launch_chal_round)
+// same with beta read from device memory (written by the round's transcript step)
 // slab form: `in`/`out` hold global outputs [row0, row0 + h) of a fold whose output has h_global
 // rows (h_global = 0: the whole vector, h_global = h, row0 = 0)
 void launch_fri_fold_dev(Context& ctx, const Ef* in, uint64_t h, const Ef* d_beta, Ef* out,
                          uint32_t* next_digests, uint64_t h_global = 0, uint64_t row0 = 0);
-// One commit-phase round in one launch: leaves (cur[2i], cur[2i+1]) hashed, the whole tree built,
-// the root observed and the next challenge sampled.  prev != nullptr: cur (2h elements) is first
-// computed as the fold of prev (4h elements) with the challenge at d_beta_prev, and stored.
-constexpr unsigned FRI_ROUND_MAX_LOG = 22;  // = mt::MAX_LOG_TREE (merkle_tree.hpp)
-void launch_fri_round(Context& ctx, const Ef* prev, const Ef* d_beta_prev, Ef* cur, uint64_t h,
-                      uint32_t* tree, DevChallenger* ch, uint32_t* root_out, Ef* beta_out);
-// The same for a round of any height, through the leaf-tree kernel (leaf_tree.hpp: one launch from 2^8
-// to 2^22 leaves; TS_LEAF_TREE=0 or a smaller round: fold launch, level launches, tree launch).  Slab
-// form as launch_fri_fold_dev, in LEAVES: `cur`/`tree` hold leaves [row0, row0 + h) of a round of
-// h_global leaves (the sub-tree of a sharded prover's slab).  Returns whether the challenger step ran
-// (as launch_merkle_levels).
-bool launch_fri_round_tall(Context& ctx, const Ef* prev, const Ef* d_beta_prev, Ef* cur, uint64_t h,
-                           uint32_t* tree, DevChallenger* ch, uint32_t* root_out, Ef* beta_out,
-                           uint64_t h_global = 0, uint64_t row0 = 0);
-unsigned merkle_tree_max_log();  // trees up to this many levels are one launch (TS_TREE_MAX_LOG)
-unsigned fri_round_max_log();    // commit rounds up to this many levels are one launch (TS_FRI_ROUND_LOG)
-// device-resident transcript (chal_dev.hpp): observe the root at `root`, sample beta
-struct DevChallenger;
-void launch_chal_round(Context& ctx, DevChallenger* ch, const uint32_t* root, uint32_t* root_out,
-                       Ef* beta_out);
+// One commit-phase round (fri/src/prover.rs:113-116): leaves (cur[2i], cur[2i+1]) hashed, the whole tree
+// built and -- with `ch` -- the root observed on the device transcript (chal_dev.hpp) and the next challenge
+// sampled, in as few launches as the shape allows; the launcher owns that choice (fri.hip).
+struct FriRoundLaunch {
+    // != nullptr: cur (2h elements) is first computed as the fold of prev (4h elements) with the challenge
+    // at d_beta_prev, and stored
+    const Ef* prev = nullptr;
+    const Ef* d_beta_prev = nullptr;
+    Ef* cur = nullptr;
+    uint64_t h = 0;  // leaves
+    uint32_t* tree = nullptr;
+    // the transcript step; nullptr: the tree only (the sub-tree of a sharded prover's slab, whose root the
+    // top kernel makes: launch_shard_top)
+    DevChallenger* ch = nullptr;
+    uint32_t* root_out = nullptr;
+    Ef* beta_out = nullptr;
+    // slab form as launch_fri_fold_dev, in LEAVES: `cur`/`tree` hold leaves [row0, row0 + h) of a round of
+    // h_global leaves
+    uint64_t h_global = 0, row0 = 0;
+};
+void launch_fri_commit_round(Context& ctx, const FriRoundLaunch& r);
 // all remaining commit-phase rounds once the vector has <= 2^FRI_TAIL_LOG elements, one workgroup
 constexpr int FRI_TAIL_LOG = 10;
 // pow_out != nullptr: the kernel also grinds (fri/src/prover.rs:43) -- *pow_out = the smallest witness

@@ -169,36 +169,26 @@ bool leaf_tree_enabled(unsigned log_leaves) {
     return on != 0 && log_leaves >= mt::LEAF_TREE_MIN_LOG;
 }
 
-bool launch_commit_tree(Context& ctx, const LeafMats& mats, unsigned log_leaves, uint32_t* tree,
-                        DevChallenger* ch, uint32_t* root_out, Ef* beta_out) {
+void launch_commit_tree(Context& ctx, const LeafMats& mats, unsigned log_leaves, uint32_t* tree,
+                        uint32_t* root_out) {
     const uint64_t height = (uint64_t)1 << log_leaves;
     if (!leaf_tree_enabled(log_leaves) || mats.total_width > 256) {
         launch_leaf_hash(ctx, mats, height, tree);
-        return launch_merkle_levels(ctx, tree, log_leaves, ch, root_out, beta_out);
+        launch_merkle_levels(ctx, tree, log_leaves, nullptr, root_out, nullptr);
+        return;
     }
     TS_REQUIRE(mats.cols != nullptr, TS_ERR_INVALID, "commit_tree: column pointer table missing");
     if (strided(mats))
-        launch_leaf_tree(ctx, strided_leaf(mats), tree, log_leaves, ch, root_out, beta_out);
+        launch_leaf_tree(ctx, strided_leaf(mats), tree, log_leaves, nullptr, root_out, nullptr);
     else
-        launch_leaf_tree(ctx, TableLeaf{mats.cols, mats.total_width}, tree, log_leaves, ch, root_out, beta_out);
-    return ch != nullptr;
-}
-
-bool launch_commit_tree_ef_pairs(Context& ctx, const uint32_t* vec, unsigned log_leaves, uint32_t* tree,
-                                 DevChallenger* ch, uint32_t* root_out, Ef* beta_out) {
-    if (!leaf_tree_enabled(log_leaves)) {
-        launch_leaf_hash_ef_pairs(ctx, vec, (uint64_t)1 << log_leaves, tree);
-        return launch_merkle_levels(ctx, tree, log_leaves, ch, root_out, beta_out);
-    }
-    launch_leaf_tree(ctx, EfPairLeaf{reinterpret_cast<const Ef*>(vec)}, tree, log_leaves, ch, root_out, beta_out);
-    return ch != nullptr;
+        launch_leaf_tree(ctx, TableLeaf{mats.cols, mats.total_width}, tree, log_leaves, nullptr, root_out, nullptr);
 }
 
 // Measured (tools/time_tree.py, us per tree above the leaves, one launch / per-level launches down to
 // 2^16): 2^17 34 / 33, 2^18 60 / 44, 2^20 89 / 71, 2^22 216 / 152.  In one launch the bulk levels run
 // as four-lane compressions out of LDS between workgroup barriers at 3 workgroups per CU, ~19 G
 // compressions/s; k_merkle_level streams them at ~34 G/s.  So the single launch takes over at 2^17.
-unsigned merkle_tree_max_log() {
+static unsigned merkle_tree_max_log() {
     static const unsigned v = [] {
         const char* e = getenv("TS_TREE_MAX_LOG");  // up to 22, for A/B runs
         const int x = e ? atoi(e) : 17;

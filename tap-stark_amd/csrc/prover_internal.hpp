@@ -1,7 +1,8 @@
-// What the three host provers share (prover_common.cpp, and the FRI commit phase in prover.cpp):
+// What the three host provers share (prover_common.cpp, and the FRI commit phase in fri_commit.cpp):
 // prove (prover.cpp), prove_sharded (sharded.cpp) and prove_tap (tap_prover.cpp) run the same pipeline
 // and differ in where the rows live and in the MMCS.
 #pragma once
+#include <functional>
 #include <initializer_list>
 
 #include "host.hpp"
@@ -18,6 +19,18 @@ struct FriRound {
 // Device-side state of one commit phase.  The transcript lives on the device from begin to finish:
 // per round the kernel that makes the root observes it and samples beta (d_betas[r]).
 struct FriCommit {
+    // The vector the next round commits to (`len` elements; of a sharded round: this rank's slab of it).
+    // deferred != nullptr: `cur` is not in memory yet -- it is the fold of the last round's vector (this pointer)
+    // with the last round's challenge, and the next launch computes it while hashing.
+    DevBuf<Ef> cur;
+    const Ef* deferred = nullptr;
+    uint64_t len = 0;
+    // One round on `cur`: allocates the tree (and `cur`, if deferred), launches and records the round, defers the
+    // next vector into the next launch or folds it now, keeps the buffers.  `top` (sharded rounds, with the slab's
+    // coordinates as in FriRoundLaunch): the launch builds the sub-tree only, top(sub-root, round) does the rest.
+    using TopStep = std::function<void(const uint32_t* d_subroot, size_t round)>;
+    void round(Context& ctx, bool defer_next, const TopStep& top = nullptr, uint64_t h_global = 0, uint64_t row0 = 0);
+
     std::vector<FriRound> rounds;
     std::vector<DevBuf<Ef>> keep_vecs;
     std::vector<DevBuf<uint32_t>> keep_trees;
@@ -39,8 +52,8 @@ constexpr size_t FRI_POW_WORD = 40;
 // moves the transcript to the device and sizes the per-round buffers
 void fri_commit_begin(Context& ctx, const FriConfig& fri, unsigned log_max_height,
                       const BfChallenger& challenger, FriCommit& st);
-// prover.rs:111-127 on a vector every rank holds whole: rounds until `blowup` values are left,
-// adding inputs[next_in..] when the folded length reaches theirs (:124-126)
+// prover.rs:111-127 on a vector every rank holds whole (it becomes st.cur): rounds until `blowup` values are
+// left, adding inputs[next_in..] when the folded length reaches theirs (:124-126)
 void fri_commit_rounds(Context& ctx, const FriConfig& fri, DevBuf<Ef> folded, uint64_t len,
                        std::vector<DevBuf<Ef>>& inputs, const std::vector<unsigned>& log_lens,
                        size_t next_in, FriCommit& st);

@@ -306,51 +306,29 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
         StageTimer t(&ctx, "FRI commit phase");
         fri_commit_begin(ctx, fri, log_N, challenger, st);
         d_tops = DevBuf<uint32_t>(&ctx, std::max<size_t>(top_words * st.R_total, 8));
-        uint64_t len = N, loc = loc0;
+        uint64_t len = N;
+        st.cur = std::move(folded);
+        st.len = loc0;
         const uint64_t min_loc = std::max<uint64_t>(2, 1ull << opt.min_local_log);
         auto sharded_round = [&](uint64_t l_glob, uint64_t l_loc) {
             return l_glob > fri.blowup() && l_loc >= min_loc;
         };
-        // != nullptr: `folded` is not in memory yet -- it is the fold of this slab (the last round's)
-        // with the last round's challenge, and the next round's launch computes it while hashing
-        const Ef* prev = nullptr;
-        while (sharded_round(len, loc)) {
-            FriRound r;
-            const uint64_t h_loc = loc / 2, h_glob = len / 2;
-            r.log_leaves = log2_strict(h_loc);
-            const size_t ri = st.rounds.size();
-            DevBuf<uint32_t> tree(&ctx, merkle_total_digests(r.log_leaves) * 8);
-            if (prev) folded = DevBuf<Ef>(&ctx, loc);
-            // the slab's sub-tree: (fold +) leaves + levels in one launch (leaf_tree.hpp)
-            launch_fri_round_tall(ctx, prev, prev ? st.d_betas.p + ri - 1 : nullptr, folded.p, h_loc, tree.p, nullptr,
-                                  nullptr, nullptr, h_glob, (uint64_t)sh.rank * h_loc);
-            // exchange 3; the top kernel observes the root and samples beta on every rank alike
-            gather_top(sh, "FRI round sub-roots", tree.p + 8 * (merkle_total_digests(r.log_leaves) - 1),
-                       d_tops.p + top_words * ri,
-                       st.dch(), st.d_roots.p + 8 * ri, st.d_betas.p + ri);
-            r.vec = folded.p;
-            r.tree = tree.p;
-            if (sharded_round(h_glob, h_loc)) {
-                prev = folded.p;  // fri/src/prover.rs:119 happens inside the next round's launch
-                st.keep_vecs.push_back(std::move(folded));
-            } else {
-                DevBuf<Ef> out(&ctx, h_loc);
-                launch_fri_fold_dev(ctx, folded.p, h_loc, st.d_betas.p + ri, out.p, nullptr, h_glob,
-                                    (uint64_t)sh.rank * h_loc);
-                st.keep_vecs.push_back(std::move(folded));
-                folded = std::move(out);
-                prev = nullptr;
-            }
-            st.keep_trees.push_back(std::move(tree));
-            st.rounds.push_back(r);
+        // exchange 3; the top kernel observes the root and samples beta on every rank alike
+        const FriCommit::TopStep top = [&](const uint32_t* d_subroot, size_t ri) {
+            gather_top(sh, "FRI round sub-roots", d_subroot, d_tops.p + top_words * ri, st.dch(),
+                       st.d_roots.p + 8 * ri, st.d_betas.p + ri);
+        };
+        while (sharded_round(len, st.len)) {
+            // the slab's sub-tree, then `top`; the next slab is folded now if the next round is replicated
+            const uint64_t h_glob = len / 2, h_loc = st.len / 2;
+            st.round(ctx, /*defer_next=*/sharded_round(h_glob, h_loc), top, h_glob, (uint64_t)sh.rank * h_loc);
             len = h_glob;
-            loc = h_loc;
             R_sh++;
         }
         // exchange 4: the rest is short; every rank folds the whole vector
         DevBuf<Ef> full(&ctx, len);
-        coll_all_gather(ctx, comm, "FRI vector", folded.p, full.p, (size_t)loc * sizeof(Ef));
-        st.keep_vecs.push_back(std::move(folded));
+        coll_all_gather(ctx, comm, "FRI vector", st.cur.p, full.p, (size_t)st.len * sizeof(Ef));
+        st.keep_vecs.push_back(std::move(st.cur));
         std::vector<DevBuf<Ef>> no_inputs;
         fri_commit_rounds(ctx, fri, std::move(full), len, no_inputs, {}, 0, st);
         tops.resize(std::max<size_t>(top_words * R_sh, 8));

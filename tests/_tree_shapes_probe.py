@@ -1,6 +1,6 @@
 """Helper of test_gpu_mmcs.py::test_tree_launch_shapes_agree (run as a child process, because the
 launch-shape knobs are read once per process): prints the roots of a few trees, an opened path and
-the hash of a proof as JSON."""
+the hashes of a few proofs as JSON."""
 import hashlib
 import json
 import os
@@ -11,6 +11,21 @@ import numpy as np
 
 import tapstark_amd as ts
 from tapstark_amd.airs import FibonacciAir, SynthMulAir, generate_synth_mul_trace, splitmix64_stream
+
+
+_fri_inputs = []  # the CPU oracle's LDEs, made once per process
+
+
+def fri_inputs():
+    # as the third case of test_gpu_parity.py::test_fri_prove_alone_matches_oracle: log_blowup 2, degrees
+    # 2^3, 2^9, 2^14, 2^15 (gaps between the heights), the tallest vector 2^17
+    if not _fri_inputs:
+        from oracle import oracle_py as orc
+        from test_abi_cpu import _fri_rs_inputs
+
+        orc.build()
+        _fri_inputs.extend(_fri_rs_inputs(orc, 2, [3, 9, 14, 15]))
+    return _fri_inputs
 
 
 def probe():
@@ -42,6 +57,12 @@ def probe():
     proof = ts.prove(config, cair, ts.BfChallenger(), trace, np.zeros(0, dtype=np.uint32))
     ts.verify(config, cair, ts.BfChallenger(), proof, np.zeros(0, dtype=np.uint32))
     out["proof_mul3"] = hashlib.sha256(proof.words.tobytes()).hexdigest()
+    # FRI alone over inputs of several heights: the commit phase defers a fold into the next launch, folds now
+    # where an input joins, and hands over to the tail kernel, through whichever round engine the knobs pick
+    pcs = ts.TwoAdicFriPcs(ts.FriConfig(2, 7, 8), ctx)
+    fri_proof = pcs.fri_prove(fri_inputs(), ts.BfChallenger(0, True))
+    pcs.fri_verify(fri_proof, ts.BfChallenger(0, True))
+    out["fri_alone"] = hashlib.sha256(fri_proof.tobytes()).hexdigest()
     return out
 
 

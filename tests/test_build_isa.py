@@ -63,4 +63,4 @@ def test_leaf_tree_handoff_isa(merkle_isa, fri_isa):
         for name, lines in _kernel(isa, "k_leaf_tree"):
             _check_handoff(name, lines)
             n += 1
-    assert n == 20  # (strided, table, ef_pairs, fri_fold, fri_leaf) x (1, 2, 4, 8 leaves per lane)
+    assert n == 16  # (strided, table, fri_fold, fri_leaf) x (1, 2, 4, 8 leaves per lane)
