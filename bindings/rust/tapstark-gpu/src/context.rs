@@ -71,6 +71,31 @@ impl<'c> DeviceMatrix<'c> {
         );
         Self { ctx, raw }
     }
+    pub fn dims(&self) -> (usize, usize) {
+        let (mut h, mut w) = (0u64, 0u32);
+        unsafe { ts_matrix_dims(self.raw, &mut h, &mut w) };
+        (h as usize, w as usize)
+    }
+    /// row-major, natural rows, canonical words
+    pub fn download(&self) -> Vec<u32> {
+        let (h, w) = self.dims();
+        let mut words = vec![0u32; h * w];
+        self.ctx.check(unsafe { ts_matrix_download(self.ctx.raw, self.raw, words.as_mut_ptr()) }, "ts_matrix_download");
+        words
+    }
+    /// `bit_reverse_rows().to_row_major_matrix()` as a new device matrix
+    pub fn bit_reverse_rows(&self) -> Self {
+        let mut raw = ptr::null_mut();
+        self.ctx.check(unsafe { ts_matrix_bit_reverse_rows(self.ctx.raw, self.raw, &mut raw) }, "ts_matrix_bit_reverse_rows");
+        Self { ctx: self.ctx, raw }
+    }
+    /// Row-major device pointer for the caller's own kernels: valid until the matrix is dropped or
+    /// consumed, ordered on the context's stream.
+    pub fn device_ptr(&mut self) -> *const u32 {
+        let mut p = ptr::null();
+        self.ctx.check(unsafe { ts_matrix_device_ptr(self.ctx.raw, self.raw, &mut p) }, "ts_matrix_device_ptr");
+        p
+    }
     pub(crate) fn into_raw(mut self) -> *mut ts_matrix {
         core::mem::replace(&mut self.raw, ptr::null_mut())
     }

@@ -110,6 +110,14 @@ extern "C" {
     pub fn ts_matrix_dims(m: *const ts_matrix, height: *mut u64, width: *mut u32) -> ts_status;
     pub fn ts_matrix_free(ctx: *mut ts_ctx, m: *mut ts_matrix);
 
+    pub fn ts_matrix_device_ptr(ctx: *mut ts_ctx, m: *mut ts_matrix, ptr: *mut *const u32) -> ts_status;
+    // TwoAdicSubgroupDft on device matrices (csrc/ntt_dft.hip): the input is read, a new matrix returned
+    pub fn ts_dft_batch(ctx: *mut ts_ctx, input: *const ts_matrix, inverse: c_int, shift: u32,
+                        out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_coset_lde_batch(ctx: *mut ts_ctx, input: *const ts_matrix, added_bits: u32, shift: u32,
+                              bit_reversed: c_int, out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_matrix_bit_reverse_rows(ctx: *mut ts_ctx, input: *const ts_matrix, out: *mut *mut ts_matrix) -> ts_status;
+
     pub fn ts_air_compile(ctx: *mut ts_ctx, tape: *const u32, n_words: usize, out: *mut *mut ts_air) -> ts_status;
     pub fn ts_air_info(air: *const ts_air, width: *mut u32, n_public: *mut u32, max_degree: *mut u32,
                        log_quotient_degree: *mut u32) -> ts_status;
@@ -127,6 +135,8 @@ extern "C" {
     pub fn ts_pcs_data_info(d: *const ts_pcs_data, n_mats: *mut u32, log_height: *mut u32) -> ts_status;
     pub fn ts_pcs_data_matrix_info(d: *const ts_pcs_data, idx: u32, height: *mut u64, width: *mut u32) -> ts_status;
     pub fn ts_pcs_data_lde(ctx: *mut ts_ctx, d: *const ts_pcs_data, idx: u32, host_row_major: *mut u32) -> ts_status;
+    pub fn ts_pcs_data_evaluations_on_domain(ctx: *mut ts_ctx, d: *const ts_pcs_data, idx: u32, log_size: u32,
+                                             out: *mut *mut ts_matrix) -> ts_status;
     pub fn ts_pcs_data_free(ctx: *mut ts_ctx, d: *mut ts_pcs_data);
     pub fn ts_quotient_chunks(ctx: *mut ts_ctx, trace_data: *const ts_pcs_data, log_blowup: u32,
                               air: *const ts_air, public_values: *const u32, n_public: u32,

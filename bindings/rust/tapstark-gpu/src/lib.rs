@@ -3,7 +3,9 @@
 //! **Uncompiled in this repository's pipeline** (no Rust toolchain in the build image; see
 //! Cargo.toml).  Written against tap-stark at the commit SURVEY.md names and include/tapstark.h
 //! ABI version 5.  The tested callers of the same C ABI are the ctypes binding
-//! (tap-stark_amd/stark.py) and examples/fib_air.cpp.
+//! (tap-stark_amd/stark.py) and examples/fib_air.cpp.  That holds for `GpuDft` (pcs.rs: `TwoAdicSubgroupDft`
+//! over ts_dft_batch / ts_coset_lde_batch) and the device form of `get_evaluations_on_domain` as well: source
+//! only, never compiled.
 //!
 //! ```ignore
 //! // uni-stark/tests/fib_air.rs:117-149 with the GPU prover
@@ -27,7 +29,7 @@ pub mod tap;
 pub use air::serialize_constraints;
 pub use comm::{prove_gpu_sharded, rccl_unique_id, RcclComm};
 pub use context::{DeviceMatrix, GpuChallenger, GpuContext};
-pub use pcs::{FriConfig, GpuFriPcs, GpuPcsError, GpuProverData};
+pub use pcs::{FriConfig, GpuDft, GpuFriPcs, GpuPcsError, GpuProverData};
 pub use proof::Proof;
 pub use prove::{prove_gpu, prove_gpu_batch, prove_gpu_stepwise, BatchError, BatchStatement, CompiledAir};
 pub use tap::{prove_gpu_tap, verify_gpu_tap, GpuTapProof, GpuTapProverData, GpuTapTreeMmcs, LockTable};

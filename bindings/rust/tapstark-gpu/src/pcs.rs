@@ -11,7 +11,6 @@ use std::ptr;
 use basic::bf_pcs::{OpenedValues as PcsOpenedValues, Pcs};
 use p3_commit::{PolynomialSpace, TwoAdicMultiplicativeCoset};
 use p3_field::{AbstractExtensionField, AbstractField, PrimeField32};
-use p3_matrix::bitrev::BitReversableMatrix;
 use p3_matrix::dense::RowMajorMatrix;
 use p3_matrix::Matrix;
 
@@ -86,6 +85,86 @@ impl<'c> GpuFriPcs<'c> {
     }
 }
 
+impl<'c> GpuFriPcs<'c> {
+    /// `get_evaluations_on_domain` without the download: the first 2^log_size rows of committed LDE `idx`,
+    /// un-bit-reversed, as a device matrix (two_adic_pcs.rs:256-257)
+    pub fn evaluations_on_domain_device(&self, prover_data: &GpuProverData<'c>, idx: usize,
+                                        log_size: usize) -> DeviceMatrix<'c> {
+        let mut raw = ptr::null_mut();
+        self.ctx.check(
+            unsafe {
+                ts_pcs_data_evaluations_on_domain(self.ctx.raw, prover_data.raw, idx as u32, log_size as u32, &mut raw)
+            },
+            "ts_pcs_data_evaluations_on_domain",
+        );
+        DeviceMatrix { ctx: self.ctx, raw }
+    }
+}
+
+/// `TwoAdicSubgroupDft` (p3-dft; the `Dft` of `TwoAdicFriPcs::new`, two_adic_pcs.rs:38-55) on the device.
+/// The trait works on host matrices, so every call uploads its argument and downloads its result; a caller
+/// that keeps its matrices in HBM uses the `*_device` methods, which take and return `DeviceMatrix`.
+#[derive(Clone, Copy)]
+pub struct GpuDft<'c> {
+    pub ctx: &'c GpuContext,
+}
+
+impl<'c> GpuDft<'c> {
+    /// `coset_dft_batch` (inverse = false) / `coset_idft_batch` (inverse = true); shift 1 = the subgroup
+    pub fn dft_device(&self, m: &DeviceMatrix<'c>, inverse: bool, shift: Val) -> DeviceMatrix<'c> {
+        let mut raw = ptr::null_mut();
+        self.ctx.check(
+            unsafe { ts_dft_batch(self.ctx.raw, m.raw, inverse as i32, shift.as_canonical_u32(), &mut raw) },
+            "ts_dft_batch",
+        );
+        DeviceMatrix { ctx: self.ctx, raw }
+    }
+    /// `coset_lde_batch`, optionally followed by `bit_reverse_rows` (what `Pcs::commit` stores)
+    pub fn coset_lde_device(&self, m: &DeviceMatrix<'c>, added_bits: usize, shift: Val,
+                            bit_reversed: bool) -> DeviceMatrix<'c> {
+        let mut raw = ptr::null_mut();
+        self.ctx.check(
+            unsafe {
+                ts_coset_lde_batch(self.ctx.raw, m.raw, added_bits as u32, shift.as_canonical_u32(),
+                                   bit_reversed as i32, &mut raw)
+            },
+            "ts_coset_lde_batch",
+        );
+        DeviceMatrix { ctx: self.ctx, raw }
+    }
+    fn up(&self, mat: &RowMajorMatrix<Val>) -> DeviceMatrix<'c> {
+        let words: Vec<u32> = mat.values.iter().map(|v| v.as_canonical_u32()).collect();
+        DeviceMatrix::upload(self.ctx, &words, mat.height(), mat.width())
+    }
+    fn down(m: DeviceMatrix<'c>) -> RowMajorMatrix<Val> {
+        let width = m.dims().1;
+        RowMajorMatrix::new(m.download().into_iter().map(Val::from_canonical_u32).collect(), width)
+    }
+}
+
+impl<'c> p3_dft::TwoAdicSubgroupDft<Val> for GpuDft<'c> {
+    type Evaluations = RowMajorMatrix<Val>;
+
+    fn dft_batch(&self, mat: RowMajorMatrix<Val>) -> Self::Evaluations {
+        Self::down(self.dft_device(&self.up(&mat), false, Val::one()))
+    }
+    fn coset_dft_batch(&self, mat: RowMajorMatrix<Val>, shift: Val) -> Self::Evaluations {
+        Self::down(self.dft_device(&self.up(&mat), false, shift))
+    }
+    fn idft_batch(&self, mat: RowMajorMatrix<Val>) -> RowMajorMatrix<Val> {
+        Self::down(self.dft_device(&self.up(&mat), true, Val::one()))
+    }
+    fn coset_idft_batch(&self, mat: RowMajorMatrix<Val>, shift: Val) -> RowMajorMatrix<Val> {
+        Self::down(self.dft_device(&self.up(&mat), true, shift))
+    }
+    fn lde_batch(&self, mat: RowMajorMatrix<Val>, added_bits: usize) -> Self::Evaluations {
+        Self::down(self.coset_lde_device(&self.up(&mat), added_bits, Val::one(), false))
+    }
+    fn coset_lde_batch(&self, mat: RowMajorMatrix<Val>, added_bits: usize, shift: Val) -> Self::Evaluations {
+        Self::down(self.coset_lde_device(&self.up(&mat), added_bits, shift, false))
+    }
+}
+
 impl<'c> Pcs<Challenge, GpuChallenger> for GpuFriPcs<'c> {
     type Domain = TwoAdicMultiplicativeCoset<Val>;
     type Commitment = Commitment;
@@ -134,21 +213,17 @@ impl<'c> Pcs<Challenge, GpuChallenger> for GpuFriPcs<'c> {
         (vec![root.map(u32::to_le_bytes)], GpuProverData { ctx: self.ctx, raw, dims })
     }
 
-    /// two_adic_pcs.rs:247-258 -- the slow, host-side form the trait demands (used by callers that
-    /// really want the evaluations; `prove_gpu` uses `quotient_chunks` instead)
+    /// two_adic_pcs.rs:247-258.  The trait demands a HOST matrix; the rows are cut and un-bit-reversed on
+    /// the device (`ts_pcs_data_evaluations_on_domain`), so domain.size() * width words cross PCIe, not the
+    /// whole N x width LDE.  `evaluations_on_domain_device` below keeps them in HBM.
     fn get_evaluations_on_domain<'a>(&self, prover_data: &'a Self::ProverData, idx: usize,
                                      domain: Self::Domain) -> impl Matrix<Val> + 'a {
         assert_eq!(domain.shift, Val::generator()); // :254
         let (height, width) = prover_data.dims[idx];
         assert!(height >= domain.size()); // :256
-        let mut words = vec![0u32; height * width];
-        self.ctx.check(
-            unsafe { ts_pcs_data_lde(self.ctx.raw, prover_data.raw, idx as u32, words.as_mut_ptr()) },
-            "ts_pcs_data_lde",
-        );
-        words.truncate(domain.size() * width); // split_rows(domain.size()).0
+        let words = self.evaluations_on_domain_device(prover_data, idx, domain.log_n).download();
         let vals: Vec<Val> = words.into_iter().map(Val::from_canonical_u32).collect();
-        RowMajorMatrix::new(vals, width).bit_reverse_rows()
+        RowMajorMatrix::new(vals, width)
     }
 
     /// two_adic_pcs.rs:260-419

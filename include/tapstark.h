@@ -118,6 +118,33 @@ ts_status ts_matrix_dims(const ts_matrix* m, uint64_t* height, uint32_t* width);
 ts_status ts_matrix_download(ts_ctx* ctx, const ts_matrix* m, uint32_t* host_row_major);
 void ts_matrix_free(ts_ctx* ctx, ts_matrix* m);
 
+/* The row-major device pointer of a matrix (natural rows, canonical words), for a caller's own kernels --
+ * their quotient, a lookup argument -- to read what the calls below return; ts_matrix_from_device is the
+ * opposite direction.  Valid until the matrix is freed or consumed; ordered on the context's stream
+ * (ts_ctx_stream): work enqueued there, or after ts_ctx_synchronize, sees the values.  Read-only. */
+ts_status ts_matrix_device_ptr(ts_ctx* ctx, ts_matrix* m, const uint32_t** ptr);
+
+/* ------------------------------------------------------------------ Dft (TwoAdicSubgroupDft) */
+/* The `Dft` of TwoAdicFriPcs::new(log_n, dft, mmcs, fri_config) (fri/src/two_adic_pcs.rs:38-55;
+ * Radix2DitParallel in uni-stark/tests/fib_air.rs:113-115), the Plonky3 p3-dft trait of SURVEY.md App. A.5,
+ * on device matrices.  Every call runs on the context's stream, only READS `in` (it is not consumed) and
+ * returns a new matrix: row-major, natural rows unless stated, canonical values.  Heights are powers of
+ * two; height 1 is the identity.  TS_ERR_INVALID (text in ts_last_error) for shift == 0 or shift >= p, a
+ * height that is no power of two, a ts_dft_batch input above 2^26 rows or a ts_coset_lde_batch result above
+ * 2^27 rows (the tallest input / LDE of ts_pcs_commit).
+ * ts_dft_batch: inverse = 0 is coset_dft_batch -- per column, out row k = sum_j in[j] (shift w_n^k)^j
+ *   (shift = 1: dft_batch); inverse = 1 is coset_idft_batch -- the coefficients of the interpolant of `in`
+ *   over shift * H_n, 1/n included (shift = 1: idft_batch). */
+ts_status ts_dft_batch(ts_ctx* ctx, const ts_matrix* in, int inverse, uint32_t shift, ts_matrix** out);
+/* coset_lde_batch (App. A.5; what Pcs::commit calls, fri/src/two_adic_pcs.rs:233-241): `in` holds
+ * evaluations over H_n; out is (n << added_bits) x width, row j = the interpolant at shift * w_N^j, or row
+ * bitrev(j) with bit_reversed = 1 (`.bit_reverse_rows()`: then word for word the ts_pcs_data_lde of a
+ * ts_pcs_commit with domain shift 31 / shift, :235).  shift = 1 is lde_batch; added_bits = 0 is allowed. */
+ts_status ts_coset_lde_batch(ts_ctx* ctx, const ts_matrix* in, uint32_t added_bits, uint32_t shift,
+                             int bit_reversed, ts_matrix** out);
+/* Matrix::bit_reverse_rows().to_row_major_matrix() (p3-matrix, used at fri/src/two_adic_pcs.rs:239,257) */
+ts_status ts_matrix_bit_reverse_rows(ts_ctx* ctx, const ts_matrix* in, ts_matrix** out);
+
 /* ------------------------------------------------------------------ AIR */
 /* Tape = serialised result of get_symbolic_constraints (uni-stark/src/symbolic_builder.rs:52-64):
  *   [0]=0x54415354 [1]=1 [2]=width [3]=n_public [4]=n_nodes [5]=n_constraints,
@@ -208,6 +235,13 @@ ts_status ts_mmcs_commit(ts_ctx* ctx, uint32_t n_mats, ts_matrix* const* mats, u
 /* BFMmcs::get_matrices (basic/src/mmcs/bf_mmcs.rs:52): committed LDE `idx`, row-major,
  * bit-reversed row order, N x width */
 ts_status ts_pcs_data_lde(ts_ctx* ctx, const ts_pcs_data* d, uint32_t idx, uint32_t* host_row_major);
+/* Pcs::get_evaluations_on_domain (fri/src/two_adic_pcs.rs:247-258) kept on the device: the first
+ * 2^log_size rows of committed LDE `idx`, un-bit-reversed (:257), as a row-major 2^log_size x width matrix --
+ * the evaluations on the coset 31 * H_{2^log_size} for a matrix committed on its natural domain.  Works
+ * for the shorter matrices of a mixed-height batch.  TS_ERR_INVALID if 2^log_size exceeds that matrix's
+ * LDE height (:256 asserts) or idx is out of range. */
+ts_status ts_pcs_data_evaluations_on_domain(ts_ctx* ctx, const ts_pcs_data* d, uint32_t idx, uint32_t log_size,
+                                            ts_matrix** out);
 ts_status ts_pcs_data_info(const ts_pcs_data* d, uint32_t* n_mats, uint32_t* log_height);
 /* height (LDE rows) and width of committed matrix `idx`; log_height above is the tallest one's */
 ts_status ts_pcs_data_matrix_info(const ts_pcs_data* d, uint32_t idx, uint64_t* height, uint32_t* width);

@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "ts_taptree_verify_inclusion", "ts_taptree_free", "ts_tap_mmcs_commit", "ts_tap_mmcs_info",
     "ts_tap_mmcs_open_batch", "ts_tap_mmcs_verify_batch", "ts_tap_mmcs_free",
     "ts_prove_tap", "ts_prove_tap_sharded", "ts_verify_tap",
+    "ts_dft_batch", "ts_coset_lde_batch", "ts_matrix_bit_reverse_rows", "ts_pcs_data_evaluations_on_domain",
+    "ts_matrix_device_ptr",
 ]
 
 STATUS = {0: "TS_OK", 1: "TS_ERR_INVALID", 2: "TS_ERR_HIP", 3: "TS_ERR_OOM",
@@ -254,5 +256,10 @@ def lib() -> C.CDLL:
                                            C.POINTER(C.c_int64)]
         l.ts_verify.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, u32p, C.c_size_t, u32p,
                                 C.c_uint32, C.POINTER(C.c_int)]
+        l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
+        l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
+        l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]
+        l.ts_pcs_data_evaluations_on_domain.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, voidpp]
+        l.ts_matrix_device_ptr.argtypes = [C.c_void_p, C.c_void_p, voidpp]
         _lib = l
     return _lib

@@ -459,6 +459,99 @@ void ts_matrix_free(ts_ctx* ctx, ts_matrix* m) {
     delete m;
 }
 
+// ------------------------------------------------------------------ transforms on device matrices
+// (TwoAdicSubgroupDft; kernels in ntt_dft.hip).  The input is only read.
+namespace {
+
+std::unique_ptr<ts_matrix> new_row_major(ts_ctx* ctx, uint64_t height, uint32_t width) {
+    auto m = std::make_unique<ts_matrix>();
+    m->m.buf = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)height * width);
+    m->m.height = height;
+    m->m.width = width;
+    m->m.layout = ts::DeviceMatrix::ROW_MAJOR;
+    return m;
+}
+
+// the matrix as row-major words with natural rows: its own buffer, or -- for one made on the device in
+// column-major form (quotient chunks) -- a copy in `tmp`
+const uint32_t* row_major_words(ts_ctx* ctx, const ts::DeviceMatrix& m, ts::DevBuf<uint32_t>& tmp) {
+    TS_REQUIRE(m.buf.p, ts::TS_ERR_INVALID, "matrix was consumed");
+    if (m.layout == ts::DeviceMatrix::ROW_MAJOR) return m.buf.p;
+    tmp = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)m.height * m.width);
+    ts::launch_transpose_unbitrev(ctx->ctx, m.buf.p, m.height, tmp.p, ts::log2_strict(m.height), m.width);
+    return tmp.p;
+}
+
+void check_shift(uint32_t shift) {
+    TS_REQUIRE(shift != 0 && shift < ts::P, ts::TS_ERR_INVALID, "coset shift must be in [1, p)");
+}
+
+}  // namespace
+
+ts_status ts_dft_batch(ts_ctx* ctx, const ts_matrix* in, int inverse, uint32_t shift, ts_matrix** out) {
+    if (!ctx || !in || !out) return TS_ERR_INVALID;
+    *out = nullptr;
+    return guard(ctx, [&] {
+        check_shift(shift);
+        const unsigned log_n = ts::log2_strict(in->m.height);
+        TS_REQUIRE(log_n <= 26, ts::TS_ERR_INVALID, "dft: height above 2^26, the tallest matrix ts_pcs_commit accepts");
+        ts::DevBuf<uint32_t> tmp;
+        const uint32_t* src = row_major_words(ctx, in->m, tmp);
+        auto m = new_row_major(ctx, in->m.height, in->m.width);
+        if (log_n == 0)  // one point: the polynomial is its value
+            TS_HIP(hipMemcpyAsync(m->m.buf.p, src, (size_t)in->m.width * 4, hipMemcpyDeviceToDevice, ctx->ctx.stream));
+        else
+            ts::dft_batch(ctx->ctx, src, m->m.buf.p, log_n, in->m.width, inverse != 0, shift);
+        *out = m.release();
+    });
+}
+
+ts_status ts_coset_lde_batch(ts_ctx* ctx, const ts_matrix* in, uint32_t added_bits, uint32_t shift, int bit_reversed,
+                             ts_matrix** out) {
+    if (!ctx || !in || !out) return TS_ERR_INVALID;
+    *out = nullptr;
+    return guard(ctx, [&] {
+        check_shift(shift);
+        const unsigned log_n = ts::log2_strict(in->m.height);
+        TS_REQUIRE(added_bits <= 27 && log_n + added_bits <= 27, ts::TS_ERR_INVALID,
+                   "coset_lde_batch: result above 2^27 rows, the tallest LDE ts_pcs_commit makes");
+        ts::DevBuf<uint32_t> tmp;
+        const uint32_t* src = row_major_words(ctx, in->m, tmp);
+        auto m = new_row_major(ctx, in->m.height << added_bits, in->m.width);
+        ts::coset_lde_batch(ctx->ctx, src, m->m.buf.p, log_n, in->m.width, added_bits, shift, bit_reversed != 0);
+        *out = m.release();
+    });
+}
+
+ts_status ts_matrix_bit_reverse_rows(ts_ctx* ctx, const ts_matrix* in, ts_matrix** out) {
+    if (!ctx || !in || !out) return TS_ERR_INVALID;
+    *out = nullptr;
+    return guard(ctx, [&] {
+        const unsigned log_h = ts::log2_strict(in->m.height);
+        ts::DevBuf<uint32_t> tmp;
+        const uint32_t* src = row_major_words(ctx, in->m, tmp);
+        auto m = new_row_major(ctx, in->m.height, in->m.width);
+        ts::launch_bit_reverse_rows(ctx->ctx, src, m->m.buf.p, log_h, in->m.width);
+        *out = m.release();
+    });
+}
+
+ts_status ts_matrix_device_ptr(ts_ctx* ctx, ts_matrix* m, const uint32_t** ptr) {
+    if (!ctx || !m || !ptr) return TS_ERR_INVALID;
+    *ptr = nullptr;
+    return guard(ctx, [&] {
+        TS_REQUIRE(m->m.buf.p, ts::TS_ERR_INVALID, "matrix was consumed");
+        if (m->m.layout != ts::DeviceMatrix::ROW_MAJOR) {
+            // made on the device in column-major form: the handle takes the row-major copy (same values)
+            ts::DevBuf<uint32_t> tmp;
+            row_major_words(ctx, m->m, tmp);
+            m->m.buf = std::move(tmp);
+            m->m.layout = ts::DeviceMatrix::ROW_MAJOR;
+        }
+        *ptr = m->m.buf.p;
+    });
+}
+
 // ------------------------------------------------------------------ AIR
 // ctx == NULL: a host-only AIR (no GPU needed), usable by ts_verify
 static ts_status air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, uint32_t segment_instr,
@@ -622,6 +715,22 @@ ts_status ts_pcs_data_lde(ts_ctx* ctx, const ts_pcs_data* d, uint32_t idx, uint3
         ts::launch_transpose_to_row_major(ctx->ctx, cm.d, cm.col_stride, rm.p, cm.height, cm.width);
         TS_HIP(hipMemcpyAsync(host, rm.p, words * 4, hipMemcpyDeviceToHost, ctx->ctx.stream));
         ctx->ctx.sync();
+    });
+}
+ts_status ts_pcs_data_evaluations_on_domain(ts_ctx* ctx, const ts_pcs_data* d, uint32_t idx, uint32_t log_size,
+                                            ts_matrix** out) {
+    if (!ctx || !d || !d->d || !out) return TS_ERR_INVALID;
+    *out = nullptr;
+    return guard(ctx, [&] {
+        TS_REQUIRE(idx < d->d->ldes.size(), ts::TS_ERR_INVALID, "evaluations_on_domain: matrix index out of range");
+        const ts::ColMat& cm = d->d->ldes[idx];
+        // two_adic_pcs.rs:256: assert!(lde.height() >= domain.size())
+        TS_REQUIRE(log_size <= 27 && (1ull << log_size) <= cm.height, ts::TS_ERR_INVALID,
+                   "evaluations_on_domain: domain larger than the committed LDE");
+        auto m = new_row_major(ctx, 1ull << log_size, cm.width);
+        // :257 lde.split_rows(domain.size()).0.bit_reverse_rows()
+        ts::launch_transpose_unbitrev(ctx->ctx, cm.d, cm.col_stride, m->m.buf.p, log_size, cm.width);
+        *out = m.release();
     });
 }
 ts_status ts_pcs_data_matrix_info(const ts_pcs_data* d, uint32_t idx, uint64_t* height, uint32_t* width) {

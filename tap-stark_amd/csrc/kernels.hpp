@@ -53,6 +53,27 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
                uint32_t beta0 = 0, uint32_t n_beta = 0, bool first_round_done = false,
                uint32_t* evals2 = nullptr, uint32_t shift2 = 0, uint32_t gw = 0);
 
+// ---- ntt_dft.hip -----------------------------------------------------------------------------
+// TwoAdicSubgroupDft on its own.  Row-major matrices are 2^log_n x w, natural rows,
+// canonical; `in` is only read, `out` is another buffer.
+// In place on `ncols` column-major columns: forward = natural coefficients -> evaluations over shift * H_n
+// in bit-reversed order; inverse = bit-reversed evaluations over shift * H_n -> natural coefficients (1/n
+// included).  Heights up to 2^26.
+void dft_columns(Context& ctx, uint32_t* cols, uint64_t col_stride, uint32_t ncols, unsigned log_n, bool inverse,
+                 uint32_t shift);
+// coset_dft_batch (inverse = false: out row k = sum_j in[j] (shift w_n^k)^j) / coset_idft_batch
+void dft_batch(Context& ctx, const uint32_t* in, uint32_t* out, unsigned log_n, uint32_t w, bool inverse,
+               uint32_t shift);
+// coset_lde_batch: out ((n << added_bits) x w) row j = the interpolant of `in` over H_n at shift * w_N^j, or
+// row bitrev(j) with bit_reversed (then the rows of Pcs::commit's LDE for shift = 31 / domain shift)
+void coset_lde_batch(Context& ctx, const uint32_t* in, uint32_t* out, unsigned log_n, uint32_t w, unsigned added_bits,
+                     uint32_t shift, bool bit_reversed);
+// dst row-major (2^log_h x w, natural rows)  <-  src column-major, rows p < 2^log_h in bit-reversed order
+void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_stride, uint32_t* dst,
+                               unsigned log_h, uint32_t w);
+// bit_reverse_rows().to_row_major_matrix(): dst[r] = src[bitrev(r)], both row-major 2^log_h x w
+void launch_bit_reverse_rows(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_h, uint32_t w);
+
 // ---- merkle.hip ------------------------------------------------------------------------------
 constexpr int MAX_BATCH_MATS = 64;
 struct LeafMats {

@@ -223,12 +223,67 @@ class DeviceMatrix:
         self.ctx.check(self.ctx._l.ts_matrix_download(self.ctx.h, self.h, _p(out)))
         return out
 
+    def bit_reverse_rows(self) -> "DeviceMatrix":
+        """``bit_reverse_rows().to_row_major_matrix()`` as a new matrix (``ts_matrix_bit_reverse_rows``)."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_matrix_bit_reverse_rows(self.ctx.h, self.h, C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
+
+    def device_ptr(self) -> int:
+        """Row-major device pointer (``ts_matrix_device_ptr``): valid until the matrix is freed or consumed,
+        ordered on the context's stream; ``from_device_ptr`` is the opposite direction."""
+        ptr = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_matrix_device_ptr(self.ctx.h, self.h, C.byref(ptr)))
+        return int(ptr.value or 0)
+
     def __del__(self):
         try:
             if self.h and self.ctx.h:
                 self.ctx._l.ts_matrix_free(self.ctx.h, self.h)
         except Exception:
             pass
+
+
+class Radix2Dft:
+    """``TwoAdicSubgroupDft`` (the ``Dft`` of ``TwoAdicFriPcs::new``, fri/src/two_adic_pcs.rs:38-55;
+    SURVEY.md App. A.5) on device matrices.  Every method takes a ``DeviceMatrix`` (or host values, which are
+    uploaded), leaves it as it is and returns a new ``DeviceMatrix``: row-major, natural rows, canonical."""
+
+    def __init__(self, ctx: "Context | None" = None):
+        self.ctx = ctx or default_context()
+
+    def _mat(self, m) -> "DeviceMatrix":
+        return m if isinstance(m, DeviceMatrix) else DeviceMatrix.upload(self.ctx, m)
+
+    def _dft(self, m, inverse: bool, shift: int) -> "DeviceMatrix":
+        m, h = self._mat(m), C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_dft_batch(self.ctx.h, m.h, int(inverse), shift, C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
+
+    def dft_batch(self, m) -> "DeviceMatrix":
+        return self._dft(m, False, 1)
+
+    def idft_batch(self, m) -> "DeviceMatrix":
+        return self._dft(m, True, 1)
+
+    def coset_dft_batch(self, m, shift: int) -> "DeviceMatrix":
+        """out row k = sum_j m[j] (shift w_n^k)^j per column."""
+        return self._dft(m, False, shift)
+
+    def coset_idft_batch(self, m, shift: int) -> "DeviceMatrix":
+        """Coefficients of the interpolant of ``m`` over shift * H_n."""
+        return self._dft(m, True, shift)
+
+    def coset_lde_batch(self, m, added_bits: int, shift: int, bit_reversed: bool = False) -> "DeviceMatrix":
+        """``m``: evaluations over H_n; out row j (row bitrev(j) with ``bit_reversed``) = the interpolant at
+        shift * w_N^j, N = n << added_bits."""
+        m, h = self._mat(m), C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_coset_lde_batch(self.ctx.h, m.h, added_bits, shift, int(bit_reversed),
+                                                      C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
+
+    def lde_batch(self, m, added_bits: int) -> "DeviceMatrix":
+        return self.coset_lde_batch(m, added_bits, 1)
 
 
 class CompiledAir:
@@ -446,6 +501,13 @@ class TwoAdicFriPcs:
         ctx.check(ctx._l.ts_pcs_commit(ctx.h, C.byref(cfg), len(mats), arr, _p(sh), _p(root),
                                        C.byref(h)))
         return root, PcsData(ctx, h, root)
+
+    def get_evaluations_on_domain(self, data: PcsData, idx: int, log_size: int) -> DeviceMatrix:
+        """two_adic_pcs.rs:247-258 kept in HBM: the first 2^log_size rows of committed LDE ``idx``,
+        un-bit-reversed (``ts_pcs_data_evaluations_on_domain``)."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_pcs_data_evaluations_on_domain(self.ctx.h, data.h, idx, log_size, C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
 
     def quotient_chunks(self, trace_data: PcsData, air: CompiledAir, public_values, alpha):
         qd = 1 << air.log_quotient_degree
