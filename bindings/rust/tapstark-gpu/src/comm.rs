@@ -51,9 +51,8 @@ where
 {
     let ctx = pcs.ctx;
     let cair = CompiledAir::new(ctx, air, public_values.len());
-    let words: Vec<u32> = trace_rows.values.iter().map(|v| v.as_canonical_u32()).collect();
     let pis: Vec<u32> = public_values.iter().map(|v| v.as_canonical_u32()).collect();
-    let m = DeviceMatrix::upload(ctx, &words, trace_rows.height(), trace_rows.width()).into_raw();
+    let m = DeviceMatrix::upload_monty(ctx, &trace_rows.values, trace_rows.height(), trace_rows.width()).into_raw();
     let cfg = pcs.fri.raw();
     let degree = trace_rows.height() * comm.comm.world as usize;
     let log_n = degree.trailing_zeros() as usize + pcs.fri.log_blowup;

@@ -3,6 +3,15 @@ use core::ffi::CStr;
 use std::ptr;
 
 use crate::ffi::*;
+use crate::proof::Val;
+
+/// The Montgomery radix of `Val`'s in-memory word: a `BabyBear` holding x stands for x * 2^-MONTY_BITS mod p.
+/// p3-baby-bear has used both 31 and 32 over time and the pinned revision cannot be read where this crate is
+/// written: A MAINTAINER MUST CONFIRM THIS WITH ONE KNOWN VALUE before the first use (INTEGRATION.md section
+/// 3c: `transmute::<BabyBear, u32>(BabyBear::one())` is 0x0ffffffe for 32 and 0x7ffffff for 31).
+pub const MONTY_BITS: u32 = 32;
+const MONTY_KIND: u8 = if MONTY_BITS == 32 { TS_COL_MONTY32 } else { TS_COL_MONTY31 };
+const _: () = assert!(core::mem::size_of::<Val>() == 4 && core::mem::align_of::<Val>() == 4);
 
 /// One per GPU, driven by one thread (SURVEY.md section 8(b) "Threading").
 pub struct GpuContext {
@@ -70,6 +79,49 @@ impl<'c> DeviceMatrix<'c> {
             "ts_matrix_upload_async",
         );
         Self { ctx, raw }
+    }
+    /// `RowMajorMatrix::new(values, width)` straight from the field elements' own memory (Montgomery words):
+    /// no `as_canonical_u32` pass and no temporary on the host, the reduction runs in HBM
+    /// (`ts_matrix_upload_packed`, one uniform `TS_COL_MONTY*` kind).  `values` is copied through a 16-byte
+    /// aligned buffer only if the slice itself is not aligned (a `Vec<Val>` of a trace's size is).
+    pub fn upload_monty(ctx: &'c GpuContext, values: &[Val], height: usize, width: usize) -> Self {
+        assert_eq!(values.len(), height * width);
+        let kind = [MONTY_KIND];
+        let fmt = ts_trace_format {
+            struct_size: core::mem::size_of::<ts_trace_format>() as u32,
+            layout: TS_LAYOUT_ROWS,
+            row_stride_bytes: 0,
+            n_kinds: 1,
+            reserved: 0,
+            kinds: kind.as_ptr(),
+        };
+        let mut raw = ptr::null_mut();
+        let mut call = |p: *const core::ffi::c_void| {
+            ctx.check(
+                unsafe { ts_matrix_upload_packed(ctx.raw, p, &fmt, height as u64, width as u32, &mut raw) },
+                "ts_matrix_upload_packed",
+            )
+        };
+        if values.as_ptr() as usize % 16 == 0 {
+            call(values.as_ptr() as *const core::ffi::c_void);
+        } else {
+            let mut aligned = vec![0u128; (values.len() * 4 + 15) / 16];
+            unsafe { ptr::copy_nonoverlapping(values.as_ptr() as *const u8, aligned.as_mut_ptr() as *mut u8, values.len() * 4) };
+            call(aligned.as_ptr() as *const core::ffi::c_void);
+        }
+        Self { ctx, raw }
+    }
+    /// row-major, natural rows, as field elements: the library writes Montgomery words
+    /// (`ts_matrix_download_monty`) straight into the `Vec<Val>`; no `from_canonical_u32` pass
+    pub fn download_monty(&self) -> Vec<Val> {
+        let (h, w) = self.dims();
+        let mut vals: Vec<Val> = Vec::with_capacity(h * w);
+        self.ctx.check(
+            unsafe { ts_matrix_download_monty(self.ctx.raw, self.raw, MONTY_BITS, vals.as_mut_ptr() as *mut u32) },
+            "ts_matrix_download_monty",
+        );
+        unsafe { vals.set_len(h * w) }; // every word is below p: a valid `Val`
+        vals
     }
     pub fn dims(&self) -> (usize, usize) {
         let (mut h, mut w) = (0u64, 0u32);

@@ -22,6 +22,21 @@ pub struct ts_air_options {
     pub reserved: u32,
 }
 
+/// `ts_trace_format` (struct_size first): how the host holds a trace (packed columns, Montgomery words).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_trace_format {
+    pub struct_size: u32,
+    pub layout: u32,
+    pub row_stride_bytes: u64,
+    pub n_kinds: u32,
+    pub reserved: u32,
+    pub kinds: *const u8,
+}
+pub const TS_COL_MONTY32: u8 = 3;
+pub const TS_COL_MONTY31: u8 = 4;
+pub const TS_LAYOUT_ROWS: u32 = 0;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct ts_fri_config {
@@ -107,6 +122,16 @@ extern "C" {
     pub fn ts_matrix_upload_async(ctx: *mut ts_ctx, host_pinned: *const u32, height: u64, width: u32,
                                   out: *mut *mut ts_matrix) -> ts_status;
     pub fn ts_matrix_download(ctx: *mut ts_ctx, m: *const ts_matrix, host_row_major: *mut u32) -> ts_status;
+    /// a trace as the host holds it: widened / Montgomery-reduced on the device
+    pub fn ts_trace_format_bytes(format: *const ts_trace_format, height: u64, width: u32, bytes: *mut u64) -> ts_status;
+    pub fn ts_matrix_upload_packed(ctx: *mut ts_ctx, host: *const c_void, format: *const ts_trace_format, height: u64,
+                                   width: u32, out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_matrix_upload_packed_async(ctx: *mut ts_ctx, host_pinned: *const c_void, format: *const ts_trace_format,
+                                         height: u64, width: u32, out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_matrix_from_device_packed(ctx: *mut ts_ctx, dev: *const c_void, format: *const ts_trace_format,
+                                        height: u64, width: u32, out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_matrix_download_monty(ctx: *mut ts_ctx, m: *const ts_matrix, monty_bits: u32,
+                                    host_row_major: *mut u32) -> ts_status;
     pub fn ts_matrix_dims(m: *const ts_matrix, height: *mut u64, width: *mut u32) -> ts_status;
     pub fn ts_matrix_free(ctx: *mut ts_ctx, m: *mut ts_matrix);
 

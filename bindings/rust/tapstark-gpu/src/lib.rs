@@ -5,7 +5,10 @@
 //! ABI version 5.  The tested callers of the same C ABI are the ctypes binding
 //! (tap-stark_amd/stark.py) and examples/fib_air.cpp.  That holds for `GpuDft` (pcs.rs: `TwoAdicSubgroupDft`
 //! over ts_dft_batch / ts_coset_lde_batch) and the device form of `get_evaluations_on_domain` as well: source
-//! only, never compiled.
+//! only, never compiled.  So do `DeviceMatrix::upload_monty` / `download_monty` (context.rs), which hand the
+//! library the field elements' own Montgomery words in place of the `as_canonical_u32` / `from_canonical_u32`
+//! passes: source only, never compiled, and `context::MONTY_BITS` must be confirmed against the pinned
+//! p3-baby-bear with one known value.
 //!
 //! ```ignore
 //! // uni-stark/tests/fib_air.rs:117-149 with the GPU prover
@@ -28,7 +31,7 @@ pub mod tap;
 
 pub use air::serialize_constraints;
 pub use comm::{prove_gpu_sharded, rccl_unique_id, RcclComm};
-pub use context::{DeviceMatrix, GpuChallenger, GpuContext};
+pub use context::{DeviceMatrix, GpuChallenger, GpuContext, MONTY_BITS};
 pub use pcs::{FriConfig, GpuDft, GpuFriPcs, GpuPcsError, GpuProverData};
 pub use proof::Proof;
 pub use prove::{prove_gpu, prove_gpu_batch, prove_gpu_stepwise, BatchError, BatchStatement, CompiledAir};

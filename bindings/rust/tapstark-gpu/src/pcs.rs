@@ -133,12 +133,11 @@ impl<'c> GpuDft<'c> {
         DeviceMatrix { ctx: self.ctx, raw }
     }
     fn up(&self, mat: &RowMajorMatrix<Val>) -> DeviceMatrix<'c> {
-        let words: Vec<u32> = mat.values.iter().map(|v| v.as_canonical_u32()).collect();
-        DeviceMatrix::upload(self.ctx, &words, mat.height(), mat.width())
+        DeviceMatrix::upload_monty(self.ctx, &mat.values, mat.height(), mat.width())
     }
     fn down(m: DeviceMatrix<'c>) -> RowMajorMatrix<Val> {
         let width = m.dims().1;
-        RowMajorMatrix::new(m.download().into_iter().map(Val::from_canonical_u32).collect(), width)
+        RowMajorMatrix::new(m.download_monty(), width)
     }
 }
 
@@ -184,8 +183,7 @@ impl<'c> Pcs<Challenge, GpuChallenger> for GpuFriPcs<'c> {
         let mut shifts = Vec::with_capacity(evaluations.len());
         for (domain, evals) in evaluations {
             assert_eq!(domain.size(), evals.height()); // :234
-            let words: Vec<u32> = evals.values.iter().map(|v| v.as_canonical_u32()).collect();
-            mats.push(DeviceMatrix::upload(self.ctx, &words, evals.height(), evals.width()).into_raw());
+            mats.push(DeviceMatrix::upload_monty(self.ctx, &evals.values, evals.height(), evals.width()).into_raw());
             shifts.push(domain.shift.as_canonical_u32());
         }
         let cfg = self.fri.raw();
@@ -221,9 +219,7 @@ impl<'c> Pcs<Challenge, GpuChallenger> for GpuFriPcs<'c> {
         assert_eq!(domain.shift, Val::generator()); // :254
         let (height, width) = prover_data.dims[idx];
         assert!(height >= domain.size()); // :256
-        let words = self.evaluations_on_domain_device(prover_data, idx, domain.log_n).download();
-        let vals: Vec<Val> = words.into_iter().map(Val::from_canonical_u32).collect();
-        RowMajorMatrix::new(vals, width)
+        RowMajorMatrix::new(self.evaluations_on_domain_device(prover_data, idx, domain.log_n).download_monty(), width)
     }
 
     /// two_adic_pcs.rs:260-419

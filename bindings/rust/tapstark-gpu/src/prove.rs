@@ -56,9 +56,8 @@ where
 {
     let ctx = pcs.ctx;
     let cair = CompiledAir::new(ctx, air, public_values.len());
-    let words: Vec<u32> = trace.values.iter().map(|v| v.as_canonical_u32()).collect();
     let pis: Vec<u32> = public_values.iter().map(|v| v.as_canonical_u32()).collect();
-    let m = DeviceMatrix::upload(ctx, &words, trace.height(), trace.width());
+    let m = DeviceMatrix::upload_monty(ctx, &trace.values, trace.height(), trace.width());
     let cfg = pcs.fri.raw();
     let mut out = vec![0u32; proof_capacity(&pcs.fri, trace.height(), trace.width(), 1 << cair.log_quotient_degree)];
     let mut n = 0usize;

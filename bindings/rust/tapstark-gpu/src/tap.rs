@@ -88,9 +88,8 @@ where
 {
     let ctx = pcs.ctx;
     let cair = CompiledAir::new(ctx, air, public_values.len());
-    let words: Vec<u32> = trace.values.iter().map(|v| v.as_canonical_u32()).collect();
     let pis: Vec<u32> = public_values.iter().map(|v| v.as_canonical_u32()).collect();
-    let m = DeviceMatrix::upload(ctx, &words, trace.height(), trace.width()).into_raw();
+    let m = DeviceMatrix::upload_monty(ctx, &trace.values, trace.height(), trace.width()).into_raw();
     let cfg = pcs.fri.raw();
     let mut out = vec![0u32; capacity(pcs, trace.height(), trace.width(), 1 << cair.log_quotient_degree)];
     let mut n = 0usize;
@@ -171,8 +170,7 @@ impl<'c> GpuTapTreeMmcs<'c> {
         let mats: Vec<*mut ts_matrix> = inputs
             .iter()
             .map(|m| {
-                let words: Vec<u32> = m.values.iter().map(|v| v.as_canonical_u32()).collect();
-                DeviceMatrix::upload(self.ctx, &words, m.height(), m.width()).into_raw()
+                DeviceMatrix::upload_monty(self.ctx, &m.values, m.height(), m.width()).into_raw()
             })
             .collect();
         let mut roots = vec![0u8; 32 * self.num_queries];

@@ -11,11 +11,14 @@
 //     mode "pinned": every trace comes from page-locked host memory (ts_host_alloc), uploaded with
 //     ts_matrix_upload_async on the lane's stream -- the upload of one lane overlaps the proofs of the
 //     others: the PCIe-inclusive rate of INTEGRATION.md section 3c;
+//     mode "packed": the same lanes and the same values, but the page-locked buffer holds every column at the
+//     smallest of u8 / u16 / u32 that fits it (ts_trace_format, rows layout) and goes up with
+//     ts_matrix_upload_packed_async: fewer bytes on the link, widened in HBM, the same proofs;
 //   * every proof is checked: proofs of the same trace must be byte-identical (the prover is
 //     deterministic) and the first one is verified with ts_verify.
 //
 //   g++ -std=c++17 -pthread -I include examples/prove_stream.cpp -L tap-stark_amd/lib -ltapstark_hip -o prove_stream
-//   ./prove_stream [log_n=20] [n_proofs=40] [lanes=4] [device|pinned] [proof0.bin]
+//   ./prove_stream [log_n=20] [n_proofs=40] [lanes=4] [device|pinned|packed] [proof0.bin]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -77,14 +80,15 @@ int main(int argc, char** argv) {
     const unsigned log_n = argc > 1 ? (unsigned)atoi(argv[1]) : 20;
     const int n_proofs = argc > 2 ? atoi(argv[2]) : 40;
     const int lanes = argc > 3 ? atoi(argv[3]) : 4;
-    const bool pinned = argc > 4 && std::string(argv[4]) == "pinned";
+    const bool packed = argc > 4 && std::string(argv[4]) == "packed";
+    const bool pinned = packed || (argc > 4 && std::string(argv[4]) == "pinned");
     const char* dump = argc > 5 ? argv[5] : nullptr;
     const uint64_t n = 1ull << log_n;
     const uint32_t w = 64;
     const ts_fri_config fri = {2, 28, 8};
     const uint64_t seed = 0x7A957A12ull;
     if (lanes < 1 || lanes > 16 || n_proofs < lanes) {
-        fprintf(stderr, "usage: prove_stream [log_n] [n_proofs >= lanes] [lanes 1..16] [device|pinned]\n");
+        fprintf(stderr, "usage: prove_stream [log_n] [n_proofs >= lanes] [lanes 1..16] [device|pinned|packed]\n");
         return 2;
     }
 
@@ -96,6 +100,11 @@ int main(int argc, char** argv) {
     // one host copy of the trace for the pinned mode (made on the device, downloaded once)
     std::vector<uint32_t*> pin(lanes, nullptr);
     std::vector<uint32_t> host_trace;
+    // packed mode: per column the smallest kind that holds it, its byte offset in a row, the bytes of a row
+    std::vector<uint8_t> kinds(w, TS_COL_U32);
+    std::vector<uint32_t> col_off(w, 0);
+    ts_trace_format fmt = {sizeof(ts_trace_format), TS_LAYOUT_ROWS, 0, w, 0, kinds.data()};
+    uint64_t pin_bytes = n * w * 4, row_bytes = 4 * w;
     {
         ts_ctx* c0 = nullptr;
         if (ts_ctx_create(0, &c0) != TS_OK) {
@@ -108,9 +117,20 @@ int main(int argc, char** argv) {
             host_trace.resize(n * w);
             if (ts_matrix_download(c0, m, host_trace.data()) != TS_OK) return 1;
             ts_matrix_free(c0, m);
+            if (packed) {
+                row_bytes = 0;
+                for (uint32_t c = 0; c < w; c++) {
+                    uint32_t top = 0;
+                    for (uint64_t r = 0; r < n; r++) top = std::max(top, host_trace[r * w + c]);
+                    kinds[c] = top < 256 ? TS_COL_U8 : top < 65536 ? TS_COL_U16 : TS_COL_U32;
+                    col_off[c] = (uint32_t)row_bytes;
+                    row_bytes += kinds[c] == TS_COL_U8 ? 1 : kinds[c] == TS_COL_U16 ? 2 : 4;
+                }
+                if (ts_trace_format_bytes(&fmt, n, w, &pin_bytes) != TS_OK || pin_bytes != n * row_bytes) return 1;
+            }
             for (int l = 0; l < lanes; l++) {
                 void* p = nullptr;
-                if (ts_host_alloc(n * w * 4, &p) != TS_OK) return 1;
+                if (ts_host_alloc(pin_bytes, &p) != TS_OK) return 1;
                 pin[l] = (uint32_t*)p;
             }
         }
@@ -141,13 +161,24 @@ int main(int argc, char** argv) {
             if (ts_ctx_create(0, &ctx) != TS_OK) return fail("ts_ctx_create");
             if (ts_air_compile(ctx, tape.data(), tape.size(), &air) != TS_OK) return fail("ts_air_compile");
             std::vector<uint32_t> out(1u << 20);
-            if (pinned) memcpy(pin[l], host_trace.data(), n * w * 4);  // stands for the caller's trace generator
+            // stands for the caller's trace generator, which writes every column at its own size (x86 is
+            // little-endian: the low bytes of a word are its first bytes)
+            if (packed) {
+                uint8_t* dst = (uint8_t*)pin[l];
+                for (uint64_t r = 0; r < n; r++)
+                    for (uint32_t c = 0; c < w; c++)
+                        memcpy(dst + r * row_bytes + col_off[c], &host_trace[r * w + c],
+                               kinds[c] == TS_COL_U8 ? 1 : kinds[c] == TS_COL_U16 ? 2 : 4);
+            } else if (pinned) {
+                memcpy(pin[l], host_trace.data(), n * w * 4);
+            }
             // `m` is consumed.  Pinned mode: the lane's buffer is only read (by the asynchronous copy)
             // until ts_prove returns, and ts_prove blocks until the proof is on the host.
             auto make_trace = [&]() -> ts_matrix* {
                 ts_matrix* m = nullptr;
-                const ts_status s = pinned ? ts_matrix_upload_async(ctx, pin[l], n, w, &m)
-                                           : ts_trace_synth_mul(ctx, n, w, seed, &m);
+                const ts_status s = packed   ? ts_matrix_upload_packed_async(ctx, pin[l], &fmt, n, w, &m)
+                                    : pinned ? ts_matrix_upload_async(ctx, pin[l], n, w, &m)
+                                             : ts_trace_synth_mul(ctx, n, w, seed, &m);
                 return s == TS_OK ? m : nullptr;
             };
             auto prove_one = [&](ts_matrix* m, std::vector<uint32_t>* keep) -> bool {
@@ -237,9 +268,16 @@ int main(int argc, char** argv) {
     for (int l = 0; l < lanes; l++)
         if (pin[l]) ts_host_free(pin[l]);
     const double ms = (t_end - t_begin) / n_proofs;
+    uint64_t fnv = 0xcbf29ce484222325ull;  // FNV-1a over the proof words: one line to compare two runs by
+    for (uint32_t word : proofs[0])
+        for (int k = 0; k < 4; k++) fnv = (fnv ^ ((word >> (8 * k)) & 0xff)) * 0x100000001b3ull;
+    printf("proof digest %016llx\n", (unsigned long long)fnv);
+    if (packed) printf("trace packed to %llu of %llu bytes\n", (unsigned long long)pin_bytes, (unsigned long long)(n * w * 4));
     printf("prove_stream: 2^%u x %u, %d proofs on %d lanes, traces %s: %.3f ms per proof (%.1f proofs/s, %.3g cells/s); "
            "one proof alone %.3f ms, start gate %.2f ms; all proofs identical (%zu words), verify -> %d\n",
-           log_n, w, n_proofs, lanes, pinned ? "from pinned host memory (ts_matrix_upload_async)" : "generated on the device",
+           log_n, w, n_proofs, lanes, packed   ? "packed in pinned host memory (ts_matrix_upload_packed_async)"
+           : pinned ? "from pinned host memory (ts_matrix_upload_async)"
+                    : "generated on the device",
            ms, 1e3 / ms, (double)n * w * 1e3 / ms, solo_ms[0], gate.gap_ms, proofs[0].size(), verdict);
     if (want_lat) {
         std::vector<double> all;

@@ -124,6 +124,56 @@ void ts_matrix_free(ts_ctx* ctx, ts_matrix* m);
  * (ts_ctx_stream): work enqueued there, or after ts_ctx_synchronize, sees the values.  Read-only. */
 ts_status ts_matrix_device_ptr(ts_ctx* ctx, ts_matrix* m, const uint32_t** ptr);
 
+/* ---- traces in the host's own form: packed columns, Montgomery words ----
+ * RowMajorMatrix::new(values, width) for a host that does not hold canonical words: the calls below take the
+ * trace as the host stores it and do the widening and the conversion in HBM, instead of the host's own pass
+ * in front of ts_matrix_upload (reference `as_u32_vec`, basic/src/field/mod.rs:48-63; on a Plonky3 host the
+ * `as_canonical_u32` map over RowMajorMatrix<BabyBear>::values, whose memory is Montgomery words).  Byte,
+ * flag and 16-bit limb columns cross the link at their own size.  The result is an ordinary row-major
+ * canonical ts_matrix; nothing downstream changes.
+ *   TS_LAYOUT_ROWS    row r starts at byte r * stride (row_stride_bytes, 0 = the bytes of a row); its columns
+ *                     follow one another at their own sizes with no padding, so a 4-byte column may sit at
+ *                     any byte offset.  The buffer is height * stride bytes.
+ *   TS_LAYOUT_PLANAR  column c is `height` elements of its size, contiguous; each column starts at the next
+ *                     multiple of 16 bytes.  row_stride_bytes must be 0.
+ * Any 32-bit word is accepted for the two Montgomery kinds and the result is canonical; TS_COL_U32 is not
+ * range-checked, exactly as ts_matrix_upload.  Which radix a p3-baby-bear revision uses must be confirmed
+ * with one known value. */
+enum { TS_COL_U32 = 0,      /* canonical word, copied as ts_matrix_upload copies it */
+       TS_COL_U16 = 1, TS_COL_U8 = 2,   /* unsigned little-endian, zero-extended */
+       TS_COL_MONTY32 = 3,  /* word x stands for x * 2^-32 mod p */
+       TS_COL_MONTY31 = 4 };/* word x stands for x * 2^-31 mod p */
+enum { TS_LAYOUT_ROWS = 0, TS_LAYOUT_PLANAR = 1 };
+typedef struct {
+    uint32_t struct_size;      /* sizeof(ts_trace_format), else TS_ERR_INVALID */
+    uint32_t layout;
+    uint64_t row_stride_bytes; /* ROWS only; 0 = tight */
+    uint32_t n_kinds;          /* 1 = every column has kinds[0]; else must equal width */
+    uint32_t reserved;         /* 0 */
+    const uint8_t* kinds;
+} ts_trace_format;
+/* Bytes of a height x width trace in this format: the one place the size is computed.  Host only, no context.
+ * It makes every check of the format the upload calls make (text in ts_last_error(NULL)). */
+ts_status ts_trace_format_bytes(const ts_trace_format* format, uint64_t height, uint32_t width, uint64_t* bytes);
+/* ts_matrix_upload / ts_matrix_upload_async / ts_matrix_from_device for such a buffer (`host_pinned` from
+ * ts_host_alloc, under the ordering contract of ts_matrix_upload_async; `dev`: a device pointer, e.g. a
+ * torch uint8 tensor's).  The copy and the decode run on the context's stream; the device staging buffer comes
+ * from the context's pool and is released in stream order.  TS_ERR_INVALID, with text in ts_last_error and
+ * before anything touches a device, for a null context (checked first), a null format, a wrong struct_size, a
+ * non-zero reserved, an unknown kind or layout, n_kinds neither 1 nor width, a stride below the row's bytes,
+ * a base pointer that is not 16-byte aligned, a height that is no power of two or above 2^27.
+ * ts_batch_item.host_trace stays canonical-only (that struct is frozen by its struct_size): a packed trace
+ * enters ts_prove_batch as a device `trace` made with ts_matrix_upload_packed_async on the lane's context. */
+ts_status ts_matrix_upload_packed(ts_ctx* ctx, const void* host, const ts_trace_format* format, uint64_t height,
+                                  uint32_t width, ts_matrix** out);
+ts_status ts_matrix_upload_packed_async(ts_ctx* ctx, const void* host_pinned, const ts_trace_format* format,
+                                        uint64_t height, uint32_t width, ts_matrix** out);
+ts_status ts_matrix_from_device_packed(ts_ctx* ctx, const void* dev, const ts_trace_format* format,
+                                       uint64_t height, uint32_t width, ts_matrix** out);
+/* ts_matrix_download as Montgomery words, for a host whose field type stores them (instead of its
+ * `from_canonical_u32` pass): word = value * 2^monty_bits mod p, monty_bits 31 or 32, else TS_ERR_INVALID. */
+ts_status ts_matrix_download_monty(ts_ctx* ctx, const ts_matrix* m, uint32_t monty_bits, uint32_t* host_row_major);
+
 /* ------------------------------------------------------------------ Dft (TwoAdicSubgroupDft) */
 /* The `Dft` of TwoAdicFriPcs::new(log_n, dft, mmcs, fri_config) (fri/src/two_adic_pcs.rs:38-55;
  * Radix2DitParallel in uni-stark/tests/fib_air.rs:113-115), the Plonky3 p3-dft trait of SURVEY.md App. A.5,

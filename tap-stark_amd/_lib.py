@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "ts_prove_tap", "ts_prove_tap_sharded", "ts_verify_tap",
     "ts_dft_batch", "ts_coset_lde_batch", "ts_matrix_bit_reverse_rows", "ts_pcs_data_evaluations_on_domain",
     "ts_matrix_device_ptr",
+    "ts_trace_format_bytes", "ts_matrix_upload_packed", "ts_matrix_upload_packed_async",
+    "ts_matrix_from_device_packed", "ts_matrix_download_monty",
 ]
 
 STATUS = {0: "TS_OK", 1: "TS_ERR_INVALID", 2: "TS_ERR_HIP", 3: "TS_ERR_OOM",
@@ -49,6 +51,12 @@ class AirOptionsC(C.Structure):
     """``ts_air_options`` (struct_size first)."""
     _fields_ = [("struct_size", C.c_uint32), ("segment_instr", C.c_uint32), ("jit_jobs", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class TraceFormatC(C.Structure):
+    """``ts_trace_format`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_uint32), ("row_stride_bytes", C.c_uint64),
+                ("n_kinds", C.c_uint32), ("reserved", C.c_uint32), ("kinds", C.POINTER(C.c_uint8))]
 
 
 class TsError(RuntimeError):
@@ -261,5 +269,10 @@ def lib() -> C.CDLL:
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]
         l.ts_pcs_data_evaluations_on_domain.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, voidpp]
         l.ts_matrix_device_ptr.argtypes = [C.c_void_p, C.c_void_p, voidpp]
+        fmtp = C.POINTER(TraceFormatC)
+        l.ts_trace_format_bytes.argtypes = [fmtp, C.c_uint64, C.c_uint32, u64p]
+        for name in ("ts_matrix_upload_packed", "ts_matrix_upload_packed_async", "ts_matrix_from_device_packed"):
+            getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, fmtp, C.c_uint64, C.c_uint32, voidpp]
+        l.ts_matrix_download_monty.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, u32p]
         _lib = l
     return _lib

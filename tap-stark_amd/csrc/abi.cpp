@@ -28,10 +28,11 @@ namespace {
 
 thread_local std::string g_create_error;
 
+// set_device = false: argument checks that must fail before anything touches a device
 template <class F>
-ts_status guard(ts_ctx* ctx, F&& f) {
+ts_status guard(ts_ctx* ctx, F&& f, bool set_device = true) {
     try {
-        if (ctx) TS_HIP(hipSetDevice(ctx->ctx.device));
+        if (ctx && set_device) TS_HIP(hipSetDevice(ctx->ctx.device));
         f();
         return TS_OK;
     } catch (const ts::Error& e) {
@@ -396,6 +397,72 @@ ts_status ts_matrix_from_device(ts_ctx* ctx, const uint32_t* dev, uint64_t heigh
                                 ts_matrix** out) {
     return matrix_from(ctx, dev, height, width, hipMemcpyDeviceToDevice, out);
 }
+// ---- traces in the host's own form (ts_trace_format; kernels in ingest.hip)
+// every check of a format, and its offsets and size; host only
+static ts::IngestPlan load_format(const ts_trace_format* f, uint64_t height, uint32_t width) {
+    TS_REQUIRE(f != nullptr, ts::TS_ERR_INVALID, "null trace format");
+    TS_REQUIRE(f->struct_size == sizeof(ts_trace_format), ts::TS_ERR_INVALID,
+               "ts_trace_format.struct_size is not sizeof(ts_trace_format)");
+    TS_REQUIRE(f->reserved == 0, ts::TS_ERR_INVALID, "ts_trace_format.reserved must be 0");
+    TS_REQUIRE(f->layout == TS_LAYOUT_ROWS || f->layout == TS_LAYOUT_PLANAR, ts::TS_ERR_INVALID,
+               "trace format: unknown layout");
+    return ts::ingest_plan(f->kinds, f->n_kinds, f->layout == TS_LAYOUT_PLANAR, f->row_stride_bytes, height, width);
+}
+ts_status ts_trace_format_bytes(const ts_trace_format* format, uint64_t height, uint32_t width, uint64_t* bytes) {
+    if (!bytes) return TS_ERR_INVALID;
+    *bytes = 0;
+    return guard(nullptr, [&] { *bytes = load_format(format, height, width).bytes; });
+}
+static ts_status matrix_from_packed(ts_ctx* ctx, const void* src, const ts_trace_format* format, uint64_t height,
+                                    uint32_t width, hipMemcpyKind kind, ts_matrix** out, bool sync = true) {
+    if (!ctx || !out) return TS_ERR_INVALID;
+    *out = nullptr;
+    ts::IngestPlan plan;
+    const ts_status refused = guard(ctx, [&] {
+        plan = load_format(format, height, width);
+        TS_REQUIRE(src != nullptr, ts::TS_ERR_INVALID, "packed trace: null buffer");
+        TS_REQUIRE(((uintptr_t)src & 15) == 0, ts::TS_ERR_INVALID, "packed trace: the buffer is not 16-byte aligned");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        auto m = std::make_unique<ts_matrix>();
+        m->m.buf = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)height * width);
+        m->m.height = height;
+        m->m.width = width;
+        m->m.layout = ts::DeviceMatrix::ROW_MAJOR;
+        if (plan.uniform4 >= 0) {  // the source is the matrix, word for word
+            TS_HIP(hipMemcpyAsync(m->m.buf.p, src, plan.bytes, kind, ctx->ctx.stream));
+            if (plan.uniform4 != ts::COL_U32)
+                ts::launch_scale_words(ctx->ctx, m->m.buf.p, m->m.buf.p, (uint64_t)height * width,
+                                       ts::monty_ingest_factor(plan.uniform4));
+        } else {
+            // a host buffer is staged in the pool; the pool hands a freed block only to later work on this
+            // stream, so releasing it at the end of this scope cannot take it from under the kernel
+            ts::DevBuf<uint8_t> staging;
+            const uint8_t* d_src = static_cast<const uint8_t*>(src);
+            if (kind != hipMemcpyDeviceToDevice) {
+                staging = ts::DevBuf<uint8_t>(&ctx->ctx, plan.bytes);
+                TS_HIP(hipMemcpyAsync(staging.p, src, plan.bytes, kind, ctx->ctx.stream));
+                d_src = staging.p;
+            }
+            ts::launch_ingest(ctx->ctx, plan, d_src, m->m.buf.p);
+        }
+        if (sync) ctx->ctx.sync();
+        *out = m.release();
+    });
+}
+ts_status ts_matrix_upload_packed(ts_ctx* ctx, const void* host, const ts_trace_format* format, uint64_t height,
+                                  uint32_t width, ts_matrix** out) {
+    return matrix_from_packed(ctx, host, format, height, width, hipMemcpyHostToDevice, out);
+}
+ts_status ts_matrix_upload_packed_async(ts_ctx* ctx, const void* host_pinned, const ts_trace_format* format,
+                                        uint64_t height, uint32_t width, ts_matrix** out) {
+    return matrix_from_packed(ctx, host_pinned, format, height, width, hipMemcpyHostToDevice, out, false);
+}
+ts_status ts_matrix_from_device_packed(ts_ctx* ctx, const void* dev, const ts_trace_format* format, uint64_t height,
+                                       uint32_t width, ts_matrix** out) {
+    return matrix_from_packed(ctx, dev, format, height, width, hipMemcpyDeviceToDevice, out);
+}
 static ts_status generated_matrix(ts_ctx* ctx, uint64_t height, uint32_t width, ts_matrix** out,
                                   const std::function<void(uint32_t*)>& fill) {
     if (!ctx || !out || height == 0 || width == 0) return TS_ERR_INVALID;
@@ -549,6 +616,26 @@ ts_status ts_matrix_device_ptr(ts_ctx* ctx, ts_matrix* m, const uint32_t** ptr) 
             m->m.layout = ts::DeviceMatrix::ROW_MAJOR;
         }
         *ptr = m->m.buf.p;
+    });
+}
+
+// (after row_major_words: a matrix made on the device in column-major form downloads the same way)
+ts_status ts_matrix_download_monty(ts_ctx* ctx, const ts_matrix* m, uint32_t monty_bits, uint32_t* host) {
+    if (!ctx || !m || !host) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(monty_bits == 31 || monty_bits == 32, ts::TS_ERR_INVALID, "download: monty_bits must be 31 or 32");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        ts::DevBuf<uint32_t> tmp;
+        const uint32_t* src = row_major_words(ctx, m->m, tmp);
+        const size_t words = (size_t)m->m.height * m->m.width;
+        // value * 2^bits = mont_mul(value, 2^(32 + bits) mod p)
+        constexpr uint32_t TWO_63_MOD_P = 0x5eeeeef2u;
+        ts::DevBuf<uint32_t> mont(&ctx->ctx, words);
+        ts::launch_scale_words(ctx->ctx, src, mont.p, words, monty_bits == 32 ? ts::R2_MOD_P : TWO_63_MOD_P);
+        TS_HIP(hipMemcpyAsync(host, mont.p, words * 4, hipMemcpyDeviceToHost, ctx->ctx.stream));
+        ctx->ctx.sync();
     });
 }
 

@@ -290,4 +290,32 @@ void launch_trace_synth_mul(Context& ctx, uint32_t* out, uint64_t n, uint32_t wi
 // build-defined SynthExt-w trace (airs.py generate_synth_ext_trace; config 5's stand-in)
 void launch_trace_synth_ext(Context& ctx, uint32_t* out, uint64_t n, uint32_t width, uint64_t seed);
 
+// ---- ingest.hip ------------------------------------------------------------------------------
+// A trace as the host holds it (include/tapstark.h ts_trace_format) -> the row-major canonical matrix.
+enum : uint8_t { COL_U32 = 0, COL_U16 = 1, COL_U8 = 2, COL_MONTY32 = 3, COL_MONTY31 = 4 };  // = TS_COL_*
+struct IngestPlan {
+    bool planar = false;
+    uint64_t height = 0;
+    uint32_t width = 0;
+    uint64_t stride = 0;  // rows layout: bytes from one row to the next
+    uint64_t bytes = 0;   // of the whole source buffer
+    // the one kind of a uniform 4-byte format in tight rows (the source is then the matrix word for word:
+    // copied straight into it, launch_scale_words for a Montgomery kind), else -1
+    int uniform4 = -1;
+    // per column (byte offset << 3) | kind; the offset within a row (rows layout) or of the column within
+    // the buffer (planar)
+    std::vector<uint64_t> table;
+};
+// The one place a format's offsets and size are worked out; host only, no device is touched.  Throws
+// TS_ERR_INVALID for an unknown kind, n_kinds neither 1 nor width, a stride below a row's bytes (or given for
+// planar), a height that is no power of two or above 2^27.
+IngestPlan ingest_plan(const uint8_t* kinds, uint32_t n_kinds, bool planar, uint64_t row_stride, uint64_t height,
+                       uint32_t width);
+// src: plan.bytes device bytes, 16-byte aligned, only read -> out: height x width row-major canonical words
+void launch_ingest(Context& ctx, const IngestPlan& plan, const uint8_t* src, uint32_t* out);
+// out[i] = in[i] * mult * 2^-32 mod p (canonical; in place allowed; 16-byte aligned): a Montgomery word to its
+// value with mult = monty_ingest_factor(kind), a value to its Montgomery word with mult = 2^(32 + radix) mod p
+void launch_scale_words(Context& ctx, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t mult);
+uint32_t monty_ingest_factor(uint32_t kind);
+
 }  // namespace ts

@@ -158,6 +158,97 @@ class PinnedHostMatrix:
             pass
 
 
+class PinnedHostBytes:
+    """``nbytes`` of page-locked host memory (``ts_host_alloc``; 16-byte aligned) as a numpy uint8 view: where a
+    packed trace (``TraceFormat``) is assembled for ``DeviceMatrix.upload_packed_async``."""
+
+    def __init__(self, nbytes: int):
+        p = C.c_void_p()
+        rc = _lib.lib().ts_host_alloc(nbytes, C.byref(p))
+        if rc:
+            raise _lib.TsError(rc, "ts_host_alloc")
+        self.ptr = p
+        self.nbytes = nbytes
+        self.array = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nbytes,))
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                _lib.lib().ts_host_free(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+
+class TraceFormat:
+    """``ts_trace_format``: how a host holds a trace -- per column ``"u32"`` (canonical word), ``"u16"`` / ``"u8"``
+    (unsigned, zero-extended), ``"monty32"`` / ``"monty31"`` (word x stands for x * 2^-32 / x * 2^-31 mod p) -- in
+    ``"rows"`` (columns packed back to back, rows ``row_stride`` bytes apart, 0 = tight) or ``"planar"`` (whole
+    columns, each starting at the next multiple of 16 bytes).  ``kinds``: one kind for every column, or one per
+    column."""
+
+    KINDS = {"u32": 0, "u16": 1, "u8": 2, "monty32": 3, "monty31": 4}
+    SIZES = {0: 4, 1: 2, 2: 1, 3: 4, 4: 4}
+    LAYOUTS = {"rows": 0, "planar": 1}
+
+    def __init__(self, kinds, layout: str = "rows", row_stride: int = 0):
+        if isinstance(kinds, (str, int)):
+            kinds = [kinds]
+        self.kinds = np.array([self.KINDS[k] if isinstance(k, str) else int(k) for k in kinds], dtype=np.uint8)
+        self.layout = self.LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+        self.row_stride = int(row_stride)
+
+    def _c(self) -> "_lib.TraceFormatC":
+        return _lib.TraceFormatC(C.sizeof(_lib.TraceFormatC), self.layout, self.row_stride, len(self.kinds), 0,
+                                 self.kinds.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def nbytes(self, height: int, width: int) -> int:
+        """``ts_trace_format_bytes``: the size of a height x width trace in this format (raises for a format the
+        library refuses)."""
+        l, fmt, n = _lib.lib(), self._c(), C.c_uint64()
+        rc = l.ts_trace_format_bytes(C.byref(fmt), height, width, C.byref(n))
+        if rc:
+            raise _lib.TsError(rc, (l.ts_last_error(None) or b"").decode())
+        return int(n.value)
+
+    def pack(self, values, out: np.ndarray | None = None) -> np.ndarray:
+        """Encodes an (h, w) array of column words into this format (numpy, for tests and examples): a uint8
+        array of ``nbytes(h, w)``, or ``out`` filled.  A word must fit its column; Montgomery words go in as
+        they are."""
+        values = _u32(values)
+        h, w = values.shape
+        kinds = np.broadcast_to(self.kinds, (w,)) if len(self.kinds) == 1 else self.kinds
+        sizes = [self.SIZES[int(k)] for k in kinds]
+        total = self.nbytes(h, w)
+        if out is None:  # 16-byte aligned, as the upload calls ask
+            raw = np.zeros(total + 15, dtype=np.uint8)
+            out = raw[(-raw.ctypes.data) % 16:][:total]
+        assert out.dtype == np.uint8 and out.shape == (total,)
+        le = values.astype("<u4").view(np.uint8).reshape(h, w, 4)  # little-endian bytes of every word
+        off = 0
+        stride = self.row_stride or sum(sizes)
+        rows = out.reshape(h, stride) if self.layout == 0 else None
+        for c, s in enumerate(sizes):
+            assert s == 4 or int(values[:, c].max()) < (1 << (8 * s)), f"column {c} does not fit {s} byte(s)"
+            if self.layout == 0:
+                rows[:, off:off + s] = le[:, c, :s]
+                off += s
+            else:
+                off = (off + 15) & ~15
+                out[off:off + h * s] = le[:, c, :s].reshape(-1)
+                off += h * s
+        assert (off if self.layout else h * stride) == total
+        return out
+
+
+def _byte_ptr(buf):
+    """(pointer, keep-alive) of a packed host buffer: ``PinnedHostBytes`` or a contiguous uint8 array."""
+    if isinstance(buf, PinnedHostBytes):
+        return buf.ptr, buf
+    a = np.ascontiguousarray(buf, dtype=np.uint8)
+    return C.c_void_p(a.ctypes.data), a
+
+
 class DeviceMatrix:
     """``RowMajorMatrix<Val>`` resident in HBM (``ts_matrix``)."""
 
@@ -186,6 +277,31 @@ class DeviceMatrix:
         h = C.c_void_p()
         ctx.check(ctx._l.ts_matrix_from_device(ctx.h, C.c_void_p(ptr), height, width, C.byref(h)))
         return cls(ctx, h)
+
+    @classmethod
+    def _packed(cls, fn, ctx: Context, ptr, fmt: TraceFormat, height: int, width: int) -> "DeviceMatrix":
+        h, f = C.c_void_p(), fmt._c()
+        ctx.check(fn(ctx.h, ptr, C.byref(f), height, width, C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def upload_packed(cls, ctx: Context, buf, fmt: TraceFormat, height: int, width: int) -> "DeviceMatrix":
+        """``ts_matrix_upload_packed``: a trace held in ``fmt`` (a uint8 array or ``PinnedHostBytes`` of
+        ``fmt.nbytes(height, width)``, 16-byte aligned) is copied as it is and widened / reduced on the device."""
+        ptr, keep = _byte_ptr(buf)
+        return cls._packed(ctx._l.ts_matrix_upload_packed, ctx, ptr, fmt, height, width)
+
+    @classmethod
+    def upload_packed_async(cls, ctx: Context, pinned: PinnedHostBytes, fmt: TraceFormat, height: int,
+                            width: int) -> "DeviceMatrix":
+        """The same without waiting (``ts_matrix_upload_packed_async``): ``pinned`` stays untouched until the next
+        synchronisation of ``ctx``."""
+        return cls._packed(ctx._l.ts_matrix_upload_packed_async, ctx, pinned.ptr, fmt, height, width)
+
+    @classmethod
+    def from_device_packed(cls, ctx: Context, ptr: int, fmt: TraceFormat, height: int, width: int) -> "DeviceMatrix":
+        """``ts_matrix_from_device_packed``: ``ptr`` is a device pointer (a torch uint8 tensor's ``data_ptr()``)."""
+        return cls._packed(ctx._l.ts_matrix_from_device_packed, ctx, C.c_void_p(ptr), fmt, height, width)
 
     @classmethod
     def fibonacci(cls, ctx: Context, a: int, b: int, n: int) -> "DeviceMatrix":
@@ -217,10 +333,15 @@ class DeviceMatrix:
         self.ctx.check(self.ctx._l.ts_matrix_dims(self.h, C.byref(hh), C.byref(ww)))
         return int(hh.value), int(ww.value)
 
-    def download(self) -> np.ndarray:
+    def download(self, monty_bits: int | None = None) -> np.ndarray:
+        """Canonical words, or with ``monty_bits`` = 31 | 32 the Montgomery words value * 2^monty_bits mod p
+        (``ts_matrix_download_monty``)."""
         hh, ww = self.dims()
         out = np.zeros((hh, ww), dtype=np.uint32)
-        self.ctx.check(self.ctx._l.ts_matrix_download(self.ctx.h, self.h, _p(out)))
+        if monty_bits is None:
+            self.ctx.check(self.ctx._l.ts_matrix_download(self.ctx.h, self.h, _p(out)))
+        else:
+            self.ctx.check(self.ctx._l.ts_matrix_download_monty(self.ctx.h, self.h, monty_bits, _p(out)))
         return out
 
     def bit_reverse_rows(self) -> "DeviceMatrix":
