@@ -4,6 +4,7 @@
 
 #include "bb.hpp"
 #include "context.hpp"
+#include "ntt_plan.hpp"
 
 namespace ts {
 
@@ -15,7 +16,7 @@ struct ColMat {
     uint64_t col_stride = 0;
 };
 
-// ---- ntt.hip ---------------------------------------------------------------------------------
+// ---- ntt.hip, ntt_lde.hip --------------------------------------------------------------------
 void launch_build_twiddles(Context& ctx, uint32_t* W, uint32_t* Winv, unsigned log_size);
 // per-coset scale tables: lo[beta][j] = s_beta^j * scale (j < 1024), hi[beta][j] = s_beta^(1024 j)
 void launch_build_shift_tables(Context& ctx, uint32_t* lo, uint32_t* hi, uint32_t n_hi,
@@ -40,6 +41,9 @@ void launch_transpose_plain(Context& ctx, const uint32_t* src, uint32_t* dst, ui
 // dst row-major (h x w)  <-  src column-major; used by debug downloads and row gathers
 void launch_transpose_to_row_major(Context& ctx, const uint32_t* src, uint64_t col_stride,
                                    uint32_t* dst, uint64_t h, uint32_t w);
+// dst row-major (2^log_h x w, natural rows)  <-  src column-major, rows p < 2^log_h in bit-reversed order
+void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_stride, uint32_t* dst,
+                               unsigned log_h, uint32_t w);
 // Coset low-degree extension of `ncols` columns (reference fri/src/two_adic_pcs.rs:233-241):
 //   in : evals[c][p] = column value at subgroup index bitrev(p)   (n per column, DESTROYED)
 //   out: out[c][beta*n + t] = p_c(shift * w_N^bitrev(beta*n+t)),  N = n << log_blowup
@@ -52,6 +56,20 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
                unsigned log_blowup, uint32_t shift, uint32_t* out, uint64_t out_col_stride,
                uint32_t beta0 = 0, uint32_t n_beta = 0, bool first_round_done = false,
                uint32_t* evals2 = nullptr, uint32_t shift2 = 0, uint32_t gw = 0);
+
+// The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles for log_n must be there).  Each refuses
+// what the plan cannot run with the caller's wording (`lde`).
+inline void ntt_require_shape(const NttPlan& p, uint32_t ncols, uint64_t stride_a, uint64_t stride_b, bool lde) {
+    if (const char* why = ntt_plan_refusal(p, ncols, stride_a, stride_b, lde)) throw Error(TS_ERR_INVALID, why);
+}
+// inverse stages log_n-1 .. sA on the chunks of `ncols` columns, in place, lazy values out (two-pass plans);
+// first_round_done: k_transpose_bitrev_r16 did the first round; data2: columns gw .. live in a second matrix
+void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
+                           bool first_round_done = false, uint32_t* data2 = nullptr, uint32_t gw = 0xffffffffu);
+// forward stages sA .. log_n-1 on the chunks of `n_blocks` consecutive 2^log_n-row blocks of every column, in
+// place, canonical values out (two-pass plans)
+void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
+                           uint32_t n_blocks);
 
 // ---- ntt_dft.hip -----------------------------------------------------------------------------
 // TwoAdicSubgroupDft on its own.  Row-major matrices are 2^log_n x w, natural rows,
@@ -68,9 +86,6 @@ void dft_batch(Context& ctx, const uint32_t* in, uint32_t* out, unsigned log_n, 
 // row bitrev(j) with bit_reversed (then the rows of Pcs::commit's LDE for shift = 31 / domain shift)
 void coset_lde_batch(Context& ctx, const uint32_t* in, uint32_t* out, unsigned log_n, uint32_t w, unsigned added_bits,
                      uint32_t shift, bool bit_reversed);
-// dst row-major (2^log_h x w, natural rows)  <-  src column-major, rows p < 2^log_h in bit-reversed order
-void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_stride, uint32_t* dst,
-                               unsigned log_h, uint32_t w);
 // bit_reverse_rows().to_row_major_matrix(): dst[r] = src[bitrev(r)], both row-major 2^log_h x w
 void launch_bit_reverse_rows(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_h, uint32_t w);
 

@@ -8,8 +8,8 @@
 // twist between passes.  The inverse runs the stages backwards with (A, B) -> (A + B, (A - B)/w).
 //
 // Execution: up to 4 stages at a time are done in registers (a thread owns the 16 elements of a
-// radix-16 group), with one LDS exchange between such rounds; the LDS image is padded by one word
-// per 16 so that every round's access pattern is bank-conflict free.  Three kernels:
+// radix-16 group), with one LDS exchange between such rounds; the LDS image is padded so that every
+// round's access pattern is bank-conflict free (ntt_lde.hip).  Three kernels there:
 //   k_intt_contig    stages log_n-1 .. sA of the inverse on 4096-element chunks   (only n > 4096)
 //   k_lde_mid        the strided stages of the inverse (sA-1 .. 0), then for every coset: scale
 //                    coefficient k by s_beta^k / n and run the strided stages of the forward
@@ -22,9 +22,6 @@
 namespace ts {
 
 constexpr int SHIFT_LO_BITS = 10;  // coset scale s^k = hi[k >> 10] * lo[k & 1023]
-
-__device__ __forceinline__ uint32_t pad(uint32_t i) { return i + (i >> 4); }
-constexpr int padded(int n) { return n + (n >> 4); }
 
 // ------------------------------------------------------------------ tables
 __global__ void k_build_twiddles(uint32_t* __restrict__ W, uint32_t* __restrict__ Winv,
@@ -131,110 +128,97 @@ const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, unsigned log_blo
 }
 
 // ------------------------------------------------------------------ transposes
-// src row-major [n][w] natural  ->  dst[c][p] = src[bitrev(p)][c]
-__global__ void k_transpose_bitrev(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
-                                   unsigned log_n, uint32_t w, uint64_t dst_col_stride,
-                                   uint32_t src_width) {
+// One 64 x 64 LDS tile transpose between a row-major matrix rm[r][c] (rows of rm_width words) and a
+// column-major one cm[c][p] (columns col_stride apart), w columns of h rows.  TO_COLUMNS: rm -> cm, else
+// cm -> rm.  BITREV: p = bitrev(r) over log_h bits (h = 2^log_h), else p = r and h is any height.
+// tile[i][j] is element (p0 + i, c0 + j).  On the row-major side a thread takes column c0 + tx of the rows
+// i = ty + 4 k (a wave moves 256 consecutive bytes of a row), on the column-major side slot p0 + tx of the
+// columns c0 + ty + 4 k.
+template <bool TO_COLUMNS, bool BITREV>
+__global__ void __launch_bounds__(256)
+k_transpose_tile(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint64_t h, unsigned log_h,
+                 uint32_t w, uint64_t col_stride, uint32_t rm_width) {
     __shared__ uint32_t tile[64][65];
-    const unsigned tr = log_n < 6 ? log_n : 6;  // log2 of tile rows
-    const uint32_t rows = 1u << tr;
-    const uint32_t p0 = blockIdx.x << tr;
+    const uint64_t p0 = (uint64_t)blockIdx.x * 64;
     const uint32_t c0 = blockIdx.y * 64;
     const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    if (rows == 64 && c0 + 64 <= w) {
+    auto row_of = [&](uint64_t p) -> uint64_t { return BITREV ? bitrev32((uint32_t)p, log_h) : p; };
+    if (p0 + 64 <= h && c0 + 64 <= w) {
         // full tile: 16 loads in flight, then 16 LDS writes; as run-time loops every iteration waited
-        // for its own load.  bitrev(p0 + i) for i < 64 = bitrev(p0) + (bitrev6(i) << (log_n - 6))
-        // (p0 is a multiple of 64: its six low bits are free), so the source rows of a thread are a
-        // base plus constants.
-        const uint32_t rb = bitrev32(p0, log_n);
-        const uint32_t* sp = src + (uint64_t)rb * src_width + c0 + tx;
-        const uint64_t row_step = (uint64_t)src_width << (log_n - 6);
+        // for its own load.  bitrev(p0 + i) for i < 64 = bitrev(p0) + (bitrev6(i) << (log_h - 6))
+        // (p0 is a multiple of 64: its six low bits are free), so the rows of a thread on the row-major
+        // side are a base plus constants.
+        const uint64_t rm = row_of(p0) * rm_width + c0 + tx;
+        const uint64_t rm_step = BITREV ? (uint64_t)rm_width << (log_h - 6) : rm_width;
+        const uint64_t cm = (uint64_t)(c0 + ty) * col_stride + p0 + tx;
+        auto rm_at = [&](int k) {
+            const uint32_t i = ty + 4 * (uint32_t)k;  // tile row
+            return rm + (uint64_t)(BITREV ? __brev(i) >> 26 : i) * rm_step;
+        };
+        auto cm_at = [&](int k) { return cm + (uint64_t)(4 * k) * col_stride; };
         uint32_t t[16];
 #pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const uint32_t i = ty + 4 * (uint32_t)k;  // tile row
-            t[k] = sp[(uint64_t)(__brev(i) >> 26) * row_step];
-        }
+        for (int k = 0; k < 16; k++) t[k] = src[TO_COLUMNS ? rm_at(k) : cm_at(k)];
 #pragma unroll
-        for (int k = 0; k < 16; k++) tile[ty + 4 * k][tx] = t[k];
+        for (int k = 0; k < 16; k++) (TO_COLUMNS ? tile[ty + 4 * k][tx] : tile[tx][ty + 4 * k]) = t[k];
         __syncthreads();
-        uint32_t* dp = dst + (uint64_t)(c0 + ty) * dst_col_stride + p0 + tx;
 #pragma unroll
-        for (int k = 0; k < 16; k++) t[k] = tile[tx][ty + 4 * k];
+        for (int k = 0; k < 16; k++) t[k] = TO_COLUMNS ? tile[tx][ty + 4 * k] : tile[ty + 4 * k][tx];
 #pragma unroll
-        for (int k = 0; k < 16; k++) dp[(uint64_t)(4 * k) * dst_col_stride] = t[k];
+        for (int k = 0; k < 16; k++) dst[TO_COLUMNS ? cm_at(k) : rm_at(k)] = t[k];
         return;
     }
-    for (uint32_t i = ty; i < rows; i += 4) {
-        uint32_t r = bitrev32(p0 + i, log_n);
-        uint32_t c = c0 + tx;
-        if (c < w) tile[i][tx] = src[(uint64_t)r * src_width + c];
+    // partial tile (also h < 64 and heights that are no power of two): every element guarded
+    auto rm_ok = [&](uint32_t j) { return p0 + j < h && c0 + tx < w; };  // (row p0 + j, column c0 + tx)
+    auto cm_ok = [&](uint32_t j) { return c0 + j < w && p0 + tx < h; };  // (column c0 + j, slot p0 + tx)
+    auto rm_at = [&](uint32_t j) { return row_of(p0 + j) * rm_width + c0 + tx; };
+    auto cm_at = [&](uint32_t j) { return (uint64_t)(c0 + j) * col_stride + p0 + tx; };
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t j = ty + 4 * (uint32_t)k;
+        if (TO_COLUMNS ? rm_ok(j) : cm_ok(j)) (TO_COLUMNS ? tile[j][tx] : tile[tx][j]) = src[TO_COLUMNS ? rm_at(j) : cm_at(j)];
     }
     __syncthreads();
-    for (uint32_t cc = ty; cc < 64; cc += 4) {
-        uint32_t c = c0 + cc;
-        if (c < w && tx < rows) dst[(uint64_t)c * dst_col_stride + p0 + tx] = tile[tx][cc];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t j = ty + 4 * (uint32_t)k;
+        if (TO_COLUMNS ? cm_ok(j) : rm_ok(j)) dst[TO_COLUMNS ? cm_at(j) : rm_at(j)] = TO_COLUMNS ? tile[tx][j] : tile[j][tx];
     }
 }
 
+// `name`: the kernel-timer name of the use (bench.py looks k_transpose_bitrev up)
+template <bool TO_COLUMNS, bool BITREV>
+static void launch_transpose_tile(Context& ctx, const char* name, const uint32_t* src, uint32_t* dst, uint64_t h,
+                                  unsigned log_h, uint32_t w, uint64_t col_stride, uint32_t rm_width) {
+    if (w == 0 || h == 0) return;
+    TS_LAUNCH_NAMED(ctx, name, (k_transpose_tile<TO_COLUMNS, BITREV>), dim3((unsigned)((h + 63) / 64), (w + 63) / 64),
+                    dim3(256), 0, src, dst, h, log_h, w, col_stride, rm_width);
+    TS_HIP(hipGetLastError());
+}
+
+// src row-major [n][w] natural  ->  dst[c][p] = src[bitrev(p)][c]
 void launch_transpose_bitrev(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_n,
                              uint32_t w, uint64_t dst_col_stride, uint32_t src_width) {
-    if (w == 0) return;
-    unsigned tr = log_n < 6 ? log_n : 6;
-    dim3 grid(1u << (log_n - tr), (w + 63) / 64);
-    TS_LAUNCH(ctx, k_transpose_bitrev, grid, dim3(256), 0, src, dst, log_n, w, dst_col_stride,
-              src_width ? src_width : w);
-    TS_HIP(hipGetLastError());
+    launch_transpose_tile<true, true>(ctx, "k_transpose_bitrev", src, dst, 1ull << log_n, log_n, w, dst_col_stride,
+                                      src_width ? src_width : w);
 }
 
 // src row-major [n][w]  ->  dst[c][r] = src[r][c], any n
-__global__ void k_transpose_plain(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
-                                  uint64_t n, uint32_t w, uint64_t dst_col_stride) {
-    __shared__ uint32_t tile[64][65];
-    const uint64_t r0 = (uint64_t)blockIdx.x * 64;
-    const uint32_t c0 = blockIdx.y * 64;
-    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (uint32_t i = ty; i < 64; i += 4) {
-        const uint32_t c = c0 + tx;
-        if (c < w && r0 + i < n) tile[i][tx] = src[(r0 + i) * w + c];
-    }
-    __syncthreads();
-    for (uint32_t cc = ty; cc < 64; cc += 4) {
-        const uint32_t c = c0 + cc;
-        if (c < w && r0 + tx < n) dst[(uint64_t)c * dst_col_stride + r0 + tx] = tile[tx][cc];
-    }
-}
-
 void launch_transpose_plain(Context& ctx, const uint32_t* src, uint32_t* dst, uint64_t n, uint32_t w,
                             uint64_t dst_col_stride) {
-    dim3 grid((unsigned)((n + 63) / 64), (w + 63) / 64);
-    TS_LAUNCH(ctx, k_transpose_plain, grid, dim3(256), 0, src, dst, n, w, dst_col_stride);
-    TS_HIP(hipGetLastError());
+    launch_transpose_tile<true, false>(ctx, "k_transpose_plain", src, dst, n, 0, w, dst_col_stride, w);
 }
 
-// dst row-major [h][w]  <-  src column-major
-__global__ void k_transpose_to_row_major(const uint32_t* __restrict__ src, uint64_t col_stride,
-                                         uint32_t* __restrict__ dst, uint64_t h, uint32_t w) {
-    __shared__ uint32_t tile[64][65];
-    const uint64_t r0 = (uint64_t)blockIdx.x * 64;
-    const uint32_t c0 = blockIdx.y * 64;
-    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (uint32_t cc = ty; cc < 64; cc += 4) {
-        uint32_t c = c0 + cc;
-        if (c < w && r0 + tx < h) tile[tx][cc] = src[(uint64_t)c * col_stride + r0 + tx];
-    }
-    __syncthreads();
-    for (uint32_t i = ty; i < 64; i += 4) {
-        uint32_t c = c0 + tx;
-        if (c < w && r0 + i < h) dst[(r0 + i) * w + c] = tile[i][tx];
-    }
-}
-
+// dst row-major [h][w]  <-  src column-major, any h
 void launch_transpose_to_row_major(Context& ctx, const uint32_t* src, uint64_t col_stride,
                                    uint32_t* dst, uint64_t h, uint32_t w) {
-    dim3 grid((unsigned)((h + 63) / 64), (w + 63) / 64);
-    TS_LAUNCH(ctx, k_transpose_to_row_major, grid, dim3(256), 0, src, col_stride, dst, h, w);
-    TS_HIP(hipGetLastError());
+    launch_transpose_tile<false, false>(ctx, "k_transpose_to_row_major", src, dst, h, 0, w, col_stride, w);
+}
+
+// dst[bitrev(p)][c] row-major, natural rows  <-  src column-major, rows p < 2^log_h in bit-reversed order
+void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_stride, uint32_t* dst,
+                               unsigned log_h, uint32_t w) {
+    launch_transpose_tile<false, true>(ctx, "k_transpose_unbitrev", src, dst, 1ull << log_h, log_h, w, col_stride, w);
 }
 
 }  // namespace ts

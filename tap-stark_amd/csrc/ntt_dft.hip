@@ -4,19 +4,19 @@
 // ts_pcs_open, without a trip to the host.
 //
 // The arithmetic is that of the coset LDE (ntt_lde.hip: block-twiddle radix-2 stages in register rounds of
-// up to 16 / 32 elements, the padded LDS image, the same plan split -- ntt_rounds.hpp); what is new is
-// every pass on its own, in one direction:
+// up to 16 / 32 elements, the padded LDS image -- ntt_rounds.hpp) under the same pass plan (ntt_plan.hpp).
+// The contiguous passes ARE the LDE's: launch_contig_inverse / launch_contig_forward (ntt_lde.hip) run
+// k_intt_contig on one matrix and k_lde_fwd_contig on one coset block.  What is new here is the strided pass on
+// its own, in one direction:
 //   k_dft_mid     the strided stages 0 .. sA-1 of ONE direction on tiles of 2^sA rows x 2^log_T slots,
 //                 with the per-coefficient factor of a coset applied where the coefficients are:
 //                 forward  x_k *= shift^k on the way in, then stages 0 .. sA-1   (natural in)
 //                 inverse  stages sA-1 .. 0, then x_k *= shift^-k / n on the way out (natural, canonical out)
 //                 For n <= 4096 it is the whole transform (one tile = one column).
-//   k_dft_contig  stages sA .. log_n-1 on 2^LM-element chunks, in place, either direction with its
-//                 twiddle table (forward: after k_dft_mid, canonical out; inverse: before it, lazy out)
-//   k_transpose_unbitrev   column-major with bit-reversed rows -> row-major with natural rows: the
-//                 output transpose of the forward transforms and of the LDE, and -- on the first
-//                 2^log_size rows of a committed LDE -- get_evaluations_on_domain
 //   k_bit_reverse_rows     row-major -> row-major, rows permuted
+// (launch_transpose_unbitrev, ntt.hip: column-major with bit-reversed rows -> row-major with natural rows, the
+// output transpose of the forward transforms and of the LDE, and -- on the first 2^log_size rows of a
+// committed LDE -- get_evaluations_on_domain.)
 // Forward: natural coefficients in, bit-reversed evaluations out; inverse: the reverse (ntt.hip header).
 // The factor is lo[k & 1023] * hi[k >> 10] from the two small tables of launch_build_shift_tables (one
 // coset): 2 loads and 2 products per element in one pass, instead of an n-word table per (n, shift) in
@@ -105,54 +105,7 @@ k_dft_mid(uint32_t* data, uint64_t col_stride, unsigned log_len, unsigned log_T,
     }
 }
 
-// ------------------------------------------------------------------ contiguous pass, one direction
-// chunk blockIdx.x of column blockIdx.y, in place: global stages log_n-LM .. log_n-1 (forward, after the
-// strided pass: canonical out) or the same backwards (inverse, before it: lazy out)
-template <int LM, bool INV>
-__global__ void __launch_bounds__(chunk_threads(LM))
-k_dft_contig(uint32_t* __restrict__ data, uint64_t col_stride, unsigned log_n, const uint32_t* __restrict__ W) {
-    __shared__ uint32_t s[padded(1 << LM)];
-    const uint32_t c = blockIdx.x;
-    uint32_t* g = data + (uint64_t)blockIdx.y * col_stride + ((uint64_t)c << LM);
-    chunk_load<LM>(s, g);
-    chunk_rounds<LM, INV>(s, log_n - LM, c, W);
-    chunk_store<LM, !INV>(s, g);
-}
-
-// ------------------------------------------------------------------ transposes
-// src column-major, rows p < 2^log_h in bit-reversed order  ->  dst[bitrev(p)][c] row-major, natural rows
-__global__ void __launch_bounds__(256)
-k_transpose_unbitrev(const uint32_t* __restrict__ src, uint64_t col_stride, uint32_t* __restrict__ dst,
-                     unsigned log_h, uint32_t w) {
-    __shared__ uint32_t tile[64][65];
-    const unsigned tr = log_h < 6 ? log_h : 6;  // log2 of tile rows
-    const uint32_t rows = 1u << tr;
-    const uint32_t p0 = blockIdx.x << tr;
-    const uint32_t c0 = blockIdx.y * 64;
-    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    // 16 loads in flight (64 consecutive p of one column each), then 16 row pieces of 64 columns
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const uint32_t c = c0 + ty + 4 * (uint32_t)k;
-        if (c < w && tx < rows) tile[tx][ty + 4 * k] = src[(uint64_t)c * col_stride + p0 + tx];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const uint32_t i = ty + 4 * (uint32_t)k;
-        if (i < rows && c0 + tx < w) dst[(uint64_t)bitrev32(p0 + i, log_h) * w + c0 + tx] = tile[i][tx];
-    }
-}
-
-void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_stride, uint32_t* dst,
-                               unsigned log_h, uint32_t w) {
-    if (w == 0) return;
-    const unsigned tr = log_h < 6 ? log_h : 6;
-    TS_LAUNCH(ctx, k_transpose_unbitrev, dim3(1u << (log_h - tr), (w + 63) / 64), dim3(256), 0, src, col_stride,
-              dst, log_h, w);
-    TS_HIP(hipGetLastError());
-}
-
+// ------------------------------------------------------------------ row permutation
 // dst[r] = src[bitrev(r)], both row-major h x w
 __global__ void __launch_bounds__(256)
 k_bit_reverse_rows(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, unsigned log_h, uint32_t w) {
@@ -171,22 +124,44 @@ void launch_bit_reverse_rows(Context& ctx, const uint32_t* src, uint32_t* dst, u
 }
 
 // ------------------------------------------------------------------ host drivers
+// the strided pass of one direction (the whole transform when the plan has one pass); `names`: the kernel-timer
+// names of the three variants in NttMid's order, spelled as tools/time_dft.py has always printed them
+template <bool INV, bool SCALE>
+static void launch_dft_mid_of(Context& ctx, const NttPlan& p, uint32_t* cols, uint64_t col_stride, uint32_t ncols,
+                              const uint32_t* f_lo, const uint32_t* f_hi, const char* const (&names)[3]) {
+    const uint32_t* W = INV ? ctx.d_twiddle_inv : ctx.d_twiddle_fwd;
+    auto launch = [&](auto kernel) {
+        TS_LAUNCH_NAMED(ctx, names[(int)p.mid], kernel, dim3(p.tiles, ncols), dim3(NT_MID), 0, cols, col_stride,
+                        p.log_len, p.log_T, p.row_shift, W, f_lo, f_hi);
+    };
+    if (p.mid == NttMid::TILE16384) launch(k_dft_mid<INV, SCALE, 0, 16384>);
+    else if (p.mid == NttMid::FIXED256) launch(k_dft_mid<INV, SCALE, 1>);
+    else launch(k_dft_mid<INV, SCALE, 0>);
+}
+
+static void launch_dft_mid(Context& ctx, const NttPlan& p, uint32_t* cols, uint64_t col_stride, uint32_t ncols,
+                           bool inverse, bool scale, const uint32_t* f_lo, const uint32_t* f_hi) {
+    if (inverse)
+        launch_dft_mid_of<true, true>(ctx, p, cols, col_stride, ncols, f_lo, f_hi,
+                                      {"(k_dft_mid<true, true, 0>)", "(k_dft_mid<true, true, 1>)",
+                                       "(k_dft_mid<true, true, 0, 16384>)"});
+    else if (scale)
+        launch_dft_mid_of<false, true>(ctx, p, cols, col_stride, ncols, f_lo, f_hi,
+                                       {"(k_dft_mid<false, true, 0>)", "(k_dft_mid<false, true, 1>)",
+                                        "(k_dft_mid<false, true, 0, 16384>)"});
+    else
+        launch_dft_mid_of<false, false>(ctx, p, cols, col_stride, ncols, f_lo, f_hi,
+                                        {"(k_dft_mid<false, false, 0>)", "(k_dft_mid<false, false, 1>)",
+                                         "(k_dft_mid<false, false, 0, 16384>)"});
+}
+
 void dft_columns(Context& ctx, uint32_t* cols, uint64_t col_stride, uint32_t ncols, unsigned log_n, bool inverse,
                  uint32_t shift) {
     if (ncols == 0) return;
     TS_REQUIRE(shift != 0 && shift < P, TS_ERR_INVALID, "dft: the coset shift must be in [1, p)");
-    TS_REQUIRE(ncols <= 65535, TS_ERR_INVALID, "dft: more than 65535 columns");
-    const unsigned LM = lde_chunk_log(log_n);
-    const bool two_pass = log_n > LM;
-    const unsigned sA = two_pass ? log_n - LM : 0;  // stages of the strided pass
-    // sA <= 13 fits the 8192-element tile, sA = 14 (n = 2^26) the 16384-element one, as in coset_lde
-    TS_REQUIRE(sA <= 14, TS_ERR_INVALID, "dft: height above 2^26");
-    TS_REQUIRE(!two_pass || col_stride % 4 == 0, TS_ERR_INVALID, "dft: column stride must be a multiple of 4 elements");
+    const NttPlan p = ntt_plan(log_n);
+    ntt_require_shape(p, ncols, col_stride, 0, false);
     ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
-    const uint32_t* W = inverse ? ctx.d_twiddle_inv : ctx.d_twiddle_fwd;
-    unsigned log_T = 0;
-    if (two_pass && sA <= 13)
-        while ((1u << (sA + log_T + 1)) <= (unsigned)TILE_ELEMS && log_T < 6) log_T++;
 
     // factor of coefficient k: shift^k (forward; none for shift 1) or shift^-k / n (inverse)
     const bool scale = inverse || shift != 1;
@@ -199,51 +174,12 @@ void dft_columns(Context& ctx, uint32_t* cols, uint64_t col_stride, uint32_t nco
         launch_build_shift_tables(ctx, lo.p, hi.p, n_hi, 1, to_mont(inverse ? inv_canon(shift) : shift), log_n, 0,
                                   inverse ? to_mont(n_inv) : R_MOD_P);
     }
-    const uint32_t* flo = lo.p;
-    const uint32_t* fhi = hi.p;
-
-    auto contig = [&] {
-        const dim3 g(1u << sA, ncols);
-#define TS_DFT_CONTIG(LMV)                                                                                     \
-    do {                                                                                                       \
-        if (inverse)                                                                                           \
-            TS_LAUNCH(ctx, (k_dft_contig<LMV, true>), g, dim3(chunk_threads(LMV)), 0, cols, col_stride, log_n, W); \
-        else                                                                                                   \
-            TS_LAUNCH(ctx, (k_dft_contig<LMV, false>), g, dim3(chunk_threads(LMV)), 0, cols, col_stride, log_n, W); \
-    } while (0)
-        if (LM == 12) TS_DFT_CONTIG(12);
-        else if (LM == 13) TS_DFT_CONTIG(13);
-        else TS_DFT_CONTIG(14);
-#undef TS_DFT_CONTIG
-    };
-    auto mid = [&] {
-        const dim3 grid(two_pass ? 1u << (LM - log_T) : 1u, ncols);
-        const unsigned log_len = two_pass ? sA : log_n, row_shift = two_pass ? LM : 0;
-#define TS_DFT_MID(...)                                                                                       \
-    TS_LAUNCH(ctx, (k_dft_mid<__VA_ARGS__>), grid, dim3(NT_MID), 0, cols, col_stride, log_len, log_T, row_shift, W, \
-              flo, fhi)
-        const int plan = sA == 14 ? 2 : (sA == 8 && log_T == 5) ? 1 : 0;
-        if (inverse) {
-            if (plan == 2) TS_DFT_MID(true, true, 0, 16384);
-            else if (plan == 1) TS_DFT_MID(true, true, 1);
-            else TS_DFT_MID(true, true, 0);
-        } else if (scale) {
-            if (plan == 2) TS_DFT_MID(false, true, 0, 16384);
-            else if (plan == 1) TS_DFT_MID(false, true, 1);
-            else TS_DFT_MID(false, true, 0);
-        } else {
-            if (plan == 2) TS_DFT_MID(false, false, 0, 16384);
-            else if (plan == 1) TS_DFT_MID(false, false, 1);
-            else TS_DFT_MID(false, false, 0);
-        }
-#undef TS_DFT_MID
-    };
     if (inverse) {
-        if (two_pass) contig();
-        mid();
+        if (p.two_pass) launch_contig_inverse(ctx, p, cols, col_stride, ncols);
+        launch_dft_mid(ctx, p, cols, col_stride, ncols, true, true, lo.p, hi.p);
     } else {
-        mid();
-        if (two_pass) contig();
+        launch_dft_mid(ctx, p, cols, col_stride, ncols, false, scale, lo.p, hi.p);
+        if (p.two_pass) launch_contig_forward(ctx, p, cols, col_stride, ncols, 1);
     }
     TS_HIP(hipGetLastError());
 }

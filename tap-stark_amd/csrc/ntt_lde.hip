@@ -32,6 +32,13 @@
 // busy 0.67 with 44 % of its wave-cycles parked at barriers and scale-table loads).  The extra one
 // or two stages go to the contiguous passes as radix-32 register rounds (13 = 5+4+4, 14 = 5+5+4):
 // still three LDS round trips per chunk.
+//
+// Those decisions are made in one place, ntt_plan(log_n) (ntt_plan.hpp, host only); the launchers at the end
+// of this file turn a plan into grids.  The two contiguous kernels also serve the standalone transforms
+// (ntt_dft.hip) through launch_contig_inverse / launch_contig_forward: an inverse pass on one matrix, a
+// forward pass on one coset block.
+#include <type_traits>
+
 #include "ntt_rounds.hpp"
 
 namespace ts {
@@ -320,16 +327,87 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
     }
 }
 
-// ------------------------------------------------------------------ host driver
-// (chunk size of the contiguous passes: lde_chunk_log, ntt_rounds.hpp)
+// ------------------------------------------------------------------ host drivers
+// The pass plan -- chunk size, tile shape, kernel variant, limits -- is ntt_plan.hpp's; the launchers below
+// only turn a plan into grids.
+//
+// KERNEL-TIMER NAMES.  bench.py (its roofline leg), tools/pmc_*.py and tools/rocpd_stats.py find a kernel's
+// time and its algorithmic bytes by these strings -- by stem, by "true" (the pass after the fused transpose),
+// by "k_lde_mid<1" -- so they are spelled out, here and in launch_lde_mid, parentheses included, and are not
+// to be tidied.  The standalone transforms (ntt_dft.hip) launch the same contiguous kernels under the same names.
+constexpr const char* INTT_NAME[3] = {"k_intt_contig<12>", "k_intt_contig<13>", "k_intt_contig<14>"};
+constexpr const char* INTT_R16_NAME[3] = {"(k_intt_contig<12, true>)", "(k_intt_contig<13, true>)",
+                                          "(k_intt_contig<14, true>)"};
+constexpr const char* FWD_NAME[3] = {"k_lde_fwd_contig<12>", "k_lde_fwd_contig<13>", "(k_lde_fwd_contig<14, 4>)"};
+
+// f(std::integral_constant<int, LM>) for the plan's chunk size
+template <class F>
+static void with_chunk_log(unsigned LM, F&& f) {
+    if (LM == 12) f(std::integral_constant<int, 12>{});
+    else if (LM == 13) f(std::integral_constant<int, 13>{});
+    else f(std::integral_constant<int, 14>{});
+}
+
 bool launch_transpose_bitrev_r16(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_n, uint32_t w,
                                  uint64_t dst_col_stride, uint32_t src_width) {
-    if (w == 0 || log_n <= lde_chunk_log(log_n)) return false;  // no contiguous inverse pass to shorten
+    if (w == 0 || !ntt_plan(log_n).fused_first_round) return false;  // no contiguous inverse pass to shorten
     ctx.ensure_twiddles(log_n);
     TS_LAUNCH(ctx, k_transpose_bitrev_r16, dim3(1u << (log_n - 6), (w + 63) / 64), dim3(256), 0, src, dst, log_n, w,
               dst_col_stride, src_width ? src_width : w, (const uint32_t*)ctx.d_twiddle_inv);
     TS_HIP(hipGetLastError());
     return true;
+}
+
+void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
+                           bool first_round_done, uint32_t* data2, uint32_t gw) {
+    const uint32_t* Winv = ctx.d_twiddle_inv;
+    with_chunk_log(p.LM, [&](auto lm) {
+        constexpr int LM = decltype(lm)::value;
+        const dim3 g(p.chunks, ncols), b(chunk_threads(LM));
+        if (first_round_done)
+            TS_LAUNCH_NAMED(ctx, INTT_R16_NAME[LM - 12], (k_intt_contig<LM, true>), g, b, 0, data, col_stride, p.log_n,
+                            Winv, data2, gw);
+        else
+            TS_LAUNCH_NAMED(ctx, INTT_NAME[LM - 12], k_intt_contig<LM>, g, b, 0, data, col_stride, p.log_n, Winv, data2,
+                            gw);
+    });
+}
+
+// the strided pass of the LDE on cosets beta0 .. beta0 + n_beta - 1 (the whole transform when the plan has
+// one pass); two matrices as coset_lde
+static void launch_lde_mid(Context& ctx, const NttPlan& p, const uint32_t* evals, uint64_t in_col_stride,
+                           uint32_t* out, uint64_t out_col_stride, uint32_t ncols, uint32_t beta0, uint32_t n_beta,
+                           const uint32_t* scale, const uint32_t* evals2, const uint32_t* scale2, uint32_t gw) {
+    const uint32_t *W = ctx.d_twiddle_fwd, *Winv = ctx.d_twiddle_inv;
+    const dim3 grid(p.tiles, ncols), b(NT_MID);
+    const dim3 grid1(p.tiles * ncols);  // the fixed plan: 1-D, see the kernel
+#define TS_MID_ARGS \
+    evals, in_col_stride, out, out_col_stride, p.log_n, p.log_len, p.log_T, p.row_shift, beta0, n_beta, W, Winv, scale, \
+        evals2, scale2, gw
+    if (p.mid == NttMid::TILE16384)
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<0, 16384>)", (k_lde_mid<0, 16384>), grid, b, 0, TS_MID_ARGS);
+    else if (p.mid == NttMid::FIXED256 && p.LM == 12)
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", k_lde_mid<1>, grid1, b, 0, TS_MID_ARGS);
+    else if (p.mid == NttMid::FIXED256 && p.LM == 13)
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 13>)", (k_lde_mid<1, 8192, 512, 13>), grid1, b, 0, TS_MID_ARGS);
+    else if (p.mid == NttMid::FIXED256)
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 14>)", (k_lde_mid<1, 8192, 512, 14>), grid1, b, 0, TS_MID_ARGS);
+    else
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<0>", k_lde_mid<0>, grid, b, 0, TS_MID_ARGS);
+#undef TS_MID_ARGS
+}
+
+void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
+                           uint32_t n_blocks) {
+    const uint32_t* W = ctx.d_twiddle_fwd;
+    with_chunk_log(p.LM, [&](auto lm) {
+        constexpr int LM = decltype(lm)::value;
+        // 4 chunks per workgroup of the 16384-element forward pass: measured 12.22 ms per proof against
+        // 12.49 with 1 and 13.34 with 2 (spills)
+        constexpr int CPW = LM == 14 ? 4 : 1;
+        TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig<LM, CPW>), dim3(p.chunks / CPW, ncols, n_blocks),
+                        dim3(chunk_threads(LM)), 0, data, col_stride, p.log_n, W);
+    });
 }
 
 void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t ncols, unsigned log_n,
@@ -341,20 +419,11 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
                "coset_lde: second matrix needs its first column and its shift");
     if (evals2 == nullptr) gw = 0xffffffffu;
     TS_REQUIRE(log_n + log_blowup <= 27, TS_ERR_INVALID, "coset_lde: log_n + log_blowup > 27");
-    TS_REQUIRE(ncols >= 1 && ncols <= 65535, TS_ERR_INVALID, "coset_lde: bad column count");
-    const unsigned LM = lde_chunk_log(log_n);
-    TS_REQUIRE(!first_round_done || log_n > LM, TS_ERR_INVARIANT, "coset_lde: no contiguous inverse pass at this size");
-    const bool two_pass = log_n > LM;
-    const unsigned sA = two_pass ? log_n - LM : 0;  // stages done by the strided (middle) kernel
-    // sA <= 13 fits the 8192-element tile; sA = 14 (n = 2^26, the longest trace a blowup of 2 leaves
-    // room for below the two-adicity 27) takes a 16384-element tile (68 KB of LDS)
-    TS_REQUIRE(sA <= 14, TS_ERR_INVALID, "coset_lde: log_n > 26");
+    const NttPlan p = ntt_plan(log_n);
+    ntt_require_shape(p, ncols, in_col_stride, out_col_stride, true);
+    TS_REQUIRE(!first_round_done || p.fused_first_round, TS_ERR_INVARIANT,
+               "coset_lde: no contiguous inverse pass at this size");
     ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
-    const uint32_t* W = ctx.d_twiddle_fwd;
-    const uint32_t* Winv = ctx.d_twiddle_inv;
-    unsigned log_T = 0;
-    if (two_pass && sA <= 13)
-        while ((1u << (sA + log_T + 1)) <= (unsigned)TILE_ELEMS && log_T < 6) log_T++;
 
     // per-coset scale table s_beta^k / n (cached per context: the trace's is the same every proof)
     const uint32_t n_cosets = 1u << log_blowup;
@@ -363,62 +432,22 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
     const uint32_t* scale = coset_scale_table(ctx, log_n, log_blowup, shift);
     const uint32_t* scale2 = evals2 ? coset_scale_table(ctx, log_n, log_blowup, shift2) : nullptr;
 
-    if (two_pass) {
-        // the vectorised chunk loads need 16-byte aligned columns
-        TS_REQUIRE(in_col_stride % 4 == 0 && out_col_stride % 4 == 0, TS_ERR_INVALID,
-                   "coset_lde: column strides must be multiples of 4 elements");
+    if (!p.two_pass) {
+        launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2, scale2,
+                       gw);
+    } else {
         // (ctx.lde_pass_mask: measurement only -- ts_bench_stage runs one of the three passes alone, on
         // whatever the buffers hold, to sample its clock and power; every product path leaves it at 7)
         if (ctx.lde_pass_mask & 1u) {
             // (stage names: the sharded prover reports where a rank's time goes)
             StageTimer t(&ctx, "lde: inverse NTT, contiguous stages");
-            const dim3 g(1u << sA, ncols);
-#define TS_INTT(LMV)                                                                                          \
-    do {                                                                                                      \
-        if (first_round_done)                                                                                 \
-            TS_LAUNCH(ctx, (k_intt_contig<LMV, true>), g, dim3(chunk_threads(LMV)), 0, evals, in_col_stride, log_n, \
-                      Winv, evals2, gw);                                                                      \
-        else                                                                                                  \
-            TS_LAUNCH(ctx, k_intt_contig<LMV>, g, dim3(chunk_threads(LMV)), 0, evals, in_col_stride, log_n, Winv, \
-                      evals2, gw);                                                                            \
-    } while (0)
-            if (LM == 12) TS_INTT(12);
-            else if (LM == 13) TS_INTT(13);
-            else TS_INTT(14);
-#undef TS_INTT
+            launch_contig_inverse(ctx, p, evals, in_col_stride, ncols, first_round_done, evals2, gw);
         }
         StageTimer t_rest(&ctx, "lde: strided pass + forward NTT of the owned cosets");
-        const dim3 grid(1u << (LM - log_T), ncols);
-        const dim3 grid1((1u << (LM - log_T)) * ncols);  // PLAN 1: 1-D, see the kernel
-#define TS_MID_ARGS                                                                            \
-    (const uint32_t*)evals, in_col_stride, out, out_col_stride, log_n, sA, log_T, (unsigned)LM, \
-        beta0, n_beta, W, Winv, scale, (const uint32_t*)evals2, scale2, gw
-        if (!(ctx.lde_pass_mask & 2u)) {
-        } else if (sA == 14)
-            TS_LAUNCH(ctx, (k_lde_mid<0, 16384>), grid, dim3(NT_MID), 0, TS_MID_ARGS);
-        else if (sA == 8 && log_T == 5 && LM == 12)
-            TS_LAUNCH(ctx, k_lde_mid<1>, grid1, dim3(NT_MID), 0, TS_MID_ARGS);
-        else if (sA == 8 && log_T == 5 && LM == 13)
-            TS_LAUNCH(ctx, (k_lde_mid<1, 8192, 512, 13>), grid1, dim3(NT_MID), 0, TS_MID_ARGS);
-        else if (sA == 8 && log_T == 5 && LM == 14)
-            TS_LAUNCH(ctx, (k_lde_mid<1, 8192, 512, 14>), grid1, dim3(NT_MID), 0, TS_MID_ARGS);
-        else
-            TS_LAUNCH(ctx, k_lde_mid<0>, grid, dim3(NT_MID), 0, TS_MID_ARGS);
-        const dim3 gf(1u << sA, ncols, n_beta);
-        // 4 chunks per workgroup of the 16384-element forward pass: measured 12.22 ms per proof against
-        // 12.49 with 1 and 13.34 with 2 (spills)
-        if (!(ctx.lde_pass_mask & 4u)) {
-        } else if (LM == 12)
-            TS_LAUNCH(ctx, k_lde_fwd_contig<12>, gf, dim3(chunk_threads(12)), 0, out, out_col_stride, log_n, W);
-        else if (LM == 13)
-            TS_LAUNCH(ctx, k_lde_fwd_contig<13>, gf, dim3(chunk_threads(13)), 0, out, out_col_stride, log_n, W);
-        else
-            TS_LAUNCH(ctx, (k_lde_fwd_contig<14, 4>), dim3(gf.x / 4, gf.y, gf.z), dim3(chunk_threads(14)), 0, out,
-                      out_col_stride, log_n, W);
-    } else {
-        TS_LAUNCH(ctx, k_lde_mid<0>, dim3(1, ncols), dim3(NT_MID), 0, (const uint32_t*)evals,
-                  in_col_stride, out, out_col_stride, log_n, log_n, 0u, 0u, beta0, n_beta, W, Winv, scale,
-                  (const uint32_t*)evals2, scale2, gw);
+        if (ctx.lde_pass_mask & 2u)
+            launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2,
+                           scale2, gw);
+        if (ctx.lde_pass_mask & 4u) launch_contig_forward(ctx, p, out, out_col_stride, ncols, n_beta);
     }
     TS_HIP(hipGetLastError());
 }

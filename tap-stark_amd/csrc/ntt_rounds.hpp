@@ -1,16 +1,16 @@
-// The register-radix rounds, the padded LDS image and the chunk plan of the NTT kernels, shared by the
-// coset LDE (ntt_lde.hip, whose header describes the image and the plan) and the standalone transforms
-// (ntt_dft.hip).  Device code only: include from a .hip file.
+// The register-radix rounds and the padded LDS image of the NTT kernels, shared by the coset LDE
+// (ntt_lde.hip, whose header describes the image and the plan) and the standalone transforms
+// (ntt_dft.hip).  Device code only: include from a .hip file.  The pass plan itself -- chunk size, tile
+// shape, kernel variant -- is host code: ntt_plan.hpp.
 #pragma once
 #include "kernels.hpp"
+#include "ntt_plan.hpp"
 
 namespace ts {
 
-constexpr int LOG_M = 12;          // default contiguous chunk = 4096 elements
 constexpr int NT_MID = 512;        // threads per workgroup, middle kernel
 // threads per workgroup of the contiguous kernels: 16 elements per thread at LM = 12, 32 above
 constexpr int chunk_threads(int lm) { return lm == 14 ? 512 : 256; }
-constexpr int TILE_ELEMS = 8192;   // strided tile (generic plan)
 
 __device__ __forceinline__ uint32_t pad(uint32_t i) { return i + (i >> 5); }
 constexpr int padded(int n) { return n + (n >> 5); }
@@ -217,12 +217,6 @@ __device__ __forceinline__ void chunk_rounds(uint32_t* s, unsigned sb, uint32_t 
         radix_round<K1, true, 4, NT>(s, LM, K0, sb, c, W);
         radix_round<K0, true, LM - K0, NT>(s, LM, 0, sb, c, W);
     }
-}
-
-// chunk size of the contiguous passes: 2^12, or log_n - 8 for n = 2^21 / 2^22 (ntt_lde.hip header).
-// The one place that decides it: the fused transpose, coset_lde and the standalone transforms ask here.
-inline unsigned lde_chunk_log(unsigned log_n) {
-    return (log_n == 21 || log_n == 22) ? log_n - 8 : (unsigned)LOG_M;
 }
 
 }  // namespace ts

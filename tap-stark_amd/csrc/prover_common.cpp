@@ -394,13 +394,13 @@ double bench_stage(Context& c, int stage, unsigned log_n, uint32_t width, unsign
                    log_n + log_blowup <= 27,
                TS_ERR_INVALID, "bench_stage: stage 0 .. 4, width 1..256, log_n + log_blowup <= 27");
     // stages 2, 3, 4: ONE pass of the LDE alone (inverse contiguous / strided middle / forward
-    // contiguous; two-pass shapes only, log_n > 12), on whatever the buffers hold
+    // contiguous; two-pass plans only, ntt_plan.hpp), on whatever the buffers hold
     struct MaskGuard {
         Context& c;
         ~MaskGuard() { c.lde_pass_mask = 7; }
     } guard_mask{c};
     if (stage >= 2) {
-        TS_REQUIRE(log_n > 12, TS_ERR_INVALID, "bench_stage: single LDE passes exist for log_n > 12 only");
+        TS_REQUIRE(ntt_plan(log_n).two_pass, TS_ERR_INVALID, "bench_stage: single LDE passes exist for log_n > 12 only");
         c.lde_pass_mask = 1u << (stage - 2);
     }
     const bool is_lde = stage != 1;

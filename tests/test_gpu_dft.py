@@ -253,3 +253,60 @@ def test_error_paths(ctx, dft):
         ts.DeviceMatrix.upload(ctx, x[: 3 << 10])
     assert ei.value.code == 1
     assert (dm.download() == x).all()
+
+
+# ------------------------------------------------------------------ partial transpose tiles
+# 2^7 x 65: full 64-row tiles with one full and one partial column tile; 2^3 x 1: below one row tile.  (No call
+# of the C ABI can hand a transpose a height that is no power of two: matrices, LDEs and taptree inputs all
+# refuse one, test_error_paths above and taptree.cpp's log2_strict.)
+@pytest.mark.parametrize("log_n,w", [(7, 65), (3, 1)], ids=["2^7x65", "2^3x1"])
+def test_partial_tile_transposes_match_oracle(ctx, dft, orc, log_n, w):
+    x = rand_mat(9000 + 64 * log_n + w, 1 << log_n, w)
+    dm = ts.DeviceMatrix.upload(ctx, x)
+    assert same(dm.bit_reverse_rows().download(), oracle_bit_reverse_rows(orc, x)), "bit_reverse_rows"
+    assert same(dft.dft_batch(dm).download(), orc.dft_batch(x)), "dft_batch"
+    assert same(dft.idft_batch(dm).download(), orc.dft_batch(x, inverse=True)), "idft_batch"
+    assert same(dm.download(), x), "the input matrix was modified"
+
+
+# ------------------------------------------------------------------ kernel-timer names
+# bench.py and the profile tools find the NTT kernels by their timer names.  The names below are those of the
+# commit before the pass plan got one owner (ntt_plan.hpp) for the same calls, character for character as its
+# launch macros spelled them.
+NTT_STEMS = ("k_intt_contig", "k_lde_mid", "k_lde_fwd_contig", "k_dft_", "k_transpose")
+LDE_TIMER_NAMES = {
+    (12, 3): ["k_lde_mid<0>", "k_transpose_bitrev", "k_transpose_unbitrev"],
+    (13, 3): ["(k_intt_contig<12, true>)", "k_lde_fwd_contig<12>", "k_lde_mid<0>", "k_transpose_bitrev_r16",
+              "k_transpose_unbitrev"],
+    (20, 1): ["(k_intt_contig<12, true>)", "k_lde_fwd_contig<12>", "k_lde_mid<1>", "k_transpose_bitrev_r16",
+              "k_transpose_unbitrev"],
+    (21, 1): ["(k_intt_contig<13, true>)", "(k_lde_mid<1, 8192, 512, 13>)", "k_lde_fwd_contig<13>",
+              "k_transpose_bitrev_r16", "k_transpose_unbitrev"],
+    (22, 1): ["(k_intt_contig<14, true>)", "(k_lde_fwd_contig<14, 4>)", "(k_lde_mid<1, 8192, 512, 14>)",
+              "k_transpose_bitrev_r16", "k_transpose_unbitrev"],
+}
+# a Fibonacci proof at 2^13, log_blowup 1: the trace (two columns: a partial transpose tile) and its quotient chunk
+FIB_TIMER_NAMES = ["(k_intt_contig<12, true>)", "k_intt_contig<12>", "k_lde_fwd_contig<12>", "k_lde_mid<0>",
+                   "k_transpose_bitrev_r16"]
+
+
+def test_kernel_timer_names(ctx, dft):
+    from tapstark_amd.airs import FibonacciAir, fibonacci_public_values, generate_fibonacci_trace
+
+    def ntt_names():
+        return sorted(k for k in ctx.take_kernel_timings() if k.lstrip("(").startswith(NTT_STEMS))
+
+    mats = {shape: ts.DeviceMatrix.upload(ctx, rand_mat(sum(shape), 1 << shape[0], shape[1])) for shape in LDE_TIMER_NAMES}
+    trace = generate_fibonacci_trace(0, 1, 1 << 13)
+    pis = fibonacci_public_values(trace)
+    config = ts.StarkConfig(ts.TwoAdicFriPcs(ts.FriConfig(1, 4, 0), ctx))
+    ctx.set_kernel_timing(True)
+    try:
+        ctx.take_kernel_timings()
+        for shape, want in LDE_TIMER_NAMES.items():
+            dft.coset_lde_batch(mats[shape], 1, 31)
+            assert ntt_names() == sorted(want), shape
+        ts.prove(config, FibonacciAir(), ts.BfChallenger(), trace, pis)
+        assert ntt_names() == sorted(FIB_TIMER_NAMES)
+    finally:
+        ctx.set_kernel_timing(False)
