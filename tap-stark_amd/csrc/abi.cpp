@@ -15,6 +15,7 @@
 #include "abi_types.hpp"
 #include "blake3.hpp"
 #include "jit.hpp"
+#include "prover_internal.hpp"
 
 // the program as the prover sees it; the handle is const in the prove calls, adopting a finished specialisation is not
 static const ts::AirProgram& ready_prog(const ts_air* air) { return const_cast<ts_air*>(air)->a.ready(); }
@@ -1304,13 +1305,7 @@ ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* 
         TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
         TS_REQUIRE(n_public == p.n_public, ts::TS_ERR_INVALID, "check_constraints: public value count");
         TS_REQUIRE(n_public == 0 || public_values, ts::TS_ERR_INVALID, "null public values");
-        std::vector<uint32_t> consts(std::max<size_t>(p.const_canonical.size(), 1), 0);
-        for (size_t k = 0; k < p.const_canonical.size(); k++) {
-            uint32_t v = p.const_public_idx[k] != ~0u ? public_values[p.const_public_idx[k]]
-                                                      : p.const_canonical[k];
-            TS_REQUIRE(v < ts::P, ts::TS_ERR_INVALID, "non-canonical public value");
-            consts[k] = ts::to_mont(v);
-        }
+        const std::vector<uint32_t> consts = ts::air_consts_mont(p, public_values, n_public);
         ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
         ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
         TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice,

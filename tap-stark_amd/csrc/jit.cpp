@@ -56,7 +56,9 @@ Rtc& rtc() {
     return r;
 }
 
-const char* kPrelude = R"SRC(
+// The generated text, by what it is: the helper functions with the two argument structs (the start of every
+// module), the kernel head (signature and row addressing, one for both kernel forms) and the epilogue.
+const char* kHelpers = R"SRC(
 typedef unsigned int u32;
 typedef unsigned long long u64;
 #define P 0x78000001u
@@ -81,23 +83,36 @@ __device__ __forceinline__ u64 lazy_fix(u64 acc) {  // high word corrected in pl
 __device__ __forceinline__ u32 lazy_finish(u64 acc) { return mont_reduce(lazy_fix(acc)); }
 struct QC { u32 inv_zh[64]; };  // = QuotConsts
 struct QO { u32* chunk[64]; };  // = QuotOut, MAX_QUOTIENT_CHUNKS
-extern "C" __global__ void __launch_bounds__(256)
-k_quotient_jit(const u32* __restrict__ lde, u64 col_stride, unsigned log_n, unsigned log_qd,
+)SRC";
+
+// What differs between the heads of k_quotient_jit and k_quotient_seg<k>; the rest of the head is one text.
+struct KernelHead {
+    const char* launch_bounds;
+    std::string name;
+    const char* extra_params;  // after row_end: the slab of a segment
+    const char* row_index;     // the statements that define the row r of this thread
+};
+
+void emit_head(std::ostream& s, const KernelHead& h) {
+    s << "extern \"C\" __global__ void __launch_bounds__(" << h.launch_bounds << ")\n" << h.name;
+    s << R"SRC((const u32* __restrict__ lde, u64 col_stride, unsigned log_n, unsigned log_qd,
                const u32* __restrict__ C, const u32* __restrict__ AP, const u32* __restrict__ isf,
                const u32* __restrict__ isl, const u32* __restrict__ ist, QC qc, QO out,
-               u32 row_begin, u32 row_end) {
+               u32 row_begin, u32 row_end)SRC" << h.extra_params << R"SRC() {
     const unsigned L = log_n + log_qd;
     const u32 total = 1u << L;
-    const u32 r = row_begin + blockIdx.x * 256u + threadIdx.x;
-    if (r >= row_end) return;
+)SRC" << h.row_index << R"SRC(    if (r >= row_end) return;
     const u32 i = L ? (__brev(r) >> (32 - L)) : 0u;
     const u32 i_next = (i + (1u << log_qd)) & (total - 1u);
     const u32 r_next = L ? (__brev(i_next) >> (32 - L)) : 0u;
     const u32* __restrict__ row0 = lde + r;
     const u32* __restrict__ row1 = lde + r_next;
     const u32 sel0 = isf[r], sel1 = isl[r], sel2 = ist[r];
-    u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;
 )SRC";
+}
+
+const char* kAccZero = "    u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;\n";
+const char* kLazyFix = "    a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);\n";
 
 const char* kEpilogue = R"SRC(
     a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);
@@ -112,35 +127,59 @@ const char* kEpilogue = R"SRC(
 }
 )SRC";
 
+// How a kernel form names the values of the program: the monolithic kernel assigns its registers in place
+// (r<reg>), a segment defines each value once (const u32 v<defining instruction>).
+struct Naming {
+    const char* def;  // what stands before the id of a result
+    const char* use;  // what stands before the id of an operand
+};
+const Naming kRegisters{"    r", "r"};
+const Naming kValues{"    const u32 v", "v"};
+
+// a leaf (LOAD / CONST / SEL) as an expression: it has no register operands
+std::string leaf_expr(const uint32_t* ins) {
+    const std::string a = std::to_string(ins[2]);
+    if (ins[0] == D_LOAD) return "to_mont(row" + a + "[" + std::to_string(ins[3]) + "ull * col_stride])";
+    return (ins[0] == D_CONST ? "C[" + a + "]" : "sel" + a);
+}
+
+// D_ASSERT: acc += value * alpha_pow[b], the sums left lazy and their high words corrected after every
+// second one (bb.hpp lazy_fix)
+void emit_assert(std::ostream& s, const Naming& nm, uint32_t va, uint32_t b, uint32_t& n_assert) {
+    for (uint32_t q = 0; q < 4; q++)
+        s << (q ? " a" : "    a") << q << " += (u64)" << nm.use << va << " * AP[" << 4 * b + q << "];";
+    s << "\n";
+    if (++n_assert % 2 == 0) s << kLazyFix;
+}
+
+// One instruction {op, dst, a, b}: its result is named `dst`, its register operands `va`, `vb`.
+void emit_instr(std::ostream& s, const Naming& nm, const uint32_t* ins, uint32_t dst, uint32_t va, uint32_t vb,
+                uint32_t& n_assert) {
+    auto binary = [&](const char* fn) {
+        s << nm.def << dst << " = " << fn << "(" << nm.use << va << ", " << nm.use << vb << ");\n";
+    };
+    switch (ins[0]) {
+        case D_LOAD: case D_CONST: case D_SEL: s << nm.def << dst << " = " << leaf_expr(ins) << ";\n"; break;
+        case D_ADD: binary("add"); break;
+        case D_SUB: binary("sub"); break;
+        case D_NEG: s << nm.def << dst << " = neg(" << nm.use << va << ");\n"; break;
+        case D_MUL: binary("mont_mul"); break;
+        default: emit_assert(s, nm, va, ins[3], n_assert); break;
+    }
+}
+
 }  // namespace
 
 std::string jit_quotient_source(const AirProgram& air) {
     std::ostringstream s;
-    s << kPrelude;
+    s << kHelpers;
+    emit_head(s, {"256", "k_quotient_jit", "", "    const u32 r = row_begin + blockIdx.x * 256u + threadIdx.x;\n"});
+    s << kAccZero;
     for (uint32_t r = 0; r < air.n_regs; r++) s << "    u32 r" << r << " = 0;\n";
-    const size_t n_instr = air.code.size() / 4;
     uint32_t n_assert = 0;
-    for (size_t pc = 0; pc < n_instr; pc++) {
-        const uint32_t op = air.code[4 * pc], dst = air.code[4 * pc + 1], a = air.code[4 * pc + 2],
-                       b = air.code[4 * pc + 3];
-        switch (op) {
-            case D_LOAD:
-                s << "    r" << dst << " = to_mont(row" << a << "[" << b << "ull * col_stride]);\n";
-                break;
-            case D_CONST: s << "    r" << dst << " = C[" << a << "];\n"; break;
-            case D_SEL: s << "    r" << dst << " = sel" << a << ";\n"; break;
-            case D_ADD: s << "    r" << dst << " = add(r" << a << ", r" << b << ");\n"; break;
-            case D_SUB: s << "    r" << dst << " = sub(r" << a << ", r" << b << ");\n"; break;
-            case D_NEG: s << "    r" << dst << " = neg(r" << a << ");\n"; break;
-            case D_MUL: s << "    r" << dst << " = mont_mul(r" << a << ", r" << b << ");\n"; break;
-            default:  // D_ASSERT: acc += reg[a] * alpha_pow[b]
-                s << "    a0 += (u64)r" << a << " * AP[" << 4 * b << "]; a1 += (u64)r" << a << " * AP["
-                  << 4 * b + 1 << "]; a2 += (u64)r" << a << " * AP[" << 4 * b + 2 << "]; a3 += (u64)r"
-                  << a << " * AP[" << 4 * b + 3 << "];\n";
-                if (++n_assert % 2 == 0)
-                    s << "    a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);\n";
-                break;
-        }
+    for (size_t pc = 0; pc < air.code.size() / 4; pc++) {
+        const uint32_t* ins = &air.code[4 * pc];
+        emit_instr(s, kRegisters, ins, ins[1], ins[2], ins[3], n_assert);
     }
     s << kEpilogue;
     return s.str();
@@ -150,37 +189,18 @@ std::string jit_quotient_source(const AirProgram& air) {
 // slab as S[slot * slab_rows] (one u32 per row of the tile: coalesced), the accumulators as 8 words after
 // lazy_fix.  Values are named v<defining instruction>; a value from an earlier segment is materialised right
 // before its first use here (a slab load, or the leaf itself re-emitted).
-const char* kSegHead = R"SRC(
-extern "C" __global__ void __launch_bounds__(256, 4)
-k_quotient_seg%u(const u32* __restrict__ lde, u64 col_stride, unsigned log_n, unsigned log_qd,
-               const u32* __restrict__ C, const u32* __restrict__ AP, const u32* __restrict__ isf,
-               const u32* __restrict__ isl, const u32* __restrict__ ist, QC qc, QO out,
-               u32 row_begin, u32 row_end, u32* __restrict__ slab, u32 slab_rows) {
-    const unsigned L = log_n + log_qd;
-    const u32 total = 1u << L;
-    const u32 t = blockIdx.x * 256u + threadIdx.x;
-    const u32 r = row_begin + t;
-    if (r >= row_end) return;
-    const u32 i = L ? (__brev(r) >> (32 - L)) : 0u;
-    const u32 i_next = (i + (1u << log_qd)) & (total - 1u);
-    const u32 r_next = L ? (__brev(i_next) >> (32 - L)) : 0u;
-    const u32* __restrict__ row0 = lde + r;
-    const u32* __restrict__ row1 = lde + r_next;
-    const u32 sel0 = isf[r], sel1 = isl[r], sel2 = ist[r];
-    u32* __restrict__ S = slab + t;
-)SRC";
-
 static std::string seg_kernel(const AirProgram& air, const SegmentPlan& plan, uint32_t k) {
     const SegmentPlan::Segment& sg = plan.segs[k];
     const bool last = k + 1 == plan.segs.size();
     const uint32_t W = plan.slab_width;
-    char head[2048];
-    snprintf(head, sizeof head, kSegHead, k);
     std::ostringstream s;
-    s << head;
+    s << "\n";
+    emit_head(s, {"256, 4", "k_quotient_seg" + std::to_string(k), ", u32* __restrict__ slab, u32 slab_rows",
+                  "    const u32 t = blockIdx.x * 256u + threadIdx.x;\n    const u32 r = row_begin + t;\n"});
+    s << "    u32* __restrict__ S = slab + t;\n";
     auto sl = [&](uint32_t slot) { return "S[" + std::to_string(slot) + "ull * slab_rows]"; };
     if (k == 0) {
-        s << "    u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;\n";
+        s << kAccZero;
     } else {
         for (int q = 0; q < 4; q++)
             s << "    u64 a" << q << " = (u64)" << sl(W + 2 * q) << " | ((u64)" << sl(W + 2 * q + 1) << " << 32);\n";
@@ -190,43 +210,21 @@ static std::string seg_kernel(const AirProgram& air, const SegmentPlan& plan, ui
     std::vector<std::vector<const SegmentPlan::Slot*>> stores(sg.end - sg.begin);
     for (const auto& lo : sg.live_out) stores[lo.at - sg.begin].push_back(&lo);
     std::vector<uint8_t> have(air.code.size() / 4, 0);
-    auto leaf = [&](uint32_t v) {
-        const uint32_t op = air.code[4 * v], a = air.code[4 * v + 2], b = air.code[4 * v + 3];
-        if (op == D_LOAD) return "to_mont(row" + std::to_string(a) + "[" + std::to_string(b) + "ull * col_stride])";
-        if (op == D_CONST) return "C[" + std::to_string(a) + "]";
-        return "sel" + std::to_string(a);  // D_SEL
-    };
     uint32_t n_assert = 0;
     for (uint32_t pc = sg.begin; pc < sg.end; pc++) {
-        const uint32_t op = air.code[4 * pc];
         const uint32_t va = plan.opdef[2 * (size_t)pc], vb = plan.opdef[2 * (size_t)pc + 1];
         for (uint32_t v : {va, vb}) {
             if (v == ~0u || v >= sg.begin || have[v]) continue;
             have[v] = 1;
-            s << "    const u32 v" << v << " = " << (slot_in[v] != ~0u ? sl(slot_in[v]) : leaf(v)) << ";\n";
+            s << kValues.def << v << " = " << (slot_in[v] != ~0u ? sl(slot_in[v]) : leaf_expr(&air.code[4 * (size_t)v])) << ";\n";
         }
-        switch (op) {
-            case D_LOAD: case D_CONST: case D_SEL: s << "    const u32 v" << pc << " = " << leaf(pc) << ";\n"; break;
-            case D_ADD: s << "    const u32 v" << pc << " = add(v" << va << ", v" << vb << ");\n"; break;
-            case D_SUB: s << "    const u32 v" << pc << " = sub(v" << va << ", v" << vb << ");\n"; break;
-            case D_NEG: s << "    const u32 v" << pc << " = neg(v" << va << ");\n"; break;
-            case D_MUL: s << "    const u32 v" << pc << " = mont_mul(v" << va << ", v" << vb << ");\n"; break;
-            default: {  // D_ASSERT
-                const uint32_t b = air.code[4 * pc + 3];
-                s << "    a0 += (u64)v" << va << " * AP[" << 4 * b << "]; a1 += (u64)v" << va << " * AP[" << 4 * b + 1
-                  << "]; a2 += (u64)v" << va << " * AP[" << 4 * b + 2 << "]; a3 += (u64)v" << va << " * AP["
-                  << 4 * b + 3 << "];\n";
-                if (++n_assert % 2 == 0)
-                    s << "    a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);\n";
-                break;
-            }
-        }
+        emit_instr(s, kValues, &air.code[4 * (size_t)pc], pc, va, vb, n_assert);
         for (const SegmentPlan::Slot* st : stores[pc - sg.begin]) s << "    " << sl(st->slot) << " = v" << st->def << ";\n";
     }
     if (last) {
         s << kEpilogue;
     } else {  // lazy_fix first: the next segment starts from the overflow invariant of a fresh sum
-        s << "    a0 = lazy_fix(a0); a1 = lazy_fix(a1); a2 = lazy_fix(a2); a3 = lazy_fix(a3);\n";
+        s << kLazyFix;
         for (int q = 0; q < 4; q++)
             s << "    " << sl(W + 2 * q) << " = (u32)a" << q << "; " << sl(W + 2 * q + 1) << " = (u32)(a" << q
               << " >> 32);\n";
@@ -242,11 +240,9 @@ uint32_t jit_segment_module_first(const SegmentPlan& plan, uint32_t n_modules, u
 
 std::vector<std::string> jit_segment_sources(const AirProgram& air, const SegmentPlan& plan, uint32_t n_modules) {
     n_modules = std::max(1u, std::min<uint32_t>(n_modules, (uint32_t)plan.segs.size()));
-    const std::string pre(kPrelude);
-    const std::string helpers = pre.substr(0, pre.find("extern \"C\""));
     std::vector<std::string> out;
     for (uint32_t j = 0; j < n_modules; j++) {
-        std::string src = helpers;
+        std::string src = kHelpers;
         for (uint32_t k = jit_segment_module_first(plan, n_modules, j); k < jit_segment_module_first(plan, n_modules, j + 1); k++)
             src += seg_kernel(air, plan, k);
         out.push_back(std::move(src));

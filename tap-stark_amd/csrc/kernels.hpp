@@ -146,8 +146,9 @@ inline uint64_t merkle_total_digests(unsigned log_leaves) { return ((uint64_t)2 
 
 // ---- quotient.hip ----------------------------------------------------------------------------
 struct AirProgram;  // air.hpp
-void launch_selectors(Context& ctx, unsigned log_n, unsigned log_qd, uint32_t* is_first,
-                      uint32_t* is_last, uint32_t* is_transition, uint32_t shift = GENERATOR);
+// is_first | is_last | is_transition on the quotient domain shift * H_{n qd} in storage (bit-reversed) order,
+// qn = 2^(log_n + log_qd) words each, Montgomery form.  Cached per context (Context::sel_tables).
+const uint32_t* selector_table(Context& ctx, unsigned log_n, unsigned log_qd, uint32_t shift);
 // quotient chunks, each written column-major (4 columns x n) with bit-reversed rows:
 // coefficient k of chunk c at chunk[c][k * n + pos]
 constexpr int MAX_QUOTIENT_CHUNKS = 64;  // quotient_degree <= 64 (log_quotient_degree <= log_blowup <= 8)
@@ -157,9 +158,9 @@ struct QuotOut {
 // Rows [row_begin, row_end) of the quotient domain only (row_end = 0: all); trace_lde.d must then
 // be such that d[c * col_stride + r] is valid for those rows r and their `next` rows (a sharded
 // prover passes its slab pointer minus the slab's first row; whole cosets keep `next` local).
+// `shift`: the domain is shift * H_{n qd}; the selectors come from selector_table for the same shift.
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
-                     const uint32_t* is_first, const uint32_t* is_last, const uint32_t* is_transition,
                      const QuotOut& out, uint64_t row_begin = 0, uint64_t row_end = 0,
                      uint32_t shift = GENERATOR);
 // sharded.cpp "local quotient": in place on the slab LDEs of the qd chunk matrices (4 columns each),

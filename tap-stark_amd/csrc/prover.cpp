@@ -133,45 +133,17 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
     // whole cosets only: `next` (natural index + qd) stays inside a coset of H_n
     TS_REQUIRE(row_begin % n == 0 && row_end % n == 0, TS_ERR_INVALID, "quotient: slab must hold whole cosets");
 
-    // selectors depend on the shape only: kept in the context between proofs (two tables, LRU)
-    Context::SelTable* st = nullptr;
-    for (auto& t : ctx_.sel_tables)
-        if (t.d && t.log_n == log_n && t.log_qd == lqd && t.shift == domain_shift) st = &t;
-    if (!st) {
-        st = ctx_.sel_tables[0].last_use <= ctx_.sel_tables[1].last_use ? &ctx_.sel_tables[0] : &ctx_.sel_tables[1];
-        if (st->d) {
-            ctx_.sync();  // an earlier launch may still read the old table
-            (void)hipFree(st->d);
-            st->d = nullptr;
-        }
-        TS_HIP(hipMalloc((void**)&st->d, 3 * qn * sizeof(uint32_t)));
-        launch_selectors(ctx_, log_n, lqd, st->d, st->d + qn, st->d + 2 * qn, domain_shift);
-        st->log_n = log_n;
-        st->log_qd = lqd;
-        st->shift = domain_shift;
-    }
-    st->last_use = ++ctx_.sel_clock;
-    struct { uint32_t* p; } sel{st->d};
-
-    // constants / public values in Montgomery form
-    std::vector<uint32_t> consts(std::max<size_t>(air.const_canonical.size(), 1), 0);
-    for (size_t k = 0; k < air.const_canonical.size(); k++) {
-        uint32_t v = air.const_public_idx[k] != ~0u ? pis[air.const_public_idx[k]] : air.const_canonical[k];
-        TS_REQUIRE(v < P, TS_ERR_INVALID, "non-canonical public value");
-        consts[k] = to_mont(v);
-    }
-    // alpha^(K-1-i): folder.rs:60-64 unrolled (acc = acc*alpha + c_i)
-    const uint32_t K = air.n_constraints;
-    const std::vector<uint32_t> pw = alpha_powers_mont(alpha, K);
-    std::vector<uint32_t> apow(std::max<size_t>(4 * (size_t)K, 4), 0);
-    for (uint32_t i = 0; i < K; i++) memcpy(&apow[4 * (size_t)(K - 1 - i)], &pw[4 * (size_t)i], 16);
-    // one upload for both (a small host-to-device copy is a launch of its own on the stream)
+    // constants / public values, then alpha^(K-1-i): folder.rs:60-64 unrolled (acc = acc*alpha + c_i).  One
+    // upload for both (a small host-to-device copy is a launch of its own on the stream)
+    std::vector<uint32_t> consts = air_consts_mont(air, pis.data(), pis.size());
     consts.resize((consts.size() + 3) & ~(size_t)3, 0);  // the powers stay 16-byte aligned
     const size_t n_consts = consts.size();
-    consts.insert(consts.end(), apow.begin(), apow.end());
+    const uint32_t K = air.n_constraints;
+    const std::vector<uint32_t> pw = alpha_powers_mont(alpha, K);
+    consts.resize(n_consts + std::max<size_t>(4 * (size_t)K, 4), 0);
+    for (uint32_t i = 0; i < K; i++) memcpy(&consts[n_consts + 4 * (size_t)(K - 1 - i)], &pw[4 * (size_t)i], 16);
     DevBuf<uint32_t> d_consts(&ctx_, consts.size());
     h2d(ctx_, d_consts.p, consts.data(), consts.size() * 4);
-    struct { uint32_t* p; } d_apow{d_consts.p + n_consts};
 
     std::vector<DeviceMatrix> chunks(qd);
     QuotOut qo;
@@ -186,8 +158,8 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
     if (row_begin < row_end) {
         ColMat lde = lde_slab;
         lde.d = lde_slab.d - slab.row0;  // global row r of the slab's range lives at d[r]
-        launch_quotient(ctx_, air, lde, log_n, lqd, d_consts.p, d_apow.p, sel.p, sel.p + qn, sel.p + 2 * qn,
-                        qo, row_begin, row_end, domain_shift);
+        launch_quotient(ctx_, air, lde, log_n, lqd, d_consts.p, d_consts.p + n_consts, qo, row_begin, row_end,
+                        domain_shift);
     }
     return chunks;  // (the staged uploads live in the context's pinned arena: no sync needed)
 }

@@ -201,6 +201,17 @@ Statement check_statement(const FriConfig& fri, const AirProgram& air, uint32_t 
 }
 
 // ------------------------------------------------------------------ host numerics
+std::vector<uint32_t> air_consts_mont(const AirProgram& air, const uint32_t* pis, size_t n) {
+    TS_REQUIRE(n == air.n_public, TS_ERR_INVALID, "wrong number of public values");
+    std::vector<uint32_t> consts(std::max<size_t>(air.const_canonical.size(), 1), 0);
+    for (size_t k = 0; k < air.const_canonical.size(); k++) {
+        const uint32_t v = air.const_public_idx[k] != ~0u ? pis[air.const_public_idx[k]] : air.const_canonical[k];
+        TS_REQUIRE(v < P, TS_ERR_INVALID, "non-canonical public value");
+        consts[k] = to_mont(v);
+    }
+    return consts;
+}
+
 std::vector<uint32_t> alpha_powers_mont(Ef alpha, size_t count) {
     std::vector<uint32_t> pw(4 * count);
     const Ef am = ef_to_mont(alpha);

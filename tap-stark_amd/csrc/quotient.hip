@@ -78,21 +78,51 @@ k_selectors(unsigned L, unsigned log_qd, const uint32_t* __restrict__ W, uint32_
     }
 }
 
-void launch_selectors(Context& ctx, unsigned log_n, unsigned log_qd, uint32_t* is_first,
-                      uint32_t* is_last, uint32_t* is_transition, uint32_t shift) {
-    const unsigned L = log_n + log_qd;
+// Z_H on the qd cosets of the quotient domain, canonical: shift^n * omega_qd^c - 1.  The one place the stage
+// works this out: the selectors multiply by it (Montgomery), the quotient divides by it.
+static void coset_vanishing(uint32_t shift, unsigned log_n, unsigned log_qd, uint32_t zh[MAX_QUOTIENT_CHUNKS]) {
     TS_REQUIRE((1u << log_qd) <= (unsigned)MAX_QUOTIENT_CHUNKS, TS_ERR_UNSUPPORTED, "quotient degree > 64 not supported");
-    ctx.ensure_twiddles(L == 0 ? 1 : L);
-    SelConsts sc;
     const uint32_t s_pow_n = pow_canon(shift, 1ull << log_n);
     const uint32_t gqd = two_adic_generator(log_qd);
-    for (uint32_t c = 0; c < (1u << log_qd); c++)
-        sc.zh_mont[c] = to_mont(sub(mul(s_pow_n, pow_canon(gqd, c)), 1));
+    for (uint32_t c = 0; c < (1u << log_qd); c++) zh[c] = sub(mul(s_pow_n, pow_canon(gqd, c)), 1);
+}
+
+static void launch_selectors(Context& ctx, unsigned log_n, unsigned log_qd, uint32_t* is_first,
+                             uint32_t* is_last, uint32_t* is_transition, uint32_t shift) {
+    const unsigned L = log_n + log_qd;
+    ctx.ensure_twiddles(L == 0 ? 1 : L);
+    SelConsts sc;
+    coset_vanishing(shift, log_n, log_qd, sc.zh_mont);
+    for (uint32_t c = 0; c < (1u << log_qd); c++) sc.zh_mont[c] = to_mont(sc.zh_mont[c]);
     const uint32_t gn_inv = inv_canon(two_adic_generator(log_n));
     const uint64_t threads = (((uint64_t)1 << L) + SEL_BATCH - 1) / SEL_BATCH;
     TS_LAUNCH(ctx, k_selectors, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, L, log_qd, ctx.d_twiddle_fwd, to_mont(shift), to_mont(gn_inv), sc, is_first,
                        is_last, is_transition);
     TS_HIP(hipGetLastError());
+}
+
+// Selectors depend on the shape and the shift only: kept in the context between proofs (Context::sel_tables,
+// two entries, least recently used goes).
+const uint32_t* selector_table(Context& ctx, unsigned log_n, unsigned log_qd, uint32_t shift) {
+    Context::SelTable* st = nullptr;
+    for (auto& t : ctx.sel_tables)
+        if (t.d && t.log_n == log_n && t.log_qd == log_qd && t.shift == shift) st = &t;
+    if (!st) {
+        st = ctx.sel_tables[0].last_use <= ctx.sel_tables[1].last_use ? &ctx.sel_tables[0] : &ctx.sel_tables[1];
+        if (st->d) {
+            ctx.sync();  // an earlier launch may still read the old table
+            (void)hipFree(st->d);
+            *st = Context::SelTable{};  // matches nothing until the new table is built
+        }
+        const uint64_t qn = 1ull << (log_n + log_qd);
+        TS_HIP(hipMalloc((void**)&st->d, 3 * qn * sizeof(uint32_t)));
+        launch_selectors(ctx, log_n, log_qd, st->d, st->d + qn, st->d + 2 * qn, shift);
+        st->log_n = log_n;
+        st->log_qd = log_qd;
+        st->shift = shift;
+    }
+    st->last_use = ++ctx.sel_clock;
+    return st->d;
 }
 
 // ------------------------------------------------------------------ interpreter
@@ -110,8 +140,15 @@ struct RegFilePlan {
     bool global;
     size_t lds_bytes;
     unsigned grid;
+    uint32_t n_tiles;  // of nthreads rows; more than `grid` where the slab caps a persistent grid
     size_t scratch_words;
 };
+
+// a measurement knob, read on every call (tests set them in-process); unset or empty: the default
+static uint64_t env_u64(const char* name, uint64_t dflt) {
+    const char* e = getenv(name);
+    return e && *e ? (uint64_t)atoi(e) : dflt;
+}
 
 static RegFilePlan plan_reg_file(Context& ctx, uint32_t n_regs, uint64_t rows) {
     RegFilePlan pl;
@@ -121,28 +158,99 @@ static RegFilePlan plan_reg_file(Context& ctx, uint32_t n_regs, uint64_t rows) {
     // LDS only while a 256-lane workgroup's file stays small (several workgroups per CU); beyond that the
     // global slab is FASTER, not just possible: 424 registers in LDS leave one wave per CU (16.6 ms on a
     // 2^18-row domain against 3.9 from the slab, profiles/r06_quotient_paths.txt).  Knobs for measurements.
-    const size_t lds_max_regs = [] { const char* e = getenv("TS_INTERP_LDS_MAX_REGS"); return e ? (size_t)atoi(e) : (size_t)48; }();
-    const unsigned waves_per_cu = [] { const char* e = getenv("TS_INTERP_WAVES_PER_CU"); return e ? (unsigned)atoi(e) : 16u; }();
+    const size_t lds_max_regs = env_u64("TS_INTERP_LDS_MAX_REGS", 48);
+    const unsigned waves_per_cu = (unsigned)env_u64("TS_INTERP_WAVES_PER_CU", 16);
     pl.global = n_regs > lds_max_regs || pl.lds_bytes > ctx.max_lds_per_block || getenv("TS_INTERP_GLOBAL_REGS") != nullptr;
-    const uint64_t tiles = (rows + pl.nthreads - 1) / pl.nthreads;
+    if (pl.global) pl.nthreads = 64;
+    pl.n_tiles = (uint32_t)((rows + pl.nthreads - 1) / pl.nthreads);
     if (pl.global) {
-        pl.nthreads = 64;
         pl.lds_bytes = 0;
-        const uint64_t t64 = (rows + 63) / 64;
         // a few waves per SIMD hide the slab's latency (16 per CU: 1.5x over 8, 32 adds nothing); the slab stays
         // below 4 GiB of the 288 (a smaller, cache-resident slab is slower: the grid is what matters)
-        uint64_t grid = std::min<uint64_t>(t64, (uint64_t)ctx.num_cus * waves_per_cu);
-        const uint64_t slab_mb = [] { const char* e = getenv("TS_INTERP_SLAB_MB"); return e ? (uint64_t)atoi(e) : (uint64_t)4096; }();
+        uint64_t grid = std::min<uint64_t>(pl.n_tiles, (uint64_t)ctx.num_cus * waves_per_cu);
+        const uint64_t slab_mb = env_u64("TS_INTERP_SLAB_MB", 4096);
         const uint64_t cap = (slab_mb << 18) / ((uint64_t)n_regs * 64);
         grid = std::max<uint64_t>(1, std::min(grid, cap));
         pl.grid = (unsigned)grid;
-        pl.scratch_words = (size_t)grid * n_regs * 64;
     } else {
-        pl.grid = (unsigned)tiles;
-        pl.scratch_words = 0;
+        pl.grid = pl.n_tiles;
     }
+    pl.scratch_words = pl.global ? (size_t)pl.grid * n_regs * 64 : 0;
     return pl;
 }
+
+// This lane's column of the register file: element `reg` at my[reg * NTHREADS].
+template <int NTHREADS, bool GLOBAL_REGS>
+__device__ __forceinline__ uint32_t* lane_regs(uint32_t* reg_slabs, uint32_t n_regs) {
+    extern __shared__ uint32_t lds_regs[];  // [n_regs][NTHREADS] unless GLOBAL_REGS
+    return GLOBAL_REGS ? reg_slabs + (size_t)blockIdx.x * n_regs * NTHREADS + threadIdx.x : lds_regs + threadIdx.x;
+}
+
+// The program on one row, for one lane: what the eight instructions (air.hpp DevOp) mean.  `Row` is what a
+// kernel knows about its row: load(a, b) = the canonical word of column b of the local (a = 0) or next row,
+// sel(a) = selector a (Montgomery), on_assert(value, b) = what constraint b's value is used for.
+//
+// Wave-uniform instruction fetch (scalar loads), one instruction ahead.  The value an instruction
+// produces stays in a VGPR for the next one (`fwd`): in a post-order evaluation the next instruction
+// nearly always consumes it, and reading it back from the register file would put a memory round
+// trip (LDS or, worse, the slab) on every link of the dependency chain.
+template <int NTHREADS, class Row>
+__device__ __forceinline__ void run_program(const uint32_t* code, uint32_t n_instr,
+                                            const uint32_t* consts_mont, uint32_t* my, Row& row) {
+    const uint4* code4 = reinterpret_cast<const uint4*>(code);
+    uint4 ins = code4[0];
+    uint32_t fwd_reg = ~0u, fwd_val = 0;
+    auto rd = [&](uint32_t reg) { return reg == fwd_reg ? fwd_val : my[(size_t)reg * NTHREADS]; };
+    for (uint32_t pc = 0; pc < n_instr; pc++) {
+        const uint4 nxt = code4[pc + 1 < n_instr ? pc + 1 : pc];
+        const uint32_t op = ins.x, dst = ins.y, a = ins.z, b = ins.w;
+        ins = nxt;
+        uint32_t v;
+        switch (op) {
+            case D_LOAD: v = to_mont(row.load(a, b)); break;
+            case D_CONST: v = consts_mont[a]; break;
+            case D_SEL: v = row.sel(a); break;
+            case D_ADD: v = add(rd(a), rd(b)); break;
+            case D_SUB: v = sub(rd(a), rd(b)); break;
+            case D_NEG: v = neg(rd(a)); break;
+            case D_MUL: v = mont_mul(rd(a), rd(b)); break;
+            default: row.on_assert(rd(a), b); continue;  // D_ASSERT
+        }
+        my[(size_t)dst * NTHREADS] = v;
+        fwd_reg = dst;
+        fwd_val = v;
+    }
+}
+
+// what both kernels' rows have in common: two row pointers and three selector words
+struct RowBase {
+    const uint32_t* row_local;
+    const uint32_t* row_next;
+    uint32_t sel0, sel1, sel2;
+    __device__ __forceinline__ uint32_t sel(uint32_t a) const {
+        // all three read first: a choice between the members themselves is compiled to an index into the
+        // struct, which then stays in memory (scratch) instead of registers
+        const uint32_t s0 = sel0, s1 = sel1, s2 = sel2;
+        return a == 0 ? s0 : (a == 1 ? s1 : s2);
+    }
+};
+
+// a row of the quotient domain in the column-major LDE; the constraints go into sum_i c_i alpha^(K-1-i)
+struct QuotientRow : RowBase {
+    uint64_t col_stride;
+    const uint32_t* alpha_pows;
+    uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
+        return (a ? row_next : row_local)[(uint64_t)b * col_stride];
+    }
+    __device__ __forceinline__ void on_assert(uint32_t c, uint32_t b) {
+        const uint32_t* ap = alpha_pows + 4 * b;
+        acc0 = add(acc0, mont_mul(c, ap[0]));
+        acc1 = add(acc1, mont_mul(c, ap[1]));
+        acc2 = add(acc2, mont_mul(c, ap[2]));
+        acc3 = add(acc3, mont_mul(c, ap[3]));
+    }
+};
 
 template <int NTHREADS, bool GLOBAL_REGS>
 __global__ void __launch_bounds__(NTHREADS)
@@ -152,11 +260,9 @@ k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
            const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
            const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
            uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    extern __shared__ uint32_t lds_regs[];  // [n_regs][NTHREADS] unless GLOBAL_REGS
     const unsigned L = log_n + log_qd;
     const uint32_t total = 1u << L;
-    uint32_t* my = GLOBAL_REGS ? reg_slabs + (size_t)blockIdx.x * n_regs * NTHREADS + threadIdx.x
-                               : lds_regs + threadIdx.x;
+    uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint32_t r = row_begin + tile * NTHREADS + threadIdx.x;
         const bool active = r < row_end;
@@ -164,50 +270,8 @@ k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
         const uint32_t i = bitrev32(rr, L);
         const uint32_t i_next = (i + (1u << log_qd)) & (total - 1);  // prover.rs:139-140,165
         const uint32_t r_next = bitrev32(i_next, L);
-        const uint32_t sel0 = is_first[rr], sel1 = is_last[rr], sel2 = is_transition[rr];
-        const uint32_t* row_local = lde + rr;
-        const uint32_t* row_next = lde + r_next;
-        uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-
-        // Wave-uniform instruction fetch (scalar loads), one instruction ahead.  The value an instruction
-        // produces stays in a VGPR for the next one (`fwd`): in a post-order evaluation the next instruction
-        // nearly always consumes it, and reading it back from the register file would put a memory round
-        // trip (LDS or, worse, the slab) on every link of the dependency chain.
-        const uint4* code4 = reinterpret_cast<const uint4*>(code);
-        uint4 ins = code4[0];
-        uint32_t fwd_reg = ~0u, fwd_val = 0;
-        auto rd = [&](uint32_t reg) { return reg == fwd_reg ? fwd_val : my[(size_t)reg * NTHREADS]; };
-        for (uint32_t pc = 0; pc < n_instr; pc++) {
-            const uint4 nxt = code4[pc + 1 < n_instr ? pc + 1 : pc];
-            const uint32_t op = ins.x, dst = ins.y, a = ins.z, b = ins.w;
-            ins = nxt;
-            uint32_t v;
-            switch (op) {
-                case D_LOAD: {
-                    const uint32_t* base = a ? row_next : row_local;
-                    v = to_mont(base[(uint64_t)b * col_stride]);
-                    break;
-                }
-                case D_CONST: v = consts_mont[a]; break;
-                case D_SEL: v = a == 0 ? sel0 : (a == 1 ? sel1 : sel2); break;
-                case D_ADD: v = add(rd(a), rd(b)); break;
-                case D_SUB: v = sub(rd(a), rd(b)); break;
-                case D_NEG: v = neg(rd(a)); break;
-                case D_MUL: v = mont_mul(rd(a), rd(b)); break;
-                default: {  // D_ASSERT
-                    const uint32_t c = rd(a);
-                    const uint32_t* ap = alpha_pows + 4 * b;
-                    acc0 = add(acc0, mont_mul(c, ap[0]));
-                    acc1 = add(acc1, mont_mul(c, ap[1]));
-                    acc2 = add(acc2, mont_mul(c, ap[2]));
-                    acc3 = add(acc3, mont_mul(c, ap[3]));
-                    continue;
-                }
-            }
-            my[(size_t)dst * NTHREADS] = v;
-            fwd_reg = dst;
-            fwd_val = v;
-        }
+        QuotientRow row{{lde + rr, lde + r_next, is_first[rr], is_last[rr], is_transition[rr]}, col_stride, alpha_pows};
+        run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
         if (!active) continue;
         // quotient(x) = constraints(x) / Z_H(x)  (prover.rs:183); flatten + split (prover.rs:78-80):
         // natural row i -> chunk i % qd, position i / qd; stored bit-reversed = r & (n-1)
@@ -215,35 +279,53 @@ k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
         const uint32_t iz = qc.inv_zh_canonical[c];
         const uint64_t n = 1ull << log_n;
         uint32_t* o = out.chunk[c] + (r & (n - 1));
-        o[0] = mont_mul(acc0, iz);
-        o[n] = mont_mul(acc1, iz);
-        o[2 * n] = mont_mul(acc2, iz);
-        o[3 * n] = mont_mul(acc3, iz);
+        o[0] = mont_mul(row.acc0, iz);
+        o[n] = mont_mul(row.acc1, iz);
+        o[2 * n] = mont_mul(row.acc2, iz);
+        o[3 * n] = mont_mul(row.acc3, iz);
     }
 }
 
-template <class K>
-static void allow_lds(K kernel, size_t lds) {
+// The four instantiations of an interpreter kernel template (one function type), and the name of its timer.
+template <class F>
+struct InterpKernels {
+    const char* name;
+    F global64, lds256, lds128, lds64;
+};
+
+// Launches the instantiation that the register-file plan for `rows` rows asks for; `args` are the kernel's own,
+// between the program and the register file.
+template <class F, class... Args>
+static void launch_interpreter(Context& ctx, const InterpKernels<F>& k, const AirProgram& air, uint64_t rows,
+                               Args... args) {
+    TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
+    const RegFilePlan pl = plan_reg_file(ctx, air.n_regs, rows);
+    DevBuf<uint32_t> slabs;
+    if (pl.global) slabs = DevBuf<uint32_t>(&ctx, pl.scratch_words);
+    const F kernel = pl.global ? k.global64 : pl.nthreads == 256 ? k.lds256 : pl.nthreads == 128 ? k.lds128 : k.lds64;
     // above 64 KiB the dynamic LDS size has to be granted per function (gfx950: 160 KiB per workgroup)
-    if (lds > 48 * 1024)
-        TS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (pl.lds_bytes > 48 * 1024)
+        TS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+    TS_LAUNCH_NAMED(ctx, k.name, kernel, dim3(pl.grid), dim3(pl.nthreads), pl.lds_bytes, air.d_code,
+                    (uint32_t)(air.code.size() / 4), air.n_regs, args..., slabs.p, pl.n_tiles);
+    TS_HIP(hipGetLastError());
 }
 
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
-                     const uint32_t* is_first, const uint32_t* is_last, const uint32_t* is_transition,
                      const QuotOut& out, uint64_t row_begin, uint64_t row_end, uint32_t shift) {
     TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
     TS_REQUIRE(log_n + log_qd <= 31, TS_ERR_INVALID, "quotient domain too large");
+    const uint64_t qn = 1ull << (log_n + log_qd);
+    if (row_end == 0) row_end = qn;
+    TS_REQUIRE(row_begin < row_end && row_end <= qn, TS_ERR_INVALID, "quotient: row range");
+    // the selectors and 1/Z_H of this launch's own (shape, shift): they cannot disagree
+    const uint32_t* is_first = selector_table(ctx, log_n, log_qd, shift);
+    const uint32_t* is_last = is_first + qn;
+    const uint32_t* is_transition = is_first + 2 * qn;
     QuotConsts qc;
-    const uint32_t s_pow_n = pow_canon(shift, 1ull << log_n);
-    const uint32_t gqd = two_adic_generator(log_qd);
-    for (uint32_t c = 0; c < (1u << log_qd); c++)
-        qc.inv_zh_canonical[c] = inv_canon(sub(mul(s_pow_n, pow_canon(gqd, c)), 1));
-    const uint32_t n_instr = (uint32_t)(air.code.size() / 4);
-    if (row_end == 0) row_end = 1ull << (log_n + log_qd);
-    TS_REQUIRE(row_begin < row_end && row_end <= (1ull << (log_n + log_qd)), TS_ERR_INVALID,
-               "quotient: row range");
+    coset_vanishing(shift, log_n, log_qd, qc.inv_zh_canonical);
+    for (uint32_t c = 0; c < (1u << log_qd); c++) qc.inv_zh_canonical[c] = inv_canon(qc.inv_zh_canonical[c]);
     const uint64_t total = row_end - row_begin;  // rows to do
     uint32_t rb = (uint32_t)row_begin, re = (uint32_t)row_end;
     const JitKernelSet* ks = air.jit.load();  // once per launch: published whole (air.hpp KernelSetRef)
@@ -263,7 +345,7 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
         // segmented kernels (jit.cpp jit_segment_sources): per tile of rows, segments 0..K-1 in stream order,
         // values crossing a cut in a slab of [slab_width + 8][tile_rows] words from the context's pool
         const uint64_t width = (uint64_t)ks->seg->slab_width + SEG_ACC_SLOTS;
-        const uint64_t slab_mb = [] { const char* e = getenv("TS_SEG_SLAB_MB"); return e && *e ? (uint64_t)atoi(e) : (uint64_t)4096; }();
+        const uint64_t slab_mb = env_u64("TS_SEG_SLAB_MB", 4096);
         uint64_t tile = std::max<uint64_t>(256, ((slab_mb << 18) / width) & ~(uint64_t)255);
         tile = std::min<uint64_t>(tile, (total + 255) & ~(uint64_t)255);
         DevBuf<uint32_t> slab(&ctx, (size_t)(width * tile));
@@ -280,23 +362,10 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
         }
         return;
     }
-    const RegFilePlan pl = plan_reg_file(ctx, air.n_regs, total);
-    DevBuf<uint32_t> slabs;
-    if (pl.global) slabs = DevBuf<uint32_t>(&ctx, pl.scratch_words);
-    const uint32_t n_tiles = (uint32_t)((total + pl.nthreads - 1) / pl.nthreads);
-#define TS_LAUNCH_Q(NTH, GLOB)                                                                          \
-    do {                                                                                                \
-        allow_lds(k_quotient<NTH, GLOB>, pl.lds_bytes);                                                 \
-        TS_LAUNCH(ctx, (k_quotient<NTH, GLOB>), dim3(pl.grid), dim3(NTH), pl.lds_bytes, air.d_code, n_instr, \
-                  air.n_regs, trace_lde.d, trace_lde.col_stride, log_n, log_qd, d_consts_mont,          \
-                  d_alpha_pows_mont, is_first, is_last, is_transition, qc, out, rb, re, slabs.p, n_tiles); \
-    } while (0)
-    if (pl.global) TS_LAUNCH_Q(64, true);
-    else if (pl.nthreads == 256) TS_LAUNCH_Q(256, false);
-    else if (pl.nthreads == 128) TS_LAUNCH_Q(128, false);
-    else TS_LAUNCH_Q(64, false);
-#undef TS_LAUNCH_Q
-    TS_HIP(hipGetLastError());
+    static const InterpKernels<decltype(&k_quotient<64, true>)> kernels{
+        "k_quotient", k_quotient<64, true>, k_quotient<256, false>, k_quotient<128, false>, k_quotient<64, false>};
+    launch_interpreter(ctx, kernels, air, total, lde_p, stride, log_n, log_qd, d_consts_mont,
+                       d_alpha_pows_mont, is_first, is_last, is_transition, qc, qo, rb, re);
 }
 
 // ------------------------------------------------------------------ chunk mix (sharded local quotient)
@@ -344,51 +413,31 @@ void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, 
 // is_last_row = (i == h-1), is_transition = (i != h-1) and the next row wrapping around.
 // One thread per row of the row-major trace; the first violation (row * 2^16 + constraint index,
 // smallest wins) is left in *violation.
+// a row of the row-major trace; the first constraint that does not vanish goes into `bad`
+struct CheckRow : RowBase {
+    uint64_t i;  // this row
+    unsigned long long& bad;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const { return (a ? row_next : row_local)[b]; }
+    __device__ __forceinline__ void on_assert(uint32_t c, uint32_t b) {
+        if (c != 0 && bad == ~0ull) bad = i * 65536ull + b;
+    }
+};
+
 template <int NTHREADS, bool GLOBAL_REGS>
 __global__ void __launch_bounds__(NTHREADS)
 k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
                     const uint32_t* __restrict__ trace, uint32_t width, uint64_t n,
                     const uint32_t* __restrict__ consts_mont, unsigned long long* __restrict__ violation,
                     uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    extern __shared__ uint32_t lds_regs[];
-    uint32_t* my = GLOBAL_REGS ? reg_slabs + (size_t)blockIdx.x * n_regs * NTHREADS + threadIdx.x
-                               : lds_regs + threadIdx.x;
+    uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t i = (uint64_t)tile * NTHREADS + threadIdx.x;
         const bool active = i < n;
         const uint64_t ii = active ? i : 0;
-        const uint32_t* row_local = trace + ii * width;
-        const uint32_t* row_next = trace + ((ii + 1) % n) * width;
-        const uint32_t sel0 = ii == 0 ? R_MOD_P : 0u;
-        const uint32_t sel1 = ii == n - 1 ? R_MOD_P : 0u;
-        const uint32_t sel2 = ii != n - 1 ? R_MOD_P : 0u;
         unsigned long long bad = ~0ull;
-        const uint4* code4 = reinterpret_cast<const uint4*>(code);
-        uint4 ins = code4[0];
-        uint32_t fwd_reg = ~0u, fwd_val = 0;  // as in k_quotient
-        auto rd = [&](uint32_t reg) { return reg == fwd_reg ? fwd_val : my[(size_t)reg * NTHREADS]; };
-        for (uint32_t pc = 0; pc < n_instr; pc++) {
-            const uint4 nxt = code4[pc + 1 < n_instr ? pc + 1 : pc];
-            const uint32_t op = ins.x, dst = ins.y, a = ins.z, b = ins.w;
-            ins = nxt;
-            uint32_t v;
-            switch (op) {
-                case D_LOAD: v = to_mont((a ? row_next : row_local)[b]); break;
-                case D_CONST: v = consts_mont[a]; break;
-                case D_SEL: v = a == 0 ? sel0 : (a == 1 ? sel1 : sel2); break;
-                case D_ADD: v = add(rd(a), rd(b)); break;
-                case D_SUB: v = sub(rd(a), rd(b)); break;
-                case D_NEG: v = neg(rd(a)); break;
-                case D_MUL: v = mont_mul(rd(a), rd(b)); break;
-                default: {  // D_ASSERT
-                    if (rd(a) != 0 && bad == ~0ull) bad = ii * 65536ull + b;
-                    continue;
-                }
-            }
-            my[(size_t)dst * NTHREADS] = v;
-            fwd_reg = dst;
-            fwd_val = v;
-        }
+        CheckRow row{{trace + ii * width, trace + ((ii + 1) % n) * width, ii == 0 ? R_MOD_P : 0u,
+                      ii == n - 1 ? R_MOD_P : 0u, ii != n - 1 ? R_MOD_P : 0u}, ii, bad};
+        run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
         if (active && bad != ~0ull) atomicMin(violation, bad);
     }
 }
@@ -396,27 +445,12 @@ k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
                               unsigned long long* d_violation) {
-    TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
     // the report is row * 2^16 + constraint index (the oracle's and stark.py's format)
     TS_REQUIRE(air.n_constraints <= 65536, TS_ERR_UNSUPPORTED, "check_constraints: more than 65536 constraints");
-    const uint32_t n_instr = (uint32_t)(air.code.size() / 4);
-    const RegFilePlan pl = plan_reg_file(ctx, air.n_regs, n);
-    DevBuf<uint32_t> slabs;
-    if (pl.global) slabs = DevBuf<uint32_t>(&ctx, pl.scratch_words);
-    const uint32_t n_tiles = (uint32_t)((n + pl.nthreads - 1) / pl.nthreads);
-#define TS_LAUNCH_C(NTH, GLOB)                                                                         \
-    do {                                                                                               \
-        allow_lds(k_check_constraints<NTH, GLOB>, pl.lds_bytes);                                       \
-        TS_LAUNCH(ctx, (k_check_constraints<NTH, GLOB>), dim3(pl.grid), dim3(NTH), pl.lds_bytes,       \
-                  air.d_code, n_instr, air.n_regs, trace_row_major, air.width, n, d_consts_mont,       \
-                  d_violation, slabs.p, n_tiles);                                                      \
-    } while (0)
-    if (pl.global) TS_LAUNCH_C(64, true);
-    else if (pl.nthreads == 256) TS_LAUNCH_C(256, false);
-    else if (pl.nthreads == 128) TS_LAUNCH_C(128, false);
-    else TS_LAUNCH_C(64, false);
-#undef TS_LAUNCH_C
-    TS_HIP(hipGetLastError());
+    static const InterpKernels<decltype(&k_check_constraints<64, true>)> kernels{
+        "k_check_constraints", k_check_constraints<64, true>, k_check_constraints<256, false>,
+        k_check_constraints<128, false>, k_check_constraints<64, false>};
+    launch_interpreter(ctx, kernels, air, n, trace_row_major, air.width, n, d_consts_mont, d_violation);
 }
 
 }  // namespace ts
