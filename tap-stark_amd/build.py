@@ -95,6 +95,15 @@ def build(force: bool = False, verbose: bool = False, asan: bool = False, define
     helper = os.path.join(lib_dir, "ts_jitc")
     if force or not os.path.exists(helper) or os.path.getmtime(helper) < os.path.getmtime(helper_src):
         run(["g++", "-O2", "-std=c++17", "-o", helper, helper_src, "-ldl"])
+    # the field probe of tests/test_field_cpu.py and tests/test_gpu_field.py: a stand-alone program over the
+    # headers of csrc/, host and device build of the primitives from one source (beside the product library
+    # only: the sanitizer and diagnostic builds are libraries for TS_LIB_PATH and have no use for it)
+    if not asan and not defines:
+        probe_src = os.path.join(PKG, "probe", "field_probe.hip")
+        probe = os.path.join(lib_dir, "field_probe")
+        if force or not os.path.exists(probe) or os.path.getmtime(probe) < max(os.path.getmtime(probe_src), hdr_m):
+            run([hipcc, f"--offload-arch={ARCH}", "-x", "hip", "-O3", "-std=c++17", "-Wall", "-Wno-unused-function",
+                 "-I", CSRC, "-o", probe, probe_src])
     return lib
 
 

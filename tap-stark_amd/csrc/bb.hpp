@@ -23,7 +23,7 @@ constexpr uint32_t P = 0x78000001u;
 constexpr uint32_t P_INV = 0x88000001u;      // p^-1 mod 2^32
 constexpr uint32_t P_NEG_INV = 0x77ffffffu;  // -p^-1 mod 2^32
 constexpr uint32_t R_MOD_P = 0x0ffffffeu;    // 2^32 mod p  (Montgomery form of 1)
-constexpr uint32_t R2_MOD_P = 0x45dddde3u;   // 2^64 mod p  (checked by tests/test_host_field)
+constexpr uint32_t R2_MOD_P = 0x45dddde3u;   // 2^64 mod p  (checked by tests/test_field_cpu.py)
 constexpr uint32_t GENERATOR = 31u;
 constexpr uint32_t TWO_ADIC_GEN_27 = 0x1a427a41u;
 constexpr uint32_t EF_W = 11u;

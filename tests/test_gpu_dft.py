@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import tapstark_amd as ts
+from _field_cases import EXTREME_KINDS, extreme_mat
 from tapstark_amd._lib import TsError
 
 pytestmark = pytest.mark.gpu
@@ -93,8 +94,17 @@ def same(a, b):
 # ------------------------------------------------------------------ dft / idft / coset forms
 @pytest.mark.parametrize("log_n,w", SHAPES, ids=SHAPE_IDS)
 def test_dft_batch_matches_oracle(ctx, dft, orc, log_n, w):
+    check_dft_batch(ctx, dft, orc, log_n, w, rand_mat(1000 + 64 * log_n + w, 1 << log_n, w))
+
+
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+@pytest.mark.parametrize("log_n,w", [(0, 1), (1, 3), (2, 3), (5, 33)], ids=["2^0x1", "2^1x3", "2^2x3", "2^5x33"])
+def test_dft_batch_extreme_matrices(ctx, dft, orc, log_n, w, kind):
+    check_dft_batch(ctx, dft, orc, log_n, w, extreme_mat(kind, 1 << log_n, w))
+
+
+def check_dft_batch(ctx, dft, orc, log_n, w, x):
     n = 1 << log_n
-    x = rand_mat(1000 + 64 * log_n + w, n, w)
     dm = ts.DeviceMatrix.upload(ctx, x)
 
     def unchanged():

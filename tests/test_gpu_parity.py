@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import tapstark_amd as ts
+from _field_cases import EXTREME_KINDS, extreme_mat
 from tapstark_amd.airs import (FibonacciAir, SynthExtAir, SynthMulAir, fibonacci_public_values,
                                generate_fibonacci_trace, generate_synth_ext_trace,
                                generate_synth_mul_trace, splitmix64_stream)
@@ -52,8 +53,17 @@ def test_commit_lde_and_merkle(ctx, orc, log_n, w, log_blowup):
         # The same LDE plans (2^24, 2^25, 2^26 rows) are covered end to end by the whole-proof digests of
         # fib_2p24_b2 / fib_2p25_b1 / fib_2p26_b1 in test_gpu_golden_large.py, which cost a second each.
         pytest.skip("2^24+ rows against every oracle digest level: TS_BIG_TESTS=1")
+    check_commit_lde_and_merkle(ctx, orc, log_n, w, log_blowup, rand_mat(17 + log_n, 1 << log_n, w))
+
+
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+@pytest.mark.parametrize("log_n,w,log_blowup", [(0, 1, 1), (1, 2, 2), (3, 2, 2), (5, 7, 1)])
+def test_commit_lde_and_merkle_extreme_matrices(ctx, orc, log_n, w, log_blowup, kind):
+    check_commit_lde_and_merkle(ctx, orc, log_n, w, log_blowup, extreme_mat(kind, 1 << log_n, w))
+
+
+def check_commit_lde_and_merkle(ctx, orc, log_n, w, log_blowup, m):
     pcs = ts.TwoAdicFriPcs(ts.FriConfig(log_blowup, 4, 8), ctx)
-    m = rand_mat(17 + log_n, 1 << log_n, w)
     # a second, non-trivial domain shift where the field has one and the case is not a big one (the
     # 2^24+ cases take tens of seconds of oracle hashing each)
     for shift in ((1, 31 * pow(0x1A427A41, 1 << (27 - (log_n + 1)), P) % P) if log_n < 24 else (1,)):
@@ -132,22 +142,41 @@ def test_quotient_chunks(ctx, orc, monkeypatch, name, make, has_pis, log_n, jit)
 # ------------------------------------------------------------------ open / reduce
 @pytest.mark.parametrize("log_n,w,qd", [(3, 2, 1), (6, 5, 2), (10, 64, 2), (13, 9, 4)])
 def test_open_reduce(ctx, orc, log_n, w, qd):
-    b = 2
-    pcs = ts.TwoAdicFriPcs(ts.FriConfig(b, 4, 8), ctx)
     trace = rand_mat(60, 1 << log_n, w)
     chunks = [rand_mat(61 + c, 1 << log_n, 4) for c in range(qd)]
+    check_open_reduce(ctx, orc, log_n, w, qd, trace, chunks, [(rand_mat(70, 1, 4)[0], rand_mat(71, 1, 4)[0])])
+
+
+PM1_EXT = np.full(4, P - 1, dtype=np.uint32)
+# (zeta, alpha): zeta is never in the base field (the oracle divides by zeta - x)
+EXTREME_OPEN_CHALLENGES = [(PM1_EXT, PM1_EXT)] + [(rand_mat(70, 1, 4)[0], np.array([a, 0, 0, 0], dtype=np.uint32))
+                                                  for a in (0, 1, P - 1)]
+
+
+# (10, 64, 2): the tile path of k_open, whose lazy_mac loop then sees x = p - 1 in every product
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+@pytest.mark.parametrize("log_n,w,qd", [(3, 2, 1), (10, 64, 2)])
+def test_open_reduce_extreme_matrices_and_challenges(ctx, orc, log_n, w, qd, kind):
+    trace = extreme_mat(kind, 1 << log_n, w)
+    chunks = [extreme_mat(kind, 1 << log_n, 4) for c in range(qd)]
+    check_open_reduce(ctx, orc, log_n, w, qd, trace, chunks, EXTREME_OPEN_CHALLENGES)
+
+
+def check_open_reduce(ctx, orc, log_n, w, qd, trace, chunks, challenges):
+    b = 2
+    pcs = ts.TwoAdicFriPcs(ts.FriConfig(b, 4, 8), ctx)
     lqd = qd.bit_length() - 1
     g = pow(0x1A427A41, 1 << (27 - (log_n + lqd)), P) if log_n + lqd else 1
     shifts = [31 * pow(g, c, P) % P for c in range(qd)]
     _, tdata = pcs.commit([((log_n, 1), trace.copy())])
     _, qdata = pcs.commit([((log_n, s), m.copy()) for s, m in zip(shifts, chunks)])
-    zeta, alpha = rand_mat(70, 1, 4)[0], rand_mat(71, 1, 4)[0]
-    opened, ro = pcs.open_reduce(tdata, qdata, w, zeta, alpha)
     tl = orc.commit_lde(trace, 1, b)
     cl = [orc.commit_lde(m, s, b) for s, m in zip(shifts, chunks)]
-    want_opened, want_ro = orc.open_reduce(tl, cl, log_n, b, zeta, alpha)
-    assert (opened == want_opened).all(), "opened values differ"
-    assert (ro == want_ro).all(), f"reduced openings differ in {int((ro != want_ro).any(axis=1).sum())} rows"
+    for zeta, alpha in challenges:
+        opened, ro = pcs.open_reduce(tdata, qdata, w, zeta, alpha)
+        want_opened, want_ro = orc.open_reduce(tl, cl, log_n, b, zeta, alpha)
+        assert (opened == want_opened).all(), "opened values differ"
+        assert (ro == want_ro).all(), f"reduced openings differ in {int((ro != want_ro).any(axis=1).sum())} rows"
 
 
 # ------------------------------------------------------------------ FRI fold
@@ -157,6 +186,15 @@ def test_fri_fold(ctx, orc, log_h):
     vec = rand_mat(80 + log_h, 2 << log_h, 4)
     beta = rand_mat(81, 1, 4)[0]
     assert (pcs.fold_matrix(vec, beta) == orc.fold_matrix(vec, beta)).all()
+
+
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+@pytest.mark.parametrize("log_h", [0, 1, 4])
+def test_fri_fold_extreme_matrices_and_challenges(ctx, orc, log_h, kind):
+    pcs = ts.TwoAdicFriPcs(ts.FriConfig(1, 4, 8), ctx)
+    vec = extreme_mat(kind, 2 << log_h, 4)
+    for beta in (PM1_EXT, np.zeros(4, dtype=np.uint32), rand_mat(81, 1, 4)[0]):
+        assert (pcs.fold_matrix(vec, beta) == orc.fold_matrix(vec, beta)).all()
 
 
 # ------------------------------------------------------------------ whole proofs
