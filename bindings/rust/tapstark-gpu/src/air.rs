@@ -24,6 +24,7 @@ const OP_ADD: u32 = 6;
 const OP_SUB: u32 = 7;
 const OP_NEG: u32 = 8;
 const OP_MUL: u32 = 9;
+const OP_PREP: u32 = 10; // version-2 tapes: Entry::Preprocessed { offset } (symbolic_variable.rs:9-15)
 
 struct TapeBuilder<F: Field> {
     nodes: Vec<[u32; 3]>,
@@ -58,8 +59,10 @@ impl<F: PrimeField32> TapeBuilder<F> {
             SymbolicExpression::Variable(v) => match v.entry {
                 Entry::Main { offset } => self.leaf([OP_MAIN, offset as u32, v.index as u32]),
                 Entry::Public => self.leaf([OP_PUBLIC, v.index as u32, 0]),
-                // the hot path has no preprocessed / permutation / challenge columns
-                // (uni-stark/src/prover.rs:46 passes preprocessed_width = 0)
+                // a preprocessed (fixed) column: proved against a commit-once key with `ts_prove_pre`
+                // (uni-stark/src/prover.rs:46 itself passes preprocessed_width = 0)
+                Entry::Preprocessed { offset } => self.leaf([OP_PREP, offset as u32, v.index as u32]),
+                // no permutation / challenge columns on the hot path
                 other => panic!("unsupported symbolic variable on the prover hot path: {other:?}"),
             },
             SymbolicExpression::IsFirstRow => self.leaf([OP_IS_FIRST_ROW, 0, 0]),
@@ -94,18 +97,33 @@ where
     F: PrimeField32,
     A: Air<SymbolicAirBuilder<F>>,
 {
-    let constraints: Vec<SymbolicExpression<F>> = get_symbolic_constraints(air, 0, num_public_values);
+    serialize_constraints_pre(air, 0, num_public_values)
+}
+
+/// The same for an AIR that reads `preprocessed_width` preprocessed columns through
+/// `PairBuilder::preprocessed()` (symbolic_builder.rs:144-148): a version-2 tape (one more header word, the
+/// leaf `OP_PREP`), to be proved with `ts_prove_pre` against the committed key.  Width 0 gives the version-1
+/// tape, word for word what `serialize_constraints` always gave.
+pub fn serialize_constraints_pre<F, A>(air: &A, preprocessed_width: usize, num_public_values: usize) -> Vec<u32>
+where
+    F: PrimeField32,
+    A: Air<SymbolicAirBuilder<F>>,
+{
+    let constraints: Vec<SymbolicExpression<F>> = get_symbolic_constraints(air, preprocessed_width, num_public_values);
     let mut tb = TapeBuilder::<F> { nodes: Vec::new(), by_ptr: HashMap::new(), by_leaf: HashMap::new() };
     let roots: Vec<u32> = constraints.iter().map(|c| tb.expr(c)).collect();
-    let mut tape = Vec::with_capacity(6 + 3 * tb.nodes.len() + roots.len());
+    let mut tape = Vec::with_capacity(7 + 3 * tb.nodes.len() + roots.len());
     tape.extend_from_slice(&[
         TAPE_MAGIC,
-        1,
+        if preprocessed_width == 0 { 1 } else { 2 },
         air.width() as u32,
         num_public_values as u32,
         tb.nodes.len() as u32,
         roots.len() as u32,
     ]);
+    if preprocessed_width != 0 {
+        tape.push(preprocessed_width as u32);
+    }
     for n in &tb.nodes {
         tape.extend_from_slice(n);
     }

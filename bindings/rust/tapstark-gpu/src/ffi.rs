@@ -146,6 +146,7 @@ extern "C" {
     pub fn ts_air_compile(ctx: *mut ts_ctx, tape: *const u32, n_words: usize, out: *mut *mut ts_air) -> ts_status;
     pub fn ts_air_info(air: *const ts_air, width: *mut u32, n_public: *mut u32, max_degree: *mut u32,
                        log_quotient_degree: *mut u32) -> ts_status;
+    pub fn ts_air_preprocessed_width(air: *const ts_air, preprocessed_width: *mut u32) -> ts_status;
     pub fn ts_air_free(ctx: *mut ts_ctx, air: *mut ts_air);
     pub fn ts_air_is_jit(air: *const ts_air) -> c_int;
     pub fn ts_air_jit_wait(ctx: *mut ts_ctx, air: *mut ts_air, state: *mut c_int, compile_seconds: *mut f64) -> ts_status;
@@ -196,6 +197,21 @@ extern "C" {
     pub fn ts_verify(cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
                      proof: *const u32, n_words: usize, public_values: *const u32, n_public: u32,
                      verdict: *mut c_int) -> ts_status;
+    // AIRs with preprocessed columns, proved against a commit-once key (include/tapstark.h "preprocessed
+    // columns"): `preprocessed` is the ts_pcs_data of ts_pcs_commit over the one preprocessed matrix, never
+    // consumed; null (key, root, matrix) exactly for an AIR with preprocessed_width 0
+    pub fn ts_quotient_chunks_pre(ctx: *mut ts_ctx, preprocessed: *const ts_pcs_data, trace_data: *const ts_pcs_data,
+                                  log_blowup: u32, air: *const ts_air, public_values: *const u32, n_public: u32,
+                                  alpha: *const u32, chunks_out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_prove_pre(ctx: *mut ts_ctx, cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
+                        preprocessed: *const ts_pcs_data, trace: *mut ts_matrix, public_values: *const u32,
+                        n_public: u32, proof_out: *mut u32, cap_words: usize, n_words_out: *mut usize) -> ts_status;
+    pub fn ts_verify_pre(cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
+                         preprocessed_root: *const u32, proof: *const u32, n_words: usize,
+                         public_values: *const u32, n_public: u32, verdict: *mut c_int) -> ts_status;
+    pub fn ts_check_constraints_pre(ctx: *mut ts_ctx, air: *const ts_air, preprocessed: *const ts_matrix,
+                                    trace: *const ts_matrix, public_values: *const u32, n_public: u32,
+                                    first_violation: *mut i64) -> ts_status;
     pub fn ts_proof_to_postcard(proof: *const u32, n_words: usize, out: *mut u8, cap_bytes: usize,
                                 n_bytes_out: *mut usize) -> ts_status;
     /// tspf_version: 0 infer, 1 / 2 explicit (a taptree proof with one query needs 2)

@@ -201,12 +201,24 @@ ts_status ts_matrix_bit_reverse_rows(ts_ctx* ctx, const ts_matrix* in, ts_matrix
  *   n_nodes x {op,a,b}, n_constraints node ids in assert_zero order.
  * ops (symbolic_expression.rs:12-37): 0 CONST(a=value) 1 MAIN(a=offset 0|1,b=column)
  *   2 PUBLIC(a=index) 3 IS_FIRST_ROW 4 IS_LAST_ROW 5 IS_TRANSITION 6 ADD(a,b) 7 SUB(a,b) 8 NEG(a)
- *   9 MUL(a,b) */
+ *   9 MUL(a,b)
+ * Version 2, for an AIR with preprocessed (fixed) columns -- the PairBuilder::preprocessed() of
+ * uni-stark/src/symbolic_builder.rs:68-99,144-148 and Entry::Preprocessed { offset } of
+ * symbolic_variable.rs:9-15,34-39 (degree multiple 1, like a main variable):
+ *   [0]=0x54415354 [1]=2 [2]=width [3]=n_public [4]=n_nodes [5]=n_constraints [6]=preprocessed_width,
+ *   then nodes and constraints as in version 1, with one more op:
+ *   10 PREP(a=offset 0|1, b=column < preprocessed_width).
+ * Version 1 is accepted and lowered exactly as before; a version-2 tape with preprocessed_width 0 behaves in
+ * every call as the version-1 tape with the same nodes.  TS_ERR_INVALID: PREP in a version-1 tape, a column >=
+ * preprocessed_width, an offset > 1, a word count that does not match the header, width 0. */
 /* ctx == NULL builds a host-only AIR (degree rules + verifier use; no kernels) */
 ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out);
 /* get_log_quotient_degree, uni-stark/src/symbolic_builder.rs:15-32 */
 ts_status ts_air_info(const ts_air* air, uint32_t* width, uint32_t* n_public,
                       uint32_t* max_constraint_degree, uint32_t* log_quotient_degree);
+/* the preprocessed_width that get_log_quotient_degree / get_symbolic_constraints take
+ * (symbolic_builder.rs:15-21,52-58): 0 for a version-1 tape */
+ts_status ts_air_preprocessed_width(const ts_air* air, uint32_t* preprocessed_width);
 /* 1 if the quotient kernel was specialised for this AIR with hiprtc, 0 if the generic on-device
  * interpreter is used (hiprtc missing, TS_NO_JIT set in the environment, the program is above the
  * compile budget, or a background compilation has not finished yet).
@@ -230,7 +242,8 @@ void ts_air_free(ts_ctx* ctx, ts_air* air);
  * straight-line HIP source compiled with hiprtc (csrc/jit.cpp); tests interpret the former and
  * compile the latter against the oracle's direct evaluation of the tape.
  * ts_air_program: out = [n_regs, n_instr, n_consts, n_instr x {op,dst,a,b}, n_consts x canonical
- *   value, n_consts x (public-value index or 0xffffffff)]; ops: 0 LOAD(a=row offset,b=column)
+ *   value, n_consts x (public-value index or 0xffffffff)]; ops: 0 LOAD(a=row offset + 2 * preprocessed,
+ *   b=column): a = 0 / 1 the main trace's local / next row, a = 2 / 3 the preprocessed matrix's (version-2 tapes)
  *   1 CONST(a=const index) 2 SEL(a=0 first|1 last|2 transition) 3 ADD 4 SUB 5 NEG 6 MUL
  *   7 ASSERT(a=register, b=constraint index).  TS_ERR_BUFFER (with *n_words set) if cap is short.
  * ts_air_jit_source: the HIP source (not NUL-terminated; *n_bytes set even on TS_ERR_BUFFER).
@@ -551,6 +564,49 @@ ts_status ts_prove_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_comm*
 ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* trace,
                                const uint32_t* public_values, uint32_t n_public,
                                int64_t* first_violation);
+
+/* The same for an AIR with preprocessed columns (check_constraints.rs:11-39 with the PairBuilder's second
+ * matrix): `preprocessed` is the uploaded height x preprocessed_width matrix, NOT consumed; NULL exactly for an
+ * AIR with preprocessed_width == 0, where the answer is ts_check_constraints'. */
+ts_status ts_check_constraints_pre(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
+                                   const ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
+                                   int64_t* first_violation);
+
+/* ------------------------------------------------------------------ preprocessed columns */
+/* An AIR with preprocessed columns (tape version 2) is proved against a KEY: the ordinary ts_pcs_data of
+ *   ts_pcs_commit(ctx, cfg, 1, {the height x preprocessed_width matrix}, {1}, root, &key)
+ * made once, never consumed, reusable by any number of proofs on its context; the verifier holds `root`.
+ * The reference's AIR language has such columns but its prove / verify pass preprocessed_width 0
+ * (uni-stark/src/prover.rs:46, verifier.rs:40), so the transcript is build-defined (DESIGN.md "Preprocessed
+ * columns"): observe(key root); commit + observe the trace; alpha; quotient over (key LDE, trace LDE); commit +
+ * observe the chunks; zeta; Pcs::open of three rounds -- key at {zeta, zeta w_n}, trace at {zeta, zeta w_n},
+ * chunks at {zeta} -- with the round order and num_reduced offsets of ts_pcs_open for that argument list
+ * (fri/src/two_adic_pcs.rs:371,383).  Proof: TSPF v3.
+ *
+ * ts_quotient_chunks_pre extends ts_quotient_chunks (prover.rs:122-194), ts_prove_pre extends ts_prove
+ * (prover.rs:25-119; `trace` consumed as there), ts_verify_pre extends ts_verify (verifier.rs:19-161; host only,
+ * verdict codes as ts_verify).
+ * TS_ERR_INVALID, with text in ts_last_error and before any device work (the trace is then treated as ts_prove
+ * treats its trace on that status): a null argument; a key that does not hold exactly one matrix, whose width is
+ * not the AIR's preprocessed_width, whose LDE height is not trace height << log_blowup, or that was made on
+ * another context; for ts_verify_pre a proof whose header version is not 3 (*verdict = 9) or whose
+ * preprocessed_width word is not the AIR's (*verdict = 1).
+ * For an AIR with preprocessed_width == 0 the key / root / matrix argument must be NULL and every call gives what
+ * its unsuffixed counterpart gives (the proof differs in its v3 header alone).
+ * The calls that take no key -- ts_prove, ts_quotient_chunks, ts_check_constraints, ts_verify, ts_prove_stream,
+ * ts_prove_batch (in the item's status), ts_prove_sharded, ts_prove_tap, ts_prove_tap_sharded, ts_verify_tap --
+ * return TS_ERR_UNSUPPORTED for an AIR with preprocessed_width > 0, and ts_proof_to_postcard does for a v3
+ * proof (the reference's OpenedValues, uni-stark/src/proof.rs, has no preprocessed fields). */
+ts_status ts_quotient_chunks_pre(ts_ctx* ctx, const ts_pcs_data* preprocessed, const ts_pcs_data* trace_data,
+                                 uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
+                                 uint32_t n_public, const uint32_t alpha[4], ts_matrix** chunks_out);
+ts_status ts_prove_pre(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                       const ts_pcs_data* preprocessed /* not consumed */, ts_matrix* trace /* consumed */,
+                       const uint32_t* public_values, uint32_t n_public, uint32_t* proof_out, size_t cap_words,
+                       size_t* n_words_out);
+ts_status ts_verify_pre(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                        const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
+                        const uint32_t* public_values, uint32_t n_public, int* verdict);
 
 /* ------------------------------------------------------------------ verify (host only) */
 /* uni_stark::verify (uni-stark/src/verifier.rs:19-25; pcs.verify fri/src/two_adic_pcs.rs:421-534;

@@ -23,7 +23,8 @@ namespace air {
 constexpr uint32_t P = 0x78000001u;  // basic/src/field/mod.rs:45
 constexpr uint32_t TAPE_MAGIC = 0x54415354u;
 enum Op : uint32_t { CONST = 0, MAIN = 1, PUBLIC = 2, IS_FIRST = 3, IS_LAST = 4, IS_TRANSITION = 5,
-                     ADD = 6, SUB = 7, NEG = 8, MUL = 9 };
+                     ADD = 6, SUB = 7, NEG = 8, MUL = 9,
+                     PREP = 10 };  // version-2 tapes: Entry::Preprocessed { offset }, symbolic_variable.rs:9-15
 
 class Builder;
 
@@ -44,7 +45,12 @@ class Filtered;
 
 class Builder {
 public:
-    Builder(uint32_t width, uint32_t num_public_values) : width_(width), n_public_(num_public_values) {
+    // preprocessed_width > 0: an AIR with preprocessed (fixed) columns, symbolic_builder.rs:68-99; its variables
+    // come first, as there, and the tape is version 2
+    Builder(uint32_t width, uint32_t num_public_values, uint32_t preprocessed_width = 0)
+        : width_(width), n_public_(num_public_values), prep_width_(preprocessed_width) {
+        for (uint32_t off = 0; off < 2; off++)
+            for (uint32_t c = 0; c < preprocessed_width; c++) prep_[off].push_back(node(PREP, off, c, 1));
         for (uint32_t off = 0; off < 2; off++)
             for (uint32_t c = 0; c < width; c++) rows_[off].push_back(node(MAIN, off, c, 1));
         for (uint32_t i = 0; i < num_public_values; i++) public_.push_back(node(PUBLIC, i, 0, 0));
@@ -52,6 +58,8 @@ public:
     // builder.main().row_slice(0 | 1)
     const std::vector<Expr>& local() const { return rows_[0]; }
     const std::vector<Expr>& next() const { return rows_[1]; }
+    // PairBuilder::preprocessed().row_slice(offset), symbolic_builder.rs:144-148
+    const std::vector<Expr>& preprocessed(uint32_t offset) const { return prep_[offset & 1]; }
     const std::vector<Expr>& public_values() const { return public_; }
     Expr constant(uint64_t v) { return node(CONST, (uint32_t)(v % P), 0, 0); }
     Expr is_first_row() { return node(IS_FIRST, 0, 0, 1); }    // symbolic_expression.rs:45
@@ -77,10 +85,12 @@ public:
         while ((1u << k) < d - 1) k++;  // log2_ceil(d - 1)
         return k;
     }
-    // [magic, version, width, n_public, n_nodes, n_constraints, nodes (op, a, b)..., constraint ids...]
+    // [magic, version, width, n_public, n_nodes, n_constraints, nodes (op, a, b)..., constraint ids...];
+    // version 2 (preprocessed_width > 0) has the preprocessed width as a seventh header word
     std::vector<uint32_t> tape() const {
-        std::vector<uint32_t> t = {TAPE_MAGIC, 1, width_, n_public_, (uint32_t)nodes_.size(),
+        std::vector<uint32_t> t = {TAPE_MAGIC, prep_width_ ? 2u : 1u, width_, n_public_, (uint32_t)nodes_.size(),
                                    (uint32_t)constraints_.size()};
+        if (prep_width_) t.push_back(prep_width_);
         for (auto& n : nodes_) {
             t.push_back(std::get<0>(n));
             t.push_back(std::get<1>(n));
@@ -103,12 +113,12 @@ public:
     uint32_t degree(Expr e) const { return degs_[e.id()]; }
 
 private:
-    uint32_t width_, n_public_;
+    uint32_t width_, n_public_, prep_width_;
     std::vector<std::tuple<uint32_t, uint32_t, uint32_t>> nodes_;
     std::vector<uint32_t> degs_;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> cse_;
     std::vector<uint32_t> constraints_;
-    std::vector<Expr> rows_[2], public_;
+    std::vector<Expr> rows_[2], prep_[2], public_;
 };
 
 // degree rules: symbolic_expression.rs:137 (add), :182 (sub), :227 (mul)

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "ts_quotient_chunks", "ts_pcs_open_reduce", "ts_pcs_open", "ts_pcs_verify", "ts_fri_prove", "ts_fri_verify", "ts_fri_fold", "ts_fri_fold_device", "ts_chal_new", "ts_chal_clone",
     "ts_chal_free", "ts_chal_observe", "ts_chal_observe_commitment", "ts_chal_sample",
     "ts_chal_sample_bits", "ts_chal_check_witness", "ts_chal_grind", "ts_chal_state", "ts_prove", "ts_prove_stream", "ts_prove_batch", "ts_prove_sharded", "ts_verify", "ts_check_constraints",
+    "ts_air_preprocessed_width", "ts_quotient_chunks_pre", "ts_prove_pre", "ts_verify_pre", "ts_check_constraints_pre",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -264,6 +265,16 @@ def lib() -> C.CDLL:
                                            C.POINTER(C.c_int64)]
         l.ts_verify.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, u32p, C.c_size_t, u32p,
                                 C.c_uint32, C.POINTER(C.c_int)]
+        # preprocessed columns (tape version 2): the key / root / matrix argument may be NULL (preprocessed_width 0)
+        l.ts_air_preprocessed_width.argtypes = [C.c_void_p, u32p]
+        l.ts_quotient_chunks_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, u32p,
+                                             C.c_uint32, u32p, voidpp]
+        l.ts_prove_pre.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   u32p, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
+        l.ts_verify_pre.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, u32p, u32p, C.c_size_t, u32p,
+                                    C.c_uint32, C.POINTER(C.c_int)]
+        l.ts_check_constraints_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32p, C.c_uint32,
+                                               C.POINTER(C.c_int64)]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

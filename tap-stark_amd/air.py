@@ -12,7 +12,9 @@ Host-side mirror of the reference's symbolic constraint capture, which is how an
 * ``FilteredAirBuilder`` (``when_first_row`` ...) -- p3-air semantics, SURVEY.md App. A.7
 
 The DAG is serialised into the "tape" the C ABI takes (``include/tapstark.h``, TS_OP_*):
-``[magic, version, width, n_public, n_nodes, n_constraints, nodes(op,a,b)..., constraint ids...]``.
+``[magic, version, width, n_public, n_nodes, n_constraints, nodes(op,a,b)..., constraint ids...]``;
+an AIR with preprocessed columns (``PairBuilder::preprocessed()``, symbolic_builder.rs:144-148) gives a
+version-2 tape: one more header word, ``preprocessed_width``, and the leaf ``OP_PREP(offset, column)``.
 Python is only the capture front-end; the tape is evaluated by HIP kernels.
 """
 from __future__ import annotations
@@ -24,6 +26,7 @@ P = 0x78000001  # reference basic/src/field/mod.rs:45
 TAPE_MAGIC = 0x54415354
 OP_CONST, OP_MAIN, OP_PUBLIC, OP_IS_FIRST, OP_IS_LAST, OP_IS_TRANSITION = 0, 1, 2, 3, 4, 5
 OP_ADD, OP_SUB, OP_NEG, OP_MUL = 6, 7, 8, 9
+OP_PREP = 10  # version-2 tapes: Entry::Preprocessed { offset }, symbolic_variable.rs:9-15
 
 
 class SymbolicExpression:
@@ -112,13 +115,22 @@ class FilteredAirBuilder:
 class SymbolicAirBuilder:
     """reference uni-stark/src/symbolic_builder.rs:68-148."""
 
-    def __init__(self, width: int, num_public_values: int):
+    def __init__(self, width: int, num_public_values: int, preprocessed_width: int = 0):
         self.width = width
         self.num_public_values = num_public_values
+        self.preprocessed_width = preprocessed_width
         self.nodes: list[tuple[int, int, int]] = []
         self._degs: list[int] = []
         self._cse: dict[tuple[int, int, int], int] = {}
         self.constraints: list[int] = []
+        # symbolic_builder.rs:79-99: the preprocessed variables first, then main, then the public values
+        # (no nodes at all for width 0: the tape of an AIR without such columns is what it always was)
+        self._preprocessed = _MainWindow(
+            [
+                _Row([self._node(OP_PREP, off, c, 1) for c in range(preprocessed_width)])
+                for off in (0, 1)
+            ]
+        )
         self._main = _MainWindow(
             [
                 _Row([self._node(OP_MAIN, off, c, 1) for c in range(width)])
@@ -147,6 +159,10 @@ class SymbolicAirBuilder:
     # -- AirBuilder surface (symbolic_builder.rs:110-139) -----------------------
     def main(self) -> _MainWindow:
         return self._main
+
+    def preprocessed(self) -> _MainWindow:
+        """PairBuilder::preprocessed (symbolic_builder.rs:144-148): two row slices, as ``main()``."""
+        return self._preprocessed
 
     def public_values(self):
         return self._public
@@ -193,6 +209,9 @@ class SymbolicAirBuilder:
     def tape(self) -> np.ndarray:
         words = [TAPE_MAGIC, 1, self.width, self.num_public_values, len(self.nodes),
                  len(self.constraints)]
+        if self.preprocessed_width:
+            words[1] = 2
+            words.append(self.preprocessed_width)
         for op, a, b in self.nodes:
             words += [op, a, b]
         words += self.constraints
@@ -209,26 +228,28 @@ class BaseAir:
         raise NotImplementedError
 
 
-def get_symbolic_constraints(air: BaseAir, num_public_values: int) -> SymbolicAirBuilder:
+def get_symbolic_constraints(air: BaseAir, num_public_values: int,
+                             preprocessed_width: int = 0) -> SymbolicAirBuilder:
     """reference uni-stark/src/symbolic_builder.rs:52-64 (returns the builder holding them)."""
-    b = SymbolicAirBuilder(air.width(), num_public_values)
+    b = SymbolicAirBuilder(air.width(), num_public_values, preprocessed_width)
     air.eval(b)
     return b
 
 
-def get_max_constraint_degree(air: BaseAir, num_public_values: int) -> int:
-    return get_symbolic_constraints(air, num_public_values).max_constraint_degree()
+def get_max_constraint_degree(air: BaseAir, num_public_values: int, preprocessed_width: int = 0) -> int:
+    return get_symbolic_constraints(air, num_public_values, preprocessed_width).max_constraint_degree()
 
 
 def log2_ceil(n: int) -> int:
     return max(0, (n - 1).bit_length())
 
 
-def get_log_quotient_degree(air: BaseAir, num_public_values: int) -> int:
-    """reference uni-stark/src/symbolic_builder.rs:15-32."""
-    d = max(get_max_constraint_degree(air, num_public_values), 2)
+def get_log_quotient_degree(air: BaseAir, num_public_values: int, preprocessed_width: int = 0) -> int:
+    """reference uni-stark/src/symbolic_builder.rs:15-32 (which takes the preprocessed width too)."""
+    d = max(get_max_constraint_degree(air, num_public_values, preprocessed_width), 2)
     return log2_ceil(d - 1)
 
 
-def air_tape(air: BaseAir, num_public_values: int) -> np.ndarray:
-    return get_symbolic_constraints(air, num_public_values).tape()
+def air_tape(air: BaseAir, num_public_values: int, preprocessed_width: int = 0) -> np.ndarray:
+    """Version 1 for preprocessed_width 0, version 2 otherwise."""
+    return get_symbolic_constraints(air, num_public_values, preprocessed_width).tape()

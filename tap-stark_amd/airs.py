@@ -212,6 +212,67 @@ def generate_synth_ext_trace(n: int, width: int = 163, seed: int = SPLITMIX_SEED
 # `Air::eval` body writes against the builder reaches the quotient evaluation through
 # get_symbolic_constraints (symbolic_builder.rs:52-64).  RandomAir is a seeded family of such
 # bodies for fuzzing the two constraint compilers (csrc/air.cpp, csrc/jit.cpp) and the verifier's
+# ---------------------------------------------------------------------------------------------
+# SelectorAir: a small hand-written AIR with preprocessed columns (BUILD-DEFINED; the reference's
+# AIR language has them -- symbolic_builder.rs:144-148 -- but none of its AIRs uses one).
+
+
+class SelectorAir(BaseAir):
+    """Preprocessed columns (sel, rc, spare), main columns (a, b, c); public values [a_0, c_last].
+
+    * ``sel (a b - c) + (1 - sel)(a + b + rc - c) = 0``: the row multiplies or adds, as the key says (degree 3)
+    * transition ``next.a = local.c``
+    * transition ``next.b = local.b + next.rc``: reads the preprocessed NEXT row
+    * first row ``a = pis[0]``, last row ``c = pis[1]``
+
+    ``spare`` is declared (committed in the key) and never referenced."""
+
+    PREPROCESSED_WIDTH = 3
+
+    def width(self) -> int:
+        return 3
+
+    def preprocessed_width(self) -> int:
+        return self.PREPROCESSED_WIDTH
+
+    def eval(self, builder) -> None:
+        prep, main = builder.preprocessed(), builder.main()
+        pis = builder.public_values()
+        pl, pn = prep.row_slice(0), prep.row_slice(1)
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        sel, rc = pl[0], pl[1]
+        a, b, c = local[0], local[1], local[2]
+        builder.assert_zero(sel * (a * b - c) + (1 - sel) * (a + b + rc - c))
+        when_transition = builder.when_transition()
+        when_transition.assert_eq(nxt[0], c)
+        when_transition.assert_eq(nxt[1], b + pn[1])
+        builder.when_first_row().assert_eq(a, pis[0])
+        builder.when_last_row().assert_eq(c, pis[1])
+
+
+def generate_selector_preprocessed(n: int, seed: int = SPLITMIX_SEED) -> np.ndarray:
+    """(n, 3) canonical u32: sel in {0, 1}, rc and spare arbitrary field elements."""
+    assert n & (n - 1) == 0
+    s = splitmix64_stream(seed, 3 * n).reshape(n, 3)
+    out = np.empty((n, 3), dtype=np.uint32)
+    out[:, 0] = (s[:, 0] >> np.uint64(7)) & np.uint64(1)
+    out[:, 1:] = s[:, 1:] % np.uint64(P)
+    return out
+
+
+def generate_selector_trace(preprocessed: np.ndarray, a0: int = 3, b0: int = 5):
+    """(trace (n, 3) u32, public values [a_0, c_last]) satisfying SelectorAir over ``preprocessed``."""
+    n = preprocessed.shape[0]
+    t = np.zeros((n, 3), dtype=np.uint32)
+    a, b = a0 % P, b0 % P
+    for i in range(n):
+        sel, rc = int(preprocessed[i, 0]), int(preprocessed[i, 1])
+        c = (a * b) % P if sel else (a + b + rc) % P
+        t[i] = (a, b, c)
+        a, b = c, (b + int(preprocessed[(i + 1) % n, 1])) % P
+    return t, np.array([t[0, 0], t[-1, 2]], dtype=np.uint32)
+
+
 # tape evaluation against the oracle: shared sub-terms, long live ranges, selectors inside and
 # outside products, public values in high-degree terms, edge constants.
 
@@ -283,8 +344,9 @@ class NumericBuilder:
     is_transition = (i != h-1), next row wrapping).  `constraints` collects one value vector per
     assert_zero, so a trace can be checked in numpy; RandomAir also writes defined columns through it."""
 
-    def __init__(self, trace: np.ndarray, public_values, define: bool = True):
+    def __init__(self, trace: np.ndarray, public_values, define: bool = True, preprocessed=None):
         self.trace = trace  # (n, w) uint64, canonical; with define=True RandomAir fills defined columns in
+        self.prep = preprocessed  # (n, P) canonical, or None: what preprocessed() reads
         self.define = define
         self.n = trace.shape[0]
         self.pis = [int(v) for v in public_values]
@@ -308,6 +370,23 @@ class NumericBuilder:
 
                     def __len__(self):
                         return b.trace.shape[1]
+
+                return _R()
+
+        return _W()
+
+    def preprocessed(self):
+        b = self
+
+        class _W:
+            def row_slice(self, off):
+                class _R:
+                    def __getitem__(self, c):
+                        col = b.prep[:, c].astype(np.uint64)
+                        return _NumExpr(b, np.roll(col, -1) if off else col, 1)
+
+                    def __len__(self):
+                        return b.prep.shape[1]
 
                 return _R()
 

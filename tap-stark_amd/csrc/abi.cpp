@@ -79,6 +79,31 @@ std::vector<uint32_t> public_inputs(const uint32_t* values, uint32_t n) {
     return pis;
 }
 
+// Calls that take no preprocessed key refuse an AIR that needs one, before anything is consumed or launched.
+void no_preprocessed(const ts_air* air, const char* call) {
+    if (air->a.prog().preprocessed_width == 0) return;
+    throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has preprocessed columns; prove it with "
+                                             "ts_prove_pre (and ts_quotient_chunks_pre, ts_check_constraints_pre, "
+                                             "ts_verify_pre)").c_str());
+}
+
+// The key of ts_*_pre calls: null exactly when the AIR has no preprocessed columns, else one committed matrix of
+// the AIR's preprocessed width, made on this context.  (Its height is checked against the trace's where both
+// are known: ts::check_preprocessed_key.)  Returns the PcsData or null.
+const ts::PcsData* preprocessed_key(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key) {
+    const uint32_t pw = air->a.prog().preprocessed_width;
+    TS_REQUIRE((key != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
+               pw ? "null preprocessed key for an AIR with preprocessed columns"
+                  : "a preprocessed key was given for an AIR without preprocessed columns");
+    if (!key) return nullptr;
+    TS_REQUIRE(key->d && key->d->ldes.size() == 1, ts::TS_ERR_INVALID,
+               "preprocessed key: exactly one committed matrix expected");
+    TS_REQUIRE(key->d->ldes[0].width == pw, ts::TS_ERR_INVALID,
+               "preprocessed key: width differs from the AIR's preprocessed width");
+    TS_REQUIRE(key->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "preprocessed key was made on another context");
+    return key->d.get();
+}
+
 // the trace is consumed, like the reference's moved RowMajorMatrix
 ts::DeviceMatrix take_trace(ts_matrix* trace) {
     TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
@@ -227,6 +252,9 @@ ts_status ts_proof_to_postcard(const uint32_t* proof, size_t n_words, uint8_t* o
     *n_bytes_out = 0;
     return guard(nullptr, [&] {
         std::vector<uint8_t> b;
+        // the reference's OpenedValues has no preprocessed fields (uni-stark/src/proof.rs): no postcard form of v3
+        TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 3), ts::TS_ERR_UNSUPPORTED,
+                   "TSPF v3 proofs (ts_prove_pre) have no postcard form");
         TS_REQUIRE(ts::tspf_to_postcard(proof, n_words, b), ts::TS_ERR_INVALID, "not a TSPF v1 proof");
         *n_bytes_out = b.size();
         TS_REQUIRE(b.size() <= cap_bytes, ts::TS_ERR_BUFFER, "postcard buffer too small");
@@ -674,6 +702,11 @@ ts_status ts_air_info(const ts_air* air, uint32_t* width, uint32_t* n_public,
     if (log_quotient_degree) *log_quotient_degree = air->a.prog().log_quotient_degree;
     return TS_OK;
 }
+ts_status ts_air_preprocessed_width(const ts_air* air, uint32_t* preprocessed_width) {
+    if (!air || !preprocessed_width) return TS_ERR_INVALID;
+    *preprocessed_width = air->a.prog().preprocessed_width;
+    return TS_OK;
+}
 void ts_air_free(ts_ctx* ctx, ts_air* air) {
     (void)ctx;
     delete air;
@@ -853,21 +886,35 @@ void ts_pcs_data_free(ts_ctx* ctx, ts_pcs_data* d) {
     delete d;
 }
 
-ts_status ts_quotient_chunks(ts_ctx* ctx, const ts_pcs_data* trace_data, uint32_t log_blowup,
-                             const ts_air* air, const uint32_t* public_values, uint32_t n_public,
-                             const uint32_t alpha[4], ts_matrix** chunks_out) {
+static ts_status quotient_chunks(ts_ctx* ctx, const ts_pcs_data* preprocessed, bool takes_key,
+                                 const ts_pcs_data* trace_data, uint32_t log_blowup, const ts_air* air,
+                                 const uint32_t* public_values, uint32_t n_public, const uint32_t alpha[4],
+                                 ts_matrix** chunks_out) {
     if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
     return guard(ctx, [&] {
+        if (!takes_key) no_preprocessed(air, "ts_quotient_chunks");
+        const ts::PcsData* key = takes_key ? preprocessed_key(ctx, air, preprocessed) : nullptr;
         ts_fri_config raw{log_blowup, 1, 0};
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));  // same [1, 8] bound as everywhere else
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        auto chunks = pcs.quotient_chunks(*trace_data->d, ready_prog(air), pis, load_ef(alpha));
+        auto chunks = pcs.quotient_chunks(*trace_data->d, ready_prog(air), pis, load_ef(alpha), key);
         for (size_t c = 0; c < chunks.size(); c++) {
             auto m = std::make_unique<ts_matrix>();
             m->m = std::move(chunks[c]);
             chunks_out[c] = m.release();
         }
     });
+}
+ts_status ts_quotient_chunks(ts_ctx* ctx, const ts_pcs_data* trace_data, uint32_t log_blowup,
+                             const ts_air* air, const uint32_t* public_values, uint32_t n_public,
+                             const uint32_t alpha[4], ts_matrix** chunks_out) {
+    return quotient_chunks(ctx, nullptr, false, trace_data, log_blowup, air, public_values, n_public, alpha, chunks_out);
+}
+ts_status ts_quotient_chunks_pre(ts_ctx* ctx, const ts_pcs_data* preprocessed, const ts_pcs_data* trace_data,
+                                 uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
+                                 uint32_t n_public, const uint32_t alpha[4], ts_matrix** chunks_out) {
+    return quotient_chunks(ctx, preprocessed, true, trace_data, log_blowup, air, public_values, n_public, alpha,
+                           chunks_out);
 }
 
 ts_status ts_pcs_open_reduce(ts_ctx* ctx, const ts_fri_config* cfg, const ts_pcs_data* trace_data,
@@ -1032,11 +1079,37 @@ ts_status ts_prove(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_
     if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
+        no_preprocessed(air, "ts_prove");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         ts::DeviceMatrix m = take_trace(trace);
         ts::StageTimer t(&ctx->ctx, "prove");
         copy_proof(ts::prove(pcs, ready_prog(air), chal->c, std::move(m), pis), proof_out, cap_words, n_words_out);
+    });
+}
+
+// prove over (preprocessed key, trace): the key is an ordinary ts_pcs_data, read and never consumed.  Every
+// refusal about the key is made before the trace is taken and before any device work.
+ts_status ts_prove_pre(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                       const ts_pcs_data* preprocessed, ts_matrix* trace, const uint32_t* public_values,
+                       uint32_t n_public, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) {
+        if (ctx) ctx->ctx.last_error = "ts_prove_pre: null argument";
+        return TS_ERR_INVALID;
+    }
+    *n_words_out = 0;
+    return guard(ctx, [&] {
+        const ts::PcsData* key = preprocessed_key(ctx, air, preprocessed);
+        const ts::FriConfig fri = load_cfg(cfg);
+        if (key)
+            TS_REQUIRE(trace->m.buf.p && key->ldes[0].height == trace->m.height << fri.log_blowup, ts::TS_ERR_INVALID,
+                       "preprocessed key: LDE height is not the trace height << log_blowup");
+        ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        ts::DeviceMatrix m = take_trace(trace);
+        ts::StageTimer t(&ctx->ctx, "prove");
+        copy_proof(ts::prove(pcs, ready_prog(air), chal->c, std::move(m), pis, key, 3), proof_out, cap_words,
+                   n_words_out);
     });
 }
 
@@ -1059,6 +1132,10 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
     for (uint32_t i = 0; i < n_proofs; i++)
         if (!traces[i] || lane_of[i] >= n_lanes) return TS_ERR_INVALID;
     if (n_public && !public_values) return TS_ERR_INVALID;
+    for (uint32_t l = 0; l < n_lanes; l++) {
+        const ts_status st = guard(ctxs[l], [&] { no_preprocessed(airs[l], "ts_prove_stream"); }, false);
+        if (st != TS_OK) return st;
+    }
     const std::vector<uint32_t> pis(public_values, public_values + n_public);
     StartGate gate(gate_ms);
     std::vector<ts_status> status(n_lanes, TS_OK);
@@ -1141,6 +1218,7 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
             ts_batch_item& it = items[i];
             if (it.lane != l || it.status != -1) continue;
             it.status = guard(ctx, [&] {
+                no_preprocessed(air, "ts_prove_batch");
                 const ts::AirProgram& prog = ready_prog(air);
                 TS_REQUIRE((it.trace != nullptr) != (it.host_trace != nullptr), ts::TS_ERR_INVALID,
                            "prove_batch: exactly one of trace / host_trace must be set");
@@ -1211,6 +1289,7 @@ ts_status ts_prove_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_comm*
         return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
+        no_preprocessed(air, "ts_prove_sharded");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts_comm cb = *comm;
@@ -1243,6 +1322,7 @@ ts_status ts_prove_tap(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
         return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
+        no_preprocessed(air, "ts_prove_tap");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
@@ -1262,6 +1342,7 @@ ts_status ts_prove_tap_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_c
         return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
+        no_preprocessed(air, "ts_prove_tap_sharded");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
@@ -1283,6 +1364,7 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
     if (!air || !chal || !proof || !verdict || !lock_scripts || !lock_offsets) return TS_ERR_INVALID;
     *verdict = -1;
     return guard(nullptr, [&] {
+        no_preprocessed(air, "ts_verify_tap");
         ts::FriConfig f = load_cfg(cfg);
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         for (size_t i = 0; i < n_scripts; i++)
@@ -1293,16 +1375,26 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
 }
 
 // ------------------------------------------------------------------ check_constraints
-ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* trace,
-                               const uint32_t* public_values, uint32_t n_public,
-                               int64_t* first_violation) {
+static ts_status check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed, bool takes_prep,
+                                   const ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
+                                   int64_t* first_violation) {
     if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
     *first_violation = -1;
     return guard(ctx, [&] {
+        if (!takes_prep) no_preprocessed(air, "ts_check_constraints");
         const ts::AirProgram& p = air->a.prog();
         TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
                    "check_constraints: needs an uploaded (row-major, unconsumed) trace");
         TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
+        TS_REQUIRE((preprocessed != nullptr) == (p.preprocessed_width > 0), ts::TS_ERR_INVALID,
+                   "check_constraints: the preprocessed matrix is needed exactly by an AIR with preprocessed columns");
+        if (preprocessed)
+            TS_REQUIRE(preprocessed->m.buf.p && preprocessed->m.layout == ts::DeviceMatrix::ROW_MAJOR &&
+                           preprocessed->m.buf.ctx == &ctx->ctx && preprocessed->m.width == p.preprocessed_width &&
+                           preprocessed->m.height == trace->m.height,
+                       ts::TS_ERR_INVALID,
+                       "check_constraints: the preprocessed matrix must be uploaded on this context, row-major, of "
+                       "the AIR's preprocessed width and the trace's height");
         TS_REQUIRE(n_public == p.n_public, ts::TS_ERR_INVALID, "check_constraints: public value count");
         TS_REQUIRE(n_public == 0 || public_values, ts::TS_ERR_INVALID, "null public values");
         const std::vector<uint32_t> consts = ts::air_consts_mont(p, public_values, n_public);
@@ -1311,12 +1403,23 @@ ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* 
         TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice,
                               ctx->ctx.stream));
         TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
-        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p);
+        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p,
+                                     preprocessed ? preprocessed->m.buf.p : nullptr);
         unsigned long long v = 0;
         TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
         ctx->ctx.sync();
         *first_violation = v == ~0ull ? -1 : (int64_t)v;
     });
+}
+ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* trace,
+                               const uint32_t* public_values, uint32_t n_public,
+                               int64_t* first_violation) {
+    return check_constraints(ctx, air, nullptr, false, trace, public_values, n_public, first_violation);
+}
+ts_status ts_check_constraints_pre(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
+                                   const ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
+                                   int64_t* first_violation) {
+    return check_constraints(ctx, air, preprocessed, true, trace, public_values, n_public, first_violation);
 }
 
 // ------------------------------------------------------------------ verify
@@ -1326,8 +1429,35 @@ ts_status ts_verify(const ts_fri_config* cfg, const ts_air* air, ts_challenger* 
     if (!air || !chal || !proof || !verdict) return TS_ERR_INVALID;
     *verdict = -1;
     return guard(nullptr, [&] {
+        no_preprocessed(air, "ts_verify");
         ts::FriConfig f = load_cfg(cfg);
         *verdict = ts::verify(f, air->a.prog(), chal->c, proof, n_words, public_inputs(public_values, n_public));
+    });
+}
+
+// host only, like ts_verify.  A proof of another TSPF version (verdict 9) or with another preprocessed width in
+// its header (verdict 1) is refused as an argument, TS_ERR_INVALID, with the verdict set.
+ts_status ts_verify_pre(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                        const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
+                        const uint32_t* public_values, uint32_t n_public, int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_pre: null argument");
+        const uint32_t pw = air->a.prog().preprocessed_width;
+        TS_REQUIRE((preprocessed_root != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
+                   pw ? "ts_verify_pre: null preprocessed root for an AIR with preprocessed columns"
+                      : "ts_verify_pre: a preprocessed root was given for an AIR without preprocessed columns");
+        ts::FriConfig f = load_cfg(cfg);
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        if (n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != 3) {
+            *verdict = 9;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre: not a TSPF v3 proof");
+        }
+        if (n_words >= 6 && proof[0] == ts::TSPF_MAGIC && proof[5] != pw) {
+            *verdict = 1;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre: the proof's preprocessed width is not the AIR's");
+        }
+        *verdict = ts::verify_pre(f, air->a.prog(), chal->c, preprocessed_root, proof, n_words, pis);
     });
 }
 

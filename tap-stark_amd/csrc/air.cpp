@@ -11,18 +11,23 @@
 namespace ts {
 
 AirProgram compile_air(const uint32_t* tape, size_t n_words) {
-    TS_REQUIRE(tape && n_words >= 6 && tape[0] == TAPE_MAGIC && tape[1] == 1, TS_ERR_INVALID,
+    TS_REQUIRE(tape && n_words >= 6 && tape[0] == TAPE_MAGIC && (tape[1] == 1 || tape[1] == 2), TS_ERR_INVALID,
                "air tape: bad header");
+    // version 2 (symbolic_builder.rs:68-99 with a preprocessed_width): one more header word, one more leaf
+    const bool v2 = tape[1] == 2;
     AirProgram p;
+    p.tape_header = v2 ? 7 : 6;
+    TS_REQUIRE(n_words >= p.tape_header, TS_ERR_INVALID, "air tape: bad header");
     p.width = tape[2];
     p.n_public = tape[3];
     const uint32_t n_nodes = tape[4];
     p.n_constraints = tape[5];
-    TS_REQUIRE((size_t)6 + 3 * (size_t)n_nodes + p.n_constraints == n_words, TS_ERR_INVALID,
+    p.preprocessed_width = v2 ? tape[6] : 0;
+    TS_REQUIRE((size_t)p.tape_header + 3 * (size_t)n_nodes + p.n_constraints == n_words, TS_ERR_INVALID,
                "air tape: length does not match header");
     TS_REQUIRE(p.width >= 1, TS_ERR_INVALID, "air tape: zero width");
-    const uint32_t* nodes = tape + 6;
-    const uint32_t* cons = tape + 6 + 3 * (size_t)n_nodes;
+    const uint32_t* nodes = tape + p.tape_header;
+    const uint32_t* cons = nodes + 3 * (size_t)n_nodes;
 
     // validation + degree_multiple (symbolic_expression.rs:41-61)
     std::vector<uint32_t> deg(n_nodes);
@@ -35,6 +40,12 @@ AirProgram compile_air(const uint32_t* tape, size_t n_words) {
                 break;
             case T_MAIN:
                 TS_REQUIRE(a <= 1 && b < p.width, TS_ERR_INVALID, "air tape: bad main variable");
+                deg[i] = 1;
+                break;
+            case T_PREP:  // degree multiple 1, like MAIN (symbolic_variable.rs:34-39)
+                TS_REQUIRE(v2, TS_ERR_INVALID, "air tape: preprocessed variable in a version-1 tape");
+                TS_REQUIRE(a <= 1 && b < p.preprocessed_width, TS_ERR_INVALID,
+                           "air tape: bad preprocessed variable");
                 deg[i] = 1;
                 break;
             case T_PUBLIC:
@@ -164,6 +175,7 @@ AirProgram compile_air(const uint32_t* tape, size_t n_words) {
                 case T_CONST: emit(D_CONST, dst, add_const(a, ~0u), 0); break;
                 case T_PUBLIC: emit(D_CONST, dst, add_const(0, a), 0); break;
                 case T_MAIN: emit(D_LOAD, dst, a, b); break;
+                case T_PREP: emit(D_LOAD, dst, a + 2, b); break;
                 case T_IS_FIRST: emit(D_SEL, dst, 0, 0); break;
                 case T_IS_LAST: emit(D_SEL, dst, 1, 0); break;
                 case T_IS_TRANSITION: emit(D_SEL, dst, 2, 0); break;

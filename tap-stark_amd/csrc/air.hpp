@@ -18,12 +18,14 @@ namespace ts {
 constexpr uint32_t TAPE_MAGIC = 0x54415354u;
 enum TapeOp : uint32_t {
     T_CONST = 0, T_MAIN = 1, T_PUBLIC = 2, T_IS_FIRST = 3, T_IS_LAST = 4, T_IS_TRANSITION = 5,
-    T_ADD = 6, T_SUB = 7, T_NEG = 8, T_MUL = 9
+    T_ADD = 6, T_SUB = 7, T_NEG = 8, T_MUL = 9,
+    T_PREP = 10  // version-2 tapes only: a preprocessed column (symbolic_variable.rs:9-15 Entry::Preprocessed)
 };
 
 // device instruction: 4 x u32 {op, dst, a, b}.  Operands of ADD/SUB/MUL/NEG/ASSERT are register ids.
 enum DevOp : uint32_t {
-    D_LOAD = 0,     // dst <- to_mont(main[a = offset][b = column])
+    D_LOAD = 0,     // dst <- to_mont(rows[a][b = column]); a = row offset + 2 * (preprocessed): 0/1 main
+                    // local/next, 2/3 preprocessed local/next
     D_CONST = 1,    // dst <- consts[a]           (Montgomery; constants and public values)
     D_SEL = 2,      // dst <- selector a (0 first, 1 last, 2 transition)
     D_ADD = 3,
@@ -58,6 +60,7 @@ struct KernelSetRef {
 
 struct AirProgram {
     uint32_t width = 0;
+    uint32_t preprocessed_width = 0;        // version-2 tapes (0: the AIR reads the main trace only)
     uint32_t n_public = 0;
     uint32_t n_constraints = 0;
     uint32_t max_degree = 0;
@@ -67,6 +70,9 @@ struct AirProgram {
     std::vector<uint32_t> const_canonical;  // constants (canonical); publics are appended per proof
     std::vector<uint32_t> const_public_idx; // for entries that are public values: index, else ~0u
     std::vector<uint32_t> tape;             // the validated input (kept for the verifier side)
+    uint32_t tape_header = 6;               // words before the nodes: 6 (version 1) or 7 (version 2)
+    const uint32_t* tape_nodes() const { return tape.data() + tape_header; }
+    const uint32_t* tape_constraints() const { return tape_nodes() + 3 * (size_t)tape[4]; }
     // device copy of `code`, owned by the context that compiled it
     uint32_t* d_code = nullptr;
     // hiprtc-specialised quotient kernel(s) (jit.cpp); null => the interpreter in quotient.hip is used

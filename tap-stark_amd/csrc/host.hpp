@@ -112,12 +112,16 @@ public:
                                     const std::vector<uint32_t>& domain_shifts, bool build_tree = true);
 
     // two_adic_pcs.rs:247-258 + uni-stark prover.rs:122-194,78-80
+    // preprocessed: the committed key of a version-2 AIR's preprocessed columns (one matrix of the trace's
+    // height), null for any other AIR
     std::vector<DeviceMatrix> quotient_chunks(const PcsData& trace_data, const AirProgram& air,
-                                              const std::vector<uint32_t>& public_values, Ef alpha);
+                                              const std::vector<uint32_t>& public_values, Ef alpha,
+                                              const PcsData* preprocessed = nullptr);
 
     // two_adic_pcs.rs:312-389 for the prove() shape; returns the FRI input (N EF4, device)
+    // preprocessed != nullptr: a third round, opened FIRST and at the trace's two points, in the same pass
     DevBuf<Ef> open_reduce(const PcsData& trace_data, const PcsData& quotient_data, Ef zeta,
-                           Ef batch_alpha, std::vector<Ef>& opened_values);
+                           Ef batch_alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed = nullptr);
 
     // The same two steps on a slab of the LDE: global rows [row0, row0 + rows) = whole cosets
     // beta0, beta0+1, ... (bit-reversed coset order), as held by one rank of the sharded prover.
@@ -130,9 +134,11 @@ public:
     std::vector<DeviceMatrix> quotient_chunks_slab(const ColMat& lde_slab, unsigned log_n, const Slab& slab,
                                                    const AirProgram& air,
                                                    const std::vector<uint32_t>& public_values, Ef alpha,
-                                                   uint32_t domain_shift = GENERATOR);
+                                                   uint32_t domain_shift = GENERATOR,
+                                                   const ColMat* prep_lde = nullptr);
     DevBuf<Ef> open_reduce_slab(const PcsData& trace_data, const PcsData& quotient_data, unsigned log_N,
-                                const Slab& slab, Ef zeta, Ef batch_alpha, std::vector<Ef>& opened_values);
+                                const Slab& slab, Ef zeta, Ef batch_alpha, std::vector<Ef>& opened_values,
+                                const PcsData* preprocessed = nullptr);
 
     // two_adic_pcs.rs:260-419 for any rounds x matrices x points: samples the batch challenge,
     // computes the opened values ((round, matrix, point, column) order) and returns the FriProof
@@ -162,9 +168,13 @@ private:
 };
 
 // ------------------------------------------------------------------ prove
-// uni-stark/src/prover.rs:25-119.  Returns the proof in TSPF v1 words.
+// uni-stark/src/prover.rs:25-119.  Returns the proof in TSPF v1 words; with proof_version 3 in TSPF v3, over
+// (preprocessed key, trace) for an AIR with preprocessed columns (prover.cpp).
 std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                            DeviceMatrix trace, const std::vector<uint32_t>& public_values);
+                            DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                            const PcsData* preprocessed = nullptr, uint32_t proof_version = 1);
+// throws TS_ERR_INVALID unless `key` holds exactly one matrix of the AIR's preprocessed width and that LDE height
+void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height);
 
 // ------------------------------------------------------------------ prove, one proof over G GPUs
 // Collectives the sharded prover needs, supplied by the host (torch.distributed over RCCL in
@@ -233,6 +243,9 @@ bool tap_verify_words(const TapLocks& locks, size_t first, uint32_t n_evals, uin
 // 6 FinalPolyMismatch, 7 OodEvaluationMismatch, 8 folded evaluation mismatch, 9 malformed buffer.
 int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
            const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values);
+// the same for a TSPF v3 proof against the root of the preprocessed key (null for an AIR without such columns)
+int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
+               const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values);
 
 // Pcs::verify (fri/src/two_adic_pcs.rs:421-534) for any rounds x matrices x points; same codes.
 struct PcsMatClaim {

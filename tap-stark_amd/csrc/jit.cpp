@@ -93,12 +93,17 @@ struct KernelHead {
     const char* row_index;     // the statements that define the row r of this thread
 };
 
-void emit_head(std::ostream& s, const KernelHead& h) {
+// An AIR with preprocessed columns reads a second committed matrix: two more parameters right after row_end and
+// two more row pointers (row2, row3: D_LOAD's a = 2, 3).  Any other AIR's source has neither.
+const char* kPrepParams = ", const u32* __restrict__ prep, u64 prep_stride";
+const char* kPrepRows = "    const u32* __restrict__ row2 = prep + r;\n    const u32* __restrict__ row3 = prep + r_next;\n";
+
+void emit_head(std::ostream& s, const KernelHead& h, bool prep) {
     s << "extern \"C\" __global__ void __launch_bounds__(" << h.launch_bounds << ")\n" << h.name;
     s << R"SRC((const u32* __restrict__ lde, u64 col_stride, unsigned log_n, unsigned log_qd,
                const u32* __restrict__ C, const u32* __restrict__ AP, const u32* __restrict__ isf,
                const u32* __restrict__ isl, const u32* __restrict__ ist, QC qc, QO out,
-               u32 row_begin, u32 row_end)SRC" << h.extra_params << R"SRC() {
+               u32 row_begin, u32 row_end)SRC" << (prep ? kPrepParams : "") << h.extra_params << R"SRC() {
     const unsigned L = log_n + log_qd;
     const u32 total = 1u << L;
 )SRC" << h.row_index << R"SRC(    if (r >= row_end) return;
@@ -109,6 +114,7 @@ void emit_head(std::ostream& s, const KernelHead& h) {
     const u32* __restrict__ row1 = lde + r_next;
     const u32 sel0 = isf[r], sel1 = isl[r], sel2 = ist[r];
 )SRC";
+    if (prep) s << kPrepRows;
 }
 
 const char* kAccZero = "    u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;\n";
@@ -139,7 +145,8 @@ const Naming kValues{"    const u32 v", "v"};
 // a leaf (LOAD / CONST / SEL) as an expression: it has no register operands
 std::string leaf_expr(const uint32_t* ins) {
     const std::string a = std::to_string(ins[2]);
-    if (ins[0] == D_LOAD) return "to_mont(row" + a + "[" + std::to_string(ins[3]) + "ull * col_stride])";
+    if (ins[0] == D_LOAD)  // the row pointer is known here: rows 2, 3 are the preprocessed matrix with its own stride
+        return "to_mont(row" + a + "[" + std::to_string(ins[3]) + (ins[2] >= 2 ? "ull * prep_stride])" : "ull * col_stride])");
     return (ins[0] == D_CONST ? "C[" + a + "]" : "sel" + a);
 }
 
@@ -173,7 +180,8 @@ void emit_instr(std::ostream& s, const Naming& nm, const uint32_t* ins, uint32_t
 std::string jit_quotient_source(const AirProgram& air) {
     std::ostringstream s;
     s << kHelpers;
-    emit_head(s, {"256", "k_quotient_jit", "", "    const u32 r = row_begin + blockIdx.x * 256u + threadIdx.x;\n"});
+    emit_head(s, {"256", "k_quotient_jit", "", "    const u32 r = row_begin + blockIdx.x * 256u + threadIdx.x;\n"},
+              air.preprocessed_width > 0);
     s << kAccZero;
     for (uint32_t r = 0; r < air.n_regs; r++) s << "    u32 r" << r << " = 0;\n";
     uint32_t n_assert = 0;
@@ -196,7 +204,8 @@ static std::string seg_kernel(const AirProgram& air, const SegmentPlan& plan, ui
     std::ostringstream s;
     s << "\n";
     emit_head(s, {"256, 4", "k_quotient_seg" + std::to_string(k), ", u32* __restrict__ slab, u32 slab_rows",
-                  "    const u32 t = blockIdx.x * 256u + threadIdx.x;\n    const u32 r = row_begin + t;\n"});
+                  "    const u32 t = blockIdx.x * 256u + threadIdx.x;\n    const u32 r = row_begin + t;\n"},
+              air.preprocessed_width > 0);
     s << "    u32* __restrict__ S = slab + t;\n";
     auto sl = [&](uint32_t slot) { return "S[" + std::to_string(slot) + "ull * slab_rows]"; };
     if (k == 0) {

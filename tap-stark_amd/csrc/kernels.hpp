@@ -162,7 +162,11 @@ struct QuotOut {
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
                      const QuotOut& out, uint64_t row_begin = 0, uint64_t row_end = 0,
-                     uint32_t shift = GENERATOR);
+                     uint32_t shift = GENERATOR, const ColMat* prep_lde = nullptr);
+// prep_lde: the committed LDE of the preprocessed columns of a version-2 AIR (air.preprocessed_width > 0; null
+// otherwise), column-major and bit-reversed like the trace's and of its height, with its own base and stride.
+// Such an AIR runs k_quotient_pre (or specialised kernels with the two extra parameters); every other AIR
+// launches exactly what it did before.
 // sharded.cpp "local quotient": in place on the slab LDEs of the qd chunk matrices (4 columns each),
 // out[c] = sum_c' mix[c * qd + c'] * in[c'] per row and per column (mix: Montgomery form, device)
 void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, uint64_t rows, uint64_t col_stride,
@@ -172,7 +176,8 @@ void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, 
 // row * 2^16 + constraint index of the first violated constraint
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
-                              unsigned long long* d_violation);
+                              unsigned long long* d_violation, const uint32_t* prep_row_major = nullptr);
+// (prep_row_major: the n x preprocessed_width matrix of a version-2 AIR, null otherwise)
 
 // ---- open.hip --------------------------------------------------------------------------------
 // d[p][i] = x_i / (z_p - x_i) (Montgomery EF4) for the low coset 31*H_n in bit-reversed order,
@@ -183,12 +188,12 @@ void launch_bary_weights(Context& ctx, unsigned log_n, const Ef* points_mont, ui
                          Ef* out, uint32_t coset_gen = 0);
 // out[col][p] = sum_i m[col][i] * d[p][i]   (canonical EF4), i over the first n rows
 // `pending` != nullptr: the finishing pass (partial sums -> out) is left to launch_bary_finish, which takes
-// up to two pending products in one launch
+// up to `capacity` pending products in one launch (2; 3 for a proof with preprocessed columns)
 struct BaryPending {
-    DevBuf<uint32_t> partial[2];
-    uint32_t* out[2] = {nullptr, nullptr};
-    uint32_t n_blocks[2] = {0, 0}, n_words[2] = {0, 0};
-    uint32_t n = 0;
+    DevBuf<uint32_t> partial[3];
+    uint32_t* out[3] = {nullptr, nullptr, nullptr};
+    uint32_t n_blocks[3] = {0, 0, 0}, n_words[3] = {0, 0, 0};
+    uint32_t n = 0, capacity = 2;
 };
 void launch_bary_dots(Context& ctx, const ColMat& m, unsigned log_n, const Ef* weights,
                       uint32_t n_points, Ef* out, BaryPending* pending = nullptr);
@@ -221,7 +226,11 @@ struct FusedReduceArgs {
     uint64_t row0, rows;
 };
 void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
-                         const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro);
+                         const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro,
+                         const ColMat* prep = nullptr, const Ef* prep_off_mont = nullptr);
+// prep != nullptr (k_reduce_fused_pre): the preprocessed columns' LDE, opened at the same two points BEFORE the
+// trace with the offsets prep_off_mont[2]; args.off_t then start after them and args.k0 / k1 hold the
+// preprocessed constants too.  d_alpha_pows_mont covers max(trace width, prep width, 4) powers.
 
 // ---- fri.hip ---------------------------------------------------------------------------------
 // out[i] = fold(in[2i], in[2i+1]; beta) (reference two_adic_pcs.rs:116-147); h = output length.

@@ -158,14 +158,11 @@ struct BaryFinishJob {
     uint32_t* out;
     uint32_t n_blocks, n_words;
 };
-__global__ void __launch_bounds__(256)
-k_bary_finish(BaryFinishJob j0, BaryFinishJob j1, uint32_t g0) {
+// one workgroup's four output words of one job
+__device__ __forceinline__ void bary_finish_group(const uint32_t* __restrict__ partial, uint32_t* __restrict__ out,
+                                                  uint32_t n_blocks, uint32_t n_words, uint32_t group) {
     __shared__ uint32_t red[4][4];
-    const bool first = blockIdx.x < g0;
-    const uint32_t* __restrict__ partial = first ? j0.partial : j1.partial;
-    uint32_t* __restrict__ out = first ? j0.out : j1.out;
-    const uint32_t n_blocks = first ? j0.n_blocks : j1.n_blocks, n_words = first ? j0.n_words : j1.n_words;
-    const uint32_t j = (first ? blockIdx.x : blockIdx.x - g0) * 4 + (threadIdx.x & 3);
+    const uint32_t j = group * 4 + (threadIdx.x & 3);
     uint32_t v = 0;
     if (j < n_words) {
         // eight loads in flight (as one load and one add per trip every trip waited for its own load: with
@@ -190,17 +187,33 @@ k_bary_finish(BaryFinishJob j0, BaryFinishJob j1, uint32_t g0) {
         out[j] = add(add(red[0][threadIdx.x], red[1][threadIdx.x]),
                      add(red[2][threadIdx.x], red[3][threadIdx.x]));
 }
+__global__ void __launch_bounds__(256)
+k_bary_finish(BaryFinishJob j0, BaryFinishJob j1, uint32_t g0) {
+    const bool first = blockIdx.x < g0;
+    bary_finish_group(first ? j0.partial : j1.partial, first ? j0.out : j1.out, first ? j0.n_blocks : j1.n_blocks,
+                      first ? j0.n_words : j1.n_words, first ? blockIdx.x : blockIdx.x - g0);
+}
+// three jobs (preprocessed columns, trace, quotient chunks): workgroups g0 .. g0+g1-1 take job 1
+__global__ void __launch_bounds__(256)
+k_bary_finish3(BaryFinishJob j0, BaryFinishJob j1, BaryFinishJob j2, uint32_t g0, uint32_t g1) {
+    const BaryFinishJob j = blockIdx.x < g0 ? j0 : blockIdx.x < g0 + g1 ? j1 : j2;
+    bary_finish_group(j.partial, j.out, j.n_blocks, j.n_words,
+                      blockIdx.x < g0 ? blockIdx.x : blockIdx.x < g0 + g1 ? blockIdx.x - g0 : blockIdx.x - g0 - g1);
+}
 
-// the finishing pass of one or two launch_bary_dots(..., pending) calls
+// the finishing pass of the pending launch_bary_dots(..., pending) calls
 void launch_bary_finish(Context& ctx, BaryPending& pend) {
     if (pend.n == 0) return;
-    BaryFinishJob j[2] = {{nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}};
-    uint32_t g[2] = {0, 0};
+    BaryFinishJob j[3] = {{nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}};
+    uint32_t g[3] = {0, 0, 0};
     for (uint32_t i = 0; i < pend.n; i++) {
         j[i] = BaryFinishJob{pend.partial[i].p, pend.out[i], pend.n_blocks[i], pend.n_words[i]};
         g[i] = (pend.n_words[i] + 3) / 4;
     }
-    TS_LAUNCH(ctx, k_bary_finish, dim3(g[0] + g[1]), dim3(256), 0, j[0], j[1], g[0]);
+    if (pend.n == 3)
+        TS_LAUNCH(ctx, k_bary_finish3, dim3(g[0] + g[1] + g[2]), dim3(256), 0, j[0], j[1], j[2], g[0], g[1]);
+    else
+        TS_LAUNCH(ctx, k_bary_finish, dim3(g[0] + g[1]), dim3(256), 0, j[0], j[1], g[0]);
     TS_HIP(hipGetLastError());
     for (uint32_t i = 0; i < pend.n; i++) pend.partial[i].reset();
     pend.n = 0;
@@ -238,7 +251,7 @@ void launch_bary_dots(Context& ctx, const ColMat& m, unsigned log_n, const Ef* w
     TS_HIP(hipGetLastError());
     BaryPending own;
     BaryPending& pend = pending ? *pending : own;
-    if (pend.n == 2) launch_bary_finish(ctx, pend);
+    if (pend.n == pend.capacity) launch_bary_finish(ctx, pend);
     pend.partial[pend.n] = std::move(partial);
     pend.out[pend.n] = reinterpret_cast<uint32_t*>(out);
     pend.n_blocks[pend.n] = n_blocks;
@@ -414,8 +427,58 @@ k_reduce_fused(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32
     *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
 }
 
+// The same pass with a third committed matrix, the preprocessed columns of the key, opened at the same two
+// points BEFORE the trace: g0 += off_p0 S_p, g1 += off_p1 S_p, with S_p shared by its two openings exactly as
+// S_t is (the constants off_p rys_p are in k0, k1).  A kernel of its own, so that k_reduce_fused stays the code
+// it was: handing its by-value argument struct to a shared body cost it 20 VGPRs.
+struct PrepReduceArgs {
+    const uint32_t* prep;
+    uint64_t stride;
+    uint32_t width;
+    Ef off_p[2];  // alpha^0, alpha^P (Montgomery); the trace's offsets then start at alpha^(2P)
+};
+__global__ void __launch_bounds__(256)
+k_reduce_fused_pre(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width,
+               unsigned log_h, const uint32_t* __restrict__ W, uint32_t gen_mont,
+               const uint32_t* __restrict__ alpha_pows, FusedReduceArgs a, PrepReduceArgs pa,
+               Ef* __restrict__ ro) {
+    const uint64_t X = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // local row
+    if (X >= a.rows) return;
+    const Ef St = row_dot_alpha(trace, trace_stride, width, X, alpha_pows);
+    const uint32_t x = mont_mul(gen_mont, root_bitrev(W, log_h, a.row0 + X));
+    Ef inv_d[2];
+    inv_denoms<2>(x, a.z_mont, inv_d);
+    uint64_t acc[4] = {0, 0, 0, 0};
+    uint32_t c = 0;
+    for (; c + 2 <= a.n_chunks; c += 2) {
+        // two width-4 chunks = one full batch of eight columns (their weights are consecutive): eight
+        // loads in flight, 32 multiply-adds, 16 range fixes -- as two 4-column tails it cost twice that
+        uint32_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = a.chunk[c + (k >> 2)][(uint64_t)(k & 3) * a.chunk_stride + X];
+        const uint32_t* ap = a.chunk_w + 16 * c;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[j] = lazy_mac(acc[j], v[k], ap[4 * k + j]);
+            if (k & 1) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = lazy_fix(acc[j]);
+            }
+        }
+    }
+    for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
+    const Ef D{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
+    const Ef Sp = row_dot_alpha(pa.prep, pa.stride, pa.width, X, alpha_pows);
+    const Ef g0 = ef_sub(ef_add(ef_add(ef_mul(St, a.off_t[0]), ef_mul(Sp, pa.off_p[0])), D), a.k0);
+    const Ef g1 = ef_sub(ef_add(ef_mul(St, a.off_t[1]), ef_mul(Sp, pa.off_p[1])), a.k1);
+    const Ef r = ef_add(ef_mul(g0, inv_d[0]), ef_mul(g1, inv_d[1]));
+    *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
+}
+
 void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
-                         const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro) {
+                         const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro,
+                         const ColMat* prep, const Ef* prep_off_mont) {
     TS_REQUIRE(args.n_chunks <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_INVALID, "reduce_fused: too many chunks");
     ctx.ensure_twiddles(log_h == 0 ? 1 : log_h);
     FusedReduceArgs a = args;
@@ -424,6 +487,16 @@ void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
         a.rows = 1ull << log_h;
     }
     TS_REQUIRE(a.row0 + a.rows <= (1ull << log_h), TS_ERR_INVALID, "reduce_fused: row range");
+    if (prep) {
+        TS_REQUIRE(prep_off_mont && prep->d && a.row0 == 0 && prep->height == a.rows && prep->col_stride >= a.rows,
+                   TS_ERR_INVALID, "reduce_fused: preprocessed matrix shape");
+        const PrepReduceArgs pa{prep->d, prep->col_stride, prep->width, {prep_off_mont[0], prep_off_mont[1]}};
+        TS_LAUNCH(ctx, k_reduce_fused_pre, dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
+                  (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
+                  (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, pa, ro);
+        TS_HIP(hipGetLastError());
+        return;
+    }
     TS_LAUNCH(ctx, k_reduce_fused, dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
               (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
               (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, ro);

@@ -104,20 +104,33 @@ std::unique_ptr<PcsData> TwoAdicFriPcs::commit(std::vector<DeviceMatrix>& evals,
 }
 
 // ------------------------------------------------------------------ quotient
+void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height) {
+    TS_REQUIRE(key.ldes.size() == 1, TS_ERR_INVALID, "preprocessed key: exactly one committed matrix expected");
+    TS_REQUIRE(air.preprocessed_width > 0 && key.ldes[0].width == air.preprocessed_width, TS_ERR_INVALID,
+               "preprocessed key: width differs from the AIR's preprocessed width");
+    TS_REQUIRE(key.ldes[0].height == lde_height, TS_ERR_INVALID,
+               "preprocessed key: LDE height is not the trace height << log_blowup");
+}
+
 std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks(const PcsData& trace_data,
                                                          const AirProgram& air,
-                                                         const std::vector<uint32_t>& pis, Ef alpha) {
+                                                         const std::vector<uint32_t>& pis, Ef alpha,
+                                                         const PcsData* preprocessed) {
     TS_REQUIRE(trace_data.ldes.size() >= 1, TS_ERR_INVALID, "quotient: no trace matrix");
     TS_REQUIRE(trace_data.log_height >= fri_.log_blowup, TS_ERR_INVALID, "quotient: bad trace data");
+    if (preprocessed) check_preprocessed_key(*preprocessed, air, trace_data.ldes[0].height);
     return quotient_chunks_slab(trace_data.ldes[0], trace_data.log_height - fri_.log_blowup, Slab{}, air,
-                                pis, alpha);
+                                pis, alpha, GENERATOR, preprocessed ? &preprocessed->ldes[0] : nullptr);
 }
 
 std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_slab, unsigned log_n,
                                                               const Slab& slab, const AirProgram& air,
                                                               const std::vector<uint32_t>& pis, Ef alpha,
-                                                              uint32_t domain_shift) {
+                                                              uint32_t domain_shift, const ColMat* prep_lde) {
     StageTimer t(&ctx_, "compute quotient polynomial");
+    TS_REQUIRE((prep_lde != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
+               "quotient: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
+    TS_REQUIRE(!prep_lde || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: preprocessed columns on a slab");
     TS_REQUIRE(lde_slab.width == air.width, TS_ERR_INVALID, "quotient: trace width != AIR width");
     TS_REQUIRE(pis.size() == air.n_public, TS_ERR_INVALID, "quotient: wrong number of public values");
     const unsigned lqd = air.log_quotient_degree;
@@ -159,18 +172,18 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
         ColMat lde = lde_slab;
         lde.d = lde_slab.d - slab.row0;  // global row r of the slab's range lives at d[r]
         launch_quotient(ctx_, air, lde, log_n, lqd, d_consts.p, d_consts.p + n_consts, qo, row_begin, row_end,
-                        domain_shift);
+                        domain_shift, prep_lde);
     }
     return chunks;  // (the staged uploads live in the context's pinned arena: no sync needed)
 }
 
 // ------------------------------------------------------------------ open
 DevBuf<Ef> TwoAdicFriPcs::open_reduce(const PcsData& trace_data, const PcsData& quotient_data, Ef zeta,
-                                      Ef alpha, std::vector<Ef>& opened_values) {
+                                      Ef alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed) {
     TS_REQUIRE(trace_data.log_height == quotient_data.log_height, TS_ERR_INVALID,
                "open: trace and quotient LDE heights differ");
     return open_reduce_slab(trace_data, quotient_data, trace_data.log_height, Slab{}, zeta, alpha,
-                            opened_values);
+                            opened_values, preprocessed);
 }
 
 // `slab` (rows != 0): the two PcsData hold only global rows [row0, row0 + rows) of the LDEs, which
@@ -178,8 +191,15 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce(const PcsData& trace_data, const PcsData& 
 // coset -- any coset of the LDE determines the polynomials, so every rank gets the same values.
 DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsData& quotient_data,
                                            unsigned log_N, const Slab& slab, Ef zeta, Ef alpha,
-                                           std::vector<Ef>& opened_values) {
+                                           std::vector<Ef>& opened_values, const PcsData* preprocessed) {
     TS_REQUIRE(trace_data.ldes.size() == 1, TS_ERR_UNSUPPORTED, "open: one trace matrix expected");
+    // a preprocessed round (one matrix of the trace's height, whole LDE) is opened first, at the trace's points:
+    // its 2 pw values lead the opened values and its columns the num_reduced count (two_adic_pcs.rs:371,383)
+    TS_REQUIRE(!preprocessed || (slab.rows == 0 && preprocessed->ldes.size() == 1 &&
+                                 preprocessed->ldes[0].height == trace_data.ldes[0].height),
+               TS_ERR_INVALID, "open: preprocessed round shape");
+    const ColMat* pm = preprocessed ? &preprocessed->ldes[0] : nullptr;
+    const uint32_t pw = pm ? pm->width : 0;
     const unsigned log_n = log_N - fri_.log_blowup;
     const uint64_t n = 1ull << log_n;
     const uint64_t N = slab.rows ? slab.rows : 1ull << log_N;  // rows held here
@@ -199,14 +219,20 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
     const Ef pts_mont[2] = {ef_to_mont(zeta), ef_to_mont(zeta_next)};
 
     // ---- opened values: barycentric interpolation on the low coset (two_adic_pcs.rs:358-369)
-    std::vector<Ef> raw(2 * (size_t)w + 4 * (size_t)qd);
+    std::vector<Ef> raw_all(2 * (size_t)pw + 2 * (size_t)w + 4 * (size_t)qd);
+    Ef* const raw = raw_all.data() + 2 * (size_t)pw;  // [-2 pw, 0): the preprocessed sums, [col][point]
     {
         StageTimer t(&ctx_, "compute opened values with Lagrange interpolation");
         DevBuf<Ef> weights(&ctx_, 2 * n);
         launch_bary_weights(ctx_, log_n, pts_mont, 2, weights.p, coset_gen);
         // the last kernels of the stage write the sums straight into the context's mailbox (host memory)
-        struct { Ef* p; } sums{reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw.size()))};
+        Ef* const mail = reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw_all.size()));
+        struct { Ef* p; } sums{mail + 2 * (size_t)pw};
         BaryPending pend;  // the trace's partial sums and the chunks' are added up in one launch
+        if (pm) {          // and the preprocessed columns', in the same one
+            pend.capacity = 3;
+            launch_bary_dots(ctx_, *pm, log_n, weights.p, 2, mail, &pend);
+        }
         launch_bary_dots(ctx_, tr, log_n, weights.p, 2, sums.p, &pend);  // [col][point]
         ColMat all;  // lde_stage lays the chunk LDEs back to back (no width limit: the dot products take any)
         if (qd > 1 && columns_as_one_matrix(quotient_data.ldes, quotient_data.ldes[0].height, 0, all) &&
@@ -217,21 +243,26 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
                 launch_bary_dots(ctx_, quotient_data.ldes[c], log_n, weights.p, 1, sums.p + 2 * w + 4 * c, &pend);
         }
         launch_bary_finish(ctx_, pend);
-        ctx_.sync_point(sums.p, raw.size() * sizeof(Ef));
-        memcpy(raw.data(), sums.p, raw.size() * sizeof(Ef));
+        ctx_.sync_point(mail, raw_all.size() * sizeof(Ef));
+        memcpy(raw_all.data(), mail, raw_all.size() * sizeof(Ef));
     }
     // p(z) = ((z/s)^n - 1)/n * sum_i p_i x_i/(z - x_i) on the coset s*H_n (s = 31 unless sharded)
     const Ef scale[2] = {bary_scale(zeta, coset_gen, n), bary_scale(zeta_next, coset_gen, n)};
-    opened_values.assign(2 * (size_t)w + 4 * (size_t)qd, ef_zero());
-    for (uint32_t c = 0; c < w; c++) {
-        opened_values[c] = efc_mul(raw[2 * c], scale[0]);          // trace_local
-        opened_values[w + c] = efc_mul(raw[2 * c + 1], scale[1]);  // trace_next
+    opened_values.assign(raw_all.size(), ef_zero());
+    for (uint32_t c = 0; c < pw; c++) {
+        opened_values[c] = efc_mul(raw_all[2 * c], scale[0]);           // preprocessed_local
+        opened_values[pw + c] = efc_mul(raw_all[2 * c + 1], scale[1]);  // preprocessed_next
     }
-    for (uint32_t k = 0; k < 4 * qd; k++) opened_values[2 * w + k] = efc_mul(raw[2 * w + k], scale[0]);
+    Ef* const ov = opened_values.data() + 2 * (size_t)pw;  // the trace's and the chunks', as without a key
+    for (uint32_t c = 0; c < w; c++) {
+        ov[c] = efc_mul(raw[2 * c], scale[0]);          // trace_local
+        ov[w + c] = efc_mul(raw[2 * c + 1], scale[1]);  // trace_next
+    }
+    for (uint32_t k = 0; k < 4 * qd; k++) ov[2 * w + k] = efc_mul(raw[2 * w + k], scale[0]);
 
     // ---- reduce (two_adic_pcs.rs:371-383)
     StageTimer t(&ctx_, "reduce rows");
-    const uint32_t max_w = std::max(w, 4u);
+    const uint32_t max_w = std::max(std::max(w, pw), 4u);
     std::vector<uint32_t> apow = alpha_powers_mont(alpha, max_w);
     const Ef am = ef_to_mont(alpha);
     // (uploaded below, together with the chunk weights: one copy on the stream instead of two)
@@ -254,11 +285,17 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         a.z_mont[0] = pts_mont[0];
         a.z_mont[1] = pts_mont[1];
         uint64_t num_reduced = 0;
+        Ef off_p[2] = {ef_zero(), ef_zero()}, kp[2] = {ef_zero(), ef_zero()};
+        for (int p = 0; pm && p < 2; p++) {
+            off_p[p] = ef_pow(am, num_reduced);
+            kp[p] = ef_mul(reduced_ys(&opened_values[(size_t)p * pw], pw), off_p[p]);
+            num_reduced += pw;
+        }
         a.off_t[0] = ef_pow(am, num_reduced);
-        a.k0 = ef_mul(reduced_ys(&opened_values[0], w), a.off_t[0]);  // canonical x Montgomery -> canonical
+        a.k0 = ef_add(kp[0], ef_mul(reduced_ys(&ov[0], w), a.off_t[0]));  // canonical x Montgomery -> canonical
         num_reduced += w;
         a.off_t[1] = ef_pow(am, num_reduced);
-        a.k1 = ef_mul(reduced_ys(&opened_values[w], w), a.off_t[1]);
+        a.k1 = ef_add(kp[1], ef_mul(reduced_ys(&ov[w], w), a.off_t[1]));
         num_reduced += w;
         a.n_chunks = qd;
         a.chunk_stride = N;
@@ -269,7 +306,7 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
             TS_REQUIRE(quotient_data.ldes[c].col_stride == N, TS_ERR_INVALID, "open: chunk stride");
             a.chunk[c] = quotient_data.ldes[c].d;
             const Ef off_c = ef_pow(am, num_reduced);
-            a.k0 = ef_add(a.k0, ef_mul(reduced_ys(&opened_values[2 * w + 4 * c], 4), off_c));
+            a.k0 = ef_add(a.k0, ef_mul(reduced_ys(&ov[2 * w + 4 * c], 4), off_c));
             for (int k = 0; k < 4; k++) {  // alpha^k off_c: the weight of column k of chunk c
                 Ef ap;
                 memcpy(ap.c, &apow[4 * (size_t)k], 16);
@@ -283,7 +320,7 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         DevBuf<uint32_t> d_apow(&ctx_, apow.size());
         h2d(ctx_, d_apow.p, apow.data(), apow.size() * 4);
         a.chunk_w = d_apow.p + n_apow;
-        launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p);
+        launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, pm, off_p);
     }
     return ro;
 }
@@ -492,9 +529,20 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
 }
 
 // ------------------------------------------------------------------ prove
+// `proof_version` 3 (ts_prove_pre): `preprocessed` is the committed key of the AIR's preprocessed columns (null
+// for an AIR without any).  The key is part of the statement: its root is observed first and is not in the
+// proof; its round is opened first.  Build-defined: the reference's prove stops at preprocessed width 0
+// (prover.rs:46).
 std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                            DeviceMatrix trace, const std::vector<uint32_t>& public_values) {
+                            DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                            const PcsData* preprocessed, uint32_t proof_version) {
     const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
+    TS_REQUIRE((preprocessed != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
+               "prove: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
+    if (preprocessed) {
+        check_preprocessed_key(*preprocessed, air, 1ull << st.log_N);
+        challenger.observe_commitment(preprocessed->root);
+    }
     pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
 
     // :50-53 commit to trace data (natural domain: shift 1)
@@ -505,7 +553,7 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
     const Ef alpha = challenger.sample();              // :63
 
     // :65-80 quotient on the disjoint domain, flattened and split into qd chunks
-    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, public_values, alpha);
+    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, public_values, alpha, preprocessed);
     std::unique_ptr<PcsData> quotient_data =
         pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));  // :80-83
     challenger.observe_commitment(quotient_data->root);                             // :84
@@ -516,17 +564,19 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
     const Ef batch_alpha = challenger.sample();
     std::vector<Ef> opened;
     std::vector<DevBuf<Ef>> inputs;
-    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened));
+    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, preprocessed));
 
-    // ---- Proof (prover.rs:105-118), TSPF v1
+    // ---- Proof (prover.rs:105-118), TSPF v1 (v3: the preprocessed width in the header, its opened values first)
     std::vector<uint32_t> pf;
     pf.reserve(64 + opened.size() * 4);
     ProofWriter pw(pf);
-    pw.header(1, st.log_degree, st.w, st.qd, 0);
+    pw.header(proof_version, st.log_degree, st.w, st.qd, air.preprocessed_width);
     pw.commitment(trace_data->root, 8);
     pw.commitment(quotient_data->root, 8);
     pw.opened_values(opened);
-    pcs.fri_prove(inputs, {st.log_N}, challenger, {trace_data.get(), quotient_data.get()}, pf);
+    std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
+    if (preprocessed) rounds.insert(rounds.begin(), preprocessed);
+    pcs.fri_prove(inputs, {st.log_N}, challenger, rounds, pf);
     return pf;
 }
 

@@ -251,13 +251,13 @@ size_t ProofWriter::words_per_query(const std::vector<Batch>& batches, const std
     return n;
 }
 
-void ProofWriter::header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t num_queries) {
+void ProofWriter::header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t extra) {
     out_.push_back(TSPF_MAGIC);
     out_.push_back(version);
     out_.push_back(log_degree);
     out_.push_back(width);
     out_.push_back(qd);
-    if (version >= 2) out_.push_back(num_queries);
+    if (version >= 2) out_.push_back(extra);
 }
 
 void ProofWriter::opened_values(const std::vector<Ef>& values) {

@@ -108,8 +108,8 @@ public:
                                   size_t n_pass_through = 0);
 
     void words(const uint32_t* p, size_t n) { out_.insert(out_.end(), p, p + n); }
-    // version 1, or 2 with the extra num_queries word
-    void header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t num_queries);
+    // version 1; 2 with the extra num_queries word; 3 with the extra preprocessed_width word
+    void header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t extra);
     void commitment(const uint32_t* roots, size_t n_words) { words(roots, n_words); }  // 8, or Q x 8 (taptrees)
     void opened_values(const std::vector<Ef>& values);
     void begin_rounds(uint32_t n_rounds) { out_.push_back(n_rounds); }  // then one commitment() per round

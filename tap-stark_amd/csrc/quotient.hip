@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "air.hpp"
 #include "kernels.hpp"
@@ -252,14 +253,36 @@ struct QuotientRow : RowBase {
     }
 };
 
-template <int NTHREADS, bool GLOBAL_REGS>
-__global__ void __launch_bounds__(NTHREADS)
-k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-           const uint32_t* __restrict__ lde, uint64_t col_stride, unsigned log_n, unsigned log_qd,
-           const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
-           const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
-           const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
-           uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+// the same row of an AIR with preprocessed columns: the committed key's LDE is a second column-major matrix with
+// its own base and stride, and D_LOAD's operand a = 2, 3 reads its local / next row
+struct PrepQuotientRow : QuotientRow {
+    const uint32_t* prep_local;
+    const uint32_t* prep_next;
+    uint64_t prep_stride;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
+        // all four read first and chosen with selects, as RowBase::sel: an index into the struct would put it
+        // in scratch
+        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next;
+        const uint64_t s0 = col_stride, s1 = prep_stride;
+        const uint32_t* lo = (a & 1) ? p1 : p0;
+        const uint32_t* hi = (a & 1) ? p3 : p2;
+        return ((a & 2) ? hi : lo)[(uint64_t)b * ((a & 2) ? s1 : s0)];
+    }
+};
+
+// The row tiles of one workgroup.  PREP = false is k_quotient as it always was (the two prep arguments are
+// unused constants there); PREP = true differs in the row type alone.
+template <int NTHREADS, bool GLOBAL_REGS, bool PREP>
+__device__ __forceinline__ void quotient_tiles(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+                                               const uint32_t* __restrict__ lde, uint64_t col_stride,
+                                               const uint32_t* __restrict__ prep, uint64_t prep_stride, unsigned log_n,
+                                               unsigned log_qd, const uint32_t* __restrict__ consts_mont,
+                                               const uint32_t* __restrict__ alpha_pows,
+                                               const uint32_t* __restrict__ is_first,
+                                               const uint32_t* __restrict__ is_last,
+                                               const uint32_t* __restrict__ is_transition, const QuotConsts& qc,
+                                               const QuotOut& out, uint32_t row_begin, uint32_t row_end,
+                                               uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
     const unsigned L = log_n + log_qd;
     const uint32_t total = 1u << L;
     uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
@@ -270,7 +293,13 @@ k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
         const uint32_t i = bitrev32(rr, L);
         const uint32_t i_next = (i + (1u << log_qd)) & (total - 1);  // prover.rs:139-140,165
         const uint32_t r_next = bitrev32(i_next, L);
-        QuotientRow row{{lde + rr, lde + r_next, is_first[rr], is_last[rr], is_transition[rr]}, col_stride, alpha_pows};
+        const QuotientRow base{{lde + rr, lde + r_next, is_first[rr], is_last[rr], is_transition[rr]}, col_stride, alpha_pows};
+        typename std::conditional<PREP, PrepQuotientRow, QuotientRow>::type row{base};
+        if constexpr (PREP) {
+            row.prep_local = prep + rr;
+            row.prep_next = prep + r_next;
+            row.prep_stride = prep_stride;
+        }
         run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
         if (!active) continue;
         // quotient(x) = constraints(x) / Z_H(x)  (prover.rs:183); flatten + split (prover.rs:78-80):
@@ -284,6 +313,34 @@ k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
         o[2 * n] = mont_mul(row.acc2, iz);
         o[3 * n] = mont_mul(row.acc3, iz);
     }
+}
+
+template <int NTHREADS, bool GLOBAL_REGS>
+__global__ void __launch_bounds__(NTHREADS)
+k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+           const uint32_t* __restrict__ lde, uint64_t col_stride, unsigned log_n, unsigned log_qd,
+           const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
+           const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
+           const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
+           uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+    quotient_tiles<NTHREADS, GLOBAL_REGS, false>(code, n_instr, n_regs, lde, col_stride, nullptr, 0, log_n, log_qd,
+                                                 consts_mont, alpha_pows, is_first, is_last, is_transition, qc, out,
+                                                 row_begin, row_end, reg_slabs, n_tiles);
+}
+
+// the interpreter over (preprocessed LDE, trace LDE): both column-major with bit-reversed rows and one height
+template <int NTHREADS, bool GLOBAL_REGS>
+__global__ void __launch_bounds__(NTHREADS)
+k_quotient_pre(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+               const uint32_t* __restrict__ lde, uint64_t col_stride, const uint32_t* __restrict__ prep,
+               uint64_t prep_stride, unsigned log_n, unsigned log_qd,
+               const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
+               const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
+               const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
+               uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+    quotient_tiles<NTHREADS, GLOBAL_REGS, true>(code, n_instr, n_regs, lde, col_stride, prep, prep_stride, log_n,
+                                                log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition, qc,
+                                                out, row_begin, row_end, reg_slabs, n_tiles);
 }
 
 // The four instantiations of an interpreter kernel template (one function type), and the name of its timer.
@@ -313,8 +370,16 @@ static void launch_interpreter(Context& ctx, const InterpKernels<F>& k, const Ai
 
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
-                     const QuotOut& out, uint64_t row_begin, uint64_t row_end, uint32_t shift) {
+                     const QuotOut& out, uint64_t row_begin, uint64_t row_end, uint32_t shift,
+                     const ColMat* prep_lde) {
     TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
+    // a program with preprocessed loads never runs without the matrix they read, and the matrix covers the rows
+    TS_REQUIRE((prep_lde != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVARIANT,
+               "quotient: preprocessed LDE and the AIR's preprocessed width disagree");
+    if (prep_lde)
+        TS_REQUIRE(prep_lde->d && prep_lde->width == air.preprocessed_width && prep_lde->height == trace_lde.height &&
+                       prep_lde->col_stride >= prep_lde->height,
+                   TS_ERR_INVALID, "quotient: preprocessed LDE shape");
     TS_REQUIRE(log_n + log_qd <= 31, TS_ERR_INVALID, "quotient domain too large");
     const uint64_t qn = 1ull << (log_n + log_qd);
     if (row_end == 0) row_end = qn;
@@ -332,10 +397,14 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
     const uint32_t* lde_p = trace_lde.d;
     uint64_t stride = trace_lde.col_stride;
     QuotOut qo = out;
+    // the specialised kernels of an AIR with preprocessed columns take (prep, prep_stride) after row_end
+    // (jit.cpp emit_head); the others have no such parameters
+    const uint32_t* prep_p = prep_lde ? prep_lde->d : nullptr;
+    uint64_t prep_stride = prep_lde ? prep_lde->col_stride : 0;
     if (ks && !ks->seg) {
         // specialised straight-line kernel (jit.cpp); same arguments, same results
         void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont,
-                        &is_first, &is_last, &is_transition, &qc, &qo, &rb, &re};
+                        &is_first, &is_last, &is_transition, &qc, &qo, &rb, &re, &prep_p, &prep_stride};
         KernelTimer kt(&ctx, "k_quotient_jit");
         TS_HIP(hipModuleLaunchKernel((hipFunction_t)ks->fns[0], (unsigned)((total + 255) / 256), 1, 1,
                                      256, 1, 1, 0, ctx.stream, args, nullptr));
@@ -354,8 +423,12 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
         KernelTimer kt(&ctx, "k_quotient_seg");
         for (uint64_t t0 = row_begin; t0 < row_end; t0 += tile) {
             uint32_t tb = (uint32_t)t0, te = (uint32_t)std::min<uint64_t>(row_end, t0 + tile);
-            void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
-                            &is_last, &is_transition, &qc, &qo, &tb, &te, &slab_p, &slab_rows};
+            void* args_main[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
+                                 &is_last, &is_transition, &qc, &qo, &tb, &te, &slab_p, &slab_rows};
+            void* args_prep[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
+                                 &is_last, &is_transition, &qc, &qo, &tb, &te, &prep_p, &prep_stride, &slab_p,
+                                 &slab_rows};
+            void** args = prep_lde ? args_prep : args_main;
             const unsigned grid = (unsigned)((te - tb + 255) / 256);
             for (void* fn : ks->fns)
                 TS_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 256, 1, 1, 0, ctx.stream, args, nullptr));
@@ -364,6 +437,12 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
     }
     static const InterpKernels<decltype(&k_quotient<64, true>)> kernels{
         "k_quotient", k_quotient<64, true>, k_quotient<256, false>, k_quotient<128, false>, k_quotient<64, false>};
+    static const InterpKernels<decltype(&k_quotient_pre<64, true>)> kernels_pre{
+        "k_quotient_pre", k_quotient_pre<64, true>, k_quotient_pre<256, false>, k_quotient_pre<128, false>,
+        k_quotient_pre<64, false>};
+    if (prep_lde)
+        return launch_interpreter(ctx, kernels_pre, air, total, lde_p, stride, prep_p, prep_stride, log_n, log_qd,
+                                  d_consts_mont, d_alpha_pows_mont, is_first, is_last, is_transition, qc, qo, rb, re);
     launch_interpreter(ctx, kernels, air, total, lde_p, stride, log_n, log_qd, d_consts_mont,
                        d_alpha_pows_mont, is_first, is_last, is_transition, qc, qo, rb, re);
 }
@@ -423,6 +502,38 @@ struct CheckRow : RowBase {
     }
 };
 
+// the same with a row-major preprocessed matrix of the same height beside the trace (operand a = 2, 3)
+struct PrepCheckRow : CheckRow {
+    const uint32_t* prep_local;
+    const uint32_t* prep_next;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
+        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next;
+        const uint32_t* lo = (a & 1) ? p1 : p0;
+        const uint32_t* hi = (a & 1) ? p3 : p2;
+        return ((a & 2) ? hi : lo)[b];
+    }
+};
+
+template <int NTHREADS, bool GLOBAL_REGS>
+__global__ void __launch_bounds__(NTHREADS)
+k_check_constraints_pre(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+                        const uint32_t* __restrict__ trace, uint32_t width, const uint32_t* __restrict__ prep,
+                        uint32_t prep_width, uint64_t n, const uint32_t* __restrict__ consts_mont,
+                        unsigned long long* __restrict__ violation, uint32_t* __restrict__ reg_slabs,
+                        uint32_t n_tiles) {
+    uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t i = (uint64_t)tile * NTHREADS + threadIdx.x;
+        const bool active = i < n;
+        const uint64_t ii = active ? i : 0, nx = (ii + 1) % n;
+        unsigned long long bad = ~0ull;
+        PrepCheckRow row{{{trace + ii * width, trace + nx * width, ii == 0 ? R_MOD_P : 0u, ii == n - 1 ? R_MOD_P : 0u,
+                           ii != n - 1 ? R_MOD_P : 0u}, ii, bad}, prep + ii * prep_width, prep + nx * prep_width};
+        run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
+        if (active && bad != ~0ull) atomicMin(violation, bad);
+    }
+}
+
 template <int NTHREADS, bool GLOBAL_REGS>
 __global__ void __launch_bounds__(NTHREADS)
 k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
@@ -444,12 +555,20 @@ k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_
 
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
-                              unsigned long long* d_violation) {
+                              unsigned long long* d_violation, const uint32_t* prep_row_major) {
+    TS_REQUIRE((prep_row_major != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVARIANT,
+               "check_constraints: preprocessed matrix and the AIR's preprocessed width disagree");
     // the report is row * 2^16 + constraint index (the oracle's and stark.py's format)
     TS_REQUIRE(air.n_constraints <= 65536, TS_ERR_UNSUPPORTED, "check_constraints: more than 65536 constraints");
     static const InterpKernels<decltype(&k_check_constraints<64, true>)> kernels{
         "k_check_constraints", k_check_constraints<64, true>, k_check_constraints<256, false>,
         k_check_constraints<128, false>, k_check_constraints<64, false>};
+    static const InterpKernels<decltype(&k_check_constraints_pre<64, true>)> kernels_pre{
+        "k_check_constraints_pre", k_check_constraints_pre<64, true>, k_check_constraints_pre<256, false>,
+        k_check_constraints_pre<128, false>, k_check_constraints_pre<64, false>};
+    if (prep_row_major)
+        return launch_interpreter(ctx, kernels_pre, air, n, trace_row_major, air.width, prep_row_major,
+                                  air.preprocessed_width, n, d_consts_mont, d_violation);
     launch_interpreter(ctx, kernels, air, n, trace_row_major, air.width, n, d_consts_mont, d_violation);
 }
 

@@ -100,18 +100,19 @@ Ef fold_row(uint64_t index, unsigned log_height, Ef beta, Ef e0, Ef e1) {
 }
 
 // tape evaluation over EF4 (verifier side: opened values are extension elements)
-void eval_tape_ext(const AirProgram& air, const Ef* local, const Ef* next,
+// (prep_local / prep_next: the opened preprocessed rows of a version-2 AIR, unread otherwise)
+void eval_tape_ext(const AirProgram& air, const Ef* prep_local, const Ef* prep_next, const Ef* local, const Ef* next,
                    const std::vector<uint32_t>& pis, Ef is_first, Ef is_last, Ef is_trans,
                    std::vector<Ef>& v) {
-    const uint32_t* tape = air.tape.data();
-    const uint32_t n_nodes = tape[4];
-    const uint32_t* nodes = tape + 6;
+    const uint32_t n_nodes = air.tape[4];
+    const uint32_t* nodes = air.tape_nodes();
     v.resize(n_nodes);
     for (uint32_t i = 0; i < n_nodes; i++) {
         const uint32_t op = nodes[3 * i], a = nodes[3 * i + 1], b = nodes[3 * i + 2];
         switch (op) {
             case T_CONST: v[i] = ef_from_base(a); break;
             case T_MAIN: v[i] = a ? next[b] : local[b]; break;
+            case T_PREP: v[i] = a ? prep_next[b] : prep_local[b]; break;
             case T_PUBLIC: v[i] = ef_from_base(pis[a]); break;
             case T_IS_FIRST: v[i] = is_first; break;
             case T_IS_LAST: v[i] = is_last; break;
@@ -340,10 +341,16 @@ static int fri_verify_impl(const FriConfig& fri, BfChallenger& challenger,
 }
 
 // 0 = accept; otherwise the reference's error (see include/tapstark.h ts_verify)
+// v3: a TSPF v3 proof (ts_verify_pre); prep_root is then the root of the preprocessed key, or null for an AIR
+// without preprocessed columns
 static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
                        const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
-                       const TapLocks* tap);
+                       const TapLocks* tap, bool v3 = false, const uint32_t* prep_root = nullptr);
 
+int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
+               const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
+    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, true, preprocessed_root);
+}
 int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
            const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
     return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr);
@@ -356,13 +363,15 @@ int verify_tap(const FriConfig& fri, const AirProgram& air, BfChallenger& challe
 
 static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
                        const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
-                       const TapLocks* tap) {
+                       const TapLocks* tap, bool v3, const uint32_t* prep_root) {
     if (pis.size() != air.n_public) return 1;
     Reader rb{proof, n_words};
-    if (rb.get() != 0x46505354u || rb.get() != (tap ? 2u : 1u)) return 9;
+    if (rb.get() != 0x46505354u || rb.get() != (v3 ? 3u : tap ? 2u : 1u)) return 9;
     const unsigned degree_bits = rb.get();
     const uint32_t pw = rb.get(), pqd = rb.get();
     if (tap && rb.get() != fri.num_queries) return 1;  // TSPF v2: roots per commitment
+    const uint32_t P_w = air.preprocessed_width;
+    if (v3 && rb.get() != P_w) return 1;               // TSPF v3: the preprocessed width
     if (rb.bad || degree_bits > 27) return 9;
     const size_t n_roots = tap ? fri.num_queries : 1, cw = 8 * n_roots;
     const unsigned lqd = air.log_quotient_degree;
@@ -371,20 +380,26 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     if (pw != w || pqd != qd) return 1;
     const uint32_t* trace_root = rb.take(cw);
     const uint32_t* quot_root = rb.take(cw);
+    const uint32_t* prep_local = rb.take(4 * (size_t)P_w);  // v3 order: the preprocessed rows lead
+    const uint32_t* prep_next = rb.take(4 * (size_t)P_w);
     const uint32_t* trace_local = rb.take(4 * (size_t)w);
     const uint32_t* trace_next = rb.take(4 * (size_t)w);
     const uint32_t* qchunks = rb.take(16 * (size_t)qd);
     if (rb.bad) return 9;
     // (the proof is a word stream: Ef is 16-byte aligned, the words are not)
-    std::vector<Ef> tl(w), tn(w), qc(4 * (size_t)qd);
+    std::vector<Ef> pl(P_w), pn(P_w), tl(w), tn(w), qc(4 * (size_t)qd);
+    if (P_w) memcpy((void*)pl.data(), prep_local, 16 * (size_t)P_w);
+    if (P_w) memcpy((void*)pn.data(), prep_next, 16 * (size_t)P_w);
     memcpy((void*)tl.data(), trace_local, 16 * (size_t)w);
     memcpy((void*)tn.data(), trace_next, 16 * (size_t)w);
     memcpy((void*)qc.data(), qchunks, 64 * (size_t)qd);
-    for (auto* vec : {&tl, &tn, &qc})
+    for (auto* vec : {&pl, &pn, &tl, &tn, &qc})
         for (auto& e : *vec)
             for (int k = 0; k < 4; k++)
                 if (e.c[k] >= P) return 9;
 
+    // the key is part of the statement: observed before anything of the proof (prover.cpp prove)
+    if (P_w) challenger.observe_commitment(prep_root);
     // verifier.rs:69-75
     for (size_t k = 0; k < n_roots; k++) challenger.observe_commitment(trace_root + 8 * k);
     const Ef alpha = challenger.sample();
@@ -402,8 +417,15 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
         std::vector<Ef> vals(qc.begin() + 4 * (size_t)c, qc.begin() + 4 * (size_t)c + 4);
         r1.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, 4, {zeta}, {vals}});
     }
+    std::vector<PcsRoundClaim> claims{r0, r1};
+    if (P_w) {  // the key's round comes first, opened at the trace's points
+        PcsRoundClaim rp;
+        rp.root = prep_root;
+        rp.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, P_w, {zeta, zeta_next}, {pl, pn}});
+        claims.insert(claims.begin(), rp);
+    }
     Reader fr{proof + rb.pos, n_words - rb.pos};
-    const int rc = fri_verify_impl(fri, challenger, {r0, r1}, false, fr.w, fr.len, tap);
+    const int rc = fri_verify_impl(fri, challenger, claims, false, fr.w, fr.len, tap);
     if (rc) return rc;
 
     // ---- verifier.rs:103-132 quotient recombination
@@ -434,9 +456,8 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     const Ef inv_zeroifier = c_inv(zh);
     // :138-153 fold the constraints at zeta
     std::vector<Ef> v;
-    eval_tape_ext(air, tl.data(), tn.data(), pis, is_first, is_last, is_trans, v);
-    const uint32_t* tape = air.tape.data();
-    const uint32_t* cons = tape + 6 + 3 * (size_t)tape[4];
+    eval_tape_ext(air, pl.data(), pn.data(), tl.data(), tn.data(), pis, is_first, is_last, is_trans, v);
+    const uint32_t* cons = air.tape_constraints();
     Ef acc = ef_zero();
     for (uint32_t c = 0; c < air.n_constraints; c++) acc = ef_add(c_mul(acc, alpha), v[cons[c]]);
     if (!ef_eq(c_mul(acc, inv_zeroifier), quotient)) return 7;  // :157 OodEvaluationMismatch

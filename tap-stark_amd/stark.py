@@ -433,6 +433,9 @@ class CompiledAir:
         self._l.ts_air_info(h, C.byref(w), C.byref(npub), C.byref(deg), C.byref(lqd))
         self.width, self.n_public = int(w.value), int(npub.value)
         self.max_constraint_degree, self.log_quotient_degree = int(deg.value), int(lqd.value)
+        pw = C.c_uint32()
+        self._l.ts_air_preprocessed_width(h, C.byref(pw))
+        self.preprocessed_width = int(pw.value)
 
     @property
     def is_jit(self) -> bool:
@@ -630,13 +633,20 @@ class TwoAdicFriPcs:
         self.ctx.check(self.ctx._l.ts_pcs_data_evaluations_on_domain(self.ctx.h, data.h, idx, log_size, C.byref(h)))
         return DeviceMatrix(self.ctx, h)
 
-    def quotient_chunks(self, trace_data: PcsData, air: CompiledAir, public_values, alpha):
+    def quotient_chunks(self, trace_data: PcsData, air: CompiledAir, public_values, alpha, preprocessed=None):
+        """``preprocessed``: the ``PreprocessedKey`` (or its ``PcsData``) of an AIR with preprocessed columns
+        (``ts_quotient_chunks_pre``); None is ``ts_quotient_chunks``."""
         qd = 1 << air.log_quotient_degree
         out = (C.c_void_p * qd)()
         pis = _u32(public_values)
         pis_p = _p(pis) if len(pis) else None
-        self.ctx.check(self.ctx._l.ts_quotient_chunks(self.ctx.h, trace_data.h, self.fri.log_blowup,
-                                                      air.h, pis_p, len(pis), _p(_u32(alpha)), out))
+        if preprocessed is None:
+            self.ctx.check(self.ctx._l.ts_quotient_chunks(self.ctx.h, trace_data.h, self.fri.log_blowup,
+                                                          air.h, pis_p, len(pis), _p(_u32(alpha)), out))
+        else:
+            key = getattr(preprocessed, "data", preprocessed)
+            self.ctx.check(self.ctx._l.ts_quotient_chunks_pre(self.ctx.h, key.h, trace_data.h, self.fri.log_blowup,
+                                                              air.h, pis_p, len(pis), _p(_u32(alpha)), out))
         return [DeviceMatrix(self.ctx, C.c_void_p(out[c])) for c in range(qd)]
 
     def open_reduce(self, trace_data: PcsData, quotient_data: PcsData, width: int, zeta, batch_alpha):
@@ -842,8 +852,8 @@ class Proof:
     ``commit_phase_commits``, ``query_proofs``, ``final_poly``, ``pow_witness``) are parsed on first
     access: ``prove()`` hands back the words without spending interpreter time on them."""
 
-    _FIELDS = ("degree_bits", "trace_commit", "quotient_commit", "trace_local", "trace_next",
-               "quotient_chunks", "commit_phase_commits", "query_proofs", "final_poly", "pow_witness")
+    _FIELDS = ("degree_bits", "trace_commit", "quotient_commit", "preprocessed_local", "preprocessed_next",
+               "trace_local", "trace_next", "quotient_chunks", "commit_phase_commits", "query_proofs", "final_poly", "pow_witness")
 
     def __init__(self, words):
         self.words = np.asarray(words, dtype=np.uint32)
@@ -900,21 +910,26 @@ class Proof:
             return out
 
         magic, version, degree_bits, width, qd = (int(x) for x in take(5))
-        if magic != TSPF_MAGIC or version not in (1, 2):
-            raise ValueError("not a TSPF v1/v2 proof")
+        if magic != TSPF_MAGIC or version not in (1, 2, 3):
+            raise ValueError("not a TSPF v1/v2/v3 proof")
         # v2 (proofs over the taptree MMCS, ts_prove_tap): num_queries roots per commitment, the
         # commitment fields are (num_queries, 8) arrays
         nr = int(take(1)[0]) if version == 2 else 1
-        d = {"degree_bits": degree_bits, "query_proofs": [], "version": version}
-        if version == 1:
+        # v3 (ts_prove_pre): the preprocessed width; the opened preprocessed rows lead the opened values and
+        # every query's input proof holds three BatchOpenings (key, trace, chunks)
+        pw = int(take(1)[0]) if version == 3 else 0
+        d = {"degree_bits": degree_bits, "query_proofs": [], "version": version, "preprocessed_width": pw}
+        if version != 2:
             d["trace_commit"], d["quotient_commit"] = take(8), take(8)
         else:
             d["trace_commit"], d["quotient_commit"] = take(8 * nr).reshape(nr, 8), take(8 * nr).reshape(nr, 8)
+        d["preprocessed_local"] = take(4 * pw).reshape(pw, 4)
+        d["preprocessed_next"] = take(4 * pw).reshape(pw, 4)
         d["trace_local"] = take(4 * width).reshape(width, 4)
         d["trace_next"] = take(4 * width).reshape(width, 4)
         d["quotient_chunks"] = take(16 * qd).reshape(qd, 4, 4)
         R = int(take(1)[0])
-        d["commit_phase_commits"] = (take(8 * R).reshape(R, 8) if version == 1
+        d["commit_phase_commits"] = (take(8 * R).reshape(R, 8) if version != 2
                                      else take(8 * nr * R).reshape(R, nr, 8))
         Q = int(take(1)[0])
         for _ in range(Q):
@@ -938,25 +953,51 @@ class Proof:
         self.__dict__.update(d)
 
 
-def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_values) -> Proof:
+class PreprocessedKey:
+    """The preprocessed (fixed) columns of an AIR, committed once: ``ts_pcs_commit`` of the one (n, P) matrix
+    on the natural domain.  ``data`` is the ``PcsData`` the prover reads (never consumed: one key serves any
+    number of proofs on its context), ``root`` what the verifier holds."""
+
+    def __init__(self, config: "StarkConfig", matrix):
+        pcs = config.pcs
+        if not isinstance(matrix, DeviceMatrix):
+            matrix = DeviceMatrix.upload(pcs.ctx, _u32(matrix))
+        n = matrix.dims()[0]
+        self.root, self.data = pcs.commit([(pcs.natural_domain_for_degree(n), matrix)])
+        self.root = self.root.copy()
+
+
+def _preprocessed_width(air) -> int:
+    f = getattr(air, "preprocessed_width", 0)
+    return int(f() if callable(f) else f)
+
+
+def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_values, preprocessed=None) -> Proof:
     """``uni_stark::prove`` (reference uni-stark/src/prover.rs:25-35).
 
     ``air`` is a ``BaseAir`` (captured symbolically like ``get_symbolic_constraints``) or an
     already ``CompiledAir``; ``trace`` an (n, w) array or a ``DeviceMatrix`` (consumed).
+    ``preprocessed``: the ``PreprocessedKey`` of an AIR with preprocessed columns (``ts_prove_pre``; the proof
+    is TSPF v3); None is ``ts_prove``.
     """
     pcs = config.pcs
     ctx = pcs.ctx
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
-        air = CompiledAir(ctx, air_tape(air, len(pis)))
+        air = CompiledAir(ctx, air_tape(air, len(pis), _preprocessed_width(air)))
     if not isinstance(trace, DeviceMatrix):
         trace = DeviceMatrix.upload(ctx, trace)
-    out = _proof_buffer(ctx, _proof_capacity(*trace.dims(), air.log_quotient_degree, pcs.fri))
+    n, w = trace.dims()
+    out = _proof_buffer(ctx, _proof_capacity(n, w + air.preprocessed_width, air.log_quotient_degree, pcs.fri))
     n_words = C.c_size_t()
     cfg = pcs.fri._c()
     pis_p = _p(pis) if len(pis) else None
-    ctx.check(ctx._l.ts_prove(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis),
-                              _p(out), len(out), C.byref(n_words)))
+    if preprocessed is None:
+        ctx.check(ctx._l.ts_prove(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis),
+                                  _p(out), len(out), C.byref(n_words)))
+    else:
+        ctx.check(ctx._l.ts_prove_pre(ctx.h, C.byref(cfg), air.h, challenger.h, preprocessed.data.h, trace.h, pis_p,
+                                      len(pis), _p(out), len(out), C.byref(n_words)))
     return Proof(out[: n_words.value].copy())
 
 
@@ -994,7 +1035,8 @@ def _proof_capacity(n: int, w: int, log_quotient_degree: int, fri: FriConfig) ->
     qd = 1 << log_quotient_degree
     R = log_N - fri.log_blowup
     Q = fri.num_queries
-    return 64 + 8 * w + 16 * qd + 8 * R + Q * (16 + w + 5 * qd + 2 * 8 * log_N + R * (9 + 8 * log_N))
+    # (three Merkle paths of the input proof: a TSPF v3 proof opens the preprocessed key's round as well)
+    return 64 + 8 * w + 16 * qd + 8 * R + Q * (18 + w + 5 * qd + 3 * 8 * log_N + R * (9 + 8 * log_N))
 
 
 def _proof_buffer(ctx, cap: int) -> np.ndarray:
@@ -1189,34 +1231,47 @@ class VerificationError(Exception):
         self.code = code
 
 
-def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_values) -> None:
+def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_values, preprocessed_root=None) -> None:
     """``uni_stark::verify`` (reference uni-stark/src/verifier.rs:19-25); host only, no GPU.
-    Raises ``VerificationError``; returns None on acceptance (``Ok(())``)."""
+    Raises ``VerificationError``; returns None on acceptance (``Ok(())``).
+    ``preprocessed_root``: the root of the ``PreprocessedKey`` a TSPF v3 proof was made against
+    (``ts_verify_pre``); None is ``ts_verify``."""
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
-        air = CompiledAir(None, air_tape(air, len(pis)))
+        air = CompiledAir(None, air_tape(air, len(pis), _preprocessed_width(air)))
     words = _u32(proof.words if isinstance(proof, Proof) else proof)
     cfg = config.pcs.fri._c()
     verdict = C.c_int(-1)
     l = _lib.lib()
-    rc = l.ts_verify(C.byref(cfg), air.h, challenger.h, _p(words), len(words),
-                     _p(pis) if len(pis) else None, len(pis), C.byref(verdict))
-    if rc:
-        raise _lib.TsError(rc, "ts_verify")
+    pis_p = _p(pis) if len(pis) else None
+    if preprocessed_root is None:
+        rc = l.ts_verify(C.byref(cfg), air.h, challenger.h, _p(words), len(words), pis_p, len(pis), C.byref(verdict))
+    else:
+        rc = l.ts_verify_pre(C.byref(cfg), air.h, challenger.h, _p(_u32(preprocessed_root)), _p(words), len(words),
+                             pis_p, len(pis), C.byref(verdict))
+    if rc and verdict.value <= 0:  # (ts_verify_pre refuses a proof of another version or width WITH a verdict)
+        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify").decode())
     if verdict.value != 0:
         raise VerificationError(verdict.value)
 
 
-def check_constraints(air, trace, public_values, ctx: Context | None = None) -> int:
+def check_constraints(air, trace, public_values, ctx: Context | None = None, preprocessed=None) -> int:
     """reference uni-stark/src/check_constraints.rs:11-39 on the GPU.  Returns -1 if every
-    constraint holds on every row, else ``row * 65536 + constraint_index`` of the first failure."""
+    constraint holds on every row, else ``row * 65536 + constraint_index`` of the first failure.
+    ``preprocessed``: the (n, P) matrix of an AIR with preprocessed columns (``ts_check_constraints_pre``)."""
     ctx = ctx or default_context()
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
-        air = CompiledAir(ctx, air_tape(air, len(pis)))
+        air = CompiledAir(ctx, air_tape(air, len(pis), _preprocessed_width(air)))
     if not isinstance(trace, DeviceMatrix):
         trace = DeviceMatrix.upload(ctx, trace)
     out = C.c_int64(-1)
-    ctx.check(ctx._l.ts_check_constraints(ctx.h, air.h, trace.h, _p(pis) if len(pis) else None,
-                                          len(pis), C.byref(out)))
+    pis_p = _p(pis) if len(pis) else None
+    if preprocessed is None:
+        ctx.check(ctx._l.ts_check_constraints(ctx.h, air.h, trace.h, pis_p, len(pis), C.byref(out)))
+    else:
+        if not isinstance(preprocessed, DeviceMatrix):
+            preprocessed = DeviceMatrix.upload(ctx, _u32(preprocessed))
+        ctx.check(ctx._l.ts_check_constraints_pre(ctx.h, air.h, preprocessed.h, trace.h, pis_p, len(pis),
+                                                  C.byref(out)))
     return int(out.value)
