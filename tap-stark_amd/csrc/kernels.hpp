@@ -52,10 +52,12 @@ void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_s
 // Two matrices of one height in ONE set of launches (the two quotient chunks: each is four columns, and a
 // launch set of its own left the chip a quarter full three times over): evals2 != nullptr holds columns
 // gw .. ncols-1 (same column stride), extended on its own coset shift2; `out` takes all ncols columns.
+// stage_timers = false: the passes record no "lde: ..." stage of their own (an extension that belongs to
+// another stage's time: the reduced opening's, prover.cpp).
 void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t ncols, unsigned log_n,
                unsigned log_blowup, uint32_t shift, uint32_t* out, uint64_t out_col_stride,
                uint32_t beta0 = 0, uint32_t n_beta = 0, bool first_round_done = false,
-               uint32_t* evals2 = nullptr, uint32_t shift2 = 0, uint32_t gw = 0);
+               uint32_t* evals2 = nullptr, uint32_t shift2 = 0, uint32_t gw = 0, bool stage_timers = true);
 
 // The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles for log_n must be there).  Each refuses
 // what the plan cannot run with the caller's wording (`lde`).
@@ -231,6 +233,14 @@ void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
 // prep != nullptr (k_reduce_fused_pre): the preprocessed columns' LDE, opened at the same two points BEFORE the
 // trace with the offsets prep_off_mont[2]; args.off_t then start after them and args.k0 / k1 hold the
 // preprocessed constants too.  d_alpha_pows_mont covers max(trace width, prep width, 4) powers.
+// The same reduced opening on the low coset only (rows t < n = 2^log_n of matrices that hold the whole LDE, no
+// preprocessed round): out = four base-field columns of n rows (stride n, canonical), to be extended by
+// coset_lde with shift 1 like a quotient chunk on 31 H_n.  `weights` = launch_bary_weights' output for
+// args.z_mont on the coset 31 H_n ([2][n]); no inversion runs.  args.row0 / rows are not used.
+void launch_reduce_low(Context& ctx, const ColMat& trace, unsigned log_n, const uint32_t* d_alpha_pows_mont,
+                       const FusedReduceArgs& args, const Ef* weights, uint32_t* out);
+// out[X] = (cols[k * col_stride + X])_{k < 4}, X < rows
+void launch_ef_interleave(Context& ctx, const uint32_t* cols, uint64_t col_stride, uint64_t rows, Ef* out);
 
 // ---- fri.hip ---------------------------------------------------------------------------------
 // out[i] = fold(in[2i], in[2i+1]; beta) (reference two_adic_pcs.rs:116-147); h = output length.

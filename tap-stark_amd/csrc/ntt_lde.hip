@@ -37,6 +37,7 @@
 // of this file turn a plan into grids.  The two contiguous kernels also serve the standalone transforms
 // (ntt_dft.hip) through launch_contig_inverse / launch_contig_forward: an inverse pass on one matrix, a
 // forward pass on one coset block.
+#include <optional>
 #include <type_traits>
 
 #include "ntt_rounds.hpp"
@@ -413,7 +414,7 @@ void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint6
 void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t ncols, unsigned log_n,
                unsigned log_blowup, uint32_t shift, uint32_t* out, uint64_t out_col_stride,
                uint32_t beta0, uint32_t n_beta, bool first_round_done, uint32_t* evals2, uint32_t shift2,
-               uint32_t gw) {
+               uint32_t gw, bool stage_timers) {
     if (ncols == 0) return;
     TS_REQUIRE(evals2 == nullptr || (gw >= 1 && gw < ncols && shift2 != 0), TS_ERR_INVALID,
                "coset_lde: second matrix needs its first column and its shift");
@@ -440,10 +441,12 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
         // whatever the buffers hold, to sample its clock and power; every product path leaves it at 7)
         if (ctx.lde_pass_mask & 1u) {
             // (stage names: the sharded prover reports where a rank's time goes)
-            StageTimer t(&ctx, "lde: inverse NTT, contiguous stages");
+            std::optional<StageTimer> t;
+            if (stage_timers) t.emplace(&ctx, "lde: inverse NTT, contiguous stages");
             launch_contig_inverse(ctx, p, evals, in_col_stride, ncols, first_round_done, evals2, gw);
         }
-        StageTimer t_rest(&ctx, "lde: strided pass + forward NTT of the owned cosets");
+        std::optional<StageTimer> t_rest;
+        if (stage_timers) t_rest.emplace(&ctx, "lde: strided pass + forward NTT of the owned cosets");
         if (ctx.lde_pass_mask & 2u)
             launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2,
                            scale2, gw);

@@ -503,4 +503,84 @@ void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
     TS_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------ reduce on the low coset
+// The reduced opening is a polynomial of degree < n, so its n values on one coset of H_n determine the other
+// N - n: k_reduce_low computes them on the low coset (rows t < n, x_t = 31 omega_n^bitrev(t)) and the caller
+// extends them with the coset LDE (prover.cpp).  Same sums, same constants and same lazy accumulation as
+// k_reduce_fused; the two inverses are not computed but read:  k_bary_weights left
+// weights[p][t] = x_t / (z_p - x_t), hence 1/(x_t - z_p) = -weights[p][t] / x_t, and 1/x_t is one product of
+// the inverse coset generator with an inverse twiddle.  Output: four base-field columns of n rows (an n x 4
+// COL_MAJOR_BITREV matrix, canonical), the shape of a quotient chunk.
+// (the chunk columns' dot product as a function: here its by-value struct argument may cost registers, which
+// k_reduce_fused and k_reduce_fused_pre avoid with inline copies of the loop)
+__device__ __forceinline__ Ef chunk_dot(const FusedReduceArgs& a, uint64_t X) {
+    uint64_t acc[4] = {0, 0, 0, 0};
+    uint32_t c = 0;
+    for (; c + 2 <= a.n_chunks; c += 2) {
+        uint32_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = a.chunk[c + (k >> 2)][(uint64_t)(k & 3) * a.chunk_stride + X];
+        const uint32_t* ap = a.chunk_w + 16 * c;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[j] = lazy_mac(acc[j], v[k], ap[4 * k + j]);
+            if (k & 1) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = lazy_fix(acc[j]);
+            }
+        }
+    }
+    for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
+    return Ef{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
+}
+
+__global__ void __launch_bounds__(256)
+k_reduce_low(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width, unsigned log_n,
+             const uint32_t* __restrict__ Winv, uint32_t gen_inv_mont, const uint32_t* __restrict__ alpha_pows,
+             FusedReduceArgs a, const Ef* __restrict__ weights, uint32_t* __restrict__ out) {
+    const uint64_t n = 1ull << log_n;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const Ef St = row_dot_alpha(trace, trace_stride, width, t, alpha_pows);
+    const Ef D = chunk_dot(a, t);
+    // -1/x_t = -(1/gen) omega_n^-bitrev(t)
+    const uint32_t nxi = neg(mont_mul(gen_inv_mont, root_bitrev(Winv, log_n, t)));
+    const Ef inv_d0 = ef_mul_base(weights[t], nxi), inv_d1 = ef_mul_base(weights[n + t], nxi);
+    const Ef g0 = ef_sub(ef_add(ef_mul(St, a.off_t[0]), D), a.k0);
+    const Ef g1 = ef_sub(ef_mul(St, a.off_t[1]), a.k1);
+    const Ef r = ef_add(ef_mul(g0, inv_d0), ef_mul(g1, inv_d1));
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[(uint64_t)k * n + t] = r.c[k];
+}
+
+void launch_reduce_low(Context& ctx, const ColMat& trace, unsigned log_n, const uint32_t* d_alpha_pows_mont,
+                       const FusedReduceArgs& args, const Ef* weights, uint32_t* out) {
+    TS_REQUIRE(args.n_chunks <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_INVALID, "reduce_low: too many chunks");
+    const uint64_t n = 1ull << log_n;
+    TS_REQUIRE(args.row0 == 0 && trace.height >= n && trace.col_stride >= n && args.chunk_stride >= n, TS_ERR_INVALID,
+               "reduce_low: the matrices must start with the low coset");
+    ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
+    TS_LAUNCH(ctx, k_reduce_low, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint32_t*)trace.d,
+              trace.col_stride, trace.width, log_n, (const uint32_t*)ctx.d_twiddle_inv,
+              to_mont(inv_canon(GENERATOR)), d_alpha_pows_mont, args, weights, out);
+    TS_HIP(hipGetLastError());
+}
+
+// out[X] = (cols[0][X], cols[1][X], cols[2][X], cols[3][X]): four base-field columns -> the array of EF4 that
+// the FRI commit phase takes; one lane per row, one 16-byte store
+__global__ void __launch_bounds__(256)
+k_ef_interleave(const uint32_t* __restrict__ cols, uint64_t col_stride, uint64_t rows, Ef* __restrict__ out) {
+    const uint64_t X = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (X >= rows) return;
+    *reinterpret_cast<uint4*>(out + X) = make_uint4(cols[X], cols[col_stride + X], cols[2 * col_stride + X],
+                                                    cols[3 * col_stride + X]);
+}
+
+void launch_ef_interleave(Context& ctx, const uint32_t* cols, uint64_t col_stride, uint64_t rows, Ef* out) {
+    TS_REQUIRE(col_stride >= rows, TS_ERR_INVALID, "ef_interleave: column stride below the row count");
+    TS_LAUNCH(ctx, k_ef_interleave, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, cols, col_stride, rows, out);
+    TS_HIP(hipGetLastError());
+}
+
 }  // namespace ts

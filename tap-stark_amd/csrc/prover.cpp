@@ -221,9 +221,9 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
     // ---- opened values: barycentric interpolation on the low coset (two_adic_pcs.rs:358-369)
     std::vector<Ef> raw_all(2 * (size_t)pw + 2 * (size_t)w + 4 * (size_t)qd);
     Ef* const raw = raw_all.data() + 2 * (size_t)pw;  // [-2 pw, 0): the preprocessed sums, [col][point]
+    DevBuf<Ef> weights(&ctx_, 2 * n);  // x_t / (z_p - x_t): the low-coset reduce below divides by them again
     {
         StageTimer t(&ctx_, "compute opened values with Lagrange interpolation");
-        DevBuf<Ef> weights(&ctx_, 2 * n);
         launch_bary_weights(ctx_, log_n, pts_mont, 2, weights.p, coset_gen);
         // the last kernels of the stage write the sums straight into the context's mailbox (host memory)
         Ef* const mail = reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw_all.size()));
@@ -275,6 +275,10 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         }
         return acc;
     };
+    // The reduced opening has degree < n: on wide proofs it is computed on the low coset only, where the
+    // inverses are the barycentric weights, and extended like a quotient chunk on 31 H_n (open.hip)
+    const bool low = slab.rows == 0 && !pm && reduce_low_wanted(w + 4 * qd);
+    if (!low) weights.reset();
     DevBuf<Ef> ro(&ctx_, N);
     {
         // offsets follow two_adic_pcs.rs:371,383: num_reduced grows by the width after every
@@ -320,7 +324,17 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         DevBuf<uint32_t> d_apow(&ctx_, apow.size());
         h2d(ctx_, d_apow.p, apow.data(), apow.size() * 4);
         a.chunk_w = d_apow.p + n_apow;
-        launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, pm, off_p);
+        if (low) {
+            DevBuf<uint32_t> ro_low(&ctx_, 4 * n), ro_cols(&ctx_, 4 * N);
+            launch_reduce_low(ctx_, tr, log_n, d_apow.p, a, weights.p, ro_low.p);
+            // the chunk-0 call of lde_stage (domain shift 31, so coset_lde's shift is 1), without its stage
+            // timers: the launches belong to "reduce rows"
+            coset_lde(ctx_, ro_low.p, n, 4, log_n, fri_.log_blowup, 1, ro_cols.p, N, 0, 0, false, nullptr, 0, 0,
+                      /*stage_timers=*/false);
+            launch_ef_interleave(ctx_, ro_cols.p, N, N, ro.p);
+        } else {
+            launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, pm, off_p);
+        }
     }
     return ro;
 }

@@ -183,6 +183,11 @@ void lde_stage(Context& ctx, const FriConfig& fri, std::vector<DeviceMatrix>& ev
     if (batched) data.lde_storage.push_back(std::move(batch));
 }
 
+bool reduce_low_wanted(uint32_t opened_columns) {
+    if (const char* e = getenv("TS_REDUCE_LOW"); e && *e) return atoi(e) != 0;
+    return opened_columns >= REDUCE_LOW_MIN_WIDTH;
+}
+
 // ------------------------------------------------------------------ the statement
 Statement check_statement(const FriConfig& fri, const AirProgram& air, uint32_t trace_width, uint64_t degree,
                           size_t n_public_values) {

@@ -72,6 +72,13 @@ void lde_stage(Context& ctx, const FriConfig& fri, std::vector<DeviceMatrix>& ev
                const std::vector<uint32_t>& domain_shifts, uint32_t beta0, uint32_t n_beta, bool allow_pair,
                PcsData& data);
 
+// ---- where the reduced opening is computed on the low coset and extended (open_reduce_slab): whole LDEs without
+// a preprocessed round (the caller's test), from REDUCE_LOW_MIN_WIDTH opened columns (trace + chunk columns) up
+// -- below it a proof is bound by its launches and the extension's extra ones cost more than the rows save
+// (profiles/reduce_low_coset_crossover.txt).  TS_REDUCE_LOW = 0 never / 1 always, read on every call.
+constexpr uint32_t REDUCE_LOW_MIN_WIDTH = 72;
+bool reduce_low_wanted(uint32_t opened_columns);
+
 // ---- the statement of a proof (uni-stark/src/prover.rs:43-46), checked
 struct Statement {
     unsigned log_degree, lqd;
