@@ -130,3 +130,246 @@ where
     tape.extend_from_slice(&roots);
     tape
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Challenge-phase (aux) columns: tape version 3 (include/tapstark.h).  uni-stark's `SymbolicAirBuilder` has one
+// trace phase and no challenge entries, so an AIR with aux columns is captured with a builder of this crate's own:
+// the mirror of `ts::air::Builder` in include/tapstark_air.hpp and of `SymbolicAirBuilder` in tap-stark_amd/air.py,
+// node for node (hash-consed {op, a, b} triples; every operator builds its nodes in the same fixed order, so the
+// three front ends give the same tape for the same `eval`).  Prove the tape with `ts_prove_aux`.
+const OP_AUX: u32 = 11; // a = offset 0|1, b = column < aux_width; degree multiple 1
+const OP_CHALLENGE: u32 = 12; // a = word index < 4 * n_challenges; degree multiple 0
+const OP_EXPOSED: u32 = 13; // a = index < n_exposed; degree multiple 0
+const BABYBEAR_P: u64 = 0x7800_0001;
+const EF_W: u64 = 11; // EF4 = F[x] / (x^4 - 11)
+
+/// A node id of an [`AuxAirBuilder`].
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct Expr(pub u32);
+
+/// An extension-field expression: four coefficients over x^4 - 11.  `assert_zero_ext` emits FOUR base
+/// constraints, so an extension-valued constraint is an ordinary constraint of the tape language.
+#[derive(Clone, Copy, Debug)]
+pub struct ExtExpr(pub [Expr; 4]);
+
+pub struct AuxAirBuilder {
+    width: u32,
+    n_public: u32,
+    preprocessed_width: u32,
+    aux_width: u32,
+    n_challenges: u32,
+    n_exposed: u32,
+    nodes: Vec<[u32; 3]>,
+    degs: Vec<u32>,
+    cse: HashMap<[u32; 3], u32>,
+    constraints: Vec<u32>,
+}
+
+impl AuxAirBuilder {
+    /// Variables in the order of the other front ends: preprocessed, main, public, aux, challenge words, exposed.
+    pub fn new(width: u32, n_public: u32, preprocessed_width: u32, aux_width: u32, n_challenges: u32, n_exposed: u32) -> Self {
+        let mut b = AuxAirBuilder {
+            width, n_public, preprocessed_width, aux_width, n_challenges, n_exposed,
+            nodes: Vec::new(), degs: Vec::new(), cse: HashMap::new(), constraints: Vec::new(),
+        };
+        for off in 0..2 { for c in 0..preprocessed_width { b.node(OP_PREP, off, c, 1); } }
+        for off in 0..2 { for c in 0..width { b.node(OP_MAIN, off, c, 1); } }
+        for i in 0..n_public { b.node(OP_PUBLIC, i, 0, 0); }
+        for off in 0..2 { for c in 0..aux_width { b.node(OP_AUX, off, c, 1); } }
+        for k in 0..4 * n_challenges { b.node(OP_CHALLENGE, k, 0, 0); }
+        for e in 0..n_exposed { b.node(OP_EXPOSED, e, 0, 0); }
+        b
+    }
+    fn node(&mut self, op: u32, a: u32, b: u32, deg: u32) -> Expr {
+        let key = [op, a, b];
+        if let Some(&id) = self.cse.get(&key) {
+            return Expr(id);
+        }
+        let id = self.nodes.len() as u32;
+        self.nodes.push(key);
+        self.degs.push(deg);
+        self.cse.insert(key, id);
+        Expr(id)
+    }
+    fn deg(&self, e: Expr) -> u32 { self.degs[e.0 as usize] }
+    pub fn main(&mut self, offset: u32, column: u32) -> Expr { self.node(OP_MAIN, offset, column, 1) }
+    pub fn preprocessed(&mut self, offset: u32, column: u32) -> Expr { self.node(OP_PREP, offset, column, 1) }
+    pub fn public(&mut self, index: u32) -> Expr { self.node(OP_PUBLIC, index, 0, 0) }
+    pub fn aux(&mut self, offset: u32, column: u32) -> Expr { self.node(OP_AUX, offset, column, 1) }
+    pub fn exposed(&mut self, index: u32) -> Expr { self.node(OP_EXPOSED, index, 0, 0) }
+    pub fn challenge(&mut self, k: u32) -> ExtExpr {
+        ExtExpr([0, 1, 2, 3].map(|j| self.node(OP_CHALLENGE, 4 * k + j, 0, 0)))
+    }
+    pub fn constant(&mut self, v: u64) -> Expr { self.node(OP_CONST, (v % BABYBEAR_P) as u32, 0, 0) }
+    pub fn is_first_row(&mut self) -> Expr { self.node(OP_IS_FIRST_ROW, 0, 0, 1) }
+    pub fn is_last_row(&mut self) -> Expr { self.node(OP_IS_LAST_ROW, 0, 0, 1) }
+    pub fn is_transition(&mut self) -> Expr { self.node(OP_IS_TRANSITION, 0, 0, 0) }
+    pub fn add(&mut self, x: Expr, y: Expr) -> Expr {
+        let d = self.deg(x).max(self.deg(y));
+        self.node(OP_ADD, x.0, y.0, d)
+    }
+    pub fn sub(&mut self, x: Expr, y: Expr) -> Expr {
+        let d = self.deg(x).max(self.deg(y));
+        self.node(OP_SUB, x.0, y.0, d)
+    }
+    pub fn mul(&mut self, x: Expr, y: Expr) -> Expr {
+        let d = self.deg(x) + self.deg(y);
+        self.node(OP_MUL, x.0, y.0, d)
+    }
+    pub fn assert_zero(&mut self, x: Expr) { self.constraints.push(x.0); }
+    /// `when(cond).assert_zero(x)`: assert_zero(cond * x)
+    pub fn assert_zero_when(&mut self, cond: Expr, x: Expr) {
+        let c = self.mul(cond, x);
+        self.assert_zero(c);
+    }
+
+    // ---- ExtExpr: the node order of every operator is that of air.py's ExtExpr
+    pub fn ext_from_base(&mut self, x: Expr) -> ExtExpr {
+        let zero = self.constant(0);
+        ExtExpr([x, zero, zero, zero])
+    }
+    pub fn ext_add(&mut self, x: ExtExpr, y: ExtExpr) -> ExtExpr { ExtExpr([0, 1, 2, 3].map(|k| self.add(x.0[k], y.0[k]))) }
+    pub fn ext_sub(&mut self, x: ExtExpr, y: ExtExpr) -> ExtExpr { ExtExpr([0, 1, 2, 3].map(|k| self.sub(x.0[k], y.0[k]))) }
+    pub fn ext_mul_base(&mut self, x: ExtExpr, y: Expr) -> ExtExpr { ExtExpr([0, 1, 2, 3].map(|k| self.mul(x.0[k], y))) }
+    /// r_k = sum_{i+j=k} a_i b_j + 11 sum_{i+j=k+4} a_i b_j
+    pub fn ext_mul(&mut self, x: ExtExpr, y: ExtExpr) -> ExtExpr {
+        let mut out = [Expr(0); 4];
+        for k in 0..4usize {
+            let lo: Vec<Expr> = (0..=k).map(|i| self.mul(x.0[i], y.0[k - i])).collect();
+            let hi: Vec<Expr> = (k + 1..4).map(|i| self.mul(x.0[i], y.0[k + 4 - i])).collect();
+            let mut acc = lo[0];
+            for &t in &lo[1..] {
+                acc = self.add(acc, t);
+            }
+            if !hi.is_empty() {
+                let mut h = hi[0];
+                for &t in &hi[1..] {
+                    h = self.add(h, t);
+                }
+                let w = self.constant(EF_W);
+                let hw = self.mul(h, w);
+                acc = self.add(acc, hw);
+            }
+            out[k] = acc;
+        }
+        ExtExpr(out)
+    }
+    pub fn assert_zero_ext(&mut self, x: ExtExpr) {
+        for c in x.0 {
+            self.assert_zero(c);
+        }
+    }
+    pub fn assert_zero_ext_when(&mut self, cond: Expr, x: ExtExpr) {
+        for c in x.0 {
+            self.assert_zero_when(cond, c);
+        }
+    }
+
+    pub fn max_constraint_degree(&self) -> u32 {
+        self.constraints.iter().map(|&c| self.degs[c as usize]).max().unwrap_or(0)
+    }
+    /// Version 3 with aux columns, challenges or exposed words; else version 2 / 1 as `serialize_constraints_pre`.
+    pub fn tape(&self) -> Vec<u32> {
+        let v3 = self.aux_width != 0 || self.n_challenges != 0 || self.n_exposed != 0;
+        let version = if v3 { 3 } else if self.preprocessed_width != 0 { 2 } else { 1 };
+        let mut tape = vec![TAPE_MAGIC, version, self.width, self.n_public, self.nodes.len() as u32, self.constraints.len() as u32];
+        if v3 {
+            tape.extend_from_slice(&[self.preprocessed_width, self.aux_width, self.n_challenges, self.n_exposed]);
+        } else if self.preprocessed_width != 0 {
+            tape.push(self.preprocessed_width);
+        }
+        for n in &self.nodes {
+            tape.extend_from_slice(n);
+        }
+        tape.extend_from_slice(&self.constraints);
+        tape
+    }
+}
+
+/// A term of a LogUp interaction: `Const(canonical value)` or `Col(main column)`, read on the local row.
+#[derive(Clone, Copy, Debug)]
+pub enum LogUpTerm {
+    Const(u32),
+    Col(u32),
+}
+
+/// LogUp over the main trace, from the spec `ts_logup_aux_build` takes: two challenges gamma, beta; interaction i
+/// has d_i = gamma + sum_j beta^j v_ij and the fraction m_i / d_i; group g pairs interactions 2g and 2g+1; aux
+/// columns 4g..4g+3 hold the group's sum h_g, the last four the exclusive running sum phi, the four exposed words
+/// the total S.  `eval` emits `h_g d_a d_b - m_a d_b - m_b d_a = 0`, `is_first phi = 0`,
+/// `is_transition (phi' - phi - sum h_g) = 0`, `is_last (phi + sum h_g - S) = 0`.  The statement S = 0 is the
+/// caller's to check after `ts_verify_aux`.
+pub struct LogUp {
+    pub interactions: Vec<(LogUpTerm, Vec<LogUpTerm>)>,
+}
+
+impl LogUp {
+    pub const N_CHALLENGES: u32 = 2;
+    pub const N_EXPOSED: u32 = 4;
+    pub fn n_groups(&self) -> u32 { (self.interactions.len() as u32 + 1) / 2 }
+    pub fn aux_width(&self) -> u32 { 4 * (self.n_groups() + 1) }
+
+    pub fn eval(&self, b: &mut AuxAirBuilder) {
+        let (gamma, beta) = (b.challenge(0), b.challenge(1));
+        let term = |b: &mut AuxAirBuilder, t: LogUpTerm| match t {
+            LogUpTerm::Const(v) => b.constant(v as u64),
+            LogUpTerm::Col(c) => b.main(0, c),
+        };
+        let n_pow = self.interactions.iter().map(|(_, v)| v.len()).max().unwrap_or(1);
+        let one = b.constant(1);
+        let mut beta_pow = vec![b.ext_from_base(one)];
+        for _ in 1..n_pow {
+            let next = b.ext_mul(*beta_pow.last().unwrap(), beta);
+            beta_pow.push(next);
+        }
+        let (mut dens, mut mults) = (Vec::new(), Vec::new());
+        for (m, values) in &self.interactions {
+            let mut d = gamma;
+            for (j, v) in values.iter().enumerate() {
+                let x = term(b, *v);
+                let t = b.ext_mul_base(beta_pow[j], x);
+                d = b.ext_add(d, t);
+            }
+            dens.push(d);
+            mults.push(term(b, *m));
+        }
+        let g_count = self.n_groups();
+        let ext_at = |b: &mut AuxAirBuilder, off: u32, first: u32| ExtExpr([0, 1, 2, 3].map(|k| b.aux(off, first + k)));
+        let mut total: Option<ExtExpr> = None;
+        for g in 0..g_count {
+            let h = ext_at(b, 0, 4 * g);
+            let (ia, ib) = (2 * g as usize, 2 * g as usize + 1);
+            let hd = b.ext_mul(h, dens[ia]);
+            if ib < dens.len() {
+                let t1 = b.ext_mul(hd, dens[ib]);
+                let t2 = b.ext_mul_base(dens[ib], mults[ia]);
+                let t3 = b.ext_sub(t1, t2);
+                let t4 = b.ext_mul_base(dens[ia], mults[ib]);
+                let c = b.ext_sub(t3, t4);
+                b.assert_zero_ext(c);
+            } else {
+                let m = b.ext_from_base(mults[ia]);
+                let c = b.ext_sub(hd, m);
+                b.assert_zero_ext(c);
+            }
+            total = Some(match total {
+                None => h,
+                Some(t) => b.ext_add(t, h),
+            });
+        }
+        let total = total.expect("LogUp: no interactions");
+        let phi = ext_at(b, 0, 4 * g_count);
+        let phi_next = ext_at(b, 1, 4 * g_count);
+        let s = ExtExpr([0, 1, 2, 3].map(|k| b.exposed(k)));
+        let first = b.is_first_row();
+        b.assert_zero_ext_when(first, phi);
+        let transition = b.is_transition();
+        let step = b.ext_sub(phi_next, phi);
+        let c = b.ext_sub(step, total);
+        b.assert_zero_ext_when(transition, c);
+        let last = b.is_last_row();
+        let end = b.ext_add(phi, total);
+        let c = b.ext_sub(end, s);
+        b.assert_zero_ext_when(last, c);
+    }
+}

@@ -22,6 +22,38 @@ pub struct ts_air_options {
     pub reserved: u32,
 }
 
+/// `ts_logup_term`: kind 0 = the canonical constant `value`, 1 = main column `value` (local row).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_logup_term {
+    pub kind: u32,
+    pub value: u32,
+}
+
+/// `ts_logup_interaction`: the multiplicity and the tuple of values of one interaction.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_logup_interaction {
+    pub multiplicity: ts_logup_term,
+    pub n_values: u32,
+    pub values: *const ts_logup_term,
+}
+
+/// `ts_logup_spec` (struct_size first).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_logup_spec {
+    pub struct_size: u32,
+    pub n_interactions: u32,
+    pub interactions: *const ts_logup_interaction,
+}
+
+/// `ts_aux_fn`: the aux source of `ts_prove_aux` (user, ctx, live trace, challenge words, n_challenges, aux_out,
+/// exposed_out) -> status.  `None` for an AIR without aux columns.
+pub type ts_aux_fn = Option<
+    unsafe extern "C" fn(*mut c_void, *mut ts_ctx, *const ts_matrix, *const u32, u32, *mut *mut ts_matrix, *mut u32) -> ts_status,
+>;
+
 /// `ts_trace_format` (struct_size first): how the host holds a trace (packed columns, Montgomery words).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -212,6 +244,24 @@ extern "C" {
     pub fn ts_check_constraints_pre(ctx: *mut ts_ctx, air: *const ts_air, preprocessed: *const ts_matrix,
                                     trace: *const ts_matrix, public_values: *const u32, n_public: u32,
                                     first_violation: *mut i64) -> ts_status;
+    // challenge-phase (aux) columns, tape version 3, and the LogUp builder (include/tapstark.h)
+    pub fn ts_air_aux_info(air: *const ts_air, aux_width: *mut u32, n_challenges: *mut u32, n_exposed: *mut u32) -> ts_status;
+    pub fn ts_quotient_chunks_aux(ctx: *mut ts_ctx, aux_data: *const ts_pcs_data, trace_data: *const ts_pcs_data,
+                                  log_blowup: u32, air: *const ts_air, public_values: *const u32, n_public: u32,
+                                  challenges: *const u32, exposed: *const u32, alpha: *const u32,
+                                  chunks_out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_check_constraints_aux(ctx: *mut ts_ctx, air: *const ts_air, aux: *const ts_matrix, trace: *const ts_matrix,
+                                    public_values: *const u32, n_public: u32, challenges: *const u32,
+                                    exposed: *const u32, first_violation: *mut i64) -> ts_status;
+    pub fn ts_prove_aux(ctx: *mut ts_ctx, cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
+                        trace: *mut ts_matrix, public_values: *const u32, n_public: u32, aux_fn: ts_aux_fn,
+                        user: *mut c_void, proof_out: *mut u32, cap_words: usize, n_words_out: *mut usize) -> ts_status;
+    pub fn ts_verify_aux(cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger, proof: *const u32,
+                         n_words: usize, public_values: *const u32, n_public: u32, exposed_out: *mut u32,
+                         cap_exposed: u32, verdict: *mut c_int) -> ts_status;
+    pub fn ts_logup_aux_width(spec: *const ts_logup_spec, aux_width: *mut u32) -> ts_status;
+    pub fn ts_logup_aux_build(ctx: *mut ts_ctx, spec: *const ts_logup_spec, trace: *const ts_matrix,
+                              challenges: *const u32, aux_out: *mut *mut ts_matrix, exposed_out: *mut u32) -> ts_status;
     pub fn ts_proof_to_postcard(proof: *const u32, n_words: usize, out: *mut u8, cap_bytes: usize,
                                 n_bytes_out: *mut usize) -> ts_status;
     /// tspf_version: 0 infer, 1 / 2 explicit (a taptree proof with one query needs 2)

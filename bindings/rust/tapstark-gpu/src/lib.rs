@@ -29,7 +29,7 @@ pub mod proof;
 pub mod prove;
 pub mod tap;
 
-pub use air::serialize_constraints;
+pub use air::{serialize_constraints, AuxAirBuilder, ExtExpr, LogUp, LogUpTerm};
 pub use comm::{prove_gpu_sharded, rccl_unique_id, RcclComm};
 pub use context::{DeviceMatrix, GpuChallenger, GpuContext, MONTY_BITS};
 pub use pcs::{FriConfig, GpuDft, GpuFriPcs, GpuPcsError, GpuProverData};

@@ -210,7 +210,22 @@ ts_status ts_matrix_bit_reverse_rows(ts_ctx* ctx, const ts_matrix* in, ts_matrix
  *   10 PREP(a=offset 0|1, b=column < preprocessed_width).
  * Version 1 is accepted and lowered exactly as before; a version-2 tape with preprocessed_width 0 behaves in
  * every call as the version-1 tape with the same nodes.  TS_ERR_INVALID: PREP in a version-1 tape, a column >=
- * preprocessed_width, an offset > 1, a word count that does not match the header, width 0. */
+ * preprocessed_width, an offset > 1, a word count that does not match the header, width 0.
+ * Version 3 (build-defined; the reference has one trace phase), for an AIR with challenge-phase (aux) columns --
+ * columns that depend on verifier challenges drawn after the main trace is committed (LogUp and its relatives):
+ *   [0]=0x54415354 [1]=3 [2]=width [3]=n_public [4]=n_nodes [5]=n_constraints [6]=preprocessed_width
+ *   [7]=aux_width [8]=n_challenges [9]=n_exposed, then nodes and constraints, with three more ops:
+ *   11 AUX(a=offset 0|1, b=column < aux_width)   degree multiple 1, like a main variable
+ *   12 CHALLENGE(a=word index < 4 n_challenges)  degree multiple 0, like a public value
+ *   13 EXPOSED(a=index < n_exposed)              degree multiple 0
+ * aux_width counts base-field columns, n_challenges extension elements (four words each), n_exposed base words.
+ * An extension-valued constraint is four base constraints (tapstark_air.hpp ExtExpr).  TS_ERR_INVALID: one of
+ * these ops in a version-1 or version-2 tape, an index out of range, an offset > 1.  Lowering: AUX takes the
+ * LOAD operands PREP takes (a = 2, 3), CHALLENGE k the public slot n_public + k, EXPOSED e the slot n_public +
+ * 4 n_challenges + e; the kernels see (aux LDE, trace LDE) where they see (key LDE, trace LDE), and the vector
+ * public values ++ challenges ++ exposed.  A tape with preprocessed_width > 0 AND aux_width > 0 compiles (degree
+ * rules, host use), but every proving call returns TS_ERR_UNSUPPORTED for it: a third matrix in the kernels is
+ * not built yet. */
 /* ctx == NULL builds a host-only AIR (degree rules + verifier use; no kernels) */
 ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out);
 /* get_log_quotient_degree, uni-stark/src/symbolic_builder.rs:15-32 */
@@ -762,6 +777,57 @@ ts_status ts_bench_alu(ts_ctx* ctx, int kind, double* units_per_second);
  * working-set size. */
 ts_status ts_bench_stage(ts_ctx* ctx, int stage, unsigned log_n, uint32_t width, unsigned log_blowup,
                          uint32_t reps, double* ms_per_rep);
+
+/* ------------------------------------------------------------------ challenge-phase (aux) columns
+ * An AIR of tape version 3 is proved in two phases (build-defined like the preprocessed prove; reference
+ * prover.rs:46 stops at one).  ts_prove_aux: (1) commit the trace, observe its root; (2) sample n_challenges
+ * extension elements as alpha is sampled; (3) call `aux_fn` with the still-live trace and the challenge words;
+ * it returns the height x aux_width aux matrix (row-major, made on `ctx`; consumed) and n_exposed words;
+ * (4) commit the aux matrix (natural domain), observe its root, then each exposed word; (5) alpha, the quotient
+ * over (aux LDE, trace LDE) with public values ++ challenges ++ exposed; (6) zeta; (7) open three rounds: aux at
+ * {zeta, zeta omega}, trace at {zeta, zeta omega}, chunks at {zeta}.  Proof = TSPF v4; it
+ * has no postcard form (TS_ERR_UNSUPPORTED).
+ * A non-zero status from the callback ends the call with that status, and the last error names the callback.
+ * An aux matrix of another shape or context: TS_ERR_INVALID.  The trace is consumed as by ts_prove.
+ * For an AIR with aux_width 0, aux_fn must be NULL and the proof is that of ts_prove but for the header.
+ * ts_verify_aux (host only) checks the proof and hands back the exposed words; the STATEMENT about them (for
+ * LogUp: "the sum is zero") is the caller's to check afterwards.  A proof of another TSPF version (*verdict = 9)
+ * or with other header words than the AIR's (*verdict = 1) is refused as an argument, TS_ERR_INVALID.
+ * Every call that takes no aux source returns TS_ERR_UNSUPPORTED for an AIR with aux_width > 0. */
+typedef ts_status (*ts_aux_fn)(void* user, ts_ctx* ctx, const ts_matrix* trace /* not consumed */,
+                               const uint32_t* challenges /* 4*n_challenges canonical words */, uint32_t n_challenges,
+                               ts_matrix** aux_out /* consumed by the prover */, uint32_t* exposed_out);
+ts_status ts_air_aux_info(const ts_air* air, uint32_t* aux_width, uint32_t* n_challenges, uint32_t* n_exposed);
+/* aux_data: the committed aux trace (one matrix, ts_pcs_commit on the natural domain); NULL iff aux_width 0 */
+ts_status ts_quotient_chunks_aux(ts_ctx* ctx, const ts_pcs_data* aux_data, const ts_pcs_data* trace_data,
+                                 uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
+                                 uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                                 const uint32_t alpha[4], ts_matrix** chunks_out);
+/* aux: the uploaded row-major aux matrix of the trace's height; NULL iff aux_width 0 */
+ts_status ts_check_constraints_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* aux, const ts_matrix* trace,
+                                   const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                   const uint32_t* exposed, int64_t* first_violation);
+ts_status ts_prove_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                       ts_matrix* trace /* consumed */, const uint32_t* public_values, uint32_t n_public,
+                       ts_aux_fn aux_fn, void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out);
+ts_status ts_verify_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal, const uint32_t* proof,
+                        size_t n_words, const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
+                        uint32_t cap_exposed, int* verdict);
+
+/* LogUp aux columns built on the device (csrc/logup.hip).  Two challenges gamma, beta.  Interaction i on row r
+ * has the denominator d_i = gamma + sum_j beta^j v_ij(r) and the fraction m_i(r) / d_i.  Interactions are paired:
+ * group g holds 2g and 2g+1 (the last group one if K is odd).  Aux columns 4g .. 4g+3 hold h_g(r), the group's
+ * sum; the last four hold phi(r) = sum_{r' < r} sum_g h_g(r'), phi(0) = 0; the four exposed words are
+ * S = phi(n-1) + sum_g h_g(n-1).  Limits (TS_ERR_INVALID): 1 <= K <= 16 interactions, 1 <= n_values <= 8, columns
+ * inside the trace, canonical constants.  A zero denominator gives TS_ERR_INVARIANT with the first row and
+ * interaction in the last error, and no output.  TS_LOGUP_BLOCK_ROWS (1 .. 1024, read on every call) shrinks the
+ * rows one workgroup owns: a test knob. */
+typedef struct { uint32_t kind /* 0 constant (canonical), 1 main column, local row */; uint32_t value; } ts_logup_term;
+typedef struct { ts_logup_term multiplicity; uint32_t n_values; const ts_logup_term* values; } ts_logup_interaction;
+typedef struct { uint32_t struct_size, n_interactions; const ts_logup_interaction* interactions; } ts_logup_spec;
+ts_status ts_logup_aux_width(const ts_logup_spec* spec, uint32_t* aux_width);  /* 4 * (ceil(K/2) + 1) */
+ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* trace,
+                             const uint32_t challenges[8], ts_matrix** aux_out, uint32_t exposed_out[4]);
 
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);

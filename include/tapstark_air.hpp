@@ -24,7 +24,10 @@ constexpr uint32_t P = 0x78000001u;  // basic/src/field/mod.rs:45
 constexpr uint32_t TAPE_MAGIC = 0x54415354u;
 enum Op : uint32_t { CONST = 0, MAIN = 1, PUBLIC = 2, IS_FIRST = 3, IS_LAST = 4, IS_TRANSITION = 5,
                      ADD = 6, SUB = 7, NEG = 8, MUL = 9,
-                     PREP = 10 };  // version-2 tapes: Entry::Preprocessed { offset }, symbolic_variable.rs:9-15
+                     PREP = 10,  // version-2 tapes: Entry::Preprocessed { offset }, symbolic_variable.rs:9-15
+                     // version-3 tapes (build-defined: challenge-phase columns, include/tapstark.h)
+                     AUX = 11, CHALLENGE = 12, EXPOSED = 13 };
+constexpr uint32_t EF_W = 11;  // EF4 = F[x] / (x^4 - 11)
 
 class Builder;
 
@@ -42,18 +45,27 @@ private:
 };
 
 class Filtered;
+struct ExtExpr;
 
 class Builder {
 public:
     // preprocessed_width > 0: an AIR with preprocessed (fixed) columns, symbolic_builder.rs:68-99; its variables
     // come first, as there, and the tape is version 2
-    Builder(uint32_t width, uint32_t num_public_values, uint32_t preprocessed_width = 0)
-        : width_(width), n_public_(num_public_values), prep_width_(preprocessed_width) {
+    // aux_width / n_challenges / n_exposed > 0: an AIR with challenge-phase columns; their variables come last and
+    // the tape is version 3
+    Builder(uint32_t width, uint32_t num_public_values, uint32_t preprocessed_width = 0, uint32_t aux_width = 0,
+            uint32_t n_challenges = 0, uint32_t n_exposed = 0)
+        : width_(width), n_public_(num_public_values), prep_width_(preprocessed_width), aux_width_(aux_width),
+          n_challenges_(n_challenges), n_exposed_(n_exposed) {
         for (uint32_t off = 0; off < 2; off++)
             for (uint32_t c = 0; c < preprocessed_width; c++) prep_[off].push_back(node(PREP, off, c, 1));
         for (uint32_t off = 0; off < 2; off++)
             for (uint32_t c = 0; c < width; c++) rows_[off].push_back(node(MAIN, off, c, 1));
         for (uint32_t i = 0; i < num_public_values; i++) public_.push_back(node(PUBLIC, i, 0, 0));
+        for (uint32_t off = 0; off < 2; off++)
+            for (uint32_t c = 0; c < aux_width; c++) aux_[off].push_back(node(AUX, off, c, 1));
+        for (uint32_t k = 0; k < 4 * n_challenges; k++) challenge_words_.push_back(node(CHALLENGE, k, 0, 0));
+        for (uint32_t e = 0; e < n_exposed; e++) exposed_.push_back(node(EXPOSED, e, 0, 0));
     }
     // builder.main().row_slice(0 | 1)
     const std::vector<Expr>& local() const { return rows_[0]; }
@@ -61,6 +73,11 @@ public:
     // PairBuilder::preprocessed().row_slice(offset), symbolic_builder.rs:144-148
     const std::vector<Expr>& preprocessed(uint32_t offset) const { return prep_[offset & 1]; }
     const std::vector<Expr>& public_values() const { return public_; }
+    // the challenge-phase trace's row slices, challenge k as an extension element, the exposed base words
+    const std::vector<Expr>& aux(uint32_t offset) const { return aux_[offset & 1]; }
+    ExtExpr challenge(uint32_t k) const;
+    const std::vector<Expr>& exposed() const { return exposed_; }
+    void assert_zero_ext(const ExtExpr& x);  // FOUR base constraints
     Expr constant(uint64_t v) { return node(CONST, (uint32_t)(v % P), 0, 0); }
     Expr is_first_row() { return node(IS_FIRST, 0, 0, 1); }    // symbolic_expression.rs:45
     Expr is_last_row() { return node(IS_LAST, 0, 0, 1); }      // :46
@@ -86,11 +103,15 @@ public:
         return k;
     }
     // [magic, version, width, n_public, n_nodes, n_constraints, nodes (op, a, b)..., constraint ids...];
-    // version 2 (preprocessed_width > 0) has the preprocessed width as a seventh header word
+    // version 2 (preprocessed_width > 0) has the preprocessed width as a seventh header word; version 3 (aux
+    // columns, challenges or exposed words) a ten-word header: ..., preprocessed_width, aux_width, n_challenges,
+    // n_exposed
     std::vector<uint32_t> tape() const {
-        std::vector<uint32_t> t = {TAPE_MAGIC, prep_width_ ? 2u : 1u, width_, n_public_, (uint32_t)nodes_.size(),
-                                   (uint32_t)constraints_.size()};
-        if (prep_width_) t.push_back(prep_width_);
+        const bool v3 = aux_width_ || n_challenges_ || n_exposed_;
+        std::vector<uint32_t> t = {TAPE_MAGIC, v3 ? 3u : prep_width_ ? 2u : 1u, width_, n_public_,
+                                   (uint32_t)nodes_.size(), (uint32_t)constraints_.size()};
+        if (v3) t.insert(t.end(), {prep_width_, aux_width_, n_challenges_, n_exposed_});
+        else if (prep_width_) t.push_back(prep_width_);
         for (auto& n : nodes_) {
             t.push_back(std::get<0>(n));
             t.push_back(std::get<1>(n));
@@ -113,12 +134,12 @@ public:
     uint32_t degree(Expr e) const { return degs_[e.id()]; }
 
 private:
-    uint32_t width_, n_public_, prep_width_;
+    uint32_t width_, n_public_, prep_width_, aux_width_, n_challenges_, n_exposed_;
     std::vector<std::tuple<uint32_t, uint32_t, uint32_t>> nodes_;
     std::vector<uint32_t> degs_;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> cse_;
     std::vector<uint32_t> constraints_;
-    std::vector<Expr> rows_[2], prep_[2], public_;
+    std::vector<Expr> rows_[2], prep_[2], public_, aux_[2], challenge_words_, exposed_;
 };
 
 // degree rules: symbolic_expression.rs:137 (add), :182 (sub), :227 (mul)
@@ -141,11 +162,78 @@ inline Expr operator+(Expr x, uint64_t c) { return x + x.builder()->constant(c);
 inline Expr operator-(Expr x, uint64_t c) { return x - x.builder()->constant(c); }
 inline Expr operator*(Expr x, uint64_t c) { return x * x.builder()->constant(c); }
 
+// An extension-field expression: four coefficients over x^4 - 11.  assert_zero_ext emits FOUR base constraints,
+// so an extension-valued constraint is an ordinary constraint of the tape language.  Every operator builds its
+// nodes in one fixed order (the Python ExtExpr's), so both front ends give the same tape.
+struct ExtExpr {
+    Expr c[4];
+    static ExtExpr from_base(Expr x) {
+        const Expr zero = x.builder()->constant(0);
+        return ExtExpr{{x, zero, zero, zero}};
+    }
+    static ExtExpr from_base(Builder& b, uint64_t v) {
+        const Expr x = b.constant(v);
+        return from_base(x);
+    }
+    ExtExpr mul_base(Expr x) const {
+        ExtExpr r;
+        for (int k = 0; k < 4; k++) r.c[k] = c[k] * x;
+        return r;
+    }
+};
+inline ExtExpr operator+(const ExtExpr& x, const ExtExpr& y) {
+    ExtExpr r;
+    for (int k = 0; k < 4; k++) r.c[k] = x.c[k] + y.c[k];
+    return r;
+}
+inline ExtExpr operator-(const ExtExpr& x, const ExtExpr& y) {
+    ExtExpr r;
+    for (int k = 0; k < 4; k++) r.c[k] = x.c[k] - y.c[k];
+    return r;
+}
+inline ExtExpr operator-(const ExtExpr& x, Expr y) { return x - ExtExpr::from_base(y); }
+inline ExtExpr operator-(const ExtExpr& x) {
+    ExtExpr r;
+    for (int k = 0; k < 4; k++) r.c[k] = -x.c[k];
+    return r;
+}
+inline ExtExpr operator*(const ExtExpr& x, Expr y) { return x.mul_base(y); }
+// r_k = sum_{i+j=k} a_i b_j + 11 sum_{i+j=k+4} a_i b_j
+inline ExtExpr operator*(const ExtExpr& x, const ExtExpr& y) {
+    ExtExpr r;
+    for (int k = 0; k < 4; k++) {
+        std::vector<Expr> lo, hi;
+        for (int i = 0; i <= k; i++) lo.push_back(x.c[i] * y.c[k - i]);
+        for (int i = k + 1; i < 4; i++) hi.push_back(x.c[i] * y.c[k + 4 - i]);
+        Expr acc = lo[0];
+        for (size_t t = 1; t < lo.size(); t++) acc = acc + lo[t];
+        if (!hi.empty()) {
+            Expr h = hi[0];
+            for (size_t t = 1; t < hi.size(); t++) h = h + hi[t];
+            const Expr w = h.builder()->constant(EF_W);
+            const Expr hw = h * w;
+            acc = acc + hw;
+        }
+        r.c[k] = acc;
+    }
+    return r;
+}
+inline ExtExpr Builder::challenge(uint32_t k) const {
+    return ExtExpr{{challenge_words_.at(4 * k), challenge_words_.at(4 * k + 1), challenge_words_.at(4 * k + 2),
+                    challenge_words_.at(4 * k + 3)}};
+}
+inline void Builder::assert_zero_ext(const ExtExpr& x) {
+    for (int k = 0; k < 4; k++) assert_zero(x.c[k]);
+}
+
 // p3-air FilteredAirBuilder: when(c).assert_zero(x) => assert_zero(c * x)
 class Filtered {
 public:
     Filtered(Builder* b, Expr cond) : b_(b), cond_(cond) {}
     void assert_zero(Expr x) { b_->assert_zero(cond_ * x); }
+    void assert_zero_ext(const ExtExpr& x) {
+        for (int k = 0; k < 4; k++) assert_zero(x.c[k]);
+    }
     void assert_eq(Expr x, Expr y) { assert_zero(x - y); }
     void assert_one(Expr x) { assert_zero(x - 1); }
     Filtered when(Expr c) { return Filtered(b_, cond_ * c); }
@@ -159,6 +247,98 @@ inline Filtered Builder::when(Expr c) { return Filtered(this, c); }
 inline Filtered Builder::when_first_row() { return when(is_first_row()); }
 inline Filtered Builder::when_last_row() { return when(is_last_row()); }
 inline Filtered Builder::when_transition() { return when(is_transition()); }
+
+
+// ---- LogUp over the main trace (include/tapstark.h, csrc/logup.hip): the constraints that match the aux columns
+// ts_logup_aux_build makes, from the same interaction spec.  Two challenges gamma, beta; interaction i has
+// d_i = gamma + sum_j beta^j v_ij and the fraction m_i / d_i; group g pairs interactions 2g and 2g+1; aux columns
+// 4g .. 4g+3 hold the group's sum h_g, the last four the exclusive running sum phi, the four exposed words S:
+//   h_g d_a d_b - m_a d_b - m_b d_a = 0 (degree 3; h_g d_a - m_a = 0 for an odd last group)
+//   is_first phi = 0,  is_transition (phi' - phi - sum_g h_g) = 0,  is_last (phi + sum_g h_g - S) = 0
+// No d is zero, so these determine the aux matrix from trace and challenges.  The statement "S = 0" is the
+// caller's to check after ts_verify_aux.
+struct LogUpTerm {
+    uint32_t kind;   // 0: the canonical constant `value`; 1: main column `value`, local row
+    uint32_t value;
+};
+struct LogUpInteraction {
+    LogUpTerm multiplicity;
+    std::vector<LogUpTerm> values;
+};
+class LogUp {
+public:
+    static constexpr uint32_t n_challenges = 2, n_exposed = 4;
+    explicit LogUp(std::vector<LogUpInteraction> interactions) : its_(std::move(interactions)) {
+        if (its_.empty()) throw std::invalid_argument("LogUp: no interactions");
+    }
+    const std::vector<LogUpInteraction>& interactions() const { return its_; }
+    uint32_t n_groups() const { return ((uint32_t)its_.size() + 1) / 2; }
+    uint32_t aux_width() const { return 4 * (n_groups() + 1); }
+
+    void eval(Builder& b) const {
+        const auto& main = b.local();
+        const auto &aux = b.aux(0), &aux_next = b.aux(1);
+        const ExtExpr gamma = b.challenge(0), beta = b.challenge(1);
+        auto term = [&](LogUpTerm t) { return t.kind == 0 ? b.constant(t.value) : main.at(t.value); };
+        size_t n_pow = 0;
+        for (auto& it : its_) n_pow = it.values.size() > n_pow ? it.values.size() : n_pow;
+        std::vector<ExtExpr> beta_pow{ExtExpr::from_base(b, 1)};
+        for (size_t j = 1; j < n_pow; j++) {
+            const ExtExpr next = beta_pow.back() * beta;
+            beta_pow.push_back(next);
+        }
+        std::vector<ExtExpr> dens;
+        std::vector<Expr> mults;
+        for (auto& it : its_) {
+            ExtExpr d = gamma;
+            for (size_t j = 0; j < it.values.size(); j++) {
+                const Expr v = term(it.values[j]);
+                const ExtExpr t = beta_pow[j].mul_base(v);
+                d = d + t;
+            }
+            dens.push_back(d);
+            mults.push_back(term(it.multiplicity));
+        }
+        const uint32_t G = n_groups();
+        auto ext_at = [](const std::vector<Expr>& row, uint32_t first) {
+            return ExtExpr{{row.at(first), row.at(first + 1), row.at(first + 2), row.at(first + 3)}};
+        };
+        ExtExpr total;
+        for (uint32_t g = 0; g < G; g++) {
+            const ExtExpr h = ext_at(aux, 4 * g);
+            const size_t ia = 2 * g, ib = 2 * g + 1;
+            const ExtExpr hd = h * dens[ia];
+            if (ib < dens.size()) {
+                const ExtExpr t1 = hd * dens[ib];
+                const ExtExpr t2 = dens[ib].mul_base(mults[ia]);
+                const ExtExpr t3 = t1 - t2;
+                const ExtExpr t4 = dens[ia].mul_base(mults[ib]);
+                b.assert_zero_ext(t3 - t4);
+            } else {
+                b.assert_zero_ext(hd - mults[ia]);
+            }
+            total = g == 0 ? h : total + h;
+        }
+        const ExtExpr phi = ext_at(aux, 4 * G), phi_next = ext_at(aux_next, 4 * G), S = ext_at(b.exposed(), 0);
+        {
+            Filtered f = b.when_first_row();
+            f.assert_zero_ext(phi);
+        }
+        {
+            Filtered f = b.when_transition();
+            const ExtExpr step = phi_next - phi;
+            f.assert_zero_ext(step - total);
+        }
+        {
+            Filtered f = b.when_last_row();
+            const ExtExpr end = phi + total;
+            f.assert_zero_ext(end - S);
+        }
+    }
+
+private:
+    std::vector<LogUpInteraction> its_;
+};
 
 }  // namespace air
 }  // namespace ts

@@ -1,7 +1,7 @@
 """tap-stark hot path, MI355X-native: host-side mirror of the reference's uni-stark/fri
 prover interface over the C-ABI HIP library (include/tapstark.h)."""
 from . import air, airs  # noqa: F401
-from .air import (BaseAir, SymbolicAirBuilder, air_tape, get_log_quotient_degree,  # noqa: F401
+from .air import (BaseAir, ExtExpr, LogUp, SymbolicAirBuilder, air_tape, get_log_quotient_degree,  # noqa: F401
                   get_max_constraint_degree, get_symbolic_constraints)
 from .stark import (BatchResult, BfChallenger, Blake3Mmcs, CompiledAir, Context, DeviceMatrix, FriConfig, PcsData, PinnedHostBytes, PreprocessedKey, PinnedHostMatrix,  # noqa: F401
                     Proof, Radix2Dft, StarkConfig, TraceFormat, TwoAdicFriPcs, VerificationError, check_constraints,

@@ -15,6 +15,11 @@ The DAG is serialised into the "tape" the C ABI takes (``include/tapstark.h``, T
 ``[magic, version, width, n_public, n_nodes, n_constraints, nodes(op,a,b)..., constraint ids...]``;
 an AIR with preprocessed columns (``PairBuilder::preprocessed()``, symbolic_builder.rs:144-148) gives a
 version-2 tape: one more header word, ``preprocessed_width``, and the leaf ``OP_PREP(offset, column)``.
+An AIR with challenge-phase columns (columns that depend on verifier challenges drawn after the main trace is
+committed: LogUp and its relatives; build-defined, the reference has one phase) gives a version-3 tape: a
+10-word header ``[..., preprocessed_width, aux_width, n_challenges, n_exposed]`` and the leaves
+``OP_AUX(offset, column)``, ``OP_CHALLENGE(word)``, ``OP_EXPOSED(index)``.  ``ExtExpr`` writes extension-valued
+constraints as four base constraints; ``LogUp`` emits the LogUp constraints from an interaction spec.
 Python is only the capture front-end; the tape is evaluated by HIP kernels.
 """
 from __future__ import annotations
@@ -27,6 +32,8 @@ TAPE_MAGIC = 0x54415354
 OP_CONST, OP_MAIN, OP_PUBLIC, OP_IS_FIRST, OP_IS_LAST, OP_IS_TRANSITION = 0, 1, 2, 3, 4, 5
 OP_ADD, OP_SUB, OP_NEG, OP_MUL = 6, 7, 8, 9
 OP_PREP = 10  # version-2 tapes: Entry::Preprocessed { offset }, symbolic_variable.rs:9-15
+OP_AUX, OP_CHALLENGE, OP_EXPOSED = 11, 12, 13  # version-3 tapes (include/tapstark.h)
+EF_W = 11  # EF4 = F[x] / (x^4 - 11)
 
 
 class SymbolicExpression:
@@ -108,17 +115,83 @@ class FilteredAirBuilder:
     def assert_one(self, x):
         self.assert_zero(self.inner._lift(x) - 1)
 
+    def assert_zero_ext(self, x):
+        for c in x.c:
+            self.assert_zero(c)
+
     def when(self, c):
         return FilteredAirBuilder(self.inner, self.condition * c)
+
+
+class ExtExpr:
+    """An extension-field expression: four ``SymbolicExpression`` coefficients over x^4 - 11.  ``assert_zero_ext``
+    emits FOUR base constraints, so an extension-valued constraint is an ordinary constraint of the tape language
+    and nothing downstream learns a new accumulation rule."""
+
+    __slots__ = ("b", "c")
+
+    def __init__(self, b: "SymbolicAirBuilder", coeffs):
+        self.b = b
+        self.c = [b._lift(x) for x in coeffs]
+        assert len(self.c) == 4
+
+    @classmethod
+    def from_base(cls, b, x) -> "ExtExpr":
+        return cls(b, [x, 0, 0, 0])
+
+    def _lift(self, o) -> "ExtExpr":
+        return o if isinstance(o, ExtExpr) else ExtExpr.from_base(self.b, o)
+
+    def __add__(self, o):
+        o = self._lift(o)
+        return ExtExpr(self.b, [x + y for x, y in zip(self.c, o.c)])
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = self._lift(o)
+        return ExtExpr(self.b, [x - y for x, y in zip(self.c, o.c)])
+
+    def __rsub__(self, o):
+        return self._lift(o).__sub__(self)
+
+    def __neg__(self):
+        return ExtExpr(self.b, [-x for x in self.c])
+
+    def mul_base(self, x) -> "ExtExpr":
+        x = self.b._lift(x)
+        return ExtExpr(self.b, [c * x for c in self.c])
+
+    def __mul__(self, o):
+        if not isinstance(o, ExtExpr):
+            return self.mul_base(o)
+        out = []
+        for k in range(4):
+            lo = [self.c[i] * o.c[k - i] for i in range(k + 1)]
+            hi = [self.c[i] * o.c[k + 4 - i] for i in range(k + 1, 4)]
+            acc = lo[0]
+            for t in lo[1:]:
+                acc = acc + t
+            if hi:
+                h = hi[0]
+                for t in hi[1:]:
+                    h = h + t
+                acc = acc + h * EF_W
+            out.append(acc)
+        return ExtExpr(self.b, out)
+
+    __rmul__ = __mul__
 
 
 class SymbolicAirBuilder:
     """reference uni-stark/src/symbolic_builder.rs:68-148."""
 
-    def __init__(self, width: int, num_public_values: int, preprocessed_width: int = 0):
+    def __init__(self, width: int, num_public_values: int, preprocessed_width: int = 0, aux_width: int = 0,
+                 n_challenges: int = 0, n_exposed: int = 0):
         self.width = width
         self.num_public_values = num_public_values
         self.preprocessed_width = preprocessed_width
+        self.aux_width, self.n_challenges, self.n_exposed = aux_width, n_challenges, n_exposed
         self.nodes: list[tuple[int, int, int]] = []
         self._degs: list[int] = []
         self._cse: dict[tuple[int, int, int], int] = {}
@@ -138,6 +211,13 @@ class SymbolicAirBuilder:
             ]
         )
         self._public = [self._node(OP_PUBLIC, i, 0, 0) for i in range(num_public_values)]
+        # version 3, after everything a version-1 or version-2 tape holds (no nodes at all for zero counts)
+        self._aux = _MainWindow(
+            [_Row([self._node(OP_AUX, off, c, 1) for c in range(aux_width)]) for off in (0, 1)]
+        )
+        self._challenges = [ExtExpr(self, [self._node(OP_CHALLENGE, 4 * k + j, 0, 0) for j in range(4)])
+                            for k in range(n_challenges)]
+        self._exposed = [self._node(OP_EXPOSED, e, 0, 0) for e in range(n_exposed)]
 
     # -- DAG -----------------------------------------------------------------
     def _node(self, op, a, b, deg) -> SymbolicExpression:
@@ -166,6 +246,22 @@ class SymbolicAirBuilder:
 
     def public_values(self):
         return self._public
+
+    def aux(self) -> _MainWindow:
+        """The challenge-phase trace: two row slices, as ``main()``."""
+        return self._aux
+
+    def challenges(self):
+        """One ``ExtExpr`` per challenge."""
+        return self._challenges
+
+    def exposed(self):
+        """The exposed base words (wrap four in an ``ExtExpr`` for an extension value)."""
+        return self._exposed
+
+    def assert_zero_ext(self, x: "ExtExpr"):
+        for c in x.c:
+            self.assert_zero(c)
 
     def is_first_row(self):
         return self._node(OP_IS_FIRST, 0, 0, 1)  # symbolic_expression.rs:45
@@ -209,7 +305,10 @@ class SymbolicAirBuilder:
     def tape(self) -> np.ndarray:
         words = [TAPE_MAGIC, 1, self.width, self.num_public_values, len(self.nodes),
                  len(self.constraints)]
-        if self.preprocessed_width:
+        if self.aux_width or self.n_challenges or self.n_exposed:
+            words[1] = 3
+            words += [self.preprocessed_width, self.aux_width, self.n_challenges, self.n_exposed]
+        elif self.preprocessed_width:
             words[1] = 2
             words.append(self.preprocessed_width)
         for op, a, b in self.nodes:
@@ -228,10 +327,10 @@ class BaseAir:
         raise NotImplementedError
 
 
-def get_symbolic_constraints(air: BaseAir, num_public_values: int,
-                             preprocessed_width: int = 0) -> SymbolicAirBuilder:
+def get_symbolic_constraints(air: BaseAir, num_public_values: int, preprocessed_width: int = 0, aux_width: int = 0,
+                             n_challenges: int = 0, n_exposed: int = 0) -> SymbolicAirBuilder:
     """reference uni-stark/src/symbolic_builder.rs:52-64 (returns the builder holding them)."""
-    b = SymbolicAirBuilder(air.width(), num_public_values, preprocessed_width)
+    b = SymbolicAirBuilder(air.width(), num_public_values, preprocessed_width, aux_width, n_challenges, n_exposed)
     air.eval(b)
     return b
 
@@ -250,6 +349,114 @@ def get_log_quotient_degree(air: BaseAir, num_public_values: int, preprocessed_w
     return log2_ceil(d - 1)
 
 
-def air_tape(air: BaseAir, num_public_values: int, preprocessed_width: int = 0) -> np.ndarray:
-    """Version 1 for preprocessed_width 0, version 2 otherwise."""
-    return get_symbolic_constraints(air, num_public_values, preprocessed_width).tape()
+def air_tape(air: BaseAir, num_public_values: int, preprocessed_width: int = 0, aux_width: int = 0,
+             n_challenges: int = 0, n_exposed: int = 0) -> np.ndarray:
+    """Version 1 for preprocessed_width 0, version 2 otherwise; version 3 with aux columns, challenges or
+    exposed words."""
+    return get_symbolic_constraints(air, num_public_values, preprocessed_width, aux_width, n_challenges,
+                                    n_exposed).tape()
+
+
+def aux_dims(air) -> tuple[int, int, int]:
+    """(aux_width, n_challenges, n_exposed) of an AIR class: attributes or methods of those names, 0 if absent."""
+    def get(name):
+        f = getattr(air, name, 0)
+        return int(f() if callable(f) else f)
+    return get("aux_width"), get("n_challenges"), get("n_exposed")
+
+
+# ---------------------------------------------------------------------------------------------- LogUp
+class LogUp:
+    """LogUp over the main trace (include/tapstark.h, csrc/logup.hip).  ``interactions`` is a list of
+    ``(multiplicity, [values...])``; a term is ``("const", canonical value)`` or ``("col", main column)``, read on
+    the local row.  Two challenges gamma, beta; interaction i has d_i = gamma + sum_j beta^j v_ij and the fraction
+    m_i / d_i; group g pairs interactions 2g and 2g+1; aux columns 4g..4g+3 hold the group's sum h_g, the last
+    four the exclusive running sum phi, and the four exposed words the total S.
+
+    ``eval(builder)`` emits the matching constraints; ``aux_source`` is the callable for ``prove(..., aux=...)``
+    (``ts_logup_aux_build``); ``verify`` raises unless the exposed sum is zero."""
+
+    n_challenges = 2
+    n_exposed = 4
+
+    def __init__(self, interactions):
+        self.interactions = [(self._term(m), [self._term(v) for v in vals]) for m, vals in interactions]
+        self.n_groups = (len(self.interactions) + 1) // 2
+        self.aux_width = 4 * (self.n_groups + 1)
+
+    @staticmethod
+    def _term(t):
+        kind, value = t
+        kind = {"const": 0, "col": 1}.get(kind, kind)
+        return int(kind), int(value) % P if kind == 0 else int(value)
+
+    def eval(self, builder) -> None:
+        main = builder.main().row_slice(0)
+        aux, aux_next = builder.aux().row_slice(0), builder.aux().row_slice(1)
+        gamma, beta = builder.challenges()[:2]
+        term = lambda t: builder.constant(t[1]) if t[0] == 0 else main[t[1]]
+        n_pow = max(len(vals) for _, vals in self.interactions)
+        beta_pow = [ExtExpr.from_base(builder, 1)]
+        for _ in range(1, n_pow):
+            beta_pow.append(beta_pow[-1] * beta)
+        dens, mults = [], []
+        for m, vals in self.interactions:
+            d = gamma
+            for j, v in enumerate(vals):
+                d = d + beta_pow[j].mul_base(term(v))
+            dens.append(d)
+            mults.append(term(m))
+        G = self.n_groups
+        total = None
+        for g in range(G):
+            h = ExtExpr(builder, [aux[4 * g + k] for k in range(4)])
+            a, b = 2 * g, 2 * g + 1
+            if b < len(dens):  # h d_a d_b - m_a d_b - m_b d_a = 0
+                builder.assert_zero_ext(h * dens[a] * dens[b] - dens[b].mul_base(mults[a]) - dens[a].mul_base(mults[b]))
+            else:              # h d_a - m_a = 0
+                builder.assert_zero_ext(h * dens[a] - mults[a])
+            total = h if total is None else total + h
+        phi = ExtExpr(builder, [aux[4 * G + k] for k in range(4)])
+        phi_next = ExtExpr(builder, [aux_next[4 * G + k] for k in range(4)])
+        S = ExtExpr(builder, builder.exposed()[:4])
+        builder.when_first_row().assert_zero_ext(phi)
+        builder.when_transition().assert_zero_ext(phi_next - phi - total)
+        builder.when_last_row().assert_zero_ext(phi + total - S)
+
+    def _spec_c(self):
+        """The ``ts_logup_spec`` and the ctypes arrays it points into (keep the tuple alive over the call)."""
+        from . import _lib
+        its = (_lib.LogupInteractionC * len(self.interactions))()
+        keep = []
+        for i, (m, vals) in enumerate(self.interactions):
+            arr = (_lib.LogupTermC * len(vals))(*[_lib.LogupTermC(k, v) for k, v in vals])
+            keep.append(arr)
+            its[i] = _lib.LogupInteractionC(_lib.LogupTermC(*m), len(vals), arr)
+        import ctypes as C
+        return _lib.LogupSpecC(C.sizeof(_lib.LogupSpecC), len(self.interactions), its), (its, keep)
+
+    def build(self, trace, challenges):
+        """``ts_logup_aux_build``: (aux ``DeviceMatrix``, the four exposed words)."""
+        import ctypes as C
+        from . import _lib
+        from .stark import DeviceMatrix
+        ctx = trace.ctx
+        spec, keep = self._spec_c()
+        ch = np.ascontiguousarray(challenges, dtype=np.uint32).reshape(-1)
+        if len(ch) != 8:
+            raise ValueError("LogUp takes two challenges (eight words)")
+        h, exposed = C.c_void_p(), np.zeros(4, dtype=np.uint32)
+        ctx.check(ctx._l.ts_logup_aux_build(ctx.h, C.byref(spec), trace.h, ch.ctypes.data_as(_lib.u32p), C.byref(h),
+                                            exposed.ctypes.data_as(_lib.u32p)))
+        del keep
+        return DeviceMatrix(ctx, h), exposed
+
+    @property
+    def aux_source(self):
+        return self.build
+
+    @staticmethod
+    def verify(exposed) -> None:
+        """The statement of a LogUp argument: the exposed sum is zero."""
+        if any(int(x) != 0 for x in np.asarray(exposed).reshape(-1)):
+            raise ValueError("LogUp: the exposed sum is not zero: the interactions do not balance")

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .air import BaseAir, P
+from .air import BaseAir, LogUp, P
 
 SPLITMIX_SEED = 0x7A957A12
 
@@ -709,3 +709,48 @@ def random_air_case(seed: int):
                     share_pct=(10, 35, 60)[r.below(3)], max_depth=3 + r.below(5))
     log_n = 1 + r.below(6) if width * nc < 20000 else 1 + r.below(3)
     return air, log_n
+
+
+# ---------------------------------------------------------------------------------------------- RangeLookupAir
+# An AIR with challenge-phase columns (tape version 3): a LogUp range check, the smallest member of the class
+# the wide synthetic AIRs stand in for.
+
+
+class RangeLookupAir(BaseAir):
+    """Main columns (value, table, mult); every ``value`` lies in the table ``0 .. n-1`` (n = 2^k rows).
+
+    * first row ``table = 0``, transition ``next.table = local.table + 1``: the table column is the row index
+    * LogUp over two interactions, (+1, value) and (mult, table), where the ``mult`` column holds MINUS the number
+      of rows whose value equals the row's table entry (a field element): sum 1/(gamma + value) +
+      sum mult/(gamma + table) = 0 exactly when the values are a multiset of table entries with those counts.
+
+    The aux columns, challenges and exposed sum are ``LogUp``'s (air.py); the sum being zero is the caller's to
+    check after ``verify`` (``RangeLookupAir.logup.verify``)."""
+
+    logup = LogUp([(("const", 1), [("col", 0)]), (("col", 2), [("col", 1)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 3
+
+    def eval(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        builder.when_first_row().assert_zero(local[1])
+        builder.when_transition().assert_eq(nxt[1], local[1] + 1)
+        self.logup.eval(builder)
+
+
+def generate_range_lookup_trace(n: int, seed: int = SPLITMIX_SEED, outside_row: int | None = None) -> np.ndarray:
+    """(n, 3) canonical u32 satisfying RangeLookupAir; ``outside_row``: that row looks up ``n``, a value outside
+    the table (the proof still verifies, the exposed sum is then non-zero)."""
+    assert n & (n - 1) == 0
+    values = (splitmix64_stream(seed, n) % np.uint64(n)).astype(np.int64)
+    if outside_row is not None:
+        values[outside_row] = n
+    counts = np.bincount(values[values < n], minlength=n).astype(np.int64)
+    out = np.empty((n, 3), dtype=np.uint32)
+    out[:, 0] = values
+    out[:, 1] = np.arange(n)
+    out[:, 2] = (P - counts) % P
+    return out

@@ -15,6 +15,7 @@
 #include "abi_types.hpp"
 #include "blake3.hpp"
 #include "jit.hpp"
+#include "logup.hpp"
 #include "prover_internal.hpp"
 
 // the program as the prover sees it; the handle is const in the prove calls, adopting a finished specialisation is not
@@ -81,16 +82,46 @@ std::vector<uint32_t> public_inputs(const uint32_t* values, uint32_t n) {
 
 // Calls that take no preprocessed key refuse an AIR that needs one, before anything is consumed or launched.
 void no_preprocessed(const ts_air* air, const char* call) {
+    if (air->a.prog().aux_width)
+        throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has challenge-phase (aux) columns; "
+                                                 "prove it with ts_prove_aux (and ts_quotient_chunks_aux, "
+                                                 "ts_check_constraints_aux, ts_verify_aux)").c_str());
     if (air->a.prog().preprocessed_width == 0) return;
     throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has preprocessed columns; prove it with "
                                              "ts_prove_pre (and ts_quotient_chunks_pre, ts_check_constraints_pre, "
                                              "ts_verify_pre)").c_str());
 }
 
+// ts_*_pre calls take no aux source either
+void no_aux(const ts_air* air, const char* call) {
+    if (air->a.prog().aux_width)
+        throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has challenge-phase (aux) columns; "
+                                                 "prove it with ts_prove_aux").c_str());
+}
+// the ts_*_aux calls: aux columns together with a key would be a third matrix in the kernels
+void no_prep_with_aux(const ts_air* air, const char* call) {
+    if (air->a.prog().preprocessed_width)
+        throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": preprocessed columns together with aux "
+                                                 "columns are not supported yet").c_str());
+}
+// public values ++ challenge words ++ exposed words, as the lowered program of a version-3 AIR indexes them
+std::vector<uint32_t> public_slots(const ts::AirProgram& p, const uint32_t* values, uint32_t n, const uint32_t* challenges,
+                                   const uint32_t* exposed) {
+    TS_REQUIRE(n == p.n_public, ts::TS_ERR_INVALID, "wrong number of public values");
+    std::vector<uint32_t> pis = public_inputs(values, n);
+    TS_REQUIRE((challenges || !p.n_challenges) && (exposed || !p.n_exposed), ts::TS_ERR_INVALID,
+               "null challenges or exposed words for an AIR that has them");
+    pis.insert(pis.end(), challenges, challenges + 4 * (size_t)p.n_challenges);
+    pis.insert(pis.end(), exposed, exposed + p.n_exposed);
+    for (uint32_t v : pis) TS_REQUIRE(v < ts::P, ts::TS_ERR_INVALID, "non-canonical public value, challenge or exposed word");
+    return pis;
+}
+
 // The key of ts_*_pre calls: null exactly when the AIR has no preprocessed columns, else one committed matrix of
 // the AIR's preprocessed width, made on this context.  (Its height is checked against the trace's where both
 // are known: ts::check_preprocessed_key.)  Returns the PcsData or null.
 const ts::PcsData* preprocessed_key(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key) {
+    no_aux(air, "a call that takes a preprocessed key");
     const uint32_t pw = air->a.prog().preprocessed_width;
     TS_REQUIRE((key != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
                pw ? "null preprocessed key for an AIR with preprocessed columns"
@@ -255,6 +286,8 @@ ts_status ts_proof_to_postcard(const uint32_t* proof, size_t n_words, uint8_t* o
         // the reference's OpenedValues has no preprocessed fields (uni-stark/src/proof.rs): no postcard form of v3
         TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 3), ts::TS_ERR_UNSUPPORTED,
                    "TSPF v3 proofs (ts_prove_pre) have no postcard form");
+        TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 4), ts::TS_ERR_UNSUPPORTED,
+                   "TSPF v4 proofs (ts_prove_aux) have no postcard form");
         TS_REQUIRE(ts::tspf_to_postcard(proof, n_words, b), ts::TS_ERR_INVALID, "not a TSPF v1 proof");
         *n_bytes_out = b.size();
         TS_REQUIRE(b.size() <= cap_bytes, ts::TS_ERR_BUFFER, "postcard buffer too small");
@@ -1382,6 +1415,7 @@ static ts_status check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matr
     *first_violation = -1;
     return guard(ctx, [&] {
         if (!takes_prep) no_preprocessed(air, "ts_check_constraints");
+        else no_aux(air, "ts_check_constraints_pre");
         const ts::AirProgram& p = air->a.prog();
         TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
                    "check_constraints: needs an uploaded (row-major, unconsumed) trace");
@@ -1443,6 +1477,7 @@ ts_status ts_verify_pre(const ts_fri_config* cfg, const ts_air* air, ts_challeng
     if (verdict) *verdict = -1;
     return guard(nullptr, [&] {
         TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_pre: null argument");
+        no_aux(air, "ts_verify_pre");
         const uint32_t pw = air->a.prog().preprocessed_width;
         TS_REQUIRE((preprocessed_root != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
                    pw ? "ts_verify_pre: null preprocessed root for an AIR with preprocessed columns"
@@ -1458,6 +1493,203 @@ ts_status ts_verify_pre(const ts_fri_config* cfg, const ts_air* air, ts_challeng
             throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre: the proof's preprocessed width is not the AIR's");
         }
         *verdict = ts::verify_pre(f, air->a.prog(), chal->c, preprocessed_root, proof, n_words, pis);
+    });
+}
+
+// ------------------------------------------------------------------ challenge-phase (aux) columns
+ts_status ts_air_aux_info(const ts_air* air, uint32_t* aux_width, uint32_t* n_challenges, uint32_t* n_exposed) {
+    if (!air) return TS_ERR_INVALID;
+    if (aux_width) *aux_width = air->a.prog().aux_width;
+    if (n_challenges) *n_challenges = air->a.prog().n_challenges;
+    if (n_exposed) *n_exposed = air->a.prog().n_exposed;
+    return TS_OK;
+}
+
+ts_status ts_quotient_chunks_aux(ts_ctx* ctx, const ts_pcs_data* aux_data, const ts_pcs_data* trace_data,
+                                 uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
+                                 uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                                 const uint32_t alpha[4], ts_matrix** chunks_out) {
+    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
+    return guard(ctx, [&] {
+        no_prep_with_aux(air, "ts_quotient_chunks_aux");
+        const ts::AirProgram& p = ready_prog(air);
+        TS_REQUIRE((aux_data != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+                   p.aux_width ? "null aux data for an AIR with aux columns"
+                               : "aux data was given for an AIR without aux columns");
+        if (aux_data) {
+            TS_REQUIRE(aux_data->d && aux_data->d->ldes.size() == 1 && aux_data->d->ldes[0].width == p.aux_width,
+                       ts::TS_ERR_INVALID, "aux data: exactly one committed matrix of the AIR's aux width expected");
+            TS_REQUIRE(aux_data->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "aux data was made on another context");
+        }
+        ts_fri_config raw{log_blowup, 1, 0};
+        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));
+        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
+        auto chunks = pcs.quotient_chunks(*trace_data->d, p, pis, load_ef(alpha), aux_data ? aux_data->d.get() : nullptr);
+        for (size_t c = 0; c < chunks.size(); c++) {
+            auto m = std::make_unique<ts_matrix>();
+            m->m = std::move(chunks[c]);
+            chunks_out[c] = m.release();
+        }
+    });
+}
+
+ts_status ts_check_constraints_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* aux, const ts_matrix* trace,
+                                   const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                   const uint32_t* exposed, int64_t* first_violation) {
+    if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
+    *first_violation = -1;
+    return guard(ctx, [&] {
+        no_prep_with_aux(air, "ts_check_constraints_aux");
+        const ts::AirProgram& p = air->a.prog();
+        TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
+                   "check_constraints: needs an uploaded (row-major, unconsumed) trace");
+        TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
+        TS_REQUIRE((aux != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+                   "check_constraints: the aux matrix is needed exactly by an AIR with aux columns");
+        if (aux)
+            TS_REQUIRE(aux->m.buf.p && aux->m.layout == ts::DeviceMatrix::ROW_MAJOR && aux->m.buf.ctx == &ctx->ctx &&
+                           aux->m.width == p.aux_width && aux->m.height == trace->m.height,
+                       ts::TS_ERR_INVALID,
+                       "check_constraints: the aux matrix must be on this context, row-major, of the AIR's aux width "
+                       "and the trace's height");
+        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
+        const std::vector<uint32_t> consts = ts::air_consts_mont(p, pis.data(), pis.size());
+        ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
+        ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
+        TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, ctx->ctx.stream));
+        TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
+        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p,
+                                     aux ? aux->m.buf.p : nullptr);
+        unsigned long long v = 0;
+        TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
+        ctx->ctx.sync();
+        *first_violation = v == ~0ull ? -1 : (int64_t)v;
+    });
+}
+
+// The callback's failure, carried through ts::prove_aux as an exception of its own so that its status -- any
+// value the host chose -- reaches the caller unchanged.
+namespace {
+struct AuxCallbackFailed {
+    ts_status status;
+};
+}  // namespace
+
+ts_status ts_prove_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                       ts_matrix* trace, const uint32_t* public_values, uint32_t n_public, ts_aux_fn aux_fn,
+                       void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) {
+        if (ctx) ctx->ctx.last_error = "ts_prove_aux: null argument";
+        return TS_ERR_INVALID;
+    }
+    *n_words_out = 0;
+    ts_status cb_status = TS_OK;
+    const ts_status st = guard(ctx, [&] {
+        no_prep_with_aux(air, "ts_prove_aux");
+        const ts::AirProgram& p = ready_prog(air);
+        TS_REQUIRE((aux_fn != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+                   p.aux_width ? "ts_prove_aux: null aux_fn for an AIR with aux columns"
+                               : "ts_prove_aux: an aux_fn was given for an AIR without aux columns");
+        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        TS_REQUIRE(trace->m.buf.ctx == &ctx->ctx || !trace->m.buf.p, ts::TS_ERR_INVALID,
+                   "trace was made on another context");
+        ts::DeviceMatrix m = take_trace(trace);
+        ts::AuxSource source;
+        if (aux_fn)
+            source = [&](const ts::DeviceMatrix& live, const uint32_t* challenges, uint32_t* exposed) {
+                // the callback sees the live trace as a ts_matrix of its own: borrowed for the call, handed back after
+                ts_matrix view;
+                view.m = std::move(const_cast<ts::DeviceMatrix&>(live));
+                ts_matrix* out = nullptr;
+                const ts_status rc = aux_fn(user, ctx, &view, challenges, p.n_challenges, &out, exposed);
+                const_cast<ts::DeviceMatrix&>(live) = std::move(view.m);
+                std::unique_ptr<ts_matrix> owned(out);
+                if (rc != TS_OK) {
+                    cb_status = rc;
+                    throw AuxCallbackFailed{rc};
+                }
+                TS_REQUIRE(owned, ts::TS_ERR_INVALID, "ts_prove_aux: the aux callback returned no matrix");
+                return std::move(owned->m);
+            };
+        ts::StageTimer t(&ctx->ctx, "prove");
+        try {
+            copy_proof(ts::prove_aux(pcs, p, chal->c, std::move(m), pis, source), proof_out, cap_words, n_words_out);
+        } catch (const AuxCallbackFailed&) {
+            const std::string inner = ctx->ctx.last_error;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_prove_aux: the aux callback (aux_fn) returned status " +
+                                                    std::to_string((int)cb_status) + (inner.empty() ? "" : ": " + inner));
+        }
+    });
+    return cb_status != TS_OK ? cb_status : st;
+}
+
+ts_status ts_verify_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal, const uint32_t* proof,
+                        size_t n_words, const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
+                        uint32_t cap_exposed, int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_aux: null argument");
+        no_prep_with_aux(air, "ts_verify_aux");
+        const ts::AirProgram& p = air->a.prog();
+        TS_REQUIRE(p.n_exposed == 0 || (exposed_out && cap_exposed >= p.n_exposed), ts::TS_ERR_INVALID,
+                   "ts_verify_aux: null or short buffer for the exposed words");
+        ts::FriConfig f = load_cfg(cfg);
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        if (n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != 4) {
+            *verdict = 9;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_aux: not a TSPF v4 proof");
+        }
+        if (n_words >= 8 && proof[0] == ts::TSPF_MAGIC &&
+            (proof[5] != p.aux_width || proof[6] != p.n_challenges || proof[7] != p.n_exposed)) {
+            *verdict = 1;
+            throw ts::Error(ts::TS_ERR_INVALID,
+                            "ts_verify_aux: the proof's aux width, challenge or exposed count is not the AIR's");
+        }
+        std::vector<uint32_t> exposed;
+        *verdict = ts::verify_aux(f, p, chal->c, proof, n_words, pis, exposed);
+        if (*verdict == 0 && !exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
+    });
+}
+
+// ------------------------------------------------------------------ LogUp aux columns
+namespace {
+ts::LogupSpec load_logup_spec(const ts_logup_spec* spec) {
+    TS_REQUIRE(spec && spec->struct_size >= sizeof(ts_logup_spec), ts::TS_ERR_INVALID, "logup: null spec or bad struct_size");
+    TS_REQUIRE(spec->n_interactions >= 1 && spec->n_interactions <= ts::LOGUP_MAX_INTERACTIONS && spec->interactions,
+               ts::TS_ERR_INVALID, "logup: between 1 and 16 interactions");
+    ts::LogupSpec s;
+    for (uint32_t i = 0; i < spec->n_interactions; i++) {
+        const ts_logup_interaction& it = spec->interactions[i];
+        TS_REQUIRE(it.n_values >= 1 && it.n_values <= ts::LOGUP_MAX_VALUES && it.values, ts::TS_ERR_INVALID,
+                   "logup: between 1 and 8 values per interaction");
+        ts::LogupInteraction li;
+        li.multiplicity = ts::LogupTerm{it.multiplicity.kind, it.multiplicity.value};
+        for (uint32_t q = 0; q < it.n_values; q++) li.values.push_back(ts::LogupTerm{it.values[q].kind, it.values[q].value});
+        s.interactions.push_back(std::move(li));
+    }
+    return s;
+}
+}  // namespace
+
+ts_status ts_logup_aux_width(const ts_logup_spec* spec, uint32_t* aux_width) {
+    if (!aux_width) return TS_ERR_INVALID;
+    *aux_width = 0;
+    return guard(nullptr, [&] { *aux_width = ts::logup_aux_width(load_logup_spec(spec)); });
+}
+
+ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* trace,
+                             const uint32_t challenges[8], ts_matrix** aux_out, uint32_t exposed_out[4]) {
+    if (!ctx || !trace || !challenges || !aux_out || !exposed_out) {
+        if (ctx) ctx->ctx.last_error = "ts_logup_aux_build: null argument";
+        return TS_ERR_INVALID;
+    }
+    *aux_out = nullptr;
+    return guard(ctx, [&] {
+        const ts::LogupSpec s = load_logup_spec(spec);
+        auto m = std::make_unique<ts_matrix>();
+        m->m = ts::logup_aux_build(ctx->ctx, s, trace->m, challenges, exposed_out);
+        *aux_out = m.release();
     });
 }
 

@@ -11,18 +11,26 @@
 namespace ts {
 
 AirProgram compile_air(const uint32_t* tape, size_t n_words) {
-    TS_REQUIRE(tape && n_words >= 6 && tape[0] == TAPE_MAGIC && (tape[1] == 1 || tape[1] == 2), TS_ERR_INVALID,
+    TS_REQUIRE(tape && n_words >= 6 && tape[0] == TAPE_MAGIC && tape[1] >= 1 && tape[1] <= 3, TS_ERR_INVALID,
                "air tape: bad header");
-    // version 2 (symbolic_builder.rs:68-99 with a preprocessed_width): one more header word, one more leaf
-    const bool v2 = tape[1] == 2;
+    // version 2 (symbolic_builder.rs:68-99 with a preprocessed_width): one more header word, one more leaf;
+    // version 3: three more words (aux_width, n_challenges, n_exposed) and three more leaves
+    const bool v3 = tape[1] == 3, v2 = tape[1] >= 2;
     AirProgram p;
-    p.tape_header = v2 ? 7 : 6;
+    p.tape_header = v3 ? 10 : v2 ? 7 : 6;
     TS_REQUIRE(n_words >= p.tape_header, TS_ERR_INVALID, "air tape: bad header");
     p.width = tape[2];
     p.n_public = tape[3];
     const uint32_t n_nodes = tape[4];
     p.n_constraints = tape[5];
     p.preprocessed_width = v2 ? tape[6] : 0;
+    if (v3) {
+        p.aux_width = tape[7];
+        p.n_challenges = tape[8];
+        p.n_exposed = tape[9];
+        TS_REQUIRE(p.n_challenges <= (1u << 20) && p.n_exposed <= (1u << 20) && p.n_public <= (1u << 28), TS_ERR_INVALID,
+                   "air tape: more than 2^20 challenges or exposed words");
+    }
     TS_REQUIRE((size_t)p.tape_header + 3 * (size_t)n_nodes + p.n_constraints == n_words, TS_ERR_INVALID,
                "air tape: length does not match header");
     TS_REQUIRE(p.width >= 1, TS_ERR_INVALID, "air tape: zero width");
@@ -50,6 +58,21 @@ AirProgram compile_air(const uint32_t* tape, size_t n_words) {
                 break;
             case T_PUBLIC:
                 TS_REQUIRE(a < p.n_public, TS_ERR_INVALID, "air tape: bad public index");
+                deg[i] = 0;
+                break;
+            case T_AUX:  // degree multiple 1, like MAIN
+                TS_REQUIRE(v3, TS_ERR_INVALID, "air tape: aux variable in a version-1 or version-2 tape");
+                TS_REQUIRE(a <= 1 && b < p.aux_width, TS_ERR_INVALID, "air tape: bad aux variable");
+                deg[i] = 1;
+                break;
+            case T_CHALLENGE:  // degree multiple 0, like a public value
+                TS_REQUIRE(v3, TS_ERR_INVALID, "air tape: challenge in a version-1 or version-2 tape");
+                TS_REQUIRE(a < 4 * p.n_challenges, TS_ERR_INVALID, "air tape: bad challenge word index");
+                deg[i] = 0;
+                break;
+            case T_EXPOSED:
+                TS_REQUIRE(v3, TS_ERR_INVALID, "air tape: exposed value in a version-1 or version-2 tape");
+                TS_REQUIRE(a < p.n_exposed, TS_ERR_INVALID, "air tape: bad exposed value index");
                 deg[i] = 0;
                 break;
             case T_IS_FIRST:
@@ -176,6 +199,11 @@ AirProgram compile_air(const uint32_t* tape, size_t n_words) {
                 case T_PUBLIC: emit(D_CONST, dst, add_const(0, a), 0); break;
                 case T_MAIN: emit(D_LOAD, dst, a, b); break;
                 case T_PREP: emit(D_LOAD, dst, a + 2, b); break;
+                // version 3: the aux trace takes the second matrix's load operands, challenges and exposed
+                // words the public slots after the public values
+                case T_AUX: emit(D_LOAD, dst, a + 2, b); break;
+                case T_CHALLENGE: emit(D_CONST, dst, add_const(0, p.n_public + a), 0); break;
+                case T_EXPOSED: emit(D_CONST, dst, add_const(0, p.n_public + 4 * p.n_challenges + a), 0); break;
                 case T_IS_FIRST: emit(D_SEL, dst, 0, 0); break;
                 case T_IS_LAST: emit(D_SEL, dst, 1, 0); break;
                 case T_IS_TRANSITION: emit(D_SEL, dst, 2, 0); break;

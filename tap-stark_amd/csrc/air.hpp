@@ -19,13 +19,17 @@ constexpr uint32_t TAPE_MAGIC = 0x54415354u;
 enum TapeOp : uint32_t {
     T_CONST = 0, T_MAIN = 1, T_PUBLIC = 2, T_IS_FIRST = 3, T_IS_LAST = 4, T_IS_TRANSITION = 5,
     T_ADD = 6, T_SUB = 7, T_NEG = 8, T_MUL = 9,
-    T_PREP = 10  // version-2 tapes only: a preprocessed column (symbolic_variable.rs:9-15 Entry::Preprocessed)
+    T_PREP = 10,  // version-2 tapes only: a preprocessed column (symbolic_variable.rs:9-15 Entry::Preprocessed)
+    // version-3 tapes only (build-defined: the reference has no challenge phase)
+    T_AUX = 11,        // a = offset 0|1, b = column of the challenge-phase (aux) trace
+    T_CHALLENGE = 12,  // a = word index < 4 * n_challenges
+    T_EXPOSED = 13     // a = index < n_exposed
 };
 
 // device instruction: 4 x u32 {op, dst, a, b}.  Operands of ADD/SUB/MUL/NEG/ASSERT are register ids.
 enum DevOp : uint32_t {
-    D_LOAD = 0,     // dst <- to_mont(rows[a][b = column]); a = row offset + 2 * (preprocessed): 0/1 main
-                    // local/next, 2/3 preprocessed local/next
+    D_LOAD = 0,     // dst <- to_mont(rows[a][b = column]); a = row offset + 2 * (second matrix): 0/1 main
+                    // local/next, 2/3 local/next of the second matrix (preprocessed columns, or aux columns)
     D_CONST = 1,    // dst <- consts[a]           (Montgomery; constants and public values)
     D_SEL = 2,      // dst <- selector a (0 first, 1 last, 2 transition)
     D_ADD = 3,
@@ -61,7 +65,14 @@ struct KernelSetRef {
 struct AirProgram {
     uint32_t width = 0;
     uint32_t preprocessed_width = 0;        // version-2 tapes (0: the AIR reads the main trace only)
+    // version-3 tapes: the challenge-phase (aux) trace, its challenges (extension elements) and exposed words
+    uint32_t aux_width = 0, n_challenges = 0, n_exposed = 0;
     uint32_t n_public = 0;
+    // The second committed matrix the kernels read (D_LOAD a = 2, 3): the preprocessed key or the aux trace.
+    // Both at once would be a third matrix, which no kernel takes: the proving calls refuse it.
+    uint32_t second_width() const { return preprocessed_width ? preprocessed_width : aux_width; }
+    // The public vector the lowered program indexes: public values ++ challenge words ++ exposed words
+    uint32_t n_public_slots() const { return n_public + 4 * n_challenges + n_exposed; }
     uint32_t n_constraints = 0;
     uint32_t max_degree = 0;
     uint32_t log_quotient_degree = 0;
@@ -70,7 +81,7 @@ struct AirProgram {
     std::vector<uint32_t> const_canonical;  // constants (canonical); publics are appended per proof
     std::vector<uint32_t> const_public_idx; // for entries that are public values: index, else ~0u
     std::vector<uint32_t> tape;             // the validated input (kept for the verifier side)
-    uint32_t tape_header = 6;               // words before the nodes: 6 (version 1) or 7 (version 2)
+    uint32_t tape_header = 6;               // words before the nodes: 6 (version 1), 7 (version 2), 10 (version 3)
     const uint32_t* tape_nodes() const { return tape.data() + tape_header; }
     const uint32_t* tape_constraints() const { return tape_nodes() + 3 * (size_t)tape[4]; }
     // device copy of `code`, owned by the context that compiled it

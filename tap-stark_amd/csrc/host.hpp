@@ -109,7 +109,10 @@ public:
     // two_adic_pcs.rs:227-245.  Consumes the matrices.  build_tree = false stops after the LDE
     // (a caller with another MMCS -- the taptree one -- commits to data->ldes itself).
     std::unique_ptr<PcsData> commit(std::vector<DeviceMatrix>& evals,
-                                    const std::vector<uint32_t>& domain_shifts, bool build_tree = true);
+                                    const std::vector<uint32_t>& domain_shifts, bool build_tree = true,
+                                    bool keep_row_major = false);
+    // (keep_row_major: a row-major input is left alive; the LDE stage only reads it.  No device copy is made:
+    // the cost is that its n x w words stay allocated until the caller releases them)
 
     // two_adic_pcs.rs:247-258 + uni-stark prover.rs:122-194,78-80
     // preprocessed: the committed key of a version-2 AIR's preprocessed columns (one matrix of the trace's
@@ -173,6 +176,14 @@ private:
 std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                             DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                             const PcsData* preprocessed = nullptr, uint32_t proof_version = 1);
+// The same over (aux trace, trace) for a version-3 AIR, TSPF v4.  After the trace's commit and the challenges,
+// `aux_source(trace, challenge words (canonical, 4 per challenge), exposed_out)` returns the height x aux_width
+// aux matrix made on the prover's context; the trace is still alive then and is released right after.  Null
+// exactly for an AIR without aux columns.  Throws what the source throws.
+using AuxSource = std::function<DeviceMatrix(const DeviceMatrix& trace, const uint32_t* challenges, uint32_t* exposed)>;
+std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                const AuxSource& aux_source);
 // throws TS_ERR_INVALID unless `key` holds exactly one matrix of the AIR's preprocessed width and that LDE height
 void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height);
 
@@ -246,6 +257,9 @@ int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger
 // the same for a TSPF v3 proof against the root of the preprocessed key (null for an AIR without such columns)
 int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
                const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values);
+// the same for a TSPF v4 proof of a version-3 AIR; `exposed` receives the proof's exposed words (on accept)
+int verify_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* proof,
+               size_t n_words, const std::vector<uint32_t>& public_values, std::vector<uint32_t>& exposed);
 
 // Pcs::verify (fri/src/two_adic_pcs.rs:421-534) for any rounds x matrices x points; same codes.
 struct PcsMatClaim {

@@ -1,0 +1,287 @@
+// LogUp columns of a challenge-phase (aux) trace, built in HBM from the still-resident main trace.
+//
+// Two challenges gamma, beta.  Interaction i on row r has the denominator d_i = gamma + sum_j beta^j v_ij(r) and
+// the fraction m_i(r) / d_i.  Interactions are paired: group g holds 2g and 2g+1 (the last group one if K is
+// odd).  The row-major aux matrix (n x 4 (G + 1), canonical) holds h_g(r), the group's sum, in columns
+// 4g .. 4g+3 and phi(r) = sum_{r' < r} sum_g h_g(r') in the last four; S = phi(n-1) + sum_g h_g(n-1) is exposed.
+//
+// Three plain launches, no grid barrier, no flag another workgroup waits for:
+//   k_logup_rows    one thread per row (LOGUP_RPT rows in turn): the fractions, with ONE base-field inversion
+//                   per batch of LOGUP_BATCH denominators (ef_inv_parts + a running product, as open.hip); the
+//                   row's sum goes into the phi slot, the workgroup's sum into totals[workgroup]
+//   k_logup_totals  one workgroup: totals -> their exclusive prefix sums, in passes of LOGUP_SCAN_THREADS
+//   k_logup_scan    the workgroup-local exclusive scan of the row sums plus the workgroup's offset -> phi; the
+//                   thread of row n-1 writes S
+// Extension addition is exact, so the association does not matter: the words are those of a serial sum.
+// A zero denominator (its norm is zero) is reported through *flag = min(row * K + i); its batch runs on with the
+// norm replaced by one, so nothing else is disturbed and the host discards the output.
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+
+#include "logup.hpp"
+
+namespace ts {
+
+constexpr int LOGUP_THREADS = 256;
+constexpr int LOGUP_RPT = 4;              // rows per thread at most: a workgroup owns up to 1024 rows
+constexpr int LOGUP_BATCH = 4;            // denominators per base-field inversion: two groups
+constexpr int LOGUP_SCAN_THREADS = 128;   // totals per pass of k_logup_totals
+
+struct LogupDev {
+    uint32_t K, G, width, aux_width;
+    Ef gamma_mont;                        // gamma R
+    Ef beta_pow[LOGUP_MAX_VALUES];        // beta^j R^2: times a canonical value = (beta^j v) R
+    struct {
+        uint32_t m_kind, m_val, n_values, pad;
+        uint32_t kind[LOGUP_MAX_VALUES], val[LOGUP_MAX_VALUES];
+    } it[LOGUP_MAX_INTERACTIONS];
+};
+
+__device__ __forceinline__ Ef ef_shfl_up(Ef v, unsigned delta) {
+    return Ef{{(uint32_t)__shfl_up((int)v.c[0], delta, 64), (uint32_t)__shfl_up((int)v.c[1], delta, 64),
+               (uint32_t)__shfl_up((int)v.c[2], delta, 64), (uint32_t)__shfl_up((int)v.c[3], delta, 64)}};
+}
+
+// Inclusive scan over the workgroup's threads (NW waves of 64): wave-64 shuffles inside a wave, LDS across
+// waves.  Returns the inclusive sum at this thread; `total` is the workgroup's sum.  Every thread calls it.
+template <int NW>
+__device__ __forceinline__ Ef block_scan_inclusive(Ef v, Ef (&wave_sums)[NW], Ef& total) {
+    const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const Ef up = ef_shfl_up(v, d);
+        if (lane >= d) v = ef_add(v, up);
+    }
+    __syncthreads();  // (a second call reuses wave_sums)
+    if (lane == 63) wave_sums[wv] = v;
+    __syncthreads();
+    Ef before = ef_zero();
+    total = ef_zero();
+#pragma unroll
+    for (int k = 0; k < NW; k++) {
+        const Ef s = wave_sums[k];
+        if (k < (int)wv) before = ef_add(before, s);
+        total = ef_add(total, s);
+    }
+    return ef_add(v, before);
+}
+
+__device__ __forceinline__ uint32_t term_value(uint32_t kind, uint32_t val, const uint32_t* __restrict__ row) {
+    return kind ? row[val] : val;
+}
+
+// sum_g h_g(r), with the h_g written to the row's first 4 G words
+__device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __restrict__ row, uint64_t r,
+                                        uint32_t* __restrict__ aux_row, unsigned long long* __restrict__ flag) {
+    Ef sum = ef_zero();
+    for (uint32_t i0 = 0; i0 < s.K; i0 += LOGUP_BATCH) {
+        Ef num[LOGUP_BATCH];
+        uint32_t nrm[LOGUP_BATCH], pre[LOGUP_BATCH], mult[LOGUP_BATCH];
+        uint32_t run = R_MOD_P;
+#pragma unroll
+        for (int j = 0; j < LOGUP_BATCH; j++) {
+            const uint32_t i = i0 + j;
+            num[j] = ef_zero();
+            nrm[j] = R_MOD_P;
+            mult[j] = 0;
+            if (i < s.K) {
+                Ef d = s.gamma_mont;
+                const uint32_t nv = s.it[i].n_values;
+#pragma unroll
+                for (int q = 0; q < LOGUP_MAX_VALUES; q++)
+                    if (q < (int)nv)
+                        d = ef_add(d, ef_mul_base(s.beta_pow[q], term_value(s.it[i].kind[q], s.it[i].val[q], row)));
+                ef_inv_parts(d, num[j], nrm[j]);
+                if (nrm[j] == 0) {  // d == 0: reported, and the batch goes on as if the norm were one
+                    atomicMin(flag, (unsigned long long)r * s.K + i);
+                    nrm[j] = R_MOD_P;
+                }
+                mult[j] = term_value(s.it[i].m_kind, s.it[i].m_val, row);
+            }
+            pre[j] = run;
+            run = mont_mul(run, nrm[j]);
+        }
+        uint32_t inv = mont_inv(run);
+        Ef frac[LOGUP_BATCH];
+#pragma unroll
+        for (int j = LOGUP_BATCH - 1; j >= 0; j--) {
+            const uint32_t ninv = mont_mul(inv, pre[j]);
+            inv = mont_mul(inv, nrm[j]);
+            // (1/d) R times the canonical multiplicity: canonical m / d
+            frac[j] = ef_mul_base(ef_mul_base(num[j], ninv), mult[j]);
+        }
+#pragma unroll
+        for (int g = 0; g < LOGUP_BATCH / 2; g++) {
+            if (i0 + 2 * g < s.K) {
+                const Ef h = ef_add(frac[2 * g], frac[2 * g + 1]);
+                *reinterpret_cast<Ef*>(aux_row + 4 * (i0 / 2 + g)) = h;
+                sum = ef_add(sum, h);
+            }
+        }
+    }
+    return sum;
+}
+
+__global__ void __launch_bounds__(LOGUP_THREADS)
+k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, uint64_t n, uint32_t block_rows, uint32_t rpt,
+             uint32_t* __restrict__ aux, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
+    __shared__ Ef wave_sums[LOGUP_THREADS / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * block_rows;
+    Ef mine = ef_zero();
+    for (uint32_t k = 0; k < rpt; k++) {
+        const uint32_t local = threadIdx.x * rpt + k;
+        const uint64_t r = base + local;
+        if (local < block_rows && r < n) {
+            uint32_t* aux_row = aux + r * s.aux_width;
+            const Ef sum = logup_row(s, trace + r * s.width, r, aux_row, flag);
+            *reinterpret_cast<Ef*>(aux_row + 4 * s.G) = sum;  // the phi slot, until k_logup_scan
+            mine = ef_add(mine, sum);
+        }
+    }
+    Ef total;
+    block_scan_inclusive<LOGUP_THREADS / 64>(mine, wave_sums, total);
+    if (threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+// totals[b] <- sum_{b' < b} totals[b'], b < n_blocks
+__global__ void __launch_bounds__(LOGUP_SCAN_THREADS)
+k_logup_totals(Ef* __restrict__ totals, uint32_t n_blocks) {
+    __shared__ Ef wave_sums[LOGUP_SCAN_THREADS / 64];
+    Ef carry = ef_zero();
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += LOGUP_SCAN_THREADS) {  // (uniform bounds: every thread loops alike)
+        const uint32_t b = b0 + threadIdx.x;
+        const Ef v = b < n_blocks ? totals[b] : ef_zero();
+        Ef pass;
+        const Ef incl = block_scan_inclusive<LOGUP_SCAN_THREADS / 64>(v, wave_sums, pass);
+        if (b < n_blocks) totals[b] = ef_add(carry, ef_sub(incl, v));
+        carry = ef_add(carry, pass);
+    }
+}
+
+__global__ void __launch_bounds__(LOGUP_THREADS)
+k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, uint32_t rpt,
+             uint32_t* __restrict__ aux, const Ef* __restrict__ offsets, Ef* __restrict__ S) {
+    __shared__ Ef wave_sums[LOGUP_THREADS / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * block_rows;
+    Ef sums[LOGUP_RPT];
+    Ef mine = ef_zero();
+#pragma unroll
+    for (int k = 0; k < LOGUP_RPT; k++) {
+        const uint32_t local = threadIdx.x * rpt + k;
+        const uint64_t r = base + local;
+        sums[k] = ef_zero();
+        if (k < (int)rpt && local < block_rows && r < n)
+            sums[k] = *reinterpret_cast<const Ef*>(aux + r * aux_width + 4 * G);
+        mine = ef_add(mine, sums[k]);
+    }
+    Ef total;
+    const Ef incl = block_scan_inclusive<LOGUP_THREADS / 64>(mine, wave_sums, total);
+    Ef run = ef_add(offsets[blockIdx.x], ef_sub(incl, mine));
+#pragma unroll
+    for (int k = 0; k < LOGUP_RPT; k++) {
+        const uint32_t local = threadIdx.x * rpt + k;
+        const uint64_t r = base + local;
+        if (k < (int)rpt && local < block_rows && r < n) {
+            *reinterpret_cast<Ef*>(aux + r * aux_width + 4 * G) = run;
+            run = ef_add(run, sums[k]);
+            if (r == n - 1) *S = run;
+        }
+    }
+}
+
+uint32_t logup_aux_width(const LogupSpec& spec) {
+    const size_t K = spec.interactions.size();
+    TS_REQUIRE(K >= 1 && K <= LOGUP_MAX_INTERACTIONS, TS_ERR_INVALID,
+               "logup: between 1 and 16 interactions");
+    for (const LogupInteraction& it : spec.interactions) {
+        TS_REQUIRE(it.values.size() >= 1 && it.values.size() <= LOGUP_MAX_VALUES, TS_ERR_INVALID,
+                   "logup: between 1 and 8 values per interaction");
+        TS_REQUIRE(it.multiplicity.kind <= 1, TS_ERR_INVALID, "logup: term kind must be 0 (constant) or 1 (column)");
+        for (const LogupTerm& t : it.values)
+            TS_REQUIRE(t.kind <= 1, TS_ERR_INVALID, "logup: term kind must be 0 (constant) or 1 (column)");
+    }
+    return 4 * ((uint32_t)(K + 1) / 2 + 1);
+}
+
+static uint32_t logup_block_rows() {
+    uint32_t rows = LOGUP_THREADS * LOGUP_RPT;
+    if (const char* e = getenv("TS_LOGUP_BLOCK_ROWS"); e && *e) {
+        const long v = atol(e);
+        TS_REQUIRE(v >= 1 && v <= LOGUP_THREADS * LOGUP_RPT, TS_ERR_INVALID,
+                   "TS_LOGUP_BLOCK_ROWS must be in [1, 1024]");
+        rows = (uint32_t)v;
+    }
+    return rows;
+}
+
+DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace,
+                             const uint32_t challenges[8], uint32_t exposed[4]) {
+    StageTimer t(&ctx, "logup aux build");
+    LogupDev s;
+    memset(&s, 0, sizeof s);
+    s.aux_width = logup_aux_width(spec);
+    s.K = (uint32_t)spec.interactions.size();
+    s.G = (s.K + 1) / 2;
+    TS_REQUIRE(trace.buf.p && trace.layout == DeviceMatrix::ROW_MAJOR && trace.buf.ctx == &ctx, TS_ERR_INVALID,
+               "logup: needs a row-major, unconsumed trace made on this context");
+    TS_REQUIRE(trace.height >= 1 && trace.height <= (1ull << 27) && trace.width >= 1, TS_ERR_INVALID,
+               "logup: trace height must be in [1, 2^27]");
+    s.width = trace.width;
+    auto term = [&](const LogupTerm& tm, uint32_t& kind, uint32_t& val) {
+        TS_REQUIRE(tm.kind ? tm.value < trace.width : tm.value < P, TS_ERR_INVALID,
+                   "logup: a column outside the trace, or a non-canonical constant");
+        kind = tm.kind;
+        val = tm.value;
+    };
+    for (uint32_t i = 0; i < s.K; i++) {
+        const LogupInteraction& it = spec.interactions[i];
+        term(it.multiplicity, s.it[i].m_kind, s.it[i].m_val);
+        s.it[i].n_values = (uint32_t)it.values.size();
+        for (size_t q = 0; q < it.values.size(); q++) term(it.values[q], s.it[i].kind[q], s.it[i].val[q]);
+    }
+    for (int k = 0; k < 8; k++) TS_REQUIRE(challenges[k] < P, TS_ERR_INVALID, "logup: non-canonical challenge");
+    const Ef gamma = ef_to_mont(Ef{{challenges[0], challenges[1], challenges[2], challenges[3]}});
+    const Ef beta = ef_to_mont(Ef{{challenges[4], challenges[5], challenges[6], challenges[7]}});
+    s.gamma_mont = gamma;
+    Ef bp = ef_one_mont();
+    for (uint32_t q = 0; q < LOGUP_MAX_VALUES; q++) {
+        s.beta_pow[q] = ef_to_mont(bp);
+        bp = ef_mul(bp, beta);
+    }
+
+    const uint64_t n = trace.height;
+    const uint32_t block_rows = logup_block_rows();
+    const uint32_t rpt = (block_rows + LOGUP_THREADS - 1) / LOGUP_THREADS;
+    const uint64_t n_blocks = (n + block_rows - 1) / block_rows;
+    TS_REQUIRE(n_blocks <= (1u << 27), TS_ERR_INVALID, "logup: too many workgroups");
+    DeviceMatrix aux;
+    aux.buf = DevBuf<uint32_t>(&ctx, n * s.aux_width);
+    aux.height = n;
+    aux.width = s.aux_width;
+    aux.layout = DeviceMatrix::ROW_MAJOR;
+    DevBuf<Ef> totals(&ctx, n_blocks);
+    // {flag (two words), pad, pad, S}: one copy back
+    DevBuf<Ef> back(&ctx, 2);
+    TS_HIP(hipMemsetAsync(back.p, 0xff, 2 * sizeof(Ef), ctx.stream));
+    unsigned long long* flag = reinterpret_cast<unsigned long long*>(back.p);
+    TS_LAUNCH(ctx, k_logup_rows, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, s, trace.buf.p, n, block_rows, rpt,
+              aux.buf.p, totals.p, flag);
+    TS_HIP(hipGetLastError());
+    TS_LAUNCH(ctx, k_logup_totals, dim3(1), dim3(LOGUP_SCAN_THREADS), 0, totals.p, (uint32_t)n_blocks);
+    TS_HIP(hipGetLastError());
+    TS_LAUNCH(ctx, k_logup_scan, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, s.aux_width, s.G, n, block_rows, rpt,
+              aux.buf.p, totals.p, back.p + 1);
+    TS_HIP(hipGetLastError());
+    uint32_t host[8];
+    d2h_sync(ctx, host, back.p, sizeof host);
+    const unsigned long long f = (unsigned long long)host[0] | ((unsigned long long)host[1] << 32);
+    if (f != ~0ull)
+        throw Error(TS_ERR_INVARIANT, "logup: zero denominator at row " + std::to_string(f / s.K) + ", interaction " +
+                                          std::to_string(f % s.K));
+    memcpy(exposed, host + 4, 16);
+    return aux;
+}
+
+}  // namespace ts

@@ -96,9 +96,10 @@ void mmcs_commit(Context& ctx, PcsData& data) {
 // the tree itself is build-defined, see merkle.hip): leaves hash the rows of the tallest matrices,
 // and the rows of the matrices of height h are compressed into the level that has h nodes.
 std::unique_ptr<PcsData> TwoAdicFriPcs::commit(std::vector<DeviceMatrix>& evals,
-                                               const std::vector<uint32_t>& domain_shifts, bool build_tree) {
+                                               const std::vector<uint32_t>& domain_shifts, bool build_tree,
+                                               bool keep_row_major) {
     auto data = std::make_unique<PcsData>();
-    lde_stage(ctx_, fri_, evals, domain_shifts, 0, 0, /*allow_pair=*/true, *data);
+    lde_stage(ctx_, fri_, evals, domain_shifts, 0, 0, /*allow_pair=*/true, *data, keep_row_major);
     if (build_tree) mmcs_commit(ctx_, *data);
     return data;
 }
@@ -106,7 +107,8 @@ std::unique_ptr<PcsData> TwoAdicFriPcs::commit(std::vector<DeviceMatrix>& evals,
 // ------------------------------------------------------------------ quotient
 void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height) {
     TS_REQUIRE(key.ldes.size() == 1, TS_ERR_INVALID, "preprocessed key: exactly one committed matrix expected");
-    TS_REQUIRE(air.preprocessed_width > 0 && key.ldes[0].width == air.preprocessed_width, TS_ERR_INVALID,
+    // (the same check serves the committed aux trace of a version-3 AIR: the kernels' second matrix)
+    TS_REQUIRE(air.second_width() > 0 && key.ldes[0].width == air.second_width(), TS_ERR_INVALID,
                "preprocessed key: width differs from the AIR's preprocessed width");
     TS_REQUIRE(key.ldes[0].height == lde_height, TS_ERR_INVALID,
                "preprocessed key: LDE height is not the trace height << log_blowup");
@@ -128,11 +130,11 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
                                                               const std::vector<uint32_t>& pis, Ef alpha,
                                                               uint32_t domain_shift, const ColMat* prep_lde) {
     StageTimer t(&ctx_, "compute quotient polynomial");
-    TS_REQUIRE((prep_lde != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
+    TS_REQUIRE((prep_lde != nullptr) == (air.second_width() > 0), TS_ERR_INVALID,
                "quotient: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
     TS_REQUIRE(!prep_lde || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: preprocessed columns on a slab");
     TS_REQUIRE(lde_slab.width == air.width, TS_ERR_INVALID, "quotient: trace width != AIR width");
-    TS_REQUIRE(pis.size() == air.n_public, TS_ERR_INVALID, "quotient: wrong number of public values");
+    TS_REQUIRE(pis.size() == air.n_public_slots(), TS_ERR_INVALID, "quotient: wrong number of public values");
     const unsigned lqd = air.log_quotient_degree;
     // two_adic_pcs.rs:256: assert!(lde.height() >= domain.size())
     TS_REQUIRE(lqd <= fri_.log_blowup, TS_ERR_INVARIANT,
@@ -590,6 +592,85 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
     pw.opened_values(opened);
     std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
     if (preprocessed) rounds.insert(rounds.begin(), preprocessed);
+    pcs.fri_prove(inputs, {st.log_N}, challenger, rounds, pf);
+    return pf;
+}
+
+// ------------------------------------------------------------------ prove with challenge-phase columns
+// Build-defined like the preprocessed prove (the reference has one trace phase).  Transcript: trace root,
+// n_challenges samples, [aux source], aux root, every exposed word, then alpha and on as in prove(), with the
+// aux trace where prove() has the key: second matrix of the quotient kernels, first round of the opening.
+// TSPF v4.
+std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                const AuxSource& aux_source) {
+    const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
+    TS_REQUIRE(air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
+               "prove_aux: preprocessed columns together with aux columns need a third matrix in the kernels");
+    const uint32_t aw = air.aux_width;
+    TS_REQUIRE((aux_source != nullptr) == (aw > 0), TS_ERR_INVALID,
+               "prove_aux: an AIR with aux columns needs an aux source, and only such an AIR takes one");
+    TS_REQUIRE(aw > 0 || air.n_exposed == 0, TS_ERR_INVALID, "prove_aux: exposed words without aux columns");
+    TS_REQUIRE(!aw || trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
+               "prove_aux: the trace must be row-major (it is handed to the aux source after its commit)");
+    pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
+    const uint64_t n = trace.height;
+
+    std::vector<DeviceMatrix> tv;
+    tv.push_back(std::move(trace));
+    // the LDE stage transposes a row-major trace into a buffer of its own and never writes the input: kept, not copied
+    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, {1u}, true, /*keep_row_major=*/aw > 0);
+    challenger.observe_commitment(trace_data->root);
+    std::vector<uint32_t> pis = public_values;
+    for (uint32_t k = 0; k < air.n_challenges; k++) {
+        const Ef c = challenger.sample();
+        pis.insert(pis.end(), c.c, c.c + 4);
+    }
+    std::unique_ptr<PcsData> aux_data;
+    std::vector<uint32_t> exposed(air.n_exposed, 0);
+    if (aw) {
+        DeviceMatrix aux = aux_source(tv[0], pis.data() + public_values.size(), exposed.data());
+        tv[0].buf.reset();  // the trace's rows are not read again
+        TS_REQUIRE(aux.buf.p && aux.buf.ctx == &pcs.ctx(), TS_ERR_INVALID,
+                   "prove_aux: the aux matrix is consumed or was made on another context");
+        TS_REQUIRE(aux.height == n && aux.width == aw, TS_ERR_INVALID,
+                   "prove_aux: the aux matrix must have the trace's height and the AIR's aux width");
+        for (uint32_t e : exposed) TS_REQUIRE(e < P, TS_ERR_INVALID, "prove_aux: non-canonical exposed word");
+        std::vector<DeviceMatrix> av;
+        av.push_back(std::move(aux));
+        aux_data = pcs.commit(av, {1u});
+        challenger.observe_commitment(aux_data->root);
+        for (uint32_t e : exposed) challenger.observe(e);
+    }
+    pis.insert(pis.end(), exposed.begin(), exposed.end());
+    const Ef alpha = challenger.sample();
+
+    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, pis, alpha, aux_data.get());
+    std::unique_ptr<PcsData> quotient_data =
+        pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));
+    challenger.observe_commitment(quotient_data->root);
+    const Ef zeta = challenger.sample();
+
+    const Ef batch_alpha = challenger.sample();
+    std::vector<Ef> opened;
+    std::vector<DevBuf<Ef>> inputs;
+    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, aux_data.get()));
+
+    std::vector<uint32_t> pf;
+    pf.reserve(64 + exposed.size() + opened.size() * 4);
+    ProofWriter pw(pf);
+    pw.header(4, st.log_degree, st.w, st.qd, aw);
+    const uint32_t more[2] = {air.n_challenges, air.n_exposed};
+    pw.words(more, 2);
+    pw.commitment(trace_data->root, 8);
+    if (aw) {
+        pw.commitment(aux_data->root, 8);
+        pw.words(exposed.data(), exposed.size());
+    }
+    pw.commitment(quotient_data->root, 8);
+    pw.opened_values(opened);
+    std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
+    if (aw) rounds.insert(rounds.begin(), aux_data.get());
     pcs.fri_prove(inputs, {st.log_N}, challenger, rounds, pf);
     return pf;
 }

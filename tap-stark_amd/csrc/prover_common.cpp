@@ -89,7 +89,7 @@ LeafMats PcsData::leaf_mats_with_table(Context& ctx) {
 // ------------------------------------------------------------------ the LDE stage of a commitment
 void lde_stage(Context& ctx, const FriConfig& fri, std::vector<DeviceMatrix>& evals,
                const std::vector<uint32_t>& domain_shifts, uint32_t beta0, uint32_t n_beta, bool allow_pair,
-               PcsData& data) {
+               PcsData& data, bool keep_row_major) {
     TS_REQUIRE(!evals.empty() && evals.size() <= (size_t)MAX_BATCH_MATS, TS_ERR_INVALID,
                "commit: between 1 and MAX_BATCH_MATS (64) matrices per batch");
     TS_REQUIRE(evals.size() == domain_shifts.size(), TS_ERR_INVALID, "commit: one domain per matrix");
@@ -178,7 +178,7 @@ void lde_stage(Context& ctx, const FriConfig& fri, std::vector<DeviceMatrix>& ev
                   rows, beta0, n_beta, r16);
         push_lde(lde, rows, m.width);
         if (!batched) data.lde_storage.push_back(std::move(own));
-        m.buf.reset();  // consumed
+        if (!(keep_row_major && m.layout == DeviceMatrix::ROW_MAJOR)) m.buf.reset();  // consumed
     }
     if (batched) data.lde_storage.push_back(std::move(batch));
 }
@@ -207,7 +207,7 @@ Statement check_statement(const FriConfig& fri, const AirProgram& air, uint32_t 
 
 // ------------------------------------------------------------------ host numerics
 std::vector<uint32_t> air_consts_mont(const AirProgram& air, const uint32_t* pis, size_t n) {
-    TS_REQUIRE(n == air.n_public, TS_ERR_INVALID, "wrong number of public values");
+    TS_REQUIRE(n == air.n_public_slots(), TS_ERR_INVALID, "wrong number of public values");
     std::vector<uint32_t> consts(std::max<size_t>(air.const_canonical.size(), 1), 0);
     for (size_t k = 0; k < air.const_canonical.size(); k++) {
         const uint32_t v = air.const_public_idx[k] != ~0u ? pis[air.const_public_idx[k]] : air.const_canonical[k];

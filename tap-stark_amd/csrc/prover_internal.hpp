@@ -70,7 +70,9 @@ uint32_t fri_pow_witness(Context& ctx, BfChallenger& challenger, unsigned bits, 
 // matrices of one shape go through ONE set of LDE launches (TS_LDE_PAIR=0 turns that off).
 void lde_stage(Context& ctx, const FriConfig& fri, std::vector<DeviceMatrix>& evals,
                const std::vector<uint32_t>& domain_shifts, uint32_t beta0, uint32_t n_beta, bool allow_pair,
-               PcsData& data);
+               PcsData& data, bool keep_row_major = false);
+// (keep_row_major: a row-major input is only read -- it is transposed into a buffer of the stage's own -- and
+// is left to the caller instead of being released)
 
 // ---- where the reduced opening is computed on the low coset and extended (open_reduce_slab): whole LDEs without
 // a preprocessed round (the caller's test), from REDUCE_LOW_MIN_WIDTH opened columns (trace + chunk columns) up
@@ -115,7 +117,8 @@ public:
                                   size_t n_pass_through = 0);
 
     void words(const uint32_t* p, size_t n) { out_.insert(out_.end(), p, p + n); }
-    // version 1; 2 with the extra num_queries word; 3 with the extra preprocessed_width word
+    // version 1; 2 with the extra num_queries word; 3 with the extra preprocessed_width word; 4 with the extra
+    // aux_width word (the caller appends n_challenges and n_exposed)
     void header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t extra);
     void commitment(const uint32_t* roots, size_t n_words) { words(roots, n_words); }  // 8, or Q x 8 (taptrees)
     void opened_values(const std::vector<Ef>& values);

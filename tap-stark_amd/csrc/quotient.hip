@@ -374,10 +374,10 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
                      const ColMat* prep_lde) {
     TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
     // a program with preprocessed loads never runs without the matrix they read, and the matrix covers the rows
-    TS_REQUIRE((prep_lde != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVARIANT,
+    TS_REQUIRE((prep_lde != nullptr) == (air.second_width() > 0), TS_ERR_INVARIANT,
                "quotient: preprocessed LDE and the AIR's preprocessed width disagree");
     if (prep_lde)
-        TS_REQUIRE(prep_lde->d && prep_lde->width == air.preprocessed_width && prep_lde->height == trace_lde.height &&
+        TS_REQUIRE(prep_lde->d && prep_lde->width == air.second_width() && prep_lde->height == trace_lde.height &&
                        prep_lde->col_stride >= prep_lde->height,
                    TS_ERR_INVALID, "quotient: preprocessed LDE shape");
     TS_REQUIRE(log_n + log_qd <= 31, TS_ERR_INVALID, "quotient domain too large");
@@ -556,7 +556,7 @@ k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
                               unsigned long long* d_violation, const uint32_t* prep_row_major) {
-    TS_REQUIRE((prep_row_major != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVARIANT,
+    TS_REQUIRE((prep_row_major != nullptr) == (air.second_width() > 0), TS_ERR_INVARIANT,
                "check_constraints: preprocessed matrix and the AIR's preprocessed width disagree");
     // the report is row * 2^16 + constraint index (the oracle's and stark.py's format)
     TS_REQUIRE(air.n_constraints <= 65536, TS_ERR_UNSUPPORTED, "check_constraints: more than 65536 constraints");
@@ -568,7 +568,7 @@ void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_
         k_check_constraints_pre<128, false>, k_check_constraints_pre<64, false>};
     if (prep_row_major)
         return launch_interpreter(ctx, kernels_pre, air, n, trace_row_major, air.width, prep_row_major,
-                                  air.preprocessed_width, n, d_consts_mont, d_violation);
+                                  air.second_width(), n, d_consts_mont, d_violation);
     launch_interpreter(ctx, kernels, air, n, trace_row_major, air.width, n, d_consts_mont, d_violation);
 }
 

@@ -114,6 +114,10 @@ void eval_tape_ext(const AirProgram& air, const Ef* prep_local, const Ef* prep_n
             case T_MAIN: v[i] = a ? next[b] : local[b]; break;
             case T_PREP: v[i] = a ? prep_next[b] : prep_local[b]; break;
             case T_PUBLIC: v[i] = ef_from_base(pis[a]); break;
+            // version 3: the aux rows are the second matrix's; `pis` is public values ++ challenges ++ exposed
+            case T_AUX: v[i] = a ? prep_next[b] : prep_local[b]; break;
+            case T_CHALLENGE: v[i] = ef_from_base(pis[air.n_public + a]); break;
+            case T_EXPOSED: v[i] = ef_from_base(pis[air.n_public + 4 * air.n_challenges + a]); break;
             case T_IS_FIRST: v[i] = is_first; break;
             case T_IS_LAST: v[i] = is_last; break;
             case T_IS_TRANSITION: v[i] = is_trans; break;
@@ -345,11 +349,16 @@ static int fri_verify_impl(const FriConfig& fri, BfChallenger& challenger,
 // without preprocessed columns
 static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
                        const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
-                       const TapLocks* tap, bool v3 = false, const uint32_t* prep_root = nullptr);
+                       const TapLocks* tap, bool v3 = false, const uint32_t* prep_root = nullptr,
+                       std::vector<uint32_t>* exposed_out = nullptr);
 
 int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
                const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
     return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, true, preprocessed_root);
+}
+int verify_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* proof,
+               size_t n_words, const std::vector<uint32_t>& pis, std::vector<uint32_t>& exposed) {
+    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, false, nullptr, &exposed);
 }
 int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
            const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
@@ -362,16 +371,20 @@ int verify_tap(const FriConfig& fri, const AirProgram& air, BfChallenger& challe
 }
 
 static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-                       const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
-                       const TapLocks* tap, bool v3, const uint32_t* prep_root) {
-    if (pis.size() != air.n_public) return 1;
+                       const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis_in,
+                       const TapLocks* tap, bool v3, const uint32_t* prep_root, std::vector<uint32_t>* exposed_out) {
+    if (pis_in.size() != air.n_public) return 1;
+    const bool v4 = exposed_out != nullptr;  // TSPF v4: the second matrix is the aux trace, committed in the proof
+    if (v4 && air.preprocessed_width) return 1;
     Reader rb{proof, n_words};
-    if (rb.get() != 0x46505354u || rb.get() != (v3 ? 3u : tap ? 2u : 1u)) return 9;
+    if (rb.get() != 0x46505354u || rb.get() != (v4 ? 4u : v3 ? 3u : tap ? 2u : 1u)) return 9;
     const unsigned degree_bits = rb.get();
     const uint32_t pw = rb.get(), pqd = rb.get();
     if (tap && rb.get() != fri.num_queries) return 1;  // TSPF v2: roots per commitment
-    const uint32_t P_w = air.preprocessed_width;
+    const uint32_t P_w = air.second_width();           // the second matrix: preprocessed key (v3) or aux trace (v4)
     if (v3 && rb.get() != P_w) return 1;               // TSPF v3: the preprocessed width
+    if (v4 && (rb.get() != P_w || rb.get() != air.n_challenges || rb.get() != air.n_exposed)) return 1;
+    if (v4 && !P_w && air.n_exposed) return 1;
     if (rb.bad || degree_bits > 27) return 9;
     const size_t n_roots = tap ? fri.num_queries : 1, cw = 8 * n_roots;
     const unsigned lqd = air.log_quotient_degree;
@@ -379,6 +392,11 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     // verifier.rs:49-59 valid_shape
     if (pw != w || pqd != qd) return 1;
     const uint32_t* trace_root = rb.take(cw);
+    const uint32_t* exposed = nullptr;
+    if (v4 && P_w) {  // v4 order: trace root, aux root, exposed words, quotient root
+        prep_root = rb.take(8);
+        exposed = rb.take(air.n_exposed);
+    }
     const uint32_t* quot_root = rb.take(cw);
     const uint32_t* prep_local = rb.take(4 * (size_t)P_w);  // v3 order: the preprocessed rows lead
     const uint32_t* prep_next = rb.take(4 * (size_t)P_w);
@@ -398,10 +416,27 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
             for (int k = 0; k < 4; k++)
                 if (e.c[k] >= P) return 9;
 
+    for (uint32_t e = 0; exposed && e < air.n_exposed; e++)
+        if (exposed[e] >= P) return 9;
+
     // the key is part of the statement: observed before anything of the proof (prover.cpp prove)
-    if (P_w) challenger.observe_commitment(prep_root);
+    if (P_w && !v4) challenger.observe_commitment(prep_root);
     // verifier.rs:69-75
     for (size_t k = 0; k < n_roots; k++) challenger.observe_commitment(trace_root + 8 * k);
+    // v4 (prover.cpp prove_aux): the challenges, then the aux root and the exposed words; the constraints read
+    // public values ++ challenge words ++ exposed words
+    std::vector<uint32_t> pis = pis_in;
+    if (v4) {
+        for (uint32_t k = 0; k < air.n_challenges; k++) {
+            const Ef c = challenger.sample();
+            pis.insert(pis.end(), c.c, c.c + 4);
+        }
+        if (P_w) {
+            challenger.observe_commitment(prep_root);
+            for (uint32_t e = 0; e < air.n_exposed; e++) challenger.observe(exposed[e]);
+            pis.insert(pis.end(), exposed, exposed + air.n_exposed);
+        }
+    }
     const Ef alpha = challenger.sample();
     for (size_t k = 0; k < n_roots; k++) challenger.observe_commitment(quot_root + 8 * k);
     const Ef zeta = challenger.sample();
@@ -461,6 +496,7 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     Ef acc = ef_zero();
     for (uint32_t c = 0; c < air.n_constraints; c++) acc = ef_add(c_mul(acc, alpha), v[cons[c]]);
     if (!ef_eq(c_mul(acc, inv_zeroifier), quotient)) return 7;  // :157 OodEvaluationMismatch
+    if (v4) exposed_out->assign(pis.end() - (P_w ? air.n_exposed : 0), pis.end());
     return 0;
 }
 

@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .air import BaseAir, air_tape
+from .air import BaseAir, air_tape, aux_dims
 
 P = 0x78000001
 TSPF_MAGIC = 0x46505354
@@ -436,6 +436,9 @@ class CompiledAir:
         pw = C.c_uint32()
         self._l.ts_air_preprocessed_width(h, C.byref(pw))
         self.preprocessed_width = int(pw.value)
+        aw, nc, ne = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._l.ts_air_aux_info(h, C.byref(aw), C.byref(nc), C.byref(ne))
+        self.aux_width, self.n_challenges, self.n_exposed = int(aw.value), int(nc.value), int(ne.value)
 
     @property
     def is_jit(self) -> bool:
@@ -633,14 +636,22 @@ class TwoAdicFriPcs:
         self.ctx.check(self.ctx._l.ts_pcs_data_evaluations_on_domain(self.ctx.h, data.h, idx, log_size, C.byref(h)))
         return DeviceMatrix(self.ctx, h)
 
-    def quotient_chunks(self, trace_data: PcsData, air: CompiledAir, public_values, alpha, preprocessed=None):
+    def quotient_chunks(self, trace_data: PcsData, air: CompiledAir, public_values, alpha, preprocessed=None,
+                        aux=None, challenges=None, exposed=None):
         """``preprocessed``: the ``PreprocessedKey`` (or its ``PcsData``) of an AIR with preprocessed columns
-        (``ts_quotient_chunks_pre``); None is ``ts_quotient_chunks``."""
+        (``ts_quotient_chunks_pre``); None is ``ts_quotient_chunks``.  ``aux``: the committed aux trace (a
+        ``PcsData``) of an AIR with challenge-phase columns, with its ``challenges`` and ``exposed`` words
+        (``ts_quotient_chunks_aux``)."""
         qd = 1 << air.log_quotient_degree
         out = (C.c_void_p * qd)()
         pis = _u32(public_values)
         pis_p = _p(pis) if len(pis) else None
-        if preprocessed is None:
+        if aux is not None or challenges is not None or exposed is not None:
+            ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
+            self.ctx.check(self.ctx._l.ts_quotient_chunks_aux(
+                self.ctx.h, aux.h if aux is not None else None, trace_data.h, self.fri.log_blowup, air.h, pis_p,
+                len(pis), _p(ch) if len(ch) else None, _p(ex) if len(ex) else None, _p(_u32(alpha)), out))
+        elif preprocessed is None:
             self.ctx.check(self.ctx._l.ts_quotient_chunks(self.ctx.h, trace_data.h, self.fri.log_blowup,
                                                           air.h, pis_p, len(pis), _p(_u32(alpha)), out))
         else:
@@ -853,6 +864,7 @@ class Proof:
     access: ``prove()`` hands back the words without spending interpreter time on them."""
 
     _FIELDS = ("degree_bits", "trace_commit", "quotient_commit", "preprocessed_local", "preprocessed_next",
+               "version", "aux_width", "n_challenges", "aux_commit", "exposed", "aux_local", "aux_next",
                "trace_local", "trace_next", "quotient_chunks", "commit_phase_commits", "query_proofs", "final_poly", "pow_witness")
 
     def __init__(self, words):
@@ -910,21 +922,32 @@ class Proof:
             return out
 
         magic, version, degree_bits, width, qd = (int(x) for x in take(5))
-        if magic != TSPF_MAGIC or version not in (1, 2, 3):
-            raise ValueError("not a TSPF v1/v2/v3 proof")
+        if magic != TSPF_MAGIC or version not in (1, 2, 3, 4):
+            raise ValueError("not a TSPF v1/v2/v3/v4 proof")
         # v2 (proofs over the taptree MMCS, ts_prove_tap): num_queries roots per commitment, the
         # commitment fields are (num_queries, 8) arrays
         nr = int(take(1)[0]) if version == 2 else 1
         # v3 (ts_prove_pre): the preprocessed width; the opened preprocessed rows lead the opened values and
         # every query's input proof holds three BatchOpenings (key, trace, chunks)
         pw = int(take(1)[0]) if version == 3 else 0
-        d = {"degree_bits": degree_bits, "query_proofs": [], "version": version, "preprocessed_width": pw}
-        if version != 2:
+        # v4 (ts_prove_aux): aux width, challenge and exposed counts; the aux root and the exposed words sit between
+        # the two commitments, the opened aux rows lead the opened values (three BatchOpenings per query)
+        aw, nc, ne = (int(x) for x in take(3)) if version == 4 else (0, 0, 0)
+        d = {"degree_bits": degree_bits, "query_proofs": [], "version": version, "preprocessed_width": pw,
+             "aux_width": aw, "n_challenges": nc, "aux_commit": None, "exposed": np.zeros(0, dtype=np.uint32)}
+        if version == 4:
+            d["trace_commit"] = take(8)
+            if aw:
+                d["aux_commit"], d["exposed"] = take(8), take(ne)
+            d["quotient_commit"] = take(8)
+        elif version != 2:
             d["trace_commit"], d["quotient_commit"] = take(8), take(8)
         else:
             d["trace_commit"], d["quotient_commit"] = take(8 * nr).reshape(nr, 8), take(8 * nr).reshape(nr, 8)
         d["preprocessed_local"] = take(4 * pw).reshape(pw, 4)
         d["preprocessed_next"] = take(4 * pw).reshape(pw, 4)
+        d["aux_local"] = take(4 * aw).reshape(aw, 4)
+        d["aux_next"] = take(4 * aw).reshape(aw, 4)
         d["trace_local"] = take(4 * width).reshape(width, 4)
         d["trace_next"] = take(4 * width).reshape(width, 4)
         d["quotient_chunks"] = take(16 * qd).reshape(qd, 4, 4)
@@ -972,27 +995,73 @@ def _preprocessed_width(air) -> int:
     return int(f() if callable(f) else f)
 
 
-def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_values, preprocessed=None) -> Proof:
+def _air_tape_of(air, n_public: int):
+    return air_tape(air, n_public, _preprocessed_width(air), *aux_dims(air))
+
+
+def _aux_callback(ctx, air, aux, failure: list):
+    """The ``ts_aux_fn`` around ``aux(trace, challenges) -> (DeviceMatrix | ndarray, exposed)``.  An exception
+    inside becomes TS_ERR_INVALID and is kept in ``failure`` for the caller to re-raise after the call."""
+
+    def fn(_user, _ctx, trace_h, challenges, n_challenges, aux_out, exposed_out):
+        view = DeviceMatrix(ctx, C.c_void_p(trace_h))
+        try:
+            ch = np.array([challenges[k] for k in range(4 * n_challenges)], dtype=np.uint32)
+            m, exposed = aux(view, ch)
+            if not isinstance(m, DeviceMatrix):
+                m = DeviceMatrix.upload(ctx, _u32(m))
+            exposed = _u32(exposed if exposed is not None else [])
+            if len(exposed) != air.n_exposed:
+                raise ValueError(f"the aux source returned {len(exposed)} exposed words, the AIR has {air.n_exposed}")
+            for k in range(len(exposed)):
+                exposed_out[k] = int(exposed[k])
+            aux_out[0] = m.h.value
+            m.h = None  # consumed by the prover
+            return 0
+        except BaseException as e:  # nothing may unwind through the C frames
+            failure.append(e)
+            return 1
+        finally:
+            view.h = None  # the prover's trace: borrowed, never freed here
+
+    return _lib.AUX_FN(fn)
+
+
+def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_values, preprocessed=None,
+          aux=None) -> Proof:
     """``uni_stark::prove`` (reference uni-stark/src/prover.rs:25-35).
 
     ``air`` is a ``BaseAir`` (captured symbolically like ``get_symbolic_constraints``) or an
     already ``CompiledAir``; ``trace`` an (n, w) array or a ``DeviceMatrix`` (consumed).
     ``preprocessed``: the ``PreprocessedKey`` of an AIR with preprocessed columns (``ts_prove_pre``; the proof
     is TSPF v3); None is ``ts_prove``.
+    ``aux``: the aux source of an AIR with challenge-phase columns, a callable ``(trace: DeviceMatrix, challenges:
+    ndarray of 4 * n_challenges words) -> (DeviceMatrix | ndarray, exposed words)`` called once after the trace is
+    committed (``ts_prove_aux``; the proof is TSPF v4).  The trace it sees is the prover's: read it, do not keep it.
+    An exception inside it ends the proof with TS_ERR_INVALID and is re-raised here.
     """
     pcs = config.pcs
     ctx = pcs.ctx
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
-        air = CompiledAir(ctx, air_tape(air, len(pis), _preprocessed_width(air)))
+        air = CompiledAir(ctx, _air_tape_of(air, len(pis)))
     if not isinstance(trace, DeviceMatrix):
         trace = DeviceMatrix.upload(ctx, trace)
     n, w = trace.dims()
-    out = _proof_buffer(ctx, _proof_capacity(n, w + air.preprocessed_width, air.log_quotient_degree, pcs.fri))
+    out = _proof_buffer(ctx, _proof_capacity(n, w + air.preprocessed_width + air.aux_width, air.log_quotient_degree,
+                                             pcs.fri) + air.n_exposed + 16)
     n_words = C.c_size_t()
     cfg = pcs.fri._c()
     pis_p = _p(pis) if len(pis) else None
-    if preprocessed is None:
+    if aux is not None:
+        failure: list = []
+        cb = _aux_callback(ctx, air, aux, failure)
+        rc = ctx._l.ts_prove_aux(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis), cb, None,
+                                 _p(out), len(out), C.byref(n_words))
+        if failure:
+            raise failure[0]
+        ctx.check(rc)
+    elif preprocessed is None:
         ctx.check(ctx._l.ts_prove(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis),
                                   _p(out), len(out), C.byref(n_words)))
     else:
@@ -1231,20 +1300,27 @@ class VerificationError(Exception):
         self.code = code
 
 
-def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_values, preprocessed_root=None) -> None:
+def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_values, preprocessed_root=None):
     """``uni_stark::verify`` (reference uni-stark/src/verifier.rs:19-25); host only, no GPU.
     Raises ``VerificationError``; returns None on acceptance (``Ok(())``).
     ``preprocessed_root``: the root of the ``PreprocessedKey`` a TSPF v3 proof was made against
-    (``ts_verify_pre``); None is ``ts_verify``."""
+    (``ts_verify_pre``); None is ``ts_verify``.
+    A TSPF v4 proof (``ts_prove_aux``) goes to ``ts_verify_aux``, and its exposed words are returned: the statement
+    about them (``LogUp.verify``: the sum is zero) is the caller's to check."""
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
-        air = CompiledAir(None, air_tape(air, len(pis), _preprocessed_width(air)))
+        air = CompiledAir(None, _air_tape_of(air, len(pis)))
     words = _u32(proof.words if isinstance(proof, Proof) else proof)
     cfg = config.pcs.fri._c()
     verdict = C.c_int(-1)
     l = _lib.lib()
     pis_p = _p(pis) if len(pis) else None
-    if preprocessed_root is None:
+    exposed = None
+    if preprocessed_root is None and len(words) >= 2 and words[0] == TSPF_MAGIC and words[1] == 4:
+        exposed = np.zeros(air.n_exposed, dtype=np.uint32)
+        rc = l.ts_verify_aux(C.byref(cfg), air.h, challenger.h, _p(words), len(words), pis_p, len(pis),
+                             _p(exposed) if len(exposed) else None, len(exposed), C.byref(verdict))
+    elif preprocessed_root is None:
         rc = l.ts_verify(C.byref(cfg), air.h, challenger.h, _p(words), len(words), pis_p, len(pis), C.byref(verdict))
     else:
         rc = l.ts_verify_pre(C.byref(cfg), air.h, challenger.h, _p(_u32(preprocessed_root)), _p(words), len(words),
@@ -1253,21 +1329,32 @@ def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_val
         raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify").decode())
     if verdict.value != 0:
         raise VerificationError(verdict.value)
+    return exposed
 
 
-def check_constraints(air, trace, public_values, ctx: Context | None = None, preprocessed=None) -> int:
+def check_constraints(air, trace, public_values, ctx: Context | None = None, preprocessed=None, aux=None,
+                      challenges=None, exposed=None) -> int:
     """reference uni-stark/src/check_constraints.rs:11-39 on the GPU.  Returns -1 if every
     constraint holds on every row, else ``row * 65536 + constraint_index`` of the first failure.
-    ``preprocessed``: the (n, P) matrix of an AIR with preprocessed columns (``ts_check_constraints_pre``)."""
+    ``preprocessed``: the (n, P) matrix of an AIR with preprocessed columns (``ts_check_constraints_pre``).
+    ``aux``, ``challenges``, ``exposed``: the (n, aux_width) aux matrix of an AIR with challenge-phase columns, the
+    challenge words it was built for and its exposed words (``ts_check_constraints_aux``)."""
     ctx = ctx or default_context()
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
-        air = CompiledAir(ctx, air_tape(air, len(pis), _preprocessed_width(air)))
+        air = CompiledAir(ctx, _air_tape_of(air, len(pis)))
     if not isinstance(trace, DeviceMatrix):
         trace = DeviceMatrix.upload(ctx, trace)
     out = C.c_int64(-1)
     pis_p = _p(pis) if len(pis) else None
-    if preprocessed is None:
+    if aux is not None or challenges is not None or exposed is not None:
+        if aux is not None and not isinstance(aux, DeviceMatrix):
+            aux = DeviceMatrix.upload(ctx, _u32(aux))
+        ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
+        ctx.check(ctx._l.ts_check_constraints_aux(ctx.h, air.h, aux.h if aux is not None else None, trace.h, pis_p,
+                                                  len(pis), _p(ch) if len(ch) else None, _p(ex) if len(ex) else None,
+                                                  C.byref(out)))
+    elif preprocessed is None:
         ctx.check(ctx._l.ts_check_constraints(ctx.h, air.h, trace.h, pis_p, len(pis), C.byref(out)))
     else:
         if not isinstance(preprocessed, DeviceMatrix):
