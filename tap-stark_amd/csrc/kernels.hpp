@@ -54,10 +54,19 @@ void launch_transpose_unbitrev(Context& ctx, const uint32_t* src, uint64_t col_s
 // gw .. ncols-1 (same column stride), extended on its own coset shift2; `out` takes all ncols columns.
 // stage_timers = false: the passes record no "lde: ..." stage of their own (an extension that belongs to
 // another stage's time: the reduced opening's, prover.cpp).
+// A call for every coset whose input lies on one of them (lde_own_coset_used: every matrix of the call, and
+// first_round_done = false) copies the input to that block and computes the others.
 void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t ncols, unsigned log_n,
                unsigned log_blowup, uint32_t shift, uint32_t* out, uint64_t out_col_stride,
                uint32_t beta0 = 0, uint32_t n_beta = 0, bool first_round_done = false,
                uint32_t* evals2 = nullptr, uint32_t shift2 = 0, uint32_t gw = 0, bool stage_timers = true);
+
+// The block of a whole LDE that coset_lde copies from its input: ntt_plan.hpp lde_own_coset, or -1 where the
+// passes compute every block -- TS_LDE_OWN_COSET=0 (read on every call: the A/B and the tests), a blowup of 1,
+// the 2^26-row plan.  A caller that could hand coset_lde a half-transformed input (launch_transpose_bitrev_r16)
+// asks here first.
+constexpr uint32_t LDE_NO_OWN = 0xffffffffu;
+int lde_own_coset_used(unsigned log_n, unsigned log_blowup, uint32_t shift);
 
 // The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles for log_n must be there).  Each refuses
 // what the plan cannot run with the caller's wording (`lde`).
@@ -69,9 +78,11 @@ inline void ntt_require_shape(const NttPlan& p, uint32_t ncols, uint64_t stride_
 void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
                            bool first_round_done = false, uint32_t* data2 = nullptr, uint32_t gw = 0xffffffffu);
 // forward stages sA .. log_n-1 on the chunks of `n_blocks` consecutive 2^log_n-row blocks of every column, in
-// place, canonical values out (two-pass plans)
+// place, canonical values out (two-pass plans).  own_a != LDE_NO_OWN: n_blocks counts a block per column that
+// is left as it is, own_a for the columns below gw and own_b from gw on
 void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
-                           uint32_t n_blocks);
+                           uint32_t n_blocks, uint32_t gw = 0xffffffffu, uint32_t own_a = LDE_NO_OWN,
+                           uint32_t own_b = LDE_NO_OWN);
 
 // ---- ntt_dft.hip -----------------------------------------------------------------------------
 // TwoAdicSubgroupDft on its own.  Row-major matrices are 2^log_n x w, natural rows,

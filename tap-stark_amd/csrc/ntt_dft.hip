@@ -203,8 +203,10 @@ void coset_lde_batch(Context& ctx, const uint32_t* in, uint32_t* out, unsigned l
                      uint32_t shift, bool bit_reversed) {
     const uint64_t n = 1ull << log_n, N = n << added_bits;
     DevBuf<uint32_t> cols(&ctx, (size_t)w * n), lde(&ctx, (size_t)w * N);
-    // as Pcs::commit (prover_common.cpp lde_stage): the transpose takes the first inverse round where it can
-    const bool r16 = launch_transpose_bitrev_r16(ctx, in, cols.p, log_n, w, n);
+    // as Pcs::commit (prover_common.cpp lde_stage): the transpose takes the first inverse round where it can --
+    // unless the input is one of the LDE's blocks (lde_batch: shift 1), which coset_lde then copies from `cols`
+    const bool r16 = lde_own_coset_used(log_n, added_bits, shift) < 0 &&
+                     launch_transpose_bitrev_r16(ctx, in, cols.p, log_n, w, n);
     if (!r16) launch_transpose_bitrev(ctx, in, cols.p, log_n, w, n);
     coset_lde(ctx, cols.p, n, w, log_n, added_bits, shift, lde.p, N, 0, 0, r16);
     if (bit_reversed) launch_transpose_to_row_major(ctx, lde.p, N, out, N, w);

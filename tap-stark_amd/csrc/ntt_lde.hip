@@ -37,6 +37,8 @@
 // of this file turn a plan into grids.  The two contiguous kernels also serve the standalone transforms
 // (ntt_dft.hip) through launch_contig_inverse / launch_contig_forward: an inverse pass on one matrix, a
 // forward pass on one coset block.
+#include <stdlib.h>
+
 #include <optional>
 #include <type_traits>
 
@@ -106,14 +108,12 @@ k_transpose_bitrev_r16(const uint32_t* __restrict__ src, uint32_t* __restrict__ 
 // rounds of chunk i run (the 16384-element chunk leaves room for two workgroups per CU only, and with
 // 16 waves per CU nothing else covers a chunk's load latency: rocprofv3 SQ counters on 2^22 x 64,
 // log_blowup 4 showed VALU busy 0.86 with 28 % of the wave-cycles parked).
-template <int LM, int CPW = 1>
-__global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)  // CPW > 1: keep two 512-thread groups per CU
-k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                 const uint32_t* __restrict__ W) {
+template <int LM, int CPW>
+__device__ __forceinline__ void lde_fwd_contig_block(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
+                                                     const uint32_t* __restrict__ W, const uint32_t beta) {
     __shared__ uint32_t s[padded(1 << LM)];
     constexpr int NT = chunk_threads(LM);
     constexpr int NV = (1 << LM) / 4 / NT;
-    const uint32_t beta = blockIdx.z;
     uint32_t* col = out + (uint64_t)blockIdx.y * out_col_stride + ((uint64_t)beta << log_n);
     if constexpr (CPW == 1) {
         const uint32_t c = blockIdx.x;
@@ -154,6 +154,23 @@ k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned l
     }
 }
 
+template <int LM, int CPW = 1>
+__global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)  // CPW > 1: keep two 512-thread groups per CU
+k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
+                 const uint32_t* __restrict__ W) {
+    lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z);
+}
+
+// The same on all blocks but one per column, the block that is its matrix's input (own_a for the columns below
+// gw, own_b from gw on: coset_lde).  The grid's z is one short and no workgroup is launched for that block.
+template <int LM, int CPW = 1>
+__global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)
+k_lde_fwd_contig_own(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
+                     const uint32_t* __restrict__ W, uint32_t gw, uint32_t own_a, uint32_t own_b) {
+    const uint32_t own = blockIdx.y < gw ? own_a : own_b;
+    lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z + (blockIdx.z >= own ? 1u : 0u));
+}
+
 // ------------------------------------------------------------------ middle kernel
 // Tile = slots {row << row_shift + j2_0 + jj : row < 2^log_len, jj < 2^log_T} of one column
 // (row_shift = LOG_M for n > 4096, where rows are 4096 apart; 0 for n <= 4096 with log_T = 0, where
@@ -162,13 +179,16 @@ k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned l
 // PLAN 0: generic (runtime round plan).  PLAN 1: log_len = 8, log_T = 5 (n = 2^(LM + 8): 2^20 with
 // 4096-element chunks, 2^21 / 2^22 with LM = 13 / 14): two radix-16 rounds with compile-time
 // distances 2^9 and 2^5.
-template <int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, int LM = LOG_M>
+// OWN (coset_lde on every coset, beta0 = 0): block own_a of the first matrix's columns and own_b of the second's
+// is the matrix itself and has been copied; the coset loop steps over it.
+template <int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, int LM = LOG_M, bool OWN = false>
 __global__ void __launch_bounds__(NTM)
 k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* __restrict__ out,
           uint64_t out_col_stride, unsigned log_n, unsigned log_len, unsigned log_T,
           unsigned row_shift, unsigned beta0, unsigned n_cosets, const uint32_t* __restrict__ W,
           const uint32_t* __restrict__ Winv, const uint32_t* __restrict__ scale_a,
-          const uint32_t* __restrict__ evals2, const uint32_t* __restrict__ scale_b, uint32_t gw) {
+          const uint32_t* __restrict__ evals2, const uint32_t* __restrict__ scale_b, uint32_t gw,
+          uint32_t own_a, uint32_t own_b) {
     __shared__ uint32_t s[padded(TILE)];
     constexpr int PER_THREAD = TILE / NTM;
     if (PLAN == 1) {
@@ -197,6 +217,7 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
     const uint32_t* g = (col_id < gw ? evals + (uint64_t)col_id * in_col_stride
                                      : evals2 + (uint64_t)(col_id - gw) * in_col_stride) + j2_0;
     const uint32_t* __restrict__ scale = col_id < gw ? scale_a : scale_b;
+    const uint32_t own = OWN ? (col_id < gw ? own_a : own_b) : 0xffffffffu;  // one value per workgroup
     const uint32_t total = 1u << (log_len + log_T);
     const uint32_t tmask = (1u << log_T) - 1;
     if constexpr (PLAN == 1) {
@@ -260,11 +281,13 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
     if constexpr (PREFETCH) {
         const uint32_t i0 = threadIdx.x;
         scp = scale + ((uint64_t)(i0 >> 5) << LM) + (i0 & 31) + j2_0;
+        const uint32_t first = OWN && own == 0 ? 1u : 0u;  // the first coset computed
 #pragma unroll
         for (int q = 0; q < 16; q++)
-            scv[q] = (scp + ((uint64_t)beta0 << log_n))[(uint64_t)q * (NTM >> 5) << LM];
+            scv[q] = (scp + ((uint64_t)(beta0 + first) << log_n))[(uint64_t)q * (NTM >> 5) << LM];
     }
     for (uint32_t bl = 0; bl < n_cosets; bl++) {
+        if (OWN && bl == own) continue;
         const uint32_t beta = beta0 + bl;
         const uint32_t* sc = scale + ((uint64_t)beta << log_n);  // s_beta^k / n, one entry per coefficient
         __syncthreads();
@@ -278,8 +301,9 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
                 // per coefficient and coset)
 #pragma unroll
                 for (int q = 0; q < 16; q++) v[q] = mont_mul_lazy(coef[j + GP * q], scv[q]);
-                if (bl + 1 < n_cosets) {
-                    const uint32_t* nx = scp + ((uint64_t)(beta + 1) << log_n);
+                const uint32_t nb = OWN && bl + 1 == own ? bl + 2 : bl + 1;  // the next coset computed
+                if (nb < n_cosets) {
+                    const uint32_t* nx = scp + ((uint64_t)(beta0 + nb) << log_n);
 #pragma unroll
                     for (int q = 0; q < 16; q++) scv[q] = nx[(uint64_t)q * (NTM >> 5) << LM];
                 }
@@ -325,6 +349,35 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
             for (uint32_t i = threadIdx.x; i < total; i += NTM)
                 o[((uint64_t)(i >> log_T) << row_shift) + (i & tmask)] = red2p(s[pad(i)]);
         }
+    }
+}
+
+// ------------------------------------------------------------------ the block that is the input
+// out block own_a (columns below gw, from evals) / own_b (from gw on, from evals2) <- the column itself: what
+// the three passes would recompute there (ntt_plan.hpp lde_own_coset).  The words are copied as they are: every
+// producer of an LDE input stores canonical words (the quotient kernels end in mont_mul, k_reduce_low in an
+// add of two reduced products, the transposes move what a caller uploaded under the ABI's canonical rule).
+// VEC (two-pass plans: n a multiple of 4096, columns 16-byte aligned): 4096 elements per workgroup.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+k_lde_own_copy(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* __restrict__ out,
+               uint64_t out_col_stride, unsigned log_n, const uint32_t* __restrict__ evals2, uint32_t gw,
+               uint32_t own_a, uint32_t own_b) {
+    const uint32_t col = blockIdx.y;
+    const uint32_t* src = col < gw ? evals + (uint64_t)col * in_col_stride
+                                   : evals2 + (uint64_t)(col - gw) * in_col_stride;
+    uint32_t* dst = out + (uint64_t)col * out_col_stride + ((uint64_t)(col < gw ? own_a : own_b) << log_n);
+    if constexpr (VEC) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(src) + (uint64_t)blockIdx.x * 1024 + threadIdx.x;
+        uint4* d4 = reinterpret_cast<uint4*>(dst) + (uint64_t)blockIdx.x * 1024 + threadIdx.x;
+        uint4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = s4[256 * k];
+#pragma unroll
+        for (int k = 0; k < 4; k++) d4[256 * k] = v[k];
+    } else {
+        const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+        if (i < (1ull << log_n)) dst[i] = src[i];
     }
 }
 
@@ -378,14 +431,26 @@ void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint6
 // one pass); two matrices as coset_lde
 static void launch_lde_mid(Context& ctx, const NttPlan& p, const uint32_t* evals, uint64_t in_col_stride,
                            uint32_t* out, uint64_t out_col_stride, uint32_t ncols, uint32_t beta0, uint32_t n_beta,
-                           const uint32_t* scale, const uint32_t* evals2, const uint32_t* scale2, uint32_t gw) {
+                           const uint32_t* scale, const uint32_t* evals2, const uint32_t* scale2, uint32_t gw,
+                           uint32_t own_a, uint32_t own_b) {
     const uint32_t *W = ctx.d_twiddle_fwd, *Winv = ctx.d_twiddle_inv;
     const dim3 grid(p.tiles, ncols), b(NT_MID);
     const dim3 grid1(p.tiles * ncols);  // the fixed plan: 1-D, see the kernel
 #define TS_MID_ARGS \
     evals, in_col_stride, out, out_col_stride, p.log_n, p.log_len, p.log_T, p.row_shift, beta0, n_beta, W, Winv, scale, \
-        evals2, scale2, gw
-    if (p.mid == NttMid::TILE16384)
+        evals2, scale2, gw, own_a, own_b
+    // (the instantiations that step over a block run under the names of the ones that do not)
+    if (own_a != LDE_NO_OWN && p.mid == NttMid::FIXED256 && p.LM == 12)
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", (k_lde_mid<1, TILE_ELEMS, NT_MID, 12, true>), grid1, b, 0, TS_MID_ARGS);
+    else if (own_a != LDE_NO_OWN && p.mid == NttMid::FIXED256 && p.LM == 13)
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 13>)", (k_lde_mid<1, 8192, 512, 13, true>), grid1, b, 0,
+                        TS_MID_ARGS);
+    else if (own_a != LDE_NO_OWN && p.mid == NttMid::FIXED256)
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 14>)", (k_lde_mid<1, 8192, 512, 14, true>), grid1, b, 0,
+                        TS_MID_ARGS);
+    else if (own_a != LDE_NO_OWN)
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<0>", (k_lde_mid<0, TILE_ELEMS, NT_MID, LOG_M, true>), grid, b, 0, TS_MID_ARGS);
+    else if (p.mid == NttMid::TILE16384)
         TS_LAUNCH_NAMED(ctx, "(k_lde_mid<0, 16384>)", (k_lde_mid<0, 16384>), grid, b, 0, TS_MID_ARGS);
     else if (p.mid == NttMid::FIXED256 && p.LM == 12)
         TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", k_lde_mid<1>, grid1, b, 0, TS_MID_ARGS);
@@ -399,16 +464,28 @@ static void launch_lde_mid(Context& ctx, const NttPlan& p, const uint32_t* evals
 }
 
 void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
-                           uint32_t n_blocks) {
+                           uint32_t n_blocks, uint32_t gw, uint32_t own_a, uint32_t own_b) {
     const uint32_t* W = ctx.d_twiddle_fwd;
     with_chunk_log(p.LM, [&](auto lm) {
         constexpr int LM = decltype(lm)::value;
         // 4 chunks per workgroup of the 16384-element forward pass: measured 12.22 ms per proof against
         // 12.49 with 1 and 13.34 with 2 (spills)
         constexpr int CPW = LM == 14 ? 4 : 1;
-        TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig<LM, CPW>), dim3(p.chunks / CPW, ncols, n_blocks),
-                        dim3(chunk_threads(LM)), 0, data, col_stride, p.log_n, W);
+        if (own_a != LDE_NO_OWN)  // one block per column is already there: n_blocks - 1 of them in z
+            TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig_own<LM, CPW>),
+                            dim3(p.chunks / CPW, ncols, n_blocks - 1), dim3(chunk_threads(LM)), 0, data, col_stride,
+                            p.log_n, W, gw, own_a, own_b);
+        else
+            TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig<LM, CPW>), dim3(p.chunks / CPW, ncols, n_blocks),
+                            dim3(chunk_threads(LM)), 0, data, col_stride, p.log_n, W);
     });
+}
+
+int lde_own_coset_used(unsigned log_n, unsigned log_blowup, uint32_t shift) {
+    if (const char* e = getenv("TS_LDE_OWN_COSET"); e && *e && atoi(e) == 0) return -1;
+    // one coset only: nothing would be left to launch; n = 2^26: the 16384-element tile has a CU to itself as it is
+    if (log_blowup == 0 || log_n + log_blowup > 27 || ntt_plan(log_n).mid == NttMid::TILE16384) return -1;
+    return lde_own_coset(log_n, log_blowup, shift);
 }
 
 void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t ncols, unsigned log_n,
@@ -433,9 +510,31 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
     const uint32_t* scale = coset_scale_table(ctx, log_n, log_blowup, shift);
     const uint32_t* scale2 = evals2 ? coset_scale_table(ctx, log_n, log_blowup, shift2) : nullptr;
 
+    // A whole LDE whose input lies on one of its cosets (the quotient chunks, the reduced opening): that block is
+    // copied -- now, the inverse pass works in place -- and the passes leave it out.  Every matrix of the launch
+    // must have one; an input the transpose has already run a round on is no longer the block.
+    uint32_t own_a = LDE_NO_OWN, own_b = LDE_NO_OWN;
+    if (beta0 == 0 && n_beta == n_cosets && !first_round_done && ctx.lde_pass_mask == 7u) {
+        const int a = lde_own_coset_used(log_n, log_blowup, shift);
+        const int b = evals2 ? lde_own_coset_used(log_n, log_blowup, shift2) : a;
+        if (a >= 0 && b >= 0) {
+            own_a = (uint32_t)a;
+            own_b = (uint32_t)b;
+            const uint64_t n = 1ull << log_n;
+            if (p.two_pass)
+                TS_LAUNCH_NAMED(ctx, "k_lde_own_copy", k_lde_own_copy<true>, dim3((unsigned)(n >> 12), ncols), dim3(256), 0,
+                                (const uint32_t*)evals, in_col_stride, out, out_col_stride, log_n,
+                                (const uint32_t*)evals2, gw, own_a, own_b);
+            else
+                TS_LAUNCH_NAMED(ctx, "k_lde_own_copy", k_lde_own_copy<false>, dim3((unsigned)((n + 255) / 256), ncols),
+                                dim3(256), 0, (const uint32_t*)evals, in_col_stride, out, out_col_stride, log_n,
+                                (const uint32_t*)evals2, gw, own_a, own_b);
+        }
+    }
+
     if (!p.two_pass) {
         launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2, scale2,
-                       gw);
+                       gw, own_a, own_b);
     } else {
         // (ctx.lde_pass_mask: measurement only -- ts_bench_stage runs one of the three passes alone, on
         // whatever the buffers hold, to sample its clock and power; every product path leaves it at 7)
@@ -449,8 +548,8 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
         if (stage_timers) t_rest.emplace(&ctx, "lde: strided pass + forward NTT of the owned cosets");
         if (ctx.lde_pass_mask & 2u)
             launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2,
-                           scale2, gw);
-        if (ctx.lde_pass_mask & 4u) launch_contig_forward(ctx, p, out, out_col_stride, ncols, n_beta);
+                           scale2, gw, own_a, own_b);
+        if (ctx.lde_pass_mask & 4u) launch_contig_forward(ctx, p, out, out_col_stride, ncols, n_beta, gw, own_a, own_b);
     }
     TS_HIP(hipGetLastError());
 }

@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "bb.hpp"
+
 namespace ts {
 
 constexpr int LOG_M = 12;          // default contiguous chunk = 4096 elements
@@ -69,6 +71,25 @@ inline const char* ntt_plan_refusal(const NttPlan& p, uint32_t ncols, uint64_t s
         return lde ? "coset_lde: column strides must be multiples of 4 elements"
                    : "dft: column stride must be a multiple of 4 elements";
     return nullptr;
+}
+
+// Which block of a whole coset LDE is its own input.  Block beta of coset_lde's output holds the values on the
+// coset s_beta = shift * w_N^bitrev_b(beta) of H_n (N = n << log_blowup, b = log_blowup; ntt.hip
+// k_build_shift_tables), in the row order of the input, and the input holds the values on H_n itself: where
+// s_beta = 1 the inverse transform, the scaling and the forward transform compose to the identity and, the words
+// in HBM being canonical, the block is the input word for word.  Returns that beta, or -1 if no coset is H_n
+// (the trace commit's shift 31).  The one owner of the question: coset_lde and the callers that prepare its
+// input ask here.  By the definition, over every beta, in the order of the exponent e = bitrev_b(beta).
+inline int lde_own_coset(unsigned log_n, unsigned log_blowup, uint32_t shift) {
+    const unsigned log_N = log_n + log_blowup;
+    if (log_N > 27 || shift == 0 || shift >= P) return -1;
+    // every s_beta lies in shift * H_N: outside the subgroup of order N none of them is 1
+    if (pow_canon(shift, 1ull << log_N) != 1u) return -1;
+    const uint32_t w = to_mont(two_adic_generator(log_N));
+    uint32_t s = shift;  // shift * w_N^e
+    for (uint32_t e = 0; e < (1u << log_blowup); e++, s = mont_mul(s, w))
+        if (s == 1u) return (int)bitrev32(e, log_blowup);
+    return -1;
 }
 
 }  // namespace ts
