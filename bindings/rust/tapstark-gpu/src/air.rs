@@ -136,7 +136,8 @@ where
 // trace phase and no challenge entries, so an AIR with aux columns is captured with a builder of this crate's own:
 // the mirror of `ts::air::Builder` in include/tapstark_air.hpp and of `SymbolicAirBuilder` in tap-stark_amd/air.py,
 // node for node (hash-consed {op, a, b} triples; every operator builds its nodes in the same fixed order, so the
-// three front ends give the same tape for the same `eval`).  Prove the tape with `ts_prove_aux`.
+// three front ends give the same tape for the same `eval`).  Prove the tape with `ts_prove_aux`, or -- built with
+// a `preprocessed_width` too, e.g. a `LogUp` with `LogUpTerm::Prep` terms -- with `ts_prove_pre_aux` against the key.
 const OP_AUX: u32 = 11; // a = offset 0|1, b = column < aux_width; degree multiple 1
 const OP_CHALLENGE: u32 = 12; // a = word index < 4 * n_challenges; degree multiple 0
 const OP_EXPOSED: u32 = 13; // a = index < n_exposed; degree multiple 0
@@ -286,11 +287,24 @@ impl AuxAirBuilder {
     }
 }
 
-/// A term of a LogUp interaction: `Const(canonical value)` or `Col(main column)`, read on the local row.
+/// A term of a LogUp interaction: `Const(canonical value)`, `Col(main column)` or `Prep(preprocessed column)` (a
+/// lookup against a fixed table: `ts_logup_term.kind = 2`, `ts_logup_aux_build_pre`), read on the local row.
 #[derive(Clone, Copy, Debug)]
 pub enum LogUpTerm {
     Const(u32),
     Col(u32),
+    Prep(u32),
+}
+
+impl LogUpTerm {
+    /// (kind, value) of the `ts_logup_term` this term is.
+    pub fn to_c(self) -> (u32, u32) {
+        match self {
+            LogUpTerm::Const(v) => (0, v),
+            LogUpTerm::Col(c) => (1, c),
+            LogUpTerm::Prep(c) => (2, c),
+        }
+    }
 }
 
 /// LogUp over the main trace, from the spec `ts_logup_aux_build` takes: two challenges gamma, beta; interaction i
@@ -314,6 +328,7 @@ impl LogUp {
         let term = |b: &mut AuxAirBuilder, t: LogUpTerm| match t {
             LogUpTerm::Const(v) => b.constant(v as u64),
             LogUpTerm::Col(c) => b.main(0, c),
+            LogUpTerm::Prep(c) => b.preprocessed(0, c),
         };
         let n_pow = self.interactions.iter().map(|(_, v)| v.len()).max().unwrap_or(1);
         let one = b.constant(1);

@@ -22,7 +22,8 @@ pub struct ts_air_options {
     pub reserved: u32,
 }
 
-/// `ts_logup_term`: kind 0 = the canonical constant `value`, 1 = main column `value` (local row).
+/// `ts_logup_term`: kind 0 = the canonical constant `value`, 1 = main column `value` (local row), 2 = preprocessed
+/// column `value` (local row; `ts_logup_aux_build_pre` only).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct ts_logup_term {
@@ -262,6 +263,29 @@ extern "C" {
     pub fn ts_logup_aux_width(spec: *const ts_logup_spec, aux_width: *mut u32) -> ts_status;
     pub fn ts_logup_aux_build(ctx: *mut ts_ctx, spec: *const ts_logup_spec, trace: *const ts_matrix,
                               challenges: *const u32, aux_out: *mut *mut ts_matrix, exposed_out: *mut u32) -> ts_status;
+    /// terms of kind 2 read column `value` of `preprocessed` (row-major n x preprocessed_width, not consumed)
+    pub fn ts_logup_aux_build_pre(ctx: *mut ts_ctx, spec: *const ts_logup_spec, preprocessed: *const ts_matrix,
+                                  trace: *const ts_matrix, challenges: *const u32, aux_out: *mut *mut ts_matrix,
+                                  exposed_out: *mut u32) -> ts_status;
+    // preprocessed AND aux columns together (TSPF v5): the _pre and _aux calls' contracts; a NULL key / root / aux
+    // argument exactly for a width of 0
+    pub fn ts_prove_pre_aux(ctx: *mut ts_ctx, cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
+                            key: *const ts_pcs_data, trace: *mut ts_matrix, public_values: *const u32, n_public: u32,
+                            aux_fn: ts_aux_fn, user: *mut c_void, proof_out: *mut u32, cap_words: usize,
+                            n_words_out: *mut usize) -> ts_status;
+    pub fn ts_verify_pre_aux(cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,
+                             preprocessed_root: *const u32, proof: *const u32, n_words: usize,
+                             public_values: *const u32, n_public: u32, exposed_out: *mut u32, cap_exposed: u32,
+                             verdict: *mut c_int) -> ts_status;
+    pub fn ts_quotient_chunks_pre_aux(ctx: *mut ts_ctx, key: *const ts_pcs_data, aux_data: *const ts_pcs_data,
+                                      trace_data: *const ts_pcs_data, log_blowup: u32, air: *const ts_air,
+                                      public_values: *const u32, n_public: u32, challenges: *const u32,
+                                      exposed: *const u32, alpha: *const u32,
+                                      chunks_out: *mut *mut ts_matrix) -> ts_status;
+    pub fn ts_check_constraints_pre_aux(ctx: *mut ts_ctx, air: *const ts_air, preprocessed: *const ts_matrix,
+                                        aux: *const ts_matrix, trace: *const ts_matrix, public_values: *const u32,
+                                        n_public: u32, challenges: *const u32, exposed: *const u32,
+                                        first_violation: *mut i64) -> ts_status;
     pub fn ts_proof_to_postcard(proof: *const u32, n_words: usize, out: *mut u8, cap_bytes: usize,
                                 n_bytes_out: *mut usize) -> ts_status;
     /// tspf_version: 0 infer, 1 / 2 explicit (a taptree proof with one query needs 2)

@@ -223,9 +223,10 @@ ts_status ts_matrix_bit_reverse_rows(ts_ctx* ctx, const ts_matrix* in, ts_matrix
  * these ops in a version-1 or version-2 tape, an index out of range, an offset > 1.  Lowering: AUX takes the
  * LOAD operands PREP takes (a = 2, 3), CHALLENGE k the public slot n_public + k, EXPOSED e the slot n_public +
  * 4 n_challenges + e; the kernels see (aux LDE, trace LDE) where they see (key LDE, trace LDE), and the vector
- * public values ++ challenges ++ exposed.  A tape with preprocessed_width > 0 AND aux_width > 0 compiles (degree
- * rules, host use), but every proving call returns TS_ERR_UNSUPPORTED for it: a third matrix in the kernels is
- * not built yet. */
+ * public values ++ challenges ++ exposed.  A tape with preprocessed_width > 0 AND aux_width > 0 reads three
+ * matrices: PREP keeps a = 2, 3 and AUX takes a = 4, 5, the local and next row of a THIRD matrix; the public slots
+ * are unchanged.  Only the ts_*_pre_aux calls below prove, check and verify such an AIR; every other proving call
+ * returns TS_ERR_UNSUPPORTED for it, before anything is consumed. */
 /* ctx == NULL builds a host-only AIR (degree rules + verifier use; no kernels) */
 ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out);
 /* get_log_quotient_degree, uni-stark/src/symbolic_builder.rs:15-32 */
@@ -257,8 +258,10 @@ void ts_air_free(ts_ctx* ctx, ts_air* air);
  * straight-line HIP source compiled with hiprtc (csrc/jit.cpp); tests interpret the former and
  * compile the latter against the oracle's direct evaluation of the tape.
  * ts_air_program: out = [n_regs, n_instr, n_consts, n_instr x {op,dst,a,b}, n_consts x canonical
- *   value, n_consts x (public-value index or 0xffffffff)]; ops: 0 LOAD(a=row offset + 2 * preprocessed,
- *   b=column): a = 0 / 1 the main trace's local / next row, a = 2 / 3 the preprocessed matrix's (version-2 tapes)
+ *   value, n_consts x (public-value index or 0xffffffff)]; ops: 0 LOAD(a=row offset + 2 * matrix,
+ *   b=column): a = 0 / 1 the main trace's local / next row, a = 2 / 3 the second matrix's (the preprocessed columns
+ *   of a version-2 tape, or the aux columns of a version-3 tape without preprocessed columns), a = 4 / 5 the
+ *   third's (the aux columns of a version-3 tape that has preprocessed columns too)
  *   1 CONST(a=const index) 2 SEL(a=0 first|1 last|2 transition) 3 ADD 4 SUB 5 NEG 6 MUL
  *   7 ASSERT(a=register, b=constraint index).  TS_ERR_BUFFER (with *n_words set) if cap is short.
  * ts_air_jit_source: the HIP source (not NUL-terminated; *n_bytes set even on TS_ERR_BUFFER).
@@ -822,12 +825,64 @@ ts_status ts_verify_aux(const ts_fri_config* cfg, const ts_air* air, ts_challeng
  * inside the trace, canonical constants.  A zero denominator gives TS_ERR_INVARIANT with the first row and
  * interaction in the last error, and no output.  TS_LOGUP_BLOCK_ROWS (1 .. 1024, read on every call) shrinks the
  * rows one workgroup owns: a test knob. */
-typedef struct { uint32_t kind /* 0 constant (canonical), 1 main column, local row */; uint32_t value; } ts_logup_term;
+typedef struct { uint32_t kind /* 0 constant (canonical), 1 main column, local row; 2 preprocessed column, local
+                                  row: ts_logup_aux_build_pre only */; uint32_t value; } ts_logup_term;
 typedef struct { ts_logup_term multiplicity; uint32_t n_values; const ts_logup_term* values; } ts_logup_interaction;
 typedef struct { uint32_t struct_size, n_interactions; const ts_logup_interaction* interactions; } ts_logup_spec;
 ts_status ts_logup_aux_width(const ts_logup_spec* spec, uint32_t* aux_width);  /* 4 * (ceil(K/2) + 1) */
 ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* trace,
                              const uint32_t challenges[8], ts_matrix** aux_out, uint32_t exposed_out[4]);
+/* The same with terms of kind 2: column `value` of the PREPROCESSED matrix, local row -- a lookup against a fixed
+ * table.  `preprocessed` is the row-major n x preprocessed_width matrix of the key's values on this context (not
+ * consumed; ts_pcs_commit consumes the matrix a key is made from, so the caller keeps a second upload or a
+ * ts_matrix_from_device copy of ts_matrix_device_ptr for this call); NULL is allowed for a spec without kind-2
+ * terms.  TS_ERR_INVALID with nothing consumed: a table of another height or context, a column >= its width.
+ * Same launches, batching, knob and zero-denominator report as ts_logup_aux_build, which keeps refusing kind 2
+ * (as does ts_logup_aux_width: the width is 4 * (ceil(K/2) + 1) whatever the kinds). */
+ts_status ts_logup_aux_build_pre(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* preprocessed,
+                                 const ts_matrix* trace, const uint32_t challenges[8], ts_matrix** aux_out,
+                                 uint32_t exposed_out[4]);
+
+/* ------------------------------------------------------------------ preprocessed AND aux columns together
+ * An AIR with preprocessed_width > 0 and aux_width > 0 (a lookup against a FIXED table: the table is in a key
+ * the verifier holds the root of).  These four calls extend their _pre and _aux parents and keep their contracts.
+ * ts_prove_pre_aux extends ts_prove_pre (the key: committed once, observed first, not consumed, not in the proof)
+ * and ts_prove_aux (the challenges, the callback, the aux commit, the exposed words).  Transcript: (1) observe the
+ * key's root; (2) commit the trace, observe its root; (3) sample n_challenges; (4) call aux_fn with the live
+ * row-major trace; (5) commit the aux matrix, observe its root and each exposed word; (6) alpha; (7) the quotient
+ * over (key LDE, aux LDE, trace LDE); (8) commit the chunks; (9) zeta; (10) the batch challenge; (11) open four
+ * rounds: key at {zeta, zeta omega}, aux at {zeta, zeta omega}, trace at {zeta, zeta omega}, chunks at {zeta}.
+ * Proof = TSPF v5: the v4 header followed by the preprocessed width; opened values
+ * preprocessed_local, preprocessed_next, aux_local, aux_next, trace_local, trace_next, chunks; four BatchOpenings
+ * per query.  No postcard form (TS_ERR_UNSUPPORTED).
+ * TS_ERR_INVALID with the last error set, before any device work and with the trace not consumed: a null
+ * argument, a key of another width, height or context.  An aux matrix of another shape or context: TS_ERR_INVALID.
+ * With preprocessed_width 0 the key (and the root) must be NULL and the result is that of the _aux call but for the
+ * header; with aux_width 0 aux_fn must be NULL and the result is that of the _pre call but for the header.
+ * ts_aux_fn is unchanged: a callback that reads the table carries its own row-major copy behind `user`
+ * (ts_logup_aux_build_pre above).
+ * ts_verify_pre_aux extends ts_verify_pre (preprocessed_root) and ts_verify_aux (exposed_out); host only.  A proof
+ * of another TSPF version (*verdict = 9) or with other header words than the AIR's (*verdict = 1) is refused as an
+ * argument, TS_ERR_INVALID; every other verify call answers a v5 proof with verdict 9.
+ * ts_quotient_chunks_pre_aux extends ts_quotient_chunks_pre / _aux: key and aux_data are each one committed
+ * matrix on the natural domain (NULL iff the width is 0).  ts_check_constraints_pre_aux extends
+ * ts_check_constraints_pre / _aux: three row-major matrices of one height. */
+ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                           const ts_pcs_data* key /* not consumed */, ts_matrix* trace /* consumed */,
+                           const uint32_t* public_values, uint32_t n_public, ts_aux_fn aux_fn, void* user,
+                           uint32_t* proof_out, size_t cap_words, size_t* n_words_out);
+ts_status ts_verify_pre_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                            const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
+                            const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
+                            uint32_t cap_exposed, int* verdict);
+ts_status ts_quotient_chunks_pre_aux(ts_ctx* ctx, const ts_pcs_data* key, const ts_pcs_data* aux_data,
+                                     const ts_pcs_data* trace_data, uint32_t log_blowup, const ts_air* air,
+                                     const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                     const uint32_t* exposed, const uint32_t alpha[4], ts_matrix** chunks_out);
+ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
+                                       const ts_matrix* aux, const ts_matrix* trace, const uint32_t* public_values,
+                                       uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                                       int64_t* first_violation);
 
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);

@@ -258,7 +258,8 @@ inline Filtered Builder::when_transition() { return when(is_transition()); }
 // No d is zero, so these determine the aux matrix from trace and challenges.  The statement "S = 0" is the
 // caller's to check after ts_verify_aux.
 struct LogUpTerm {
-    uint32_t kind;   // 0: the canonical constant `value`; 1: main column `value`, local row
+    uint32_t kind;   // 0: the canonical constant `value`; 1: main column `value`, local row; 2: preprocessed
+                     // column `value`, local row (a lookup against a fixed table: ts_logup_aux_build_pre)
     uint32_t value;
 };
 struct LogUpInteraction {
@@ -279,7 +280,10 @@ public:
         const auto& main = b.local();
         const auto &aux = b.aux(0), &aux_next = b.aux(1);
         const ExtExpr gamma = b.challenge(0), beta = b.challenge(1);
-        auto term = [&](LogUpTerm t) { return t.kind == 0 ? b.constant(t.value) : main.at(t.value); };
+        const auto& prep = b.preprocessed(0);
+        auto term = [&](LogUpTerm t) {
+            return t.kind == 0 ? b.constant(t.value) : t.kind == 2 ? prep.at(t.value) : main.at(t.value);
+        };
         size_t n_pow = 0;
         for (auto& it : its_) n_pow = it.values.size() > n_pow ? it.values.size() : n_pow;
         std::vector<ExtExpr> beta_pow{ExtExpr::from_base(b, 1)};

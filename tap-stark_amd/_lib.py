@@ -28,7 +28,8 @@ ABI_SYMBOLS = [
     "ts_chal_sample_bits", "ts_chal_check_witness", "ts_chal_grind", "ts_chal_state", "ts_prove", "ts_prove_stream", "ts_prove_batch", "ts_prove_sharded", "ts_verify", "ts_check_constraints",
     "ts_air_preprocessed_width", "ts_quotient_chunks_pre", "ts_prove_pre", "ts_verify_pre", "ts_check_constraints_pre",
     "ts_air_aux_info", "ts_quotient_chunks_aux", "ts_check_constraints_aux", "ts_prove_aux", "ts_verify_aux",
-    "ts_logup_aux_width", "ts_logup_aux_build",
+    "ts_logup_aux_width", "ts_logup_aux_build", "ts_logup_aux_build_pre",
+    "ts_prove_pre_aux", "ts_verify_pre_aux", "ts_quotient_chunks_pre_aux", "ts_check_constraints_pre_aux",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -310,6 +311,18 @@ def lib() -> C.CDLL:
                                     C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_int)]
         l.ts_logup_aux_width.argtypes = [C.POINTER(LogupSpecC), u32p]
         l.ts_logup_aux_build.argtypes = [C.c_void_p, C.POINTER(LogupSpecC), C.c_void_p, u32p, voidpp, u32p]
+        l.ts_logup_aux_build_pre.argtypes = [C.c_void_p, C.POINTER(LogupSpecC), C.c_void_p, C.c_void_p, u32p, voidpp,
+                                             u32p]
+        # preprocessed and aux columns together: the key / root / aux arguments may be NULL (a width of 0)
+        l.ts_quotient_chunks_pre_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                 C.c_void_p, u32p, C.c_uint32, u32p, u32p, u32p, voidpp]
+        l.ts_check_constraints_pre_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32p,
+                                                   C.c_uint32, u32p, u32p, C.POINTER(C.c_int64)]
+        l.ts_prove_pre_aux.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, u32p, C.c_uint32, AUX_FN, C.c_void_p, u32p, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]
+        l.ts_verify_pre_aux.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, u32p, u32p, C.c_size_t, u32p,
+                                        C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_int)]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

@@ -368,8 +368,8 @@ def aux_dims(air) -> tuple[int, int, int]:
 # ---------------------------------------------------------------------------------------------- LogUp
 class LogUp:
     """LogUp over the main trace (include/tapstark.h, csrc/logup.hip).  ``interactions`` is a list of
-    ``(multiplicity, [values...])``; a term is ``("const", canonical value)`` or ``("col", main column)``, read on
-    the local row.  Two challenges gamma, beta; interaction i has d_i = gamma + sum_j beta^j v_ij and the fraction
+    ``(multiplicity, [values...])``; a term is ``("const", canonical value)``, ``("col", main column)`` or
+    ``("prep", preprocessed column)`` (a lookup against a fixed table; kind 2), read on the local row.  Two challenges gamma, beta; interaction i has d_i = gamma + sum_j beta^j v_ij and the fraction
     m_i / d_i; group g pairs interactions 2g and 2g+1; aux columns 4g..4g+3 hold the group's sum h_g, the last
     four the exclusive running sum phi, and the four exposed words the total S.
 
@@ -387,14 +387,15 @@ class LogUp:
     @staticmethod
     def _term(t):
         kind, value = t
-        kind = {"const": 0, "col": 1}.get(kind, kind)
+        kind = {"const": 0, "col": 1, "prep": 2}.get(kind, kind)
         return int(kind), int(value) % P if kind == 0 else int(value)
 
     def eval(self, builder) -> None:
         main = builder.main().row_slice(0)
         aux, aux_next = builder.aux().row_slice(0), builder.aux().row_slice(1)
         gamma, beta = builder.challenges()[:2]
-        term = lambda t: builder.constant(t[1]) if t[0] == 0 else main[t[1]]
+        prep = builder.preprocessed().row_slice(0)
+        term = lambda t: builder.constant(t[1]) if t[0] == 0 else (prep[t[1]] if t[0] == 2 else main[t[1]])
         n_pow = max(len(vals) for _, vals in self.interactions)
         beta_pow = [ExtExpr.from_base(builder, 1)]
         for _ in range(1, n_pow):
@@ -435,8 +436,14 @@ class LogUp:
         import ctypes as C
         return _lib.LogupSpecC(C.sizeof(_lib.LogupSpecC), len(self.interactions), its), (its, keep)
 
-    def build(self, trace, challenges):
-        """``ts_logup_aux_build``: (aux ``DeviceMatrix``, the four exposed words)."""
+    @property
+    def reads_preprocessed(self) -> bool:
+        return any(t[0] == 2 for m, vals in self.interactions for t in [m, *vals])
+
+    def build(self, trace, challenges, preprocessed=None):
+        """``ts_logup_aux_build``: (aux ``DeviceMatrix``, the four exposed words).  ``preprocessed``: the row-major
+        ``DeviceMatrix`` of the table's values, for a spec with ``("prep", c)`` terms (``ts_logup_aux_build_pre``;
+        not consumed)."""
         import ctypes as C
         from . import _lib
         from .stark import DeviceMatrix
@@ -446,14 +453,24 @@ class LogUp:
         if len(ch) != 8:
             raise ValueError("LogUp takes two challenges (eight words)")
         h, exposed = C.c_void_p(), np.zeros(4, dtype=np.uint32)
-        ctx.check(ctx._l.ts_logup_aux_build(ctx.h, C.byref(spec), trace.h, ch.ctypes.data_as(_lib.u32p), C.byref(h),
-                                            exposed.ctypes.data_as(_lib.u32p)))
+        if preprocessed is not None:
+            ctx.check(ctx._l.ts_logup_aux_build_pre(ctx.h, C.byref(spec), preprocessed.h, trace.h,
+                                                    ch.ctypes.data_as(_lib.u32p), C.byref(h),
+                                                    exposed.ctypes.data_as(_lib.u32p)))
+        else:
+            ctx.check(ctx._l.ts_logup_aux_build(ctx.h, C.byref(spec), trace.h, ch.ctypes.data_as(_lib.u32p), C.byref(h),
+                                                exposed.ctypes.data_as(_lib.u32p)))
         del keep
         return DeviceMatrix(ctx, h), exposed
 
     @property
     def aux_source(self):
         return self.build
+
+    def aux_source_with(self, preprocessed):
+        """The aux source of a spec with ``("prep", c)`` terms: ``preprocessed`` is the table's row-major
+        ``DeviceMatrix`` (``PreprocessedKey.values``)."""
+        return lambda trace, challenges: self.build(trace, challenges, preprocessed)
 
     @staticmethod
     def verify(exposed) -> None:

@@ -754,3 +754,40 @@ def generate_range_lookup_trace(n: int, seed: int = SPLITMIX_SEED, outside_row: 
     out[:, 1] = np.arange(n)
     out[:, 2] = (P - counts) % P
     return out
+
+
+# ---------------------------------------------------------------------------------------------- TableLookupAir
+# The same range check as a real AIR states it: the table is a PREPROCESSED column, committed once in a key the
+# verifier holds the root of, so nothing of the statement rests on a column the prover fills in.
+
+
+class TableLookupAir(BaseAir):
+    """Main columns (value, mult), one preprocessed column (table); every ``value`` is an entry of the table.
+
+    LogUp over K = 2 interactions, (+1, value) and (mult, table): ``mult`` holds MINUS the number of rows whose
+    value equals the row's table entry.  There are no other constraints: what the table holds is fixed by the
+    key (``generate_lookup_table``), not by the AIR.  Proved with ``prove(..., preprocessed=key,
+    aux=TableLookupAir.logup.aux_source_with(key.values))``; the sum being zero is the caller's to check."""
+
+    logup = LogUp([(("const", 1), [("col", 0)]), (("col", 1), [("prep", 0)])])
+    preprocessed_width = 1
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 2
+
+    def eval(self, builder) -> None:
+        self.logup.eval(builder)
+
+
+def generate_lookup_table(n: int) -> np.ndarray:
+    """(n, 1) canonical u32: the table 0 .. n-1 of TableLookupAir's key."""
+    assert n & (n - 1) == 0
+    return np.arange(n, dtype=np.uint32).reshape(n, 1)
+
+
+def generate_table_lookup_trace(n: int, seed: int = SPLITMIX_SEED, outside_row: int | None = None) -> np.ndarray:
+    """(n, 2) canonical u32 satisfying TableLookupAir against ``generate_lookup_table(n)``: the value and
+    multiplicity columns of ``generate_range_lookup_trace``."""
+    t = generate_range_lookup_trace(n, seed, outside_row)
+    return np.ascontiguousarray(t[:, [0, 2]])

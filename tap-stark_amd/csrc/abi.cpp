@@ -288,6 +288,8 @@ ts_status ts_proof_to_postcard(const uint32_t* proof, size_t n_words, uint8_t* o
                    "TSPF v3 proofs (ts_prove_pre) have no postcard form");
         TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 4), ts::TS_ERR_UNSUPPORTED,
                    "TSPF v4 proofs (ts_prove_aux) have no postcard form");
+        TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 5), ts::TS_ERR_UNSUPPORTED,
+                   "TSPF v5 proofs (ts_prove_pre_aux) have no postcard form");
         TS_REQUIRE(ts::tspf_to_postcard(proof, n_words, b), ts::TS_ERR_INVALID, "not a TSPF v1 proof");
         *n_bytes_out = b.size();
         TS_REQUIRE(b.size() <= cap_bytes, ts::TS_ERR_BUFFER, "postcard buffer too small");
@@ -1654,6 +1656,21 @@ ts_status ts_verify_aux(const ts_fri_config* cfg, const ts_air* air, ts_challeng
 
 // ------------------------------------------------------------------ LogUp aux columns
 namespace {
+// The key of the ts_*_pre_aux calls (as preprocessed_key above, for an AIR that may have aux columns too).
+const ts::PcsData* preprocessed_key_any(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key, const char* call) {
+    const uint32_t pw = air->a.prog().preprocessed_width;
+    TS_REQUIRE((key != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
+               (std::string(call) + (pw ? ": null preprocessed key for an AIR with preprocessed columns"
+                                        : ": a preprocessed key was given for an AIR without preprocessed columns")).c_str());
+    if (!key) return nullptr;
+    TS_REQUIRE(key->d && key->d->ldes.size() == 1, ts::TS_ERR_INVALID,
+               "preprocessed key: exactly one committed matrix expected");
+    TS_REQUIRE(key->d->ldes[0].width == pw, ts::TS_ERR_INVALID,
+               "preprocessed key: width differs from the AIR's preprocessed width");
+    TS_REQUIRE(key->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "preprocessed key was made on another context");
+    return key->d.get();
+}
+
 ts::LogupSpec load_logup_spec(const ts_logup_spec* spec) {
     TS_REQUIRE(spec && spec->struct_size >= sizeof(ts_logup_spec), ts::TS_ERR_INVALID, "logup: null spec or bad struct_size");
     TS_REQUIRE(spec->n_interactions >= 1 && spec->n_interactions <= ts::LOGUP_MAX_INTERACTIONS && spec->interactions,
@@ -1690,6 +1707,191 @@ ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_ma
         auto m = std::make_unique<ts_matrix>();
         m->m = ts::logup_aux_build(ctx->ctx, s, trace->m, challenges, exposed_out);
         *aux_out = m.release();
+    });
+}
+
+// ts_logup_aux_build with terms of kind 2: columns of a row-major table of the trace's height (the values of a
+// preprocessed key; not consumed)
+ts_status ts_logup_aux_build_pre(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* preprocessed,
+                                 const ts_matrix* trace, const uint32_t challenges[8], ts_matrix** aux_out,
+                                 uint32_t exposed_out[4]) {
+    if (!ctx || !trace || !challenges || !aux_out || !exposed_out) {
+        if (ctx) ctx->ctx.last_error = "ts_logup_aux_build_pre: null argument";
+        return TS_ERR_INVALID;
+    }
+    *aux_out = nullptr;
+    return guard(ctx, [&] {
+        const ts::LogupSpec s = load_logup_spec(spec);
+        auto m = std::make_unique<ts_matrix>();
+        m->m = ts::logup_aux_build(ctx->ctx, s, trace->m, challenges, exposed_out, preprocessed ? &preprocessed->m : nullptr,
+                                   /*takes_table=*/true);
+        *aux_out = m.release();
+    });
+}
+
+// ------------------------------------------------------------------ preprocessed and aux columns together
+// Extends ts_quotient_chunks_pre and ts_quotient_chunks_aux: the quotient over (key, aux, trace).
+ts_status ts_quotient_chunks_pre_aux(ts_ctx* ctx, const ts_pcs_data* key, const ts_pcs_data* aux_data,
+                                     const ts_pcs_data* trace_data, uint32_t log_blowup, const ts_air* air,
+                                     const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                     const uint32_t* exposed, const uint32_t alpha[4], ts_matrix** chunks_out) {
+    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) {
+        if (ctx) ctx->ctx.last_error = "ts_quotient_chunks_pre_aux: null argument";
+        return TS_ERR_INVALID;
+    }
+    return guard(ctx, [&] {
+        const ts::PcsData* k = preprocessed_key_any(ctx, air, key, "ts_quotient_chunks_pre_aux");
+        const ts::AirProgram& p = ready_prog(air);
+        TS_REQUIRE((aux_data != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+                   p.aux_width ? "null aux data for an AIR with aux columns"
+                               : "aux data was given for an AIR without aux columns");
+        if (aux_data) {
+            TS_REQUIRE(aux_data->d && aux_data->d->ldes.size() == 1 && aux_data->d->ldes[0].width == p.aux_width,
+                       ts::TS_ERR_INVALID, "aux data: exactly one committed matrix of the AIR's aux width expected");
+            TS_REQUIRE(aux_data->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "aux data was made on another context");
+        }
+        ts_fri_config raw{log_blowup, 1, 0};
+        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));
+        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
+        const ts::PcsData* a = aux_data ? aux_data->d.get() : nullptr;
+        auto chunks = pcs.quotient_chunks(*trace_data->d, p, pis, load_ef(alpha), k ? k : a, k ? a : nullptr);
+        for (size_t c = 0; c < chunks.size(); c++) {
+            auto m = std::make_unique<ts_matrix>();
+            m->m = std::move(chunks[c]);
+            chunks_out[c] = m.release();
+        }
+    });
+}
+
+// Extends ts_check_constraints_pre and ts_check_constraints_aux: three row-major matrices of one height.
+ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
+                                       const ts_matrix* aux, const ts_matrix* trace, const uint32_t* public_values,
+                                       uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                                       int64_t* first_violation) {
+    if (!ctx || !air || !trace || !first_violation) {
+        if (ctx) ctx->ctx.last_error = "ts_check_constraints_pre_aux: null argument";
+        return TS_ERR_INVALID;
+    }
+    *first_violation = -1;
+    return guard(ctx, [&] {
+        const ts::AirProgram& p = air->a.prog();
+        TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
+                   "check_constraints: needs an uploaded (row-major, unconsumed) trace");
+        TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
+        auto beside = [&](const ts_matrix* m, uint32_t width, const char* what) {
+            TS_REQUIRE((m != nullptr) == (width > 0), ts::TS_ERR_INVALID,
+                       (std::string("check_constraints: the ") + what + " matrix is needed exactly by an AIR with " + what +
+                        " columns").c_str());
+            if (m)
+                TS_REQUIRE(m->m.buf.p && m->m.layout == ts::DeviceMatrix::ROW_MAJOR && m->m.buf.ctx == &ctx->ctx &&
+                               m->m.width == width && m->m.height == trace->m.height,
+                           ts::TS_ERR_INVALID,
+                           (std::string("check_constraints: the ") + what + " matrix must be on this context, row-major, of "
+                            "the AIR's " + what + " width and the trace's height").c_str());
+        };
+        beside(preprocessed, p.preprocessed_width, "preprocessed");
+        beside(aux, p.aux_width, "aux");
+        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
+        const std::vector<uint32_t> consts = ts::air_consts_mont(p, pis.data(), pis.size());
+        ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
+        ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
+        TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, ctx->ctx.stream));
+        TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
+        const uint32_t* pp = preprocessed ? preprocessed->m.buf.p : nullptr;
+        const uint32_t* ap = aux ? aux->m.buf.p : nullptr;
+        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p, pp ? pp : ap,
+                                     pp ? ap : nullptr);
+        unsigned long long v = 0;
+        TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
+        ctx->ctx.sync();
+        *first_violation = v == ~0ull ? -1 : (int64_t)v;
+    });
+}
+
+// Extends ts_prove_pre (the key: part of the statement, not consumed) and ts_prove_aux (the callback); TSPF v5.
+ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                           const ts_pcs_data* key, ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
+                           ts_aux_fn aux_fn, void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) {
+        if (ctx) ctx->ctx.last_error = "ts_prove_pre_aux: null argument";
+        return TS_ERR_INVALID;
+    }
+    *n_words_out = 0;
+    ts_status cb_status = TS_OK;
+    const ts_status st = guard(ctx, [&] {
+        const ts::PcsData* k = preprocessed_key_any(ctx, air, key, "ts_prove_pre_aux");
+        const ts::AirProgram& p = ready_prog(air);
+        TS_REQUIRE((aux_fn != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+                   p.aux_width ? "ts_prove_pre_aux: null aux_fn for an AIR with aux columns"
+                               : "ts_prove_pre_aux: an aux_fn was given for an AIR without aux columns");
+        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        TS_REQUIRE(trace->m.buf.ctx == &ctx->ctx || !trace->m.buf.p, ts::TS_ERR_INVALID,
+                   "trace was made on another context");
+        TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+        // the key's height is known against the trace's before the trace is consumed
+        if (k) ts::check_preprocessed_key(*k, p, trace->m.height << pcs.fri().log_blowup);
+        ts::DeviceMatrix m = take_trace(trace);
+        ts::AuxSource source;
+        if (aux_fn)
+            source = [&](const ts::DeviceMatrix& live, const uint32_t* challenges, uint32_t* exposed) {
+                // as ts_prove_aux: the live trace borrowed as a ts_matrix for the call, handed back after
+                ts_matrix view;
+                view.m = std::move(const_cast<ts::DeviceMatrix&>(live));
+                ts_matrix* out = nullptr;
+                const ts_status rc = aux_fn(user, ctx, &view, challenges, p.n_challenges, &out, exposed);
+                const_cast<ts::DeviceMatrix&>(live) = std::move(view.m);
+                std::unique_ptr<ts_matrix> owned(out);
+                if (rc != TS_OK) {
+                    cb_status = rc;
+                    throw AuxCallbackFailed{rc};
+                }
+                TS_REQUIRE(owned, ts::TS_ERR_INVALID, "ts_prove_pre_aux: the aux callback returned no matrix");
+                return std::move(owned->m);
+            };
+        ts::StageTimer t(&ctx->ctx, "prove");
+        try {
+            copy_proof(ts::prove_pre_aux(pcs, p, chal->c, std::move(m), pis, k, source), proof_out, cap_words,
+                       n_words_out);
+        } catch (const AuxCallbackFailed&) {
+            const std::string inner = ctx->ctx.last_error;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_prove_pre_aux: the aux callback (aux_fn) returned status " +
+                                                    std::to_string((int)cb_status) + (inner.empty() ? "" : ": " + inner));
+        }
+    });
+    return cb_status != TS_OK ? cb_status : st;
+}
+
+// Extends ts_verify_pre (the key's root) and ts_verify_aux (the exposed words); host only.
+ts_status ts_verify_pre_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                            const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
+                            const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
+                            uint32_t cap_exposed, int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_pre_aux: null argument");
+        const ts::AirProgram& p = air->a.prog();
+        const uint32_t pw = p.preprocessed_width;
+        TS_REQUIRE((preprocessed_root != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
+                   pw ? "ts_verify_pre_aux: null preprocessed root for an AIR with preprocessed columns"
+                      : "ts_verify_pre_aux: a preprocessed root was given for an AIR without preprocessed columns");
+        TS_REQUIRE(p.n_exposed == 0 || (exposed_out && cap_exposed >= p.n_exposed), ts::TS_ERR_INVALID,
+                   "ts_verify_pre_aux: null or short buffer for the exposed words");
+        ts::FriConfig f = load_cfg(cfg);
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        if (n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != 5) {
+            *verdict = 9;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre_aux: not a TSPF v5 proof");
+        }
+        if (n_words >= 9 && proof[0] == ts::TSPF_MAGIC &&
+            (proof[5] != p.aux_width || proof[6] != p.n_challenges || proof[7] != p.n_exposed || proof[8] != pw)) {
+            *verdict = 1;
+            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre_aux: the proof's aux width, challenge or exposed count "
+                                                "or preprocessed width is not the AIR's");
+        }
+        std::vector<uint32_t> exposed;
+        *verdict = ts::verify_pre_aux(f, p, chal->c, preprocessed_root, proof, n_words, pis, exposed);
+        if (*verdict == 0 && !exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
     });
 }
 

@@ -119,12 +119,16 @@ public:
     // height), null for any other AIR
     std::vector<DeviceMatrix> quotient_chunks(const PcsData& trace_data, const AirProgram& air,
                                               const std::vector<uint32_t>& public_values, Ef alpha,
-                                              const PcsData* preprocessed = nullptr);
+                                              const PcsData* preprocessed = nullptr, const PcsData* aux = nullptr);
+    // (a version-3 AIR without preprocessed columns passes its committed aux trace as `preprocessed`: the
+    // kernels' second matrix; `aux` is the committed aux trace of an AIR that has both, the third matrix)
 
     // two_adic_pcs.rs:312-389 for the prove() shape; returns the FRI input (N EF4, device)
     // preprocessed != nullptr: a third round, opened FIRST and at the trace's two points, in the same pass
     DevBuf<Ef> open_reduce(const PcsData& trace_data, const PcsData& quotient_data, Ef zeta,
-                           Ef batch_alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed = nullptr);
+                           Ef batch_alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed = nullptr,
+                           const PcsData* aux = nullptr);
+    // aux != nullptr (with preprocessed): a fourth round, opened SECOND and at the same two points
 
     // The same two steps on a slab of the LDE: global rows [row0, row0 + rows) = whole cosets
     // beta0, beta0+1, ... (bit-reversed coset order), as held by one rank of the sharded prover.
@@ -138,10 +142,10 @@ public:
                                                    const AirProgram& air,
                                                    const std::vector<uint32_t>& public_values, Ef alpha,
                                                    uint32_t domain_shift = GENERATOR,
-                                                   const ColMat* prep_lde = nullptr);
+                                                   const ColMat* prep_lde = nullptr, const ColMat* aux_lde = nullptr);
     DevBuf<Ef> open_reduce_slab(const PcsData& trace_data, const PcsData& quotient_data, unsigned log_N,
                                 const Slab& slab, Ef zeta, Ef batch_alpha, std::vector<Ef>& opened_values,
-                                const PcsData* preprocessed = nullptr);
+                                const PcsData* preprocessed = nullptr, const PcsData* aux = nullptr);
 
     // two_adic_pcs.rs:260-419 for any rounds x matrices x points: samples the batch challenge,
     // computes the opened values ((round, matrix, point, column) order) and returns the FriProof
@@ -184,6 +188,15 @@ using AuxSource = std::function<DeviceMatrix(const DeviceMatrix& trace, const ui
 std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                                 DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                                 const AuxSource& aux_source);
+// The same over (preprocessed key, aux trace, trace) for a version-3 AIR that may have preprocessed columns too,
+// TSPF v5.  Transcript: key root, trace root, challenges, [aux source], aux root, exposed words, alpha, quotient
+// over the three matrices, chunks, zeta, the batch challenge, the four-round opening (key, aux, trace, chunks).
+// `preprocessed` null exactly for preprocessed width 0, `aux_source` null exactly for aux width 0.
+std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                    DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                    const PcsData* preprocessed, const AuxSource& aux_source);
+// throws TS_ERR_INVALID unless `aux` holds exactly one matrix of the aux width of an AIR with both kinds of column
+void check_third_matrix(const PcsData& aux, const AirProgram& air, uint64_t lde_height);
 // throws TS_ERR_INVALID unless `key` holds exactly one matrix of the AIR's preprocessed width and that LDE height
 void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height);
 
@@ -260,6 +273,10 @@ int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challe
 // the same for a TSPF v4 proof of a version-3 AIR; `exposed` receives the proof's exposed words (on accept)
 int verify_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* proof,
                size_t n_words, const std::vector<uint32_t>& public_values, std::vector<uint32_t>& exposed);
+// the same for a TSPF v5 proof against the root of the preprocessed key (null for an AIR without such columns)
+int verify_pre_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
+                   const uint32_t* preprocessed_root, const uint32_t* proof, size_t n_words,
+                   const std::vector<uint32_t>& public_values, std::vector<uint32_t>& exposed);
 
 // Pcs::verify (fri/src/two_adic_pcs.rs:421-534) for any rounds x matrices x points; same codes.
 struct PcsMatClaim {

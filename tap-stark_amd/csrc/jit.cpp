@@ -98,12 +98,16 @@ struct KernelHead {
 const char* kPrepParams = ", const u32* __restrict__ prep, u64 prep_stride";
 const char* kPrepRows = "    const u32* __restrict__ row2 = prep + r;\n    const u32* __restrict__ row3 = prep + r_next;\n";
 
-void emit_head(std::ostream& s, const KernelHead& h, bool prep) {
+// An AIR with preprocessed AND aux columns reads a third: one more pair after the prep pair, rows row4, row5.
+const char* kAuxParams = ", const u32* __restrict__ aux, u64 aux_stride";
+const char* kAuxRows = "    const u32* __restrict__ row4 = aux + r;\n    const u32* __restrict__ row5 = aux + r_next;\n";
+
+void emit_head(std::ostream& s, const KernelHead& h, bool prep, bool aux) {
     s << "extern \"C\" __global__ void __launch_bounds__(" << h.launch_bounds << ")\n" << h.name;
     s << R"SRC((const u32* __restrict__ lde, u64 col_stride, unsigned log_n, unsigned log_qd,
                const u32* __restrict__ C, const u32* __restrict__ AP, const u32* __restrict__ isf,
                const u32* __restrict__ isl, const u32* __restrict__ ist, QC qc, QO out,
-               u32 row_begin, u32 row_end)SRC" << (prep ? kPrepParams : "") << h.extra_params << R"SRC() {
+               u32 row_begin, u32 row_end)SRC" << (prep ? kPrepParams : "") << (aux ? kAuxParams : "") << h.extra_params << R"SRC() {
     const unsigned L = log_n + log_qd;
     const u32 total = 1u << L;
 )SRC" << h.row_index << R"SRC(    if (r >= row_end) return;
@@ -115,6 +119,7 @@ void emit_head(std::ostream& s, const KernelHead& h, bool prep) {
     const u32 sel0 = isf[r], sel1 = isl[r], sel2 = ist[r];
 )SRC";
     if (prep) s << kPrepRows;
+    if (aux) s << kAuxRows;
 }
 
 const char* kAccZero = "    u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;\n";
@@ -145,8 +150,10 @@ const Naming kValues{"    const u32 v", "v"};
 // a leaf (LOAD / CONST / SEL) as an expression: it has no register operands
 std::string leaf_expr(const uint32_t* ins) {
     const std::string a = std::to_string(ins[2]);
-    if (ins[0] == D_LOAD)  // the row pointer is known here: rows 2, 3 are the preprocessed matrix with its own stride
-        return "to_mont(row" + a + "[" + std::to_string(ins[3]) + (ins[2] >= 2 ? "ull * prep_stride])" : "ull * col_stride])");
+    if (ins[0] == D_LOAD)  // the row pointer is known here: rows 2, 3 are the second matrix with its own stride,
+                           // rows 4, 5 the third
+        return "to_mont(row" + a + "[" + std::to_string(ins[3]) +
+               (ins[2] >= 4 ? "ull * aux_stride])" : ins[2] >= 2 ? "ull * prep_stride])" : "ull * col_stride])");
     return (ins[0] == D_CONST ? "C[" + a + "]" : "sel" + a);
 }
 
@@ -181,7 +188,7 @@ std::string jit_quotient_source(const AirProgram& air) {
     std::ostringstream s;
     s << kHelpers;
     emit_head(s, {"256", "k_quotient_jit", "", "    const u32 r = row_begin + blockIdx.x * 256u + threadIdx.x;\n"},
-              air.second_width() > 0);
+              air.second_width() > 0, air.has_third());
     s << kAccZero;
     for (uint32_t r = 0; r < air.n_regs; r++) s << "    u32 r" << r << " = 0;\n";
     uint32_t n_assert = 0;
@@ -205,7 +212,7 @@ static std::string seg_kernel(const AirProgram& air, const SegmentPlan& plan, ui
     s << "\n";
     emit_head(s, {"256, 4", "k_quotient_seg" + std::to_string(k), ", u32* __restrict__ slab, u32 slab_rows",
                   "    const u32 t = blockIdx.x * 256u + threadIdx.x;\n    const u32 r = row_begin + t;\n"},
-              air.second_width() > 0);
+              air.second_width() > 0, air.has_third());
     s << "    u32* __restrict__ S = slab + t;\n";
     auto sl = [&](uint32_t slot) { return "S[" + std::to_string(slot) + "ull * slab_rows]"; };
     if (k == 0) {
@@ -262,7 +269,7 @@ std::vector<std::string> jit_segment_sources(const AirProgram& air, const Segmen
 // ---- optional on-disk cache of code objects (TS_JIT_CACHE_DIR): the reference pays for `Air::eval` once, at
 // build time; a prover process that restarts should not pay hiprtc again for an AIR it has compiled before.
 // Key: 128 bits of FNV-1a over (generator version, hiprtc version, arch, source).
-static const char* kGeneratorVersion = "tapstark-jit-1";
+static const char* kGeneratorVersion = "tapstark-jit-2";  // 2: a third matrix (aux beside preprocessed columns)
 
 std::string jit_cache_path(const std::string& src, const char* arch) {
     const char* dir = getenv("TS_JIT_CACHE_DIR");

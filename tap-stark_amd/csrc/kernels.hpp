@@ -175,11 +175,13 @@ struct QuotOut {
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
                      const QuotOut& out, uint64_t row_begin = 0, uint64_t row_end = 0,
-                     uint32_t shift = GENERATOR, const ColMat* prep_lde = nullptr);
+                     uint32_t shift = GENERATOR, const ColMat* prep_lde = nullptr, const ColMat* aux_lde = nullptr);
 // prep_lde: the committed LDE of the preprocessed columns of a version-2 AIR (air.preprocessed_width > 0; null
 // otherwise), column-major and bit-reversed like the trace's and of its height, with its own base and stride.
 // Such an AIR runs k_quotient_pre (or specialised kernels with the two extra parameters); every other AIR
-// launches exactly what it did before.
+// launches exactly what it did before.  (A version-3 AIR without preprocessed columns passes its aux LDE here.)
+// aux_lde: the committed aux LDE of an AIR with preprocessed AND aux columns (air.has_third(); null otherwise),
+// under the same shape rules; such an AIR runs k_quotient_pre_aux or specialised kernels with two more parameters.
 // sharded.cpp "local quotient": in place on the slab LDEs of the qd chunk matrices (4 columns each),
 // out[c] = sum_c' mix[c * qd + c'] * in[c'] per row and per column (mix: Montgomery form, device)
 void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, uint64_t rows, uint64_t col_stride,
@@ -189,8 +191,10 @@ void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, 
 // row * 2^16 + constraint index of the first violated constraint
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
-                              unsigned long long* d_violation, const uint32_t* prep_row_major = nullptr);
-// (prep_row_major: the n x preprocessed_width matrix of a version-2 AIR, null otherwise)
+                              unsigned long long* d_violation, const uint32_t* prep_row_major = nullptr,
+                              const uint32_t* aux_row_major = nullptr);
+// (prep_row_major: the n x second_width matrix of an AIR with a second matrix, null otherwise; aux_row_major: the
+// n x aux_width matrix of an AIR with preprocessed and aux columns, null otherwise: k_check_pre_aux)
 
 // ---- open.hip --------------------------------------------------------------------------------
 // d[p][i] = x_i / (z_p - x_i) (Montgomery EF4) for the low coset 31*H_n in bit-reversed order,
@@ -201,11 +205,11 @@ void launch_bary_weights(Context& ctx, unsigned log_n, const Ef* points_mont, ui
                          Ef* out, uint32_t coset_gen = 0);
 // out[col][p] = sum_i m[col][i] * d[p][i]   (canonical EF4), i over the first n rows
 // `pending` != nullptr: the finishing pass (partial sums -> out) is left to launch_bary_finish, which takes
-// up to `capacity` pending products in one launch (2; 3 for a proof with preprocessed columns)
+// up to `capacity` pending products in one launch (2; 3 for a proof with a second committed matrix, 4 with a third)
 struct BaryPending {
-    DevBuf<uint32_t> partial[3];
-    uint32_t* out[3] = {nullptr, nullptr, nullptr};
-    uint32_t n_blocks[3] = {0, 0, 0}, n_words[3] = {0, 0, 0};
+    DevBuf<uint32_t> partial[4];
+    uint32_t* out[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t n_blocks[4] = {0, 0, 0, 0}, n_words[4] = {0, 0, 0, 0};
     uint32_t n = 0, capacity = 2;
 };
 void launch_bary_dots(Context& ctx, const ColMat& m, unsigned log_n, const Ef* weights,
@@ -240,10 +244,13 @@ struct FusedReduceArgs {
 };
 void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
                          const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro,
-                         const ColMat* prep = nullptr, const Ef* prep_off_mont = nullptr);
+                         const ColMat* prep = nullptr, const Ef* prep_off_mont = nullptr,
+                         const ColMat* aux = nullptr, const Ef* aux_off_mont = nullptr);
 // prep != nullptr (k_reduce_fused_pre): the preprocessed columns' LDE, opened at the same two points BEFORE the
 // trace with the offsets prep_off_mont[2]; args.off_t then start after them and args.k0 / k1 hold the
 // preprocessed constants too.  d_alpha_pows_mont covers max(trace width, prep width, 4) powers.
+// aux != nullptr too (k_reduce_fused_pre_aux): a fourth round, the aux trace's LDE, opened at the same two points
+// after prep and before the trace with the offsets aux_off_mont[2]; the powers then cover the aux width as well.
 // The same reduced opening on the low coset only (rows t < n = 2^log_n of matrices that hold the whole LDE, no
 // preprocessed round): out = four base-field columns of n rows (stride n, canonical), to be extended by
 // coset_lde with shift 1 like a quotient chunk on 31 H_n.  `weights` = launch_bary_weights' output for

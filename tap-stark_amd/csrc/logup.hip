@@ -30,7 +30,7 @@ constexpr int LOGUP_BATCH = 4;            // denominators per base-field inversi
 constexpr int LOGUP_SCAN_THREADS = 128;   // totals per pass of k_logup_totals
 
 struct LogupDev {
-    uint32_t K, G, width, aux_width;
+    uint32_t K, G, width, aux_width, table_width;
     Ef gamma_mont;                        // gamma R
     Ef beta_pow[LOGUP_MAX_VALUES];        // beta^j R^2: times a canonical value = (beta^j v) R
     struct {
@@ -68,12 +68,15 @@ __device__ __forceinline__ Ef block_scan_inclusive(Ef v, Ef (&wave_sums)[NW], Ef
     return ef_add(v, before);
 }
 
-__device__ __forceinline__ uint32_t term_value(uint32_t kind, uint32_t val, const uint32_t* __restrict__ row) {
-    return kind ? row[val] : val;
+// kind 0: the constant; 1: column `val` of the trace's row; 2: column `val` of the table's row (ts_logup_aux_build_pre)
+__device__ __forceinline__ uint32_t term_value(uint32_t kind, uint32_t val, const uint32_t* __restrict__ row,
+                                               const uint32_t* __restrict__ table_row) {
+    return kind == 0 ? val : (kind == 1 ? row : table_row)[val];
 }
 
 // sum_g h_g(r), with the h_g written to the row's first 4 G words
-__device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __restrict__ row, uint64_t r,
+__device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __restrict__ row,
+                                        const uint32_t* __restrict__ table_row, uint64_t r,
                                         uint32_t* __restrict__ aux_row, unsigned long long* __restrict__ flag) {
     Ef sum = ef_zero();
     for (uint32_t i0 = 0; i0 < s.K; i0 += LOGUP_BATCH) {
@@ -92,13 +95,13 @@ __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __res
 #pragma unroll
                 for (int q = 0; q < LOGUP_MAX_VALUES; q++)
                     if (q < (int)nv)
-                        d = ef_add(d, ef_mul_base(s.beta_pow[q], term_value(s.it[i].kind[q], s.it[i].val[q], row)));
+                        d = ef_add(d, ef_mul_base(s.beta_pow[q], term_value(s.it[i].kind[q], s.it[i].val[q], row, table_row)));
                 ef_inv_parts(d, num[j], nrm[j]);
                 if (nrm[j] == 0) {  // d == 0: reported, and the batch goes on as if the norm were one
                     atomicMin(flag, (unsigned long long)r * s.K + i);
                     nrm[j] = R_MOD_P;
                 }
-                mult[j] = term_value(s.it[i].m_kind, s.it[i].m_val, row);
+                mult[j] = term_value(s.it[i].m_kind, s.it[i].m_val, row, table_row);
             }
             pre[j] = run;
             run = mont_mul(run, nrm[j]);
@@ -124,8 +127,12 @@ __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __res
     return sum;
 }
 
+// TABLE = false is the kernel as it was before table terms (the table row is the trace's row again and folds
+// away); TABLE = true reads a second row-major matrix
+template <bool TABLE>
 __global__ void __launch_bounds__(LOGUP_THREADS)
-k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, uint64_t n, uint32_t block_rows, uint32_t rpt,
+k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ table, uint64_t n,
+             uint32_t block_rows, uint32_t rpt,
              uint32_t* __restrict__ aux, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
     __shared__ Ef wave_sums[LOGUP_THREADS / 64];
     const uint64_t base = (uint64_t)blockIdx.x * block_rows;
@@ -135,7 +142,8 @@ k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, uint64_t n, u
         const uint64_t r = base + local;
         if (local < block_rows && r < n) {
             uint32_t* aux_row = aux + r * s.aux_width;
-            const Ef sum = logup_row(s, trace + r * s.width, r, aux_row, flag);
+            const uint32_t* row = trace + r * s.width;
+            const Ef sum = logup_row(s, row, TABLE ? table + r * s.table_width : row, r, aux_row, flag);
             *reinterpret_cast<Ef*>(aux_row + 4 * s.G) = sum;  // the phi slot, until k_logup_scan
             mine = ef_add(mine, sum);
         }
@@ -191,16 +199,17 @@ k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, ui
     }
 }
 
-uint32_t logup_aux_width(const LogupSpec& spec) {
+uint32_t logup_aux_width(const LogupSpec& spec, uint32_t max_kind) {
     const size_t K = spec.interactions.size();
     TS_REQUIRE(K >= 1 && K <= LOGUP_MAX_INTERACTIONS, TS_ERR_INVALID,
                "logup: between 1 and 16 interactions");
     for (const LogupInteraction& it : spec.interactions) {
         TS_REQUIRE(it.values.size() >= 1 && it.values.size() <= LOGUP_MAX_VALUES, TS_ERR_INVALID,
                    "logup: between 1 and 8 values per interaction");
-        TS_REQUIRE(it.multiplicity.kind <= 1, TS_ERR_INVALID, "logup: term kind must be 0 (constant) or 1 (column)");
-        for (const LogupTerm& t : it.values)
-            TS_REQUIRE(t.kind <= 1, TS_ERR_INVALID, "logup: term kind must be 0 (constant) or 1 (column)");
+        const char* kinds = max_kind >= 2 ? "logup: term kind must be 0 (constant), 1 (column) or 2 (preprocessed column)"
+                                          : "logup: term kind must be 0 (constant) or 1 (column)";
+        TS_REQUIRE(it.multiplicity.kind <= max_kind, TS_ERR_INVALID, kinds);
+        for (const LogupTerm& t : it.values) TS_REQUIRE(t.kind <= max_kind, TS_ERR_INVALID, kinds);
     }
     return 4 * ((uint32_t)(K + 1) / 2 + 1);
 }
@@ -217,11 +226,12 @@ static uint32_t logup_block_rows() {
 }
 
 DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace,
-                             const uint32_t challenges[8], uint32_t exposed[4]) {
+                             const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table,
+                             bool takes_table) {
     StageTimer t(&ctx, "logup aux build");
     LogupDev s;
     memset(&s, 0, sizeof s);
-    s.aux_width = logup_aux_width(spec);
+    s.aux_width = logup_aux_width(spec, takes_table ? 2 : 1);
     s.K = (uint32_t)spec.interactions.size();
     s.G = (s.K + 1) / 2;
     TS_REQUIRE(trace.buf.p && trace.layout == DeviceMatrix::ROW_MAJOR && trace.buf.ctx == &ctx, TS_ERR_INVALID,
@@ -229,9 +239,17 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
     TS_REQUIRE(trace.height >= 1 && trace.height <= (1ull << 27) && trace.width >= 1, TS_ERR_INVALID,
                "logup: trace height must be in [1, 2^27]");
     s.width = trace.width;
+    if (table) {
+        TS_REQUIRE(table->buf.p && table->layout == DeviceMatrix::ROW_MAJOR && table->buf.ctx == &ctx, TS_ERR_INVALID,
+                   "logup: the preprocessed table must be row-major, unconsumed and made on this context");
+        TS_REQUIRE(table->height == trace.height && table->width >= 1, TS_ERR_INVALID,
+                   "logup: the preprocessed table must have the trace's height");
+        s.table_width = table->width;
+    }
     auto term = [&](const LogupTerm& tm, uint32_t& kind, uint32_t& val) {
-        TS_REQUIRE(tm.kind ? tm.value < trace.width : tm.value < P, TS_ERR_INVALID,
-                   "logup: a column outside the trace, or a non-canonical constant");
+        TS_REQUIRE(tm.kind != 2 || table, TS_ERR_INVALID, "logup: a preprocessed-column term without a preprocessed table");
+        TS_REQUIRE(tm.kind == 2 ? tm.value < s.table_width : tm.kind ? tm.value < trace.width : tm.value < P, TS_ERR_INVALID,
+                   "logup: a column outside the trace or the preprocessed table, or a non-canonical constant");
         kind = tm.kind;
         val = tm.value;
     };
@@ -266,8 +284,13 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
     DevBuf<Ef> back(&ctx, 2);
     TS_HIP(hipMemsetAsync(back.p, 0xff, 2 * sizeof(Ef), ctx.stream));
     unsigned long long* flag = reinterpret_cast<unsigned long long*>(back.p);
-    TS_LAUNCH(ctx, k_logup_rows, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, s, trace.buf.p, n, block_rows, rpt,
-              aux.buf.p, totals.p, flag);
+    // (no spec with a kind-2 term gets here without a table: `term` above)
+    if (table)
+        TS_LAUNCH_NAMED(ctx, "k_logup_rows_pre", k_logup_rows<true>, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, s, trace.buf.p,
+                  (const uint32_t*)table->buf.p, n, block_rows, rpt, aux.buf.p, totals.p, flag);
+    else
+        TS_LAUNCH_NAMED(ctx, "k_logup_rows", k_logup_rows<false>, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, s, trace.buf.p,
+                  (const uint32_t*)nullptr, n, block_rows, rpt, aux.buf.p, totals.p, flag);
     TS_HIP(hipGetLastError());
     TS_LAUNCH(ctx, k_logup_totals, dim3(1), dim3(LOGUP_SCAN_THREADS), 0, totals.p, (uint32_t)n_blocks);
     TS_HIP(hipGetLastError());

@@ -12,7 +12,8 @@ constexpr uint32_t LOGUP_MAX_INTERACTIONS = 16;
 constexpr uint32_t LOGUP_MAX_VALUES = 8;
 
 struct LogupTerm {
-    uint32_t kind;   // 0: the canonical constant `value`; 1: main column `value`, local row
+    uint32_t kind;   // 0: the canonical constant `value`; 1: main column `value`, local row; 2: column `value` of
+                     // the preprocessed table, local row (logup_aux_build with takes_table only)
     uint32_t value;
 };
 struct LogupInteraction {
@@ -23,12 +24,15 @@ struct LogupSpec {
     std::vector<LogupInteraction> interactions;
 };
 
-// 4 * (ceil(K / 2) + 1); throws TS_ERR_INVALID on a spec outside the limits
-uint32_t logup_aux_width(const LogupSpec& spec);
+// 4 * (ceil(K / 2) + 1); throws TS_ERR_INVALID on a spec outside the limits (a term kind above max_kind included)
+uint32_t logup_aux_width(const LogupSpec& spec, uint32_t max_kind = 1);
 // The n x aux_width row-major aux matrix of `trace` (row-major, this context) for challenges = gamma ++ beta
 // (canonical), and the exposed sum S.  Throws TS_ERR_INVARIANT naming the first (row, interaction) whose
 // denominator is zero; synchronises the stream once.
+// takes_table: terms of kind 2 are allowed and read `table`, the row-major values of the preprocessed columns
+// (this context, the trace's height, not consumed; may be null for a spec without such terms).
 DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace,
-                             const uint32_t challenges[8], uint32_t exposed[4]);
+                             const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table = nullptr,
+                             bool takes_table = false);
 
 }  // namespace ts

@@ -201,16 +201,30 @@ k_bary_finish3(BaryFinishJob j0, BaryFinishJob j1, BaryFinishJob j2, uint32_t g0
                       blockIdx.x < g0 ? blockIdx.x : blockIdx.x < g0 + g1 ? blockIdx.x - g0 : blockIdx.x - g0 - g1);
 }
 
+// four jobs (preprocessed columns, aux columns, trace, quotient chunks): a kernel of its own beside the two above
+__global__ void __launch_bounds__(256)
+k_bary_finish4(BaryFinishJob j0, BaryFinishJob j1, BaryFinishJob j2, BaryFinishJob j3, uint32_t g0, uint32_t g1,
+               uint32_t g2) {
+    const uint32_t b = blockIdx.x;
+    const BaryFinishJob j = b < g0 ? j0 : b < g0 + g1 ? j1 : b < g0 + g1 + g2 ? j2 : j3;
+    bary_finish_group(j.partial, j.out, j.n_blocks, j.n_words,
+                      b < g0 ? b : b < g0 + g1 ? b - g0 : b < g0 + g1 + g2 ? b - g0 - g1 : b - g0 - g1 - g2);
+}
+
 // the finishing pass of the pending launch_bary_dots(..., pending) calls
 void launch_bary_finish(Context& ctx, BaryPending& pend) {
     if (pend.n == 0) return;
-    BaryFinishJob j[3] = {{nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}};
-    uint32_t g[3] = {0, 0, 0};
+    BaryFinishJob j[4] = {{nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0},
+                          {nullptr, nullptr, 0, 0}};
+    uint32_t g[4] = {0, 0, 0, 0};
     for (uint32_t i = 0; i < pend.n; i++) {
         j[i] = BaryFinishJob{pend.partial[i].p, pend.out[i], pend.n_blocks[i], pend.n_words[i]};
         g[i] = (pend.n_words[i] + 3) / 4;
     }
-    if (pend.n == 3)
+    if (pend.n == 4)
+        TS_LAUNCH(ctx, k_bary_finish4, dim3(g[0] + g[1] + g[2] + g[3]), dim3(256), 0, j[0], j[1], j[2], j[3], g[0], g[1],
+                  g[2]);
+    else if (pend.n == 3)
         TS_LAUNCH(ctx, k_bary_finish3, dim3(g[0] + g[1] + g[2]), dim3(256), 0, j[0], j[1], j[2], g[0], g[1]);
     else
         TS_LAUNCH(ctx, k_bary_finish, dim3(g[0] + g[1]), dim3(256), 0, j[0], j[1], g[0]);
@@ -476,9 +490,59 @@ k_reduce_fused_pre(const uint32_t* __restrict__ trace, uint64_t trace_stride, ui
     *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
 }
 
+// The same pass with the key's columns AND the aux trace's, opened in that order before the trace, each at the
+// same two points: g_p += off_p[p] S_key + off_a[p] S_aux, S_key and S_aux each shared by its two openings (the
+// constants are in k0, k1).  A kernel of its own for the reason given above PrepReduceArgs.
+struct PrepAuxReduceArgs {
+    const uint32_t* prep;
+    const uint32_t* aux;
+    uint64_t prep_stride, aux_stride;
+    uint32_t prep_width, aux_width;
+    Ef off_p[2];  // alpha^0, alpha^P (Montgomery)
+    Ef off_a[2];  // alpha^(2P), alpha^(2P + A); the trace's offsets then start at alpha^(2P + 2A)
+};
+__global__ void __launch_bounds__(256)
+k_reduce_fused_pre_aux(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width,
+                       unsigned log_h, const uint32_t* __restrict__ W, uint32_t gen_mont,
+                       const uint32_t* __restrict__ alpha_pows, FusedReduceArgs a, PrepAuxReduceArgs pa,
+                       Ef* __restrict__ ro) {
+    const uint64_t X = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // local row
+    if (X >= a.rows) return;
+    const Ef St = row_dot_alpha(trace, trace_stride, width, X, alpha_pows);
+    const uint32_t x = mont_mul(gen_mont, root_bitrev(W, log_h, a.row0 + X));
+    Ef inv_d[2];
+    inv_denoms<2>(x, a.z_mont, inv_d);
+    uint64_t acc[4] = {0, 0, 0, 0};
+    uint32_t c = 0;
+    for (; c + 2 <= a.n_chunks; c += 2) {  // (as k_reduce_fused: two width-4 chunks are one batch of eight columns)
+        uint32_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = a.chunk[c + (k >> 2)][(uint64_t)(k & 3) * a.chunk_stride + X];
+        const uint32_t* ap = a.chunk_w + 16 * c;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[j] = lazy_mac(acc[j], v[k], ap[4 * k + j]);
+            if (k & 1) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = lazy_fix(acc[j]);
+            }
+        }
+    }
+    for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
+    const Ef D{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
+    const Ef Sp = row_dot_alpha(pa.prep, pa.prep_stride, pa.prep_width, X, alpha_pows);
+    const Ef Sa = row_dot_alpha(pa.aux, pa.aux_stride, pa.aux_width, X, alpha_pows);
+    const Ef g0 = ef_sub(ef_add(ef_add(ef_add(ef_mul(St, a.off_t[0]), ef_mul(Sp, pa.off_p[0])), ef_mul(Sa, pa.off_a[0])), D),
+                         a.k0);
+    const Ef g1 = ef_sub(ef_add(ef_add(ef_mul(St, a.off_t[1]), ef_mul(Sp, pa.off_p[1])), ef_mul(Sa, pa.off_a[1])), a.k1);
+    const Ef r = ef_add(ef_mul(g0, inv_d[0]), ef_mul(g1, inv_d[1]));
+    *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
+}
+
 void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
                          const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro,
-                         const ColMat* prep, const Ef* prep_off_mont) {
+                         const ColMat* prep, const Ef* prep_off_mont, const ColMat* aux, const Ef* aux_off_mont) {
     TS_REQUIRE(args.n_chunks <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_INVALID, "reduce_fused: too many chunks");
     ctx.ensure_twiddles(log_h == 0 ? 1 : log_h);
     FusedReduceArgs a = args;
@@ -487,6 +551,20 @@ void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
         a.rows = 1ull << log_h;
     }
     TS_REQUIRE(a.row0 + a.rows <= (1ull << log_h), TS_ERR_INVALID, "reduce_fused: row range");
+    TS_REQUIRE(!aux || prep, TS_ERR_INVARIANT, "reduce_fused: a third matrix without a second");
+    if (aux) {
+        for (const ColMat* m : {prep, aux})
+            TS_REQUIRE(m->d && a.row0 == 0 && m->height == a.rows && m->col_stride >= a.rows, TS_ERR_INVALID,
+                       "reduce_fused: preprocessed or aux matrix shape");
+        TS_REQUIRE(prep_off_mont && aux_off_mont, TS_ERR_INVALID, "reduce_fused: missing offsets");
+        const PrepAuxReduceArgs pa{prep->d, aux->d, prep->col_stride, aux->col_stride, prep->width, aux->width,
+                                   {prep_off_mont[0], prep_off_mont[1]}, {aux_off_mont[0], aux_off_mont[1]}};
+        TS_LAUNCH(ctx, k_reduce_fused_pre_aux, dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
+                  (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
+                  (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, pa, ro);
+        TS_HIP(hipGetLastError());
+        return;
+    }
     if (prep) {
         TS_REQUIRE(prep_off_mont && prep->d && a.row0 == 0 && prep->height == a.rows && prep->col_stride >= a.rows,
                    TS_ERR_INVALID, "reduce_fused: preprocessed matrix shape");

@@ -114,22 +114,38 @@ void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t 
                "preprocessed key: LDE height is not the trace height << log_blowup");
 }
 
+// the committed aux trace of an AIR with preprocessed and aux columns: the kernels' third matrix
+void check_third_matrix(const PcsData& aux, const AirProgram& air, uint64_t lde_height) {
+    TS_REQUIRE(aux.ldes.size() == 1, TS_ERR_INVALID, "aux data: exactly one committed matrix expected");
+    TS_REQUIRE(air.has_third() && aux.ldes[0].width == air.third_width(), TS_ERR_INVALID,
+               "aux data: width differs from the AIR's aux width");
+    TS_REQUIRE(aux.ldes[0].height == lde_height, TS_ERR_INVALID,
+               "aux data: LDE height is not the trace height << log_blowup");
+}
+
 std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks(const PcsData& trace_data,
                                                          const AirProgram& air,
                                                          const std::vector<uint32_t>& pis, Ef alpha,
-                                                         const PcsData* preprocessed) {
+                                                         const PcsData* preprocessed, const PcsData* aux) {
     TS_REQUIRE(trace_data.ldes.size() >= 1, TS_ERR_INVALID, "quotient: no trace matrix");
     TS_REQUIRE(trace_data.log_height >= fri_.log_blowup, TS_ERR_INVALID, "quotient: bad trace data");
     if (preprocessed) check_preprocessed_key(*preprocessed, air, trace_data.ldes[0].height);
+    if (aux) check_third_matrix(*aux, air, trace_data.ldes[0].height);
     return quotient_chunks_slab(trace_data.ldes[0], trace_data.log_height - fri_.log_blowup, Slab{}, air,
-                                pis, alpha, GENERATOR, preprocessed ? &preprocessed->ldes[0] : nullptr);
+                                pis, alpha, GENERATOR, preprocessed ? &preprocessed->ldes[0] : nullptr,
+                                aux ? &aux->ldes[0] : nullptr);
 }
 
 std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_slab, unsigned log_n,
                                                               const Slab& slab, const AirProgram& air,
                                                               const std::vector<uint32_t>& pis, Ef alpha,
-                                                              uint32_t domain_shift, const ColMat* prep_lde) {
+                                                              uint32_t domain_shift, const ColMat* prep_lde,
+                                                              const ColMat* aux_lde) {
     StageTimer t(&ctx_, "compute quotient polynomial");
+    TS_REQUIRE((aux_lde != nullptr) == air.has_third(), TS_ERR_INVALID,
+               "quotient: an AIR with preprocessed and aux columns needs both committed matrices, and only such an "
+               "AIR takes two");
+    TS_REQUIRE(!aux_lde || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: aux columns beside preprocessed ones on a slab");
     TS_REQUIRE((prep_lde != nullptr) == (air.second_width() > 0), TS_ERR_INVALID,
                "quotient: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
     TS_REQUIRE(!prep_lde || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: preprocessed columns on a slab");
@@ -174,18 +190,19 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
         ColMat lde = lde_slab;
         lde.d = lde_slab.d - slab.row0;  // global row r of the slab's range lives at d[r]
         launch_quotient(ctx_, air, lde, log_n, lqd, d_consts.p, d_consts.p + n_consts, qo, row_begin, row_end,
-                        domain_shift, prep_lde);
+                        domain_shift, prep_lde, aux_lde);
     }
     return chunks;  // (the staged uploads live in the context's pinned arena: no sync needed)
 }
 
 // ------------------------------------------------------------------ open
 DevBuf<Ef> TwoAdicFriPcs::open_reduce(const PcsData& trace_data, const PcsData& quotient_data, Ef zeta,
-                                      Ef alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed) {
+                                      Ef alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed,
+                                      const PcsData* aux) {
     TS_REQUIRE(trace_data.log_height == quotient_data.log_height, TS_ERR_INVALID,
                "open: trace and quotient LDE heights differ");
     return open_reduce_slab(trace_data, quotient_data, trace_data.log_height, Slab{}, zeta, alpha,
-                            opened_values, preprocessed);
+                            opened_values, preprocessed, aux);
 }
 
 // `slab` (rows != 0): the two PcsData hold only global rows [row0, row0 + rows) of the LDEs, which
@@ -193,8 +210,16 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce(const PcsData& trace_data, const PcsData& 
 // coset -- any coset of the LDE determines the polynomials, so every rank gets the same values.
 DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsData& quotient_data,
                                            unsigned log_N, const Slab& slab, Ef zeta, Ef alpha,
-                                           std::vector<Ef>& opened_values, const PcsData* preprocessed) {
+                                           std::vector<Ef>& opened_values, const PcsData* preprocessed,
+                                           const PcsData* aux) {
     TS_REQUIRE(trace_data.ldes.size() == 1, TS_ERR_UNSUPPORTED, "open: one trace matrix expected");
+    // an aux round beside a preprocessed one (four rounds: key, aux, trace, chunks) is opened second, at the
+    // trace's points too: its 2 aw values follow the key's and its columns the key's in the num_reduced count
+    TS_REQUIRE(!aux || (preprocessed && slab.rows == 0 && aux->ldes.size() == 1 &&
+                        aux->ldes[0].height == trace_data.ldes[0].height),
+               TS_ERR_INVALID, "open: aux round shape");
+    const ColMat* xm = aux ? &aux->ldes[0] : nullptr;
+    const uint32_t aw = xm ? xm->width : 0;
     // a preprocessed round (one matrix of the trace's height, whole LDE) is opened first, at the trace's points:
     // its 2 pw values lead the opened values and its columns the num_reduced count (two_adic_pcs.rs:371,383)
     TS_REQUIRE(!preprocessed || (slab.rows == 0 && preprocessed->ldes.size() == 1 &&
@@ -221,20 +246,22 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
     const Ef pts_mont[2] = {ef_to_mont(zeta), ef_to_mont(zeta_next)};
 
     // ---- opened values: barycentric interpolation on the low coset (two_adic_pcs.rs:358-369)
-    std::vector<Ef> raw_all(2 * (size_t)pw + 2 * (size_t)w + 4 * (size_t)qd);
-    Ef* const raw = raw_all.data() + 2 * (size_t)pw;  // [-2 pw, 0): the preprocessed sums, [col][point]
+    std::vector<Ef> raw_all(2 * (size_t)pw + 2 * (size_t)aw + 2 * (size_t)w + 4 * (size_t)qd);
+    // [-2 pw - 2 aw, -2 aw): the preprocessed sums, [col][point]; [-2 aw, 0): the aux sums of a four-round opening
+    Ef* const raw = raw_all.data() + 2 * (size_t)pw + 2 * (size_t)aw;
     DevBuf<Ef> weights(&ctx_, 2 * n);  // x_t / (z_p - x_t): the low-coset reduce below divides by them again
     {
         StageTimer t(&ctx_, "compute opened values with Lagrange interpolation");
         launch_bary_weights(ctx_, log_n, pts_mont, 2, weights.p, coset_gen);
         // the last kernels of the stage write the sums straight into the context's mailbox (host memory)
         Ef* const mail = reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw_all.size()));
-        struct { Ef* p; } sums{mail + 2 * (size_t)pw};
+        struct { Ef* p; } sums{mail + 2 * (size_t)pw + 2 * (size_t)aw};
         BaryPending pend;  // the trace's partial sums and the chunks' are added up in one launch
         if (pm) {          // and the preprocessed columns', in the same one
-            pend.capacity = 3;
+            pend.capacity = xm ? 4 : 3;
             launch_bary_dots(ctx_, *pm, log_n, weights.p, 2, mail, &pend);
         }
+        if (xm) launch_bary_dots(ctx_, *xm, log_n, weights.p, 2, mail + 2 * (size_t)pw, &pend);  // a fourth job
         launch_bary_dots(ctx_, tr, log_n, weights.p, 2, sums.p, &pend);  // [col][point]
         ColMat all;  // lde_stage lays the chunk LDEs back to back (no width limit: the dot products take any)
         if (qd > 1 && columns_as_one_matrix(quotient_data.ldes, quotient_data.ldes[0].height, 0, all) &&
@@ -255,7 +282,11 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
         opened_values[c] = efc_mul(raw_all[2 * c], scale[0]);           // preprocessed_local
         opened_values[pw + c] = efc_mul(raw_all[2 * c + 1], scale[1]);  // preprocessed_next
     }
-    Ef* const ov = opened_values.data() + 2 * (size_t)pw;  // the trace's and the chunks', as without a key
+    for (uint32_t c = 0; c < aw; c++) {
+        opened_values[2 * (size_t)pw + c] = efc_mul(raw_all[2 * (size_t)pw + 2 * c], scale[0]);           // aux_local
+        opened_values[2 * (size_t)pw + aw + c] = efc_mul(raw_all[2 * (size_t)pw + 2 * c + 1], scale[1]);  // aux_next
+    }
+    Ef* const ov = opened_values.data() + 2 * (size_t)pw + 2 * (size_t)aw;  // the trace's and the chunks', as without a key
     for (uint32_t c = 0; c < w; c++) {
         ov[c] = efc_mul(raw[2 * c], scale[0]);          // trace_local
         ov[w + c] = efc_mul(raw[2 * c + 1], scale[1]);  // trace_next
@@ -264,7 +295,7 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
 
     // ---- reduce (two_adic_pcs.rs:371-383)
     StageTimer t(&ctx_, "reduce rows");
-    const uint32_t max_w = std::max(std::max(w, pw), 4u);
+    const uint32_t max_w = std::max(std::max(std::max(w, pw), aw), 4u);
     std::vector<uint32_t> apow = alpha_powers_mont(alpha, max_w);
     const Ef am = ef_to_mont(alpha);
     // (uploaded below, together with the chunk weights: one copy on the stream instead of two)
@@ -296,6 +327,12 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
             off_p[p] = ef_pow(am, num_reduced);
             kp[p] = ef_mul(reduced_ys(&opened_values[(size_t)p * pw], pw), off_p[p]);
             num_reduced += pw;
+        }
+        Ef off_a[2] = {ef_zero(), ef_zero()};
+        for (int p = 0; xm && p < 2; p++) {
+            off_a[p] = ef_pow(am, num_reduced);
+            kp[p] = ef_add(kp[p], ef_mul(reduced_ys(&opened_values[2 * (size_t)pw + (size_t)p * aw], aw), off_a[p]));
+            num_reduced += aw;
         }
         a.off_t[0] = ef_pow(am, num_reduced);
         a.k0 = ef_add(kp[0], ef_mul(reduced_ys(&ov[0], w), a.off_t[0]));  // canonical x Montgomery -> canonical
@@ -335,7 +372,7 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
                       /*stage_timers=*/false);
             launch_ef_interleave(ctx_, ro_cols.p, N, N, ro.p);
         } else {
-            launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, pm, off_p);
+            launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, pm, off_p, xm, off_a);
         }
     }
     return ro;
@@ -601,18 +638,29 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
 // n_challenges samples, [aux source], aux root, every exposed word, then alpha and on as in prove(), with the
 // aux trace where prove() has the key: second matrix of the quotient kernels, first round of the opening.
 // TSPF v4.
-std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                const AuxSource& aux_source) {
+// `proof_version` 5 (prove_pre_aux): `preprocessed` is the committed key of the AIR's preprocessed columns (null
+// for an AIR without any).  Its root is observed before the trace's, as in prove(); the quotient reads (key, aux,
+// trace) and the opening has four rounds: key, aux, trace, chunks.  TSPF v5 = the v4 header and one more word,
+// the preprocessed width.
+static std::vector<uint32_t> prove_challenge_phase(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                                   DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                                   const AuxSource& aux_source, const PcsData* preprocessed,
+                                                   uint32_t proof_version) {
     const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
-    TS_REQUIRE(air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
+    TS_REQUIRE(proof_version == 5 || air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
                "prove_aux: preprocessed columns together with aux columns need a third matrix in the kernels");
+    TS_REQUIRE((preprocessed != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
+               "prove: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
     const uint32_t aw = air.aux_width;
     TS_REQUIRE((aux_source != nullptr) == (aw > 0), TS_ERR_INVALID,
                "prove_aux: an AIR with aux columns needs an aux source, and only such an AIR takes one");
     TS_REQUIRE(aw > 0 || air.n_exposed == 0, TS_ERR_INVALID, "prove_aux: exposed words without aux columns");
     TS_REQUIRE(!aw || trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
                "prove_aux: the trace must be row-major (it is handed to the aux source after its commit)");
+    if (preprocessed) {
+        check_preprocessed_key(*preprocessed, air, 1ull << st.log_N);
+        challenger.observe_commitment(preprocessed->root);
+    }
     pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
     const uint64_t n = trace.height;
 
@@ -645,7 +693,10 @@ std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
     pis.insert(pis.end(), exposed.begin(), exposed.end());
     const Ef alpha = challenger.sample();
 
-    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, pis, alpha, aux_data.get());
+    // the kernels' second matrix is the key if there is one, else the aux trace; with both the aux trace is third
+    const PcsData* second = preprocessed ? preprocessed : aux_data.get();
+    const PcsData* third = preprocessed ? aux_data.get() : nullptr;
+    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, pis, alpha, second, third);
     std::unique_ptr<PcsData> quotient_data =
         pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));
     challenger.observe_commitment(quotient_data->root);
@@ -654,14 +705,14 @@ std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
     const Ef batch_alpha = challenger.sample();
     std::vector<Ef> opened;
     std::vector<DevBuf<Ef>> inputs;
-    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, aux_data.get()));
+    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, second, third));
 
     std::vector<uint32_t> pf;
     pf.reserve(64 + exposed.size() + opened.size() * 4);
     ProofWriter pw(pf);
-    pw.header(4, st.log_degree, st.w, st.qd, aw);
-    const uint32_t more[2] = {air.n_challenges, air.n_exposed};
-    pw.words(more, 2);
+    pw.header(proof_version, st.log_degree, st.w, st.qd, aw);
+    const uint32_t more[3] = {air.n_challenges, air.n_exposed, air.preprocessed_width};
+    pw.words(more, proof_version == 5 ? 3 : 2);
     pw.commitment(trace_data->root, 8);
     if (aw) {
         pw.commitment(aux_data->root, 8);
@@ -671,8 +722,22 @@ std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
     pw.opened_values(opened);
     std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
     if (aw) rounds.insert(rounds.begin(), aux_data.get());
+    if (preprocessed) rounds.insert(rounds.begin(), preprocessed);
     pcs.fri_prove(inputs, {st.log_N}, challenger, rounds, pf);
     return pf;
 }
 
+std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                const AuxSource& aux_source) {
+    return prove_challenge_phase(pcs, air, challenger, std::move(trace), public_values, aux_source, nullptr, 4);
+}
+
+std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                    DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                    const PcsData* preprocessed, const AuxSource& aux_source) {
+    return prove_challenge_phase(pcs, air, challenger, std::move(trace), public_values, aux_source, preprocessed, 5);
+}
+
 }  // namespace ts
+

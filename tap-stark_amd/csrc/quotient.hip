@@ -270,12 +270,32 @@ struct PrepQuotientRow : QuotientRow {
     }
 };
 
-// The row tiles of one workgroup.  PREP = false is k_quotient as it always was (the two prep arguments are
-// unused constants there); PREP = true differs in the row type alone.
-template <int NTHREADS, bool GLOBAL_REGS, bool PREP>
+// the same row of an AIR with preprocessed AND aux columns: (key LDE, aux LDE, trace LDE), all column-major with
+// bit-reversed rows and one height; D_LOAD's operand a = 2, 3 reads the key, a = 4, 5 the aux trace
+struct PrepAuxQuotientRow : PrepQuotientRow {
+    const uint32_t* aux_local;
+    const uint32_t* aux_next;
+    uint64_t aux_stride;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
+        // all six read first and chosen with selects, as PrepQuotientRow::load
+        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next, *p4 = aux_local,
+                       *p5 = aux_next;
+        const uint64_t s0 = col_stride, s1 = prep_stride, s2 = aux_stride;
+        const uint32_t* m0 = (a & 1) ? p1 : p0;
+        const uint32_t* m1 = (a & 1) ? p3 : p2;
+        const uint32_t* m2 = (a & 1) ? p5 : p4;
+        const uint32_t* m = (a & 4) ? m2 : ((a & 2) ? m1 : m0);
+        return m[(uint64_t)b * ((a & 4) ? s2 : ((a & 2) ? s1 : s0))];
+    }
+};
+
+// The row tiles of one workgroup.  MATS = 1 is k_quotient as it always was (the prep and aux arguments are
+// unused constants there); MATS = 2 (a second matrix) and 3 (a third) differ in the row type alone.
+template <int NTHREADS, bool GLOBAL_REGS, int MATS>
 __device__ __forceinline__ void quotient_tiles(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
                                                const uint32_t* __restrict__ lde, uint64_t col_stride,
-                                               const uint32_t* __restrict__ prep, uint64_t prep_stride, unsigned log_n,
+                                               const uint32_t* __restrict__ prep, uint64_t prep_stride,
+                                               const uint32_t* __restrict__ aux, uint64_t aux_stride, unsigned log_n,
                                                unsigned log_qd, const uint32_t* __restrict__ consts_mont,
                                                const uint32_t* __restrict__ alpha_pows,
                                                const uint32_t* __restrict__ is_first,
@@ -294,11 +314,17 @@ __device__ __forceinline__ void quotient_tiles(const uint32_t* __restrict__ code
         const uint32_t i_next = (i + (1u << log_qd)) & (total - 1);  // prover.rs:139-140,165
         const uint32_t r_next = bitrev32(i_next, L);
         const QuotientRow base{{lde + rr, lde + r_next, is_first[rr], is_last[rr], is_transition[rr]}, col_stride, alpha_pows};
-        typename std::conditional<PREP, PrepQuotientRow, QuotientRow>::type row{base};
-        if constexpr (PREP) {
+        typename std::conditional<MATS == 3, PrepAuxQuotientRow,
+                                  typename std::conditional<MATS == 2, PrepQuotientRow, QuotientRow>::type>::type row{base};
+        if constexpr (MATS >= 2) {
             row.prep_local = prep + rr;
             row.prep_next = prep + r_next;
             row.prep_stride = prep_stride;
+        }
+        if constexpr (MATS == 3) {
+            row.aux_local = aux + rr;
+            row.aux_next = aux + r_next;
+            row.aux_stride = aux_stride;
         }
         run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
         if (!active) continue;
@@ -323,9 +349,9 @@ k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
            const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
            const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
            uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    quotient_tiles<NTHREADS, GLOBAL_REGS, false>(code, n_instr, n_regs, lde, col_stride, nullptr, 0, log_n, log_qd,
-                                                 consts_mont, alpha_pows, is_first, is_last, is_transition, qc, out,
-                                                 row_begin, row_end, reg_slabs, n_tiles);
+    quotient_tiles<NTHREADS, GLOBAL_REGS, 1>(code, n_instr, n_regs, lde, col_stride, nullptr, 0, nullptr, 0, log_n,
+                                             log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition, qc, out,
+                                             row_begin, row_end, reg_slabs, n_tiles);
 }
 
 // the interpreter over (preprocessed LDE, trace LDE): both column-major with bit-reversed rows and one height
@@ -338,9 +364,24 @@ k_quotient_pre(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_r
                const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
                const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
                uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    quotient_tiles<NTHREADS, GLOBAL_REGS, true>(code, n_instr, n_regs, lde, col_stride, prep, prep_stride, log_n,
-                                                log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition, qc,
-                                                out, row_begin, row_end, reg_slabs, n_tiles);
+    quotient_tiles<NTHREADS, GLOBAL_REGS, 2>(code, n_instr, n_regs, lde, col_stride, prep, prep_stride, nullptr, 0,
+                                             log_n, log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition,
+                                             qc, out, row_begin, row_end, reg_slabs, n_tiles);
+}
+
+// the interpreter over (preprocessed LDE, aux LDE, trace LDE): all column-major with bit-reversed rows, one height
+template <int NTHREADS, bool GLOBAL_REGS>
+__global__ void __launch_bounds__(NTHREADS)
+k_quotient_pre_aux(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+                   const uint32_t* __restrict__ lde, uint64_t col_stride, const uint32_t* __restrict__ prep,
+                   uint64_t prep_stride, const uint32_t* __restrict__ aux, uint64_t aux_stride, unsigned log_n,
+                   unsigned log_qd, const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
+                   const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
+                   const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
+                   uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+    quotient_tiles<NTHREADS, GLOBAL_REGS, 3>(code, n_instr, n_regs, lde, col_stride, prep, prep_stride, aux, aux_stride,
+                                             log_n, log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition,
+                                             qc, out, row_begin, row_end, reg_slabs, n_tiles);
 }
 
 // The four instantiations of an interpreter kernel template (one function type), and the name of its timer.
@@ -371,8 +412,15 @@ static void launch_interpreter(Context& ctx, const InterpKernels<F>& k, const Ai
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
                      const QuotOut& out, uint64_t row_begin, uint64_t row_end, uint32_t shift,
-                     const ColMat* prep_lde) {
+                     const ColMat* prep_lde, const ColMat* aux_lde) {
     TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
+    // a third matrix exactly for an AIR with preprocessed and aux columns; same shape rules as the second
+    TS_REQUIRE((aux_lde != nullptr) == air.has_third(), TS_ERR_INVARIANT,
+               "quotient: aux LDE (third matrix) and the AIR's widths disagree");
+    if (aux_lde)
+        TS_REQUIRE(aux_lde->d && aux_lde->width == air.third_width() && aux_lde->height == trace_lde.height &&
+                       aux_lde->col_stride >= aux_lde->height,
+                   TS_ERR_INVALID, "quotient: aux LDE shape");
     // a program with preprocessed loads never runs without the matrix they read, and the matrix covers the rows
     TS_REQUIRE((prep_lde != nullptr) == (air.second_width() > 0), TS_ERR_INVARIANT,
                "quotient: preprocessed LDE and the AIR's preprocessed width disagree");
@@ -401,10 +449,13 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
     // (jit.cpp emit_head); the others have no such parameters
     const uint32_t* prep_p = prep_lde ? prep_lde->d : nullptr;
     uint64_t prep_stride = prep_lde ? prep_lde->col_stride : 0;
+    // and those of an AIR with both kinds of column (aux, aux_stride) after the prep pair
+    const uint32_t* aux_p = aux_lde ? aux_lde->d : nullptr;
+    uint64_t aux_stride = aux_lde ? aux_lde->col_stride : 0;
     if (ks && !ks->seg) {
         // specialised straight-line kernel (jit.cpp); same arguments, same results
-        void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont,
-                        &is_first, &is_last, &is_transition, &qc, &qo, &rb, &re, &prep_p, &prep_stride};
+        void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first, &is_last,
+                        &is_transition, &qc, &qo, &rb, &re, &prep_p, &prep_stride, &aux_p, &aux_stride};
         KernelTimer kt(&ctx, "k_quotient_jit");
         TS_HIP(hipModuleLaunchKernel((hipFunction_t)ks->fns[0], (unsigned)((total + 255) / 256), 1, 1,
                                      256, 1, 1, 0, ctx.stream, args, nullptr));
@@ -428,7 +479,10 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
             void* args_prep[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
                                  &is_last, &is_transition, &qc, &qo, &tb, &te, &prep_p, &prep_stride, &slab_p,
                                  &slab_rows};
-            void** args = prep_lde ? args_prep : args_main;
+            void* args_prep_aux[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
+                                     &is_last, &is_transition, &qc, &qo, &tb, &te, &prep_p, &prep_stride, &aux_p,
+                                     &aux_stride, &slab_p, &slab_rows};
+            void** args = aux_lde ? args_prep_aux : prep_lde ? args_prep : args_main;
             const unsigned grid = (unsigned)((te - tb + 255) / 256);
             for (void* fn : ks->fns)
                 TS_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 256, 1, 1, 0, ctx.stream, args, nullptr));
@@ -440,6 +494,13 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
     static const InterpKernels<decltype(&k_quotient_pre<64, true>)> kernels_pre{
         "k_quotient_pre", k_quotient_pre<64, true>, k_quotient_pre<256, false>, k_quotient_pre<128, false>,
         k_quotient_pre<64, false>};
+    static const InterpKernels<decltype(&k_quotient_pre_aux<64, true>)> kernels_pre_aux{
+        "k_quotient_pre_aux", k_quotient_pre_aux<64, true>, k_quotient_pre_aux<256, false>,
+        k_quotient_pre_aux<128, false>, k_quotient_pre_aux<64, false>};
+    if (aux_lde)
+        return launch_interpreter(ctx, kernels_pre_aux, air, total, lde_p, stride, prep_p, prep_stride, aux_p,
+                                  aux_stride, log_n, log_qd, d_consts_mont, d_alpha_pows_mont, is_first, is_last,
+                                  is_transition, qc, qo, rb, re);
     if (prep_lde)
         return launch_interpreter(ctx, kernels_pre, air, total, lde_p, stride, prep_p, prep_stride, log_n, log_qd,
                                   d_consts_mont, d_alpha_pows_mont, is_first, is_last, is_transition, qc, qo, rb, re);
@@ -534,6 +595,42 @@ k_check_constraints_pre(const uint32_t* __restrict__ code, uint32_t n_instr, uin
     }
 }
 
+// the same with two row-major matrices of the trace's height beside it: preprocessed (a = 2, 3), aux (a = 4, 5)
+struct PrepAuxCheckRow : PrepCheckRow {
+    const uint32_t* aux_local;
+    const uint32_t* aux_next;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
+        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next, *p4 = aux_local,
+                       *p5 = aux_next;
+        const uint32_t* m0 = (a & 1) ? p1 : p0;
+        const uint32_t* m1 = (a & 1) ? p3 : p2;
+        const uint32_t* m2 = (a & 1) ? p5 : p4;
+        return ((a & 4) ? m2 : ((a & 2) ? m1 : m0))[b];
+    }
+};
+
+template <int NTHREADS, bool GLOBAL_REGS>
+__global__ void __launch_bounds__(NTHREADS)
+k_check_pre_aux(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+                const uint32_t* __restrict__ trace, uint32_t width, const uint32_t* __restrict__ prep,
+                uint32_t prep_width, const uint32_t* __restrict__ aux, uint32_t aux_width, uint64_t n,
+                const uint32_t* __restrict__ consts_mont, unsigned long long* __restrict__ violation,
+                uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+    uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t i = (uint64_t)tile * NTHREADS + threadIdx.x;
+        const bool active = i < n;
+        const uint64_t ii = active ? i : 0, nx = (ii + 1) % n;
+        unsigned long long bad = ~0ull;
+        PrepAuxCheckRow row{{{{trace + ii * width, trace + nx * width, ii == 0 ? R_MOD_P : 0u,
+                               ii == n - 1 ? R_MOD_P : 0u, ii != n - 1 ? R_MOD_P : 0u}, ii, bad},
+                             prep + ii * prep_width, prep + nx * prep_width},
+                            aux + ii * aux_width, aux + nx * aux_width};
+        run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
+        if (active && bad != ~0ull) atomicMin(violation, bad);
+    }
+}
+
 template <int NTHREADS, bool GLOBAL_REGS>
 __global__ void __launch_bounds__(NTHREADS)
 k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
@@ -555,7 +652,10 @@ k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_
 
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
-                              unsigned long long* d_violation, const uint32_t* prep_row_major) {
+                              unsigned long long* d_violation, const uint32_t* prep_row_major,
+                              const uint32_t* aux_row_major) {
+    TS_REQUIRE((aux_row_major != nullptr) == air.has_third(), TS_ERR_INVARIANT,
+               "check_constraints: aux matrix (third matrix) and the AIR's widths disagree");
     TS_REQUIRE((prep_row_major != nullptr) == (air.second_width() > 0), TS_ERR_INVARIANT,
                "check_constraints: preprocessed matrix and the AIR's preprocessed width disagree");
     // the report is row * 2^16 + constraint index (the oracle's and stark.py's format)
@@ -566,6 +666,12 @@ void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_
     static const InterpKernels<decltype(&k_check_constraints_pre<64, true>)> kernels_pre{
         "k_check_constraints_pre", k_check_constraints_pre<64, true>, k_check_constraints_pre<256, false>,
         k_check_constraints_pre<128, false>, k_check_constraints_pre<64, false>};
+    static const InterpKernels<decltype(&k_check_pre_aux<64, true>)> kernels_pre_aux{
+        "k_check_pre_aux", k_check_pre_aux<64, true>, k_check_pre_aux<256, false>, k_check_pre_aux<128, false>,
+        k_check_pre_aux<64, false>};
+    if (aux_row_major)
+        return launch_interpreter(ctx, kernels_pre_aux, air, n, trace_row_major, air.width, prep_row_major,
+                                  air.second_width(), aux_row_major, air.third_width(), n, d_consts_mont, d_violation);
     if (prep_row_major)
         return launch_interpreter(ctx, kernels_pre, air, n, trace_row_major, air.width, prep_row_major,
                                   air.second_width(), n, d_consts_mont, d_violation);

@@ -100,8 +100,10 @@ Ef fold_row(uint64_t index, unsigned log_height, Ef beta, Ef e0, Ef e1) {
 }
 
 // tape evaluation over EF4 (verifier side: opened values are extension elements)
-// (prep_local / prep_next: the opened preprocessed rows of a version-2 AIR, unread otherwise)
-void eval_tape_ext(const AirProgram& air, const Ef* prep_local, const Ef* prep_next, const Ef* local, const Ef* next,
+// (prep_local / prep_next: the opened preprocessed rows of a version-2 AIR, aux_local / aux_next: the opened aux
+// rows of a version-3 AIR; unread otherwise)
+void eval_tape_ext(const AirProgram& air, const Ef* prep_local, const Ef* prep_next, const Ef* aux_local,
+                   const Ef* aux_next, const Ef* local, const Ef* next,
                    const std::vector<uint32_t>& pis, Ef is_first, Ef is_last, Ef is_trans,
                    std::vector<Ef>& v) {
     const uint32_t n_nodes = air.tape[4];
@@ -114,8 +116,8 @@ void eval_tape_ext(const AirProgram& air, const Ef* prep_local, const Ef* prep_n
             case T_MAIN: v[i] = a ? next[b] : local[b]; break;
             case T_PREP: v[i] = a ? prep_next[b] : prep_local[b]; break;
             case T_PUBLIC: v[i] = ef_from_base(pis[a]); break;
-            // version 3: the aux rows are the second matrix's; `pis` is public values ++ challenges ++ exposed
-            case T_AUX: v[i] = a ? prep_next[b] : prep_local[b]; break;
+            // version 3: `pis` is public values ++ challenges ++ exposed
+            case T_AUX: v[i] = a ? aux_next[b] : aux_local[b]; break;
             case T_CHALLENGE: v[i] = ef_from_base(pis[air.n_public + a]); break;
             case T_EXPOSED: v[i] = ef_from_base(pis[air.n_public + 4 * air.n_challenges + a]); break;
             case T_IS_FIRST: v[i] = is_first; break;
@@ -350,7 +352,7 @@ static int fri_verify_impl(const FriConfig& fri, BfChallenger& challenger,
 static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
                        const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
                        const TapLocks* tap, bool v3 = false, const uint32_t* prep_root = nullptr,
-                       std::vector<uint32_t>* exposed_out = nullptr);
+                       std::vector<uint32_t>* exposed_out = nullptr, bool v5 = false);
 
 int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
                const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
@@ -359,6 +361,12 @@ int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challe
 int verify_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* proof,
                size_t n_words, const std::vector<uint32_t>& pis, std::vector<uint32_t>& exposed) {
     return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, false, nullptr, &exposed);
+}
+// v5: a TSPF v5 proof (ts_verify_pre_aux): the key's root as in v3, the aux trace and exposed words as in v4
+int verify_pre_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
+                   const uint32_t* preprocessed_root, const uint32_t* proof, size_t n_words,
+                   const std::vector<uint32_t>& pis, std::vector<uint32_t>& exposed) {
+    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, false, preprocessed_root, &exposed, true);
 }
 int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
            const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
@@ -372,19 +380,24 @@ int verify_tap(const FriConfig& fri, const AirProgram& air, BfChallenger& challe
 
 static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
                        const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis_in,
-                       const TapLocks* tap, bool v3, const uint32_t* prep_root, std::vector<uint32_t>* exposed_out) {
+                       const TapLocks* tap, bool v3, const uint32_t* prep_root, std::vector<uint32_t>* exposed_out,
+                       bool v5) {
     if (pis_in.size() != air.n_public) return 1;
-    const bool v4 = exposed_out != nullptr;  // TSPF v4: the second matrix is the aux trace, committed in the proof
-    if (v4 && air.preprocessed_width) return 1;
+    // TSPF v4: the second matrix is the aux trace, committed in the proof; v5: the key AND the aux trace
+    const bool v4 = exposed_out != nullptr && !v5;
+    const bool keyed = v3 || v5, phased = v4 || v5;
+    if ((!keyed && air.preprocessed_width) || (!phased && air.aux_width)) return 1;
     Reader rb{proof, n_words};
-    if (rb.get() != 0x46505354u || rb.get() != (v4 ? 4u : v3 ? 3u : tap ? 2u : 1u)) return 9;
+    if (rb.get() != 0x46505354u || rb.get() != (v5 ? 5u : v4 ? 4u : v3 ? 3u : tap ? 2u : 1u)) return 9;
     const unsigned degree_bits = rb.get();
     const uint32_t pw = rb.get(), pqd = rb.get();
     if (tap && rb.get() != fri.num_queries) return 1;  // TSPF v2: roots per commitment
-    const uint32_t P_w = air.second_width();           // the second matrix: preprocessed key (v3) or aux trace (v4)
+    const uint32_t P_w = air.preprocessed_width;       // the key's round (v3, v5)
+    const uint32_t A_w = air.aux_width;                // the aux trace's round (v4, v5)
     if (v3 && rb.get() != P_w) return 1;               // TSPF v3: the preprocessed width
-    if (v4 && (rb.get() != P_w || rb.get() != air.n_challenges || rb.get() != air.n_exposed)) return 1;
-    if (v4 && !P_w && air.n_exposed) return 1;
+    if (phased && (rb.get() != A_w || rb.get() != air.n_challenges || rb.get() != air.n_exposed)) return 1;
+    if (v5 && rb.get() != P_w) return 1;               // TSPF v5: the v4 header, then the preprocessed width
+    if (phased && !A_w && air.n_exposed) return 1;
     if (rb.bad || degree_bits > 27) return 9;
     const size_t n_roots = tap ? fri.num_queries : 1, cw = 8 * n_roots;
     const unsigned lqd = air.log_quotient_degree;
@@ -392,26 +405,31 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     // verifier.rs:49-59 valid_shape
     if (pw != w || pqd != qd) return 1;
     const uint32_t* trace_root = rb.take(cw);
+    const uint32_t* aux_root = nullptr;
     const uint32_t* exposed = nullptr;
-    if (v4 && P_w) {  // v4 order: trace root, aux root, exposed words, quotient root
-        prep_root = rb.take(8);
+    if (A_w) {  // v4 order: trace root, aux root, exposed words, quotient root
+        aux_root = rb.take(8);
         exposed = rb.take(air.n_exposed);
     }
     const uint32_t* quot_root = rb.take(cw);
     const uint32_t* prep_local = rb.take(4 * (size_t)P_w);  // v3 order: the preprocessed rows lead
     const uint32_t* prep_next = rb.take(4 * (size_t)P_w);
+    const uint32_t* aux_local = rb.take(4 * (size_t)A_w);   // then the aux rows
+    const uint32_t* aux_next = rb.take(4 * (size_t)A_w);
     const uint32_t* trace_local = rb.take(4 * (size_t)w);
     const uint32_t* trace_next = rb.take(4 * (size_t)w);
     const uint32_t* qchunks = rb.take(16 * (size_t)qd);
     if (rb.bad) return 9;
     // (the proof is a word stream: Ef is 16-byte aligned, the words are not)
-    std::vector<Ef> pl(P_w), pn(P_w), tl(w), tn(w), qc(4 * (size_t)qd);
+    std::vector<Ef> pl(P_w), pn(P_w), al(A_w), an(A_w), tl(w), tn(w), qc(4 * (size_t)qd);
     if (P_w) memcpy((void*)pl.data(), prep_local, 16 * (size_t)P_w);
     if (P_w) memcpy((void*)pn.data(), prep_next, 16 * (size_t)P_w);
+    if (A_w) memcpy((void*)al.data(), aux_local, 16 * (size_t)A_w);
+    if (A_w) memcpy((void*)an.data(), aux_next, 16 * (size_t)A_w);
     memcpy((void*)tl.data(), trace_local, 16 * (size_t)w);
     memcpy((void*)tn.data(), trace_next, 16 * (size_t)w);
     memcpy((void*)qc.data(), qchunks, 64 * (size_t)qd);
-    for (auto* vec : {&pl, &pn, &tl, &tn, &qc})
+    for (auto* vec : {&pl, &pn, &al, &an, &tl, &tn, &qc})
         for (auto& e : *vec)
             for (int k = 0; k < 4; k++)
                 if (e.c[k] >= P) return 9;
@@ -420,19 +438,19 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
         if (exposed[e] >= P) return 9;
 
     // the key is part of the statement: observed before anything of the proof (prover.cpp prove)
-    if (P_w && !v4) challenger.observe_commitment(prep_root);
+    if (P_w) challenger.observe_commitment(prep_root);
     // verifier.rs:69-75
     for (size_t k = 0; k < n_roots; k++) challenger.observe_commitment(trace_root + 8 * k);
-    // v4 (prover.cpp prove_aux): the challenges, then the aux root and the exposed words; the constraints read
+    // v4, v5 (prover.cpp prove_aux): the challenges, then the aux root and the exposed words; the constraints read
     // public values ++ challenge words ++ exposed words
     std::vector<uint32_t> pis = pis_in;
-    if (v4) {
+    if (phased) {
         for (uint32_t k = 0; k < air.n_challenges; k++) {
             const Ef c = challenger.sample();
             pis.insert(pis.end(), c.c, c.c + 4);
         }
-        if (P_w) {
-            challenger.observe_commitment(prep_root);
+        if (A_w) {
+            challenger.observe_commitment(aux_root);
             for (uint32_t e = 0; e < air.n_exposed; e++) challenger.observe(exposed[e]);
             pis.insert(pis.end(), exposed, exposed + air.n_exposed);
         }
@@ -453,7 +471,13 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
         r1.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, 4, {zeta}, {vals}});
     }
     std::vector<PcsRoundClaim> claims{r0, r1};
-    if (P_w) {  // the key's round comes first, opened at the trace's points
+    if (A_w) {  // the aux trace's round comes before the trace's, opened at the trace's points
+        PcsRoundClaim ra;
+        ra.root = aux_root;
+        ra.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, A_w, {zeta, zeta_next}, {al, an}});
+        claims.insert(claims.begin(), ra);
+    }
+    if (P_w) {  // the key's round comes first of all
         PcsRoundClaim rp;
         rp.root = prep_root;
         rp.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, P_w, {zeta, zeta_next}, {pl, pn}});
@@ -491,12 +515,13 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     const Ef inv_zeroifier = c_inv(zh);
     // :138-153 fold the constraints at zeta
     std::vector<Ef> v;
-    eval_tape_ext(air, pl.data(), pn.data(), tl.data(), tn.data(), pis, is_first, is_last, is_trans, v);
+    eval_tape_ext(air, pl.data(), pn.data(), al.data(), an.data(), tl.data(), tn.data(), pis, is_first, is_last,
+                  is_trans, v);
     const uint32_t* cons = air.tape_constraints();
     Ef acc = ef_zero();
     for (uint32_t c = 0; c < air.n_constraints; c++) acc = ef_add(c_mul(acc, alpha), v[cons[c]]);
     if (!ef_eq(c_mul(acc, inv_zeroifier), quotient)) return 7;  // :157 OodEvaluationMismatch
-    if (v4) exposed_out->assign(pis.end() - (P_w ? air.n_exposed : 0), pis.end());
+    if (phased) exposed_out->assign(pis.end() - (A_w ? air.n_exposed : 0), pis.end());
     return 0;
 }
 

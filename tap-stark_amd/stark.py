@@ -641,12 +641,19 @@ class TwoAdicFriPcs:
         """``preprocessed``: the ``PreprocessedKey`` (or its ``PcsData``) of an AIR with preprocessed columns
         (``ts_quotient_chunks_pre``); None is ``ts_quotient_chunks``.  ``aux``: the committed aux trace (a
         ``PcsData``) of an AIR with challenge-phase columns, with its ``challenges`` and ``exposed`` words
-        (``ts_quotient_chunks_aux``)."""
+        (``ts_quotient_chunks_aux``).  Both ``preprocessed`` and ``aux``: an AIR with both kinds of column
+        (``ts_quotient_chunks_pre_aux``)."""
         qd = 1 << air.log_quotient_degree
         out = (C.c_void_p * qd)()
         pis = _u32(public_values)
         pis_p = _p(pis) if len(pis) else None
-        if aux is not None or challenges is not None or exposed is not None:
+        if preprocessed is not None and aux is not None:
+            key = getattr(preprocessed, "data", preprocessed)
+            ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
+            self.ctx.check(self.ctx._l.ts_quotient_chunks_pre_aux(
+                self.ctx.h, key.h, aux.h, trace_data.h, self.fri.log_blowup, air.h, pis_p, len(pis),
+                _p(ch) if len(ch) else None, _p(ex) if len(ex) else None, _p(_u32(alpha)), out))
+        elif aux is not None or challenges is not None or exposed is not None:
             ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
             self.ctx.check(self.ctx._l.ts_quotient_chunks_aux(
                 self.ctx.h, aux.h if aux is not None else None, trace_data.h, self.fri.log_blowup, air.h, pis_p,
@@ -922,8 +929,8 @@ class Proof:
             return out
 
         magic, version, degree_bits, width, qd = (int(x) for x in take(5))
-        if magic != TSPF_MAGIC or version not in (1, 2, 3, 4):
-            raise ValueError("not a TSPF v1/v2/v3/v4 proof")
+        if magic != TSPF_MAGIC or version not in (1, 2, 3, 4, 5):
+            raise ValueError("not a TSPF v1/v2/v3/v4/v5 proof")
         # v2 (proofs over the taptree MMCS, ts_prove_tap): num_queries roots per commitment, the
         # commitment fields are (num_queries, 8) arrays
         nr = int(take(1)[0]) if version == 2 else 1
@@ -932,10 +939,14 @@ class Proof:
         pw = int(take(1)[0]) if version == 3 else 0
         # v4 (ts_prove_aux): aux width, challenge and exposed counts; the aux root and the exposed words sit between
         # the two commitments, the opened aux rows lead the opened values (three BatchOpenings per query)
-        aw, nc, ne = (int(x) for x in take(3)) if version == 4 else (0, 0, 0)
+        aw, nc, ne = (int(x) for x in take(3)) if version in (4, 5) else (0, 0, 0)
+        # v5 (ts_prove_pre_aux): the v4 header, then the preprocessed width; commitments and exposed words as v4; the
+        # opened preprocessed rows, then the aux rows, lead the opened values (four BatchOpenings per query)
+        if version == 5:
+            pw = int(take(1)[0])
         d = {"degree_bits": degree_bits, "query_proofs": [], "version": version, "preprocessed_width": pw,
              "aux_width": aw, "n_challenges": nc, "aux_commit": None, "exposed": np.zeros(0, dtype=np.uint32)}
-        if version == 4:
+        if version in (4, 5):
             d["trace_commit"] = take(8)
             if aw:
                 d["aux_commit"], d["exposed"] = take(8), take(ne)
@@ -979,10 +990,17 @@ class Proof:
 class PreprocessedKey:
     """The preprocessed (fixed) columns of an AIR, committed once: ``ts_pcs_commit`` of the one (n, P) matrix
     on the natural domain.  ``data`` is the ``PcsData`` the prover reads (never consumed: one key serves any
-    number of proofs on its context), ``root`` what the verifier holds."""
+    number of proofs on its context), ``root`` what the verifier holds.  ``keep_values=True`` (an array given)
+    keeps a second, row-major device copy of the values in ``values``: the commit consumes its matrix, and a LogUp
+    aux source that reads the table (``LogUp.build(..., preprocessed=key.values)``) needs the rows."""
 
-    def __init__(self, config: "StarkConfig", matrix):
+    def __init__(self, config: "StarkConfig", matrix, keep_values: bool = False):
         pcs = config.pcs
+        self.values = None
+        if keep_values:
+            if isinstance(matrix, DeviceMatrix):
+                raise ValueError("keep_values needs the values as an array: a DeviceMatrix is consumed by the commit")
+            self.values = DeviceMatrix.upload(pcs.ctx, _u32(matrix))
         if not isinstance(matrix, DeviceMatrix):
             matrix = DeviceMatrix.upload(pcs.ctx, _u32(matrix))
         n = matrix.dims()[0]
@@ -1039,6 +1057,7 @@ def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_valu
     ndarray of 4 * n_challenges words) -> (DeviceMatrix | ndarray, exposed words)`` called once after the trace is
     committed (``ts_prove_aux``; the proof is TSPF v4).  The trace it sees is the prover's: read it, do not keep it.
     An exception inside it ends the proof with TS_ERR_INVALID and is re-raised here.
+    Both ``preprocessed`` and ``aux``: an AIR with both kinds of column (``ts_prove_pre_aux``; TSPF v5).
     """
     pcs = config.pcs
     ctx = pcs.ctx
@@ -1053,7 +1072,18 @@ def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_valu
     n_words = C.c_size_t()
     cfg = pcs.fri._c()
     pis_p = _p(pis) if len(pis) else None
-    if aux is not None:
+    if aux is not None and preprocessed is not None:
+        # one more Merkle path and batch header per query than _proof_capacity counts
+        extra = pcs.fri.num_queries * (8 * (max(n, 1).bit_length() - 1 + pcs.fri.log_blowup) + 8)
+        out = _proof_buffer(ctx, len(out) + extra)
+        failure: list = []
+        cb = _aux_callback(ctx, air, aux, failure)
+        rc = ctx._l.ts_prove_pre_aux(ctx.h, C.byref(cfg), air.h, challenger.h, preprocessed.data.h, trace.h, pis_p,
+                                     len(pis), cb, None, _p(out), len(out), C.byref(n_words))
+        if failure:
+            raise failure[0]
+        ctx.check(rc)
+    elif aux is not None:
         failure: list = []
         cb = _aux_callback(ctx, air, aux, failure)
         rc = ctx._l.ts_prove_aux(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis), cb, None,
@@ -1306,7 +1336,8 @@ def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_val
     ``preprocessed_root``: the root of the ``PreprocessedKey`` a TSPF v3 proof was made against
     (``ts_verify_pre``); None is ``ts_verify``.
     A TSPF v4 proof (``ts_prove_aux``) goes to ``ts_verify_aux``, and its exposed words are returned: the statement
-    about them (``LogUp.verify``: the sum is zero) is the caller's to check."""
+    about them (``LogUp.verify``: the sum is zero) is the caller's to check.  A TSPF v5 proof (``ts_prove_pre_aux``)
+    with its ``preprocessed_root`` goes to ``ts_verify_pre_aux`` and returns its exposed words likewise."""
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
         air = CompiledAir(None, _air_tape_of(air, len(pis)))
@@ -1316,7 +1347,12 @@ def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_val
     l = _lib.lib()
     pis_p = _p(pis) if len(pis) else None
     exposed = None
-    if preprocessed_root is None and len(words) >= 2 and words[0] == TSPF_MAGIC and words[1] == 4:
+    if preprocessed_root is not None and len(words) >= 2 and words[0] == TSPF_MAGIC and words[1] == 5:
+        exposed = np.zeros(air.n_exposed, dtype=np.uint32)
+        rc = l.ts_verify_pre_aux(C.byref(cfg), air.h, challenger.h, _p(_u32(preprocessed_root)), _p(words), len(words),
+                                 pis_p, len(pis), _p(exposed) if len(exposed) else None, len(exposed),
+                                 C.byref(verdict))
+    elif preprocessed_root is None and len(words) >= 2 and words[0] == TSPF_MAGIC and words[1] == 4:
         exposed = np.zeros(air.n_exposed, dtype=np.uint32)
         rc = l.ts_verify_aux(C.byref(cfg), air.h, challenger.h, _p(words), len(words), pis_p, len(pis),
                              _p(exposed) if len(exposed) else None, len(exposed), C.byref(verdict))
@@ -1338,7 +1374,8 @@ def check_constraints(air, trace, public_values, ctx: Context | None = None, pre
     constraint holds on every row, else ``row * 65536 + constraint_index`` of the first failure.
     ``preprocessed``: the (n, P) matrix of an AIR with preprocessed columns (``ts_check_constraints_pre``).
     ``aux``, ``challenges``, ``exposed``: the (n, aux_width) aux matrix of an AIR with challenge-phase columns, the
-    challenge words it was built for and its exposed words (``ts_check_constraints_aux``)."""
+    challenge words it was built for and its exposed words (``ts_check_constraints_aux``).  Both ``preprocessed``
+    and ``aux``: an AIR with both kinds of column (``ts_check_constraints_pre_aux``)."""
     ctx = ctx or default_context()
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
@@ -1347,7 +1384,16 @@ def check_constraints(air, trace, public_values, ctx: Context | None = None, pre
         trace = DeviceMatrix.upload(ctx, trace)
     out = C.c_int64(-1)
     pis_p = _p(pis) if len(pis) else None
-    if aux is not None or challenges is not None or exposed is not None:
+    if preprocessed is not None and aux is not None:
+        if not isinstance(preprocessed, DeviceMatrix):
+            preprocessed = DeviceMatrix.upload(ctx, _u32(preprocessed))
+        if not isinstance(aux, DeviceMatrix):
+            aux = DeviceMatrix.upload(ctx, _u32(aux))
+        ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
+        ctx.check(ctx._l.ts_check_constraints_pre_aux(ctx.h, air.h, preprocessed.h, aux.h, trace.h, pis_p, len(pis),
+                                                      _p(ch) if len(ch) else None, _p(ex) if len(ex) else None,
+                                                      C.byref(out)))
+    elif aux is not None or challenges is not None or exposed is not None:
         if aux is not None and not isinstance(aux, DeviceMatrix):
             aux = DeviceMatrix.upload(ctx, _u32(aux))
         ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
