@@ -88,6 +88,12 @@ ts_status ts_ctx_graph_stats(ts_ctx* ctx, uint64_t out[4]);
  * 6 / 7 / 8 = proof-of-work witnesses (fri/src/prover.rs:43) taken from the device search after the
  * host's one-step check_witness / device candidates the host refused (never expected) / searches the
  * host ran itself (no device candidate below 2^12, or TS_HOST_GRIND=1).
+ * 9 = device blocks filled with the test pattern since the context was created; 0 unless the TEST KNOB
+ * TS_POOL_POISON=<32-bit word, as strtoul(.., 0) reads it> was set when ts_ctx_create ran.  The context then
+ * fills every block its pool hands out (the whole rounded block, recycled ones too) and every table it allocates
+ * (twiddles, coset scales, selectors) with that word and waits for the fill, so that nothing can pass by reading
+ * what an earlier use left behind; proofs are the same, only slower.  Unset or empty: off, at the cost of one
+ * branch per block.  A value that is no 32-bit word makes ts_ctx_create return TS_ERR_INVALID.
  * TS_ERR_INVALID for an unknown index. */
 ts_status ts_ctx_stat(ts_ctx* ctx, int which, uint64_t* out);
 

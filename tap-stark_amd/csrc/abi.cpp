@@ -404,6 +404,7 @@ ts_status ts_ctx_stat(ts_ctx* ctx, int which, uint64_t* out) {
     case 6: *out = ctx->ctx.pow_hints_accepted; break;
     case 7: *out = ctx->ctx.pow_hints_rejected; break;
     case 8: *out = ctx->ctx.pow_host_grinds; break;
+    case 9: *out = ctx->ctx.poison_fills; break;
     default: return TS_ERR_INVALID;
     }
     return TS_OK;

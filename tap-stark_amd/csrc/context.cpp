@@ -1,3 +1,4 @@
+#include <errno.h>
 #include <stdio.h>
 #include <time.h>
 #include <stdlib.h>
@@ -9,7 +10,22 @@
 
 namespace ts {
 
+// TS_POOL_POISON: unset or empty = off, else a 32-bit word in any base strtoul(.., 0) reads
+static bool poison_knob(uint32_t* word) {
+    const char* e = getenv("TS_POOL_POISON");
+    if (!e || !*e) return false;
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long v = strtoul(e, &end, 0);
+    TS_REQUIRE(errno == 0 && end != e && *end == 0 && e[0] != '-' && v <= 0xFFFFFFFFul, TS_ERR_INVALID,
+               "TS_POOL_POISON is not a 32-bit word (decimal, 0x hex or 0 octal)");
+    *word = (uint32_t)v;
+    return true;
+}
+
 Context::Context(int dev) : device(dev) {
+    pool_debug = getenv("TS_POOL_DEBUG") != nullptr;
+    poison_on = poison_knob(&poison_word);  // before the device is touched: a bad value is refused anywhere
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0)
@@ -63,7 +79,6 @@ void* Context::alloc(size_t bytes) {
         free_blocks.erase(it);
     } else {
         TS_HIP(hipSetDevice(device));
-        static const bool pool_debug = getenv("TS_POOL_DEBUG") != nullptr;
         if (pool_debug) {
             struct timespec ts_;
             clock_gettime(CLOCK_MONOTONIC, &ts_);
@@ -83,7 +98,18 @@ void* Context::alloc(size_t bytes) {
         bytes_reserved += sz;
     }
     live_blocks[p] = sz;
+    if (poison_on) poison(p, sz);
     return p;
+}
+
+// The stream is non-blocking and a block may next be written from elsewhere (another rank's stream in the
+// in-process collectives, a caller's own stream through ts_matrix_device_ptr): the fill must have landed
+// before the block is handed out, so it is waited for.
+void Context::poison(void* p, size_t bytes) {
+    TS_HIP(hipSetDevice(device));
+    TS_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)poison_word, bytes / 4, stream));
+    TS_HIP(hipStreamSynchronize(stream));
+    poison_fills++;
 }
 
 void Context::free(void* p) {
@@ -216,6 +242,10 @@ void Context::ensure_twiddles(unsigned log_size) {
     const size_t n = (size_t)1 << log_size;
     TS_HIP(hipMalloc((void**)&d_twiddle_fwd, n * 4));
     TS_HIP(hipMalloc((void**)&d_twiddle_inv, n * 4));
+    if (poison_on) {
+        poison(d_twiddle_fwd, n * 4);
+        poison(d_twiddle_inv, n * 4);
+    }
     twiddle_log = log_size;
     launch_build_twiddles(*this, d_twiddle_fwd, d_twiddle_inv, log_size);
 }

@@ -60,6 +60,15 @@ struct Context {
     std::multimap<size_t, void*> free_blocks;
     std::map<void*, size_t> live_blocks;
     size_t bytes_reserved = 0;
+    bool pool_debug = false;  // TS_POOL_DEBUG, read once by the constructor: alloc reads no environment
+    // TEST KNOB TS_POOL_POISON=<32-bit word>, read once by the constructor: every block the pool hands out
+    // (the whole rounded block) and every table allocated beside it is first filled with the word, so that a
+    // kernel or driver that leaves something unwritten, or reads past what was written, can no longer find
+    // the right words there from an earlier use (tests/test_gpu_pool_poison.py).  Off: one branch per block.
+    bool poison_on = false;
+    uint32_t poison_word = 0;
+    uint64_t poison_fills = 0;  // blocks filled since creation (ts_ctx_stat 9)
+    void poison(void* p, size_t bytes);
 
     // twiddle tables in bit-reversed block order (kernels_ntt.hip): W[m + i] = w_{2m}^bitrev(i),
     // Montgomery form; index 0 unused.  Grown on demand, never shrunk.

@@ -113,6 +113,7 @@ const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, unsigned log_blo
     }
     uint32_t* d = nullptr;
     TS_HIP(hipMalloc((void**)&d, words * 4));
+    if (ctx.poison_on) ctx.poison(d, words * 4);
     const uint64_t n = 1ull << log_n;
     const uint32_t n_lo = 1u << SHIFT_LO_BITS;
     const uint32_t n_hi = log_n > (unsigned)SHIFT_LO_BITS ? 1u << (log_n - SHIFT_LO_BITS) : 1u;

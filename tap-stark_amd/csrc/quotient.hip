@@ -117,6 +117,7 @@ const uint32_t* selector_table(Context& ctx, unsigned log_n, unsigned log_qd, ui
         }
         const uint64_t qn = 1ull << (log_n + log_qd);
         TS_HIP(hipMalloc((void**)&st->d, 3 * qn * sizeof(uint32_t)));
+        if (ctx.poison_on) ctx.poison(st->d, 3 * qn * sizeof(uint32_t));
         launch_selectors(ctx, log_n, log_qd, st->d, st->d + qn, st->d + 2 * qn, shift);
         st->log_n = log_n;
         st->log_qd = log_qd;

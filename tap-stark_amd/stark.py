@@ -109,7 +109,8 @@ class Context:
                 "pool_bytes": int(out[3]), "reserve_failures": self.stat(4)}
 
     def stat(self, which: int) -> int:
-        """``ts_ctx_stat``: 3 pool bytes, 5 local-quotient fall-backs, 6-8 proof-of-work witness counters;
+        """``ts_ctx_stat``: 3 pool bytes, 5 local-quotient fall-backs, 6-8 proof-of-work witness counters,
+        9 device blocks filled with the test pattern of ``TS_POOL_POISON`` (0 when it was unset at creation);
         0, 1, 2 and 4 (the retired graph replay's counters) are always 0."""
         v = C.c_uint64()
         self.check(self._l.ts_ctx_stat(self.h, which, C.byref(v)))

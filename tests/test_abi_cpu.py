@@ -45,6 +45,26 @@ def test_device_count_and_null_context_diagnostics(lib):
     assert lib.ts_bench_stage(None, 0, 10, 4, 1, 1, C.byref(ms)) == 1
 
 
+def test_pool_poison_knob_is_parsed_before_the_device_is_touched(lib, monkeypatch):
+    """TS_POOL_POISON (test knob, include/tapstark.h): a value that is no 32-bit word makes ts_ctx_create return
+    TS_ERR_INVALID with a text, with or without a GPU; a word gets as far as the device (TS_ERR_HIP without one)."""
+    h = C.c_void_p()
+    for bad in ("poison", "0x", "0x100000000", "-1", "4294967296", "7 up", " ", "1 "):
+        monkeypatch.setenv("TS_POOL_POISON", bad)
+        assert lib.ts_ctx_create(0, C.byref(h)) == 1 and not h.value, bad
+        assert "TS_POOL_POISON" in (lib.ts_last_error(None) or b"").decode(), bad
+    for ok in ("", "0", "1", "0xFFFFFFFF", "4294967295", "017"):
+        monkeypatch.setenv("TS_POOL_POISON", ok)
+        rc = lib.ts_ctx_create(0, C.byref(h))
+        assert rc == (0 if lib.ts_device_count() else 2), ok
+        if rc == 0:
+            v = C.c_uint64(7)
+            assert lib.ts_ctx_stat(h, 9, C.byref(v)) == 0 and v.value == 0  # nothing allocated yet
+            assert lib.ts_ctx_stat(h, 10, C.byref(v)) == 1
+            lib.ts_ctx_destroy(h)
+            h = C.c_void_p()
+
+
 def test_no_cpu_fallback_without_device(lib):
     import torch
 

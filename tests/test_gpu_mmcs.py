@@ -183,5 +183,6 @@ def test_stage_bench_and_context_counters(ctx):
     # the retired hipGraph replay's counters
     assert [st["replays"], st["fallbacks"], st["shapes"], st["reserve_failures"]] == [0, 0, 0, 0]
     assert ctx.stat(7) == 0  # proof-of-work candidates of the device search refused by the host: never
+    assert ctx.stat(9) == 0  # blocks filled with the test pattern of TS_POOL_POISON: none, the knob is unset
     with pytest.raises(TsError):
-        ctx.stat(9)
+        ctx.stat(10)
