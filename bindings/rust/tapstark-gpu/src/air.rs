@@ -388,3 +388,50 @@ impl LogUp {
         b.assert_zero_ext_when(last, c);
     }
 }
+
+impl LogUp {
+    /// `ts_logup_multiplicities`: fills, in HBM, the multiplicity column of the table-side interaction `table` of
+    /// the resident `trace` -- its multiplicity term must be `Col(c)`, and c receives the result; its values are
+    /// the table's tuple -- from the interactions `lookups` (their multiplicity terms are the weights), negated so
+    /// that the filled trace balances the argument.  `preprocessed`: the row-major values `Prep` terms read.
+    /// Returns (n_missing, first_missing): the lookups of non-zero weight that are in no table row and the least
+    /// `row * lookups.len() + lookup` among them (`u64::MAX` when none); panics on a miss unless `allow_missing`.
+    /// Call it before `prove`, which consumes the trace.
+    pub fn fill_multiplicities(&self, trace: &mut crate::context::DeviceMatrix<'_>, table: usize, lookups: &[usize],
+                               preprocessed: Option<&crate::context::DeviceMatrix<'_>>, allow_missing: bool) -> (u64, u64) {
+        use crate::ffi::{ts_logup_mult_spec, ts_logup_multiplicities, ts_logup_term};
+        let c = |t: LogUpTerm| { let (kind, value) = t.to_c(); ts_logup_term { kind, value } };
+        let (m, tuple) = &self.interactions[table];
+        let out_column = match m {
+            LogUpTerm::Col(col) => *col,
+            _ => panic!("LogUp::fill_multiplicities: the table interaction's multiplicity must be a main column"),
+        };
+        assert!(!lookups.is_empty() && !lookups.contains(&table), "LogUp::fill_multiplicities: the lookups");
+        let table_terms: Vec<ts_logup_term> = tuple.iter().map(|t| c(*t)).collect();
+        let (mut lookup_terms, mut weights) = (Vec::new(), Vec::new());
+        for &i in lookups {
+            let (w, values) = &self.interactions[i];
+            assert_eq!(values.len(), tuple.len(), "LogUp::fill_multiplicities: interaction {i} has another number of values");
+            lookup_terms.extend(values.iter().map(|t| c(*t)));
+            weights.push(c(*w));
+        }
+        let spec = ts_logup_mult_spec {
+            struct_size: core::mem::size_of::<ts_logup_mult_spec>() as u32,
+            n_values: table_terms.len() as u32,
+            table: table_terms.as_ptr(),
+            n_lookups: weights.len() as u32,
+            lookups: lookup_terms.as_ptr(),
+            weights: weights.as_ptr(),
+            out_column,
+            negate: 1,
+        };
+        let (mut n_missing, mut first_missing) = (0u64, u64::MAX);
+        let rc = unsafe {
+            ts_logup_multiplicities(trace.ctx.raw, &spec, preprocessed.map_or(core::ptr::null(), |p| p.raw as *const _),
+                                    trace.raw, if allow_missing { &mut n_missing } else { core::ptr::null_mut() },
+                                    &mut first_missing)
+        };
+        trace.ctx.check(rc, "ts_logup_multiplicities");
+        (n_missing, first_missing)
+    }
+}

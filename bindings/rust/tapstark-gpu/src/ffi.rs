@@ -49,6 +49,21 @@ pub struct ts_logup_spec {
     pub interactions: *const ts_logup_interaction,
 }
 
+/// `ts_logup_mult_spec` (struct_size first): the table's tuple, the lookups' tuples and weights, and the main
+/// column that receives the multiplicities (`ts_logup_multiplicities`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_logup_mult_spec {
+    pub struct_size: u32,
+    pub n_values: u32,
+    pub table: *const ts_logup_term,
+    pub n_lookups: u32,
+    pub lookups: *const ts_logup_term,
+    pub weights: *const ts_logup_term,
+    pub out_column: u32,
+    pub negate: u32,
+}
+
 /// `ts_aux_fn`: the aux source of `ts_prove_aux` (user, ctx, live trace, challenge words, n_challenges, aux_out,
 /// exposed_out) -> status.  `None` for an AIR without aux columns.
 pub type ts_aux_fn = Option<
@@ -267,6 +282,9 @@ extern "C" {
     pub fn ts_logup_aux_build_pre(ctx: *mut ts_ctx, spec: *const ts_logup_spec, preprocessed: *const ts_matrix,
                                   trace: *const ts_matrix, challenges: *const u32, aux_out: *mut *mut ts_matrix,
                                   exposed_out: *mut u32) -> ts_status;
+    /// fills main column `spec.out_column` of the resident `trace` in place; `n_missing` / `first_missing` may be null
+    pub fn ts_logup_multiplicities(ctx: *mut ts_ctx, spec: *const ts_logup_mult_spec, preprocessed: *const ts_matrix,
+                                   trace: *mut ts_matrix, n_missing: *mut u64, first_missing: *mut u64) -> ts_status;
     // preprocessed AND aux columns together (TSPF v5): the _pre and _aux calls' contracts; a NULL key / root / aux
     // argument exactly for a width of 0
     pub fn ts_prove_pre_aux(ctx: *mut ts_ctx, cfg: *const ts_fri_config, air: *const ts_air, chal: *mut ts_challenger,

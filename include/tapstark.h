@@ -849,6 +849,41 @@ ts_status ts_logup_aux_build_pre(ts_ctx* ctx, const ts_logup_spec* spec, const t
                                  const ts_matrix* trace, const uint32_t challenges[8], ts_matrix** aux_out,
                                  uint32_t exposed_out[4]);
 
+/* The multiplicity column of one table, built in place in the resident main trace (csrc/logup_mult.hip).  Table
+ * rows with equal tuples form a class whose representative is its lowest row.  For every row r and lookup l with
+ * weight w != 0 whose tuple equals a class's tuple, w is added (in the field) to the representative; afterwards
+ * trace[t][out_column] holds that sum mod p -- (p - sum) mod p with `negate` -- on a representative row and 0 on
+ * every other row; no other word of the trace changes.  A lookup of weight 0 is skipped.  A lookup of non-zero
+ * weight whose tuple is in no table row is a MISS: *n_missing counts them, *first_missing is the least
+ * r * n_lookups + l among them (~0 when there are none), the status is TS_OK and the column holds the sums of the
+ * lookups that did hit; with n_missing == NULL any miss gives TS_ERR_INVARIANT with the row and the lookup in the
+ * last error.  Terms: kind 0 a canonical constant, 1 a main column, 2 a preprocessed column (needs `preprocessed`,
+ * row-major, the trace's height, this context, not consumed), all on the local row.  Column words are matched as
+ * they are stored; a weight is reduced mod p.  The result is the same words on every run.
+ * TS_ERR_INVALID before any device work, nothing written: a wrong struct_size, n_values outside 1 .. 8, n_lookups
+ * outside 1 .. 16, negate above 1, a term kind above 2, a column outside its matrix, a non-canonical constant, a
+ * kind-2 term without `preprocessed`, a table of another height or context, a trace that is not row-major, is
+ * consumed or is from another context, a height outside [1, 2^27], and out_column among the main columns any term
+ * reads.  A slot table with no free slot cannot happen (it is half empty) and is reported as TS_ERR_INVARIANT too, the
+ * ABI having no status for an internal error: the last error's text ("internal error") tells it from a miss.
+ * TS_LOGUP_HASH_BITS (0 .. 32, read on every call, unset = 32) keeps that many low bits of the private hash: a test
+ * knob that lengthens probe chains and changes no output. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t n_values;             /* tuple width, 1 .. 8 */
+    const ts_logup_term* table;    /* n_values terms: the table's tuple on row t */
+    uint32_t n_lookups;            /* 1 .. 16 */
+    const ts_logup_term* lookups;  /* n_lookups * n_values terms: lookup l's tuple on row r */
+    const ts_logup_term* weights;  /* n_lookups terms: lookup l's weight on row r (a field element;
+                                      constant 1 for a plain lookup, a 0/1 selector column, ...) */
+    uint32_t out_column;           /* the MAIN column that receives the result */
+    uint32_t negate;               /* 1: store p - sum (what a LogUp table interaction wants), 0: the sum */
+} ts_logup_mult_spec;
+ts_status ts_logup_multiplicities(ts_ctx* ctx, const ts_logup_mult_spec* spec,
+                                  const ts_matrix* preprocessed /* may be NULL */,
+                                  ts_matrix* trace /* not consumed; out_column overwritten */,
+                                  uint64_t* n_missing, uint64_t* first_missing /* both may be NULL */);
+
 /* ------------------------------------------------------------------ preprocessed AND aux columns together
  * An AIR with preprocessed_width > 0 and aux_width > 0 (a lookup against a FIXED table: the table is in a key
  * the verifier holds the root of).  These four calls extend their _pre and _aux parents and keep their contracts.

@@ -340,6 +340,48 @@ public:
         }
     }
 
+#ifdef TAPSTARK_H
+    // The ts_logup_mult_spec (needs tapstark.h included first) that fills the multiplicity column of the table-side
+    // interaction `table` -- its multiplicity term must be a main column: that column receives the result, its
+    // values are the table's tuple -- from the interactions `lookups` (their multiplicity terms are the weights),
+    // negated so that the filled trace balances.  `spec` points into the object's own storage: keep the object
+    // alive and where it is over the call.
+    struct MultSpec {
+        std::vector<ts_logup_term> table, lookups, weights;
+        ts_logup_mult_spec spec;
+        MultSpec() = default;
+        MultSpec(const MultSpec& o) : table(o.table), lookups(o.lookups), weights(o.weights), spec(o.spec) { repoint(); }
+        MultSpec& operator=(const MultSpec& o) {
+            table = o.table, lookups = o.lookups, weights = o.weights, spec = o.spec;
+            repoint();
+            return *this;
+        }
+        void repoint() { spec.table = table.data(), spec.lookups = lookups.data(), spec.weights = weights.data(); }
+    };
+    MultSpec mult_spec(size_t table, const std::vector<size_t>& lookups) const {
+        const LogUpInteraction& t = its_.at(table);
+        if (t.multiplicity.kind != 1)
+            throw std::invalid_argument("LogUp::mult_spec: the table interaction's multiplicity must be a main column");
+        if (lookups.empty()) throw std::invalid_argument("LogUp::mult_spec: no lookups");
+        MultSpec m;
+        for (const LogUpTerm& v : t.values) m.table.push_back(ts_logup_term{v.kind, v.value});
+        for (size_t i : lookups) {
+            const LogUpInteraction& l = its_.at(i);
+            if (i == table || l.values.size() != t.values.size())
+                throw std::invalid_argument("LogUp::mult_spec: a lookup is the table or has another number of values");
+            for (const LogUpTerm& v : l.values) m.lookups.push_back(ts_logup_term{v.kind, v.value});
+            m.weights.push_back(ts_logup_term{l.multiplicity.kind, l.multiplicity.value});
+        }
+        m.spec.struct_size = sizeof(ts_logup_mult_spec);
+        m.spec.n_values = (uint32_t)t.values.size();
+        m.spec.n_lookups = (uint32_t)lookups.size();
+        m.spec.out_column = t.multiplicity.value;
+        m.spec.negate = 1;
+        m.repoint();
+        return m;
+    }
+#endif
+
 private:
     std::vector<LogUpInteraction> its_;
 };

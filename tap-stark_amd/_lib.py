@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "ts_air_preprocessed_width", "ts_quotient_chunks_pre", "ts_prove_pre", "ts_verify_pre", "ts_check_constraints_pre",
     "ts_air_aux_info", "ts_quotient_chunks_aux", "ts_check_constraints_aux", "ts_prove_aux", "ts_verify_aux",
     "ts_logup_aux_width", "ts_logup_aux_build", "ts_logup_aux_build_pre",
+    "ts_logup_multiplicities",
     "ts_prove_pre_aux", "ts_verify_pre_aux", "ts_quotient_chunks_pre_aux", "ts_check_constraints_pre_aux",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
@@ -125,6 +126,13 @@ class LogupSpecC(C.Structure):
     """``ts_logup_spec`` (struct_size first)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_interactions", C.c_uint32),
                 ("interactions", C.POINTER(LogupInteractionC))]
+
+
+class LogupMultSpecC(C.Structure):
+    """``ts_logup_mult_spec`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_values", C.c_uint32), ("table", C.POINTER(LogupTermC)),
+                ("n_lookups", C.c_uint32), ("lookups", C.POINTER(LogupTermC)), ("weights", C.POINTER(LogupTermC)),
+                ("out_column", C.c_uint32), ("negate", C.c_uint32)]
 
 
 # ``ts_aux_fn``: (user, ctx, trace, challenges, n_challenges, aux_out, exposed_out) -> status
@@ -313,6 +321,8 @@ def lib() -> C.CDLL:
         l.ts_logup_aux_build.argtypes = [C.c_void_p, C.POINTER(LogupSpecC), C.c_void_p, u32p, voidpp, u32p]
         l.ts_logup_aux_build_pre.argtypes = [C.c_void_p, C.POINTER(LogupSpecC), C.c_void_p, C.c_void_p, u32p, voidpp,
                                              u32p]
+        l.ts_logup_multiplicities.argtypes = [C.c_void_p, C.POINTER(LogupMultSpecC), C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         # preprocessed and aux columns together: the key / root / aux arguments may be NULL (a width of 0)
         l.ts_quotient_chunks_pre_aux.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                  C.c_void_p, u32p, C.c_uint32, u32p, u32p, u32p, voidpp]

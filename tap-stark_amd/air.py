@@ -477,3 +477,59 @@ class LogUp:
         """The statement of a LogUp argument: the exposed sum is zero."""
         if any(int(x) != 0 for x in np.asarray(exposed).reshape(-1)):
             raise ValueError("LogUp: the exposed sum is not zero: the interactions do not balance")
+
+    def mult_spec(self, table: int, lookups=None) -> dict:
+        """The arguments of ``logup_multiplicities`` for the table-side interaction ``table`` (its multiplicity
+        term must be ``("col", c)``: that c receives the result; its values are the table's tuple) and the
+        interactions ``lookups`` that look it up (default: every other interaction with the same number of
+        values; their multiplicity terms are the weights).  ``negate`` is 1: the filled trace balances the sum."""
+        m, tuple_terms = self.interactions[table]
+        if m[0] != 1:
+            raise ValueError("LogUp.fill_multiplicities: the table interaction's multiplicity must be a main column")
+        if lookups is None:
+            lookups = [i for i, (_, vals) in enumerate(self.interactions) if i != table and len(vals) == len(tuple_terms)]
+        lookups = [int(i) for i in lookups]
+        if not lookups or table in lookups:
+            raise ValueError("LogUp.fill_multiplicities: needs at least one lookup interaction, none of them the table")
+        for i in lookups:
+            if len(self.interactions[i][1]) != len(tuple_terms):
+                raise ValueError(f"LogUp.fill_multiplicities: interaction {i} has another number of values than the table")
+        return {"table": list(tuple_terms), "lookups": [list(self.interactions[i][1]) for i in lookups],
+                "weights": [self.interactions[i][0] for i in lookups], "out_column": m[1], "negate": 1}
+
+    def fill_multiplicities(self, trace, table: int, lookups=None, preprocessed=None, allow_missing: bool = False):
+        """``ts_logup_multiplicities`` for this helper's interactions (``mult_spec``): fills the table interaction's
+        multiplicity column of the resident ``trace`` in place.  Returns ``(n_missing, first_missing)``; raises
+        if a lookup of non-zero weight is in no table row, unless ``allow_missing``."""
+        return logup_multiplicities(trace, **self.mult_spec(table, lookups), preprocessed=preprocessed,
+                                    allow_missing=allow_missing)
+
+
+def logup_multiplicities(trace, table, lookups, weights, out_column: int, negate: int = 1, preprocessed=None,
+                         allow_missing: bool = False):
+    """``ts_logup_multiplicities`` (include/tapstark.h, csrc/logup_mult.hip) with the explicit spec: ``table`` is
+    the table's tuple (a list of terms, as ``LogUp`` takes them), ``lookups`` one tuple per lookup, ``weights`` one
+    term per lookup.  Column ``out_column`` of the resident row-major ``trace`` is overwritten in HBM with, on the
+    lowest table row of each tuple, the field sum of the weights of the lookups that equal it (``p`` minus it with
+    ``negate``), and 0 on the other rows.  ``preprocessed``: the row-major ``DeviceMatrix`` that ``("prep", c)``
+    terms read.  Returns ``(n_missing, first_missing)``: the lookups of non-zero weight found in no table row and the
+    least ``row * len(lookups) + lookup`` among them (``2**64 - 1`` when none); with ``allow_missing`` false a miss
+    raises ``TsError`` (TS_ERR_INVARIANT) instead."""
+    import ctypes as C
+    from . import _lib
+    T = _lib.LogupTermC
+    table = [LogUp._term(t) for t in table]
+    lookups = [[LogUp._term(t) for t in tup] for tup in lookups]
+    weights = [LogUp._term(t) for t in weights]
+    if len(weights) != len(lookups) or any(len(tup) != len(table) for tup in lookups):
+        raise ValueError("logup_multiplicities: one weight per lookup and one term per table value in every lookup")
+    t_arr = (T * len(table))(*[T(k, v) for k, v in table])
+    l_arr = (T * (len(lookups) * len(table)))(*[T(k, v) for tup in lookups for k, v in tup])
+    w_arr = (T * len(weights))(*[T(k, v) for k, v in weights])
+    spec = _lib.LogupMultSpecC(C.sizeof(_lib.LogupMultSpecC), len(table), t_arr, len(lookups), l_arr, w_arr,
+                               int(out_column), int(negate))
+    ctx = trace.ctx
+    n_missing, first = C.c_uint64(0), C.c_uint64(0)
+    ctx.check(ctx._l.ts_logup_multiplicities(ctx.h, C.byref(spec), preprocessed.h if preprocessed is not None else None,
+                                             trace.h, C.byref(n_missing) if allow_missing else None, C.byref(first)))
+    return int(n_missing.value), int(first.value)

@@ -791,3 +791,16 @@ def generate_table_lookup_trace(n: int, seed: int = SPLITMIX_SEED, outside_row: 
     multiplicity columns of ``generate_range_lookup_trace``."""
     t = generate_range_lookup_trace(n, seed, outside_row)
     return np.ascontiguousarray(t[:, [0, 2]])
+
+
+def fill_range_lookup_multiplicities(trace, allow_missing: bool = False):
+    """Fills column 2 of a resident RangeLookupAir trace (values in column 0, the table in column 1) in HBM:
+    what ``generate_range_lookup_trace`` computes with ``np.bincount``.  Returns ``(n_missing, first_missing)``."""
+    return RangeLookupAir.logup.fill_multiplicities(trace, table=1, allow_missing=allow_missing)
+
+
+def fill_table_lookup_multiplicities(trace, table_values, allow_missing: bool = False):
+    """Fills column 1 of a resident TableLookupAir trace against ``table_values``, the row-major ``DeviceMatrix``
+    of the key's table (``PreprocessedKey.values``).  Returns ``(n_missing, first_missing)``."""
+    return TableLookupAir.logup.fill_multiplicities(trace, table=1, preprocessed=table_values,
+                                                    allow_missing=allow_missing)

@@ -1730,6 +1730,42 @@ ts_status ts_logup_aux_build_pre(ts_ctx* ctx, const ts_logup_spec* spec, const t
     });
 }
 
+// The multiplicity column of one table, in place in the resident trace (logup_mult.hip).
+ts_status ts_logup_multiplicities(ts_ctx* ctx, const ts_logup_mult_spec* spec, const ts_matrix* preprocessed,
+                                  ts_matrix* trace, uint64_t* n_missing, uint64_t* first_missing) {
+    if (!ctx || !spec || !trace) {
+        if (ctx) ctx->ctx.last_error = "ts_logup_multiplicities: null argument";
+        return TS_ERR_INVALID;
+    }
+    if (n_missing) *n_missing = 0;
+    if (first_missing) *first_missing = ~0ull;
+    return guard(ctx, [&] {
+        TS_REQUIRE(spec->struct_size == sizeof(ts_logup_mult_spec), ts::TS_ERR_INVALID,
+                   "logup multiplicities: bad struct_size");
+        TS_REQUIRE(spec->n_values >= 1 && spec->n_values <= ts::LOGUP_MAX_VALUES && spec->table, ts::TS_ERR_INVALID,
+                   "logup multiplicities: between 1 and 8 values");
+        TS_REQUIRE(spec->n_lookups >= 1 && spec->n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && spec->lookups && spec->weights,
+                   ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookups");
+        ts::LogupMultSpec s;
+        auto load = [](const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
+            for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
+        };
+        load(spec->table, spec->n_values, s.table);
+        load(spec->lookups, (size_t)spec->n_lookups * spec->n_values, s.lookups);
+        load(spec->weights, spec->n_lookups, s.weights);
+        s.out_column = spec->out_column;
+        s.negate = spec->negate;
+        const ts::LogupMultResult r = ts::logup_multiplicities(ctx->ctx, s, trace->m, preprocessed ? &preprocessed->m : nullptr);
+        if (n_missing) *n_missing = r.n_missing;
+        if (first_missing) *first_missing = r.first_missing;
+        if (!n_missing && r.n_missing)
+            throw ts::Error(ts::TS_ERR_INVARIANT,
+                            "logup multiplicities: the tuple of row " + std::to_string(r.first_missing / spec->n_lookups) +
+                                ", lookup " + std::to_string(r.first_missing % spec->n_lookups) + " is in no table row (" +
+                                std::to_string(r.n_missing) + " such lookups)");
+    });
+}
+
 // ------------------------------------------------------------------ preprocessed and aux columns together
 // Extends ts_quotient_chunks_pre and ts_quotient_chunks_aux: the quotient over (key, aux, trace).
 ts_status ts_quotient_chunks_pre_aux(ts_ctx* ctx, const ts_pcs_data* key, const ts_pcs_data* aux_data,

@@ -35,4 +35,26 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
                              const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table = nullptr,
                              bool takes_table = false);
 
+// ---- the multiplicity column of one table (logup_mult.hip)
+constexpr uint32_t LOGUP_MULT_MAX_LOOKUPS = 16;
+
+struct LogupMultSpec {
+    std::vector<LogupTerm> table;     // n_values terms: the table's tuple on row t
+    std::vector<LogupTerm> lookups;   // n_lookups * n_values terms: lookup l's tuple on row r
+    std::vector<LogupTerm> weights;   // n_lookups terms: lookup l's weight on row r
+    uint32_t out_column = 0;          // the main column that receives the result
+    uint32_t negate = 0;              // 1: p - sum
+};
+struct LogupMultResult {
+    uint64_t n_missing, first_missing;  // lookups of non-zero weight in no table row; the least r * n_lookups + l (~0: none)
+};
+// Overwrites trace[t][out_column] (row-major, this context, not consumed) for every t with the field sum of the
+// weights of the lookups whose tuple is the table's tuple on row t -- on the lowest row of each class of equal
+// table rows, 0 on the others -- or p minus it.  `table`: the row-major values of the preprocessed columns for
+// kind-2 terms (the trace's height, this context; may be null without such terms).  Throws TS_ERR_INVALID before
+// any device work on a spec outside the limits (out_column among the main columns it reads included);
+// synchronises the stream once.
+LogupMultResult logup_multiplicities(Context& ctx, const LogupMultSpec& spec, DeviceMatrix& trace,
+                                     const DeviceMatrix* table);
+
 }  // namespace ts

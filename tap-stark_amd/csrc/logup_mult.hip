@@ -1,0 +1,260 @@
+// LogUp multiplicity column, built in HBM from the still-resident main trace: for every table row the (field)
+// sum of the weights of the lookups whose tuple equals the row's tuple, stored in (or negated into) one main
+// column.  Table rows with equal tuples form a class; the class's lowest row receives the sum, the others 0.
+//
+// Three plain launches and one small copy back; no grid barrier, no cooperative launch, no workgroup waits for
+// another; every loop is bounded by `capacity` (the power of two >= 2 n), MULT_MAX_LOOKUPS or the wave size:
+//   k_mult_insert  one table row per lane: hash the tuple, probe linearly; atomicCAS(slot, EMPTY, row) either
+//                  inserts the row or returns the row that holds the slot; that row's tuple is read from the
+//                  matrix (read-only for the launch) and compared: equal -> atomicMin(slot, row), else next slot.
+//                  A slot's content is only ever taken from the value an atomic returned (a plain load of a word
+//                  another XCD has just written can be stale); a slot never goes back to empty and never changes
+//                  class, so each class ends in exactly one slot, holding its lowest row, whatever the order.
+//   k_mult_count   one trace row per lane, looping over the lookups: weight 0 is skipped; otherwise probe with
+//                  plain loads (the slots are final: an earlier launch wrote them); empty -> a miss (64-bit
+//                  atomicAdd on the count, atomicMin on r * L + l); equal tuple -> no-return 64-bit
+//                  atomicAdd(&sums[rep], w), w canonical.  Integer adds commute: the sums do not depend on order.
+//                  They cannot wrap: 2^27 rows * 16 lookups * p < 2^62.
+//   k_mult_write   one table row per lane: sums[t] % p, or p minus it, into trace[t][out_column].
+// The hash is private to this file and changes no output; TS_LOGUP_HASH_BITS (0 .. 32, read on every call) masks
+// it to that many low bits before it is reduced to a slot: a test knob that makes probe chains as long as the table.
+// Contention: a wave whose hits all go to ONE representative (padding rows, a selector-heavy trace) sums their weights
+// with shuffles and issues one add; every other wave issues one add per hit (DESIGN.md has the measurement: a ballot
+// loop over every distinct destination of a wave lost on the byte-valued and the uniform inputs and was not kept).
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+
+#include "logup.hpp"
+
+namespace ts {
+
+constexpr int MULT_THREADS = 256;
+constexpr uint32_t MULT_EMPTY = 0xFFFFFFFFu;
+
+struct MultDev {
+    uint32_t n_values, n_lookups, width, table_width, out_column, negate, hash_mask, cap_mask;
+    uint32_t t_kind[LOGUP_MAX_VALUES], t_val[LOGUP_MAX_VALUES];
+    uint32_t w_kind[LOGUP_MULT_MAX_LOOKUPS], w_val[LOGUP_MULT_MAX_LOOKUPS];
+    uint32_t l_kind[LOGUP_MULT_MAX_LOOKUPS][LOGUP_MAX_VALUES], l_val[LOGUP_MULT_MAX_LOOKUPS][LOGUP_MAX_VALUES];
+};
+
+// what the one copy back holds (32 bytes)
+struct MultBack {
+    unsigned long long n_missing, first_missing;
+    uint32_t error, pad[3];
+};
+
+__device__ __forceinline__ uint32_t mult_term(uint32_t kind, uint32_t val, const uint32_t* __restrict__ row,
+                                              const uint32_t* __restrict__ pre_row) {
+    return kind == 0 ? val : (kind == 1 ? row : pre_row)[val];
+}
+
+struct MultTuple {
+    uint32_t v[LOGUP_MAX_VALUES];
+};
+
+__device__ __forceinline__ uint32_t mult_hash(const MultTuple& t, uint32_t nv) {
+    uint32_t h = 0x9E3779B9u;
+#pragma unroll
+    for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++)
+        if (q < (int)nv) {
+            h = (h ^ t.v[q]) * 0x85EBCA6Bu;
+            h ^= h >> 13;
+        }
+    h *= 0xC2B2AE35u;
+    return h ^ (h >> 16);
+}
+
+// the table's tuple on row t
+__device__ __forceinline__ MultTuple mult_table_tuple(const MultDev& s, const uint32_t* __restrict__ trace,
+                                                      const uint32_t* __restrict__ pre, uint64_t t) {
+    const uint32_t* row = trace + t * s.width;
+    const uint32_t* pre_row = pre + t * s.table_width;
+    MultTuple out;
+#pragma unroll
+    for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++)
+        out.v[q] = q < (int)s.n_values ? mult_term(s.t_kind[q], s.t_val[q], row, pre_row) : 0;
+    return out;
+}
+
+__device__ __forceinline__ bool mult_equal(const MultTuple& a, const MultTuple& b) {
+    bool eq = true;  // (the words past n_values are zero on both sides)
+#pragma unroll
+    for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++) eq = eq && a.v[q] == b.v[q];
+    return eq;
+}
+
+__global__ void __launch_bounds__(MULT_THREADS)
+k_mult_insert(const MultDev s, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ pre, uint64_t n,
+              uint32_t* __restrict__ slots, MultBack* __restrict__ back) {
+    const uint64_t t = (uint64_t)blockIdx.x * MULT_THREADS + threadIdx.x;
+    if (t >= n) return;
+    const MultTuple mine = mult_table_tuple(s, trace, pre, t);
+    const uint32_t h = mult_hash(mine, s.n_values) & s.hash_mask;
+    for (uint64_t step = 0; step <= s.cap_mask; step++) {
+        uint32_t* slot = slots + ((h + (uint32_t)step) & s.cap_mask);
+        const uint32_t old = atomicCAS(slot, MULT_EMPTY, (uint32_t)t);
+        if (old == MULT_EMPTY) return;
+        if (mult_equal(mult_table_tuple(s, trace, pre, old), mine)) {
+            atomicMin(slot, (uint32_t)t);
+            return;
+        }
+    }
+    atomicOr(&back->error, 1u);  // every slot holds another class: impossible at load <= 1/2
+}
+
+__device__ __forceinline__ unsigned long long mult_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(MULT_THREADS)
+k_mult_count(const MultDev s, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ pre, uint64_t n,
+             const uint32_t* __restrict__ slots, unsigned long long* __restrict__ sums, MultBack* __restrict__ back) {
+    const uint64_t r = (uint64_t)blockIdx.x * MULT_THREADS + threadIdx.x;
+    const bool live = r < n;  // (no early return: every lane of the wave takes part in the ballots below)
+    const unsigned lane = threadIdx.x & 63;
+    const uint32_t* row = trace + (live ? r : 0) * s.width;
+    const uint32_t* pre_row = pre + (live ? r : 0) * s.table_width;
+    for (uint32_t l = 0; l < s.n_lookups; l++) {
+        uint32_t w = live ? mult_term(s.w_kind[l], s.w_val[l], row, pre_row) : 0;
+        w = w >= P ? w - P : w;  // canonical, whatever word the column held (2^32 < 3 p)
+        w = w >= P ? w - P : w;
+        uint32_t rep = MULT_EMPTY;
+        if (w != 0) {
+            MultTuple mine;
+#pragma unroll
+            for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++)
+                mine.v[q] = q < (int)s.n_values ? mult_term(s.l_kind[l][q], s.l_val[l][q], row, pre_row) : 0;
+            const uint32_t h = mult_hash(mine, s.n_values) & s.hash_mask;
+            for (uint64_t step = 0; step <= s.cap_mask; step++) {
+                const uint32_t at = slots[(h + (uint32_t)step) & s.cap_mask];
+                if (at == MULT_EMPTY) break;
+                if (mult_equal(mult_table_tuple(s, trace, pre, at), mine)) {
+                    rep = at;
+                    break;
+                }
+            }
+            if (rep == MULT_EMPTY) {  // (a full table of other classes is a miss too)
+                atomicAdd(&back->n_missing, 1ull);
+                atomicMin(&back->first_missing, (unsigned long long)r * s.n_lookups + l);
+            }
+        }
+        const bool hit = rep != MULT_EMPTY;
+        const unsigned long long hits = __ballot(hit);
+        if (hits == 0) continue;  // (wave-uniform)
+        const int leader = __ffsll((long long)hits) - 1;
+        const uint32_t dest = (uint32_t)__shfl((int)rep, leader, 64);
+        if ((hits & (hits - 1)) && __ballot(hit && rep == dest) == hits) {
+            // several hits, one representative: one add for the wave
+            const unsigned long long sum = mult_wave_sum(hit ? (unsigned long long)w : 0ull);
+            if (lane == (unsigned)leader) atomicAdd(sums + dest, sum);
+        } else if (hit) {
+            atomicAdd(sums + rep, (unsigned long long)w);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(MULT_THREADS)
+k_mult_write(uint32_t width, uint32_t out_column, uint32_t negate, uint64_t n,
+             const unsigned long long* __restrict__ sums, uint32_t* __restrict__ trace) {
+    const uint64_t t = (uint64_t)blockIdx.x * MULT_THREADS + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t v = (uint32_t)(sums[t] % P);
+    trace[t * width + out_column] = negate && v ? P - v : v;
+}
+
+// an integer knob in [lo, hi], or `unset`
+static long mult_knob(const char* name, long lo, long hi, long unset) {
+    const char* e = getenv(name);
+    if (!e || !*e) return unset;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    TS_REQUIRE(end && !*end && v >= lo && v <= hi, TS_ERR_INVALID,
+               (std::string(name) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]").c_str());
+    return v;
+}
+
+LogupMultResult logup_multiplicities(Context& ctx, const LogupMultSpec& spec, DeviceMatrix& trace,
+                                     const DeviceMatrix* table) {
+    StageTimer timer(&ctx, "logup multiplicities");
+    MultDev s;
+    memset(&s, 0, sizeof s);
+    const size_t nv = spec.table.size(), nl = spec.weights.size();
+    TS_REQUIRE(nv >= 1 && nv <= LOGUP_MAX_VALUES, TS_ERR_INVALID, "logup multiplicities: between 1 and 8 values");
+    TS_REQUIRE(nl >= 1 && nl <= LOGUP_MULT_MAX_LOOKUPS && spec.lookups.size() == nl * nv, TS_ERR_INVALID,
+               "logup multiplicities: between 1 and 16 lookups of n_values terms each");
+    TS_REQUIRE(spec.negate <= 1, TS_ERR_INVALID, "logup multiplicities: negate must be 0 or 1");
+    TS_REQUIRE(trace.buf.p && trace.layout == DeviceMatrix::ROW_MAJOR && trace.buf.ctx == &ctx, TS_ERR_INVALID,
+               "logup multiplicities: needs a row-major, unconsumed trace made on this context");
+    TS_REQUIRE(trace.height >= 1 && trace.height <= (1ull << 27) && trace.width >= 1, TS_ERR_INVALID,
+               "logup multiplicities: trace height must be in [1, 2^27]");
+    TS_REQUIRE(spec.out_column < trace.width, TS_ERR_INVALID, "logup multiplicities: out_column outside the trace");
+    s.width = trace.width;
+    if (table) {
+        TS_REQUIRE(table->buf.p && table->layout == DeviceMatrix::ROW_MAJOR && table->buf.ctx == &ctx, TS_ERR_INVALID,
+                   "logup multiplicities: the preprocessed table must be row-major, unconsumed and made on this context");
+        TS_REQUIRE(table->height == trace.height && table->width >= 1, TS_ERR_INVALID,
+                   "logup multiplicities: the preprocessed table must have the trace's height");
+        s.table_width = table->width;
+    }
+    auto term = [&](const LogupTerm& tm, uint32_t& kind, uint32_t& val) {
+        TS_REQUIRE(tm.kind <= 2, TS_ERR_INVALID,
+                   "logup multiplicities: term kind must be 0 (constant), 1 (column) or 2 (preprocessed column)");
+        TS_REQUIRE(tm.kind != 2 || table, TS_ERR_INVALID,
+                   "logup multiplicities: a preprocessed-column term without a preprocessed table");
+        TS_REQUIRE(tm.kind == 2 ? tm.value < s.table_width : tm.kind ? tm.value < trace.width : tm.value < P, TS_ERR_INVALID,
+                   "logup multiplicities: a column outside the trace or the preprocessed table, or a non-canonical constant");
+        TS_REQUIRE(tm.kind != 1 || tm.value != spec.out_column, TS_ERR_INVALID,
+                   "logup multiplicities: out_column is among the main columns the spec reads");
+        kind = tm.kind;
+        val = tm.value;
+    };
+    for (size_t q = 0; q < nv; q++) term(spec.table[q], s.t_kind[q], s.t_val[q]);
+    for (size_t l = 0; l < nl; l++) {
+        term(spec.weights[l], s.w_kind[l], s.w_val[l]);
+        for (size_t q = 0; q < nv; q++) term(spec.lookups[l * nv + q], s.l_kind[l][q], s.l_val[l][q]);
+    }
+    const long bits = mult_knob("TS_LOGUP_HASH_BITS", 0, 32, 32);
+    s.n_values = (uint32_t)nv;
+    s.n_lookups = (uint32_t)nl;
+    s.out_column = spec.out_column;
+    s.negate = spec.negate;
+    s.hash_mask = bits >= 32 ? 0xFFFFFFFFu : (1u << bits) - 1;
+
+    const uint64_t n = trace.height;
+    uint64_t capacity = 2;
+    while (capacity < 2 * n) capacity <<= 1;  // <= 2^28
+    s.cap_mask = (uint32_t)(capacity - 1);
+    DevBuf<uint32_t> slots(&ctx, capacity);
+    DevBuf<unsigned long long> sums(&ctx, n);
+    DevBuf<MultBack> back(&ctx, 1);
+    TS_HIP(hipMemsetAsync(slots.p, 0xff, capacity * sizeof(uint32_t), ctx.stream));
+    TS_HIP(hipMemsetAsync(sums.p, 0, n * sizeof(unsigned long long), ctx.stream));
+    TS_HIP(hipMemsetAsync(back.p, 0, sizeof(MultBack), ctx.stream));
+    TS_HIP(hipMemsetAsync(&back.p->first_missing, 0xff, sizeof(unsigned long long), ctx.stream));
+    const uint32_t* pre = table ? table->buf.p : trace.buf.p;  // (no kind-2 term gets here without a table)
+    const dim3 grid((unsigned)((n + MULT_THREADS - 1) / MULT_THREADS)), block(MULT_THREADS);
+    TS_LAUNCH(ctx, k_mult_insert, grid, block, 0, s, (const uint32_t*)trace.buf.p, pre, n, slots.p, back.p);
+    TS_HIP(hipGetLastError());
+    TS_LAUNCH(ctx, k_mult_count, grid, block, 0, s, (const uint32_t*)trace.buf.p, pre, n, (const uint32_t*)slots.p, sums.p,
+              back.p);
+    TS_HIP(hipGetLastError());
+    TS_LAUNCH(ctx, k_mult_write, grid, block, 0, s.width, s.out_column, s.negate, n,
+              (const unsigned long long*)sums.p, trace.buf.p);
+    TS_HIP(hipGetLastError());
+    MultBack host;
+    d2h_sync(ctx, &host, back.p, sizeof host);
+    if (host.error)
+        throw Error(TS_ERR_INVARIANT, "logup multiplicities: internal error: the slot table was full");
+    return LogupMultResult{host.n_missing, host.first_missing};
+}
+
+}  // namespace ts
