@@ -137,6 +137,50 @@ pub struct ts_batch_item {
 }
 pub const TS_BATCH_DIGEST: u32 = 1;
 
+/// What a lane of `ts_prove_batch_lookup` owns for all of its items: the AIR's committed key and the row-major
+/// table its kind-2 terms read; neither is consumed.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ts_batch_lane {
+    pub struct_size: u32, // = size_of::<ts_batch_lane>()
+    pub key: *const ts_pcs_data,     // null iff preprocessed_width == 0
+    pub key_values: *const ts_matrix, // may be null
+}
+
+/// One statement of `ts_prove_batch_lookup`: `ts_batch_item`'s inputs, the aux source (exactly one of `logup` /
+/// `aux_fn` for an AIR with aux columns), the multiplicity fills, then what the library writes back.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ts_batch_lookup_item {
+    pub struct_size: u32, // = size_of::<ts_batch_lookup_item>() (the library refuses the whole call otherwise)
+    pub lane: u32,
+    pub trace: *mut ts_matrix,
+    pub host_trace: *const u32,
+    pub height: u64,
+    pub width: u32,
+    pub n_public: u32,
+    pub public_values: *const u32,
+    pub challenger: *const ts_challenger,
+    pub proof_out: *mut u32,
+    pub cap_words: usize,
+    pub logup: *const ts_logup_spec, // run by the library on the lane's stream ...
+    pub aux_fn: ts_aux_fn,           // ... or a callback on the lane's thread
+    pub aux_user: *mut c_void,
+    pub mult: *const ts_logup_mult_spec, // n_mult fills of the resident trace, before the commit
+    pub n_mult: u32,
+    pub cap_exposed: u32,
+    pub exposed_out: *mut u32,
+    pub status: ts_status, // -1 = not attempted
+    pub n_exposed: u32,
+    pub n_words: usize,
+    pub n_missing: u64,
+    pub first_missing: u64,
+    pub proof_blake3: [u32; 8],
+    pub final_state: [u32; 34],
+    pub start_ms: f64,
+    pub wall_ms: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct ts_rccl_info {
@@ -295,6 +339,10 @@ extern "C" {
                              preprocessed_root: *const u32, proof: *const u32, n_words: usize,
                              public_values: *const u32, n_public: u32, exposed_out: *mut u32, cap_exposed: u32,
                              verdict: *mut c_int) -> ts_status;
+    /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
+    pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
+                                 n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,
+                                 n_items: u32, gate_ms: f64, flags: u32) -> ts_status;
     pub fn ts_quotient_chunks_pre_aux(ctx: *mut ts_ctx, key: *const ts_pcs_data, aux_data: *const ts_pcs_data,
                                       trace_data: *const ts_pcs_data, log_blowup: u32, air: *const ts_air,
                                       public_values: *const u32, n_public: u32, challenges: *const u32,

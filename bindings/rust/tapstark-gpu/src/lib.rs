@@ -34,5 +34,6 @@ pub use comm::{prove_gpu_sharded, rccl_unique_id, RcclComm};
 pub use context::{DeviceMatrix, GpuChallenger, GpuContext, MONTY_BITS};
 pub use pcs::{FriConfig, GpuDft, GpuFriPcs, GpuPcsError, GpuProverData};
 pub use proof::Proof;
-pub use prove::{prove_gpu, prove_gpu_batch, prove_gpu_stepwise, BatchError, BatchStatement, CompiledAir};
+pub use prove::{prove_gpu, prove_gpu_batch, prove_gpu_batch_lookup, prove_gpu_stepwise, BatchError, BatchStatement, CompiledAir,
+                LookupBatchError, LookupLane, LookupProof};
 pub use tap::{prove_gpu_tap, verify_gpu_tap, GpuTapProof, GpuTapProverData, GpuTapTreeMmcs, LockTable};

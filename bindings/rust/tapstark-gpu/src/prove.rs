@@ -14,10 +14,10 @@ use uni_stark::SymbolicAirBuilder;
 
 use basic::bf_pcs::Pcs;
 
-use crate::air::serialize_constraints;
+use crate::air::{serialize_constraints, LogUp, LogUpTerm};
 use crate::context::{DeviceMatrix, GpuChallenger, GpuContext, PinnedTrace};
 use crate::ffi::*;
-use crate::pcs::{FriConfig, GpuFriPcs};
+use crate::pcs::{FriConfig, GpuFriPcs, GpuProverData};
 use crate::proof::{Challenge, Commitments, OpenedValues, Proof, Val};
 
 /// An AIR registered with the library (tape uploaded, quotient kernel specialised with hiprtc)
@@ -29,6 +29,15 @@ pub struct CompiledAir<'c> {
 impl<'c> CompiledAir<'c> {
     pub fn new<A: Air<SymbolicAirBuilder<Val>>>(ctx: &'c GpuContext, air: &A, num_public_values: usize) -> Self {
         let tape = serialize_constraints::<Val, A>(air, num_public_values);
+        let mut raw = ptr::null_mut();
+        ctx.check(unsafe { ts_air_compile(ctx.raw, tape.as_ptr(), tape.len(), &mut raw) }, "ts_air_compile");
+        let mut lqd = 0u32;
+        unsafe { ts_air_info(raw, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), &mut lqd) };
+        Self { ctx, raw, log_quotient_degree: lqd as usize }
+    }
+
+    /// An AIR from its tape: what `AuxAirBuilder::tape()` gives for an AIR with preprocessed or aux columns.
+    pub fn from_tape(ctx: &'c GpuContext, tape: &[u32]) -> Self {
         let mut raw = ptr::null_mut();
         ctx.check(unsafe { ts_air_compile(ctx.raw, tape.as_ptr(), tape.len(), &mut raw) }, "ts_air_compile");
         let mut lqd = 0u32;
@@ -209,6 +218,222 @@ pub fn prove_gpu_batch(fri: FriConfig, lanes: &[&CompiledAir<'_>], statements: &
         .map(|(i, it)| match it.status {
             TS_OK => Ok(Proof::from_tspf(&outs[i][..it.n_words])),
             status => Err(BatchError { status: if refused { rc } else { status }, n_words: it.n_words }),
+        })
+        .collect()
+}
+
+/// One lane of `prove_gpu_batch_lookup`: its AIR, and what the lane owns for all of its statements.
+pub struct LookupLane<'a> {
+    pub air: &'a CompiledAir<'a>,
+    /// the AIR's committed key (made on the lane's context); `None` exactly for an AIR without preprocessed columns
+    pub key: Option<&'a GpuProverData<'a>>,
+    /// the row-major table values `LogUpTerm::Prep` terms read (the key's commit consumed its own matrix)
+    pub key_values: Option<&'a DeviceMatrix<'a>>,
+    /// the aux source of every statement of the lane, run by the library on the lane's stream; `None` for an AIR
+    /// without aux columns
+    pub logup: Option<&'a LogUp>,
+    /// multiplicity fills of every statement's trace, before its commit: (table interaction, lookup interactions)
+    /// of `logup`, as `LogUp::fill_multiplicities` takes them
+    pub fills: Vec<(usize, Vec<usize>)>,
+}
+
+/// A proved statement of `prove_gpu_batch_lookup`: the TSPF v5 words (`ts_verify_pre_aux` checks them) and the
+/// exposed words, whose statement -- for LogUp: all zero -- is the caller's to check.
+pub struct LookupProof {
+    pub words: Vec<u32>,
+    pub exposed: Vec<u32>,
+}
+
+/// Why a statement of `prove_gpu_batch_lookup` has no proof: `BatchError`, and for a multiplicity fill that found a
+/// lookup in no table row (`TS_ERR_INVARIANT`; the lane goes on) the count and the first `row * lookups + lookup`.
+#[derive(Debug, Clone, Copy)]
+pub struct LookupBatchError {
+    pub status: ts_status,
+    pub n_words: usize,
+    pub n_missing: u64,
+    pub first_missing: u64,
+}
+
+/// `prove_gpu_batch` for AIRs with a preprocessed key, challenge-phase columns or both (`ts_prove_batch_lookup`):
+/// the key per lane, the LogUp columns and multiplicity columns built by the library inside the lane, no callback
+/// per proof.  Statement i's words are those of `ts_prove_pre_aux` on its lane's context.
+pub fn prove_gpu_batch_lookup(fri: FriConfig, lanes: &[LookupLane<'_>], statements: &[BatchStatement<'_>],
+                              gate_ms: f64) -> Vec<Result<LookupProof, LookupBatchError>> {
+    let term = |t: LogUpTerm| {
+        let (kind, value) = t.to_c();
+        ts_logup_term { kind, value }
+    };
+    let ctxs: Vec<*mut ts_ctx> = lanes.iter().map(|l| l.air.ctx.raw).collect();
+    let airs: Vec<*const ts_air> = lanes.iter().map(|l| l.air.raw as *const ts_air).collect();
+    let raw_lanes: Vec<ts_batch_lane> = lanes
+        .iter()
+        .map(|l| ts_batch_lane {
+            struct_size: core::mem::size_of::<ts_batch_lane>() as u32,
+            key: l.key.map_or(ptr::null(), |k| k.raw as *const ts_pcs_data),
+            key_values: l.key_values.map_or(ptr::null(), |m| m.raw as *const ts_matrix),
+        })
+        .collect();
+    // per lane: the spec's terms, interactions and header, and the fills' terms and headers; all of it lives to the
+    // end of this function, and no vector is touched after a pointer into it was taken
+    let values: Vec<Vec<Vec<ts_logup_term>>> = lanes
+        .iter()
+        .map(|l| l.logup.map_or(Vec::new(), |u| {
+            u.interactions.iter().map(|(_, v)| v.iter().map(|t| term(*t)).collect()).collect()
+        }))
+        .collect();
+    let interactions: Vec<Vec<ts_logup_interaction>> = lanes
+        .iter()
+        .enumerate()
+        .map(|(k, l)| l.logup.map_or(Vec::new(), |u| {
+            u.interactions
+                .iter()
+                .enumerate()
+                .map(|(i, (m, v))| ts_logup_interaction {
+                    multiplicity: term(*m),
+                    n_values: v.len() as u32,
+                    values: values[k][i].as_ptr(),
+                })
+                .collect()
+        }))
+        .collect();
+    let specs: Vec<ts_logup_spec> = interactions
+        .iter()
+        .map(|its| ts_logup_spec {
+            struct_size: core::mem::size_of::<ts_logup_spec>() as u32,
+            n_interactions: its.len() as u32,
+            interactions: its.as_ptr(),
+        })
+        .collect();
+    // (table tuple, lookups' tuples, weights) per fill
+    let fill_terms: Vec<Vec<(Vec<ts_logup_term>, Vec<ts_logup_term>, Vec<ts_logup_term>, u32)>> = lanes
+        .iter()
+        .map(|l| {
+            l.fills
+                .iter()
+                .map(|(table, lookups)| {
+                    let u = l.logup.expect("prove_gpu_batch_lookup: fills need the lane's LogUp");
+                    let (m, tuple) = &u.interactions[*table];
+                    let out_column = match m {
+                        LogUpTerm::Col(c) => *c,
+                        _ => panic!("prove_gpu_batch_lookup: the table interaction's multiplicity must be a main column"),
+                    };
+                    let mut lookup_terms = Vec::new();
+                    let mut weights = Vec::new();
+                    for &i in lookups {
+                        let (w, v) = &u.interactions[i];
+                        assert_eq!(v.len(), tuple.len(), "prove_gpu_batch_lookup: interaction {i} has another number of values");
+                        lookup_terms.extend(v.iter().map(|t| term(*t)));
+                        weights.push(term(*w));
+                    }
+                    (tuple.iter().map(|t| term(*t)).collect(), lookup_terms, weights, out_column)
+                })
+                .collect()
+        })
+        .collect();
+    let fill_specs: Vec<Vec<ts_logup_mult_spec>> = fill_terms
+        .iter()
+        .map(|fs| {
+            fs.iter()
+                .map(|(table, lookups, weights, out_column)| ts_logup_mult_spec {
+                    struct_size: core::mem::size_of::<ts_logup_mult_spec>() as u32,
+                    n_values: table.len() as u32,
+                    table: table.as_ptr(),
+                    n_lookups: weights.len() as u32,
+                    lookups: lookups.as_ptr(),
+                    weights: weights.as_ptr(),
+                    out_column: *out_column,
+                    negate: 1,
+                })
+                .collect()
+        })
+        .collect();
+
+    let words: Vec<Vec<u32>> =
+        statements.iter().map(|s| s.trace.values.iter().map(|v| v.as_canonical_u32()).collect()).collect();
+    let pis: Vec<Vec<u32>> =
+        statements.iter().map(|s| s.public_values.iter().map(|v| v.as_canonical_u32()).collect()).collect();
+    // the widths beside the trace's and the exposed words, per lane
+    let dims: Vec<(usize, usize)> = lanes
+        .iter()
+        .map(|l| {
+            let (mut pw, mut aw, mut nc, mut ne) = (0u32, 0u32, 0u32, 0u32);
+            unsafe {
+                ts_air_preprocessed_width(l.air.raw, &mut pw);
+                ts_air_aux_info(l.air.raw, &mut aw, &mut nc, &mut ne);
+            }
+            ((pw + aw) as usize, ne as usize)
+        })
+        .collect();
+    let mut outs: Vec<Vec<u32>> = statements
+        .iter()
+        .map(|s| {
+            let lqd = lanes.get(s.lane).map_or(0, |l| l.air.log_quotient_degree);
+            let (extra, ne) = dims.get(s.lane).copied().unwrap_or((0, 0));
+            let log_lde = s.trace.height().trailing_zeros() as usize + fri.log_blowup;
+            // two more Merkle paths and batch headers per query than a plain proof of the joined width
+            vec![0u32; proof_capacity(&fri, s.trace.height(), s.trace.width() + extra, 1 << lqd) + ne + 16
+                       + 2 * fri.num_queries * (8 * log_lde + 8)]
+        })
+        .collect();
+    let mut exposed: Vec<[u32; 4]> = vec![[0; 4]; statements.len()];
+    let mut items: Vec<ts_batch_lookup_item> = statements
+        .iter()
+        .enumerate()
+        .map(|(i, s)| {
+            let l = s.lane;
+            let has_spec = lanes.get(l).map_or(false, |lane| lane.logup.is_some());
+            let fills = fill_specs.get(l).map_or(&[][..], |f| &f[..]);
+            ts_batch_lookup_item {
+                struct_size: core::mem::size_of::<ts_batch_lookup_item>() as u32,
+                lane: l as u32,
+                trace: ptr::null_mut(),
+                host_trace: words[i].as_ptr(),
+                height: s.trace.height() as u64,
+                width: s.trace.width() as u32,
+                n_public: pis[i].len() as u32,
+                public_values: if pis[i].is_empty() { ptr::null() } else { pis[i].as_ptr() },
+                challenger: s.challenger.map_or(ptr::null(), |c| c.raw as *const ts_challenger),
+                proof_out: outs[i].as_mut_ptr(),
+                cap_words: outs[i].len(),
+                logup: if has_spec { &specs[l] } else { ptr::null() },
+                aux_fn: None,
+                aux_user: ptr::null_mut(),
+                mult: if fills.is_empty() { ptr::null() } else { fills.as_ptr() },
+                n_mult: fills.len() as u32,
+                cap_exposed: 4,
+                exposed_out: exposed[i].as_mut_ptr(),
+                status: -1,
+                n_exposed: 0,
+                n_words: 0,
+                n_missing: 0,
+                first_missing: u64::MAX,
+                proof_blake3: [0; 8],
+                final_state: [0; 34],
+                start_ms: 0.0,
+                wall_ms: 0.0,
+            }
+        })
+        .collect();
+    let cfg = fri.raw();
+    let rc = unsafe {
+        ts_prove_batch_lookup(ctxs.as_ptr(), airs.as_ptr(), raw_lanes.as_ptr(), ctxs.len() as u32, &cfg,
+                              items.as_mut_ptr(), items.len() as u32, gate_ms, 0)
+    };
+    let refused = rc != TS_OK && items.iter().all(|it| it.status == -1);
+    items
+        .iter()
+        .enumerate()
+        .map(|(i, it)| match it.status {
+            TS_OK => Ok(LookupProof {
+                words: outs[i][..it.n_words].to_vec(),
+                exposed: exposed[i][..(it.n_exposed as usize).min(4)].to_vec(),
+            }),
+            status => Err(LookupBatchError {
+                status: if refused { rc } else { status },
+                n_words: it.n_words,
+                n_missing: it.n_missing,
+                first_missing: it.first_missing,
+            }),
         })
         .collect()
 }

@@ -925,6 +925,88 @@ ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_
                                        uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
                                        int64_t* first_violation);
 
+/* ------------------------------------------------------------------ lookup AIRs in batch lanes
+ * ts_prove_batch for AIRs with preprocessed columns, challenge-phase columns or both: the same lanes (one context
+ * and one host thread each, a lane takes its items in index order), the same gate, stamps, digest flag and return
+ * value, and per item the device work of ts_prove_pre_aux.  The key belongs to the LANE (lanes[l] goes with
+ * ctxs[l] and airs[l]; `lanes` may be NULL when no lane's AIR has preprocessed columns), the aux source to the
+ * ITEM, and it may be declarative: a ts_logup_spec the library runs itself on the lane's stream, so that
+ * neither a C host nor a host behind an interpreter lock needs a callback per proof.
+ * Equality: item i's proof words, exposed words and final challenger state are those of ts_prove_pre_aux for the
+ * same context, AIR, key, public values and a clone of the challenger, the trace as it stands after the item's
+ * multiplicity fills, and an aux source that returns what the item's source returns.  Hence TSPF v5 for every
+ * item, whatever the widths: an AIR with neither width gets what ts_prove_pre_aux gives it with a null key and a
+ * null source.
+ *   lane, trace | host_trace, height, width, n_public, public_values, challenger, proof_out, cap_words
+ *                       as in ts_batch_item.  A device trace must be ROW-MAJOR whenever aux_width > 0 or
+ *                       n_mult > 0 (as ts_prove_aux requires).
+ *   logup | aux_fn      the aux source: exactly one of them for an AIR with aux_width > 0, both NULL for
+ *                       aux_width == 0.  `logup`: the library calls the builder of ts_logup_aux_build_pre with
+ *                       (spec, the lane's key_values, the live trace, the challenges); the AIR must have 2
+ *                       challenges and 4 exposed words and the spec's aux width must be the AIR's; a kind-2 term
+ *                       needs the lane's key_values.  `aux_fn`: called on the LANE's thread with the lane's
+ *                       context and aux_user; a non-zero status fails the item with that status.
+ *   n_mult, mult        0 .. 8 multiplicity fills of the resident row-major trace (the device handle's, or the
+ *                       host trace once uploaded), in order, after the upload and before the commit: each is
+ *                       ts_logup_multiplicities with the lane's key_values.
+ *   exposed_out         cap_exposed words, or NULL / 0: the exposed words of a finished proof.
+ * Outputs: status, n_words, proof_blake3, final_state, start_ms, wall_ms as in ts_batch_item; n_exposed (the
+ * AIR's); n_missing / first_missing: those of the first fill that misses (0 / ~0 when none does).
+ * Whole-call refusals (TS_ERR_INVALID before any trace is consumed or any item written): those of ts_prove_batch,
+ * any struct_size other than sizeof(ts_batch_lookup_item) in an item or sizeof(ts_batch_lane) in a lane, and
+ * lanes == NULL while some lane's AIR has preprocessed columns.
+ * Item refusals (TS_ERR_INVALID in the item's status, its trace NOT consumed, the other items still run): those
+ * of ts_prove_batch; both aux sources, or none for an AIR with aux columns, or one for an AIR without; a spec
+ * that does not fit the AIR; a kind-2 term (in `logup` or a fill) on a lane without key_values; n_mult > 8 or
+ * a null `mult`; a column-major device trace where a row-major one is needed; a non-null exposed_out shorter
+ * than the AIR's exposed words; a key that is null for an AIR with preprocessed columns (or given for one
+ * without), or a key or key_values of another width, height or context than the item's trace needs.  A proof
+ * buffer too small is TS_ERR_BUFFER with n_words set, as in ts_prove_batch.
+ * Data errors do not stop a lane: a lookup in no table row (a fill's miss) or a zero denominator reported by the
+ * builder is a statement about the item's data, raised after the kernels finished normally.  The item gets
+ * TS_ERR_INVARIANT with the text ts_logup_multiplicities / ts_logup_aux_build_pre give, its trace is consumed,
+ * and the lane goes on to its next item; so it does after a non-zero callback status.  TS_ERR_HIP, TS_ERR_OOM and
+ * any other TS_ERR_INVARIANT stop the lane, as in ts_prove_batch.
+ * ts_prove_batch and ts_prove_stream keep refusing these AIRs with TS_ERR_UNSUPPORTED. */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(ts_batch_lane) */
+    const ts_pcs_data* key;        /* the lane AIR's committed key, made on the lane's context; NULL iff
+                                      preprocessed_width == 0; never consumed, serves every item of the lane */
+    const ts_matrix* key_values;   /* row-major n x preprocessed_width values on the lane's context, read by
+                                      kind-2 terms of `logup` / `mult`; may be NULL; never consumed */
+} ts_batch_lane;
+typedef struct {
+    uint32_t struct_size;            /* = sizeof(ts_batch_lookup_item): another layout refuses the whole call */
+    uint32_t lane;                   /* < n_lanes */
+    ts_matrix* trace;                /* device trace made on the lane's context (consumed) ... */
+    const uint32_t* host_trace;      /* ... OR canonical row-major host values, height x width */
+    uint64_t height;                 /* of host_trace */
+    uint32_t width;                  /* of host_trace */
+    uint32_t n_public;
+    const uint32_t* public_values;
+    const ts_challenger* challenger; /* NULL = fresh; else cloned, never modified */
+    uint32_t* proof_out;
+    size_t cap_words;
+    const ts_logup_spec* logup;      /* aux source, declarative ... */
+    ts_aux_fn aux_fn;                /* ... OR a callback, run on the lane's thread */
+    void* aux_user;
+    const ts_logup_mult_spec* mult;  /* n_mult fills, in order */
+    uint32_t n_mult;                 /* 0 .. 8 */
+    uint32_t cap_exposed;
+    uint32_t* exposed_out;           /* may be NULL */
+    /* outputs */
+    ts_status status;
+    uint32_t n_exposed;
+    size_t n_words;
+    uint64_t n_missing, first_missing;
+    uint32_t proof_blake3[8];
+    uint32_t final_state[34];
+    double start_ms, wall_ms;
+} ts_batch_lookup_item;
+ts_status ts_prove_batch_lookup(ts_ctx* const* ctxs, const ts_air* const* airs, const ts_batch_lane* lanes,
+                                uint32_t n_lanes, const ts_fri_config* cfg, ts_batch_lookup_item* items,
+                                uint32_t n_items, double gate_ms, uint32_t flags);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

@@ -3,6 +3,6 @@ prover interface over the C-ABI HIP library (include/tapstark.h)."""
 from . import air, airs  # noqa: F401
 from .air import (BaseAir, ExtExpr, LogUp, SymbolicAirBuilder, air_tape, get_log_quotient_degree,  # noqa: F401
                   get_max_constraint_degree, get_symbolic_constraints)
-from .stark import (BatchResult, BfChallenger, Blake3Mmcs, CompiledAir, Context, DeviceMatrix, FriConfig, PcsData, PinnedHostBytes, PreprocessedKey, PinnedHostMatrix,  # noqa: F401
+from .stark import (BatchLookupResult, BatchResult, BfChallenger, Blake3Mmcs, CompiledAir, Context, DeviceMatrix, FriConfig, PcsData, PinnedHostBytes, PreprocessedKey, PinnedHostMatrix,  # noqa: F401
                     Proof, Radix2Dft, StarkConfig, TraceFormat, TwoAdicFriPcs, VerificationError, check_constraints,
-                    default_context, prove, prove_batch, prove_sharded, prove_stream, verify)
+                    default_context, prove, prove_batch, prove_batch_lookup, prove_sharded, prove_stream, verify, verify_pre_aux)

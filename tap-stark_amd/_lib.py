@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "ts_logup_aux_width", "ts_logup_aux_build", "ts_logup_aux_build_pre",
     "ts_logup_multiplicities",
     "ts_prove_pre_aux", "ts_verify_pre_aux", "ts_quotient_chunks_pre_aux", "ts_check_constraints_pre_aux",
+    "ts_prove_batch_lookup",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -138,6 +139,25 @@ class LogupMultSpecC(C.Structure):
 # ``ts_aux_fn``: (user, ctx, trace, challenges, n_challenges, aux_out, exposed_out) -> status
 AUX_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32,
                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint32))
+
+
+class BatchLaneC(C.Structure):
+    """``ts_batch_lane``: what a lane of ``ts_prove_batch_lookup`` owns for all of its items."""
+    _fields_ = [("struct_size", C.c_uint32), ("key", C.c_void_p), ("key_values", C.c_void_p)]
+
+
+class BatchLookupItemC(C.Structure):
+    """``ts_batch_lookup_item``: one statement of ``ts_prove_batch_lookup``, inputs then outputs."""
+    _fields_ = [("struct_size", C.c_uint32), ("lane", C.c_uint32), ("trace", C.c_void_p),
+                ("host_trace", C.c_void_p), ("height", C.c_uint64), ("width", C.c_uint32),
+                ("n_public", C.c_uint32), ("public_values", C.c_void_p), ("challenger", C.c_void_p),
+                ("proof_out", C.c_void_p), ("cap_words", C.c_size_t),
+                ("logup", C.POINTER(LogupSpecC)), ("aux_fn", C.c_void_p), ("aux_user", C.c_void_p),
+                ("mult", C.POINTER(LogupMultSpecC)), ("n_mult", C.c_uint32), ("cap_exposed", C.c_uint32),
+                ("exposed_out", C.c_void_p),
+                ("status", C.c_int), ("n_exposed", C.c_uint32), ("n_words", C.c_size_t),
+                ("n_missing", C.c_uint64), ("first_missing", C.c_uint64), ("proof_blake3", C.c_uint32 * 8),
+                ("final_state", C.c_uint32 * 34), ("start_ms", C.c_double), ("wall_ms", C.c_double)]
 
 _lib = None
 
@@ -333,6 +353,9 @@ def lib() -> C.CDLL:
                                        C.POINTER(C.c_size_t)]
         l.ts_verify_pre_aux.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.c_void_p, u32p, u32p, C.c_size_t, u32p,
                                         C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_int)]
+        l.ts_prove_batch_lookup.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(BatchLaneC),
+                                            C.c_uint32, C.POINTER(FriConfigC), C.POINTER(BatchLookupItemC),
+                                            C.c_uint32, C.c_double, C.c_uint32]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

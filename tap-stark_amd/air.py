@@ -505,16 +505,9 @@ class LogUp:
                                     allow_missing=allow_missing)
 
 
-def logup_multiplicities(trace, table, lookups, weights, out_column: int, negate: int = 1, preprocessed=None,
-                         allow_missing: bool = False):
-    """``ts_logup_multiplicities`` (include/tapstark.h, csrc/logup_mult.hip) with the explicit spec: ``table`` is
-    the table's tuple (a list of terms, as ``LogUp`` takes them), ``lookups`` one tuple per lookup, ``weights`` one
-    term per lookup.  Column ``out_column`` of the resident row-major ``trace`` is overwritten in HBM with, on the
-    lowest table row of each tuple, the field sum of the weights of the lookups that equal it (``p`` minus it with
-    ``negate``), and 0 on the other rows.  ``preprocessed``: the row-major ``DeviceMatrix`` that ``("prep", c)``
-    terms read.  Returns ``(n_missing, first_missing)``: the lookups of non-zero weight found in no table row and the
-    least ``row * len(lookups) + lookup`` among them (``2**64 - 1`` when none); with ``allow_missing`` false a miss
-    raises ``TsError`` (TS_ERR_INVARIANT) instead."""
+def mult_spec_c(table, lookups, weights, out_column: int, negate: int = 1):
+    """The ``ts_logup_mult_spec`` of the arguments ``logup_multiplicities`` takes (``LogUp.mult_spec`` makes them),
+    and the ctypes arrays it points into (keep the tuple alive while the spec is in use)."""
     import ctypes as C
     from . import _lib
     T = _lib.LogupTermC
@@ -528,6 +521,21 @@ def logup_multiplicities(trace, table, lookups, weights, out_column: int, negate
     w_arr = (T * len(weights))(*[T(k, v) for k, v in weights])
     spec = _lib.LogupMultSpecC(C.sizeof(_lib.LogupMultSpecC), len(table), t_arr, len(lookups), l_arr, w_arr,
                                int(out_column), int(negate))
+    return spec, (t_arr, l_arr, w_arr)
+
+
+def logup_multiplicities(trace, table, lookups, weights, out_column: int, negate: int = 1, preprocessed=None,
+                         allow_missing: bool = False):
+    """``ts_logup_multiplicities`` (include/tapstark.h, csrc/logup_mult.hip) with the explicit spec: ``table`` is
+    the table's tuple (a list of terms, as ``LogUp`` takes them), ``lookups`` one tuple per lookup, ``weights`` one
+    term per lookup.  Column ``out_column`` of the resident row-major ``trace`` is overwritten in HBM with, on the
+    lowest table row of each tuple, the field sum of the weights of the lookups that equal it (``p`` minus it with
+    ``negate``), and 0 on the other rows.  ``preprocessed``: the row-major ``DeviceMatrix`` that ``("prep", c)``
+    terms read.  Returns ``(n_missing, first_missing)``: the lookups of non-zero weight found in no table row and the
+    least ``row * len(lookups) + lookup`` among them (``2**64 - 1`` when none); with ``allow_missing`` false a miss
+    raises ``TsError`` (TS_ERR_INVARIANT) instead."""
+    import ctypes as C
+    spec, keep = mult_spec_c(table, lookups, weights, out_column, negate)
     ctx = trace.ctx
     n_missing, first = C.c_uint64(0), C.c_uint64(0)
     ctx.check(ctx._l.ts_logup_multiplicities(ctx.h, C.byref(spec), preprocessed.h if preprocessed is not None else None,

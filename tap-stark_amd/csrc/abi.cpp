@@ -234,6 +234,111 @@ ts::DeviceMatrix lane_trace(ts_matrix* trace, ts_ctx* ctx, const ts::AirProgram&
     return take_trace(trace);
 }
 
+// ---- the lane body of ts_prove_batch and ts_prove_batch_lookup: ONE owner of the per-item argument checks, the
+// upload on the lane's stream, the gate, the proof copy, the digest and the state export.  `Item` has
+// ts_batch_item's fields under the same names; a call supplies what differs through BatchCall's three hooks.
+struct ItemOutcome {
+    bool lane_goes_on = false;  // the failure says something about the item's data, not about the context
+    ts_status status = TS_OK;   // non-zero: replaces the item's status (an aux callback's own status)
+};
+template <class Item>
+struct BatchCall {
+    const char* name = "";  // the entry point, in texts that name it
+    const char* what = "";  // the prefix of the per-item refusals
+    ts_ctx* const* ctxs = nullptr;
+    const ts_air* const* airs = nullptr;
+    // the item's outputs beyond ts_batch_item's, before anything runs
+    void reset(Item&) const {}
+    // refusals that depend on the lane's AIR alone: before any other check of the item
+    void refuse(uint32_t) const {}
+    // refusals that need the trace's shape: after the shared checks, before the trace is taken or uploaded
+    // (`trace`: the device handle's matrix, null for a host trace)
+    void admit(uint32_t, Item&, const ts::AirProgram&, uint64_t, const ts::DeviceMatrix*) const {}
+};
+
+template <class Call, class Item>
+ts_status run_batch(const Call& call, uint32_t n_lanes, const ts::FriConfig& fri, Item* items, uint32_t n_items,
+                    double gate_ms, uint32_t flags) {
+    for (uint32_t i = 0; i < n_items; i++) {
+        Item& it = items[i];
+        it.status = -1;
+        it.n_words = 0;
+        it.start_ms = it.wall_ms = 0;
+        memset(it.proof_blake3, 0, sizeof it.proof_blake3);
+        memset(it.final_state, 0, sizeof it.final_state);
+        call.reset(it);
+    }
+    // items no lane can take, or whose trace handle an earlier item already names (two lane threads would
+    // race for it), fail here
+    std::vector<std::pair<const ts_matrix*, uint32_t>> handles;
+    for (uint32_t i = 0; i < n_items; i++) {
+        if (items[i].lane >= n_lanes) items[i].status = TS_ERR_INVALID;
+        else if (items[i].trace) handles.emplace_back(items[i].trace, i);
+    }
+    std::sort(handles.begin(), handles.end());
+    for (size_t k = 1; k < handles.size(); k++)
+        if (handles[k].first == handles[k - 1].first) items[handles[k].second].status = TS_ERR_INVALID;
+
+    const std::string what = call.what;
+    StartGate gate(gate_ms);
+    auto lane_main = [&](uint32_t l) {
+        ts_ctx* ctx = call.ctxs[l];
+        const ts_air* air = call.airs[l];
+        std::unique_ptr<ts::TwoAdicFriPcs> pcs;
+        for (uint32_t i = 0; i < n_items; i++) {
+            Item& it = items[i];
+            if (it.lane != l || it.status != -1) continue;
+            ItemOutcome outcome;
+            it.status = guard(ctx, [&] {
+                call.refuse(l);
+                const ts::AirProgram& prog = ready_prog(air);
+                TS_REQUIRE((it.trace != nullptr) != (it.host_trace != nullptr), ts::TS_ERR_INVALID,
+                           what + ": exactly one of trace / host_trace must be set");
+                TS_REQUIRE(it.proof_out, ts::TS_ERR_INVALID, what + ": null proof_out");
+                TS_REQUIRE(it.n_public == prog.n_public, ts::TS_ERR_INVALID,
+                           what + ": n_public differs from the lane's AIR");
+                const std::vector<uint32_t> pis = public_inputs(it.public_values, it.n_public);
+                if (!it.trace) {
+                    TS_REQUIRE(it.height >= 1 && (it.height & (it.height - 1)) == 0 && it.height <= (1ull << 27),
+                               ts::TS_ERR_INVALID, what + ": host trace height must be a power of two <= 2^27");
+                    TS_REQUIRE(it.width == prog.width, ts::TS_ERR_INVALID,
+                               what + ": host trace width differs from the lane's AIR");
+                }
+                call.admit(l, it, prog, it.trace ? it.trace->m.height : it.height, it.trace ? &it.trace->m : nullptr);
+                ts::DeviceMatrix trace;
+                if (it.trace) trace = lane_trace(it.trace, ctx, prog);
+                ts::BfChallenger chal = it.challenger ? it.challenger->c : ts::BfChallenger(0, true);
+                if (!pcs) pcs = std::make_unique<ts::TwoAdicFriPcs>(ctx->ctx, fri);
+                const double t0 = gate.enter();
+                if (!it.trace) {  // H2D on the lane's stream: ordered before the proof's kernels, no host wait here
+                    trace.buf = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)it.height * it.width);
+                    trace.height = it.height;
+                    trace.width = it.width;
+                    trace.layout = ts::DeviceMatrix::ROW_MAJOR;
+                    TS_HIP(hipMemcpyAsync(trace.buf.p, it.host_trace, (size_t)it.height * it.width * 4,
+                                          hipMemcpyHostToDevice, ctx->ctx.stream));
+                }
+                std::vector<uint32_t> proof = call.prove(l, it, *pcs, prog, chal, std::move(trace), pis, outcome);
+                it.start_ms = t0;
+                it.wall_ms = gate.now_ms() - t0;
+                chal.export_state(it.final_state);
+                copy_proof(proof, it.proof_out, it.cap_words, &it.n_words);
+                if (flags & TS_BATCH_DIGEST)
+                    ts::b3::hash_stream([&](uint64_t k) { return proof[k]; }, proof.size(), it.proof_blake3);
+            });
+            if (outcome.status != TS_OK) it.status = outcome.status;
+            // a device fault leaves the lane's context in doubt: its later items stay unattempted
+            if (!outcome.lane_goes_on &&
+                (it.status == TS_ERR_HIP || it.status == TS_ERR_OOM || it.status == TS_ERR_INVARIANT))
+                break;
+        }
+    };
+    if (run_lanes(n_lanes, lane_main) != TS_OK) return TS_ERR_OOM;
+    for (uint32_t i = 0; i < n_items; i++)
+        if (items[i].status != TS_OK) return items[i].status;
+    return TS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1226,78 +1331,19 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
     if ((!items && n_items) || !check_lanes(ctxs, airs, n_lanes, cfg, fri)) return TS_ERR_INVALID;
     for (uint32_t i = 0; i < n_items; i++)
         if (items[i].struct_size != sizeof(ts_batch_item)) return TS_ERR_INVALID;
-    for (uint32_t i = 0; i < n_items; i++) {
-        ts_batch_item& it = items[i];
-        it.status = -1;
-        it.n_words = 0;
-        it.start_ms = it.wall_ms = 0;
-        memset(it.proof_blake3, 0, sizeof it.proof_blake3);
-        memset(it.final_state, 0, sizeof it.final_state);
-    }
-    // items no lane can take, or whose trace handle an earlier item already names (two lane threads would
-    // race for it), fail here
-    std::vector<std::pair<const ts_matrix*, uint32_t>> handles;
-    for (uint32_t i = 0; i < n_items; i++) {
-        if (items[i].lane >= n_lanes) items[i].status = TS_ERR_INVALID;
-        else if (items[i].trace) handles.emplace_back(items[i].trace, i);
-    }
-    std::sort(handles.begin(), handles.end());
-    for (size_t k = 1; k < handles.size(); k++)
-        if (handles[k].first == handles[k - 1].first) items[handles[k].second].status = TS_ERR_INVALID;
-
-    StartGate gate(gate_ms);
-    auto lane_main = [&](uint32_t l) {
-        ts_ctx* ctx = ctxs[l];
-        const ts_air* air = airs[l];
-        std::unique_ptr<ts::TwoAdicFriPcs> pcs;
-        for (uint32_t i = 0; i < n_items; i++) {
-            ts_batch_item& it = items[i];
-            if (it.lane != l || it.status != -1) continue;
-            it.status = guard(ctx, [&] {
-                no_preprocessed(air, "ts_prove_batch");
-                const ts::AirProgram& prog = ready_prog(air);
-                TS_REQUIRE((it.trace != nullptr) != (it.host_trace != nullptr), ts::TS_ERR_INVALID,
-                           "prove_batch: exactly one of trace / host_trace must be set");
-                TS_REQUIRE(it.proof_out, ts::TS_ERR_INVALID, "prove_batch: null proof_out");
-                TS_REQUIRE(it.n_public == prog.n_public, ts::TS_ERR_INVALID,
-                           "prove_batch: n_public differs from the lane's AIR");
-                const std::vector<uint32_t> pis = public_inputs(it.public_values, it.n_public);
-                ts::DeviceMatrix trace;
-                if (it.trace) {
-                    trace = lane_trace(it.trace, ctx, prog);
-                } else {
-                    TS_REQUIRE(it.height >= 1 && (it.height & (it.height - 1)) == 0 && it.height <= (1ull << 27),
-                               ts::TS_ERR_INVALID, "prove_batch: host trace height must be a power of two <= 2^27");
-                    TS_REQUIRE(it.width == prog.width, ts::TS_ERR_INVALID,
-                               "prove_batch: host trace width differs from the lane's AIR");
-                }
-                ts::BfChallenger chal = it.challenger ? it.challenger->c : ts::BfChallenger(0, true);
-                if (!pcs) pcs = std::make_unique<ts::TwoAdicFriPcs>(ctx->ctx, fri);
-                const double t0 = gate.enter();
-                if (!it.trace) {  // H2D on the lane's stream: ordered before the proof's kernels, no host wait here
-                    trace.buf = ts::DevBuf<uint32_t>(&ctx->ctx, (size_t)it.height * it.width);
-                    trace.height = it.height;
-                    trace.width = it.width;
-                    trace.layout = ts::DeviceMatrix::ROW_MAJOR;
-                    TS_HIP(hipMemcpyAsync(trace.buf.p, it.host_trace, (size_t)it.height * it.width * 4,
-                                          hipMemcpyHostToDevice, ctx->ctx.stream));
-                }
-                std::vector<uint32_t> proof = ts::prove(*pcs, prog, chal, std::move(trace), pis);
-                it.start_ms = t0;
-                it.wall_ms = gate.now_ms() - t0;
-                chal.export_state(it.final_state);
-                copy_proof(proof, it.proof_out, it.cap_words, &it.n_words);
-                if (flags & TS_BATCH_DIGEST)
-                    ts::b3::hash_stream([&](uint64_t k) { return proof[k]; }, proof.size(), it.proof_blake3);
-            });
-            // a device fault leaves the lane's context in doubt: its later items stay unattempted
-            if (it.status == TS_ERR_HIP || it.status == TS_ERR_OOM || it.status == TS_ERR_INVARIANT) break;
+    struct Plain : BatchCall<ts_batch_item> {
+        void refuse(uint32_t l) const { no_preprocessed(airs[l], name); }
+        std::vector<uint32_t> prove(uint32_t, ts_batch_item&, ts::TwoAdicFriPcs& pcs, const ts::AirProgram& prog,
+                                    ts::BfChallenger& chal, ts::DeviceMatrix trace, const std::vector<uint32_t>& pis,
+                                    ItemOutcome&) const {
+            return ts::prove(pcs, prog, chal, std::move(trace), pis);
         }
-    };
-    if (run_lanes(n_lanes, lane_main) != TS_OK) return TS_ERR_OOM;
-    for (uint32_t i = 0; i < n_items; i++)
-        if (items[i].status != TS_OK) return items[i].status;
-    return TS_OK;
+    } call;
+    call.name = "ts_prove_batch";
+    call.what = "prove_batch";
+    call.ctxs = ctxs;
+    call.airs = airs;
+    return run_batch(call, n_lanes, fri, items, n_items, gate_ms, flags);
 }
 
 static ts::Comm wrap_comm(const ts_comm& cb) {
@@ -1576,6 +1622,33 @@ namespace {
 struct AuxCallbackFailed {
     ts_status status;
 };
+
+// The aux source around a host's ts_aux_fn, for every call that takes one (`call` names it in the texts).  The
+// callback sees the live trace as a ts_matrix of its own: borrowed for the call, handed back after.  A non-zero
+// status is left in `cb_status` and leaves as AuxCallbackFailed; callback_failure() is the ts::Error for it.
+ts::AuxSource callback_aux_source(ts_ctx* ctx, const ts::AirProgram& p, ts_aux_fn aux_fn, void* user,
+                                  ts_status& cb_status, const char* call) {
+    return [ctx, &p, aux_fn, user, &cb_status, call](const ts::DeviceMatrix& live, const uint32_t* challenges,
+                                                     uint32_t* exposed) {
+        ts_matrix view;
+        view.m = std::move(const_cast<ts::DeviceMatrix&>(live));
+        ts_matrix* out = nullptr;
+        const ts_status rc = aux_fn(user, ctx, &view, challenges, p.n_challenges, &out, exposed);
+        const_cast<ts::DeviceMatrix&>(live) = std::move(view.m);
+        std::unique_ptr<ts_matrix> owned(out);
+        if (rc != TS_OK) {
+            cb_status = rc;
+            throw AuxCallbackFailed{rc};
+        }
+        TS_REQUIRE(owned, ts::TS_ERR_INVALID, std::string(call) + ": the aux callback returned no matrix");
+        return std::move(owned->m);
+    };
+}
+ts::Error callback_failure(ts_ctx* ctx, ts_status cb_status, const char* call) {
+    const std::string inner = ctx->ctx.last_error;
+    return ts::Error(ts::TS_ERR_INVALID, std::string(call) + ": the aux callback (aux_fn) returned status " +
+                                             std::to_string((int)cb_status) + (inner.empty() ? "" : ": " + inner));
+}
 }  // namespace
 
 ts_status ts_prove_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
@@ -1599,29 +1672,12 @@ ts_status ts_prove_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
                    "trace was made on another context");
         ts::DeviceMatrix m = take_trace(trace);
         ts::AuxSource source;
-        if (aux_fn)
-            source = [&](const ts::DeviceMatrix& live, const uint32_t* challenges, uint32_t* exposed) {
-                // the callback sees the live trace as a ts_matrix of its own: borrowed for the call, handed back after
-                ts_matrix view;
-                view.m = std::move(const_cast<ts::DeviceMatrix&>(live));
-                ts_matrix* out = nullptr;
-                const ts_status rc = aux_fn(user, ctx, &view, challenges, p.n_challenges, &out, exposed);
-                const_cast<ts::DeviceMatrix&>(live) = std::move(view.m);
-                std::unique_ptr<ts_matrix> owned(out);
-                if (rc != TS_OK) {
-                    cb_status = rc;
-                    throw AuxCallbackFailed{rc};
-                }
-                TS_REQUIRE(owned, ts::TS_ERR_INVALID, "ts_prove_aux: the aux callback returned no matrix");
-                return std::move(owned->m);
-            };
+        if (aux_fn) source = callback_aux_source(ctx, p, aux_fn, user, cb_status, "ts_prove_aux");
         ts::StageTimer t(&ctx->ctx, "prove");
         try {
             copy_proof(ts::prove_aux(pcs, p, chal->c, std::move(m), pis, source), proof_out, cap_words, n_words_out);
         } catch (const AuxCallbackFailed&) {
-            const std::string inner = ctx->ctx.last_error;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_prove_aux: the aux callback (aux_fn) returned status " +
-                                                    std::to_string((int)cb_status) + (inner.empty() ? "" : ": " + inner));
+            throw callback_failure(ctx, cb_status, "ts_prove_aux");
         }
     });
     return cb_status != TS_OK ? cb_status : st;
@@ -1688,6 +1744,25 @@ ts::LogupSpec load_logup_spec(const ts_logup_spec* spec) {
     }
     return s;
 }
+
+ts::LogupMultSpec load_mult_spec(const ts_logup_mult_spec* spec) {
+    TS_REQUIRE(spec->struct_size == sizeof(ts_logup_mult_spec), ts::TS_ERR_INVALID,
+               "logup multiplicities: bad struct_size");
+    TS_REQUIRE(spec->n_values >= 1 && spec->n_values <= ts::LOGUP_MAX_VALUES && spec->table, ts::TS_ERR_INVALID,
+               "logup multiplicities: between 1 and 8 values");
+    TS_REQUIRE(spec->n_lookups >= 1 && spec->n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && spec->lookups && spec->weights,
+               ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookups");
+    ts::LogupMultSpec s;
+    auto load = [](const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
+        for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
+    };
+    load(spec->table, spec->n_values, s.table);
+    load(spec->lookups, (size_t)spec->n_lookups * spec->n_values, s.lookups);
+    load(spec->weights, spec->n_lookups, s.weights);
+    s.out_column = spec->out_column;
+    s.negate = spec->negate;
+    return s;
+}
 }  // namespace
 
 ts_status ts_logup_aux_width(const ts_logup_spec* spec, uint32_t* aux_width) {
@@ -1740,29 +1815,11 @@ ts_status ts_logup_multiplicities(ts_ctx* ctx, const ts_logup_mult_spec* spec, c
     if (n_missing) *n_missing = 0;
     if (first_missing) *first_missing = ~0ull;
     return guard(ctx, [&] {
-        TS_REQUIRE(spec->struct_size == sizeof(ts_logup_mult_spec), ts::TS_ERR_INVALID,
-                   "logup multiplicities: bad struct_size");
-        TS_REQUIRE(spec->n_values >= 1 && spec->n_values <= ts::LOGUP_MAX_VALUES && spec->table, ts::TS_ERR_INVALID,
-                   "logup multiplicities: between 1 and 8 values");
-        TS_REQUIRE(spec->n_lookups >= 1 && spec->n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && spec->lookups && spec->weights,
-                   ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookups");
-        ts::LogupMultSpec s;
-        auto load = [](const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
-            for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
-        };
-        load(spec->table, spec->n_values, s.table);
-        load(spec->lookups, (size_t)spec->n_lookups * spec->n_values, s.lookups);
-        load(spec->weights, spec->n_lookups, s.weights);
-        s.out_column = spec->out_column;
-        s.negate = spec->negate;
+        const ts::LogupMultSpec s = load_mult_spec(spec);
         const ts::LogupMultResult r = ts::logup_multiplicities(ctx->ctx, s, trace->m, preprocessed ? &preprocessed->m : nullptr);
         if (n_missing) *n_missing = r.n_missing;
         if (first_missing) *first_missing = r.first_missing;
-        if (!n_missing && r.n_missing)
-            throw ts::Error(ts::TS_ERR_INVARIANT,
-                            "logup multiplicities: the tuple of row " + std::to_string(r.first_missing / spec->n_lookups) +
-                                ", lookup " + std::to_string(r.first_missing % spec->n_lookups) + " is in no table row (" +
-                                std::to_string(r.n_missing) + " such lookups)");
+        if (!n_missing && r.n_missing) throw ts::Error(ts::TS_ERR_INVARIANT, ts::logup_miss_text(r, spec->n_lookups));
     });
 }
 
@@ -1870,30 +1927,13 @@ ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* 
         if (k) ts::check_preprocessed_key(*k, p, trace->m.height << pcs.fri().log_blowup);
         ts::DeviceMatrix m = take_trace(trace);
         ts::AuxSource source;
-        if (aux_fn)
-            source = [&](const ts::DeviceMatrix& live, const uint32_t* challenges, uint32_t* exposed) {
-                // as ts_prove_aux: the live trace borrowed as a ts_matrix for the call, handed back after
-                ts_matrix view;
-                view.m = std::move(const_cast<ts::DeviceMatrix&>(live));
-                ts_matrix* out = nullptr;
-                const ts_status rc = aux_fn(user, ctx, &view, challenges, p.n_challenges, &out, exposed);
-                const_cast<ts::DeviceMatrix&>(live) = std::move(view.m);
-                std::unique_ptr<ts_matrix> owned(out);
-                if (rc != TS_OK) {
-                    cb_status = rc;
-                    throw AuxCallbackFailed{rc};
-                }
-                TS_REQUIRE(owned, ts::TS_ERR_INVALID, "ts_prove_pre_aux: the aux callback returned no matrix");
-                return std::move(owned->m);
-            };
+        if (aux_fn) source = callback_aux_source(ctx, p, aux_fn, user, cb_status, "ts_prove_pre_aux");
         ts::StageTimer t(&ctx->ctx, "prove");
         try {
             copy_proof(ts::prove_pre_aux(pcs, p, chal->c, std::move(m), pis, k, source), proof_out, cap_words,
                        n_words_out);
         } catch (const AuxCallbackFailed&) {
-            const std::string inner = ctx->ctx.last_error;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_prove_pre_aux: the aux callback (aux_fn) returned status " +
-                                                    std::to_string((int)cb_status) + (inner.empty() ? "" : ": " + inner));
+            throw callback_failure(ctx, cb_status, "ts_prove_pre_aux");
         }
     });
     return cb_status != TS_OK ? cb_status : st;
@@ -1930,6 +1970,141 @@ ts_status ts_verify_pre_aux(const ts_fri_config* cfg, const ts_air* air, ts_chal
         *verdict = ts::verify_pre_aux(f, p, chal->c, preprocessed_root, proof, n_words, pis, exposed);
         if (*verdict == 0 && !exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
     });
+}
+
+// ------------------------------------------------------------------ prove_batch_lookup
+// ts_prove_batch's lanes (run_batch above) for AIRs with a key, aux columns or both: per item the device work of
+// ts_prove_pre_aux, with the key owned by the lane and the aux source by the item -- a ts_logup_spec the lane runs
+// itself, or a callback on the lane's thread.  What a lane holds while a proof is in flight: DESIGN.md section 4, "Lookup AIRs in batch lanes".
+namespace {
+bool reads_table(const std::vector<ts::LogupTerm>& terms) {
+    return std::any_of(terms.begin(), terms.end(), [](const ts::LogupTerm& t) { return t.kind == 2; });
+}
+
+struct LookupCall : BatchCall<ts_batch_lookup_item> {
+    const ts_batch_lane* lanes = nullptr;
+    ts::FriConfig fri;
+    // what admit() parsed for the item its lane is on, for prove()
+    struct Parsed {
+        bool has_spec = false;
+        ts::LogupSpec spec;
+        std::vector<ts::LogupMultSpec> fills;
+    };
+    mutable std::vector<Parsed> parsed;  // one per lane, touched by that lane's thread only
+
+    const ts_matrix* table(uint32_t l) const { return lanes ? lanes[l].key_values : nullptr; }
+
+    void reset(ts_batch_lookup_item& it) const {
+        it.n_exposed = 0;
+        it.n_missing = 0;
+        it.first_missing = ~0ull;
+    }
+
+    void admit(uint32_t l, ts_batch_lookup_item& it, const ts::AirProgram& prog, uint64_t height,
+               const ts::DeviceMatrix* trace) const {
+        ts_ctx* ctx = ctxs[l];
+        const std::string w = what;
+        const ts::PcsData* k = preprocessed_key_any(ctx, airs[l], lanes ? lanes[l].key : nullptr, name);
+        if (k) ts::check_preprocessed_key(*k, prog, height << fri.log_blowup);
+        const ts_matrix* kv = table(l);
+        if (kv)
+            TS_REQUIRE(kv->m.buf.p && kv->m.layout == ts::DeviceMatrix::ROW_MAJOR && kv->m.buf.ctx == &ctx->ctx &&
+                           kv->m.width == prog.preprocessed_width && kv->m.height == height,
+                       ts::TS_ERR_INVALID, w + ": key_values must be on the lane's context, row-major, of the AIR's "
+                                               "preprocessed width and the trace's height");
+        const uint32_t aw = prog.aux_width;
+        if (aw)
+            TS_REQUIRE((it.logup != nullptr) != (it.aux_fn != nullptr), ts::TS_ERR_INVALID,
+                       w + ": exactly one of logup / aux_fn must be set for an AIR with aux columns");
+        else
+            TS_REQUIRE(!it.logup && !it.aux_fn, ts::TS_ERR_INVALID,
+                       w + ": an aux source was given for an AIR without aux columns");
+        Parsed& ps = parsed[l];
+        ps = Parsed{};
+        if (it.logup) {
+            ps.spec = load_logup_spec(it.logup);
+            ps.has_spec = true;
+            TS_REQUIRE(prog.n_challenges == 2 && prog.n_exposed == 4 && ts::logup_aux_width(ps.spec, 2) == aw,
+                       ts::TS_ERR_INVALID, w + ": a logup spec needs an AIR with 2 challenges, 4 exposed words and "
+                                               "the spec's aux width");
+            for (const ts::LogupInteraction& in : ps.spec.interactions)
+                TS_REQUIRE(kv || !(in.multiplicity.kind == 2 || reads_table(in.values)), ts::TS_ERR_INVALID,
+                           w + ": the logup spec reads the preprocessed table, the lane has no key_values");
+        }
+        TS_REQUIRE(it.n_mult <= 8 && (it.n_mult == 0 || it.mult), ts::TS_ERR_INVALID,
+                   w + ": at most 8 multiplicity fills, and n_mult of them in mult");
+        for (uint32_t q = 0; q < it.n_mult; q++) {
+            ps.fills.push_back(load_mult_spec(&it.mult[q]));
+            const ts::LogupMultSpec& f = ps.fills.back();
+            TS_REQUIRE(kv || !(reads_table(f.table) || reads_table(f.lookups) || reads_table(f.weights)),
+                       ts::TS_ERR_INVALID, w + ": a multiplicity fill reads the preprocessed table, the lane has no key_values");
+        }
+        if (trace && (aw || it.n_mult))
+            TS_REQUIRE(trace->layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
+                       w + ": the device trace must be row-major (the aux source and the fills read its rows)");
+        TS_REQUIRE(!it.exposed_out || it.cap_exposed >= prog.n_exposed, ts::TS_ERR_INVALID,
+                   w + ": exposed_out is shorter than the AIR's exposed words");
+        it.n_exposed = prog.n_exposed;
+    }
+
+    std::vector<uint32_t> prove(uint32_t l, ts_batch_lookup_item& it, ts::TwoAdicFriPcs& pcs, const ts::AirProgram& prog,
+                                ts::BfChallenger& chal, ts::DeviceMatrix trace, const std::vector<uint32_t>& pis,
+                                ItemOutcome& outcome) const {
+        ts_ctx* ctx = ctxs[l];
+        Parsed& ps = parsed[l];
+        const ts::PcsData* key = lanes && lanes[l].key ? lanes[l].key->d.get() : nullptr;
+        const ts::DeviceMatrix* tab = table(l) ? &table(l)->m : nullptr;
+        ts_status cb_status = TS_OK;
+        ts::AuxSource inner;
+        if (ps.has_spec) inner = ts::logup_aux_source(ctx->ctx, std::move(ps.spec), tab);
+        else if (it.aux_fn) inner = callback_aux_source(ctx, prog, it.aux_fn, it.aux_user, cb_status, name);
+        // the exposed words as the source hands them over: the caller's copy, made once the proof stands
+        std::vector<uint32_t> exposed;
+        ts::AuxSource source;
+        if (inner)
+            source = [&](const ts::DeviceMatrix& live, const uint32_t* challenges, uint32_t* exposed_out) {
+                ts::DeviceMatrix aux = inner(live, challenges, exposed_out);
+                exposed.assign(exposed_out, exposed_out + prog.n_exposed);
+                return aux;
+            };
+        ts::LogupMultResult miss{0, ~0ull};
+        std::vector<uint32_t> proof;
+        try {
+            proof = ts::prove_lookup(pcs, prog, chal, std::move(trace), pis, key, source, ps.fills, tab, &miss);
+        } catch (const ts::LookupDataError&) {
+            it.n_missing = miss.n_missing;
+            it.first_missing = miss.first_missing;
+            outcome.lane_goes_on = true;
+            throw;
+        } catch (const AuxCallbackFailed&) {
+            outcome.lane_goes_on = true;
+            outcome.status = cb_status;
+            throw callback_failure(ctx, cb_status, name);
+        }
+        if (it.exposed_out && !exposed.empty()) memcpy(it.exposed_out, exposed.data(), exposed.size() * 4);
+        return proof;
+    }
+};
+}  // namespace
+
+ts_status ts_prove_batch_lookup(ts_ctx* const* ctxs, const ts_air* const* airs, const ts_batch_lane* lanes,
+                                uint32_t n_lanes, const ts_fri_config* cfg, ts_batch_lookup_item* items,
+                                uint32_t n_items, double gate_ms, uint32_t flags) {
+    // whole-call refusals first: nothing is consumed or written before these pass
+    LookupCall call;
+    if ((!items && n_items) || !check_lanes(ctxs, airs, n_lanes, cfg, call.fri)) return TS_ERR_INVALID;
+    for (uint32_t i = 0; i < n_items; i++)
+        if (items[i].struct_size != sizeof(ts_batch_lookup_item)) return TS_ERR_INVALID;
+    for (uint32_t l = 0; l < n_lanes; l++)
+        if (lanes ? lanes[l].struct_size != sizeof(ts_batch_lane) : airs[l]->a.prog().preprocessed_width != 0)
+            return TS_ERR_INVALID;
+    call.name = "ts_prove_batch_lookup";
+    call.what = "prove_batch_lookup";
+    call.ctxs = ctxs;
+    call.airs = airs;
+    call.lanes = lanes;
+    call.parsed.resize(n_lanes);
+    return run_batch(call, n_lanes, call.fri, items, n_items, gate_ms, flags);
 }
 
 }  // extern "C"

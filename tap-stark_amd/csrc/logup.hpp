@@ -57,4 +57,24 @@ struct LogupMultResult {
 LogupMultResult logup_multiplicities(Context& ctx, const LogupMultSpec& spec, DeviceMatrix& trace,
                                      const DeviceMatrix* table);
 
+// ---- a lookup proof inside a batch lane (prover.cpp): no launch of its own
+// What a lookup argument says about an item's DATA, raised after the kernels finished normally: a zero denominator
+// reported by the builder, a lookup found in no table row.  The context is sound, so a lane goes on after one.
+struct LookupDataError : Error {
+    using Error::Error;
+};
+// the text of a miss, as ts_logup_multiplicities reports it
+std::string logup_miss_text(const LogupMultResult& r, uint32_t n_lookups);
+// The aux source that runs `spec` on the live trace: logup_aux_build with takes_table and `table` (the lane's
+// row-major table values; may be null for a spec without kind-2 terms; must outlive the source).  The builder's
+// zero-denominator report leaves as a LookupDataError.
+AuxSource logup_aux_source(Context& ctx, LogupSpec spec, const DeviceMatrix* table);
+// prove_pre_aux of the trace as it stands after `fills`: each is logup_multiplicities on the row-major trace with
+// `table`, in order, before the commit.  A fill that misses throws LookupDataError (logup_miss_text) after *miss
+// received its counts; *miss is {0, ~0} otherwise.
+std::vector<uint32_t> prove_lookup(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                   DeviceMatrix trace, const std::vector<uint32_t>& public_values, const PcsData* key,
+                                   const AuxSource& aux_source, const std::vector<LogupMultSpec>& fills,
+                                   const DeviceMatrix* table, LogupMultResult* miss);
+
 }  // namespace ts

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 
+#include "logup.hpp"
 #include "prover_internal.hpp"
 
 namespace ts {
@@ -737,6 +738,43 @@ std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, B
                                     DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                                     const PcsData* preprocessed, const AuxSource& aux_source) {
     return prove_challenge_phase(pcs, air, challenger, std::move(trace), public_values, aux_source, preprocessed, 5);
+}
+
+// ------------------------------------------------------------------ a lookup proof inside a batch lane
+// prove_pre_aux with its two lookup steps run by the library on the lane's stream instead of by the host: the
+// multiplicity fills before the commit, the LogUp builder as the aux source.  Same launches in the same order as
+// the solo calls, so the proof is theirs word for word.
+std::string logup_miss_text(const LogupMultResult& r, uint32_t n_lookups) {
+    return "logup multiplicities: the tuple of row " + std::to_string(r.first_missing / n_lookups) + ", lookup " +
+           std::to_string(r.first_missing % n_lookups) + " is in no table row (" + std::to_string(r.n_missing) +
+           " such lookups)";
+}
+
+AuxSource logup_aux_source(Context& ctx, LogupSpec spec, const DeviceMatrix* table) {
+    return [&ctx, spec = std::move(spec), table](const DeviceMatrix& live, const uint32_t* challenges, uint32_t* exposed) {
+        try {
+            return logup_aux_build(ctx, spec, live, challenges, exposed, table, /*takes_table=*/true);
+        } catch (const Error& e) {
+            // the builder's one invariant: a zero denominator, read back after its kernels finished
+            if (e.code == TS_ERR_INVARIANT) throw LookupDataError(e.code, e.what());
+            throw;
+        }
+    };
+}
+
+std::vector<uint32_t> prove_lookup(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                   DeviceMatrix trace, const std::vector<uint32_t>& public_values, const PcsData* key,
+                                   const AuxSource& aux_source, const std::vector<LogupMultSpec>& fills,
+                                   const DeviceMatrix* table, LogupMultResult* miss) {
+    *miss = LogupMultResult{0, ~0ull};
+    for (const LogupMultSpec& f : fills) {
+        const LogupMultResult r = logup_multiplicities(pcs.ctx(), f, trace, table);
+        if (r.n_missing) {
+            *miss = r;
+            throw LookupDataError(TS_ERR_INVARIANT, logup_miss_text(r, (uint32_t)f.weights.size()));
+        }
+    }
+    return prove_pre_aux(pcs, air, challenger, std::move(trace), public_values, key, aux_source);
 }
 
 }  // namespace ts

@@ -1277,6 +1277,150 @@ def prove_batch(lanes, traces, lane_of, public_values=None, challengers=None, ga
     return res
 
 
+@dataclass
+class BatchLookupResult(BatchResult):
+    """``BatchResult`` of ``prove_batch_lookup``: also ``exposed[i]`` (the exposed words of item i's proof, None
+    unless ``status[i]`` is 0) and ``n_missing[i]`` / ``first_missing[i]`` (those of the item's first multiplicity
+    fill that missed; 0 and ``2**64 - 1`` when none did)."""
+    exposed: list = field(default_factory=list)
+    n_missing: np.ndarray | None = None
+    first_missing: np.ndarray | None = None
+
+
+def _per_lane(value, n_lanes: int, what: str) -> list:
+    if value is None:
+        return [None] * n_lanes
+    value = list(value)
+    if len(value) != n_lanes:
+        raise ValueError(f"prove_batch_lookup: {len(value)} {what} for {n_lanes} lanes")
+    return value
+
+
+def prove_batch_lookup(lanes, traces, lane_of, public_values=None, challengers=None, keys=None, logups=None,
+                       fills=None, gate_ms: float = 0.0, digests: bool = False, check: bool = True,
+                       _struct_size: int | None = None, _cap_words=None, _edit_items=None) -> BatchLookupResult:
+    """``ts_prove_batch_lookup``: ``prove_batch`` for AIRs with preprocessed columns, challenge-phase columns or
+    both.  Every proof is the TSPF v5 proof ``prove(..., preprocessed=key, aux=source)`` gives on the lane's context.
+
+    ``lanes``, ``traces``, ``lane_of``, ``public_values``, ``challengers``, ``gate_ms``, ``digests``, ``check``: as
+    ``prove_batch``.  Per LANE: ``keys[l]`` a ``PreprocessedKey`` made on the lane's context or None (its ``.values``,
+    when kept, is the table that ``("prep", c)`` terms read); ``logups[l]`` a ``LogUp`` or None, the aux source of
+    every item of lane l, run by the library on the lane's stream (no Python callback per proof); ``fills[l]`` a
+    list of ``LogUp.mult_spec(...)`` dicts or None: the multiplicity columns filled in the resident trace of every
+    item of lane l after its upload and before its commit.  A device trace of a lane with a ``LogUp`` or fills must
+    be row-major.  (``_struct_size`` / ``_cap_words``: test hooks, as in ``prove_batch``; ``_edit_items(items,
+    lanes_c)``: a test hook that may change the ctypes records before the call.)"""
+    from .air import mult_spec_c
+
+    n, n_l = len(traces), len(lanes)
+    lane_of = [int(x) for x in lane_of]
+    if len(lane_of) != n:
+        raise ValueError(f"prove_batch_lookup: {len(lane_of)} lane indices for {n} traces")
+    pis = [np.zeros(0, dtype=np.uint32) if p is None else _u32(p).reshape(-1)
+           for p in _per_item(public_values, n, _is_vector, "public-value vectors")]
+    chals = _per_item(challengers, n, lambda v: isinstance(v, BfChallenger), "challengers")
+    caps = _per_item(_cap_words, n, lambda v: isinstance(v, int), "buffer sizes")
+    if not lanes:
+        raise ValueError("prove_batch_lookup: no lanes")
+    keys = _per_lane(keys, n_l, "keys")
+    logups = _per_lane(logups, n_l, "LogUp specs")
+    fills = _per_lane(fills, n_l, "fill lists")
+    l = _lib.lib()
+    ctxs, airs, fri = _lane_arrays(lanes)
+    cfg = fri._c()
+    keep, outs, exps = [], [], []  # host buffers that must outlive the call
+    lanes_c = (_lib.BatchLaneC * n_l)()
+    specs, mults = [None] * n_l, [None] * n_l
+    for k in range(n_l):
+        lanes_c[k].struct_size = C.sizeof(_lib.BatchLaneC)
+        if keys[k] is not None:
+            lanes_c[k].key = keys[k].data.h
+            if keys[k].values is not None:
+                lanes_c[k].key_values = keys[k].values.h
+        if logups[k] is not None:
+            specs[k] = logups[k]._spec_c()
+        if fills[k]:
+            made = [mult_spec_c(**f) for f in fills[k]]
+            arr = (_lib.LogupMultSpecC * len(made))(*[m[0] for m in made])
+            mults[k] = (arr, made)
+    items = (_lib.BatchLookupItemC * max(n, 1))()
+    for i, t in enumerate(traces):
+        it = items[i]
+        it.struct_size = C.sizeof(_lib.BatchLookupItemC) if _struct_size is None else _struct_size
+        lane = lane_of[i]
+        it.lane = lane
+        it.status = -1
+        if isinstance(t, DeviceMatrix):
+            it.trace = t.h
+            h, w = t.dims()
+        elif isinstance(t, PinnedHostMatrix):
+            it.host_trace = t.ptr
+            h, w = t.shape
+        else:
+            a = _u32(t)
+            if a.ndim != 2:
+                raise ValueError(f"prove_batch_lookup: trace {i} is not a 2-D array")
+            keep.append(a)
+            it.host_trace = a.ctypes.data
+            h, w = a.shape
+        it.height, it.width = h, w
+        it.n_public = len(pis[i])
+        it.public_values = pis[i].ctypes.data if len(pis[i]) else None
+        it.challenger = chals[i].h if chals[i] is not None else None
+        air = lanes[lane][1] if 0 <= lane < n_l else None
+        if air is not None:
+            if specs[lane] is not None:
+                it.logup = C.pointer(specs[lane][0])
+            if mults[lane] is not None:
+                it.mult = mults[lane][0]
+                it.n_mult = len(mults[lane][0])
+        n_exp = air.n_exposed if air is not None else 0
+        if caps[i] is not None:
+            cap = caps[i]
+        else:  # as prove() sizes the buffer of a pre+aux proof
+            pw, aw = (air.preprocessed_width, air.aux_width) if air is not None else (0, 0)
+            log_N = max(h, 1).bit_length() - 1 + fri.log_blowup
+            cap = (_proof_capacity(h, w + pw + aw, _lane_lqd(lanes, lane), fri) + n_exp + 16 +
+                   fri.num_queries * (8 * log_N + 8))
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        outs.append(out)
+        it.proof_out = out.ctypes.data
+        it.cap_words = cap
+        ex = np.zeros(max(n_exp, 1), dtype=np.uint32)
+        exps.append(ex)
+        it.exposed_out = ex.ctypes.data
+        it.cap_exposed = n_exp
+    if _edit_items is not None:
+        hold = _edit_items(items, lanes_c)  # noqa: F841  (what the hook made stays alive over the call)
+    rc = l.ts_prove_batch_lookup(ctxs, airs, lanes_c, n_l, C.byref(cfg), items, n, float(gate_ms),
+                                 _lib.BATCH_DIGEST if digests else 0)
+    del keep, specs, mults
+    status = np.array([items[i].status for i in range(n)], dtype=np.int32)
+    if rc and (status == -1).all():  # the whole call was refused: no item was touched
+        msg = ("ts_prove_batch_lookup refused the call (null arrays, lane count, a repeated context, FriConfig, "
+               "struct_size or a missing lane array)")
+        raise _lib.TsError(rc, msg)
+    n_words = np.array([items[i].n_words for i in range(n)], dtype=np.int64)
+    errors = [None if s == 0 else _lane_error(lanes, lane_of[i]) for i, s in enumerate(status)]
+    res = BatchLookupResult(
+        rc=int(rc),
+        proofs=[Proof(outs[i][: n_words[i]].copy()) if status[i] == 0 else None for i in range(n)],
+        status=status, n_words=n_words,
+        digests=np.array([list(items[i].proof_blake3) for i in range(n)], dtype=np.uint32).reshape(n, 8)
+        if digests else None,
+        final_states=np.array([list(items[i].final_state) for i in range(n)], dtype=np.uint32).reshape(n, 34),
+        start_ms=np.array([items[i].start_ms for i in range(n)]),
+        wall_ms=np.array([items[i].wall_ms for i in range(n)]),
+        errors=errors,
+        exposed=[exps[i][: items[i].n_exposed].copy() if status[i] == 0 else None for i in range(n)],
+        n_missing=np.array([items[i].n_missing for i in range(n)], dtype=np.uint64),
+        first_missing=np.array([items[i].first_missing for i in range(n)], dtype=np.uint64))
+    if check and rc:
+        bad = next(i for i in range(n) if status[i] != 0)
+        raise _lib.TsError(int(status[bad]), f"item {bad}: {errors[bad] or 'not attempted'}")
+    return res
+
+
 def prove_sharded(config: StarkConfig, air, challenger: BfChallenger, trace_rows, public_values,
                   comm, min_local_log: int = 0, trace_replicated: bool = False,
                   local_quotient: bool = False, _options_struct_size: int | None = None) -> Proof:
@@ -1364,6 +1508,29 @@ def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_val
                              pis_p, len(pis), C.byref(verdict))
     if rc and verdict.value <= 0:  # (ts_verify_pre refuses a proof of another version or width WITH a verdict)
         raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify").decode())
+    if verdict.value != 0:
+        raise VerificationError(verdict.value)
+    return exposed
+
+
+def verify_pre_aux(config: StarkConfig, air, challenger: BfChallenger, proof, public_values, preprocessed_root=None):
+    """``ts_verify_pre_aux`` whatever the AIR's widths: the verifier of every ``prove_batch_lookup`` proof (TSPF v5
+    also for an AIR without a key, which ``verify`` routes there only together with a root).  ``preprocessed_root``
+    is None exactly for an AIR without preprocessed columns.  Returns the exposed words; raises as ``verify``."""
+    pis = _u32(public_values)
+    if isinstance(air, BaseAir):
+        air = CompiledAir(None, _air_tape_of(air, len(pis)))
+    words = _u32(proof.words if isinstance(proof, Proof) else proof)
+    cfg = config.pcs.fri._c()
+    verdict = C.c_int(-1)
+    l = _lib.lib()
+    exposed = np.zeros(air.n_exposed, dtype=np.uint32)
+    rc = l.ts_verify_pre_aux(C.byref(cfg), air.h, challenger.h,
+                             _p(_u32(preprocessed_root)) if preprocessed_root is not None else None, _p(words),
+                             len(words), _p(pis) if len(pis) else None, len(pis),
+                             _p(exposed) if len(exposed) else None, len(exposed), C.byref(verdict))
+    if rc and verdict.value <= 0:
+        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_pre_aux").decode())
     if verdict.value != 0:
         raise VerificationError(verdict.value)
     return exposed
