@@ -773,7 +773,8 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
 
 /* Measurement aid: the whole-chip rate of NTT butterflies (kind 0), Blake3 compressions (kind 1) or
  * SHA-256 compressions (kind 2) with no memory traffic -- kinds 3 / 4: the butterflies with the LDS traffic
- * of a contiguous NTT pass added (4-byte / 16-byte accesses; measurement of what LDS costs in power) --, using the library's own arithmetic -- the integer-ALU ceiling bench.py
+ * of a contiguous NTT pass added (4-byte / 16-byte accesses; measurement of what LDS costs in power), kind 5: the
+ * butterflies on a Plantard-form twiddle (8 instructions instead of 10) --, using the library's own arithmetic -- the integer-ALU ceiling bench.py
  * reports beside the achieved rates. */
 ts_status ts_bench_alu(ts_ctx* ctx, int kind, double* units_per_second);
 

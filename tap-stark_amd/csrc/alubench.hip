@@ -39,6 +39,33 @@ __global__ void __launch_bounds__(256) k_alu_butterflies(uint32_t* __restrict__ 
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
+// Kind 5: the forward butterfly on a Plantard twiddle (ntt_rounds.hpp, the uint2 tables): a = red2p(a),
+// t = plant_mul(b, W'), a' = a + t, b' = a - t + p -- 8 VALU instructions against the 10 of kind 0, 3 of them
+// on the multiplier instead of 3 of 10.
+__global__ void __launch_bounds__(256) k_alu_butterflies_plant(uint32_t* __restrict__ out, uint32_t seed) {
+    uint32_t a[BF_ILP], b[BF_ILP];
+#pragma unroll
+    for (int i = 0; i < BF_ILP; i++) {
+        a[i] = (seed + threadIdx.x * 7 + i) % P;
+        b[i] = (seed * 3 + threadIdx.x + i) % P;
+    }
+    const uint64_t w = plant_const(seed % P);
+    const uint32_t w_lo = (uint32_t)w, w_hi = (uint32_t)(w >> 32);
+    for (int it = 0; it < BF_ITER; it++) {
+#pragma unroll
+        for (int i = 0; i < BF_ILP; i++) {
+            const uint32_t x = red2p(a[i]);
+            const uint32_t t = plant_mul(b[i], w_lo, w_hi);
+            a[i] = x + t;
+            b[i] = x - t + P;
+        }
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < BF_ILP; i++) s ^= a[i] ^ b[i];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
 __global__ void __launch_bounds__(256) k_alu_blake3(uint32_t* __restrict__ out, uint32_t seed) {
     uint32_t m[16], cv[8];
 #pragma unroll
@@ -136,10 +163,11 @@ __global__ void __launch_bounds__(256) k_alu_sha256(uint32_t* __restrict__ out, 
 }  // namespace
 
 // kind 0: NTT butterflies per second; kind 1: Blake3 compressions per second; kind 2: SHA-256
-// compressions per second (whole chip)
+// compressions per second (whole chip); kind 5: NTT butterflies per second on a Plantard twiddle
 double alu_ceiling(Context& ctx, int kind) {
-    TS_REQUIRE(kind >= 0 && kind <= 4, TS_ERR_INVALID,
-               "alu_ceiling: kind is 0 (butterflies), 1 (blake3), 2 (sha256), 3 / 4 (butterflies + LDS round trips)");
+    TS_REQUIRE(kind >= 0 && kind <= 5, TS_ERR_INVALID,
+               "alu_ceiling: kind is 0 (butterflies), 1 (blake3), 2 (sha256), 3 / 4 (butterflies + LDS round trips), "
+               "5 (Plantard butterflies)");
     const int blocks = ctx.num_cus * 16, threads = 256, reps = 5;
     DevBuf<uint32_t> out(&ctx, (size_t)blocks * threads);
     hipEvent_t e0, e1;
@@ -154,6 +182,8 @@ double alu_ceiling(Context& ctx, int kind) {
             hipLaunchKernelGGL(k_alu_butterflies_lds<false>, dim3(blocks), dim3(threads), 0, ctx.stream, out.p, 12345u);
         else if (kind == 4)
             hipLaunchKernelGGL(k_alu_butterflies_lds<true>, dim3(blocks), dim3(threads), 0, ctx.stream, out.p, 12345u);
+        else if (kind == 5)
+            hipLaunchKernelGGL(k_alu_butterflies_plant, dim3(blocks), dim3(threads), 0, ctx.stream, out.p, 12345u);
         else
             hipLaunchKernelGGL(k_alu_sha256, dim3(blocks), dim3(threads), 0, ctx.stream, out.p, 12345u);
     };
@@ -167,7 +197,7 @@ double alu_ceiling(Context& ctx, int kind) {
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     const double per = (double)ms / reps * 1e-3;
-    const double units = kind == 0 ? (double)BF_ITER * BF_ILP : kind == 1 ? (double)B3_ITER
+    const double units = kind == 0 || kind == 5 ? (double)BF_ITER * BF_ILP : kind == 1 ? (double)B3_ITER
                          : kind == 2 ? (double)SHA_ITER : (double)LDSB_ROUNDS * 32;
     return units * blocks * threads / per;
 }

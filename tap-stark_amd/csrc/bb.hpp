@@ -82,6 +82,28 @@ TS_HD uint32_t from_mont(uint32_t a) { return mont_reduce((uint64_t)a); }
 // plain (canonical x canonical -> canonical) product; host-side convenience, slow path on device
 TS_HD uint32_t mul(uint32_t a, uint32_t b) { return mont_mul(to_mont(a), b); }
 
+// ---- product by a precomputed constant in Plantard's form (T. Plantard, "Efficient word size modular
+// arithmetic", IEEE TETC 2021) ---------------------------------------------------------------------
+// For a constant w < p store the 64-bit word  W' = ((w * (-2^64) mod p) * p^-1) mod 2^64.  Then for ANY
+// 32-bit a (reduced or not):  u = bits 32..63 of a * W' mod 2^64,  r = ((u + 1) * p) >> 32  ==  a w mod p,
+// canonical.  The paper's bound for exactness is a w < 2^32 (2^32 - p), which every a < 2^32 and w < p meet;
+// tests/test_plantard_cpu.py checks the edges of both operands against integer arithmetic.
+// Device: v_mul_hi_u32, v_mad_u64_u32 (low word), v_mad_u64_u32 (high word) -- three instructions, no range
+// correction, against 3 for mont_mul_lazy (output in [0, 2p), input bounded) and 5 for mont_mul.  A radix-2
+// butterfly whose twiddle is stored this way costs 8 VALU instructions (ntt_rounds.hpp), not the 10 of the
+// Montgomery form that earlier notes called the floor for a 31-bit prime in 32-bit lanes.
+constexpr uint64_t P_INV64 = 0x383FFFFF88000001ull;  // p^-1 mod 2^64
+TS_HD uint64_t plant_const(uint32_t w_canonical) {
+    // w * (-2^64) mod p: the Montgomery product of (w 2^32) and (p - 2^64 mod p) is their plain product / 2^32
+    return (uint64_t)mont_mul(to_mont(w_canonical), P - R2_MOD_P) * P_INV64;
+}
+// the two halves of W' apart: what a kernel has after loading a uint2 table entry
+TS_HD uint32_t plant_mul(uint32_t a, uint32_t w_lo, uint32_t w_hi) {
+    const uint32_t u = (uint32_t)((uint64_t)a * w_hi + mulhi32(a, w_lo));
+    return (uint32_t)(((uint64_t)u * P + P) >> 32);
+}
+TS_HD uint32_t plant_mul(uint32_t a, uint64_t wp) { return plant_mul(a, (uint32_t)wp, (uint32_t)(wp >> 32)); }
+
 TS_HD uint32_t pow_canon(uint32_t a, uint64_t e) {
     uint32_t r = R_MOD_P, am = to_mont(a);
     while (e) {

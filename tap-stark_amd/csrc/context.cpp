@@ -46,6 +46,8 @@ Context::~Context() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (d_twiddle_fwd) (void)hipFree(d_twiddle_fwd);
     if (d_twiddle_inv) (void)hipFree(d_twiddle_inv);
+    if (d_plant_fwd) (void)hipFree(d_plant_fwd);
+    if (d_plant_inv) (void)hipFree(d_plant_inv);
     for (auto& t : scale_tables) (void)hipFree(t.d);
     for (auto& t : sel_tables)
         if (t.d) (void)hipFree(t.d);
@@ -248,6 +250,24 @@ void Context::ensure_twiddles(unsigned log_size) {
     }
     twiddle_log = log_size;
     launch_build_twiddles(*this, d_twiddle_fwd, d_twiddle_inv, log_size);
+}
+
+void Context::ensure_plant_twiddles(unsigned log_size) {
+    if (log_size <= plant_log && d_plant_fwd) return;
+    TS_REQUIRE(log_size <= 27, TS_ERR_INVALID, "two-adicity of BabyBear is 27");
+    sync();
+    if (d_plant_fwd) (void)hipFree(d_plant_fwd);
+    if (d_plant_inv) (void)hipFree(d_plant_inv);
+    d_plant_fwd = d_plant_inv = nullptr;
+    const size_t n = (size_t)1 << log_size;
+    TS_HIP(hipMalloc((void**)&d_plant_fwd, n * 8));
+    TS_HIP(hipMalloc((void**)&d_plant_inv, n * 8));
+    if (poison_on) {
+        poison(d_plant_fwd, n * 8);
+        poison(d_plant_inv, n * 8);
+    }
+    plant_log = log_size;
+    launch_build_plant_twiddles(*this, d_plant_fwd, d_plant_inv, log_size);
 }
 
 }  // namespace ts

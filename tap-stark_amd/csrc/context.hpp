@@ -75,6 +75,12 @@ struct Context {
     uint32_t* d_twiddle_fwd = nullptr;
     uint32_t* d_twiddle_inv = nullptr;
     unsigned twiddle_log = 0;
+    // the same twiddles as Plantard words {low, high} (bb.hpp plant_const), for the NTT passes alone
+    // (ntt_rounds.hpp): sized by the longest TRANSFORM asked for (log_n, not log_N -- the Montgomery tables
+    // above also serve the selectors, the FRI fold and the openings over the whole LDE domain)
+    uint2* d_plant_fwd = nullptr;
+    uint2* d_plant_inv = nullptr;
+    unsigned plant_log = 0;
 
     // coset scale tables of the LDE (ntt_lde.hip): T[beta][k] = s_beta^k / n for one (log_n,
     // log_blowup, shift); a trace commit asks for the same one every proof, so a few are kept
@@ -175,6 +181,7 @@ struct Context {
     void d2h_point(void* host_dst, const void* dev_src, size_t bytes);  // an async copy + sync
     void* pinned(size_t bytes);
     void ensure_twiddles(unsigned log_size);
+    void ensure_plant_twiddles(unsigned log_size);  // a transform of 2^log_size points
     // (polling hipStreamQuery instead was measured and made no difference: profiles/r06_sync_spin_ab.txt)
     void sync() { TS_HIP(hipStreamSynchronize(stream)); }
 };

@@ -18,6 +18,8 @@ struct ColMat {
 
 // ---- ntt.hip, ntt_lde.hip --------------------------------------------------------------------
 void launch_build_twiddles(Context& ctx, uint32_t* W, uint32_t* Winv, unsigned log_size);
+// the same table in Plantard form: WP[m + i] = plant_const(w_{2m}^bitrev(i)) as {low, high}
+void launch_build_plant_twiddles(Context& ctx, uint2* WP, uint2* WPinv, unsigned log_size);
 // per-coset scale tables: lo[beta][j] = s_beta^j * scale (j < 1024), hi[beta][j] = s_beta^(1024 j)
 void launch_build_shift_tables(Context& ctx, uint32_t* lo, uint32_t* hi, uint32_t n_hi,
                                uint32_t n_cosets, uint32_t shift_mont, unsigned log_N,
@@ -68,12 +70,14 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
 constexpr uint32_t LDE_NO_OWN = 0xffffffffu;
 int lde_own_coset_used(unsigned log_n, unsigned log_blowup, uint32_t shift);
 
-// The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles for log_n must be there).  Each refuses
+// The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles for log_n must be there, the Montgomery
+// tables and the Plantard ones: Context::ensure_twiddles and ensure_plant_twiddles).  Each refuses
 // what the plan cannot run with the caller's wording (`lde`).
 inline void ntt_require_shape(const NttPlan& p, uint32_t ncols, uint64_t stride_a, uint64_t stride_b, bool lde) {
     if (const char* why = ntt_plan_refusal(p, ncols, stride_a, stride_b, lde)) throw Error(TS_ERR_INVALID, why);
 }
-// inverse stages log_n-1 .. sA on the chunks of `ncols` columns, in place, lazy values out (two-pass plans);
+// inverse stages log_n-1 .. sA on the chunks of `ncols` columns, in place (two-pass plans; canonical words in and,
+// every chunk size taking the Plantard inverse form, canonical words out: ntt_lde.hip ContigForm);
 // first_round_done: k_transpose_bitrev_r16 did the first round; data2: columns gw .. live in a second matrix
 void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
                            bool first_round_done = false, uint32_t* data2 = nullptr, uint32_t gw = 0xffffffffu);

@@ -16,7 +16,9 @@
 //                    transform, writing coset block beta -- the coefficients never touch HBM
 //   k_lde_fwd_contig stages sA .. log_n-1 of the forward transform, in place on 4096-element chunks
 // For n <= 4096 k_lde_mid alone does everything.  Data in HBM is canonical; twiddles are
-// Montgomery, so mont_mul(data, twiddle) is canonical.
+// Montgomery, so mont_mul(data, twiddle) is canonical -- or, for the NTT passes that take them, Plantard
+// words (bb.hpp plant_const): plant_mul(any word, twiddle) is canonical in three instructions, a butterfly
+// 8 instead of 10 (ntt_rounds.hpp states the two forms; ntt_lde.hip says which kernel takes which).
 #include "kernels.hpp"
 
 namespace ts {
@@ -24,29 +26,46 @@ namespace ts {
 constexpr int SHIFT_LO_BITS = 10;  // coset scale s^k = hi[k >> 10] * lo[k & 1023]
 
 // ------------------------------------------------------------------ tables
-__global__ void k_build_twiddles(uint32_t* __restrict__ W, uint32_t* __restrict__ Winv,
-                                 unsigned log_size) {
-    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (1u << log_size)) return;
-    if (idx == 0) {
-        W[0] = R_MOD_P;
-        Winv[0] = R_MOD_P;
-        return;
-    }
+// entry idx of the table, Montgomery form: w_{2m}^bitrev(i) for idx = m + i (1 at the unused index 0)
+__device__ __forceinline__ uint32_t twiddle_mont(uint32_t idx) {
+    if (idx == 0) return R_MOD_P;
     unsigned logm = 31 - __clz(idx);
     uint32_t i = idx - (1u << logm);
     // omega_{2m}: generator of the subgroup of order 2^(logm+1)
     uint32_t g27 = to_mont(TWO_ADIC_GEN_27);
     uint32_t g = mont_pow(g27, 1ull << (27 - (logm + 1)));
     uint32_t e = bitrev32(i, logm);
-    uint32_t w = mont_pow(g, e);
+    return mont_pow(g, e);
+}
+
+__global__ void k_build_twiddles(uint32_t* __restrict__ W, uint32_t* __restrict__ Winv,
+                                 unsigned log_size) {
+    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (1u << log_size)) return;
+    const uint32_t w = twiddle_mont(idx);
     W[idx] = w;
     Winv[idx] = mont_inv(w);
+}
+
+// the Plantard words of the same entries (the NTT passes' own tables: ntt_rounds.hpp)
+__global__ void k_build_plant_twiddles(uint2* __restrict__ WP, uint2* __restrict__ WPinv, unsigned log_size) {
+    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (1u << log_size)) return;
+    const uint32_t w = twiddle_mont(idx);
+    const uint64_t f = plant_const(from_mont(w)), b = plant_const(from_mont(mont_inv(w)));
+    WP[idx] = make_uint2((uint32_t)f, (uint32_t)(f >> 32));
+    WPinv[idx] = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
 }
 
 void launch_build_twiddles(Context& ctx, uint32_t* W, uint32_t* Winv, unsigned log_size) {
     uint32_t n = 1u << log_size;
     TS_LAUNCH(ctx, k_build_twiddles, dim3((n + 255) / 256), dim3(256), 0, W, Winv, log_size);
+    TS_HIP(hipGetLastError());
+}
+
+void launch_build_plant_twiddles(Context& ctx, uint2* WP, uint2* WPinv, unsigned log_size) {
+    uint32_t n = 1u << log_size;
+    TS_LAUNCH(ctx, k_build_plant_twiddles, dim3((n + 255) / 256), dim3(256), 0, WP, WPinv, log_size);
     TS_HIP(hipGetLastError());
 }
 

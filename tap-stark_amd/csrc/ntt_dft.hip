@@ -39,10 +39,10 @@ __device__ __forceinline__ uint32_t dft_factor(const uint32_t* __restrict__ lo, 
 // place (row_shift = LM for n > 2^LM; 0 with log_T = 0 where the tile is the whole column).
 // PLAN 0: run-time round plan.  PLAN 1: log_len = 8, log_T = 5 (n = 2^(LM + 8)): two radix-16 rounds with
 // compile-time distances 2^9 and 2^5, the first of them from stage 0 (no product for the twiddle 1).
-template <bool INV, bool SCALE, int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID>
+template <bool INV, bool SCALE, int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, class TW = uint32_t>
 __global__ void __launch_bounds__(NTM)
 k_dft_mid(uint32_t* data, uint64_t col_stride, unsigned log_len, unsigned log_T, unsigned row_shift,
-          const uint32_t* __restrict__ W, const uint32_t* __restrict__ f_lo, const uint32_t* __restrict__ f_hi) {
+          const TW* __restrict__ W, const uint32_t* __restrict__ f_lo, const uint32_t* __restrict__ f_hi) {
     __shared__ uint32_t s[padded(TILE)];
     constexpr int PER_THREAD = TILE / NTM;
     if (PLAN == 1) {
@@ -124,19 +124,29 @@ void launch_bit_reverse_rows(Context& ctx, const uint32_t* src, uint32_t* dst, u
 }
 
 // ------------------------------------------------------------------ host drivers
+// the twiddle form of each instantiation of k_dft_mid, by the rule of ntt_lde.hip (ContigForm / MidForm)
+template <bool INV, int PLAN, int TILE> struct DftMidFormOf {
+    using type = uint2;
+};
+// the inverse run-time plan on the 8192-element tile: 61 -> 65 VGPRs, three workgroups per CU instead of four
+template <> struct DftMidFormOf<true, 0, TILE_ELEMS> {
+    using type = uint32_t;
+};
+template <bool INV, int PLAN, int TILE> using DftMidForm = typename DftMidFormOf<INV, PLAN, TILE>::type;
+
 // the strided pass of one direction (the whole transform when the plan has one pass); `names`: the kernel-timer
 // names of the three variants in NttMid's order, spelled as tools/time_dft.py has always printed them
 template <bool INV, bool SCALE>
 static void launch_dft_mid_of(Context& ctx, const NttPlan& p, uint32_t* cols, uint64_t col_stride, uint32_t ncols,
                               const uint32_t* f_lo, const uint32_t* f_hi, const char* const (&names)[3]) {
-    const uint32_t* W = INV ? ctx.d_twiddle_inv : ctx.d_twiddle_fwd;
+    const TwTables W = INV ? twiddles_inv(ctx) : twiddles_fwd(ctx);
     auto launch = [&](auto kernel) {
         TS_LAUNCH_NAMED(ctx, names[(int)p.mid], kernel, dim3(p.tiles, ncols), dim3(NT_MID), 0, cols, col_stride,
                         p.log_len, p.log_T, p.row_shift, W, f_lo, f_hi);
     };
-    if (p.mid == NttMid::TILE16384) launch(k_dft_mid<INV, SCALE, 0, 16384>);
-    else if (p.mid == NttMid::FIXED256) launch(k_dft_mid<INV, SCALE, 1>);
-    else launch(k_dft_mid<INV, SCALE, 0>);
+    if (p.mid == NttMid::TILE16384) launch(k_dft_mid<INV, SCALE, 0, 16384, NT_MID, DftMidForm<INV, 0, 16384>>);
+    else if (p.mid == NttMid::FIXED256) launch(k_dft_mid<INV, SCALE, 1, TILE_ELEMS, NT_MID, DftMidForm<INV, 1, TILE_ELEMS>>);
+    else launch(k_dft_mid<INV, SCALE, 0, TILE_ELEMS, NT_MID, DftMidForm<INV, 0, TILE_ELEMS>>);
 }
 
 static void launch_dft_mid(Context& ctx, const NttPlan& p, uint32_t* cols, uint64_t col_stride, uint32_t ncols,
@@ -162,6 +172,7 @@ void dft_columns(Context& ctx, uint32_t* cols, uint64_t col_stride, uint32_t nco
     const NttPlan p = ntt_plan(log_n);
     ntt_require_shape(p, ncols, col_stride, 0, false);
     ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
+    ctx.ensure_plant_twiddles(log_n == 0 ? 1 : log_n);
 
     // factor of coefficient k: shift^k (forward; none for shift 1) or shift^-k / n (inverse)
     const bool scale = inverse || shift != 1;

@@ -47,10 +47,10 @@
 namespace ts {
 
 // chunk `c` of column blockIdx.y: global stages log_n-1 .. log_n-LM of the inverse (n > 2^LM)
-template <int LM, bool SKIP_R16 = false>
+template <int LM, bool SKIP_R16 = false, class TW = uint32_t>
 __global__ void __launch_bounds__(chunk_threads(LM))
 k_intt_contig(uint32_t* __restrict__ data, uint64_t col_stride, unsigned log_n,
-              const uint32_t* __restrict__ Winv, uint32_t* __restrict__ data2, uint32_t gw) {
+              const TW* __restrict__ Winv, uint32_t* __restrict__ data2, uint32_t gw) {
     __shared__ uint32_t s[padded(1 << LM)];
     const uint32_t c = blockIdx.x;
     // columns gw .. of a two-matrix launch live in the second matrix (coset_lde: evals2)
@@ -59,7 +59,7 @@ k_intt_contig(uint32_t* __restrict__ data, uint64_t col_stride, unsigned log_n,
     uint32_t* g = col + ((uint64_t)c << LM);
     chunk_load<LM>(s, g);
     chunk_rounds<LM, true, SKIP_R16>(s, log_n - LM, c, Winv);
-    chunk_store<LM, false>(s, g);  // read next by k_lde_mid's inverse rounds
+    chunk_store<LM, false>(s, g);  // read next by k_lde_mid's inverse rounds (Plantard form: canonical as they are)
 }
 
 // The transpose of a row-major trace (src[r][c], natural rows -> dst[c][p], p = bitrev(r)) with the
@@ -72,7 +72,7 @@ k_intt_contig(uint32_t* __restrict__ data, uint64_t col_stride, unsigned log_n,
 __global__ void __launch_bounds__(256)
 k_transpose_bitrev_r16(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, unsigned log_n,
                        uint32_t w, uint64_t dst_col_stride, uint32_t src_width,
-                       const uint32_t* __restrict__ Winv) {
+                       const uint2* __restrict__ Winv) {
     __shared__ uint32_t tile[64][65];
     const uint32_t p0 = blockIdx.x << 6;
     const uint32_t c0 = blockIdx.y * 64;
@@ -89,7 +89,7 @@ k_transpose_bitrev_r16(const uint32_t* __restrict__ src, uint32_t* __restrict__ 
 #pragma unroll
         for (int q = 0; q < 16; q++) v[q] = 0;
     }
-    // global stages log_n-1 .. log_n-4 on group (p0 >> 4) + ty (lazy [0, 2p) values out)
+    // global stages log_n-1 .. log_n-4 on group (p0 >> 4) + ty (Plantard form: canonical words in, canonical out)
     radix_butterflies<4, true, false>(v, log_n - 4, 0, 0, (p0 >> 4) + ty, Winv);
 #pragma unroll
     for (int q = 0; q < 16; q++) tile[16 * ty + q][tx] = v[q];
@@ -108,9 +108,9 @@ k_transpose_bitrev_r16(const uint32_t* __restrict__ src, uint32_t* __restrict__ 
 // rounds of chunk i run (the 16384-element chunk leaves room for two workgroups per CU only, and with
 // 16 waves per CU nothing else covers a chunk's load latency: rocprofv3 SQ counters on 2^22 x 64,
 // log_blowup 4 showed VALU busy 0.86 with 28 % of the wave-cycles parked).
-template <int LM, int CPW>
+template <int LM, int CPW, class TW>
 __device__ __forceinline__ void lde_fwd_contig_block(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                                                     const uint32_t* __restrict__ W, const uint32_t beta) {
+                                                     const TW* __restrict__ W, const uint32_t beta) {
     __shared__ uint32_t s[padded(1 << LM)];
     constexpr int NT = chunk_threads(LM);
     constexpr int NV = (1 << LM) / 4 / NT;
@@ -154,19 +154,19 @@ __device__ __forceinline__ void lde_fwd_contig_block(uint32_t* __restrict__ out,
     }
 }
 
-template <int LM, int CPW = 1>
+template <int LM, int CPW = 1, class TW = uint32_t>
 __global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)  // CPW > 1: keep two 512-thread groups per CU
 k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                 const uint32_t* __restrict__ W) {
+                 const TW* __restrict__ W) {
     lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z);
 }
 
 // The same on all blocks but one per column, the block that is its matrix's input (own_a for the columns below
 // gw, own_b from gw on: coset_lde).  The grid's z is one short and no workgroup is launched for that block.
-template <int LM, int CPW = 1>
+template <int LM, int CPW = 1, class TW = uint32_t>
 __global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)
 k_lde_fwd_contig_own(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                     const uint32_t* __restrict__ W, uint32_t gw, uint32_t own_a, uint32_t own_b) {
+                     const TW* __restrict__ W, uint32_t gw, uint32_t own_a, uint32_t own_b) {
     const uint32_t own = blockIdx.y < gw ? own_a : own_b;
     lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z + (blockIdx.z >= own ? 1u : 0u));
 }
@@ -181,12 +181,13 @@ k_lde_fwd_contig_own(uint32_t* __restrict__ out, uint64_t out_col_stride, unsign
 // distances 2^9 and 2^5.
 // OWN (coset_lde on every coset, beta0 = 0): block own_a of the first matrix's columns and own_b of the second's
 // is the matrix itself and has been copied; the coset loop steps over it.
-template <int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, int LM = LOG_M, bool OWN = false>
+template <int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, int LM = LOG_M, bool OWN = false, class TWF = uint32_t,
+          class TWI = uint32_t>
 __global__ void __launch_bounds__(NTM)
 k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* __restrict__ out,
           uint64_t out_col_stride, unsigned log_n, unsigned log_len, unsigned log_T,
-          unsigned row_shift, unsigned beta0, unsigned n_cosets, const uint32_t* __restrict__ W,
-          const uint32_t* __restrict__ Winv, const uint32_t* __restrict__ scale_a,
+          unsigned row_shift, unsigned beta0, unsigned n_cosets, const TWF* __restrict__ W,
+          const TWI* __restrict__ Winv, const uint32_t* __restrict__ scale_a,
           const uint32_t* __restrict__ evals2, const uint32_t* __restrict__ scale_b, uint32_t gw,
           uint32_t own_a, uint32_t own_b) {
     __shared__ uint32_t s[padded(TILE)];
@@ -394,6 +395,36 @@ constexpr const char* INTT_R16_NAME[3] = {"(k_intt_contig<12, true>)", "(k_intt_
                                           "(k_intt_contig<14, true>)"};
 constexpr const char* FWD_NAME[3] = {"k_lde_fwd_contig<12>", "k_lde_fwd_contig<13>", "(k_lde_fwd_contig<14, 4>)"};
 
+// THE TWIDDLE FORM OF EACH INSTANTIATION (ntt_rounds.hpp: uint32_t = Montgomery table, uint2 = Plantard table).
+// An instantiation takes the Plantard form where, against the Montgomery one, it gains no scratch, loses no
+// wave per SIMD and executes fewer VALU instructions (profiles/plantard_kernel_resources.txt has the table).
+// Range contract between the passes: every inverse pass here leaves canonical words when it is Plantard and
+// lazy ones when it is Montgomery; a Plantard inverse pass behind a Montgomery one would have to reduce on
+// load, so ContigForm<LM>::Inv being Plantard is what lets MidForm<..>::Inv of the same plan be.
+template <int LM> struct ContigForm {
+    using Inv = uint2;
+    using Fwd = uint2;
+};
+// k_lde_fwd_contig<14, 4> on the Plantard table: 121 -> 128 VGPRs and 40 bytes of scratch
+template <> struct ContigForm<14> {
+    using Inv = uint2;
+    using Fwd = uint32_t;
+};
+template <int PLAN, int TILE> struct MidForm {
+    using Inv = uint2;
+    using Fwd = uint2;
+};
+// the run-time plan's forward rounds on the Plantard table: 121 -> 150 VGPRs, one workgroup per CU instead of two
+// (128 and 8 bytes of scratch when held to two); its inverse rounds alone: 121, as before
+template <> struct MidForm<0, TILE_ELEMS> {
+    using Inv = uint2;
+    using Fwd = uint32_t;
+};
+static_assert(std::is_same<ContigForm<12>::Inv, uint2>::value && std::is_same<ContigForm<13>::Inv, uint2>::value &&
+                  std::is_same<ContigForm<14>::Inv, uint2>::value,
+              "the strided inverse rounds (here and in ntt_dft.hip) take canonical words: a Montgomery k_intt_contig "
+              "would have to be reduced on load");
+
 // f(std::integral_constant<int, LM>) for the plan's chunk size
 template <class F>
 static void with_chunk_log(unsigned LM, F&& f) {
@@ -405,25 +436,26 @@ static void with_chunk_log(unsigned LM, F&& f) {
 bool launch_transpose_bitrev_r16(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_n, uint32_t w,
                                  uint64_t dst_col_stride, uint32_t src_width) {
     if (w == 0 || !ntt_plan(log_n).fused_first_round) return false;  // no contiguous inverse pass to shorten
-    ctx.ensure_twiddles(log_n);
+    ctx.ensure_plant_twiddles(log_n);
     TS_LAUNCH(ctx, k_transpose_bitrev_r16, dim3(1u << (log_n - 6), (w + 63) / 64), dim3(256), 0, src, dst, log_n, w,
-              dst_col_stride, src_width ? src_width : w, (const uint32_t*)ctx.d_twiddle_inv);
+              dst_col_stride, src_width ? src_width : w, (const uint2*)ctx.d_plant_inv);
     TS_HIP(hipGetLastError());
     return true;
 }
 
 void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
                            bool first_round_done, uint32_t* data2, uint32_t gw) {
-    const uint32_t* Winv = ctx.d_twiddle_inv;
+    const TwTables Winv = twiddles_inv(ctx);
     with_chunk_log(p.LM, [&](auto lm) {
         constexpr int LM = decltype(lm)::value;
+        using TW = typename ContigForm<LM>::Inv;
         const dim3 g(p.chunks, ncols), b(chunk_threads(LM));
         if (first_round_done)
-            TS_LAUNCH_NAMED(ctx, INTT_R16_NAME[LM - 12], (k_intt_contig<LM, true>), g, b, 0, data, col_stride, p.log_n,
-                            Winv, data2, gw);
+            TS_LAUNCH_NAMED(ctx, INTT_R16_NAME[LM - 12], (k_intt_contig<LM, true, TW>), g, b, 0, data, col_stride,
+                            p.log_n, Winv, data2, gw);
         else
-            TS_LAUNCH_NAMED(ctx, INTT_NAME[LM - 12], k_intt_contig<LM>, g, b, 0, data, col_stride, p.log_n, Winv, data2,
-                            gw);
+            TS_LAUNCH_NAMED(ctx, INTT_NAME[LM - 12], (k_intt_contig<LM, false, TW>), g, b, 0, data, col_stride, p.log_n,
+                            Winv, data2, gw);
     });
 }
 
@@ -433,50 +465,54 @@ static void launch_lde_mid(Context& ctx, const NttPlan& p, const uint32_t* evals
                            uint32_t* out, uint64_t out_col_stride, uint32_t ncols, uint32_t beta0, uint32_t n_beta,
                            const uint32_t* scale, const uint32_t* evals2, const uint32_t* scale2, uint32_t gw,
                            uint32_t own_a, uint32_t own_b) {
-    const uint32_t *W = ctx.d_twiddle_fwd, *Winv = ctx.d_twiddle_inv;
+    const TwTables W = twiddles_fwd(ctx), Winv = twiddles_inv(ctx);
     const dim3 grid(p.tiles, ncols), b(NT_MID);
     const dim3 grid1(p.tiles * ncols);  // the fixed plan: 1-D, see the kernel
 #define TS_MID_ARGS \
     evals, in_col_stride, out, out_col_stride, p.log_n, p.log_len, p.log_T, p.row_shift, beta0, n_beta, W, Winv, scale, \
         evals2, scale2, gw, own_a, own_b
+#define TS_MID_K(PLAN, TILE, LM, OWN) \
+    (k_lde_mid<PLAN, TILE, NT_MID, LM, OWN, typename MidForm<PLAN, TILE>::Fwd, typename MidForm<PLAN, TILE>::Inv>)
     // (the instantiations that step over a block run under the names of the ones that do not)
     if (own_a != LDE_NO_OWN && p.mid == NttMid::FIXED256 && p.LM == 12)
-        TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", (k_lde_mid<1, TILE_ELEMS, NT_MID, 12, true>), grid1, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", TS_MID_K(1, TILE_ELEMS, 12, true), grid1, b, 0, TS_MID_ARGS);
     else if (own_a != LDE_NO_OWN && p.mid == NttMid::FIXED256 && p.LM == 13)
-        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 13>)", (k_lde_mid<1, 8192, 512, 13, true>), grid1, b, 0,
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 13>)", TS_MID_K(1, 8192, 13, true), grid1, b, 0,
                         TS_MID_ARGS);
     else if (own_a != LDE_NO_OWN && p.mid == NttMid::FIXED256)
-        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 14>)", (k_lde_mid<1, 8192, 512, 14, true>), grid1, b, 0,
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 14>)", TS_MID_K(1, 8192, 14, true), grid1, b, 0,
                         TS_MID_ARGS);
     else if (own_a != LDE_NO_OWN)
-        TS_LAUNCH_NAMED(ctx, "k_lde_mid<0>", (k_lde_mid<0, TILE_ELEMS, NT_MID, LOG_M, true>), grid, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<0>", TS_MID_K(0, TILE_ELEMS, LOG_M, true), grid, b, 0, TS_MID_ARGS);
     else if (p.mid == NttMid::TILE16384)
-        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<0, 16384>)", (k_lde_mid<0, 16384>), grid, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<0, 16384>)", TS_MID_K(0, 16384, LOG_M, false), grid, b, 0, TS_MID_ARGS);
     else if (p.mid == NttMid::FIXED256 && p.LM == 12)
-        TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", k_lde_mid<1>, grid1, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<1>", TS_MID_K(1, TILE_ELEMS, LOG_M, false), grid1, b, 0, TS_MID_ARGS);
     else if (p.mid == NttMid::FIXED256 && p.LM == 13)
-        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 13>)", (k_lde_mid<1, 8192, 512, 13>), grid1, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 13>)", TS_MID_K(1, 8192, 13, false), grid1, b, 0, TS_MID_ARGS);
     else if (p.mid == NttMid::FIXED256)
-        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 14>)", (k_lde_mid<1, 8192, 512, 14>), grid1, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "(k_lde_mid<1, 8192, 512, 14>)", TS_MID_K(1, 8192, 14, false), grid1, b, 0, TS_MID_ARGS);
     else
-        TS_LAUNCH_NAMED(ctx, "k_lde_mid<0>", k_lde_mid<0>, grid, b, 0, TS_MID_ARGS);
+        TS_LAUNCH_NAMED(ctx, "k_lde_mid<0>", TS_MID_K(0, TILE_ELEMS, LOG_M, false), grid, b, 0, TS_MID_ARGS);
 #undef TS_MID_ARGS
+#undef TS_MID_K
 }
 
 void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
                            uint32_t n_blocks, uint32_t gw, uint32_t own_a, uint32_t own_b) {
-    const uint32_t* W = ctx.d_twiddle_fwd;
+    const TwTables W = twiddles_fwd(ctx);
     with_chunk_log(p.LM, [&](auto lm) {
         constexpr int LM = decltype(lm)::value;
+        using TW = typename ContigForm<LM>::Fwd;
         // 4 chunks per workgroup of the 16384-element forward pass: measured 12.22 ms per proof against
         // 12.49 with 1 and 13.34 with 2 (spills)
         constexpr int CPW = LM == 14 ? 4 : 1;
         if (own_a != LDE_NO_OWN)  // one block per column is already there: n_blocks - 1 of them in z
-            TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig_own<LM, CPW>),
+            TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig_own<LM, CPW, TW>),
                             dim3(p.chunks / CPW, ncols, n_blocks - 1), dim3(chunk_threads(LM)), 0, data, col_stride,
                             p.log_n, W, gw, own_a, own_b);
         else
-            TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig<LM, CPW>), dim3(p.chunks / CPW, ncols, n_blocks),
+            TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig<LM, CPW, TW>), dim3(p.chunks / CPW, ncols, n_blocks),
                             dim3(chunk_threads(LM)), 0, data, col_stride, p.log_n, W);
     });
 }
@@ -502,6 +538,7 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
     TS_REQUIRE(!first_round_done || p.fused_first_round, TS_ERR_INVARIANT,
                "coset_lde: no contiguous inverse pass at this size");
     ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
+    ctx.ensure_plant_twiddles(log_n == 0 ? 1 : log_n);
 
     // per-coset scale table s_beta^k / n (cached per context: the trace's is the same every proof)
     const uint32_t n_cosets = 1u << log_blowup;

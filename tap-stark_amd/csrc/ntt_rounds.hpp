@@ -25,11 +25,48 @@ constexpr int padded(int n) { return n + (n >> 5); }
 // distance 2^log_dl of the round's last stage.  LOG_DL >= 0 fixes that distance at compile time
 // (LDS addresses become base + immediate offsets); LOG_DL = -1 takes it from the arguments.
 // The K stages of one register group v[0 .. 2^K): global stages s_base + u0 .. + K - 1 on the group
-// whose block index at stage u0 is `hi` (chunk c).  Values stay in the lazy range [0, 2p).
-template <int K, bool INV, bool TOP>
+// whose block index at stage u0 is `hi` (chunk c).
+//
+// The twiddle table's element type selects the product, and with it the ranges (stated here, once):
+//   const uint32_t*  Montgomery words (Context::d_twiddle_fwd / _inv).  Forward and inverse: inputs and outputs
+//                    in the lazy range [0, 2p), right mod p.  10 VALU instructions per multiplied butterfly
+//                    (forward 2 + 5 + 1 + 2: a -> [0, p), t = mont_mul in [0, p), a + t, a - t + p; inverse
+//                    4 + 1 + 2 + 3 with the product left in [0, 2p)).
+//   const uint2*     Plantard words {low, high} (Context::d_plant_fwd / _inv; bb.hpp plant_mul: any 32-bit
+//                    operand in, canonical product out, 3 instructions).  8 per multiplied butterfly.
+//                    Forward: inputs and outputs in [0, 2p) as above (2 + 3 + 1 + 2).
+//                    Inverse: inputs CANONICAL, outputs canonical: add(a, b) and plant_mul(a - b + p)
+//                    (3 + 2 + 3; a twiddle-1 butterfly of a TOP round is add and sub).  Nothing needs reducing
+//                    between the passes of an inverse transform; a producer that leaves lazy values (a
+//                    Montgomery pass) has to be reduced on load by the pass that takes this form.
+// mul: canonical product; mul_lazy: product in [0, 2p) where that is cheaper (Montgomery)
+template <class TW> struct TwForm;
+template <> struct TwForm<uint32_t> {
+    static constexpr bool plantard = false;
+    static __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t w) { return mont_mul(a, w); }
+    static __device__ __forceinline__ uint32_t mul_lazy(uint32_t a, uint32_t w) { return mont_mul_lazy(a, w); }
+};
+template <> struct TwForm<uint2> {
+    static constexpr bool plantard = true;
+    static __device__ __forceinline__ uint32_t mul(uint32_t a, uint2 w) { return plant_mul(a, w.x, w.y); }
+    static __device__ __forceinline__ uint32_t mul_lazy(uint32_t a, uint2 w) { return mul(a, w); }
+};
+
+// Host side: both tables of one direction; the parameter type of the kernel launched picks its own.
+struct TwTables {
+    const uint32_t* mont;
+    const uint2* plant;
+    operator const uint32_t*() const { return mont; }
+    operator const uint2*() const { return plant; }
+};
+inline TwTables twiddles_fwd(const Context& ctx) { return TwTables{ctx.d_twiddle_fwd, ctx.d_plant_fwd}; }
+inline TwTables twiddles_inv(const Context& ctx) { return TwTables{ctx.d_twiddle_inv, ctx.d_plant_inv}; }
+
+template <int K, bool INV, bool TOP, class TW>
 __device__ __forceinline__ void radix_butterflies(uint32_t (&v)[1 << K], unsigned s_base, unsigned u0,
                                                   uint32_t c, uint32_t hi,
-                                                  const uint32_t* __restrict__ W) {
+                                                  const TW* __restrict__ W) {
+    using F = TwForm<TW>;
     constexpr int R = 1 << K;
     if (!INV) {
 #pragma unroll
@@ -38,16 +75,15 @@ __device__ __forceinline__ void radix_butterflies(uint32_t (&v)[1 << K], unsigne
             // ONE address per stage: the 2^d twiddles of this group are consecutive words, read at
             // immediate offsets from wp (indexing W[wb + j] made the compiler rebuild a 64-bit
             // address for every j: ~3 VALU instructions per twiddle, 8 % of a contiguous pass)
-            const uint32_t* __restrict__ wp = W + ((1u << (s_base + u0 + d)) + (c << (u0 + d)) + (hi << d));
+            const TW* __restrict__ wp = W + ((1u << (s_base + u0 + d)) + (c << (u0 + d)) + (hi << d));
 #pragma unroll
             for (int q = 0; q < R; q++) {
                 if ((q & half) == 0) {
-                    // lazy range: inputs and outputs in [0, 2p) (2p < 2^32), 10 VALU
-                    // instructions instead of 11: a -> [0, p), t in [0, p), a + t and a - t + p
+                    // a -> [0, p), t in [0, p), a + t and a - t + p in [0, 2p) (2p < 2^32)
                     const uint32_t a = red2p(v[q]);
                     uint32_t t = v[q + half];
                     if (TOP && (q >> (K - d)) == 0) t = red2p(t);
-                    else t = mont_mul(t, wp[q >> (K - d)]);
+                    else t = F::mul(t, wp[q >> (K - d)]);
                     v[q] = a + t;
                     v[q + half] = a - t + P;
                 }
@@ -57,16 +93,23 @@ __device__ __forceinline__ void radix_butterflies(uint32_t (&v)[1 << K], unsigne
 #pragma unroll
         for (int d = K - 1; d >= 0; d--) {
             const int half = R >> (d + 1);
-            const uint32_t* __restrict__ wp = W + ((1u << (s_base + u0 + d)) + (c << (u0 + d)) + (hi << d));
+            const TW* __restrict__ wp = W + ((1u << (s_base + u0 + d)) + (c << (u0 + d)) + (hi << d));
 #pragma unroll
             for (int q = 0; q < R; q++) {
                 if ((q & half) == 0) {
-                    // lazy range [0, 2p) in and out: the product is left uncorrected
-                    const uint32_t a = red2p(v[q]), b = red2p(v[q + half]);
-                    v[q] = a + b;
-                    uint32_t dlt = a - b + P;
-                    if (!(TOP && (q >> (K - d)) == 0)) dlt = mont_mul_lazy(dlt, wp[q >> (K - d)]);
-                    v[q + half] = dlt;
+                    const bool one = TOP && (q >> (K - d)) == 0;  // twiddle 1
+                    if (F::plantard) {
+                        const uint32_t a = v[q], b = v[q + half];
+                        v[q] = add(a, b);
+                        v[q + half] = one ? sub(a, b) : F::mul(a - b + P, wp[q >> (K - d)]);
+                    } else {
+                        // lazy range [0, 2p) in and out: the product is left uncorrected
+                        const uint32_t a = red2p(v[q]), b = red2p(v[q + half]);
+                        v[q] = a + b;
+                        uint32_t dlt = a - b + P;
+                        if (!one) dlt = F::mul_lazy(dlt, wp[q >> (K - d)]);
+                        v[q + half] = dlt;
+                    }
                 }
             }
         }
@@ -76,10 +119,10 @@ __device__ __forceinline__ void radix_butterflies(uint32_t (&v)[1 << K], unsigne
 // TOP = true: the round starts at global stage 0 of a whole transform (s_base = u0 = c = 0, one group
 // block): block 0 of every stage has the twiddle w^0 = 1, i.e. butterflies with q < 2^(K-d) at local
 // stage d need no multiplication (all of stage 0, half of stage 1, ...: 47 % of a radix-16 round).
-template <int K, bool INV, int LOG_DL, int NTH, bool TOP = false>
+template <int K, bool INV, int LOG_DL, int NTH, bool TOP = false, class TW>
 __device__ __forceinline__ void radix_round(uint32_t* s, unsigned log_total, unsigned u0,
                                             unsigned s_base, uint32_t c,
-                                            const uint32_t* __restrict__ W) {
+                                            const TW* __restrict__ W) {
     constexpr int R = 1 << K;
     const unsigned log_dl = LOG_DL >= 0 ? (unsigned)LOG_DL : log_total - u0 - K;
     const uint32_t n_groups = 1u << (log_total - K);
@@ -119,10 +162,10 @@ __device__ __forceinline__ void radix_round(uint32_t* s, unsigned log_total, uns
     __syncthreads();
 }
 
-template <bool INV, int NTH>
+template <bool INV, int NTH, class TW>
 __device__ __forceinline__ void radix_round_rt(int k, uint32_t* s, unsigned log_total, unsigned u0,
                                                unsigned s_base, uint32_t c,
-                                               const uint32_t* __restrict__ W) {
+                                               const TW* __restrict__ W) {
     switch (k) {
         case 4: radix_round<4, INV, -1, NTH>(s, log_total, u0, s_base, c, W); break;
         case 3: radix_round<3, INV, -1, NTH>(s, log_total, u0, s_base, c, W); break;
@@ -133,10 +176,10 @@ __device__ __forceinline__ void radix_round_rt(int k, uint32_t* s, unsigned log_
 
 // Generic plan: log_len stages in ceil(log_len/4) rounds of nearly equal size (10 = 4+3+3): the
 // first `rem` rounds take q+1 stages, the others q.
-template <int NTH>
+template <int NTH, class TW>
 __device__ __forceinline__ void tile_forward_rt(uint32_t* s, unsigned log_len, unsigned log_T,
                                                 unsigned s_base, uint32_t c,
-                                                const uint32_t* __restrict__ W) {
+                                                const TW* __restrict__ W) {
     if (log_len == 0) return;
     const unsigned nr = (log_len + 3) / 4, q = log_len / nr, rem = log_len % nr;
     unsigned u = 0;
@@ -146,10 +189,10 @@ __device__ __forceinline__ void tile_forward_rt(uint32_t* s, unsigned log_len, u
         u += k;
     }
 }
-template <int NTH>
+template <int NTH, class TW>
 __device__ __forceinline__ void tile_inverse_rt(uint32_t* s, unsigned log_len, unsigned log_T,
                                                 unsigned s_base, uint32_t c,
-                                                const uint32_t* __restrict__ Winv) {
+                                                const TW* __restrict__ Winv) {
     if (log_len == 0) return;
     const unsigned nr = (log_len + 3) / 4, q = log_len / nr, rem = log_len % nr;
     unsigned u = log_len;
@@ -202,8 +245,8 @@ __device__ __forceinline__ void chunk_store(const uint32_t* s, uint32_t* __restr
 
 // the LM local stages of a chunk, forward (u = 0 .. LM-1) or inverse (backwards)
 // SKIP_R16 (inverse only): the round at distance 1 was done by k_transpose_bitrev_r16 already.
-template <int LM, bool INV, bool SKIP_R16 = false>
-__device__ __forceinline__ void chunk_rounds(uint32_t* s, unsigned sb, uint32_t c, const uint32_t* __restrict__ W) {
+template <int LM, bool INV, bool SKIP_R16 = false, class TW>
+__device__ __forceinline__ void chunk_rounds(uint32_t* s, unsigned sb, uint32_t c, const TW* __restrict__ W) {
     constexpr int NT = chunk_threads(LM);
     constexpr int K0 = LM == 12 ? 4 : 5;   // stages 0 .. K0-1, distance 2^(LM - K0)
     constexpr int K1 = LM == 14 ? 5 : 4;   // stages K0 .. K0+K1-1, distance 16

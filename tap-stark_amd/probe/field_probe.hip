@@ -1,4 +1,5 @@
-// Field probe: every primitive of csrc/bb.hpp, and the register butterflies of csrc/ntt_rounds.hpp, applied to
+// Field probe: every primitive of csrc/bb.hpp, and the register butterflies of csrc/ntt_rounds.hpp (on the
+// Montgomery table type, ops 32-35, and on the Plantard one, ops 48-51: tests/_plantard_cases.py), applied to
 // operands chosen by a test and written back word for word, so that tests/_field_cases.py can compare the
 // host build (--host, no HIP call: runs without a GPU) and the device build of the SAME source with plain
 // Python integer arithmetic.  Built beside the library by tapstark_amd.build (lib/field_probe).
@@ -56,7 +57,18 @@ enum Op : uint32_t {
     // device only: v[16], W[16] -> v[16]; radix_butterflies<4, INV, TOP>(v, 0, 0, 0, 0, W)
     OP_BFLY = 32,       // + (INV ? 1 : 0) + (TOP ? 2 : 0)
     OP_BFLY_END = 36,
+    // the Plantard product (bb.hpp), host and device
+    OP_PLANT_CONSTS = 40,  // 1 -> 2   P_INV64 lo, hi
+    OP_PLANT_CONST = 41,   // w -> 2   plant_const(w) lo, hi
+    OP_PLANT_MUL = 42,     // a, w -> 1   plant_mul(a, plant_const(w))
+    // device only: v[16], W'[16] as {lo, hi} pairs -> v[16]; radix_butterflies<4, INV, TOP>(v, 0, 0, 0, 0, W') on the
+    // Plantard table type
+    OP_PLANT_BFLY = 48,    // + (INV ? 1 : 0) + (TOP ? 2 : 0)
+    OP_PLANT_BFLY_END = 52,
 };
+constexpr bool device_only(uint32_t op) {
+    return (op >= OP_BFLY && op < OP_BFLY_END) || (op >= OP_PLANT_BFLY && op < OP_PLANT_BFLY_END);
+}
 
 struct Shape {
     uint32_t n_in, n_out;
@@ -75,7 +87,12 @@ TS_HD Shape shape_of(uint32_t op) {
         case OP_EF_INV_PARTS: return {4, 5};
         case OP_EF_POW: return {6, 4};
         case OP_POW_CANON: case OP_MONT_POW: return {3, 1};
-        default: return (op >= OP_BFLY && op < OP_BFLY_END) ? Shape{32, 16} : Shape{0, 0};
+        case OP_PLANT_CONSTS: case OP_PLANT_CONST: return {1, 2};
+        case OP_PLANT_MUL: return {2, 1};
+        default:
+            return (op >= OP_BFLY && op < OP_BFLY_END)               ? Shape{32, 16}
+                   : (op >= OP_PLANT_BFLY && op < OP_PLANT_BFLY_END) ? Shape{48, 16}
+                                                                     : Shape{0, 0};
     }
 }
 
@@ -135,6 +152,14 @@ TS_HD void apply(uint32_t op, const uint32_t* in, uint32_t* out) {
         case OP_TWO_ADIC_GEN: out[0] = two_adic_generator(in[0]); break;
         case OP_POW_CANON: out[0] = pow_canon(in[0], u64_at(in + 1)); break;
         case OP_MONT_POW: out[0] = mont_pow(in[0], u64_at(in + 1)); break;
+        case OP_PLANT_CONSTS: out[0] = (uint32_t)P_INV64; out[1] = (uint32_t)(P_INV64 >> 32); break;
+        case OP_PLANT_CONST: {
+            const uint64_t w = plant_const(in[0]);
+            out[0] = (uint32_t)w;
+            out[1] = (uint32_t)(w >> 32);
+            break;
+        }
+        case OP_PLANT_MUL: out[0] = plant_mul(in[0], plant_const(in[1])); break;
         default: break;
     }
 }
@@ -154,6 +179,18 @@ __global__ void __launch_bounds__(256) k_probe_bfly(const uint32_t* __restrict__
     uint32_t v[16];
     for (int q = 0; q < 16; q++) v[q] = in[(size_t)i * 32 + q];
     radix_butterflies<4, INV, TOP>(v, 0, 0, 0, 0, in + (size_t)i * 32 + 16);
+    for (int q = 0; q < 16; q++) out[(size_t)i * 16 + q] = v[q];
+}
+
+template <bool INV, bool TOP>
+__global__ void __launch_bounds__(256) k_probe_plant_bfly(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                          uint32_t count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    uint32_t v[16];
+    for (int q = 0; q < 16; q++) v[q] = in[(size_t)i * 48 + q];
+    // 48 words an item, the table 16 words in: 8-byte aligned
+    radix_butterflies<4, INV, TOP>(v, 0, 0, 0, 0, reinterpret_cast<const uint2*>(in + (size_t)i * 48 + 16));
     for (int q = 0; q < 16; q++) out[(size_t)i * 16 + q] = v[q];
 }
 
@@ -196,6 +233,10 @@ int run_device(uint32_t op, const uint32_t* in, uint32_t* out, uint32_t count, S
         case OP_BFLY + 1: k_probe_bfly<true, false><<<grid, block>>>(d_in, d_out, count); break;
         case OP_BFLY + 2: k_probe_bfly<false, true><<<grid, block>>>(d_in, d_out, count); break;
         case OP_BFLY + 3: k_probe_bfly<true, true><<<grid, block>>>(d_in, d_out, count); break;
+        case OP_PLANT_BFLY + 0: k_probe_plant_bfly<false, false><<<grid, block>>>(d_in, d_out, count); break;
+        case OP_PLANT_BFLY + 1: k_probe_plant_bfly<true, false><<<grid, block>>>(d_in, d_out, count); break;
+        case OP_PLANT_BFLY + 2: k_probe_plant_bfly<false, true><<<grid, block>>>(d_in, d_out, count); break;
+        case OP_PLANT_BFLY + 3: k_probe_plant_bfly<true, true><<<grid, block>>>(d_in, d_out, count); break;
         default: k_probe<<<grid, block>>>(op, d_in, d_out, count, sh.n_in, sh.n_out); break;
     }
     HIP_OR_FAIL(hipGetLastError());
@@ -249,7 +290,7 @@ int main(int argc, char** argv) {
                     in[pos + 2], in[pos + 3]);
             return 2;
         }
-        if (host && op >= N_SCALAR_OPS) {
+        if (host && device_only(op)) {
             fprintf(stderr, "field_probe: record %u: op %u exists in the device build only\n", r, op);
             return 2;
         }
