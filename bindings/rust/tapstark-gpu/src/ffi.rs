@@ -147,6 +147,18 @@ pub struct ts_batch_lane {
     pub key_values: *const ts_matrix, // may be null
 }
 
+/// One table of `ts_prove_multi`: a plain AIR (no preprocessed, no aux columns), its trace (consumed) and its
+/// public values.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ts_multi_table {
+    pub struct_size: u32, // = size_of::<ts_multi_table>()
+    pub n_public: u32,
+    pub air: *const ts_air,
+    pub trace: *mut ts_matrix,
+    pub public_values: *const u32,
+}
+
 /// One statement of `ts_prove_batch_lookup`: `ts_batch_item`'s inputs, the aux source (exactly one of `logup` /
 /// `aux_fn` for an AIR with aux columns), the multiplicity fills, then what the library writes back.
 #[repr(C)]
@@ -339,6 +351,14 @@ extern "C" {
                              preprocessed_root: *const u32, proof: *const u32, n_words: usize,
                              public_values: *const u32, n_public: u32, exposed_out: *mut u32, cap_exposed: u32,
                              verdict: *mut c_int) -> ts_status;
+    /// several plain AIR tables of mixed heights in one proof (TSPF v6): one trace commit, one chunk commit, one FRI
+    pub fn ts_prove_multi(ctx: *mut ts_ctx, cfg: *const ts_fri_config, chal: *mut ts_challenger,
+                          tables: *mut ts_multi_table, n_tables: u32, proof_out: *mut u32, cap_words: usize,
+                          n_words_out: *mut usize) -> ts_status;
+    /// host only; verdict codes as ts_verify
+    pub fn ts_verify_multi(cfg: *const ts_fri_config, chal: *mut ts_challenger, airs: *const *const ts_air,
+                           n_tables: u32, public_values: *const *const u32, n_public: *const u32, proof: *const u32,
+                           n_words: usize, verdict: *mut c_int) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

@@ -83,6 +83,64 @@ where
     Proof::from_tspf(&out[..n])
 }
 
+/// One table of `prove_gpu_multi`: a compiled plain AIR (no preprocessed, no aux columns), its trace on the AIR's
+/// context (consumed) and its public values as canonical words.
+pub struct MultiTable<'a> {
+    pub air: &'a CompiledAir<'a>,
+    pub trace: DeviceMatrix<'a>,
+    pub public_values: Vec<u32>,
+}
+
+/// Several AIR tables of mixed heights in ONE proof (`ts_prove_multi`): the TSPF v6 words, for
+/// `verify_gpu_multi`.  The challenger observes the table count and every log-degree first, so it ends where the
+/// verifier's will.
+pub fn prove_gpu_multi(pcs: &GpuFriPcs<'_>, challenger: &mut GpuChallenger, tables: Vec<MultiTable<'_>>) -> Vec<u32> {
+    let ctx = pcs.ctx;
+    let cfg = pcs.fri.raw();
+    let pis: Vec<Vec<u32>> = tables.iter().map(|t| t.public_values.clone()).collect();
+    let airs: Vec<*const ts_air> = tables.iter().map(|t| t.air.raw as *const ts_air).collect();
+    let raws: Vec<*mut ts_matrix> = tables.into_iter().map(|t| t.trace.into_raw()).collect();
+    let mut raw_tables: Vec<ts_multi_table> = (0..raws.len())
+        .map(|t| ts_multi_table {
+            struct_size: core::mem::size_of::<ts_multi_table>() as u32,
+            n_public: pis[t].len() as u32,
+            air: airs[t],
+            trace: raws[t],
+            public_values: if pis[t].is_empty() { ptr::null() } else { pis[t].as_ptr() },
+        })
+        .collect();
+    // the call consumes the traces, so the buffer is sized generously rather than asked for in a first call
+    // (TS_ERR_BUFFER would report the size, with the traces gone)
+    let mut out = vec![0u32; 1 << 22];
+    let mut n = 0usize;
+    let rc = unsafe {
+        ts_prove_multi(ctx.raw, &cfg, challenger.raw, raw_tables.as_mut_ptr(), raw_tables.len() as u32,
+                       out.as_mut_ptr(), out.len(), &mut n)
+    };
+    for m in raws {
+        unsafe { ts_matrix_free(ctx.raw, m) };
+    }
+    ctx.check(rc, "ts_prove_multi");
+    out.truncate(n);
+    out
+}
+
+/// `ts_verify_multi` (host only): the verdict, 0 = accepted, codes as `ts_verify`.
+pub fn verify_gpu_multi(fri: FriConfig, challenger: &mut GpuChallenger, airs: &[&CompiledAir<'_>],
+                        public_values: &[Vec<u32>], proof: &[u32]) -> i32 {
+    let cfg = fri.raw();
+    let raw_airs: Vec<*const ts_air> = airs.iter().map(|a| a.raw as *const ts_air).collect();
+    let ptrs: Vec<*const u32> =
+        public_values.iter().map(|p| if p.is_empty() { ptr::null() } else { p.as_ptr() }).collect();
+    let counts: Vec<u32> = public_values.iter().map(|p| p.len() as u32).collect();
+    let mut verdict: std::os::raw::c_int = -1;
+    let rc = unsafe {
+        ts_verify_multi(&cfg, challenger.raw, raw_airs.as_ptr(), raw_airs.len() as u32, ptrs.as_ptr(),
+                        counts.as_ptr(), proof.as_ptr(), proof.len(), &mut verdict)
+    };
+    if rc != 0 { -1 } else { verdict as i32 }
+}
+
 /// A stream of proofs from HOST traces at the PCIe-inclusive rate (INTEGRATION.md "Three rates").
 ///
 /// `prove_gpu` above uploads synchronously from pageable memory: the GPU idles during the copy and

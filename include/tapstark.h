@@ -1008,6 +1008,56 @@ ts_status ts_prove_batch_lookup(ts_ctx* const* ctxs, const ts_air* const* airs, 
                                 uint32_t n_lanes, const ts_fri_config* cfg, ts_batch_lookup_item* items,
                                 uint32_t n_items, double gate_ms, uint32_t flags);
 
+/* ---- several AIR tables of mixed heights in ONE proof ---------------------------------------------------
+ * A statement made of T chips of different heights (a CPU table, a memory table, a byte table ...) proved with one
+ * FRI commit phase, one proof-of-work grind and one set of queries instead of T of each.  Plain AIRs only: tape
+ * version 1, or a later version with preprocessed width 0 and aux width 0.  Build-defined (the reference proves
+ * one table).  Transcript:
+ *   1. observe the word T = n_tables, then log_degree_t for t = 0 .. T-1, as base words (ts_chal_observe): the
+ *      heights are bound before anything is committed;
+ *   2. ONE commit of all T traces on their natural domains, in table order (heights in any order, repeats
+ *      allowed); observe the root; sample alpha;
+ *   3. the quotient chunks of every table over that table's LDE in the batch, with its own public values and its
+ *      constraints folded from alpha^0: chunk c of table t is what ts_quotient_chunks gives for that trace
+ *      committed alone;
+ *   4. ONE commit of all chunks of all tables, table-major and chunk-minor, chunk c of table t on the coset of
+ *      its own split domain (as ts_prove shifts the chunks of one table); observe the root; sample zeta;
+ *   5. two rounds opened as ts_pcs_open opens them (the batch challenge is sampled first): trace matrix t at
+ *      {zeta, zeta * omega_{n_t}}, every chunk at {zeta};
+ *   6. the FriProof, exactly as ts_pcs_open writes it for those two rounds.
+ * Proof = TSPF v6: [magic, 6, T], T x [log_degree, width, qd], trace root, quotient root, the opened values in
+ * ts_pcs_open's (round, matrix, point, column) order, the FriProof words.  v6 has no postcard form
+ * (TS_ERR_UNSUPPORTED), and every other verify call answers a v6 proof with verdict 9.
+ * Refusals, all before any trace is consumed and each with a text in ts_last_error:
+ *   TS_ERR_INVALID      a null argument; n_tables 0 or above 64; a struct_size other than sizeof(ts_multi_table);
+ *                       a trace or AIR of another context; a consumed trace; a width or n_public that is not the
+ *                       AIR's; one trace handle in two tables; more than 64 quotient chunks over all tables
+ *   TS_ERR_UNSUPPORTED  a table whose AIR has preprocessed or aux columns
+ *   TS_ERR_INVARIANT    log_quotient_degree > log_blowup for some table
+ * TS_ERR_BUFFER sets *n_words_out to the size needed, as ts_prove does (the traces are consumed then).  A trace
+ * that violates its constraints gets the status ts_prove gives that table alone.
+ * TS_MULTI_OPEN_GENERIC=1 in the environment (read on every call; a test and measurement knob) routes step 5
+ * through the generic opening of ts_pcs_open instead of the one-pass-per-height kernels; the proof is the same. */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(ts_multi_table), else the whole call is TS_ERR_INVALID */
+    uint32_t n_public;
+    const ts_air* air;             /* compiled on ctx; preprocessed_width == 0 and aux_width == 0 */
+    ts_matrix* trace;              /* made on ctx; consumed */
+    const uint32_t* public_values;
+} ts_multi_table;
+ts_status ts_prove_multi(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal,
+                         ts_multi_table* tables, uint32_t n_tables,
+                         uint32_t* proof_out, size_t cap_words, size_t* n_words_out);
+/* host only (AIRs compiled with a NULL context serve).  Parses TSPF v6, replays the transcript above, runs per
+ * table the out-of-domain check of ts_verify on that table's domain (selectors at zeta, the quotient recomposed
+ * from its chunks), then ts_pcs_verify over the two rounds.  Verdict codes as ts_verify: a header that disagrees
+ * with the AIRs in T, a width or a qd is 1, a truncated or over-long buffer 9.  public_values[t] may be NULL
+ * where n_public[t] == 0.  Reads nothing outside proof[0 .. n_words). */
+ts_status ts_verify_multi(const ts_fri_config* cfg, ts_challenger* chal,
+                          const ts_air* const* airs, uint32_t n_tables,
+                          const uint32_t* const* public_values, const uint32_t* n_public,
+                          const uint32_t* proof, size_t n_words, int* verdict);   /* host only */
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

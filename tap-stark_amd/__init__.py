@@ -6,3 +6,4 @@ from .air import (BaseAir, ExtExpr, LogUp, SymbolicAirBuilder, air_tape, get_log
 from .stark import (BatchLookupResult, BatchResult, BfChallenger, Blake3Mmcs, CompiledAir, Context, DeviceMatrix, FriConfig, PcsData, PinnedHostBytes, PreprocessedKey, PinnedHostMatrix,  # noqa: F401
                     Proof, Radix2Dft, StarkConfig, TraceFormat, TwoAdicFriPcs, VerificationError, check_constraints,
                     default_context, prove, prove_batch, prove_batch_lookup, prove_sharded, prove_stream, verify, verify_pre_aux)
+from .stark import MultiProof, MultiTableOpening, prove_multi, verify_multi  # noqa: F401

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "ts_logup_multiplicities",
     "ts_prove_pre_aux", "ts_verify_pre_aux", "ts_quotient_chunks_pre_aux", "ts_check_constraints_pre_aux",
     "ts_prove_batch_lookup",
+    "ts_prove_multi", "ts_verify_multi",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -144,6 +145,12 @@ AUX_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_
 class BatchLaneC(C.Structure):
     """``ts_batch_lane``: what a lane of ``ts_prove_batch_lookup`` owns for all of its items."""
     _fields_ = [("struct_size", C.c_uint32), ("key", C.c_void_p), ("key_values", C.c_void_p)]
+
+
+class MultiTableC(C.Structure):
+    """``ts_multi_table``: one table of ``ts_prove_multi``."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_public", C.c_uint32), ("air", C.c_void_p), ("trace", C.c_void_p),
+                ("public_values", C.POINTER(C.c_uint32))]
 
 
 class BatchLookupItemC(C.Structure):
@@ -356,6 +363,10 @@ def lib() -> C.CDLL:
         l.ts_prove_batch_lookup.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(BatchLaneC),
                                             C.c_uint32, C.POINTER(FriConfigC), C.POINTER(BatchLookupItemC),
                                             C.c_uint32, C.c_double, C.c_uint32]
+        l.ts_prove_multi.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.c_void_p, C.POINTER(MultiTableC),
+                                     C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
+        l.ts_verify_multi.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32,
+                                      C.POINTER(u32p), u32p, u32p, C.c_size_t, C.POINTER(C.c_int)]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

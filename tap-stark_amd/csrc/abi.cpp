@@ -395,6 +395,8 @@ ts_status ts_proof_to_postcard(const uint32_t* proof, size_t n_words, uint8_t* o
                    "TSPF v4 proofs (ts_prove_aux) have no postcard form");
         TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 5), ts::TS_ERR_UNSUPPORTED,
                    "TSPF v5 proofs (ts_prove_pre_aux) have no postcard form");
+        TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 6), ts::TS_ERR_UNSUPPORTED,
+                   "TSPF v6 proofs (ts_prove_multi) have no postcard form");
         TS_REQUIRE(ts::tspf_to_postcard(proof, n_words, b), ts::TS_ERR_INVALID, "not a TSPF v1 proof");
         *n_bytes_out = b.size();
         TS_REQUIRE(b.size() <= cap_bytes, ts::TS_ERR_BUFFER, "postcard buffer too small");
@@ -1252,6 +1254,72 @@ ts_status ts_prove_pre(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
         copy_proof(ts::prove(pcs, ready_prog(air), chal->c, std::move(m), pis, key, 3), proof_out, cap_words,
                    n_words_out);
     });
+}
+
+// ------------------------------------------------------------------ prove_multi
+// Several plain AIR tables of mixed heights in one proof (prove_multi.cpp).  Every refusal is made before the
+// first trace is taken.
+ts_status ts_prove_multi(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_table* tables,
+                         uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    if (!ctx) return TS_ERR_INVALID;
+    if (n_words_out) *n_words_out = 0;
+    return guard(ctx, [&] {
+        TS_REQUIRE(cfg && chal && tables && proof_out && n_words_out, ts::TS_ERR_INVALID, "ts_prove_multi: null argument");
+        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+                   "ts_prove_multi: between 1 and 64 tables");
+        const ts::FriConfig fri = load_cfg(cfg);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            const ts_multi_table& mt = tables[t];
+            TS_REQUIRE(mt.struct_size == sizeof(ts_multi_table), ts::TS_ERR_INVALID,
+                       "ts_prove_multi: ts_multi_table.struct_size is not sizeof(ts_multi_table)");
+            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, "ts_prove_multi: null AIR or trace");
+            TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
+                       "ts_prove_multi: an AIR was compiled on another context (or host-only)");
+            TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+            TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
+                       "ts_prove_multi: a trace was made on another context");
+            for (uint32_t k = 0; k < t; k++)
+                TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID,
+                           "ts_prove_multi: one trace handle in two tables");
+        }
+        // the statement's own refusals (widths, public values, UNSUPPORTED columns, lqd, the chunk count) on
+        // shapes alone: the matrices stay with their handles until all of it holds
+        std::vector<ts::MultiTable> mts(n_tables);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            mts[t].air = &ready_prog(tables[t].air);
+            mts[t].public_values = public_inputs(tables[t].public_values, tables[t].n_public);
+            mts[t].trace.width = tables[t].trace->m.width;
+            mts[t].trace.height = tables[t].trace->m.height;
+        }
+        ts::check_multi_statement(fri, mts);
+        ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
+        for (uint32_t t = 0; t < n_tables; t++) mts[t].trace = take_trace(tables[t].trace);
+        ts::StageTimer timer(&ctx->ctx, "prove");
+        copy_proof(ts::prove_multi(pcs, chal->c, mts), proof_out, cap_words, n_words_out);
+    });
+}
+
+ts_status ts_verify_multi(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
+                          const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,
+                          size_t n_words, int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(cfg && chal && airs && public_values && n_public && proof && verdict, ts::TS_ERR_INVALID,
+                   "ts_verify_multi: null argument");
+        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+                   "ts_verify_multi: between 1 and 64 tables");
+        const ts::FriConfig fri = load_cfg(cfg);
+        std::vector<const ts::AirProgram*> progs(n_tables);
+        std::vector<std::vector<uint32_t>> pis(n_tables);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, "ts_verify_multi: null AIR");
+            if (airs[t]->a.prog().preprocessed_width || airs[t]->a.prog().aux_width)
+                throw ts::Error(ts::TS_ERR_UNSUPPORTED, "ts_verify_multi: a table's AIR has preprocessed or aux columns");
+            progs[t] = &airs[t]->a.prog();
+            pis[t] = public_inputs(public_values[t], n_public[t]);
+        }
+        *verdict = ts::verify_multi(fri, chal->c, progs, pis, proof, n_words);
+    }, false);
 }
 
 // ------------------------------------------------------------------ prove_stream

@@ -41,6 +41,7 @@ public:
     }
     bool is_specialised() { return ready().jit.load() != nullptr; }
     const AirProgram& prog() const { return prog_; }
+    const Context* context() const { return code_.ctx; }  // the context it was compiled on; null: host-only
     const SegmentPlan* seg() const { return seg_.get(); }
     std::string source() const;  // the HIP source of the whole specialisation, as one module
 

@@ -200,6 +200,27 @@ void check_third_matrix(const PcsData& aux, const AirProgram& air, uint64_t lde_
 // throws TS_ERR_INVALID unless `key` holds exactly one matrix of the AIR's preprocessed width and that LDE height
 void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height);
 
+// ------------------------------------------------------------------ prove, several tables in one proof
+// Build-defined (the reference proves one table; prove_multi.cpp): T plain AIRs (no
+// preprocessed, no aux columns) of any heights share one trace commitment, one alpha, one commitment to all
+// quotient chunks, one zeta and ONE opening -- one FRI commit phase, one grind, one set of queries.  TSPF v6.
+constexpr uint32_t MAX_MULTI_TABLES = 64;
+struct MultiTable {
+    const AirProgram* air = nullptr;
+    DeviceMatrix trace;  // consumed
+    std::vector<uint32_t> public_values;
+};
+// throws what prove() throws for a table alone (check_statement), TS_ERR_UNSUPPORTED for an AIR with preprocessed
+// or aux columns, TS_ERR_INVALID for more than 64 tables or chunks; nothing is consumed before these checks
+void check_multi_statement(const FriConfig& fri, const std::vector<MultiTable>& tables);
+std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiTable>& tables);
+// TS_MULTI_OPEN_GENERIC=1 (read on every call; a test and measurement knob): prove_multi opens through
+// TwoAdicFriPcs::open instead of the per-class kernels.  Same proof.
+bool multi_open_generic();
+// host only; verdict codes as verify()
+int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
+                 const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words);
+
 // ------------------------------------------------------------------ prove, one proof over G GPUs
 // Collectives the sharded prover needs, supplied by the host (torch.distributed over RCCL in
 // tap-stark_amd/dist.py).  Buffers are device memory; the call is ordered on `stream`: the callee

@@ -264,6 +264,39 @@ void launch_reduce_low(Context& ctx, const ColMat& trace, unsigned log_n, const 
 // out[X] = (cols[k * col_stride + X])_{k < 4}, X < rows
 void launch_ef_interleave(Context& ctx, const uint32_t* cols, uint64_t col_stride, uint64_t rows, Ef* out);
 
+// ---- open_multi.hip --------------------------------------------------------------------------
+// The opening of a multi-table proof (prove_multi.cpp), one pass per height class: every committed matrix of
+// LDE height 2^log_h, of both rounds, is opened at z0 = zeta, and the trace matrices among them at
+// z1 = zeta omega_n as well.  One matrix of a class, as the kernel reads it from a table in device memory:
+struct ClassJob {
+    const uint32_t* d;       // column-major, bit-reversed rows, 2^log_h of them
+    uint64_t col_stride;
+    uint32_t width;
+    uint32_t has_next;       // 1: a trace matrix, opened at both points; 0: a quotient chunk, at z0 only
+    // has_next: the column weights are the alpha powers and off[p] = alpha^num_reduced at its (matrix, point)
+    // visit (two_adic_pcs.rs:371,383; Montgomery).  Otherwise `weights` holds alpha^k off_0 per column k
+    // (device memory, Montgomery, 4 words each): the chunks of a class then cost one dot product in all.
+    const uint32_t* weights;
+    Ef off[2];
+};
+struct ClassReduceArgs {
+    Ef z_mont[2];
+    Ef k0, k1;  // sum over the class of off_p * reduced_ys_p (canonical), folded on the host
+};
+// ro[X] = inv(x_X - z0) (sum_m off_{m,0} S_m(X) - k0) + inv(x_X - z1) (sum_{m trace} off_{m,1} S_m(X) - k1) for
+// every row X of the class; one store per row, `ro` is never read.  d_jobs: n_jobs >= 1 entries, device memory.
+void launch_reduce_class(Context& ctx, const ClassJob* d_jobs, uint32_t n_jobs, unsigned log_h,
+                         const uint32_t* d_alpha_pows_mont, const ClassReduceArgs& args, Ef* ro);
+// The finishing pass of any number of launch_bary_dots products in one launch (k_bary_finish / 3 / 4 take up to
+// four by value): out[j] = sum over blocks of partial[block][j].  d_jobs: the jobs; d_groups: per workgroup
+// {job, group of four output words within it}; both device memory.
+struct BaryFinishJob {
+    const uint32_t* partial;
+    uint32_t* out;
+    uint32_t n_blocks, n_words;
+};
+void launch_bary_finish_jobs(Context& ctx, const BaryFinishJob* d_jobs, const uint2* d_groups, uint32_t n_groups);
+
 // ---- fri.hip ---------------------------------------------------------------------------------
 // out[i] = fold(in[2i], in[2i+1]; beta) (reference two_adic_pcs.rs:116-147); h = output length.
 // If next_digests != nullptr (h >= 2) also writes the h/2 leaf digests of the next round.

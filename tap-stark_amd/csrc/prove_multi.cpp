@@ -1,0 +1,305 @@
+// prove_multi: T plain AIR tables of mixed heights in one proof.  Build-defined (the reference's prove takes one
+// trace, uni-stark/src/prover.rs:25-119); every stage is the single-table prover's, batched:
+//   1. observe T, then log_degree_t for every table (base words): the heights are part of the statement
+//   2. ONE commit of all traces on their natural domains, table order (two_adic_pcs.rs:227-245 takes mixed
+//      heights); observe the root; sample alpha
+//   3. per table the quotient chunks over that table's LDE inside the batch, constraints folded from alpha^0
+//   4. ONE commit of all chunks, table-major, chunk-minor, chunk c of table t on chunk_domain_shifts(31,
+//      log_degree_t, lqd_t)[c]; observe the root; sample zeta
+//   5. Pcs::open over two rounds: trace t at {zeta, zeta omega_{n_t}}, every chunk at {zeta}
+// Proof = TSPF v6.  Step 5 runs one pass per height class (open_multi.hip) or, with
+// TS_MULTI_OPEN_GENERIC=1, TwoAdicFriPcs::open; the words are the same.
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+
+#include "prover_internal.hpp"
+
+namespace ts {
+
+bool multi_open_generic() {
+    const char* e = getenv("TS_MULTI_OPEN_GENERIC");
+    return e && *e && atoi(e) != 0;
+}
+
+void check_multi_statement(const FriConfig& fri, const std::vector<MultiTable>& tables) {
+    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
+               "prove_multi: between 1 and 64 tables");
+    uint32_t n_chunks = 0;
+    for (const MultiTable& t : tables) {
+        TS_REQUIRE(t.air, TS_ERR_INVALID, "prove_multi: null AIR");
+        TS_REQUIRE(t.air->preprocessed_width == 0 && t.air->aux_width == 0, TS_ERR_UNSUPPORTED,
+                   "prove_multi: a table's AIR has preprocessed or challenge-phase (aux) columns; only plain AIRs "
+                   "share a multi-table proof");
+        n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
+    }
+    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
+               "prove_multi: more than 64 quotient chunks over all tables (the limit of one committed batch)");
+}
+
+namespace {
+
+// one committed matrix of the two rounds, in the visiting order of TwoAdicFriPcs::open: round, matrix
+struct OpenMat {
+    const ColMat* m;
+    unsigned log_n;
+    bool trace;    // opened at zeta omega_n as well
+    size_t first;  // of its opened values (and of its raw sums) in (round, matrix, point, column) order
+};
+
+// Step 5 on the per-class kernels: the opened values of every matrix with ONE host wait, then one
+// k_reduce_class launch per LDE height.  `batch_alpha` is already sampled.
+void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta, Ef batch_alpha,
+                  std::vector<Ef>& opened, std::vector<DevBuf<Ef>>& inputs, std::vector<unsigned>& log_lens) {
+    Context& ctx = pcs.ctx();
+    const unsigned log_blowup = pcs.fri().log_blowup;
+    size_t n_opened = 0;
+    uint32_t max_w = 4;
+    for (const OpenMat& om : mats) {
+        n_opened = om.first + (size_t)om.m->width * (om.trace ? 2 : 1);
+        max_w = std::max(max_w, om.m->width);
+    }
+
+    // ---- opened values: barycentric interpolation on each matrix's low coset (two_adic_pcs.rs:358-369)
+    struct Points { Ef z[2]; Ef scale[2]; DevBuf<Ef> weights; };
+    std::map<unsigned, Points> by_log_n;  // one weight table per trace height, two points each
+    std::vector<Ef> raw(n_opened);
+    {
+        StageTimer t(&ctx, "compute opened values with Lagrange interpolation");
+        for (const OpenMat& om : mats) {
+            if (by_log_n.count(om.log_n)) continue;
+            Points& pt = by_log_n[om.log_n];
+            const uint64_t n = 1ull << om.log_n;
+            pt.z[0] = zeta;
+            pt.z[1] = efc_mul_base(zeta, two_adic_generator(om.log_n));  // prover.rs:92 next_point
+            for (int p = 0; p < 2; p++) pt.scale[p] = bary_scale(pt.z[p], GENERATOR, n);
+            const Ef pts_mont[2] = {ef_to_mont(pt.z[0]), ef_to_mont(pt.z[1])};
+            pt.weights = DevBuf<Ef>(&ctx, 2 * n);
+            launch_bary_weights(ctx, om.log_n, pts_mont, 2, pt.weights.p);
+        }
+        // every finishing job writes its sums straight into the context's mailbox (host memory)
+        Ef* const mail = reinterpret_cast<Ef*>(ctx.mailbox(4 * n_opened));
+        std::vector<DevBuf<uint32_t>> partials;
+        std::vector<BaryFinishJob> jobs;
+        std::vector<uint2> groups;
+        for (const OpenMat& om : mats) {
+            BaryPending pend;  // the dot kernel's partial sums are taken over, its own finishing pass is not run
+            launch_bary_dots(ctx, *om.m, om.log_n, by_log_n[om.log_n].weights.p, om.trace ? 2 : 1, mail + om.first,
+                             &pend);
+            jobs.push_back(BaryFinishJob{pend.partial[0].p, pend.out[0], pend.n_blocks[0], pend.n_words[0]});
+            for (uint32_t g = 0; g < (pend.n_words[0] + 3) / 4; g++)
+                groups.push_back(make_uint2((uint32_t)jobs.size() - 1, g));
+            partials.push_back(std::move(pend.partial[0]));
+            pend.n = 0;
+        }
+        // both tables in one upload
+        static_assert(sizeof(BaryFinishJob) % sizeof(uint2) == 0, "the group table follows the jobs, aligned");
+        std::vector<char> tab(jobs.size() * sizeof(BaryFinishJob) + groups.size() * sizeof(uint2));
+        memcpy(tab.data(), jobs.data(), jobs.size() * sizeof(BaryFinishJob));
+        memcpy(tab.data() + jobs.size() * sizeof(BaryFinishJob), groups.data(), groups.size() * sizeof(uint2));
+        DevBuf<uint64_t> d_tab(&ctx, tab.size() / 8);
+        h2d(ctx, d_tab.p, tab.data(), tab.size());
+        launch_bary_finish_jobs(ctx, reinterpret_cast<const BaryFinishJob*>(d_tab.p),
+                                reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(d_tab.p) +
+                                                               jobs.size() * sizeof(BaryFinishJob)),
+                                (uint32_t)groups.size());
+        ctx.sync_point(mail, n_opened * sizeof(Ef));
+        memcpy((void*)raw.data(), mail, n_opened * sizeof(Ef));
+    }
+    // p(z) = ((z/31)^n - 1)/n * sum_i p_i x_i/(z - x_i); the dot kernel left [col][point]
+    opened.assign(n_opened, ef_zero());
+    for (const OpenMat& om : mats) {
+        const Points& pt = by_log_n[om.log_n];
+        const uint32_t w = om.m->width;
+        Ef* const ov = opened.data() + om.first;
+        const Ef* const rw = raw.data() + om.first;
+        for (uint32_t c = 0; c < w; c++) {
+            if (om.trace) {
+                ov[c] = efc_mul(rw[2 * c], pt.scale[0]);          // local
+                ov[w + c] = efc_mul(rw[2 * c + 1], pt.scale[1]);  // next
+            } else {
+                ov[c] = efc_mul(rw[c], pt.scale[0]);
+            }
+        }
+    }
+
+    // ---- reduce (two_adic_pcs.rs:371-383), one launch per height class
+    StageTimer t(&ctx, "reduce rows");
+    std::vector<uint32_t> apow = alpha_powers_mont(batch_alpha, max_w);
+    const size_t n_apow = apow.size();
+    const Ef am = ef_to_mont(batch_alpha);
+    auto reduced_ys = [&](const Ef* ys, uint32_t width) {  // dot_product(alpha.powers(), ys), :372
+        Ef acc = ef_zero();
+        for (uint32_t i = 0; i < width; i++) {
+            Ef ap;
+            memcpy(ap.c, &apow[4 * (size_t)i], 16);
+            acc = ef_add(acc, ef_mul(ys[i], ap));  // canonical x Montgomery -> canonical
+        }
+        return acc;
+    };
+    struct Class {
+        std::vector<ClassJob> jobs;
+        std::vector<size_t> weights_at;  // per job: word offset of its folded weights behind the alpha powers
+        uint64_t num_reduced = 0;        // :332, grows by the width after every (matrix, point)
+        ClassReduceArgs args;
+    };
+    std::map<unsigned, Class> classes;  // by LDE log-height
+    std::vector<uint32_t> folded;       // alpha^k off_0 per chunk column
+    for (const OpenMat& om : mats) {
+        const unsigned log_h = om.log_n + log_blowup;
+        const bool fresh = !classes.count(log_h);
+        Class& cl = classes[log_h];
+        if (fresh) {
+            const Points& pt = by_log_n[om.log_n];
+            cl.args.z_mont[0] = ef_to_mont(pt.z[0]);
+            cl.args.z_mont[1] = ef_to_mont(pt.z[1]);
+            cl.args.k0 = cl.args.k1 = ef_zero();
+        }
+        const uint32_t w = om.m->width;
+        ClassJob j;
+        memset(&j, 0, sizeof j);
+        j.d = om.m->d;
+        j.col_stride = om.m->col_stride;
+        j.width = w;
+        j.has_next = om.trace ? 1 : 0;
+        j.off[0] = ef_pow(am, cl.num_reduced);  // :371
+        cl.args.k0 = ef_add(cl.args.k0, ef_mul(reduced_ys(&opened[om.first], w), j.off[0]));
+        cl.num_reduced += w;  // :383
+        size_t at = 0;
+        if (om.trace) {
+            j.off[1] = ef_pow(am, cl.num_reduced);
+            cl.args.k1 = ef_add(cl.args.k1, ef_mul(reduced_ys(&opened[om.first + w], w), j.off[1]));
+            cl.num_reduced += w;
+        } else {
+            at = n_apow + folded.size();
+            for (uint32_t k = 0; k < w; k++) {  // alpha^k off_0: the weight of column k
+                Ef ap;
+                memcpy(ap.c, &apow[4 * (size_t)k], 16);
+                const Ef wk = ef_mul(ap, j.off[0]);
+                folded.insert(folded.end(), wk.c, wk.c + 4);
+            }
+        }
+        cl.jobs.push_back(j);
+        cl.weights_at.push_back(at);
+    }
+    apow.insert(apow.end(), folded.begin(), folded.end());
+    DevBuf<uint32_t> d_apow(&ctx, apow.size());
+    h2d(ctx, d_apow.p, apow.data(), apow.size() * 4);
+    std::vector<ClassJob> all_jobs;
+    for (auto& [log_h, cl] : classes)
+        for (size_t k = 0; k < cl.jobs.size(); k++) {
+            if (!cl.jobs[k].has_next) cl.jobs[k].weights = d_apow.p + cl.weights_at[k];
+            all_jobs.push_back(cl.jobs[k]);
+        }
+    DevBuf<ClassJob> d_jobs(&ctx, all_jobs.size());
+    h2d(ctx, d_jobs.p, all_jobs.data(), all_jobs.size() * sizeof(ClassJob));
+    // :389-393 fri_input: the reduced openings by descending height
+    std::vector<size_t> first_job;
+    size_t at = 0;
+    for (auto& [log_h, cl] : classes) {
+        first_job.push_back(at);
+        at += cl.jobs.size();
+    }
+    size_t ci = classes.size();
+    for (auto it = classes.rbegin(); it != classes.rend(); ++it) {
+        ci--;
+        const unsigned log_h = it->first;
+        DevBuf<Ef> ro(&ctx, 1ull << log_h);
+        launch_reduce_class(ctx, d_jobs.p + first_job[ci], (uint32_t)it->second.jobs.size(), log_h, d_apow.p,
+                            it->second.args, ro.p);
+        inputs.push_back(std::move(ro));
+        log_lens.push_back(log_h);
+    }
+}
+
+}  // namespace
+
+std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiTable>& tables) {
+    check_multi_statement(pcs.fri(), tables);
+    const size_t T = tables.size();
+    std::vector<Statement> st;
+    unsigned log_max = 0;
+    for (const MultiTable& t : tables) {
+        st.push_back(check_statement(pcs.fri(), *t.air, t.trace.width, t.trace.height, t.public_values.size()));
+        log_max = std::max(log_max, st.back().log_N);
+    }
+    pcs.ctx().ensure_twiddles(std::max(1u, log_max));
+
+    // the statement's shape: a prover must not choose the heights after the fact
+    challenger.observe((uint32_t)T);
+    for (const Statement& s : st) challenger.observe(s.log_degree);
+
+    // one commit of every trace on its natural domain (shift 1)
+    std::vector<DeviceMatrix> tv;
+    for (MultiTable& t : tables) tv.push_back(std::move(t.trace));
+    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, std::vector<uint32_t>(T, 1u));
+    challenger.observe_commitment(trace_data->root);
+    const Ef alpha = challenger.sample();
+
+    // the chunks of every table over its own LDE in the batch, then one commit of all of them
+    std::vector<DeviceMatrix> chunks;
+    std::vector<uint32_t> shifts;
+    for (size_t t = 0; t < T; t++) {
+        std::vector<DeviceMatrix> c =
+            pcs.quotient_chunks_slab(trace_data->ldes[t], st[t].log_degree, TwoAdicFriPcs::Slab{}, *tables[t].air,
+                                     tables[t].public_values, alpha);
+        const std::vector<uint32_t> sh = chunk_domain_shifts(GENERATOR, st[t].log_degree, st[t].lqd);
+        for (auto& m : c) chunks.push_back(std::move(m));
+        shifts.insert(shifts.end(), sh.begin(), sh.end());
+    }
+    std::unique_ptr<PcsData> quotient_data = pcs.commit(chunks, shifts);
+    challenger.observe_commitment(quotient_data->root);
+    const Ef zeta = challenger.sample();
+
+    // the two rounds in the visiting order of Pcs::open
+    std::vector<OpenMat> mats;
+    size_t first = 0, qi = 0;
+    for (size_t t = 0; t < T; t++) {
+        mats.push_back(OpenMat{&trace_data->ldes[t], st[t].log_degree, true, first});
+        first += 2 * (size_t)st[t].w;
+    }
+    for (size_t t = 0; t < T; t++)
+        for (uint32_t c = 0; c < st[t].qd; c++, qi++) {
+            const ColMat& m = quotient_data->ldes[qi];
+            TS_REQUIRE(m.width == 4 && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
+                       "prove_multi: a committed chunk has another shape than its table's");
+            mats.push_back(OpenMat{&m, st[t].log_degree, false, first});
+            first += 4;
+        }
+
+    std::vector<Ef> opened;
+    std::vector<uint32_t> fri_words;
+    const std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
+    if (multi_open_generic()) {
+        std::vector<TwoAdicFriPcs::OpenRound> rs(2);
+        rs[0].data = rounds[0];
+        rs[1].data = rounds[1];
+        for (const OpenMat& om : mats) {
+            std::vector<Ef> pts{zeta};
+            if (om.trace) pts.push_back(efc_mul_base(zeta, two_adic_generator(om.log_n)));
+            rs[om.trace ? 0 : 1].points.push_back(std::move(pts));
+        }
+        fri_words = pcs.open(rs, challenger, opened);
+    } else {
+        const Ef batch_alpha = challenger.sample();  // two_adic_pcs.rs:312
+        std::vector<DevBuf<Ef>> inputs;
+        std::vector<unsigned> log_lens;
+        open_classes(pcs, mats, zeta, batch_alpha, opened, inputs, log_lens);
+        pcs.fri_prove(inputs, log_lens, challenger, rounds, fri_words);
+    }
+
+    std::vector<uint32_t> pf;
+    pf.reserve(32 + 3 * T + opened.size() * 4 + fri_words.size());
+    ProofWriter pw(pf);
+    std::vector<ProofWriter::TableShape> shapes;
+    for (const Statement& s : st) shapes.push_back({s.log_degree, s.w, s.qd});
+    pw.header_multi(shapes);
+    pw.commitment(trace_data->root, 8);
+    pw.commitment(quotient_data->root, 8);
+    pw.opened_values(opened);
+    pw.words(fri_words.data(), fri_words.size());
+    return pf;
+}
+
+}  // namespace ts

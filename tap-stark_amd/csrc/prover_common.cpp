@@ -265,6 +265,17 @@ void ProofWriter::header(uint32_t version, unsigned log_degree, uint32_t width, 
     if (version >= 2) out_.push_back(extra);
 }
 
+void ProofWriter::header_multi(const std::vector<TableShape>& tables) {
+    out_.push_back(TSPF_MAGIC);
+    out_.push_back(6);
+    out_.push_back((uint32_t)tables.size());
+    for (auto& t : tables) {
+        out_.push_back(t.log_degree);
+        out_.push_back(t.width);
+        out_.push_back(t.qd);
+    }
+}
+
 void ProofWriter::opened_values(const std::vector<Ef>& values) {
     for (auto& e : values) words(e.c, 4);
 }

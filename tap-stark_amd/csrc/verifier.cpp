@@ -354,6 +354,10 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
                        const TapLocks* tap, bool v3 = false, const uint32_t* prep_root = nullptr,
                        std::vector<uint32_t>* exposed_out = nullptr, bool v5 = false);
 
+static bool ood_holds(const AirProgram& air, unsigned degree_bits, Ef zeta, Ef alpha, const Ef* pl, const Ef* pn,
+                      const Ef* al, const Ef* an, const Ef* tl, const Ef* tn, const std::vector<Ef>& qc,
+                      const std::vector<uint32_t>& pis);
+
 int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
                const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
     return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, true, preprocessed_root);
@@ -487,6 +491,21 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     const int rc = fri_verify_impl(fri, challenger, claims, false, fr.w, fr.len, tap);
     if (rc) return rc;
 
+    if (!ood_holds(air, degree_bits, zeta, alpha, pl.data(), pn.data(), al.data(), an.data(), tl.data(), tn.data(),
+                   qc, pis))
+        return 7;  // :157 OodEvaluationMismatch
+    if (phased) exposed_out->assign(pis.end() - (A_w ? air.n_exposed : 0), pis.end());
+    return 0;
+}
+
+// verifier.rs:103-157: the constraints folded at zeta over the opened rows, divided by the zeroifier, against the
+// quotient recomposed from its opened chunks (qc: 4 values per chunk)
+static bool ood_holds(const AirProgram& air, unsigned degree_bits, Ef zeta, Ef alpha, const Ef* pl, const Ef* pn,
+                      const Ef* al, const Ef* an, const Ef* tl, const Ef* tn, const std::vector<Ef>& qc,
+                      const std::vector<uint32_t>& pis) {
+    const unsigned lqd = air.log_quotient_degree;
+    const uint32_t qd = 1u << lqd;
+    const uint32_t gn = two_adic_generator(degree_bits);
     // ---- verifier.rs:103-132 quotient recombination
     const std::vector<uint32_t> shifts = chunk_domain_shifts(GENERATOR, degree_bits, lqd);
     Ef quotient = ef_zero();
@@ -515,14 +534,88 @@ static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger
     const Ef inv_zeroifier = c_inv(zh);
     // :138-153 fold the constraints at zeta
     std::vector<Ef> v;
-    eval_tape_ext(air, pl.data(), pn.data(), al.data(), an.data(), tl.data(), tn.data(), pis, is_first, is_last,
-                  is_trans, v);
+    eval_tape_ext(air, pl, pn, al, an, tl, tn, pis, is_first, is_last, is_trans, v);
     const uint32_t* cons = air.tape_constraints();
     Ef acc = ef_zero();
     for (uint32_t c = 0; c < air.n_constraints; c++) acc = ef_add(c_mul(acc, alpha), v[cons[c]]);
-    if (!ef_eq(c_mul(acc, inv_zeroifier), quotient)) return 7;  // :157 OodEvaluationMismatch
-    if (phased) exposed_out->assign(pis.end() - (A_w ? air.n_exposed : 0), pis.end());
-    return 0;
+    return ef_eq(c_mul(acc, inv_zeroifier), quotient);
+}
+
+// ------------------------------------------------------------------ verify, several tables in one proof
+// The verifier of prove_multi (prove_multi.cpp), TSPF v6: [magic, 6, T], T x [log_degree, width, qd], the two
+// roots, the opened values in (round, matrix, point, column) order, the FriProof.  Replays the transcript, runs
+// the out-of-domain check of verify_impl per table on that table's domain, then Pcs::verify over the two rounds.
+int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
+                 const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words) {
+    const size_t T = airs.size();
+    if (T == 0 || T > MAX_MULTI_TABLES || public_values.size() != T) return 1;
+    for (size_t t = 0; t < T; t++)
+        if (!airs[t] || airs[t]->preprocessed_width || airs[t]->aux_width || public_values[t].size() != airs[t]->n_public)
+            return 1;
+    Reader rb{proof, n_words};
+    if (rb.get() != TSPF_MAGIC || rb.get() != 6u) return 9;
+    const uint32_t pT = rb.get();
+    if (rb.bad) return 9;
+    if (pT != T) return 1;
+    const uint32_t* shapes = rb.take(3 * T);
+    if (rb.bad) return 9;
+    size_t n_vals = 0;  // opened EF4 values
+    for (size_t t = 0; t < T; t++) {
+        if (shapes[3 * t] > 27) return 9;
+        if (shapes[3 * t + 1] != airs[t]->width || shapes[3 * t + 2] != (1u << airs[t]->log_quotient_degree)) return 1;
+        n_vals += 2 * (size_t)airs[t]->width + 4 * (size_t)shapes[3 * t + 2];
+    }
+    const uint32_t* trace_root = rb.take(8);
+    const uint32_t* quot_root = rb.take(8);
+    const uint32_t* vals = rb.take(4 * n_vals);
+    if (rb.bad) return 9;
+    for (size_t k = 0; k < 4 * n_vals; k++)
+        if (vals[k] >= P) return 9;
+    // (the proof is a word stream: Ef is 16-byte aligned, the words are not)
+    std::vector<Ef> ov(n_vals);
+    memcpy((void*)ov.data(), vals, 16 * n_vals);
+
+    challenger.observe((uint32_t)T);
+    for (size_t t = 0; t < T; t++) challenger.observe(shapes[3 * t]);
+    challenger.observe_commitment(trace_root);
+    const Ef alpha = challenger.sample();
+    challenger.observe_commitment(quot_root);
+    const Ef zeta = challenger.sample();
+
+    PcsRoundClaim r0, r1;
+    r0.root = trace_root;
+    r1.root = quot_root;
+    size_t at = 0, qat = 0;
+    for (size_t t = 0; t < T; t++) qat += 2 * (size_t)airs[t]->width;  // the chunks' values follow every trace's
+    for (size_t t = 0; t < T; t++) {
+        const unsigned degree_bits = shapes[3 * t];
+        const uint32_t w = airs[t]->width, qd = shapes[3 * t + 2];
+        const Ef zeta_next = c_mul_base(zeta, two_adic_generator(degree_bits));
+        const std::vector<Ef> tl(ov.begin() + at, ov.begin() + at + w), tn(ov.begin() + at + w, ov.begin() + at + 2 * w);
+        const std::vector<Ef> qc(ov.begin() + qat, ov.begin() + qat + 4 * (size_t)qd);
+        if (!ood_holds(*airs[t], degree_bits, zeta, alpha, nullptr, nullptr, nullptr, nullptr, tl.data(), tn.data(), qc,
+                       public_values[t]))
+            return 7;
+        r0.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, w, {zeta, zeta_next}, {tl, tn}});
+        for (uint32_t c = 0; c < qd; c++)
+            r1.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, 4, {zeta},
+                                          {std::vector<Ef>(qc.begin() + 4 * (size_t)c, qc.begin() + 4 * (size_t)c + 4)}});
+        at += 2 * (size_t)w;
+        qat += 4 * (size_t)qd;
+    }
+    // the counts that lead the FriProof belong to the shape this format fixes (verdict 1, like the header's): R
+    // commit-phase roots for the tallest table, then num_queries answers
+    Reader fr{proof + rb.pos, n_words - rb.pos};
+    const uint32_t R = fr.get();
+    if (fr.bad) return 9;
+    unsigned log_max = 0;
+    for (size_t t = 0; t < T; t++) log_max = std::max<unsigned>(log_max, shapes[3 * t]);
+    if (R != log_max) return 1;
+    fr.take(8 * (size_t)R);
+    const uint32_t Q = fr.get();
+    if (fr.bad) return 9;
+    if (Q != fri.num_queries) return 1;
+    return fri_verify_impl(fri, challenger, {r0, r1}, false, proof + rb.pos, n_words - rb.pos);
 }
 
 }  // namespace ts

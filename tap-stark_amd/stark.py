@@ -1101,6 +1101,152 @@ def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_valu
     return Proof(out[: n_words.value].copy())
 
 
+@dataclass
+class MultiTableOpening:
+    """One table of a :class:`MultiProof`: its header words and its opened values."""
+    log_degree: int
+    width: int
+    qd: int
+    trace_local: np.ndarray      # (width, 4)
+    trace_next: np.ndarray       # (width, 4)
+    quotient_chunks: np.ndarray  # (qd, 4, 4)
+
+
+class MultiProof:
+    """A TSPF v6 proof (``ts_prove_multi``): several AIR tables of mixed heights under one trace commitment, one
+    quotient commitment and one FRI proof.  ``words`` keeps the wire form; ``tables`` (a list of
+    :class:`MultiTableOpening`), ``trace_commit``, ``quotient_commit``, ``commit_phase_commits``, ``query_proofs``,
+    ``final_poly`` and ``pow_witness`` are parsed on first access, as ``Proof`` does.  ``fri_words`` are the
+    FriProof words, ``opened_words`` the opened values in (round, matrix, point, column) order."""
+
+    _FIELDS = ("tables", "trace_commit", "quotient_commit", "opened_words", "fri_words", "commit_phase_commits",
+               "query_proofs", "final_poly", "pow_witness")
+
+    def __init__(self, words):
+        self.words = np.asarray(words, dtype=np.uint32)
+
+    def __getattr__(self, name):  # only reached for attributes not set yet
+        if name in MultiProof._FIELDS:
+            self._parse()
+            return self.__dict__[name]
+        raise AttributeError(name)
+
+    @classmethod
+    def parse(cls, words) -> "MultiProof":
+        """Eager form: raises ``ValueError`` on a malformed buffer."""
+        pf = cls(words)
+        pf._parse()
+        return pf
+
+    def _parse(self) -> None:
+        w = self.words
+        pos = 0
+
+        def take(n):
+            nonlocal pos
+            out = w[pos:pos + n]
+            if len(out) != n:
+                raise ValueError("truncated proof")
+            pos += n
+            return out
+
+        magic, version, T = (int(x) for x in take(3))
+        if magic != TSPF_MAGIC or version != 6 or not 1 <= T <= 64:
+            raise ValueError("not a TSPF v6 proof")
+        shapes = take(3 * T).reshape(T, 3)
+        d = {"trace_commit": take(8), "quotient_commit": take(8), "query_proofs": []}
+        start = pos
+        locals_ = [(take(4 * int(wd)).reshape(-1, 4), take(4 * int(wd)).reshape(-1, 4)) for _, wd, _ in shapes]
+        d["tables"] = [MultiTableOpening(int(ld), int(wd), int(qd), tl, tn, take(16 * int(qd)).reshape(-1, 4, 4))
+                       for (ld, wd, qd), (tl, tn) in zip(shapes, locals_)]
+        d["opened_words"] = w[start:pos]
+        d["fri_words"] = w[pos:]
+        R = int(take(1)[0])
+        d["commit_phase_commits"] = take(8 * R).reshape(R, 8)
+        for _ in range(int(take(1)[0])):
+            batches = []
+            for _ in range(int(take(1)[0])):
+                vals = [take(int(take(1)[0])) for _ in range(int(take(1)[0]))]
+                plen = int(take(1)[0])
+                batches.append(BatchOpening(vals, take(8 * plen).reshape(plen, 8)))
+            steps = []
+            for _ in range(R):
+                vals = take(8).reshape(2, 4)
+                plen = int(take(1)[0])
+                steps.append((vals, take(8 * plen).reshape(plen, 8)))
+            d["query_proofs"].append(QueryProof(batches, steps))
+        d["final_poly"] = take(4)
+        d["pow_witness"] = int(take(1)[0])
+        if pos != len(w):
+            raise ValueError("trailing words in proof")
+        self.__dict__.update(d)
+
+
+def _multi_capacity(shapes, fri: FriConfig) -> int:
+    """Exact TSPF v6 words of a proof over ``shapes`` = [(n, w, log_quotient_degree), ...]."""
+    logs = [max(n, 1).bit_length() - 1 + fri.log_blowup for n, _, _ in shapes]
+    log_max, Q = max(logs), fri.num_queries
+    R = log_max - fri.log_blowup
+    n_chunks = sum(1 << lqd for _, _, lqd in shapes)
+    w_total = sum(w for _, w, _ in shapes)
+    per_q = 1 + (2 + len(shapes) + w_total + 8 * log_max) + (2 + n_chunks + 4 * n_chunks + 8 * log_max)
+    per_q += sum(9 + 8 * (log_max - 1 - i) for i in range(R))
+    return 3 + 3 * len(shapes) + 16 + 8 * w_total + 16 * n_chunks + 2 + 8 * R + Q * per_q + 5
+
+
+def prove_multi(config: StarkConfig, airs, challenger: BfChallenger, traces, public_values) -> MultiProof:
+    """``ts_prove_multi``: one proof over several plain AIR tables of mixed heights (TSPF v6).  ``airs``: one
+    ``BaseAir`` or ``CompiledAir`` per table (no preprocessed, no aux columns); ``traces``: (n_t, w_t) arrays or
+    ``DeviceMatrix`` (consumed); ``public_values``: one sequence per table.  The transcript observes the table
+    count and every log-degree, commits all traces in one batch and all quotient chunks in another, and opens
+    both in one FRI proof (include/tapstark.h)."""
+    pcs = config.pcs
+    ctx = pcs.ctx
+    T = len(airs)
+    if len(traces) != T or len(public_values) != T:
+        raise ValueError("prove_multi: one trace and one public-value list per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
+    tabs = (_lib.MultiTableC * max(T, 1))()
+    for k in range(T):
+        tabs[k].struct_size = C.sizeof(_lib.MultiTableC)
+        tabs[k].n_public = len(pis[k])
+        tabs[k].air = airs[k].h
+        tabs[k].trace = traces[k].h
+        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
+    shapes = [(*t.dims(), a.log_quotient_degree) for t, a in zip(traces, airs)]
+    out = _proof_buffer(ctx, _multi_capacity(shapes, pcs.fri) if T else 1)
+    n_words = C.c_size_t()
+    cfg = pcs.fri._c()
+    ctx.check(ctx._l.ts_prove_multi(ctx.h, C.byref(cfg), challenger.h, tabs, T, _p(out), len(out),
+                                    C.byref(n_words)))
+    return MultiProof(out[: n_words.value].copy())
+
+
+def verify_multi(config: StarkConfig, airs, challenger: BfChallenger, proof, public_values) -> None:
+    """``ts_verify_multi``; host only, no GPU (host-only ``CompiledAir``s serve, as in ``verify``).  Raises
+    ``VerificationError``; returns None on acceptance."""
+    T = len(airs)
+    if len(public_values) != T:
+        raise ValueError("verify_multi: one public-value list per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
+    l = _lib.lib()
+    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
+    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
+    n_pub = _u32([len(p) for p in pis] or [0])
+    cfg = config.pcs.fri._c()
+    verdict = C.c_int(-1)
+    rc = l.ts_verify_multi(C.byref(cfg), challenger.h, handles, T, pv, _p(n_pub), _p(words), len(words),
+                           C.byref(verdict))
+    if rc:
+        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_multi").decode())
+    if verdict.value != 0:
+        raise VerificationError(verdict.value)
+
+
 def prove_stream(lanes, traces, lane_of, public_values, gate_ms: float = 0.0, want_times: bool = True):
     """``ts_prove_stream``: ``len(traces)`` independent proofs on the contexts of ``lanes`` = [(StarkConfig,
     CompiledAir), ...] (one context each, same device, same FriConfig), one host thread per lane INSIDE the
