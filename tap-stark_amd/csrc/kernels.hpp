@@ -246,19 +246,23 @@ struct FusedReduceArgs {
     // every matrix and of `ro` (rows = 0: the whole domain)
     uint64_t row0, rows;
 };
+// The matrices opened at the same two points BEFORE the trace, in opening order: the LDE of the key's
+// preprocessed columns (one: timed as k_reduce_fused_pre), then the aux trace's (two: k_reduce_fused_pre_aux).
+// Each is a whole LDE of the trace's height.  off[i] = alpha^num_reduced at matrix i's two visits (Montgomery);
+// args.off_t then start after them, args.k0 / k1 hold their constants too, and d_alpha_pows_mont covers
+// max(every width, 4) powers.
+struct LeadingMats {
+    uint32_t n = 0;
+    const ColMat* m[2] = {nullptr, nullptr};
+    Ef off[2][2];
+};
 void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
                          const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro,
-                         const ColMat* prep = nullptr, const Ef* prep_off_mont = nullptr,
-                         const ColMat* aux = nullptr, const Ef* aux_off_mont = nullptr);
-// prep != nullptr (k_reduce_fused_pre): the preprocessed columns' LDE, opened at the same two points BEFORE the
-// trace with the offsets prep_off_mont[2]; args.off_t then start after them and args.k0 / k1 hold the
-// preprocessed constants too.  d_alpha_pows_mont covers max(trace width, prep width, 4) powers.
-// aux != nullptr too (k_reduce_fused_pre_aux): a fourth round, the aux trace's LDE, opened at the same two points
-// after prep and before the trace with the offsets aux_off_mont[2]; the powers then cover the aux width as well.
+                         const LeadingMats& lead = LeadingMats());
 // The same reduced opening on the low coset only (rows t < n = 2^log_n of matrices that hold the whole LDE, no
-// preprocessed round): out = four base-field columns of n rows (stride n, canonical), to be extended by
+// leading matrices): out = four base-field columns of n rows (stride n, canonical), to be extended by
 // coset_lde with shift 1 like a quotient chunk on 31 H_n.  `weights` = launch_bary_weights' output for
-// args.z_mont on the coset 31 H_n ([2][n]); no inversion runs.  args.row0 / rows are not used.
+// args.z_mont on the coset 31 H_n ([2][n]); no inversion runs.  args.rows is not used.
 void launch_reduce_low(Context& ctx, const ColMat& trace, unsigned log_n, const uint32_t* d_alpha_pows_mont,
                        const FusedReduceArgs& args, const Ef* weights, uint32_t* out);
 // out[X] = (cols[k * col_stride + X])_{k < 4}, X < rows
@@ -287,7 +291,7 @@ struct ClassReduceArgs {
 // every row X of the class; one store per row, `ro` is never read.  d_jobs: n_jobs >= 1 entries, device memory.
 void launch_reduce_class(Context& ctx, const ClassJob* d_jobs, uint32_t n_jobs, unsigned log_h,
                          const uint32_t* d_alpha_pows_mont, const ClassReduceArgs& args, Ef* ro);
-// The finishing pass of any number of launch_bary_dots products in one launch (k_bary_finish / 3 / 4 take up to
+// The finishing pass of any number of launch_bary_dots products in one launch (k_bary_finish<N> takes up to
 // four by value): out[j] = sum over blocks of partial[block][j].  d_jobs: the jobs; d_groups: per workgroup
 // {job, group of four output words within it}; both device memory.
 struct BaryFinishJob {

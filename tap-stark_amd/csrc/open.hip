@@ -146,49 +146,51 @@ k_bary_dots(const uint32_t* __restrict__ m, uint64_t col_stride, uint32_t width,
 }
 
 // out[j] = sum over blocks of partial[block][j]  (mod p); one workgroup per 4 output words
-// (bary_finish_group, open_dev.hpp).  Up to two jobs in one launch (the trace's sums and the quotient
-// chunks'): workgroups 0 .. g0-1 take job 0.
+// (bary_finish_group, open_dev.hpp).  Up to N jobs in one launch, by value (the trace's sums and the quotient
+// chunks'; with a key, its columns' first; with an aux round, that one's second): the first groups[0]
+// workgroups take job 0, the next groups[1] job 1, and so on.
+template <int N>
+struct BaryFinishArgs {
+    BaryFinishJob j[N];
+    uint32_t groups[N];
+};
+template <int N>
 __global__ void __launch_bounds__(256)
-k_bary_finish(BaryFinishJob j0, BaryFinishJob j1, uint32_t g0) {
-    const bool first = blockIdx.x < g0;
-    bary_finish_group(first ? j0.partial : j1.partial, first ? j0.out : j1.out, first ? j0.n_blocks : j1.n_blocks,
-                      first ? j0.n_words : j1.n_words, first ? blockIdx.x : blockIdx.x - g0);
-}
-// three jobs (preprocessed columns, trace, quotient chunks): workgroups g0 .. g0+g1-1 take job 1
-__global__ void __launch_bounds__(256)
-k_bary_finish3(BaryFinishJob j0, BaryFinishJob j1, BaryFinishJob j2, uint32_t g0, uint32_t g1) {
-    const BaryFinishJob j = blockIdx.x < g0 ? j0 : blockIdx.x < g0 + g1 ? j1 : j2;
-    bary_finish_group(j.partial, j.out, j.n_blocks, j.n_words,
-                      blockIdx.x < g0 ? blockIdx.x : blockIdx.x < g0 + g1 ? blockIdx.x - g0 : blockIdx.x - g0 - g1);
+k_bary_finish(BaryFinishArgs<N> a) {
+    BaryFinishJob j = a.j[0];
+    uint32_t group = blockIdx.x, first = 0;
+#pragma unroll
+    for (int k = 1; k < N; k++) {
+        first += a.groups[k - 1];
+        if (blockIdx.x >= first) {
+            j = a.j[k];
+            group = blockIdx.x - first;
+        }
+    }
+    bary_finish_group(j.partial, j.out, j.n_blocks, j.n_words, group);
 }
 
-// four jobs (preprocessed columns, aux columns, trace, quotient chunks): a kernel of its own beside the two above
-__global__ void __launch_bounds__(256)
-k_bary_finish4(BaryFinishJob j0, BaryFinishJob j1, BaryFinishJob j2, BaryFinishJob j3, uint32_t g0, uint32_t g1,
-               uint32_t g2) {
-    const uint32_t b = blockIdx.x;
-    const BaryFinishJob j = b < g0 ? j0 : b < g0 + g1 ? j1 : b < g0 + g1 + g2 ? j2 : j3;
-    bary_finish_group(j.partial, j.out, j.n_blocks, j.n_words,
-                      b < g0 ? b : b < g0 + g1 ? b - g0 : b < g0 + g1 + g2 ? b - g0 - g1 : b - g0 - g1 - g2);
+template <int N>
+static void launch_bary_finish_n(Context& ctx, const char* name, const BaryPending& pend) {
+    BaryFinishArgs<N> a{};
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < pend.n; i++) {
+        a.j[i] = BaryFinishJob{pend.partial[i].p, pend.out[i], pend.n_blocks[i], pend.n_words[i]};
+        a.groups[i] = (pend.n_words[i] + 3) / 4;
+        total += a.groups[i];
+    }
+    TS_LAUNCH_NAMED(ctx, name, k_bary_finish<N>, dim3(total), dim3(256), 0, a);
 }
 
 // the finishing pass of the pending launch_bary_dots(..., pending) calls
 void launch_bary_finish(Context& ctx, BaryPending& pend) {
     if (pend.n == 0) return;
-    BaryFinishJob j[4] = {{nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0}, {nullptr, nullptr, 0, 0},
-                          {nullptr, nullptr, 0, 0}};
-    uint32_t g[4] = {0, 0, 0, 0};
-    for (uint32_t i = 0; i < pend.n; i++) {
-        j[i] = BaryFinishJob{pend.partial[i].p, pend.out[i], pend.n_blocks[i], pend.n_words[i]};
-        g[i] = (pend.n_words[i] + 3) / 4;
-    }
     if (pend.n == 4)
-        TS_LAUNCH(ctx, k_bary_finish4, dim3(g[0] + g[1] + g[2] + g[3]), dim3(256), 0, j[0], j[1], j[2], j[3], g[0], g[1],
-                  g[2]);
+        launch_bary_finish_n<4>(ctx, "k_bary_finish<4>", pend);
     else if (pend.n == 3)
-        TS_LAUNCH(ctx, k_bary_finish3, dim3(g[0] + g[1] + g[2]), dim3(256), 0, j[0], j[1], j[2], g[0], g[1]);
+        launch_bary_finish_n<3>(ctx, "k_bary_finish<3>", pend);
     else
-        TS_LAUNCH(ctx, k_bary_finish, dim3(g[0] + g[1]), dim3(256), 0, j[0], j[1], g[0]);
+        launch_bary_finish_n<2>(ctx, "k_bary_finish<2>", pend);
     TS_HIP(hipGetLastError());
     for (uint32_t i = 0; i < pend.n; i++) pend.partial[i].reset();
     pend.n = 0;
@@ -284,16 +286,45 @@ void launch_reduce(Context& ctx, const ColMat& m, unsigned log_h, const uint32_t
 // Evaluated as  g0 = off_t0 S_t + D - k0,  g1 = off_t1 S_t - k1,  D = one dot product over every
 // chunk column with the folded weights alpha^k off_c (FusedReduceArgs): four EF4 products per row
 // instead of 5 + n_chunks -- this kernel, too, is bound by VALU issue, not by its 4 TB/s.
+//
+// EXTRA leading matrices (the key's preprocessed columns, then the aux trace's) are opened at the same two
+// points BEFORE the trace: g0 += off_m0 S_m, g1 += off_m1 S_m, with S_m shared by its two openings exactly as
+// S_t is (the constants off_m rys_m are in k0, k1).
+//
+// LOW: the same sums on the low coset only.  The reduced opening is a polynomial of degree < n, so its n values
+// on one coset of H_n determine the other N - n: the kernel computes them on the low coset (rows t < n,
+// x_t = 31 omega_n^bitrev(t)) and the caller extends them with the coset LDE (prover.cpp).  The two inverses are
+// not computed but read:  k_bary_weights left weights[p][t] = x_t / (z_p - x_t), hence
+// 1/(x_t - z_p) = -weights[p][t] / x_t, and 1/x_t is one product of the inverse coset generator with an inverse
+// twiddle (W and gen_mont are then the inverse table and 1/31, log_h is log_n).  Output: four base-field columns
+// of n rows (an n x 4 COL_MAJOR_BITREV matrix, canonical), the shape of a quotient chunk, instead of one EF4.
+//
+// The chunk-column loop stays in this body: as a helper function it cost the EXTRA = 0 form 20 VGPRs, whether
+// the helper took the by-value struct or its members.
+template <int EXTRA>
+struct ExtraReduceArgs {
+    struct {
+        const uint32_t* d;
+        uint64_t stride;
+        uint32_t width;
+        Ef off[2];  // alpha^num_reduced at the matrix's two visits (Montgomery)
+    } m[EXTRA ? EXTRA : 1];  // in opening order
+};
+
+template <int EXTRA, bool LOW>
 __global__ void __launch_bounds__(256)
-k_reduce_fused(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width,
-               unsigned log_h, const uint32_t* __restrict__ W, uint32_t gen_mont,
-               const uint32_t* __restrict__ alpha_pows, FusedReduceArgs a, Ef* __restrict__ ro) {
+k_reduce_fused(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width, unsigned log_h,
+               const uint32_t* __restrict__ W, uint32_t gen_mont, const uint32_t* __restrict__ alpha_pows,
+               FusedReduceArgs a, ExtraReduceArgs<EXTRA> e, const Ef* __restrict__ weights,
+               uint32_t* __restrict__ out) {
     const uint64_t X = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // local row
     if (X >= a.rows) return;
     const Ef St = row_dot_alpha(trace, trace_stride, width, X, alpha_pows);
-    const uint32_t x = mont_mul(gen_mont, root_bitrev(W, log_h, a.row0 + X));
     Ef inv_d[2];
-    inv_denoms<2>(x, a.z_mont, inv_d);
+    if constexpr (!LOW) {
+        const uint32_t x = mont_mul(gen_mont, root_bitrev(W, log_h, a.row0 + X));
+        inv_denoms<2>(x, a.z_mont, inv_d);
+    }
     uint64_t acc[4] = {0, 0, 0, 0};
     uint32_t c = 0;
     for (; c + 2 <= a.n_chunks; c += 2) {
@@ -315,114 +346,49 @@ k_reduce_fused(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32
     }
     for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
     const Ef D{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
-    const Ef g0 = ef_sub(ef_add(ef_mul(St, a.off_t[0]), D), a.k0);
-    const Ef g1 = ef_sub(ef_mul(St, a.off_t[1]), a.k1);
-    const Ef r = ef_add(ef_mul(g0, inv_d[0]), ef_mul(g1, inv_d[1]));
-    *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
+    if constexpr (LOW) {
+        // -1/x_t = -(1/gen) omega_n^-bitrev(t)
+        const uint32_t nxi = neg(mont_mul(gen_mont, root_bitrev(W, log_h, X)));
+        inv_d[0] = ef_mul_base(weights[X], nxi);
+        inv_d[1] = ef_mul_base(weights[a.rows + X], nxi);
+    }
+    Ef g0 = ef_add(ef_mul(St, a.off_t[0]), D), g1 = ef_mul(St, a.off_t[1]);
+#pragma unroll
+    for (int i = 0; i < EXTRA; i++) {
+        const Ef S = row_dot_alpha(e.m[i].d, e.m[i].stride, e.m[i].width, X, alpha_pows);
+        g0 = ef_add(g0, ef_mul(S, e.m[i].off[0]));
+        g1 = ef_add(g1, ef_mul(S, e.m[i].off[1]));
+    }
+    const Ef r = ef_add(ef_mul(ef_sub(g0, a.k0), inv_d[0]), ef_mul(ef_sub(g1, a.k1), inv_d[1]));
+    if constexpr (LOW) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) out[(uint64_t)k * a.rows + X] = r.c[k];
+    } else {
+        *reinterpret_cast<uint4*>(out + 4 * X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
+    }
 }
 
-// The same pass with a third committed matrix, the preprocessed columns of the key, opened at the same two
-// points BEFORE the trace: g0 += off_p0 S_p, g1 += off_p1 S_p, with S_p shared by its two openings exactly as
-// S_t is (the constants off_p rys_p are in k0, k1).  A kernel of its own, so that k_reduce_fused stays the code
-// it was: handing its by-value argument struct to a shared body cost it 20 VGPRs.
-struct PrepReduceArgs {
-    const uint32_t* prep;
-    uint64_t stride;
-    uint32_t width;
-    Ef off_p[2];  // alpha^0, alpha^P (Montgomery); the trace's offsets then start at alpha^(2P)
-};
-__global__ void __launch_bounds__(256)
-k_reduce_fused_pre(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width,
-               unsigned log_h, const uint32_t* __restrict__ W, uint32_t gen_mont,
-               const uint32_t* __restrict__ alpha_pows, FusedReduceArgs a, PrepReduceArgs pa,
-               Ef* __restrict__ ro) {
-    const uint64_t X = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // local row
-    if (X >= a.rows) return;
-    const Ef St = row_dot_alpha(trace, trace_stride, width, X, alpha_pows);
-    const uint32_t x = mont_mul(gen_mont, root_bitrev(W, log_h, a.row0 + X));
-    Ef inv_d[2];
-    inv_denoms<2>(x, a.z_mont, inv_d);
-    uint64_t acc[4] = {0, 0, 0, 0};
-    uint32_t c = 0;
-    for (; c + 2 <= a.n_chunks; c += 2) {
-        // two width-4 chunks = one full batch of eight columns (their weights are consecutive): eight
-        // loads in flight, 32 multiply-adds, 16 range fixes -- as two 4-column tails it cost twice that
-        uint32_t v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = a.chunk[c + (k >> 2)][(uint64_t)(k & 3) * a.chunk_stride + X];
-        const uint32_t* ap = a.chunk_w + 16 * c;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[j] = lazy_mac(acc[j], v[k], ap[4 * k + j]);
-            if (k & 1) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[j] = lazy_fix(acc[j]);
-            }
-        }
+template <int EXTRA>
+static void launch_reduce_fused_n(Context& ctx, const char* name, const ColMat& trace, unsigned log_h,
+                                  const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& a,
+                                  const LeadingMats& lead, Ef* ro) {
+    ExtraReduceArgs<EXTRA> e{};
+    for (int i = 0; i < EXTRA; i++) {
+        e.m[i].d = lead.m[i]->d;
+        e.m[i].stride = lead.m[i]->col_stride;
+        e.m[i].width = lead.m[i]->width;
+        e.m[i].off[0] = lead.off[i][0];
+        e.m[i].off[1] = lead.off[i][1];
     }
-    for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
-    const Ef D{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
-    const Ef Sp = row_dot_alpha(pa.prep, pa.stride, pa.width, X, alpha_pows);
-    const Ef g0 = ef_sub(ef_add(ef_add(ef_mul(St, a.off_t[0]), ef_mul(Sp, pa.off_p[0])), D), a.k0);
-    const Ef g1 = ef_sub(ef_add(ef_mul(St, a.off_t[1]), ef_mul(Sp, pa.off_p[1])), a.k1);
-    const Ef r = ef_add(ef_mul(g0, inv_d[0]), ef_mul(g1, inv_d[1]));
-    *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
-}
-
-// The same pass with the key's columns AND the aux trace's, opened in that order before the trace, each at the
-// same two points: g_p += off_p[p] S_key + off_a[p] S_aux, S_key and S_aux each shared by its two openings (the
-// constants are in k0, k1).  A kernel of its own for the reason given above PrepReduceArgs.
-struct PrepAuxReduceArgs {
-    const uint32_t* prep;
-    const uint32_t* aux;
-    uint64_t prep_stride, aux_stride;
-    uint32_t prep_width, aux_width;
-    Ef off_p[2];  // alpha^0, alpha^P (Montgomery)
-    Ef off_a[2];  // alpha^(2P), alpha^(2P + A); the trace's offsets then start at alpha^(2P + 2A)
-};
-__global__ void __launch_bounds__(256)
-k_reduce_fused_pre_aux(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width,
-                       unsigned log_h, const uint32_t* __restrict__ W, uint32_t gen_mont,
-                       const uint32_t* __restrict__ alpha_pows, FusedReduceArgs a, PrepAuxReduceArgs pa,
-                       Ef* __restrict__ ro) {
-    const uint64_t X = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // local row
-    if (X >= a.rows) return;
-    const Ef St = row_dot_alpha(trace, trace_stride, width, X, alpha_pows);
-    const uint32_t x = mont_mul(gen_mont, root_bitrev(W, log_h, a.row0 + X));
-    Ef inv_d[2];
-    inv_denoms<2>(x, a.z_mont, inv_d);
-    uint64_t acc[4] = {0, 0, 0, 0};
-    uint32_t c = 0;
-    for (; c + 2 <= a.n_chunks; c += 2) {  // (as k_reduce_fused: two width-4 chunks are one batch of eight columns)
-        uint32_t v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = a.chunk[c + (k >> 2)][(uint64_t)(k & 3) * a.chunk_stride + X];
-        const uint32_t* ap = a.chunk_w + 16 * c;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[j] = lazy_mac(acc[j], v[k], ap[4 * k + j]);
-            if (k & 1) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[j] = lazy_fix(acc[j]);
-            }
-        }
-    }
-    for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
-    const Ef D{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
-    const Ef Sp = row_dot_alpha(pa.prep, pa.prep_stride, pa.prep_width, X, alpha_pows);
-    const Ef Sa = row_dot_alpha(pa.aux, pa.aux_stride, pa.aux_width, X, alpha_pows);
-    const Ef g0 = ef_sub(ef_add(ef_add(ef_add(ef_mul(St, a.off_t[0]), ef_mul(Sp, pa.off_p[0])), ef_mul(Sa, pa.off_a[0])), D),
-                         a.k0);
-    const Ef g1 = ef_sub(ef_add(ef_add(ef_mul(St, a.off_t[1]), ef_mul(Sp, pa.off_p[1])), ef_mul(Sa, pa.off_a[1])), a.k1);
-    const Ef r = ef_add(ef_mul(g0, inv_d[0]), ef_mul(g1, inv_d[1]));
-    *reinterpret_cast<uint4*>(ro + X) = make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]);
+    TS_LAUNCH_NAMED(ctx, name, (k_reduce_fused<EXTRA, false>), dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
+                    (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
+                    (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, e,
+                    (const Ef*)nullptr, reinterpret_cast<uint32_t*>(ro));
 }
 
 void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
                          const uint32_t* d_alpha_pows_mont, const FusedReduceArgs& args, Ef* ro,
-                         const ColMat* prep, const Ef* prep_off_mont, const ColMat* aux, const Ef* aux_off_mont) {
+                         const LeadingMats& lead) {
     TS_REQUIRE(args.n_chunks <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_INVALID, "reduce_fused: too many chunks");
     ctx.ensure_twiddles(log_h == 0 ? 1 : log_h);
     FusedReduceArgs a = args;
@@ -431,87 +397,22 @@ void launch_reduce_fused(Context& ctx, const ColMat& trace, unsigned log_h,
         a.rows = 1ull << log_h;
     }
     TS_REQUIRE(a.row0 + a.rows <= (1ull << log_h), TS_ERR_INVALID, "reduce_fused: row range");
-    TS_REQUIRE(!aux || prep, TS_ERR_INVARIANT, "reduce_fused: a third matrix without a second");
-    if (aux) {
-        for (const ColMat* m : {prep, aux})
-            TS_REQUIRE(m->d && a.row0 == 0 && m->height == a.rows && m->col_stride >= a.rows, TS_ERR_INVALID,
-                       "reduce_fused: preprocessed or aux matrix shape");
-        TS_REQUIRE(prep_off_mont && aux_off_mont, TS_ERR_INVALID, "reduce_fused: missing offsets");
-        const PrepAuxReduceArgs pa{prep->d, aux->d, prep->col_stride, aux->col_stride, prep->width, aux->width,
-                                   {prep_off_mont[0], prep_off_mont[1]}, {aux_off_mont[0], aux_off_mont[1]}};
-        TS_LAUNCH(ctx, k_reduce_fused_pre_aux, dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
-                  (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
-                  (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, pa, ro);
-        TS_HIP(hipGetLastError());
-        return;
+    TS_REQUIRE(lead.n <= 2, TS_ERR_INVARIANT, "reduce_fused: more than two leading matrices");
+    for (uint32_t i = 0; i < lead.n; i++) {
+        const ColMat* m = lead.m[i];
+        TS_REQUIRE(m && m->d && a.row0 == 0 && m->height == a.rows && m->col_stride >= a.rows, TS_ERR_INVALID,
+                   "reduce_fused: preprocessed or aux matrix shape");
     }
-    if (prep) {
-        TS_REQUIRE(prep_off_mont && prep->d && a.row0 == 0 && prep->height == a.rows && prep->col_stride >= a.rows,
-                   TS_ERR_INVALID, "reduce_fused: preprocessed matrix shape");
-        const PrepReduceArgs pa{prep->d, prep->col_stride, prep->width, {prep_off_mont[0], prep_off_mont[1]}};
-        TS_LAUNCH(ctx, k_reduce_fused_pre, dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
-                  (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
-                  (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, pa, ro);
-        TS_HIP(hipGetLastError());
-        return;
-    }
-    TS_LAUNCH(ctx, k_reduce_fused, dim3((unsigned)((a.rows + 255) / 256)), dim3(256), 0,
-              (const uint32_t*)trace.d, trace.col_stride, trace.width, log_h,
-              (const uint32_t*)ctx.d_twiddle_fwd, to_mont(GENERATOR), d_alpha_pows_mont, a, ro);
+    if (lead.n == 2)
+        launch_reduce_fused_n<2>(ctx, "k_reduce_fused_pre_aux", trace, log_h, d_alpha_pows_mont, a, lead, ro);
+    else if (lead.n == 1)
+        launch_reduce_fused_n<1>(ctx, "k_reduce_fused_pre", trace, log_h, d_alpha_pows_mont, a, lead, ro);
+    else
+        launch_reduce_fused_n<0>(ctx, "k_reduce_fused", trace, log_h, d_alpha_pows_mont, a, lead, ro);
     TS_HIP(hipGetLastError());
 }
 
 // ------------------------------------------------------------------ reduce on the low coset
-// The reduced opening is a polynomial of degree < n, so its n values on one coset of H_n determine the other
-// N - n: k_reduce_low computes them on the low coset (rows t < n, x_t = 31 omega_n^bitrev(t)) and the caller
-// extends them with the coset LDE (prover.cpp).  Same sums, same constants and same lazy accumulation as
-// k_reduce_fused; the two inverses are not computed but read:  k_bary_weights left
-// weights[p][t] = x_t / (z_p - x_t), hence 1/(x_t - z_p) = -weights[p][t] / x_t, and 1/x_t is one product of
-// the inverse coset generator with an inverse twiddle.  Output: four base-field columns of n rows (an n x 4
-// COL_MAJOR_BITREV matrix, canonical), the shape of a quotient chunk.
-// (the chunk columns' dot product as a function: here its by-value struct argument may cost registers, which
-// k_reduce_fused and k_reduce_fused_pre avoid with inline copies of the loop)
-__device__ __forceinline__ Ef chunk_dot(const FusedReduceArgs& a, uint64_t X) {
-    uint64_t acc[4] = {0, 0, 0, 0};
-    uint32_t c = 0;
-    for (; c + 2 <= a.n_chunks; c += 2) {
-        uint32_t v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = a.chunk[c + (k >> 2)][(uint64_t)(k & 3) * a.chunk_stride + X];
-        const uint32_t* ap = a.chunk_w + 16 * c;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[j] = lazy_mac(acc[j], v[k], ap[4 * k + j]);
-            if (k & 1) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[j] = lazy_fix(acc[j]);
-            }
-        }
-    }
-    for (; c < a.n_chunks; c++) row_dot_acc(acc, a.chunk[c], a.chunk_stride, 4, X, a.chunk_w + 16 * c);
-    return Ef{{lazy_finish(acc[0]), lazy_finish(acc[1]), lazy_finish(acc[2]), lazy_finish(acc[3])}};
-}
-
-__global__ void __launch_bounds__(256)
-k_reduce_low(const uint32_t* __restrict__ trace, uint64_t trace_stride, uint32_t width, unsigned log_n,
-             const uint32_t* __restrict__ Winv, uint32_t gen_inv_mont, const uint32_t* __restrict__ alpha_pows,
-             FusedReduceArgs a, const Ef* __restrict__ weights, uint32_t* __restrict__ out) {
-    const uint64_t n = 1ull << log_n;
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const Ef St = row_dot_alpha(trace, trace_stride, width, t, alpha_pows);
-    const Ef D = chunk_dot(a, t);
-    // -1/x_t = -(1/gen) omega_n^-bitrev(t)
-    const uint32_t nxi = neg(mont_mul(gen_inv_mont, root_bitrev(Winv, log_n, t)));
-    const Ef inv_d0 = ef_mul_base(weights[t], nxi), inv_d1 = ef_mul_base(weights[n + t], nxi);
-    const Ef g0 = ef_sub(ef_add(ef_mul(St, a.off_t[0]), D), a.k0);
-    const Ef g1 = ef_sub(ef_mul(St, a.off_t[1]), a.k1);
-    const Ef r = ef_add(ef_mul(g0, inv_d0), ef_mul(g1, inv_d1));
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[(uint64_t)k * n + t] = r.c[k];
-}
-
 void launch_reduce_low(Context& ctx, const ColMat& trace, unsigned log_n, const uint32_t* d_alpha_pows_mont,
                        const FusedReduceArgs& args, const Ef* weights, uint32_t* out) {
     TS_REQUIRE(args.n_chunks <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_INVALID, "reduce_low: too many chunks");
@@ -519,9 +420,11 @@ void launch_reduce_low(Context& ctx, const ColMat& trace, unsigned log_n, const 
     TS_REQUIRE(args.row0 == 0 && trace.height >= n && trace.col_stride >= n && args.chunk_stride >= n, TS_ERR_INVALID,
                "reduce_low: the matrices must start with the low coset");
     ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
-    TS_LAUNCH(ctx, k_reduce_low, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint32_t*)trace.d,
-              trace.col_stride, trace.width, log_n, (const uint32_t*)ctx.d_twiddle_inv,
-              to_mont(inv_canon(GENERATOR)), d_alpha_pows_mont, args, weights, out);
+    FusedReduceArgs a = args;
+    a.rows = n;
+    TS_LAUNCH_NAMED(ctx, "k_reduce_low", (k_reduce_fused<0, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                    (const uint32_t*)trace.d, trace.col_stride, trace.width, log_n, (const uint32_t*)ctx.d_twiddle_inv,
+                    to_mont(inv_canon(GENERATOR)), d_alpha_pows_mont, a, ExtraReduceArgs<0>{}, weights, out);
     TS_HIP(hipGetLastError());
 }
 

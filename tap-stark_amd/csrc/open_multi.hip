@@ -57,7 +57,7 @@ void launch_reduce_class(Context& ctx, const ClassJob* d_jobs, uint32_t n_jobs, 
 }
 
 // ------------------------------------------------------------------ barycentric finish, any number of jobs
-// k_bary_finish / 3 / 4 with the jobs in device memory: workgroup b adds up four output words of job
+// k_bary_finish<N> (open.hip) with the jobs in device memory: workgroup b adds up four output words of job
 // groups[b].x, the groups[b].y-th four of them.
 __global__ void __launch_bounds__(256)
 k_bary_finish_jobs(const BaryFinishJob* __restrict__ jobs, const uint2* __restrict__ groups) {

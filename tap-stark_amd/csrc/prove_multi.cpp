@@ -109,43 +109,20 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
     }
     // p(z) = ((z/31)^n - 1)/n * sum_i p_i x_i/(z - x_i); the dot kernel left [col][point]
     opened.assign(n_opened, ef_zero());
-    for (const OpenMat& om : mats) {
-        const Points& pt = by_log_n[om.log_n];
-        const uint32_t w = om.m->width;
-        Ef* const ov = opened.data() + om.first;
-        const Ef* const rw = raw.data() + om.first;
-        for (uint32_t c = 0; c < w; c++) {
-            if (om.trace) {
-                ov[c] = efc_mul(rw[2 * c], pt.scale[0]);          // local
-                ov[w + c] = efc_mul(rw[2 * c + 1], pt.scale[1]);  // next
-            } else {
-                ov[c] = efc_mul(rw[c], pt.scale[0]);
-            }
-        }
-    }
+    for (const OpenMat& om : mats)
+        opened_from_raw(raw.data() + om.first, om.m->width, om.trace ? 2 : 1, by_log_n[om.log_n].scale,
+                        opened.data() + om.first);
 
     // ---- reduce (two_adic_pcs.rs:371-383), one launch per height class
     StageTimer t(&ctx, "reduce rows");
-    std::vector<uint32_t> apow = alpha_powers_mont(batch_alpha, max_w);
-    const size_t n_apow = apow.size();
-    const Ef am = ef_to_mont(batch_alpha);
-    auto reduced_ys = [&](const Ef* ys, uint32_t width) {  // dot_product(alpha.powers(), ys), :372
-        Ef acc = ef_zero();
-        for (uint32_t i = 0; i < width; i++) {
-            Ef ap;
-            memcpy(ap.c, &apow[4 * (size_t)i], 16);
-            acc = ef_add(acc, ef_mul(ys[i], ap));  // canonical x Montgomery -> canonical
-        }
-        return acc;
-    };
+    AlphaLedger ledger(batch_alpha, max_w);
+    std::vector<uint32_t> words = ledger.powers();  // and behind them alpha^k off_0 per chunk column: one upload
     struct Class {
         std::vector<ClassJob> jobs;
-        std::vector<size_t> weights_at;  // per job: word offset of its folded weights behind the alpha powers
-        uint64_t num_reduced = 0;        // :332, grows by the width after every (matrix, point)
+        std::vector<size_t> weights_at;  // per job: word offset of its folded weights in `words`
         ClassReduceArgs args;
     };
     std::map<unsigned, Class> classes;  // by LDE log-height
-    std::vector<uint32_t> folded;       // alpha^k off_0 per chunk column
     for (const OpenMat& om : mats) {
         const unsigned log_h = om.log_n + log_blowup;
         const bool fresh = !classes.count(log_h);
@@ -154,7 +131,6 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
             const Points& pt = by_log_n[om.log_n];
             cl.args.z_mont[0] = ef_to_mont(pt.z[0]);
             cl.args.z_mont[1] = ef_to_mont(pt.z[1]);
-            cl.args.k0 = cl.args.k1 = ef_zero();
         }
         const uint32_t w = om.m->width;
         ClassJob j;
@@ -163,35 +139,23 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
         j.col_stride = om.m->col_stride;
         j.width = w;
         j.has_next = om.trace ? 1 : 0;
-        j.off[0] = ef_pow(am, cl.num_reduced);  // :371
-        cl.args.k0 = ef_add(cl.args.k0, ef_mul(reduced_ys(&opened[om.first], w), j.off[0]));
-        cl.num_reduced += w;  // :383
-        size_t at = 0;
-        if (om.trace) {
-            j.off[1] = ef_pow(am, cl.num_reduced);
-            cl.args.k1 = ef_add(cl.args.k1, ef_mul(reduced_ys(&opened[om.first + w], w), j.off[1]));
-            cl.num_reduced += w;
-        } else {
-            at = n_apow + folded.size();
-            for (uint32_t k = 0; k < w; k++) {  // alpha^k off_0: the weight of column k
-                Ef ap;
-                memcpy(ap.c, &apow[4 * (size_t)k], 16);
-                const Ef wk = ef_mul(ap, j.off[0]);
-                folded.insert(folded.end(), wk.c, wk.c + 4);
-            }
-        }
+        j.off[0] = ledger.visit(log_h, &opened[om.first], w, 0).off;
+        if (om.trace) j.off[1] = ledger.visit(log_h, &opened[om.first + w], w, 1).off;
+        cl.weights_at.push_back(words.size());
+        if (!om.trace) ledger.fold_weights(j.off[0], w, words);
         cl.jobs.push_back(j);
-        cl.weights_at.push_back(at);
     }
-    apow.insert(apow.end(), folded.begin(), folded.end());
-    DevBuf<uint32_t> d_apow(&ctx, apow.size());
-    h2d(ctx, d_apow.p, apow.data(), apow.size() * 4);
+    DevBuf<uint32_t> d_apow(&ctx, words.size());
+    h2d(ctx, d_apow.p, words.data(), words.size() * 4);
     std::vector<ClassJob> all_jobs;
-    for (auto& [log_h, cl] : classes)
+    for (auto& [log_h, cl] : classes) {
+        cl.args.k0 = ledger.k(log_h, 0);
+        cl.args.k1 = ledger.k(log_h, 1);
         for (size_t k = 0; k < cl.jobs.size(); k++) {
             if (!cl.jobs[k].has_next) cl.jobs[k].weights = d_apow.p + cl.weights_at[k];
             all_jobs.push_back(cl.jobs[k]);
         }
+    }
     DevBuf<ClassJob> d_jobs(&ctx, all_jobs.size());
     h2d(ctx, d_jobs.p, all_jobs.data(), all_jobs.size() * sizeof(ClassJob));
     // :389-393 fri_input: the reduced openings by descending height

@@ -214,20 +214,19 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
                                            std::vector<Ef>& opened_values, const PcsData* preprocessed,
                                            const PcsData* aux) {
     TS_REQUIRE(trace_data.ldes.size() == 1, TS_ERR_UNSUPPORTED, "open: one trace matrix expected");
-    // an aux round beside a preprocessed one (four rounds: key, aux, trace, chunks) is opened second, at the
-    // trace's points too: its 2 aw values follow the key's and its columns the key's in the num_reduced count
+    // The rounds opened before the trace, at the trace's points, in opening order: a preprocessed round (the key)
+    // first, an aux round beside it (four rounds: key, aux, trace, chunks) second.  Each is one matrix of the
+    // trace's height, whole LDE; its 2 width values lead the opened values and its columns the offsets
+    // (two_adic_pcs.rs:371,383).
     TS_REQUIRE(!aux || (preprocessed && slab.rows == 0 && aux->ldes.size() == 1 &&
                         aux->ldes[0].height == trace_data.ldes[0].height),
                TS_ERR_INVALID, "open: aux round shape");
-    const ColMat* xm = aux ? &aux->ldes[0] : nullptr;
-    const uint32_t aw = xm ? xm->width : 0;
-    // a preprocessed round (one matrix of the trace's height, whole LDE) is opened first, at the trace's points:
-    // its 2 pw values lead the opened values and its columns the num_reduced count (two_adic_pcs.rs:371,383)
     TS_REQUIRE(!preprocessed || (slab.rows == 0 && preprocessed->ldes.size() == 1 &&
                                  preprocessed->ldes[0].height == trace_data.ldes[0].height),
                TS_ERR_INVALID, "open: preprocessed round shape");
-    const ColMat* pm = preprocessed ? &preprocessed->ldes[0] : nullptr;
-    const uint32_t pw = pm ? pm->width : 0;
+    LeadingMats lead;
+    for (const PcsData* d : {preprocessed, aux})
+        if (d) lead.m[lead.n++] = &d->ldes[0];
     const unsigned log_n = log_N - fri_.log_blowup;
     const uint64_t n = 1ull << log_n;
     const uint64_t N = slab.rows ? slab.rows : 1ull << log_N;  // rows held here
@@ -241,140 +240,106 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
     for (auto& m : quotient_data.ldes)
         TS_REQUIRE(m.width == 4, TS_ERR_INVALID, "open: quotient chunks must have width 4");
     ctx_.ensure_twiddles(std::max(1u, log_N));
+    // the matrices opened at both points, in opening order: the leading ones, then the trace.  Raw sums and
+    // opened values are laid out in that order, 2 width words each, and the 4 qd of the chunks behind them
+    const ColMat* two_point[3];
+    uint32_t n_two = 0, max_w = 4;
+    size_t chunks_at = 0;
+    for (uint32_t i = 0; i < lead.n; i++) two_point[n_two++] = lead.m[i];
+    two_point[n_two++] = &tr;
+    for (uint32_t i = 0; i < n_two; i++) {
+        chunks_at += 2 * (size_t)two_point[i]->width;
+        max_w = std::max(max_w, two_point[i]->width);
+    }
 
     // prover.rs:92 zeta_next = trace_domain.next_point(zeta) = zeta * omega_n
     const Ef zeta_next = efc_mul_base(zeta, two_adic_generator(log_n));
     const Ef pts_mont[2] = {ef_to_mont(zeta), ef_to_mont(zeta_next)};
 
     // ---- opened values: barycentric interpolation on the low coset (two_adic_pcs.rs:358-369)
-    std::vector<Ef> raw_all(2 * (size_t)pw + 2 * (size_t)aw + 2 * (size_t)w + 4 * (size_t)qd);
-    // [-2 pw - 2 aw, -2 aw): the preprocessed sums, [col][point]; [-2 aw, 0): the aux sums of a four-round opening
-    Ef* const raw = raw_all.data() + 2 * (size_t)pw + 2 * (size_t)aw;
+    std::vector<Ef> raw(chunks_at + 4 * (size_t)qd);  // [col][point] per matrix
     DevBuf<Ef> weights(&ctx_, 2 * n);  // x_t / (z_p - x_t): the low-coset reduce below divides by them again
     {
         StageTimer t(&ctx_, "compute opened values with Lagrange interpolation");
         launch_bary_weights(ctx_, log_n, pts_mont, 2, weights.p, coset_gen);
         // the last kernels of the stage write the sums straight into the context's mailbox (host memory)
-        Ef* const mail = reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw_all.size()));
-        struct { Ef* p; } sums{mail + 2 * (size_t)pw + 2 * (size_t)aw};
-        BaryPending pend;  // the trace's partial sums and the chunks' are added up in one launch
-        if (pm) {          // and the preprocessed columns', in the same one
-            pend.capacity = xm ? 4 : 3;
-            launch_bary_dots(ctx_, *pm, log_n, weights.p, 2, mail, &pend);
+        Ef* const mail = reinterpret_cast<Ef*>(ctx_.mailbox(4 * raw.size()));
+        BaryPending pend;  // every matrix's partial sums are added up in one launch
+        pend.capacity = n_two + 1;
+        Ef* sums = mail;
+        for (uint32_t i = 0; i < n_two; i++) {
+            launch_bary_dots(ctx_, *two_point[i], log_n, weights.p, 2, sums, &pend);
+            sums += 2 * (size_t)two_point[i]->width;
         }
-        if (xm) launch_bary_dots(ctx_, *xm, log_n, weights.p, 2, mail + 2 * (size_t)pw, &pend);  // a fourth job
-        launch_bary_dots(ctx_, tr, log_n, weights.p, 2, sums.p, &pend);  // [col][point]
         ColMat all;  // lde_stage lays the chunk LDEs back to back (no width limit: the dot products take any)
         if (qd > 1 && columns_as_one_matrix(quotient_data.ldes, quotient_data.ldes[0].height, 0, all) &&
             all.width == 4 * qd) {
-            launch_bary_dots(ctx_, all, log_n, weights.p, 1, sums.p + 2 * w, &pend);
+            launch_bary_dots(ctx_, all, log_n, weights.p, 1, sums, &pend);
         } else {
             for (uint32_t c = 0; c < qd; c++)
-                launch_bary_dots(ctx_, quotient_data.ldes[c], log_n, weights.p, 1, sums.p + 2 * w + 4 * c, &pend);
+                launch_bary_dots(ctx_, quotient_data.ldes[c], log_n, weights.p, 1, sums + 4 * c, &pend);
         }
         launch_bary_finish(ctx_, pend);
-        ctx_.sync_point(mail, raw_all.size() * sizeof(Ef));
-        memcpy(raw_all.data(), mail, raw_all.size() * sizeof(Ef));
+        ctx_.sync_point(mail, raw.size() * sizeof(Ef));
+        memcpy(raw.data(), mail, raw.size() * sizeof(Ef));
     }
     // p(z) = ((z/s)^n - 1)/n * sum_i p_i x_i/(z - x_i) on the coset s*H_n (s = 31 unless sharded)
     const Ef scale[2] = {bary_scale(zeta, coset_gen, n), bary_scale(zeta_next, coset_gen, n)};
-    opened_values.assign(raw_all.size(), ef_zero());
-    for (uint32_t c = 0; c < pw; c++) {
-        opened_values[c] = efc_mul(raw_all[2 * c], scale[0]);           // preprocessed_local
-        opened_values[pw + c] = efc_mul(raw_all[2 * c + 1], scale[1]);  // preprocessed_next
+    opened_values.assign(raw.size(), ef_zero());
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_two; i++) {  // local, then next
+        opened_from_raw(&raw[at], two_point[i]->width, 2, scale, &opened_values[at]);
+        at += 2 * (size_t)two_point[i]->width;
     }
-    for (uint32_t c = 0; c < aw; c++) {
-        opened_values[2 * (size_t)pw + c] = efc_mul(raw_all[2 * (size_t)pw + 2 * c], scale[0]);           // aux_local
-        opened_values[2 * (size_t)pw + aw + c] = efc_mul(raw_all[2 * (size_t)pw + 2 * c + 1], scale[1]);  // aux_next
-    }
-    Ef* const ov = opened_values.data() + 2 * (size_t)pw + 2 * (size_t)aw;  // the trace's and the chunks', as without a key
-    for (uint32_t c = 0; c < w; c++) {
-        ov[c] = efc_mul(raw[2 * c], scale[0]);          // trace_local
-        ov[w + c] = efc_mul(raw[2 * c + 1], scale[1]);  // trace_next
-    }
-    for (uint32_t k = 0; k < 4 * qd; k++) ov[2 * w + k] = efc_mul(raw[2 * w + k], scale[0]);
+    opened_from_raw(&raw[at], 4 * qd, 1, scale, &opened_values[at]);
 
     // ---- reduce (two_adic_pcs.rs:371-383)
     StageTimer t(&ctx_, "reduce rows");
-    const uint32_t max_w = std::max(std::max(std::max(w, pw), aw), 4u);
-    std::vector<uint32_t> apow = alpha_powers_mont(alpha, max_w);
-    const Ef am = ef_to_mont(alpha);
-    // (uploaded below, together with the chunk weights: one copy on the stream instead of two)
-    auto reduced_ys = [&](const Ef* ys, uint32_t width) {  // dot_product(alpha.powers(), ys), :372
-        Ef acc = ef_zero();
-        for (uint32_t i = 0; i < width; i++) {
-            Ef ap;
-            memcpy(ap.c, &apow[4 * (size_t)i], 16);
-            acc = ef_add(acc, ef_mul(ys[i], ap));  // canonical x Montgomery -> canonical
-        }
-        return acc;
-    };
     // The reduced opening has degree < n: on wide proofs it is computed on the low coset only, where the
     // inverses are the barycentric weights, and extended like a quotient chunk on 31 H_n (open.hip)
-    const bool low = slab.rows == 0 && !pm && reduce_low_wanted(w + 4 * qd);
+    const bool low = slab.rows == 0 && lead.n == 0 && reduce_low_wanted(w + 4 * qd);
     if (!low) weights.reset();
     DevBuf<Ef> ro(&ctx_, N);
-    {
-        // offsets follow two_adic_pcs.rs:371,383: num_reduced grows by the width after every
-        // (matrix, point); all matrices share log_height here
-        TS_REQUIRE(qd <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_UNSUPPORTED, "open: more than 64 quotient chunks");
-        FusedReduceArgs a;
-        memset(&a, 0, sizeof a);
-        a.z_mont[0] = pts_mont[0];
-        a.z_mont[1] = pts_mont[1];
-        uint64_t num_reduced = 0;
-        Ef off_p[2] = {ef_zero(), ef_zero()}, kp[2] = {ef_zero(), ef_zero()};
-        for (int p = 0; pm && p < 2; p++) {
-            off_p[p] = ef_pow(am, num_reduced);
-            kp[p] = ef_mul(reduced_ys(&opened_values[(size_t)p * pw], pw), off_p[p]);
-            num_reduced += pw;
-        }
-        Ef off_a[2] = {ef_zero(), ef_zero()};
-        for (int p = 0; xm && p < 2; p++) {
-            off_a[p] = ef_pow(am, num_reduced);
-            kp[p] = ef_add(kp[p], ef_mul(reduced_ys(&opened_values[2 * (size_t)pw + (size_t)p * aw], aw), off_a[p]));
-            num_reduced += aw;
-        }
-        a.off_t[0] = ef_pow(am, num_reduced);
-        a.k0 = ef_add(kp[0], ef_mul(reduced_ys(&ov[0], w), a.off_t[0]));  // canonical x Montgomery -> canonical
-        num_reduced += w;
-        a.off_t[1] = ef_pow(am, num_reduced);
-        a.k1 = ef_add(kp[1], ef_mul(reduced_ys(&ov[w], w), a.off_t[1]));
-        num_reduced += w;
-        a.n_chunks = qd;
-        a.chunk_stride = N;
-        a.row0 = slab.row0;
-        a.rows = N;
-        std::vector<uint32_t> cw(16 * (size_t)qd);
-        for (uint32_t c = 0; c < qd; c++) {
-            TS_REQUIRE(quotient_data.ldes[c].col_stride == N, TS_ERR_INVALID, "open: chunk stride");
-            a.chunk[c] = quotient_data.ldes[c].d;
-            const Ef off_c = ef_pow(am, num_reduced);
-            a.k0 = ef_add(a.k0, ef_mul(reduced_ys(&ov[2 * w + 4 * c], 4), off_c));
-            for (int k = 0; k < 4; k++) {  // alpha^k off_c: the weight of column k of chunk c
-                Ef ap;
-                memcpy(ap.c, &apow[4 * (size_t)k], 16);
-                const Ef wk = ef_mul(ap, off_c);
-                memcpy(&cw[16 * (size_t)c + 4 * k], wk.c, 16);
-            }
-            num_reduced += 4;
-        }
-        const size_t n_apow = apow.size();
-        apow.insert(apow.end(), cw.begin(), cw.end());
-        DevBuf<uint32_t> d_apow(&ctx_, apow.size());
-        h2d(ctx_, d_apow.p, apow.data(), apow.size() * 4);
-        a.chunk_w = d_apow.p + n_apow;
-        if (low) {
-            DevBuf<uint32_t> ro_low(&ctx_, 4 * n), ro_cols(&ctx_, 4 * N);
-            launch_reduce_low(ctx_, tr, log_n, d_apow.p, a, weights.p, ro_low.p);
-            // the chunk-0 call of lde_stage (domain shift 31, so coset_lde's shift is 1), without its stage
-            // timers: the launches belong to "reduce rows"
-            coset_lde(ctx_, ro_low.p, n, 4, log_n, fri_.log_blowup, 1, ro_cols.p, N, 0, 0, false, nullptr, 0, 0,
-                      /*stage_timers=*/false);
-            launch_ef_interleave(ctx_, ro_cols.p, N, N, ro.p);
-        } else {
-            launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, pm, off_p, xm, off_a);
-        }
+    TS_REQUIRE(qd <= (uint32_t)MAX_QUOTIENT_CHUNKS, TS_ERR_UNSUPPORTED, "open: more than 64 quotient chunks");
+    FusedReduceArgs a;
+    memset(&a, 0, sizeof a);
+    a.z_mont[0] = pts_mont[0];
+    a.z_mont[1] = pts_mont[1];
+    a.n_chunks = qd;
+    a.chunk_stride = N;
+    a.row0 = slab.row0;
+    a.rows = N;
+    // every matrix shares log_height here: one height of the ledger, visited in opening order
+    AlphaLedger ledger(alpha, max_w);
+    const Ef* ys = opened_values.data();
+    for (uint32_t i = 0; i < n_two; i++) {
+        const uint32_t mw = two_point[i]->width;
+        Ef* const off = i < lead.n ? lead.off[i] : a.off_t;
+        for (int p = 0; p < 2; p++, ys += mw) off[p] = ledger.visit(log_N, ys, mw, p).off;
+    }
+    // the alpha powers and, behind them, the chunk weights: one copy on the stream instead of two
+    std::vector<uint32_t> words = ledger.powers();
+    const size_t n_apow = words.size();
+    for (uint32_t c = 0; c < qd; c++, ys += 4) {
+        TS_REQUIRE(quotient_data.ldes[c].col_stride == N, TS_ERR_INVALID, "open: chunk stride");
+        a.chunk[c] = quotient_data.ldes[c].d;
+        ledger.fold_weights(ledger.visit(log_N, ys, 4, 0).off, 4, words);  // alpha^k off_c: column k of chunk c
+    }
+    a.k0 = ledger.k(log_N, 0);
+    a.k1 = ledger.k(log_N, 1);
+    DevBuf<uint32_t> d_apow(&ctx_, words.size());
+    h2d(ctx_, d_apow.p, words.data(), words.size() * 4);
+    a.chunk_w = d_apow.p + n_apow;
+    if (low) {
+        DevBuf<uint32_t> ro_low(&ctx_, 4 * n), ro_cols(&ctx_, 4 * N);
+        launch_reduce_low(ctx_, tr, log_n, d_apow.p, a, weights.p, ro_low.p);
+        // the chunk-0 call of lde_stage (domain shift 31, so coset_lde's shift is 1), without its stage
+        // timers: the launches belong to "reduce rows"
+        coset_lde(ctx_, ro_low.p, n, 4, log_n, fri_.log_blowup, 1, ro_cols.p, N, 0, 0, false, nullptr, 0, 0,
+                  /*stage_timers=*/false);
+        launch_ef_interleave(ctx_, ro_cols.p, N, N, ro.p);
+    } else {
+        launch_reduce_fused(ctx_, tr, log_N, d_apow.p, a, ro.p, lead);
     }
     return ro;
 }
@@ -496,7 +461,6 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
                                           std::vector<Ef>& opened_values) {
     TS_REQUIRE(!rounds.empty(), TS_ERR_INVALID, "open: no rounds");
     const Ef alpha = challenger.sample();  // :312
-    const Ef am = ef_to_mont(alpha);
     uint32_t max_w = 1;
     unsigned log_global_max = 0;
     for (auto& r : rounds) {
@@ -506,13 +470,12 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
         log_global_max = std::max(log_global_max, r.data->log_height);  // :319-326
     }
     ctx_.ensure_twiddles(std::max(1u, log_global_max));
-    const std::vector<uint32_t> apow = alpha_powers_mont(alpha, max_w);
-    DevBuf<uint32_t> d_apow(&ctx_, apow.size());
-    h2d(ctx_, d_apow.p, apow.data(), apow.size() * 4);
+    AlphaLedger ledger(alpha, max_w);  // :332 num_reduced by log_height
+    DevBuf<uint32_t> d_apow(&ctx_, ledger.powers().size());
+    h2d(ctx_, d_apow.p, ledger.powers().data(), ledger.powers().size() * 4);
 
     opened_values.clear();
-    DevBuf<Ef> ro[32];            // :331 reduced_openings by log_height
-    uint64_t num_reduced[32] = {0};  // :332
+    DevBuf<Ef> ro[AlphaLedger::MAX_LOG_HEIGHT];  // :331 reduced_openings by log_height
     for (auto& r : rounds) {
         for (size_t mi = 0; mi < r.data->ldes.size(); mi++) {
             const ColMat& m = r.data->ldes[mi];
@@ -536,30 +499,22 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
                     d2h_sync(ctx_, raw.data(), sums.p, raw.size() * sizeof(Ef));
                 }
                 StageTimer t(&ctx_, "reduce rows");
+                Ef scale[2];
+                for (uint32_t p = 0; p < np; p++) scale[p] = bary_scale(pts[p0 + p], GENERATOR, n);  // low coset: s = 31
+                const size_t first = opened_values.size();
+                opened_values.resize(first + raw.size());
+                opened_from_raw(raw.data(), w, np, scale, &opened_values[first]);
                 ReduceArgs a;
                 memset(&a, 0, sizeof a);
                 a.n_points = np;
                 for (uint32_t p = 0; p < np; p++) {
-                    const Ef scale = bary_scale(pts[p0 + p], GENERATOR, n);  // the low coset: s = 31
-                    Ef rys = ef_zero();  // :372 dot_product(alpha.powers(), ys)
-                    for (uint32_t c = 0; c < w; c++) {
-                        const Ef y = efc_mul(raw[(size_t)c * np + p], scale);
-                        opened_values.push_back(y);
-                        Ef ap;
-                        memcpy(ap.c, &apow[4 * (size_t)c], 16);
-                        rys = ef_add(rys, ef_mul(y, ap));
-                    }
+                    const AlphaLedger::Visit v = ledger.visit(log_h, &opened_values[first + (size_t)p * w], w, (int)p);
                     a.z_mont[p] = pts_mont[p];
-                    a.off_mont[p] = ef_pow(am, num_reduced[log_h]);  // :371
-                    a.rys[p] = rys;
-                    num_reduced[log_h] += w;  // :383
+                    a.off_mont[p] = v.off;  // :371
+                    a.rys[p] = v.rys;       // :372
                 }
-                if (!ro[log_h].p) {
-                    ro[log_h] = DevBuf<Ef>(&ctx_, m.height);
-                    a.accumulate = 0;
-                } else {
-                    a.accumulate = 1;
-                }
+                a.accumulate = ro[log_h].p ? 1 : 0;
+                if (!ro[log_h].p) ro[log_h] = DevBuf<Ef>(&ctx_, m.height);
                 launch_reduce(ctx_, m, log_h, d_apow.p, a, ro[log_h].p);  // :375-381
             }
         }

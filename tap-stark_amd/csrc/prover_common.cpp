@@ -217,17 +217,6 @@ std::vector<uint32_t> air_consts_mont(const AirProgram& air, const uint32_t* pis
     return consts;
 }
 
-std::vector<uint32_t> alpha_powers_mont(Ef alpha, size_t count) {
-    std::vector<uint32_t> pw(4 * count);
-    const Ef am = ef_to_mont(alpha);
-    Ef cur = ef_one_mont();
-    for (size_t i = 0; i < count; i++) {
-        memcpy(&pw[4 * i], cur.c, 16);
-        cur = ef_mul(cur, am);
-    }
-    return pw;
-}
-
 Ef bary_scale(Ef point, uint32_t coset_gen, uint64_t n) {
     Ef un = efc_pow(efc_mul_base(point, inv_canon(coset_gen)), n);
     un.c[0] = sub(un.c[0], 1);

@@ -6,6 +6,7 @@
 #include <initializer_list>
 
 #include "host.hpp"
+#include "open_plan.hpp"  // alpha_powers_mont, AlphaLedger, opened_from_raw
 
 namespace ts {
 
@@ -95,8 +96,6 @@ Statement check_statement(const FriConfig& fri, const AirProgram& air, uint32_t 
 // the constant table of an AIR's program for one statement (D_CONST reads it): constants and the `n` public
 // values `pis`, Montgomery form, at least one word; refuses a public value that is not canonical
 std::vector<uint32_t> air_consts_mont(const AirProgram& air, const uint32_t* pis, size_t n);
-// alpha^0 .. alpha^(count-1) in Montgomery form, four words each
-std::vector<uint32_t> alpha_powers_mont(Ef alpha, size_t count);
 // ((z/s)^n - 1)/n, the factor in front of the barycentric sum over the coset s H_n (canonical)
 Ef bary_scale(Ef point, uint32_t coset_gen, uint64_t n);
 // split_domains (prover.rs:80): chunk c of the quotient lives on the coset base_shift * omega_{n qd}^c
