@@ -117,15 +117,14 @@ std::vector<uint32_t> public_slots(const ts::AirProgram& p, const uint32_t* valu
     return pis;
 }
 
-// The key of ts_*_pre calls: null exactly when the AIR has no preprocessed columns, else one committed matrix of
-// the AIR's preprocessed width, made on this context.  (Its height is checked against the trace's where both
-// are known: ts::check_preprocessed_key.)  Returns the PcsData or null.
-const ts::PcsData* preprocessed_key(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key) {
-    no_aux(air, "a call that takes a preprocessed key");
+// The key of the calls that take one (`call` names it in the texts): null exactly when the AIR has no preprocessed
+// columns, else one committed matrix of the AIR's preprocessed width, made on this context.  (Its height is
+// checked against the trace's where both are known: ts::check_side_matrix.)  Returns the PcsData or null.
+const ts::PcsData* preprocessed_key_any(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key, const char* call) {
     const uint32_t pw = air->a.prog().preprocessed_width;
     TS_REQUIRE((key != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
-               pw ? "null preprocessed key for an AIR with preprocessed columns"
-                  : "a preprocessed key was given for an AIR without preprocessed columns");
+               std::string(call) + (pw ? ": null preprocessed key for an AIR with preprocessed columns"
+                                       : ": a preprocessed key was given for an AIR without preprocessed columns"));
     if (!key) return nullptr;
     TS_REQUIRE(key->d && key->d->ldes.size() == 1, ts::TS_ERR_INVALID,
                "preprocessed key: exactly one committed matrix expected");
@@ -133,6 +132,40 @@ const ts::PcsData* preprocessed_key(ts_ctx* ctx, const ts_air* air, const ts_pcs
                "preprocessed key: width differs from the AIR's preprocessed width");
     TS_REQUIRE(key->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "preprocessed key was made on another context");
     return key->d.get();
+}
+// the same for the ts_*_pre calls, which take no aux source
+const ts::PcsData* preprocessed_key(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key) {
+    no_aux(air, "a call that takes a preprocessed key");
+    return preprocessed_key_any(ctx, air, key, "a call that takes a preprocessed key");
+}
+
+// The committed aux trace of the calls that take one: null exactly when the AIR has no aux columns, else one
+// committed matrix of the AIR's aux width, made on this context.  Returns the PcsData or null.
+const ts::PcsData* committed_aux(ts_ctx* ctx, const ts::AirProgram& p, const ts_pcs_data* aux_data) {
+    TS_REQUIRE((aux_data != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+               p.aux_width ? "null aux data for an AIR with aux columns"
+                           : "aux data was given for an AIR without aux columns");
+    if (!aux_data) return nullptr;
+    TS_REQUIRE(aux_data->d && aux_data->d->ldes.size() == 1 && aux_data->d->ldes[0].width == p.aux_width,
+               ts::TS_ERR_INVALID, "aux data: exactly one committed matrix of the AIR's aux width expected");
+    TS_REQUIRE(aux_data->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "aux data was made on another context");
+    return aux_data->d.get();
+}
+
+// A row-major matrix beside the trace of a ts_check_constraints* call (`what`: "preprocessed" or "aux"): null
+// exactly when the AIR has no such columns (`width` of them), else on this context, of that width and the trace's
+// height.  Appended to `side`: the caller adds the preprocessed matrix before the aux one.
+void add_side_rows(ts_ctx* ctx, const ts_matrix* m, uint32_t width, const std::string& what, const ts_matrix* trace,
+                   ts::SideRows& side) {
+    TS_REQUIRE((m != nullptr) == (width > 0), ts::TS_ERR_INVALID,
+               "check_constraints: the " + what + " matrix is needed exactly by an AIR with " + what + " columns");
+    if (!m) return;
+    TS_REQUIRE(m->m.buf.p && m->m.layout == ts::DeviceMatrix::ROW_MAJOR && m->m.buf.ctx == &ctx->ctx &&
+                   m->m.width == width && m->m.height == trace->m.height,
+               ts::TS_ERR_INVALID, "check_constraints: the " + what + " matrix must be on this context, row-major, of "
+                                   "the AIR's " + what + " width and the trace's height");
+    side.d[side.n] = m->m.buf.p;
+    side.width[side.n++] = width;
 }
 
 // the trace is consumed, like the reference's moved RowMajorMatrix
@@ -1029,35 +1062,42 @@ void ts_pcs_data_free(ts_ctx* ctx, ts_pcs_data* d) {
     delete d;
 }
 
-static ts_status quotient_chunks(ts_ctx* ctx, const ts_pcs_data* preprocessed, bool takes_key,
-                                 const ts_pcs_data* trace_data, uint32_t log_blowup, const ts_air* air,
-                                 const uint32_t* public_values, uint32_t n_public, const uint32_t alpha[4],
-                                 ts_matrix** chunks_out) {
-    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
-    return guard(ctx, [&] {
-        if (!takes_key) no_preprocessed(air, "ts_quotient_chunks");
-        const ts::PcsData* key = takes_key ? preprocessed_key(ctx, air, preprocessed) : nullptr;
-        ts_fri_config raw{log_blowup, 1, 0};
-        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));  // same [1, 8] bound as everywhere else
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        auto chunks = pcs.quotient_chunks(*trace_data->d, ready_prog(air), pis, load_ef(alpha), key);
-        for (size_t c = 0; c < chunks.size(); c++) {
-            auto m = std::make_unique<ts_matrix>();
-            m->m = std::move(chunks[c]);
-            chunks_out[c] = m.release();
-        }
-    });
+// What every ts_quotient_chunks* call does after its own admission rule: `side` holds the committed side matrices
+// it admitted, key first, then aux; `challenges` and `exposed` are null for a call that takes none.
+static void quotient_chunks(ts_ctx* ctx, const ts::AirProgram& p, const ts::SideData& side,
+                            const ts_pcs_data* trace_data, uint32_t log_blowup, const uint32_t* public_values,
+                            uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                            const uint32_t alpha[4], ts_matrix** chunks_out) {
+    ts_fri_config raw{log_blowup, 1, 0};
+    ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));  // same [1, 8] bound as everywhere else
+    const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
+    auto chunks = pcs.quotient_chunks(*trace_data->d, p, pis, load_ef(alpha), side);
+    for (size_t c = 0; c < chunks.size(); c++) {
+        auto m = std::make_unique<ts_matrix>();
+        m->m = std::move(chunks[c]);
+        chunks_out[c] = m.release();
+    }
 }
 ts_status ts_quotient_chunks(ts_ctx* ctx, const ts_pcs_data* trace_data, uint32_t log_blowup,
                              const ts_air* air, const uint32_t* public_values, uint32_t n_public,
                              const uint32_t alpha[4], ts_matrix** chunks_out) {
-    return quotient_chunks(ctx, nullptr, false, trace_data, log_blowup, air, public_values, n_public, alpha, chunks_out);
+    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
+    return guard(ctx, [&] {
+        no_preprocessed(air, "ts_quotient_chunks");
+        quotient_chunks(ctx, ready_prog(air), {}, trace_data, log_blowup, public_values, n_public, nullptr, nullptr,
+                        alpha, chunks_out);
+    });
 }
 ts_status ts_quotient_chunks_pre(ts_ctx* ctx, const ts_pcs_data* preprocessed, const ts_pcs_data* trace_data,
                                  uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
                                  uint32_t n_public, const uint32_t alpha[4], ts_matrix** chunks_out) {
-    return quotient_chunks(ctx, preprocessed, true, trace_data, log_blowup, air, public_values, n_public, alpha,
-                           chunks_out);
+    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
+    return guard(ctx, [&] {
+        ts::SideData side;
+        if (const ts::PcsData* key = preprocessed_key(ctx, air, preprocessed)) side.push_back(key);
+        quotient_chunks(ctx, ready_prog(air), side, trace_data, log_blowup, public_values, n_public, nullptr, nullptr,
+                        alpha, chunks_out);
+    });
 }
 
 ts_status ts_pcs_open_reduce(ts_ctx* ctx, const ts_fri_config* cfg, const ts_pcs_data* trace_data,
@@ -1525,52 +1565,49 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
 }
 
 // ------------------------------------------------------------------ check_constraints
-static ts_status check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed, bool takes_prep,
+// What every ts_check_constraints* call does after its own admission rule: `side` holds the row-major side
+// matrices it admitted (add_side_rows), preprocessed first, then aux; `challenges` and `exposed` are null for a
+// call that takes none.
+static void check_constraints(ts_ctx* ctx, const ts::AirProgram& p, const ts::SideRows& side, const ts_matrix* trace,
+                              const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                              const uint32_t* exposed, int64_t* first_violation) {
+    TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
+               "check_constraints: needs an uploaded (row-major, unconsumed) trace");
+    TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
+    const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
+    const std::vector<uint32_t> consts = ts::air_consts_mont(p, pis.data(), pis.size());
+    ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
+    ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
+    TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, ctx->ctx.stream));
+    TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
+    ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p, side);
+    unsigned long long v = 0;
+    TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
+    ctx->ctx.sync();
+    *first_violation = v == ~0ull ? -1 : (int64_t)v;
+}
+ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* trace,
+                               const uint32_t* public_values, uint32_t n_public,
+                               int64_t* first_violation) {
+    if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
+    *first_violation = -1;
+    return guard(ctx, [&] {
+        no_preprocessed(air, "ts_check_constraints");
+        check_constraints(ctx, air->a.prog(), {}, trace, public_values, n_public, nullptr, nullptr, first_violation);
+    });
+}
+ts_status ts_check_constraints_pre(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
                                    const ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
                                    int64_t* first_violation) {
     if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
     *first_violation = -1;
     return guard(ctx, [&] {
-        if (!takes_prep) no_preprocessed(air, "ts_check_constraints");
-        else no_aux(air, "ts_check_constraints_pre");
+        no_aux(air, "ts_check_constraints_pre");
         const ts::AirProgram& p = air->a.prog();
-        TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
-                   "check_constraints: needs an uploaded (row-major, unconsumed) trace");
-        TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
-        TS_REQUIRE((preprocessed != nullptr) == (p.preprocessed_width > 0), ts::TS_ERR_INVALID,
-                   "check_constraints: the preprocessed matrix is needed exactly by an AIR with preprocessed columns");
-        if (preprocessed)
-            TS_REQUIRE(preprocessed->m.buf.p && preprocessed->m.layout == ts::DeviceMatrix::ROW_MAJOR &&
-                           preprocessed->m.buf.ctx == &ctx->ctx && preprocessed->m.width == p.preprocessed_width &&
-                           preprocessed->m.height == trace->m.height,
-                       ts::TS_ERR_INVALID,
-                       "check_constraints: the preprocessed matrix must be uploaded on this context, row-major, of "
-                       "the AIR's preprocessed width and the trace's height");
-        TS_REQUIRE(n_public == p.n_public, ts::TS_ERR_INVALID, "check_constraints: public value count");
-        TS_REQUIRE(n_public == 0 || public_values, ts::TS_ERR_INVALID, "null public values");
-        const std::vector<uint32_t> consts = ts::air_consts_mont(p, public_values, n_public);
-        ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
-        ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
-        TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice,
-                              ctx->ctx.stream));
-        TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
-        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p,
-                                     preprocessed ? preprocessed->m.buf.p : nullptr);
-        unsigned long long v = 0;
-        TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
-        ctx->ctx.sync();
-        *first_violation = v == ~0ull ? -1 : (int64_t)v;
+        ts::SideRows side;
+        add_side_rows(ctx, preprocessed, p.preprocessed_width, "preprocessed", trace, side);
+        check_constraints(ctx, p, side, trace, public_values, n_public, nullptr, nullptr, first_violation);
     });
-}
-ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* trace,
-                               const uint32_t* public_values, uint32_t n_public,
-                               int64_t* first_violation) {
-    return check_constraints(ctx, air, nullptr, false, trace, public_values, n_public, first_violation);
-}
-ts_status ts_check_constraints_pre(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
-                                   const ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
-                                   int64_t* first_violation) {
-    return check_constraints(ctx, air, preprocessed, true, trace, public_values, n_public, first_violation);
 }
 
 // ------------------------------------------------------------------ verify
@@ -1630,23 +1667,10 @@ ts_status ts_quotient_chunks_aux(ts_ctx* ctx, const ts_pcs_data* aux_data, const
     return guard(ctx, [&] {
         no_prep_with_aux(air, "ts_quotient_chunks_aux");
         const ts::AirProgram& p = ready_prog(air);
-        TS_REQUIRE((aux_data != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
-                   p.aux_width ? "null aux data for an AIR with aux columns"
-                               : "aux data was given for an AIR without aux columns");
-        if (aux_data) {
-            TS_REQUIRE(aux_data->d && aux_data->d->ldes.size() == 1 && aux_data->d->ldes[0].width == p.aux_width,
-                       ts::TS_ERR_INVALID, "aux data: exactly one committed matrix of the AIR's aux width expected");
-            TS_REQUIRE(aux_data->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "aux data was made on another context");
-        }
-        ts_fri_config raw{log_blowup, 1, 0};
-        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));
-        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
-        auto chunks = pcs.quotient_chunks(*trace_data->d, p, pis, load_ef(alpha), aux_data ? aux_data->d.get() : nullptr);
-        for (size_t c = 0; c < chunks.size(); c++) {
-            auto m = std::make_unique<ts_matrix>();
-            m->m = std::move(chunks[c]);
-            chunks_out[c] = m.release();
-        }
+        ts::SideData side;
+        if (const ts::PcsData* a = committed_aux(ctx, p, aux_data)) side.push_back(a);
+        quotient_chunks(ctx, p, side, trace_data, log_blowup, public_values, n_public, challenges, exposed, alpha,
+                        chunks_out);
     });
 }
 
@@ -1658,29 +1682,9 @@ ts_status ts_check_constraints_aux(ts_ctx* ctx, const ts_air* air, const ts_matr
     return guard(ctx, [&] {
         no_prep_with_aux(air, "ts_check_constraints_aux");
         const ts::AirProgram& p = air->a.prog();
-        TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
-                   "check_constraints: needs an uploaded (row-major, unconsumed) trace");
-        TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
-        TS_REQUIRE((aux != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
-                   "check_constraints: the aux matrix is needed exactly by an AIR with aux columns");
-        if (aux)
-            TS_REQUIRE(aux->m.buf.p && aux->m.layout == ts::DeviceMatrix::ROW_MAJOR && aux->m.buf.ctx == &ctx->ctx &&
-                           aux->m.width == p.aux_width && aux->m.height == trace->m.height,
-                       ts::TS_ERR_INVALID,
-                       "check_constraints: the aux matrix must be on this context, row-major, of the AIR's aux width "
-                       "and the trace's height");
-        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
-        const std::vector<uint32_t> consts = ts::air_consts_mont(p, pis.data(), pis.size());
-        ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
-        ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
-        TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, ctx->ctx.stream));
-        TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
-        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p,
-                                     aux ? aux->m.buf.p : nullptr);
-        unsigned long long v = 0;
-        TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
-        ctx->ctx.sync();
-        *first_violation = v == ~0ull ? -1 : (int64_t)v;
+        ts::SideRows side;
+        add_side_rows(ctx, aux, p.aux_width, "aux", trace, side);
+        check_constraints(ctx, p, side, trace, public_values, n_public, challenges, exposed, first_violation);
     });
 }
 
@@ -1781,21 +1785,6 @@ ts_status ts_verify_aux(const ts_fri_config* cfg, const ts_air* air, ts_challeng
 
 // ------------------------------------------------------------------ LogUp aux columns
 namespace {
-// The key of the ts_*_pre_aux calls (as preprocessed_key above, for an AIR that may have aux columns too).
-const ts::PcsData* preprocessed_key_any(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key, const char* call) {
-    const uint32_t pw = air->a.prog().preprocessed_width;
-    TS_REQUIRE((key != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
-               (std::string(call) + (pw ? ": null preprocessed key for an AIR with preprocessed columns"
-                                        : ": a preprocessed key was given for an AIR without preprocessed columns")).c_str());
-    if (!key) return nullptr;
-    TS_REQUIRE(key->d && key->d->ldes.size() == 1, ts::TS_ERR_INVALID,
-               "preprocessed key: exactly one committed matrix expected");
-    TS_REQUIRE(key->d->ldes[0].width == pw, ts::TS_ERR_INVALID,
-               "preprocessed key: width differs from the AIR's preprocessed width");
-    TS_REQUIRE(key->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "preprocessed key was made on another context");
-    return key->d.get();
-}
-
 ts::LogupSpec load_logup_spec(const ts_logup_spec* spec) {
     TS_REQUIRE(spec && spec->struct_size >= sizeof(ts_logup_spec), ts::TS_ERR_INVALID, "logup: null spec or bad struct_size");
     TS_REQUIRE(spec->n_interactions >= 1 && spec->n_interactions <= ts::LOGUP_MAX_INTERACTIONS && spec->interactions,
@@ -1902,26 +1891,12 @@ ts_status ts_quotient_chunks_pre_aux(ts_ctx* ctx, const ts_pcs_data* key, const 
         return TS_ERR_INVALID;
     }
     return guard(ctx, [&] {
-        const ts::PcsData* k = preprocessed_key_any(ctx, air, key, "ts_quotient_chunks_pre_aux");
+        ts::SideData side;
+        if (const ts::PcsData* k = preprocessed_key_any(ctx, air, key, "ts_quotient_chunks_pre_aux")) side.push_back(k);
         const ts::AirProgram& p = ready_prog(air);
-        TS_REQUIRE((aux_data != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
-                   p.aux_width ? "null aux data for an AIR with aux columns"
-                               : "aux data was given for an AIR without aux columns");
-        if (aux_data) {
-            TS_REQUIRE(aux_data->d && aux_data->d->ldes.size() == 1 && aux_data->d->ldes[0].width == p.aux_width,
-                       ts::TS_ERR_INVALID, "aux data: exactly one committed matrix of the AIR's aux width expected");
-            TS_REQUIRE(aux_data->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "aux data was made on another context");
-        }
-        ts_fri_config raw{log_blowup, 1, 0};
-        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));
-        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
-        const ts::PcsData* a = aux_data ? aux_data->d.get() : nullptr;
-        auto chunks = pcs.quotient_chunks(*trace_data->d, p, pis, load_ef(alpha), k ? k : a, k ? a : nullptr);
-        for (size_t c = 0; c < chunks.size(); c++) {
-            auto m = std::make_unique<ts_matrix>();
-            m->m = std::move(chunks[c]);
-            chunks_out[c] = m.release();
-        }
+        if (const ts::PcsData* a = committed_aux(ctx, p, aux_data)) side.push_back(a);
+        quotient_chunks(ctx, p, side, trace_data, log_blowup, public_values, n_public, challenges, exposed, alpha,
+                        chunks_out);
     });
 }
 
@@ -1937,36 +1912,10 @@ ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_
     *first_violation = -1;
     return guard(ctx, [&] {
         const ts::AirProgram& p = air->a.prog();
-        TS_REQUIRE(trace->m.buf.p && trace->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
-                   "check_constraints: needs an uploaded (row-major, unconsumed) trace");
-        TS_REQUIRE(trace->m.width == p.width, ts::TS_ERR_INVALID, "check_constraints: width != AIR width");
-        auto beside = [&](const ts_matrix* m, uint32_t width, const char* what) {
-            TS_REQUIRE((m != nullptr) == (width > 0), ts::TS_ERR_INVALID,
-                       (std::string("check_constraints: the ") + what + " matrix is needed exactly by an AIR with " + what +
-                        " columns").c_str());
-            if (m)
-                TS_REQUIRE(m->m.buf.p && m->m.layout == ts::DeviceMatrix::ROW_MAJOR && m->m.buf.ctx == &ctx->ctx &&
-                               m->m.width == width && m->m.height == trace->m.height,
-                           ts::TS_ERR_INVALID,
-                           (std::string("check_constraints: the ") + what + " matrix must be on this context, row-major, of "
-                            "the AIR's " + what + " width and the trace's height").c_str());
-        };
-        beside(preprocessed, p.preprocessed_width, "preprocessed");
-        beside(aux, p.aux_width, "aux");
-        const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
-        const std::vector<uint32_t> consts = ts::air_consts_mont(p, pis.data(), pis.size());
-        ts::DevBuf<uint32_t> d_consts(&ctx->ctx, consts.size());
-        ts::DevBuf<unsigned long long> d_v(&ctx->ctx, 1);
-        TS_HIP(hipMemcpyAsync(d_consts.p, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, ctx->ctx.stream));
-        TS_HIP(hipMemsetAsync(d_v.p, 0xff, 8, ctx->ctx.stream));
-        const uint32_t* pp = preprocessed ? preprocessed->m.buf.p : nullptr;
-        const uint32_t* ap = aux ? aux->m.buf.p : nullptr;
-        ts::launch_check_constraints(ctx->ctx, p, trace->m.buf.p, trace->m.height, d_consts.p, d_v.p, pp ? pp : ap,
-                                     pp ? ap : nullptr);
-        unsigned long long v = 0;
-        TS_HIP(hipMemcpyAsync(&v, d_v.p, 8, hipMemcpyDeviceToHost, ctx->ctx.stream));
-        ctx->ctx.sync();
-        *first_violation = v == ~0ull ? -1 : (int64_t)v;
+        ts::SideRows side;
+        add_side_rows(ctx, preprocessed, p.preprocessed_width, "preprocessed", trace, side);
+        add_side_rows(ctx, aux, p.aux_width, "aux", trace, side);
+        check_constraints(ctx, p, side, trace, public_values, n_public, challenges, exposed, first_violation);
     });
 }
 
@@ -1992,7 +1941,7 @@ ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* 
                    "trace was made on another context");
         TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
         // the key's height is known against the trace's before the trace is consumed
-        if (k) ts::check_preprocessed_key(*k, p, trace->m.height << pcs.fri().log_blowup);
+        if (k) ts::check_side_matrix(*k, p, 0, trace->m.height << pcs.fri().log_blowup);
         ts::DeviceMatrix m = take_trace(trace);
         ts::AuxSource source;
         if (aux_fn) source = callback_aux_source(ctx, p, aux_fn, user, cb_status, "ts_prove_pre_aux");
@@ -2073,7 +2022,7 @@ struct LookupCall : BatchCall<ts_batch_lookup_item> {
         ts_ctx* ctx = ctxs[l];
         const std::string w = what;
         const ts::PcsData* k = preprocessed_key_any(ctx, airs[l], lanes ? lanes[l].key : nullptr, name);
-        if (k) ts::check_preprocessed_key(*k, prog, height << fri.log_blowup);
+        if (k) ts::check_side_matrix(*k, prog, 0, height << fri.log_blowup);
         const ts_matrix* kv = table(l);
         if (kv)
             TS_REQUIRE(kv->m.buf.p && kv->m.layout == ts::DeviceMatrix::ROW_MAJOR && kv->m.buf.ctx == &ctx->ctx &&

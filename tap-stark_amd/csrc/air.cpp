@@ -199,7 +199,7 @@ AirProgram compile_air(const uint32_t* tape, size_t n_words) {
                 case T_PUBLIC: emit(D_CONST, dst, add_const(0, a), 0); break;
                 case T_MAIN: emit(D_LOAD, dst, a, b); break;
                 case T_PREP: emit(D_LOAD, dst, a + 2, b); break;
-                // version 3: the aux trace takes the second matrix's load operands (the third's beside
+                // version 3: the aux trace takes side matrix 0's load operands (side matrix 1's beside
                 // preprocessed columns), challenges and exposed words the public slots after the public values
                 case T_AUX: emit(D_LOAD, dst, a + p.aux_load_base(), b); break;
                 case T_CHALLENGE: emit(D_CONST, dst, add_const(0, p.n_public + a), 0); break;

@@ -29,8 +29,7 @@ enum TapeOp : uint32_t {
 // device instruction: 4 x u32 {op, dst, a, b}.  Operands of ADD/SUB/MUL/NEG/ASSERT are register ids.
 enum DevOp : uint32_t {
     D_LOAD = 0,     // dst <- to_mont(rows[a][b = column]); a = row offset + 2 * (matrix): 0/1 main local/next,
-                    // 2/3 local/next of the second matrix (preprocessed columns, or aux columns of an AIR
-                    // without preprocessed ones), 4/5 of the third (aux columns beside preprocessed ones)
+                    // 2/3 local/next of side matrix 0, 4/5 of side matrix 1 (AirProgram::n_side)
     D_CONST = 1,    // dst <- consts[a]           (Montgomery; constants and public values)
     D_SEL = 2,      // dst <- selector a (0 first, 1 last, 2 transition)
     D_ADD = 3,
@@ -69,13 +68,13 @@ struct AirProgram {
     // version-3 tapes: the challenge-phase (aux) trace, its challenges (extension elements) and exposed words
     uint32_t aux_width = 0, n_challenges = 0, n_exposed = 0;
     uint32_t n_public = 0;
-    // The committed matrices the kernels read beside the main trace.  The second (D_LOAD a = 2, 3) is the
-    // preprocessed key if the AIR has one, else the aux trace; an AIR with both reads the aux trace as a third
-    // matrix (a = 4, 5), which only the *_pre_aux kernels and calls take.
-    uint32_t second_width() const { return preprocessed_width ? preprocessed_width : aux_width; }
-    bool second_is_aux() const { return preprocessed_width == 0 && aux_width > 0; }
-    bool has_third() const { return preprocessed_width > 0 && aux_width > 0; }
-    uint32_t third_width() const { return has_third() ? aux_width : 0; }
+    // The side matrices: the committed matrices the program reads beside the main trace, in D_LOAD operand order
+    // (side matrix i is a = 2 + 2i, 3 + 2i).  Key first, then aux: the preprocessed key if the AIR has one, then
+    // the aux trace if it has one.  The same order is the opening order and the order of every list of them
+    // (SideLdes, SideRows, LeadingMats).
+    uint32_t n_side() const { return (preprocessed_width > 0) + (aux_width > 0); }
+    bool side_is_aux(uint32_t i) const { return aux_width > 0 && i + 1 == n_side(); }
+    uint32_t side_width(uint32_t i) const { return side_is_aux(i) ? aux_width : i == 0 ? preprocessed_width : 0; }
     // D_LOAD's operand a of the aux trace's local row
     uint32_t aux_load_base() const { return preprocessed_width ? 4 : 2; }
     // The public vector the lowered program indexes: public values ++ challenge words ++ exposed words

@@ -99,6 +99,10 @@ unsigned log2_strict(uint64_t n);  // throws TS_ERR_INVALID unless n is a power 
 // data.log_height = log2 of the tallest matrix.  Fills data.tree, data.col_table, data.root.
 void mmcs_commit(Context& ctx, PcsData& data);
 
+// The committed side matrices of an AIR, one PcsData of one matrix each, in the AIR's order (air.hpp
+// AirProgram::n_side: the preprocessed key first, then the aux trace)
+using SideData = std::vector<const PcsData*>;
+
 // ------------------------------------------------------------------ PCS (TwoAdicFriPcs)
 class TwoAdicFriPcs {
 public:
@@ -115,20 +119,16 @@ public:
     // the cost is that its n x w words stay allocated until the caller releases them)
 
     // two_adic_pcs.rs:247-258 + uni-stark prover.rs:122-194,78-80
-    // preprocessed: the committed key of a version-2 AIR's preprocessed columns (one matrix of the trace's
-    // height), null for any other AIR
+    // side: the committed side matrices of the AIR (SideData above; empty for an AIR that reads the trace only)
     std::vector<DeviceMatrix> quotient_chunks(const PcsData& trace_data, const AirProgram& air,
                                               const std::vector<uint32_t>& public_values, Ef alpha,
-                                              const PcsData* preprocessed = nullptr, const PcsData* aux = nullptr);
-    // (a version-3 AIR without preprocessed columns passes its committed aux trace as `preprocessed`: the
-    // kernels' second matrix; `aux` is the committed aux trace of an AIR that has both, the third matrix)
+                                              const SideData& side = {});
 
     // two_adic_pcs.rs:312-389 for the prove() shape; returns the FRI input (N EF4, device)
-    // preprocessed != nullptr: a third round, opened FIRST and at the trace's two points, in the same pass
+    // side: one more round per side matrix, opened BEFORE the trace's in the list's order and at the trace's two
+    // points, in the same pass
     DevBuf<Ef> open_reduce(const PcsData& trace_data, const PcsData& quotient_data, Ef zeta,
-                           Ef batch_alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed = nullptr,
-                           const PcsData* aux = nullptr);
-    // aux != nullptr (with preprocessed): a fourth round, opened SECOND and at the same two points
+                           Ef batch_alpha, std::vector<Ef>& opened_values, const SideData& side = {});
 
     // The same two steps on a slab of the LDE: global rows [row0, row0 + rows) = whole cosets
     // beta0, beta0+1, ... (bit-reversed coset order), as held by one rank of the sharded prover.
@@ -142,10 +142,10 @@ public:
                                                    const AirProgram& air,
                                                    const std::vector<uint32_t>& public_values, Ef alpha,
                                                    uint32_t domain_shift = GENERATOR,
-                                                   const ColMat* prep_lde = nullptr, const ColMat* aux_lde = nullptr);
+                                                   const SideLdes& side = SideLdes());
     DevBuf<Ef> open_reduce_slab(const PcsData& trace_data, const PcsData& quotient_data, unsigned log_N,
                                 const Slab& slab, Ef zeta, Ef batch_alpha, std::vector<Ef>& opened_values,
-                                const PcsData* preprocessed = nullptr, const PcsData* aux = nullptr);
+                                const SideData& side = {});
 
     // two_adic_pcs.rs:260-419 for any rounds x matrices x points: samples the batch challenge,
     // computes the opened values ((round, matrix, point, column) order) and returns the FriProof
@@ -195,10 +195,9 @@ std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfCha
 std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                                     DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                                     const PcsData* preprocessed, const AuxSource& aux_source);
-// throws TS_ERR_INVALID unless `aux` holds exactly one matrix of the aux width of an AIR with both kinds of column
-void check_third_matrix(const PcsData& aux, const AirProgram& air, uint64_t lde_height);
-// throws TS_ERR_INVALID unless `key` holds exactly one matrix of the AIR's preprocessed width and that LDE height
-void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height);
+// throws TS_ERR_INVALID unless `data` holds exactly one committed matrix, of the width of the AIR's side matrix i
+// and of that LDE height ("preprocessed key: ..." or "aux data: ...", whichever side matrix i is)
+void check_side_matrix(const PcsData& data, const AirProgram& air, uint32_t i, uint64_t lde_height);
 
 // ------------------------------------------------------------------ prove, several tables in one proof
 // Build-defined (the reference proves one table; prove_multi.cpp): T plain AIRs (no

@@ -188,7 +188,7 @@ std::string jit_quotient_source(const AirProgram& air) {
     std::ostringstream s;
     s << kHelpers;
     emit_head(s, {"256", "k_quotient_jit", "", "    const u32 r = row_begin + blockIdx.x * 256u + threadIdx.x;\n"},
-              air.second_width() > 0, air.has_third());
+              air.n_side() >= 1, air.n_side() == 2);
     s << kAccZero;
     for (uint32_t r = 0; r < air.n_regs; r++) s << "    u32 r" << r << " = 0;\n";
     uint32_t n_assert = 0;
@@ -212,7 +212,7 @@ static std::string seg_kernel(const AirProgram& air, const SegmentPlan& plan, ui
     s << "\n";
     emit_head(s, {"256, 4", "k_quotient_seg" + std::to_string(k), ", u32* __restrict__ slab, u32 slab_rows",
                   "    const u32 t = blockIdx.x * 256u + threadIdx.x;\n    const u32 r = row_begin + t;\n"},
-              air.second_width() > 0, air.has_third());
+              air.n_side() >= 1, air.n_side() == 2);
     s << "    u32* __restrict__ S = slab + t;\n";
     auto sl = [&](uint32_t slot) { return "S[" + std::to_string(slot) + "ull * slab_rows]"; };
     if (k == 0) {

@@ -176,16 +176,19 @@ struct QuotOut {
 // be such that d[c * col_stride + r] is valid for those rows r and their `next` rows (a sharded
 // prover passes its slab pointer minus the slab's first row; whole cosets keep `next` local).
 // `shift`: the domain is shift * H_{n qd}; the selectors come from selector_table for the same shift.
+// The side matrices of an AIR (AirProgram::n_side of them, in its order: key first, then aux), as the quotient
+// reads them: committed LDEs, column-major and bit-reversed like the trace's and of its height, each with its own
+// base and stride.  One of them runs the interpreter timed as k_quotient_pre, two as k_quotient_pre_aux, or
+// specialised kernels with one (pointer, stride) parameter pair per matrix; none launches what a plain AIR does.
+constexpr uint32_t MAX_SIDE_MATS = 2;
+struct SideLdes {
+    uint32_t n = 0;
+    const ColMat* m[MAX_SIDE_MATS] = {nullptr, nullptr};
+};
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
                      const QuotOut& out, uint64_t row_begin = 0, uint64_t row_end = 0,
-                     uint32_t shift = GENERATOR, const ColMat* prep_lde = nullptr, const ColMat* aux_lde = nullptr);
-// prep_lde: the committed LDE of the preprocessed columns of a version-2 AIR (air.preprocessed_width > 0; null
-// otherwise), column-major and bit-reversed like the trace's and of its height, with its own base and stride.
-// Such an AIR runs k_quotient_pre (or specialised kernels with the two extra parameters); every other AIR
-// launches exactly what it did before.  (A version-3 AIR without preprocessed columns passes its aux LDE here.)
-// aux_lde: the committed aux LDE of an AIR with preprocessed AND aux columns (air.has_third(); null otherwise),
-// under the same shape rules; such an AIR runs k_quotient_pre_aux or specialised kernels with two more parameters.
+                     uint32_t shift = GENERATOR, const SideLdes& side = SideLdes());
 // sharded.cpp "local quotient": in place on the slab LDEs of the qd chunk matrices (4 columns each),
 // out[c] = sum_c' mix[c * qd + c'] * in[c'] per row and per column (mix: Montgomery form, device)
 void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, uint64_t rows, uint64_t col_stride,
@@ -193,12 +196,16 @@ void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, 
 
 // check_constraints.rs:11-39 on the row-major trace; *d_violation (preset to ~0) receives
 // row * 2^16 + constraint index of the first violated constraint
+// `side`: the same side matrices as their values, row-major: matrix i is n x width[i] words at d[i] (one is
+// timed as k_check_constraints_pre, two as k_check_pre_aux).  Passed to the kernel by value.
+struct SideRows {
+    uint32_t n = 0;
+    const uint32_t* d[MAX_SIDE_MATS] = {nullptr, nullptr};
+    uint32_t width[MAX_SIDE_MATS] = {0, 0};
+};
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
-                              unsigned long long* d_violation, const uint32_t* prep_row_major = nullptr,
-                              const uint32_t* aux_row_major = nullptr);
-// (prep_row_major: the n x second_width matrix of an AIR with a second matrix, null otherwise; aux_row_major: the
-// n x aux_width matrix of an AIR with preprocessed and aux columns, null otherwise: k_check_pre_aux)
+                              unsigned long long* d_violation, const SideRows& side = SideRows());
 
 // ---- open.hip --------------------------------------------------------------------------------
 // d[p][i] = x_i / (z_p - x_i) (Montgomery EF4) for the low coset 31*H_n in bit-reversed order,

@@ -106,50 +106,41 @@ std::unique_ptr<PcsData> TwoAdicFriPcs::commit(std::vector<DeviceMatrix>& evals,
 }
 
 // ------------------------------------------------------------------ quotient
-void check_preprocessed_key(const PcsData& key, const AirProgram& air, uint64_t lde_height) {
-    TS_REQUIRE(key.ldes.size() == 1, TS_ERR_INVALID, "preprocessed key: exactly one committed matrix expected");
-    // (the same check serves the committed aux trace of a version-3 AIR: the kernels' second matrix)
-    TS_REQUIRE(air.second_width() > 0 && key.ldes[0].width == air.second_width(), TS_ERR_INVALID,
-               "preprocessed key: width differs from the AIR's preprocessed width");
-    TS_REQUIRE(key.ldes[0].height == lde_height, TS_ERR_INVALID,
-               "preprocessed key: LDE height is not the trace height << log_blowup");
-}
-
-// the committed aux trace of an AIR with preprocessed and aux columns: the kernels' third matrix
-void check_third_matrix(const PcsData& aux, const AirProgram& air, uint64_t lde_height) {
-    TS_REQUIRE(aux.ldes.size() == 1, TS_ERR_INVALID, "aux data: exactly one committed matrix expected");
-    TS_REQUIRE(air.has_third() && aux.ldes[0].width == air.third_width(), TS_ERR_INVALID,
-               "aux data: width differs from the AIR's aux width");
-    TS_REQUIRE(aux.ldes[0].height == lde_height, TS_ERR_INVALID,
-               "aux data: LDE height is not the trace height << log_blowup");
+void check_side_matrix(const PcsData& data, const AirProgram& air, uint32_t i, uint64_t lde_height) {
+    const bool aux = air.side_is_aux(i);
+    const std::string what = aux ? "aux data" : "preprocessed key";
+    TS_REQUIRE(data.ldes.size() == 1, TS_ERR_INVALID, what + ": exactly one committed matrix expected");
+    TS_REQUIRE(i < air.n_side() && data.ldes[0].width == air.side_width(i), TS_ERR_INVALID,
+               what + ": width differs from the AIR's " + (aux ? "aux" : "preprocessed") + " width");
+    TS_REQUIRE(data.ldes[0].height == lde_height, TS_ERR_INVALID,
+               what + ": LDE height is not the trace height << log_blowup");
 }
 
 std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks(const PcsData& trace_data,
                                                          const AirProgram& air,
                                                          const std::vector<uint32_t>& pis, Ef alpha,
-                                                         const PcsData* preprocessed, const PcsData* aux) {
+                                                         const SideData& side) {
     TS_REQUIRE(trace_data.ldes.size() >= 1, TS_ERR_INVALID, "quotient: no trace matrix");
     TS_REQUIRE(trace_data.log_height >= fri_.log_blowup, TS_ERR_INVALID, "quotient: bad trace data");
-    if (preprocessed) check_preprocessed_key(*preprocessed, air, trace_data.ldes[0].height);
-    if (aux) check_third_matrix(*aux, air, trace_data.ldes[0].height);
+    TS_REQUIRE(side.size() <= MAX_SIDE_MATS, TS_ERR_INVALID, "quotient: more than two committed side matrices");
+    SideLdes ldes;
+    for (const PcsData* d : side) {
+        check_side_matrix(*d, air, ldes.n, trace_data.ldes[0].height);
+        ldes.m[ldes.n++] = &d->ldes[0];
+    }
     return quotient_chunks_slab(trace_data.ldes[0], trace_data.log_height - fri_.log_blowup, Slab{}, air,
-                                pis, alpha, GENERATOR, preprocessed ? &preprocessed->ldes[0] : nullptr,
-                                aux ? &aux->ldes[0] : nullptr);
+                                pis, alpha, GENERATOR, ldes);
 }
 
 std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_slab, unsigned log_n,
                                                               const Slab& slab, const AirProgram& air,
                                                               const std::vector<uint32_t>& pis, Ef alpha,
-                                                              uint32_t domain_shift, const ColMat* prep_lde,
-                                                              const ColMat* aux_lde) {
+                                                              uint32_t domain_shift, const SideLdes& side) {
     StageTimer t(&ctx_, "compute quotient polynomial");
-    TS_REQUIRE((aux_lde != nullptr) == air.has_third(), TS_ERR_INVALID,
-               "quotient: an AIR with preprocessed and aux columns needs both committed matrices, and only such an "
-               "AIR takes two");
-    TS_REQUIRE(!aux_lde || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: aux columns beside preprocessed ones on a slab");
-    TS_REQUIRE((prep_lde != nullptr) == (air.second_width() > 0), TS_ERR_INVALID,
-               "quotient: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
-    TS_REQUIRE(!prep_lde || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: preprocessed columns on a slab");
+    TS_REQUIRE(side.n == air.n_side(), TS_ERR_INVALID,
+               "quotient: an AIR needs the committed key of its preprocessed columns and the committed aux trace of "
+               "its aux columns, and only such an AIR takes them");
+    TS_REQUIRE(side.n == 0 || slab.rows == 0, TS_ERR_UNSUPPORTED, "quotient: preprocessed or aux columns on a slab");
     TS_REQUIRE(lde_slab.width == air.width, TS_ERR_INVALID, "quotient: trace width != AIR width");
     TS_REQUIRE(pis.size() == air.n_public_slots(), TS_ERR_INVALID, "quotient: wrong number of public values");
     const unsigned lqd = air.log_quotient_degree;
@@ -191,19 +182,18 @@ std::vector<DeviceMatrix> TwoAdicFriPcs::quotient_chunks_slab(const ColMat& lde_
         ColMat lde = lde_slab;
         lde.d = lde_slab.d - slab.row0;  // global row r of the slab's range lives at d[r]
         launch_quotient(ctx_, air, lde, log_n, lqd, d_consts.p, d_consts.p + n_consts, qo, row_begin, row_end,
-                        domain_shift, prep_lde, aux_lde);
+                        domain_shift, side);
     }
     return chunks;  // (the staged uploads live in the context's pinned arena: no sync needed)
 }
 
 // ------------------------------------------------------------------ open
 DevBuf<Ef> TwoAdicFriPcs::open_reduce(const PcsData& trace_data, const PcsData& quotient_data, Ef zeta,
-                                      Ef alpha, std::vector<Ef>& opened_values, const PcsData* preprocessed,
-                                      const PcsData* aux) {
+                                      Ef alpha, std::vector<Ef>& opened_values, const SideData& side) {
     TS_REQUIRE(trace_data.log_height == quotient_data.log_height, TS_ERR_INVALID,
                "open: trace and quotient LDE heights differ");
     return open_reduce_slab(trace_data, quotient_data, trace_data.log_height, Slab{}, zeta, alpha,
-                            opened_values, preprocessed, aux);
+                            opened_values, side);
 }
 
 // `slab` (rows != 0): the two PcsData hold only global rows [row0, row0 + rows) of the LDEs, which
@@ -211,22 +201,19 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce(const PcsData& trace_data, const PcsData& 
 // coset -- any coset of the LDE determines the polynomials, so every rank gets the same values.
 DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsData& quotient_data,
                                            unsigned log_N, const Slab& slab, Ef zeta, Ef alpha,
-                                           std::vector<Ef>& opened_values, const PcsData* preprocessed,
-                                           const PcsData* aux) {
+                                           std::vector<Ef>& opened_values, const SideData& side) {
     TS_REQUIRE(trace_data.ldes.size() == 1, TS_ERR_UNSUPPORTED, "open: one trace matrix expected");
-    // The rounds opened before the trace, at the trace's points, in opening order: a preprocessed round (the key)
-    // first, an aux round beside it (four rounds: key, aux, trace, chunks) second.  Each is one matrix of the
-    // trace's height, whole LDE; its 2 width values lead the opened values and its columns the offsets
-    // (two_adic_pcs.rs:371,383).
-    TS_REQUIRE(!aux || (preprocessed && slab.rows == 0 && aux->ldes.size() == 1 &&
-                        aux->ldes[0].height == trace_data.ldes[0].height),
-               TS_ERR_INVALID, "open: aux round shape");
-    TS_REQUIRE(!preprocessed || (slab.rows == 0 && preprocessed->ldes.size() == 1 &&
-                                 preprocessed->ldes[0].height == trace_data.ldes[0].height),
-               TS_ERR_INVALID, "open: preprocessed round shape");
+    // The rounds opened before the trace, at the trace's points, in opening order = the side matrices' order: a
+    // preprocessed round (the key), then an aux round (four rounds with both: key, aux, trace, chunks).  Each is
+    // one matrix of the trace's height, whole LDE; its 2 width values lead the opened values and its columns the
+    // offsets (two_adic_pcs.rs:371,383).
+    TS_REQUIRE(side.size() <= MAX_SIDE_MATS, TS_ERR_INVALID, "open: more than two rounds before the trace's");
     LeadingMats lead;
-    for (const PcsData* d : {preprocessed, aux})
-        if (d) lead.m[lead.n++] = &d->ldes[0];
+    for (const PcsData* d : side) {
+        TS_REQUIRE(slab.rows == 0 && d->ldes.size() == 1 && d->ldes[0].height == trace_data.ldes[0].height,
+                   TS_ERR_INVALID, "open: preprocessed or aux round shape");
+        lead.m[lead.n++] = &d->ldes[0];
+    }
     const unsigned log_n = log_N - fri_.log_blowup;
     const uint64_t n = 1ull << log_n;
     const uint64_t N = slab.rows ? slab.rows : 1ull << log_N;  // rows held here
@@ -538,73 +525,22 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
 }
 
 // ------------------------------------------------------------------ prove
-// `proof_version` 3 (ts_prove_pre): `preprocessed` is the committed key of the AIR's preprocessed columns (null
-// for an AIR without any).  The key is part of the statement: its root is observed first and is not in the
-// proof; its round is opened first.  Build-defined: the reference's prove stops at preprocessed width 0
-// (prover.rs:46).
-std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                            DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                            const PcsData* preprocessed, uint32_t proof_version) {
+// One body for the four proof formats.  uni-stark/src/prover.rs:25-119 is the case without
+// side matrices; the key and the challenge phase are build-defined (the reference's prove stops at preprocessed
+// width 0, prover.rs:46, and has one trace phase).
+//   `preprocessed`: the committed key of the AIR's preprocessed columns, null exactly for an AIR without any.  The
+//     key is part of the statement: its root is observed first and is not in the proof.
+//   `aux_source`: null exactly for an AIR without aux columns.  After the trace's commit come n_challenges
+//     samples, [the aux source], the aux root and every exposed word; then alpha and on as without them.
+// The quotient reads the side matrices (key, then aux) beside the trace; the opening has one round for each
+// before the trace's and the chunks', in that order.
+// `proof_version` 1 and 3 (prove): the header ends with the preprocessed width (v3 only); 4 and 5 (prove_aux,
+// prove_pre_aux): with the aux width, n_challenges, n_exposed and, v5 only, the preprocessed width.
+static std::vector<uint32_t> prove_body(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                                        DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                                        const AuxSource& aux_source, const PcsData* preprocessed,
+                                        uint32_t proof_version) {
     const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
-    TS_REQUIRE((preprocessed != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
-               "prove: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
-    if (preprocessed) {
-        check_preprocessed_key(*preprocessed, air, 1ull << st.log_N);
-        challenger.observe_commitment(preprocessed->root);
-    }
-    pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
-
-    // :50-53 commit to trace data (natural domain: shift 1)
-    std::vector<DeviceMatrix> tv;
-    tv.push_back(std::move(trace));
-    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, {1u});
-    challenger.observe_commitment(trace_data->root);  // :60
-    const Ef alpha = challenger.sample();              // :63
-
-    // :65-80 quotient on the disjoint domain, flattened and split into qd chunks
-    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, public_values, alpha, preprocessed);
-    std::unique_ptr<PcsData> quotient_data =
-        pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));  // :80-83
-    challenger.observe_commitment(quotient_data->root);                             // :84
-    const Ef zeta = challenger.sample();                                            // :91
-
-    // :94-104 open; two_adic_pcs.rs:312 batch-combination challenge first.  Same result as
-    // pcs.open({trace: [zeta, zeta_next]}, {chunks: [zeta]}), through the one-pass reduce kernel.
-    const Ef batch_alpha = challenger.sample();
-    std::vector<Ef> opened;
-    std::vector<DevBuf<Ef>> inputs;
-    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, preprocessed));
-
-    // ---- Proof (prover.rs:105-118), TSPF v1 (v3: the preprocessed width in the header, its opened values first)
-    std::vector<uint32_t> pf;
-    pf.reserve(64 + opened.size() * 4);
-    ProofWriter pw(pf);
-    pw.header(proof_version, st.log_degree, st.w, st.qd, air.preprocessed_width);
-    pw.commitment(trace_data->root, 8);
-    pw.commitment(quotient_data->root, 8);
-    pw.opened_values(opened);
-    std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
-    if (preprocessed) rounds.insert(rounds.begin(), preprocessed);
-    pcs.fri_prove(inputs, {st.log_N}, challenger, rounds, pf);
-    return pf;
-}
-
-// ------------------------------------------------------------------ prove with challenge-phase columns
-// Build-defined like the preprocessed prove (the reference has one trace phase).  Transcript: trace root,
-// n_challenges samples, [aux source], aux root, every exposed word, then alpha and on as in prove(), with the
-// aux trace where prove() has the key: second matrix of the quotient kernels, first round of the opening.
-// TSPF v4.
-// `proof_version` 5 (prove_pre_aux): `preprocessed` is the committed key of the AIR's preprocessed columns (null
-// for an AIR without any).  Its root is observed before the trace's, as in prove(); the quotient reads (key, aux,
-// trace) and the opening has four rounds: key, aux, trace, chunks.  TSPF v5 = the v4 header and one more word,
-// the preprocessed width.
-static std::vector<uint32_t> prove_challenge_phase(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                                   DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                                   const AuxSource& aux_source, const PcsData* preprocessed,
-                                                   uint32_t proof_version) {
-    const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
-    TS_REQUIRE(proof_version == 5 || air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
-               "prove_aux: preprocessed columns together with aux columns need a third matrix in the kernels");
     TS_REQUIRE((preprocessed != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
                "prove: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
     const uint32_t aw = air.aux_width;
@@ -613,18 +549,21 @@ static std::vector<uint32_t> prove_challenge_phase(TwoAdicFriPcs& pcs, const Air
     TS_REQUIRE(aw > 0 || air.n_exposed == 0, TS_ERR_INVALID, "prove_aux: exposed words without aux columns");
     TS_REQUIRE(!aw || trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
                "prove_aux: the trace must be row-major (it is handed to the aux source after its commit)");
+    SideData side;
     if (preprocessed) {
-        check_preprocessed_key(*preprocessed, air, 1ull << st.log_N);
+        check_side_matrix(*preprocessed, air, 0, 1ull << st.log_N);
         challenger.observe_commitment(preprocessed->root);
+        side.push_back(preprocessed);
     }
     pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
     const uint64_t n = trace.height;
 
+    // :50-53 commit to trace data (natural domain: shift 1)
     std::vector<DeviceMatrix> tv;
     tv.push_back(std::move(trace));
     // the LDE stage transposes a row-major trace into a buffer of its own and never writes the input: kept, not copied
     std::unique_ptr<PcsData> trace_data = pcs.commit(tv, {1u}, true, /*keep_row_major=*/aw > 0);
-    challenger.observe_commitment(trace_data->root);
+    challenger.observe_commitment(trace_data->root);  // :60
     std::vector<uint32_t> pis = public_values;
     for (uint32_t k = 0; k < air.n_challenges; k++) {
         const Ef c = challenger.sample();
@@ -645,30 +584,33 @@ static std::vector<uint32_t> prove_challenge_phase(TwoAdicFriPcs& pcs, const Air
         aux_data = pcs.commit(av, {1u});
         challenger.observe_commitment(aux_data->root);
         for (uint32_t e : exposed) challenger.observe(e);
+        side.push_back(aux_data.get());
     }
     pis.insert(pis.end(), exposed.begin(), exposed.end());
-    const Ef alpha = challenger.sample();
+    const Ef alpha = challenger.sample();  // :63
 
-    // the kernels' second matrix is the key if there is one, else the aux trace; with both the aux trace is third
-    const PcsData* second = preprocessed ? preprocessed : aux_data.get();
-    const PcsData* third = preprocessed ? aux_data.get() : nullptr;
-    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, pis, alpha, second, third);
+    // :65-80 quotient on the disjoint domain, flattened and split into qd chunks
+    std::vector<DeviceMatrix> chunks = pcs.quotient_chunks(*trace_data, air, pis, alpha, side);
     std::unique_ptr<PcsData> quotient_data =
-        pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));
-    challenger.observe_commitment(quotient_data->root);
-    const Ef zeta = challenger.sample();
+        pcs.commit(chunks, chunk_domain_shifts(GENERATOR, st.log_degree, st.lqd));  // :80-83
+    challenger.observe_commitment(quotient_data->root);                             // :84
+    const Ef zeta = challenger.sample();                                            // :91
 
+    // :94-104 open; two_adic_pcs.rs:312 batch-combination challenge first.  Same result as
+    // pcs.open({trace: [zeta, zeta_next]}, {chunks: [zeta]}), through the one-pass reduce kernel.
     const Ef batch_alpha = challenger.sample();
     std::vector<Ef> opened;
     std::vector<DevBuf<Ef>> inputs;
-    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, second, third));
+    inputs.push_back(pcs.open_reduce(*trace_data, *quotient_data, zeta, batch_alpha, opened, side));
 
+    // ---- Proof (prover.rs:105-118)
+    const bool challenge_phase = proof_version >= 4;
     std::vector<uint32_t> pf;
     pf.reserve(64 + exposed.size() + opened.size() * 4);
     ProofWriter pw(pf);
-    pw.header(proof_version, st.log_degree, st.w, st.qd, aw);
+    pw.header(proof_version, st.log_degree, st.w, st.qd, challenge_phase ? aw : air.preprocessed_width);
     const uint32_t more[3] = {air.n_challenges, air.n_exposed, air.preprocessed_width};
-    pw.words(more, proof_version == 5 ? 3 : 2);
+    if (challenge_phase) pw.words(more, proof_version == 5 ? 3 : 2);
     pw.commitment(trace_data->root, 8);
     if (aw) {
         pw.commitment(aux_data->root, 8);
@@ -676,23 +618,36 @@ static std::vector<uint32_t> prove_challenge_phase(TwoAdicFriPcs& pcs, const Air
     }
     pw.commitment(quotient_data->root, 8);
     pw.opened_values(opened);
-    std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
-    if (aw) rounds.insert(rounds.begin(), aux_data.get());
-    if (preprocessed) rounds.insert(rounds.begin(), preprocessed);
+    std::vector<const PcsData*> rounds = side;
+    rounds.push_back(trace_data.get());
+    rounds.push_back(quotient_data.get());
     pcs.fri_prove(inputs, {st.log_N}, challenger, rounds, pf);
     return pf;
 }
 
+// TSPF v1; with proof_version 3 (ts_prove_pre) TSPF v3, over (preprocessed key, trace)
+std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
+                            DeviceMatrix trace, const std::vector<uint32_t>& public_values,
+                            const PcsData* preprocessed, uint32_t proof_version) {
+    TS_REQUIRE(air.aux_width == 0 && air.n_challenges == 0 && air.n_exposed == 0, TS_ERR_INVALID,
+               "prove: the AIR has a challenge phase (aux columns, challenges or exposed words); prove_aux proves it");
+    return prove_body(pcs, air, challenger, std::move(trace), public_values, nullptr, preprocessed, proof_version);
+}
+
+// TSPF v4, over (aux trace, trace)
 std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                                 DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                                 const AuxSource& aux_source) {
-    return prove_challenge_phase(pcs, air, challenger, std::move(trace), public_values, aux_source, nullptr, 4);
+    TS_REQUIRE(air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
+               "prove_aux: preprocessed columns together with aux columns are proved by prove_pre_aux (TSPF v5)");
+    return prove_body(pcs, air, challenger, std::move(trace), public_values, aux_source, nullptr, 4);
 }
 
+// TSPF v5 = the v4 header and one more word, the preprocessed width; over (key, aux trace, trace)
 std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                                     DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                                     const PcsData* preprocessed, const AuxSource& aux_source) {
-    return prove_challenge_phase(pcs, air, challenger, std::move(trace), public_values, aux_source, preprocessed, 5);
+    return prove_body(pcs, air, challenger, std::move(trace), public_values, aux_source, preprocessed, 5);
 }
 
 // ------------------------------------------------------------------ a lookup proof inside a batch lane

@@ -13,7 +13,6 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "air.hpp"
 #include "kernels.hpp"
@@ -237,13 +236,52 @@ struct RowBase {
     }
 };
 
-// a row of the quotient domain in the column-major LDE; the constraints go into sum_i c_i alpha^(K-1-i)
+// The side matrices as the quotient kernels take them, by value and as their LAST argument: base and column stride
+// of the LDE of side matrix i < MATS - 1 (air.hpp AirProgram::n_side).  The other entries are not read; behind
+// every other argument they do not move one either, so the MATS = 1 form is instruction for instruction the
+// kernel that took no such argument.
+struct SideCols {
+    struct {
+        const uint32_t* d;
+        uint64_t stride;
+    } m[MAX_SIDE_MATS];
+};
+
+// A row of the quotient domain in MATS column-major LDEs of one height with bit-reversed rows: the trace's and
+// MATS - 1 side matrices', each with its own base and stride.  The constraints go into sum_i c_i alpha^(K-1-i).
+// One struct, and the select chain written per MATS under `if constexpr`: the form that passed the scratch, VGPR
+// and static-VALU gates (profiles/quotient_one_kernel_resources.txt).
+template <int MATS>
 struct QuotientRow : RowBase {
     uint64_t col_stride;
     const uint32_t* alpha_pows;
     uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+    // side matrix 0 (D_LOAD's a = 2, 3) and 1 (a = 4, 5); set for the matrices the kernel has.  Named members and
+    // not arrays: load() chooses between them at run time
+    const uint32_t *s0_local, *s0_next, *s1_local, *s1_next;
+    uint64_t s0_stride, s1_stride;
     __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
-        return (a ? row_next : row_local)[(uint64_t)b * col_stride];
+        if constexpr (MATS == 1) {
+            return (a ? row_next : row_local)[(uint64_t)b * col_stride];
+        } else if constexpr (MATS == 2) {
+            // all four read first and chosen with selects, as RowBase::sel: an index into the struct would put it
+            // in scratch
+            const uint32_t *p0 = row_local, *p1 = row_next, *p2 = s0_local, *p3 = s0_next;
+            const uint64_t t0 = col_stride, t1 = s0_stride;
+            const uint32_t* lo = (a & 1) ? p1 : p0;
+            const uint32_t* hi = (a & 1) ? p3 : p2;
+            return ((a & 2) ? hi : lo)[(uint64_t)b * ((a & 2) ? t1 : t0)];
+        } else {
+            // all six read first and chosen with selects
+            const uint32_t *p0 = row_local, *p1 = row_next, *p2 = s0_local, *p3 = s0_next, *p4 = s1_local,
+                           *p5 = s1_next;
+            const uint64_t t0 = col_stride, t1 = s0_stride, t2 = s1_stride;
+            const uint32_t* m0 = (a & 1) ? p1 : p0;
+            const uint32_t* m1 = (a & 1) ? p3 : p2;
+            const uint32_t* m2 = (a & 1) ? p5 : p4;
+            const uint32_t* m = (a & 4) ? m2 : ((a & 2) ? m1 : m0);
+            return m[(uint64_t)b * ((a & 4) ? t2 : ((a & 2) ? t1 : t0))];
+        }
     }
     __device__ __forceinline__ void on_assert(uint32_t c, uint32_t b) {
         const uint32_t* ap = alpha_pows + 4 * b;
@@ -254,56 +292,16 @@ struct QuotientRow : RowBase {
     }
 };
 
-// the same row of an AIR with preprocessed columns: the committed key's LDE is a second column-major matrix with
-// its own base and stride, and D_LOAD's operand a = 2, 3 reads its local / next row
-struct PrepQuotientRow : QuotientRow {
-    const uint32_t* prep_local;
-    const uint32_t* prep_next;
-    uint64_t prep_stride;
-    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
-        // all four read first and chosen with selects, as RowBase::sel: an index into the struct would put it
-        // in scratch
-        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next;
-        const uint64_t s0 = col_stride, s1 = prep_stride;
-        const uint32_t* lo = (a & 1) ? p1 : p0;
-        const uint32_t* hi = (a & 1) ? p3 : p2;
-        return ((a & 2) ? hi : lo)[(uint64_t)b * ((a & 2) ? s1 : s0)];
-    }
-};
-
-// the same row of an AIR with preprocessed AND aux columns: (key LDE, aux LDE, trace LDE), all column-major with
-// bit-reversed rows and one height; D_LOAD's operand a = 2, 3 reads the key, a = 4, 5 the aux trace
-struct PrepAuxQuotientRow : PrepQuotientRow {
-    const uint32_t* aux_local;
-    const uint32_t* aux_next;
-    uint64_t aux_stride;
-    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
-        // all six read first and chosen with selects, as PrepQuotientRow::load
-        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next, *p4 = aux_local,
-                       *p5 = aux_next;
-        const uint64_t s0 = col_stride, s1 = prep_stride, s2 = aux_stride;
-        const uint32_t* m0 = (a & 1) ? p1 : p0;
-        const uint32_t* m1 = (a & 1) ? p3 : p2;
-        const uint32_t* m2 = (a & 1) ? p5 : p4;
-        const uint32_t* m = (a & 4) ? m2 : ((a & 2) ? m1 : m0);
-        return m[(uint64_t)b * ((a & 4) ? s2 : ((a & 2) ? s1 : s0))];
-    }
-};
-
-// The row tiles of one workgroup.  MATS = 1 is k_quotient as it always was (the prep and aux arguments are
-// unused constants there); MATS = 2 (a second matrix) and 3 (a third) differ in the row type alone.
+// The interpreter over the trace LDE and MATS - 1 side LDEs; a workgroup walks its row tiles.  MATS = 1 is timed as
+// k_quotient, 2 as k_quotient_pre, 3 as k_quotient_pre_aux (launch_quotient).
 template <int NTHREADS, bool GLOBAL_REGS, int MATS>
-__device__ __forceinline__ void quotient_tiles(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-                                               const uint32_t* __restrict__ lde, uint64_t col_stride,
-                                               const uint32_t* __restrict__ prep, uint64_t prep_stride,
-                                               const uint32_t* __restrict__ aux, uint64_t aux_stride, unsigned log_n,
-                                               unsigned log_qd, const uint32_t* __restrict__ consts_mont,
-                                               const uint32_t* __restrict__ alpha_pows,
-                                               const uint32_t* __restrict__ is_first,
-                                               const uint32_t* __restrict__ is_last,
-                                               const uint32_t* __restrict__ is_transition, const QuotConsts& qc,
-                                               const QuotOut& out, uint32_t row_begin, uint32_t row_end,
-                                               uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+__global__ void __launch_bounds__(NTHREADS)
+k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
+           const uint32_t* __restrict__ lde, uint64_t col_stride, unsigned log_n, unsigned log_qd,
+           const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
+           const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
+           const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
+           uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles, SideCols side) {
     const unsigned L = log_n + log_qd;
     const uint32_t total = 1u << L;
     uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
@@ -314,18 +312,17 @@ __device__ __forceinline__ void quotient_tiles(const uint32_t* __restrict__ code
         const uint32_t i = bitrev32(rr, L);
         const uint32_t i_next = (i + (1u << log_qd)) & (total - 1);  // prover.rs:139-140,165
         const uint32_t r_next = bitrev32(i_next, L);
-        const QuotientRow base{{lde + rr, lde + r_next, is_first[rr], is_last[rr], is_transition[rr]}, col_stride, alpha_pows};
-        typename std::conditional<MATS == 3, PrepAuxQuotientRow,
-                                  typename std::conditional<MATS == 2, PrepQuotientRow, QuotientRow>::type>::type row{base};
+        QuotientRow<MATS> row{{lde + rr, lde + r_next, is_first[rr], is_last[rr], is_transition[rr]}, col_stride,
+                              alpha_pows};
         if constexpr (MATS >= 2) {
-            row.prep_local = prep + rr;
-            row.prep_next = prep + r_next;
-            row.prep_stride = prep_stride;
+            row.s0_local = side.m[0].d + rr;
+            row.s0_next = side.m[0].d + r_next;
+            row.s0_stride = side.m[0].stride;
         }
         if constexpr (MATS == 3) {
-            row.aux_local = aux + rr;
-            row.aux_next = aux + r_next;
-            row.aux_stride = aux_stride;
+            row.s1_local = side.m[1].d + rr;
+            row.s1_next = side.m[1].d + r_next;
+            row.s1_stride = side.m[1].stride;
         }
         run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
         if (!active) continue;
@@ -342,61 +339,21 @@ __device__ __forceinline__ void quotient_tiles(const uint32_t* __restrict__ code
     }
 }
 
-template <int NTHREADS, bool GLOBAL_REGS>
-__global__ void __launch_bounds__(NTHREADS)
-k_quotient(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-           const uint32_t* __restrict__ lde, uint64_t col_stride, unsigned log_n, unsigned log_qd,
-           const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
-           const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
-           const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
-           uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    quotient_tiles<NTHREADS, GLOBAL_REGS, 1>(code, n_instr, n_regs, lde, col_stride, nullptr, 0, nullptr, 0, log_n,
-                                             log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition, qc, out,
-                                             row_begin, row_end, reg_slabs, n_tiles);
-}
-
-// the interpreter over (preprocessed LDE, trace LDE): both column-major with bit-reversed rows and one height
-template <int NTHREADS, bool GLOBAL_REGS>
-__global__ void __launch_bounds__(NTHREADS)
-k_quotient_pre(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-               const uint32_t* __restrict__ lde, uint64_t col_stride, const uint32_t* __restrict__ prep,
-               uint64_t prep_stride, unsigned log_n, unsigned log_qd,
-               const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
-               const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
-               const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
-               uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    quotient_tiles<NTHREADS, GLOBAL_REGS, 2>(code, n_instr, n_regs, lde, col_stride, prep, prep_stride, nullptr, 0,
-                                             log_n, log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition,
-                                             qc, out, row_begin, row_end, reg_slabs, n_tiles);
-}
-
-// the interpreter over (preprocessed LDE, aux LDE, trace LDE): all column-major with bit-reversed rows, one height
-template <int NTHREADS, bool GLOBAL_REGS>
-__global__ void __launch_bounds__(NTHREADS)
-k_quotient_pre_aux(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-                   const uint32_t* __restrict__ lde, uint64_t col_stride, const uint32_t* __restrict__ prep,
-                   uint64_t prep_stride, const uint32_t* __restrict__ aux, uint64_t aux_stride, unsigned log_n,
-                   unsigned log_qd, const uint32_t* __restrict__ consts_mont, const uint32_t* __restrict__ alpha_pows,
-                   const uint32_t* __restrict__ is_first, const uint32_t* __restrict__ is_last,
-                   const uint32_t* __restrict__ is_transition, QuotConsts qc, QuotOut out,
-                   uint32_t row_begin, uint32_t row_end, uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    quotient_tiles<NTHREADS, GLOBAL_REGS, 3>(code, n_instr, n_regs, lde, col_stride, prep, prep_stride, aux, aux_stride,
-                                             log_n, log_qd, consts_mont, alpha_pows, is_first, is_last, is_transition,
-                                             qc, out, row_begin, row_end, reg_slabs, n_tiles);
-}
-
-// The four instantiations of an interpreter kernel template (one function type), and the name of its timer.
+// The four register-file forms of an interpreter kernel for one MATS (one function type for every MATS), and the
+// name of its timer.  A launcher keeps one table per kernel family, indexed by the number of side matrices.
 template <class F>
 struct InterpKernels {
     const char* name;
     F global64, lds256, lds128, lds64;
 };
+#define TS_INTERP_KERNELS(name, K, MATS) \
+    { name, K<64, true, MATS>, K<256, false, MATS>, K<128, false, MATS>, K<64, false, MATS> }
 
 // Launches the instantiation that the register-file plan for `rows` rows asks for; `args` are the kernel's own,
-// between the program and the register file.
-template <class F, class... Args>
+// between the program and the register file, and `side` (the side matrices, by value) is its last.
+template <class F, class Side, class... Args>
 static void launch_interpreter(Context& ctx, const InterpKernels<F>& k, const AirProgram& air, uint64_t rows,
-                               Args... args) {
+                               const Side& side, Args... args) {
     TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
     const RegFilePlan pl = plan_reg_file(ctx, air.n_regs, rows);
     DevBuf<uint32_t> slabs;
@@ -406,29 +363,27 @@ static void launch_interpreter(Context& ctx, const InterpKernels<F>& k, const Ai
     if (pl.lds_bytes > 48 * 1024)
         TS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
     TS_LAUNCH_NAMED(ctx, k.name, kernel, dim3(pl.grid), dim3(pl.nthreads), pl.lds_bytes, air.d_code,
-                    (uint32_t)(air.code.size() / 4), air.n_regs, args..., slabs.p, pl.n_tiles);
+                    (uint32_t)(air.code.size() / 4), air.n_regs, args..., slabs.p, pl.n_tiles, side);
     TS_HIP(hipGetLastError());
 }
 
 void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_lde, unsigned log_n,
                      unsigned log_qd, const uint32_t* d_consts_mont, const uint32_t* d_alpha_pows_mont,
                      const QuotOut& out, uint64_t row_begin, uint64_t row_end, uint32_t shift,
-                     const ColMat* prep_lde, const ColMat* aux_lde) {
+                     const SideLdes& side) {
     TS_REQUIRE(air.d_code != nullptr, TS_ERR_INVALID, "air program not uploaded");
-    // a third matrix exactly for an AIR with preprocessed and aux columns; same shape rules as the second
-    TS_REQUIRE((aux_lde != nullptr) == air.has_third(), TS_ERR_INVARIANT,
-               "quotient: aux LDE (third matrix) and the AIR's widths disagree");
-    if (aux_lde)
-        TS_REQUIRE(aux_lde->d && aux_lde->width == air.third_width() && aux_lde->height == trace_lde.height &&
-                       aux_lde->col_stride >= aux_lde->height,
-                   TS_ERR_INVALID, "quotient: aux LDE shape");
-    // a program with preprocessed loads never runs without the matrix they read, and the matrix covers the rows
-    TS_REQUIRE((prep_lde != nullptr) == (air.second_width() > 0), TS_ERR_INVARIANT,
-               "quotient: preprocessed LDE and the AIR's preprocessed width disagree");
-    if (prep_lde)
-        TS_REQUIRE(prep_lde->d && prep_lde->width == air.second_width() && prep_lde->height == trace_lde.height &&
-                       prep_lde->col_stride >= prep_lde->height,
-                   TS_ERR_INVALID, "quotient: preprocessed LDE shape");
+    // a program with preprocessed or aux loads never runs without the matrices they read, and they cover the rows
+    TS_REQUIRE(side.n == air.n_side(), TS_ERR_INVARIANT,
+               "quotient: the preprocessed and aux LDEs given and the AIR's preprocessed and aux widths disagree");
+    SideCols cols{};
+    for (uint32_t i = 0; i < side.n; i++) {
+        const ColMat* m = side.m[i];
+        TS_REQUIRE(m && m->d && m->width == air.side_width(i) && m->height == trace_lde.height &&
+                       m->col_stride >= m->height,
+                   TS_ERR_INVALID, air.side_is_aux(i) ? "quotient: aux LDE shape" : "quotient: preprocessed LDE shape");
+        cols.m[i].d = m->d;
+        cols.m[i].stride = m->col_stride;
+    }
     TS_REQUIRE(log_n + log_qd <= 31, TS_ERR_INVALID, "quotient domain too large");
     const uint64_t qn = 1ull << (log_n + log_qd);
     if (row_end == 0) row_end = qn;
@@ -446,23 +401,24 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
     const uint32_t* lde_p = trace_lde.d;
     uint64_t stride = trace_lde.col_stride;
     QuotOut qo = out;
-    // the specialised kernels of an AIR with preprocessed columns take (prep, prep_stride) after row_end
-    // (jit.cpp emit_head); the others have no such parameters
-    const uint32_t* prep_p = prep_lde ? prep_lde->d : nullptr;
-    uint64_t prep_stride = prep_lde ? prep_lde->col_stride : 0;
-    // and those of an AIR with both kinds of column (aux, aux_stride) after the prep pair
-    const uint32_t* aux_p = aux_lde ? aux_lde->d : nullptr;
-    uint64_t aux_stride = aux_lde ? aux_lde->col_stride : 0;
-    if (ks && !ks->seg) {
-        // specialised straight-line kernel (jit.cpp); same arguments, same results
-        void* args[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first, &is_last,
-                        &is_transition, &qc, &qo, &rb, &re, &prep_p, &prep_stride, &aux_p, &aux_stride};
-        KernelTimer kt(&ctx, "k_quotient_jit");
-        TS_HIP(hipModuleLaunchKernel((hipFunction_t)ks->fns[0], (unsigned)((total + 255) / 256), 1, 1,
-                                     256, 1, 1, 0, ctx.stream, args, nullptr));
-        return;
-    }
     if (ks) {
+        // The specialised kernels (jit.cpp emit_head): the thirteen arguments every one takes, then (pointer,
+        // stride) per side matrix, then the slab pair of a segmented kernel.  rb, re: the rows of one launch
+        uint32_t* slab_p = nullptr;
+        uint32_t slab_rows = 0;
+        std::vector<void*> args = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
+                                   &is_last, &is_transition, &qc, &qo, &rb, &re};
+        for (uint32_t i = 0; i < side.n; i++) {
+            args.push_back(&cols.m[i].d);
+            args.push_back(&cols.m[i].stride);
+        }
+        if (!ks->seg) {
+            // specialised straight-line kernel; same arguments, same results
+            KernelTimer kt(&ctx, "k_quotient_jit");
+            TS_HIP(hipModuleLaunchKernel((hipFunction_t)ks->fns[0], (unsigned)((total + 255) / 256), 1, 1,
+                                         256, 1, 1, 0, ctx.stream, args.data(), nullptr));
+            return;
+        }
         // segmented kernels (jit.cpp jit_segment_sources): per tile of rows, segments 0..K-1 in stream order,
         // values crossing a cut in a slab of [slab_width + 8][tile_rows] words from the context's pool
         const uint64_t width = (uint64_t)ks->seg->slab_width + SEG_ACC_SLOTS;
@@ -470,42 +426,25 @@ void launch_quotient(Context& ctx, const AirProgram& air, const ColMat& trace_ld
         uint64_t tile = std::max<uint64_t>(256, ((slab_mb << 18) / width) & ~(uint64_t)255);
         tile = std::min<uint64_t>(tile, (total + 255) & ~(uint64_t)255);
         DevBuf<uint32_t> slab(&ctx, (size_t)(width * tile));
-        uint32_t* slab_p = slab.p;
-        uint32_t slab_rows = (uint32_t)tile;
+        slab_p = slab.p;
+        slab_rows = (uint32_t)tile;
+        args.push_back(&slab_p);
+        args.push_back(&slab_rows);
         KernelTimer kt(&ctx, "k_quotient_seg");
         for (uint64_t t0 = row_begin; t0 < row_end; t0 += tile) {
-            uint32_t tb = (uint32_t)t0, te = (uint32_t)std::min<uint64_t>(row_end, t0 + tile);
-            void* args_main[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
-                                 &is_last, &is_transition, &qc, &qo, &tb, &te, &slab_p, &slab_rows};
-            void* args_prep[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
-                                 &is_last, &is_transition, &qc, &qo, &tb, &te, &prep_p, &prep_stride, &slab_p,
-                                 &slab_rows};
-            void* args_prep_aux[] = {&lde_p, &stride, &log_n, &log_qd, &d_consts_mont, &d_alpha_pows_mont, &is_first,
-                                     &is_last, &is_transition, &qc, &qo, &tb, &te, &prep_p, &prep_stride, &aux_p,
-                                     &aux_stride, &slab_p, &slab_rows};
-            void** args = aux_lde ? args_prep_aux : prep_lde ? args_prep : args_main;
-            const unsigned grid = (unsigned)((te - tb + 255) / 256);
+            rb = (uint32_t)t0;
+            re = (uint32_t)std::min<uint64_t>(row_end, t0 + tile);
+            const unsigned grid = (unsigned)((re - rb + 255) / 256);
             for (void* fn : ks->fns)
-                TS_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 256, 1, 1, 0, ctx.stream, args, nullptr));
+                TS_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, 256, 1, 1, 0, ctx.stream, args.data(),
+                                             nullptr));
         }
         return;
     }
-    static const InterpKernels<decltype(&k_quotient<64, true>)> kernels{
-        "k_quotient", k_quotient<64, true>, k_quotient<256, false>, k_quotient<128, false>, k_quotient<64, false>};
-    static const InterpKernels<decltype(&k_quotient_pre<64, true>)> kernels_pre{
-        "k_quotient_pre", k_quotient_pre<64, true>, k_quotient_pre<256, false>, k_quotient_pre<128, false>,
-        k_quotient_pre<64, false>};
-    static const InterpKernels<decltype(&k_quotient_pre_aux<64, true>)> kernels_pre_aux{
-        "k_quotient_pre_aux", k_quotient_pre_aux<64, true>, k_quotient_pre_aux<256, false>,
-        k_quotient_pre_aux<128, false>, k_quotient_pre_aux<64, false>};
-    if (aux_lde)
-        return launch_interpreter(ctx, kernels_pre_aux, air, total, lde_p, stride, prep_p, prep_stride, aux_p,
-                                  aux_stride, log_n, log_qd, d_consts_mont, d_alpha_pows_mont, is_first, is_last,
-                                  is_transition, qc, qo, rb, re);
-    if (prep_lde)
-        return launch_interpreter(ctx, kernels_pre, air, total, lde_p, stride, prep_p, prep_stride, log_n, log_qd,
-                                  d_consts_mont, d_alpha_pows_mont, is_first, is_last, is_transition, qc, qo, rb, re);
-    launch_interpreter(ctx, kernels, air, total, lde_p, stride, log_n, log_qd, d_consts_mont,
+    static const InterpKernels<decltype(&k_quotient<64, true, 1>)> kernels[MAX_SIDE_MATS + 1] = {
+        TS_INTERP_KERNELS("k_quotient", k_quotient, 1), TS_INTERP_KERNELS("k_quotient_pre", k_quotient, 2),
+        TS_INTERP_KERNELS("k_quotient_pre_aux", k_quotient, 3)};
+    launch_interpreter(ctx, kernels[side.n], air, total, cols, lde_p, stride, log_n, log_qd, d_consts_mont,
                        d_alpha_pows_mont, is_first, is_last, is_transition, qc, qo, rb, re);
 }
 
@@ -554,98 +493,59 @@ void launch_chunk_mix(Context& ctx, uint32_t* const* d_chunk_ptrs, uint32_t qd, 
 // is_last_row = (i == h-1), is_transition = (i != h-1) and the next row wrapping around.
 // One thread per row of the row-major trace; the first violation (row * 2^16 + constraint index,
 // smallest wins) is left in *violation.
-// a row of the row-major trace; the first constraint that does not vanish goes into `bad`
+// A row of the row-major trace and of the MATS - 1 row-major side matrices of its height beside it (D_LOAD's
+// a = 2, 3 and a = 4, 5); the first constraint that does not vanish goes into `bad`.  As QuotientRow: one struct,
+// the select chain per MATS.
+template <int MATS>
 struct CheckRow : RowBase {
     uint64_t i;  // this row
     unsigned long long& bad;
-    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const { return (a ? row_next : row_local)[b]; }
+    const uint32_t *s0_local, *s0_next, *s1_local, *s1_next;
+    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
+        if constexpr (MATS == 1) {
+            return (a ? row_next : row_local)[b];
+        } else if constexpr (MATS == 2) {
+            const uint32_t *p0 = row_local, *p1 = row_next, *p2 = s0_local, *p3 = s0_next;
+            const uint32_t* lo = (a & 1) ? p1 : p0;
+            const uint32_t* hi = (a & 1) ? p3 : p2;
+            return ((a & 2) ? hi : lo)[b];
+        } else {
+            const uint32_t *p0 = row_local, *p1 = row_next, *p2 = s0_local, *p3 = s0_next, *p4 = s1_local,
+                           *p5 = s1_next;
+            const uint32_t* m0 = (a & 1) ? p1 : p0;
+            const uint32_t* m1 = (a & 1) ? p3 : p2;
+            const uint32_t* m2 = (a & 1) ? p5 : p4;
+            return ((a & 4) ? m2 : ((a & 2) ? m1 : m0))[b];
+        }
+    }
     __device__ __forceinline__ void on_assert(uint32_t c, uint32_t b) {
         if (c != 0 && bad == ~0ull) bad = i * 65536ull + b;
     }
 };
 
-// the same with a row-major preprocessed matrix of the same height beside the trace (operand a = 2, 3)
-struct PrepCheckRow : CheckRow {
-    const uint32_t* prep_local;
-    const uint32_t* prep_next;
-    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
-        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next;
-        const uint32_t* lo = (a & 1) ? p1 : p0;
-        const uint32_t* hi = (a & 1) ? p3 : p2;
-        return ((a & 2) ? hi : lo)[b];
-    }
-};
-
-template <int NTHREADS, bool GLOBAL_REGS>
-__global__ void __launch_bounds__(NTHREADS)
-k_check_constraints_pre(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-                        const uint32_t* __restrict__ trace, uint32_t width, const uint32_t* __restrict__ prep,
-                        uint32_t prep_width, uint64_t n, const uint32_t* __restrict__ consts_mont,
-                        unsigned long long* __restrict__ violation, uint32_t* __restrict__ reg_slabs,
-                        uint32_t n_tiles) {
-    uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t i = (uint64_t)tile * NTHREADS + threadIdx.x;
-        const bool active = i < n;
-        const uint64_t ii = active ? i : 0, nx = (ii + 1) % n;
-        unsigned long long bad = ~0ull;
-        PrepCheckRow row{{{trace + ii * width, trace + nx * width, ii == 0 ? R_MOD_P : 0u, ii == n - 1 ? R_MOD_P : 0u,
-                           ii != n - 1 ? R_MOD_P : 0u}, ii, bad}, prep + ii * prep_width, prep + nx * prep_width};
-        run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
-        if (active && bad != ~0ull) atomicMin(violation, bad);
-    }
-}
-
-// the same with two row-major matrices of the trace's height beside it: preprocessed (a = 2, 3), aux (a = 4, 5)
-struct PrepAuxCheckRow : PrepCheckRow {
-    const uint32_t* aux_local;
-    const uint32_t* aux_next;
-    __device__ __forceinline__ uint32_t load(uint32_t a, uint32_t b) const {
-        const uint32_t *p0 = row_local, *p1 = row_next, *p2 = prep_local, *p3 = prep_next, *p4 = aux_local,
-                       *p5 = aux_next;
-        const uint32_t* m0 = (a & 1) ? p1 : p0;
-        const uint32_t* m1 = (a & 1) ? p3 : p2;
-        const uint32_t* m2 = (a & 1) ? p5 : p4;
-        return ((a & 4) ? m2 : ((a & 2) ? m1 : m0))[b];
-    }
-};
-
-template <int NTHREADS, bool GLOBAL_REGS>
-__global__ void __launch_bounds__(NTHREADS)
-k_check_pre_aux(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
-                const uint32_t* __restrict__ trace, uint32_t width, const uint32_t* __restrict__ prep,
-                uint32_t prep_width, const uint32_t* __restrict__ aux, uint32_t aux_width, uint64_t n,
-                const uint32_t* __restrict__ consts_mont, unsigned long long* __restrict__ violation,
-                uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
-    uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t i = (uint64_t)tile * NTHREADS + threadIdx.x;
-        const bool active = i < n;
-        const uint64_t ii = active ? i : 0, nx = (ii + 1) % n;
-        unsigned long long bad = ~0ull;
-        PrepAuxCheckRow row{{{{trace + ii * width, trace + nx * width, ii == 0 ? R_MOD_P : 0u,
-                               ii == n - 1 ? R_MOD_P : 0u, ii != n - 1 ? R_MOD_P : 0u}, ii, bad},
-                             prep + ii * prep_width, prep + nx * prep_width},
-                            aux + ii * aux_width, aux + nx * aux_width};
-        run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
-        if (active && bad != ~0ull) atomicMin(violation, bad);
-    }
-}
-
-template <int NTHREADS, bool GLOBAL_REGS>
+// MATS = 1 is timed as k_check_constraints, 2 as k_check_constraints_pre, 3 as k_check_pre_aux
+template <int NTHREADS, bool GLOBAL_REGS, int MATS>
 __global__ void __launch_bounds__(NTHREADS)
 k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_t n_regs,
                     const uint32_t* __restrict__ trace, uint32_t width, uint64_t n,
                     const uint32_t* __restrict__ consts_mont, unsigned long long* __restrict__ violation,
-                    uint32_t* __restrict__ reg_slabs, uint32_t n_tiles) {
+                    uint32_t* __restrict__ reg_slabs, uint32_t n_tiles, SideRows side) {
     uint32_t* my = lane_regs<NTHREADS, GLOBAL_REGS>(reg_slabs, n_regs);
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t i = (uint64_t)tile * NTHREADS + threadIdx.x;
         const bool active = i < n;
-        const uint64_t ii = active ? i : 0;
+        const uint64_t ii = active ? i : 0, nx = (ii + 1) % n;
         unsigned long long bad = ~0ull;
-        CheckRow row{{trace + ii * width, trace + ((ii + 1) % n) * width, ii == 0 ? R_MOD_P : 0u,
-                      ii == n - 1 ? R_MOD_P : 0u, ii != n - 1 ? R_MOD_P : 0u}, ii, bad};
+        CheckRow<MATS> row{{trace + ii * width, trace + nx * width, ii == 0 ? R_MOD_P : 0u, ii == n - 1 ? R_MOD_P : 0u,
+                            ii != n - 1 ? R_MOD_P : 0u}, ii, bad};
+        if constexpr (MATS >= 2) {
+            row.s0_local = side.d[0] + ii * side.width[0];
+            row.s0_next = side.d[0] + nx * side.width[0];
+        }
+        if constexpr (MATS == 3) {
+            row.s1_local = side.d[1] + ii * side.width[1];
+            row.s1_next = side.d[1] + nx * side.width[1];
+        }
         run_program<NTHREADS>(code, n_instr, consts_mont, my, row);
         if (active && bad != ~0ull) atomicMin(violation, bad);
     }
@@ -653,30 +553,22 @@ k_check_constraints(const uint32_t* __restrict__ code, uint32_t n_instr, uint32_
 
 void launch_check_constraints(Context& ctx, const AirProgram& air, const uint32_t* trace_row_major,
                               uint64_t n, const uint32_t* d_consts_mont,
-                              unsigned long long* d_violation, const uint32_t* prep_row_major,
-                              const uint32_t* aux_row_major) {
-    TS_REQUIRE((aux_row_major != nullptr) == air.has_third(), TS_ERR_INVARIANT,
-               "check_constraints: aux matrix (third matrix) and the AIR's widths disagree");
-    TS_REQUIRE((prep_row_major != nullptr) == (air.second_width() > 0), TS_ERR_INVARIANT,
-               "check_constraints: preprocessed matrix and the AIR's preprocessed width disagree");
+                              unsigned long long* d_violation, const SideRows& side) {
+    TS_REQUIRE(side.n == air.n_side(), TS_ERR_INVARIANT,
+               "check_constraints: the preprocessed and aux matrices given and the AIR's preprocessed and aux widths "
+               "disagree");
+    for (uint32_t i = 0; i < side.n; i++)
+        TS_REQUIRE(side.d[i] && side.width[i] == air.side_width(i), TS_ERR_INVALID,
+                   air.side_is_aux(i) ? "check_constraints: aux matrix shape"
+                                      : "check_constraints: preprocessed matrix shape");
     // the report is row * 2^16 + constraint index (the oracle's and stark.py's format)
     TS_REQUIRE(air.n_constraints <= 65536, TS_ERR_UNSUPPORTED, "check_constraints: more than 65536 constraints");
-    static const InterpKernels<decltype(&k_check_constraints<64, true>)> kernels{
-        "k_check_constraints", k_check_constraints<64, true>, k_check_constraints<256, false>,
-        k_check_constraints<128, false>, k_check_constraints<64, false>};
-    static const InterpKernels<decltype(&k_check_constraints_pre<64, true>)> kernels_pre{
-        "k_check_constraints_pre", k_check_constraints_pre<64, true>, k_check_constraints_pre<256, false>,
-        k_check_constraints_pre<128, false>, k_check_constraints_pre<64, false>};
-    static const InterpKernels<decltype(&k_check_pre_aux<64, true>)> kernels_pre_aux{
-        "k_check_pre_aux", k_check_pre_aux<64, true>, k_check_pre_aux<256, false>, k_check_pre_aux<128, false>,
-        k_check_pre_aux<64, false>};
-    if (aux_row_major)
-        return launch_interpreter(ctx, kernels_pre_aux, air, n, trace_row_major, air.width, prep_row_major,
-                                  air.second_width(), aux_row_major, air.third_width(), n, d_consts_mont, d_violation);
-    if (prep_row_major)
-        return launch_interpreter(ctx, kernels_pre, air, n, trace_row_major, air.width, prep_row_major,
-                                  air.second_width(), n, d_consts_mont, d_violation);
-    launch_interpreter(ctx, kernels, air, n, trace_row_major, air.width, n, d_consts_mont, d_violation);
+    static const InterpKernels<decltype(&k_check_constraints<64, true, 1>)> kernels[MAX_SIDE_MATS + 1] = {
+        TS_INTERP_KERNELS("k_check_constraints", k_check_constraints, 1),
+        TS_INTERP_KERNELS("k_check_constraints_pre", k_check_constraints, 2),
+        TS_INTERP_KERNELS("k_check_pre_aux", k_check_constraints, 3)};
+    launch_interpreter(ctx, kernels[side.n], air, n, side, trace_row_major, air.width, n, d_consts_mont, d_violation);
 }
+#undef TS_INTERP_KERNELS
 
 }  // namespace ts

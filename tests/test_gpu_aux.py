@@ -34,6 +34,7 @@ TS_ERR_INVALID, TS_ERR_UNSUPPORTED, TS_ERR_INVARIANT = 1, 4, 5
 SEEDS = [s for s in range(36) if random_air_case(s)[0].width() >= 2]
 VALID_SEEDS = [s for s in SEEDS if s % 3 == 0]
 SEGMENT_SEEDS = [0, 6, 9, 12, 21, 27]
+TALL_SEED = next(s for s in VALID_SEEDS if random_air_case(s)[0].valid)  # checked again at n = 2^10
 WAIT_JIT_INSTR = 3000  # larger programs stay on the interpreter in the specialised pass, as in test_gpu_air_fuzz.py
 
 
@@ -256,11 +257,14 @@ def test_quotient_segmented(ctx, cases, monkeypatch, seed):
 
 
 # ------------------------------------------------------------------ 3. check_constraints
-def test_check_constraints_over_aux_and_main(ctx, orc, cases, monkeypatch):
+def test_check_constraints_over_aux_and_main(ctx, orc, cases, monkeypatch, global_slab=False):
     n_bad = 0
     for seed in SEEDS:
         case = cases[seed]
         cair = _compile(ctx, case.v3, monkeypatch, False)
+        if global_slab:  # read at every launch: the register file goes to the global slab from here on
+            monkeypatch.setenv("TS_INTERP_LDS_MAX_REGS", "1")
+            assert cair.program()["n_regs"] > 1
         n = 1 << case.log_n
         check = lambda aux, main: ts.check_constraints(cair, main, case.pis, ctx, aux=aux, challenges=case.ch,
                                                        exposed=case.ex)
@@ -277,6 +281,31 @@ def test_check_constraints_over_aux_and_main(ctx, orc, cases, monkeypatch):
         assert check(bad_aux, case.main) == \
             orc.check_constraints(case.joined_tape, np.hstack([bad_aux, case.main]), case.joined_pis), seed
     assert n_bad >= 10 and len(VALID_SEEDS) >= 10
+
+
+def test_check_constraints_over_aux_and_main_global_slab(ctx, orc, cases, monkeypatch):
+    """The same through k_check_constraints_pre<64, true> (the aux trace is the one side matrix): one 64-lane tile
+    mostly inactive (n = 2) and exactly full (n = 2^6) among the seeded cases, then n = 2^10, sixteen tiles, which
+    they do not reach: a valid trace, and a cell changed in the last tile but one."""
+    assert {1, 6} <= {cases[s].log_n for s in SEEDS}
+    test_check_constraints_over_aux_and_main(ctx, orc, cases, monkeypatch, global_slab=True)
+    case = cases[TALL_SEED]
+    n, r = 1 << 10, (1 << 10) - 70
+    joined, all_pis, _ = generate_random_air_trace(case.air, n)
+    joined = np.ascontiguousarray(joined, dtype=np.uint32)
+    pis, ch, ex = split_publics(all_pis)
+    joined_pis = np.concatenate([pis, ch, ex]).astype(np.uint32)
+    cair = _compile(ctx, case.v3, monkeypatch, False)
+    check = lambda m: ts.check_constraints(cair, np.ascontiguousarray(m[:, case.A:]), pis, ctx,
+                                           aux=np.ascontiguousarray(m[:, :case.A]), challenges=ch, exposed=ex)
+    assert check(joined) == -1 == orc.check_constraints(case.joined_tape, joined, joined_pis)
+    late = []
+    for col in (0, joined.shape[1] - 1):  # an aux cell, a main cell
+        bad = joined.copy()
+        bad[r, col] ^= 1
+        late.append(orc.check_constraints(case.joined_tape, bad, joined_pis))
+        assert check(bad) == late[-1], col
+    assert max(late) >> 16 >= r - 1
 
 
 # ------------------------------------------------------------------ 4. whole proofs

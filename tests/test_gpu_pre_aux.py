@@ -279,12 +279,21 @@ def test_quotient_argument_refusals(ctx, wrap_cases, monkeypatch):
 
 
 # ------------------------------------------------------------------ 2. check_constraints
-def test_check_constraints_wrap_air(ctx, orc, wrap_cases, monkeypatch):
+def _global_slab(monkeypatch, cair):
+    """The interpreter's register file goes to the global slab from here on, as _compile_path("interp_global") sends
+    it: k_check_pre_aux<64, true> runs instead of the LDS forms."""
+    monkeypatch.setenv("TS_INTERP_LDS_MAX_REGS", "1")
+    assert cair.program()["n_regs"] > 1
+
+
+def test_check_constraints_wrap_air(ctx, orc, wrap_cases, monkeypatch, global_slab=False):
     """-1 on valid traces; one changed cell in each of the three matrices in turn is reported with the row and
     constraint the oracle's check of the joined AIR reports.  A cell of row 0 read only through `next` shows at the
     wrap-around row n - 1, constraint 0."""
     for d in (2, 3, 5):
         cair = _compile(ctx, WrapAir(d).tape(), monkeypatch, False)
+        if global_slab:
+            _global_slab(monkeypatch, cair)
         for case in wrap_cases[d]:
             if case.b != max(case.lqd, 1):
                 continue
@@ -308,10 +317,19 @@ def test_check_constraints_wrap_air(ctx, orc, wrap_cases, monkeypatch):
                 assert got == want(*mats) and got >= 0, (d, n, which)
 
 
-def test_check_constraints_random_splits(ctx, orc, split_cases, monkeypatch):
+def test_check_constraints_wrap_air_global_slab(ctx, orc, wrap_cases, monkeypatch):
+    """The same through k_check_pre_aux<64, true>.  n = 2: the wrap-around row beside 62 inactive lanes of the one
+    64-lane tile; n = 2^6: exactly one full tile; n = 2^10: a grid-stride walk over several."""
+    assert {1, 6, 10} <= {c.log_n for c in wrap_cases[3]}
+    test_check_constraints_wrap_air(ctx, orc, wrap_cases, monkeypatch, global_slab=True)
+
+
+def test_check_constraints_random_splits(ctx, orc, split_cases, monkeypatch, global_slab=False):
     n_valid = 0
     for (seed, which), case in split_cases.items():
         cair = _compile(ctx, case.tape, monkeypatch, False)
+        if global_slab:
+            _global_slab(monkeypatch, cair)
         n = 1 << case.log_n
         check = lambda prep, aux, main: ts.check_constraints(cair, main, case.pis, ctx, preprocessed=prep, aux=aux,
                                                              challenges=case.ch, exposed=case.ex)
@@ -325,6 +343,10 @@ def test_check_constraints_random_splits(ctx, orc, split_cases, monkeypatch):
             assert check(*mats) == orc.check_constraints(case.joined_tape, np.hstack(mats), case.joined_pis), \
                 (seed, which, k)
     assert n_valid >= 6
+
+
+def test_check_constraints_random_splits_global_slab(ctx, orc, split_cases, monkeypatch):
+    test_check_constraints_random_splits(ctx, orc, split_cases, monkeypatch, global_slab=True)
 
 
 # ------------------------------------------------------------------ 3. ts_logup_aux_build_pre

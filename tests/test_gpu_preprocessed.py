@@ -32,6 +32,7 @@ TS_ERR_INVALID, TS_ERR_UNSUPPORTED = 1, 4
 SEEDS = [s for s in range(36) if random_air_case(s)[0].width() >= 2]
 VALID_SEEDS = [s for s in SEEDS if s % 3 == 0]
 SEGMENT_SEEDS = [0, 6, 9, 12, 21, 27]
+TALL_SEED = next(s for s in VALID_SEEDS if random_air_case(s)[0].valid)  # proved again at n = 2^10
 WAIT_JIT_INSTR = 3000  # larger programs stay on the interpreter in the specialised pass, as in test_gpu_air_fuzz.py
 
 
@@ -180,10 +181,13 @@ def test_quotient_global_slab_interpreter(ctx):
 
 
 # ------------------------------------------------------------------ B. check_constraints
-def test_check_constraints_over_two_matrices(ctx, orc, cases, monkeypatch):
+def test_check_constraints_over_two_matrices(ctx, orc, cases, monkeypatch, global_slab=False):
     for seed in VALID_SEEDS:
         case = cases[seed]
         cair = _compile(ctx, case.v2, monkeypatch, False)
+        if global_slab:  # read at every launch: the register file goes to the global slab from here on
+            monkeypatch.setenv("TS_INTERP_LDS_MAX_REGS", "1")
+            assert cair.program()["n_regs"] > 1
         joined_tape = join_tape(case.v2)
         assert (joined_tape == case.v1).all()
         n = 1 << case.log_n
@@ -197,6 +201,29 @@ def test_check_constraints_over_two_matrices(ctx, orc, cases, monkeypatch):
         bad_prep[(seed * 5) % n, seed % case.pw] ^= 1
         assert ts.check_constraints(cair, case.main, case.pis, ctx, preprocessed=bad_prep) == \
             orc.check_constraints(joined_tape, np.hstack([bad_prep, case.main]), case.pis), seed
+
+
+def test_check_constraints_over_two_matrices_global_slab(ctx, orc, cases, monkeypatch):
+    """The same through k_check_constraints_pre<64, true>: one 64-lane tile mostly inactive (n = 2) and exactly full
+    (n = 2^6) among the seeded cases, then n = 2^10, sixteen tiles, which they do not reach: a valid trace, and a
+    cell changed in the last tile but one."""
+    assert {1, 6} <= {cases[s].log_n for s in VALID_SEEDS}
+    test_check_constraints_over_two_matrices(ctx, orc, cases, monkeypatch, global_slab=True)
+    case = cases[TALL_SEED]
+    n, r = 1 << 10, (1 << 10) - 70
+    joined, pis, _ = generate_random_air_trace(case.air, n)
+    joined = np.ascontiguousarray(joined, dtype=np.uint32)
+    cair = _compile(ctx, case.v2, monkeypatch, False)
+    check = lambda m: ts.check_constraints(cair, np.ascontiguousarray(m[:, case.pw:]), pis, ctx,
+                                           preprocessed=np.ascontiguousarray(m[:, :case.pw]))
+    assert check(joined) == -1 == orc.check_constraints(case.v1, joined, pis)
+    late = []
+    for col in (0, joined.shape[1] - 1):  # a preprocessed cell, a main cell
+        bad = joined.copy()
+        bad[r, col] ^= 1
+        late.append(orc.check_constraints(case.v1, bad, pis))
+        assert check(bad) == late[-1], col
+    assert max(late) >> 16 >= r - 1
 
 
 # ------------------------------------------------------------------ C. whole proofs
