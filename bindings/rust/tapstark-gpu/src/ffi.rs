@@ -159,6 +159,44 @@ pub struct ts_multi_table {
     pub public_values: *const u32,
 }
 
+/// One table of `ts_prove_multi_bus`: a `ts_multi_table` whose AIR may have LogUp aux columns (2 challenges, 4
+/// exposed words), built by the library from `logup` (null exactly for an AIR without aux columns).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ts_multi_bus_table {
+    pub struct_size: u32, // = size_of::<ts_multi_bus_table>()
+    pub n_public: u32,
+    pub air: *const ts_air,
+    pub trace: *mut ts_matrix, // consumed; row-major where the AIR has aux columns
+    pub public_values: *const u32,
+    pub logup: *const ts_logup_spec,
+}
+
+/// `ts_logup_bus_looker`: the lookups one looker trace brings to `ts_logup_multiplicities_bus`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_logup_bus_looker {
+    pub n_lookups: u32,
+    pub pad: u32,
+    pub lookups: *const ts_logup_term, // n_lookups * n_values, over this looker's row
+    pub weights: *const ts_logup_term, // n_lookups
+}
+
+/// `ts_logup_mult_bus_spec` (struct_size first): the table's tuple over the table trace, the lookers, and the
+/// column of the table trace that receives the multiplicities.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_logup_mult_bus_spec {
+    pub struct_size: u32,
+    pub n_values: u32,
+    pub table: *const ts_logup_term,
+    pub n_lookers: u32,
+    pub out_column: u32,
+    pub lookers: *const ts_logup_bus_looker,
+    pub negate: u32,
+    pub pad: u32,
+}
+
 /// One statement of `ts_prove_batch_lookup`: `ts_batch_item`'s inputs, the aux source (exactly one of `logup` /
 /// `aux_fn` for an AIR with aux columns), the multiplicity fills, then what the library writes back.
 #[repr(C)]
@@ -359,6 +397,26 @@ extern "C" {
     pub fn ts_verify_multi(cfg: *const ts_fri_config, chal: *mut ts_challenger, airs: *const *const ts_air,
                            n_tables: u32, public_values: *const *const u32, n_public: *const u32, proof: *const u32,
                            n_words: usize, verdict: *mut c_int) -> ts_status;
+    /// ts_prove_multi with a LogUp bus across the tables (TSPF v7): gamma and beta once for every table, one commit
+    /// of all aux matrices, three rounds opened
+    pub fn ts_prove_multi_bus(ctx: *mut ts_ctx, cfg: *const ts_fri_config, chal: *mut ts_challenger,
+                              tables: *mut ts_multi_bus_table, n_tables: u32, proof_out: *mut u32, cap_words: usize,
+                              n_words_out: *mut usize) -> ts_status;
+    /// host only; on verdict 0 `exposed_out` holds 4 words per table with aux columns and `bus_sum` their EF4 sum
+    pub fn ts_verify_multi_bus(cfg: *const ts_fri_config, chal: *mut ts_challenger, airs: *const *const ts_air,
+                               n_tables: u32, public_values: *const *const u32, n_public: *const u32,
+                               proof: *const u32, n_words: usize, exposed_out: *mut u32, cap_exposed: u32,
+                               bus_sum: *mut u32, verdict: *mut c_int) -> ts_status;
+    /// n ts_logup_aux_build calls with one set of challenges in three launches; `aux_out`: n handles, `exposed_out`:
+    /// 4 n words
+    pub fn ts_logup_aux_build_multi(ctx: *mut ts_ctx, n: u32, specs: *const *const ts_logup_spec,
+                                    traces: *const *const ts_matrix, challenges: *const u32,
+                                    aux_out: *mut *mut ts_matrix, exposed_out: *mut u32) -> ts_status;
+    /// ts_logup_multiplicities with the lookups on the rows of `lookers` (n_lookers traces of any heights);
+    /// `first_missing`: (looker, row, lookup), may be null
+    pub fn ts_logup_multiplicities_bus(ctx: *mut ts_ctx, spec: *const ts_logup_mult_bus_spec,
+                                       table_trace: *mut ts_matrix, lookers: *const *const ts_matrix,
+                                       n_missing: *mut u64, first_missing: *mut u64) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

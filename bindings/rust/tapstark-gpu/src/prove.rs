@@ -141,6 +141,104 @@ pub fn verify_gpu_multi(fri: FriConfig, challenger: &mut GpuChallenger, airs: &[
     if rc != 0 { -1 } else { verdict as i32 }
 }
 
+/// One table of `prove_gpu_multi_bus`: a `MultiTable` whose AIR may have LogUp aux columns; `logup` is the
+/// `ts_logup_spec` of those columns (the caller keeps what it points into alive), `None` for a plain AIR.
+pub struct MultiBusTable<'a> {
+    pub air: &'a CompiledAir<'a>,
+    pub trace: DeviceMatrix<'a>,
+    pub public_values: Vec<u32>,
+    pub logup: Option<&'a ts_logup_spec>,
+}
+
+/// Several AIR tables of mixed heights tied by a LogUp bus in ONE proof (`ts_prove_multi_bus`): the TSPF v7 words,
+/// for `verify_gpu_multi_bus`.
+pub fn prove_gpu_multi_bus(pcs: &GpuFriPcs<'_>, challenger: &mut GpuChallenger, tables: Vec<MultiBusTable<'_>>) -> Vec<u32> {
+    let ctx = pcs.ctx;
+    let cfg = pcs.fri.raw();
+    let pis: Vec<Vec<u32>> = tables.iter().map(|t| t.public_values.clone()).collect();
+    let airs: Vec<*const ts_air> = tables.iter().map(|t| t.air.raw as *const ts_air).collect();
+    let specs: Vec<*const ts_logup_spec> =
+        tables.iter().map(|t| t.logup.map_or(ptr::null(), |s| s as *const ts_logup_spec)).collect();
+    let raws: Vec<*mut ts_matrix> = tables.into_iter().map(|t| t.trace.into_raw()).collect();
+    let mut raw_tables: Vec<ts_multi_bus_table> = (0..raws.len())
+        .map(|t| ts_multi_bus_table {
+            struct_size: core::mem::size_of::<ts_multi_bus_table>() as u32,
+            n_public: pis[t].len() as u32,
+            air: airs[t],
+            trace: raws[t],
+            public_values: if pis[t].is_empty() { ptr::null() } else { pis[t].as_ptr() },
+            logup: specs[t],
+        })
+        .collect();
+    let mut out = vec![0u32; 1 << 22];  // (sized generously: the call consumes the traces, as prove_gpu_multi)
+    let mut n = 0usize;
+    let rc = unsafe {
+        ts_prove_multi_bus(ctx.raw, &cfg, challenger.raw, raw_tables.as_mut_ptr(), raw_tables.len() as u32,
+                           out.as_mut_ptr(), out.len(), &mut n)
+    };
+    for m in raws {
+        unsafe { ts_matrix_free(ctx.raw, m) };
+    }
+    ctx.check(rc, "ts_prove_multi_bus");
+    out.truncate(n);
+    out
+}
+
+/// `ts_verify_multi_bus` (host only): the verdict (0 = accepted, codes as `ts_verify`), the exposed words (four per
+/// table with aux columns) and their EF4 sum over the tables.  The bus balances exactly when the sum is zero; that
+/// check is the caller's.
+pub fn verify_gpu_multi_bus(fri: FriConfig, challenger: &mut GpuChallenger, airs: &[&CompiledAir<'_>],
+                            public_values: &[Vec<u32>], proof: &[u32]) -> (i32, Vec<u32>, [u32; 4]) {
+    let cfg = fri.raw();
+    let raw_airs: Vec<*const ts_air> = airs.iter().map(|a| a.raw as *const ts_air).collect();
+    let ptrs: Vec<*const u32> =
+        public_values.iter().map(|p| if p.is_empty() { ptr::null() } else { p.as_ptr() }).collect();
+    let counts: Vec<u32> = public_values.iter().map(|p| p.len() as u32).collect();
+    let mut verdict: std::os::raw::c_int = -1;
+    let mut exposed = vec![0u32; 4 * airs.len().max(1)];
+    let mut bus_sum = [0u32; 4];
+    let rc = unsafe {
+        ts_verify_multi_bus(&cfg, challenger.raw, raw_airs.as_ptr(), raw_airs.len() as u32, ptrs.as_ptr(),
+                            counts.as_ptr(), proof.as_ptr(), proof.len(), exposed.as_mut_ptr(), exposed.len() as u32,
+                            bus_sum.as_mut_ptr(), &mut verdict)
+    };
+    (if rc != 0 { -1 } else { verdict as i32 }, exposed, bus_sum)
+}
+
+/// `ts_logup_aux_build_multi`: the LogUp matrices of `traces` under `specs` for one pair of challenges, in three
+/// launches; returns the aux matrices and the exposed sums (four words per table).
+pub fn logup_aux_build_multi<'a>(ctx: &'a GpuContext, specs: &[&ts_logup_spec], traces: &[&DeviceMatrix<'a>],
+                                 challenges: &[u32; 8]) -> (Vec<DeviceMatrix<'a>>, Vec<u32>) {
+    assert_eq!(specs.len(), traces.len());
+    let sp: Vec<*const ts_logup_spec> = specs.iter().map(|s| *s as *const ts_logup_spec).collect();
+    let tr: Vec<*const ts_matrix> = traces.iter().map(|t| t.raw as *const ts_matrix).collect();
+    let mut out: Vec<*mut ts_matrix> = vec![ptr::null_mut(); specs.len()];
+    let mut exposed = vec![0u32; 4 * specs.len()];
+    ctx.check(
+        unsafe {
+            ts_logup_aux_build_multi(ctx.raw, specs.len() as u32, sp.as_ptr(), tr.as_ptr(), challenges.as_ptr(),
+                                     out.as_mut_ptr(), exposed.as_mut_ptr())
+        },
+        "ts_logup_aux_build_multi",
+    );
+    (out.into_iter().map(|raw| DeviceMatrix { ctx, raw }).collect(), exposed)
+}
+
+/// `ts_logup_multiplicities_bus`: fills `spec.out_column` of the resident `table_trace` from the lookups on the
+/// rows of `lookers`; returns (n_missing, [looker, row, lookup] of the least miss).
+pub fn logup_multiplicities_bus<'a>(ctx: &'a GpuContext, spec: &ts_logup_mult_bus_spec, table_trace: &mut DeviceMatrix<'a>,
+                                    lookers: &[&DeviceMatrix<'a>]) -> (u64, [u64; 3]) {
+    let lk: Vec<*const ts_matrix> = lookers.iter().map(|t| t.raw as *const ts_matrix).collect();
+    let (mut n_missing, mut first) = (0u64, [u64::MAX; 3]);
+    ctx.check(
+        unsafe {
+            ts_logup_multiplicities_bus(ctx.raw, spec, table_trace.raw, lk.as_ptr(), &mut n_missing, first.as_mut_ptr())
+        },
+        "ts_logup_multiplicities_bus",
+    );
+    (n_missing, first)
+}
+
 /// A stream of proofs from HOST traces at the PCIe-inclusive rate (INTEGRATION.md "Three rates").
 ///
 /// `prove_gpu` above uploads synchronously from pageable memory: the GPU idles during the copy and

@@ -1058,6 +1058,115 @@ ts_status ts_verify_multi(const ts_fri_config* cfg, ts_challenger* chal,
                           const uint32_t* const* public_values, const uint32_t* n_public,
                           const uint32_t* proof, size_t n_words, int* verdict);   /* host only */
 
+/* ---- the tables of a multi-table proof connected: a LogUp bus across heights ----------------------------------
+ * ts_prove_multi with a challenge phase ACROSS the tables: every table may carry LogUp aux columns (ts_logup_spec
+ * over its own trace, terms of kind 0 and 1), all of them built from ONE gamma and ONE beta, so that the sends of
+ * one table and the receives of another -- of any heights -- cancel in the sum of the exposed words.  Plain tables
+ * may sit beside them.  ts_prove_multi itself keeps refusing aux AIRs.  Build-defined.  Transcript:
+ *   1. observe T and every log_degree, as TSPF v6 does;
+ *   2. ONE commit of all traces; observe the root;
+ *   3. sample gamma, then beta, ONCE: one bus has one tuple encoding gamma + sum_j beta^j v_j.  Several buses in
+ *      one statement are told apart by a constant first value of the tuple (("const", TAG), ...): tuples of
+ *      different tags never meet in a denominator, so each bus balances on its own inside the one sum;
+ *   4. the aux matrix of every table that has aux columns (ts_logup_aux_build_multi below: what
+ *      ts_logup_aux_build gives for that trace and those challenges); ONE commit of them in table order, on their
+ *      natural domains; observe the aux root, then the exposed words, four per aux table, in table order;
+ *   5. sample alpha;
+ *   6. per table the chunks over (aux LDE, trace LDE) with the public vector pis ++ gamma ++ beta ++ its four
+ *      exposed words: chunk c of table t is what ts_quotient_chunks_aux gives for that trace and aux matrix
+ *      committed alone; a table without aux columns as in v6;
+ *   7. ONE commit of all chunks; observe the root; sample zeta;
+ *   8. sample the batch challenge;
+ *   9. three rounds in the order of TSPF v4: the aux matrices at {zeta, zeta * omega_{n_t}}, the traces at the
+ *      same points, every chunk at {zeta}.
+ * Proof = TSPF v7: [magic, 7, T], T x [log_degree, width, qd, aux_width, n_exposed], trace root, aux root, the
+ * exposed words in table order, quotient root, the opened values in ts_pcs_open's (round, matrix, point, column)
+ * order, the FriProof with three BatchOpenings per query.  v7 has no postcard form, and every other verify call
+ * answers a v7 proof with verdict 9.  With T = 1 the words behind the header are those of ts_prove_aux with
+ * ts_logup_aux_build as its source, for a challenger that has observed (1, log_degree).
+ * Refusals, all before any trace is consumed and each with a text in ts_last_error:
+ *   TS_ERR_INVALID      whatever ts_prove_multi refuses with TS_ERR_INVALID; no table with aux columns (the text
+ *                       points at ts_prove_multi); a spec that is missing for an aux AIR, given for a plain one, of
+ *                       another aux width than the AIR's, with a term of kind 2, a column outside the trace or a
+ *                       non-canonical constant; an aux AIR without exactly 2 challenges and 4 exposed words; a
+ *                       column-major trace under an aux table
+ *   TS_ERR_UNSUPPORTED  a table whose AIR has preprocessed columns
+ *   TS_ERR_INVARIANT    log_quotient_degree > log_blowup for some table
+ * After the traces are consumed: TS_ERR_INVARIANT "logup: zero denominator at table t, row r, interaction i" (the
+ * least such triple), TS_ERR_BUFFER with the size needed.
+ * Memory: the row-major traces stay alive through their commit (the LDE stage only reads them) and are released
+ * once the aux matrices exist.
+ * TS_MULTI_OPEN_GENERIC=1 routes step 9 through the generic opening, TS_MULTI_LOGUP_PER_TABLE=1 step 4 through one
+ * ts_logup_aux_build per table (both read on every call; test and measurement knobs); the proof is the same. */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(ts_multi_bus_table), else the whole call is TS_ERR_INVALID */
+    uint32_t n_public;
+    const ts_air* air;             /* preprocessed_width == 0; aux_width == 0, or n_challenges == 2 && n_exposed == 4 */
+    ts_matrix* trace;              /* consumed; row-major where aux_width > 0 */
+    const uint32_t* public_values;
+    const ts_logup_spec* logup;    /* NULL iff aux_width == 0; kinds 0 and 1 only; its aux width = the AIR's */
+} ts_multi_bus_table;
+ts_status ts_prove_multi_bus(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal,
+                             ts_multi_bus_table* tables, uint32_t n_tables,
+                             uint32_t* proof_out, size_t cap_words, size_t* n_words_out);
+/* host only.  ts_verify_multi extended with the two samples, the aux root and the exposed words, the per-table
+ * out-of-domain check with the aux values, and ts_pcs_verify over the three rounds.  On verdict 0 exposed_out
+ * (cap_exposed >= 4 per table with aux columns) holds the exposed words in table order and bus_sum their EF4 sum
+ * over the tables.  "The bus balances" -- bus_sum == 0 -- is the caller's statement to check, as ts_verify_aux
+ * leaves the exposed sum to its caller. */
+ts_status ts_verify_multi_bus(const ts_fri_config* cfg, ts_challenger* chal,
+                              const ts_air* const* airs, uint32_t n_tables,
+                              const uint32_t* const* public_values, const uint32_t* n_public,
+                              const uint32_t* proof, size_t n_words,
+                              uint32_t* exposed_out, uint32_t cap_exposed, uint32_t bus_sum[4], int* verdict);
+/* The LogUp columns of n traces for ONE set of challenges: the work of n ts_logup_aux_build calls in three launches
+ * over the workgroups of all tables, one upload (the specs travel in a job table in device memory instead of the
+ * launch argument) and one copy back.  aux_out[k] and exposed_out[4k .. 4k+3] are word for word what
+ * ts_logup_aux_build(specs[k], traces[k], challenges) gives (extension addition is exact).  1 <= n <= 64; refusals
+ * as the single call's, for any k, with nothing allocated and every aux_out[k] NULL.  A zero denominator is
+ * TS_ERR_INVARIANT "logup: zero denominator at table k, row r, interaction i" for the least such triple, and no
+ * output.  TS_LOGUP_BLOCK_ROWS applies as in the single call. */
+ts_status ts_logup_aux_build_multi(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs,
+                                   const ts_matrix* const* traces, const uint32_t challenges[8],
+                                   ts_matrix** aux_out /* n */, uint32_t* exposed_out /* 4 n */);
+
+/* The multiplicity column of a table whose lookups live in OTHER traces: the table side of a LogUp bus, filled in
+ * HBM.  ts_logup_multiplicities counts lookups on the rows of the trace that holds the table; here the table's
+ * tuple (`table`, n_values terms of kind 0 or 1) is read on the rows of `table_trace`, and every looker k brings
+ * its own row-major trace lookers[k] (any height; read, not consumed; it may be table_trace itself) with 1 to 16
+ * lookups (n_values terms each) and their weights, terms of kind 0 or 1 over THAT looker's row.  Semantics as
+ * ts_logup_multiplicities: rows with equal tuples form a class and the class's lowest row receives the field sum
+ * of the weights (p minus it with negate) while the others receive 0; a weight of 0 is skipped; the same words on
+ * every run; TS_LOGUP_HASH_BITS honoured.  A lookup of non-zero weight whose tuple is in no table row is a miss:
+ * *n_missing counts them and first_missing[3] = (looker, row, lookup) of the least one in that lexicographic order
+ * (~0 each when there is none); with n_missing NULL a miss is TS_ERR_INVARIANT.  Launches: one insert over the
+ * table, one count per looker, one write; one copy back.  With one looker that is table_trace the column is
+ * exactly ts_logup_multiplicities'.
+ * TS_ERR_INVALID before any device work: what the single-trace call refuses, per matrix (not row-major, consumed,
+ * another context -- a looker's too --, height outside [1, 2^27], a column outside its trace, a non-canonical
+ * constant, a term kind above 1, negate above 1, counts outside their limits, struct_size); out_column outside
+ * table_trace or among the table_trace columns that any term reads, the table's or those of a looker that is
+ * table_trace. */
+typedef struct {
+    uint32_t n_lookups;                 /* 1 .. 16 */
+    uint32_t pad;
+    const ts_logup_term* lookups;       /* n_lookups * n_values, lookup-major, over this looker's row */
+    const ts_logup_term* weights;       /* n_lookups */
+} ts_logup_bus_looker;
+typedef struct {
+    uint32_t struct_size;               /* = sizeof(ts_logup_mult_bus_spec) */
+    uint32_t n_values;                  /* 1 .. 8 */
+    const ts_logup_term* table;         /* n_values terms over table_trace's row */
+    uint32_t n_lookers;                 /* 1 .. 16 */
+    uint32_t out_column;                /* the column of table_trace that is overwritten */
+    const ts_logup_bus_looker* lookers;
+    uint32_t negate;                    /* 0 | 1 */
+    uint32_t pad;
+} ts_logup_mult_bus_spec;
+ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec, ts_matrix* table_trace,
+                                      const ts_matrix* const* lookers /* n_lookers */, uint64_t* n_missing,
+                                      uint64_t first_missing[3]);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

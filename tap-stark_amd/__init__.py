@@ -7,3 +7,5 @@ from .stark import (BatchLookupResult, BatchResult, BfChallenger, Blake3Mmcs, Co
                     Proof, Radix2Dft, StarkConfig, TraceFormat, TwoAdicFriPcs, VerificationError, check_constraints,
                     default_context, prove, prove_batch, prove_batch_lookup, prove_sharded, prove_stream, verify, verify_pre_aux)
 from .stark import MultiProof, MultiTableOpening, prove_multi, verify_multi  # noqa: F401
+from .stark import MultiBusProof, MultiBusTableOpening, prove_multi_bus, verify_multi_bus  # noqa: F401
+from .air import logup_build_multi, logup_multiplicities_bus  # noqa: F401

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "ts_prove_pre_aux", "ts_verify_pre_aux", "ts_quotient_chunks_pre_aux", "ts_check_constraints_pre_aux",
     "ts_prove_batch_lookup",
     "ts_prove_multi", "ts_verify_multi",
+    "ts_prove_multi_bus", "ts_verify_multi_bus", "ts_logup_aux_build_multi", "ts_logup_multiplicities_bus",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -151,6 +152,25 @@ class MultiTableC(C.Structure):
     """``ts_multi_table``: one table of ``ts_prove_multi``."""
     _fields_ = [("struct_size", C.c_uint32), ("n_public", C.c_uint32), ("air", C.c_void_p), ("trace", C.c_void_p),
                 ("public_values", C.POINTER(C.c_uint32))]
+
+
+class LogupBusLookerC(C.Structure):
+    """``ts_logup_bus_looker``: the lookups one looker trace brings to ``ts_logup_multiplicities_bus``."""
+    _fields_ = [("n_lookups", C.c_uint32), ("pad", C.c_uint32), ("lookups", C.POINTER(LogupTermC)),
+                ("weights", C.POINTER(LogupTermC))]
+
+
+class LogupMultBusSpecC(C.Structure):
+    """``ts_logup_mult_bus_spec`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_values", C.c_uint32), ("table", C.POINTER(LogupTermC)),
+                ("n_lookers", C.c_uint32), ("out_column", C.c_uint32), ("lookers", C.POINTER(LogupBusLookerC)),
+                ("negate", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class MultiBusTableC(C.Structure):
+    """``ts_multi_bus_table``: one table of ``ts_prove_multi_bus``."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_public", C.c_uint32), ("air", C.c_void_p), ("trace", C.c_void_p),
+                ("public_values", C.POINTER(C.c_uint32)), ("logup", C.POINTER(LogupSpecC))]
 
 
 class BatchLookupItemC(C.Structure):
@@ -367,6 +387,15 @@ def lib() -> C.CDLL:
                                      C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
         l.ts_verify_multi.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32,
                                       C.POINTER(u32p), u32p, u32p, C.c_size_t, C.POINTER(C.c_int)]
+        l.ts_prove_multi_bus.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.c_void_p, C.POINTER(MultiBusTableC),
+                                         C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
+        l.ts_verify_multi_bus.argtypes = [C.POINTER(FriConfigC), C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32,
+                                          C.POINTER(u32p), u32p, u32p, C.c_size_t, u32p, C.c_uint32, u32p,
+                                          C.POINTER(C.c_int)]
+        l.ts_logup_multiplicities_bus.argtypes = [C.c_void_p, C.POINTER(LogupMultBusSpecC), C.c_void_p,
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        l.ts_logup_aux_build_multi.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LogupSpecC)),
+                                               C.POINTER(C.c_void_p), u32p, C.POINTER(C.c_void_p), u32p]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

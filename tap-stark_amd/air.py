@@ -505,6 +505,75 @@ class LogUp:
                                     allow_missing=allow_missing)
 
 
+def logup_build_multi(logups, traces, challenges):
+    """``ts_logup_aux_build_multi``: the aux matrices of ``traces`` (row-major ``DeviceMatrix``, one context, not
+    consumed) under ``logups`` (one :class:`LogUp` per trace, terms of kind 0 and 1) for ONE pair of challenges, in
+    three launches and one copy back instead of three launches and a host wait per table.  Returns ``(list of
+    aux DeviceMatrix, exposed)`` with ``exposed`` of shape (n, 4): per table what ``LogUp.build`` returns."""
+    import ctypes as C
+    from . import _lib
+    from .stark import DeviceMatrix
+    n = len(logups)
+    if n == 0 or len(traces) != n:
+        raise ValueError("logup_build_multi: one trace per LogUp, at least one")
+    ctx = traces[0].ctx
+    specs = [lg._spec_c() for lg in logups]
+    spec_ptrs = (C.POINTER(_lib.LogupSpecC) * n)(*[C.pointer(sp) for sp, _ in specs])
+    handles = (C.c_void_p * n)(*[t.h for t in traces])
+    ch = np.ascontiguousarray(challenges, dtype=np.uint32).reshape(-1)
+    if len(ch) != 8:
+        raise ValueError("LogUp takes two challenges (eight words)")
+    out = (C.c_void_p * n)()
+    exposed = np.zeros((n, 4), dtype=np.uint32)
+    ctx.check(ctx._l.ts_logup_aux_build_multi(ctx.h, n, spec_ptrs, handles, ch.ctypes.data_as(_lib.u32p), out,
+                                              exposed.ctypes.data_as(_lib.u32p)))
+    del specs
+    return [DeviceMatrix(ctx, C.c_void_p(h)) for h in out], exposed
+
+
+def mult_bus_spec_c(table, lookers, out_column: int, negate: int = 1):
+    """The ``ts_logup_mult_bus_spec`` of the arguments ``logup_multiplicities_bus`` takes, and the ctypes arrays it
+    points into (keep the tuple alive while the spec is in use)."""
+    import ctypes as C
+    from . import _lib
+    T = _lib.LogupTermC
+    table = [LogUp._term(t) for t in table]
+    t_arr = (T * len(table))(*[T(k, v) for k, v in table])
+    l_arr = (_lib.LogupBusLookerC * max(len(lookers), 1))()
+    keep = [t_arr, l_arr]
+    for i, (lookups, weights) in enumerate(lookers):
+        lookups = [[LogUp._term(t) for t in tup] for tup in lookups]
+        weights = [LogUp._term(t) for t in weights]
+        if len(weights) != len(lookups) or any(len(tup) != len(table) for tup in lookups):
+            raise ValueError("logup_multiplicities_bus: one weight per lookup and one term per table value in every lookup")
+        lk = (T * max(len(lookups) * len(table), 1))(*[T(k, v) for tup in lookups for k, v in tup])
+        wt = (T * max(len(weights), 1))(*[T(k, v) for k, v in weights])
+        keep += [lk, wt]
+        l_arr[i] = _lib.LogupBusLookerC(len(lookups), 0, lk, wt)
+    spec = _lib.LogupMultBusSpecC(C.sizeof(_lib.LogupMultBusSpecC), len(table), t_arr, len(lookers), int(out_column),
+                                  l_arr, int(negate), 0)
+    return spec, keep
+
+
+def logup_multiplicities_bus(table_trace, table, lookers, out_column: int, negate: int = 1, allow_missing: bool = False):
+    """``ts_logup_multiplicities_bus`` (include/tapstark.h, csrc/logup_mult.hip): the multiplicity column of a table
+    whose lookups are rows of OTHER traces.  ``table``: the table's tuple, terms over ``table_trace``'s row;
+    ``lookers``: a list of ``(trace, lookups, weights)`` with ``trace`` a resident row-major ``DeviceMatrix`` of any
+    height (not consumed; it may be ``table_trace``), ``lookups`` one tuple of terms per lookup and ``weights`` one
+    term per lookup, over that trace's row.  Column ``out_column`` of ``table_trace`` is overwritten in HBM as
+    ``logup_multiplicities`` does.  Returns ``(n_missing, (looker, row, lookup) of the least miss or None)``; with
+    ``allow_missing`` false a miss raises ``TsError`` (TS_ERR_INVARIANT) instead."""
+    import ctypes as C
+    spec, keep = mult_bus_spec_c(table, [(lk, w) for _, lk, w in lookers], out_column, negate)
+    ctx = table_trace.ctx
+    handles = (C.c_void_p * max(len(lookers), 1))(*[m.h for m, _, _ in lookers])
+    n_missing, first = C.c_uint64(0), (C.c_uint64 * 3)()
+    ctx.check(ctx._l.ts_logup_multiplicities_bus(ctx.h, C.byref(spec), table_trace.h, handles,
+                                                 C.byref(n_missing) if allow_missing else None, first))
+    del keep
+    return int(n_missing.value), (tuple(int(x) for x in first) if n_missing.value else None)
+
+
 def mult_spec_c(table, lookups, weights, out_column: int, negate: int = 1):
     """The ``ts_logup_mult_spec`` of the arguments ``logup_multiplicities`` takes (``LogUp.mult_spec`` makes them),
     and the ctypes arrays it points into (keep the tuple alive while the spec is in use)."""

@@ -804,3 +804,91 @@ def fill_table_lookup_multiplicities(trace, table_values, allow_missing: bool = 
     of the key's table (``PreprocessedKey.values``).  Returns ``(n_missing, first_missing)``."""
     return TableLookupAir.logup.fill_multiplicities(trace, table=1, preprocessed=table_values,
                                                     allow_missing=allow_missing)
+
+
+# ---------------------------------------------------------------------------------------------- the bus AIRs
+# Tables of a multi-table proof tied by a LogUp bus (prove_multi_bus): senders put (BUS_TAG, value) on the bus, a
+# range table of another height takes each off as often as it was sent.  The tag is the constant first value that
+# tells this bus from any other in the same statement.
+
+BUS_TAG = 7
+
+
+class BusSendAir(BaseAir):
+    """Main columns (value_0, sel_0, ..., value_{k-1}, sel_{k-1}); every ``sel_i`` is boolean and row r sends
+    (BUS_TAG, value_i) with multiplicity sel_i.  Constraint degree 3 for every k."""
+
+    n_challenges, n_exposed = LogUp.n_challenges, LogUp.n_exposed
+
+    def __init__(self, k: int = 1):
+        self.k = int(k)
+        self.logup = LogUp([(("col", 2 * i + 1), [("const", BUS_TAG), ("col", 2 * i)]) for i in range(self.k)])
+        self.aux_width = self.logup.aux_width
+
+    def width(self) -> int:
+        return 2 * self.k
+
+    def eval(self, builder) -> None:
+        local = builder.main().row_slice(0)
+        for i in range(self.k):
+            builder.assert_zero(local[2 * i + 1] * (local[2 * i + 1] - 1))
+        # implied by the line above; it puts BusSendAir(1), whose lone LogUp group is quadratic, at the constraint
+        # degree 3 of every other bus AIR, so that all tables of a bus have two quotient chunks
+        builder.assert_zero(local[0] * local[1] * (local[1] - 1))
+        self.logup.eval(builder)
+
+
+class BusRangeAir(BaseAir):
+    """Main columns (table, mult): first row ``table = 0``, ``next.table = table + 1``; the row receives
+    (BUS_TAG, table) with multiplicity ``mult`` = MINUS the number of times the senders sent it."""
+
+    logup = LogUp([(("col", 1), [("const", BUS_TAG), ("col", 0)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 2
+
+    def eval(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        builder.when_first_row().assert_zero(local[0])
+        builder.when_transition().assert_eq(nxt[0], local[0] + 1)
+        # implied by the first line; constraint degree 3, as every bus AIR (see BusSendAir)
+        builder.when_first_row().assert_zero(local[0] * nxt[0])
+        self.logup.eval(builder)
+
+
+def generate_bus_send_trace(n: int, k: int, table_height: int, seed: int = SPLITMIX_SEED) -> np.ndarray:
+    """(n, 2k) canonical u32 satisfying BusSendAir(k): values below ``table_height``, selectors 0 or 1."""
+    r = splitmix64_stream(seed, 2 * n * k).reshape(n, 2 * k)
+    out = np.empty((n, 2 * k), dtype=np.uint32)
+    out[:, 0::2] = (r[:, 0::2] % np.uint64(table_height)).astype(np.uint32)
+    out[:, 1::2] = ((r[:, 1::2] >> np.uint64(17)) & np.uint64(1)).astype(np.uint32)
+    return out
+
+
+def generate_bus_range_trace(n: int, sender_traces) -> np.ndarray:
+    """(n, 2) canonical u32 satisfying BusRangeAir: the table 0 .. n-1 and MINUS the count of every entry among
+    the selected values of ``sender_traces`` (values outside the table are not counted: the bus then does not
+    balance)."""
+    counts = np.zeros(n, dtype=np.int64)
+    for t in sender_traces:
+        t = np.asarray(t)
+        vals = t[:, 0::2][t[:, 1::2] == 1].astype(np.int64)
+        counts += np.bincount(vals[vals < n], minlength=n)
+    out = np.empty((n, 2), dtype=np.uint32)
+    out[:, 0] = np.arange(n)
+    out[:, 1] = (P - counts % P) % P
+    return out
+
+
+def fill_bus_range_multiplicities(range_trace, sender_traces, allow_missing: bool = False):
+    """Fills column 1 of a resident BusRangeAir trace in HBM from the resident BusSendAir traces (any heights, any
+    k): what ``generate_bus_range_trace`` computes on the host.  Returns what ``logup_multiplicities_bus`` returns."""
+    from .air import logup_multiplicities_bus
+    lookers = []
+    for m in sender_traces:
+        k = m.dims()[1] // 2
+        lookers.append((m, [[("col", 2 * i)] for i in range(k)], [("col", 2 * i + 1) for i in range(k)]))
+    return logup_multiplicities_bus(range_trace, [("col", 0)], lookers, out_column=1, negate=1,
+                                    allow_missing=allow_missing)

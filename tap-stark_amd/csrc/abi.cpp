@@ -430,6 +430,8 @@ ts_status ts_proof_to_postcard(const uint32_t* proof, size_t n_words, uint8_t* o
                    "TSPF v5 proofs (ts_prove_pre_aux) have no postcard form");
         TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 6), ts::TS_ERR_UNSUPPORTED,
                    "TSPF v6 proofs (ts_prove_multi) have no postcard form");
+        TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 7), ts::TS_ERR_UNSUPPORTED,
+                   "TSPF v7 proofs (ts_prove_multi_bus) have no postcard form");
         TS_REQUIRE(ts::tspf_to_postcard(proof, n_words, b), ts::TS_ERR_INVALID, "not a TSPF v1 proof");
         *n_bytes_out = b.size();
         TS_REQUIRE(b.size() <= cap_bytes, ts::TS_ERR_BUFFER, "postcard buffer too small");
@@ -1878,6 +1880,177 @@ ts_status ts_logup_multiplicities(ts_ctx* ctx, const ts_logup_mult_spec* spec, c
         if (first_missing) *first_missing = r.first_missing;
         if (!n_missing && r.n_missing) throw ts::Error(ts::TS_ERR_INVARIANT, ts::logup_miss_text(r, spec->n_lookups));
     });
+}
+
+// The multiplicity column of a table whose lookups are rows of other traces (logup_mult.hip).
+ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec, ts_matrix* table_trace,
+                                      const ts_matrix* const* lookers, uint64_t* n_missing, uint64_t first_missing[3]) {
+    if (!ctx) return TS_ERR_INVALID;
+    if (n_missing) *n_missing = 0;
+    if (first_missing) first_missing[0] = first_missing[1] = first_missing[2] = ~0ull;
+    return guard(ctx, [&] {
+        TS_REQUIRE(spec && table_trace && lookers, ts::TS_ERR_INVALID, "ts_logup_multiplicities_bus: null argument");
+        TS_REQUIRE(spec->struct_size == sizeof(ts_logup_mult_bus_spec), ts::TS_ERR_INVALID,
+                   "logup multiplicities: bad struct_size");
+        TS_REQUIRE(spec->n_values >= 1 && spec->n_values <= ts::LOGUP_MAX_VALUES && spec->table, ts::TS_ERR_INVALID,
+                   "logup multiplicities: between 1 and 8 values");
+        TS_REQUIRE(spec->n_lookers >= 1 && spec->n_lookers <= ts::LOGUP_MULT_MAX_LOOKERS && spec->lookers,
+                   ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookers");
+        auto load = [](const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
+            for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
+        };
+        ts::LogupMultBusSpec s;
+        load(spec->table, spec->n_values, s.table);
+        std::vector<const ts::DeviceMatrix*> mats;
+        for (uint32_t k = 0; k < spec->n_lookers; k++) {
+            const ts_logup_bus_looker& in = spec->lookers[k];
+            TS_REQUIRE(in.n_lookups >= 1 && in.n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && in.lookups && in.weights,
+                       ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookups per looker");
+            TS_REQUIRE(lookers[k], ts::TS_ERR_INVALID, "ts_logup_multiplicities_bus: null looker");
+            ts::LogupMultLooker lk;
+            load(in.lookups, (size_t)in.n_lookups * spec->n_values, lk.lookups);
+            load(in.weights, in.n_lookups, lk.weights);
+            s.lookers.push_back(std::move(lk));
+            mats.push_back(&lookers[k]->m);
+        }
+        s.out_column = spec->out_column;
+        s.negate = spec->negate;
+        const ts::LogupMultBusResult r = ts::logup_multiplicities_bus(ctx->ctx, s, table_trace->m, mats);
+        if (n_missing) *n_missing = r.n_missing;
+        if (first_missing) {
+            first_missing[0] = r.looker;
+            first_missing[1] = r.row;
+            first_missing[2] = r.lookup;
+        }
+        if (!n_missing && r.n_missing)
+            throw ts::Error(ts::TS_ERR_INVARIANT,
+                            "logup multiplicities: the tuple of looker " + std::to_string(r.looker) + ", row " +
+                                std::to_string(r.row) + ", lookup " + std::to_string(r.lookup) + " is in no table row (" +
+                                std::to_string(r.n_missing) + " such lookups)");
+    });
+}
+
+// The LogUp columns of n traces for one set of challenges, in three launches (logup.hip logup_aux_build_multi).
+ts_status ts_logup_aux_build_multi(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs,
+                                   const ts_matrix* const* traces, const uint32_t challenges[8], ts_matrix** aux_out,
+                                   uint32_t* exposed_out) {
+    if (!ctx) return TS_ERR_INVALID;
+    if (aux_out && n >= 1 && n <= ts::LOGUP_MAX_TABLES)
+        for (uint32_t k = 0; k < n; k++) aux_out[k] = nullptr;
+    return guard(ctx, [&] {
+        TS_REQUIRE(specs && traces && challenges && aux_out && exposed_out, ts::TS_ERR_INVALID,
+                   "ts_logup_aux_build_multi: null argument");
+        TS_REQUIRE(n >= 1 && n <= ts::LOGUP_MAX_TABLES, ts::TS_ERR_INVALID,
+                   "ts_logup_aux_build_multi: between 1 and 64 tables");
+        std::vector<ts::LogupSpec> loaded(n);
+        std::vector<const ts::LogupSpec*> sp(n);
+        std::vector<const ts::DeviceMatrix*> tr(n);
+        for (uint32_t k = 0; k < n; k++) {
+            TS_REQUIRE(traces[k], ts::TS_ERR_INVALID, "ts_logup_aux_build_multi: null trace");
+            loaded[k] = load_logup_spec(specs[k]);
+            sp[k] = &loaded[k];
+            tr[k] = &traces[k]->m;
+        }
+        std::vector<uint32_t> exposed(4 * (size_t)n);
+        std::vector<ts::DeviceMatrix> aux = ts::logup_aux_build_multi(ctx->ctx, sp, tr, challenges, exposed.data());
+        std::vector<std::unique_ptr<ts_matrix>> handles(n);
+        for (uint32_t k = 0; k < n; k++) {
+            handles[k] = std::make_unique<ts_matrix>();
+            handles[k]->m = std::move(aux[k]);
+        }
+        for (uint32_t k = 0; k < n; k++) aux_out[k] = handles[k].release();
+        memcpy(exposed_out, exposed.data(), exposed.size() * 4);
+    });
+}
+
+// ------------------------------------------------------------------ prove_multi_bus
+// ts_prove_multi with LogUp aux columns on a bus across the tables (prove_multi.cpp).  Every refusal is made before
+// the first trace is taken.
+ts_status ts_prove_multi_bus(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_bus_table* tables,
+                             uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    if (!ctx) return TS_ERR_INVALID;
+    if (n_words_out) *n_words_out = 0;
+    return guard(ctx, [&] {
+        TS_REQUIRE(cfg && chal && tables && proof_out && n_words_out, ts::TS_ERR_INVALID,
+                   "ts_prove_multi_bus: null argument");
+        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+                   "ts_prove_multi_bus: between 1 and 64 tables");
+        const ts::FriConfig fri = load_cfg(cfg);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            const ts_multi_bus_table& mt = tables[t];
+            TS_REQUIRE(mt.struct_size == sizeof(ts_multi_bus_table), ts::TS_ERR_INVALID,
+                       "ts_prove_multi_bus: ts_multi_bus_table.struct_size is not sizeof(ts_multi_bus_table)");
+            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, "ts_prove_multi_bus: null AIR or trace");
+            TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
+                       "ts_prove_multi_bus: an AIR was compiled on another context (or host-only)");
+            TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+            TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
+                       "ts_prove_multi_bus: a trace was made on another context");
+            for (uint32_t k = 0; k < t; k++)
+                TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID,
+                           "ts_prove_multi_bus: one trace handle in two tables");
+        }
+        // the statement's own refusals on shapes alone: the matrices stay with their handles until all of it holds
+        std::vector<ts::MultiBusTable> mts(n_tables);
+        std::vector<ts::LogupSpec> specs(n_tables);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            mts[t].air = &ready_prog(tables[t].air);
+            mts[t].public_values = public_inputs(tables[t].public_values, tables[t].n_public);
+            mts[t].trace.width = tables[t].trace->m.width;
+            mts[t].trace.height = tables[t].trace->m.height;
+            mts[t].trace.layout = tables[t].trace->m.layout;
+            if (tables[t].logup) {
+                specs[t] = load_logup_spec(tables[t].logup);
+                mts[t].logup = &specs[t];
+            }
+        }
+        ts::check_multi_bus_statement(fri, mts);
+        ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
+        for (uint32_t t = 0; t < n_tables; t++) mts[t].trace = take_trace(tables[t].trace);
+        ts::StageTimer timer(&ctx->ctx, "prove");
+        copy_proof(ts::prove_multi_bus(pcs, chal->c, mts), proof_out, cap_words, n_words_out);
+    });
+}
+
+ts_status ts_verify_multi_bus(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
+                              const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,
+                              size_t n_words, uint32_t* exposed_out, uint32_t cap_exposed, uint32_t bus_sum[4],
+                              int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(cfg && chal && airs && public_values && n_public && proof && exposed_out && bus_sum && verdict,
+                   ts::TS_ERR_INVALID, "ts_verify_multi_bus: null argument");
+        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+                   "ts_verify_multi_bus: between 1 and 64 tables");
+        const ts::FriConfig fri = load_cfg(cfg);
+        std::vector<const ts::AirProgram*> progs(n_tables);
+        std::vector<std::vector<uint32_t>> pis(n_tables);
+        uint32_t n_aux = 0;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, "ts_verify_multi_bus: null AIR");
+            const ts::AirProgram& p = airs[t]->a.prog();
+            if (p.preprocessed_width)
+                throw ts::Error(ts::TS_ERR_UNSUPPORTED, "ts_verify_multi_bus: a table's AIR has preprocessed columns");
+            TS_REQUIRE(p.aux_width ? p.n_challenges == 2 && p.n_exposed == 4 : !p.n_challenges && !p.n_exposed,
+                       ts::TS_ERR_INVALID,
+                       "ts_verify_multi_bus: an AIR on the bus has aux columns, 2 challenges and 4 exposed words, a "
+                       "plain one none of them");
+            n_aux += p.aux_width ? 1 : 0;
+            progs[t] = &p;
+            pis[t] = public_inputs(public_values[t], n_public[t]);
+        }
+        TS_REQUIRE(n_aux > 0, ts::TS_ERR_INVALID,
+                   "ts_verify_multi_bus: no table has aux columns; ts_verify_multi verifies plain tables (TSPF v6)");
+        TS_REQUIRE(cap_exposed >= 4 * n_aux, ts::TS_ERR_INVALID,
+                   "ts_verify_multi_bus: short buffer for the exposed words (4 per table with aux columns)");
+        std::vector<uint32_t> exposed;
+        uint32_t sum[4] = {0, 0, 0, 0};
+        *verdict = ts::verify_multi_bus(fri, chal->c, progs, pis, proof, n_words, exposed, sum);
+        if (*verdict == 0) {
+            memcpy(exposed_out, exposed.data(), exposed.size() * 4);
+            memcpy(bus_sum, sum, 16);
+        }
+    }, false);
 }
 
 // ------------------------------------------------------------------ preprocessed and aux columns together

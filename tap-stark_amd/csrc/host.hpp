@@ -219,6 +219,12 @@ bool multi_open_generic();
 // host only; verdict codes as verify()
 int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
                  const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words);
+// The same for a TSPF v7 proof (prove_multi_bus, logup.hpp): tables with aux columns (2 challenges, 4 exposed words)
+// beside plain ones, at least one of them.  On acceptance `exposed` holds the exposed words, four per aux table in
+// table order, and bus_sum their EF4 sum; that the bus balances (bus_sum == 0) is the caller's to check.
+int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
+                     const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words,
+                     std::vector<uint32_t>& exposed, uint32_t bus_sum[4]);
 
 // ------------------------------------------------------------------ prove, one proof over G GPUs
 // Collectives the sharded prover needs, supplied by the host (torch.distributed over RCCL in

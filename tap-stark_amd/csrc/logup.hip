@@ -5,7 +5,8 @@
 // odd).  The row-major aux matrix (n x 4 (G + 1), canonical) holds h_g(r), the group's sum, in columns
 // 4g .. 4g+3 and phi(r) = sum_{r' < r} sum_g h_g(r') in the last four; S = phi(n-1) + sum_g h_g(n-1) is exposed.
 //
-// Three plain launches, no grid barrier, no flag another workgroup waits for:
+// Three plain launches, no grid barrier, no flag another workgroup waits for (logup_aux_build_multi: the same three
+// over the workgroups of SEVERAL tables, the specs in a job table in device memory -- the *_jobs kernels below):
 //   k_logup_rows    one thread per row (LOGUP_RPT rows in turn): the fractions, with ONE base-field inversion
 //                   per batch of LOGUP_BATCH denominators (ef_inv_parts + a running product, as open.hip); the
 //                   row's sum goes into the phi slot, the workgroup's sum into totals[workgroup]
@@ -77,7 +78,8 @@ __device__ __forceinline__ uint32_t term_value(uint32_t kind, uint32_t val, cons
 // sum_g h_g(r), with the h_g written to the row's first 4 G words
 __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __restrict__ row,
                                         const uint32_t* __restrict__ table_row, uint64_t r,
-                                        uint32_t* __restrict__ aux_row, unsigned long long* __restrict__ flag) {
+                                        uint32_t* __restrict__ aux_row, unsigned long long* __restrict__ flag,
+                                        unsigned long long flag_base = 0) {
     Ef sum = ef_zero();
     for (uint32_t i0 = 0; i0 < s.K; i0 += LOGUP_BATCH) {
         Ef num[LOGUP_BATCH];
@@ -98,7 +100,7 @@ __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __res
                         d = ef_add(d, ef_mul_base(s.beta_pow[q], term_value(s.it[i].kind[q], s.it[i].val[q], row, table_row)));
                 ef_inv_parts(d, num[j], nrm[j]);
                 if (nrm[j] == 0) {  // d == 0: reported, and the batch goes on as if the norm were one
-                    atomicMin(flag, (unsigned long long)r * s.K + i);
+                    atomicMin(flag, flag_base + (unsigned long long)r * s.K + i);
                     nrm[j] = R_MOD_P;
                 }
                 mult[j] = term_value(s.it[i].m_kind, s.it[i].m_val, row, table_row);
@@ -127,15 +129,15 @@ __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __res
     return sum;
 }
 
-// TABLE = false is the kernel as it was before table terms (the table row is the trace's row again and folds
-// away); TABLE = true reads a second row-major matrix
+// workgroup `block` of one table: rows [block * block_rows, ...), its sum into totals[block]
 template <bool TABLE>
-__global__ void __launch_bounds__(LOGUP_THREADS)
-k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ table, uint64_t n,
-             uint32_t block_rows, uint32_t rpt,
-             uint32_t* __restrict__ aux, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
+__device__ __forceinline__ void logup_rows_block(const LogupDev& s, const uint32_t* __restrict__ trace,
+                                                 const uint32_t* __restrict__ table, uint64_t n, uint32_t block_rows,
+                                                 uint32_t rpt, uint32_t block, uint32_t* __restrict__ aux,
+                                                 Ef* __restrict__ totals, unsigned long long* __restrict__ flag,
+                                                 unsigned long long flag_base) {
     __shared__ Ef wave_sums[LOGUP_THREADS / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * block_rows;
+    const uint64_t base = (uint64_t)block * block_rows;
     Ef mine = ef_zero();
     for (uint32_t k = 0; k < rpt; k++) {
         const uint32_t local = threadIdx.x * rpt + k;
@@ -143,19 +145,28 @@ k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, const uint32_
         if (local < block_rows && r < n) {
             uint32_t* aux_row = aux + r * s.aux_width;
             const uint32_t* row = trace + r * s.width;
-            const Ef sum = logup_row(s, row, TABLE ? table + r * s.table_width : row, r, aux_row, flag);
+            const Ef sum = logup_row(s, row, TABLE ? table + r * s.table_width : row, r, aux_row, flag, flag_base);
             *reinterpret_cast<Ef*>(aux_row + 4 * s.G) = sum;  // the phi slot, until k_logup_scan
             mine = ef_add(mine, sum);
         }
     }
     Ef total;
     block_scan_inclusive<LOGUP_THREADS / 64>(mine, wave_sums, total);
-    if (threadIdx.x == 0) totals[blockIdx.x] = total;
+    if (threadIdx.x == 0) totals[block] = total;
+}
+
+// TABLE = false is the kernel as it was before table terms (the table row is the trace's row again and folds
+// away); TABLE = true reads a second row-major matrix
+template <bool TABLE>
+__global__ void __launch_bounds__(LOGUP_THREADS)
+k_logup_rows(const LogupDev s, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ table, uint64_t n,
+             uint32_t block_rows, uint32_t rpt,
+             uint32_t* __restrict__ aux, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
+    logup_rows_block<TABLE>(s, trace, table, n, block_rows, rpt, blockIdx.x, aux, totals, flag, 0);
 }
 
 // totals[b] <- sum_{b' < b} totals[b'], b < n_blocks
-__global__ void __launch_bounds__(LOGUP_SCAN_THREADS)
-k_logup_totals(Ef* __restrict__ totals, uint32_t n_blocks) {
+__device__ __forceinline__ void logup_totals_scan(Ef* __restrict__ totals, uint32_t n_blocks) {
     __shared__ Ef wave_sums[LOGUP_SCAN_THREADS / 64];
     Ef carry = ef_zero();
     for (uint32_t b0 = 0; b0 < n_blocks; b0 += LOGUP_SCAN_THREADS) {  // (uniform bounds: every thread loops alike)
@@ -168,11 +179,17 @@ k_logup_totals(Ef* __restrict__ totals, uint32_t n_blocks) {
     }
 }
 
-__global__ void __launch_bounds__(LOGUP_THREADS)
-k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, uint32_t rpt,
-             uint32_t* __restrict__ aux, const Ef* __restrict__ offsets, Ef* __restrict__ S) {
+__global__ void __launch_bounds__(LOGUP_SCAN_THREADS)
+k_logup_totals(Ef* __restrict__ totals, uint32_t n_blocks) {
+    logup_totals_scan(totals, n_blocks);
+}
+
+// workgroup `block` of one table: the row sums in the phi slots -> phi, from offsets[block] on
+__device__ __forceinline__ void logup_scan_block(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows,
+                                                 uint32_t rpt, uint32_t block, uint32_t* __restrict__ aux,
+                                                 const Ef* __restrict__ offsets, Ef* __restrict__ S) {
     __shared__ Ef wave_sums[LOGUP_THREADS / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * block_rows;
+    const uint64_t base = (uint64_t)block * block_rows;
     Ef sums[LOGUP_RPT];
     Ef mine = ef_zero();
 #pragma unroll
@@ -186,7 +203,7 @@ k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, ui
     }
     Ef total;
     const Ef incl = block_scan_inclusive<LOGUP_THREADS / 64>(mine, wave_sums, total);
-    Ef run = ef_add(offsets[blockIdx.x], ef_sub(incl, mine));
+    Ef run = ef_add(offsets[block], ef_sub(incl, mine));
 #pragma unroll
     for (int k = 0; k < LOGUP_RPT; k++) {
         const uint32_t local = threadIdx.x * rpt + k;
@@ -197,6 +214,63 @@ k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, ui
             if (r == n - 1) *S = run;
         }
     }
+}
+
+__global__ void __launch_bounds__(LOGUP_THREADS)
+k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, uint32_t rpt,
+             uint32_t* __restrict__ aux, const Ef* __restrict__ offsets, Ef* __restrict__ S) {
+    logup_scan_block(aux_width, G, n, block_rows, rpt, blockIdx.x, aux, offsets, S);
+}
+
+// ---- every table of a multi-table proof in the same three launches (logup_aux_build_multi).  The specs live in a
+// job table in device memory instead of the launch argument; a workgroup finds its job from the first-workgroup
+// prefix `first` (n_jobs + 1 ascending words, first[n_jobs] = the grid) with a search on blockIdx alone, so the job
+// index is the same in every lane and the job's words are read with scalar loads, as k_reduce_class reads its jobs.
+// (a pointer read from memory is a generic one to the compiler and costs flat loads and stores; the job's pointers
+// are device allocations and are typed so, which keeps the global accesses the by-value kernels have)
+typedef const uint32_t __attribute__((address_space(1)))* LogupGlobalConstWords;
+typedef uint32_t __attribute__((address_space(1)))* LogupGlobalWords;
+struct LogupJob {
+    LogupDev s;
+    LogupGlobalConstWords trace;
+    LogupGlobalWords aux;
+    uint64_t n;
+    uint32_t first_block, n_blocks;  // its workgroups in the rows and scan launches = its stretch of `totals`
+    uint32_t index;                  // the table's number: the high word of a zero-denominator report, its S slot
+    uint32_t pad;
+};
+
+__device__ __forceinline__ uint32_t logup_job_of_block(const uint32_t* __restrict__ first, uint32_t n_jobs) {
+    uint32_t lo = 0, hi = n_jobs;  // first[lo] <= blockIdx.x < first[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (first[mid] <= blockIdx.x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(LOGUP_THREADS)
+k_logup_rows_jobs(const LogupJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs,
+                  uint32_t block_rows, uint32_t rpt, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
+    const LogupJob& j = jobs[logup_job_of_block(first, n_jobs)];
+    logup_rows_block<false>(j.s, (const uint32_t*)j.trace, nullptr, j.n, block_rows, rpt, blockIdx.x - j.first_block, (uint32_t*)j.aux,
+                            totals + j.first_block, flag, (unsigned long long)j.index << 32);
+}
+
+// one workgroup per table: the scan never crosses into another table's totals
+__global__ void __launch_bounds__(LOGUP_SCAN_THREADS)
+k_logup_totals_jobs(const LogupJob* __restrict__ jobs, Ef* __restrict__ totals) {
+    const LogupJob& j = jobs[blockIdx.x];
+    logup_totals_scan(totals + j.first_block, j.n_blocks);
+}
+
+__global__ void __launch_bounds__(LOGUP_THREADS)
+k_logup_scan_jobs(const LogupJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs,
+                  uint32_t block_rows, uint32_t rpt, const Ef* __restrict__ totals, Ef* __restrict__ S) {
+    const LogupJob& j = jobs[logup_job_of_block(first, n_jobs)];
+    logup_scan_block(j.s.aux_width, j.s.G, j.n, block_rows, rpt, blockIdx.x - j.first_block, (uint32_t*)j.aux,
+                     totals + j.first_block, S + j.index);
 }
 
 uint32_t logup_aux_width(const LogupSpec& spec, uint32_t max_kind) {
@@ -225,10 +299,10 @@ static uint32_t logup_block_rows() {
     return rows;
 }
 
-DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace,
-                             const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table,
-                             bool takes_table) {
-    StageTimer t(&ctx, "logup aux build");
+// The device form of `spec` over `trace` (and `table`) for challenges = gamma ++ beta; every refusal of the builder
+// about the spec, the matrices and the challenges is made here, before anything is allocated.
+static LogupDev logup_dev(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace, const uint32_t challenges[8],
+                          const DeviceMatrix* table, bool takes_table) {
     LogupDev s;
     memset(&s, 0, sizeof s);
     s.aux_width = logup_aux_width(spec, takes_table ? 2 : 1);
@@ -268,6 +342,14 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
         s.beta_pow[q] = ef_to_mont(bp);
         bp = ef_mul(bp, beta);
     }
+    return s;
+}
+
+DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace,
+                             const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table,
+                             bool takes_table) {
+    StageTimer t(&ctx, "logup aux build");
+    const LogupDev s = logup_dev(ctx, spec, trace, challenges, table, takes_table);
 
     const uint64_t n = trace.height;
     const uint32_t block_rows = logup_block_rows();
@@ -304,6 +386,76 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
         throw Error(TS_ERR_INVARIANT, "logup: zero denominator at row " + std::to_string(f / s.K) + ", interaction " +
                                           std::to_string(f % s.K));
     memcpy(exposed, host + 4, 16);
+    return aux;
+}
+
+// n logup_aux_build calls with one set of challenges in three launches, one upload and one copy back.
+std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<const LogupSpec*>& specs,
+                                                const std::vector<const DeviceMatrix*>& traces,
+                                                const uint32_t challenges[8], uint32_t* exposed,
+                                                const uint32_t* table_ids) {
+    StageTimer t(&ctx, "logup aux build");
+    const size_t T = specs.size();
+    TS_REQUIRE(T >= 1 && T <= LOGUP_MAX_TABLES && traces.size() == T, TS_ERR_INVALID,
+               "logup: between 1 and 64 tables, one trace per spec");
+    const uint32_t block_rows = logup_block_rows();
+    const uint32_t rpt = (block_rows + LOGUP_THREADS - 1) / LOGUP_THREADS;
+    // every refusal first: nothing is allocated before the last table passed
+    std::vector<LogupJob> jobs(T);
+    std::vector<uint32_t> first(T + 1, 0);
+    uint64_t n_blocks = 0;
+    for (size_t k = 0; k < T; k++) {
+        TS_REQUIRE(specs[k] && traces[k], TS_ERR_INVALID, "logup: null spec or trace");
+        LogupJob& j = jobs[k];
+        memset((void*)&j, 0, sizeof j);
+        j.s = logup_dev(ctx, *specs[k], *traces[k], challenges, nullptr, false);
+        j.n = traces[k]->height;
+        j.trace = (LogupGlobalConstWords)traces[k]->buf.p;
+        j.index = (uint32_t)k;
+        j.first_block = first[k] = (uint32_t)n_blocks;
+        j.n_blocks = (uint32_t)((j.n + block_rows - 1) / block_rows);
+        n_blocks += j.n_blocks;
+        TS_REQUIRE(n_blocks <= (1u << 30), TS_ERR_INVALID, "logup: too many workgroups");
+    }
+    first[T] = (uint32_t)n_blocks;
+    std::vector<DeviceMatrix> aux(T);
+    for (size_t k = 0; k < T; k++) {
+        aux[k].buf = DevBuf<uint32_t>(&ctx, jobs[k].n * jobs[k].s.aux_width);
+        aux[k].height = jobs[k].n;
+        aux[k].width = jobs[k].s.aux_width;
+        aux[k].layout = DeviceMatrix::ROW_MAJOR;
+        jobs[k].aux = (LogupGlobalWords)aux[k].buf.p;
+    }
+    // the jobs and, behind them, the first-workgroup prefix: one upload
+    static_assert(sizeof(LogupJob) % 16 == 0, "the prefix follows the jobs, aligned");
+    std::vector<char> tab(T * sizeof(LogupJob) + (T + 1) * sizeof(uint32_t));
+    memcpy(tab.data(), (const void*)jobs.data(), T * sizeof(LogupJob));
+    memcpy(tab.data() + T * sizeof(LogupJob), first.data(), (T + 1) * sizeof(uint32_t));
+    DevBuf<Ef> d_tab(&ctx, (tab.size() + sizeof(Ef) - 1) / sizeof(Ef));
+    h2d(ctx, d_tab.p, tab.data(), tab.size());
+    const LogupJob* d_jobs = reinterpret_cast<const LogupJob*>(d_tab.p);
+    const uint32_t* d_first = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(d_tab.p) + T * sizeof(LogupJob));
+    DevBuf<Ef> totals(&ctx, n_blocks);
+    // {flag (two words), pad, pad, S_0 .. S_{T-1}}: one copy back
+    DevBuf<Ef> back(&ctx, 1 + T);
+    TS_HIP(hipMemsetAsync(back.p, 0xff, (1 + T) * sizeof(Ef), ctx.stream));
+    unsigned long long* flag = reinterpret_cast<unsigned long long*>(back.p);
+    TS_LAUNCH(ctx, k_logup_rows_jobs, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, d_jobs, d_first, (uint32_t)T,
+              block_rows, rpt, totals.p, flag);
+    TS_HIP(hipGetLastError());
+    TS_LAUNCH(ctx, k_logup_totals_jobs, dim3((unsigned)T), dim3(LOGUP_SCAN_THREADS), 0, d_jobs, totals.p);
+    TS_HIP(hipGetLastError());
+    TS_LAUNCH(ctx, k_logup_scan_jobs, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, d_jobs, d_first, (uint32_t)T,
+              block_rows, rpt, (const Ef*)totals.p, back.p + 1);
+    TS_HIP(hipGetLastError());
+    std::vector<uint32_t> host(4 * (1 + T));
+    d2h_sync(ctx, host.data(), back.p, host.size() * 4);
+    if (host[0] != ~0u || host[1] != ~0u) {  // the least (table, row * K + interaction)
+        const uint32_t k = host[1], K = jobs[k < T ? k : 0].s.K;
+        throw Error(TS_ERR_INVARIANT, "logup: zero denominator at table " + std::to_string(table_ids && k < T ? table_ids[k] : k) + ", row " +
+                                          std::to_string(host[0] / K) + ", interaction " + std::to_string(host[0] % K));
+    }
+    memcpy(exposed, host.data() + 4, 16 * T);
     return aux;
 }
 

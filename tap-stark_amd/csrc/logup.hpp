@@ -35,6 +35,36 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
                              const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table = nullptr,
                              bool takes_table = false);
 
+// The same for T traces with ONE set of challenges (the LogUp bus of a multi-table proof): aux matrix k is word for
+// word logup_aux_build(specs[k], traces[k]) and exposed[4k .. 4k+3] its S.  The specs travel in a job table in
+// device memory; three launches over the workgroups of all tables, one upload, one copy back.  Terms of kind 0 and
+// 1 only.  Throws what the single call throws, before anything is allocated, and TS_ERR_INVARIANT naming the least
+// (table, row, interaction) whose denominator is zero (table k is called table_ids[k] there, if given);
+// synchronises the stream once.
+constexpr uint32_t LOGUP_MAX_TABLES = 64;
+std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<const LogupSpec*>& specs,
+                                                const std::vector<const DeviceMatrix*>& traces,
+                                                const uint32_t challenges[8], uint32_t* exposed,
+                                                const uint32_t* table_ids = nullptr);
+
+// ---- several tables in one proof, tied by a LogUp bus (prove_multi.cpp; TSPF v7)
+struct MultiBusTable {
+    const AirProgram* air = nullptr;   // no preprocessed columns; aux columns exactly with n_challenges 2, n_exposed 4
+    DeviceMatrix trace;                // consumed; row-major where the AIR has aux columns
+    std::vector<uint32_t> public_values;
+    const LogupSpec* logup = nullptr;  // null exactly for an AIR without aux columns; terms of kind 0 and 1
+};
+// throws what check_multi_statement throws for the tables as plain ones, TS_ERR_UNSUPPORTED for preprocessed
+// columns, TS_ERR_INVALID for a spec that is missing, unwanted or does not fit its AIR and trace, for a column-major
+// trace under an aux table and for a statement without any aux table; on shapes alone, nothing is consumed
+void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables);
+// Throws TS_ERR_INVARIANT naming (table, row, interaction) of a zero denominator; the traces
+// are consumed by then.
+std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables);
+// TS_MULTI_LOGUP_PER_TABLE=1 (read on every call; a test and measurement knob): prove_multi_bus loops
+// logup_aux_build per table instead of logup_aux_build_multi.  Same proof.
+bool multi_logup_per_table();
+
 // ---- the multiplicity column of one table (logup_mult.hip)
 constexpr uint32_t LOGUP_MULT_MAX_LOOKUPS = 16;
 
@@ -56,6 +86,30 @@ struct LogupMultResult {
 // synchronises the stream once.
 LogupMultResult logup_multiplicities(Context& ctx, const LogupMultSpec& spec, DeviceMatrix& trace,
                                      const DeviceMatrix* table);
+
+// ---- the same with the lookups in OTHER traces: the table side of a LogUp bus (logup_mult.hip)
+constexpr uint32_t LOGUP_MULT_MAX_LOOKERS = 16;
+struct LogupMultLooker {
+    std::vector<LogupTerm> lookups;   // n_lookups * n_values terms over THIS looker's row
+    std::vector<LogupTerm> weights;   // n_lookups terms over this looker's row
+};
+struct LogupMultBusSpec {
+    std::vector<LogupTerm> table;     // n_values terms over the TABLE trace's row; kinds 0 and 1 on every side
+    std::vector<LogupMultLooker> lookers;
+    uint32_t out_column = 0;          // the column of the table trace that receives the result
+    uint32_t negate = 0;
+};
+struct LogupMultBusResult {
+    uint64_t n_missing;               // lookups of non-zero weight in no table row, over all lookers
+    uint64_t looker, row, lookup;     // the least miss in that lexicographic order (~0 each: none)
+};
+// logup_multiplicities with the lookups on the rows of `lookers` (row-major, this context, any heights, read only;
+// one of them may be the table trace itself): same classes, sums, skipped zero weights and words on every run.  One
+// k_mult_insert launch over the table, one count launch per looker, one k_mult_write launch, one copy back.
+// Throws TS_ERR_INVALID before any device work, as the single-trace call does per matrix; out_column may be read
+// by no term over the table trace.
+LogupMultBusResult logup_multiplicities_bus(Context& ctx, const LogupMultBusSpec& spec, DeviceMatrix& trace,
+                                            const std::vector<const DeviceMatrix*>& lookers);
 
 // ---- a lookup proof inside a batch lane (prover.cpp): no launch of its own
 // What a lookup argument says about an item's DATA, raised after the kernels finished normally: a zero denominator

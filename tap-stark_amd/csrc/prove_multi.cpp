@@ -9,11 +9,20 @@
 //   5. Pcs::open over two rounds: trace t at {zeta, zeta omega_{n_t}}, every chunk at {zeta}
 // Proof = TSPF v6.  Step 5 runs one pass per height class (open_multi.hip) or, with
 // TS_MULTI_OPEN_GENERIC=1, TwoAdicFriPcs::open; the words are the same.
+//
+// prove_multi_bus: the same with a challenge phase ACROSS the tables, a LogUp bus (TSPF v7).  After the trace root
+// gamma and beta are sampled ONCE for every table; every table with aux columns gets its LogUp matrix
+// (logup_aux_build_multi: all tables in three launches), ONE commit holds them in table order; its root and the
+// exposed sums (four words per aux table) are observed before alpha.  A table's quotient reads (aux LDE, trace LDE)
+// and the public vector pis ++ gamma ++ beta ++ its exposed words.  The opening has three rounds, in the order of
+// TSPF v4: aux matrices and traces at {zeta, zeta omega_{n_t}}, chunks at {zeta}.
 #include <stdlib.h>
 #include <string.h>
 
 #include <map>
+#include <string>
 
+#include "logup.hpp"
 #include "prover_internal.hpp"
 
 namespace ts {
@@ -43,8 +52,9 @@ namespace {
 // one committed matrix of the two rounds, in the visiting order of TwoAdicFriPcs::open: round, matrix
 struct OpenMat {
     const ColMat* m;
+    unsigned round;  // of `rounds` in open_rounds
     unsigned log_n;
-    bool trace;    // opened at zeta omega_n as well
+    bool has_next; // opened at zeta omega_n as well: a trace or an aux matrix (a ClassJob with has_next)
     size_t first;  // of its opened values (and of its raw sums) in (round, matrix, point, column) order
 };
 
@@ -57,7 +67,7 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
     size_t n_opened = 0;
     uint32_t max_w = 4;
     for (const OpenMat& om : mats) {
-        n_opened = om.first + (size_t)om.m->width * (om.trace ? 2 : 1);
+        n_opened = om.first + (size_t)om.m->width * (om.has_next ? 2 : 1);
         max_w = std::max(max_w, om.m->width);
     }
 
@@ -85,7 +95,7 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
         std::vector<uint2> groups;
         for (const OpenMat& om : mats) {
             BaryPending pend;  // the dot kernel's partial sums are taken over, its own finishing pass is not run
-            launch_bary_dots(ctx, *om.m, om.log_n, by_log_n[om.log_n].weights.p, om.trace ? 2 : 1, mail + om.first,
+            launch_bary_dots(ctx, *om.m, om.log_n, by_log_n[om.log_n].weights.p, om.has_next ? 2 : 1, mail + om.first,
                              &pend);
             jobs.push_back(BaryFinishJob{pend.partial[0].p, pend.out[0], pend.n_blocks[0], pend.n_words[0]});
             for (uint32_t g = 0; g < (pend.n_words[0] + 3) / 4; g++)
@@ -110,7 +120,7 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
     // p(z) = ((z/31)^n - 1)/n * sum_i p_i x_i/(z - x_i); the dot kernel left [col][point]
     opened.assign(n_opened, ef_zero());
     for (const OpenMat& om : mats)
-        opened_from_raw(raw.data() + om.first, om.m->width, om.trace ? 2 : 1, by_log_n[om.log_n].scale,
+        opened_from_raw(raw.data() + om.first, om.m->width, om.has_next ? 2 : 1, by_log_n[om.log_n].scale,
                         opened.data() + om.first);
 
     // ---- reduce (two_adic_pcs.rs:371-383), one launch per height class
@@ -138,11 +148,11 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
         j.d = om.m->d;
         j.col_stride = om.m->col_stride;
         j.width = w;
-        j.has_next = om.trace ? 1 : 0;
+        j.has_next = om.has_next ? 1 : 0;
         j.off[0] = ledger.visit(log_h, &opened[om.first], w, 0).off;
-        if (om.trace) j.off[1] = ledger.visit(log_h, &opened[om.first + w], w, 1).off;
+        if (om.has_next) j.off[1] = ledger.visit(log_h, &opened[om.first + w], w, 1).off;
         cl.weights_at.push_back(words.size());
-        if (!om.trace) ledger.fold_weights(j.off[0], w, words);
+        if (!om.has_next) ledger.fold_weights(j.off[0], w, words);
         cl.jobs.push_back(j);
     }
     DevBuf<uint32_t> d_apow(&ctx, words.size());
@@ -175,6 +185,31 @@ void open_classes(TwoAdicFriPcs& pcs, const std::vector<OpenMat>& mats, Ef zeta,
         inputs.push_back(std::move(ro));
         log_lens.push_back(log_h);
     }
+}
+
+// Step 5 of both provers: `mats` in the visiting order of Pcs::open over `rounds`; samples the batch challenge,
+// fills `opened` in (round, matrix, point, column) order and returns the FriProof words.  The per-class kernels,
+// or TwoAdicFriPcs::open with TS_MULTI_OPEN_GENERIC=1: the same words.
+std::vector<uint32_t> open_rounds(TwoAdicFriPcs& pcs, BfChallenger& challenger, const std::vector<const PcsData*>& rounds,
+                                  const std::vector<OpenMat>& mats, Ef zeta, std::vector<Ef>& opened) {
+    std::vector<uint32_t> fri_words;
+    if (multi_open_generic()) {
+        std::vector<TwoAdicFriPcs::OpenRound> rs(rounds.size());
+        for (size_t r = 0; r < rounds.size(); r++) rs[r].data = rounds[r];
+        for (const OpenMat& om : mats) {
+            std::vector<Ef> pts{zeta};
+            if (om.has_next) pts.push_back(efc_mul_base(zeta, two_adic_generator(om.log_n)));
+            rs[om.round].points.push_back(std::move(pts));
+        }
+        fri_words = pcs.open(rs, challenger, opened);
+    } else {
+        const Ef batch_alpha = challenger.sample();  // two_adic_pcs.rs:312
+        std::vector<DevBuf<Ef>> inputs;
+        std::vector<unsigned> log_lens;
+        open_classes(pcs, mats, zeta, batch_alpha, opened, inputs, log_lens);
+        pcs.fri_prove(inputs, log_lens, challenger, rounds, fri_words);
+    }
+    return fri_words;
 }
 
 }  // namespace
@@ -220,7 +255,7 @@ std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, 
     std::vector<OpenMat> mats;
     size_t first = 0, qi = 0;
     for (size_t t = 0; t < T; t++) {
-        mats.push_back(OpenMat{&trace_data->ldes[t], st[t].log_degree, true, first});
+        mats.push_back(OpenMat{&trace_data->ldes[t], 0, st[t].log_degree, true, first});
         first += 2 * (size_t)st[t].w;
     }
     for (size_t t = 0; t < T; t++)
@@ -228,38 +263,196 @@ std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, 
             const ColMat& m = quotient_data->ldes[qi];
             TS_REQUIRE(m.width == 4 && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
                        "prove_multi: a committed chunk has another shape than its table's");
-            mats.push_back(OpenMat{&m, st[t].log_degree, false, first});
+            mats.push_back(OpenMat{&m, 1, st[t].log_degree, false, first});
             first += 4;
         }
 
     std::vector<Ef> opened;
-    std::vector<uint32_t> fri_words;
-    const std::vector<const PcsData*> rounds{trace_data.get(), quotient_data.get()};
-    if (multi_open_generic()) {
-        std::vector<TwoAdicFriPcs::OpenRound> rs(2);
-        rs[0].data = rounds[0];
-        rs[1].data = rounds[1];
-        for (const OpenMat& om : mats) {
-            std::vector<Ef> pts{zeta};
-            if (om.trace) pts.push_back(efc_mul_base(zeta, two_adic_generator(om.log_n)));
-            rs[om.trace ? 0 : 1].points.push_back(std::move(pts));
-        }
-        fri_words = pcs.open(rs, challenger, opened);
-    } else {
-        const Ef batch_alpha = challenger.sample();  // two_adic_pcs.rs:312
-        std::vector<DevBuf<Ef>> inputs;
-        std::vector<unsigned> log_lens;
-        open_classes(pcs, mats, zeta, batch_alpha, opened, inputs, log_lens);
-        pcs.fri_prove(inputs, log_lens, challenger, rounds, fri_words);
-    }
+    const std::vector<uint32_t> fri_words =
+        open_rounds(pcs, challenger, {trace_data.get(), quotient_data.get()}, mats, zeta, opened);
 
     std::vector<uint32_t> pf;
     pf.reserve(32 + 3 * T + opened.size() * 4 + fri_words.size());
     ProofWriter pw(pf);
     std::vector<ProofWriter::TableShape> shapes;
-    for (const Statement& s : st) shapes.push_back({s.log_degree, s.w, s.qd});
+    for (const Statement& s : st) shapes.push_back({s.log_degree, s.w, s.qd, 0, 0});
     pw.header_multi(shapes);
     pw.commitment(trace_data->root, 8);
+    pw.commitment(quotient_data->root, 8);
+    pw.opened_values(opened);
+    pw.words(fri_words.data(), fri_words.size());
+    return pf;
+}
+
+// ------------------------------------------------------------------ the same with a LogUp bus across the tables
+bool multi_logup_per_table() {
+    const char* e = getenv("TS_MULTI_LOGUP_PER_TABLE");
+    return e && *e && atoi(e) != 0;
+}
+
+void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables) {
+    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
+               "prove_multi_bus: between 1 and 64 tables");
+    uint32_t n_chunks = 0, n_aux = 0;
+    for (size_t k = 0; k < tables.size(); k++) {
+        const MultiBusTable& t = tables[k];
+        const std::string w = "prove_multi_bus: table " + std::to_string(k);
+        TS_REQUIRE(t.air, TS_ERR_INVALID, w + ": null AIR");
+        TS_REQUIRE(t.air->preprocessed_width == 0, TS_ERR_UNSUPPORTED,
+                   w + ": the AIR has preprocessed columns; a multi-table proof has no key round");
+        const uint32_t aw = t.air->aux_width;
+        if (aw) {
+            TS_REQUIRE(t.air->n_challenges == 2 && t.air->n_exposed == 4, TS_ERR_INVALID,
+                       w + ": an AIR on the bus has 2 challenges (gamma, beta) and 4 exposed words (its sum)");
+            TS_REQUIRE(t.logup, TS_ERR_INVALID, w + ": the AIR has aux columns and no logup spec");
+            // (a kind-2 term is refused here: there is no preprocessed table to read)
+            TS_REQUIRE(logup_aux_width(*t.logup, 1) == aw, TS_ERR_INVALID,
+                       w + ": the logup spec's aux width is not the AIR's");
+            for (const LogupInteraction& it : t.logup->interactions) {
+                std::vector<LogupTerm> terms = it.values;
+                terms.push_back(it.multiplicity);
+                for (const LogupTerm& tm : terms)
+                    TS_REQUIRE(tm.kind ? tm.value < t.trace.width : tm.value < P, TS_ERR_INVALID,
+                               w + ": the logup spec reads a column outside the trace, or has a non-canonical constant");
+            }
+            TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
+                       w + ": the trace of a table with aux columns must be row-major (the LogUp builder reads its rows)");
+            n_aux++;
+        } else {
+            TS_REQUIRE(t.air->n_challenges == 0 && t.air->n_exposed == 0, TS_ERR_INVALID,
+                       w + ": challenges or exposed words without aux columns");
+            TS_REQUIRE(!t.logup, TS_ERR_INVALID, w + ": a logup spec for an AIR without aux columns");
+        }
+        n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
+    }
+    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
+               "prove_multi_bus: more than 64 quotient chunks over all tables (the limit of one committed batch)");
+    TS_REQUIRE(n_aux > 0, TS_ERR_INVALID,
+               "prove_multi_bus: no table has aux columns; plain tables are proved by ts_prove_multi (TSPF v6)");
+}
+
+std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables) {
+    check_multi_bus_statement(pcs.fri(), tables);
+    Context& ctx = pcs.ctx();
+    const size_t T = tables.size();
+    std::vector<Statement> st;
+    unsigned log_max = 0;
+    for (const MultiBusTable& t : tables) {
+        st.push_back(check_statement(pcs.fri(), *t.air, t.trace.width, t.trace.height, t.public_values.size()));
+        log_max = std::max(log_max, st.back().log_N);
+    }
+    ctx.ensure_twiddles(std::max(1u, log_max));
+
+    challenger.observe((uint32_t)T);
+    for (const Statement& s : st) challenger.observe(s.log_degree);
+
+    // one commit of every trace; the row-major ones stay alive for the LogUp builder (the LDE stage only reads them)
+    std::vector<DeviceMatrix> tv;
+    for (MultiBusTable& t : tables) tv.push_back(std::move(t.trace));
+    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, std::vector<uint32_t>(T, 1u), true, /*keep_row_major=*/true);
+    for (size_t t = 0; t < T; t++)
+        if (!tables[t].air->aux_width) tv[t].buf.reset();  // a plain table's rows are not read again
+    challenger.observe_commitment(trace_data->root);
+    uint32_t challenges[8];
+    for (int k = 0; k < 2; k++) {  // gamma, beta: one tuple encoding on the whole bus
+        const Ef c = challenger.sample();
+        memcpy(challenges + 4 * k, c.c, 16);
+    }
+
+    // the LogUp matrices of the tables that have one, then ONE commit of them in table order
+    std::vector<size_t> aux_of(T, ~(size_t)0), aux_tables;
+    for (size_t t = 0; t < T; t++)
+        if (tables[t].air->aux_width) {
+            aux_of[t] = aux_tables.size();
+            aux_tables.push_back(t);
+        }
+    const size_t A = aux_tables.size();
+    std::vector<uint32_t> exposed(4 * A, 0);
+    std::vector<DeviceMatrix> av;
+    if (multi_logup_per_table()) {
+        for (size_t a = 0; a < A; a++) {
+            const size_t t = aux_tables[a];
+            try {
+                av.push_back(logup_aux_build(ctx, *tables[t].logup, tv[t], challenges, &exposed[4 * a]));
+            } catch (const Error& e) {  // the single call names row and interaction: add the table
+                if (e.code != TS_ERR_INVARIANT) throw;
+                throw Error(TS_ERR_INVARIANT, "table " + std::to_string(t) + ": " + e.what());
+            }
+        }
+    } else {
+        std::vector<const LogupSpec*> specs;
+        std::vector<const DeviceMatrix*> traces;
+        for (size_t t : aux_tables) {
+            specs.push_back(tables[t].logup);
+            traces.push_back(&tv[t]);
+        }
+        std::vector<uint32_t> ids(aux_tables.begin(), aux_tables.end());  // a report names the proof's table
+        av = logup_aux_build_multi(ctx, specs, traces, challenges, exposed.data(), ids.data());
+    }
+    for (DeviceMatrix& m : tv) m.buf.reset();  // no trace row is read again
+    std::unique_ptr<PcsData> aux_data = pcs.commit(av, std::vector<uint32_t>(A, 1u));
+    challenger.observe_commitment(aux_data->root);
+    for (uint32_t e : exposed) challenger.observe(e);
+    const Ef alpha = challenger.sample();
+
+    // the chunks of every table over (its aux LDE, its trace LDE) in the batches, then one commit of all of them
+    std::vector<DeviceMatrix> chunks;
+    std::vector<uint32_t> shifts;
+    for (size_t t = 0; t < T; t++) {
+        std::vector<uint32_t> pis = tables[t].public_values;
+        SideLdes side;
+        if (aux_of[t] != ~(size_t)0) {
+            pis.insert(pis.end(), challenges, challenges + 8);
+            pis.insert(pis.end(), &exposed[4 * aux_of[t]], &exposed[4 * aux_of[t]] + 4);
+            const ColMat& m = aux_data->ldes[aux_of[t]];
+            TS_REQUIRE(m.width == tables[t].air->aux_width && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
+                       "prove_multi_bus: a committed aux matrix has another shape than its table's");
+            side.m[side.n++] = &m;
+        }
+        std::vector<DeviceMatrix> c = pcs.quotient_chunks_slab(trace_data->ldes[t], st[t].log_degree, TwoAdicFriPcs::Slab{},
+                                                               *tables[t].air, pis, alpha, GENERATOR, side);
+        const std::vector<uint32_t> sh = chunk_domain_shifts(GENERATOR, st[t].log_degree, st[t].lqd);
+        for (auto& m : c) chunks.push_back(std::move(m));
+        shifts.insert(shifts.end(), sh.begin(), sh.end());
+    }
+    std::unique_ptr<PcsData> quotient_data = pcs.commit(chunks, shifts);
+    challenger.observe_commitment(quotient_data->root);
+    const Ef zeta = challenger.sample();
+
+    // the three rounds in the visiting order of Pcs::open
+    std::vector<OpenMat> mats;
+    size_t first = 0, qi = 0;
+    for (size_t a = 0; a < A; a++) {
+        const size_t t = aux_tables[a];
+        mats.push_back(OpenMat{&aux_data->ldes[a], 0, st[t].log_degree, true, first});
+        first += 2 * (size_t)aux_data->ldes[a].width;
+    }
+    for (size_t t = 0; t < T; t++) {
+        mats.push_back(OpenMat{&trace_data->ldes[t], 1, st[t].log_degree, true, first});
+        first += 2 * (size_t)st[t].w;
+    }
+    for (size_t t = 0; t < T; t++)
+        for (uint32_t c = 0; c < st[t].qd; c++, qi++) {
+            const ColMat& m = quotient_data->ldes[qi];
+            TS_REQUIRE(m.width == 4 && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
+                       "prove_multi_bus: a committed chunk has another shape than its table's");
+            mats.push_back(OpenMat{&m, 2, st[t].log_degree, false, first});
+            first += 4;
+        }
+    std::vector<Ef> opened;
+    const std::vector<uint32_t> fri_words =
+        open_rounds(pcs, challenger, {aux_data.get(), trace_data.get(), quotient_data.get()}, mats, zeta, opened);
+
+    std::vector<uint32_t> pf;
+    pf.reserve(32 + 5 * T + exposed.size() + opened.size() * 4 + fri_words.size());
+    ProofWriter pw(pf);
+    std::vector<ProofWriter::TableShape> shapes;
+    for (size_t t = 0; t < T; t++)
+        shapes.push_back({st[t].log_degree, st[t].w, st[t].qd, tables[t].air->aux_width, tables[t].air->n_exposed});
+    pw.header_multi(shapes, 7);
+    pw.commitment(trace_data->root, 8);
+    pw.commitment(aux_data->root, 8);
+    pw.words(exposed.data(), exposed.size());
     pw.commitment(quotient_data->root, 8);
     pw.opened_values(opened);
     pw.words(fri_words.data(), fri_words.size());

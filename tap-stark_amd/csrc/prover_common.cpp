@@ -254,14 +254,18 @@ void ProofWriter::header(uint32_t version, unsigned log_degree, uint32_t width, 
     if (version >= 2) out_.push_back(extra);
 }
 
-void ProofWriter::header_multi(const std::vector<TableShape>& tables) {
+void ProofWriter::header_multi(const std::vector<TableShape>& tables, uint32_t version) {
     out_.push_back(TSPF_MAGIC);
-    out_.push_back(6);
+    out_.push_back(version);
     out_.push_back((uint32_t)tables.size());
     for (auto& t : tables) {
         out_.push_back(t.log_degree);
         out_.push_back(t.width);
         out_.push_back(t.qd);
+        if (version >= 7) {
+            out_.push_back(t.aux_width);
+            out_.push_back(t.n_exposed);
+        }
     }
 }
 

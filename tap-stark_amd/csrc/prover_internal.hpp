@@ -119,9 +119,10 @@ public:
     // version 1; 2 with the extra num_queries word; 3 with the extra preprocessed_width word; 4 with the extra
     // aux_width word (the caller appends n_challenges and n_exposed)
     void header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t extra);
-    // version 6 (prove_multi): [magic, 6, T], then T x [log_degree, width, qd] in table order
-    struct TableShape { unsigned log_degree; uint32_t width, qd; };
-    void header_multi(const std::vector<TableShape>& tables);
+    // version 6 (prove_multi): [magic, 6, T], then T x [log_degree, width, qd] in table order; version 7
+    // (prove_multi_bus): [magic, 7, T], then T x [log_degree, width, qd, aux_width, n_exposed]
+    struct TableShape { unsigned log_degree; uint32_t width, qd, aux_width, n_exposed; };
+    void header_multi(const std::vector<TableShape>& tables, uint32_t version = 6);
     void commitment(const uint32_t* roots, size_t n_words) { words(roots, n_words); }  // 8, or Q x 8 (taptrees)
     void opened_values(const std::vector<Ef>& values);
     void begin_rounds(uint32_t n_rounds) { out_.push_back(n_rounds); }  // then one commitment() per round

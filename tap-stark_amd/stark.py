@@ -1247,6 +1247,158 @@ def verify_multi(config: StarkConfig, airs, challenger: BfChallenger, proof, pub
         raise VerificationError(verdict.value)
 
 
+@dataclass
+class MultiBusTableOpening(MultiTableOpening):
+    """One table of a :class:`MultiBusProof`: what :class:`MultiTableOpening` holds, its aux header words and
+    opened aux rows, and its four exposed words (its share of the bus sum); empty arrays for a plain table."""
+    aux_width: int = 0
+    n_exposed: int = 0
+    aux_local: np.ndarray = None   # (aux_width, 4)
+    aux_next: np.ndarray = None    # (aux_width, 4)
+    exposed: np.ndarray = None     # (n_exposed,)
+
+
+class MultiBusProof(MultiProof):
+    """A TSPF v7 proof (``ts_prove_multi_bus``): a :class:`MultiProof` whose tables are tied by a LogUp bus.  Beside
+    the fields of ``MultiProof`` (``tables`` holds :class:`MultiBusTableOpening`): ``aux_commit``, ``exposed`` (the
+    exposed words, four per table with aux columns, in table order) and ``bus_sum`` (their EF4 sum over the tables:
+    zero exactly when the bus balances)."""
+
+    _FIELDS = MultiProof._FIELDS + ("aux_commit", "exposed", "bus_sum")
+
+    def __getattr__(self, name):
+        if name in MultiBusProof._FIELDS:
+            self._parse()
+            return self.__dict__[name]
+        raise AttributeError(name)
+
+    def _parse(self) -> None:
+        w = self.words
+        pos = 0
+
+        def take(n):
+            nonlocal pos
+            out = w[pos:pos + n]
+            if len(out) != n:
+                raise ValueError("truncated proof")
+            pos += n
+            return out
+
+        magic, version, T = (int(x) for x in take(3))
+        if magic != TSPF_MAGIC or version != 7 or not 1 <= T <= 64:
+            raise ValueError("not a TSPF v7 proof")
+        shapes = [tuple(int(x) for x in row) for row in take(5 * T).reshape(T, 5)]
+        d = {"trace_commit": take(8), "aux_commit": take(8), "query_proofs": []}
+        d["exposed"] = take(sum(ne for *_, aw, ne in shapes if aw))
+        d["bus_sum"] = (d["exposed"].reshape(-1, 4).astype(np.uint64).sum(axis=0) % np.uint64(P)).astype(np.uint32)
+        d["quotient_commit"] = take(8)
+        start = pos
+        aux = [(take(4 * aw).reshape(-1, 4), take(4 * aw).reshape(-1, 4)) if aw else (w[:0].reshape(0, 4),) * 2
+               for *_, aw, _ in shapes]
+        locals_ = [(take(4 * wd).reshape(-1, 4), take(4 * wd).reshape(-1, 4)) for _, wd, *_ in shapes]
+        d["tables"], e = [], 0
+        for (ld, wd, qd, aw, ne), (al, an), (tl, tn) in zip(shapes, aux, locals_):
+            ex = d["exposed"][e:e + ne] if aw else w[:0]
+            e += ne if aw else 0
+            d["tables"].append(MultiBusTableOpening(ld, wd, qd, tl, tn, take(16 * qd).reshape(-1, 4, 4), aw, ne, al, an, ex))
+        d["opened_words"] = w[start:pos]
+        d["fri_words"] = w[pos:]
+        R = int(take(1)[0])
+        d["commit_phase_commits"] = take(8 * R).reshape(R, 8)
+        for _ in range(int(take(1)[0])):
+            batches = []
+            for _ in range(int(take(1)[0])):
+                vals = [take(int(take(1)[0])) for _ in range(int(take(1)[0]))]
+                plen = int(take(1)[0])
+                batches.append(BatchOpening(vals, take(8 * plen).reshape(plen, 8)))
+            steps = []
+            for _ in range(R):
+                vals = take(8).reshape(2, 4)
+                plen = int(take(1)[0])
+                steps.append((vals, take(8 * plen).reshape(plen, 8)))
+            d["query_proofs"].append(QueryProof(batches, steps))
+        d["final_poly"] = take(4)
+        d["pow_witness"] = int(take(1)[0])
+        if pos != len(w):
+            raise ValueError("trailing words in proof")
+        self.__dict__.update(d)
+
+
+def _multi_bus_capacity(shapes, fri: FriConfig) -> int:
+    """An upper bound (exact when the tallest table has aux columns) on the TSPF v7 words of a proof over
+    ``shapes`` = [(n, w, log_quotient_degree, aux_width), ...]."""
+    v6 = _multi_capacity([(n, w, lqd) for n, w, lqd, _ in shapes], fri)
+    log_max = max(max(n, 1).bit_length() - 1 for n, *_ in shapes) + fri.log_blowup
+    aux = [aw for *_, aw in shapes if aw]
+    return v6 + 2 * len(shapes) + 8 + 4 * len(aux) + 8 * sum(aux) + fri.num_queries * (
+        2 + len(aux) + sum(aux) + 8 * log_max)
+
+
+def prove_multi_bus(config: StarkConfig, airs, challenger: BfChallenger, traces, public_values, logups) -> MultiBusProof:
+    """``ts_prove_multi_bus``: ``prove_multi`` with a LogUp bus across the tables (TSPF v7).  ``logups``: per table
+    the :class:`~tapstark_amd.air.LogUp` whose columns are the AIR's aux columns, or None for a plain table.  Gamma
+    and beta are sampled once for every table; ``proof.bus_sum`` is zero exactly when everything sent on the bus
+    is received (``verify_multi_bus`` checks it).  An AIR given as a ``BaseAir`` is compiled with the aux
+    dimensions of its ``LogUp``."""
+    pcs = config.pcs
+    ctx = pcs.ctx
+    T = len(airs)
+    if len(traces) != T or len(public_values) != T or len(logups) != T:
+        raise ValueError("prove_multi_bus: one trace, one public-value list and one LogUp (or None) per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
+    tabs = (_lib.MultiBusTableC * max(T, 1))()
+    keep = []
+    for k in range(T):
+        tabs[k].struct_size = C.sizeof(_lib.MultiBusTableC)
+        tabs[k].n_public = len(pis[k])
+        tabs[k].air = airs[k].h
+        tabs[k].trace = traces[k].h
+        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
+        if logups[k] is not None:
+            keep.append(logups[k]._spec_c())
+            tabs[k].logup = C.pointer(keep[-1][0])
+    shapes = [(*t.dims(), a.log_quotient_degree, lg.aux_width if lg is not None else 0)
+              for t, a, lg in zip(traces, airs, logups)]
+    out = _proof_buffer(ctx, _multi_bus_capacity(shapes, pcs.fri) if T else 1)
+    n_words = C.c_size_t()
+    cfg = pcs.fri._c()
+    ctx.check(ctx._l.ts_prove_multi_bus(ctx.h, C.byref(cfg), challenger.h, tabs, T, _p(out), len(out),
+                                        C.byref(n_words)))
+    del keep
+    return MultiBusProof(out[: n_words.value].copy())
+
+
+def verify_multi_bus(config: StarkConfig, airs, challenger: BfChallenger, proof, public_values, check_bus: bool = True):
+    """``ts_verify_multi_bus``; host only.  Raises ``VerificationError`` on a rejected proof and, with ``check_bus``,
+    ``ValueError`` when the exposed sums of the tables do not add up to zero (something sent on the bus is not
+    received).  Returns ``(exposed, bus_sum)``: the exposed words, four per table with aux columns, and their sum."""
+    T = len(airs)
+    if len(public_values) != T:
+        raise ValueError("verify_multi_bus: one public-value list per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
+    l = _lib.lib()
+    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
+    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
+    n_pub = _u32([len(p) for p in pis] or [0])
+    cfg = config.pcs.fri._c()
+    verdict = C.c_int(-1)
+    exposed, bus_sum = np.zeros(4 * max(T, 1), dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    rc = l.ts_verify_multi_bus(C.byref(cfg), challenger.h, handles, T, pv, _p(n_pub), _p(words), len(words),
+                               _p(exposed), len(exposed), _p(bus_sum), C.byref(verdict))
+    if rc:
+        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_multi_bus").decode())
+    if verdict.value != 0:
+        raise VerificationError(verdict.value)
+    n_aux = sum(1 for a in airs if a.aux_width)
+    if check_bus and bus_sum.any():
+        raise ValueError("verify_multi_bus: the exposed sums of the tables do not add up to zero: the bus does not balance")
+    return exposed[: 4 * n_aux], bus_sum
+
+
 def prove_stream(lanes, traces, lane_of, public_values, gate_ms: float = 0.0, want_times: bool = True):
     """``ts_prove_stream``: ``len(traces)`` independent proofs on the contexts of ``lanes`` = [(StarkConfig,
     CompiledAir), ...] (one context each, same device, same FriConfig), one host thread per lane INSIDE the
