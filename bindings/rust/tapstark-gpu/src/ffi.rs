@@ -5,7 +5,7 @@ use core::ffi::{c_char, c_int, c_uint, c_void};
 
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
 opaque!(ts_ctx, ts_matrix, ts_air, ts_pcs_data, ts_challenger, ts_rccl_comm, ts_comm_group, ts_taptree,
-        ts_tap_mmcs_data);
+        ts_tap_mmcs_data, ts_multi_key);
 
 pub type ts_status = c_int;
 pub const TS_OK: ts_status = 0;
@@ -417,6 +417,35 @@ extern "C" {
     pub fn ts_logup_multiplicities_bus(ctx: *mut ts_ctx, spec: *const ts_logup_mult_bus_spec,
                                        table_trace: *mut ts_matrix, lookers: *const *const ts_matrix,
                                        n_missing: *mut u64, first_missing: *mut u64) -> ts_status;
+    /// the key of a multi-table proof: ONE committed batch of 1..64 preprocessed matrices of mixed heights (the root of
+    /// ts_pcs_commit of the same list); made once, consumed by no proof.  keep_values = 1 keeps the row-major inputs
+    /// alive inside the key (no second copy) for ts_multi_key_values
+    pub fn ts_multi_key_commit(ctx: *mut ts_ctx, cfg: *const ts_fri_config, n_mats: u32, mats: *const *mut ts_matrix,
+                               keep_values: c_int, root_out: *mut u32, out: *mut *mut ts_multi_key) -> ts_status;
+    pub fn ts_multi_key_info(key: *const ts_multi_key, idx: u32, height: *mut u64, width: *mut u32) -> ts_status;
+    /// a borrowed handle (lives as long as the key; never freed or consumed by the caller)
+    pub fn ts_multi_key_values(key: *const ts_multi_key, idx: u32, out: *mut *const ts_matrix) -> ts_status;
+    pub fn ts_multi_key_free(ctx: *mut ts_ctx, key: *mut ts_multi_key) -> ts_status;
+    /// ts_prove_multi_bus against a key (TSPF v8): the i-th table with preprocessed columns reads key matrix i; specs
+    /// may use kind-2 terms; without any aux table the challenge phase is skipped
+    pub fn ts_prove_multi_key(ctx: *mut ts_ctx, cfg: *const ts_fri_config, chal: *mut ts_challenger,
+                              key: *const ts_multi_key, tables: *mut ts_multi_bus_table, n_tables: u32,
+                              proof_out: *mut u32, cap_words: usize, n_words_out: *mut usize) -> ts_status;
+    /// host only; `key_root`: the eight words the verifier holds; outputs as ts_verify_multi_bus (none without aux tables)
+    pub fn ts_verify_multi_key(cfg: *const ts_fri_config, chal: *mut ts_challenger, key_root: *const u32,
+                               airs: *const *const ts_air, n_tables: u32, public_values: *const *const u32,
+                               n_public: *const u32, proof: *const u32, n_words: usize, exposed_out: *mut u32,
+                               cap_exposed: u32, bus_sum: *mut u32, verdict: *mut c_int) -> ts_status;
+    /// ts_logup_aux_build_multi with kind-2 terms: table k's read `preprocessed[k]` (entries may be null)
+    pub fn ts_logup_aux_build_multi_pre(ctx: *mut ts_ctx, n: u32, specs: *const *const ts_logup_spec,
+                                        preprocessed: *const *const ts_matrix, traces: *const *const ts_matrix,
+                                        challenges: *const u32, aux_out: *mut *mut ts_matrix,
+                                        exposed_out: *mut u32) -> ts_status;
+    /// ts_logup_multiplicities_bus whose table terms may be of kind 2: columns of `table_preprocessed`
+    pub fn ts_logup_multiplicities_bus_pre(ctx: *mut ts_ctx, spec: *const ts_logup_mult_bus_spec,
+                                           table_preprocessed: *const ts_matrix, table_trace: *mut ts_matrix,
+                                           lookers: *const *const ts_matrix, n_missing: *mut u64,
+                                           first_missing: *mut u64) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

@@ -239,6 +239,100 @@ pub fn logup_multiplicities_bus<'a>(ctx: &'a GpuContext, spec: &ts_logup_mult_bu
     (n_missing, first)
 }
 
+/// `ts_multi_key`: the preprocessed matrices of a multi-table proof committed once in one batch (mixed heights); never
+/// consumed, so one key serves any number of `prove_gpu_multi_key` calls.  `root` is what the verifier holds.
+pub struct MultiKey<'a> {
+    ctx: &'a GpuContext,
+    pub(crate) raw: *mut ts_multi_key,
+    pub root: [u32; 8],
+}
+
+impl<'a> MultiKey<'a> {
+    /// `ts_multi_key_commit`: consumes `matrices`; with `keep_values` their rows stay alive inside the key.
+    pub fn commit(pcs: &GpuFriPcs<'a>, matrices: Vec<DeviceMatrix<'a>>, keep_values: bool) -> Self {
+        let ctx = pcs.ctx;
+        let cfg = pcs.fri.raw();
+        let raws: Vec<*mut ts_matrix> = matrices.into_iter().map(|m| m.into_raw()).collect();
+        let (mut raw, mut root) = (ptr::null_mut(), [0u32; 8]);
+        let rc = unsafe {
+            ts_multi_key_commit(ctx.raw, &cfg, raws.len() as u32, raws.as_ptr(), keep_values as std::os::raw::c_int,
+                                root.as_mut_ptr(), &mut raw)
+        };
+        for m in raws {
+            unsafe { ts_matrix_free(ctx.raw, m) };
+        }
+        ctx.check(rc, "ts_multi_key_commit");
+        MultiKey { ctx, raw, root }
+    }
+
+    /// `ts_multi_key_values`: the row-major values of matrix `idx`, borrowed from the key; `None` without kept values.
+    pub fn values(&self, idx: u32) -> Option<*const ts_matrix> {
+        let mut out: *const ts_matrix = ptr::null();
+        let rc = unsafe { ts_multi_key_values(self.raw, idx, &mut out) };
+        if rc != 0 { None } else { Some(out) }
+    }
+}
+
+impl Drop for MultiKey<'_> {
+    fn drop(&mut self) {
+        unsafe { ts_multi_key_free(self.ctx.raw, self.raw) };
+    }
+}
+
+/// `ts_prove_multi_key`: `prove_gpu_multi_bus` against a commit-once key (TSPF v8).  The i-th table whose AIR has
+/// preprocessed columns reads matrix i of `key`; a `logup` may use kind-2 terms over it.
+pub fn prove_gpu_multi_key(pcs: &GpuFriPcs<'_>, challenger: &mut GpuChallenger, key: &MultiKey<'_>,
+                           tables: Vec<MultiBusTable<'_>>) -> Vec<u32> {
+    let ctx = pcs.ctx;
+    let cfg = pcs.fri.raw();
+    let pis: Vec<Vec<u32>> = tables.iter().map(|t| t.public_values.clone()).collect();
+    let airs: Vec<*const ts_air> = tables.iter().map(|t| t.air.raw as *const ts_air).collect();
+    let specs: Vec<*const ts_logup_spec> =
+        tables.iter().map(|t| t.logup.map_or(ptr::null(), |s| s as *const ts_logup_spec)).collect();
+    let raws: Vec<*mut ts_matrix> = tables.into_iter().map(|t| t.trace.into_raw()).collect();
+    let mut raw_tables: Vec<ts_multi_bus_table> = (0..raws.len())
+        .map(|t| ts_multi_bus_table {
+            struct_size: core::mem::size_of::<ts_multi_bus_table>() as u32,
+            n_public: pis[t].len() as u32,
+            air: airs[t],
+            trace: raws[t],
+            public_values: if pis[t].is_empty() { ptr::null() } else { pis[t].as_ptr() },
+            logup: specs[t],
+        })
+        .collect();
+    let mut out = vec![0u32; 1 << 22];
+    let mut n = 0usize;
+    let rc = unsafe {
+        ts_prove_multi_key(ctx.raw, &cfg, challenger.raw, key.raw, raw_tables.as_mut_ptr(), raw_tables.len() as u32,
+                           out.as_mut_ptr(), out.len(), &mut n)
+    };
+    for m in raws {
+        unsafe { ts_matrix_free(ctx.raw, m) };
+    }
+    ctx.check(rc, "ts_prove_multi_key");
+    out.truncate(n);
+    out
+}
+
+/// `ts_verify_multi_key` (host only): as `verify_gpu_multi_bus`, against the key's root.
+pub fn verify_gpu_multi_key(fri: FriConfig, challenger: &mut GpuChallenger, key_root: &[u32; 8], airs: &[&CompiledAir<'_>],
+                            public_values: &[Vec<u32>], proof: &[u32]) -> (i32, Vec<u32>, [u32; 4]) {
+    let cfg = fri.raw();
+    let raw_airs: Vec<*const ts_air> = airs.iter().map(|a| a.raw as *const ts_air).collect();
+    let ptrs: Vec<*const u32> =
+        public_values.iter().map(|p| if p.is_empty() { ptr::null() } else { p.as_ptr() }).collect();
+    let counts: Vec<u32> = public_values.iter().map(|p| p.len() as u32).collect();
+    let mut verdict: std::os::raw::c_int = -1;
+    let mut exposed = vec![0u32; 4 * airs.len().max(1)];
+    let mut bus_sum = [0u32; 4];
+    let rc = unsafe {
+        ts_verify_multi_key(&cfg, challenger.raw, key_root.as_ptr(), raw_airs.as_ptr(), raw_airs.len() as u32,
+                            ptrs.as_ptr(), counts.as_ptr(), proof.as_ptr(), proof.len(), exposed.as_mut_ptr(),
+                            exposed.len() as u32, bus_sum.as_mut_ptr(), &mut verdict)
+    };
+    (if rc != 0 { -1 } else { verdict as i32 }, exposed, bus_sum)
+}
+
 /// A stream of proofs from HOST traces at the PCIe-inclusive rate (INTEGRATION.md "Three rates").
 ///
 /// `prove_gpu` above uploads synchronously from pageable memory: the GPU idles during the copy and

@@ -1167,6 +1167,90 @@ ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec*
                                       const ts_matrix* const* lookers /* n_lookers */, uint64_t* n_missing,
                                       uint64_t first_missing[3]);
 
+/* ---- a multi-table proof against a commit-once key: fixed tables on the bus -------------------------------------
+ * The tables a bus needs beyond a range -- byte operations (a, b, a xor b), a program ROM, a decode table -- are not
+ * pinned by a transition constraint: they are preprocessed columns whose commitment the verifier holds.  A
+ * ts_multi_key is ONE committed batch of 1 .. 64 preprocessed matrices of mixed power-of-two heights on their natural
+ * domains (shift 1): its root is what ts_pcs_commit gives for the same list.  It is made once on a context, consumed
+ * by no proof, and serves any number of them; the matrices' LDE and leaf hashing leave every proof.
+ * keep_values = 1 (row-major matrices only) keeps the inputs alive inside the key, with no second copy (the LDE stage
+ * only reads them): ts_multi_key_values lends matrix idx as a handle for ts_logup_aux_build_multi_pre,
+ * ts_logup_multiplicities_bus_pre and for kind-2 terms inside ts_prove_multi_key; the handle lives as long as the key
+ * and must not be freed or consumed.  Without kept values ts_multi_key_values is TS_ERR_INVALID.  `mats` are consumed.
+ * ts_multi_key_info gives the natural height and the width of matrix idx. */
+typedef struct ts_multi_key ts_multi_key;
+ts_status ts_multi_key_commit(ts_ctx* ctx, const ts_fri_config* cfg, uint32_t n_mats, ts_matrix* const* mats /*consumed*/,
+                              int keep_values, uint32_t root_out[8], ts_multi_key** out);
+ts_status ts_multi_key_info(const ts_multi_key* key, uint32_t idx, uint64_t* height, uint32_t* width);
+ts_status ts_multi_key_values(const ts_multi_key* key, uint32_t idx, const ts_matrix** out /* borrowed */);
+ts_status ts_multi_key_free(ts_ctx* ctx, ts_multi_key* key);
+
+/* ts_prove_multi_bus against a key.  The i-th table with preprocessed_width > 0, in table order, reads key matrix i,
+ * which must have the table's height and the AIR's preprocessed width; the key holds exactly as many matrices as
+ * there are such tables and was committed with cfg's log_blowup.  A table is plain, key-only, aux-only (the bus AIRs
+ * of v7) or key and aux (a fixed table on the bus).  A table's ts_logup_spec may use terms of kind 2: column `value`
+ * of that table's key matrix on the local row; the key must then have been made with keep_values = 1.
+ * Build-defined.  Transcript (v7's, with the key):
+ *   1. observe T and every log_degree;
+ *   2. observe the key root, as ts_prove_pre does first;
+ *   3. ONE commit of all traces; observe the root;
+ *   4. if at least one table has aux columns (A > 0): sample gamma, then beta; the aux matrices
+ *      (ts_logup_aux_build_multi_pre below: what ts_logup_aux_build_pre gives per table); ONE commit of them in table
+ *      order; observe the aux root, then the exposed words in table order.  With A = 0 this step is skipped whole:
+ *      no samples, no aux commitment, no aux root and no exposed words in the proof;
+ *   5. sample alpha;
+ *   6. per table the chunks over the side list (key LDE, aux LDE), each where present, in the order of
+ *      ts_quotient_chunks_pre_aux; the public vector is v7's;
+ *   7. ONE commit of all chunks; observe the root; sample zeta, then the batch challenge;
+ *   8. the rounds in the order of TSPF v5: the key matrices at {zeta, zeta * omega_{n_t}}, the aux matrices at the
+ *      same points if A > 0, the traces at the same points, every chunk at {zeta}.
+ * Proof = TSPF v8: [magic, 8, T], T x [log_degree, width, qd, aux_width, n_exposed, preprocessed_width], trace root,
+ * aux root and exposed words only if A > 0, quotient root, the opened values in ts_pcs_open's (round, matrix, point,
+ * column) order, the FriProof with one BatchOpening per round per query.  The key root is NOT in the proof, as in v3
+ * and v5.  v8 has no postcard form; every other verify call answers a v8 proof with verdict 9 and
+ * ts_verify_multi_key answers any other version with 9.  With T = 1 the words behind the header are those of
+ * ts_prove_pre_aux for a challenger that has observed (1, log_degree).
+ * Refusals, all before any trace is consumed and each with a text in ts_last_error:
+ *   what ts_prove_multi_bus refuses, with the same status, except preprocessed columns and a statement without aux
+ *   tables; TS_ERR_INVALID for a NULL key or a key that no table uses (the text points at ts_prove_multi_bus), a key
+ *   of another context, of another log_blowup, of another matrix count, or with a matrix of another height or width
+ *   than its table's; a kind-2 term on a table without preprocessed columns or outside its key matrix, or against a
+ *   key without kept values.
+ * TS_MULTI_OPEN_GENERIC and TS_MULTI_LOGUP_PER_TABLE apply as in v7 (the per-table builder is
+ * ts_logup_aux_build_pre); the proof is the same.  A height class of the opening may hold 64 key + 64 aux + 64 trace
+ * + 64 chunk matrices: the per-class kernels read their jobs from device memory and have no bound of their own. */
+typedef ts_multi_bus_table ts_multi_key_table;   /* air: any preprocessed_width; logup: kinds 0, 1 and 2 */
+ts_status ts_prove_multi_key(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, const ts_multi_key* key,
+                             ts_multi_key_table* tables, uint32_t n_tables,
+                             uint32_t* proof_out, size_t cap_words, size_t* n_words_out);
+/* host only.  ts_verify_multi_bus extended by the key root observation, the preprocessed opened values in each
+ * table's out-of-domain check, and ts_pcs_verify over three or four rounds with key_root as the first commitment.
+ * Verdict codes as ts_verify.  Reads nothing outside proof[0 .. n_words).  With A = 0 exposed_out may be NULL and
+ * bus_sum is zero. */
+ts_status ts_verify_multi_key(const ts_fri_config* cfg, ts_challenger* chal, const uint32_t key_root[8],
+                              const ts_air* const* airs, uint32_t n_tables,
+                              const uint32_t* const* public_values, const uint32_t* n_public,
+                              const uint32_t* proof, size_t n_words,
+                              uint32_t* exposed_out, uint32_t cap_exposed, uint32_t bus_sum[4], int* verdict);
+/* ts_logup_aux_build_multi whose specs may use terms of kind 2: table k's read preprocessed[k], the row-major values
+ * of its preprocessed columns (the trace's height, this context, not consumed; NULL for a table without such terms).
+ * Every aux word and every S equals ts_logup_aux_build_pre(specs[k], preprocessed[k], traces[k]) word for word; a job
+ * without a table runs the code it runs in ts_logup_aux_build_multi.  Refusals and the zero-denominator report as
+ * there. */
+ts_status ts_logup_aux_build_multi_pre(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs,
+                                       const ts_matrix* const* preprocessed /* n, entries may be NULL */,
+                                       const ts_matrix* const* traces, const uint32_t challenges[8],
+                                       ts_matrix** aux_out /* n */, uint32_t* exposed_out /* 4 n */);
+/* ts_logup_multiplicities_bus whose `table` terms may be of kind 2: a column of table_preprocessed (row-major,
+ * table_trace's height, same context, not consumed; NULL without such terms).  The lookers keep kinds 0 and 1 and
+ * out_column stays a main column of table_trace.  Classes, the lowest row as representative, misses, negate and
+ * TS_LOGUP_HASH_BITS as there; with no kind-2 term and a NULL matrix the column is exactly
+ * ts_logup_multiplicities_bus's. */
+ts_status ts_logup_multiplicities_bus_pre(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec,
+                                          const ts_matrix* table_preprocessed, ts_matrix* table_trace,
+                                          const ts_matrix* const* lookers /* n_lookers */, uint64_t* n_missing,
+                                          uint64_t first_missing[3]);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "ts_prove_batch_lookup",
     "ts_prove_multi", "ts_verify_multi",
     "ts_prove_multi_bus", "ts_verify_multi_bus", "ts_logup_aux_build_multi", "ts_logup_multiplicities_bus",
+    "ts_multi_key_commit", "ts_multi_key_info", "ts_multi_key_values", "ts_multi_key_free",
+    "ts_prove_multi_key", "ts_verify_multi_key", "ts_logup_aux_build_multi_pre", "ts_logup_multiplicities_bus_pre",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -396,6 +398,22 @@ def lib() -> C.CDLL:
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         l.ts_logup_aux_build_multi.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LogupSpecC)),
                                                C.POINTER(C.c_void_p), u32p, C.POINTER(C.c_void_p), u32p]
+        l.ts_multi_key_commit.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.c_uint32, C.POINTER(C.c_void_p), C.c_int,
+                                          u32p, C.POINTER(C.c_void_p)]
+        l.ts_multi_key_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), u32p]
+        l.ts_multi_key_values.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        l.ts_multi_key_free.argtypes = [C.c_void_p, C.c_void_p]
+        l.ts_prove_multi_key.argtypes = [C.c_void_p, C.POINTER(FriConfigC), C.c_void_p, C.c_void_p,
+                                         C.POINTER(MultiBusTableC), C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
+        l.ts_verify_multi_key.argtypes = [C.POINTER(FriConfigC), C.c_void_p, u32p, C.POINTER(C.c_void_p), C.c_uint32,
+                                          C.POINTER(u32p), u32p, u32p, C.c_size_t, u32p, C.c_uint32, u32p,
+                                          C.POINTER(C.c_int)]
+        l.ts_logup_multiplicities_bus_pre.argtypes = [C.c_void_p, C.POINTER(LogupMultBusSpecC), C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_uint64)]
+        l.ts_logup_aux_build_multi_pre.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LogupSpecC)),
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u32p,
+                                                   C.POINTER(C.c_void_p), u32p]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

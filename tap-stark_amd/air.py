@@ -505,8 +505,11 @@ class LogUp:
                                     allow_missing=allow_missing)
 
 
-def logup_build_multi(logups, traces, challenges):
-    """``ts_logup_aux_build_multi``: the aux matrices of ``traces`` (row-major ``DeviceMatrix``, one context, not
+def logup_build_multi(logups, traces, challenges, preprocessed=None):
+    """``preprocessed`` (``ts_logup_aux_build_multi_pre``): one entry per trace, the row-major ``DeviceMatrix`` of that
+    table's preprocessed values (``MultiKey.values(i)``; not consumed) or None; ``("prep", c)`` terms read it.
+
+    ``ts_logup_aux_build_multi``: the aux matrices of ``traces`` (row-major ``DeviceMatrix``, one context, not
     consumed) under ``logups`` (one :class:`LogUp` per trace, terms of kind 0 and 1) for ONE pair of challenges, in
     three launches and one copy back instead of three launches and a host wait per table.  Returns ``(list of
     aux DeviceMatrix, exposed)`` with ``exposed`` of shape (n, 4): per table what ``LogUp.build`` returns."""
@@ -525,8 +528,15 @@ def logup_build_multi(logups, traces, challenges):
         raise ValueError("LogUp takes two challenges (eight words)")
     out = (C.c_void_p * n)()
     exposed = np.zeros((n, 4), dtype=np.uint32)
-    ctx.check(ctx._l.ts_logup_aux_build_multi(ctx.h, n, spec_ptrs, handles, ch.ctypes.data_as(_lib.u32p), out,
-                                              exposed.ctypes.data_as(_lib.u32p)))
+    if preprocessed is not None:
+        if len(preprocessed) != n:
+            raise ValueError("logup_build_multi: one preprocessed matrix (or None) per trace")
+        pre = (C.c_void_p * n)(*[m.h if m is not None else None for m in preprocessed])
+        ctx.check(ctx._l.ts_logup_aux_build_multi_pre(ctx.h, n, spec_ptrs, pre, handles, ch.ctypes.data_as(_lib.u32p),
+                                                      out, exposed.ctypes.data_as(_lib.u32p)))
+    else:
+        ctx.check(ctx._l.ts_logup_aux_build_multi(ctx.h, n, spec_ptrs, handles, ch.ctypes.data_as(_lib.u32p), out,
+                                                  exposed.ctypes.data_as(_lib.u32p)))
     del specs
     return [DeviceMatrix(ctx, C.c_void_p(h)) for h in out], exposed
 
@@ -555,8 +565,13 @@ def mult_bus_spec_c(table, lookers, out_column: int, negate: int = 1):
     return spec, keep
 
 
-def logup_multiplicities_bus(table_trace, table, lookers, out_column: int, negate: int = 1, allow_missing: bool = False):
-    """``ts_logup_multiplicities_bus`` (include/tapstark.h, csrc/logup_mult.hip): the multiplicity column of a table
+def logup_multiplicities_bus(table_trace, table, lookers, out_column: int, negate: int = 1, allow_missing: bool = False,
+                             table_preprocessed=None, pre: bool = False):
+    """``table_preprocessed`` (or ``pre=True`` with None): ``ts_logup_multiplicities_bus_pre``, whose ``table`` terms
+    may be ``("prep", c)``: column c of ``table_preprocessed``, the row-major values of the table's preprocessed
+    columns (``MultiKey.values(i)``; the table trace's height, not consumed).
+
+    ``ts_logup_multiplicities_bus`` (include/tapstark.h, csrc/logup_mult.hip): the multiplicity column of a table
     whose lookups are rows of OTHER traces.  ``table``: the table's tuple, terms over ``table_trace``'s row;
     ``lookers``: a list of ``(trace, lookups, weights)`` with ``trace`` a resident row-major ``DeviceMatrix`` of any
     height (not consumed; it may be ``table_trace``), ``lookups`` one tuple of terms per lookup and ``weights`` one
@@ -568,8 +583,13 @@ def logup_multiplicities_bus(table_trace, table, lookers, out_column: int, negat
     ctx = table_trace.ctx
     handles = (C.c_void_p * max(len(lookers), 1))(*[m.h for m, _, _ in lookers])
     n_missing, first = C.c_uint64(0), (C.c_uint64 * 3)()
-    ctx.check(ctx._l.ts_logup_multiplicities_bus(ctx.h, C.byref(spec), table_trace.h, handles,
-                                                 C.byref(n_missing) if allow_missing else None, first))
+    if table_preprocessed is not None or pre:
+        ctx.check(ctx._l.ts_logup_multiplicities_bus_pre(
+            ctx.h, C.byref(spec), table_preprocessed.h if table_preprocessed is not None else None, table_trace.h,
+            handles, C.byref(n_missing) if allow_missing else None, first))
+    else:
+        ctx.check(ctx._l.ts_logup_multiplicities_bus(ctx.h, C.byref(spec), table_trace.h, handles,
+                                                     C.byref(n_missing) if allow_missing else None, first))
     del keep
     return int(n_missing.value), (tuple(int(x) for x in first) if n_missing.value else None)
 

@@ -892,3 +892,118 @@ def fill_bus_range_multiplicities(range_trace, sender_traces, allow_missing: boo
         lookers.append((m, [[("col", 2 * i)] for i in range(k)], [("col", 2 * i + 1) for i in range(k)]))
     return logup_multiplicities_bus(range_trace, [("col", 0)], lookers, out_column=1, negate=1,
                                     allow_missing=allow_missing)
+
+
+# ---------------------------------------------------------------------------------------------- fixed tables on the bus
+# Tables of a multi-table proof against a commit-once key (prove_multi_key): what a table holds is fixed by the
+# key's preprocessed columns, not by a constraint, so it need not be an arithmetic progression.
+
+
+class BusKeyTableAir(BaseAir):
+    """Preprocessed columns v_0 .. v_{n_values-1} (a matrix of the key), one main column ``mult``: the row receives
+    (tag, v_0, ..., v_{n_values-1}) with multiplicity ``mult`` = MINUS the number of times the senders sent it.  No
+    other constraint: the key fixes the contents.  One LogUp group over one interaction: constraint degree 2, one
+    quotient chunk at every blowup (no padding is needed to fit log_blowup 1)."""
+
+    n_challenges, n_exposed = LogUp.n_challenges, LogUp.n_exposed
+
+    def __init__(self, tag: int = BUS_TAG, n_values: int = 1):
+        self.tag, self.n_values = int(tag), int(n_values)
+        self.preprocessed_width = self.n_values
+        self.logup = LogUp([(("col", 0), [("const", self.tag)] + [("prep", j) for j in range(self.n_values)])])
+        self.aux_width = self.logup.aux_width
+
+    def width(self) -> int:
+        return 1
+
+    def eval(self, builder) -> None:
+        self.logup.eval(builder)
+
+
+class BusTupleSendAir(BaseAir):
+    """Main columns (v_{0,0}, ..., v_{0,n_values-1}, sel_0, ..., v_{k-1,*}, sel_{k-1}): every ``sel_i`` is boolean and
+    row r sends (tag, v_{i,0}, ..., v_{i,n_values-1}) with multiplicity sel_i.  Constraint degree 2 for k = 1 (one
+    quotient chunk) and 3 for k >= 2 (two chunks); both fit log_blowup 1 unpadded."""
+
+    n_challenges, n_exposed = LogUp.n_challenges, LogUp.n_exposed
+
+    def __init__(self, tag: int, k: int = 1, n_values: int = 3):
+        self.tag, self.k, self.n_values = int(tag), int(k), int(n_values)
+        s = self.n_values + 1
+        self.logup = LogUp([(("col", s * i + self.n_values),
+                             [("const", self.tag)] + [("col", s * i + j) for j in range(self.n_values)])
+                            for i in range(self.k)])
+        self.aux_width = self.logup.aux_width
+
+    def width(self) -> int:
+        return self.k * (self.n_values + 1)
+
+    def eval(self, builder) -> None:
+        local = builder.main().row_slice(0)
+        s = self.n_values + 1
+        for i in range(self.k):
+            sel = local[s * i + self.n_values]
+            builder.assert_zero(sel * (sel - 1))
+        self.logup.eval(builder)
+
+
+def generate_range_key(n: int) -> np.ndarray:
+    """(n, 1) canonical u32: the key matrix 0 .. n-1 of a ``BusKeyTableAir(tag, 1)``."""
+    return generate_lookup_table(n)
+
+
+def generate_xor_key(bits: int) -> np.ndarray:
+    """(4^bits, 3) canonical u32: the rows (a, b, a xor b) over ``bits``-bit operands, row a * 2^bits + b."""
+    a, b = np.divmod(np.arange(1 << (2 * bits), dtype=np.uint32), np.uint32(1 << bits))
+    return np.ascontiguousarray(np.stack([a, b, a ^ b], axis=1).astype(np.uint32))
+
+
+def generate_xor_send_trace(n: int, k: int, bits: int, seed: int = SPLITMIX_SEED) -> np.ndarray:
+    """(n, 4k) canonical u32 satisfying ``BusTupleSendAir(tag, k, 3)``: tuples (a, b, a xor b) over ``bits``-bit
+    operands, selectors 0 or 1."""
+    r = splitmix64_stream(seed, 3 * n * k).reshape(n, k, 3).astype(np.uint64)
+    out = np.empty((n, k, 4), dtype=np.uint32)
+    a, b = r[:, :, 0] % np.uint64(1 << bits), r[:, :, 1] % np.uint64(1 << bits)
+    out[:, :, 0], out[:, :, 1], out[:, :, 2] = a, b, a ^ b
+    out[:, :, 3] = (r[:, :, 2] >> np.uint64(17)) & np.uint64(1)
+    return np.ascontiguousarray(out.reshape(n, 4 * k))
+
+
+def generate_key_table_trace(key_values: np.ndarray, sender_tuples) -> np.ndarray:
+    """(n, 1) canonical u32 satisfying a ``BusKeyTableAir``: MINUS the count of every row of ``key_values`` among
+    ``sender_tuples``, an (m, n_values) array of the selected tuples (the first row of a duplicate table entry counts;
+    tuples outside the table are not counted: the bus then does not balance)."""
+    key_values = np.asarray(key_values)
+    n = key_values.shape[0]
+    first = {}
+    for r in range(n):
+        first.setdefault(tuple(int(x) for x in key_values[r]), r)
+    counts = np.zeros(n, dtype=np.int64)
+    for tup in np.asarray(sender_tuples).reshape(-1, key_values.shape[1]):
+        r = first.get(tuple(int(x) for x in tup))
+        if r is not None:
+            counts[r] += 1
+    return ((P - counts % P) % P).astype(np.uint32).reshape(n, 1)
+
+
+def selected_tuples(trace: np.ndarray, n_values: int) -> np.ndarray:
+    """The (m, n_values) tuples a ``BusSendAir`` (n_values = 1) or ``BusTupleSendAir`` trace sends: those whose
+    selector is 1."""
+    t = np.asarray(trace).reshape(trace.shape[0], -1, n_values + 1)
+    return t[:, :, :n_values][t[:, :, n_values] == 1]
+
+
+def fill_bus_key_multiplicities(table_trace, key_values, sender_traces, n_values: int = 1, allow_missing: bool = False):
+    """Fills column 0 of a resident ``BusKeyTableAir`` trace in HBM from the resident sender traces (``BusSendAir`` for
+    n_values = 1, ``BusTupleSendAir`` otherwise; any heights, any k) against ``key_values``, the row-major
+    ``DeviceMatrix`` of the table's key matrix (``MultiKey.values(i)``): what ``generate_key_table_trace`` computes on
+    the host.  Returns what ``logup_multiplicities_bus`` returns."""
+    from .air import logup_multiplicities_bus
+    s = n_values + 1
+    lookers = []
+    for m in sender_traces:
+        k = m.dims()[1] // s
+        lookers.append((m, [[("col", s * i + j) for j in range(n_values)] for i in range(k)],
+                        [("col", s * i + n_values) for i in range(k)]))
+    return logup_multiplicities_bus(table_trace, [("prep", j) for j in range(n_values)], lookers, out_column=0, negate=1,
+                                    allow_missing=allow_missing, table_preprocessed=key_values)

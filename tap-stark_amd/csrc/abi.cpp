@@ -432,6 +432,8 @@ ts_status ts_proof_to_postcard(const uint32_t* proof, size_t n_words, uint8_t* o
                    "TSPF v6 proofs (ts_prove_multi) have no postcard form");
         TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 7), ts::TS_ERR_UNSUPPORTED,
                    "TSPF v7 proofs (ts_prove_multi_bus) have no postcard form");
+        TS_REQUIRE(!(n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] == 8), ts::TS_ERR_UNSUPPORTED,
+                   "TSPF v8 proofs (ts_prove_multi_key) have no postcard form");
         TS_REQUIRE(ts::tspf_to_postcard(proof, n_words, b), ts::TS_ERR_INVALID, "not a TSPF v1 proof");
         *n_bytes_out = b.size();
         TS_REQUIRE(b.size() <= cap_bytes, ts::TS_ERR_BUFFER, "postcard buffer too small");
@@ -1883,8 +1885,10 @@ ts_status ts_logup_multiplicities(ts_ctx* ctx, const ts_logup_mult_spec* spec, c
 }
 
 // The multiplicity column of a table whose lookups are rows of other traces (logup_mult.hip).
-ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec, ts_matrix* table_trace,
-                                      const ts_matrix* const* lookers, uint64_t* n_missing, uint64_t first_missing[3]) {
+namespace {
+ts_status mult_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec, const ts_matrix* table_pre, bool takes_pre,
+                   ts_matrix* table_trace, const ts_matrix* const* lookers, uint64_t* n_missing,
+                   uint64_t first_missing[3]) {
     if (!ctx) return TS_ERR_INVALID;
     if (n_missing) *n_missing = 0;
     if (first_missing) first_missing[0] = first_missing[1] = first_missing[2] = ~0ull;
@@ -1915,7 +1919,7 @@ ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec*
         }
         s.out_column = spec->out_column;
         s.negate = spec->negate;
-        const ts::LogupMultBusResult r = ts::logup_multiplicities_bus(ctx->ctx, s, table_trace->m, mats);
+        const ts::LogupMultBusResult r = ts::logup_multiplicities_bus(ctx->ctx, s, table_trace->m, mats, table_pre ? &table_pre->m : nullptr, takes_pre);
         if (n_missing) *n_missing = r.n_missing;
         if (first_missing) {
             first_missing[0] = r.looker;
@@ -1929,30 +1933,45 @@ ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec*
                                 std::to_string(r.n_missing) + " such lookups)");
     });
 }
+}  // namespace
+
+ts_status ts_logup_multiplicities_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec, ts_matrix* table_trace,
+                                      const ts_matrix* const* lookers, uint64_t* n_missing, uint64_t first_missing[3]) {
+    return mult_bus(ctx, spec, nullptr, false, table_trace, lookers, n_missing, first_missing);
+}
+
+// The same with kind-2 terms on the table's side: columns of the table's preprocessed matrix (the values of a key).
+ts_status ts_logup_multiplicities_bus_pre(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec,
+                                          const ts_matrix* table_preprocessed, ts_matrix* table_trace,
+                                          const ts_matrix* const* lookers, uint64_t* n_missing,
+                                          uint64_t first_missing[3]) {
+    return mult_bus(ctx, spec, table_preprocessed, true, table_trace, lookers, n_missing, first_missing);
+}
 
 // The LogUp columns of n traces for one set of challenges, in three launches (logup.hip logup_aux_build_multi).
-ts_status ts_logup_aux_build_multi(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs,
-                                   const ts_matrix* const* traces, const uint32_t challenges[8], ts_matrix** aux_out,
-                                   uint32_t* exposed_out) {
+namespace {
+ts_status aux_build_multi(ts_ctx* ctx, const std::string& call, uint32_t n, const ts_logup_spec* const* specs,
+                          const ts_matrix* const* preprocessed, bool takes_tables, const ts_matrix* const* traces,
+                          const uint32_t challenges[8], ts_matrix** aux_out, uint32_t* exposed_out) {
     if (!ctx) return TS_ERR_INVALID;
     if (aux_out && n >= 1 && n <= ts::LOGUP_MAX_TABLES)
         for (uint32_t k = 0; k < n; k++) aux_out[k] = nullptr;
     return guard(ctx, [&] {
-        TS_REQUIRE(specs && traces && challenges && aux_out && exposed_out, ts::TS_ERR_INVALID,
-                   "ts_logup_aux_build_multi: null argument");
-        TS_REQUIRE(n >= 1 && n <= ts::LOGUP_MAX_TABLES, ts::TS_ERR_INVALID,
-                   "ts_logup_aux_build_multi: between 1 and 64 tables");
+        TS_REQUIRE(specs && traces && challenges && aux_out && exposed_out && (preprocessed || !takes_tables),
+                   ts::TS_ERR_INVALID, call + ": null argument");
+        TS_REQUIRE(n >= 1 && n <= ts::LOGUP_MAX_TABLES, ts::TS_ERR_INVALID, call + ": between 1 and 64 tables");
         std::vector<ts::LogupSpec> loaded(n);
         std::vector<const ts::LogupSpec*> sp(n);
-        std::vector<const ts::DeviceMatrix*> tr(n);
+        std::vector<const ts::DeviceMatrix*> tr(n), pre(n, nullptr);
         for (uint32_t k = 0; k < n; k++) {
-            TS_REQUIRE(traces[k], ts::TS_ERR_INVALID, "ts_logup_aux_build_multi: null trace");
+            TS_REQUIRE(traces[k], ts::TS_ERR_INVALID, call + ": null trace");
+            if (takes_tables && preprocessed[k]) pre[k] = &preprocessed[k]->m;
             loaded[k] = load_logup_spec(specs[k]);
             sp[k] = &loaded[k];
             tr[k] = &traces[k]->m;
         }
         std::vector<uint32_t> exposed(4 * (size_t)n);
-        std::vector<ts::DeviceMatrix> aux = ts::logup_aux_build_multi(ctx->ctx, sp, tr, challenges, exposed.data());
+        std::vector<ts::DeviceMatrix> aux = ts::logup_aux_build_multi(ctx->ctx, sp, tr, challenges, exposed.data(), nullptr, takes_tables ? &pre : nullptr);
         std::vector<std::unique_ptr<ts_matrix>> handles(n);
         for (uint32_t k = 0; k < n; k++) {
             handles[k] = std::make_unique<ts_matrix>();
@@ -1962,33 +1981,52 @@ ts_status ts_logup_aux_build_multi(ts_ctx* ctx, uint32_t n, const ts_logup_spec*
         memcpy(exposed_out, exposed.data(), exposed.size() * 4);
     });
 }
+}  // namespace
+
+ts_status ts_logup_aux_build_multi(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs,
+                                   const ts_matrix* const* traces, const uint32_t challenges[8], ts_matrix** aux_out,
+                                   uint32_t* exposed_out) {
+    return aux_build_multi(ctx, "ts_logup_aux_build_multi", n, specs, nullptr, false, traces, challenges, aux_out,
+                           exposed_out);
+}
+
+// The same with kind-2 terms: table k's read preprocessed[k], the row-major values of its preprocessed columns.
+ts_status ts_logup_aux_build_multi_pre(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs,
+                                       const ts_matrix* const* preprocessed, const ts_matrix* const* traces,
+                                       const uint32_t challenges[8], ts_matrix** aux_out, uint32_t* exposed_out) {
+    return aux_build_multi(ctx, "ts_logup_aux_build_multi_pre", n, specs, preprocessed, true, traces, challenges, aux_out,
+                           exposed_out);
+}
 
 // ------------------------------------------------------------------ prove_multi_bus
 // ts_prove_multi with LogUp aux columns on a bus across the tables (prove_multi.cpp).  Every refusal is made before
 // the first trace is taken.
-ts_status ts_prove_multi_bus(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_bus_table* tables,
-                             uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+namespace {
+// `key` null: ts_prove_multi_bus; else ts_prove_multi_key (`with_key`: which of the two is running, for a null key)
+ts_status prove_multi_phased(ts_ctx* ctx, const std::string& call, bool with_key, const ts_fri_config* cfg,
+                             ts_challenger* chal, const ts_multi_key* key, ts_multi_bus_table* tables, uint32_t n_tables,
+                             uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
     if (!ctx) return TS_ERR_INVALID;
     if (n_words_out) *n_words_out = 0;
     return guard(ctx, [&] {
         TS_REQUIRE(cfg && chal && tables && proof_out && n_words_out, ts::TS_ERR_INVALID,
-                   "ts_prove_multi_bus: null argument");
+                   call + ": null argument");
         TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
-                   "ts_prove_multi_bus: between 1 and 64 tables");
+                   call + ": between 1 and 64 tables");
         const ts::FriConfig fri = load_cfg(cfg);
         for (uint32_t t = 0; t < n_tables; t++) {
             const ts_multi_bus_table& mt = tables[t];
             TS_REQUIRE(mt.struct_size == sizeof(ts_multi_bus_table), ts::TS_ERR_INVALID,
-                       "ts_prove_multi_bus: ts_multi_bus_table.struct_size is not sizeof(ts_multi_bus_table)");
-            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, "ts_prove_multi_bus: null AIR or trace");
+                       call + ": ts_multi_bus_table.struct_size is not sizeof(ts_multi_bus_table)");
+            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, call + ": null AIR or trace");
             TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
-                       "ts_prove_multi_bus: an AIR was compiled on another context (or host-only)");
+                       call + ": an AIR was compiled on another context (or host-only)");
             TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
             TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
-                       "ts_prove_multi_bus: a trace was made on another context");
+                       call + ": a trace was made on another context");
             for (uint32_t k = 0; k < t; k++)
                 TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID,
-                           "ts_prove_multi_bus: one trace handle in two tables");
+                           call + ": one trace handle in two tables");
         }
         // the statement's own refusals on shapes alone: the matrices stay with their handles until all of it holds
         std::vector<ts::MultiBusTable> mts(n_tables);
@@ -2004,13 +2042,140 @@ ts_status ts_prove_multi_bus(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenge
                 mts[t].logup = &specs[t];
             }
         }
-        ts::check_multi_bus_statement(fri, mts);
+        if (with_key) {
+            TS_REQUIRE(!key || key->k.ctx == &ctx->ctx, ts::TS_ERR_INVALID, call + ": the key was made on another context");
+            ts::check_multi_key_statement(fri, mts, key ? &key->k : nullptr);
+        } else {
+            ts::check_multi_bus_statement(fri, mts);
+        }
         ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
         for (uint32_t t = 0; t < n_tables; t++) mts[t].trace = take_trace(tables[t].trace);
         ts::StageTimer timer(&ctx->ctx, "prove");
-        copy_proof(ts::prove_multi_bus(pcs, chal->c, mts), proof_out, cap_words, n_words_out);
+        copy_proof(with_key ? ts::prove_multi_key(pcs, chal->c, mts, key->k) : ts::prove_multi_bus(pcs, chal->c, mts),
+                   proof_out, cap_words, n_words_out);
     });
 }
+}  // namespace
+
+ts_status ts_prove_multi_bus(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_bus_table* tables,
+                             uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    return prove_multi_phased(ctx, "ts_prove_multi_bus", false, cfg, chal, nullptr, tables, n_tables, proof_out, cap_words,
+                              n_words_out);
+}
+
+// ------------------------------------------------------------------ the key of a multi-table proof
+// ts_pcs_commit of the matrices on their natural domains; with keep_values the row-major inputs stay alive as handles
+// of the key (TwoAdicFriPcs::commit's keep_row_major: no second copy).
+ts_status ts_multi_key_commit(ts_ctx* ctx, const ts_fri_config* cfg, uint32_t n_mats, ts_matrix* const* mats,
+                              int keep_values, uint32_t root_out[8], ts_multi_key** out) {
+    if (!ctx) return TS_ERR_INVALID;
+    if (out) *out = nullptr;
+    return guard(ctx, [&] {
+        TS_REQUIRE(cfg && mats && out, ts::TS_ERR_INVALID, "ts_multi_key_commit: null argument");
+        TS_REQUIRE(n_mats >= 1 && n_mats <= (uint32_t)ts::MAX_BATCH_MATS, ts::TS_ERR_INVALID,
+                   "ts_multi_key_commit: between 1 and 64 matrices");
+        const ts::FriConfig fri = load_cfg(cfg);
+        for (uint32_t i = 0; i < n_mats; i++) {
+            TS_REQUIRE(mats[i] && mats[i]->m.buf.p, ts::TS_ERR_INVALID, "ts_multi_key_commit: null or consumed matrix");
+            TS_REQUIRE(mats[i]->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
+                       "ts_multi_key_commit: a matrix was made on another context");
+            TS_REQUIRE(!keep_values || mats[i]->m.layout == ts::DeviceMatrix::ROW_MAJOR, ts::TS_ERR_INVALID,
+                       "ts_multi_key_commit: keep_values needs row-major (uploaded) matrices");
+            ts::log2_strict(mats[i]->m.height);
+            for (uint32_t k = 0; k < i; k++)
+                TS_REQUIRE(mats[k] != mats[i], ts::TS_ERR_INVALID, "ts_multi_key_commit: one matrix handle twice");
+        }
+        auto key = std::make_unique<ts_multi_key>();
+        key->k.ctx = &ctx->ctx;
+        key->k.log_blowup = fri.log_blowup;
+        std::vector<ts::DeviceMatrix> ms;
+        for (uint32_t i = 0; i < n_mats; i++) {
+            key->k.heights.push_back(mats[i]->m.height);
+            key->k.widths.push_back(mats[i]->m.width);
+            ms.push_back(std::move(mats[i]->m));
+        }
+        ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
+        key->k.data = pcs.commit(ms, std::vector<uint32_t>(n_mats, 1u), true, /*keep_row_major=*/keep_values != 0);
+        for (uint32_t i = 0; i < n_mats; i++) {
+            if (keep_values) {
+                key->values.push_back(std::make_unique<ts_matrix>());
+                key->values.back()->m = std::move(ms[i]);
+                key->k.values.push_back(&key->values.back()->m);
+            } else {
+                key->k.values.push_back(nullptr);
+            }
+        }
+        if (root_out) memcpy(root_out, key->k.data->root, 32);
+        *out = key.release();
+    });
+}
+ts_status ts_multi_key_info(const ts_multi_key* key, uint32_t idx, uint64_t* height, uint32_t* width) {
+    if (!key || idx >= key->k.heights.size()) return TS_ERR_INVALID;
+    if (height) *height = key->k.heights[idx];
+    if (width) *width = key->k.widths[idx];
+    return TS_OK;
+}
+ts_status ts_multi_key_values(const ts_multi_key* key, uint32_t idx, const ts_matrix** out) {
+    if (out) *out = nullptr;
+    if (!key || !out || idx >= key->k.values.size() || !key->k.values[idx]) return TS_ERR_INVALID;
+    *out = key->values[idx].get();
+    return TS_OK;
+}
+ts_status ts_multi_key_free(ts_ctx* ctx, ts_multi_key* key) {
+    if (!key) return TS_OK;
+    if (!ctx || key->k.ctx != &ctx->ctx) return TS_ERR_INVALID;
+    return guard(ctx, [&] { delete key; });
+}
+
+// ts_prove_multi_bus against a key: tables with preprocessed columns read the key's matrices in order (TSPF v8).
+ts_status ts_prove_multi_key(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, const ts_multi_key* key,
+                             ts_multi_key_table* tables, uint32_t n_tables, uint32_t* proof_out, size_t cap_words,
+                             size_t* n_words_out) {
+    return prove_multi_phased(ctx, "ts_prove_multi_key", true, cfg, chal, key, tables, n_tables, proof_out, cap_words,
+                              n_words_out);
+}
+
+ts_status ts_verify_multi_key(const ts_fri_config* cfg, ts_challenger* chal, const uint32_t key_root[8],
+                              const ts_air* const* airs, uint32_t n_tables, const uint32_t* const* public_values,
+                              const uint32_t* n_public, const uint32_t* proof, size_t n_words, uint32_t* exposed_out,
+                              uint32_t cap_exposed, uint32_t bus_sum[4], int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(cfg && chal && key_root && airs && public_values && n_public && proof && bus_sum && verdict,
+                   ts::TS_ERR_INVALID, "ts_verify_multi_key: null argument");
+        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+                   "ts_verify_multi_key: between 1 and 64 tables");
+        const ts::FriConfig fri = load_cfg(cfg);
+        std::vector<const ts::AirProgram*> progs(n_tables);
+        std::vector<std::vector<uint32_t>> pis(n_tables);
+        uint32_t n_aux = 0, n_pre = 0;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, "ts_verify_multi_key: null AIR");
+            const ts::AirProgram& p = airs[t]->a.prog();
+            TS_REQUIRE(p.aux_width ? p.n_challenges == 2 && p.n_exposed == 4 : !p.n_challenges && !p.n_exposed,
+                       ts::TS_ERR_INVALID,
+                       "ts_verify_multi_key: an AIR on the bus has aux columns, 2 challenges and 4 exposed words, any "
+                       "other none of them");
+            n_aux += p.aux_width ? 1 : 0;
+            n_pre += p.preprocessed_width ? 1 : 0;
+            progs[t] = &p;
+            pis[t] = public_inputs(public_values[t], n_public[t]);
+        }
+        TS_REQUIRE(n_pre > 0, ts::TS_ERR_INVALID,
+                   "ts_verify_multi_key: no table has preprocessed columns; ts_verify_multi_bus (TSPF v7) and "
+                   "ts_verify_multi (TSPF v6) verify tables without a key");
+        TS_REQUIRE(n_aux == 0 || (exposed_out && cap_exposed >= 4 * n_aux), ts::TS_ERR_INVALID,
+                   "ts_verify_multi_key: null or short buffer for the exposed words (4 per table with aux columns)");
+        std::vector<uint32_t> exposed;
+        uint32_t sum[4] = {0, 0, 0, 0};
+        *verdict = ts::verify_multi_key(fri, chal->c, key_root, progs, pis, proof, n_words, exposed, sum);
+        if (*verdict == 0) {
+            if (!exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
+            memcpy(bus_sum, sum, 16);
+        }
+    }, false);
+}
+
 
 ts_status ts_verify_multi_bus(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
                               const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,

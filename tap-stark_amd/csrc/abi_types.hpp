@@ -7,6 +7,7 @@
 #include "../../include/tapstark.h"
 #include "air_spec.hpp"
 #include "host.hpp"
+#include "logup.hpp"
 
 struct ts_ctx {
     ts::Context ctx;
@@ -20,4 +21,10 @@ struct ts_matrix {
 };
 struct ts_pcs_data {
     std::unique_ptr<ts::PcsData> d;
+};
+// the key of a multi-table proof: the committed batch and, with keep_values, the row-major inputs as handles the
+// caller may borrow (ts_multi_key_values)
+struct ts_multi_key {
+    ts::MultiKey k;
+    std::vector<std::unique_ptr<ts_matrix>> values;
 };

@@ -225,6 +225,12 @@ int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vect
 int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
                      const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words,
                      std::vector<uint32_t>& exposed, uint32_t bus_sum[4]);
+// The same for a TSPF v8 proof (prove_multi_key, logup.hpp): tables of any kind, at least one with preprocessed
+// columns, against the root of the key that holds those columns.  Without any aux table `exposed` is empty and
+// bus_sum zero.
+int verify_multi_key(const FriConfig& fri, BfChallenger& challenger, const uint32_t key_root[8],
+                     const std::vector<const AirProgram*>& airs, const std::vector<std::vector<uint32_t>>& public_values,
+                     const uint32_t* proof, size_t n_words, std::vector<uint32_t>& exposed, uint32_t bus_sum[4]);
 
 // ------------------------------------------------------------------ prove, one proof over G GPUs
 // Collectives the sharded prover needs, supplied by the host (torch.distributed over RCCL in

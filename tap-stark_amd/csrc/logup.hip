@@ -238,6 +238,8 @@ struct LogupJob {
     uint32_t first_block, n_blocks;  // its workgroups in the rows and scan launches = its stretch of `totals`
     uint32_t index;                  // the table's number: the high word of a zero-denominator report, its S slot
     uint32_t pad;
+    LogupGlobalConstWords table;     // the row-major values of its preprocessed columns (kind-2 terms), or null
+    uint64_t pad2;
 };
 
 __device__ __forceinline__ uint32_t logup_job_of_block(const uint32_t* __restrict__ first, uint32_t n_jobs) {
@@ -250,12 +252,24 @@ __device__ __forceinline__ uint32_t logup_job_of_block(const uint32_t* __restric
     return lo;
 }
 
+// TABLES = false is the kernel of logup_aux_build_multi, unchanged.  TABLES = true is launched only when some job
+// has a table (logup_aux_build_multi_pre): a job with one runs logup_rows_block<true>, a job without keeps the
+// <false> body; the choice depends on the job alone, so it is the same in every lane of the workgroup.  A second
+// instantiation rather than one kernel with the branch: with the branch the kernel takes the 66 VGPRs and occupancy
+// 7 of the table body (k_logup_rows<true> has the same), and every bus proof without a key would run at them
+// instead of 64 and 8 (profiles/multi_key_kernel_resources.txt).  Neither form uses scratch.
+template <bool TABLES>
 __global__ void __launch_bounds__(LOGUP_THREADS)
 k_logup_rows_jobs(const LogupJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs,
                   uint32_t block_rows, uint32_t rpt, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
     const LogupJob& j = jobs[logup_job_of_block(first, n_jobs)];
-    logup_rows_block<false>(j.s, (const uint32_t*)j.trace, nullptr, j.n, block_rows, rpt, blockIdx.x - j.first_block, (uint32_t*)j.aux,
-                            totals + j.first_block, flag, (unsigned long long)j.index << 32);
+    if (TABLES && j.table)
+        logup_rows_block<true>(j.s, (const uint32_t*)j.trace, (const uint32_t*)j.table, j.n, block_rows, rpt,
+                               blockIdx.x - j.first_block, (uint32_t*)j.aux, totals + j.first_block, flag,
+                               (unsigned long long)j.index << 32);
+    else
+        logup_rows_block<false>(j.s, (const uint32_t*)j.trace, nullptr, j.n, block_rows, rpt, blockIdx.x - j.first_block, (uint32_t*)j.aux,
+                                totals + j.first_block, flag, (unsigned long long)j.index << 32);
 }
 
 // one workgroup per table: the scan never crosses into another table's totals
@@ -393,11 +407,13 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
 std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<const LogupSpec*>& specs,
                                                 const std::vector<const DeviceMatrix*>& traces,
                                                 const uint32_t challenges[8], uint32_t* exposed,
-                                                const uint32_t* table_ids) {
+                                                const uint32_t* table_ids,
+                                                const std::vector<const DeviceMatrix*>* tables) {
     StageTimer t(&ctx, "logup aux build");
     const size_t T = specs.size();
-    TS_REQUIRE(T >= 1 && T <= LOGUP_MAX_TABLES && traces.size() == T, TS_ERR_INVALID,
+    TS_REQUIRE(T >= 1 && T <= LOGUP_MAX_TABLES && traces.size() == T && (!tables || tables->size() == T), TS_ERR_INVALID,
                "logup: between 1 and 64 tables, one trace per spec");
+    bool any_table = false;
     const uint32_t block_rows = logup_block_rows();
     const uint32_t rpt = (block_rows + LOGUP_THREADS - 1) / LOGUP_THREADS;
     // every refusal first: nothing is allocated before the last table passed
@@ -408,7 +424,10 @@ std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<
         TS_REQUIRE(specs[k] && traces[k], TS_ERR_INVALID, "logup: null spec or trace");
         LogupJob& j = jobs[k];
         memset((void*)&j, 0, sizeof j);
-        j.s = logup_dev(ctx, *specs[k], *traces[k], challenges, nullptr, false);
+        const DeviceMatrix* table = tables ? (*tables)[k] : nullptr;
+        j.s = logup_dev(ctx, *specs[k], *traces[k], challenges, table, /*takes_table=*/tables != nullptr);
+        j.table = table ? (LogupGlobalConstWords)table->buf.p : nullptr;
+        any_table = any_table || table;
         j.n = traces[k]->height;
         j.trace = (LogupGlobalConstWords)traces[k]->buf.p;
         j.index = (uint32_t)k;
@@ -440,8 +459,12 @@ std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<
     DevBuf<Ef> back(&ctx, 1 + T);
     TS_HIP(hipMemsetAsync(back.p, 0xff, (1 + T) * sizeof(Ef), ctx.stream));
     unsigned long long* flag = reinterpret_cast<unsigned long long*>(back.p);
-    TS_LAUNCH(ctx, k_logup_rows_jobs, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0, d_jobs, d_first, (uint32_t)T,
-              block_rows, rpt, totals.p, flag);
+    if (any_table)
+        TS_LAUNCH_NAMED(ctx, "k_logup_rows_jobs_pre", k_logup_rows_jobs<true>, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0,
+                        d_jobs, d_first, (uint32_t)T, block_rows, rpt, totals.p, flag);
+    else
+        TS_LAUNCH_NAMED(ctx, "k_logup_rows_jobs", k_logup_rows_jobs<false>, dim3((unsigned)n_blocks), dim3(LOGUP_THREADS), 0,
+                        d_jobs, d_first, (uint32_t)T, block_rows, rpt, totals.p, flag);
     TS_HIP(hipGetLastError());
     TS_LAUNCH(ctx, k_logup_totals_jobs, dim3((unsigned)T), dim3(LOGUP_SCAN_THREADS), 0, d_jobs, totals.p);
     TS_HIP(hipGetLastError());

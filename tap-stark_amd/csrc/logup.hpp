@@ -1,5 +1,6 @@
 // LogUp aux columns (logup.hip): the spec as the C ABI hands it over, and the builder.
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "prover_internal.hpp"
@@ -41,11 +42,15 @@ DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMa
 // 1 only.  Throws what the single call throws, before anything is allocated, and TS_ERR_INVARIANT naming the least
 // (table, row, interaction) whose denominator is zero (table k is called table_ids[k] there, if given);
 // synchronises the stream once.
+// `tables` (logup_aux_build_multi_pre): one entry per spec, the row-major values of that table's preprocessed columns
+// or null; terms of kind 2 are then allowed and read it, as logup_aux_build with takes_table does.  A job without a
+// table runs the body it runs without `tables`.
 constexpr uint32_t LOGUP_MAX_TABLES = 64;
 std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<const LogupSpec*>& specs,
                                                 const std::vector<const DeviceMatrix*>& traces,
                                                 const uint32_t challenges[8], uint32_t* exposed,
-                                                const uint32_t* table_ids = nullptr);
+                                                const uint32_t* table_ids = nullptr,
+                                                const std::vector<const DeviceMatrix*>* tables = nullptr);
 
 // ---- several tables in one proof, tied by a LogUp bus (prove_multi.cpp; TSPF v7)
 struct MultiBusTable {
@@ -61,6 +66,29 @@ void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusT
 // Throws TS_ERR_INVARIANT naming (table, row, interaction) of a zero denominator; the traces
 // are consumed by then.
 std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables);
+
+// ---- the same against a commit-once key: fixed tables on the bus (prove_multi.cpp; TSPF v8)
+// One committed batch of preprocessed matrices of mixed heights, on their natural domains; made once, consumed by
+// no proof.  `values[i]`: the row-major input of matrix i, kept alive by the commit (no second copy) and owned by
+// whoever made the key, where it was made with keep_values; null otherwise.
+struct MultiKey {
+    std::unique_ptr<PcsData> data;
+    std::vector<const DeviceMatrix*> values;
+    std::vector<uint64_t> heights;  // natural heights
+    std::vector<uint32_t> widths;
+    unsigned log_blowup = 0;
+    Context* ctx = nullptr;
+};
+// The i-th table with preprocessed columns, in table order, reads key matrix i.  A table is plain, key-only,
+// aux-only or both; a spec's kind-2 terms read the table's key matrix (the key then needs kept values).  Throws what
+// check_multi_bus_statement throws except for preprocessed columns and for a statement without an aux table, and
+// TS_ERR_INVALID for a null key, a key no table uses and a key whose count, heights, widths or blowup do not fit; on
+// shapes alone, nothing is consumed.
+void check_multi_key_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables, const MultiKey* key);
+// prove_multi_bus with the key's root observed after the shapes, the key matrices as the first side matrix of their
+// tables' quotients and as the first opened round; without any aux table the challenge phase is skipped whole.
+std::vector<uint32_t> prove_multi_key(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables,
+                                      const MultiKey& key);
 // TS_MULTI_LOGUP_PER_TABLE=1 (read on every call; a test and measurement knob): prove_multi_bus loops
 // logup_aux_build per table instead of logup_aux_build_multi.  Same proof.
 bool multi_logup_per_table();
@@ -108,8 +136,12 @@ struct LogupMultBusResult {
 // k_mult_insert launch over the table, one count launch per looker, one k_mult_write launch, one copy back.
 // Throws TS_ERR_INVALID before any device work, as the single-trace call does per matrix; out_column may be read
 // by no term over the table trace.
+// takes_pre (logup_multiplicities_bus_pre): the TABLE's terms may be of kind 2 and read `table_pre`, the row-major
+// values of the table's preprocessed columns (the table trace's height, this context, not consumed; may be null
+// without such terms); the lookers keep kinds 0 and 1.
 LogupMultBusResult logup_multiplicities_bus(Context& ctx, const LogupMultBusSpec& spec, DeviceMatrix& trace,
-                                            const std::vector<const DeviceMatrix*>& lookers);
+                                            const std::vector<const DeviceMatrix*>& lookers,
+                                            const DeviceMatrix* table_pre = nullptr, bool takes_pre = false);
 
 // ---- a lookup proof inside a batch lane (prover.cpp): no launch of its own
 // What a lookup argument says about an item's DATA, raised after the kernels finished normally: a zero denominator

@@ -176,7 +176,8 @@ k_mult_count(const MultDev s, const uint32_t* __restrict__ trace, const uint32_t
 
 // ---- the lookups live in OTHER traces (logup_multiplicities_bus): one launch per looker.  k_mult_count with the
 // looker's rows and terms apart from the table's: the lookup tuple and its weight are read from the looker's row,
-// the probe compares against the TABLE's rows (`s`, `table`).  A miss is keyed (looker, row, lookup).
+// the probe compares against the TABLE's rows (`s`, `table`, and `pre` for its kind-2 terms: the table trace again
+// where there are none).  A miss is keyed (looker, row, lookup).
 struct MultLookerDev {
     uint32_t n_lookups, width, index, pad;
     uint32_t w_kind[LOGUP_MULT_MAX_LOOKUPS], w_val[LOGUP_MULT_MAX_LOOKUPS];
@@ -185,7 +186,7 @@ struct MultLookerDev {
 
 __global__ void __launch_bounds__(MULT_THREADS)
 k_mult_count_bus(const MultDev s, const MultLookerDev k, const uint32_t* __restrict__ table,
-                 const uint32_t* __restrict__ looker, uint64_t n_looker, const uint32_t* __restrict__ slots,
+                 const uint32_t* __restrict__ pre, const uint32_t* __restrict__ looker, uint64_t n_looker, const uint32_t* __restrict__ slots,
                  unsigned long long* __restrict__ sums, MultBack* __restrict__ back) {
     const uint64_t r = (uint64_t)blockIdx.x * MULT_THREADS + threadIdx.x;
     const bool live = r < n_looker;  // (no early return: the dead lanes of a short looker take part in the ballots)
@@ -200,7 +201,7 @@ k_mult_count_bus(const MultDev s, const MultLookerDev k, const uint32_t* __restr
 #pragma unroll
             for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++)
                 mine.v[q] = q < (int)s.n_values ? mult_term(k.l_kind[l][q], k.l_val[l][q], row, row) : 0;
-            rep = mult_probe(s, table, table, slots, mine);
+            rep = mult_probe(s, table, pre, slots, mine);
             if (rep == MULT_EMPTY) {
                 atomicAdd(&back->n_missing, 1ull);
                 atomicMin(&back->first_missing,
@@ -308,7 +309,8 @@ LogupMultResult logup_multiplicities(Context& ctx, const LogupMultSpec& spec, De
 
 // ------------------------------------------------------------------ the table in one trace, the lookups in others
 LogupMultBusResult logup_multiplicities_bus(Context& ctx, const LogupMultBusSpec& spec, DeviceMatrix& trace,
-                                            const std::vector<const DeviceMatrix*>& lookers) {
+                                            const std::vector<const DeviceMatrix*>& lookers, const DeviceMatrix* table_pre,
+                                            bool takes_pre) {
     StageTimer timer(&ctx, "logup multiplicities");
     MultDev s;
     memset(&s, 0, sizeof s);
@@ -326,17 +328,30 @@ LogupMultBusResult logup_multiplicities_bus(Context& ctx, const LogupMultBusSpec
     matrix(&trace, "the table trace");
     TS_REQUIRE(spec.out_column < trace.width, TS_ERR_INVALID, "logup multiplicities: out_column outside the trace");
     s.width = trace.width;
-    // a term over matrix `m`; the table trace's out_column is read by no term of any side
-    auto term = [&](const LogupTerm& tm, const DeviceMatrix& m, uint32_t& kind, uint32_t& val) {
-        TS_REQUIRE(tm.kind <= 1, TS_ERR_INVALID, "logup multiplicities: term kind must be 0 (constant) or 1 (column)");
-        TS_REQUIRE(tm.kind ? tm.value < m.width : tm.value < P, TS_ERR_INVALID,
+    if (table_pre) {
+        TS_REQUIRE(takes_pre, TS_ERR_INVALID, "logup multiplicities: this call takes no preprocessed table");
+        matrix(table_pre, "the preprocessed table");
+        TS_REQUIRE(table_pre->height == trace.height, TS_ERR_INVALID,
+                   "logup multiplicities: the preprocessed table must have the table trace's height");
+        s.table_width = table_pre->width;
+    }
+    // a term over matrix `m`; the table trace's out_column is read by no term of any side.  Kind 2 (the table's
+    // terms of logup_multiplicities_bus_pre only) reads the preprocessed table.
+    auto term = [&](const LogupTerm& tm, const DeviceMatrix& m, uint32_t& kind, uint32_t& val, bool table_side = false) {
+        const bool pre_ok = takes_pre && table_side;
+        TS_REQUIRE(tm.kind <= (pre_ok ? 2u : 1u), TS_ERR_INVALID,
+                   pre_ok ? "logup multiplicities: term kind must be 0 (constant), 1 (column) or 2 (preprocessed column)"
+                          : "logup multiplicities: term kind must be 0 (constant) or 1 (column)");
+        TS_REQUIRE(tm.kind != 2 || table_pre, TS_ERR_INVALID,
+                   "logup multiplicities: a preprocessed-column term without a preprocessed table");
+        TS_REQUIRE(tm.kind == 2 ? tm.value < s.table_width : tm.kind ? tm.value < m.width : tm.value < P, TS_ERR_INVALID,
                    "logup multiplicities: a column outside its trace, or a non-canonical constant");
         TS_REQUIRE(tm.kind != 1 || m.buf.p != trace.buf.p || tm.value != spec.out_column, TS_ERR_INVALID,
                    "logup multiplicities: out_column is among the table-trace columns the spec reads");
         kind = tm.kind;
         val = tm.value;
     };
-    for (size_t q = 0; q < nv; q++) term(spec.table[q], trace, s.t_kind[q], s.t_val[q]);
+    for (size_t q = 0; q < nv; q++) term(spec.table[q], trace, s.t_kind[q], s.t_val[q], true);
     std::vector<MultLookerDev> lk(nk);
     for (size_t k = 0; k < nk; k++) {
         const LogupMultLooker& in = spec.lookers[k];
@@ -372,13 +387,13 @@ LogupMultBusResult logup_multiplicities_bus(Context& ctx, const LogupMultBusSpec
     TS_HIP(hipMemsetAsync(back.p, 0, sizeof(MultBack), ctx.stream));
     TS_HIP(hipMemsetAsync(&back.p->first_missing, 0xff, sizeof(unsigned long long), ctx.stream));
     const dim3 grid((unsigned)((n + MULT_THREADS - 1) / MULT_THREADS)), block(MULT_THREADS);
-    TS_LAUNCH(ctx, k_mult_insert, grid, block, 0, s, (const uint32_t*)trace.buf.p, (const uint32_t*)trace.buf.p, n,
-              slots.p, back.p);
+    const uint32_t* pre = table_pre ? table_pre->buf.p : trace.buf.p;  // (no kind-2 term gets here without a table)
+    TS_LAUNCH(ctx, k_mult_insert, grid, block, 0, s, (const uint32_t*)trace.buf.p, pre, n, slots.p, back.p);
     TS_HIP(hipGetLastError());
     for (size_t k = 0; k < nk; k++) {
         const uint64_t nr = lookers[k]->height;
         TS_LAUNCH(ctx, k_mult_count_bus, dim3((unsigned)((nr + MULT_THREADS - 1) / MULT_THREADS)), block, 0, s, lk[k],
-                  (const uint32_t*)trace.buf.p, (const uint32_t*)lookers[k]->buf.p, nr, (const uint32_t*)slots.p, sums.p,
+                  (const uint32_t*)trace.buf.p, pre, (const uint32_t*)lookers[k]->buf.p, nr, (const uint32_t*)slots.p, sums.p,
                   back.p);
         TS_HIP(hipGetLastError());
     }

@@ -16,6 +16,12 @@
 // exposed sums (four words per aux table) are observed before alpha.  A table's quotient reads (aux LDE, trace LDE)
 // and the public vector pis ++ gamma ++ beta ++ its exposed words.  The opening has three rounds, in the order of
 // TSPF v4: aux matrices and traces at {zeta, zeta omega_{n_t}}, chunks at {zeta}.
+//
+// prove_multi_key: prove_multi_bus against a commit-once key of preprocessed matrices (MultiKey, logup.hpp; TSPF v8),
+// the same body (prove_multi_phased).  The key's root is observed after the shapes and is not in the proof; the i-th
+// table with preprocessed columns reads key matrix i: its LDE is the first side matrix of that table's quotient
+// and the key is the first opened round, in the order of TSPF v5.  A LogUp spec may read the key's kept values
+// (kind-2 terms).  Without any table with aux columns the challenge phase is skipped whole: three rounds.
 #include <stdlib.h>
 #include <string.h>
 
@@ -290,6 +296,36 @@ bool multi_logup_per_table() {
     return e && *e && atoi(e) != 0;
 }
 
+// the checks of one table's challenge phase (`w` leads the texts); `pre_width`: the width of the key matrix its
+// kind-2 terms read, 0 where they are refused
+static void check_bus_table(const MultiBusTable& t, const std::string& w, uint32_t pre_width) {
+    const uint32_t aw = t.air->aux_width;
+    if (aw) {
+        TS_REQUIRE(t.air->n_challenges == 2 && t.air->n_exposed == 4, TS_ERR_INVALID,
+                   w + ": an AIR on the bus has 2 challenges (gamma, beta) and 4 exposed words (its sum)");
+        TS_REQUIRE(t.logup, TS_ERR_INVALID, w + ": the AIR has aux columns and no logup spec");
+        // (without a key matrix a kind-2 term is refused here: there is no preprocessed table to read)
+        TS_REQUIRE(logup_aux_width(*t.logup, pre_width ? 2 : 1) == aw, TS_ERR_INVALID,
+                   w + ": the logup spec's aux width is not the AIR's");
+        for (const LogupInteraction& it : t.logup->interactions) {
+            std::vector<LogupTerm> terms = it.values;
+            terms.push_back(it.multiplicity);
+            for (const LogupTerm& tm : terms)
+                TS_REQUIRE(tm.kind == 2 ? tm.value < pre_width : tm.kind ? tm.value < t.trace.width : tm.value < P,
+                           TS_ERR_INVALID,
+                           w + (pre_width ? ": the logup spec reads a column outside the trace or the key matrix, or has a "
+                                            "non-canonical constant"
+                                          : ": the logup spec reads a column outside the trace, or has a non-canonical constant"));
+        }
+        TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
+                   w + ": the trace of a table with aux columns must be row-major (the LogUp builder reads its rows)");
+    } else {
+        TS_REQUIRE(t.air->n_challenges == 0 && t.air->n_exposed == 0, TS_ERR_INVALID,
+                   w + ": challenges or exposed words without aux columns");
+        TS_REQUIRE(!t.logup, TS_ERR_INVALID, w + ": a logup spec for an AIR without aux columns");
+    }
+}
+
 void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables) {
     TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
                "prove_multi_bus: between 1 and 64 tables");
@@ -300,29 +336,8 @@ void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusT
         TS_REQUIRE(t.air, TS_ERR_INVALID, w + ": null AIR");
         TS_REQUIRE(t.air->preprocessed_width == 0, TS_ERR_UNSUPPORTED,
                    w + ": the AIR has preprocessed columns; a multi-table proof has no key round");
-        const uint32_t aw = t.air->aux_width;
-        if (aw) {
-            TS_REQUIRE(t.air->n_challenges == 2 && t.air->n_exposed == 4, TS_ERR_INVALID,
-                       w + ": an AIR on the bus has 2 challenges (gamma, beta) and 4 exposed words (its sum)");
-            TS_REQUIRE(t.logup, TS_ERR_INVALID, w + ": the AIR has aux columns and no logup spec");
-            // (a kind-2 term is refused here: there is no preprocessed table to read)
-            TS_REQUIRE(logup_aux_width(*t.logup, 1) == aw, TS_ERR_INVALID,
-                       w + ": the logup spec's aux width is not the AIR's");
-            for (const LogupInteraction& it : t.logup->interactions) {
-                std::vector<LogupTerm> terms = it.values;
-                terms.push_back(it.multiplicity);
-                for (const LogupTerm& tm : terms)
-                    TS_REQUIRE(tm.kind ? tm.value < t.trace.width : tm.value < P, TS_ERR_INVALID,
-                               w + ": the logup spec reads a column outside the trace, or has a non-canonical constant");
-            }
-            TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
-                       w + ": the trace of a table with aux columns must be row-major (the LogUp builder reads its rows)");
-            n_aux++;
-        } else {
-            TS_REQUIRE(t.air->n_challenges == 0 && t.air->n_exposed == 0, TS_ERR_INVALID,
-                       w + ": challenges or exposed words without aux columns");
-            TS_REQUIRE(!t.logup, TS_ERR_INVALID, w + ": a logup spec for an AIR without aux columns");
-        }
+        check_bus_table(t, w, 0);
+        n_aux += t.air->aux_width ? 1 : 0;
         n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
     }
     TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
@@ -331,8 +346,52 @@ void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusT
                "prove_multi_bus: no table has aux columns; plain tables are proved by ts_prove_multi (TSPF v6)");
 }
 
-std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables) {
-    check_multi_bus_statement(pcs.fri(), tables);
+void check_multi_key_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables, const MultiKey* key) {
+    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
+               "prove_multi_key: between 1 and 64 tables");
+    uint32_t n_chunks = 0;
+    size_t n_pre = 0;
+    for (const MultiBusTable& t : tables) {
+        TS_REQUIRE(t.air, TS_ERR_INVALID, "prove_multi_key: null AIR");
+        n_pre += t.air->preprocessed_width ? 1 : 0;
+    }
+    TS_REQUIRE(key && key->data && n_pre > 0, TS_ERR_INVALID,
+               "prove_multi_key: a null key, or no table has preprocessed columns; tables without a key are proved by "
+               "ts_prove_multi_bus (TSPF v7) or ts_prove_multi (TSPF v6)");
+    TS_REQUIRE(key->heights.size() == n_pre, TS_ERR_INVALID,
+               "prove_multi_key: the key holds " + std::to_string(key->heights.size()) + " matrices and " +
+                   std::to_string(n_pre) + " tables have preprocessed columns");
+    TS_REQUIRE(key->log_blowup == fri.log_blowup, TS_ERR_INVALID,
+               "prove_multi_key: the key was committed with another log_blowup");
+    size_t ki = 0;
+    for (size_t k = 0; k < tables.size(); k++) {
+        const MultiBusTable& t = tables[k];
+        const std::string w = "prove_multi_key: table " + std::to_string(k);
+        const uint32_t pw = t.air->preprocessed_width;
+        if (pw) {
+            TS_REQUIRE(key->heights[ki] == t.trace.height && key->widths[ki] == pw, TS_ERR_INVALID,
+                       w + ": key matrix " + std::to_string(ki) + " has not the table's height and the AIR's preprocessed width");
+        }
+        check_bus_table(t, w, pw);
+        bool reads_key = false;
+        if (t.logup)
+            for (const LogupInteraction& it : t.logup->interactions) {
+                reads_key = reads_key || it.multiplicity.kind == 2;
+                for (const LogupTerm& tm : it.values) reads_key = reads_key || tm.kind == 2;
+            }
+        TS_REQUIRE(!reads_key || (pw && key->values[ki]), TS_ERR_INVALID,
+                   w + ": the logup spec reads preprocessed columns and the key was made without keep_values");
+        ki += pw ? 1 : 0;
+        n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
+    }
+    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
+               "prove_multi_key: more than 64 quotient chunks over all tables (the limit of one committed batch)");
+}
+
+// One body for TSPF v7 (key == nullptr: at least one aux table, no preprocessed columns) and TSPF v8 (a key; the
+// challenge phase only if some table has aux columns).  The statement has been checked.
+static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger& challenger,
+                                                std::vector<MultiBusTable>& tables, const MultiKey* key) {
     Context& ctx = pcs.ctx();
     const size_t T = tables.size();
     std::vector<Statement> st;
@@ -345,6 +404,14 @@ std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challeng
 
     challenger.observe((uint32_t)T);
     for (const Statement& s : st) challenger.observe(s.log_degree);
+    // the key is part of the statement: its root is observed and is not in the proof, as prove_pre does
+    std::vector<size_t> key_of(T, ~(size_t)0);
+    if (key) {
+        size_t ki = 0;
+        for (size_t t = 0; t < T; t++)
+            if (tables[t].air->preprocessed_width) key_of[t] = ki++;
+        challenger.observe_commitment(key->data->root);
+    }
 
     // one commit of every trace; the row-major ones stay alive for the LogUp builder (the LDE stage only reads them)
     std::vector<DeviceMatrix> tv;
@@ -353,27 +420,32 @@ std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challeng
     for (size_t t = 0; t < T; t++)
         if (!tables[t].air->aux_width) tv[t].buf.reset();  // a plain table's rows are not read again
     challenger.observe_commitment(trace_data->root);
-    uint32_t challenges[8];
-    for (int k = 0; k < 2; k++) {  // gamma, beta: one tuple encoding on the whole bus
-        const Ef c = challenger.sample();
-        memcpy(challenges + 4 * k, c.c, 16);
-    }
-
-    // the LogUp matrices of the tables that have one, then ONE commit of them in table order
     std::vector<size_t> aux_of(T, ~(size_t)0), aux_tables;
     for (size_t t = 0; t < T; t++)
         if (tables[t].air->aux_width) {
             aux_of[t] = aux_tables.size();
             aux_tables.push_back(t);
         }
-    const size_t A = aux_tables.size();
+    const size_t A = aux_tables.size();  // 0 (a key proof only): no samples, no aux commitment
+    uint32_t challenges[8] = {0};
+    for (int k = 0; A && k < 2; k++) {  // gamma, beta: one tuple encoding on the whole bus
+        const Ef c = challenger.sample();
+        memcpy(challenges + 4 * k, c.c, 16);
+    }
+
+    // the LogUp matrices of the tables that have one, then ONE commit of them in table order
     std::vector<uint32_t> exposed(4 * A, 0);
     std::vector<DeviceMatrix> av;
-    if (multi_logup_per_table()) {
+    auto key_values = [&](size_t t) -> const DeviceMatrix* {
+        return key_of[t] != ~(size_t)0 ? key->values[key_of[t]] : nullptr;
+    };
+    if (A == 0) {
+    } else if (multi_logup_per_table()) {
         for (size_t a = 0; a < A; a++) {
             const size_t t = aux_tables[a];
             try {
-                av.push_back(logup_aux_build(ctx, *tables[t].logup, tv[t], challenges, &exposed[4 * a]));
+                av.push_back(logup_aux_build(ctx, *tables[t].logup, tv[t], challenges, &exposed[4 * a], key_values(t),
+                                             /*takes_table=*/key != nullptr));
             } catch (const Error& e) {  // the single call names row and interaction: add the table
                 if (e.code != TS_ERR_INVARIANT) throw;
                 throw Error(TS_ERR_INVARIANT, "table " + std::to_string(t) + ": " + e.what());
@@ -381,32 +453,43 @@ std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challeng
         }
     } else {
         std::vector<const LogupSpec*> specs;
-        std::vector<const DeviceMatrix*> traces;
+        std::vector<const DeviceMatrix*> traces, pre;
         for (size_t t : aux_tables) {
             specs.push_back(tables[t].logup);
             traces.push_back(&tv[t]);
+            pre.push_back(key_values(t));
         }
         std::vector<uint32_t> ids(aux_tables.begin(), aux_tables.end());  // a report names the proof's table
-        av = logup_aux_build_multi(ctx, specs, traces, challenges, exposed.data(), ids.data());
+        av = logup_aux_build_multi(ctx, specs, traces, challenges, exposed.data(), ids.data(), key ? &pre : nullptr);
     }
     for (DeviceMatrix& m : tv) m.buf.reset();  // no trace row is read again
-    std::unique_ptr<PcsData> aux_data = pcs.commit(av, std::vector<uint32_t>(A, 1u));
-    challenger.observe_commitment(aux_data->root);
-    for (uint32_t e : exposed) challenger.observe(e);
+    std::unique_ptr<PcsData> aux_data;
+    if (A) {
+        aux_data = pcs.commit(av, std::vector<uint32_t>(A, 1u));
+        challenger.observe_commitment(aux_data->root);
+        for (uint32_t e : exposed) challenger.observe(e);
+    }
     const Ef alpha = challenger.sample();
 
-    // the chunks of every table over (its aux LDE, its trace LDE) in the batches, then one commit of all of them
+    // the chunks of every table over (its key LDE, its aux LDE, its trace LDE) in the batches, each side matrix where
+    // the table has one, then one commit of all of them
     std::vector<DeviceMatrix> chunks;
     std::vector<uint32_t> shifts;
     for (size_t t = 0; t < T; t++) {
         std::vector<uint32_t> pis = tables[t].public_values;
         SideLdes side;
+        if (key_of[t] != ~(size_t)0) {
+            const ColMat& m = key->data->ldes[key_of[t]];
+            TS_REQUIRE(m.width == tables[t].air->preprocessed_width && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
+                       "prove_multi_key: a key matrix has another shape than its table's");
+            side.m[side.n++] = &m;
+        }
         if (aux_of[t] != ~(size_t)0) {
             pis.insert(pis.end(), challenges, challenges + 8);
             pis.insert(pis.end(), &exposed[4 * aux_of[t]], &exposed[4 * aux_of[t]] + 4);
             const ColMat& m = aux_data->ldes[aux_of[t]];
             TS_REQUIRE(m.width == tables[t].air->aux_width && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
-                       "prove_multi_bus: a committed aux matrix has another shape than its table's");
+                       "prove_multi: a committed aux matrix has another shape than its table's");
             side.m[side.n++] = &m;
         }
         std::vector<DeviceMatrix> c = pcs.quotient_chunks_slab(trace_data->ldes[t], st[t].log_degree, TwoAdicFriPcs::Slab{},
@@ -419,44 +502,72 @@ std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challeng
     challenger.observe_commitment(quotient_data->root);
     const Ef zeta = challenger.sample();
 
-    // the three rounds in the visiting order of Pcs::open
+    // the rounds in the visiting order of Pcs::open: [key,] [aux,] traces, chunks
     std::vector<OpenMat> mats;
+    std::vector<const PcsData*> rounds;
     size_t first = 0, qi = 0;
-    for (size_t a = 0; a < A; a++) {
-        const size_t t = aux_tables[a];
-        mats.push_back(OpenMat{&aux_data->ldes[a], 0, st[t].log_degree, true, first});
-        first += 2 * (size_t)aux_data->ldes[a].width;
+    if (key) {
+        for (size_t t = 0; t < T; t++)
+            if (key_of[t] != ~(size_t)0) {
+                const ColMat& m = key->data->ldes[key_of[t]];
+                mats.push_back(OpenMat{&m, (unsigned)rounds.size(), st[t].log_degree, true, first});
+                first += 2 * (size_t)m.width;
+            }
+        rounds.push_back(key->data.get());
+    }
+    if (A) {
+        for (size_t a = 0; a < A; a++) {
+            const size_t t = aux_tables[a];
+            mats.push_back(OpenMat{&aux_data->ldes[a], (unsigned)rounds.size(), st[t].log_degree, true, first});
+            first += 2 * (size_t)aux_data->ldes[a].width;
+        }
+        rounds.push_back(aux_data.get());
     }
     for (size_t t = 0; t < T; t++) {
-        mats.push_back(OpenMat{&trace_data->ldes[t], 1, st[t].log_degree, true, first});
+        mats.push_back(OpenMat{&trace_data->ldes[t], (unsigned)rounds.size(), st[t].log_degree, true, first});
         first += 2 * (size_t)st[t].w;
     }
+    rounds.push_back(trace_data.get());
     for (size_t t = 0; t < T; t++)
         for (uint32_t c = 0; c < st[t].qd; c++, qi++) {
             const ColMat& m = quotient_data->ldes[qi];
             TS_REQUIRE(m.width == 4 && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
                        "prove_multi_bus: a committed chunk has another shape than its table's");
-            mats.push_back(OpenMat{&m, 2, st[t].log_degree, false, first});
+            mats.push_back(OpenMat{&m, (unsigned)rounds.size(), st[t].log_degree, false, first});
             first += 4;
         }
+    rounds.push_back(quotient_data.get());
     std::vector<Ef> opened;
-    const std::vector<uint32_t> fri_words =
-        open_rounds(pcs, challenger, {aux_data.get(), trace_data.get(), quotient_data.get()}, mats, zeta, opened);
+    const std::vector<uint32_t> fri_words = open_rounds(pcs, challenger, rounds, mats, zeta, opened);
 
     std::vector<uint32_t> pf;
     pf.reserve(32 + 5 * T + exposed.size() + opened.size() * 4 + fri_words.size());
     ProofWriter pw(pf);
     std::vector<ProofWriter::TableShape> shapes;
     for (size_t t = 0; t < T; t++)
-        shapes.push_back({st[t].log_degree, st[t].w, st[t].qd, tables[t].air->aux_width, tables[t].air->n_exposed});
-    pw.header_multi(shapes, 7);
+        shapes.push_back({st[t].log_degree, st[t].w, st[t].qd, tables[t].air->aux_width, tables[t].air->n_exposed,
+                          tables[t].air->preprocessed_width});
+    pw.header_multi(shapes, key ? 8 : 7);
     pw.commitment(trace_data->root, 8);
-    pw.commitment(aux_data->root, 8);
-    pw.words(exposed.data(), exposed.size());
+    if (A) {
+        pw.commitment(aux_data->root, 8);
+        pw.words(exposed.data(), exposed.size());
+    }
     pw.commitment(quotient_data->root, 8);
     pw.opened_values(opened);
     pw.words(fri_words.data(), fri_words.size());
     return pf;
+}
+
+std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables) {
+    check_multi_bus_statement(pcs.fri(), tables);
+    return prove_multi_phased(pcs, challenger, tables, nullptr);
+}
+
+std::vector<uint32_t> prove_multi_key(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables,
+                                      const MultiKey& key) {
+    check_multi_key_statement(pcs.fri(), tables, &key);
+    return prove_multi_phased(pcs, challenger, tables, &key);
 }
 
 }  // namespace ts

@@ -266,6 +266,7 @@ void ProofWriter::header_multi(const std::vector<TableShape>& tables, uint32_t v
             out_.push_back(t.aux_width);
             out_.push_back(t.n_exposed);
         }
+        if (version >= 8) out_.push_back(t.preprocessed_width);
     }
 }
 

@@ -120,8 +120,9 @@ public:
     // aux_width word (the caller appends n_challenges and n_exposed)
     void header(uint32_t version, unsigned log_degree, uint32_t width, uint32_t qd, uint32_t extra);
     // version 6 (prove_multi): [magic, 6, T], then T x [log_degree, width, qd] in table order; version 7
-    // (prove_multi_bus): [magic, 7, T], then T x [log_degree, width, qd, aux_width, n_exposed]
-    struct TableShape { unsigned log_degree; uint32_t width, qd, aux_width, n_exposed; };
+    // (prove_multi_bus): [magic, 7, T], then T x [log_degree, width, qd, aux_width, n_exposed]; version 8
+    // (prove_multi_key): the same with preprocessed_width as a sixth word per table
+    struct TableShape { unsigned log_degree; uint32_t width, qd, aux_width, n_exposed, preprocessed_width = 0; };
     void header_multi(const std::vector<TableShape>& tables, uint32_t version = 6);
     void commitment(const uint32_t* roots, size_t n_words) { words(roots, n_words); }  // 8, or Q x 8 (taptrees)
     void opened_values(const std::vector<Ef>& values);

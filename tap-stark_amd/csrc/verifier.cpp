@@ -626,37 +626,42 @@ int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vect
 // the out-of-domain check per table over (aux, trace) with pis ++ challenges ++ that table's exposed words.
 // `exposed` receives the proof's exposed words and `bus_sum` their EF4 sum over the tables on acceptance; whether
 // the bus balances (bus_sum == 0) is the caller's statement, as verify_aux leaves it.
-int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
-                     const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words,
-                     std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
+// One body for v7 (key_root == nullptr) and v8 (verify_multi_key below).
+static int verify_multi_phased(const FriConfig& fri, BfChallenger& challenger, const uint32_t* key_root,
+                               const std::vector<const AirProgram*>& airs,
+                               const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof,
+                               size_t n_words, std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
     const size_t T = airs.size();
+    const size_t SW = key_root ? 6 : 5;  // header words per table
     if (T == 0 || T > MAX_MULTI_TABLES || public_values.size() != T) return 1;
-    size_t A = 0;
+    size_t A = 0, K = 0;
     for (size_t t = 0; t < T; t++) {
-        if (!airs[t] || airs[t]->preprocessed_width || public_values[t].size() != airs[t]->n_public) return 1;
+        if (!airs[t] || public_values[t].size() != airs[t]->n_public) return 1;
         const AirProgram& a = *airs[t];
         if (a.aux_width ? (a.n_challenges != 2 || a.n_exposed != 4) : (a.n_challenges || a.n_exposed)) return 1;
         A += a.aux_width ? 1 : 0;
+        K += a.preprocessed_width ? 1 : 0;
     }
-    if (A == 0) return 1;
+    if (key_root ? K == 0 : (K != 0 || A == 0)) return 1;
     Reader rb{proof, n_words};
-    if (rb.get() != TSPF_MAGIC || rb.get() != 7u) return 9;
+    if (rb.get() != TSPF_MAGIC || rb.get() != (key_root ? 8u : 7u)) return 9;
     const uint32_t pT = rb.get();
     if (rb.bad) return 9;
     if (pT != T) return 1;
-    const uint32_t* shapes = rb.take(5 * T);
+    const uint32_t* shapes = rb.take(SW * T);
     if (rb.bad) return 9;
     size_t n_vals = 0;  // opened EF4 values
     for (size_t t = 0; t < T; t++) {
-        const uint32_t* sh = shapes + 5 * t;
+        const uint32_t* sh = shapes + SW * t;
         if (sh[0] > 27) return 9;
         if (sh[1] != airs[t]->width || sh[2] != (1u << airs[t]->log_quotient_degree) || sh[3] != airs[t]->aux_width ||
-            sh[4] != airs[t]->n_exposed)
+            sh[4] != airs[t]->n_exposed || (key_root && sh[5] != airs[t]->preprocessed_width))
             return 1;
-        n_vals += 2 * (size_t)airs[t]->aux_width + 2 * (size_t)airs[t]->width + 4 * (size_t)sh[2];
+        n_vals += 2 * (size_t)airs[t]->preprocessed_width + 2 * (size_t)airs[t]->aux_width + 2 * (size_t)airs[t]->width +
+                  4 * (size_t)sh[2];
     }
     const uint32_t* trace_root = rb.take(8);
-    const uint32_t* aux_root = rb.take(8);
+    const uint32_t* aux_root = A ? rb.take(8) : nullptr;
     const uint32_t* exp_words = rb.take(4 * A);
     const uint32_t* quot_root = rb.take(8);
     const uint32_t* vals = rb.take(4 * n_vals);
@@ -670,36 +675,45 @@ int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::
     memcpy((void*)ov.data(), vals, 16 * n_vals);
 
     challenger.observe((uint32_t)T);
-    for (size_t t = 0; t < T; t++) challenger.observe(shapes[5 * t]);
+    for (size_t t = 0; t < T; t++) challenger.observe(shapes[SW * t]);
+    if (key_root) challenger.observe_commitment(key_root);
     challenger.observe_commitment(trace_root);
-    uint32_t challenges[8];
-    for (int k = 0; k < 2; k++) {
-        const Ef c = challenger.sample();
-        memcpy(challenges + 4 * k, c.c, 16);
+    uint32_t challenges[8] = {0};
+    if (A) {  // the challenge phase, skipped whole by a key proof without aux tables
+        for (int k = 0; k < 2; k++) {
+            const Ef c = challenger.sample();
+            memcpy(challenges + 4 * k, c.c, 16);
+        }
+        challenger.observe_commitment(aux_root);
+        for (size_t k = 0; k < 4 * A; k++) challenger.observe(exp_words[k]);
     }
-    challenger.observe_commitment(aux_root);
-    for (size_t k = 0; k < 4 * A; k++) challenger.observe(exp_words[k]);
     const Ef alpha = challenger.sample();
     challenger.observe_commitment(quot_root);
     const Ef zeta = challenger.sample();
 
-    PcsRoundClaim ra, r0, r1;
+    PcsRoundClaim rk, ra, r0, r1;
+    rk.root = key_root;
     ra.root = aux_root;
     r0.root = trace_root;
     r1.root = quot_root;
-    size_t aat = 0, at = 0, qat = 0, ai = 0;  // the traces' values follow every aux matrix's, the chunks' every trace's
+    // the values in round order: every key matrix's, then every aux matrix's, every trace's, every chunk's
+    size_t kat = 0, aat = 0, at = 0, qat = 0, ai = 0;
+    for (size_t t = 0; t < T; t++) aat += 2 * (size_t)airs[t]->preprocessed_width;
+    at = aat;
     for (size_t t = 0; t < T; t++) at += 2 * (size_t)airs[t]->aux_width;
     qat = at;
     for (size_t t = 0; t < T; t++) qat += 2 * (size_t)airs[t]->width;
     Ef sum = ef_zero();
     for (size_t t = 0; t < T; t++) {
-        const unsigned degree_bits = shapes[5 * t];
-        const uint32_t w = airs[t]->width, qd = shapes[5 * t + 2], aw = airs[t]->aux_width;
+        const unsigned degree_bits = shapes[SW * t];
+        const uint32_t w = airs[t]->width, qd = shapes[SW * t + 2], aw = airs[t]->aux_width, kw = airs[t]->preprocessed_width;
         const Ef zeta_next = c_mul_base(zeta, two_adic_generator(degree_bits));
+        const std::vector<Ef> kl(ov.begin() + kat, ov.begin() + kat + kw), kn(ov.begin() + kat + kw, ov.begin() + kat + 2 * kw);
         const std::vector<Ef> al(ov.begin() + aat, ov.begin() + aat + aw), an(ov.begin() + aat + aw, ov.begin() + aat + 2 * aw);
         const std::vector<Ef> tl(ov.begin() + at, ov.begin() + at + w), tn(ov.begin() + at + w, ov.begin() + at + 2 * w);
         const std::vector<Ef> qc(ov.begin() + qat, ov.begin() + qat + 4 * (size_t)qd);
         std::vector<uint32_t> pis = public_values[t];
+        if (kw) rk.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, kw, {zeta, zeta_next}, {kl, kn}});
         if (aw) {
             pis.insert(pis.end(), challenges, challenges + 8);
             pis.insert(pis.end(), exp_words + 4 * ai, exp_words + 4 * ai + 4);
@@ -707,13 +721,14 @@ int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::
             ra.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, aw, {zeta, zeta_next}, {al, an}});
             ai++;
         }
-        if (!ood_holds(*airs[t], degree_bits, zeta, alpha, nullptr, nullptr, al.data(), an.data(), tl.data(), tn.data(), qc,
-                       pis))
+        if (!ood_holds(*airs[t], degree_bits, zeta, alpha, kl.data(), kn.data(), al.data(), an.data(), tl.data(), tn.data(),
+                       qc, pis))
             return 7;
         r0.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, w, {zeta, zeta_next}, {tl, tn}});
         for (uint32_t c = 0; c < qd; c++)
             r1.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, 4, {zeta},
                                           {std::vector<Ef>(qc.begin() + 4 * (size_t)c, qc.begin() + 4 * (size_t)c + 4)}});
+        kat += 2 * (size_t)kw;
         aat += 2 * (size_t)aw;
         at += 2 * (size_t)w;
         qat += 4 * (size_t)qd;
@@ -723,17 +738,40 @@ int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::
     const uint32_t R = fr.get();
     if (fr.bad) return 9;
     unsigned log_max = 0;
-    for (size_t t = 0; t < T; t++) log_max = std::max<unsigned>(log_max, shapes[5 * t]);
+    for (size_t t = 0; t < T; t++) log_max = std::max<unsigned>(log_max, shapes[SW * t]);
     if (R != log_max) return 1;
     fr.take(8 * (size_t)R);
     const uint32_t Q = fr.get();
     if (fr.bad) return 9;
     if (Q != fri.num_queries) return 1;
-    const int rc = fri_verify_impl(fri, challenger, {ra, r0, r1}, false, proof + rb.pos, n_words - rb.pos);
+    std::vector<PcsRoundClaim> claims;
+    if (key_root) claims.push_back(rk);
+    if (A) claims.push_back(ra);
+    claims.push_back(r0);
+    claims.push_back(r1);
+    const int rc = fri_verify_impl(fri, challenger, claims, false, proof + rb.pos, n_words - rb.pos);
     if (rc) return rc;
     exposed.assign(exp_words, exp_words + 4 * A);
     memcpy(bus_sum, sum.c, 16);
     return 0;
+}
+
+int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
+                     const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words,
+                     std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
+    return verify_multi_phased(fri, challenger, nullptr, airs, public_values, proof, n_words, exposed, bus_sum);
+}
+
+// ------------------------------------------------------------------ verify, several tables, a bus and a key
+// The verifier of prove_multi_key (prove_multi.cpp), TSPF v8: v7 with a sixth header word per table (the
+// preprocessed width), the key root observed after the shapes (it is not in the proof), the preprocessed opened values
+// in each table's out-of-domain check, and the key's round first among three or four.  Without an aux table the proof
+// holds no aux root and no exposed words, and no challenge is sampled before alpha.
+int verify_multi_key(const FriConfig& fri, BfChallenger& challenger, const uint32_t key_root[8],
+                     const std::vector<const AirProgram*>& airs, const std::vector<std::vector<uint32_t>>& public_values,
+                     const uint32_t* proof, size_t n_words, std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
+    if (!key_root) return 1;
+    return verify_multi_phased(fri, challenger, key_root, airs, public_values, proof, n_words, exposed, bus_sum);
 }
 
 }  // namespace ts

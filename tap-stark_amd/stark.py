@@ -1265,6 +1265,7 @@ class MultiBusProof(MultiProof):
     zero exactly when the bus balances)."""
 
     _FIELDS = MultiProof._FIELDS + ("aux_commit", "exposed", "bus_sum")
+    _VERSION = 7
 
     def __getattr__(self, name):
         if name in MultiBusProof._FIELDS:
@@ -1285,22 +1286,31 @@ class MultiBusProof(MultiProof):
             return out
 
         magic, version, T = (int(x) for x in take(3))
-        if magic != TSPF_MAGIC or version != 7 or not 1 <= T <= 64:
-            raise ValueError("not a TSPF v7 proof")
-        shapes = [tuple(int(x) for x in row) for row in take(5 * T).reshape(T, 5)]
-        d = {"trace_commit": take(8), "aux_commit": take(8), "query_proofs": []}
-        d["exposed"] = take(sum(ne for *_, aw, ne in shapes if aw))
+        V = self._VERSION  # 7; 8 (MultiKeyProof): a sixth word per table, the aux words only with an aux table
+        if magic != TSPF_MAGIC or version != V or not 1 <= T <= 64:
+            raise ValueError(f"not a TSPF v{V} proof")
+        SW = 6 if V == 8 else 5
+        shapes = [tuple(int(x) for x in row) + (0,) * (6 - SW) for row in take(SW * T).reshape(T, SW)]
+        has_aux = V == 7 or any(aw for _, _, _, aw, _, _ in shapes)
+        d = {"trace_commit": take(8), "aux_commit": take(8) if has_aux else None, "query_proofs": []}
+        d["exposed"] = take(sum(ne for _, _, _, aw, ne, _ in shapes if aw))
         d["bus_sum"] = (d["exposed"].reshape(-1, 4).astype(np.uint64).sum(axis=0) % np.uint64(P)).astype(np.uint32)
         d["quotient_commit"] = take(8)
         start = pos
-        aux = [(take(4 * aw).reshape(-1, 4), take(4 * aw).reshape(-1, 4)) if aw else (w[:0].reshape(0, 4),) * 2
-               for *_, aw, _ in shapes]
+        empty = (w[:0].reshape(0, 4),) * 2
+        prep = [(take(4 * pw).reshape(-1, 4), take(4 * pw).reshape(-1, 4)) if pw else empty for *_, pw in shapes]
+        aux = [(take(4 * aw).reshape(-1, 4), take(4 * aw).reshape(-1, 4)) if aw else empty
+               for _, _, _, aw, _, _ in shapes]
         locals_ = [(take(4 * wd).reshape(-1, 4), take(4 * wd).reshape(-1, 4)) for _, wd, *_ in shapes]
         d["tables"], e = [], 0
-        for (ld, wd, qd, aw, ne), (al, an), (tl, tn) in zip(shapes, aux, locals_):
+        for (ld, wd, qd, aw, ne, pw), (pl, pn), (al, an), (tl, tn) in zip(shapes, prep, aux, locals_):
             ex = d["exposed"][e:e + ne] if aw else w[:0]
             e += ne if aw else 0
-            d["tables"].append(MultiBusTableOpening(ld, wd, qd, tl, tn, take(16 * qd).reshape(-1, 4, 4), aw, ne, al, an, ex))
+            chunks = take(16 * qd).reshape(-1, 4, 4)
+            if V == 8:
+                d["tables"].append(MultiKeyTableOpening(ld, wd, qd, tl, tn, chunks, aw, ne, al, an, ex, pw, pl, pn))
+            else:
+                d["tables"].append(MultiBusTableOpening(ld, wd, qd, tl, tn, chunks, aw, ne, al, an, ex))
         d["opened_words"] = w[start:pos]
         d["fri_words"] = w[pos:]
         R = int(take(1)[0])
@@ -1396,6 +1406,162 @@ def verify_multi_bus(config: StarkConfig, airs, challenger: BfChallenger, proof,
     n_aux = sum(1 for a in airs if a.aux_width)
     if check_bus and bus_sum.any():
         raise ValueError("verify_multi_bus: the exposed sums of the tables do not add up to zero: the bus does not balance")
+    return exposed[: 4 * n_aux], bus_sum
+
+
+@dataclass
+class MultiKeyTableOpening(MultiBusTableOpening):
+    """One table of a :class:`MultiKeyProof`: what :class:`MultiBusTableOpening` holds, its preprocessed width and the
+    opened rows of its key matrix; empty arrays for a table without preprocessed columns."""
+    preprocessed_width: int = 0
+    preprocessed_local: np.ndarray = None   # (preprocessed_width, 4)
+    preprocessed_next: np.ndarray = None    # (preprocessed_width, 4)
+
+
+class MultiKeyProof(MultiBusProof):
+    """A TSPF v8 proof (``ts_prove_multi_key``): a :class:`MultiBusProof` against a commit-once :class:`MultiKey`.
+    ``tables`` holds :class:`MultiKeyTableOpening`; without any aux table ``aux_commit`` is None, ``exposed`` empty
+    and ``bus_sum`` zero.  The key root is not in the proof."""
+
+    _VERSION = 8
+
+
+class _BorrowedMatrix(DeviceMatrix):
+    """A handle owned by another object (``owner`` is kept alive with it) and never freed from here."""
+
+    def __init__(self, ctx, handle, owner):
+        super().__init__(ctx, handle)
+        self._owner = owner
+
+    def __del__(self):
+        pass
+
+
+class MultiKey:
+    """``ts_multi_key``: the preprocessed matrices of a multi-table proof, committed ONCE in one batch on their natural
+    domains (mixed power-of-two heights).  Never consumed: one key serves any number of ``prove_multi_key`` calls on
+    its context; ``root`` is what the verifier holds.  ``matrices``: arrays or ``DeviceMatrix`` (consumed).  With
+    ``keep_values`` (default) the row-major inputs stay alive inside the key without a second copy and ``values(i)``
+    lends matrix i for ``logup_build_multi(..., preprocessed=)``, ``logup_multiplicities_bus(..., table_preprocessed=)``
+    and for ``("prep", c)`` terms inside the proof."""
+
+    def __init__(self, config: "StarkConfig", matrices, keep_values: bool = True):
+        pcs = config.pcs
+        self.ctx = ctx = pcs.ctx
+        self.h = None
+        mats = [m if isinstance(m, DeviceMatrix) else DeviceMatrix.upload(ctx, _u32(m)) for m in matrices]
+        handles = (C.c_void_p * max(len(mats), 1))(*[m.h for m in mats])
+        cfg = pcs.fri._c()
+        self.root = np.zeros(8, dtype=np.uint32)
+        h = C.c_void_p()
+        ctx.check(ctx._l.ts_multi_key_commit(ctx.h, C.byref(cfg), len(mats), handles, 1 if keep_values else 0,
+                                             _p(self.root), C.byref(h)))
+        self.h = h
+        self.n = len(mats)
+        self.keep_values = bool(keep_values)
+
+    def info(self, i: int):
+        """(height, width) of matrix ``i``."""
+        hh, ww = C.c_uint64(), C.c_uint32()
+        self.ctx.check(self.ctx._l.ts_multi_key_info(self.h, i, C.byref(hh), C.byref(ww)))
+        return int(hh.value), int(ww.value)
+
+    def values(self, i: int) -> DeviceMatrix:
+        """The row-major values of matrix ``i``, borrowed from the key (``ts_multi_key_values``)."""
+        h = C.c_void_p()
+        rc = self.ctx._l.ts_multi_key_values(self.h, i, C.byref(h))
+        if rc:
+            raise _lib.TsError(rc, "ts_multi_key_values: no such matrix, or the key was made without keep_values")
+        return _BorrowedMatrix(self.ctx, h, self)
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.ctx._l.ts_multi_key_free(self.ctx.h, self.h)
+        except Exception:
+            pass
+
+
+def _multi_key_capacity(shapes, fri: FriConfig) -> int:
+    """An upper bound (exact when the tallest table has a key matrix) on the TSPF v8 words of a proof over ``shapes`` =
+    [(n, w, log_quotient_degree, aux_width, preprocessed_width), ...]."""
+    aux = [aw for *_, aw, _ in shapes if aw]
+    log_max = max(max(n, 1).bit_length() - 1 for n, *_ in shapes) + fri.log_blowup
+    if aux:
+        v7 = _multi_bus_capacity([sh[:4] for sh in shapes], fri)
+    else:  # no aux root, no exposed words, no aux round
+        v7 = _multi_capacity([sh[:3] for sh in shapes], fri) + 2 * len(shapes)
+    pre = [pw for *_, pw in shapes if pw]
+    return v7 + len(shapes) + 8 * sum(pre) + fri.num_queries * (2 + len(pre) + sum(pre) + 8 * log_max)
+
+
+def prove_multi_key(config: StarkConfig, key: MultiKey, airs, challenger: BfChallenger, traces, public_values,
+                    logups) -> MultiKeyProof:
+    """``ts_prove_multi_key``: ``prove_multi_bus`` against a commit-once key (TSPF v8).  The i-th AIR with preprocessed
+    columns, in table order, reads matrix i of ``key``.  ``logups`` as in ``prove_multi_bus``; their terms may be
+    ``("prep", c)``: column c of that table's key matrix (the key then keeps its values).  Without any aux table the
+    challenge phase is skipped."""
+    pcs = config.pcs
+    ctx = pcs.ctx
+    T = len(airs)
+    if len(traces) != T or len(public_values) != T or len(logups) != T:
+        raise ValueError("prove_multi_key: one trace, one public-value list and one LogUp (or None) per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
+    tabs = (_lib.MultiBusTableC * max(T, 1))()
+    keep = []
+    for k in range(T):
+        tabs[k].struct_size = C.sizeof(_lib.MultiBusTableC)
+        tabs[k].n_public = len(pis[k])
+        tabs[k].air = airs[k].h
+        tabs[k].trace = traces[k].h
+        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
+        if logups[k] is not None:
+            keep.append(logups[k]._spec_c())
+            tabs[k].logup = C.pointer(keep[-1][0])
+    shapes = [(*t.dims(), a.log_quotient_degree, lg.aux_width if lg is not None else 0, a.preprocessed_width)
+              for t, a, lg in zip(traces, airs, logups)]
+    out = _proof_buffer(ctx, _multi_key_capacity(shapes, pcs.fri) if T else 1)
+    n_words = C.c_size_t()
+    cfg = pcs.fri._c()
+    ctx.check(ctx._l.ts_prove_multi_key(ctx.h, C.byref(cfg), challenger.h, key.h if key is not None else None, tabs, T,
+                                        _p(out), len(out), C.byref(n_words)))
+    del keep
+    return MultiKeyProof(out[: n_words.value].copy())
+
+
+def verify_multi_key(config: StarkConfig, key_root, airs, challenger: BfChallenger, proof, public_values,
+                     check_bus: bool = True):
+    """``ts_verify_multi_key``; host only.  ``key_root``: the eight words of the key's commitment (``MultiKey.root``).
+    Raises ``VerificationError`` on a rejected proof and, with ``check_bus``, ``ValueError`` when the exposed sums do
+    not add up to zero.  Returns ``(exposed, bus_sum)`` as ``verify_multi_bus`` does; both empty / zero without an aux
+    table."""
+    T = len(airs)
+    if len(public_values) != T:
+        raise ValueError("verify_multi_key: one public-value list per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
+    root = _u32(key_root).reshape(-1)
+    if len(root) != 8:
+        raise ValueError("verify_multi_key: the key root has eight words")
+    l = _lib.lib()
+    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
+    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
+    n_pub = _u32([len(p) for p in pis] or [0])
+    cfg = config.pcs.fri._c()
+    verdict = C.c_int(-1)
+    exposed, bus_sum = np.zeros(4 * max(T, 1), dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    rc = l.ts_verify_multi_key(C.byref(cfg), challenger.h, _p(root), handles, T, pv, _p(n_pub), _p(words), len(words),
+                               _p(exposed), len(exposed), _p(bus_sum), C.byref(verdict))
+    if rc:
+        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_multi_key").decode())
+    if verdict.value != 0:
+        raise VerificationError(verdict.value)
+    n_aux = sum(1 for a in airs if a.aux_width)
+    if check_bus and bus_sum.any():
+        raise ValueError("verify_multi_key: the exposed sums of the tables do not add up to zero: the bus does not balance")
     return exposed[: 4 * n_aux], bus_sum
 
 
