@@ -197,6 +197,35 @@ pub struct ts_logup_mult_bus_spec {
     pub pad: u32,
 }
 
+/// `ts_bus_share`: one table's part of the tuple a `ts_bus_report` names (`first_*` are `!0` without a contribution).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_bus_share {
+    pub count: u64,
+    pub sum: u32,
+    pub first_row: u32,
+    pub first_interaction: u32,
+    pub pad: u32,
+}
+
+/// `ts_bus_report`: what `ts_bus_check` says about a bus (`struct_size` is an input; `first_*` are `!0` when balanced).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_bus_report {
+    pub struct_size: u32,
+    pub pad: u32,
+    pub n_contributions: u64,
+    pub n_tuples: u64,
+    pub n_unbalanced: u64,
+    pub first_table: u32,
+    pub first_row: u32,
+    pub first_interaction: u32,
+    pub n_values: u32,
+    pub tuple: [u32; 8],
+    pub sum: u32,
+    pub pad2: u32,
+}
+
 /// One statement of `ts_prove_batch_lookup`: `ts_batch_item`'s inputs, the aux source (exactly one of `logup` /
 /// `aux_fn` for an AIR with aux columns), the multiplicity fills, then what the library writes back.
 #[repr(C)]
@@ -446,6 +475,14 @@ extern "C" {
                                            table_preprocessed: *const ts_matrix, table_trace: *mut ts_matrix,
                                            lookers: *const *const ts_matrix, n_missing: *mut u64,
                                            first_missing: *mut u64) -> ts_status;
+    /// the exact balance of a LogUp bus from the resident traces: a hash join over every table, no challenge
+    pub fn ts_bus_check(ctx: *mut ts_ctx, n: u32, specs: *const *const ts_logup_spec,
+                        preprocessed: *const *const ts_matrix, traces: *const *const ts_matrix,
+                        report: *mut ts_bus_report, shares: *mut ts_bus_share) -> ts_status;
+    /// the debug counterpart of ts_prove_multi_bus / ts_prove_multi_key: the traces are not consumed
+    pub fn ts_check_multi(ctx: *mut ts_ctx, key: *const ts_multi_key, tables: *const ts_multi_bus_table, n_tables: u32,
+                          challenges: *const u32, bad_table: *mut i32, first_violation: *mut i64,
+                          report: *mut ts_bus_report, shares: *mut ts_bus_share) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

@@ -1251,6 +1251,64 @@ ts_status ts_logup_multiplicities_bus_pre(ts_ctx* ctx, const ts_logup_mult_bus_s
                                           const ts_matrix* const* lookers /* n_lookers */, uint64_t* n_missing,
                                           uint64_t first_missing[3]);
 
+/* ---- before you prove: the exact balance of a bus, and the debug counterpart of the bus proofs -----------------------
+ * ts_verify_multi_bus and ts_verify_multi_key answer an unbalanced bus with bus_sum != 0 after a whole proof, and
+ * bus_sum does not say which tuple is out of balance.  ts_bus_check says it from the resident traces, without a
+ * challenge and exactly: a hash join in HBM over every table of the bus.
+ *   A CONTRIBUTION is a triple (table k, row r, interaction i of specs[k]) whose multiplicity term, reduced mod p, is
+ *   non-zero (a word of 0 or of p is none; p + 1 counts as 1).  Terms of kinds 0, 1 and 2 are read exactly as
+ *   ts_logup_aux_build_multi_pre reads them.
+ *   The TUPLE of a contribution is its value terms ZERO-PADDED to 8 words; words are compared as stored, as the
+ *   multiplicity calls do.  The padding is what the argument means: gamma + sum_j beta^j v_j cannot tell (a, b) from
+ *   (a, b, 0), so they are the same tuple on the bus.
+ *   The bus is BALANCED iff every tuple's multiplicities sum to 0 mod p.
+ *   first_table, first_row, first_interaction: the least contribution, in (table, row, interaction) order, over all
+ *   contributions to unbalanced tuples; n_values, tuple and sum describe that contribution's tuple.
+ *   shares[k] (if given) describes table k's part of that tuple: the number of its contributions, their multiplicity
+ *   sum mod p, and the least (row, interaction) among them, ~0 each when table k has none.  When the bus is balanced
+ *   shares is all zero with ~0 rows and interactions.
+ * Every output is a count, a minimum or an integer sum: the same on every run.  No trace is written or consumed.
+ * specs[k] == NULL: table k is not on the bus and traces[k] is not looked at.  preprocessed may be NULL (no kind-2
+ * term anywhere), as may any entry.  TS_LOGUP_HASH_BITS is honoured as in ts_logup_multiplicities.
+ * TS_ERR_INVALID, with a text, before any device work: what ts_logup_aux_build_multi_pre refuses for any k (a trace
+ * that is not row-major, consumed or of another context, a height outside [1, 2^27], counts outside their limits, a
+ * kind-2 term without its matrix, a column outside its matrix, a non-canonical constant); n outside 1 .. 64; every spec
+ * NULL; the sum over k of height_k * K_k above 2^30 (which also keeps the 64-bit sums below 2^61); a struct_size that
+ * is not sizeof the report.  A full slot table is TS_ERR_INVARIANT "internal error", as in the multiplicity calls.
+ * Launches: one insert over the rows of all tables (the specs travel in a job table in device memory), one over the
+ * slots, one copy back; only if unbalanced one more launch over the rows for the shares, and a second copy back. */
+typedef struct { uint64_t count; uint32_t sum, first_row, first_interaction, pad; } ts_bus_share;
+typedef struct {
+    uint32_t struct_size, pad;      /* in: sizeof(ts_bus_report), else TS_ERR_INVALID */
+    uint64_t n_contributions;       /* (table, row, interaction) with multiplicity != 0 mod p */
+    uint64_t n_tuples;              /* distinct tuples among them */
+    uint64_t n_unbalanced;          /* tuples whose multiplicities do not sum to 0 mod p */
+    uint32_t first_table, first_row, first_interaction;  /* ~0 each when balanced */
+    uint32_t n_values;              /* of that contribution's interaction */
+    uint32_t tuple[8];              /* its values, zero-padded */
+    uint32_t sum, pad2;             /* its multiplicity sum, canonical, != 0 */
+} ts_bus_report;
+ts_status ts_bus_check(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs /* entries may be NULL */,
+                       const ts_matrix* const* preprocessed /* may be NULL; entries may be NULL */,
+                       const ts_matrix* const* traces, ts_bus_report* report, ts_bus_share* shares /* n, may be NULL */);
+/* The debug counterpart of ts_prove_multi_bus and ts_prove_multi_key, as ts_check_constraints is of ts_prove: the
+ * statement's tables with their traces NOT consumed, and any gamma and beta (challenges: eight canonical words, the
+ * caller's choice).  `key`: NULL iff no table has preprocessed columns, else made with keep_values = 1; the i-th table
+ * with preprocessed columns reads key matrix i.  A host composition, no kernel of its own:
+ *   1. the argument checks of ts_prove_multi_key that need no FRI configuration: struct_size, handles, contexts, one
+ *      trace handle twice, specs against AIRs and traces, the key's count, heights and widths; every trace row-major;
+ *   2. ts_logup_aux_build_multi_pre over the tables with aux columns: a zero denominator at these challenges is
+ *      TS_ERR_INVARIANT as there;
+ *   3. per table, in order, ts_check_constraints_pre_aux with that table's key matrix, aux matrix and exposed words:
+ *      *bad_table is the first table with a violation and *first_violation that call's answer, both -1 when all hold
+ *      (the later tables are then not checked);
+ *   4. ts_bus_check over the same specs into report and shares (n_tables of them, may be NULL); without any table
+ *      that has aux columns the report is the balanced one with zero counts;
+ *   5. the aux matrices are freed. */
+ts_status ts_check_multi(ts_ctx* ctx, const ts_multi_key* key, const ts_multi_key_table* tables, uint32_t n_tables,
+                         const uint32_t challenges[8], int32_t* bad_table, int64_t* first_violation,
+                         ts_bus_report* report, ts_bus_share* shares);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

@@ -10,3 +10,5 @@ from .stark import MultiProof, MultiTableOpening, prove_multi, verify_multi  # n
 from .stark import MultiBusProof, MultiBusTableOpening, prove_multi_bus, verify_multi_bus  # noqa: F401
 from .air import logup_build_multi, logup_multiplicities_bus  # noqa: F401
 from .stark import MultiKey, MultiKeyProof, MultiKeyTableOpening, prove_multi_key, verify_multi_key  # noqa: F401
+from .air import BusReport, BusShare, bus_check  # noqa: F401
+from .stark import check_multi  # noqa: F401

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "ts_prove_multi_bus", "ts_verify_multi_bus", "ts_logup_aux_build_multi", "ts_logup_multiplicities_bus",
     "ts_multi_key_commit", "ts_multi_key_info", "ts_multi_key_values", "ts_multi_key_free",
     "ts_prove_multi_key", "ts_verify_multi_key", "ts_logup_aux_build_multi_pre", "ts_logup_multiplicities_bus_pre",
+    "ts_bus_check", "ts_check_multi",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -173,6 +174,20 @@ class MultiBusTableC(C.Structure):
     """``ts_multi_bus_table``: one table of ``ts_prove_multi_bus``."""
     _fields_ = [("struct_size", C.c_uint32), ("n_public", C.c_uint32), ("air", C.c_void_p), ("trace", C.c_void_p),
                 ("public_values", C.POINTER(C.c_uint32)), ("logup", C.POINTER(LogupSpecC))]
+
+
+class BusShareC(C.Structure):
+    """``ts_bus_share``: one table's part of the tuple a ``ts_bus_report`` names."""
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_uint32), ("first_row", C.c_uint32),
+                ("first_interaction", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class BusReportC(C.Structure):
+    """``ts_bus_report`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_uint32), ("n_contributions", C.c_uint64),
+                ("n_tuples", C.c_uint64), ("n_unbalanced", C.c_uint64), ("first_table", C.c_uint32),
+                ("first_row", C.c_uint32), ("first_interaction", C.c_uint32), ("n_values", C.c_uint32),
+                ("tuple", C.c_uint32 * 8), ("sum", C.c_uint32), ("pad2", C.c_uint32)]
 
 
 class BatchLookupItemC(C.Structure):
@@ -414,6 +429,11 @@ def lib() -> C.CDLL:
         l.ts_logup_aux_build_multi_pre.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LogupSpecC)),
                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u32p,
                                                    C.POINTER(C.c_void_p), u32p]
+        l.ts_bus_check.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LogupSpecC)), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_void_p), C.POINTER(BusReportC), C.POINTER(BusShareC)]
+        l.ts_check_multi.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MultiBusTableC), C.c_uint32, u32p,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(BusReportC),
+                                     C.POINTER(BusShareC)]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

@@ -541,6 +541,91 @@ def logup_build_multi(logups, traces, challenges, preprocessed=None):
     return [DeviceMatrix(ctx, C.c_void_p(h)) for h in out], exposed
 
 
+class BusShare:
+    """``ts_bus_share``: one table's part of the tuple a :class:`BusReport` names -- the number of its contributions,
+    their multiplicity sum mod p and the least ``(row, interaction)`` among them (``first`` is None without any)."""
+
+    __slots__ = ("count", "sum", "first")
+
+    def __init__(self, count: int, sum_: int, first):
+        self.count, self.sum, self.first = int(count), int(sum_), first
+
+    def astuple(self):
+        return (self.count, self.sum, self.first)
+
+    def __eq__(self, other):
+        return self.astuple() == (other.astuple() if isinstance(other, BusShare) else tuple(other))
+
+    def __repr__(self):
+        return f"BusShare(count={self.count}, sum={self.sum}, first={self.first})"
+
+
+class BusReport:
+    """``ts_bus_report`` with its shares: ``n_contributions`` (table, row, interaction) triples of non-zero
+    multiplicity, ``n_tuples`` distinct zero-padded tuples among them, ``n_unbalanced`` of them whose multiplicities do
+    not sum to 0 mod p.  Unbalanced: ``first`` = (table, row, interaction) of the least contribution to any such tuple,
+    ``n_values`` and ``tuple`` (eight words) its tuple, ``sum`` that tuple's multiplicity sum; ``shares`` one
+    :class:`BusShare` per table.  Balanced: ``first`` is None, the rest zero and every share empty."""
+
+    __slots__ = ("n_contributions", "n_tuples", "n_unbalanced", "first", "n_values", "tuple", "sum", "shares")
+
+    def __init__(self, n_contributions, n_tuples, n_unbalanced, first, n_values, tuple_, sum_, shares):
+        self.n_contributions, self.n_tuples, self.n_unbalanced = int(n_contributions), int(n_tuples), int(n_unbalanced)
+        self.first, self.n_values, self.tuple, self.sum = first, int(n_values), [int(x) for x in tuple_], int(sum_)
+        self.shares = list(shares)
+
+    @property
+    def balanced(self) -> bool:
+        return self.n_unbalanced == 0
+
+    def asdict(self) -> dict:
+        d = {k: getattr(self, k) for k in self.__slots__}
+        d["shares"] = [s.astuple() for s in self.shares]
+        return d
+
+    def __eq__(self, other):
+        return isinstance(other, BusReport) and self.asdict() == other.asdict()
+
+    def __repr__(self):
+        return f"BusReport({self.asdict()})"
+
+    @classmethod
+    def _from_c(cls, rep, shares, n: int) -> "BusReport":
+        none = 0xFFFFFFFF
+        first = None if rep.n_unbalanced == 0 else (int(rep.first_table), int(rep.first_row), int(rep.first_interaction))
+        sh = [BusShare(s.count, s.sum, None if s.first_row == none and s.first_interaction == none
+                       else (int(s.first_row), int(s.first_interaction))) for s in shares[:n]]
+        return cls(rep.n_contributions, rep.n_tuples, rep.n_unbalanced, first, rep.n_values, list(rep.tuple), rep.sum, sh)
+
+
+def bus_check(logups, traces, preprocessed=None) -> BusReport:
+    """``ts_bus_check`` (include/tapstark.h, csrc/bus_check.hip): the exact balance of a LogUp bus from the resident
+    traces, before any challenge.  ``logups``: one :class:`LogUp` per table, or None for a table that is not on the bus;
+    ``traces``: the row-major ``DeviceMatrix`` of every table (not consumed; None is allowed beside a None LogUp);
+    ``preprocessed``: per table the matrix its ``("prep", c)`` terms read (``MultiKey.values(i)``) or None.  A tuple is
+    an interaction's values zero-padded to eight words; the bus balances iff every tuple's multiplicities sum to 0 mod
+    p over all tables, rows and interactions.  Returns a :class:`BusReport`."""
+    import ctypes as C
+    from . import _lib
+    n = len(logups)
+    if len(traces) != n or (preprocessed is not None and len(preprocessed) != n):
+        raise ValueError("bus_check: one trace (and one preprocessed matrix or None) per LogUp")
+    ctx = next((t.ctx for t in traces if t is not None), None)
+    if ctx is None:
+        raise ValueError("bus_check: no trace")
+    specs = [lg._spec_c() if lg is not None else None for lg in logups]
+    spec_ptrs = (C.POINTER(_lib.LogupSpecC) * max(n, 1))(*[C.pointer(sp[0]) if sp is not None else None for sp in specs])
+    handles = (C.c_void_p * max(n, 1))(*[t.h if t is not None else None for t in traces])
+    pre = None
+    if preprocessed is not None:
+        pre = (C.c_void_p * max(n, 1))(*[m.h if m is not None else None for m in preprocessed])
+    rep = _lib.BusReportC(struct_size=C.sizeof(_lib.BusReportC))
+    shares = (_lib.BusShareC * max(n, 1))()
+    ctx.check(ctx._l.ts_bus_check(ctx.h, n, spec_ptrs, pre, handles, C.byref(rep), shares))
+    del specs
+    return BusReport._from_c(rep, shares, n)
+
+
 def mult_bus_spec_c(table, lookers, out_column: int, negate: int = 1):
     """The ``ts_logup_mult_bus_spec`` of the arguments ``logup_multiplicities_bus`` takes, and the ctypes arrays it
     points into (keep the tuple alive while the spec is in use)."""

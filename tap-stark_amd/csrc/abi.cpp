@@ -2257,6 +2257,158 @@ ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_
     });
 }
 
+// ------------------------------------------------------------------ before you prove: the bus, exactly
+namespace {
+void reset_bus_report(ts_bus_report* report, ts_bus_share* shares, uint32_t n) {
+    const uint32_t size = report->struct_size;
+    memset(report, 0, sizeof *report);
+    report->struct_size = size;
+    report->first_table = report->first_row = report->first_interaction = ~0u;
+    if (shares)
+        for (uint32_t k = 0; k < n; k++) shares[k] = ts_bus_share{0, 0, ~0u, ~0u, 0};
+}
+// the refusals of ts_bus_check and ts_check_multi (`call`) that are made on the arguments alone, in this order, before
+// a context is looked at: the text, or empty
+std::string bus_report_refusal(const std::string& call, const ts_ctx* ctx, uint32_t n, const ts_bus_report* report) {
+    if (!report) return call + ": null report";
+    if (n < 1 || n > ts::LOGUP_MAX_TABLES) return call + ": between 1 and 64 tables";
+    if (!ctx) return call + ": null context";
+    if (report->struct_size != sizeof(ts_bus_report))
+        return call + ": ts_bus_report.struct_size is not sizeof(ts_bus_report)";
+    return "";
+}
+}  // namespace
+
+// The balance of a whole bus from the resident traces (bus_check.hip).
+ts_status ts_bus_check(ts_ctx* ctx, uint32_t n, const ts_logup_spec* const* specs, const ts_matrix* const* preprocessed,
+                       const ts_matrix* const* traces, ts_bus_report* report, ts_bus_share* shares) {
+    if (const std::string no = bus_report_refusal("ts_bus_check", ctx, n, report); !no.empty()) {
+        (ctx ? ctx->ctx.last_error : g_create_error) = no;
+        return TS_ERR_INVALID;
+    }
+    reset_bus_report(report, shares, n);
+    return guard(ctx, [&] {
+        TS_REQUIRE(specs && traces, ts::TS_ERR_INVALID, "ts_bus_check: null argument");
+        std::vector<ts::LogupSpec> loaded(n);
+        std::vector<const ts::LogupSpec*> sp(n, nullptr);
+        std::vector<const ts::DeviceMatrix*> tr(n, nullptr), pre(n, nullptr);
+        for (uint32_t k = 0; k < n; k++) {
+            if (!specs[k]) continue;
+            TS_REQUIRE(traces[k], ts::TS_ERR_INVALID, "ts_bus_check: null trace");
+            if (preprocessed && preprocessed[k]) pre[k] = &preprocessed[k]->m;
+            loaded[k] = load_logup_spec(specs[k]);
+            sp[k] = &loaded[k];
+            tr[k] = &traces[k]->m;
+        }
+        const ts::BusReport r = ts::bus_check(ctx->ctx, sp, tr, pre);
+        report->n_contributions = r.n_contributions;
+        report->n_tuples = r.n_tuples;
+        report->n_unbalanced = r.n_unbalanced;
+        report->first_table = r.first_table;
+        report->first_row = r.first_row;
+        report->first_interaction = r.first_interaction;
+        report->n_values = r.n_values;
+        memcpy(report->tuple, r.tuple, sizeof report->tuple);
+        report->sum = r.sum;
+        if (shares)
+            for (uint32_t k = 0; k < n; k++)
+                shares[k] = ts_bus_share{r.shares[k].count, r.shares[k].sum, r.shares[k].first_row,
+                                         r.shares[k].first_interaction, 0};
+    });
+}
+
+// The debug counterpart of ts_prove_multi_bus / ts_prove_multi_key: the builder, the per-table constraint check and
+// the bus check over traces that stay with their handles.
+ts_status ts_check_multi(ts_ctx* ctx, const ts_multi_key* key, const ts_multi_key_table* tables, uint32_t n_tables,
+                         const uint32_t challenges[8], int32_t* bad_table, int64_t* first_violation,
+                         ts_bus_report* report, ts_bus_share* shares) {
+    if (bad_table) *bad_table = -1;
+    if (first_violation) *first_violation = -1;
+    if (const std::string no = bus_report_refusal("ts_check_multi", ctx, n_tables, report); !no.empty()) {
+        (ctx ? ctx->ctx.last_error : g_create_error) = no;
+        return TS_ERR_INVALID;
+    }
+    reset_bus_report(report, shares, n_tables);
+    return guard(ctx, [&] {
+        const std::string call = "ts_check_multi";
+        TS_REQUIRE(tables && challenges && bad_table && first_violation, ts::TS_ERR_INVALID, call + ": null argument");
+        for (uint32_t t = 0; t < n_tables; t++) {
+            const ts_multi_key_table& mt = tables[t];
+            TS_REQUIRE(mt.struct_size == sizeof(ts_multi_bus_table), ts::TS_ERR_INVALID,
+                       call + ": ts_multi_bus_table.struct_size is not sizeof(ts_multi_bus_table)");
+            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, call + ": null AIR or trace");
+            TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
+                       call + ": an AIR was compiled on another context (or host-only)");
+            TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+            TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
+                       call + ": a trace was made on another context");
+            for (uint32_t k = 0; k < t; k++)
+                TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID, call + ": one trace handle in two tables");
+        }
+        std::vector<ts::MultiBusTable> mts(n_tables);
+        std::vector<ts::LogupSpec> specs(n_tables);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            mts[t].air = &ready_prog(tables[t].air);
+            mts[t].public_values = public_inputs(tables[t].public_values, tables[t].n_public);
+            mts[t].trace.width = tables[t].trace->m.width;
+            mts[t].trace.height = tables[t].trace->m.height;
+            mts[t].trace.layout = tables[t].trace->m.layout;
+            if (tables[t].logup) {
+                specs[t] = load_logup_spec(tables[t].logup);
+                mts[t].logup = &specs[t];
+            }
+        }
+        TS_REQUIRE(!key || key->k.ctx == &ctx->ctx, ts::TS_ERR_INVALID, call + ": the key was made on another context");
+        ts::check_multi_debug_statement(mts, key ? &key->k : nullptr);
+
+        // per table its key matrix (null without preprocessed columns); the aux tables and their builder arguments
+        std::vector<const ts_matrix*> pre(n_tables, nullptr), traces(n_tables, nullptr);
+        std::vector<const ts_logup_spec*> bus_specs(n_tables, nullptr);
+        std::vector<const ts_logup_spec*> a_specs;
+        std::vector<const ts_matrix*> a_pre, a_traces;
+        std::vector<int> aux_of(n_tables, -1);
+        size_t ki = 0;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            traces[t] = tables[t].trace;
+            if (mts[t].air->preprocessed_width) pre[t] = key->values[ki++].get();
+            if (!tables[t].logup) continue;
+            bus_specs[t] = tables[t].logup;
+            aux_of[t] = (int)a_specs.size();
+            a_specs.push_back(tables[t].logup);
+            a_pre.push_back(pre[t]);
+            a_traces.push_back(tables[t].trace);
+        }
+        auto passed = [&](ts_status st) {  // a call of this library on the same context: its text is the text
+            if (st != TS_OK) throw ts::Error(st, std::string(ctx->ctx.last_error));
+        };
+        const uint32_t n_aux = (uint32_t)a_specs.size();
+        std::vector<ts_matrix*> aux(n_aux, nullptr);
+        std::vector<uint32_t> exposed(4 * (size_t)n_aux);
+        struct FreeAux {
+            std::vector<ts_matrix*>& aux;
+            ~FreeAux() {
+                for (ts_matrix* m : aux) delete m;
+            }
+        } free_aux{aux};
+        if (n_aux)
+            passed(ts_logup_aux_build_multi_pre(ctx, n_aux, a_specs.data(), a_pre.data(), a_traces.data(), challenges,
+                                                aux.data(), exposed.data()));
+        for (uint32_t t = 0; t < n_tables; t++) {
+            const int a = aux_of[t];
+            int64_t fv = -1;
+            passed(ts_check_constraints_pre_aux(ctx, tables[t].air, pre[t], a >= 0 ? aux[a] : nullptr, tables[t].trace,
+                                                tables[t].public_values, tables[t].n_public, a >= 0 ? challenges : nullptr,
+                                                a >= 0 ? exposed.data() + 4 * (size_t)a : nullptr, &fv));
+            if (fv != -1) {
+                *bad_table = (int32_t)t;
+                *first_violation = fv;
+                break;
+            }
+        }
+        if (n_aux) passed(ts_bus_check(ctx, n_tables, bus_specs.data(), pre.data(), traces.data(), report, shares));
+    });
+}
+
 // Extends ts_prove_pre (the key: part of the statement, not consumed) and ts_prove_aux (the callback); TSPF v5.
 ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
                            const ts_pcs_data* key, ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,

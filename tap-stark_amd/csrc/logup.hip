@@ -359,6 +359,11 @@ static LogupDev logup_dev(Context& ctx, const LogupSpec& spec, const DeviceMatri
     return s;
 }
 
+void logup_check_spec(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace, const DeviceMatrix* table) {
+    const uint32_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    (void)logup_dev(ctx, spec, trace, no_challenges, table, /*takes_table=*/true);
+}
+
 DeviceMatrix logup_aux_build(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace,
                              const uint32_t challenges[8], uint32_t exposed[4], const DeviceMatrix* table,
                              bool takes_table) {

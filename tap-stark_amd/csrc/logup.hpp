@@ -143,6 +143,39 @@ LogupMultBusResult logup_multiplicities_bus(Context& ctx, const LogupMultBusSpec
                                             const std::vector<const DeviceMatrix*>& lookers,
                                             const DeviceMatrix* table_pre = nullptr, bool takes_pre = false);
 
+// ---- the exact balance of a whole bus, before any challenge (bus_check.hip)
+// The refusals logup_aux_build_multi makes with `tables` about one spec, its trace and its preprocessed table (null
+// without kind-2 terms), and nothing else: no allocation, no device work.
+void logup_check_spec(Context& ctx, const LogupSpec& spec, const DeviceMatrix& trace, const DeviceMatrix* table);
+constexpr uint64_t BUS_CHECK_MAX_CONTRIBUTIONS = 1ull << 30;  // sum over the tables of height * interactions
+struct BusShare {
+    uint64_t count = 0;                        // table k's contributions to the reported tuple
+    uint32_t sum = 0;                          // their multiplicity sum mod p
+    uint32_t first_row = ~0u, first_interaction = ~0u;  // the least (row, interaction) among them, ~0 without any
+};
+struct BusReport {
+    uint64_t n_contributions = 0;              // (table, row, interaction) whose multiplicity is non-zero mod p
+    uint64_t n_tuples = 0;                     // distinct zero-padded tuples among them
+    uint64_t n_unbalanced = 0;                 // tuples whose multiplicities do not sum to 0 mod p
+    uint32_t first_table = ~0u, first_row = ~0u, first_interaction = ~0u;  // the least contribution to any of those
+    uint32_t n_values = 0;                     // of that contribution's interaction
+    uint32_t tuple[LOGUP_MAX_VALUES] = {};     // its values, zero-padded
+    uint32_t sum = 0;                          // its tuple's multiplicity sum, canonical, non-zero
+    std::vector<BusShare> shares;              // one per table
+};
+// A hash join over the resident traces: for every distinct tuple (the value terms of an interaction, zero-padded to
+// eight words and compared as stored) the field sum of the multiplicities over all tables, rows and interactions.
+// specs[k] null: table k is not on the bus (its trace is not looked at).  `tables`: per spec the row-major values of
+// its preprocessed columns or null, as logup_aux_build_multi takes them.  Reads the traces only; every output is a
+// count, a minimum or an integer sum and the same on every run.  Throws TS_ERR_INVALID before any device work (what
+// logup_check_spec refuses for any k, a count outside 1 .. 64, no spec at all, more than 2^30 possible contributions);
+// synchronises the stream once, twice when the bus is unbalanced.
+BusReport bus_check(Context& ctx, const std::vector<const LogupSpec*>& specs,
+                    const std::vector<const DeviceMatrix*>& traces, const std::vector<const DeviceMatrix*>& tables);
+// the shape checks of check_multi_key_statement that need no FriConfig, for the debug counterpart of the bus proofs:
+// `key` is null exactly when no table has preprocessed columns
+void check_multi_debug_statement(const std::vector<MultiBusTable>& tables, const MultiKey* key);
+
 // ---- a lookup proof inside a batch lane (prover.cpp): no launch of its own
 // What a lookup argument says about an item's DATA, raised after the kernels finished normally: a zero denominator
 // reported by the builder, a lookup found in no table row.  The context is sound, so a lane goes on after one.

@@ -18,7 +18,7 @@
 //   k_mult_write   one table row per lane: sums[t] % p, or p minus it, into trace[t][out_column].
 // logup_multiplicities_bus (the lookups are rows of OTHER traces) launches k_mult_count_bus once per looker between
 // the same insert and write: k_mult_count with the looker's rows apart from the table's.
-// The hash is private to this file and changes no output; TS_LOGUP_HASH_BITS (0 .. 32, read on every call) masks
+// The hash (logup_hash.hpp, shared with bus_check.hip) changes no output; TS_LOGUP_HASH_BITS (0 .. 32, read on every call) masks
 // it to that many low bits before it is reduced to a slot: a test knob that makes probe chains as long as the table.
 // Contention: a wave whose hits all go to ONE representative (padding rows, a selector-heavy trace) sums their weights
 // with shuffles and issues one add; every other wave issues one add per hit (DESIGN.md has the measurement: a ballot
@@ -28,7 +28,7 @@
 
 #include <string>
 
-#include "logup.hpp"
+#include "logup_hash.hpp"
 
 namespace ts {
 
@@ -48,27 +48,6 @@ struct MultBack {
     uint32_t error, pad[3];
 };
 
-__device__ __forceinline__ uint32_t mult_term(uint32_t kind, uint32_t val, const uint32_t* __restrict__ row,
-                                              const uint32_t* __restrict__ pre_row) {
-    return kind == 0 ? val : (kind == 1 ? row : pre_row)[val];
-}
-
-struct MultTuple {
-    uint32_t v[LOGUP_MAX_VALUES];
-};
-
-__device__ __forceinline__ uint32_t mult_hash(const MultTuple& t, uint32_t nv) {
-    uint32_t h = 0x9E3779B9u;
-#pragma unroll
-    for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++)
-        if (q < (int)nv) {
-            h = (h ^ t.v[q]) * 0x85EBCA6Bu;
-            h ^= h >> 13;
-        }
-    h *= 0xC2B2AE35u;
-    return h ^ (h >> 16);
-}
-
 // the table's tuple on row t
 __device__ __forceinline__ MultTuple mult_table_tuple(const MultDev& s, const uint32_t* __restrict__ trace,
                                                       const uint32_t* __restrict__ pre, uint64_t t) {
@@ -79,13 +58,6 @@ __device__ __forceinline__ MultTuple mult_table_tuple(const MultDev& s, const ui
     for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++)
         out.v[q] = q < (int)s.n_values ? mult_term(s.t_kind[q], s.t_val[q], row, pre_row) : 0;
     return out;
-}
-
-__device__ __forceinline__ bool mult_equal(const MultTuple& a, const MultTuple& b) {
-    bool eq = true;  // (the words past n_values are zero on both sides)
-#pragma unroll
-    for (int q = 0; q < (int)LOGUP_MAX_VALUES; q++) eq = eq && a.v[q] == b.v[q];
-    return eq;
 }
 
 __global__ void __launch_bounds__(MULT_THREADS)
@@ -219,17 +191,6 @@ k_mult_write(uint32_t width, uint32_t out_column, uint32_t negate, uint64_t n,
     if (t >= n) return;
     const uint32_t v = (uint32_t)(sums[t] % P);
     trace[t * width + out_column] = negate && v ? P - v : v;
-}
-
-// an integer knob in [lo, hi], or `unset`
-static long mult_knob(const char* name, long lo, long hi, long unset) {
-    const char* e = getenv(name);
-    if (!e || !*e) return unset;
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    TS_REQUIRE(end && !*end && v >= lo && v <= hi, TS_ERR_INVALID,
-               (std::string(name) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]").c_str());
-    return v;
 }
 
 LogupMultResult logup_multiplicities(Context& ctx, const LogupMultSpec& spec, DeviceMatrix& trace,

@@ -388,6 +388,41 @@ void check_multi_key_statement(const FriConfig& fri, const std::vector<MultiBusT
                "prove_multi_key: more than 64 quotient chunks over all tables (the limit of one committed batch)");
 }
 
+void check_multi_debug_statement(const std::vector<MultiBusTable>& tables, const MultiKey* key) {
+    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
+               "check_multi: between 1 and 64 tables");
+    size_t n_pre = 0;
+    for (const MultiBusTable& t : tables) {
+        TS_REQUIRE(t.air, TS_ERR_INVALID, "check_multi: null AIR");
+        n_pre += t.air->preprocessed_width ? 1 : 0;
+    }
+    TS_REQUIRE((key != nullptr) == (n_pre > 0), TS_ERR_INVALID,
+               n_pre ? "check_multi: a null key and a table with preprocessed columns"
+                     : "check_multi: a key was given and no table has preprocessed columns");
+    if (key) {
+        TS_REQUIRE(key->data && key->heights.size() == n_pre, TS_ERR_INVALID,
+                   "check_multi: the key holds " + std::to_string(key->heights.size()) + " matrices and " +
+                       std::to_string(n_pre) + " tables have preprocessed columns");
+    }
+    size_t ki = 0;
+    for (size_t k = 0; k < tables.size(); k++) {
+        const MultiBusTable& t = tables[k];
+        const std::string w = "check_multi: table " + std::to_string(k);
+        const uint32_t pw = t.air->preprocessed_width;
+        TS_REQUIRE(t.trace.width == t.air->width, TS_ERR_INVALID, w + ": the trace has not the AIR's width");
+        TS_REQUIRE(t.public_values.size() == t.air->n_public, TS_ERR_INVALID, w + ": wrong number of public values");
+        if (pw) {
+            TS_REQUIRE(key->heights[ki] == t.trace.height && key->widths[ki] == pw, TS_ERR_INVALID,
+                       w + ": key matrix " + std::to_string(ki) + " has not the table's height and the AIR's preprocessed width");
+            // (the constraint check reads the rows of every key matrix, the builder those a spec names)
+            TS_REQUIRE(key->values[ki], TS_ERR_INVALID, w + ": the key was made without keep_values");
+        }
+        check_bus_table(t, w, pw);
+        TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID, w + ": the trace must be row-major");
+        ki += pw ? 1 : 0;
+    }
+}
+
 // One body for TSPF v7 (key == nullptr: at least one aux table, no preprocessed columns) and TSPF v8 (a key; the
 // challenge phase only if some table has aux columns).  The statement has been checked.
 static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger& challenger,

@@ -1565,6 +1565,47 @@ def verify_multi_key(config: StarkConfig, key_root, airs, challenger: BfChalleng
     return exposed[: 4 * n_aux], bus_sum
 
 
+def check_multi(key, airs, traces, public_values, logups, challenges, ctx: Context | None = None):
+    """``ts_check_multi``: the debug counterpart of ``prove_multi_bus`` / ``prove_multi_key``, to be run before them.
+    ``key``: the :class:`MultiKey` (with kept values) or None when no AIR has preprocessed columns; ``traces`` are NOT
+    consumed (arrays are uploaded to ``ctx``); ``challenges``: any gamma and beta, eight canonical words.  Builds the
+    LogUp columns, checks every table's constraints in order and then the exact balance of the bus.  Returns
+    ``(bad_table, first_violation, report)``: the first table with a violated constraint and what
+    ``check_constraints`` gives for it (both -1 when all hold), and the :class:`~tapstark_amd.air.BusReport` of
+    ``bus_check``."""
+    from .air import BusReport
+    T = len(airs)
+    if len(traces) != T or len(public_values) != T or len(logups) != T:
+        raise ValueError("check_multi: one trace, one public-value list and one LogUp (or None) per AIR")
+    if ctx is None:
+        ctx = key.ctx if key is not None else next((t.ctx for t in traces if isinstance(t, DeviceMatrix)), None)
+    ctx = ctx or default_context()
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
+    tabs = (_lib.MultiBusTableC * max(T, 1))()
+    keep = []
+    for k in range(T):
+        tabs[k].struct_size = C.sizeof(_lib.MultiBusTableC)
+        tabs[k].n_public = len(pis[k])
+        tabs[k].air = airs[k].h
+        tabs[k].trace = traces[k].h
+        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
+        if logups[k] is not None:
+            keep.append(logups[k]._spec_c())
+            tabs[k].logup = C.pointer(keep[-1][0])
+    ch = _u32(challenges).reshape(-1)
+    if len(ch) != 8:
+        raise ValueError("check_multi: two challenges (eight words)")
+    bad, fv = C.c_int32(-1), C.c_int64(-1)
+    rep = _lib.BusReportC(struct_size=C.sizeof(_lib.BusReportC))
+    shares = (_lib.BusShareC * max(T, 1))()
+    ctx.check(ctx._l.ts_check_multi(ctx.h, key.h if key is not None else None, tabs, T, _p(ch), C.byref(bad),
+                                    C.byref(fv), C.byref(rep), shares))
+    del keep
+    return int(bad.value), int(fv.value), BusReport._from_c(rep, shares, T)
+
+
 def prove_stream(lanes, traces, lane_of, public_values, gate_ms: float = 0.0, want_times: bool = True):
     """``ts_prove_stream``: ``len(traces)`` independent proofs on the contexts of ``lanes`` = [(StarkConfig,
     CompiledAir), ...] (one context each, same device, same FriConfig), one host thread per lane INSIDE the
