@@ -226,6 +226,20 @@ pub struct ts_bus_report {
     pub pad2: u32,
 }
 
+/// `ts_sort_spec`: the keys of `ts_matrix_sort_rows` (most significant first), the leading keys that define a group,
+/// the appended columns (bit 0: source row, bit 1: group start) and the rows that are sorted.  Like the rest of this
+/// file the declaration has not been compiled: there is no Rust toolchain where the library is built.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_sort_spec {
+    pub struct_size: u32, // = size_of::<ts_sort_spec>()
+    pub n_keys: u32,
+    pub key_columns: [u32; 4],
+    pub group_keys: u32,
+    pub flags: u32,
+    pub n_live: u64,
+}
+
 /// One statement of `ts_prove_batch_lookup`: `ts_batch_item`'s inputs, the aux source (exactly one of `logup` /
 /// `aux_fn` for an AIR with aux columns), the multiplicity fills, then what the library writes back.
 #[repr(C)]
@@ -483,6 +497,12 @@ extern "C" {
     pub fn ts_check_multi(ctx: *mut ts_ctx, key: *const ts_multi_key, tables: *const ts_multi_bus_table, n_tables: u32,
                           challenges: *const u32, bad_table: *mut i32, first_violation: *mut i64,
                           report: *mut ts_bus_report, shares: *mut ts_bus_share) -> ts_status;
+    /// the rows of a resident matrix in the stable order of up to four key columns; `src` is only read
+    pub fn ts_matrix_sort_rows(ctx: *mut ts_ctx, spec: *const ts_sort_spec, src: *const ts_matrix,
+                               out: *mut *mut ts_matrix) -> ts_status;
+    /// out[i] = src[index[i][index_column]]: the sort's last kernel over a caller's index
+    pub fn ts_matrix_gather_rows(ctx: *mut ts_ctx, src: *const ts_matrix, index: *const ts_matrix, index_column: u32,
+                                 out: *mut *mut ts_matrix) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

@@ -1309,6 +1309,51 @@ ts_status ts_check_multi(ts_ctx* ctx, const ts_multi_key* key, const ts_multi_ke
                          const uint32_t challenges[8], int32_t* bad_table, int64_t* first_violation,
                          ts_bus_report* report, ts_bus_share* shares);
 
+/* ---- rows in sorted order: a memory table, or any table whose constraints compare neighbours of a sorted order ----
+ * ts_logup_multiplicities closed the host round trip for multiplicity columns; these two close it for ROW ORDER.  They
+ * replace: ts_matrix_download, a stable host sort (np.lexsort), indexing, ts_matrix_upload.
+ * ts_matrix_sort_rows: `src` is row-major, on ctx, neither consumed nor written.  *out is a new row-major matrix of
+ * src's height and of src's width plus one column per set flag bit, the source-row column first, then group-start.
+ *   Order: the rows [0, n_live) are ordered lexicographically by the words of key_columns AS STORED, compared as
+ *   unsigned 32-bit words (a non-canonical word is not reduced: as the multiplicity calls compare words).  The sort is
+ *   STABLE -- rows with equal keys keep their source order --, so the result is unique and the same on every run.  Rows
+ *   [n_live, height) keep place and content.  n_live == 0 is a plain copy.
+ *   Source-row column: the row of src that the output row came from (its own index at or beyond n_live).
+ *   Group-start column: 1 on live row i if i == 0 or if one of its first group_keys key words differs from those of
+ *   live row i - 1; 0 on every other row, every row at or beyond n_live included.  With group_keys == 0 it is 1 on
+ *   live row 0 only.
+ * TS_ERR_INVALID, each with a text in ts_last_error, before any device work: a NULL argument; struct_size; n_keys
+ * outside 1 .. 4; a key column outside src; a key column named twice; group_keys > n_keys; a flag bit above 1;
+ * n_live > height; a matrix that is not row-major, is consumed or belongs to another context; a height outside
+ * [1, 2^27] (any value inside is taken, not only powers of two); an output wider than 2^16 columns, the widest matrix
+ * these calls make; TS_SORT_BLOCK_ROWS outside [1, 2048].
+ * Launches: one histogram over the live rows for all 4 * n_keys byte digits and ONE copy back of its table -- the
+ * call's only host wait (none with n_live < 2) --; then per byte digit that moves anything (a digit on which every
+ * live row agrees is skipped: canonical words never fill more than two bins of the top byte, 16-bit addresses skip
+ * two passes of four) one count, one, three or five scan launches and one scatter of a uint32 row permutation with
+ * the key word carried beside it, plus one key load per key column that has such a pass; one gather.  Temporaries
+ * come from ctx's pool.
+ * TS_SORT_BLOCK_ROWS (1 .. 2048, read on every call; a test knob): the positions one workgroup owns; the matrix is the
+ * same for every value. */
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(ts_sort_spec), else TS_ERR_INVALID */
+    uint32_t n_keys;           /* 1 .. 4 */
+    uint32_t key_columns[4];   /* most significant first; columns of src; no column twice */
+    uint32_t group_keys;       /* 0 .. n_keys: the leading keys that define a group (see flags) */
+    uint32_t flags;            /* bit 0: append a source-row column; bit 1: append a group-start column */
+    uint64_t n_live;           /* rows [0, n_live) are sorted; rows [n_live, height) keep place and content */
+} ts_sort_spec;
+enum { TS_SORT_SOURCE_ROW = 1, TS_SORT_GROUP_START = 2 };
+ts_status ts_matrix_sort_rows(ts_ctx* ctx, const ts_sort_spec* spec, const ts_matrix* src, ts_matrix** out);
+/* out[i] = src[index[i][index_column]]: the sort's own last kernel over a caller's index, so that the source-row
+ * column of a narrow key matrix reorders a wide payload matrix.  *out has index's height and src's width; both inputs
+ * are row-major, on ctx, read and not consumed.  TS_ERR_INVALID before any device work: a NULL argument, a matrix as
+ * ts_matrix_sort_rows refuses it, index_column outside index, src wider than 2^16 columns.  An index word >= src's
+ * height is TS_ERR_INVALID "gather: row index r at row i outside the source" for the least such i (recorded by the
+ * kernel with a 64-bit integer minimum), and there is no output.  One launch, one copy back. */
+ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matrix* index, uint32_t index_column,
+                                ts_matrix** out);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

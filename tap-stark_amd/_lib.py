@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "ts_multi_key_commit", "ts_multi_key_info", "ts_multi_key_values", "ts_multi_key_free",
     "ts_prove_multi_key", "ts_verify_multi_key", "ts_logup_aux_build_multi_pre", "ts_logup_multiplicities_bus_pre",
     "ts_bus_check", "ts_check_multi",
+    "ts_matrix_sort_rows", "ts_matrix_gather_rows",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -188,6 +189,12 @@ class BusReportC(C.Structure):
                 ("n_tuples", C.c_uint64), ("n_unbalanced", C.c_uint64), ("first_table", C.c_uint32),
                 ("first_row", C.c_uint32), ("first_interaction", C.c_uint32), ("n_values", C.c_uint32),
                 ("tuple", C.c_uint32 * 8), ("sum", C.c_uint32), ("pad2", C.c_uint32)]
+
+
+class SortSpecC(C.Structure):
+    """``ts_sort_spec`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_keys", C.c_uint32), ("key_columns", C.c_uint32 * 4),
+                ("group_keys", C.c_uint32), ("flags", C.c_uint32), ("n_live", C.c_uint64)]
 
 
 class BatchLookupItemC(C.Structure):
@@ -434,6 +441,8 @@ def lib() -> C.CDLL:
         l.ts_check_multi.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MultiBusTableC), C.c_uint32, u32p,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(BusReportC),
                                      C.POINTER(BusShareC)]
+        l.ts_matrix_sort_rows.argtypes = [C.c_void_p, C.POINTER(SortSpecC), C.c_void_p, voidpp]
+        l.ts_matrix_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, voidpp]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

@@ -1007,3 +1007,160 @@ def fill_bus_key_multiplicities(table_trace, key_values, sender_traces, n_values
                         [("col", s * i + n_values) for i in range(k)]))
     return logup_multiplicities_bus(table_trace, [("prep", j) for j in range(n_values)], lookers, out_column=0, negate=1,
                                     allow_missing=allow_missing, table_preprocessed=key_values)
+
+
+# ---------------------------------------------------------------------------------------------- a memory table on the bus
+# Two tables of a multi-table proof that hold the same accesses in two orders: MemoryAccessAir in execution order,
+# MemoryTableAir sorted by (addr, clk) -- made in HBM with ``DeviceMatrix.sort_rows`` -- where "a read returns the last
+# write" is a constraint between neighbouring rows.  The bus ties the two; a range check of ``gap`` (an existing
+# BusRangeAir) is what makes "sorted" a proved statement.
+
+MEM_TAG = 11
+
+
+class MemoryAccessAir(BaseAir):
+    """Main columns (addr, clk, value, is_write, sel): ``sel`` and ``is_write`` boolean, first row ``clk = 0``,
+    ``next.clk = clk + 1``; the row sends (MEM_TAG, addr, clk, value, is_write) with multiplicity ``sel``
+    (BusTupleSendAir's interaction with the clock pinned).  Constraint degree 3."""
+
+    ADDR, CLK, VALUE, IS_WRITE, SEL = range(5)
+    logup = LogUp([(("col", 4), [("const", MEM_TAG), ("col", 0), ("col", 1), ("col", 2), ("col", 3)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 5
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        sel, is_write = local[self.SEL], local[self.IS_WRITE]
+        builder.assert_zero(sel * (sel - 1))
+        builder.assert_zero(is_write * (is_write - 1))
+        builder.when_first_row().assert_zero(local[self.CLK])
+        builder.when_transition().assert_eq(nxt[self.CLK], local[self.CLK] + 1)
+        # implied by the first line; constraint degree 3, as every bus AIR (see BusSendAir)
+        builder.assert_zero(local[self.ADDR] * sel * (sel - 1))
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+class MemoryTableAir(BaseAir):
+    """Main columns (addr, clk, value, is_write, live, recv, gap, start): the accesses sorted by (addr, clk), the live
+    rows first.  ``start`` is the group-start column ``sort_rows`` appends (the first access of an address), which is
+    why it stands last; ``live``, ``recv`` and ``gap`` are the caller's.  With ``cont = live - start``:
+
+    * ``live``, ``start``, ``is_write`` boolean; ``start (1 - live) = 0``; ``recv + live = 0``; first row ``cont = 0``;
+    * dead rows stay dead: ``(1 - live) next.live = 0`` on transitions;
+    * on transitions ``next.cont (next.addr - addr) = 0``; a read returns the last value:
+      ``next.cont (1 - next.is_write) (next.value - value) = 0``;
+    * the first access of an address is a write: ``start (1 - is_write) = 0``;
+    * on transitions ``next.start (next.addr - addr - 1 - next.gap) + next.cont (next.clk - clk - 1 - next.gap) = 0``.
+
+    The row receives (MEM_TAG, addr, clk, value, is_write) with multiplicity ``recv`` and sends (BUS_TAG, gap) with
+    multiplicity ``live`` to a BusRangeAir: addresses strictly ascend from group to group and clocks inside a group
+    because every ``gap`` is in the range table.  Constraint degree 3."""
+
+    ADDR, CLK, VALUE, IS_WRITE, LIVE, RECV, GAP, START = range(8)
+    logup = LogUp([(("col", 5), [("const", MEM_TAG), ("col", 0), ("col", 1), ("col", 2), ("col", 3)]),
+                   (("col", 4), [("const", BUS_TAG), ("col", 6)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 8
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        live, start, is_write = local[self.LIVE], local[self.START], local[self.IS_WRITE]
+        cont_next = nxt[self.LIVE] - nxt[self.START]
+        for b in (live, start, is_write):
+            builder.assert_zero(b * (b - 1))
+        builder.assert_zero(start * (1 - live))
+        builder.assert_zero(local[self.RECV] + live)
+        builder.when_first_row().assert_zero(live - start)
+        builder.assert_zero(start * (1 - is_write))
+        t = builder.when_transition()
+        t.assert_zero((1 - live) * nxt[self.LIVE])
+        t.assert_zero(cont_next * (nxt[self.ADDR] - local[self.ADDR]))
+        t.assert_zero(cont_next * (1 - nxt[self.IS_WRITE]) * (nxt[self.VALUE] - local[self.VALUE]))
+        t.assert_zero(nxt[self.START] * (nxt[self.ADDR] - local[self.ADDR] - 1 - nxt[self.GAP])
+                      + cont_next * (nxt[self.CLK] - local[self.CLK] - 1 - nxt[self.GAP]))
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+def generate_memory_accesses(n: int, n_addr: int, seed: int = SPLITMIX_SEED, n_selected: int | None = None) -> np.ndarray:
+    """(n, 5) canonical u32 satisfying MemoryAccessAir: a simulated memory over ``n_addr`` addresses driven by a
+    SplitMix64 stream.  Row r is the access at clock r; a read returns the last value written to its address and the
+    first access of every address is a write.  The first ``n_selected`` rows (default: all) have ``sel = 1``; the
+    others are padding that is not sent."""
+    n_selected = n if n_selected is None else n_selected
+    r = splitmix64_stream(seed, 3 * n).reshape(n, 3).astype(np.uint64)
+    out = np.zeros((n, 5), dtype=np.uint32)
+    out[:, 1] = np.arange(n)
+    memory = {}
+    for i in range(n):
+        addr = int(r[i, 0] % np.uint64(n_addr))
+        write = bool((int(r[i, 1]) >> 17) & 1) or addr not in memory
+        if write and i < n_selected:
+            memory[addr] = int(r[i, 2])
+        out[i, 0], out[i, 3] = addr, write
+        out[i, 2] = int(r[i, 2]) if write else memory[addr]
+        out[i, 4] = i < n_selected
+    return out
+
+
+def memory_table_source(accesses: np.ndarray) -> tuple[np.ndarray, int]:
+    """((n, 7) canonical u32, n_live): what ``sort_rows(keys=[0, 1], group_keys=1, n_live=n_live, group_start=True)``
+    turns into a MemoryTableAir trace but for ``gap``: columns (addr, clk, value, is_write, live, recv, gap = 0) of the
+    accesses, whose selected rows must come first."""
+    a = np.asarray(accesses, dtype=np.uint32)
+    sel = a[:, 4].astype(np.int64)
+    n_live = int(sel.sum())
+    if not (sel[:n_live] == 1).all():
+        raise ValueError("memory_table_source: the selected accesses must be the first rows")
+    out = np.zeros((a.shape[0], 7), dtype=np.uint32)
+    out[:, :4] = a[:, :4]
+    out[:, 4] = sel
+    out[:, 5] = (P - sel) % P
+    return out, n_live
+
+
+def fill_memory_gaps(table: np.ndarray) -> np.ndarray:
+    """The downloaded sorted table with ``gap`` filled on the host (the library does not compute derived arithmetic
+    columns): on live row i >= 1 the address step minus one where a group starts, the clock step minus one inside a
+    group, mod p; 0 on row 0 and on dead rows.  A table that is not sorted gets a gap near p, outside any range table."""
+    t = np.array(table, dtype=np.uint32)
+    A = MemoryTableAir
+    cur, prev = t[1:].astype(np.int64), t[:-1].astype(np.int64)
+    step = np.where(cur[:, A.START] == 1, cur[:, A.ADDR] - prev[:, A.ADDR], cur[:, A.CLK] - prev[:, A.CLK]) - 1
+    t[:, A.GAP] = 0
+    t[1:, A.GAP] = np.where(cur[:, A.LIVE] == 1, step % P, 0)
+    return t
+
+
+def generate_memory_table(accesses: np.ndarray) -> np.ndarray:
+    """(n, 8) canonical u32 satisfying MemoryTableAir, all on the host (``np.lexsort``): what the device route --
+    ``memory_table_source``, ``sort_rows``, ``fill_memory_gaps`` -- gives."""
+    src, n_live = memory_table_source(accesses)
+    order = np.arange(src.shape[0])
+    order[:n_live] = np.lexsort((src[:n_live, 1], src[:n_live, 0]))
+    t = np.zeros((src.shape[0], 8), dtype=np.uint32)
+    t[:, :7] = src[order]
+    t[0, 7] = n_live > 0
+    if n_live > 1:
+        t[1:n_live, 7] = t[1:n_live, 0] != t[:n_live - 1, 0]
+    return fill_memory_gaps(t)
+
+
+def fill_memory_range_multiplicities(range_trace, memory_table, allow_missing: bool = False):
+    """Fills column 1 of a resident BusRangeAir trace in HBM from the ``gap`` column of a resident MemoryTableAir trace
+    (weight ``live``).  Returns what ``logup_multiplicities_bus`` returns."""
+    from .air import logup_multiplicities_bus
+    A = MemoryTableAir
+    return logup_multiplicities_bus(range_trace, [("col", 0)], [(memory_table, [[("col", A.GAP)]], [("col", A.LIVE)])],
+                                    out_column=1, negate=1, allow_missing=allow_missing)

@@ -17,6 +17,7 @@
 #include "jit.hpp"
 #include "logup.hpp"
 #include "prover_internal.hpp"
+#include "sort.hpp"
 
 // the program as the prover sees it; the handle is const in the prove calls, adopting a finished specialisation is not
 static const ts::AirProgram& ready_prog(const ts_air* air) { return const_cast<ts_air*>(air)->a.ready(); }
@@ -1946,6 +1947,44 @@ ts_status ts_logup_multiplicities_bus_pre(ts_ctx* ctx, const ts_logup_mult_bus_s
                                           const ts_matrix* const* lookers, uint64_t* n_missing,
                                           uint64_t first_missing[3]) {
     return mult_bus(ctx, spec, table_preprocessed, true, table_trace, lookers, n_missing, first_missing);
+}
+
+// The rows of a resident matrix in sorted order, and rows gathered through an index column (sort.hip).
+ts_status ts_matrix_sort_rows(ts_ctx* ctx, const ts_sort_spec* spec, const ts_matrix* src, ts_matrix** out) {
+    if (out) *out = nullptr;
+    if (!ctx) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(spec && src && out, ts::TS_ERR_INVALID, "ts_matrix_sort_rows: null argument");
+        TS_REQUIRE(spec->struct_size == sizeof(ts_sort_spec), ts::TS_ERR_INVALID, "sort rows: bad struct_size");
+        TS_REQUIRE(spec->n_keys >= 1 && spec->n_keys <= ts::SORT_MAX_KEYS, ts::TS_ERR_INVALID,
+                   "sort rows: between 1 and 4 keys");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        ts::SortSpec s;
+        s.key_columns.assign(spec->key_columns, spec->key_columns + spec->n_keys);
+        s.group_keys = spec->group_keys;
+        s.flags = spec->flags;
+        s.n_live = spec->n_live;
+        auto m = std::make_unique<ts_matrix>();
+        m->m = ts::sort_rows(ctx->ctx, s, src->m);
+        *out = m.release();
+    });
+}
+
+ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matrix* index, uint32_t index_column,
+                                ts_matrix** out) {
+    if (out) *out = nullptr;
+    if (!ctx) return TS_ERR_INVALID;
+    if (!src || !index || !out) {
+        ctx->ctx.last_error = "ts_matrix_gather_rows: null argument";
+        return TS_ERR_INVALID;
+    }
+    return guard(ctx, [&] {
+        auto m = std::make_unique<ts_matrix>();
+        m->m = ts::gather_rows(ctx->ctx, src->m, index->m, index_column);
+        *out = m.release();
+    });
 }
 
 // The LogUp columns of n traces for one set of challenges, in three launches (logup.hip logup_aux_build_multi).

@@ -351,6 +351,30 @@ class DeviceMatrix:
         self.ctx.check(self.ctx._l.ts_matrix_bit_reverse_rows(self.ctx.h, self.h, C.byref(h)))
         return DeviceMatrix(self.ctx, h)
 
+    def sort_rows(self, keys, group_keys: int = 0, n_live: int | None = None, source_row: bool = False,
+                  group_start: bool = False) -> "DeviceMatrix":
+        """A new matrix with rows [0, n_live) in the stable order of the key columns ``keys`` (most significant
+        first; words compared as stored, unsigned), the others in place; ``source_row`` and ``group_start`` append
+        a column each, in that order (``ts_matrix_sort_rows``).  This matrix is only read."""
+        keys = [int(k) for k in keys]
+        spec = _lib.SortSpecC()
+        spec.struct_size = C.sizeof(_lib.SortSpecC)
+        spec.n_keys = len(keys)
+        for q, k in enumerate(keys[:4]):
+            spec.key_columns[q] = k
+        spec.group_keys = group_keys
+        spec.flags = (1 if source_row else 0) | (2 if group_start else 0)
+        spec.n_live = self.dims()[0] if n_live is None else n_live
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_matrix_sort_rows(self.ctx.h, C.byref(spec), self.h, C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
+
+    def gather_rows(self, index: "DeviceMatrix", column: int = 0) -> "DeviceMatrix":
+        """``out[i] = self[index[i][column]]`` as a new matrix of ``index``'s height (``ts_matrix_gather_rows``)."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_matrix_gather_rows(self.ctx.h, self.h, index.h, column, C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
+
     def device_ptr(self) -> int:
         """Row-major device pointer (``ts_matrix_device_ptr``): valid until the matrix is freed or consumed,
         ordered on the context's stream; ``from_device_ptr`` is the opposite direction."""
