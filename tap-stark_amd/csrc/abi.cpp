@@ -1301,72 +1301,6 @@ ts_status ts_prove_pre(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
     });
 }
 
-// ------------------------------------------------------------------ prove_multi
-// Several plain AIR tables of mixed heights in one proof (prove_multi.cpp).  Every refusal is made before the
-// first trace is taken.
-ts_status ts_prove_multi(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_table* tables,
-                         uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
-    if (!ctx) return TS_ERR_INVALID;
-    if (n_words_out) *n_words_out = 0;
-    return guard(ctx, [&] {
-        TS_REQUIRE(cfg && chal && tables && proof_out && n_words_out, ts::TS_ERR_INVALID, "ts_prove_multi: null argument");
-        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
-                   "ts_prove_multi: between 1 and 64 tables");
-        const ts::FriConfig fri = load_cfg(cfg);
-        for (uint32_t t = 0; t < n_tables; t++) {
-            const ts_multi_table& mt = tables[t];
-            TS_REQUIRE(mt.struct_size == sizeof(ts_multi_table), ts::TS_ERR_INVALID,
-                       "ts_prove_multi: ts_multi_table.struct_size is not sizeof(ts_multi_table)");
-            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, "ts_prove_multi: null AIR or trace");
-            TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
-                       "ts_prove_multi: an AIR was compiled on another context (or host-only)");
-            TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
-            TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
-                       "ts_prove_multi: a trace was made on another context");
-            for (uint32_t k = 0; k < t; k++)
-                TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID,
-                           "ts_prove_multi: one trace handle in two tables");
-        }
-        // the statement's own refusals (widths, public values, UNSUPPORTED columns, lqd, the chunk count) on
-        // shapes alone: the matrices stay with their handles until all of it holds
-        std::vector<ts::MultiTable> mts(n_tables);
-        for (uint32_t t = 0; t < n_tables; t++) {
-            mts[t].air = &ready_prog(tables[t].air);
-            mts[t].public_values = public_inputs(tables[t].public_values, tables[t].n_public);
-            mts[t].trace.width = tables[t].trace->m.width;
-            mts[t].trace.height = tables[t].trace->m.height;
-        }
-        ts::check_multi_statement(fri, mts);
-        ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
-        for (uint32_t t = 0; t < n_tables; t++) mts[t].trace = take_trace(tables[t].trace);
-        ts::StageTimer timer(&ctx->ctx, "prove");
-        copy_proof(ts::prove_multi(pcs, chal->c, mts), proof_out, cap_words, n_words_out);
-    });
-}
-
-ts_status ts_verify_multi(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
-                          const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,
-                          size_t n_words, int* verdict) {
-    if (verdict) *verdict = -1;
-    return guard(nullptr, [&] {
-        TS_REQUIRE(cfg && chal && airs && public_values && n_public && proof && verdict, ts::TS_ERR_INVALID,
-                   "ts_verify_multi: null argument");
-        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
-                   "ts_verify_multi: between 1 and 64 tables");
-        const ts::FriConfig fri = load_cfg(cfg);
-        std::vector<const ts::AirProgram*> progs(n_tables);
-        std::vector<std::vector<uint32_t>> pis(n_tables);
-        for (uint32_t t = 0; t < n_tables; t++) {
-            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, "ts_verify_multi: null AIR");
-            if (airs[t]->a.prog().preprocessed_width || airs[t]->a.prog().aux_width)
-                throw ts::Error(ts::TS_ERR_UNSUPPORTED, "ts_verify_multi: a table's AIR has preprocessed or aux columns");
-            progs[t] = &airs[t]->a.prog();
-            pis[t] = public_inputs(public_values[t], n_public[t]);
-        }
-        *verdict = ts::verify_multi(fri, chal->c, progs, pis, proof, n_words);
-    }, false);
-}
-
 // ------------------------------------------------------------------ prove_stream
 // Throughput mode as ONE call: n_proofs independent proofs of one AIR on `n_lanes` contexts of a device, one
 // host thread per lane INSIDE the call (examples/prove_stream.cpp as an entry point).  Proofs are independent
@@ -2037,69 +1971,175 @@ ts_status ts_logup_aux_build_multi_pre(ts_ctx* ctx, uint32_t n, const ts_logup_s
                            exposed_out);
 }
 
-// ------------------------------------------------------------------ prove_multi_bus
-// ts_prove_multi with LogUp aux columns on a bus across the tables (prove_multi.cpp).  Every refusal is made before
-// the first trace is taken.
+// ------------------------------------------------------------------ prove_multi, prove_multi_bus, prove_multi_key
+// Several AIR tables of mixed heights in one proof (prove_multi.cpp): plain ones (TSPF v6), with LogUp aux columns on
+// a bus across the tables (v7), against a commit-once key (v8).  Every refusal is made before the first trace is taken.
 namespace {
-// `key` null: ts_prove_multi_bus; else ts_prove_multi_key (`with_key`: which of the two is running, for a null key)
-ts_status prove_multi_phased(ts_ctx* ctx, const std::string& call, bool with_key, const ts_fri_config* cfg,
-                             ts_challenger* chal, const ts_multi_key* key, ts_multi_bus_table* tables, uint32_t n_tables,
-                             uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+// A table array of the C ABI, read as ts_multi_bus_table: ts_multi_table is that struct without its last field, logup.
+struct MultiTables {
+    const char* p;
+    size_t size;  // of one table
+    std::string type;
+    uint32_t n;
+    MultiTables(const ts_multi_table* t, uint32_t n) : p((const char*)t), size(sizeof *t), type("ts_multi_table"), n(n) {}
+    MultiTables(const ts_multi_bus_table* t, uint32_t n)
+        : p((const char*)t), size(sizeof *t), type("ts_multi_bus_table"), n(n) {}
+    ts_multi_bus_table operator[](uint32_t t) const {
+        ts_multi_bus_table v{};
+        memcpy(&v, p + t * size, size);
+        return v;
+    }
+};
+static_assert(sizeof(ts_multi_table) == offsetof(ts_multi_bus_table, logup) &&
+                  offsetof(ts_multi_table, air) == offsetof(ts_multi_bus_table, air) &&
+                  offsetof(ts_multi_table, trace) == offsetof(ts_multi_bus_table, trace) &&
+                  offsetof(ts_multi_table, public_values) == offsetof(ts_multi_bus_table, public_values),
+              "ts_multi_table is a prefix of ts_multi_bus_table");
+
+// the admission of the handles of `call`'s tables, table by table
+void admit_multi_tables(ts_ctx* ctx, const std::string& call, const MultiTables& tables) {
+    for (uint32_t t = 0; t < tables.n; t++) {
+        const ts_multi_bus_table mt = tables[t];
+        TS_REQUIRE(mt.struct_size == tables.size, ts::TS_ERR_INVALID,
+                   call + ": " + tables.type + ".struct_size is not sizeof(" + tables.type + ")");
+        TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, call + ": null AIR or trace");
+        TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
+                   call + ": an AIR was compiled on another context (or host-only)");
+        TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+        TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID, call + ": a trace was made on another context");
+        for (uint32_t k = 0; k < t; k++)
+            TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID, call + ": one trace handle in two tables");
+    }
+}
+
+// the statement of admitted tables on shapes alone: the matrices stay with their handles until all of it holds.
+// `specs` keeps the loaded specs alive.
+std::vector<ts::MultiBusTable> multi_table_shapes(const MultiTables& tables, std::vector<ts::LogupSpec>& specs) {
+    std::vector<ts::MultiBusTable> mts(tables.n);
+    specs.resize(tables.n);
+    for (uint32_t t = 0; t < tables.n; t++) {
+        const ts_multi_bus_table mt = tables[t];
+        mts[t].air = &ready_prog(mt.air);
+        mts[t].public_values = public_inputs(mt.public_values, mt.n_public);
+        mts[t].trace.width = mt.trace->m.width;
+        mts[t].trace.height = mt.trace->m.height;
+        mts[t].trace.layout = mt.trace->m.layout;
+        if (mt.logup) {
+            specs[t] = load_logup_spec(mt.logup);
+            mts[t].logup = &specs[t];
+        }
+    }
+    return mts;
+}
+
+// `version`: 6 ts_prove_multi, 7 ts_prove_multi_bus (both without a key), 8 ts_prove_multi_key
+ts_status prove_multi_call(ts_ctx* ctx, uint32_t version, const ts_fri_config* cfg, ts_challenger* chal,
+                           const ts_multi_key* key, const MultiTables& tables, uint32_t* proof_out, size_t cap_words,
+                           size_t* n_words_out) {
     if (!ctx) return TS_ERR_INVALID;
     if (n_words_out) *n_words_out = 0;
     return guard(ctx, [&] {
-        TS_REQUIRE(cfg && chal && tables && proof_out && n_words_out, ts::TS_ERR_INVALID,
-                   call + ": null argument");
-        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+        const std::string call = std::string("ts_") + ts::multi_call(version, nullptr).name;
+        TS_REQUIRE(cfg && chal && tables.p && proof_out && n_words_out, ts::TS_ERR_INVALID, call + ": null argument");
+        TS_REQUIRE(tables.n >= 1 && tables.n <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
                    call + ": between 1 and 64 tables");
         const ts::FriConfig fri = load_cfg(cfg);
-        for (uint32_t t = 0; t < n_tables; t++) {
-            const ts_multi_bus_table& mt = tables[t];
-            TS_REQUIRE(mt.struct_size == sizeof(ts_multi_bus_table), ts::TS_ERR_INVALID,
-                       call + ": ts_multi_bus_table.struct_size is not sizeof(ts_multi_bus_table)");
-            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, call + ": null AIR or trace");
-            TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
-                       call + ": an AIR was compiled on another context (or host-only)");
-            TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
-            TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
-                       call + ": a trace was made on another context");
-            for (uint32_t k = 0; k < t; k++)
-                TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID,
-                           call + ": one trace handle in two tables");
-        }
-        // the statement's own refusals on shapes alone: the matrices stay with their handles until all of it holds
-        std::vector<ts::MultiBusTable> mts(n_tables);
-        std::vector<ts::LogupSpec> specs(n_tables);
-        for (uint32_t t = 0; t < n_tables; t++) {
-            mts[t].air = &ready_prog(tables[t].air);
-            mts[t].public_values = public_inputs(tables[t].public_values, tables[t].n_public);
-            mts[t].trace.width = tables[t].trace->m.width;
-            mts[t].trace.height = tables[t].trace->m.height;
-            mts[t].trace.layout = tables[t].trace->m.layout;
-            if (tables[t].logup) {
-                specs[t] = load_logup_spec(tables[t].logup);
-                mts[t].logup = &specs[t];
-            }
-        }
-        if (with_key) {
-            TS_REQUIRE(!key || key->k.ctx == &ctx->ctx, ts::TS_ERR_INVALID, call + ": the key was made on another context");
-            ts::check_multi_key_statement(fri, mts, key ? &key->k : nullptr);
-        } else {
-            ts::check_multi_bus_statement(fri, mts);
-        }
+        admit_multi_tables(ctx, call, tables);
+        std::vector<ts::LogupSpec> specs;
+        std::vector<ts::MultiBusTable> mts = multi_table_shapes(tables, specs);
+        TS_REQUIRE(!key || key->k.ctx == &ctx->ctx, ts::TS_ERR_INVALID, call + ": the key was made on another context");
+        ts::check_multi_statement(ts::multi_call(version, &fri), mts, key ? &key->k : nullptr);
         ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
-        for (uint32_t t = 0; t < n_tables; t++) mts[t].trace = take_trace(tables[t].trace);
+        for (uint32_t t = 0; t < tables.n; t++) mts[t].trace = take_trace(tables[t].trace);
         ts::StageTimer timer(&ctx->ctx, "prove");
-        copy_proof(with_key ? ts::prove_multi_key(pcs, chal->c, mts, key->k) : ts::prove_multi_bus(pcs, chal->c, mts),
+        copy_proof(version == 6   ? ts::prove_multi(pcs, chal->c, mts)
+                   : version == 7 ? ts::prove_multi_bus(pcs, chal->c, mts)
+                                  : ts::prove_multi_key(pcs, chal->c, mts, key->k),
                    proof_out, cap_words, n_words_out);
     });
 }
+
+// The three host-only verify calls: `version` as above.  ts_verify_multi has no exposed or bus outputs (null here);
+// ts_verify_multi_key may be handed no exposed buffer where no table has aux columns.
+ts_status verify_multi_call(uint32_t version, const ts_fri_config* cfg, ts_challenger* chal, const uint32_t* key_root,
+                            const ts_air* const* airs, uint32_t n_tables, const uint32_t* const* public_values,
+                            const uint32_t* n_public, const uint32_t* proof, size_t n_words, uint32_t* exposed_out,
+                            uint32_t cap_exposed, uint32_t* bus_sum, int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        const std::string call = version == 6 ? "ts_verify_multi" : version == 7 ? "ts_verify_multi_bus" : "ts_verify_multi_key";
+        TS_REQUIRE(cfg && chal && airs && public_values && n_public && proof && verdict && (version == 6 || bus_sum) &&
+                       (version != 7 || exposed_out) && (version != 8 || key_root),
+                   ts::TS_ERR_INVALID, call + ": null argument");
+        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
+                   call + ": between 1 and 64 tables");
+        const ts::FriConfig fri = load_cfg(cfg);
+        std::vector<const ts::AirProgram*> progs(n_tables);
+        std::vector<std::vector<uint32_t>> pis(n_tables);
+        uint32_t n_aux = 0, n_pre = 0;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, call + ": null AIR");
+            const ts::AirProgram& p = airs[t]->a.prog();
+            if (version == 6)
+                TS_REQUIRE(!p.preprocessed_width && !p.aux_width, ts::TS_ERR_UNSUPPORTED,
+                           call + ": a table's AIR has preprocessed or aux columns");
+            else {
+                TS_REQUIRE(version == 8 || !p.preprocessed_width, ts::TS_ERR_UNSUPPORTED,
+                           call + ": a table's AIR has preprocessed columns");
+                TS_REQUIRE(p.aux_width ? p.n_challenges == 2 && p.n_exposed == 4 : !p.n_challenges && !p.n_exposed,
+                           ts::TS_ERR_INVALID,
+                           call + ": an AIR on the bus has aux columns, 2 challenges and 4 exposed words, " +
+                               (version == 8 ? "any other" : "a plain one") + " none of them");
+            }
+            n_aux += p.aux_width ? 1 : 0;
+            n_pre += p.preprocessed_width ? 1 : 0;
+            progs[t] = &p;
+            pis[t] = public_inputs(public_values[t], n_public[t]);
+        }
+        TS_REQUIRE(version != 8 || n_pre > 0, ts::TS_ERR_INVALID,
+                   call + ": no table has preprocessed columns; ts_verify_multi_bus (TSPF v7) and "
+                          "ts_verify_multi (TSPF v6) verify tables without a key");
+        TS_REQUIRE(version != 7 || n_aux > 0, ts::TS_ERR_INVALID,
+                   call + ": no table has aux columns; ts_verify_multi verifies plain tables (TSPF v6)");
+        TS_REQUIRE(n_aux == 0 || (exposed_out && cap_exposed >= 4 * n_aux), ts::TS_ERR_INVALID,
+                   call + (version == 8 ? ": null or short" : ": short") +
+                       " buffer for the exposed words (4 per table with aux columns)");
+        std::vector<uint32_t> exposed;
+        uint32_t sum[4] = {0, 0, 0, 0};
+        *verdict = version == 6   ? ts::verify_multi(fri, chal->c, progs, pis, proof, n_words)
+                   : version == 7 ? ts::verify_multi_bus(fri, chal->c, progs, pis, proof, n_words, exposed, sum)
+                                  : ts::verify_multi_key(fri, chal->c, key_root, progs, pis, proof, n_words, exposed, sum);
+        if (*verdict == 0 && version != 6) {
+            if (!exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
+            memcpy(bus_sum, sum, 16);
+        }
+    }, false);
+}
 }  // namespace
+
+ts_status ts_prove_multi(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_table* tables,
+                         uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    return prove_multi_call(ctx, 6, cfg, chal, nullptr, MultiTables(tables, n_tables), proof_out, cap_words, n_words_out);
+}
+
+ts_status ts_verify_multi(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
+                          const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,
+                          size_t n_words, int* verdict) {
+    return verify_multi_call(6, cfg, chal, nullptr, airs, n_tables, public_values, n_public, proof, n_words, nullptr, 0,
+                             nullptr, verdict);
+}
 
 ts_status ts_prove_multi_bus(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, ts_multi_bus_table* tables,
                              uint32_t n_tables, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
-    return prove_multi_phased(ctx, "ts_prove_multi_bus", false, cfg, chal, nullptr, tables, n_tables, proof_out, cap_words,
-                              n_words_out);
+    return prove_multi_call(ctx, 7, cfg, chal, nullptr, MultiTables(tables, n_tables), proof_out, cap_words, n_words_out);
+}
+
+ts_status ts_verify_multi_bus(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
+                              const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,
+                              size_t n_words, uint32_t* exposed_out, uint32_t cap_exposed, uint32_t bus_sum[4],
+                              int* verdict) {
+    return verify_multi_call(7, cfg, chal, nullptr, airs, n_tables, public_values, n_public, proof, n_words, exposed_out,
+                             cap_exposed, bus_sum, verdict);
 }
 
 // ------------------------------------------------------------------ the key of a multi-table proof
@@ -2170,91 +2210,15 @@ ts_status ts_multi_key_free(ts_ctx* ctx, ts_multi_key* key) {
 ts_status ts_prove_multi_key(ts_ctx* ctx, const ts_fri_config* cfg, ts_challenger* chal, const ts_multi_key* key,
                              ts_multi_key_table* tables, uint32_t n_tables, uint32_t* proof_out, size_t cap_words,
                              size_t* n_words_out) {
-    return prove_multi_phased(ctx, "ts_prove_multi_key", true, cfg, chal, key, tables, n_tables, proof_out, cap_words,
-                              n_words_out);
+    return prove_multi_call(ctx, 8, cfg, chal, key, MultiTables(tables, n_tables), proof_out, cap_words, n_words_out);
 }
 
 ts_status ts_verify_multi_key(const ts_fri_config* cfg, ts_challenger* chal, const uint32_t key_root[8],
                               const ts_air* const* airs, uint32_t n_tables, const uint32_t* const* public_values,
                               const uint32_t* n_public, const uint32_t* proof, size_t n_words, uint32_t* exposed_out,
                               uint32_t cap_exposed, uint32_t bus_sum[4], int* verdict) {
-    if (verdict) *verdict = -1;
-    return guard(nullptr, [&] {
-        TS_REQUIRE(cfg && chal && key_root && airs && public_values && n_public && proof && bus_sum && verdict,
-                   ts::TS_ERR_INVALID, "ts_verify_multi_key: null argument");
-        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
-                   "ts_verify_multi_key: between 1 and 64 tables");
-        const ts::FriConfig fri = load_cfg(cfg);
-        std::vector<const ts::AirProgram*> progs(n_tables);
-        std::vector<std::vector<uint32_t>> pis(n_tables);
-        uint32_t n_aux = 0, n_pre = 0;
-        for (uint32_t t = 0; t < n_tables; t++) {
-            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, "ts_verify_multi_key: null AIR");
-            const ts::AirProgram& p = airs[t]->a.prog();
-            TS_REQUIRE(p.aux_width ? p.n_challenges == 2 && p.n_exposed == 4 : !p.n_challenges && !p.n_exposed,
-                       ts::TS_ERR_INVALID,
-                       "ts_verify_multi_key: an AIR on the bus has aux columns, 2 challenges and 4 exposed words, any "
-                       "other none of them");
-            n_aux += p.aux_width ? 1 : 0;
-            n_pre += p.preprocessed_width ? 1 : 0;
-            progs[t] = &p;
-            pis[t] = public_inputs(public_values[t], n_public[t]);
-        }
-        TS_REQUIRE(n_pre > 0, ts::TS_ERR_INVALID,
-                   "ts_verify_multi_key: no table has preprocessed columns; ts_verify_multi_bus (TSPF v7) and "
-                   "ts_verify_multi (TSPF v6) verify tables without a key");
-        TS_REQUIRE(n_aux == 0 || (exposed_out && cap_exposed >= 4 * n_aux), ts::TS_ERR_INVALID,
-                   "ts_verify_multi_key: null or short buffer for the exposed words (4 per table with aux columns)");
-        std::vector<uint32_t> exposed;
-        uint32_t sum[4] = {0, 0, 0, 0};
-        *verdict = ts::verify_multi_key(fri, chal->c, key_root, progs, pis, proof, n_words, exposed, sum);
-        if (*verdict == 0) {
-            if (!exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
-            memcpy(bus_sum, sum, 16);
-        }
-    }, false);
-}
-
-
-ts_status ts_verify_multi_bus(const ts_fri_config* cfg, ts_challenger* chal, const ts_air* const* airs, uint32_t n_tables,
-                              const uint32_t* const* public_values, const uint32_t* n_public, const uint32_t* proof,
-                              size_t n_words, uint32_t* exposed_out, uint32_t cap_exposed, uint32_t bus_sum[4],
-                              int* verdict) {
-    if (verdict) *verdict = -1;
-    return guard(nullptr, [&] {
-        TS_REQUIRE(cfg && chal && airs && public_values && n_public && proof && exposed_out && bus_sum && verdict,
-                   ts::TS_ERR_INVALID, "ts_verify_multi_bus: null argument");
-        TS_REQUIRE(n_tables >= 1 && n_tables <= ts::MAX_MULTI_TABLES, ts::TS_ERR_INVALID,
-                   "ts_verify_multi_bus: between 1 and 64 tables");
-        const ts::FriConfig fri = load_cfg(cfg);
-        std::vector<const ts::AirProgram*> progs(n_tables);
-        std::vector<std::vector<uint32_t>> pis(n_tables);
-        uint32_t n_aux = 0;
-        for (uint32_t t = 0; t < n_tables; t++) {
-            TS_REQUIRE(airs[t], ts::TS_ERR_INVALID, "ts_verify_multi_bus: null AIR");
-            const ts::AirProgram& p = airs[t]->a.prog();
-            if (p.preprocessed_width)
-                throw ts::Error(ts::TS_ERR_UNSUPPORTED, "ts_verify_multi_bus: a table's AIR has preprocessed columns");
-            TS_REQUIRE(p.aux_width ? p.n_challenges == 2 && p.n_exposed == 4 : !p.n_challenges && !p.n_exposed,
-                       ts::TS_ERR_INVALID,
-                       "ts_verify_multi_bus: an AIR on the bus has aux columns, 2 challenges and 4 exposed words, a "
-                       "plain one none of them");
-            n_aux += p.aux_width ? 1 : 0;
-            progs[t] = &p;
-            pis[t] = public_inputs(public_values[t], n_public[t]);
-        }
-        TS_REQUIRE(n_aux > 0, ts::TS_ERR_INVALID,
-                   "ts_verify_multi_bus: no table has aux columns; ts_verify_multi verifies plain tables (TSPF v6)");
-        TS_REQUIRE(cap_exposed >= 4 * n_aux, ts::TS_ERR_INVALID,
-                   "ts_verify_multi_bus: short buffer for the exposed words (4 per table with aux columns)");
-        std::vector<uint32_t> exposed;
-        uint32_t sum[4] = {0, 0, 0, 0};
-        *verdict = ts::verify_multi_bus(fri, chal->c, progs, pis, proof, n_words, exposed, sum);
-        if (*verdict == 0) {
-            memcpy(exposed_out, exposed.data(), exposed.size() * 4);
-            memcpy(bus_sum, sum, 16);
-        }
-    }, false);
+    return verify_multi_call(8, cfg, chal, key_root, airs, n_tables, public_values, n_public, proof, n_words, exposed_out,
+                             cap_exposed, bus_sum, verdict);
 }
 
 // ------------------------------------------------------------------ preprocessed and aux columns together
@@ -2371,34 +2335,12 @@ ts_status ts_check_multi(ts_ctx* ctx, const ts_multi_key* key, const ts_multi_ke
     return guard(ctx, [&] {
         const std::string call = "ts_check_multi";
         TS_REQUIRE(tables && challenges && bad_table && first_violation, ts::TS_ERR_INVALID, call + ": null argument");
-        for (uint32_t t = 0; t < n_tables; t++) {
-            const ts_multi_key_table& mt = tables[t];
-            TS_REQUIRE(mt.struct_size == sizeof(ts_multi_bus_table), ts::TS_ERR_INVALID,
-                       call + ": ts_multi_bus_table.struct_size is not sizeof(ts_multi_bus_table)");
-            TS_REQUIRE(mt.air && mt.trace, ts::TS_ERR_INVALID, call + ": null AIR or trace");
-            TS_REQUIRE(mt.air->a.context() == &ctx->ctx, ts::TS_ERR_INVALID,
-                       call + ": an AIR was compiled on another context (or host-only)");
-            TS_REQUIRE(mt.trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
-            TS_REQUIRE(mt.trace->m.buf.ctx == &ctx->ctx, ts::TS_ERR_INVALID,
-                       call + ": a trace was made on another context");
-            for (uint32_t k = 0; k < t; k++)
-                TS_REQUIRE(tables[k].trace != mt.trace, ts::TS_ERR_INVALID, call + ": one trace handle in two tables");
-        }
-        std::vector<ts::MultiBusTable> mts(n_tables);
-        std::vector<ts::LogupSpec> specs(n_tables);
-        for (uint32_t t = 0; t < n_tables; t++) {
-            mts[t].air = &ready_prog(tables[t].air);
-            mts[t].public_values = public_inputs(tables[t].public_values, tables[t].n_public);
-            mts[t].trace.width = tables[t].trace->m.width;
-            mts[t].trace.height = tables[t].trace->m.height;
-            mts[t].trace.layout = tables[t].trace->m.layout;
-            if (tables[t].logup) {
-                specs[t] = load_logup_spec(tables[t].logup);
-                mts[t].logup = &specs[t];
-            }
-        }
+        const MultiTables admitted(tables, n_tables);
+        admit_multi_tables(ctx, call, admitted);
+        std::vector<ts::LogupSpec> specs;
+        const std::vector<ts::MultiBusTable> mts = multi_table_shapes(admitted, specs);
         TS_REQUIRE(!key || key->k.ctx == &ctx->ctx, ts::TS_ERR_INVALID, call + ": the key was made on another context");
-        ts::check_multi_debug_statement(mts, key ? &key->k : nullptr);
+        ts::check_multi_statement(ts::multi_call(0, nullptr), mts, key ? &key->k : nullptr);
 
         // per table its key matrix (null without preprocessed columns); the aux tables and their builder arguments
         std::vector<const ts_matrix*> pre(n_tables, nullptr), traces(n_tables, nullptr);

@@ -203,16 +203,8 @@ void check_side_matrix(const PcsData& data, const AirProgram& air, uint32_t i, u
 // Build-defined (the reference proves one table; prove_multi.cpp): T plain AIRs (no
 // preprocessed, no aux columns) of any heights share one trace commitment, one alpha, one commitment to all
 // quotient chunks, one zeta and ONE opening -- one FRI commit phase, one grind, one set of queries.  TSPF v6.
+// The table struct, the statement check and the three provers (v6, v7, v8) are declared in logup.hpp.
 constexpr uint32_t MAX_MULTI_TABLES = 64;
-struct MultiTable {
-    const AirProgram* air = nullptr;
-    DeviceMatrix trace;  // consumed
-    std::vector<uint32_t> public_values;
-};
-// throws what prove() throws for a table alone (check_statement), TS_ERR_UNSUPPORTED for an AIR with preprocessed
-// or aux columns, TS_ERR_INVALID for more than 64 tables or chunks; nothing is consumed before these checks
-void check_multi_statement(const FriConfig& fri, const std::vector<MultiTable>& tables);
-std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiTable>& tables);
 // TS_MULTI_OPEN_GENERIC=1 (read on every call; a test and measurement knob): prove_multi opens through
 // TwoAdicFriPcs::open instead of the per-class kernels.  Same proof.
 bool multi_open_generic();

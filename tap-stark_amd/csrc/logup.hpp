@@ -52,22 +52,13 @@ std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<
                                                 const uint32_t* table_ids = nullptr,
                                                 const std::vector<const DeviceMatrix*>* tables = nullptr);
 
-// ---- several tables in one proof, tied by a LogUp bus (prove_multi.cpp; TSPF v7)
+// ---- several tables in one proof (prove_multi.cpp; TSPF v6, v7 and v8)
 struct MultiBusTable {
-    const AirProgram* air = nullptr;   // no preprocessed columns; aux columns exactly with n_challenges 2, n_exposed 4
+    const AirProgram* air = nullptr;   // aux columns exactly with n_challenges 2, n_exposed 4
     DeviceMatrix trace;                // consumed; row-major where the AIR has aux columns
     std::vector<uint32_t> public_values;
-    const LogupSpec* logup = nullptr;  // null exactly for an AIR without aux columns; terms of kind 0 and 1
+    const LogupSpec* logup = nullptr;  // null exactly for an AIR without aux columns (a plain table)
 };
-// throws what check_multi_statement throws for the tables as plain ones, TS_ERR_UNSUPPORTED for preprocessed
-// columns, TS_ERR_INVALID for a spec that is missing, unwanted or does not fit its AIR and trace, for a column-major
-// trace under an aux table and for a statement without any aux table; on shapes alone, nothing is consumed
-void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables);
-// Throws TS_ERR_INVARIANT naming (table, row, interaction) of a zero denominator; the traces
-// are consumed by then.
-std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables);
-
-// ---- the same against a commit-once key: fixed tables on the bus (prove_multi.cpp; TSPF v8)
 // One committed batch of preprocessed matrices of mixed heights, on their natural domains; made once, consumed by
 // no proof.  `values[i]`: the row-major input of matrix i, kept alive by the commit (no second copy) and owned by
 // whoever made the key, where it was made with keep_values; null otherwise.
@@ -79,14 +70,33 @@ struct MultiKey {
     unsigned log_blowup = 0;
     Context* ctx = nullptr;
 };
-// The i-th table with preprocessed columns, in table order, reads key matrix i.  A table is plain, key-only,
-// aux-only or both; a spec's kind-2 terms read the table's key matrix (the key then needs kept values).  Throws what
-// check_multi_bus_statement throws except for preprocessed columns and for a statement without an aux table, and
-// TS_ERR_INVALID for a null key, a key no table uses and a key whose count, heights, widths or blowup do not fit; on
-// shapes alone, nothing is consumed.
-void check_multi_key_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables, const MultiKey* key);
-// prove_multi_bus with the key's root observed after the shapes, the key matrices as the first side matrix of their
-// tables' quotients and as the first opened round; without any aux table the challenge phase is skipped whole.
+// What a call makes of a round that only some statements have (the key's, the aux matrices'): never there, there in
+// every statement, or there where a table has such columns.
+enum class MultiRound { NEVER, ALWAYS, AS_TABLES_HAVE };
+struct MultiCall {
+    const char* name;       // leads every text
+    MultiRound key, aux;
+    const FriConfig* fri;   // null: the shape rules that need none (widths, public values; every trace row-major)
+};
+// the calls there are: version 6 prove_multi (tied by nothing: plain tables), 7 prove_multi_bus (a LogUp bus: at least
+// one aux table, no key), 8 prove_multi_key (fixed tables on the bus: a key, aux tables or none); any other version
+// check_multi, the debug counterpart of the bus proofs (`fri` is not looked at; a key exactly when a table has
+// preprocessed columns, made with keep_values)
+MultiCall multi_call(uint32_t version, const FriConfig* fri);
+// The one statement walk, on shapes alone; nothing is consumed.  Throws what prove() throws for a table alone
+// (check_statement); TS_ERR_UNSUPPORTED for columns of a round the call never has; TS_ERR_INVALID for more than 64
+// tables or chunks, for a spec that is missing, unwanted or does not fit its AIR, trace and key matrix, for a
+// column-major trace under an aux table, for a statement without a round the call always has, for a null key, a key no
+// table uses and a key whose count, heights, widths, blowup or kept values do not fit.  The i-th table with
+// preprocessed columns, in table order, reads key matrix i; a spec's kind-2 terms read the table's key matrix.
+void check_multi_statement(const MultiCall& call, const std::vector<MultiBusTable>& tables, const MultiKey* key);
+// The three provers, one body; each checks its statement first.  prove_multi_bus: gamma and beta once for every table,
+// one commit of the LogUp matrices.  prove_multi_key: the key's root observed after the shapes, the key matrices as
+// the first side matrix of their tables' quotients and as the first opened round; without any aux table the challenge
+// phase is skipped whole.  Throw TS_ERR_INVARIANT naming (table, row, interaction) of a zero denominator; the traces
+// are consumed by then.
+std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables);
+std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables);
 std::vector<uint32_t> prove_multi_key(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables,
                                       const MultiKey& key);
 // TS_MULTI_LOGUP_PER_TABLE=1 (read on every call; a test and measurement knob): prove_multi_bus loops
@@ -172,9 +182,6 @@ struct BusReport {
 // synchronises the stream once, twice when the bus is unbalanced.
 BusReport bus_check(Context& ctx, const std::vector<const LogupSpec*>& specs,
                     const std::vector<const DeviceMatrix*>& traces, const std::vector<const DeviceMatrix*>& tables);
-// the shape checks of check_multi_key_statement that need no FriConfig, for the debug counterpart of the bus proofs:
-// `key` is null exactly when no table has preprocessed columns
-void check_multi_debug_statement(const std::vector<MultiBusTable>& tables, const MultiKey* key);
 
 // ---- a lookup proof inside a batch lane (prover.cpp): no launch of its own
 // What a lookup argument says about an item's DATA, raised after the kernels finished normally: a zero denominator

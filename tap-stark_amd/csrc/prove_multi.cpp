@@ -17,11 +17,15 @@
 // and the public vector pis ++ gamma ++ beta ++ its exposed words.  The opening has three rounds, in the order of
 // TSPF v4: aux matrices and traces at {zeta, zeta omega_{n_t}}, chunks at {zeta}.
 //
-// prove_multi_key: prove_multi_bus against a commit-once key of preprocessed matrices (MultiKey, logup.hpp; TSPF v8),
-// the same body (prove_multi_phased).  The key's root is observed after the shapes and is not in the proof; the i-th
+// prove_multi_key: prove_multi_bus against a commit-once key of preprocessed matrices (MultiKey, logup.hpp; TSPF v8).
+// The key's root is observed after the shapes and is not in the proof; the i-th
 // table with preprocessed columns reads key matrix i: its LDE is the first side matrix of that table's quotient
 // and the key is the first opened round, in the order of TSPF v5.  A LogUp spec may read the key's kept values
 // (kind-2 terms).  Without any table with aux columns the challenge phase is skipped whole: three rounds.
+//
+// The three are one body (prove_multi_versioned) behind one statement walk (check_multi_statement): the rounds a
+// statement has -- a key or none, aux tables or none -- select the paths, and the header's version is all that tells a
+// v6 proof from a v7 body without aux tables, which the statement walk refuses.
 #include <stdlib.h>
 #include <string.h>
 
@@ -36,21 +40,6 @@ namespace ts {
 bool multi_open_generic() {
     const char* e = getenv("TS_MULTI_OPEN_GENERIC");
     return e && *e && atoi(e) != 0;
-}
-
-void check_multi_statement(const FriConfig& fri, const std::vector<MultiTable>& tables) {
-    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
-               "prove_multi: between 1 and 64 tables");
-    uint32_t n_chunks = 0;
-    for (const MultiTable& t : tables) {
-        TS_REQUIRE(t.air, TS_ERR_INVALID, "prove_multi: null AIR");
-        TS_REQUIRE(t.air->preprocessed_width == 0 && t.air->aux_width == 0, TS_ERR_UNSUPPORTED,
-                   "prove_multi: a table's AIR has preprocessed or challenge-phase (aux) columns; only plain AIRs "
-                   "share a multi-table proof");
-        n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
-    }
-    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
-               "prove_multi: more than 64 quotient chunks over all tables (the limit of one committed batch)");
 }
 
 namespace {
@@ -220,213 +209,118 @@ std::vector<uint32_t> open_rounds(TwoAdicFriPcs& pcs, BfChallenger& challenger, 
 
 }  // namespace
 
-std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiTable>& tables) {
-    check_multi_statement(pcs.fri(), tables);
-    const size_t T = tables.size();
-    std::vector<Statement> st;
-    unsigned log_max = 0;
-    for (const MultiTable& t : tables) {
-        st.push_back(check_statement(pcs.fri(), *t.air, t.trace.width, t.trace.height, t.public_values.size()));
-        log_max = std::max(log_max, st.back().log_N);
-    }
-    pcs.ctx().ensure_twiddles(std::max(1u, log_max));
-
-    // the statement's shape: a prover must not choose the heights after the fact
-    challenger.observe((uint32_t)T);
-    for (const Statement& s : st) challenger.observe(s.log_degree);
-
-    // one commit of every trace on its natural domain (shift 1)
-    std::vector<DeviceMatrix> tv;
-    for (MultiTable& t : tables) tv.push_back(std::move(t.trace));
-    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, std::vector<uint32_t>(T, 1u));
-    challenger.observe_commitment(trace_data->root);
-    const Ef alpha = challenger.sample();
-
-    // the chunks of every table over its own LDE in the batch, then one commit of all of them
-    std::vector<DeviceMatrix> chunks;
-    std::vector<uint32_t> shifts;
-    for (size_t t = 0; t < T; t++) {
-        std::vector<DeviceMatrix> c =
-            pcs.quotient_chunks_slab(trace_data->ldes[t], st[t].log_degree, TwoAdicFriPcs::Slab{}, *tables[t].air,
-                                     tables[t].public_values, alpha);
-        const std::vector<uint32_t> sh = chunk_domain_shifts(GENERATOR, st[t].log_degree, st[t].lqd);
-        for (auto& m : c) chunks.push_back(std::move(m));
-        shifts.insert(shifts.end(), sh.begin(), sh.end());
-    }
-    std::unique_ptr<PcsData> quotient_data = pcs.commit(chunks, shifts);
-    challenger.observe_commitment(quotient_data->root);
-    const Ef zeta = challenger.sample();
-
-    // the two rounds in the visiting order of Pcs::open
-    std::vector<OpenMat> mats;
-    size_t first = 0, qi = 0;
-    for (size_t t = 0; t < T; t++) {
-        mats.push_back(OpenMat{&trace_data->ldes[t], 0, st[t].log_degree, true, first});
-        first += 2 * (size_t)st[t].w;
-    }
-    for (size_t t = 0; t < T; t++)
-        for (uint32_t c = 0; c < st[t].qd; c++, qi++) {
-            const ColMat& m = quotient_data->ldes[qi];
-            TS_REQUIRE(m.width == 4 && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
-                       "prove_multi: a committed chunk has another shape than its table's");
-            mats.push_back(OpenMat{&m, 1, st[t].log_degree, false, first});
-            first += 4;
-        }
-
-    std::vector<Ef> opened;
-    const std::vector<uint32_t> fri_words =
-        open_rounds(pcs, challenger, {trace_data.get(), quotient_data.get()}, mats, zeta, opened);
-
-    std::vector<uint32_t> pf;
-    pf.reserve(32 + 3 * T + opened.size() * 4 + fri_words.size());
-    ProofWriter pw(pf);
-    std::vector<ProofWriter::TableShape> shapes;
-    for (const Statement& s : st) shapes.push_back({s.log_degree, s.w, s.qd, 0, 0});
-    pw.header_multi(shapes);
-    pw.commitment(trace_data->root, 8);
-    pw.commitment(quotient_data->root, 8);
-    pw.opened_values(opened);
-    pw.words(fri_words.data(), fri_words.size());
-    return pf;
-}
-
-// ------------------------------------------------------------------ the same with a LogUp bus across the tables
 bool multi_logup_per_table() {
     const char* e = getenv("TS_MULTI_LOGUP_PER_TABLE");
     return e && *e && atoi(e) != 0;
 }
 
-// the checks of one table's challenge phase (`w` leads the texts); `pre_width`: the width of the key matrix its
-// kind-2 terms read, 0 where they are refused
-static void check_bus_table(const MultiBusTable& t, const std::string& w, uint32_t pre_width) {
-    const uint32_t aw = t.air->aux_width;
-    if (aw) {
-        TS_REQUIRE(t.air->n_challenges == 2 && t.air->n_exposed == 4, TS_ERR_INVALID,
-                   w + ": an AIR on the bus has 2 challenges (gamma, beta) and 4 exposed words (its sum)");
-        TS_REQUIRE(t.logup, TS_ERR_INVALID, w + ": the AIR has aux columns and no logup spec");
-        // (without a key matrix a kind-2 term is refused here: there is no preprocessed table to read)
-        TS_REQUIRE(logup_aux_width(*t.logup, pre_width ? 2 : 1) == aw, TS_ERR_INVALID,
-                   w + ": the logup spec's aux width is not the AIR's");
-        for (const LogupInteraction& it : t.logup->interactions) {
-            std::vector<LogupTerm> terms = it.values;
-            terms.push_back(it.multiplicity);
-            for (const LogupTerm& tm : terms)
-                TS_REQUIRE(tm.kind == 2 ? tm.value < pre_width : tm.kind ? tm.value < t.trace.width : tm.value < P,
-                           TS_ERR_INVALID,
-                           w + (pre_width ? ": the logup spec reads a column outside the trace or the key matrix, or has a "
-                                            "non-canonical constant"
-                                          : ": the logup spec reads a column outside the trace, or has a non-canonical constant"));
-        }
-        TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
-                   w + ": the trace of a table with aux columns must be row-major (the LogUp builder reads its rows)");
-    } else {
-        TS_REQUIRE(t.air->n_challenges == 0 && t.air->n_exposed == 0, TS_ERR_INVALID,
-                   w + ": challenges or exposed words without aux columns");
-        TS_REQUIRE(!t.logup, TS_ERR_INVALID, w + ": a logup spec for an AIR without aux columns");
+MultiCall multi_call(uint32_t version, const FriConfig* fri) {
+    switch (version) {
+        case 6: return {"prove_multi", MultiRound::NEVER, MultiRound::NEVER, fri};
+        case 7: return {"prove_multi_bus", MultiRound::NEVER, MultiRound::ALWAYS, fri};
+        case 8: return {"prove_multi_key", MultiRound::ALWAYS, MultiRound::AS_TABLES_HAVE, fri};
+        default: return {"check_multi", MultiRound::AS_TABLES_HAVE, MultiRound::AS_TABLES_HAVE, nullptr};
     }
 }
 
-void check_multi_bus_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables) {
-    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
-               "prove_multi_bus: between 1 and 64 tables");
-    uint32_t n_chunks = 0, n_aux = 0;
-    for (size_t k = 0; k < tables.size(); k++) {
-        const MultiBusTable& t = tables[k];
-        const std::string w = "prove_multi_bus: table " + std::to_string(k);
-        TS_REQUIRE(t.air, TS_ERR_INVALID, w + ": null AIR");
-        TS_REQUIRE(t.air->preprocessed_width == 0, TS_ERR_UNSUPPORTED,
-                   w + ": the AIR has preprocessed columns; a multi-table proof has no key round");
-        check_bus_table(t, w, 0);
-        n_aux += t.air->aux_width ? 1 : 0;
-        n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
-    }
-    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
-               "prove_multi_bus: more than 64 quotient chunks over all tables (the limit of one committed batch)");
-    TS_REQUIRE(n_aux > 0, TS_ERR_INVALID,
-               "prove_multi_bus: no table has aux columns; plain tables are proved by ts_prove_multi (TSPF v6)");
-}
-
-void check_multi_key_statement(const FriConfig& fri, const std::vector<MultiBusTable>& tables, const MultiKey* key) {
-    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
-               "prove_multi_key: between 1 and 64 tables");
+void check_multi_statement(const MultiCall& call, const std::vector<MultiBusTable>& tables, const MultiKey* key) {
+    const std::string name = call.name;
+    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID, name + ": between 1 and 64 tables");
     uint32_t n_chunks = 0;
-    size_t n_pre = 0;
+    size_t n_pre = 0, n_aux = 0;
     for (const MultiBusTable& t : tables) {
-        TS_REQUIRE(t.air, TS_ERR_INVALID, "prove_multi_key: null AIR");
+        TS_REQUIRE(t.air, TS_ERR_INVALID, name + ": null AIR");
         n_pre += t.air->preprocessed_width ? 1 : 0;
+        n_aux += t.air->aux_width ? 1 : 0;
     }
-    TS_REQUIRE(key && key->data && n_pre > 0, TS_ERR_INVALID,
-               "prove_multi_key: a null key, or no table has preprocessed columns; tables without a key are proved by "
-               "ts_prove_multi_bus (TSPF v7) or ts_prove_multi (TSPF v6)");
-    TS_REQUIRE(key->heights.size() == n_pre, TS_ERR_INVALID,
-               "prove_multi_key: the key holds " + std::to_string(key->heights.size()) + " matrices and " +
-                   std::to_string(n_pre) + " tables have preprocessed columns");
-    TS_REQUIRE(key->log_blowup == fri.log_blowup, TS_ERR_INVALID,
-               "prove_multi_key: the key was committed with another log_blowup");
-    size_t ki = 0;
-    for (size_t k = 0; k < tables.size(); k++) {
-        const MultiBusTable& t = tables[k];
-        const std::string w = "prove_multi_key: table " + std::to_string(k);
-        const uint32_t pw = t.air->preprocessed_width;
-        if (pw) {
-            TS_REQUIRE(key->heights[ki] == t.trace.height && key->widths[ki] == pw, TS_ERR_INVALID,
-                       w + ": key matrix " + std::to_string(ki) + " has not the table's height and the AIR's preprocessed width");
-        }
-        check_bus_table(t, w, pw);
-        bool reads_key = false;
-        if (t.logup)
-            for (const LogupInteraction& it : t.logup->interactions) {
-                reads_key = reads_key || it.multiplicity.kind == 2;
-                for (const LogupTerm& tm : it.values) reads_key = reads_key || tm.kind == 2;
-            }
-        TS_REQUIRE(!reads_key || (pw && key->values[ki]), TS_ERR_INVALID,
-                   w + ": the logup spec reads preprocessed columns and the key was made without keep_values");
-        ki += pw ? 1 : 0;
-        n_chunks += check_statement(fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
-    }
-    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
-               "prove_multi_key: more than 64 quotient chunks over all tables (the limit of one committed batch)");
-}
-
-void check_multi_debug_statement(const std::vector<MultiBusTable>& tables, const MultiKey* key) {
-    TS_REQUIRE(!tables.empty() && tables.size() <= MAX_MULTI_TABLES, TS_ERR_INVALID,
-               "check_multi: between 1 and 64 tables");
-    size_t n_pre = 0;
-    for (const MultiBusTable& t : tables) {
-        TS_REQUIRE(t.air, TS_ERR_INVALID, "check_multi: null AIR");
-        n_pre += t.air->preprocessed_width ? 1 : 0;
-    }
-    TS_REQUIRE((key != nullptr) == (n_pre > 0), TS_ERR_INVALID,
-               n_pre ? "check_multi: a null key and a table with preprocessed columns"
-                     : "check_multi: a key was given and no table has preprocessed columns");
+    // the key round (a call without one is handed no key and refuses preprocessed columns table by table)
+    if (call.key == MultiRound::ALWAYS)
+        TS_REQUIRE(key && key->data && n_pre > 0, TS_ERR_INVALID,
+                   name + ": a null key, or no table has preprocessed columns; tables without a key are proved by "
+                          "ts_prove_multi_bus (TSPF v7) or ts_prove_multi (TSPF v6)");
+    if (call.key == MultiRound::AS_TABLES_HAVE)
+        TS_REQUIRE((key != nullptr) == (n_pre > 0), TS_ERR_INVALID,
+                   name + (n_pre ? ": a null key and a table with preprocessed columns"
+                                 : ": a key was given and no table has preprocessed columns"));
     if (key) {
         TS_REQUIRE(key->data && key->heights.size() == n_pre, TS_ERR_INVALID,
-                   "check_multi: the key holds " + std::to_string(key->heights.size()) + " matrices and " +
+                   name + ": the key holds " + std::to_string(key->heights.size()) + " matrices and " +
                        std::to_string(n_pre) + " tables have preprocessed columns");
+        TS_REQUIRE(!call.fri || key->log_blowup == call.fri->log_blowup, TS_ERR_INVALID,
+                   name + ": the key was committed with another log_blowup");
     }
     size_t ki = 0;
     for (size_t k = 0; k < tables.size(); k++) {
         const MultiBusTable& t = tables[k];
-        const std::string w = "check_multi: table " + std::to_string(k);
-        const uint32_t pw = t.air->preprocessed_width;
-        TS_REQUIRE(t.trace.width == t.air->width, TS_ERR_INVALID, w + ": the trace has not the AIR's width");
-        TS_REQUIRE(t.public_values.size() == t.air->n_public, TS_ERR_INVALID, w + ": wrong number of public values");
+        const std::string w = name + ": table " + std::to_string(k);
+        const uint32_t pw = t.air->preprocessed_width, aw = t.air->aux_width;
+        if (call.aux == MultiRound::NEVER)
+            TS_REQUIRE(pw == 0 && aw == 0, TS_ERR_UNSUPPORTED,
+                       name + ": a table's AIR has preprocessed or challenge-phase (aux) columns; only plain AIRs "
+                              "share a multi-table proof");
+        else if (call.key == MultiRound::NEVER)
+            TS_REQUIRE(pw == 0, TS_ERR_UNSUPPORTED,
+                       w + ": the AIR has preprocessed columns; a multi-table proof has no key round");
+        if (!call.fri) {  // (with a FriConfig check_statement below says the same)
+            TS_REQUIRE(t.trace.width == t.air->width, TS_ERR_INVALID, w + ": the trace has not the AIR's width");
+            TS_REQUIRE(t.public_values.size() == t.air->n_public, TS_ERR_INVALID, w + ": wrong number of public values");
+        }
         if (pw) {
             TS_REQUIRE(key->heights[ki] == t.trace.height && key->widths[ki] == pw, TS_ERR_INVALID,
                        w + ": key matrix " + std::to_string(ki) + " has not the table's height and the AIR's preprocessed width");
             // (the constraint check reads the rows of every key matrix, the builder those a spec names)
-            TS_REQUIRE(key->values[ki], TS_ERR_INVALID, w + ": the key was made without keep_values");
+            TS_REQUIRE(call.fri || key->values[ki], TS_ERR_INVALID, w + ": the key was made without keep_values");
         }
-        check_bus_table(t, w, pw);
-        TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID, w + ": the trace must be row-major");
+        // the table's challenge phase; its kind-2 terms read a key matrix and are refused without one
+        bool reads_key = false;
+        if (aw) {
+            TS_REQUIRE(t.air->n_challenges == 2 && t.air->n_exposed == 4, TS_ERR_INVALID,
+                       w + ": an AIR on the bus has 2 challenges (gamma, beta) and 4 exposed words (its sum)");
+            TS_REQUIRE(t.logup, TS_ERR_INVALID, w + ": the AIR has aux columns and no logup spec");
+            TS_REQUIRE(logup_aux_width(*t.logup, pw ? 2 : 1) == aw, TS_ERR_INVALID,
+                       w + ": the logup spec's aux width is not the AIR's");
+            for (const LogupInteraction& it : t.logup->interactions) {
+                std::vector<LogupTerm> terms = it.values;
+                terms.push_back(it.multiplicity);
+                for (const LogupTerm& tm : terms) {
+                    TS_REQUIRE(tm.kind == 2 ? tm.value < pw : tm.kind ? tm.value < t.trace.width : tm.value < P,
+                               TS_ERR_INVALID,
+                               w + (pw ? ": the logup spec reads a column outside the trace or the key matrix, or has a "
+                                         "non-canonical constant"
+                                       : ": the logup spec reads a column outside the trace, or has a non-canonical constant"));
+                    reads_key = reads_key || tm.kind == 2;
+                }
+            }
+            TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID,
+                       w + ": the trace of a table with aux columns must be row-major (the LogUp builder reads its rows)");
+        } else if (call.aux != MultiRound::NEVER) {
+            TS_REQUIRE(t.air->n_challenges == 0 && t.air->n_exposed == 0, TS_ERR_INVALID,
+                       w + ": challenges or exposed words without aux columns");
+            TS_REQUIRE(!t.logup, TS_ERR_INVALID, w + ": a logup spec for an AIR without aux columns");
+        }
+        TS_REQUIRE(!reads_key || (pw && key->values[ki]), TS_ERR_INVALID,
+                   w + ": the logup spec reads preprocessed columns and the key was made without keep_values");
         ki += pw ? 1 : 0;
+        if (call.fri)
+            n_chunks += check_statement(*call.fri, *t.air, t.trace.width, t.trace.height, t.public_values.size()).qd;
+        else
+            TS_REQUIRE(t.trace.layout == DeviceMatrix::ROW_MAJOR, TS_ERR_INVALID, w + ": the trace must be row-major");
     }
+    TS_REQUIRE(n_chunks <= (uint32_t)MAX_BATCH_MATS, TS_ERR_INVALID,
+               name + ": more than 64 quotient chunks over all tables (the limit of one committed batch)");
+    TS_REQUIRE(call.aux != MultiRound::ALWAYS || n_aux > 0, TS_ERR_INVALID,
+               name + ": no table has aux columns; plain tables are proved by ts_prove_multi (TSPF v6)");
 }
 
-// One body for TSPF v7 (key == nullptr: at least one aux table, no preprocessed columns) and TSPF v8 (a key; the
-// challenge phase only if some table has aux columns).  The statement has been checked.
-static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger& challenger,
-                                                std::vector<MultiBusTable>& tables, const MultiKey* key) {
+// One body for TSPF v6 (no key, no table with aux columns), v7 (no key, at least one aux table) and v8 (a key; the
+// challenge phase only if some table has aux columns): the rounds the statement has select the paths, `version` is
+// the header's.
+static std::vector<uint32_t> prove_multi_versioned(TwoAdicFriPcs& pcs, BfChallenger& challenger,
+                                                   std::vector<MultiBusTable>& tables, const MultiKey* key,
+                                                   uint32_t version) {
+    const MultiCall call = multi_call(version, &pcs.fri());
+    check_multi_statement(call, tables, key);
+    const std::string name = call.name;  // of the running call, in front of the invariant texts
     Context& ctx = pcs.ctx();
     const size_t T = tables.size();
     std::vector<Statement> st;
@@ -437,6 +331,7 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
     }
     ctx.ensure_twiddles(std::max(1u, log_max));
 
+    // the statement's shape: a prover must not choose the heights after the fact
     challenger.observe((uint32_t)T);
     for (const Statement& s : st) challenger.observe(s.log_degree);
     // the key is part of the statement: its root is observed and is not in the proof, as prove_pre does
@@ -447,21 +342,22 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
             if (tables[t].air->preprocessed_width) key_of[t] = ki++;
         challenger.observe_commitment(key->data->root);
     }
-
-    // one commit of every trace; the row-major ones stay alive for the LogUp builder (the LDE stage only reads them)
-    std::vector<DeviceMatrix> tv;
-    for (MultiBusTable& t : tables) tv.push_back(std::move(t.trace));
-    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, std::vector<uint32_t>(T, 1u), true, /*keep_row_major=*/true);
-    for (size_t t = 0; t < T; t++)
-        if (!tables[t].air->aux_width) tv[t].buf.reset();  // a plain table's rows are not read again
-    challenger.observe_commitment(trace_data->root);
     std::vector<size_t> aux_of(T, ~(size_t)0), aux_tables;
     for (size_t t = 0; t < T; t++)
         if (tables[t].air->aux_width) {
             aux_of[t] = aux_tables.size();
             aux_tables.push_back(t);
         }
-    const size_t A = aux_tables.size();  // 0 (a key proof only): no samples, no aux commitment
+    const size_t A = aux_tables.size();  // 0: no samples, no aux commitment
+
+    // one commit of every trace on its natural domain (shift 1); with an aux table the row-major ones stay alive for
+    // the LogUp builder (the LDE stage only reads them)
+    std::vector<DeviceMatrix> tv;
+    for (MultiBusTable& t : tables) tv.push_back(std::move(t.trace));
+    std::unique_ptr<PcsData> trace_data = pcs.commit(tv, std::vector<uint32_t>(T, 1u), true, /*keep_row_major=*/A > 0);
+    for (size_t t = 0; t < T; t++)
+        if (!tables[t].air->aux_width) tv[t].buf.reset();  // a plain table's rows are not read again
+    challenger.observe_commitment(trace_data->root);
     uint32_t challenges[8] = {0};
     for (int k = 0; A && k < 2; k++) {  // gamma, beta: one tuple encoding on the whole bus
         const Ef c = challenger.sample();
@@ -516,7 +412,7 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
         if (key_of[t] != ~(size_t)0) {
             const ColMat& m = key->data->ldes[key_of[t]];
             TS_REQUIRE(m.width == tables[t].air->preprocessed_width && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
-                       "prove_multi_key: a key matrix has another shape than its table's");
+                       name + ": a key matrix has another shape than its table's");
             side.m[side.n++] = &m;
         }
         if (aux_of[t] != ~(size_t)0) {
@@ -524,7 +420,7 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
             pis.insert(pis.end(), &exposed[4 * aux_of[t]], &exposed[4 * aux_of[t]] + 4);
             const ColMat& m = aux_data->ldes[aux_of[t]];
             TS_REQUIRE(m.width == tables[t].air->aux_width && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
-                       "prove_multi: a committed aux matrix has another shape than its table's");
+                       name + ": a committed aux matrix has another shape than its table's");
             side.m[side.n++] = &m;
         }
         std::vector<DeviceMatrix> c = pcs.quotient_chunks_slab(trace_data->ldes[t], st[t].log_degree, TwoAdicFriPcs::Slab{},
@@ -567,7 +463,7 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
         for (uint32_t c = 0; c < st[t].qd; c++, qi++) {
             const ColMat& m = quotient_data->ldes[qi];
             TS_REQUIRE(m.width == 4 && m.height == (1ull << st[t].log_N), TS_ERR_INVARIANT,
-                       "prove_multi_bus: a committed chunk has another shape than its table's");
+                       name + ": a committed chunk has another shape than its table's");
             mats.push_back(OpenMat{&m, (unsigned)rounds.size(), st[t].log_degree, false, first});
             first += 4;
         }
@@ -582,7 +478,7 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
     for (size_t t = 0; t < T; t++)
         shapes.push_back({st[t].log_degree, st[t].w, st[t].qd, tables[t].air->aux_width, tables[t].air->n_exposed,
                           tables[t].air->preprocessed_width});
-    pw.header_multi(shapes, key ? 8 : 7);
+    pw.header_multi(shapes, version);
     pw.commitment(trace_data->root, 8);
     if (A) {
         pw.commitment(aux_data->root, 8);
@@ -594,15 +490,17 @@ static std::vector<uint32_t> prove_multi_phased(TwoAdicFriPcs& pcs, BfChallenger
     return pf;
 }
 
+std::vector<uint32_t> prove_multi(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables) {
+    return prove_multi_versioned(pcs, challenger, tables, nullptr, 6);
+}
+
 std::vector<uint32_t> prove_multi_bus(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables) {
-    check_multi_bus_statement(pcs.fri(), tables);
-    return prove_multi_phased(pcs, challenger, tables, nullptr);
+    return prove_multi_versioned(pcs, challenger, tables, nullptr, 7);
 }
 
 std::vector<uint32_t> prove_multi_key(TwoAdicFriPcs& pcs, BfChallenger& challenger, std::vector<MultiBusTable>& tables,
                                       const MultiKey& key) {
-    check_multi_key_statement(pcs.fri(), tables, &key);
-    return prove_multi_phased(pcs, challenger, tables, &key);
+    return prove_multi_versioned(pcs, challenger, tables, &key, 8);
 }
 
 }  // namespace ts

@@ -542,123 +542,57 @@ static bool ood_holds(const AirProgram& air, unsigned degree_bits, Ef zeta, Ef a
 }
 
 // ------------------------------------------------------------------ verify, several tables in one proof
-// The verifier of prove_multi (prove_multi.cpp), TSPF v6: [magic, 6, T], T x [log_degree, width, qd], the two
-// roots, the opened values in (round, matrix, point, column) order, the FriProof.  Replays the transcript, runs
-// the out-of-domain check of verify_impl per table on that table's domain, then Pcs::verify over the two rounds.
-int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
-                 const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words) {
-    const size_t T = airs.size();
-    if (T == 0 || T > MAX_MULTI_TABLES || public_values.size() != T) return 1;
-    for (size_t t = 0; t < T; t++)
-        if (!airs[t] || airs[t]->preprocessed_width || airs[t]->aux_width || public_values[t].size() != airs[t]->n_public)
-            return 1;
-    Reader rb{proof, n_words};
-    if (rb.get() != TSPF_MAGIC || rb.get() != 6u) return 9;
-    const uint32_t pT = rb.get();
-    if (rb.bad) return 9;
-    if (pT != T) return 1;
-    const uint32_t* shapes = rb.take(3 * T);
-    if (rb.bad) return 9;
-    size_t n_vals = 0;  // opened EF4 values
-    for (size_t t = 0; t < T; t++) {
-        if (shapes[3 * t] > 27) return 9;
-        if (shapes[3 * t + 1] != airs[t]->width || shapes[3 * t + 2] != (1u << airs[t]->log_quotient_degree)) return 1;
-        n_vals += 2 * (size_t)airs[t]->width + 4 * (size_t)shapes[3 * t + 2];
-    }
-    const uint32_t* trace_root = rb.take(8);
-    const uint32_t* quot_root = rb.take(8);
-    const uint32_t* vals = rb.take(4 * n_vals);
-    if (rb.bad) return 9;
-    for (size_t k = 0; k < 4 * n_vals; k++)
-        if (vals[k] >= P) return 9;
-    // (the proof is a word stream: Ef is 16-byte aligned, the words are not)
-    std::vector<Ef> ov(n_vals);
-    memcpy((void*)ov.data(), vals, 16 * n_vals);
-
-    challenger.observe((uint32_t)T);
-    for (size_t t = 0; t < T; t++) challenger.observe(shapes[3 * t]);
-    challenger.observe_commitment(trace_root);
-    const Ef alpha = challenger.sample();
-    challenger.observe_commitment(quot_root);
-    const Ef zeta = challenger.sample();
-
-    PcsRoundClaim r0, r1;
-    r0.root = trace_root;
-    r1.root = quot_root;
-    size_t at = 0, qat = 0;
-    for (size_t t = 0; t < T; t++) qat += 2 * (size_t)airs[t]->width;  // the chunks' values follow every trace's
-    for (size_t t = 0; t < T; t++) {
-        const unsigned degree_bits = shapes[3 * t];
-        const uint32_t w = airs[t]->width, qd = shapes[3 * t + 2];
-        const Ef zeta_next = c_mul_base(zeta, two_adic_generator(degree_bits));
-        const std::vector<Ef> tl(ov.begin() + at, ov.begin() + at + w), tn(ov.begin() + at + w, ov.begin() + at + 2 * w);
-        const std::vector<Ef> qc(ov.begin() + qat, ov.begin() + qat + 4 * (size_t)qd);
-        if (!ood_holds(*airs[t], degree_bits, zeta, alpha, nullptr, nullptr, nullptr, nullptr, tl.data(), tn.data(), qc,
-                       public_values[t]))
-            return 7;
-        r0.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, w, {zeta, zeta_next}, {tl, tn}});
-        for (uint32_t c = 0; c < qd; c++)
-            r1.mats.push_back(PcsMatClaim{degree_bits + fri.log_blowup, 4, {zeta},
-                                          {std::vector<Ef>(qc.begin() + 4 * (size_t)c, qc.begin() + 4 * (size_t)c + 4)}});
-        at += 2 * (size_t)w;
-        qat += 4 * (size_t)qd;
-    }
-    // the counts that lead the FriProof belong to the shape this format fixes (verdict 1, like the header's): R
-    // commit-phase roots for the tallest table, then num_queries answers
-    Reader fr{proof + rb.pos, n_words - rb.pos};
-    const uint32_t R = fr.get();
-    if (fr.bad) return 9;
-    unsigned log_max = 0;
-    for (size_t t = 0; t < T; t++) log_max = std::max<unsigned>(log_max, shapes[3 * t]);
-    if (R != log_max) return 1;
-    fr.take(8 * (size_t)R);
-    const uint32_t Q = fr.get();
-    if (fr.bad) return 9;
-    if (Q != fri.num_queries) return 1;
-    return fri_verify_impl(fri, challenger, {r0, r1}, false, proof + rb.pos, n_words - rb.pos);
-}
-
-// ------------------------------------------------------------------ verify, several tables and a LogUp bus
-// The verifier of prove_multi_bus (prove_multi.cpp), TSPF v7: [magic, 7, T], T x [log_degree, width, qd, aux_width,
-// n_exposed], trace root, aux root, the exposed words (four per aux table, table order), quotient root, the opened
-// values in (round, matrix, point, column) order over (aux matrices, traces, chunks), the FriProof.  verify_multi
-// with the challenge phase of verify_impl: gamma and beta once for every table, the aux root and the exposed words,
-// the out-of-domain check per table over (aux, trace) with pis ++ challenges ++ that table's exposed words.
+// The verifier of the multi-table provers (prove_multi.cpp), one body for three formats:
+//   TSPF v6 (prove_multi): [magic, 6, T], T x [log_degree, width, qd], trace root, quotient root, the opened values
+//     in (round, matrix, point, column) order over (traces, chunks), the FriProof.  Plain tables only.
+//   TSPF v7 (prove_multi_bus): T x [.., aux_width, n_exposed]; behind the trace root the aux root and the exposed
+//     words (four per aux table, table order); the aux matrices' round before the traces'.  No preprocessed columns,
+//     at least one aux table.
+//   TSPF v8 (prove_multi_key): a sixth header word per table (the preprocessed width), the key root observed after
+//     the shapes (it is not in the proof), the key's round first of all.  At least one table with preprocessed
+//     columns; without an aux table the proof holds no aux root and no exposed words, and no challenge is sampled
+//     before alpha.
+// Replays the transcript -- with aux tables the challenge phase of verify_impl: gamma and beta once for every table,
+// the aux root and the exposed words -- runs the out-of-domain check of verify_impl per table on that table's domain
+// over (key, aux, trace) with pis ++ challenges ++ that table's exposed words, then Pcs::verify over the rounds.
 // `exposed` receives the proof's exposed words and `bus_sum` their EF4 sum over the tables on acceptance; whether
 // the bus balances (bus_sum == 0) is the caller's statement, as verify_aux leaves it.
-// One body for v7 (key_root == nullptr) and v8 (verify_multi_key below).
-static int verify_multi_phased(const FriConfig& fri, BfChallenger& challenger, const uint32_t* key_root,
-                               const std::vector<const AirProgram*>& airs,
-                               const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof,
-                               size_t n_words, std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
+static int verify_multi_impl(const FriConfig& fri, BfChallenger& challenger, uint32_t version, const uint32_t* key_root,
+                             const std::vector<const AirProgram*>& airs,
+                             const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof,
+                             size_t n_words, std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
     const size_t T = airs.size();
-    const size_t SW = key_root ? 6 : 5;  // header words per table
+    const size_t SW = version == 6 ? 3 : version == 7 ? 5 : 6;  // header words per table
     if (T == 0 || T > MAX_MULTI_TABLES || public_values.size() != T) return 1;
     size_t A = 0, K = 0;
     for (size_t t = 0; t < T; t++) {
         if (!airs[t] || public_values[t].size() != airs[t]->n_public) return 1;
         const AirProgram& a = *airs[t];
-        if (a.aux_width ? (a.n_challenges != 2 || a.n_exposed != 4) : (a.n_challenges || a.n_exposed)) return 1;
+        if (version > 6 && (a.aux_width ? (a.n_challenges != 2 || a.n_exposed != 4) : (a.n_challenges || a.n_exposed)))
+            return 1;
         A += a.aux_width ? 1 : 0;
         K += a.preprocessed_width ? 1 : 0;
     }
-    if (key_root ? K == 0 : (K != 0 || A == 0)) return 1;
+    if (version == 6 ? (A || K) : version == 7 ? (K || !A) : !K) return 1;
     Reader rb{proof, n_words};
-    if (rb.get() != TSPF_MAGIC || rb.get() != (key_root ? 8u : 7u)) return 9;
+    if (rb.get() != TSPF_MAGIC || rb.get() != version) return 9;
     const uint32_t pT = rb.get();
     if (rb.bad) return 9;
     if (pT != T) return 1;
     const uint32_t* shapes = rb.take(SW * T);
     if (rb.bad) return 9;
     size_t n_vals = 0;  // opened EF4 values
+    unsigned log_max = 0;
     for (size_t t = 0; t < T; t++) {
         const uint32_t* sh = shapes + SW * t;
         if (sh[0] > 27) return 9;
-        if (sh[1] != airs[t]->width || sh[2] != (1u << airs[t]->log_quotient_degree) || sh[3] != airs[t]->aux_width ||
-            sh[4] != airs[t]->n_exposed || (key_root && sh[5] != airs[t]->preprocessed_width))
+        if (sh[1] != airs[t]->width || sh[2] != (1u << airs[t]->log_quotient_degree) ||
+            (SW > 3 && (sh[3] != airs[t]->aux_width || sh[4] != airs[t]->n_exposed)) ||
+            (SW > 5 && sh[5] != airs[t]->preprocessed_width))
             return 1;
         n_vals += 2 * (size_t)airs[t]->preprocessed_width + 2 * (size_t)airs[t]->aux_width + 2 * (size_t)airs[t]->width +
                   4 * (size_t)sh[2];
+        log_max = std::max<unsigned>(log_max, sh[0]);
     }
     const uint32_t* trace_root = rb.take(8);
     const uint32_t* aux_root = A ? rb.take(8) : nullptr;
@@ -679,7 +613,7 @@ static int verify_multi_phased(const FriConfig& fri, BfChallenger& challenger, c
     if (key_root) challenger.observe_commitment(key_root);
     challenger.observe_commitment(trace_root);
     uint32_t challenges[8] = {0};
-    if (A) {  // the challenge phase, skipped whole by a key proof without aux tables
+    if (A) {  // the challenge phase, skipped whole by a proof without aux tables
         for (int k = 0; k < 2; k++) {
             const Ef c = challenger.sample();
             memcpy(challenges + 4 * k, c.c, 16);
@@ -733,12 +667,11 @@ static int verify_multi_phased(const FriConfig& fri, BfChallenger& challenger, c
         at += 2 * (size_t)w;
         qat += 4 * (size_t)qd;
     }
-    // the counts that lead the FriProof belong to the shape this format fixes, as in verify_multi
+    // the counts that lead the FriProof belong to the shape this format fixes (verdict 1, like the header's): R
+    // commit-phase roots for the tallest table, then num_queries answers
     Reader fr{proof + rb.pos, n_words - rb.pos};
     const uint32_t R = fr.get();
     if (fr.bad) return 9;
-    unsigned log_max = 0;
-    for (size_t t = 0; t < T; t++) log_max = std::max<unsigned>(log_max, shapes[SW * t]);
     if (R != log_max) return 1;
     fr.take(8 * (size_t)R);
     const uint32_t Q = fr.get();
@@ -756,22 +689,24 @@ static int verify_multi_phased(const FriConfig& fri, BfChallenger& challenger, c
     return 0;
 }
 
+int verify_multi(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
+                 const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words) {
+    std::vector<uint32_t> exposed;  // none in a v6 proof
+    uint32_t bus_sum[4];
+    return verify_multi_impl(fri, challenger, 6, nullptr, airs, public_values, proof, n_words, exposed, bus_sum);
+}
+
 int verify_multi_bus(const FriConfig& fri, BfChallenger& challenger, const std::vector<const AirProgram*>& airs,
                      const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof, size_t n_words,
                      std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
-    return verify_multi_phased(fri, challenger, nullptr, airs, public_values, proof, n_words, exposed, bus_sum);
+    return verify_multi_impl(fri, challenger, 7, nullptr, airs, public_values, proof, n_words, exposed, bus_sum);
 }
 
-// ------------------------------------------------------------------ verify, several tables, a bus and a key
-// The verifier of prove_multi_key (prove_multi.cpp), TSPF v8: v7 with a sixth header word per table (the
-// preprocessed width), the key root observed after the shapes (it is not in the proof), the preprocessed opened values
-// in each table's out-of-domain check, and the key's round first among three or four.  Without an aux table the proof
-// holds no aux root and no exposed words, and no challenge is sampled before alpha.
 int verify_multi_key(const FriConfig& fri, BfChallenger& challenger, const uint32_t key_root[8],
                      const std::vector<const AirProgram*>& airs, const std::vector<std::vector<uint32_t>>& public_values,
                      const uint32_t* proof, size_t n_words, std::vector<uint32_t>& exposed, uint32_t bus_sum[4]) {
     if (!key_root) return 1;
-    return verify_multi_phased(fri, challenger, key_root, airs, public_values, proof, n_words, exposed, bus_sum);
+    return verify_multi_impl(fri, challenger, 8, key_root, airs, public_values, proof, n_words, exposed, bus_sum);
 }
 
 }  // namespace ts

@@ -14,7 +14,7 @@ read like the reference's own:
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields as dataclass_fields
 
 import numpy as np
 
@@ -888,6 +888,45 @@ class QueryProof:
     commit_phase_openings: list
 
 
+class _Words:
+    """The words of a proof, taken in order: ``take(n)`` raises ``ValueError`` past the end."""
+
+    def __init__(self, w):
+        self.w, self.pos = w, 0
+
+    def __call__(self, n):
+        out = self.w[self.pos:self.pos + n]
+        if len(out) != n:
+            raise ValueError("truncated proof")
+        self.pos += n
+        return out
+
+
+def _parse_fri_tail(take: _Words, R_shape) -> dict:
+    """The FriProof (fri/src/proof.rs:13-21) that ends every TSPF format, and nothing behind it: the commit-phase
+    roots (``R_shape`` words each: (8,), or (num_queries, 8) over taptrees), the query proofs, the final polynomial
+    and the proof-of-work witness."""
+    R = int(take(1)[0])
+    d = {"commit_phase_commits": take(int(np.prod(R_shape)) * R).reshape(R, *R_shape), "query_proofs": []}
+    for _ in range(int(take(1)[0])):
+        batches = []
+        for _ in range(int(take(1)[0])):
+            vals = [take(int(take(1)[0])) for _ in range(int(take(1)[0]))]
+            plen = int(take(1)[0])
+            batches.append(BatchOpening(vals, take(8 * plen).reshape(plen, 8)))
+        steps = []
+        for _ in range(R):
+            vals = take(8).reshape(2, 4)
+            plen = int(take(1)[0])
+            steps.append((vals, take(8 * plen).reshape(plen, 8)))
+        d["query_proofs"].append(QueryProof(batches, steps))
+    d["final_poly"] = take(4)
+    d["pow_witness"] = int(take(1)[0])
+    if take.pos != len(take.w):
+        raise ValueError("trailing words in proof")
+    return d
+
+
 class Proof:
     """reference uni-stark/src/proof.rs:17-37 (+ FriProof fri/src/proof.rs:13-21) over the TSPF v1
     words the library writes; ``words`` keeps the wire form.  The structured fields (``degree_bits``,
@@ -942,17 +981,7 @@ class Proof:
         return pf
 
     def _parse(self) -> None:
-        w = self.words
-        pos = 0
-
-        def take(n):
-            nonlocal pos
-            out = w[pos:pos + n]
-            if len(out) != n:
-                raise ValueError("truncated proof")
-            pos += n
-            return out
-
+        take = _Words(self.words)
         magic, version, degree_bits, width, qd = (int(x) for x in take(5))
         if magic != TSPF_MAGIC or version not in (1, 2, 3, 4, 5):
             raise ValueError("not a TSPF v1/v2/v3/v4/v5 proof")
@@ -969,7 +998,7 @@ class Proof:
         # opened preprocessed rows, then the aux rows, lead the opened values (four BatchOpenings per query)
         if version == 5:
             pw = int(take(1)[0])
-        d = {"degree_bits": degree_bits, "query_proofs": [], "version": version, "preprocessed_width": pw,
+        d = {"degree_bits": degree_bits, "version": version, "preprocessed_width": pw,
              "aux_width": aw, "n_challenges": nc, "aux_commit": None, "exposed": np.zeros(0, dtype=np.uint32)}
         if version in (4, 5):
             d["trace_commit"] = take(8)
@@ -987,28 +1016,7 @@ class Proof:
         d["trace_local"] = take(4 * width).reshape(width, 4)
         d["trace_next"] = take(4 * width).reshape(width, 4)
         d["quotient_chunks"] = take(16 * qd).reshape(qd, 4, 4)
-        R = int(take(1)[0])
-        d["commit_phase_commits"] = (take(8 * R).reshape(R, 8) if version != 2
-                                     else take(8 * nr * R).reshape(R, nr, 8))
-        Q = int(take(1)[0])
-        for _ in range(Q):
-            nb = int(take(1)[0])
-            batches = []
-            for _ in range(nb):
-                nm = int(take(1)[0])
-                vals = [take(int(take(1)[0])) for _ in range(nm)]
-                plen = int(take(1)[0])
-                batches.append(BatchOpening(vals, take(8 * plen).reshape(plen, 8)))
-            steps = []
-            for _ in range(R):
-                vals = take(8).reshape(2, 4)
-                plen = int(take(1)[0])
-                steps.append((vals, take(8 * plen).reshape(plen, 8)))
-            d["query_proofs"].append(QueryProof(batches, steps))
-        d["final_poly"] = take(4)
-        d["pow_witness"] = int(take(1)[0])
-        if pos != len(w):
-            raise ValueError("trailing words in proof")
+        d.update(_parse_fri_tail(take, (8,) if version != 2 else (nr, 8)))
         self.__dict__.update(d)
 
 
@@ -1145,12 +1153,14 @@ class MultiProof:
 
     _FIELDS = ("tables", "trace_commit", "quotient_commit", "opened_words", "fri_words", "commit_phase_commits",
                "query_proofs", "final_poly", "pow_witness")
+    _VERSION = 6
+    _OPENING = MultiTableOpening
 
     def __init__(self, words):
         self.words = np.asarray(words, dtype=np.uint32)
 
     def __getattr__(self, name):  # only reached for attributes not set yet
-        if name in MultiProof._FIELDS:
+        if name in self._FIELDS:
             self._parse()
             return self.__dict__[name]
         raise AttributeError(name)
@@ -1163,47 +1173,39 @@ class MultiProof:
         return pf
 
     def _parse(self) -> None:
-        w = self.words
-        pos = 0
-
-        def take(n):
-            nonlocal pos
-            out = w[pos:pos + n]
-            if len(out) != n:
-                raise ValueError("truncated proof")
-            pos += n
-            return out
-
+        """The one parser of TSPF v6, v7 and v8, keyed on ``_VERSION``: per table v7 adds (aux_width, n_exposed) to
+        the header and v8 the preprocessed width; the aux root and the exposed words are there for v7 always and for
+        v8 with an aux table; the opened values are every key matrix's, every aux matrix's, every trace's, then every
+        chunk's."""
+        w, V = self.words, self._VERSION
+        take = _Words(w)
         magic, version, T = (int(x) for x in take(3))
-        if magic != TSPF_MAGIC or version != 6 or not 1 <= T <= 64:
-            raise ValueError("not a TSPF v6 proof")
-        shapes = take(3 * T).reshape(T, 3)
-        d = {"trace_commit": take(8), "quotient_commit": take(8), "query_proofs": []}
-        start = pos
-        locals_ = [(take(4 * int(wd)).reshape(-1, 4), take(4 * int(wd)).reshape(-1, 4)) for _, wd, _ in shapes]
-        d["tables"] = [MultiTableOpening(int(ld), int(wd), int(qd), tl, tn, take(16 * int(qd)).reshape(-1, 4, 4))
-                       for (ld, wd, qd), (tl, tn) in zip(shapes, locals_)]
-        d["opened_words"] = w[start:pos]
-        d["fri_words"] = w[pos:]
-        R = int(take(1)[0])
-        d["commit_phase_commits"] = take(8 * R).reshape(R, 8)
-        for _ in range(int(take(1)[0])):
-            batches = []
-            for _ in range(int(take(1)[0])):
-                vals = [take(int(take(1)[0])) for _ in range(int(take(1)[0]))]
-                plen = int(take(1)[0])
-                batches.append(BatchOpening(vals, take(8 * plen).reshape(plen, 8)))
-            steps = []
-            for _ in range(R):
-                vals = take(8).reshape(2, 4)
-                plen = int(take(1)[0])
-                steps.append((vals, take(8 * plen).reshape(plen, 8)))
-            d["query_proofs"].append(QueryProof(batches, steps))
-        d["final_poly"] = take(4)
-        d["pow_witness"] = int(take(1)[0])
-        if pos != len(w):
-            raise ValueError("trailing words in proof")
-        self.__dict__.update(d)
+        if magic != TSPF_MAGIC or version != V or not 1 <= T <= 64:
+            raise ValueError(f"not a TSPF v{V} proof")
+        SW = {6: 3, 7: 5, 8: 6}[V]
+        shapes = [tuple(int(x) for x in row) + (0,) * (6 - SW) for row in take(SW * T).reshape(T, SW)]
+        has_aux = V == 7 or any(aw for _, _, _, aw, _, _ in shapes)
+        d = {"trace_commit": take(8), "aux_commit": take(8) if has_aux else None}
+        d["exposed"] = take(sum(ne for _, _, _, aw, ne, _ in shapes if aw))
+        d["bus_sum"] = (d["exposed"].reshape(-1, 4).astype(np.uint64).sum(axis=0) % np.uint64(P)).astype(np.uint32)
+        d["quotient_commit"] = take(8)
+        start = take.pos
+        empty = (w[:0].reshape(0, 4),) * 2
+        prep = [(take(4 * pw).reshape(-1, 4), take(4 * pw).reshape(-1, 4)) if pw else empty for *_, pw in shapes]
+        aux = [(take(4 * aw).reshape(-1, 4), take(4 * aw).reshape(-1, 4)) if aw else empty
+               for _, _, _, aw, _, _ in shapes]
+        locals_ = [(take(4 * wd).reshape(-1, 4), take(4 * wd).reshape(-1, 4)) for _, wd, *_ in shapes]
+        d["tables"], e = [], 0
+        n_fields = len(dataclass_fields(self._OPENING))  # each opening class extends the one before
+        for (ld, wd, qd, aw, ne, pw), (pl, pn), (al, an), (tl, tn) in zip(shapes, prep, aux, locals_):
+            ex = d["exposed"][e:e + ne] if aw else w[:0]
+            e += ne if aw else 0
+            chunks = take(16 * qd).reshape(-1, 4, 4)
+            d["tables"].append(self._OPENING(*(ld, wd, qd, tl, tn, chunks, aw, ne, al, an, ex, pw, pl, pn)[:n_fields]))
+        d["opened_words"] = w[start:take.pos]
+        d["fri_words"] = w[take.pos:]
+        d.update(_parse_fri_tail(take, (8,)))
+        self.__dict__.update({k: d[k] for k in self._FIELDS})
 
 
 def _multi_capacity(shapes, fri: FriConfig) -> int:
@@ -1218,6 +1220,60 @@ def _multi_capacity(shapes, fri: FriConfig) -> int:
     return 3 + 3 * len(shapes) + 16 + 8 * w_total + 16 * n_chunks + 2 + 8 * R + Q * per_q + 5
 
 
+def _multi_tables_c(ctx, airs, traces, pis, logups, struct):
+    """The table array of the multi-table calls: ``struct`` is ``MultiTableC`` (``logups`` None) or
+    ``MultiBusTableC``.  ``BaseAir``s are compiled on ``ctx`` and arrays uploaded to it.  Returns ``(airs, traces,
+    tabs, keep)``; ``keep`` owns the public values and the specs ``tabs`` points at."""
+    T = len(airs)
+    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
+    tabs = (struct * max(T, 1))()
+    keep = [pis]
+    for k in range(T):
+        tabs[k].struct_size = C.sizeof(struct)
+        tabs[k].n_public = len(pis[k])
+        tabs[k].air = airs[k].h
+        tabs[k].trace = traces[k].h
+        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
+        if logups is not None and logups[k] is not None:
+            keep.append(logups[k]._spec_c())
+            tabs[k].logup = C.pointer(keep[-1][0])
+    return airs, traces, tabs, keep
+
+
+def _verify_multi_call(name, config, airs, challenger, proof, public_values, key_root=None, check_bus=False):
+    """``ts_verify_multi`` (nothing handed back), ``ts_verify_multi_bus`` and ``ts_verify_multi_key`` (``key_root``
+    leads the tables; both hand back the exposed words and their sum)."""
+    T = len(airs)
+    if len(public_values) != T:
+        raise ValueError(f"{name}: one public-value list per AIR")
+    pis = [_u32(p) for p in public_values]
+    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
+    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
+    root = None if key_root is None else _u32(key_root).reshape(-1)
+    if root is not None and len(root) != 8:
+        raise ValueError(f"{name}: the key root has eight words")
+    l = _lib.lib()
+    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
+    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
+    n_pub = _u32([len(p) for p in pis] or [0])
+    cfg = config.pcs.fri._c()
+    verdict = C.c_int(-1)
+    exposed, bus_sum = np.zeros(4 * max(T, 1), dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    outs = () if name == "verify_multi" else (_p(exposed), len(exposed), _p(bus_sum))
+    rc = getattr(l, "ts_" + name)(C.byref(cfg), challenger.h, *(() if root is None else (_p(root),)), handles, T, pv,
+                                  _p(n_pub), _p(words), len(words), *outs, C.byref(verdict))
+    if rc:
+        raise _lib.TsError(rc, (l.ts_last_error(None) or ("ts_" + name).encode()).decode())
+    if verdict.value != 0:
+        raise VerificationError(verdict.value)
+    if not outs:
+        return None
+    if check_bus and bus_sum.any():
+        raise ValueError(f"{name}: the exposed sums of the tables do not add up to zero: the bus does not balance")
+    return exposed[: 4 * sum(1 for a in airs if a.aux_width)], bus_sum
+
+
 def prove_multi(config: StarkConfig, airs, challenger: BfChallenger, traces, public_values) -> MultiProof:
     """``ts_prove_multi``: one proof over several plain AIR tables of mixed heights (TSPF v6).  ``airs``: one
     ``BaseAir`` or ``CompiledAir`` per table (no preprocessed, no aux columns); ``traces``: (n_t, w_t) arrays or
@@ -1229,46 +1285,22 @@ def prove_multi(config: StarkConfig, airs, challenger: BfChallenger, traces, pub
     T = len(airs)
     if len(traces) != T or len(public_values) != T:
         raise ValueError("prove_multi: one trace and one public-value list per AIR")
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
-    tabs = (_lib.MultiTableC * max(T, 1))()
-    for k in range(T):
-        tabs[k].struct_size = C.sizeof(_lib.MultiTableC)
-        tabs[k].n_public = len(pis[k])
-        tabs[k].air = airs[k].h
-        tabs[k].trace = traces[k].h
-        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
+    airs, traces, tabs, keep = _multi_tables_c(ctx, airs, traces, [_u32(p) for p in public_values], None,
+                                               _lib.MultiTableC)
     shapes = [(*t.dims(), a.log_quotient_degree) for t, a in zip(traces, airs)]
     out = _proof_buffer(ctx, _multi_capacity(shapes, pcs.fri) if T else 1)
     n_words = C.c_size_t()
     cfg = pcs.fri._c()
     ctx.check(ctx._l.ts_prove_multi(ctx.h, C.byref(cfg), challenger.h, tabs, T, _p(out), len(out),
                                     C.byref(n_words)))
+    del keep
     return MultiProof(out[: n_words.value].copy())
 
 
 def verify_multi(config: StarkConfig, airs, challenger: BfChallenger, proof, public_values) -> None:
     """``ts_verify_multi``; host only, no GPU (host-only ``CompiledAir``s serve, as in ``verify``).  Raises
     ``VerificationError``; returns None on acceptance."""
-    T = len(airs)
-    if len(public_values) != T:
-        raise ValueError("verify_multi: one public-value list per AIR")
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
-    l = _lib.lib()
-    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
-    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
-    n_pub = _u32([len(p) for p in pis] or [0])
-    cfg = config.pcs.fri._c()
-    verdict = C.c_int(-1)
-    rc = l.ts_verify_multi(C.byref(cfg), challenger.h, handles, T, pv, _p(n_pub), _p(words), len(words),
-                           C.byref(verdict))
-    if rc:
-        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_multi").decode())
-    if verdict.value != 0:
-        raise VerificationError(verdict.value)
+    _verify_multi_call("verify_multi", config, airs, challenger, proof, public_values)
 
 
 @dataclass
@@ -1290,72 +1322,7 @@ class MultiBusProof(MultiProof):
 
     _FIELDS = MultiProof._FIELDS + ("aux_commit", "exposed", "bus_sum")
     _VERSION = 7
-
-    def __getattr__(self, name):
-        if name in MultiBusProof._FIELDS:
-            self._parse()
-            return self.__dict__[name]
-        raise AttributeError(name)
-
-    def _parse(self) -> None:
-        w = self.words
-        pos = 0
-
-        def take(n):
-            nonlocal pos
-            out = w[pos:pos + n]
-            if len(out) != n:
-                raise ValueError("truncated proof")
-            pos += n
-            return out
-
-        magic, version, T = (int(x) for x in take(3))
-        V = self._VERSION  # 7; 8 (MultiKeyProof): a sixth word per table, the aux words only with an aux table
-        if magic != TSPF_MAGIC or version != V or not 1 <= T <= 64:
-            raise ValueError(f"not a TSPF v{V} proof")
-        SW = 6 if V == 8 else 5
-        shapes = [tuple(int(x) for x in row) + (0,) * (6 - SW) for row in take(SW * T).reshape(T, SW)]
-        has_aux = V == 7 or any(aw for _, _, _, aw, _, _ in shapes)
-        d = {"trace_commit": take(8), "aux_commit": take(8) if has_aux else None, "query_proofs": []}
-        d["exposed"] = take(sum(ne for _, _, _, aw, ne, _ in shapes if aw))
-        d["bus_sum"] = (d["exposed"].reshape(-1, 4).astype(np.uint64).sum(axis=0) % np.uint64(P)).astype(np.uint32)
-        d["quotient_commit"] = take(8)
-        start = pos
-        empty = (w[:0].reshape(0, 4),) * 2
-        prep = [(take(4 * pw).reshape(-1, 4), take(4 * pw).reshape(-1, 4)) if pw else empty for *_, pw in shapes]
-        aux = [(take(4 * aw).reshape(-1, 4), take(4 * aw).reshape(-1, 4)) if aw else empty
-               for _, _, _, aw, _, _ in shapes]
-        locals_ = [(take(4 * wd).reshape(-1, 4), take(4 * wd).reshape(-1, 4)) for _, wd, *_ in shapes]
-        d["tables"], e = [], 0
-        for (ld, wd, qd, aw, ne, pw), (pl, pn), (al, an), (tl, tn) in zip(shapes, prep, aux, locals_):
-            ex = d["exposed"][e:e + ne] if aw else w[:0]
-            e += ne if aw else 0
-            chunks = take(16 * qd).reshape(-1, 4, 4)
-            if V == 8:
-                d["tables"].append(MultiKeyTableOpening(ld, wd, qd, tl, tn, chunks, aw, ne, al, an, ex, pw, pl, pn))
-            else:
-                d["tables"].append(MultiBusTableOpening(ld, wd, qd, tl, tn, chunks, aw, ne, al, an, ex))
-        d["opened_words"] = w[start:pos]
-        d["fri_words"] = w[pos:]
-        R = int(take(1)[0])
-        d["commit_phase_commits"] = take(8 * R).reshape(R, 8)
-        for _ in range(int(take(1)[0])):
-            batches = []
-            for _ in range(int(take(1)[0])):
-                vals = [take(int(take(1)[0])) for _ in range(int(take(1)[0]))]
-                plen = int(take(1)[0])
-                batches.append(BatchOpening(vals, take(8 * plen).reshape(plen, 8)))
-            steps = []
-            for _ in range(R):
-                vals = take(8).reshape(2, 4)
-                plen = int(take(1)[0])
-                steps.append((vals, take(8 * plen).reshape(plen, 8)))
-            d["query_proofs"].append(QueryProof(batches, steps))
-        d["final_poly"] = take(4)
-        d["pow_witness"] = int(take(1)[0])
-        if pos != len(w):
-            raise ValueError("trailing words in proof")
-        self.__dict__.update(d)
+    _OPENING = MultiBusTableOpening
 
 
 def _multi_bus_capacity(shapes, fri: FriConfig) -> int:
@@ -1379,20 +1346,8 @@ def prove_multi_bus(config: StarkConfig, airs, challenger: BfChallenger, traces,
     T = len(airs)
     if len(traces) != T or len(public_values) != T or len(logups) != T:
         raise ValueError("prove_multi_bus: one trace, one public-value list and one LogUp (or None) per AIR")
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
-    tabs = (_lib.MultiBusTableC * max(T, 1))()
-    keep = []
-    for k in range(T):
-        tabs[k].struct_size = C.sizeof(_lib.MultiBusTableC)
-        tabs[k].n_public = len(pis[k])
-        tabs[k].air = airs[k].h
-        tabs[k].trace = traces[k].h
-        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
-        if logups[k] is not None:
-            keep.append(logups[k]._spec_c())
-            tabs[k].logup = C.pointer(keep[-1][0])
+    airs, traces, tabs, keep = _multi_tables_c(ctx, airs, traces, [_u32(p) for p in public_values], logups,
+                                               _lib.MultiBusTableC)
     shapes = [(*t.dims(), a.log_quotient_degree, lg.aux_width if lg is not None else 0)
               for t, a, lg in zip(traces, airs, logups)]
     out = _proof_buffer(ctx, _multi_bus_capacity(shapes, pcs.fri) if T else 1)
@@ -1408,29 +1363,7 @@ def verify_multi_bus(config: StarkConfig, airs, challenger: BfChallenger, proof,
     """``ts_verify_multi_bus``; host only.  Raises ``VerificationError`` on a rejected proof and, with ``check_bus``,
     ``ValueError`` when the exposed sums of the tables do not add up to zero (something sent on the bus is not
     received).  Returns ``(exposed, bus_sum)``: the exposed words, four per table with aux columns, and their sum."""
-    T = len(airs)
-    if len(public_values) != T:
-        raise ValueError("verify_multi_bus: one public-value list per AIR")
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
-    l = _lib.lib()
-    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
-    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
-    n_pub = _u32([len(p) for p in pis] or [0])
-    cfg = config.pcs.fri._c()
-    verdict = C.c_int(-1)
-    exposed, bus_sum = np.zeros(4 * max(T, 1), dtype=np.uint32), np.zeros(4, dtype=np.uint32)
-    rc = l.ts_verify_multi_bus(C.byref(cfg), challenger.h, handles, T, pv, _p(n_pub), _p(words), len(words),
-                               _p(exposed), len(exposed), _p(bus_sum), C.byref(verdict))
-    if rc:
-        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_multi_bus").decode())
-    if verdict.value != 0:
-        raise VerificationError(verdict.value)
-    n_aux = sum(1 for a in airs if a.aux_width)
-    if check_bus and bus_sum.any():
-        raise ValueError("verify_multi_bus: the exposed sums of the tables do not add up to zero: the bus does not balance")
-    return exposed[: 4 * n_aux], bus_sum
+    return _verify_multi_call("verify_multi_bus", config, airs, challenger, proof, public_values, check_bus=check_bus)
 
 
 @dataclass
@@ -1448,6 +1381,7 @@ class MultiKeyProof(MultiBusProof):
     and ``bus_sum`` zero.  The key root is not in the proof."""
 
     _VERSION = 8
+    _OPENING = MultiKeyTableOpening
 
 
 class _BorrowedMatrix(DeviceMatrix):
@@ -1530,20 +1464,8 @@ def prove_multi_key(config: StarkConfig, key: MultiKey, airs, challenger: BfChal
     T = len(airs)
     if len(traces) != T or len(public_values) != T or len(logups) != T:
         raise ValueError("prove_multi_key: one trace, one public-value list and one LogUp (or None) per AIR")
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
-    tabs = (_lib.MultiBusTableC * max(T, 1))()
-    keep = []
-    for k in range(T):
-        tabs[k].struct_size = C.sizeof(_lib.MultiBusTableC)
-        tabs[k].n_public = len(pis[k])
-        tabs[k].air = airs[k].h
-        tabs[k].trace = traces[k].h
-        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
-        if logups[k] is not None:
-            keep.append(logups[k]._spec_c())
-            tabs[k].logup = C.pointer(keep[-1][0])
+    airs, traces, tabs, keep = _multi_tables_c(ctx, airs, traces, [_u32(p) for p in public_values], logups,
+                                               _lib.MultiBusTableC)
     shapes = [(*t.dims(), a.log_quotient_degree, lg.aux_width if lg is not None else 0, a.preprocessed_width)
               for t, a, lg in zip(traces, airs, logups)]
     out = _proof_buffer(ctx, _multi_key_capacity(shapes, pcs.fri) if T else 1)
@@ -1561,32 +1483,8 @@ def verify_multi_key(config: StarkConfig, key_root, airs, challenger: BfChalleng
     Raises ``VerificationError`` on a rejected proof and, with ``check_bus``, ``ValueError`` when the exposed sums do
     not add up to zero.  Returns ``(exposed, bus_sum)`` as ``verify_multi_bus`` does; both empty / zero without an aux
     table."""
-    T = len(airs)
-    if len(public_values) != T:
-        raise ValueError("verify_multi_key: one public-value list per AIR")
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(None, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    words = _u32(proof.words if isinstance(proof, MultiProof) else proof)
-    root = _u32(key_root).reshape(-1)
-    if len(root) != 8:
-        raise ValueError("verify_multi_key: the key root has eight words")
-    l = _lib.lib()
-    handles = (C.c_void_p * max(T, 1))(*[a.h for a in airs])
-    pv = (_lib.u32p * max(T, 1))(*[_p(p) if len(p) else None for p in pis])
-    n_pub = _u32([len(p) for p in pis] or [0])
-    cfg = config.pcs.fri._c()
-    verdict = C.c_int(-1)
-    exposed, bus_sum = np.zeros(4 * max(T, 1), dtype=np.uint32), np.zeros(4, dtype=np.uint32)
-    rc = l.ts_verify_multi_key(C.byref(cfg), challenger.h, _p(root), handles, T, pv, _p(n_pub), _p(words), len(words),
-                               _p(exposed), len(exposed), _p(bus_sum), C.byref(verdict))
-    if rc:
-        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_multi_key").decode())
-    if verdict.value != 0:
-        raise VerificationError(verdict.value)
-    n_aux = sum(1 for a in airs if a.aux_width)
-    if check_bus and bus_sum.any():
-        raise ValueError("verify_multi_key: the exposed sums of the tables do not add up to zero: the bus does not balance")
-    return exposed[: 4 * n_aux], bus_sum
+    return _verify_multi_call("verify_multi_key", config, airs, challenger, proof, public_values, key_root=key_root,
+                              check_bus=check_bus)
 
 
 def check_multi(key, airs, traces, public_values, logups, challenges, ctx: Context | None = None):
@@ -1604,20 +1502,8 @@ def check_multi(key, airs, traces, public_values, logups, challenges, ctx: Conte
     if ctx is None:
         ctx = key.ctx if key is not None else next((t.ctx for t in traces if isinstance(t, DeviceMatrix)), None)
     ctx = ctx or default_context()
-    pis = [_u32(p) for p in public_values]
-    airs = [CompiledAir(ctx, _air_tape_of(a, len(p))) if isinstance(a, BaseAir) else a for a, p in zip(airs, pis)]
-    traces = [t if isinstance(t, DeviceMatrix) else DeviceMatrix.upload(ctx, t) for t in traces]
-    tabs = (_lib.MultiBusTableC * max(T, 1))()
-    keep = []
-    for k in range(T):
-        tabs[k].struct_size = C.sizeof(_lib.MultiBusTableC)
-        tabs[k].n_public = len(pis[k])
-        tabs[k].air = airs[k].h
-        tabs[k].trace = traces[k].h
-        tabs[k].public_values = _p(pis[k]) if len(pis[k]) else None
-        if logups[k] is not None:
-            keep.append(logups[k]._spec_c())
-            tabs[k].logup = C.pointer(keep[-1][0])
+    airs, traces, tabs, keep = _multi_tables_c(ctx, airs, traces, [_u32(p) for p in public_values], logups,
+                                               _lib.MultiBusTableC)
     ch = _u32(challenges).reshape(-1)
     if len(ch) != 8:
         raise ValueError("check_multi: two challenges (eight words)")

@@ -275,3 +275,41 @@ def test_truncated_and_over_long_buffers_are_malformed(golden):
         rc, verdict = _verdict(cfg, root, airs, pis, words[:n])
         assert rc == TS_OK and verdict == 9, (n, rc, verdict)
     assert _verdict(cfg, root, airs, pis, np.concatenate([words, [0]])) == (TS_OK, 9)
+
+
+def _fri_tail_words(pf):
+    """The FriProof of a parsed proof, back in wire order."""
+    out = [len(pf.commit_phase_commits), *pf.commit_phase_commits.reshape(-1), len(pf.query_proofs)]
+    for q in pf.query_proofs:
+        out.append(len(q.input_proof))
+        for b in q.input_proof:
+            out.append(len(b.opened_values))
+            for v in b.opened_values:
+                out += [len(v), *v]
+            out += [len(b.opening_proof), *b.opening_proof.reshape(-1)]
+        for vals, path in q.commit_phase_openings:
+            out += [*vals.reshape(-1), len(path), *path.reshape(-1)]
+    return out + [*pf.final_poly, pf.pow_witness]
+
+
+@pytest.mark.parametrize("cls, load", [(ts.MultiProof, mc.load_golden), (ts.MultiBusProof, bc.load_golden),
+                                       (ts.MultiKeyProof, kc.load_golden)])
+def test_the_parsed_fields_are_the_words_in_wire_order(cls, load):
+    """One parser reads TSPF v6, v7 and v8: every word of each committed fixture lands in exactly one field, in order."""
+    from tapstark_amd.stark import TSPF_MAGIC
+    words = load()[3]
+    pf = cls.parse(words)
+    header = ("log_degree", "width", "qd", "aux_width", "n_exposed", "preprocessed_width")[:{6: 3, 7: 5, 8: 6}[cls._VERSION]]
+    out = [TSPF_MAGIC, cls._VERSION, len(pf.tables)]
+    for t in pf.tables:
+        out += [getattr(t, h) for h in header]
+    out += [*pf.trace_commit]
+    if cls._VERSION >= 7:  # both fixtures have aux tables: the v8 one carries its aux root too
+        assert pf.aux_commit is not None and len(pf.exposed) == 4 * sum(1 for t in pf.tables if t.aux_width)
+        out += [*pf.aux_commit, *pf.exposed]
+    out += [*pf.quotient_commit, *pf.opened_words, *_fri_tail_words(pf)]
+    assert np.array_equal(np.array(out, dtype=np.uint64), words)
+    assert np.array_equal(pf.fri_words, np.array(_fri_tail_words(pf), dtype=np.uint64))
+    for other in {ts.MultiProof, ts.MultiBusProof, ts.MultiKeyProof} - {cls}:
+        with pytest.raises(ValueError, match=f"not a TSPF v{other._VERSION} proof"):
+            other.parse(words)
