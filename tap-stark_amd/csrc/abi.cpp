@@ -81,29 +81,39 @@ std::vector<uint32_t> public_inputs(const uint32_t* values, uint32_t n) {
     return pis;
 }
 
-// Calls that take no preprocessed key refuse an AIR that needs one, before anything is consumed or launched.
-void no_preprocessed(const ts_air* air, const char* call) {
-    if (air->a.prog().aux_width)
-        throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has challenge-phase (aux) columns; "
-                                                 "prove it with ts_prove_aux (and ts_quotient_chunks_aux, "
-                                                 "ts_check_constraints_aux, ts_verify_aux)").c_str());
-    if (air->a.prog().preprocessed_width == 0) return;
-    throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has preprocessed columns; prove it with "
-                                             "ts_prove_pre (and ts_quotient_chunks_pre, ts_check_constraints_pre, "
-                                             "ts_verify_pre)").c_str());
-}
+// The four single-table formats.  The operations of a format are "ts_<operation><suffix>": prove, verify,
+// quotient_chunks, check_constraints.  DESIGN.md section 5 has the table of what each takes and refuses.
+struct SingleCall {
+    uint32_t version;    // the TSPF version its prove call writes and its verify call takes
+    const char* suffix;  // of the entry points' names
+    bool key;            // takes a preprocessed key (prove, quotient_chunks), its root (verify), the matrix (check)
+    bool aux;            // takes an aux source (prove), aux data (quotient_chunks), the matrix (check); verify hands
+                         // back the exposed words
+    // Three differences between the formats, kept as they are ("Kept differences"):
+    bool any_context;          // prove does not refuse a trace made on another context
+    bool own_height_text;      // prove words its key-height refusal itself; the others leave it to check_side_matrix
+    bool anonymous_key_texts;  // the AIR-kind and key refusals of prove and quotient_chunks do not name the entry point
 
-// ts_*_pre calls take no aux source either
-void no_aux(const ts_air* air, const char* call) {
-    if (air->a.prog().aux_width)
-        throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": the AIR has challenge-phase (aux) columns; "
-                                                 "prove it with ts_prove_aux").c_str());
-}
-// the ts_*_aux calls: aux columns together with a key would be a third matrix in the kernels
-void no_prep_with_aux(const ts_air* air, const char* call) {
-    if (air->a.prog().preprocessed_width)
-        throw ts::Error(ts::TS_ERR_UNSUPPORTED, (std::string(call) + ": preprocessed columns together with aux "
-                                                 "columns are not supported yet").c_str());
+    std::string name(const char* op) const { return std::string("ts_") + op + suffix; }
+    std::string keyed_name(const char* op) const {
+        return anonymous_key_texts ? "a call that takes a preprocessed key" : name(op);
+    }
+};
+constexpr SingleCall PLAIN{1, "", false, false, true, false, false}, PRE{3, "_pre", true, false, true, true, true},
+    AUX{4, "_aux", false, true, false, false, false}, PRE_AUX{5, "_pre_aux", true, true, false, false, false};
+
+// The one admission of an AIR to a single-table call (`call` names it in the texts), before anything is consumed or
+// launched: a call without an aux argument refuses aux columns, a call without a key argument preprocessed ones.
+void admit_air(const SingleCall& sc, const ts_air* air, const std::string& call) {
+    const ts::AirProgram& p = air->a.prog();
+    TS_REQUIRE(sc.aux || !p.aux_width, ts::TS_ERR_UNSUPPORTED,
+               call + ": the AIR has challenge-phase (aux) columns; prove it with ts_prove_aux" +
+                   (sc.key ? "" : " (and ts_quotient_chunks_aux, ts_check_constraints_aux, ts_verify_aux)"));
+    // (aux columns together with a key would be a third matrix in the kernels of the ts_*_aux calls)
+    TS_REQUIRE(sc.key || !p.preprocessed_width, ts::TS_ERR_UNSUPPORTED,
+               call + (sc.aux ? ": preprocessed columns together with aux columns are not supported yet"
+                              : ": the AIR has preprocessed columns; prove it with ts_prove_pre (and "
+                                "ts_quotient_chunks_pre, ts_check_constraints_pre, ts_verify_pre)"));
 }
 // public values ++ challenge words ++ exposed words, as the lowered program of a version-3 AIR indexes them
 std::vector<uint32_t> public_slots(const ts::AirProgram& p, const uint32_t* values, uint32_t n, const uint32_t* challenges,
@@ -133,11 +143,6 @@ const ts::PcsData* preprocessed_key_any(ts_ctx* ctx, const ts_air* air, const ts
                "preprocessed key: width differs from the AIR's preprocessed width");
     TS_REQUIRE(key->d->tree.ctx == &ctx->ctx, ts::TS_ERR_INVALID, "preprocessed key was made on another context");
     return key->d.get();
-}
-// the same for the ts_*_pre calls, which take no aux source
-const ts::PcsData* preprocessed_key(ts_ctx* ctx, const ts_air* air, const ts_pcs_data* key) {
-    no_aux(air, "a call that takes a preprocessed key");
-    return preprocessed_key_any(ctx, air, key, "a call that takes a preprocessed key");
 }
 
 // The committed aux trace of the calls that take one: null exactly when the AIR has no aux columns, else one
@@ -1083,26 +1088,53 @@ static void quotient_chunks(ts_ctx* ctx, const ts::AirProgram& p, const ts::Side
         chunks_out[c] = m.release();
     }
 }
+// The head of the four calls: the admission, then the side matrices the format takes, key first (the quotient over
+// (key, aux, trace)).  `key`, `aux_data`, `challenges` and `exposed` are null from a call that has no such argument.
+static ts_status single_quotient_chunks(const SingleCall& sc, ts_ctx* ctx, const ts_pcs_data* key,
+                                        const ts_pcs_data* aux_data, const ts_pcs_data* trace_data, uint32_t log_blowup,
+                                        const ts_air* air, const uint32_t* public_values, uint32_t n_public,
+                                        const uint32_t* challenges, const uint32_t* exposed, const uint32_t alpha[4],
+                                        ts_matrix** chunks_out) {
+    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) {
+        if (ctx) ctx->ctx.last_error = sc.name("quotient_chunks") + ": null argument";
+        return TS_ERR_INVALID;
+    }
+    return guard(ctx, [&] {
+        const std::string call = sc.keyed_name("quotient_chunks");
+        admit_air(sc, air, call);
+        ts::SideData side;
+        if (const ts::PcsData* k = sc.key ? preprocessed_key_any(ctx, air, key, call.c_str()) : nullptr) side.push_back(k);
+        const ts::AirProgram& p = ready_prog(air);
+        if (const ts::PcsData* a = sc.aux ? committed_aux(ctx, p, aux_data) : nullptr) side.push_back(a);
+        quotient_chunks(ctx, p, side, trace_data, log_blowup, public_values, n_public, challenges, exposed, alpha,
+                        chunks_out);
+    });
+}
 ts_status ts_quotient_chunks(ts_ctx* ctx, const ts_pcs_data* trace_data, uint32_t log_blowup,
                              const ts_air* air, const uint32_t* public_values, uint32_t n_public,
                              const uint32_t alpha[4], ts_matrix** chunks_out) {
-    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
-    return guard(ctx, [&] {
-        no_preprocessed(air, "ts_quotient_chunks");
-        quotient_chunks(ctx, ready_prog(air), {}, trace_data, log_blowup, public_values, n_public, nullptr, nullptr,
-                        alpha, chunks_out);
-    });
+    return single_quotient_chunks(PLAIN, ctx, nullptr, nullptr, trace_data, log_blowup, air, public_values, n_public,
+                                  nullptr, nullptr, alpha, chunks_out);
 }
 ts_status ts_quotient_chunks_pre(ts_ctx* ctx, const ts_pcs_data* preprocessed, const ts_pcs_data* trace_data,
                                  uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
                                  uint32_t n_public, const uint32_t alpha[4], ts_matrix** chunks_out) {
-    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
-    return guard(ctx, [&] {
-        ts::SideData side;
-        if (const ts::PcsData* key = preprocessed_key(ctx, air, preprocessed)) side.push_back(key);
-        quotient_chunks(ctx, ready_prog(air), side, trace_data, log_blowup, public_values, n_public, nullptr, nullptr,
-                        alpha, chunks_out);
-    });
+    return single_quotient_chunks(PRE, ctx, preprocessed, nullptr, trace_data, log_blowup, air, public_values, n_public,
+                                  nullptr, nullptr, alpha, chunks_out);
+}
+ts_status ts_quotient_chunks_aux(ts_ctx* ctx, const ts_pcs_data* aux_data, const ts_pcs_data* trace_data,
+                                 uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
+                                 uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                                 const uint32_t alpha[4], ts_matrix** chunks_out) {
+    return single_quotient_chunks(AUX, ctx, nullptr, aux_data, trace_data, log_blowup, air, public_values, n_public,
+                                  challenges, exposed, alpha, chunks_out);
+}
+ts_status ts_quotient_chunks_pre_aux(ts_ctx* ctx, const ts_pcs_data* key, const ts_pcs_data* aux_data,
+                                     const ts_pcs_data* trace_data, uint32_t log_blowup, const ts_air* air,
+                                     const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                     const uint32_t* exposed, const uint32_t alpha[4], ts_matrix** chunks_out) {
+    return single_quotient_chunks(PRE_AUX, ctx, key, aux_data, trace_data, log_blowup, air, public_values, n_public,
+                                  challenges, exposed, alpha, chunks_out);
 }
 
 ts_status ts_pcs_open_reduce(ts_ctx* ctx, const ts_fri_config* cfg, const ts_pcs_data* trace_data,
@@ -1260,46 +1292,7 @@ void ts_chal_state(const ts_challenger* c, uint32_t out[34]) {
     if (c && out) c->c.export_state(out);
 }
 
-// ------------------------------------------------------------------ prove
-ts_status ts_prove(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                   ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
-                   uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
-    if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) return TS_ERR_INVALID;
-    *n_words_out = 0;
-    return guard(ctx, [&] {
-        no_preprocessed(air, "ts_prove");
-        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        ts::DeviceMatrix m = take_trace(trace);
-        ts::StageTimer t(&ctx->ctx, "prove");
-        copy_proof(ts::prove(pcs, ready_prog(air), chal->c, std::move(m), pis), proof_out, cap_words, n_words_out);
-    });
-}
-
-// prove over (preprocessed key, trace): the key is an ordinary ts_pcs_data, read and never consumed.  Every
-// refusal about the key is made before the trace is taken and before any device work.
-ts_status ts_prove_pre(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                       const ts_pcs_data* preprocessed, ts_matrix* trace, const uint32_t* public_values,
-                       uint32_t n_public, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
-    if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) {
-        if (ctx) ctx->ctx.last_error = "ts_prove_pre: null argument";
-        return TS_ERR_INVALID;
-    }
-    *n_words_out = 0;
-    return guard(ctx, [&] {
-        const ts::PcsData* key = preprocessed_key(ctx, air, preprocessed);
-        const ts::FriConfig fri = load_cfg(cfg);
-        if (key)
-            TS_REQUIRE(trace->m.buf.p && key->ldes[0].height == trace->m.height << fri.log_blowup, ts::TS_ERR_INVALID,
-                       "preprocessed key: LDE height is not the trace height << log_blowup");
-        ts::TwoAdicFriPcs pcs(ctx->ctx, fri);
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        ts::DeviceMatrix m = take_trace(trace);
-        ts::StageTimer t(&ctx->ctx, "prove");
-        copy_proof(ts::prove(pcs, ready_prog(air), chal->c, std::move(m), pis, key, 3), proof_out, cap_words,
-                   n_words_out);
-    });
-}
+// (ts_prove and its three siblings: "prove, the four single-table formats" below, behind the aux callback they share)
 
 // ------------------------------------------------------------------ prove_stream
 // Throughput mode as ONE call: n_proofs independent proofs of one AIR on `n_lanes` contexts of a device, one
@@ -1321,7 +1314,7 @@ ts_status ts_prove_stream(ts_ctx* const* ctxs, const ts_air* const* airs, uint32
         if (!traces[i] || lane_of[i] >= n_lanes) return TS_ERR_INVALID;
     if (n_public && !public_values) return TS_ERR_INVALID;
     for (uint32_t l = 0; l < n_lanes; l++) {
-        const ts_status st = guard(ctxs[l], [&] { no_preprocessed(airs[l], "ts_prove_stream"); }, false);
+        const ts_status st = guard(ctxs[l], [&] { admit_air(PLAIN, airs[l], "ts_prove_stream"); }, false);
         if (st != TS_OK) return st;
     }
     const std::vector<uint32_t> pis(public_values, public_values + n_public);
@@ -1379,7 +1372,7 @@ ts_status ts_prove_batch(ts_ctx* const* ctxs, const ts_air* const* airs, uint32_
     for (uint32_t i = 0; i < n_items; i++)
         if (items[i].struct_size != sizeof(ts_batch_item)) return TS_ERR_INVALID;
     struct Plain : BatchCall<ts_batch_item> {
-        void refuse(uint32_t l) const { no_preprocessed(airs[l], name); }
+        void refuse(uint32_t l) const { admit_air(PLAIN, airs[l], name); }
         std::vector<uint32_t> prove(uint32_t, ts_batch_item&, ts::TwoAdicFriPcs& pcs, const ts::AirProgram& prog,
                                     ts::BfChallenger& chal, ts::DeviceMatrix trace, const std::vector<uint32_t>& pis,
                                     ItemOutcome&) const {
@@ -1418,7 +1411,7 @@ ts_status ts_prove_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_comm*
         return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
-        no_preprocessed(air, "ts_prove_sharded");
+        admit_air(PLAIN, air, "ts_prove_sharded");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts_comm cb = *comm;
@@ -1451,7 +1444,7 @@ ts_status ts_prove_tap(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
         return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
-        no_preprocessed(air, "ts_prove_tap");
+        admit_air(PLAIN, air, "ts_prove_tap");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
@@ -1471,7 +1464,7 @@ ts_status ts_prove_tap_sharded(ts_ctx* ctx, const ts_fri_config* cfg, const ts_c
         return TS_ERR_INVALID;
     *n_words_out = 0;
     return guard(ctx, [&] {
-        no_preprocessed(air, "ts_prove_tap_sharded");
+        admit_air(PLAIN, air, "ts_prove_tap_sharded");
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
@@ -1493,13 +1486,13 @@ ts_status ts_verify_tap(const ts_fri_config* cfg, const ts_air* air, ts_challeng
     if (!air || !chal || !proof || !verdict || !lock_scripts || !lock_offsets) return TS_ERR_INVALID;
     *verdict = -1;
     return guard(nullptr, [&] {
-        no_preprocessed(air, "ts_verify_tap");
+        admit_air(PLAIN, air, "ts_verify_tap");
         ts::FriConfig f = load_cfg(cfg);
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
         for (size_t i = 0; i < n_scripts; i++)
             TS_REQUIRE(lock_offsets[i + 1] >= lock_offsets[i], ts::TS_ERR_INVALID, "bad lock script offsets");
-        *verdict = ts::verify_tap(f, air->a.prog(), chal->c, proof, n_words, pis,
-                                  tap_locks(lock_scripts, lock_offsets, n_scripts));
+        const ts::TapLocks locks = tap_locks(lock_scripts, lock_offsets, n_scripts);
+        *verdict = ts::verify(2, f, air->a.prog(), chal->c, proof, n_words, pis, nullptr, nullptr, &locks);
     });
 }
 
@@ -1525,68 +1518,50 @@ static void check_constraints(ts_ctx* ctx, const ts::AirProgram& p, const ts::Si
     ctx->ctx.sync();
     *first_violation = v == ~0ull ? -1 : (int64_t)v;
 }
+// The head of the four calls: the admission, then the row-major side matrices the format takes, preprocessed first.
+// `preprocessed`, `aux`, `challenges` and `exposed` are null from a call that has no such argument.
+static ts_status single_check_constraints(const SingleCall& sc, ts_ctx* ctx, const ts_air* air,
+                                          const ts_matrix* preprocessed, const ts_matrix* aux, const ts_matrix* trace,
+                                          const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                          const uint32_t* exposed, int64_t* first_violation) {
+    if (!ctx || !air || !trace || !first_violation) {
+        if (ctx) ctx->ctx.last_error = sc.name("check_constraints") + ": null argument";
+        return TS_ERR_INVALID;
+    }
+    *first_violation = -1;
+    return guard(ctx, [&] {
+        admit_air(sc, air, sc.name("check_constraints"));
+        const ts::AirProgram& p = air->a.prog();
+        ts::SideRows side;
+        if (sc.key) add_side_rows(ctx, preprocessed, p.preprocessed_width, "preprocessed", trace, side);
+        if (sc.aux) add_side_rows(ctx, aux, p.aux_width, "aux", trace, side);
+        check_constraints(ctx, p, side, trace, public_values, n_public, challenges, exposed, first_violation);
+    });
+}
 ts_status ts_check_constraints(ts_ctx* ctx, const ts_air* air, const ts_matrix* trace,
                                const uint32_t* public_values, uint32_t n_public,
                                int64_t* first_violation) {
-    if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
-    *first_violation = -1;
-    return guard(ctx, [&] {
-        no_preprocessed(air, "ts_check_constraints");
-        check_constraints(ctx, air->a.prog(), {}, trace, public_values, n_public, nullptr, nullptr, first_violation);
-    });
+    return single_check_constraints(PLAIN, ctx, air, nullptr, nullptr, trace, public_values, n_public, nullptr, nullptr,
+                                    first_violation);
 }
 ts_status ts_check_constraints_pre(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
                                    const ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
                                    int64_t* first_violation) {
-    if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
-    *first_violation = -1;
-    return guard(ctx, [&] {
-        no_aux(air, "ts_check_constraints_pre");
-        const ts::AirProgram& p = air->a.prog();
-        ts::SideRows side;
-        add_side_rows(ctx, preprocessed, p.preprocessed_width, "preprocessed", trace, side);
-        check_constraints(ctx, p, side, trace, public_values, n_public, nullptr, nullptr, first_violation);
-    });
+    return single_check_constraints(PRE, ctx, air, preprocessed, nullptr, trace, public_values, n_public, nullptr,
+                                    nullptr, first_violation);
 }
-
-// ------------------------------------------------------------------ verify
-ts_status ts_verify(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                    const uint32_t* proof, size_t n_words, const uint32_t* public_values,
-                    uint32_t n_public, int* verdict) {
-    if (!air || !chal || !proof || !verdict) return TS_ERR_INVALID;
-    *verdict = -1;
-    return guard(nullptr, [&] {
-        no_preprocessed(air, "ts_verify");
-        ts::FriConfig f = load_cfg(cfg);
-        *verdict = ts::verify(f, air->a.prog(), chal->c, proof, n_words, public_inputs(public_values, n_public));
-    });
+ts_status ts_check_constraints_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* aux, const ts_matrix* trace,
+                                   const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
+                                   const uint32_t* exposed, int64_t* first_violation) {
+    return single_check_constraints(AUX, ctx, air, nullptr, aux, trace, public_values, n_public, challenges, exposed,
+                                    first_violation);
 }
-
-// host only, like ts_verify.  A proof of another TSPF version (verdict 9) or with another preprocessed width in
-// its header (verdict 1) is refused as an argument, TS_ERR_INVALID, with the verdict set.
-ts_status ts_verify_pre(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                        const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
-                        const uint32_t* public_values, uint32_t n_public, int* verdict) {
-    if (verdict) *verdict = -1;
-    return guard(nullptr, [&] {
-        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_pre: null argument");
-        no_aux(air, "ts_verify_pre");
-        const uint32_t pw = air->a.prog().preprocessed_width;
-        TS_REQUIRE((preprocessed_root != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
-                   pw ? "ts_verify_pre: null preprocessed root for an AIR with preprocessed columns"
-                      : "ts_verify_pre: a preprocessed root was given for an AIR without preprocessed columns");
-        ts::FriConfig f = load_cfg(cfg);
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        if (n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != 3) {
-            *verdict = 9;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre: not a TSPF v3 proof");
-        }
-        if (n_words >= 6 && proof[0] == ts::TSPF_MAGIC && proof[5] != pw) {
-            *verdict = 1;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre: the proof's preprocessed width is not the AIR's");
-        }
-        *verdict = ts::verify_pre(f, air->a.prog(), chal->c, preprocessed_root, proof, n_words, pis);
-    });
+ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
+                                       const ts_matrix* aux, const ts_matrix* trace, const uint32_t* public_values,
+                                       uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
+                                       int64_t* first_violation) {
+    return single_check_constraints(PRE_AUX, ctx, air, preprocessed, aux, trace, public_values, n_public, challenges,
+                                    exposed, first_violation);
 }
 
 // ------------------------------------------------------------------ challenge-phase (aux) columns
@@ -1598,36 +1573,7 @@ ts_status ts_air_aux_info(const ts_air* air, uint32_t* aux_width, uint32_t* n_ch
     return TS_OK;
 }
 
-ts_status ts_quotient_chunks_aux(ts_ctx* ctx, const ts_pcs_data* aux_data, const ts_pcs_data* trace_data,
-                                 uint32_t log_blowup, const ts_air* air, const uint32_t* public_values,
-                                 uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
-                                 const uint32_t alpha[4], ts_matrix** chunks_out) {
-    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) return TS_ERR_INVALID;
-    return guard(ctx, [&] {
-        no_prep_with_aux(air, "ts_quotient_chunks_aux");
-        const ts::AirProgram& p = ready_prog(air);
-        ts::SideData side;
-        if (const ts::PcsData* a = committed_aux(ctx, p, aux_data)) side.push_back(a);
-        quotient_chunks(ctx, p, side, trace_data, log_blowup, public_values, n_public, challenges, exposed, alpha,
-                        chunks_out);
-    });
-}
-
-ts_status ts_check_constraints_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* aux, const ts_matrix* trace,
-                                   const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
-                                   const uint32_t* exposed, int64_t* first_violation) {
-    if (!ctx || !air || !trace || !first_violation) return TS_ERR_INVALID;
-    *first_violation = -1;
-    return guard(ctx, [&] {
-        no_prep_with_aux(air, "ts_check_constraints_aux");
-        const ts::AirProgram& p = air->a.prog();
-        ts::SideRows side;
-        add_side_rows(ctx, aux, p.aux_width, "aux", trace, side);
-        check_constraints(ctx, p, side, trace, public_values, n_public, challenges, exposed, first_violation);
-    });
-}
-
-// The callback's failure, carried through ts::prove_aux as an exception of its own so that its status -- any
+// The callback's failure, carried through ts::prove as an exception of its own so that its status -- any
 // value the host chose -- reaches the caller unchanged.
 namespace {
 struct AuxCallbackFailed {
@@ -1662,64 +1608,150 @@ ts::Error callback_failure(ts_ctx* ctx, ts_status cb_status, const char* call) {
 }
 }  // namespace
 
-ts_status ts_prove_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                       ts_matrix* trace, const uint32_t* public_values, uint32_t n_public, ts_aux_fn aux_fn,
-                       void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+// ------------------------------------------------------------------ prove, the four single-table formats
+// The key is an ordinary ts_pcs_data, part of the statement, read and never consumed; the aux source is the host's
+// callback.  Every refusal is made before the trace is taken and before any device work; the callback's own status
+// wins over the call's.
+static ts_status single_prove(const SingleCall& sc, ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air,
+                              ts_challenger* chal, const ts_pcs_data* key, ts_matrix* trace,
+                              const uint32_t* public_values, uint32_t n_public, ts_aux_fn aux_fn, void* user,
+                              uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    const std::string call = sc.name("prove");
     if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) {
-        if (ctx) ctx->ctx.last_error = "ts_prove_aux: null argument";
+        if (ctx) ctx->ctx.last_error = call + ": null argument";
         return TS_ERR_INVALID;
     }
     *n_words_out = 0;
     ts_status cb_status = TS_OK;
     const ts_status st = guard(ctx, [&] {
-        no_prep_with_aux(air, "ts_prove_aux");
+        const std::string keyed = sc.keyed_name("prove");
+        admit_air(sc, air, keyed);
+        const ts::PcsData* k = sc.key ? preprocessed_key_any(ctx, air, key, keyed.c_str()) : nullptr;
         const ts::AirProgram& p = ready_prog(air);
-        TS_REQUIRE((aux_fn != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
-                   p.aux_width ? "ts_prove_aux: null aux_fn for an AIR with aux columns"
-                               : "ts_prove_aux: an aux_fn was given for an AIR without aux columns");
+        if (sc.aux)
+            TS_REQUIRE((aux_fn != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
+                       call + (p.aux_width ? ": null aux_fn for an AIR with aux columns"
+                                           : ": an aux_fn was given for an AIR without aux columns"));
         ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
+        // the key's height is known against the trace's before the trace is consumed
+        const unsigned log_blowup = pcs.fri().log_blowup;
+        if (k && sc.own_height_text)
+            TS_REQUIRE(trace->m.buf.p && k->ldes[0].height == trace->m.height << log_blowup, ts::TS_ERR_INVALID,
+                       "preprocessed key: LDE height is not the trace height << log_blowup");
         const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        TS_REQUIRE(trace->m.buf.ctx == &ctx->ctx || !trace->m.buf.p, ts::TS_ERR_INVALID,
-                   "trace was made on another context");
+        if (!sc.any_context)
+            TS_REQUIRE(trace->m.buf.ctx == &ctx->ctx || !trace->m.buf.p, ts::TS_ERR_INVALID,
+                       "trace was made on another context");
+        if (k && !sc.own_height_text) {
+            TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
+            ts::check_side_matrix(*k, p, 0, trace->m.height << log_blowup);
+        }
         ts::DeviceMatrix m = take_trace(trace);
         ts::AuxSource source;
-        if (aux_fn) source = callback_aux_source(ctx, p, aux_fn, user, cb_status, "ts_prove_aux");
+        if (aux_fn) source = callback_aux_source(ctx, p, aux_fn, user, cb_status, call.c_str());
         ts::StageTimer t(&ctx->ctx, "prove");
         try {
-            copy_proof(ts::prove_aux(pcs, p, chal->c, std::move(m), pis, source), proof_out, cap_words, n_words_out);
+            copy_proof(ts::prove(pcs, p, chal->c, std::move(m), pis, k, source, sc.version), proof_out, cap_words,
+                       n_words_out);
         } catch (const AuxCallbackFailed&) {
-            throw callback_failure(ctx, cb_status, "ts_prove_aux");
+            throw callback_failure(ctx, cb_status, call.c_str());
         }
     });
     return cb_status != TS_OK ? cb_status : st;
 }
+ts_status ts_prove(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                   ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
+                   uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    return single_prove(PLAIN, ctx, cfg, air, chal, nullptr, trace, public_values, n_public, nullptr, nullptr, proof_out,
+                        cap_words, n_words_out);
+}
+ts_status ts_prove_pre(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                       const ts_pcs_data* preprocessed, ts_matrix* trace, const uint32_t* public_values,
+                       uint32_t n_public, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    return single_prove(PRE, ctx, cfg, air, chal, preprocessed, trace, public_values, n_public, nullptr, nullptr,
+                        proof_out, cap_words, n_words_out);
+}
+ts_status ts_prove_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                       ts_matrix* trace, const uint32_t* public_values, uint32_t n_public, ts_aux_fn aux_fn,
+                       void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    return single_prove(AUX, ctx, cfg, air, chal, nullptr, trace, public_values, n_public, aux_fn, user, proof_out,
+                        cap_words, n_words_out);
+}
+ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                           const ts_pcs_data* key, ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
+                           ts_aux_fn aux_fn, void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
+    return single_prove(PRE_AUX, ctx, cfg, air, chal, key, trace, public_values, n_public, aux_fn, user, proof_out,
+                        cap_words, n_words_out);
+}
 
+// ------------------------------------------------------------------ verify, the four single-table formats
+// Host only.  A proof of another TSPF version (verdict 9) or with other widths in its header than the AIR's (verdict
+// 1) is refused as an argument, TS_ERR_INVALID, with the verdict set; ts_verify alone leaves both to the verifier.
+static ts_status single_verify(const SingleCall& sc, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                               const uint32_t* preprocessed_root, const uint32_t* proof, size_t n_words,
+                               const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
+                               uint32_t cap_exposed, int* verdict) {
+    if (verdict) *verdict = -1;
+    return guard(nullptr, [&] {
+        const std::string call = sc.name("verify");
+        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, call + ": null argument");
+        admit_air(sc, air, call);
+        const ts::AirProgram& p = air->a.prog();
+        const uint32_t pw = p.preprocessed_width;
+        if (sc.key)
+            TS_REQUIRE((preprocessed_root != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
+                       call + (pw ? ": null preprocessed root for an AIR with preprocessed columns"
+                                  : ": a preprocessed root was given for an AIR without preprocessed columns"));
+        if (sc.aux)
+            TS_REQUIRE(p.n_exposed == 0 || (exposed_out && cap_exposed >= p.n_exposed), ts::TS_ERR_INVALID,
+                       call + ": null or short buffer for the exposed words");
+        ts::FriConfig f = load_cfg(cfg);
+        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
+        // the header behind word 4: v4 and v5 the aux width and the two counts, then v3 and v5 the preprocessed width
+        std::vector<uint32_t> widths;
+        if (sc.aux) widths = {p.aux_width, p.n_challenges, p.n_exposed};
+        if (sc.key) widths.push_back(pw);
+        if (sc.version != 1 && n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != sc.version) {
+            *verdict = 9;
+            throw ts::Error(ts::TS_ERR_INVALID, call + ": not a TSPF v" + std::to_string(sc.version) + " proof");
+        }
+        if (!widths.empty() && n_words >= 5 + widths.size() && proof[0] == ts::TSPF_MAGIC &&
+            !std::equal(widths.begin(), widths.end(), proof + 5)) {
+            *verdict = 1;
+            throw ts::Error(ts::TS_ERR_INVALID,
+                            call + ": the proof's " + (sc.aux ? "aux width, challenge or exposed count" : "") +
+                                (sc.aux && sc.key ? " or " : "") + (sc.key ? "preprocessed width" : "") +
+                                " is not the AIR's");
+        }
+        std::vector<uint32_t> exposed;
+        *verdict = ts::verify(sc.version, f, p, chal->c, proof, n_words, pis, preprocessed_root,
+                              sc.aux ? &exposed : nullptr);
+        if (*verdict == 0 && !exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
+    });
+}
+ts_status ts_verify(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                    const uint32_t* proof, size_t n_words, const uint32_t* public_values,
+                    uint32_t n_public, int* verdict) {
+    return single_verify(PLAIN, cfg, air, chal, nullptr, proof, n_words, public_values, n_public, nullptr, 0, verdict);
+}
+ts_status ts_verify_pre(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                        const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
+                        const uint32_t* public_values, uint32_t n_public, int* verdict) {
+    return single_verify(PRE, cfg, air, chal, preprocessed_root, proof, n_words, public_values, n_public, nullptr, 0,
+                         verdict);
+}
 ts_status ts_verify_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal, const uint32_t* proof,
                         size_t n_words, const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
                         uint32_t cap_exposed, int* verdict) {
-    if (verdict) *verdict = -1;
-    return guard(nullptr, [&] {
-        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_aux: null argument");
-        no_prep_with_aux(air, "ts_verify_aux");
-        const ts::AirProgram& p = air->a.prog();
-        TS_REQUIRE(p.n_exposed == 0 || (exposed_out && cap_exposed >= p.n_exposed), ts::TS_ERR_INVALID,
-                   "ts_verify_aux: null or short buffer for the exposed words");
-        ts::FriConfig f = load_cfg(cfg);
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        if (n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != 4) {
-            *verdict = 9;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_aux: not a TSPF v4 proof");
-        }
-        if (n_words >= 8 && proof[0] == ts::TSPF_MAGIC &&
-            (proof[5] != p.aux_width || proof[6] != p.n_challenges || proof[7] != p.n_exposed)) {
-            *verdict = 1;
-            throw ts::Error(ts::TS_ERR_INVALID,
-                            "ts_verify_aux: the proof's aux width, challenge or exposed count is not the AIR's");
-        }
-        std::vector<uint32_t> exposed;
-        *verdict = ts::verify_aux(f, p, chal->c, proof, n_words, pis, exposed);
-        if (*verdict == 0 && !exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
-    });
+    return single_verify(AUX, cfg, air, chal, nullptr, proof, n_words, public_values, n_public, exposed_out, cap_exposed,
+                         verdict);
+}
+ts_status ts_verify_pre_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
+                            const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
+                            const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
+                            uint32_t cap_exposed, int* verdict) {
+    return single_verify(PRE_AUX, cfg, air, chal, preprocessed_root, proof, n_words, public_values, n_public, exposed_out,
+                         cap_exposed, verdict);
 }
 
 // ------------------------------------------------------------------ LogUp aux columns
@@ -2221,45 +2253,6 @@ ts_status ts_verify_multi_key(const ts_fri_config* cfg, ts_challenger* chal, con
                              cap_exposed, bus_sum, verdict);
 }
 
-// ------------------------------------------------------------------ preprocessed and aux columns together
-// Extends ts_quotient_chunks_pre and ts_quotient_chunks_aux: the quotient over (key, aux, trace).
-ts_status ts_quotient_chunks_pre_aux(ts_ctx* ctx, const ts_pcs_data* key, const ts_pcs_data* aux_data,
-                                     const ts_pcs_data* trace_data, uint32_t log_blowup, const ts_air* air,
-                                     const uint32_t* public_values, uint32_t n_public, const uint32_t* challenges,
-                                     const uint32_t* exposed, const uint32_t alpha[4], ts_matrix** chunks_out) {
-    if (!ctx || !trace_data || !trace_data->d || !air || !alpha || !chunks_out) {
-        if (ctx) ctx->ctx.last_error = "ts_quotient_chunks_pre_aux: null argument";
-        return TS_ERR_INVALID;
-    }
-    return guard(ctx, [&] {
-        ts::SideData side;
-        if (const ts::PcsData* k = preprocessed_key_any(ctx, air, key, "ts_quotient_chunks_pre_aux")) side.push_back(k);
-        const ts::AirProgram& p = ready_prog(air);
-        if (const ts::PcsData* a = committed_aux(ctx, p, aux_data)) side.push_back(a);
-        quotient_chunks(ctx, p, side, trace_data, log_blowup, public_values, n_public, challenges, exposed, alpha,
-                        chunks_out);
-    });
-}
-
-// Extends ts_check_constraints_pre and ts_check_constraints_aux: three row-major matrices of one height.
-ts_status ts_check_constraints_pre_aux(ts_ctx* ctx, const ts_air* air, const ts_matrix* preprocessed,
-                                       const ts_matrix* aux, const ts_matrix* trace, const uint32_t* public_values,
-                                       uint32_t n_public, const uint32_t* challenges, const uint32_t* exposed,
-                                       int64_t* first_violation) {
-    if (!ctx || !air || !trace || !first_violation) {
-        if (ctx) ctx->ctx.last_error = "ts_check_constraints_pre_aux: null argument";
-        return TS_ERR_INVALID;
-    }
-    *first_violation = -1;
-    return guard(ctx, [&] {
-        const ts::AirProgram& p = air->a.prog();
-        ts::SideRows side;
-        add_side_rows(ctx, preprocessed, p.preprocessed_width, "preprocessed", trace, side);
-        add_side_rows(ctx, aux, p.aux_width, "aux", trace, side);
-        check_constraints(ctx, p, side, trace, public_values, n_public, challenges, exposed, first_violation);
-    });
-}
-
 // ------------------------------------------------------------------ before you prove: the bus, exactly
 namespace {
 void reset_bus_report(ts_bus_report* report, ts_bus_share* shares, uint32_t n) {
@@ -2387,76 +2380,6 @@ ts_status ts_check_multi(ts_ctx* ctx, const ts_multi_key* key, const ts_multi_ke
             }
         }
         if (n_aux) passed(ts_bus_check(ctx, n_tables, bus_specs.data(), pre.data(), traces.data(), report, shares));
-    });
-}
-
-// Extends ts_prove_pre (the key: part of the statement, not consumed) and ts_prove_aux (the callback); TSPF v5.
-ts_status ts_prove_pre_aux(ts_ctx* ctx, const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                           const ts_pcs_data* key, ts_matrix* trace, const uint32_t* public_values, uint32_t n_public,
-                           ts_aux_fn aux_fn, void* user, uint32_t* proof_out, size_t cap_words, size_t* n_words_out) {
-    if (!ctx || !air || !chal || !trace || !proof_out || !n_words_out) {
-        if (ctx) ctx->ctx.last_error = "ts_prove_pre_aux: null argument";
-        return TS_ERR_INVALID;
-    }
-    *n_words_out = 0;
-    ts_status cb_status = TS_OK;
-    const ts_status st = guard(ctx, [&] {
-        const ts::PcsData* k = preprocessed_key_any(ctx, air, key, "ts_prove_pre_aux");
-        const ts::AirProgram& p = ready_prog(air);
-        TS_REQUIRE((aux_fn != nullptr) == (p.aux_width > 0), ts::TS_ERR_INVALID,
-                   p.aux_width ? "ts_prove_pre_aux: null aux_fn for an AIR with aux columns"
-                               : "ts_prove_pre_aux: an aux_fn was given for an AIR without aux columns");
-        ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(cfg));
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        TS_REQUIRE(trace->m.buf.ctx == &ctx->ctx || !trace->m.buf.p, ts::TS_ERR_INVALID,
-                   "trace was made on another context");
-        TS_REQUIRE(trace->m.buf.p, ts::TS_ERR_INVALID, "trace matrix was already consumed");
-        // the key's height is known against the trace's before the trace is consumed
-        if (k) ts::check_side_matrix(*k, p, 0, trace->m.height << pcs.fri().log_blowup);
-        ts::DeviceMatrix m = take_trace(trace);
-        ts::AuxSource source;
-        if (aux_fn) source = callback_aux_source(ctx, p, aux_fn, user, cb_status, "ts_prove_pre_aux");
-        ts::StageTimer t(&ctx->ctx, "prove");
-        try {
-            copy_proof(ts::prove_pre_aux(pcs, p, chal->c, std::move(m), pis, k, source), proof_out, cap_words,
-                       n_words_out);
-        } catch (const AuxCallbackFailed&) {
-            throw callback_failure(ctx, cb_status, "ts_prove_pre_aux");
-        }
-    });
-    return cb_status != TS_OK ? cb_status : st;
-}
-
-// Extends ts_verify_pre (the key's root) and ts_verify_aux (the exposed words); host only.
-ts_status ts_verify_pre_aux(const ts_fri_config* cfg, const ts_air* air, ts_challenger* chal,
-                            const uint32_t preprocessed_root[8], const uint32_t* proof, size_t n_words,
-                            const uint32_t* public_values, uint32_t n_public, uint32_t* exposed_out,
-                            uint32_t cap_exposed, int* verdict) {
-    if (verdict) *verdict = -1;
-    return guard(nullptr, [&] {
-        TS_REQUIRE(air && chal && proof && verdict, ts::TS_ERR_INVALID, "ts_verify_pre_aux: null argument");
-        const ts::AirProgram& p = air->a.prog();
-        const uint32_t pw = p.preprocessed_width;
-        TS_REQUIRE((preprocessed_root != nullptr) == (pw > 0), ts::TS_ERR_INVALID,
-                   pw ? "ts_verify_pre_aux: null preprocessed root for an AIR with preprocessed columns"
-                      : "ts_verify_pre_aux: a preprocessed root was given for an AIR without preprocessed columns");
-        TS_REQUIRE(p.n_exposed == 0 || (exposed_out && cap_exposed >= p.n_exposed), ts::TS_ERR_INVALID,
-                   "ts_verify_pre_aux: null or short buffer for the exposed words");
-        ts::FriConfig f = load_cfg(cfg);
-        const std::vector<uint32_t> pis = public_inputs(public_values, n_public);
-        if (n_words >= 2 && proof[0] == ts::TSPF_MAGIC && proof[1] != 5) {
-            *verdict = 9;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre_aux: not a TSPF v5 proof");
-        }
-        if (n_words >= 9 && proof[0] == ts::TSPF_MAGIC &&
-            (proof[5] != p.aux_width || proof[6] != p.n_challenges || proof[7] != p.n_exposed || proof[8] != pw)) {
-            *verdict = 1;
-            throw ts::Error(ts::TS_ERR_INVALID, "ts_verify_pre_aux: the proof's aux width, challenge or exposed count "
-                                                "or preprocessed width is not the AIR's");
-        }
-        std::vector<uint32_t> exposed;
-        *verdict = ts::verify_pre_aux(f, p, chal->c, preprocessed_root, proof, n_words, pis, exposed);
-        if (*verdict == 0 && !exposed.empty()) memcpy(exposed_out, exposed.data(), exposed.size() * 4);
     });
 }
 

@@ -175,26 +175,21 @@ private:
 };
 
 // ------------------------------------------------------------------ prove
-// uni-stark/src/prover.rs:25-119.  Returns the proof in TSPF v1 words; with proof_version 3 in TSPF v3, over
-// (preprocessed key, trace) for an AIR with preprocessed columns (prover.cpp).
-std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                            DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                            const PcsData* preprocessed = nullptr, uint32_t proof_version = 1);
-// The same over (aux trace, trace) for a version-3 AIR, TSPF v4.  After the trace's commit and the challenges,
-// `aux_source(trace, challenge words (canonical, 4 per challenge), exposed_out)` returns the height x aux_width
-// aux matrix made on the prover's context; the trace is still alive then and is released right after.  Null
-// exactly for an AIR without aux columns.  Throws what the source throws.
+// uni-stark/src/prover.rs:25-119, the one single-table prover (prover.cpp).  `proof_version` names the wire format:
+//   1  TSPF v1, over the trace alone: no preprocessed columns, no challenge phase;
+//   3  TSPF v3, over (preprocessed key, trace): no challenge phase;
+//   4  TSPF v4, over (aux trace, trace) for a version-3 AIR: no preprocessed columns;
+//   5  TSPF v5, over (preprocessed key, aux trace, trace).  Transcript: key root, trace root, challenges, [aux
+//      source], aux root, exposed words, alpha, quotient over the three matrices, chunks, zeta, the batch challenge,
+//      the four-round opening (key, aux, trace, chunks).
+// `preprocessed` is null exactly for preprocessed width 0, `aux_source` null exactly for aux width 0.  After the
+// trace's commit and the challenges, `aux_source(trace, challenge words (canonical, 4 per challenge), exposed_out)`
+// returns the height x aux_width aux matrix made on the prover's context; the trace is still alive then and is
+// released right after.  Throws what the source throws.
 using AuxSource = std::function<DeviceMatrix(const DeviceMatrix& trace, const uint32_t* challenges, uint32_t* exposed)>;
-std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                const AuxSource& aux_source);
-// The same over (preprocessed key, aux trace, trace) for a version-3 AIR that may have preprocessed columns too,
-// TSPF v5.  Transcript: key root, trace root, challenges, [aux source], aux root, exposed words, alpha, quotient
-// over the three matrices, chunks, zeta, the batch challenge, the four-round opening (key, aux, trace, chunks).
-// `preprocessed` null exactly for preprocessed width 0, `aux_source` null exactly for aux width 0.
-std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                    DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                    const PcsData* preprocessed, const AuxSource& aux_source);
+std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger, DeviceMatrix trace,
+                            const std::vector<uint32_t>& public_values, const PcsData* preprocessed = nullptr,
+                            const AuxSource& aux_source = nullptr, uint32_t proof_version = 1);
 // throws TS_ERR_INVALID unless `data` holds exactly one committed matrix, of the width of the AIR's side matrix i
 // and of that LDE height ("preprocessed key: ..." or "aux data: ...", whichever side matrix i is)
 void check_side_matrix(const PcsData& data, const AirProgram& air, uint32_t i, uint64_t lde_height);
@@ -276,9 +271,6 @@ struct TapLocks {
 std::vector<uint32_t> prove_tap(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
                                 DeviceMatrix trace, const std::vector<uint32_t>& public_values,
                                 const TapLocks& locks, const Comm* comm = nullptr);
-int verify_tap(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-               const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values,
-               const TapLocks& locks);
 // verify_batch on words (taptree.cpp): leaf rebuilt from `locks[first .. first + n_evals]`, the index
 // and the opened values; digests as 8 words = their bytes read little-endian
 bool tap_verify_words(const TapLocks& locks, size_t first, uint32_t n_evals, uint32_t u32_size,
@@ -289,18 +281,13 @@ bool tap_verify_words(const TapLocks& locks, size_t first, uint32_t n_evals, uin
 // uni-stark/src/verifier.rs:19-161.  0 = accept; 1 InvalidProofShape, 2 InvalidOpeningArgument
 // (FRI proof shape), 3 InvalidPowWitness, 4 input MMCS error, 5 commit-phase MMCS error,
 // 6 FinalPolyMismatch, 7 OodEvaluationMismatch, 8 folded evaluation mismatch, 9 malformed buffer.
-int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-           const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values);
-// the same for a TSPF v3 proof against the root of the preprocessed key (null for an AIR without such columns)
-int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
-               const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values);
-// the same for a TSPF v4 proof of a version-3 AIR; `exposed` receives the proof's exposed words (on accept)
-int verify_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* proof,
-               size_t n_words, const std::vector<uint32_t>& public_values, std::vector<uint32_t>& exposed);
-// the same for a TSPF v5 proof against the root of the preprocessed key (null for an AIR without such columns)
-int verify_pre_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-                   const uint32_t* preprocessed_root, const uint32_t* proof, size_t n_words,
-                   const std::vector<uint32_t>& public_values, std::vector<uint32_t>& exposed);
+// `version` is the TSPF version the proof must have: 1, 2 (over taptrees: `tap` holds the lock scripts), 3, 4 or 5.
+// Versions 3 and 5 are keyed: `preprocessed_root` is the root of the preprocessed key (null for an AIR without such
+// columns).  Versions 4 and 5 have a challenge phase: `exposed` receives the proof's exposed words on acceptance.
+int verify(uint32_t version, const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
+           const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& public_values,
+           const uint32_t* preprocessed_root = nullptr, std::vector<uint32_t>* exposed = nullptr,
+           const TapLocks* tap = nullptr);
 
 // Pcs::verify (fri/src/two_adic_pcs.rs:421-534) for any rounds x matrices x points; same codes.
 struct PcsMatClaim {

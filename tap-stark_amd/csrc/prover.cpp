@@ -534,12 +534,16 @@ std::vector<uint32_t> TwoAdicFriPcs::open(const std::vector<OpenRound>& rounds, 
 //     samples, [the aux source], the aux root and every exposed word; then alpha and on as without them.
 // The quotient reads the side matrices (key, then aux) beside the trace; the opening has one round for each
 // before the trace's and the chunks', in that order.
-// `proof_version` 1 and 3 (prove): the header ends with the preprocessed width (v3 only); 4 and 5 (prove_aux,
-// prove_pre_aux): with the aux width, n_challenges, n_exposed and, v5 only, the preprocessed width.
-static std::vector<uint32_t> prove_body(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                        DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                        const AuxSource& aux_source, const PcsData* preprocessed,
-                                        uint32_t proof_version) {
+// `proof_version` 1 and 3: the header ends with the preprocessed width (v3 only), and an AIR with a challenge
+// phase is refused; 4 and 5: with the aux width, n_challenges, n_exposed and, v5 only, the preprocessed width, and v4
+// refuses preprocessed columns.  (The C ABI's admission refuses both first; nothing is consumed before them.)
+std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger, DeviceMatrix trace,
+                            const std::vector<uint32_t>& public_values, const PcsData* preprocessed,
+                            const AuxSource& aux_source, uint32_t proof_version) {
+    TS_REQUIRE(proof_version >= 4 || (air.aux_width == 0 && air.n_challenges == 0 && air.n_exposed == 0), TS_ERR_INVALID,
+               "prove: the AIR has a challenge phase (aux columns, challenges or exposed words); prove_aux proves it");
+    TS_REQUIRE(proof_version != 4 || air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
+               "prove_aux: preprocessed columns together with aux columns are proved by prove_pre_aux (TSPF v5)");
     const Statement st = check_statement(pcs.fri(), air, trace.width, trace.height, public_values.size());
     TS_REQUIRE((preprocessed != nullptr) == (air.preprocessed_width > 0), TS_ERR_INVALID,
                "prove: an AIR with preprocessed columns needs their committed key, and only such an AIR takes one");
@@ -625,33 +629,8 @@ static std::vector<uint32_t> prove_body(TwoAdicFriPcs& pcs, const AirProgram& ai
     return pf;
 }
 
-// TSPF v1; with proof_version 3 (ts_prove_pre) TSPF v3, over (preprocessed key, trace)
-std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                            DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                            const PcsData* preprocessed, uint32_t proof_version) {
-    TS_REQUIRE(air.aux_width == 0 && air.n_challenges == 0 && air.n_exposed == 0, TS_ERR_INVALID,
-               "prove: the AIR has a challenge phase (aux columns, challenges or exposed words); prove_aux proves it");
-    return prove_body(pcs, air, challenger, std::move(trace), public_values, nullptr, preprocessed, proof_version);
-}
-
-// TSPF v4, over (aux trace, trace)
-std::vector<uint32_t> prove_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                const AuxSource& aux_source) {
-    TS_REQUIRE(air.preprocessed_width == 0, TS_ERR_UNSUPPORTED,
-               "prove_aux: preprocessed columns together with aux columns are proved by prove_pre_aux (TSPF v5)");
-    return prove_body(pcs, air, challenger, std::move(trace), public_values, aux_source, nullptr, 4);
-}
-
-// TSPF v5 = the v4 header and one more word, the preprocessed width; over (key, aux trace, trace)
-std::vector<uint32_t> prove_pre_aux(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallenger& challenger,
-                                    DeviceMatrix trace, const std::vector<uint32_t>& public_values,
-                                    const PcsData* preprocessed, const AuxSource& aux_source) {
-    return prove_body(pcs, air, challenger, std::move(trace), public_values, aux_source, preprocessed, 5);
-}
-
 // ------------------------------------------------------------------ a lookup proof inside a batch lane
-// prove_pre_aux with its two lookup steps run by the library on the lane's stream instead of by the host: the
+// A TSPF v5 prove with its two lookup steps run by the library on the lane's stream instead of by the host: the
 // multiplicity fills before the commit, the LogUp builder as the aux source.  Same launches in the same order as
 // the solo calls, so the proof is theirs word for word.
 std::string logup_miss_text(const LogupMultResult& r, uint32_t n_lookups) {
@@ -684,7 +663,7 @@ std::vector<uint32_t> prove_lookup(TwoAdicFriPcs& pcs, const AirProgram& air, Bf
             throw LookupDataError(TS_ERR_INVARIANT, logup_miss_text(r, (uint32_t)f.weights.size()));
         }
     }
-    return prove_pre_aux(pcs, air, challenger, std::move(trace), public_values, key, aux_source);
+    return prove(pcs, air, challenger, std::move(trace), public_values, key, aux_source, 5);
 }
 
 }  // namespace ts

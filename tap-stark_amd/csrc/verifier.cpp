@@ -346,53 +346,24 @@ static int fri_verify_impl(const FriConfig& fri, BfChallenger& challenger,
     return 0;
 }
 
-// 0 = accept; otherwise the reference's error (see include/tapstark.h ts_verify)
-// v3: a TSPF v3 proof (ts_verify_pre); prep_root is then the root of the preprocessed key, or null for an AIR
-// without preprocessed columns
-static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-                       const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
-                       const TapLocks* tap, bool v3 = false, const uint32_t* prep_root = nullptr,
-                       std::vector<uint32_t>* exposed_out = nullptr, bool v5 = false);
-
 static bool ood_holds(const AirProgram& air, unsigned degree_bits, Ef zeta, Ef alpha, const Ef* pl, const Ef* pn,
                       const Ef* al, const Ef* an, const Ef* tl, const Ef* tn, const std::vector<Ef>& qc,
                       const std::vector<uint32_t>& pis);
 
-int verify_pre(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* preprocessed_root,
-               const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
-    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, true, preprocessed_root);
-}
-int verify_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger, const uint32_t* proof,
-               size_t n_words, const std::vector<uint32_t>& pis, std::vector<uint32_t>& exposed) {
-    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, false, nullptr, &exposed);
-}
-// v5: a TSPF v5 proof (ts_verify_pre_aux): the key's root as in v3, the aux trace and exposed words as in v4
-int verify_pre_aux(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-                   const uint32_t* preprocessed_root, const uint32_t* proof, size_t n_words,
-                   const std::vector<uint32_t>& pis, std::vector<uint32_t>& exposed) {
-    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr, false, preprocessed_root, &exposed, true);
-}
-int verify(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-           const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis) {
-    return verify_impl(fri, air, challenger, proof, n_words, pis, nullptr);
-}
-int verify_tap(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-               const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis,
-               const TapLocks& locks) {
-    return verify_impl(fri, air, challenger, proof, n_words, pis, &locks);
-}
-
-static int verify_impl(const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
-                       const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis_in,
-                       const TapLocks* tap, bool v3, const uint32_t* prep_root, std::vector<uint32_t>* exposed_out,
-                       bool v5) {
+// 0 = accept; otherwise the reference's error (see include/tapstark.h ts_verify).  One body for TSPF v1 to v5, keyed
+// on `version` (host.hpp): `tap` (v2), `prep_root` (v3, v5) and `exposed_out` (v4, v5) are the data of those
+// versions, not switches.
+int verify(uint32_t version, const FriConfig& fri, const AirProgram& air, BfChallenger& challenger,
+           const uint32_t* proof, size_t n_words, const std::vector<uint32_t>& pis_in, const uint32_t* prep_root,
+           std::vector<uint32_t>* exposed_out, const TapLocks* tap) {
     if (pis_in.size() != air.n_public) return 1;
-    // TSPF v4: the second matrix is the aux trace, committed in the proof; v5: the key AND the aux trace
-    const bool v4 = exposed_out != nullptr && !v5;
-    const bool keyed = v3 || v5, phased = v4 || v5;
+    // keyed: the key's round leads; phased: the second matrix is the aux trace, committed in the proof
+    const bool v3 = version == 3, v5 = version == 5;
+    const bool keyed = v3 || v5, phased = version >= 4;
+    if (version != 2) tap = nullptr;
     if ((!keyed && air.preprocessed_width) || (!phased && air.aux_width)) return 1;
     Reader rb{proof, n_words};
-    if (rb.get() != 0x46505354u || rb.get() != (v5 ? 5u : v4 ? 4u : v3 ? 3u : tap ? 2u : 1u)) return 9;
+    if (rb.get() != 0x46505354u || rb.get() != version) return 9;
     const unsigned degree_bits = rb.get();
     const uint32_t pw = rb.get(), pqd = rb.get();
     if (tap && rb.get() != fri.num_queries) return 1;  // TSPF v2: roots per commitment
@@ -552,11 +523,11 @@ static bool ood_holds(const AirProgram& air, unsigned degree_bits, Ef zeta, Ef a
 //     the shapes (it is not in the proof), the key's round first of all.  At least one table with preprocessed
 //     columns; without an aux table the proof holds no aux root and no exposed words, and no challenge is sampled
 //     before alpha.
-// Replays the transcript -- with aux tables the challenge phase of verify_impl: gamma and beta once for every table,
-// the aux root and the exposed words -- runs the out-of-domain check of verify_impl per table on that table's domain
+// Replays the transcript -- with aux tables the challenge phase of verify: gamma and beta once for every table,
+// the aux root and the exposed words -- runs the out-of-domain check of verify per table on that table's domain
 // over (key, aux, trace) with pis ++ challenges ++ that table's exposed words, then Pcs::verify over the rounds.
 // `exposed` receives the proof's exposed words and `bus_sum` their EF4 sum over the tables on acceptance; whether
-// the bus balances (bus_sum == 0) is the caller's statement, as verify_aux leaves it.
+// the bus balances (bus_sum == 0) is the caller's statement, as the single-table verifier leaves it.
 static int verify_multi_impl(const FriConfig& fri, BfChallenger& challenger, uint32_t version, const uint32_t* key_root,
                              const std::vector<const AirProgram*>& airs,
                              const std::vector<std::vector<uint32_t>>& public_values, const uint32_t* proof,

@@ -671,25 +671,13 @@ class TwoAdicFriPcs:
         qd = 1 << air.log_quotient_degree
         out = (C.c_void_p * qd)()
         pis = _u32(public_values)
-        pis_p = _p(pis) if len(pis) else None
-        if preprocessed is not None and aux is not None:
-            key = getattr(preprocessed, "data", preprocessed)
-            ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
-            self.ctx.check(self.ctx._l.ts_quotient_chunks_pre_aux(
-                self.ctx.h, key.h, aux.h, trace_data.h, self.fri.log_blowup, air.h, pis_p, len(pis),
-                _p(ch) if len(ch) else None, _p(ex) if len(ex) else None, _p(_u32(alpha)), out))
-        elif aux is not None or challenges is not None or exposed is not None:
-            ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
-            self.ctx.check(self.ctx._l.ts_quotient_chunks_aux(
-                self.ctx.h, aux.h if aux is not None else None, trace_data.h, self.fri.log_blowup, air.h, pis_p,
-                len(pis), _p(ch) if len(ch) else None, _p(ex) if len(ex) else None, _p(_u32(alpha)), out))
-        elif preprocessed is None:
-            self.ctx.check(self.ctx._l.ts_quotient_chunks(self.ctx.h, trace_data.h, self.fri.log_blowup,
-                                                          air.h, pis_p, len(pis), _p(_u32(alpha)), out))
-        else:
-            key = getattr(preprocessed, "data", preprocessed)
-            self.ctx.check(self.ctx._l.ts_quotient_chunks_pre(self.ctx.h, key.h, trace_data.h, self.fri.log_blowup,
-                                                              air.h, pis_p, len(pis), _p(_u32(alpha)), out))
+        fn, key_args, aux_args = _single_call(self.ctx._l, "quotient_chunks",
+                                              *_side_arguments(preprocessed, aux, challenges, exposed))
+        key = getattr(preprocessed, "data", preprocessed)
+        self.ctx.check(fn(self.ctx.h, *key_args(key.h if key is not None else None),
+                          *aux_args(aux.h if aux is not None else None), trace_data.h, self.fri.log_blowup, air.h,
+                          _p(pis) if len(pis) else None, len(pis), *aux_args(*_challenge_words(challenges, exposed)),
+                          _p(_u32(alpha)), out))
         return [DeviceMatrix(self.ctx, C.c_void_p(out[c])) for c in range(qd)]
 
     def open_reduce(self, trace_data: PcsData, quotient_data: PcsData, width: int, zeta, batch_alpha):
@@ -937,6 +925,12 @@ class Proof:
     _FIELDS = ("degree_bits", "trace_commit", "quotient_commit", "preprocessed_local", "preprocessed_next",
                "version", "aux_width", "n_challenges", "aux_commit", "exposed", "aux_local", "aux_next",
                "trace_local", "trace_next", "quotient_chunks", "commit_phase_commits", "query_proofs", "final_poly", "pow_witness")
+    # TSPF version -> (the header words behind magic, version, degree_bits, width and quotient degree; whether a
+    # commitment is `nr` roots, the commitment fields then (nr, 8) arrays).  v2 (ts_prove_tap, over the taptree MMCS):
+    # num_queries roots per commitment.  v3 (ts_prove_pre): the preprocessed width.  v4 (ts_prove_aux): aux width,
+    # challenge and exposed counts.  v5 (ts_prove_pre_aux): the v4 header, then the preprocessed width.
+    _HEADER = {1: ((), False), 2: (("nr",), True), 3: (("pw",), False), 4: (("aw", "nc", "ne"), False),
+               5: (("aw", "nc", "ne", "pw"), False)}
 
     def __init__(self, words):
         self.words = np.asarray(words, dtype=np.uint32)
@@ -983,32 +977,21 @@ class Proof:
     def _parse(self) -> None:
         take = _Words(self.words)
         magic, version, degree_bits, width, qd = (int(x) for x in take(5))
-        if magic != TSPF_MAGIC or version not in (1, 2, 3, 4, 5):
+        if magic != TSPF_MAGIC or version not in self._HEADER:
             raise ValueError("not a TSPF v1/v2/v3/v4/v5 proof")
-        # v2 (proofs over the taptree MMCS, ts_prove_tap): num_queries roots per commitment, the
-        # commitment fields are (num_queries, 8) arrays
-        nr = int(take(1)[0]) if version == 2 else 1
-        # v3 (ts_prove_pre): the preprocessed width; the opened preprocessed rows lead the opened values and
-        # every query's input proof holds three BatchOpenings (key, trace, chunks)
-        pw = int(take(1)[0]) if version == 3 else 0
-        # v4 (ts_prove_aux): aux width, challenge and exposed counts; the aux root and the exposed words sit between
-        # the two commitments, the opened aux rows lead the opened values (three BatchOpenings per query)
-        aw, nc, ne = (int(x) for x in take(3)) if version in (4, 5) else (0, 0, 0)
-        # v5 (ts_prove_pre_aux): the v4 header, then the preprocessed width; commitments and exposed words as v4; the
-        # opened preprocessed rows, then the aux rows, lead the opened values (four BatchOpenings per query)
-        if version == 5:
-            pw = int(take(1)[0])
+        extras, many_roots = self._HEADER[version]
+        h = {"nr": 1, "pw": 0, "aw": 0, "nc": 0, "ne": 0}
+        h.update(zip(extras, (int(x) for x in take(len(extras)))))
+        nr, pw, aw, nc, ne = (h[k] for k in ("nr", "pw", "aw", "nc", "ne"))
+        commitment = (lambda: take(8 * nr).reshape(nr, 8)) if many_roots else (lambda: take(8))
         d = {"degree_bits": degree_bits, "version": version, "preprocessed_width": pw,
              "aux_width": aw, "n_challenges": nc, "aux_commit": None, "exposed": np.zeros(0, dtype=np.uint32)}
-        if version in (4, 5):
-            d["trace_commit"] = take(8)
-            if aw:
-                d["aux_commit"], d["exposed"] = take(8), take(ne)
-            d["quotient_commit"] = take(8)
-        elif version != 2:
-            d["trace_commit"], d["quotient_commit"] = take(8), take(8)
-        else:
-            d["trace_commit"], d["quotient_commit"] = take(8 * nr).reshape(nr, 8), take(8 * nr).reshape(nr, 8)
+        d["trace_commit"] = commitment()
+        if aw:  # the aux root and the exposed words sit between the two commitments
+            d["aux_commit"], d["exposed"] = take(8), take(ne)
+        d["quotient_commit"] = commitment()
+        # the opened rows of the key, then of the aux trace, lead the opened values; every query's input proof holds
+        # one BatchOpening for each of them before the trace's and the chunks'
         d["preprocessed_local"] = take(4 * pw).reshape(pw, 4)
         d["preprocessed_next"] = take(4 * pw).reshape(pw, 4)
         d["aux_local"] = take(4 * aw).reshape(aw, 4)
@@ -1016,7 +999,7 @@ class Proof:
         d["trace_local"] = take(4 * width).reshape(width, 4)
         d["trace_next"] = take(4 * width).reshape(width, 4)
         d["quotient_chunks"] = take(16 * qd).reshape(qd, 4, 4)
-        d.update(_parse_fri_tail(take, (8,) if version != 2 else (nr, 8)))
+        d.update(_parse_fri_tail(take, (nr, 8) if many_roots else (8,)))
         self.__dict__.update(d)
 
 
@@ -1048,6 +1031,27 @@ def _preprocessed_width(air) -> int:
 
 def _air_tape_of(air, n_public: int):
     return air_tape(air, n_public, _preprocessed_width(air), *aux_dims(air))
+
+
+def _single_call(l, op: str, has_key: bool, has_aux: bool):
+    """The one dispatch of the single-table calls: the entry point ``ts_<op>[_pre][_aux]`` for a call with a key
+    argument, an aux argument or both, and two filters ``key_args(*a)`` / ``aux_args(*a)`` that give ``a`` where the
+    entry point has such arguments and ``()`` where it has not."""
+    fn = getattr(l, "ts_" + op + ("_pre" if has_key else "") + ("_aux" if has_aux else ""))
+    return fn, (lambda *a: a if has_key else ()), (lambda *a: a if has_aux else ())
+
+
+def _side_arguments(preprocessed, aux, challenges, exposed):
+    """(has_key, has_aux) of a quotient_chunks or check_constraints call: challenge or exposed words alone select the
+    aux call, and without the aux argument itself that call is the one without a key."""
+    has_aux = aux is not None or challenges is not None or exposed is not None
+    return preprocessed is not None and (aux is not None or not has_aux), has_aux
+
+
+def _challenge_words(challenges, exposed):
+    """The two pointer arguments of the aux calls (None for no words)."""
+    ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
+    return _p(ch) if len(ch) else None, _p(ex) if len(ex) else None
 
 
 def _aux_callback(ctx, air, aux, failure: list):
@@ -1104,32 +1108,19 @@ def prove(config: StarkConfig, air, challenger: BfChallenger, trace, public_valu
                                              pcs.fri) + air.n_exposed + 16)
     n_words = C.c_size_t()
     cfg = pcs.fri._c()
-    pis_p = _p(pis) if len(pis) else None
-    if aux is not None and preprocessed is not None:
+    has_key, has_aux = preprocessed is not None, aux is not None
+    if has_key and has_aux:
         # one more Merkle path and batch header per query than _proof_capacity counts
         extra = pcs.fri.num_queries * (8 * (max(n, 1).bit_length() - 1 + pcs.fri.log_blowup) + 8)
         out = _proof_buffer(ctx, len(out) + extra)
-        failure: list = []
-        cb = _aux_callback(ctx, air, aux, failure)
-        rc = ctx._l.ts_prove_pre_aux(ctx.h, C.byref(cfg), air.h, challenger.h, preprocessed.data.h, trace.h, pis_p,
-                                     len(pis), cb, None, _p(out), len(out), C.byref(n_words))
-        if failure:
-            raise failure[0]
-        ctx.check(rc)
-    elif aux is not None:
-        failure: list = []
-        cb = _aux_callback(ctx, air, aux, failure)
-        rc = ctx._l.ts_prove_aux(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis), cb, None,
-                                 _p(out), len(out), C.byref(n_words))
-        if failure:
-            raise failure[0]
-        ctx.check(rc)
-    elif preprocessed is None:
-        ctx.check(ctx._l.ts_prove(ctx.h, C.byref(cfg), air.h, challenger.h, trace.h, pis_p, len(pis),
-                                  _p(out), len(out), C.byref(n_words)))
-    else:
-        ctx.check(ctx._l.ts_prove_pre(ctx.h, C.byref(cfg), air.h, challenger.h, preprocessed.data.h, trace.h, pis_p,
-                                      len(pis), _p(out), len(out), C.byref(n_words)))
+    fn, key_args, aux_args = _single_call(ctx._l, "prove", has_key, has_aux)
+    failure: list = []
+    cb = _aux_callback(ctx, air, aux, failure) if has_aux else None
+    rc = fn(ctx.h, C.byref(cfg), air.h, challenger.h, *key_args(preprocessed.data.h if has_key else None), trace.h,
+            _p(pis) if len(pis) else None, len(pis), *aux_args(cb, None), _p(out), len(out), C.byref(n_words))
+    if failure:
+        raise failure[0]
+    ctx.check(rc)
     return Proof(out[: n_words.value].copy())
 
 
@@ -1898,30 +1889,29 @@ def verify(config: StarkConfig, air, challenger: BfChallenger, proof, public_val
     A TSPF v4 proof (``ts_prove_aux``) goes to ``ts_verify_aux``, and its exposed words are returned: the statement
     about them (``LogUp.verify``: the sum is zero) is the caller's to check.  A TSPF v5 proof (``ts_prove_pre_aux``)
     with its ``preprocessed_root`` goes to ``ts_verify_pre_aux`` and returns its exposed words likewise."""
+    words = _u32(proof.words if isinstance(proof, Proof) else proof)
+    version = int(words[1]) if len(words) >= 2 and words[0] == TSPF_MAGIC else 0
+    has_key = preprocessed_root is not None
+    return _verify_call(has_key, version == (5 if has_key else 4), config, air, challenger, words, public_values,
+                        preprocessed_root)
+
+
+def _verify_call(has_key: bool, has_aux: bool, config, air, challenger, words, public_values, preprocessed_root):
+    """One ``ts_verify[_pre][_aux]`` call: the exposed words from the entry points that hand them back, else None."""
     pis = _u32(public_values)
     if isinstance(air, BaseAir):
         air = CompiledAir(None, _air_tape_of(air, len(pis)))
-    words = _u32(proof.words if isinstance(proof, Proof) else proof)
+    l = _lib.lib()
+    fn, key_args, aux_args = _single_call(l, "verify", has_key, has_aux)
     cfg = config.pcs.fri._c()
     verdict = C.c_int(-1)
-    l = _lib.lib()
-    pis_p = _p(pis) if len(pis) else None
-    exposed = None
-    if preprocessed_root is not None and len(words) >= 2 and words[0] == TSPF_MAGIC and words[1] == 5:
-        exposed = np.zeros(air.n_exposed, dtype=np.uint32)
-        rc = l.ts_verify_pre_aux(C.byref(cfg), air.h, challenger.h, _p(_u32(preprocessed_root)), _p(words), len(words),
-                                 pis_p, len(pis), _p(exposed) if len(exposed) else None, len(exposed),
-                                 C.byref(verdict))
-    elif preprocessed_root is None and len(words) >= 2 and words[0] == TSPF_MAGIC and words[1] == 4:
-        exposed = np.zeros(air.n_exposed, dtype=np.uint32)
-        rc = l.ts_verify_aux(C.byref(cfg), air.h, challenger.h, _p(words), len(words), pis_p, len(pis),
-                             _p(exposed) if len(exposed) else None, len(exposed), C.byref(verdict))
-    elif preprocessed_root is None:
-        rc = l.ts_verify(C.byref(cfg), air.h, challenger.h, _p(words), len(words), pis_p, len(pis), C.byref(verdict))
-    else:
-        rc = l.ts_verify_pre(C.byref(cfg), air.h, challenger.h, _p(_u32(preprocessed_root)), _p(words), len(words),
-                             pis_p, len(pis), C.byref(verdict))
-    if rc and verdict.value <= 0:  # (ts_verify_pre refuses a proof of another version or width WITH a verdict)
+    exposed = np.zeros(air.n_exposed, dtype=np.uint32) if has_aux else None
+    rc = fn(C.byref(cfg), air.h, challenger.h,
+            *key_args(_p(_u32(preprocessed_root)) if preprocessed_root is not None else None), _p(words), len(words),
+            _p(pis) if len(pis) else None, len(pis),
+            *aux_args(_p(exposed) if has_aux and len(exposed) else None, len(exposed) if has_aux else 0),
+            C.byref(verdict))
+    if rc and verdict.value <= 0:  # (a proof of another version or width is refused WITH a verdict)
         raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify").decode())
     if verdict.value != 0:
         raise VerificationError(verdict.value)
@@ -1932,23 +1922,8 @@ def verify_pre_aux(config: StarkConfig, air, challenger: BfChallenger, proof, pu
     """``ts_verify_pre_aux`` whatever the AIR's widths: the verifier of every ``prove_batch_lookup`` proof (TSPF v5
     also for an AIR without a key, which ``verify`` routes there only together with a root).  ``preprocessed_root``
     is None exactly for an AIR without preprocessed columns.  Returns the exposed words; raises as ``verify``."""
-    pis = _u32(public_values)
-    if isinstance(air, BaseAir):
-        air = CompiledAir(None, _air_tape_of(air, len(pis)))
     words = _u32(proof.words if isinstance(proof, Proof) else proof)
-    cfg = config.pcs.fri._c()
-    verdict = C.c_int(-1)
-    l = _lib.lib()
-    exposed = np.zeros(air.n_exposed, dtype=np.uint32)
-    rc = l.ts_verify_pre_aux(C.byref(cfg), air.h, challenger.h,
-                             _p(_u32(preprocessed_root)) if preprocessed_root is not None else None, _p(words),
-                             len(words), _p(pis) if len(pis) else None, len(pis),
-                             _p(exposed) if len(exposed) else None, len(exposed), C.byref(verdict))
-    if rc and verdict.value <= 0:
-        raise _lib.TsError(rc, (l.ts_last_error(None) or b"ts_verify_pre_aux").decode())
-    if verdict.value != 0:
-        raise VerificationError(verdict.value)
-    return exposed
+    return _verify_call(True, True, config, air, challenger, words, public_values, preprocessed_root)
 
 
 def check_constraints(air, trace, public_values, ctx: Context | None = None, preprocessed=None, aux=None,
@@ -1966,28 +1941,13 @@ def check_constraints(air, trace, public_values, ctx: Context | None = None, pre
     if not isinstance(trace, DeviceMatrix):
         trace = DeviceMatrix.upload(ctx, trace)
     out = C.c_int64(-1)
-    pis_p = _p(pis) if len(pis) else None
-    if preprocessed is not None and aux is not None:
-        if not isinstance(preprocessed, DeviceMatrix):
-            preprocessed = DeviceMatrix.upload(ctx, _u32(preprocessed))
-        if not isinstance(aux, DeviceMatrix):
-            aux = DeviceMatrix.upload(ctx, _u32(aux))
-        ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
-        ctx.check(ctx._l.ts_check_constraints_pre_aux(ctx.h, air.h, preprocessed.h, aux.h, trace.h, pis_p, len(pis),
-                                                      _p(ch) if len(ch) else None, _p(ex) if len(ex) else None,
-                                                      C.byref(out)))
-    elif aux is not None or challenges is not None or exposed is not None:
-        if aux is not None and not isinstance(aux, DeviceMatrix):
-            aux = DeviceMatrix.upload(ctx, _u32(aux))
-        ch, ex = _u32(challenges if challenges is not None else []), _u32(exposed if exposed is not None else [])
-        ctx.check(ctx._l.ts_check_constraints_aux(ctx.h, air.h, aux.h if aux is not None else None, trace.h, pis_p,
-                                                  len(pis), _p(ch) if len(ch) else None, _p(ex) if len(ex) else None,
-                                                  C.byref(out)))
-    elif preprocessed is None:
-        ctx.check(ctx._l.ts_check_constraints(ctx.h, air.h, trace.h, pis_p, len(pis), C.byref(out)))
-    else:
-        if not isinstance(preprocessed, DeviceMatrix):
-            preprocessed = DeviceMatrix.upload(ctx, _u32(preprocessed))
-        ctx.check(ctx._l.ts_check_constraints_pre(ctx.h, air.h, preprocessed.h, trace.h, pis_p, len(pis),
-                                                  C.byref(out)))
+    has_key, has_aux = _side_arguments(preprocessed, aux, challenges, exposed)
+    fn, key_args, aux_args = _single_call(ctx._l, "check_constraints", has_key, has_aux)
+    if has_key and not isinstance(preprocessed, DeviceMatrix):
+        preprocessed = DeviceMatrix.upload(ctx, _u32(preprocessed))
+    if aux is not None and not isinstance(aux, DeviceMatrix):
+        aux = DeviceMatrix.upload(ctx, _u32(aux))
+    ctx.check(fn(ctx.h, air.h, *key_args(preprocessed.h if has_key else None),
+                 *aux_args(aux.h if aux is not None else None), trace.h, _p(pis) if len(pis) else None, len(pis),
+                 *aux_args(*_challenge_words(challenges, exposed)), C.byref(out)))
     return int(out.value)
