@@ -503,6 +503,16 @@ extern "C" {
     /// out[i] = src[index[i][index_column]]: the sort's last kernel over a caller's index
     pub fn ts_matrix_gather_rows(ctx: *mut ts_ctx, src: *const ts_matrix, index: *const ts_matrix, index_column: u32,
                                  out: *mut *mut ts_matrix) -> ts_status;
+    /// a new matrix whose named columns are a row program ("TDER" word tape) over `src`, the others copied; `src` is
+    /// only read
+    pub fn ts_matrix_derive(ctx: *mut ts_ctx, program: *const u32, n_words: usize, src: *const ts_matrix,
+                            out: *mut *mut ts_matrix) -> ts_status;
+    /// host only: the checks of a row program that need no matrix, and what it lowers to (each output may be null)
+    pub fn ts_derive_check(program: *const u32, n_words: usize, src_width: u32, out_width: *mut u32,
+                           n_instructions: *mut u32, n_live: *mut u32) -> ts_status;
+    /// host only: the lowered program over `height` host rows of `src_width` words
+    pub fn ts_derive_rows_host(program: *const u32, n_words: usize, src_row_major: *const u32, height: u64,
+                               src_width: u32, out_row_major: *mut u32, out_cap_words: usize) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

@@ -232,7 +232,9 @@ ts_status ts_matrix_bit_reverse_rows(ts_ctx* ctx, const ts_matrix* in, ts_matrix
  * public values ++ challenges ++ exposed.  A tape with preprocessed_width > 0 AND aux_width > 0 reads three
  * matrices: PREP keeps a = 2, 3 and AUX takes a = 4, 5, the local and next row of a THIRD matrix; the public slots
  * are unchanged.  Only the ts_*_pre_aux calls below prove, check and verify such an AIR; every other proving call
- * returns TS_ERR_UNSUPPORTED for it, before anything is consumed. */
+ * returns TS_ERR_UNSUPPORTED for it, before anything is consumed.
+ * The library has a second node tape, the ROW PROGRAM of ts_matrix_derive ("TDER", at the end of this header): ops 0 to 9
+ * keep their numbers and meaning there where they coincide (1 reads a column of the source matrix, 2 does not exist). */
 /* ctx == NULL builds a host-only AIR (degree rules + verifier use; no kernels) */
 ts_status ts_air_compile(ts_ctx* ctx, const uint32_t* tape, size_t n_words, ts_air** out);
 /* get_log_quotient_degree, uni-stark/src/symbolic_builder.rs:15-32 */
@@ -1353,6 +1355,68 @@ ts_status ts_matrix_sort_rows(ts_ctx* ctx, const ts_sort_spec* spec, const ts_ma
  * kernel with a 64-bit integer minimum), and there is no output.  One launch, one copy back. */
 ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matrix* index, uint32_t index_column,
                                 ts_matrix** out);
+
+/* ---- derived columns: a row program evaluated in HBM ----
+ * The sort closed the host round trip for row order; this closes it for every witness column that is a function of its
+ * own row and its two neighbours: limb decompositions, is-zero inverses, comparison bits, a xor b, negated selectors,
+ * the index column of a range table, the `gap` of a memory table.  It replaces: ts_matrix_download, a host loop,
+ * ts_matrix_upload.
+ * The program is a word tape, written as the AIR tape is:
+ *   [0]=0x52454454 ("TDER") [1]=1 [2]=src_width [3]=n_nodes [4]=n_outputs,
+ *   n_nodes x {op,a,b}       operands that are nodes name EARLIER nodes only
+ *   n_outputs x {node, dst_column}
+ * Every node's value is a canonical BabyBear element in [0, p), p = 0x78000001.  Ops:
+ *    0 CONST(a=value < p)
+ *    1 COL(a=row offset: 0 this row, 1 next row, 2 previous row; b=column < src_width): the word AS STORED, reduced
+ *      mod p -- 0xFFFFFFFF gives 268435453 and p gives 0.  Rows are cyclic, as an AIR's next row is: next of row h-1 is
+ *      row 0, previous of row 0 is row h-1
+ *    3 IS_FIRST_ROW (1 on row 0)  4 IS_LAST_ROW (1 on row h-1)  5 IS_TRANSITION (1 - IS_LAST_ROW)
+ *    6 ADD(a,b)  7 SUB(a,b)  8 NEG(a)  9 MUL(a,b): field operations
+ *   32 ROW: the row index (< 2^27 < p)
+ *   33 INV(a): the field inverse, INV(0) = 0 (the is-zero witness convention)
+ *   34 IS_ZERO(a): 1 if a == 0, else 0
+ *   35 LT(a,b): 1 if a < b as integers in [0, p), else 0
+ *   36 BITS(a, b = shift | nbits << 8): (a >> shift) & (2^nbits - 1) on the canonical integer; nbits >= 1, shift +
+ *      nbits <= 31
+ *   37 AND(a,b)  38 XOR(a,b): bitwise on the canonical integers, the result reduced mod p (a result in [p, 2^31) becomes
+ *      result - p)
+ * Op 2 and every other number are TS_ERR_INVALID.
+ * Output: *out is a NEW row-major matrix of src's height and of width W_out = max(src_width, 1 + max dst_column).  A
+ * column named by an output holds that node's value, canonical.  Every other column must be < src_width and is copied
+ * from src as stored (not reduced); every column >= src_width must be named, and no column may be named twice (one node
+ * may go to several columns).  All reads see src: an output that overwrites column c does not change what COL of c
+ * reads.  src is neither consumed nor written.  Every output word is a pure function of src, so the result is the same
+ * on every run.
+ * Lowering (ts_derive_check reports it): nodes no output reaches are dropped (they are still checked); one instruction
+ * per remaining node, in tape order; a value lives in one slot from its instruction to its last use, and an
+ * instruction's destination may take the slot of an operand whose last use it is; an output is stored when its node is
+ * computed.  n_live is the most slots held at once.
+ * TS_ERR_INVALID, each with a text in ts_last_error, before any device work: a NULL argument; a wrong magic or version,
+ * or a word count that does not match the header; [2] != src's width; an unknown op; an operand >= the node's own
+ * index; a COL offset > 2 or a column outside src; CONST >= p; BITS with nbits = 0 or shift + nbits > 31; n_nodes = 0 or
+ * n_outputs = 0, or either above its limit; an output node >= n_nodes; a broken rule on destination columns; W_out >
+ * 2^16; n_live > TS_DERIVE_MAX_LIVE (the text names both numbers); a matrix that is not row-major, is consumed or
+ * belongs to another context; a height outside [1, 2^27] (any value inside is taken).  A refused call leaves *out NULL.
+ * Launches: the lowered list goes to the device in one asynchronous copy through the context's page-locked staging
+ * arena, then ONE kernel, one lane per row: a workgroup copies the untouched columns of its 256 rows with coalesced
+ * accesses and interprets the list (scalar instruction fetch, the slot file in LDS).  The call makes no host wait of
+ * its own (the arena waits once when it wraps, as for every small upload).  Temporaries come from ctx's pool.
+ * The interpreter is the only form: a program is not specialised into a kernel of its own.
+ * Out of scope: anything not row-local -- prefix sums, "carry the last written value", rows that depend on derived
+ * values of other rows (chain two calls instead); more than one source matrix; parameters other than constants;
+ * extension-field values; use inside batch lanes. */
+enum { TS_DERIVE_MAX_NODES = 4096, TS_DERIVE_MAX_OUTPUTS = 256, TS_DERIVE_MAX_LIVE = 48 };
+ts_status ts_matrix_derive(ts_ctx* ctx, const uint32_t* program, size_t n_words, const ts_matrix* src, ts_matrix** out);
+/* Host only, no context: every check above that needs no matrix, against a source of src_width columns; the text of a
+ * refusal is what ts_last_error returns for a NULL context.  out_width = W_out, n_instructions = the nodes kept,
+ * n_live as above; each of the three may be NULL. */
+ts_status ts_derive_check(const uint32_t* program, size_t n_words, uint32_t src_width, uint32_t* out_width,
+                          uint32_t* n_instructions, uint32_t* n_live);
+/* Host only: THE SAME lowered instruction list and slot allocation the device gets, over `height` host rows of
+ * src_width words; out_row_major receives height * W_out words (TS_ERR_BUFFER if out_cap_words is less).  A reference
+ * for tests and for callers without a device, not a fast path. */
+ts_status ts_derive_rows_host(const uint32_t* program, size_t n_words, const uint32_t* src_row_major, uint64_t height,
+                              uint32_t src_width, uint32_t* out_row_major, size_t out_cap_words);
 
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);

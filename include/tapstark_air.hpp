@@ -386,5 +386,76 @@ private:
     std::vector<LogUpInteraction> its_;
 };
 
+// ---- row programs for ts_matrix_derive (include/tapstark.h "derived columns"): the counterpart of
+// tap-stark_amd/derive.py, node for node -- nothing is shared or folded, an integer operand becomes a CONST node where
+// it is met, so a program written statement by statement in the same order gives the same tape words in both.  (C++
+// leaves the order in which the two sides of an operator are evaluated open: write one operation per statement where
+// the words matter.)  Nothing is checked here; ts_derive_check is the judge.
+class Derive;
+
+class DExpr {
+public:
+    DExpr(Derive* b, uint32_t id) : b_(b), id_(id) {}
+    uint32_t id() const { return id_; }
+    Derive* builder() const { return b_; }
+    inline DExpr inv() const;
+    inline DExpr is_zero() const;
+    inline DExpr lt(DExpr o) const;
+    inline DExpr bits(uint32_t shift, uint32_t n) const;  // (x >> shift) & (2^n - 1) on the canonical integer
+
+private:
+    Derive* b_;
+    uint32_t id_;
+};
+
+class Derive {
+public:
+    enum Op : uint32_t { CONST = 0, COL = 1, IS_FIRST = 3, IS_LAST = 4, IS_TRANSITION = 5, ADD = 6, SUB = 7, NEG = 8,
+                         MUL = 9, ROW = 32, INV = 33, IS_ZERO = 34, LT = 35, BITS = 36, AND = 37, XOR = 38 };
+    static constexpr uint32_t MAGIC = 0x52454454u;  // "TDER"
+
+    explicit Derive(uint32_t src_width) : src_width_(src_width) {}
+    DExpr node(uint32_t op, uint32_t a, uint32_t b) {
+        nodes_.insert(nodes_.end(), {op, a, b});
+        return DExpr(this, (uint32_t)(nodes_.size() / 3 - 1));
+    }
+    DExpr constant(uint64_t v) { return node(CONST, (uint32_t)(v % P), 0); }
+    DExpr col(uint32_t c) { return node(COL, 0, c); }
+    DExpr next(uint32_t c) { return node(COL, 1, c); }
+    DExpr prev(uint32_t c) { return node(COL, 2, c); }
+    DExpr row() { return node(ROW, 0, 0); }
+    DExpr is_first_row() { return node(IS_FIRST, 0, 0); }
+    DExpr is_last_row() { return node(IS_LAST, 0, 0); }
+    DExpr is_transition() { return node(IS_TRANSITION, 0, 0); }
+    void output(DExpr x, uint32_t dst_column) { outputs_.insert(outputs_.end(), {x.id(), dst_column}); }
+    std::vector<uint32_t> tape() const {
+        std::vector<uint32_t> t = {MAGIC, 1, src_width_, (uint32_t)(nodes_.size() / 3), (uint32_t)(outputs_.size() / 2)};
+        t.insert(t.end(), nodes_.begin(), nodes_.end());
+        t.insert(t.end(), outputs_.begin(), outputs_.end());
+        return t;
+    }
+
+private:
+    uint32_t src_width_;
+    std::vector<uint32_t> nodes_, outputs_;
+};
+
+inline DExpr DExpr::inv() const { return b_->node(Derive::INV, id_, 0); }
+inline DExpr DExpr::is_zero() const { return b_->node(Derive::IS_ZERO, id_, 0); }
+inline DExpr DExpr::lt(DExpr o) const { return b_->node(Derive::LT, id_, o.id()); }
+inline DExpr DExpr::bits(uint32_t shift, uint32_t n) const { return b_->node(Derive::BITS, id_, shift | n << 8); }
+inline DExpr operator+(DExpr x, DExpr y) { return x.builder()->node(Derive::ADD, x.id(), y.id()); }
+inline DExpr operator-(DExpr x, DExpr y) { return x.builder()->node(Derive::SUB, x.id(), y.id()); }
+inline DExpr operator*(DExpr x, DExpr y) { return x.builder()->node(Derive::MUL, x.id(), y.id()); }
+inline DExpr operator&(DExpr x, DExpr y) { return x.builder()->node(Derive::AND, x.id(), y.id()); }
+inline DExpr operator^(DExpr x, DExpr y) { return x.builder()->node(Derive::XOR, x.id(), y.id()); }
+inline DExpr operator-(DExpr x) { return x.builder()->node(Derive::NEG, x.id(), 0); }
+inline DExpr operator+(DExpr x, uint64_t c) { return x + x.builder()->constant(c); }
+inline DExpr operator-(DExpr x, uint64_t c) { return x - x.builder()->constant(c); }
+inline DExpr operator*(DExpr x, uint64_t c) { return x * x.builder()->constant(c); }
+inline DExpr operator+(uint64_t c, DExpr x) { return x.builder()->constant(c) + x; }
+inline DExpr operator-(uint64_t c, DExpr x) { return x.builder()->constant(c) - x; }
+inline DExpr operator*(uint64_t c, DExpr x) { return x.builder()->constant(c) * x; }
+
 }  // namespace air
 }  // namespace ts

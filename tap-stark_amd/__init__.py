@@ -12,3 +12,4 @@ from .air import logup_build_multi, logup_multiplicities_bus  # noqa: F401
 from .stark import MultiKey, MultiKeyProof, MultiKeyTableOpening, prove_multi_key, verify_multi_key  # noqa: F401
 from .air import BusReport, BusShare, bus_check  # noqa: F401
 from .stark import check_multi  # noqa: F401
+from .derive import DeriveBuilder, derive_check, derive_rows_host  # noqa: F401

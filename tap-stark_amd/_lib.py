@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "ts_prove_multi_key", "ts_verify_multi_key", "ts_logup_aux_build_multi_pre", "ts_logup_multiplicities_bus_pre",
     "ts_bus_check", "ts_check_multi",
     "ts_matrix_sort_rows", "ts_matrix_gather_rows",
+    "ts_matrix_derive", "ts_derive_check", "ts_derive_rows_host",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -443,6 +444,9 @@ def lib() -> C.CDLL:
                                      C.POINTER(BusShareC)]
         l.ts_matrix_sort_rows.argtypes = [C.c_void_p, C.POINTER(SortSpecC), C.c_void_p, voidpp]
         l.ts_matrix_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, voidpp]
+        l.ts_matrix_derive.argtypes = [C.c_void_p, u32p, C.c_size_t, C.c_void_p, voidpp]
+        l.ts_derive_check.argtypes = [u32p, C.c_size_t, C.c_uint32, u32p, u32p, u32p]
+        l.ts_derive_rows_host.argtypes = [u32p, C.c_size_t, u32p, C.c_uint64, C.c_uint32, u32p, C.c_size_t]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

@@ -1131,8 +1131,8 @@ def memory_table_source(accesses: np.ndarray) -> tuple[np.ndarray, int]:
 
 
 def fill_memory_gaps(table: np.ndarray) -> np.ndarray:
-    """The downloaded sorted table with ``gap`` filled on the host (the library does not compute derived arithmetic
-    columns): on live row i >= 1 the address step minus one where a group starts, the clock step minus one inside a
+    """The downloaded sorted table with ``gap`` filled on the host (``memory_gap_program`` is the same column computed
+    in HBM): on live row i >= 1 the address step minus one where a group starts, the clock step minus one inside a
     group, mod p; 0 on row 0 and on dead rows.  A table that is not sorted gets a gap near p, outside any range table."""
     t = np.array(table, dtype=np.uint32)
     A = MemoryTableAir
@@ -1141,6 +1141,28 @@ def fill_memory_gaps(table: np.ndarray) -> np.ndarray:
     t[:, A.GAP] = 0
     t[1:, A.GAP] = np.where(cur[:, A.LIVE] == 1, step % P, 0)
     return t
+
+
+def memory_table_source_program():
+    """``memory_table_source`` as a row program for ``DeviceMatrix.derive``: the (n, 5) accesses become (n, 7) -- columns
+    0 to 4 copied (``sel`` is ``live``), 5 = ``recv`` = -live, 6 = ``gap`` = 0.  ``n_live`` stays the caller's to know."""
+    from .derive import DeriveBuilder
+    b = DeriveBuilder(5)
+    b.output(-b.col(4), 5)
+    b.output(b.constant(0), 6)
+    return b
+
+
+def memory_gap_program():
+    """``fill_memory_gaps`` as a row program over the sorted (n, 8) table: column 6 = ``live (1 - is_first_row)
+    (start (addr - prev addr) + (1 - start) (clk - prev clk) - 1)``."""
+    from .derive import DeriveBuilder
+    A = MemoryTableAir
+    b = DeriveBuilder(8)
+    start = b.col(A.START)
+    step = start * (b.col(A.ADDR) - b.prev(A.ADDR)) + (1 - start) * (b.col(A.CLK) - b.prev(A.CLK)) - 1
+    b.output(b.col(A.LIVE) * (1 - b.is_first_row()) * step, A.GAP)
+    return b
 
 
 def generate_memory_table(accesses: np.ndarray) -> np.ndarray:

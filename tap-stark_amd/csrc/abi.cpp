@@ -14,6 +14,7 @@
 
 #include "abi_types.hpp"
 #include "blake3.hpp"
+#include "derive.hpp"
 #include "jit.hpp"
 #include "logup.hpp"
 #include "prover_internal.hpp"
@@ -1950,6 +1951,47 @@ ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matr
         auto m = std::make_unique<ts_matrix>();
         m->m = ts::gather_rows(ctx->ctx, src->m, index->m, index_column);
         *out = m.release();
+    });
+}
+
+// Derived columns: a row program over a resident matrix (derive.hip), its checks and its host evaluation (derive.cpp).
+ts_status ts_matrix_derive(ts_ctx* ctx, const uint32_t* program, size_t n_words, const ts_matrix* src, ts_matrix** out) {
+    if (out) *out = nullptr;
+    if (!ctx) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(program && src && out, ts::TS_ERR_INVALID, "ts_matrix_derive: null argument");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        auto m = std::make_unique<ts_matrix>();
+        m->m = ts::derive_matrix(ctx->ctx, program, n_words, src->m);
+        *out = m.release();
+    });
+}
+
+ts_status ts_derive_check(const uint32_t* program, size_t n_words, uint32_t src_width, uint32_t* out_width,
+                          uint32_t* n_instructions, uint32_t* n_live) {
+    if (out_width) *out_width = 0;
+    if (n_instructions) *n_instructions = 0;
+    if (n_live) *n_live = 0;
+    return guard(nullptr, [&] {
+        const ts::DeriveProgram prog = ts::derive_lower(program, n_words, src_width);
+        if (out_width) *out_width = prog.out_width;
+        if (n_instructions) *n_instructions = prog.n_nodes_kept;
+        if (n_live) *n_live = prog.n_live;
+    });
+}
+
+ts_status ts_derive_rows_host(const uint32_t* program, size_t n_words, const uint32_t* src_row_major, uint64_t height,
+                              uint32_t src_width, uint32_t* out_row_major, size_t out_cap_words) {
+    return guard(nullptr, [&] {
+        TS_REQUIRE(program && src_row_major && out_row_major, ts::TS_ERR_INVALID, "ts_derive_rows_host: null argument");
+        TS_REQUIRE(height >= 1 && height <= ts::DERIVE_MAX_HEIGHT, ts::TS_ERR_INVALID,
+                   "derive: the height of the source must be in [1, 2^27]");
+        const ts::DeriveProgram prog = ts::derive_lower(program, n_words, src_width);
+        TS_REQUIRE((uint64_t)out_cap_words >= height * prog.out_width, ts::TS_ERR_BUFFER,
+                   "ts_derive_rows_host: the output buffer holds fewer than height * out_width words");
+        ts::derive_rows_host(prog, src_row_major, height, out_row_major);
     });
 }
 

@@ -375,6 +375,15 @@ class DeviceMatrix:
         self.ctx.check(self.ctx._l.ts_matrix_gather_rows(self.ctx.h, self.h, index.h, column, C.byref(h)))
         return DeviceMatrix(self.ctx, h)
 
+    def derive(self, program) -> "DeviceMatrix":
+        """A new matrix of this height: the columns a row program names computed from this matrix, the others copied
+        (``ts_matrix_derive``).  ``program`` is a ``derive.DeriveBuilder`` or its tape; this matrix is only read."""
+        from .derive import _tape
+        t = _tape(program)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_matrix_derive(self.ctx.h, _p(t), len(t), self.h, C.byref(h)))
+        return DeviceMatrix(self.ctx, h)
+
     def device_ptr(self) -> int:
         """Row-major device pointer (``ts_matrix_device_ptr``): valid until the matrix is freed or consumed,
         ordered on the context's stream; ``from_device_ptr`` is the opposite direction."""
