@@ -240,6 +240,41 @@ pub struct ts_sort_spec {
     pub n_live: u64,
 }
 
+/// A term of a scan: kind 0 a constant below p, kind 1 column `value` of the source.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_scan_term {
+    pub kind: u32,
+    pub value: u32,
+}
+
+/// One recurrence of `ts_matrix_scan`: y[i] = a[i] y[i-1] + b[i], y[-1] = init.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_scan_column {
+    pub a: ts_scan_term,
+    pub b: ts_scan_term,
+    pub init: u32,
+    pub reset_column: u32, // TS_SCAN_NO_RESET or a column of the source
+    pub dst_column: u32,
+    pub flags: u32, // bit 0: TS_SCAN_EXCLUSIVE
+}
+
+pub const TS_SCAN_MAX_COLUMNS: usize = 8;
+pub const TS_SCAN_NO_RESET: u32 = 0xFFFF_FFFF;
+pub const TS_SCAN_EXCLUSIVE: u32 = 1;
+
+/// The scans of one `ts_matrix_scan` call.  Like every declaration of this file it has not been compiled.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_scan_spec {
+    pub struct_size: u32, // = size_of::<ts_scan_spec>()
+    pub n_columns: u32,
+    pub columns: [ts_scan_column; TS_SCAN_MAX_COLUMNS],
+    pub out_width: u32,
+    pub pad: u32,
+}
+
 /// One statement of `ts_prove_batch_lookup`: `ts_batch_item`'s inputs, the aux source (exactly one of `logup` /
 /// `aux_fn` for an AIR with aux columns), the multiplicity fills, then what the library writes back.
 #[repr(C)]
@@ -513,6 +548,13 @@ extern "C" {
     /// host only: the lowered program over `height` host rows of `src_width` words
     pub fn ts_derive_rows_host(program: *const u32, n_words: usize, src_row_major: *const u32, height: u64,
                                src_width: u32, out_row_major: *mut u32, out_cap_words: usize) -> ts_status;
+    /// a new matrix whose dst columns hold linear recurrences y[i] = a[i] y[i-1] + b[i] down the rows of `src`, the
+    /// other kept columns copied; `finals` (n_columns words, y[h-1] of each) may be null; `src` is only read
+    pub fn ts_matrix_scan(ctx: *mut ts_ctx, spec: *const ts_scan_spec, src: *const ts_matrix, out: *mut *mut ts_matrix,
+                          finals: *mut u32) -> ts_status;
+    /// host only: the same scans as a sequential loop over `height` host rows of `src_width` words
+    pub fn ts_scan_rows_host(spec: *const ts_scan_spec, src_row_major: *const u32, height: u64, src_width: u32,
+                             out_row_major: *mut u32, out_cap_words: usize, finals: *mut u32) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

@@ -1402,9 +1402,9 @@ ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matr
  * accesses and interprets the list (scalar instruction fetch, the slot file in LDS).  The call makes no host wait of
  * its own (the arena waits once when it wraps, as for every small upload).  Temporaries come from ctx's pool.
  * The interpreter is the only form: a program is not specialised into a kernel of its own.
- * Out of scope: anything not row-local -- prefix sums, "carry the last written value", rows that depend on derived
- * values of other rows (chain two calls instead); more than one source matrix; parameters other than constants;
- * extension-field values; use inside batch lanes. */
+ * Out of scope: anything not row-local -- rows that depend on derived values of other rows (chain two calls instead;
+ * a first-order recurrence down the rows is ts_matrix_scan below); more than one source matrix; parameters other than
+ * constants; extension-field values; use inside batch lanes. */
 enum { TS_DERIVE_MAX_NODES = 4096, TS_DERIVE_MAX_OUTPUTS = 256, TS_DERIVE_MAX_LIVE = 48 };
 ts_status ts_matrix_derive(ts_ctx* ctx, const uint32_t* program, size_t n_words, const ts_matrix* src, ts_matrix** out);
 /* Host only, no context: every check above that needs no matrix, against a source of src_width columns; the text of a
@@ -1417,6 +1417,71 @@ ts_status ts_derive_check(const uint32_t* program, size_t n_words, uint32_t src_
  * for tests and for callers without a device, not a fast path. */
 ts_status ts_derive_rows_host(const uint32_t* program, size_t n_words, const uint32_t* src_row_major, uint64_t height,
                               uint32_t src_width, uint32_t* out_row_major, size_t out_cap_words);
+
+/* ---- scanned columns: linear recurrences down the rows, in HBM ----
+ * The derive closed the host round trip for columns that are a function of their own row and its neighbours; this closes
+ * it for the columns a sequential machine's trace is made of: the value a read returns (the last value written to its
+ * address), a running count, sum or balance inside a group, a byte-to-word Horner accumulator, the running product of a
+ * permutation argument, a running random linear combination.  Each is a first-order linear recurrence over BabyBear,
+ *   y[i] = a[i] * y[i-1] + b[i],   y[-1] = init,
+ * optionally started over where a group starts.  It replaces: ts_matrix_download, a sequential host loop,
+ * ts_matrix_upload.
+ * A spec holds 1 to TS_SCAN_MAX_COLUMNS scans over the same source; each names its a and b (a constant < p, or a column
+ * of src whose word is read AS STORED and reduced mod p -- 0xFFFFFFFF gives 268435453 and p gives 0), init (canonical),
+ * a reset column or TS_SCAN_NO_RESET (where that column's word, reduced mod p, is != 0, row i starts over:
+ * y[i] = a[i] * init + b[i]), its dst column and flags.  TS_SCAN_EXCLUSIVE: dst[i] is the state BEFORE row i -- y[i-1],
+ * init on row 0 and on a reset row -- instead of y[i].
+ * Output: *out is a NEW row-major matrix of src's height.  Its width is W = max(src_width, 1 + max dst_column) when
+ * out_width is 0; else out_width, with 1 + max dst_column <= out_width <= W: the result keeps columns [0, out_width)
+ * only, so helper columns at the tail of src (an `a` and a `b` made by ts_matrix_derive) are dropped.  Every dst word is
+ * canonical.  Every other kept column must be < src_width and is copied from src as stored (not reduced); every kept
+ * column >= src_width must be a dst, and no column may be dst twice.  All reads see src: a scan that overwrites column c
+ * does not change what another scan reads from c.  src is neither consumed nor written.  The result is a pure function
+ * of src: field arithmetic is exact and the composition of the maps x -> a x + b associative, so it is the same on every
+ * run and for every value of the knob below.  finals, if not NULL, receives n_columns words: y[h-1] of each scan,
+ * canonical (for an exclusive scan too: the state AFTER the last row).
+ * TS_ERR_INVALID, each with a text in ts_last_error, before any device work: a NULL argument (finals may be NULL); a
+ * wrong struct_size; n_columns outside 1..8; a term kind above 1; a constant or init that is not below p; a column
+ * outside src; a flag bit above 0; a broken rule on dst columns or out_width; a width above 2^16; a height outside
+ * [1, 2^27] (any value inside is taken); a matrix that is not row-major, is consumed or belongs to another context;
+ * TS_SCAN_BLOCK_ROWS outside its range.  A refused call leaves *out NULL.
+ * Launches: THREE kernels, reduce-then-scan, no workgroup waits for another.  (1) one workgroup per block of rows
+ * composes the maps of its rows, every scan at once, into one map per scan; (2) one workgroup scans the block maps and
+ * applies them to init: the state each block starts from, and y[h-1]; (3) the first grid again recomputes its in-block
+ * scan from that state, writes the dst words and copies the untouched kept columns with coalesced accesses.  The spec
+ * travels in the launch arguments; one bit per column goes to the device in one asynchronous copy through the context's
+ * page-locked staging arena.  Waits: with finals == NULL the call makes no host wait of its own (the arena waits once
+ * when it wraps, as for every small upload); with finals exactly one, for the copy back of n_columns words.
+ * Temporaries come from ctx's pool.
+ * TS_SCAN_BLOCK_ROWS (1 .. 1024, default 1024, read on every call) sets the rows one workgroup owns: a test knob that
+ * makes small matrices cross the wave, the workgroup and several trips of launch 2's loop.  No output depends on it.
+ * Out of scope: suffix (reverse) scans; extension-field state; more than one source matrix; second-order recurrences
+ * (y[i] from y[i-1] AND y[i-2]); a or b that depend on a scanned value (chain two calls); use inside batch lanes. */
+typedef struct { uint32_t kind, value; } ts_scan_term;      /* 0: constant, value < p;  1: column `value` of src */
+typedef struct {
+    ts_scan_term a, b;       /* y[i] = a[i] * y[i-1] + b[i] in BabyBear; a column word is read AS STORED and reduced mod p */
+    uint32_t init;           /* y[-1], canonical, < p */
+    uint32_t reset_column;   /* TS_SCAN_NO_RESET or a column of src: where its word, reduced mod p, is != 0, row i
+                                starts over: y[i] = a[i] * init + b[i] */
+    uint32_t dst_column;
+    uint32_t flags;          /* bit 0 TS_SCAN_EXCLUSIVE */
+} ts_scan_column;
+enum { TS_SCAN_MAX_COLUMNS = 8, TS_SCAN_EXCLUSIVE = 1 };
+#define TS_SCAN_NO_RESET 0xFFFFFFFFu
+typedef struct {
+    uint32_t struct_size, n_columns;            /* sizeof(ts_scan_spec); 1 .. 8 */
+    ts_scan_column columns[TS_SCAN_MAX_COLUMNS];
+    uint32_t out_width;      /* 0: W; else the result keeps columns [0, out_width) only */
+    uint32_t pad;
+} ts_scan_spec;
+ts_status ts_matrix_scan(ts_ctx* ctx, const ts_scan_spec* spec, const ts_matrix* src, ts_matrix** out,
+                         uint32_t* finals /* n_columns words: y[h-1] of each, canonical; may be NULL */);
+/* Host only, no context: every check above that needs no matrix (the text of a refusal is what ts_last_error returns
+ * for a NULL context), then the plain sequential loop over `height` host rows of src_width words.  out_row_major
+ * receives height * out-width words (TS_ERR_BUFFER if out_cap_words is less; nothing is written then, nor by a refused
+ * call).  A reference for tests and for callers without a device, not a fast path. */
+ts_status ts_scan_rows_host(const ts_scan_spec* spec, const uint32_t* src_row_major, uint64_t height, uint32_t src_width,
+                            uint32_t* out_row_major, size_t out_cap_words, uint32_t* finals /* may be NULL */);
 
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);

@@ -8,7 +8,8 @@
 //   get_symbolic_constraints      uni-stark/src/symbolic_builder.rs:52-64
 //   FilteredAirBuilder            p3-air (when_first_row / when_transition / when_last_row)
 // Write `eval(ts::air::Builder&)` the way the reference writes `eval(&self, builder: &mut AB)`, then
-// hand `builder.tape()` to ts_air_compile.  No dependency beyond the standard library.
+// hand `builder.tape()` to ts_air_compile.  No dependency beyond the standard library and tapstark.h beside it (whose
+// ts_scan_spec the Scan builder at the end fills).
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +17,8 @@
 #include <stdexcept>
 #include <tuple>
 #include <vector>
+
+#include "tapstark.h"
 
 namespace ts {
 namespace air {
@@ -456,6 +459,40 @@ inline DExpr operator*(DExpr x, uint64_t c) { return x * x.builder()->constant(c
 inline DExpr operator+(uint64_t c, DExpr x) { return x.builder()->constant(c) + x; }
 inline DExpr operator-(uint64_t c, DExpr x) { return x.builder()->constant(c) - x; }
 inline DExpr operator*(uint64_t c, DExpr x) { return x.builder()->constant(c) * x; }
+
+// ---- scans for ts_matrix_scan (include/tapstark.h "scanned columns"): the counterpart of tap-stark_amd/scan.py.  A
+// term is a constant (reduced mod p here) or Scan::col(c); add() appends one recurrence y[i] = a[i] y[i-1] + b[i] and
+// spec() is the struct the call takes.  Nothing is checked here: the call is the judge (a ninth scan is counted, not
+// stored, so that it is refused).
+class Scan {
+public:
+    static ts_scan_term constant(uint64_t v) { return ts_scan_term{0, (uint32_t)(v % P)}; }
+    static ts_scan_term col(uint32_t c) { return ts_scan_term{1, c}; }
+
+    explicit Scan(uint32_t out_width = 0) : spec_() {
+        spec_.struct_size = (uint32_t)sizeof(ts_scan_spec);
+        spec_.out_width = out_width;
+    }
+    Scan& add(uint32_t dst, ts_scan_term a, ts_scan_term b, uint32_t init = 0, uint32_t reset = TS_SCAN_NO_RESET,
+              bool exclusive = false) {
+        if (spec_.n_columns < TS_SCAN_MAX_COLUMNS)
+            spec_.columns[spec_.n_columns] = ts_scan_column{a, b, init, reset, dst, exclusive ? (uint32_t)TS_SCAN_EXCLUSIVE : 0u};
+        spec_.n_columns++;
+        return *this;
+    }
+    // y[i] = y[i-1] + src[i][column]
+    Scan& running_sum(uint32_t column, uint32_t dst, uint32_t reset = TS_SCAN_NO_RESET) {
+        return add(dst, constant(1), col(column), 0, reset);
+    }
+    // y[i] = src[i][column] * y[i-1], from 1
+    Scan& running_product(uint32_t column, uint32_t dst, uint32_t reset = TS_SCAN_NO_RESET) {
+        return add(dst, col(column), constant(0), 1, reset);
+    }
+    const ts_scan_spec& spec() const { return spec_; }
+
+private:
+    ts_scan_spec spec_;
+};
 
 }  // namespace air
 }  // namespace ts

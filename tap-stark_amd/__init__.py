@@ -13,3 +13,4 @@ from .stark import MultiKey, MultiKeyProof, MultiKeyTableOpening, prove_multi_ke
 from .air import BusReport, BusShare, bus_check  # noqa: F401
 from .stark import check_multi  # noqa: F401
 from .derive import DeriveBuilder, derive_check, derive_rows_host  # noqa: F401
+from .scan import ScanSpec, carry_last, running_product, running_sum, scan_rows_host  # noqa: F401

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "ts_bus_check", "ts_check_multi",
     "ts_matrix_sort_rows", "ts_matrix_gather_rows",
     "ts_matrix_derive", "ts_derive_check", "ts_derive_rows_host",
+    "ts_matrix_scan", "ts_scan_rows_host",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -196,6 +197,23 @@ class SortSpecC(C.Structure):
     """``ts_sort_spec`` (struct_size first)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_keys", C.c_uint32), ("key_columns", C.c_uint32 * 4),
                 ("group_keys", C.c_uint32), ("flags", C.c_uint32), ("n_live", C.c_uint64)]
+
+
+class ScanTermC(C.Structure):
+    """``ts_scan_term``."""
+    _fields_ = [("kind", C.c_uint32), ("value", C.c_uint32)]
+
+
+class ScanColumnC(C.Structure):
+    """``ts_scan_column``."""
+    _fields_ = [("a", ScanTermC), ("b", ScanTermC), ("init", C.c_uint32), ("reset_column", C.c_uint32),
+                ("dst_column", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ScanSpecC(C.Structure):
+    """``ts_scan_spec`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_columns", C.c_uint32), ("columns", ScanColumnC * 8),
+                ("out_width", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class BatchLookupItemC(C.Structure):
@@ -447,6 +465,8 @@ def lib() -> C.CDLL:
         l.ts_matrix_derive.argtypes = [C.c_void_p, u32p, C.c_size_t, C.c_void_p, voidpp]
         l.ts_derive_check.argtypes = [u32p, C.c_size_t, C.c_uint32, u32p, u32p, u32p]
         l.ts_derive_rows_host.argtypes = [u32p, C.c_size_t, u32p, C.c_uint64, C.c_uint32, u32p, C.c_size_t]
+        l.ts_matrix_scan.argtypes = [C.c_void_p, C.POINTER(ScanSpecC), C.c_void_p, voidpp, u32p]
+        l.ts_scan_rows_host.argtypes = [C.POINTER(ScanSpecC), u32p, C.c_uint64, C.c_uint32, u32p, C.c_size_t, u32p]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

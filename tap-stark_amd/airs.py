@@ -1165,6 +1165,37 @@ def memory_gap_program():
     return b
 
 
+def memory_table_unfilled_source_program():
+    """``memory_table_source_program`` for a table whose read values are still to be found: the same (n, 7) columns, but
+    ``value`` = ``is_write * value``, 0 on every read.  After the sort, ``memory_fill_helper_program`` and
+    ``memory_fill_scan`` put the read values back in HBM."""
+    b = memory_table_source_program()
+    b.output(b.col(MemoryAccessAir.IS_WRITE) * b.col(MemoryAccessAir.VALUE), MemoryAccessAir.VALUE)
+    return b
+
+
+def memory_fill_helper_program():
+    """The two columns ``memory_fill_scan`` reads, appended to the sorted (n, 8) table: 8 = ``a`` = ``live (1 -
+    is_write)``, 9 = ``b`` = ``is_write * value``.  A live read carries the value before it; a write, and every dead row,
+    keeps its own."""
+    from .derive import DeriveBuilder
+    A = MemoryTableAir
+    b = DeriveBuilder(8)
+    is_write = b.col(A.IS_WRITE)
+    b.output(b.col(A.LIVE) * (1 - is_write), 8)
+    b.output(is_write * b.col(A.VALUE), 9)
+    return b
+
+
+def memory_fill_scan():
+    """The value every read returns -- the last value written to its address -- as one scan over the (n, 10) matrix of
+    ``memory_fill_helper_program``: ``value[i] = a[i] value[i-1] + b[i]``, started over from 0 where ``start`` is 1 (the
+    first access of an address).  The result is the (n, 8) table again: the helper columns are dropped."""
+    from .scan import ScanSpec, col
+    A = MemoryTableAir
+    return ScanSpec(out_width=8).add(A.VALUE, a=col(8), b=col(9), init=0, reset=A.START)
+
+
 def generate_memory_table(accesses: np.ndarray) -> np.ndarray:
     """(n, 8) canonical u32 satisfying MemoryTableAir, all on the host (``np.lexsort``): what the device route --
     ``memory_table_source``, ``sort_rows``, ``fill_memory_gaps`` -- gives."""

@@ -18,6 +18,7 @@
 #include "jit.hpp"
 #include "logup.hpp"
 #include "prover_internal.hpp"
+#include "scan.hpp"
 #include "sort.hpp"
 
 // the program as the prover sees it; the handle is const in the prove calls, adopting a finished specialisation is not
@@ -1992,6 +1993,52 @@ ts_status ts_derive_rows_host(const uint32_t* program, size_t n_words, const uin
         TS_REQUIRE((uint64_t)out_cap_words >= height * prog.out_width, ts::TS_ERR_BUFFER,
                    "ts_derive_rows_host: the output buffer holds fewer than height * out_width words");
         ts::derive_rows_host(prog, src_row_major, height, out_row_major);
+    });
+}
+
+// Scanned columns: linear recurrences down the rows of a resident matrix (scan.hip), their checks and the sequential
+// loop over host rows (scan.cpp).
+namespace {
+ts::ScanSpec scan_spec(const std::string& call, const ts_scan_spec* spec) {
+    TS_REQUIRE(spec->struct_size == sizeof(ts_scan_spec), ts::TS_ERR_INVALID, call + ": bad struct_size");
+    TS_REQUIRE(spec->n_columns >= 1 && spec->n_columns <= TS_SCAN_MAX_COLUMNS, ts::TS_ERR_INVALID,
+               "scan: n_columns " + std::to_string(spec->n_columns) + " outside [1, 8]");
+    ts::ScanSpec s;
+    for (uint32_t k = 0; k < spec->n_columns; k++) {
+        const ts_scan_column& c = spec->columns[k];
+        s.columns.push_back({c.a.kind, c.a.value, c.b.kind, c.b.value, c.init, c.reset_column, c.dst_column, c.flags});
+    }
+    s.out_width = spec->out_width;
+    return s;
+}
+}  // namespace
+
+ts_status ts_matrix_scan(ts_ctx* ctx, const ts_scan_spec* spec, const ts_matrix* src, ts_matrix** out, uint32_t* finals) {
+    if (out) *out = nullptr;
+    if (!ctx) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(spec && src && out, ts::TS_ERR_INVALID, "ts_matrix_scan: null argument");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        const ts::ScanSpec s = scan_spec("ts_matrix_scan", spec);
+        auto m = std::make_unique<ts_matrix>();
+        m->m = ts::scan_matrix(ctx->ctx, s, src->m, finals);
+        *out = m.release();
+    });
+}
+
+ts_status ts_scan_rows_host(const ts_scan_spec* spec, const uint32_t* src_row_major, uint64_t height, uint32_t src_width,
+                            uint32_t* out_row_major, size_t out_cap_words, uint32_t* finals) {
+    return guard(nullptr, [&] {
+        TS_REQUIRE(spec && src_row_major && out_row_major, ts::TS_ERR_INVALID, "ts_scan_rows_host: null argument");
+        const ts::ScanSpec s = scan_spec("ts_scan_rows_host", spec);
+        TS_REQUIRE(height >= 1 && height <= ts::SCAN_MAX_HEIGHT, ts::TS_ERR_INVALID,
+                   "scan: the height of the source must be in [1, 2^27]");
+        const ts::ScanPlan plan = ts::scan_check(s, src_width);
+        TS_REQUIRE((uint64_t)out_cap_words >= height * plan.out_width, ts::TS_ERR_BUFFER,
+                   "ts_scan_rows_host: the output buffer holds fewer than height * out_width words");
+        ts::scan_rows_host(s, plan, src_row_major, height, out_row_major, finals);
     });
 }
 

@@ -384,6 +384,17 @@ class DeviceMatrix:
         self.ctx.check(self.ctx._l.ts_matrix_derive(self.ctx.h, _p(t), len(t), self.h, C.byref(h)))
         return DeviceMatrix(self.ctx, h)
 
+    def scan(self, spec, finals: bool = False):
+        """A new matrix of this height: the columns the scans of ``spec`` (a ``scan.ScanSpec``) name hold linear
+        recurrences down the rows of this matrix, the other kept columns are copied (``ts_matrix_scan``); this matrix is
+        only read.  With ``finals`` the pair (matrix, the last value of each scan) -- and one host wait."""
+        last = np.zeros(8, dtype=np.uint32)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._l.ts_matrix_scan(self.ctx.h, C.byref(spec.c_spec()), self.h, C.byref(h),
+                                                  _p(last) if finals else None))
+        out = DeviceMatrix(self.ctx, h)
+        return (out, last[:len(spec.columns)].copy()) if finals else out
+
     def device_ptr(self) -> int:
         """Row-major device pointer (``ts_matrix_device_ptr``): valid until the matrix is freed or consumed,
         ordered on the context's stream; ``from_device_ptr`` is the opposite direction."""
