@@ -584,6 +584,12 @@ void ts_host_free(void* p) {
 }
 
 // ------------------------------------------------------------------ matrices
+// a new handle that owns `m`
+static ts_matrix* new_matrix(ts::DeviceMatrix m) {
+    auto h = std::make_unique<ts_matrix>();
+    h->m = std::move(m);
+    return h.release();
+}
 static ts_status matrix_from(ts_ctx* ctx, const uint32_t* src, uint64_t height, uint32_t width,
                              hipMemcpyKind kind, ts_matrix** out, bool sync = true) {
     if (!ctx || !out) return TS_ERR_INVALID;
@@ -1084,11 +1090,7 @@ static void quotient_chunks(ts_ctx* ctx, const ts::AirProgram& p, const ts::Side
     ts::TwoAdicFriPcs pcs(ctx->ctx, load_cfg(&raw));  // same [1, 8] bound as everywhere else
     const std::vector<uint32_t> pis = public_slots(p, public_values, n_public, challenges, exposed);
     auto chunks = pcs.quotient_chunks(*trace_data->d, p, pis, load_ef(alpha), side);
-    for (size_t c = 0; c < chunks.size(); c++) {
-        auto m = std::make_unique<ts_matrix>();
-        m->m = std::move(chunks[c]);
-        chunks_out[c] = m.release();
-    }
+    for (size_t c = 0; c < chunks.size(); c++) chunks_out[c] = new_matrix(std::move(chunks[c]));
 }
 // The head of the four calls: the admission, then the side matrices the format takes, key first (the quotient over
 // (key, aux, trace)).  `key`, `aux_data`, `challenges` and `exposed` are null from a call that has no such argument.
@@ -1758,6 +1760,10 @@ ts_status ts_verify_pre_aux(const ts_fri_config* cfg, const ts_air* air, ts_chal
 
 // ------------------------------------------------------------------ LogUp aux columns
 namespace {
+void load_terms(const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
+    for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
+}
+
 ts::LogupSpec load_logup_spec(const ts_logup_spec* spec) {
     TS_REQUIRE(spec && spec->struct_size >= sizeof(ts_logup_spec), ts::TS_ERR_INVALID, "logup: null spec or bad struct_size");
     TS_REQUIRE(spec->n_interactions >= 1 && spec->n_interactions <= ts::LOGUP_MAX_INTERACTIONS && spec->interactions,
@@ -1767,28 +1773,32 @@ ts::LogupSpec load_logup_spec(const ts_logup_spec* spec) {
         const ts_logup_interaction& it = spec->interactions[i];
         TS_REQUIRE(it.n_values >= 1 && it.n_values <= ts::LOGUP_MAX_VALUES && it.values, ts::TS_ERR_INVALID,
                    "logup: between 1 and 8 values per interaction");
-        ts::LogupInteraction li;
-        li.multiplicity = ts::LogupTerm{it.multiplicity.kind, it.multiplicity.value};
-        for (uint32_t q = 0; q < it.n_values; q++) li.values.push_back(ts::LogupTerm{it.values[q].kind, it.values[q].value});
-        s.interactions.push_back(std::move(li));
+        s.interactions.push_back({ts::LogupTerm{it.multiplicity.kind, it.multiplicity.value}, {}});
+        load_terms(it.values, it.n_values, s.interactions.back().values);
     }
     return s;
 }
 
-ts::LogupMultSpec load_mult_spec(const ts_logup_mult_spec* spec) {
-    TS_REQUIRE(spec->struct_size == sizeof(ts_logup_mult_spec), ts::TS_ERR_INVALID,
-               "logup multiplicities: bad struct_size");
-    TS_REQUIRE(spec->n_values >= 1 && spec->n_values <= ts::LOGUP_MAX_VALUES && spec->table, ts::TS_ERR_INVALID,
+// what ts_logup_mult_spec and ts_logup_mult_bus_spec share: the struct's size and the table's terms
+void load_mult_table(bool size_ok, uint32_t n_values, const ts_logup_term* table, std::vector<ts::LogupTerm>& to) {
+    TS_REQUIRE(size_ok, ts::TS_ERR_INVALID, "logup multiplicities: bad struct_size");
+    TS_REQUIRE(n_values >= 1 && n_values <= ts::LOGUP_MAX_VALUES && table, ts::TS_ERR_INVALID,
                "logup multiplicities: between 1 and 8 values");
-    TS_REQUIRE(spec->n_lookups >= 1 && spec->n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && spec->lookups && spec->weights,
-               ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookups");
+    load_terms(table, n_values, to);
+}
+// and one set of lookups with their weights, n_values terms each
+void load_mult_lookups(uint32_t n_lookups, uint32_t n_values, const ts_logup_term* lookups,
+                       const ts_logup_term* weights, std::vector<ts::LogupTerm>& l, std::vector<ts::LogupTerm>& w) {
+    TS_REQUIRE(n_lookups >= 1 && n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && lookups && weights, ts::TS_ERR_INVALID,
+               "logup multiplicities: between 1 and 16 lookups, each with its weight");
+    load_terms(lookups, (size_t)n_lookups * n_values, l);
+    load_terms(weights, n_lookups, w);
+}
+
+ts::LogupMultSpec load_mult_spec(const ts_logup_mult_spec* spec) {
     ts::LogupMultSpec s;
-    auto load = [](const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
-        for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
-    };
-    load(spec->table, spec->n_values, s.table);
-    load(spec->lookups, (size_t)spec->n_lookups * spec->n_values, s.lookups);
-    load(spec->weights, spec->n_lookups, s.weights);
+    load_mult_table(spec->struct_size == sizeof(ts_logup_mult_spec), spec->n_values, spec->table, s.table);
+    load_mult_lookups(spec->n_lookups, spec->n_values, spec->lookups, spec->weights, s.lookups, s.weights);
     s.out_column = spec->out_column;
     s.negate = spec->negate;
     return s;
@@ -1801,19 +1811,26 @@ ts_status ts_logup_aux_width(const ts_logup_spec* spec, uint32_t* aux_width) {
     return guard(nullptr, [&] { *aux_width = ts::logup_aux_width(load_logup_spec(spec)); });
 }
 
-ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* trace,
-                             const uint32_t challenges[8], ts_matrix** aux_out, uint32_t exposed_out[4]) {
+namespace {
+ts_status aux_build(ts_ctx* ctx, const char* call, const ts_logup_spec* spec, const ts_matrix* preprocessed,
+                    bool takes_table, const ts_matrix* trace, const uint32_t challenges[8], ts_matrix** aux_out,
+                    uint32_t exposed_out[4]) {
     if (!ctx || !trace || !challenges || !aux_out || !exposed_out) {
-        if (ctx) ctx->ctx.last_error = "ts_logup_aux_build: null argument";
+        if (ctx) ctx->ctx.last_error = std::string(call) + ": null argument";
         return TS_ERR_INVALID;
     }
     *aux_out = nullptr;
     return guard(ctx, [&] {
         const ts::LogupSpec s = load_logup_spec(spec);
-        auto m = std::make_unique<ts_matrix>();
-        m->m = ts::logup_aux_build(ctx->ctx, s, trace->m, challenges, exposed_out);
-        *aux_out = m.release();
+        *aux_out = new_matrix(ts::logup_aux_build(ctx->ctx, s, trace->m, challenges, exposed_out,
+                                                  preprocessed ? &preprocessed->m : nullptr, takes_table));
     });
+}
+}  // namespace
+
+ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* trace,
+                             const uint32_t challenges[8], ts_matrix** aux_out, uint32_t exposed_out[4]) {
+    return aux_build(ctx, "ts_logup_aux_build", spec, nullptr, false, trace, challenges, aux_out, exposed_out);
 }
 
 // ts_logup_aux_build with terms of kind 2: columns of a row-major table of the trace's height (the values of a
@@ -1821,18 +1838,7 @@ ts_status ts_logup_aux_build(ts_ctx* ctx, const ts_logup_spec* spec, const ts_ma
 ts_status ts_logup_aux_build_pre(ts_ctx* ctx, const ts_logup_spec* spec, const ts_matrix* preprocessed,
                                  const ts_matrix* trace, const uint32_t challenges[8], ts_matrix** aux_out,
                                  uint32_t exposed_out[4]) {
-    if (!ctx || !trace || !challenges || !aux_out || !exposed_out) {
-        if (ctx) ctx->ctx.last_error = "ts_logup_aux_build_pre: null argument";
-        return TS_ERR_INVALID;
-    }
-    *aux_out = nullptr;
-    return guard(ctx, [&] {
-        const ts::LogupSpec s = load_logup_spec(spec);
-        auto m = std::make_unique<ts_matrix>();
-        m->m = ts::logup_aux_build(ctx->ctx, s, trace->m, challenges, exposed_out, preprocessed ? &preprocessed->m : nullptr,
-                                   /*takes_table=*/true);
-        *aux_out = m.release();
-    });
+    return aux_build(ctx, "ts_logup_aux_build_pre", spec, preprocessed, true, trace, challenges, aux_out, exposed_out);
 }
 
 // The multiplicity column of one table, in place in the resident trace (logup_mult.hip).
@@ -1863,26 +1869,16 @@ ts_status mult_bus(ts_ctx* ctx, const ts_logup_mult_bus_spec* spec, const ts_mat
     if (first_missing) first_missing[0] = first_missing[1] = first_missing[2] = ~0ull;
     return guard(ctx, [&] {
         TS_REQUIRE(spec && table_trace && lookers, ts::TS_ERR_INVALID, "ts_logup_multiplicities_bus: null argument");
-        TS_REQUIRE(spec->struct_size == sizeof(ts_logup_mult_bus_spec), ts::TS_ERR_INVALID,
-                   "logup multiplicities: bad struct_size");
-        TS_REQUIRE(spec->n_values >= 1 && spec->n_values <= ts::LOGUP_MAX_VALUES && spec->table, ts::TS_ERR_INVALID,
-                   "logup multiplicities: between 1 and 8 values");
+        ts::LogupMultBusSpec s;
+        load_mult_table(spec->struct_size == sizeof(ts_logup_mult_bus_spec), spec->n_values, spec->table, s.table);
         TS_REQUIRE(spec->n_lookers >= 1 && spec->n_lookers <= ts::LOGUP_MULT_MAX_LOOKERS && spec->lookers,
                    ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookers");
-        auto load = [](const ts_logup_term* from, size_t count, std::vector<ts::LogupTerm>& to) {
-            for (size_t i = 0; i < count; i++) to.push_back(ts::LogupTerm{from[i].kind, from[i].value});
-        };
-        ts::LogupMultBusSpec s;
-        load(spec->table, spec->n_values, s.table);
         std::vector<const ts::DeviceMatrix*> mats;
         for (uint32_t k = 0; k < spec->n_lookers; k++) {
             const ts_logup_bus_looker& in = spec->lookers[k];
-            TS_REQUIRE(in.n_lookups >= 1 && in.n_lookups <= ts::LOGUP_MULT_MAX_LOOKUPS && in.lookups && in.weights,
-                       ts::TS_ERR_INVALID, "logup multiplicities: between 1 and 16 lookups per looker");
-            TS_REQUIRE(lookers[k], ts::TS_ERR_INVALID, "ts_logup_multiplicities_bus: null looker");
             ts::LogupMultLooker lk;
-            load(in.lookups, (size_t)in.n_lookups * spec->n_values, lk.lookups);
-            load(in.weights, in.n_lookups, lk.weights);
+            load_mult_lookups(in.n_lookups, spec->n_values, in.lookups, in.weights, lk.lookups, lk.weights);
+            TS_REQUIRE(lookers[k], ts::TS_ERR_INVALID, "ts_logup_multiplicities_bus: null looker");
             s.lookers.push_back(std::move(lk));
             mats.push_back(&lookers[k]->m);
         }
@@ -1934,9 +1930,7 @@ ts_status ts_matrix_sort_rows(ts_ctx* ctx, const ts_sort_spec* spec, const ts_ma
         s.group_keys = spec->group_keys;
         s.flags = spec->flags;
         s.n_live = spec->n_live;
-        auto m = std::make_unique<ts_matrix>();
-        m->m = ts::sort_rows(ctx->ctx, s, src->m);
-        *out = m.release();
+        *out = new_matrix(ts::sort_rows(ctx->ctx, s, src->m));
     });
 }
 
@@ -1949,9 +1943,7 @@ ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matr
         return TS_ERR_INVALID;
     }
     return guard(ctx, [&] {
-        auto m = std::make_unique<ts_matrix>();
-        m->m = ts::gather_rows(ctx->ctx, src->m, index->m, index_column);
-        *out = m.release();
+        *out = new_matrix(ts::gather_rows(ctx->ctx, src->m, index->m, index_column));
     });
 }
 
@@ -1964,9 +1956,7 @@ ts_status ts_matrix_derive(ts_ctx* ctx, const uint32_t* program, size_t n_words,
     }, false);
     if (refused) return refused;
     return guard(ctx, [&] {
-        auto m = std::make_unique<ts_matrix>();
-        m->m = ts::derive_matrix(ctx->ctx, program, n_words, src->m);
-        *out = m.release();
+        *out = new_matrix(ts::derive_matrix(ctx->ctx, program, n_words, src->m));
     });
 }
 
@@ -2022,9 +2012,7 @@ ts_status ts_matrix_scan(ts_ctx* ctx, const ts_scan_spec* spec, const ts_matrix*
     if (refused) return refused;
     return guard(ctx, [&] {
         const ts::ScanSpec s = scan_spec("ts_matrix_scan", spec);
-        auto m = std::make_unique<ts_matrix>();
-        m->m = ts::scan_matrix(ctx->ctx, s, src->m, finals);
-        *out = m.release();
+        *out = new_matrix(ts::scan_matrix(ctx->ctx, s, src->m, finals));
     });
 }
 

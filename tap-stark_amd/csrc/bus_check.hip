@@ -21,7 +21,7 @@
 //                 64-bit atomicAdd of the canonical multiplicity: integer adds commute, and 2^30 * p < 2^61.  A wave
 //                 whose contributions of one interaction all carry ONE tuple sends its lowest lane alone through the
 //                 probe and sums the multiplicities with shuffles into one add (the wave-level combine of
-//                 mult_add_hits, extended to the probe): 0.39 ms against 18.3 on 2^20 rows of one tuple, 12.3 with the
+//                 add_hits, extended to the probe): 0.39 ms against 18.3 on 2^20 rows of one tuple, 12.3 with the
 //                 add combined alone; no difference beyond the run-to-run spread on the bus statements
 //                 (profiles/bus_check.json, profiles/bus_check_combine_experiment.json).
 //   k_bus_scan    one slot per lane (plain loads: an earlier launch wrote them): the used slots, those whose sum is not
@@ -31,30 +31,25 @@
 //                 read once per lane with uniform loads, and every contribution of that tuple is counted per table:
 //                 count, integer sum and least (row, interaction), combined inside the wave (a wave lies in one table)
 //                 and added with one atomic each.
-// Nothing is written to a trace.  TS_LOGUP_HASH_BITS is honoured as in logup_mult.hip (logup_hash.hpp).
+// Nothing is written to a trace.  TS_LOGUP_HASH_BITS is honoured as in logup_mult.hip (logup_dev.hpp).
 #include <string.h>
 
 #include <string>
 
-#include "logup_hash.hpp"
+#include "logup_dev.hpp"
 
 namespace ts {
 
 constexpr int BUS_THREADS = 256;
 constexpr unsigned long long BUS_EMPTY = ~0ull;
 
-typedef const uint32_t __attribute__((address_space(1)))* BusGlobalConstWords;
-struct BusInteraction {
-    uint32_t m_kind, m_val, n_values, pad;
-    uint32_t kind[LOGUP_MAX_VALUES], val[LOGUP_MAX_VALUES];
-};
 // one per table, at the table's index; a table that is not on the bus has K = 0, no rows and no workgroups
 struct BusJob {
-    BusGlobalConstWords trace;
-    BusGlobalConstWords pre;  // the row-major values of its preprocessed columns (kind-2 terms), or null
+    GlobalConstWords trace;
+    GlobalConstWords pre;  // the row-major values of its preprocessed columns (kind-2 terms), or null
     uint64_t n;
     uint32_t first_block, K, width, pre_width;
-    BusInteraction it[LOGUP_MAX_INTERACTIONS];
+    LogupInteractionDev it[LOGUP_MAX_INTERACTIONS];
 };
 
 // what the first copy back holds
@@ -79,17 +74,6 @@ __host__ __device__ __forceinline__ uint32_t bus_key_table(unsigned long long ke
 __host__ __device__ __forceinline__ uint32_t bus_key_row(unsigned long long key) { return (uint32_t)key >> 4; }
 __host__ __device__ __forceinline__ uint32_t bus_key_interaction(unsigned long long key) { return (uint32_t)key & 15u; }
 
-// first[lo] <= blockIdx.x < first[lo + 1]: the same in every lane (tables without workgroups are stepped over)
-__device__ __forceinline__ uint32_t bus_job_of_block(const uint32_t* __restrict__ first, uint32_t n_jobs) {
-    uint32_t lo = 0, hi = n_jobs;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (first[mid] <= blockIdx.x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ const uint32_t* bus_row(const BusJob& j, uint64_t r) {
     return (const uint32_t*)j.trace + r * j.width;
 }
@@ -98,7 +82,7 @@ __device__ __forceinline__ const uint32_t* bus_pre_row(const BusJob& j, uint64_t
 }
 
 // the zero-padded tuple of interaction i on the row
-__device__ __forceinline__ MultTuple bus_tuple(const BusInteraction& it, const uint32_t* __restrict__ row,
+__device__ __forceinline__ MultTuple bus_tuple(const LogupInteractionDev& it, const uint32_t* __restrict__ row,
                                                const uint32_t* __restrict__ pre_row) {
     MultTuple out;
 #pragma unroll
@@ -114,47 +98,11 @@ __device__ __forceinline__ MultTuple bus_tuple_of_key(const BusJob* __restrict__
     return bus_tuple(j.it[bus_key_interaction(key)], row, bus_pre_row(j, bus_key_row(key), row));
 }
 
-__device__ __forceinline__ unsigned long long bus_shfl_xor(unsigned long long v, int d) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-// over the wave; every lane calls them
-__device__ __forceinline__ unsigned long long bus_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += bus_shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ unsigned long long bus_wave_min(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = bus_shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-// sums[at] += m on the lanes with `hit`; EVERY lane of the wave calls it (ballots), dead lanes with hit = false.  A
-// wave whose hits all go to ONE slot (padding rows, a selector-heavy trace) sums them with shuffles and issues one
-// add, as mult_add_hits does in logup_mult.hip; every other wave issues one add per hit.
-__device__ __forceinline__ void bus_add_hits(bool hit, uint32_t at, uint32_t m, unsigned long long* __restrict__ sums) {
-    const unsigned long long hits = __ballot(hit);
-    if (hits == 0) return;  // (wave-uniform)
-    const int leader = __ffsll((long long)hits) - 1;
-    const uint32_t dest = (uint32_t)__shfl((int)at, leader, 64);
-    if ((hits & (hits - 1)) && __ballot(hit && at == dest) == hits) {
-        const unsigned long long sum = bus_wave_sum(hit ? (unsigned long long)m : 0ull);
-        if ((threadIdx.x & 63) == (unsigned)leader) atomicAdd(sums + dest, sum);
-    } else if (hit) {
-        atomicAdd(sums + at, (unsigned long long)m);
-    }
-}
-
 __global__ void __launch_bounds__(BUS_THREADS)
 k_bus_insert(const BusJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs, uint32_t hash_mask,
              uint32_t cap_mask, unsigned long long* __restrict__ slots, unsigned long long* __restrict__ sums,
              BusBack* __restrict__ back) {
-    const uint32_t table = bus_job_of_block(first, n_jobs);
+    const uint32_t table = job_of_block(first, n_jobs);
     const BusJob& j = jobs[table];
     const uint64_t r = (uint64_t)(blockIdx.x - j.first_block) * BUS_THREADS + threadIdx.x;
     const bool live = r < j.n;  // (no early return: every lane of the wave takes part in the ballots and sums below)
@@ -162,7 +110,7 @@ k_bus_insert(const BusJob* __restrict__ jobs, const uint32_t* __restrict__ first
     const uint32_t* pre_row = bus_pre_row(j, live ? r : 0, row);
     unsigned long long mine = 0;
     for (uint32_t i = 0; i < j.K; i++) {  // (K is the job's: the same trip count in every lane)
-        const BusInteraction& it = j.it[i];
+        const LogupInteractionDev& it = j.it[i];
         const uint32_t m = live ? mult_canonical(mult_term(it.m_kind, it.m_val, row, pre_row)) : 0;
         // a wave whose contributions of this interaction all carry ONE tuple sends its lowest lane alone through the
         // probe (lanes ascend with the rows, so that lane holds the wave's least key) and shares the slot it found
@@ -199,9 +147,9 @@ k_bus_insert(const BusJob* __restrict__ jobs, const uint32_t* __restrict__ first
             at = (uint32_t)__shfl((int)at, leader, 64);
             placed = m != 0 && __shfl((int)placed, leader, 64) != 0;
         }
-        bus_add_hits(placed, at, m, sums);
+        add_hits(placed, at, m, sums);
     }
-    const unsigned long long total = bus_wave_sum(mine);
+    const unsigned long long total = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && total) atomicAdd(&back->n_contributions, total);
 }
 
@@ -214,7 +162,7 @@ k_bus_scan(const unsigned long long* __restrict__ slots, const unsigned long lon
     const bool bad = used && sums[at] % P != 0;
     const unsigned long long n_used = __popcll(__ballot(used)), n_bad = __popcll(__ballot(bad));
     if (n_used == 0) return;  // (wave-uniform)
-    const unsigned long long least = n_bad ? bus_wave_min(bad ? key : BUS_EMPTY) : BUS_EMPTY;
+    const unsigned long long least = n_bad ? wave_min(bad ? key : BUS_EMPTY) : BUS_EMPTY;
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&back->n_tuples, n_used);
         if (n_bad) {
@@ -227,7 +175,7 @@ k_bus_scan(const unsigned long long* __restrict__ slots, const unsigned long lon
 __global__ void __launch_bounds__(BUS_THREADS)
 k_bus_shares(const BusJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs,
              unsigned long long reported, BusShareDev* __restrict__ shares, BusTupleBack* __restrict__ tuple_back) {
-    const uint32_t table = bus_job_of_block(first, n_jobs);
+    const uint32_t table = job_of_block(first, n_jobs);
     const BusJob& j = jobs[table];
     const MultTuple target = bus_tuple_of_key(jobs, reported);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -241,7 +189,7 @@ k_bus_shares(const BusJob* __restrict__ jobs, const uint32_t* __restrict__ first
         const uint32_t* row = bus_row(j, r);
         const uint32_t* pre_row = bus_pre_row(j, r, row);
         for (uint32_t i = 0; i < j.K; i++) {
-            const BusInteraction& it = j.it[i];
+            const LogupInteractionDev& it = j.it[i];
             const uint32_t m = mult_canonical(mult_term(it.m_kind, it.m_val, row, pre_row));
             if (m == 0 || !mult_equal(bus_tuple(it, row, pre_row), target)) continue;
             count++;
@@ -250,9 +198,9 @@ k_bus_shares(const BusJob* __restrict__ jobs, const uint32_t* __restrict__ first
             least = at < least ? at : least;
         }
     }
-    count = bus_wave_sum(count);
-    sum = bus_wave_sum(sum);
-    least = bus_wave_min(least);
+    count = wave_sum(count);
+    sum = wave_sum(sum);
+    least = wave_min(least);
     if ((threadIdx.x & 63) == 0 && count) {
         atomicAdd(&shares[table].count, count);
         atomicAdd(&shares[table].sum, sum);
@@ -280,23 +228,13 @@ BusReport bus_check(Context& ctx, const std::vector<const LogupSpec*>& specs,
         TS_REQUIRE(traces[k], TS_ERR_INVALID, "bus check: a spec without a trace");
         logup_check_spec(ctx, *specs[k], *traces[k], tables[k]);
         const LogupSpec& spec = *specs[k];
-        j.trace = (BusGlobalConstWords)traces[k]->buf.p;
-        j.pre = tables[k] ? (BusGlobalConstWords)tables[k]->buf.p : nullptr;
+        j.trace = (GlobalConstWords)traces[k]->buf.p;
+        j.pre = tables[k] ? (GlobalConstWords)tables[k]->buf.p : nullptr;
         j.n = traces[k]->height;
         j.K = (uint32_t)spec.interactions.size();
         j.width = traces[k]->width;
         j.pre_width = tables[k] ? tables[k]->width : 0;
-        for (uint32_t i = 0; i < j.K; i++) {
-            const LogupInteraction& in = spec.interactions[i];
-            BusInteraction& it = j.it[i];
-            it.m_kind = in.multiplicity.kind;
-            it.m_val = in.multiplicity.value;
-            it.n_values = (uint32_t)in.values.size();
-            for (size_t q = 0; q < in.values.size(); q++) {
-                it.kind[q] = in.values[q].kind;
-                it.val[q] = in.values[q].value;
-            }
-        }
+        load_interactions(spec, j.it);
         n_blocks += (j.n + BUS_THREADS - 1) / BUS_THREADS;
         possible += j.n * j.K;
     }
@@ -309,15 +247,9 @@ BusReport bus_check(Context& ctx, const std::vector<const LogupSpec*>& specs,
     uint64_t capacity = 2;
     while (capacity < 2 * possible) capacity <<= 1;  // <= 2^31
     const uint32_t cap_mask = (uint32_t)(capacity - 1);
-    // the jobs and, behind them, the first-workgroup prefix: one upload
-    static_assert(sizeof(BusJob) % 8 == 0, "the prefix follows the jobs, aligned");
-    std::vector<char> tab(T * sizeof(BusJob) + (T + 1) * sizeof(uint32_t));
-    memcpy(tab.data(), (const void*)jobs.data(), T * sizeof(BusJob));
-    memcpy(tab.data() + T * sizeof(BusJob), first.data(), (T + 1) * sizeof(uint32_t));
-    DevBuf<unsigned long long> d_tab(&ctx, (tab.size() + 7) / 8);
-    h2d(ctx, d_tab.p, tab.data(), tab.size());
-    const BusJob* d_jobs = reinterpret_cast<const BusJob*>(d_tab.p);
-    const uint32_t* d_first = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(d_tab.p) + T * sizeof(BusJob));
+    const JobTable<BusJob> d_tab = upload_jobs(ctx, jobs, first);
+    const BusJob* d_jobs = d_tab.jobs;
+    const uint32_t* d_first = d_tab.first;
     DevBuf<unsigned long long> slots(&ctx, capacity);
     DevBuf<unsigned long long> sums(&ctx, capacity);
     DevBuf<BusBack> back(&ctx, 1);

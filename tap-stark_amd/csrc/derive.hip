@@ -78,10 +78,7 @@ k_derive(const uint4* __restrict__ code, const uint32_t* __restrict__ named, con
 
 DeviceMatrix derive_matrix(Context& ctx, const uint32_t* program, size_t n_words, const DeviceMatrix& src) {
     StageTimer timer(&ctx, "derive");
-    TS_REQUIRE(src.buf.p && src.layout == DeviceMatrix::ROW_MAJOR && src.buf.ctx == &ctx, TS_ERR_INVALID,
-               "derive: the source must be a row-major, unconsumed matrix made on this context");
-    TS_REQUIRE(src.height >= 1 && src.height <= DERIVE_MAX_HEIGHT && src.width >= 1, TS_ERR_INVALID,
-               "derive: the height of the source must be in [1, 2^27]");
+    require_resident(ctx, src, "derive", "the source");
     const DeriveProgram prog = derive_lower(program, n_words, src.width);
 
     DeviceMatrix out;

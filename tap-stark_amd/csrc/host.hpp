@@ -70,6 +70,14 @@ struct DeviceMatrix {
     uint32_t width = 0;
     Layout layout = ROW_MAJOR;
 };
+// The admission of a resident matrix that `call` reads or fills in place, before anything is allocated or launched
+// (TS_ERR_INVALID): row-major, not consumed, of this context, between 1 and 2^27 rows and at least one column.
+inline void require_resident(const Context& ctx, const DeviceMatrix& m, const char* call, const char* what) {
+    TS_REQUIRE(m.buf.p && m.layout == DeviceMatrix::ROW_MAJOR && m.buf.ctx == &ctx, TS_ERR_INVALID,
+               std::string(call) + ": " + what + " must be a row-major, unconsumed matrix made on this context");
+    TS_REQUIRE(m.height >= 1 && m.height <= (1ull << 27) && m.width >= 1, TS_ERR_INVALID,
+               std::string(call) + ": the height of " + what + " must be in [1, 2^27]");
+}
 
 // Pcs::ProverData / BFMmcs::ProverData: the committed LDEs (column-major, bit-reversed rows) and
 // the whole Merkle tree, all resident in HBM.

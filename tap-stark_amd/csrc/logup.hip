@@ -21,7 +21,7 @@
 
 #include <string>
 
-#include "logup.hpp"
+#include "logup_dev.hpp"
 
 namespace ts {
 
@@ -34,10 +34,7 @@ struct LogupDev {
     uint32_t K, G, width, aux_width, table_width;
     Ef gamma_mont;                        // gamma R
     Ef beta_pow[LOGUP_MAX_VALUES];        // beta^j R^2: times a canonical value = (beta^j v) R
-    struct {
-        uint32_t m_kind, m_val, n_values, pad;
-        uint32_t kind[LOGUP_MAX_VALUES], val[LOGUP_MAX_VALUES];
-    } it[LOGUP_MAX_INTERACTIONS];
+    LogupInteractionDev it[LOGUP_MAX_INTERACTIONS];
 };
 
 __device__ __forceinline__ Ef ef_shfl_up(Ef v, unsigned delta) {
@@ -69,12 +66,6 @@ __device__ __forceinline__ Ef block_scan_inclusive(Ef v, Ef (&wave_sums)[NW], Ef
     return ef_add(v, before);
 }
 
-// kind 0: the constant; 1: column `val` of the trace's row; 2: column `val` of the table's row (ts_logup_aux_build_pre)
-__device__ __forceinline__ uint32_t term_value(uint32_t kind, uint32_t val, const uint32_t* __restrict__ row,
-                                               const uint32_t* __restrict__ table_row) {
-    return kind == 0 ? val : (kind == 1 ? row : table_row)[val];
-}
-
 // sum_g h_g(r), with the h_g written to the row's first 4 G words
 __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __restrict__ row,
                                         const uint32_t* __restrict__ table_row, uint64_t r,
@@ -97,13 +88,13 @@ __device__ __forceinline__ Ef logup_row(const LogupDev& s, const uint32_t* __res
 #pragma unroll
                 for (int q = 0; q < LOGUP_MAX_VALUES; q++)
                     if (q < (int)nv)
-                        d = ef_add(d, ef_mul_base(s.beta_pow[q], term_value(s.it[i].kind[q], s.it[i].val[q], row, table_row)));
+                        d = ef_add(d, ef_mul_base(s.beta_pow[q], mult_term(s.it[i].kind[q], s.it[i].val[q], row, table_row)));
                 ef_inv_parts(d, num[j], nrm[j]);
                 if (nrm[j] == 0) {  // d == 0: reported, and the batch goes on as if the norm were one
                     atomicMin(flag, flag_base + (unsigned long long)r * s.K + i);
                     nrm[j] = R_MOD_P;
                 }
-                mult[j] = term_value(s.it[i].m_kind, s.it[i].m_val, row, table_row);
+                mult[j] = mult_term(s.it[i].m_kind, s.it[i].m_val, row, table_row);
             }
             pre[j] = run;
             run = mont_mul(run, nrm[j]);
@@ -223,34 +214,18 @@ k_logup_scan(uint32_t aux_width, uint32_t G, uint64_t n, uint32_t block_rows, ui
 }
 
 // ---- every table of a multi-table proof in the same three launches (logup_aux_build_multi).  The specs live in a
-// job table in device memory instead of the launch argument; a workgroup finds its job from the first-workgroup
-// prefix `first` (n_jobs + 1 ascending words, first[n_jobs] = the grid) with a search on blockIdx alone, so the job
-// index is the same in every lane and the job's words are read with scalar loads, as k_reduce_class reads its jobs.
-// (a pointer read from memory is a generic one to the compiler and costs flat loads and stores; the job's pointers
-// are device allocations and are typed so, which keeps the global accesses the by-value kernels have)
-typedef const uint32_t __attribute__((address_space(1)))* LogupGlobalConstWords;
-typedef uint32_t __attribute__((address_space(1)))* LogupGlobalWords;
+// job table in device memory instead of the launch argument (logup_dev.hpp: job_of_block, the typed pointers).
 struct LogupJob {
     LogupDev s;
-    LogupGlobalConstWords trace;
-    LogupGlobalWords aux;
+    GlobalConstWords trace;
+    GlobalWords aux;
     uint64_t n;
     uint32_t first_block, n_blocks;  // its workgroups in the rows and scan launches = its stretch of `totals`
     uint32_t index;                  // the table's number: the high word of a zero-denominator report, its S slot
     uint32_t pad;
-    LogupGlobalConstWords table;     // the row-major values of its preprocessed columns (kind-2 terms), or null
+    GlobalConstWords table;     // the row-major values of its preprocessed columns (kind-2 terms), or null
     uint64_t pad2;
 };
-
-__device__ __forceinline__ uint32_t logup_job_of_block(const uint32_t* __restrict__ first, uint32_t n_jobs) {
-    uint32_t lo = 0, hi = n_jobs;  // first[lo] <= blockIdx.x < first[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (first[mid] <= blockIdx.x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // TABLES = false is the kernel of logup_aux_build_multi, unchanged.  TABLES = true is launched only when some job
 // has a table (logup_aux_build_multi_pre): a job with one runs logup_rows_block<true>, a job without keeps the
@@ -262,7 +237,7 @@ template <bool TABLES>
 __global__ void __launch_bounds__(LOGUP_THREADS)
 k_logup_rows_jobs(const LogupJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs,
                   uint32_t block_rows, uint32_t rpt, Ef* __restrict__ totals, unsigned long long* __restrict__ flag) {
-    const LogupJob& j = jobs[logup_job_of_block(first, n_jobs)];
+    const LogupJob& j = jobs[job_of_block(first, n_jobs)];
     if (TABLES && j.table)
         logup_rows_block<true>(j.s, (const uint32_t*)j.trace, (const uint32_t*)j.table, j.n, block_rows, rpt,
                                blockIdx.x - j.first_block, (uint32_t*)j.aux, totals + j.first_block, flag,
@@ -282,7 +257,7 @@ k_logup_totals_jobs(const LogupJob* __restrict__ jobs, Ef* __restrict__ totals) 
 __global__ void __launch_bounds__(LOGUP_THREADS)
 k_logup_scan_jobs(const LogupJob* __restrict__ jobs, const uint32_t* __restrict__ first, uint32_t n_jobs,
                   uint32_t block_rows, uint32_t rpt, const Ef* __restrict__ totals, Ef* __restrict__ S) {
-    const LogupJob& j = jobs[logup_job_of_block(first, n_jobs)];
+    const LogupJob& j = jobs[job_of_block(first, n_jobs)];
     logup_scan_block(j.s.aux_width, j.s.G, j.n, block_rows, rpt, blockIdx.x - j.first_block, (uint32_t*)j.aux,
                      totals + j.first_block, S + j.index);
 }
@@ -319,34 +294,22 @@ static LogupDev logup_dev(Context& ctx, const LogupSpec& spec, const DeviceMatri
                           const DeviceMatrix* table, bool takes_table) {
     LogupDev s;
     memset(&s, 0, sizeof s);
-    s.aux_width = logup_aux_width(spec, takes_table ? 2 : 1);
+    const uint32_t max_kind = takes_table ? 2 : 1;
+    s.aux_width = logup_aux_width(spec, max_kind);
     s.K = (uint32_t)spec.interactions.size();
     s.G = (s.K + 1) / 2;
-    TS_REQUIRE(trace.buf.p && trace.layout == DeviceMatrix::ROW_MAJOR && trace.buf.ctx == &ctx, TS_ERR_INVALID,
-               "logup: needs a row-major, unconsumed trace made on this context");
-    TS_REQUIRE(trace.height >= 1 && trace.height <= (1ull << 27) && trace.width >= 1, TS_ERR_INVALID,
-               "logup: trace height must be in [1, 2^27]");
+    require_resident(ctx, trace, "logup", "the trace");
     s.width = trace.width;
     if (table) {
-        TS_REQUIRE(table->buf.p && table->layout == DeviceMatrix::ROW_MAJOR && table->buf.ctx == &ctx, TS_ERR_INVALID,
-                   "logup: the preprocessed table must be row-major, unconsumed and made on this context");
-        TS_REQUIRE(table->height == trace.height && table->width >= 1, TS_ERR_INVALID,
-                   "logup: the preprocessed table must have the trace's height");
+        require_resident(ctx, *table, "logup", "the preprocessed table");
+        TS_REQUIRE(table->height == trace.height, TS_ERR_INVALID, "logup: the preprocessed table must have the trace's height");
         s.table_width = table->width;
     }
-    auto term = [&](const LogupTerm& tm, uint32_t& kind, uint32_t& val) {
-        TS_REQUIRE(tm.kind != 2 || table, TS_ERR_INVALID, "logup: a preprocessed-column term without a preprocessed table");
-        TS_REQUIRE(tm.kind == 2 ? tm.value < s.table_width : tm.kind ? tm.value < trace.width : tm.value < P, TS_ERR_INVALID,
-                   "logup: a column outside the trace or the preprocessed table, or a non-canonical constant");
-        kind = tm.kind;
-        val = tm.value;
-    };
-    for (uint32_t i = 0; i < s.K; i++) {
-        const LogupInteraction& it = spec.interactions[i];
-        term(it.multiplicity, s.it[i].m_kind, s.it[i].m_val);
-        s.it[i].n_values = (uint32_t)it.values.size();
-        for (size_t q = 0; q < it.values.size(); q++) term(it.values[q], s.it[i].kind[q], s.it[i].val[q]);
+    for (const LogupInteraction& it : spec.interactions) {
+        require_term("logup", it.multiplicity, max_kind, trace.width, table);
+        for (const LogupTerm& tm : it.values) require_term("logup", tm, max_kind, trace.width, table);
     }
+    load_interactions(spec, s.it);
     for (int k = 0; k < 8; k++) TS_REQUIRE(challenges[k] < P, TS_ERR_INVALID, "logup: non-canonical challenge");
     const Ef gamma = ef_to_mont(Ef{{challenges[0], challenges[1], challenges[2], challenges[3]}});
     const Ef beta = ef_to_mont(Ef{{challenges[4], challenges[5], challenges[6], challenges[7]}});
@@ -431,10 +394,10 @@ std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<
         memset((void*)&j, 0, sizeof j);
         const DeviceMatrix* table = tables ? (*tables)[k] : nullptr;
         j.s = logup_dev(ctx, *specs[k], *traces[k], challenges, table, /*takes_table=*/tables != nullptr);
-        j.table = table ? (LogupGlobalConstWords)table->buf.p : nullptr;
+        j.table = table ? (GlobalConstWords)table->buf.p : nullptr;
         any_table = any_table || table;
         j.n = traces[k]->height;
-        j.trace = (LogupGlobalConstWords)traces[k]->buf.p;
+        j.trace = (GlobalConstWords)traces[k]->buf.p;
         j.index = (uint32_t)k;
         j.first_block = first[k] = (uint32_t)n_blocks;
         j.n_blocks = (uint32_t)((j.n + block_rows - 1) / block_rows);
@@ -448,17 +411,11 @@ std::vector<DeviceMatrix> logup_aux_build_multi(Context& ctx, const std::vector<
         aux[k].height = jobs[k].n;
         aux[k].width = jobs[k].s.aux_width;
         aux[k].layout = DeviceMatrix::ROW_MAJOR;
-        jobs[k].aux = (LogupGlobalWords)aux[k].buf.p;
+        jobs[k].aux = (GlobalWords)aux[k].buf.p;
     }
-    // the jobs and, behind them, the first-workgroup prefix: one upload
-    static_assert(sizeof(LogupJob) % 16 == 0, "the prefix follows the jobs, aligned");
-    std::vector<char> tab(T * sizeof(LogupJob) + (T + 1) * sizeof(uint32_t));
-    memcpy(tab.data(), (const void*)jobs.data(), T * sizeof(LogupJob));
-    memcpy(tab.data() + T * sizeof(LogupJob), first.data(), (T + 1) * sizeof(uint32_t));
-    DevBuf<Ef> d_tab(&ctx, (tab.size() + sizeof(Ef) - 1) / sizeof(Ef));
-    h2d(ctx, d_tab.p, tab.data(), tab.size());
-    const LogupJob* d_jobs = reinterpret_cast<const LogupJob*>(d_tab.p);
-    const uint32_t* d_first = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(d_tab.p) + T * sizeof(LogupJob));
+    const JobTable<LogupJob> d_tab = upload_jobs(ctx, jobs, first);
+    const LogupJob* d_jobs = d_tab.jobs;
+    const uint32_t* d_first = d_tab.first;
     DevBuf<Ef> totals(&ctx, n_blocks);
     // {flag (two words), pad, pad, S_0 .. S_{T-1}}: one copy back
     DevBuf<Ef> back(&ctx, 1 + T);

@@ -143,7 +143,7 @@ struct LogupMultBusResult {
 };
 // logup_multiplicities with the lookups on the rows of `lookers` (row-major, this context, any heights, read only;
 // one of them may be the table trace itself): same classes, sums, skipped zero weights and words on every run.  One
-// k_mult_insert launch over the table, one count launch per looker, one k_mult_write launch, one copy back.
+// k_mult_insert launch over the table, one k_mult_count launch per looker, one k_mult_write launch, one copy back.
 // Throws TS_ERR_INVALID before any device work, as the single-trace call does per matrix; out_column may be read
 // by no term over the table trace.
 // takes_pre (logup_multiplicities_bus_pre): the TABLE's terms may be of kind 2 and read `table_pre`, the row-major

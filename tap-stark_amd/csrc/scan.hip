@@ -22,7 +22,7 @@
 // Addressing: row * width is 64-bit everywhere.
 #include <string>
 
-#include "logup_hash.hpp"  // mult_knob
+#include "logup_dev.hpp"  // mult_knob
 #include "prover_internal.hpp"
 #include "scan.hpp"
 
@@ -200,10 +200,7 @@ k_scan_apply(const ScanDev d, const uint32_t* __restrict__ named, const uint32_t
 
 DeviceMatrix scan_matrix(Context& ctx, const ScanSpec& spec, const DeviceMatrix& src, uint32_t* finals) {
     StageTimer timer(&ctx, "scan");
-    TS_REQUIRE(src.buf.p && src.layout == DeviceMatrix::ROW_MAJOR && src.buf.ctx == &ctx, TS_ERR_INVALID,
-               "scan: the source must be a row-major, unconsumed matrix made on this context");
-    TS_REQUIRE(src.height >= 1 && src.height <= SCAN_MAX_HEIGHT && src.width >= 1, TS_ERR_INVALID,
-               "scan: the height of the source must be in [1, 2^27]");
+    require_resident(ctx, src, "scan", "the source");
     const ScanPlan plan = scan_check(spec, src.width);
     // TS_SCAN_BLOCK_ROWS (1 .. 1024, read on every call): the rows one workgroup owns, a test knob that makes small
     // matrices cross the wave, the workgroup and several trips of the totals loop.  The result does not depend on it.

@@ -35,7 +35,7 @@
 #include <algorithm>
 #include <string>
 
-#include "logup_hash.hpp"
+#include "logup_dev.hpp"
 #include "sort.hpp"
 
 namespace ts {
@@ -269,13 +269,6 @@ k_sort_gather(const GatherDev g, const uint32_t* __restrict__ src, const uint32_
 
 namespace {
 
-void sort_check_matrix(Context& ctx, const DeviceMatrix& m, const char* call, const char* what) {
-    TS_REQUIRE(m.buf.p && m.layout == DeviceMatrix::ROW_MAJOR && m.buf.ctx == &ctx, TS_ERR_INVALID,
-               std::string(call) + ": " + what + " must be a row-major, unconsumed matrix made on this context");
-    TS_REQUIRE(m.height >= 1 && m.height <= (1ull << 27) && m.width >= 1, TS_ERR_INVALID,
-               std::string(call) + ": the height of " + what + " must be in [1, 2^27]");
-}
-
 void launch_gather(Context& ctx, GatherDev g, const uint32_t* src, const uint32_t* index, uint32_t* out,
                    unsigned long long* back) {
     g.rows_per_block = std::min(256u, std::max(1u, 4096u / g.out_width));
@@ -308,7 +301,7 @@ DeviceMatrix sort_rows(Context& ctx, const SortSpec& spec, const DeviceMatrix& s
     StageTimer timer(&ctx, "sort rows");
     const size_t nk = spec.key_columns.size();
     TS_REQUIRE(nk >= 1 && nk <= SORT_MAX_KEYS, TS_ERR_INVALID, "sort rows: between 1 and 4 keys");
-    sort_check_matrix(ctx, src, "sort rows", "the source");
+    require_resident(ctx, src, "sort rows", "the source");
     for (size_t q = 0; q < nk; q++) {
         TS_REQUIRE(spec.key_columns[q] < src.width, TS_ERR_INVALID, "sort rows: a key column outside the source");
         for (size_t e = 0; e < q; e++)
@@ -410,8 +403,8 @@ DeviceMatrix sort_rows(Context& ctx, const SortSpec& spec, const DeviceMatrix& s
 
 DeviceMatrix gather_rows(Context& ctx, const DeviceMatrix& src, const DeviceMatrix& index, uint32_t index_column) {
     StageTimer timer(&ctx, "gather rows");
-    sort_check_matrix(ctx, src, "gather", "the source");
-    sort_check_matrix(ctx, index, "gather", "the index");
+    require_resident(ctx, src, "gather", "the source");
+    require_resident(ctx, index, "gather", "the index");
     TS_REQUIRE(index_column < index.width, TS_ERR_INVALID, "gather: index_column outside the index matrix");
     TS_REQUIRE(src.width <= SORT_MAX_WIDTH, TS_ERR_INVALID, "gather: the source is wider than 2^16 columns");
     DeviceMatrix out;
