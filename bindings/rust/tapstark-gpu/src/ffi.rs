@@ -263,6 +263,10 @@ pub struct ts_scan_column {
 pub const TS_SCAN_MAX_COLUMNS: usize = 8;
 pub const TS_SCAN_NO_RESET: u32 = 0xFFFF_FFFF;
 pub const TS_SCAN_EXCLUSIVE: u32 = 1;
+/// The limits of a `ts_matrix_collect_rows` spec.
+pub const TS_COLLECT_MAX_SOURCES: usize = 4;
+pub const TS_COLLECT_MAX_EMITTERS: usize = 16;
+pub const TS_COLLECT_MAX_WIDTH: usize = 64;
 
 /// The scans of one `ts_matrix_scan` call.  Like every declaration of this file it has not been compiled.
 #[repr(C)]
@@ -555,6 +559,18 @@ extern "C" {
     /// host only: the same scans as a sequential loop over `height` host rows of `src_width` words
     pub fn ts_scan_rows_host(spec: *const ts_scan_spec, src_row_major: *const u32, height: u64, src_width: u32,
                              out_row_major: *mut u32, out_cap_words: usize, finals: *mut u32) -> ts_status;
+    /// a new matrix of the rows that the emitters of a "TCOL" word tape select from `n_sources` resident matrices, in
+    /// (source, row, emitter) order, padded to `out_height` rows (0: the least power of two that holds them); `n_live`
+    /// receives the number of selected rows; the sources are only read.  Like every declaration of this file it has
+    /// not been compiled.
+    pub fn ts_matrix_collect_rows(ctx: *mut ts_ctx, spec: *const u32, n_words: usize, sources: *const *const ts_matrix,
+                                  out_height: u64, out: *mut *mut ts_matrix, n_live: *mut u64) -> ts_status;
+    /// host only: the checks of a collect spec that need no matrix (each output may be null)
+    pub fn ts_collect_check(spec: *const u32, n_words: usize, n_sources: *mut u32, out_width: *mut u32) -> ts_status;
+    /// host only: the same collection as a sequential loop over host rows, `heights[s]` rows for source s
+    pub fn ts_collect_rows_host(spec: *const u32, n_words: usize, src_row_major: *const *const u32, heights: *const u64,
+                                out_height: u64, out_row_major: *mut u32, out_cap_words: usize,
+                                out_height_used: *mut u64, n_live: *mut u64) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

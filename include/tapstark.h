@@ -94,6 +94,8 @@ ts_status ts_ctx_graph_stats(ts_ctx* ctx, uint64_t out[4]);
  * (twiddles, coset scales, selectors) with that word and waits for the fill, so that nothing can pass by reading
  * what an earlier use left behind; proofs are the same, only slower.  Unset or empty: off, at the cost of one
  * branch per block.  A value that is no 32-bit word makes ts_ctx_create return TS_ERR_INVALID.
+ * 11 = pool blocks handed out and not yet given back (matrices, commitments and the temporaries of a call in
+ * progress): a call that is refused leaves it where it was.  10 is not used.
  * TS_ERR_INVALID for an unknown index. */
 ts_status ts_ctx_stat(ts_ctx* ctx, int which, uint64_t* out);
 
@@ -1482,6 +1484,71 @@ ts_status ts_matrix_scan(ts_ctx* ctx, const ts_scan_spec* spec, const ts_matrix*
  * call).  A reference for tests and for callers without a device, not a fast path. */
 ts_status ts_scan_rows_host(const ts_scan_spec* spec, const uint32_t* src_row_major, uint64_t height, uint32_t src_width,
                             uint32_t* out_row_major, size_t out_cap_words, uint32_t* finals /* may be NULL */);
+
+/* ---- collected rows: the selected rows of resident traces as one table, in HBM ----
+ * Every call above keeps the height of its source and reads one matrix.  A machine's execution trace has one row per
+ * step and several access slots per row, some of them conditional; the table the sort and the scan work on has one row
+ * per ACCESS.  Getting from the one to the other is a stream compaction: select the slots, reshape each to a common
+ * tuple, stack them in execution order, pad to a power of two.  This call does that in HBM.  It replaces:
+ * ts_matrix_download, a concatenation of masked slices on the host, ts_matrix_upload.
+ * The spec is a word tape, written as the derive program is:
+ *   [0]=0x4C4F4354 ("TCOL") [1]=1 [2]=n_sources (1..4) [3]=n_emitters (1..16) [4]=out_width (1..64),
+ *   n_sources x src_width[s]          the width of source s, 1 .. 2^16
+ *   out_width x pad word              the pad row, each word < p = 0x78000001
+ *   n_emitters x {source, sel_kind, sel_value, out_width x {kind, value}}
+ * Selector: sel_kind 0 is the constant 1 (sel_value must be 1: any other constant is refused) -- the emitter fires on
+ * every row of its source; sel_kind 1 is column sel_value of the emitter's source -- the emitter fires on a row where
+ * that word, reduced mod p, is != 0.  This is the rule of the scan's reset column: 0, p and 2p do not fire, 1 and
+ * 0xFFFFFFFF do.
+ * Terms, one per output column: kind 0 a constant < p; kind 1 column `value` of the emitter's source, copied AS STORED
+ * (not reduced, like an untouched column of derive); kind 2 the index of the source row (value must be 0).
+ * Order: the output rows are the fired (source, row, emitter) triples in lexicographic order of (source index, row,
+ * emitter index in the spec): a source's rows in execution order, a row's slots in spec order, the sources stacked.
+ * The result is unique, the same on every run and for every value of the knob below.
+ * Height: *n_live is the number of triples that fired.  out_height is 0 or a power of two in [1, 2^27]; 0 means the
+ * least power of two >= max(n_live, 1).  *out is a NEW row-major matrix of that height and out_width columns; rows
+ * [n_live, height) hold the pad row.  n_live above a given out_height is TS_ERR_INVALID "collect: N rows selected,
+ * out_height H"; n_live above 2^27 is TS_ERR_INVALID too.  In both cases there is no output, *n_live is 0 and every
+ * pool block the call took is returned.
+ * Sources: n_sources handles, row-major, on ctx, neither consumed nor written, each of any height in [1, 2^27].  One
+ * handle may appear as several sources.
+ * TS_ERR_INVALID, each with a text in ts_last_error, before any device work, leaving *out NULL: a NULL argument; a
+ * wrong magic or version, or a word count that does not match the header; a count outside its range; src_width[s] that
+ * differs from the matrix's width; a source index, column, kind, constant or pad word out of range; a matrix that is
+ * not row-major, is consumed or belongs to another context; an out_height that is not 0 or a power of two in range;
+ * TS_COLLECT_BLOCK_ROWS outside its range.
+ * Launches: THREE kernels, reduce-then-scan, no workgroup waits for another.  The blocks of all sources form one job
+ * grid; a block is a run of at most min(TS_COLLECT_BLOCK_ROWS, 4096 / E_s) consecutive rows of ONE source (E_s: the
+ * emitters of that source).  (1) one workgroup per block counts what fires in it, reading the selector columns only;
+ * (2) one workgroup makes the exclusive scan of the block counts, the carry in 64 bits: where each block's rows start
+ * in the result, and the total; (3) the job grid again lists its fired (row, emitter) pairs in LDS and writes its rows,
+ * one contiguous word range per block, with coalesced stores and reads gathered inside the block's own rows; the
+ * workgroups behind the job grid in the same launch fill the pad rows.  Selectors, pad row and term table go to the
+ * device in one asynchronous copy through the context's page-locked staging arena.  Every output word is written
+ * exactly once and nothing reads the output.
+ * Waits: exactly ONE, between launches 2 and 3, for the copy back of the total (8 bytes): it sizes the result when
+ * out_height is 0 and decides the overflow refusal in every case.  Temporaries come from ctx's pool.
+ * TS_COLLECT_BLOCK_ROWS (1 .. 1024, default 1024, read on every call) caps the rows one workgroup owns: a test knob
+ * that makes small matrices cross the wave, the workgroup and several trips of launch 2's loop.  No output word depends
+ * on it.  A value so small that the job grid would pass 2^24 workgroups is refused.
+ * Out of scope: use inside batch lanes; a predicate other than one column (derive it first); any reordering (sort
+ * afterwards); removal of duplicates; more than 4 sources, 16 emitters or 64 output columns; extension-field words; a
+ * kernel specialised per spec. */
+enum { TS_COLLECT_MAX_SOURCES = 4, TS_COLLECT_MAX_EMITTERS = 16, TS_COLLECT_MAX_WIDTH = 64 };
+ts_status ts_matrix_collect_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_words,
+                                 const ts_matrix* const* sources /* n_sources */, uint64_t out_height,
+                                 ts_matrix** out, uint64_t* n_live);
+/* Host only, no context: every check above that needs no matrix; the text of a refusal is what ts_last_error returns
+ * for a NULL context.  n_sources and out_width are the header's; each may be NULL. */
+ts_status ts_collect_check(const uint32_t* spec, size_t n_words, uint32_t* n_sources, uint32_t* out_width);
+/* Host only: the same checks, then the plain sequential loop over host rows: source s is heights[s] rows (1 .. 2^27)
+ * of src_width[s] words at src_row_major[s].  out_row_major receives *out_height_used * out_width words, pad rows
+ * included (TS_ERR_BUFFER if out_cap_words is less; nothing is written then, nor by a refused call).  The height rules
+ * and the overflow refusal are those above.  A reference for tests and for callers without a device, not a fast
+ * path. */
+ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint32_t* const* src_row_major,
+                               const uint64_t* heights, uint64_t out_height, uint32_t* out_row_major,
+                               size_t out_cap_words, uint64_t* out_height_used, uint64_t* n_live);
 
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);

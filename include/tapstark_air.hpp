@@ -494,5 +494,45 @@ private:
     ts_scan_spec spec_;
 };
 
+// ---- specs for ts_matrix_collect_rows (include/tapstark.h "collected rows"): the counterpart of
+// tap-stark_amd/collect.py, word for word.  A term is Collect::constant(v) (reduced mod p here), Collect::col(c) or
+// Collect::row(); a selector is Collect::always() or Collect::col(c).  emit() appends one emitter and tape() is the
+// word tape the call takes.  Nothing is checked here; ts_collect_check is the judge.
+class Collect {
+public:
+    struct Term {
+        uint32_t kind, value;
+    };
+    static constexpr uint32_t MAGIC = 0x4C4F4354u;  // "TCOL"
+    static Term constant(uint64_t v) { return Term{0, (uint32_t)(v % P)}; }
+    static Term col(uint32_t c) { return Term{1, c}; }
+    static Term row() { return Term{2, 0}; }
+    static Term always() { return Term{0, 1}; }
+
+    // a pad row shorter than out_width is filled with zeros
+    Collect(std::vector<uint32_t> src_widths, uint32_t out_width, std::vector<uint32_t> pad = {})
+        : src_widths_(std::move(src_widths)), out_width_(out_width), pad_(std::move(pad)) {
+        pad_.resize(out_width_, 0);
+    }
+    Collect& emit(uint32_t source, Term when, const std::vector<Term>& terms) {
+        records_.insert(records_.end(), {source, when.kind, when.value});
+        for (const Term& t : terms) records_.insert(records_.end(), {t.kind, t.value});
+        n_emitters_++;
+        return *this;
+    }
+    std::vector<uint32_t> tape() const {
+        std::vector<uint32_t> t = {MAGIC, 1, (uint32_t)src_widths_.size(), n_emitters_, out_width_};
+        t.insert(t.end(), src_widths_.begin(), src_widths_.end());
+        t.insert(t.end(), pad_.begin(), pad_.end());
+        t.insert(t.end(), records_.begin(), records_.end());
+        return t;
+    }
+
+private:
+    std::vector<uint32_t> src_widths_;
+    uint32_t out_width_, n_emitters_ = 0;
+    std::vector<uint32_t> pad_, records_;
+};
+
 }  // namespace air
 }  // namespace ts

@@ -1210,6 +1210,93 @@ def generate_memory_table(accesses: np.ndarray) -> np.ndarray:
     return fill_memory_gaps(t)
 
 
+class MemoryCpuAir(BaseAir):
+    """A machine's side of the memory bus: one row per step, two access slots per row, each conditional.  Main columns
+    (clk, ts_a, addr_a, val_a, sel_a, ts_b, addr_b, val_b, wr_b, sel_b): first row ``clk = 0``, ``next.clk = clk + 1``,
+    ``ts_a = 2 clk``, ``ts_b = 2 clk + 1``, ``sel_a``, ``sel_b`` and ``wr_b`` boolean.  Slot a is a read: the row sends
+    (MEM_TAG, addr_a, ts_a, val_a, 0) with multiplicity ``sel_a``; slot b a read or a write: (MEM_TAG, addr_b, ts_b,
+    val_b, wr_b) with multiplicity ``sel_b``.  The receiving MemoryTableAir trace is made from this one in HBM:
+    ``collect_rows`` with ``memory_cpu_collect_spec`` stacks the selected slots as an access table, and from there the
+    route of the access table is taken unchanged.  Constraint degree 3."""
+
+    CLK, TS_A, ADDR_A, VAL_A, SEL_A, TS_B, ADDR_B, VAL_B, WR_B, SEL_B = range(10)
+    WIDTH = 10
+    logup = LogUp([(("col", 4), [("const", MEM_TAG), ("col", 2), ("col", 1), ("col", 3), ("const", 0)]),
+                   (("col", 9), [("const", MEM_TAG), ("col", 6), ("col", 5), ("col", 7), ("col", 8)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return self.WIDTH
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        for c in (self.SEL_A, self.SEL_B, self.WR_B):
+            builder.assert_zero(local[c] * (local[c] - 1))
+        builder.when_first_row().assert_zero(local[self.CLK])
+        builder.when_transition().assert_eq(nxt[self.CLK], local[self.CLK] + 1)
+        builder.assert_eq(local[self.TS_A], local[self.CLK] * 2)
+        builder.assert_eq(local[self.TS_B], local[self.CLK] * 2 + 1)
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+def generate_memory_cpu_trace(n: int, n_addr: int, seed: int = SPLITMIX_SEED) -> np.ndarray:
+    """(n, 10) canonical u32 satisfying MemoryCpuAir: a simulated memory over ``n_addr`` addresses driven by a
+    SplitMix64 stream.  On row r slot b comes after slot a (``ts_b = ts_a + 1``).  Slot a is a read of an address that
+    has been written, selected on some rows only (never before the first write); slot b is a read or a write, selected
+    on some rows only, and the first access of every address is a write, as in ``generate_memory_accesses``.  An
+    unselected slot holds an address and a value all the same: they are not sent."""
+    A = MemoryCpuAir
+    r = splitmix64_stream(seed, 6 * n).reshape(n, 6).astype(np.uint64)
+    out = np.zeros((n, A.WIDTH), dtype=np.uint32)
+    out[:, A.CLK] = np.arange(n)
+    out[:, A.TS_A] = 2 * np.arange(n)
+    out[:, A.TS_B] = 2 * np.arange(n) + 1
+    memory = {}
+    for i in range(n):
+        addr_a = int(r[i, 0] % np.uint64(n_addr))
+        sel_a = bool((int(r[i, 1]) >> 17) & 1) and addr_a in memory
+        out[i, A.ADDR_A], out[i, A.SEL_A] = addr_a, sel_a
+        out[i, A.VAL_A] = memory[addr_a] if sel_a else int(r[i, 1] % np.uint64(P))
+        addr_b = int(r[i, 2] % np.uint64(n_addr))
+        sel_b = bool((int(r[i, 3]) >> 17) & 3)  # three rows of four
+        write = bool((int(r[i, 4]) >> 17) & 1) or addr_b not in memory
+        value = int(r[i, 5] % np.uint64(P)) if write else memory[addr_b]
+        if write and sel_b:
+            memory[addr_b] = value
+        out[i, A.ADDR_B], out[i, A.VAL_B], out[i, A.WR_B], out[i, A.SEL_B] = addr_b, value, write, sel_b
+    return out
+
+
+def memory_cpu_collect_spec():
+    """The access table of a MemoryCpuAir trace as a spec for ``collect_rows``: slot a and slot b of every row, where
+    selected, in the (addr, clk, value, is_write, sel) shape of MemoryAccessAir with ``clk`` = the slot's timestamp and
+    ``sel = 1``; the pad row is all zero, so it is a dead row of the memory table.  ``n_live`` from the call is what the
+    sort takes."""
+    from .collect import CollectSpec, col
+    A = MemoryCpuAir
+    spec = CollectSpec([A.WIDTH], 5)
+    spec.emit(0, when=col(A.SEL_A), terms=[col(A.ADDR_A), col(A.TS_A), col(A.VAL_A), 0, 1])
+    spec.emit(0, when=col(A.SEL_B), terms=[col(A.ADDR_B), col(A.TS_B), col(A.VAL_B), col(A.WR_B), 1])
+    return spec
+
+
+def memory_cpu_table(ctx, cpu_trace, out_height: int = 0):
+    """The MemoryTableAir trace of a resident MemoryCpuAir trace, without leaving HBM: collect the selected slots, then
+    the route of an access table unchanged -- unfilled source columns, the sort with ``n_live`` from the collect, the
+    helper columns, the fill scan, the gaps.  Returns (the collected access matrix, the table, n_live)."""
+    from .stark import collect_rows
+    T = MemoryTableAir
+    d_acc, n_live = collect_rows(ctx, memory_cpu_collect_spec(), [cpu_trace], out_height)
+    d_sorted = d_acc.derive(memory_table_unfilled_source_program()).sort_rows([T.ADDR, T.CLK], group_keys=1,
+                                                                              n_live=n_live, group_start=True)
+    d_table = d_sorted.derive(memory_fill_helper_program()).scan(memory_fill_scan()).derive(memory_gap_program())
+    return d_acc, d_table, n_live
+
+
 def fill_memory_range_multiplicities(range_trace, memory_table, allow_missing: bool = False):
     """Fills column 1 of a resident BusRangeAir trace in HBM from the ``gap`` column of a resident MemoryTableAir trace
     (weight ``live``).  Returns what ``logup_multiplicities_bus`` returns."""

@@ -14,6 +14,7 @@
 
 #include "abi_types.hpp"
 #include "blake3.hpp"
+#include "collect.hpp"
 #include "derive.hpp"
 #include "jit.hpp"
 #include "logup.hpp"
@@ -557,6 +558,7 @@ ts_status ts_ctx_stat(ts_ctx* ctx, int which, uint64_t* out) {
     case 7: *out = ctx->ctx.pow_hints_rejected; break;
     case 8: *out = ctx->ctx.pow_host_grinds; break;
     case 9: *out = ctx->ctx.poison_fills; break;
+    case 11: *out = ctx->ctx.live_blocks.size(); break;  // (10 stays unknown)
     default: return TS_ERR_INVALID;
     }
     return TS_OK;
@@ -2027,6 +2029,65 @@ ts_status ts_scan_rows_host(const ts_scan_spec* spec, const uint32_t* src_row_ma
         TS_REQUIRE((uint64_t)out_cap_words >= height * plan.out_width, ts::TS_ERR_BUFFER,
                    "ts_scan_rows_host: the output buffer holds fewer than height * out_width words");
         ts::scan_rows_host(s, plan, src_row_major, height, out_row_major, finals);
+    });
+}
+
+// Collected rows: the selected rows of up to four resident matrices as one new matrix (collect.hip), the checks and the
+// sequential loop over host rows (collect.cpp).
+ts_status ts_matrix_collect_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_words, const ts_matrix* const* sources,
+                                 uint64_t out_height, ts_matrix** out, uint64_t* n_live) {
+    if (out) *out = nullptr;
+    if (n_live) *n_live = 0;
+    if (!ctx) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(spec && sources && out && n_live, ts::TS_ERR_INVALID, "ts_matrix_collect_rows: null argument");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        const ts::CollectPlan plan = ts::collect_check(spec, n_words);  // (and so how many handles `sources` holds)
+        const ts::DeviceMatrix* mats[ts::COLLECT_MAX_SOURCES] = {};
+        for (uint32_t s = 0; s < plan.n_sources; s++) {
+            TS_REQUIRE(sources[s], ts::TS_ERR_INVALID, "ts_matrix_collect_rows: null argument");
+            mats[s] = &sources[s]->m;
+        }
+        uint64_t live = 0;
+        *out = new_matrix(ts::collect_matrix(ctx->ctx, plan, mats, out_height, &live));
+        *n_live = live;
+    });
+}
+
+ts_status ts_collect_check(const uint32_t* spec, size_t n_words, uint32_t* n_sources, uint32_t* out_width) {
+    if (n_sources) *n_sources = 0;
+    if (out_width) *out_width = 0;
+    return guard(nullptr, [&] {
+        const ts::CollectPlan plan = ts::collect_check(spec, n_words);
+        if (n_sources) *n_sources = plan.n_sources;
+        if (out_width) *out_width = plan.out_width;
+    });
+}
+
+ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint32_t* const* src_row_major,
+                               const uint64_t* heights, uint64_t out_height, uint32_t* out_row_major,
+                               size_t out_cap_words, uint64_t* out_height_used, uint64_t* n_live) {
+    if (out_height_used) *out_height_used = 0;
+    if (n_live) *n_live = 0;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(spec && src_row_major && heights && out_row_major && out_height_used && n_live, ts::TS_ERR_INVALID,
+                   "ts_collect_rows_host: null argument");
+        const ts::CollectPlan plan = ts::collect_check(spec, n_words);
+        for (uint32_t s = 0; s < plan.n_sources; s++) {
+            TS_REQUIRE(src_row_major[s], ts::TS_ERR_INVALID, "ts_collect_rows_host: null argument");
+            TS_REQUIRE(heights[s] >= 1 && heights[s] <= ts::COLLECT_MAX_HEIGHT, ts::TS_ERR_INVALID,
+                       "collect: the height of source " + std::to_string(s) + " must be in [1, 2^27]");
+        }
+        ts::collect_check_out_height(out_height);
+        const uint64_t live = ts::collect_count_host(plan, src_row_major, heights);
+        const uint64_t height = ts::collect_height(live, out_height);
+        TS_REQUIRE((uint64_t)out_cap_words >= height * plan.out_width, ts::TS_ERR_BUFFER,
+                   "ts_collect_rows_host: the output buffer holds fewer than height * out_width words");
+        ts::collect_rows_host(plan, src_row_major, heights, height, out_row_major);
+        *out_height_used = height;
+        *n_live = live;
     });
 }
 

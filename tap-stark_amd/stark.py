@@ -111,7 +111,8 @@ class Context:
     def stat(self, which: int) -> int:
         """``ts_ctx_stat``: 3 pool bytes, 5 local-quotient fall-backs, 6-8 proof-of-work witness counters,
         9 device blocks filled with the test pattern of ``TS_POOL_POISON`` (0 when it was unset at creation);
-        0, 1, 2 and 4 (the retired graph replay's counters) are always 0."""
+        11 pool blocks handed out and not yet given back; 0, 1, 2 and 4 (the retired graph replay's counters) are
+        always 0; 10 is not used."""
         v = C.c_uint64()
         self.check(self._l.ts_ctx_stat(self.h, which, C.byref(v)))
         return int(v.value)
@@ -408,6 +409,19 @@ class DeviceMatrix:
                 self.ctx._l.ts_matrix_free(self.ctx.h, self.h)
         except Exception:
             pass
+
+
+def collect_rows(ctx: Context, spec, sources, out_height: int = 0):
+    """The pair (a new matrix, n_live): the rows the emitters of ``spec`` (a ``collect.CollectSpec`` or its tape) select
+    from the resident matrices ``sources``, in (source, row, emitter) order, padded to ``out_height`` rows or to the
+    least power of two that holds them (``ts_matrix_collect_rows``).  The sources are only read.  One host wait."""
+    from .collect import _tape
+    t = _tape(spec)
+    sources = list(sources)
+    handles = (C.c_void_p * max(len(sources), 4))(*[m.h for m in sources])
+    h, live = C.c_void_p(), C.c_uint64()
+    ctx.check(ctx._l.ts_matrix_collect_rows(ctx.h, _p(t), len(t), handles, out_height, C.byref(h), C.byref(live)))
+    return DeviceMatrix(ctx, h), int(live.value)
 
 
 class Radix2Dft:
