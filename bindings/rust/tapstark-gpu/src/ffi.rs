@@ -267,6 +267,30 @@ pub const TS_SCAN_EXCLUSIVE: u32 = 1;
 pub const TS_COLLECT_MAX_SOURCES: usize = 4;
 pub const TS_COLLECT_MAX_EMITTERS: usize = 16;
 pub const TS_COLLECT_MAX_WIDTH: usize = 64;
+/// The limits and the flags of a `ts_matrix_join_rows` spec.
+pub const TS_JOIN_MAX_KEYS: usize = 8;
+pub const TS_JOIN_MAX_FETCH: usize = 32;
+pub const TS_JOIN_TABLE_ROW: u32 = 1;
+pub const TS_JOIN_HIT: u32 = 2;
+pub const TS_JOIN_KEEP: u32 = 4;
+
+/// The keyed fetch of one `ts_matrix_join_rows` call: the arrays are the caller's and are read during the call only.
+/// Like every declaration of this file it has not been compiled.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ts_join_spec {
+    pub struct_size: u32, // = size_of::<ts_join_spec>()
+    pub n_keys: u32,
+    pub src_keys: *const ts_logup_term,
+    pub table_keys: *const ts_logup_term,
+    pub when: ts_logup_term,
+    pub n_fetch: u32,
+    pub table_columns: *const u32,
+    pub dst_columns: *const u32,
+    pub defaults: *const u32,
+    pub flags: u32,
+    pub table_rows: u64,
+}
 
 /// The scans of one `ts_matrix_scan` call.  Like every declaration of this file it has not been compiled.
 #[repr(C)]
@@ -571,6 +595,19 @@ extern "C" {
     pub fn ts_collect_rows_host(spec: *const u32, n_words: usize, src_row_major: *const *const u32, heights: *const u64,
                                 out_height: u64, out_row_major: *mut u32, out_cap_words: usize,
                                 out_height_used: *mut u64, n_live: *mut u64) -> ts_status;
+    /// a new matrix of `src`'s height: `src` with columns of the `table` row that carries the same key tuple fetched
+    /// into its rows; `n_missing` (null: a miss is an error) and `first_missing` report the rows that take part and
+    /// find no table row; `src` and `table` (which may be one handle) are only read.  Like every declaration of this
+    /// file it has not been compiled.
+    pub fn ts_matrix_join_rows(ctx: *mut ts_ctx, spec: *const ts_join_spec, src: *const ts_matrix,
+                               table: *const ts_matrix, out: *mut *mut ts_matrix, n_missing: *mut u64,
+                               first_missing: *mut u64) -> ts_status;
+    /// host only: the checks of a join spec that need no matrix but the two widths (`out_width` may be null)
+    pub fn ts_join_check(spec: *const ts_join_spec, src_width: u32, table_width: u32, out_width: *mut u32) -> ts_status;
+    /// host only: the same join as a sequential loop over host rows
+    pub fn ts_join_rows_host(spec: *const ts_join_spec, src: *const u32, src_height: u64, src_width: u32,
+                             table: *const u32, table_height: u64, table_width: u32, out: *mut u32, out_words: u64,
+                             n_missing: *mut u64, first_missing: *mut u64) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

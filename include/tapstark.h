@@ -1550,6 +1550,83 @@ ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint3
                                const uint64_t* heights, uint64_t out_height, uint32_t* out_row_major,
                                size_t out_cap_words, uint64_t* out_height_used, uint64_t* n_live);
 
+/* ---- joined rows: columns of another table, fetched by key, in HBM ----
+ * Every call above reads the rows of its own sources.  A column whose value is DEFINED BY ANOTHER TABLE -- the
+ * instruction a machine row fetched from a program ROM (pc -> opcode, operands), the flags an opcode decodes to, an
+ * S-box entry given by its key tuple, a value read from a snapshot keyed by (segment, address) -- is a keyed fetch: for
+ * every row of `src` find the row of `table` with the same key tuple and write chosen columns of that row into the
+ * source's row.  This call does that in HBM.  It replaces: ts_matrix_download, a dictionary or sort-and-search join on
+ * the host, ts_matrix_upload.
+ * Keys: n_keys (1 .. 8) terms on each side, ts_logup_term of kind 0 (a canonical constant) or 1 (a column of the
+ * side's own row); kind 2 is refused.  Matching is the rule of ts_logup_multiplicities: key words are compared AS
+ * STORED, with no reduction (p + 1 does not match 1).  Only the table's rows [0, table_rows) are entered (0 = all of
+ * them: a padded table gives the number of its real rows).  Entered rows with equal tuples form a class; the class's
+ * LOWEST row is the match.  The result is the same words on every run and for every value of the knob below.
+ * Taking part: `when` is a term on src's row; the row takes part iff the word, reduced mod p, is != 0 -- the selector
+ * rule of ts_matrix_collect_rows: 0, p and 2p do not fire, 1 and 0xFFFFFFFF do.  The constant 1 is "every row".
+ * What a row receives: for f < n_fetch, a matched row gets table[match][table_columns[f]], as stored, in column
+ * dst_columns[f]; a row that takes no part, or that finds no match, gets defaults[f] (canonical).  With TS_JOIN_KEEP
+ * such a row instead keeps src's own word where the dst column lies inside src (a dst column behind src still gets its
+ * default): several joins can be chained, each filling the rows its `when` selects.
+ * Misses: a miss is a row that takes part and finds no table row.  *n_missing counts them, *first_missing is the least
+ * such source row (~0 when there is none); the status is TS_OK and the result is complete.  With n_missing == NULL any
+ * miss is TS_ERR_INVARIANT with the row in the last error; *out is NULL then and every pool block the call took is
+ * returned.  first_missing may be NULL in either case.
+ * Shape of the result, as ts_matrix_derive: *out is a NEW row-major matrix of src's height.  Its width is
+ * max(src_width, 1 + max dst_columns), then one more column for TS_JOIN_TABLE_ROW (the matched row's index, 0 without
+ * a match) and one more for TS_JOIN_HIT (1 on a matched row, 0 elsewhere), in that order.  Every column at or beyond
+ * src's width must be named by dst_columns; no dst column appears twice; every other column is copied as stored.  All
+ * reads see src, so a dst column may overwrite a key column or the `when` column.  src and table may be the same
+ * handle; neither is consumed or written.
+ * TS_ERR_INVALID, each with a text in ts_last_error, before any device work, leaving *out NULL: a NULL argument; a
+ * wrong struct_size; n_keys outside 1 .. 8 or n_fetch outside 0 .. 32; n_fetch == 0 with neither TS_JOIN_TABLE_ROW nor
+ * TS_JOIN_HIT; an unknown flag; a term kind above 1; a column outside its matrix; a non-canonical constant or default;
+ * a dst column named twice or a column behind src that is not named; table_rows above the table's height; a result
+ * wider than 2^16; a height outside [1, 2^27]; a matrix that is not row-major, is consumed or is from another context;
+ * TS_LOGUP_HASH_BITS outside its range.
+ * Launches: TWO kernels (csrc/join.hip) behind the fills of the slot table and of the report, no workgroup waits for
+ * another.  (1) insert, the protocol of the multiplicity fill: one table row per lane, atomicCAS / atomicMin on a slot
+ * table of the power of two at or above 2 * table_rows; (2) fetch: a workgroup owns 256 source rows; one lane per row
+ * evaluates `when`, builds the tuple, probes and leaves the matched row in LDS (the misses of a wave are one add); then
+ * all lanes write the block's rows as one contiguous word range with coalesced stores, choosing per word the source
+ * word, a table word through the LDS match, or a default.  Every result word is written exactly once.
+ * Waits: exactly ONE, after launch 2, for the copy back of the miss report (32 bytes).  Temporaries come from ctx's
+ * pool.  TS_LOGUP_HASH_BITS (0 .. 32, read on every call) lengthens the probe chains here too and changes no output.
+ * A full slot table cannot happen and is TS_ERR_INVARIANT "internal error", as in the multiplicity calls.
+ * Out of scope: a table index kept between calls (a handle built once for a ROM and probed by many traces); more than
+ * one match per row; preprocessed-kind (kind 2) terms -- pass ts_multi_key_values(key, i) as the table instead;
+ * extension-field words; use inside batch lanes. */
+#define TS_JOIN_MAX_KEYS   8u      /* = the LogUp tuple width */
+#define TS_JOIN_MAX_FETCH  32u
+#define TS_JOIN_TABLE_ROW  1u      /* append the matched table row's index (0 on a row without a match) */
+#define TS_JOIN_HIT        2u      /* append 1 on a matched row, 0 elsewhere */
+#define TS_JOIN_KEEP       4u      /* a row without a match keeps src's word in a dst column inside src */
+typedef struct {
+    uint32_t struct_size;             /* = sizeof(ts_join_spec), else TS_ERR_INVALID */
+    uint32_t n_keys;                  /* 1 .. 8 */
+    const ts_logup_term* src_keys;    /* n_keys terms on src's row: kind 0 constant, 1 column */
+    const ts_logup_term* table_keys;  /* n_keys terms on the table's row, same kinds */
+    ts_logup_term when;               /* src's row takes part iff this word mod p != 0; constant 1 = every row */
+    uint32_t n_fetch;                 /* 0 .. 32 */
+    const uint32_t* table_columns;    /* n_fetch columns of the table ... */
+    const uint32_t* dst_columns;      /* ... written to these columns of the result */
+    const uint32_t* defaults;         /* n_fetch canonical words for rows without a match */
+    uint32_t flags;
+    uint64_t table_rows;              /* only rows [0, table_rows) of the table are entered; 0 = all */
+} ts_join_spec;
+ts_status ts_matrix_join_rows(ts_ctx* ctx, const ts_join_spec* spec, const ts_matrix* src, const ts_matrix* table,
+                              ts_matrix** out, uint64_t* n_missing, uint64_t* first_missing);
+/* Host only, no context: every check above that needs no matrix but the two widths; the text of a refusal is what
+ * ts_last_error returns for a NULL context.  out_width (may be NULL) is the width of the result. */
+ts_status ts_join_check(const ts_join_spec* spec, uint32_t src_width, uint32_t table_width, uint32_t* out_width);
+/* Host only: the same checks, then the plain sequential loop: src is src_height rows of src_width words, table is
+ * table_height rows of table_width words, both row-major; they may be one buffer.  out receives src_height * out_width
+ * words (TS_ERR_BUFFER if out_words is less; nothing is written then, nor by a refused call, nor by a miss with
+ * n_missing == NULL).  A reference for tests and for callers without a device, not a fast path. */
+ts_status ts_join_rows_host(const ts_join_spec* spec, const uint32_t* src, uint64_t src_height, uint32_t src_width,
+                            const uint32_t* table, uint64_t table_height, uint32_t table_width, uint32_t* out,
+                            uint64_t out_words, uint64_t* n_missing, uint64_t* first_missing);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

@@ -534,5 +534,46 @@ private:
     std::vector<uint32_t> pad_, records_;
 };
 
+// ---- specs for ts_matrix_join_rows (include/tapstark.h "joined rows"): the counterpart of tap-stark_amd/join.py.  It
+// owns the arrays a ts_join_spec points to: spec() is valid until the next call of a builder method and as long as the
+// Join lives.  A key term is Join::constant(v) (reduced mod p here) or Join::col(c).  Nothing is checked here;
+// ts_join_check is the judge.
+class Join {
+public:
+    static ts_logup_term constant(uint64_t v) { return ts_logup_term{0, (uint32_t)(v % P)}; }
+    static ts_logup_term col(uint32_t c) { return ts_logup_term{1, c}; }
+
+    explicit Join(uint32_t flags = 0, uint64_t table_rows = 0) : flags_(flags), table_rows_(table_rows) {}
+    Join& key(ts_logup_term on_src, ts_logup_term on_table) {
+        src_keys_.push_back(on_src);
+        table_keys_.push_back(on_table);
+        return *this;
+    }
+    Join& when(ts_logup_term t) {
+        when_ = t;
+        return *this;
+    }
+    Join& fetch(uint32_t table_column, uint32_t dst_column, uint32_t default_word = 0) {
+        table_columns_.push_back(table_column);
+        dst_columns_.push_back(dst_column);
+        defaults_.push_back(default_word);
+        return *this;
+    }
+    const ts_join_spec* spec() {
+        spec_ = ts_join_spec{(uint32_t)sizeof(ts_join_spec), (uint32_t)src_keys_.size(), src_keys_.data(),
+                             table_keys_.data(), when_, (uint32_t)table_columns_.size(), table_columns_.data(),
+                             dst_columns_.data(), defaults_.data(), flags_, table_rows_};
+        return &spec_;
+    }
+
+private:
+    uint32_t flags_;
+    uint64_t table_rows_;
+    ts_logup_term when_ = {0, 1};
+    std::vector<ts_logup_term> src_keys_, table_keys_;
+    std::vector<uint32_t> table_columns_, dst_columns_, defaults_;
+    ts_join_spec spec_ = {};
+};
+
 }  // namespace air
 }  // namespace ts

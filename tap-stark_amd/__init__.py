@@ -16,3 +16,4 @@ from .derive import DeriveBuilder, derive_check, derive_rows_host  # noqa: F401
 from .scan import ScanSpec, carry_last, running_product, running_sum, scan_rows_host  # noqa: F401
 from .collect import CollectSpec, collect_check, collect_rows_host  # noqa: F401
 from .stark import collect_rows  # noqa: F401
+from .join import JoinSpec, join_check, join_rows_host  # noqa: F401

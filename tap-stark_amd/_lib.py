@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "ts_matrix_derive", "ts_derive_check", "ts_derive_rows_host",
     "ts_matrix_scan", "ts_scan_rows_host",
     "ts_matrix_collect_rows", "ts_collect_check", "ts_collect_rows_host",
+    "ts_matrix_join_rows", "ts_join_check", "ts_join_rows_host",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -215,6 +216,14 @@ class ScanSpecC(C.Structure):
     """``ts_scan_spec`` (struct_size first)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_columns", C.c_uint32), ("columns", ScanColumnC * 8),
                 ("out_width", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class JoinSpecC(C.Structure):
+    """``ts_join_spec`` (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_keys", C.c_uint32), ("src_keys", C.POINTER(LogupTermC)),
+                ("table_keys", C.POINTER(LogupTermC)), ("when", LogupTermC), ("n_fetch", C.c_uint32),
+                ("table_columns", C.POINTER(C.c_uint32)), ("dst_columns", C.POINTER(C.c_uint32)),
+                ("defaults", C.POINTER(C.c_uint32)), ("flags", C.c_uint32), ("table_rows", C.c_uint64)]
 
 
 class BatchLookupItemC(C.Structure):
@@ -472,6 +481,10 @@ def lib() -> C.CDLL:
         l.ts_collect_check.argtypes = [u32p, C.c_size_t, u32p, u32p]
         l.ts_collect_rows_host.argtypes = [u32p, C.c_size_t, C.POINTER(u32p), u64p, C.c_uint64, u32p, C.c_size_t, u64p,
                                            u64p]
+        l.ts_matrix_join_rows.argtypes = [C.c_void_p, C.POINTER(JoinSpecC), C.c_void_p, C.c_void_p, voidpp, u64p, u64p]
+        l.ts_join_check.argtypes = [C.POINTER(JoinSpecC), C.c_uint32, C.c_uint32, u32p]
+        l.ts_join_rows_host.argtypes = [C.POINTER(JoinSpecC), u32p, C.c_uint64, C.c_uint32, u32p, C.c_uint64, C.c_uint32,
+                                        u32p, C.c_uint64, u64p, u64p]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

@@ -1304,3 +1304,48 @@ def fill_memory_range_multiplicities(range_trace, memory_table, allow_missing: b
     A = MemoryTableAir
     return logup_multiplicities_bus(range_trace, [("col", 0)], [(memory_table, [[("col", A.GAP)]], [("col", A.LIVE)])],
                                     out_column=1, negate=1, allow_missing=allow_missing)
+
+
+# ---------------------------------------------------------------------------------------------- a program ROM on the bus
+# A machine trace whose rows fetch instructions from a fixed program: BusTupleSendAir(ROM_TAG, k, 3) senders of
+# (pc, opcode, arg) against a BusKeyTableAir(ROM_TAG, 3) whose contents are a matrix of the key.  The producer knows
+# ``pc`` and ``sel``; opcode and arg are DEFINED BY THE ROM and are fetched in HBM with ``DeviceMatrix.join_rows``.
+ROM_TAG = 13
+
+
+def generate_rom_key(n: int, seed: int = SPLITMIX_SEED) -> np.ndarray:
+    """(n, 3) canonical u32, the key matrix of a ``BusKeyTableAir(ROM_TAG, 3)``: rows (pc, opcode, arg) with distinct,
+    sparse ``pc`` values in no order (so a row number is no key), opcode < 64, arg < p."""
+    r = splitmix64_stream(seed, 4 * n).reshape(n, 4).astype(np.uint64)
+    order = np.argsort(r[:, 0], kind="stable").astype(np.uint64)
+    out = np.empty((n, 3), dtype=np.uint32)
+    out[:, 0] = np.uint64(16) * order + r[:, 1] % np.uint64(16) + np.uint64(4096)
+    out[:, 1] = r[:, 2] % np.uint64(64)
+    out[:, 2] = r[:, 3] % np.uint64(P)
+    return out
+
+
+def generate_rom_fetch_trace(n: int, k: int, key: np.ndarray, seed: int = SPLITMIX_SEED, unfilled: bool = False) -> np.ndarray:
+    """(n, 4k) canonical u32 satisfying ``BusTupleSendAir(ROM_TAG, k, 3)``: slot i of a row holds (pc, opcode, arg, sel)
+    with ``pc`` a ROM row's; a selected slot carries that row's opcode and arg, an unselected one zeros.  ``unfilled``:
+    opcode and arg are 0 everywhere -- what a producer has before the fetch; ``rom_join_spec`` fills them."""
+    key = np.asarray(key, dtype=np.uint32)
+    r = splitmix64_stream(seed, 2 * n * k).reshape(n, k, 2).astype(np.uint64)
+    rows = (r[:, :, 0] % np.uint64(key.shape[0])).astype(np.int64)
+    sel = ((r[:, :, 1] >> np.uint64(17)) & np.uint64(1)).astype(np.uint32)
+    out = np.zeros((n, k, 4), dtype=np.uint32)
+    out[:, :, 0] = key[rows, 0]
+    out[:, :, 3] = sel
+    if not unfilled:
+        out[:, :, 1] = key[rows, 1] * sel
+        out[:, :, 2] = key[rows, 2] * sel
+    return np.ascontiguousarray(out.reshape(n, 4 * k))
+
+
+def rom_join_spec(k: int):
+    """The fetch of an unfilled ``generate_rom_fetch_trace`` as ``k`` specs for ``DeviceMatrix.join_rows``, one per
+    slot, to be chained (each keeps what the others wrote: ``KEEP``): slot i's ``pc`` against column 0 of the ROM's key
+    matrix (``MultiKey.values``), on the rows its ``sel`` selects; opcode and arg into the slot."""
+    from .join import KEEP, JoinSpec, col
+    return [JoinSpec(keys=[(col(4 * i), col(0))], when=col(4 * i + 3), fetch=[(1, 4 * i + 1, 0), (2, 4 * i + 2, 0)],
+                     flags=KEEP) for i in range(k)]

@@ -17,6 +17,7 @@
 #include "collect.hpp"
 #include "derive.hpp"
 #include "jit.hpp"
+#include "join.hpp"
 #include "logup.hpp"
 #include "prover_internal.hpp"
 #include "scan.hpp"
@@ -2088,6 +2089,81 @@ ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint3
         ts::collect_rows_host(plan, src_row_major, heights, height, out_row_major);
         *out_height_used = height;
         *n_live = live;
+    });
+}
+
+// Joined rows: columns of the table row with the same key, fetched into a copy of the source (join.hip), the checks and
+// the sequential loop over host rows (join.cpp).
+namespace {
+static_assert(sizeof(ts::JoinTerm) == sizeof(ts_logup_term), "JoinTerm is ts_logup_term");
+ts::JoinPlan load_join(const ts_join_spec* spec, uint32_t src_width, uint32_t table_width) {
+    TS_REQUIRE(spec, ts::TS_ERR_INVALID, "join: null spec");
+    const bool size_ok = spec->struct_size == sizeof(ts_join_spec);
+    ts::JoinSpecIn in = {};
+    in.size_ok = size_ok;
+    if (size_ok) {  // (the fields of another struct are not read)
+        in.n_keys = spec->n_keys;
+        in.src_keys = reinterpret_cast<const ts::JoinTerm*>(spec->src_keys);
+        in.table_keys = reinterpret_cast<const ts::JoinTerm*>(spec->table_keys);
+        in.when = ts::JoinTerm{spec->when.kind, spec->when.value};
+        in.n_fetch = spec->n_fetch;
+        in.table_columns = spec->table_columns;
+        in.dst_columns = spec->dst_columns;
+        in.defaults = spec->defaults;
+        in.flags = spec->flags;
+        in.table_rows = spec->table_rows;
+    }
+    return ts::join_check(in, src_width, table_width);
+}
+}  // namespace
+
+ts_status ts_matrix_join_rows(ts_ctx* ctx, const ts_join_spec* spec, const ts_matrix* src, const ts_matrix* table,
+                              ts_matrix** out, uint64_t* n_missing, uint64_t* first_missing) {
+    if (out) *out = nullptr;
+    if (n_missing) *n_missing = 0;
+    if (first_missing) *first_missing = ~0ull;
+    if (!ctx) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(spec && src && table && out, ts::TS_ERR_INVALID, "ts_matrix_join_rows: null argument");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        ts::require_resident(ctx->ctx, src->m, "join", "the source");  // (a consumed matrix has no width to check against)
+        ts::require_resident(ctx->ctx, table->m, "join", "the table");
+        const ts::JoinPlan plan = load_join(spec, src->m.width, table->m.width);
+        uint64_t n = 0, first = ~0ull;
+        *out = new_matrix(ts::join_matrix(ctx->ctx, plan, src->m, table->m, n_missing == nullptr, &n, &first));
+        if (n_missing) *n_missing = n;
+        if (first_missing) *first_missing = first;
+    });
+}
+
+ts_status ts_join_check(const ts_join_spec* spec, uint32_t src_width, uint32_t table_width, uint32_t* out_width) {
+    if (out_width) *out_width = 0;
+    return guard(nullptr, [&] {
+        const ts::JoinPlan plan = load_join(spec, src_width, table_width);
+        if (out_width) *out_width = plan.out_width;
+    });
+}
+
+ts_status ts_join_rows_host(const ts_join_spec* spec, const uint32_t* src, uint64_t src_height, uint32_t src_width,
+                            const uint32_t* table, uint64_t table_height, uint32_t table_width, uint32_t* out,
+                            uint64_t out_words, uint64_t* n_missing, uint64_t* first_missing) {
+    if (n_missing) *n_missing = 0;
+    if (first_missing) *first_missing = ~0ull;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(spec && src && table && out, ts::TS_ERR_INVALID, "ts_join_rows_host: null argument");
+        const ts::JoinPlan plan = load_join(spec, src_width, table_width);
+        const uint64_t n_table = ts::join_table_rows(plan, src_height, table_height);
+        TS_REQUIRE(out_words >= src_height * plan.out_width, ts::TS_ERR_BUFFER,
+                   "ts_join_rows_host: the output buffer holds fewer than height * out_width words");
+        std::vector<uint32_t> match;
+        uint64_t first = ~0ull;
+        const uint64_t n = ts::join_match_host(plan, src, src_height, table, n_table, match, &first);
+        if (!n_missing && n) throw ts::Error(ts::TS_ERR_INVARIANT, ts::join_miss_text(n, first));
+        ts::join_rows_host(plan, src, src_height, table, match, out);
+        if (n_missing) *n_missing = n;
+        if (first_missing) *first_missing = first;
     });
 }
 

@@ -396,6 +396,19 @@ class DeviceMatrix:
         out = DeviceMatrix(self.ctx, h)
         return (out, last[:len(spec.columns)].copy()) if finals else out
 
+    def join_rows(self, table: "DeviceMatrix", spec, allow_missing: bool = False):
+        """The triple (a new matrix, n_missing, first_missing): this matrix with columns of ``table`` fetched by key
+        into its rows as ``spec`` (a ``join.JoinSpec``) says (``ts_matrix_join_rows``).  A miss is a row that takes part
+        and finds its key in no table row: ``first_missing`` is the least such row or None; without ``allow_missing``
+        any miss raises ``TsError``.  This matrix and ``table`` (which may be this matrix) are only read.  One host
+        wait."""
+        s, _keep = spec.c_spec()
+        h, n, first = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        self.ctx.check(self.ctx._l.ts_matrix_join_rows(self.ctx.h, C.byref(s), self.h, table.h, C.byref(h),
+                                                       C.byref(n) if allow_missing else None, C.byref(first)))
+        first_missing = None if first.value == 0xFFFFFFFFFFFFFFFF else int(first.value)
+        return DeviceMatrix(self.ctx, h), int(n.value), first_missing
+
     def device_ptr(self) -> int:
         """Row-major device pointer (``ts_matrix_device_ptr``): valid until the matrix is freed or consumed,
         ordered on the context's stream; ``from_device_ptr`` is the opposite direction."""
