@@ -608,6 +608,18 @@ extern "C" {
     pub fn ts_join_rows_host(spec: *const ts_join_spec, src: *const u32, src_height: u64, src_width: u32,
                              table: *const u32, table_height: u64, table_width: u32, out: *mut u32, out_words: u64,
                              n_missing: *mut u64, first_missing: *mut u64) -> ts_status;
+    /// a new matrix: every row of `src` repeated by the count the "TEXP" word tape `spec` reads from it, in (row,
+    /// inner index) order, padded to `out_height` rows (0: the least power of two that holds them); `src` is only
+    /// read.  A row over the spec's max_count is TS_ERR_INVARIANT, a total over the height TS_ERR_INVALID.  Like every
+    /// declaration of this file it has not been compiled.
+    pub fn ts_matrix_expand_rows(ctx: *mut ts_ctx, spec: *const u32, n_words: usize, src: *const ts_matrix,
+                                 out_height: u64, out: *mut *mut ts_matrix, n_live: *mut u64) -> ts_status;
+    /// host only: the checks of an expand spec that need no matrix (each output may be null)
+    pub fn ts_expand_check(spec: *const u32, n_words: usize, src_width: *mut u32, out_width: *mut u32) -> ts_status;
+    /// host only: the same expansion as a sequential loop over `height` host rows
+    pub fn ts_expand_rows_host(spec: *const u32, n_words: usize, src_row_major: *const u32, height: u64,
+                               out_height: u64, out_row_major: *mut u32, out_cap_words: usize,
+                               out_height_used: *mut u64, n_live: *mut u64) -> ts_status;
     /// ts_prove_batch's lanes for AIRs with a key, aux columns or both: per item the work of ts_prove_pre_aux
     pub fn ts_prove_batch_lookup(ctxs: *const *mut ts_ctx, airs: *const *const ts_air, lanes: *const ts_batch_lane,
                                  n_lanes: u32, cfg: *const ts_fri_config, items: *mut ts_batch_lookup_item,

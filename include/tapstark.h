@@ -1627,6 +1627,82 @@ ts_status ts_join_rows_host(const ts_join_spec* spec, const uint32_t* src, uint6
                             const uint32_t* table, uint64_t table_height, uint32_t table_width, uint32_t* out,
                             uint64_t out_words, uint64_t* n_missing, uint64_t* first_missing);
 
+/* ---- expanded rows: a data-dependent number of rows per source row, in HBM ----
+ * The collect selects rows: its output has at most 16 rows per source row, each written out in the spec.  A table with
+ * a DATA-DEPENDENT number of rows per source row -- the elements of a block instruction (memcpy or memset of `len`
+ * words, load or store multiple), the R rounds of a precompile call, the `cycles` rows a chip spends on an instruction,
+ * a run-length-encoded trace unrolled -- is the inverse: a load-balanced expansion.  This call does that in HBM.  It
+ * replaces: ts_matrix_download, a repeat of every row by its count and an index ramp on the host, ts_matrix_upload.
+ * The spec is a word tape, written as the collect's is:
+ *   [0]=0x50584554 ("TEXP") [1]=1 [2]=src_width (1..2^16) [3]=out_width (1..64)
+ *   [4]=sel_kind [5]=sel_value        0/1: every row (the collect's rule: the value must be 1);
+ *                                     1/c: column c, the row takes part iff the word, reduced mod p, is != 0
+ *   [6]=count_kind [7]=count_value    0/c: the constant c, 1 <= c <= max_count (0 is refused);
+ *                                     1/c: column c
+ *   [8]=max_count                     1 .. 2^27
+ *   out_width x pad word              the pad row, each word < p = 0x78000001
+ *   out_width x {kind, value, step}   one term per output column
+ * Count: a row that takes part asks for cnt = its count word reduced mod p (p asks for 0 rows, p + 3 for 3), or the
+ * constant; a row that takes no part asks for 0.  cnt = 0 is allowed and emits nothing.  cnt > max_count on a row that
+ * takes part is a data error (below).
+ * Terms, for output row (source row r, inner index j, 0 <= j < cnt):
+ *   kind 0  a constant `value` < p
+ *   kind 1  column `value` of row r, copied AS STORED (not reduced, like the collect's kind 1)
+ *   kind 2  the row index r
+ *   kind 3  the inner index j
+ *   kind 4  what remains, cnt - 1 - j
+ *   kind 5  1 if j == 0, else 0
+ *   kind 6  1 if j == cnt - 1, else 0
+ *   kind 7  the stepped word (word mod p + j * step) mod p, canonical, over column `value`, with `step` < p: the
+ *           address of element j of a span
+ * `step` must be 0 for every kind but 7; `value` must be 0 for kinds 2 to 6.
+ * Order: the output rows are the (r, j) pairs in lexicographic order.  The result is unique, the same on every run and
+ * for every value of the knob below.
+ * Height: *n_live is the sum of all cnt.  out_height is 0 or a power of two in [1, 2^27]; 0 means the least power of
+ * two >= max(n_live, 1).  *out is a NEW row-major matrix of that height and out_width columns; rows [n_live, height)
+ * hold the pad row.  src is neither consumed nor written.
+ * TS_ERR_INVALID, each with a text in ts_last_error, before any device work, leaving *out NULL: a NULL argument; a
+ * wrong magic or version, or a word count that does not match the header; a width, max_count, selector, count, column,
+ * kind, constant, pad word, step or value word that breaks a rule above; src_width that differs from the matrix's
+ * width; a matrix that is not row-major, is consumed or belongs to another context; a height outside [1, 2^27]; an
+ * out_height that is not 0 or a power of two in range; TS_EXPAND_BLOCK_ROWS outside its range.
+ * Refused after the one wait, in this order when both hold; there is no output then, *n_live is 0, *out is NULL and
+ * every pool block the call took is returned:
+ *   1. TS_ERR_INVARIANT "expand: row R asks for C rows, max_count M": R is the LEAST row over max_count, C its count;
+ *   2. TS_ERR_INVALID "expand: N rows asked for, out_height H" (H = 2^27 when out_height is 0).  N is exact for any
+ *      input, up to 2^27 rows of 2^27 each: every sum that feeds it is 64-bit.
+ * Launches: THREE kernels (csrc/expand.hip), reduce-then-scan, no workgroup waits for another.  (1) one workgroup per
+ * block of at most TS_EXPAND_BLOCK_ROWS source rows reads the selector and count columns only and leaves every row's
+ * position inside its block, the block's sum and the block's least row over max_count; (2) one workgroup makes the
+ * exclusive scan of the block sums, the carry in 64 bits, and leaves the total and the least offending row with its
+ * count behind them; (3) the grid is partitioned by OUTPUT rows: a workgroup owns a tile of consecutive output rows,
+ * finds the source row of each by binary search (the largest row whose offset is at or below it, so rows asking for
+ * nothing lose), and writes the tile as one contiguous word range with coalesced stores and reads gathered in the
+ * source rows; the workgroups behind the tiles in the same launch fill the pad rows.  One row asking for 2^22 rows
+ * costs what 2^22 rows asking for one do.  Pad row and term table go to the device in one asynchronous copy through the
+ * context's page-locked staging arena.  Every output word is written exactly once and nothing reads the output.
+ * Waits: exactly ONE, between launches 2 and 3, for the copy back of the total, the least offending row and its count
+ * (24 bytes).  Temporaries come from ctx's pool: 4 bytes per source row and 16 per block.
+ * TS_EXPAND_BLOCK_ROWS (1 .. 1024, default 1024, read on every call) caps the source rows of a block of launch 1 and
+ * the output rows of a tile of launch 3: a test knob that makes small matrices cross the lane, the wave, the workgroup,
+ * several trips of launch 2's loop and tiles that straddle blocks.  No output word depends on it.  A value so small
+ * that a grid would pass 2^24 workgroups is refused (for launch 3 this is known only after the wait).
+ * Out of scope: several sources, or several output forms per element (stack with the collect or sort afterwards); use
+ * inside batch lanes; extension-field words; a kernel specialised per spec. */
+enum { TS_EXPAND_MAX_WIDTH = 64, TS_EXPAND_MAX_COUNT = 1 << 27 };
+ts_status ts_matrix_expand_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_words, const ts_matrix* src,
+                                uint64_t out_height, ts_matrix** out, uint64_t* n_live);
+/* Host only, no context: every check above that needs no matrix; the text of a refusal is what ts_last_error returns
+ * for a NULL context.  src_width and out_width are the header's; each may be NULL. */
+ts_status ts_expand_check(const uint32_t* spec, size_t n_words, uint32_t* src_width, uint32_t* out_width);
+/* Host only: the same checks, then the plain sequential loop over `height` (1 .. 2^27) host rows of src_width words.
+ * out_row_major receives *out_height_used * out_width words, pad rows included (TS_ERR_BUFFER if out_cap_words is less;
+ * nothing is written then, nor by a refused call).  The height rules and the two late refusals are those above.  A
+ * reference for tests and for callers without a device, not a fast path. */
+ts_status ts_expand_rows_host(const uint32_t* spec, size_t n_words, const uint32_t* src_row_major, uint64_t height,
+                              uint64_t out_height, uint32_t* out_row_major, size_t out_cap_words,
+                              uint64_t* out_height_used, uint64_t* n_live);
+
 /* library/ABI version (bumped on any incompatible change) */
 uint32_t ts_abi_version(void);
 

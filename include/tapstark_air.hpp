@@ -534,6 +534,60 @@ private:
     std::vector<uint32_t> pad_, records_;
 };
 
+// ---- specs for ts_matrix_expand_rows (include/tapstark.h "expanded rows"): the counterpart of
+// tap-stark_amd/expand.py, word for word.  A term is Expand::constant(v) (reduced mod p here), Expand::col(c),
+// Expand::row(), Expand::inner(), Expand::remaining(), Expand::first(), Expand::last() or Expand::stepped(c, step);
+// count() and when() take Expand::col(c), count() also Expand::times(n).  tape() is the word tape the call takes.
+// Nothing is checked here; ts_expand_check is the judge.
+class Expand {
+public:
+    struct Term {
+        uint32_t kind, value, step;
+    };
+    static constexpr uint32_t MAGIC = 0x50584554u;  // "TEXP"
+    static Term constant(uint64_t v) { return Term{0, (uint32_t)(v % P), 0}; }
+    static Term col(uint32_t c) { return Term{1, c, 0}; }
+    static Term row() { return Term{2, 0, 0}; }
+    static Term inner() { return Term{3, 0, 0}; }
+    static Term remaining() { return Term{4, 0, 0}; }
+    static Term first() { return Term{5, 0, 0}; }
+    static Term last() { return Term{6, 0, 0}; }
+    static Term stepped(uint32_t c, uint64_t step = 1) { return Term{7, c, (uint32_t)(step % P)}; }
+    static Term times(uint32_t n) { return Term{0, n, 0}; }  // a constant count
+    static Term always() { return Term{0, 1, 0}; }
+
+    // a pad row shorter than out_width is filled with zeros
+    Expand(uint32_t src_width, uint32_t out_width, uint32_t max_count, std::vector<uint32_t> pad = {})
+        : src_width_(src_width), out_width_(out_width), max_count_(max_count), pad_(std::move(pad)) {
+        pad_.resize(out_width_, 0);
+    }
+    Expand& count(Term t) {
+        count_ = t;
+        return *this;
+    }
+    Expand& when(Term t) {
+        when_ = t;
+        return *this;
+    }
+    Expand& terms(const std::vector<Term>& terms) {
+        terms_ = terms;
+        return *this;
+    }
+    std::vector<uint32_t> tape() const {
+        std::vector<uint32_t> t = {MAGIC, 1, src_width_, out_width_, when_.kind, when_.value, count_.kind, count_.value,
+                                   max_count_};
+        t.insert(t.end(), pad_.begin(), pad_.end());
+        for (const Term& x : terms_) t.insert(t.end(), {x.kind, x.value, x.step});
+        return t;
+    }
+
+private:
+    uint32_t src_width_, out_width_, max_count_;
+    Term when_ = {0, 1, 0}, count_ = {0, 1, 0};
+    std::vector<uint32_t> pad_;
+    std::vector<Term> terms_;
+};
+
 // ---- specs for ts_matrix_join_rows (include/tapstark.h "joined rows"): the counterpart of tap-stark_amd/join.py.  It
 // owns the arrays a ts_join_spec points to: spec() is valid until the next call of a builder method and as long as the
 // Join lives.  A key term is Join::constant(v) (reduced mod p here) or Join::col(c).  Nothing is checked here;

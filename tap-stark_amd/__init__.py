@@ -17,3 +17,5 @@ from .scan import ScanSpec, carry_last, running_product, running_sum, scan_rows_
 from .collect import CollectSpec, collect_check, collect_rows_host  # noqa: F401
 from .stark import collect_rows  # noqa: F401
 from .join import JoinSpec, join_check, join_rows_host  # noqa: F401
+from .expand import ExpandSpec, expand_check, expand_rows_host  # noqa: F401
+from .stark import expand_rows  # noqa: F401

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "ts_matrix_scan", "ts_scan_rows_host",
     "ts_matrix_collect_rows", "ts_collect_check", "ts_collect_rows_host",
     "ts_matrix_join_rows", "ts_join_check", "ts_join_rows_host",
+    "ts_matrix_expand_rows", "ts_expand_check", "ts_expand_rows_host",
     "ts_proof_to_postcard", "ts_proof_from_postcard", "ts_proof_from_postcard_v",
     "ts_rccl_available", "ts_rccl_unique_id", "ts_comm_rccl_create", "ts_comm_rccl_destroy",
     "ts_comm_rccl_info",
@@ -485,6 +486,9 @@ def lib() -> C.CDLL:
         l.ts_join_check.argtypes = [C.POINTER(JoinSpecC), C.c_uint32, C.c_uint32, u32p]
         l.ts_join_rows_host.argtypes = [C.POINTER(JoinSpecC), u32p, C.c_uint64, C.c_uint32, u32p, C.c_uint64, C.c_uint32,
                                         u32p, C.c_uint64, u64p, u64p]
+        l.ts_matrix_expand_rows.argtypes = [C.c_void_p, u32p, C.c_size_t, C.c_void_p, C.c_uint64, voidpp, u64p]
+        l.ts_expand_check.argtypes = [u32p, C.c_size_t, u32p, u32p]
+        l.ts_expand_rows_host.argtypes = [u32p, C.c_size_t, u32p, C.c_uint64, C.c_uint64, u32p, C.c_size_t, u64p, u64p]
         l.ts_dft_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, voidpp]
         l.ts_coset_lde_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, voidpp]
         l.ts_matrix_bit_reverse_rows.argtypes = [C.c_void_p, C.c_void_p, voidpp]

@@ -1349,3 +1349,161 @@ def rom_join_spec(k: int):
     from .join import KEEP, JoinSpec, col
     return [JoinSpec(keys=[(col(4 * i), col(0))], when=col(4 * i + 3), fetch=[(1, 4 * i + 1, 0), (2, 4 * i + 2, 0)],
                      flags=KEEP) for i in range(k)]
+
+
+# ---------------------------------------------------------------------------------------------- spans on the bus
+# A block instruction (memcpy or memset of ``len`` words, load or store multiple) is one row of the machine and ``len``
+# rows of its chip: a table with a data-dependent number of rows per source row.  The chip's trace is made from the
+# machine's in HBM with ``expand_rows``; the bus ties the two and a BusRangeAir takes every address of every span.
+SPAN_TAG = 17
+
+
+class SpanCallAir(BaseAir):
+    """The machine's side of the span bus: one row per step.  Main columns (id, base, len, sel): first row ``id = 0``,
+    ``next.id = id + 1``, ``sel`` boolean; the row sends (SPAN_TAG, id, base, len) with multiplicity ``sel``.  The
+    receiving SpanChipAir trace is made from this one in HBM by ``span_chip_table``.  Constraint degree 3."""
+
+    ID, BASE, LEN, SEL = range(4)
+    WIDTH = 4
+    logup = LogUp([(("col", 3), [("const", SPAN_TAG), ("col", 0), ("col", 1), ("col", 2)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return self.WIDTH
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        sel = local[self.SEL]
+        builder.assert_zero(sel * (sel - 1))
+        builder.when_first_row().assert_zero(local[self.ID])
+        builder.when_transition().assert_eq(nxt[self.ID], local[self.ID] + 1)
+        # implied by the first line; constraint degree 3, as every bus AIR (see BusSendAir)
+        builder.assert_zero(local[self.BASE] * sel * (sel - 1))
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+class SpanChipAir(BaseAir):
+    """The chip of the span bus: one row per element of every selected span, the live rows first.  Main columns (id,
+    base, len, j, first, last, live, addr, recv).  With ``cont' = next.live - next.first``:
+
+    * ``first``, ``last``, ``live`` boolean; ``first (1 - live) = 0``; ``last (1 - live) = 0``; ``recv + first = 0``;
+      first row ``live - first = 0``;
+    * ``first j = 0``; ``last (len - 1 - j) = 0``; ``addr = base + j``;
+    * on transitions: dead rows stay dead, ``(1 - live) next.live = 0``; a continued span keeps its call,
+      ``cont' (next.id - id) = 0`` and the same for ``base`` and ``len``, and counts on, ``cont' (next.j - j - 1) = 0``;
+      nothing continues a finished span, ``last cont' = 0``; an unfinished one is continued,
+      ``live (1 - last) (1 - cont') = 0``;
+    * last row ``live (1 - last) = 0``.
+
+    The row receives (SPAN_TAG, id, base, len) with multiplicity ``recv`` -- once per span, on its first element -- and
+    sends (BUS_TAG, addr) with multiplicity ``live`` to a BusRangeAir, so every address of every span lies in the range
+    table.  Constraint degree 3.  It is a demonstrator of the route -- a chip whose trace ``expand_rows`` makes in HBM
+    -- not a vetted chip."""
+
+    ID, BASE, LEN, J, FIRST, LAST, LIVE, ADDR, RECV = range(9)
+    WIDTH = 9
+    logup = LogUp([(("col", 8), [("const", SPAN_TAG), ("col", 0), ("col", 1), ("col", 2)]),
+                   (("col", 6), [("const", BUS_TAG), ("col", 7)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return self.WIDTH
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        first, last, live, j = local[self.FIRST], local[self.LAST], local[self.LIVE], local[self.J]
+        cont_next = nxt[self.LIVE] - nxt[self.FIRST]
+        for b in (first, last, live):
+            builder.assert_zero(b * (b - 1))
+        builder.assert_zero(first * (1 - live))
+        builder.assert_zero(last * (1 - live))
+        builder.assert_zero(local[self.RECV] + first)
+        builder.when_first_row().assert_zero(live - first)
+        builder.assert_zero(first * j)
+        builder.assert_zero(last * (local[self.LEN] - 1 - j))
+        builder.assert_eq(local[self.ADDR], local[self.BASE] + j)
+        t = builder.when_transition()
+        t.assert_zero((1 - live) * nxt[self.LIVE])
+        for c in (self.ID, self.BASE, self.LEN):
+            t.assert_zero(cont_next * (nxt[c] - local[c]))
+        t.assert_zero(cont_next * (nxt[self.J] - j - 1))
+        t.assert_zero(last * cont_next)
+        t.assert_zero(live * (1 - last) * (1 - cont_next))
+        builder.when_last_row().assert_zero(live * (1 - last))
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+def generate_span_call_trace(n: int, max_len: int, table_height: int, seed: int = SPLITMIX_SEED) -> np.ndarray:
+    """(n, 4) canonical u32 satisfying SpanCallAir, driven by a SplitMix64 stream: about half of the rows selected; a
+    selected row has 1 <= len <= max_len and base + len <= table_height.  An unselected row holds a base and a length
+    all the same: they are not sent and its span is not expanded."""
+    assert 1 <= max_len <= table_height
+    r = splitmix64_stream(seed, 3 * n).reshape(n, 3).astype(np.uint64)
+    out = np.zeros((n, 4), dtype=np.uint32)
+    out[:, 0] = np.arange(n)
+    length = r[:, 0] % np.uint64(max_len) + np.uint64(1)
+    out[:, 2] = length
+    out[:, 1] = r[:, 1] % (np.uint64(table_height + 1) - length)
+    out[:, 3] = (r[:, 2] >> np.uint64(17)) & np.uint64(1)
+    return out
+
+
+def span_expand_spec(max_len: int):
+    """The element table of a SpanCallAir trace as a spec for ``expand_rows``, ONE call: a selected row asks for ``len``
+    rows (id, base, len, j, first, last, live = 1, addr = base + j); the pad row is all zero, so it is a dead row of the
+    chip."""
+    from .expand import FIRST, J, LAST, ExpandSpec, col, stepped
+    A = SpanCallAir
+    return ExpandSpec(A.WIDTH, 8, count=col(A.LEN), when=col(A.SEL), max_count=max_len,
+                      terms=[col(A.ID), col(A.BASE), col(A.LEN), J, FIRST, LAST, 1, stepped(A.BASE, 1)])
+
+
+def span_chip_table(ctx, call_trace, out_height: int = 0, max_len: int = 1 << 27):
+    """The SpanChipAir trace of a resident SpanCallAir trace, without leaving HBM: the expansion, then one ``derive``
+    that appends ``recv = 0 - first``.  A selected row longer than ``max_len`` is refused and named.  Returns (the
+    table, n_live)."""
+    from .derive import DeriveBuilder
+    from .stark import expand_rows
+    d_rows, n_live = expand_rows(ctx, span_expand_spec(max_len), call_trace, out_height)
+    b = DeriveBuilder(8)
+    b.output(-b.col(SpanChipAir.FIRST), SpanChipAir.RECV)
+    return d_rows.derive(b), n_live
+
+
+def generate_span_chip_trace(call_trace: np.ndarray, out_height: int = 0) -> np.ndarray:
+    """``span_chip_table`` on the host with numpy, for the comparison: (height, 9) canonical u32 satisfying
+    SpanChipAir, padded with dead rows to ``out_height`` or to the least power of two that holds the elements."""
+    A, T = SpanCallAir, SpanChipAir
+    calls = np.asarray(call_trace, dtype=np.uint32)
+    calls = calls[calls[:, A.SEL] == 1].astype(np.int64)
+    cnt = calls[:, A.LEN]
+    n_live = int(cnt.sum())
+    height = out_height or 1 << max(n_live - 1, 0).bit_length()
+    assert n_live <= height
+    out = np.zeros((height, T.WIDTH), dtype=np.int64)
+    live = out[:n_live]
+    live[:, :3] = np.repeat(calls[:, [A.ID, A.BASE, A.LEN]], cnt, axis=0)
+    live[:, T.J] = np.arange(n_live) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    live[:, T.FIRST] = live[:, T.J] == 0
+    live[:, T.LAST] = live[:, T.J] == live[:, T.LEN] - 1
+    live[:, T.LIVE] = 1
+    live[:, T.ADDR] = (live[:, T.BASE] + live[:, T.J]) % P
+    live[:, T.RECV] = (P - live[:, T.FIRST]) % P
+    return out.astype(np.uint32)
+
+
+def fill_span_range_multiplicities(range_trace, chip_table, allow_missing: bool = False):
+    """Fills column 1 of a resident BusRangeAir trace in HBM from the ``addr`` column of a resident SpanChipAir trace
+    (weight ``live``).  Returns what ``logup_multiplicities_bus`` returns."""
+    from .air import logup_multiplicities_bus
+    A = SpanChipAir
+    return logup_multiplicities_bus(range_trace, [("col", 0)], [(chip_table, [[("col", A.ADDR)]], [("col", A.LIVE)])],
+                                    out_column=1, negate=1, allow_missing=allow_missing)

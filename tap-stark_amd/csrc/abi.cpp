@@ -15,6 +15,7 @@
 #include "abi_types.hpp"
 #include "blake3.hpp"
 #include "collect.hpp"
+#include "expand.hpp"
 #include "derive.hpp"
 #include "jit.hpp"
 #include "join.hpp"
@@ -2089,6 +2090,57 @@ ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint3
         ts::collect_rows_host(plan, src_row_major, heights, height, out_row_major);
         *out_height_used = height;
         *n_live = live;
+    });
+}
+
+// Expanded rows: every row of a resident matrix repeated by its own count as one new matrix (expand.hip), the checks and
+// the sequential loop over host rows (expand.cpp).
+ts_status ts_matrix_expand_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_words, const ts_matrix* src,
+                                uint64_t out_height, ts_matrix** out, uint64_t* n_live) {
+    if (out) *out = nullptr;
+    if (n_live) *n_live = 0;
+    if (!ctx) return TS_ERR_INVALID;
+    const ts_status refused = guard(ctx, [&] {
+        TS_REQUIRE(spec && src && out && n_live, ts::TS_ERR_INVALID, "ts_matrix_expand_rows: null argument");
+    }, false);
+    if (refused) return refused;
+    return guard(ctx, [&] {
+        const ts::ExpandPlan plan = ts::expand_check(spec, n_words);
+        uint64_t live = 0;
+        *out = new_matrix(ts::expand_matrix(ctx->ctx, plan, src->m, out_height, &live));
+        *n_live = live;
+    });
+}
+
+ts_status ts_expand_check(const uint32_t* spec, size_t n_words, uint32_t* src_width, uint32_t* out_width) {
+    if (src_width) *src_width = 0;
+    if (out_width) *out_width = 0;
+    return guard(nullptr, [&] {
+        const ts::ExpandPlan plan = ts::expand_check(spec, n_words);
+        if (src_width) *src_width = plan.src_width;
+        if (out_width) *out_width = plan.out_width;
+    });
+}
+
+ts_status ts_expand_rows_host(const uint32_t* spec, size_t n_words, const uint32_t* src_row_major, uint64_t height,
+                              uint64_t out_height, uint32_t* out_row_major, size_t out_cap_words,
+                              uint64_t* out_height_used, uint64_t* n_live) {
+    if (out_height_used) *out_height_used = 0;
+    if (n_live) *n_live = 0;
+    return guard(nullptr, [&] {
+        TS_REQUIRE(spec && src_row_major && out_row_major && out_height_used && n_live, ts::TS_ERR_INVALID,
+                   "ts_expand_rows_host: null argument");
+        const ts::ExpandPlan plan = ts::expand_check(spec, n_words);
+        TS_REQUIRE(height >= 1 && height <= ts::EXPAND_MAX_HEIGHT, ts::TS_ERR_INVALID,
+                   "expand: the height of the source must be in [1, 2^27]");
+        ts::expand_check_out_height(out_height);
+        const ts::ExpandTotals totals = ts::expand_count_host(plan, src_row_major, height);
+        const uint64_t used = ts::expand_height(plan, totals, out_height);
+        TS_REQUIRE((uint64_t)out_cap_words >= used * plan.out_width, ts::TS_ERR_BUFFER,
+                   "ts_expand_rows_host: the output buffer holds fewer than height * out_width words");
+        ts::expand_rows_host(plan, src_row_major, height, used, out_row_major);
+        *out_height_used = used;
+        *n_live = totals.total;
     });
 }
 

@@ -409,6 +409,10 @@ class DeviceMatrix:
         first_missing = None if first.value == 0xFFFFFFFFFFFFFFFF else int(first.value)
         return DeviceMatrix(self.ctx, h), int(n.value), first_missing
 
+    def expand_rows(self, spec, out_height: int = 0):
+        """``expand_rows(self.ctx, spec, self, out_height)``."""
+        return expand_rows(self.ctx, spec, self, out_height)
+
     def device_ptr(self) -> int:
         """Row-major device pointer (``ts_matrix_device_ptr``): valid until the matrix is freed or consumed,
         ordered on the context's stream; ``from_device_ptr`` is the opposite direction."""
@@ -434,6 +438,17 @@ def collect_rows(ctx: Context, spec, sources, out_height: int = 0):
     handles = (C.c_void_p * max(len(sources), 4))(*[m.h for m in sources])
     h, live = C.c_void_p(), C.c_uint64()
     ctx.check(ctx._l.ts_matrix_collect_rows(ctx.h, _p(t), len(t), handles, out_height, C.byref(h), C.byref(live)))
+    return DeviceMatrix(ctx, h), int(live.value)
+
+
+def expand_rows(ctx: Context, spec, src: DeviceMatrix, out_height: int = 0):
+    """The pair (a new matrix, n_live): every row of the resident matrix ``src`` repeated by the count ``spec`` (an
+    ``expand.ExpandSpec`` or its tape) reads from it, in (row, inner index) order, padded to ``out_height`` rows or to
+    the least power of two that holds them (``ts_matrix_expand_rows``).  ``src`` is only read.  One host wait."""
+    from .expand import _tape
+    t = _tape(spec)
+    h, live = C.c_void_p(), C.c_uint64()
+    ctx.check(ctx._l.ts_matrix_expand_rows(ctx.h, _p(t), len(t), src.h, out_height, C.byref(h), C.byref(live)))
     return DeviceMatrix(ctx, h), int(live.value)
 
 
