@@ -252,22 +252,21 @@ void Context::ensure_twiddles(unsigned log_size) {
     launch_build_twiddles(*this, d_twiddle_fwd, d_twiddle_inv, log_size);
 }
 
-void Context::ensure_plant_twiddles(unsigned log_size) {
-    if (log_size <= plant_log && d_plant_fwd) return;
-    TS_REQUIRE(log_size <= 27, TS_ERR_INVALID, "two-adicity of BabyBear is 27");
-    sync();
-    if (d_plant_fwd) (void)hipFree(d_plant_fwd);
-    if (d_plant_inv) (void)hipFree(d_plant_inv);
-    d_plant_fwd = d_plant_inv = nullptr;
-    const size_t n = (size_t)1 << log_size;
-    TS_HIP(hipMalloc((void**)&d_plant_fwd, n * 8));
-    TS_HIP(hipMalloc((void**)&d_plant_inv, n * 8));
-    if (poison_on) {
-        poison(d_plant_fwd, n * 8);
-        poison(d_plant_inv, n * 8);
-    }
-    plant_log = log_size;
-    launch_build_plant_twiddles(*this, d_plant_fwd, d_plant_inv, log_size);
+void Context::ensure_plant_twiddles(unsigned log_fwd, unsigned log_inv) {
+    auto grow = [&](uint2*& d, unsigned& have, unsigned want, bool inverse) {
+        if (want <= have && d) return;
+        TS_REQUIRE(want <= 27, TS_ERR_INVALID, "two-adicity of BabyBear is 27");
+        sync();
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        const size_t n = (size_t)1 << want;
+        TS_HIP(hipMalloc((void**)&d, n * 8));
+        if (poison_on) poison(d, n * 8);
+        have = want;
+        launch_build_plant_twiddles(*this, d, want, inverse);
+    };
+    if (log_fwd) grow(d_plant_fwd, plant_fwd_log, log_fwd, false);
+    if (log_inv) grow(d_plant_inv, plant_inv_log, log_inv, true);
 }
 
 }  // namespace ts

@@ -76,16 +76,17 @@ struct Context {
     uint32_t* d_twiddle_inv = nullptr;
     unsigned twiddle_log = 0;
     // the same twiddles as Plantard words {low, high} (bb.hpp plant_const), for the NTT passes alone
-    // (ntt_rounds.hpp): sized by the longest TRANSFORM asked for (log_n, not log_N -- the Montgomery tables
-    // above also serve the selectors, the FRI fold and the openings over the whole LDE domain)
+    // (ntt_rounds.hpp), each direction with a size of its own: the inverse table by the longest TRANSFORM asked
+    // for (log_n), the forward one by the longest LDE (log_n + log_blowup: the forward passes of coset beta
+    // take block beta's stages of the N-point transform, ntt_lde.hip) -- 8 MB and 32 MB at 2^20 x blowup 4
     uint2* d_plant_fwd = nullptr;
     uint2* d_plant_inv = nullptr;
-    unsigned plant_log = 0;
+    unsigned plant_fwd_log = 0, plant_inv_log = 0;
 
-    // coset scale tables of the LDE (ntt_lde.hip): T[beta][k] = s_beta^k / n for one (log_n,
-    // log_blowup, shift); a trace commit asks for the same one every proof, so a few are kept
+    // scale tables of the LDE (ntt_lde.hip): T[k] = shift^k / n for one (log_n, shift); a trace commit
+    // asks for the same one every proof, so a few are kept
     struct ScaleTable {
-        unsigned log_n, log_blowup;
+        unsigned log_n;
         uint32_t shift;
         uint32_t* d;
         size_t words;
@@ -181,7 +182,14 @@ struct Context {
     void d2h_point(void* host_dst, const void* dev_src, size_t bytes);  // an async copy + sync
     void* pinned(size_t bytes);
     void ensure_twiddles(unsigned log_size);
-    void ensure_plant_twiddles(unsigned log_size);  // a transform of 2^log_size points
+    // forward table for 2^log_fwd points, inverse for 2^log_inv; 0 = that direction is not asked for
+    void ensure_plant_twiddles(unsigned log_fwd, unsigned log_inv);
+    // what a prover asks for once, before its first launch, so that no table is rebuilt between two launches
+    // of a proof: the Montgomery tables and the Plantard forward table over the whole LDE domain
+    void ensure_lde_twiddles(unsigned log_N) {
+        ensure_twiddles(log_N);
+        ensure_plant_twiddles(log_N, 0);
+    }
     // (polling hipStreamQuery instead was measured and made no difference: profiles/r06_sync_spin_ab.txt)
     void sync() { TS_HIP(hipStreamSynchronize(stream)); }
 };

@@ -18,15 +18,18 @@ struct ColMat {
 
 // ---- ntt.hip, ntt_lde.hip --------------------------------------------------------------------
 void launch_build_twiddles(Context& ctx, uint32_t* W, uint32_t* Winv, unsigned log_size);
-// the same table in Plantard form: WP[m + i] = plant_const(w_{2m}^bitrev(i)) as {low, high}
-void launch_build_plant_twiddles(Context& ctx, uint2* WP, uint2* WPinv, unsigned log_size);
+// the same table in Plantard form, one direction: WP[m + i] = plant_const(w_{2m}^(+-bitrev(i))) as {low, high}
+void launch_build_plant_twiddles(Context& ctx, uint2* WP, unsigned log_size, bool inverse);
 // per-coset scale tables: lo[beta][j] = s_beta^j * scale (j < 1024), hi[beta][j] = s_beta^(1024 j)
 void launch_build_shift_tables(Context& ctx, uint32_t* lo, uint32_t* hi, uint32_t n_hi,
                                uint32_t n_cosets, uint32_t shift_mont, unsigned log_N,
                                unsigned log_blowup, uint32_t scale_mont);
-// T[beta][k] = s_beta^k / n (Montgomery), s_beta = shift * w_N^bitrev_b(beta), k < n: the factor the
-// LDE applies to coefficient k before the forward transform of coset beta.  Cached per context.
-const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, unsigned log_blowup, uint32_t shift);
+// T[k] = shift^k / n (Montgomery), k < n: the factor the LDE applies to coefficient k, once, before the
+// forward transforms of its cosets (the coset's own part, w_N^(bitrev_b(beta) k), is in the N-point twiddles
+// those transforms take: ntt_lde.hip).  Cached per context.  nullptr for shift 1: the factor is the constant
+// lde_inv_n_mont(log_n), which coset_lde hands its kernel as a value.
+const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, uint32_t shift);
+inline uint32_t lde_inv_n_mont(unsigned log_n) { return to_mont(inv_canon((uint32_t)((1ull << log_n) % P))); }
 // src: row-major n x w (natural rows)  ->  dst: column-major, rows in bit-reversed order
 // src_width (0 = w): the row length of `src` when only w of its columns (starting at `src`) are taken
 void launch_transpose_bitrev(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_n,
@@ -70,9 +73,9 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
 constexpr uint32_t LDE_NO_OWN = 0xffffffffu;
 int lde_own_coset_used(unsigned log_n, unsigned log_blowup, uint32_t shift);
 
-// The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles for log_n must be there, the Montgomery
-// tables and the Plantard ones: Context::ensure_twiddles and ensure_plant_twiddles).  Each refuses
-// what the plan cannot run with the caller's wording (`lde`).
+// The pass launchers of both (ntt_plan.hpp decides the shapes; twiddles must be there, the Montgomery tables and
+// the Plantard ones: Context::ensure_twiddles and ensure_plant_twiddles -- for log_n, and in the forward
+// direction for log_n + log_blowup).  Each refuses what the plan cannot run with the caller's wording (`lde`).
 inline void ntt_require_shape(const NttPlan& p, uint32_t ncols, uint64_t stride_a, uint64_t stride_b, bool lde) {
     if (const char* why = ntt_plan_refusal(p, ncols, stride_a, stride_b, lde)) throw Error(TS_ERR_INVALID, why);
 }
@@ -83,10 +86,12 @@ void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint6
                            bool first_round_done = false, uint32_t* data2 = nullptr, uint32_t gw = 0xffffffffu);
 // forward stages sA .. log_n-1 on the chunks of `n_blocks` consecutive 2^log_n-row blocks of every column, in
 // place, canonical values out (two-pass plans).  own_a != LDE_NO_OWN: n_blocks counts a block per column that
-// is left as it is, own_a for the columns below gw and own_b from gw on
+// is left as it is, own_a for the columns below gw and own_b from gw on.
+// Block bl is coset beta0 + bl of an LDE of blowup 2^log_blowup and takes that block's stages of the
+// (n << log_blowup)-point transform; a standalone transform passes 0 and 0.
 void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
-                           uint32_t n_blocks, uint32_t gw = 0xffffffffu, uint32_t own_a = LDE_NO_OWN,
-                           uint32_t own_b = LDE_NO_OWN);
+                           uint32_t n_blocks, unsigned log_blowup, uint32_t beta0, uint32_t gw = 0xffffffffu,
+                           uint32_t own_a = LDE_NO_OWN, uint32_t own_b = LDE_NO_OWN);
 
 // ---- ntt_dft.hip -----------------------------------------------------------------------------
 // TwoAdicSubgroupDft on its own.  Row-major matrices are 2^log_n x w, natural rows,

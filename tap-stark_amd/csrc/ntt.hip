@@ -11,9 +11,10 @@
 // radix-16 group), with one LDS exchange between such rounds; the LDS image is padded so that every
 // round's access pattern is bank-conflict free (ntt_lde.hip).  Three kernels there:
 //   k_intt_contig    stages log_n-1 .. sA of the inverse on 4096-element chunks   (only n > 4096)
-//   k_lde_mid        the strided stages of the inverse (sA-1 .. 0), then for every coset: scale
-//                    coefficient k by s_beta^k / n and run the strided stages of the forward
-//                    transform, writing coset block beta -- the coefficients never touch HBM
+//   k_lde_mid        the strided stages of the inverse (sA-1 .. 0), coefficient k scaled by shift^k / n,
+//                    then for every coset the strided stages of the forward transform with the N-point
+//                    twiddles of block beta (ntt_lde.hip), writing coset block beta -- the coefficients
+//                    never touch HBM
 //   k_lde_fwd_contig stages sA .. log_n-1 of the forward transform, in place on 4096-element chunks
 // For n <= 4096 k_lde_mid alone does everything.  Data in HBM is canonical; twiddles are
 // Montgomery, so mont_mul(data, twiddle) is canonical -- or, for the NTT passes that take them, Plantard
@@ -47,14 +48,13 @@ __global__ void k_build_twiddles(uint32_t* __restrict__ W, uint32_t* __restrict_
     Winv[idx] = mont_inv(w);
 }
 
-// the Plantard words of the same entries (the NTT passes' own tables: ntt_rounds.hpp)
-__global__ void k_build_plant_twiddles(uint2* __restrict__ WP, uint2* __restrict__ WPinv, unsigned log_size) {
+// the Plantard words of the same entries, one direction (the NTT passes' own tables: ntt_rounds.hpp)
+__global__ void k_build_plant_twiddles(uint2* __restrict__ WP, unsigned log_size, bool inverse) {
     uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (1u << log_size)) return;
     const uint32_t w = twiddle_mont(idx);
-    const uint64_t f = plant_const(from_mont(w)), b = plant_const(from_mont(mont_inv(w)));
+    const uint64_t f = plant_const(from_mont(inverse ? mont_inv(w) : w));
     WP[idx] = make_uint2((uint32_t)f, (uint32_t)(f >> 32));
-    WPinv[idx] = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
 }
 
 void launch_build_twiddles(Context& ctx, uint32_t* W, uint32_t* Winv, unsigned log_size) {
@@ -63,9 +63,9 @@ void launch_build_twiddles(Context& ctx, uint32_t* W, uint32_t* Winv, unsigned l
     TS_HIP(hipGetLastError());
 }
 
-void launch_build_plant_twiddles(Context& ctx, uint2* WP, uint2* WPinv, unsigned log_size) {
+void launch_build_plant_twiddles(Context& ctx, uint2* WP, unsigned log_size, bool inverse) {
     uint32_t n = 1u << log_size;
-    TS_LAUNCH(ctx, k_build_plant_twiddles, dim3((n + 255) / 256), dim3(256), 0, WP, WPinv, log_size);
+    TS_LAUNCH(ctx, k_build_plant_twiddles, dim3((n + 255) / 256), dim3(256), 0, WP, log_size, inverse);
     TS_HIP(hipGetLastError());
 }
 
@@ -98,26 +98,23 @@ void launch_build_shift_tables(Context& ctx, uint32_t* lo, uint32_t* hi, uint32_
     TS_HIP(hipGetLastError());
 }
 
-// T[beta][k] = lo[beta][k & 1023] * hi[beta][k >> 10] = s_beta^k * scale   (Montgomery), k < n
+// T[k] = lo[k & 1023] * hi[k >> 10] = shift^k * scale   (Montgomery), k < n
 __global__ void __launch_bounds__(256)
-k_build_scale_table(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, uint32_t n_hi,
-                    unsigned log_n, uint32_t* __restrict__ T) {
-    const uint32_t beta = blockIdx.y;
+k_build_scale_table(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, unsigned log_n,
+                    uint32_t* __restrict__ T) {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= (1ull << log_n)) return;
-    const uint32_t n_lo = 1u << SHIFT_LO_BITS;
-    T[((uint64_t)beta << log_n) + k] =
-        mont_mul(lo[beta * n_lo + (k & (n_lo - 1))], hi[(uint64_t)beta * n_hi + (k >> SHIFT_LO_BITS)]);
+    T[k] = mont_mul(lo[k & ((1u << SHIFT_LO_BITS) - 1)], hi[k >> SHIFT_LO_BITS]);
 }
 
-const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, unsigned log_blowup, uint32_t shift) {
+const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, uint32_t shift) {
+    if (shift == 1) return nullptr;  // the constant 1/n: coset_lde passes it as a value
     for (auto& t : ctx.scale_tables)
-        if (t.log_n == log_n && t.log_blowup == log_blowup && t.shift == shift) {
+        if (t.log_n == log_n && t.shift == shift) {
             t.last_use = ++ctx.scale_clock;
             return t.d;
         }
-    const uint32_t n_cosets = 1u << log_blowup;
-    const size_t words = (size_t)n_cosets << log_n;
+    const size_t words = (size_t)1 << log_n;
     // keep at most 8 tables / 2 GiB; evicting needs the stream idle (a launch may still read one)
     size_t total = words * 4;
     for (auto& t : ctx.scale_tables) total += t.words * 4;
@@ -136,14 +133,13 @@ const uint32_t* coset_scale_table(Context& ctx, unsigned log_n, unsigned log_blo
     const uint64_t n = 1ull << log_n;
     const uint32_t n_lo = 1u << SHIFT_LO_BITS;
     const uint32_t n_hi = log_n > (unsigned)SHIFT_LO_BITS ? 1u << (log_n - SHIFT_LO_BITS) : 1u;
-    DevBuf<uint32_t> lo(&ctx, (size_t)n_cosets * n_lo), hi(&ctx, (size_t)n_cosets * n_hi);
-    const uint32_t n_inv_mont = to_mont(inv_canon((uint32_t)(n % P)));
-    launch_build_shift_tables(ctx, lo.p, hi.p, n_hi, n_cosets, to_mont(shift), log_n + log_blowup, log_blowup,
-                              n_inv_mont);
-    TS_LAUNCH(ctx, k_build_scale_table, dim3((unsigned)((n + 255) / 256), n_cosets), dim3(256), 0,
-              (const uint32_t*)lo.p, (const uint32_t*)hi.p, n_hi, log_n, d);
+    DevBuf<uint32_t> lo(&ctx, n_lo), hi(&ctx, n_hi);
+    // one coset, no blowup: s_0 = shift (as the standalone transforms build their factor, ntt_dft.hip)
+    launch_build_shift_tables(ctx, lo.p, hi.p, n_hi, 1, to_mont(shift), log_n, 0, lde_inv_n_mont(log_n));
+    TS_LAUNCH(ctx, k_build_scale_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint32_t*)lo.p,
+              (const uint32_t*)hi.p, log_n, d);
     TS_HIP(hipGetLastError());
-    ctx.scale_tables.push_back(Context::ScaleTable{log_n, log_blowup, shift, d, words, ++ctx.scale_clock});
+    ctx.scale_tables.push_back(Context::ScaleTable{log_n, shift, d, words, ++ctx.scale_clock});
     return d;
 }
 

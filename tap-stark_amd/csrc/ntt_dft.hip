@@ -172,7 +172,7 @@ void dft_columns(Context& ctx, uint32_t* cols, uint64_t col_stride, uint32_t nco
     const NttPlan p = ntt_plan(log_n);
     ntt_require_shape(p, ncols, col_stride, 0, false);
     ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
-    ctx.ensure_plant_twiddles(log_n == 0 ? 1 : log_n);
+    ctx.ensure_plant_twiddles(log_n == 0 ? 1 : log_n, log_n == 0 ? 1 : log_n);
 
     // factor of coefficient k: shift^k (forward; none for shift 1) or shift^-k / n (inverse)
     const bool scale = inverse || shift != 1;
@@ -190,7 +190,7 @@ void dft_columns(Context& ctx, uint32_t* cols, uint64_t col_stride, uint32_t nco
         launch_dft_mid(ctx, p, cols, col_stride, ncols, true, true, lo.p, hi.p);
     } else {
         launch_dft_mid(ctx, p, cols, col_stride, ncols, false, scale, lo.p, hi.p);
-        if (p.two_pass) launch_contig_forward(ctx, p, cols, col_stride, ncols, 1);
+        if (p.two_pass) launch_contig_forward(ctx, p, cols, col_stride, ncols, 1, 0, 0);
     }
     TS_HIP(hipGetLastError());
 }

@@ -18,11 +18,24 @@
 // profiles/r03_config3_sq_counters.txt -- lanes 0 and 31 of every 32-element run met on one bank.)
 // Three kernels:
 //   k_intt_contig    stages log_n-1 .. sA of the inverse on 2^LM-element chunks   (only n > 2^LM)
-//   k_lde_mid        the strided stages of the inverse (sA-1 .. 0), then for every coset: scale
-//                    coefficient k by s_beta^k / n and run the strided stages of the forward
-//                    transform, writing coset block beta -- the coefficients never touch HBM
+//   k_lde_mid        the strided stages of the inverse (sA-1 .. 0), coefficient k scaled once by
+//                    shift^k / n, then for every coset the strided stages of the forward transform,
+//                    writing coset block beta -- the coefficients never touch HBM
 //   k_lde_fwd_contig stages sA .. log_n-1 of the forward transform, in place on 2^LM-element chunks
 // For n <= 4096 k_lde_mid alone does everything.
+//
+// COSET TWIDDLES.  Block beta of the LDE holds the values on s_beta H_n, s_beta = shift w_N^bitrev_b(beta)
+// (N = n 2^b): the n-point forward transform of the coefficients times s_beta^k.  The coset's own part of that
+// factor, w_N^(bitrev_b(beta) k), is what the N-point transform of the zero-padded coefficients applies on the
+// way to block beta: its first b stages only copy, and stage s + b uses, on block (beta << s) + blk,
+//     W[2^(s+b) + (beta << s) + blk] = w_{2^(s+1)}^bitrev_s(blk) * w_{2^(s+b+1)}^bitrev_b(beta)
+// -- the n-point twiddle of local stage s times the factor's ratio across that stage's distance.  So the forward
+// rounds of coset beta run with the ordinary table, stage base s_base = b and chunk index c = beta (plus the
+// chunk's own bits in the contiguous pass): the index form radix_butterflies has anyway.  What is left of the
+// factor, shift^k / n, does not depend on the coset and is applied once, after the inverse rounds, from a table of
+// n words per (n, shift) (coset_scale_table; the constant 1/n for shift 1) -- no per-coset table of n 2^b words
+// (16 MB at 2^20 x 4 cosets, 268 MB at 2^22 x 16), no multiply and no table load inside the coset loop.  The
+// forward tables reach log_n + b for it (Context::ensure_lde_twiddles); the inverse Plantard table stays at log_n.
 //
 // The contiguous chunk is 2^LM elements, LM = 12 except for n = 2^21 and 2^22, where it grows to
 // 2^13 / 2^14 (LM = log_n - 8) so that the strided pass keeps the shape it has at n = 2^20 -- 8
@@ -39,6 +52,7 @@
 // forward pass on one coset block.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <optional>
 #include <type_traits>
 
@@ -103,23 +117,29 @@ k_transpose_bitrev_r16(const uint32_t* __restrict__ src, uint32_t* __restrict__ 
         if (c0 + ty + 4 * k < w) dp[(uint64_t)(4 * k) * dst_col_stride] = t[k];
 }
 
-// in place on chunk `c` of coset block `beta` of column blockIdx.y: forward stages sA .. log_n-1.
+// in place on chunk `c` of block `bl` of column blockIdx.y, coset beta = beta0 + bl of an LDE of blowup 2^log_b:
+// forward stages sA .. log_n-1 of the n-point transform with the coset's own factor folded into the twiddles,
+// i.e. stages sA + log_b .. of the N-point transform on block beta (the header's "coset twiddles"); a standalone
+// transform is log_b = 0, beta = 0.
 // CPW > 1: a workgroup takes CPW consecutive chunks and loads chunk i+1 into registers while the
 // rounds of chunk i run (the 16384-element chunk leaves room for two workgroups per CU only, and with
 // 16 waves per CU nothing else covers a chunk's load latency: rocprofv3 SQ counters on 2^22 x 64,
 // log_blowup 4 showed VALU busy 0.86 with 28 % of the wave-cycles parked).
 template <int LM, int CPW, class TW>
 __device__ __forceinline__ void lde_fwd_contig_block(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                                                     const TW* __restrict__ W, const uint32_t beta) {
+                                                     const TW* __restrict__ W, const uint32_t bl, unsigned log_b,
+                                                     uint32_t beta0) {
     __shared__ uint32_t s[padded(1 << LM)];
     constexpr int NT = chunk_threads(LM);
     constexpr int NV = (1 << LM) / 4 / NT;
-    uint32_t* col = out + (uint64_t)blockIdx.y * out_col_stride + ((uint64_t)beta << log_n);
+    uint32_t* col = out + (uint64_t)blockIdx.y * out_col_stride + ((uint64_t)bl << log_n);
+    const unsigned sb = log_n - LM + log_b;                 // the chunk's first stage in the N-point transform
+    const uint32_t cb = (beta0 + bl) << (log_n - LM);       // block beta's first chunk there
     if constexpr (CPW == 1) {
         const uint32_t c = blockIdx.x;
         uint32_t* o = col + ((uint64_t)c << LM);
         chunk_load<LM>(s, o);
-        chunk_rounds<LM, false>(s, log_n - LM, c, W);
+        chunk_rounds<LM, false>(s, sb, cb + c, W);
         chunk_store<LM, true>(s, o);
     } else {
         const uint32_t c0 = blockIdx.x * CPW;
@@ -147,7 +167,7 @@ __device__ __forceinline__ void lde_fwd_contig_block(uint32_t* __restrict__ out,
 #pragma unroll
                 for (int k = 0; k < NV; k++) v[k] = g4[threadIdx.x + (uint32_t)k * NT];
             }
-            chunk_rounds<LM, false>(s, log_n - LM, c, W);
+            chunk_rounds<LM, false>(s, sb, cb + c, W);
             chunk_store<LM, true>(s, col + ((uint64_t)c << LM));
             __syncthreads();  // the image is rewritten at the top of the loop
         }
@@ -157,8 +177,8 @@ __device__ __forceinline__ void lde_fwd_contig_block(uint32_t* __restrict__ out,
 template <int LM, int CPW = 1, class TW = uint32_t>
 __global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)  // CPW > 1: keep two 512-thread groups per CU
 k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                 const TW* __restrict__ W) {
-    lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z);
+                 const TW* __restrict__ W, unsigned log_b, uint32_t beta0) {
+    lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z, log_b, beta0);
 }
 
 // The same on all blocks but one per column, the block that is its matrix's input (own_a for the columns below
@@ -166,16 +186,22 @@ k_lde_fwd_contig(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned l
 template <int LM, int CPW = 1, class TW = uint32_t>
 __global__ void __launch_bounds__(chunk_threads(LM), CPW > 1 ? 4 : 1)
 k_lde_fwd_contig_own(uint32_t* __restrict__ out, uint64_t out_col_stride, unsigned log_n,
-                     const TW* __restrict__ W, uint32_t gw, uint32_t own_a, uint32_t own_b) {
+                     const TW* __restrict__ W, unsigned log_b, uint32_t beta0, uint32_t gw, uint32_t own_a,
+                     uint32_t own_b) {
     const uint32_t own = blockIdx.y < gw ? own_a : own_b;
-    lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z + (blockIdx.z >= own ? 1u : 0u));
+    lde_fwd_contig_block<LM, CPW>(out, out_col_stride, log_n, W, blockIdx.z + (blockIdx.z >= own ? 1u : 0u), log_b,
+                                  beta0);
 }
 
 // ------------------------------------------------------------------ middle kernel
 // Tile = slots {row << row_shift + j2_0 + jj : row < 2^log_len, jj < 2^log_T} of one column
 // (row_shift = LOG_M for n > 4096, where rows are 4096 apart; 0 for n <= 4096 with log_T = 0, where
-// the tile is the whole column).  Finishes the inverse transform (stages log_len-1 .. 0), then for
-// each coset: scaled copy -> forward stages 0 .. log_len-1 -> block beta of `out`.
+// the tile is the whole column).  Finishes the inverse transform (stages log_len-1 .. 0), multiplies
+// coefficient k by shift^k / n -- once: the factor does not depend on the coset -- and then for each coset
+// runs forward stages 0 .. log_len-1 with block beta's twiddles of the N-point transform (s_base = log_b,
+// c = beta: the header's "coset twiddles") -> block beta of `out`.
+// scale_a / scale_b: the table shift^k / n of the columns below / from gw (coset_scale_table), or nullptr
+// where the shift is 1 and the factor is the constant inv_n for every k.
 // PLAN 0: generic (runtime round plan).  PLAN 1: log_len = 8, log_T = 5 (n = 2^(LM + 8): 2^20 with
 // 4096-element chunks, 2^21 / 2^22 with LM = 13 / 14): two radix-16 rounds with compile-time
 // distances 2^9 and 2^5.
@@ -186,9 +212,9 @@ template <int PLAN, int TILE = TILE_ELEMS, int NTM = NT_MID, int LM = LOG_M, boo
 __global__ void __launch_bounds__(NTM)
 k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* __restrict__ out,
           uint64_t out_col_stride, unsigned log_n, unsigned log_len, unsigned log_T,
-          unsigned row_shift, unsigned beta0, unsigned n_cosets, const TWF* __restrict__ W,
+          unsigned row_shift, unsigned log_b, unsigned beta0, unsigned n_cosets, const TWF* __restrict__ W,
           const TWI* __restrict__ Winv, const uint32_t* __restrict__ scale_a,
-          const uint32_t* __restrict__ evals2, const uint32_t* __restrict__ scale_b, uint32_t gw,
+          const uint32_t* __restrict__ evals2, const uint32_t* __restrict__ scale_b, uint32_t inv_n, uint32_t gw,
           uint32_t own_a, uint32_t own_b) {
     __shared__ uint32_t s[padded(TILE)];
     constexpr int PER_THREAD = TILE / NTM;
@@ -214,7 +240,7 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
     }
     const uint32_t j2_0 = bx << log_T;
     // a two-matrix launch (coset_lde: evals2): columns gw .. come from the second matrix and take its
-    // coset's scale table; the output columns follow each other either way
+    // shift's scale table; the output columns follow each other either way
     const uint32_t* g = (col_id < gw ? evals + (uint64_t)col_id * in_col_stride
                                      : evals2 + (uint64_t)(col_id - gw) * in_col_stride) + j2_0;
     const uint32_t* __restrict__ scale = col_id < gw ? scale_a : scale_b;
@@ -235,6 +261,19 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
     } else {
         for (uint32_t i = threadIdx.x; i < total; i += NTM)
             s[pad(i)] = g[((uint64_t)(i >> log_T) << row_shift) + (i & tmask)];
+    }
+    // the factors of the coefficients this thread will keep (slot i = threadIdx.x + k NTM is coefficient
+    // off(i) + j2_0): asked for here, used after the inverse rounds, which cover the loads
+    uint32_t scv[PER_THREAD];
+    if (scale != nullptr) {  // one value per workgroup
+#pragma unroll
+        for (int k = 0; k < PER_THREAD; k++) {
+            const uint32_t i = threadIdx.x + (uint32_t)k * NTM;
+            scv[k] = i < total ? scale[((uint64_t)(i >> log_T) << row_shift) + (i & tmask) + j2_0] : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < PER_THREAD; k++) scv[k] = inv_n;
     }
     __syncthreads();
     if (PLAN == 1) {
@@ -266,59 +305,40 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
             for (int q = 0; q < 16; q++) coef[j + GP * q] = v[q];
         }
     }
+    // shift^k / n, once for every coset (lazy product: the butterflies that follow take [0, 2p) -- two
+    // instructions fewer per coefficient).  What is left of s_beta^k, w_N^(bitrev_b(beta) k), is the difference
+    // between the n-point twiddles and block beta's of the N-point transform, which the forward rounds take.
+#pragma unroll
+    for (int k = 0; k < PER_THREAD; k++) coef[k] = mont_mul_lazy(coef[k], scv[k]);
     // cosets beta0 .. beta0 + n_cosets - 1 go to blocks 0 .. n_cosets - 1 of `out` (a rank of a
     // sharded prover owns a contiguous range of cosets)
-    // PLAN 1: the 16 scale-table entries of the NEXT coset are loaded while this coset is computed
-    // (the table of a big shape -- 268 MB at 2^22 rows, log_blowup 4 -- is served from L2 at best, and
-    // with one LDS round per coset there is little else to hide that latency behind): 16 more VGPRs
-    // (109 -> 125, still two workgroups per CU).
-    // (nontemporal stores of the coset blocks, to keep the table slices in L2, changed nothing at
-    // 2^22 x 64, log_blowup 4: 7.92 against 7.90 ms per launch.  Nor did two LDS images used in turn,
-    // which make the barrier at the top of the coset loop unnecessary (3 -> 2 barriers per coset, but
-    // 114 VGPRs and run-time image addresses): 0.61 against 0.59-0.60 ms at C3, 8.19 against 7.9-8.1.)
-    constexpr bool PREFETCH = PLAN == 1;
-    uint32_t scv[PREFETCH ? 16 : 1];
-    const uint32_t* scp = nullptr;  // this thread's first entry in coset block 0 of the table
-    if constexpr (PREFETCH) {
-        const uint32_t i0 = threadIdx.x;
-        scp = scale + ((uint64_t)(i0 >> 5) << LM) + (i0 & 31) + j2_0;
-        const uint32_t first = OWN && own == 0 ? 1u : 0u;  // the first coset computed
-#pragma unroll
-        for (int q = 0; q < 16; q++)
-            scv[q] = (scp + ((uint64_t)(beta0 + first) << log_n))[(uint64_t)q * (NTM >> 5) << LM];
-    }
+    // (nontemporal stores of the coset blocks changed nothing at 2^22 x 64, log_blowup 4: 7.92 against
+    // 7.90 ms per launch.  Nor did two LDS images used in turn, which make the barrier at the top of the
+    // coset loop unnecessary (3 -> 2 barriers per coset, but more VGPRs and run-time image addresses): 0.61
+    // against 0.59-0.60 ms at C3, 8.19 against 7.9-8.1.)
     for (uint32_t bl = 0; bl < n_cosets; bl++) {
         if (OWN && bl == own) continue;
         const uint32_t beta = beta0 + bl;
-        const uint32_t* sc = scale + ((uint64_t)beta << log_n);  // s_beta^k / n, one entry per coefficient
         __syncthreads();
         if constexpr (PLAN == 1) {
-            // scaled coefficients and the first forward round (the thread's own elements) stay in
-            // registers; LDS is written once, for the following rounds
+            // the first forward round (the thread's own elements) stays in registers; LDS is written
+            // once, for the following rounds.  No twiddle-1 shortcut: block beta's twiddles are 1 for
+            // beta = 0 only, and a second copy of the loop body for that coset is not worth its code.
 #pragma unroll
             for (int j = 0; j < GP; j++) {
                 uint32_t v[16];
-                // (lazy product: the butterflies that follow take [0, 2p) -- two instructions fewer
-                // per coefficient and coset)
 #pragma unroll
-                for (int q = 0; q < 16; q++) v[q] = mont_mul_lazy(coef[j + GP * q], scv[q]);
-                const uint32_t nb = OWN && bl + 1 == own ? bl + 2 : bl + 1;  // the next coset computed
-                if (nb < n_cosets) {
-                    const uint32_t* nx = scp + ((uint64_t)(beta0 + nb) << log_n);
-#pragma unroll
-                    for (int q = 0; q < 16; q++) scv[q] = nx[(uint64_t)q * (NTM >> 5) << LM];
-                }
-                radix_butterflies<4, false, true>(v, 0, 0, 0, 0, W);
+                for (int q = 0; q < 16; q++) v[q] = coef[j + GP * q];
+                radix_butterflies<4, false, false>(v, log_b, 0, beta, 0, W);
 #pragma unroll
                 for (int q = 0; q < 16; q++) s[pad(threadIdx.x + (uint32_t)(j + GP * q) * NTM)] = v[q];
             }
             __syncthreads();
             uint32_t* og = out + (uint64_t)col_id * out_col_stride + ((uint64_t)bl << log_n) + j2_0;
-            // (writing this round's results straight to HBM from registers: round 2 it needed 137 VGPRs
-            // -- one workgroup per CU -- and ran 0.85 ms against 0.64; since the scale prefetch
-            // simplified the addressing it fits in 123 and runs 0.584-0.591 ms per proof against
-            // 0.588-0.601: within the noise of whole proofs, so the LDS round stays)
-            radix_round<4, false, 5, NTM>(s, 13, 4, 0, 0, W);
+            // (writing this round's results straight to HBM from registers was tried twice: 137 VGPRs
+            // -- one workgroup per CU -- and 0.85 ms against 0.64, later 123 VGPRs and 0.584-0.591 ms per
+            // proof against 0.588-0.601: within the noise of whole proofs, so the LDS round stays)
+            radix_round<4, false, 5, NTM>(s, 13, 4, log_b, beta, W);
             // lazy values: k_lde_fwd_contig reads them next.  Unrolled: 16 LDS reads in flight, then
             // 16 stores whose addresses differ by constants (as a run-time loop each iteration
             // cost 7 VALU instructions and waited for its own LDS read)
@@ -333,14 +353,10 @@ k_lde_mid(const uint32_t* __restrict__ evals, uint64_t in_col_stride, uint32_t* 
 #pragma unroll
             for (int k = 0; k < PER_THREAD; k++) {
                 const uint32_t i = threadIdx.x + (uint32_t)k * NTM;
-                if (i < total) {
-                    // coefficient index of this slot
-                    const uint32_t kk = ((i >> log_T) << row_shift) + (i & tmask) + j2_0;
-                    s[pad(i)] = mont_mul_lazy(coef[k], sc[kk]);
-                }
+                if (i < total) s[pad(i)] = coef[k];
             }
             __syncthreads();
-            tile_forward_rt<NTM>(s, log_len, log_T, 0, 0, W);
+            tile_forward_rt<NTM>(s, log_len, log_T, log_b, beta, W);
         }
         uint32_t* o = out + (uint64_t)col_id * out_col_stride + ((uint64_t)bl << log_n) + j2_0;
         if (row_shift != 0) {  // n > 4096: k_lde_fwd_contig follows and takes lazy values
@@ -436,7 +452,7 @@ static void with_chunk_log(unsigned LM, F&& f) {
 bool launch_transpose_bitrev_r16(Context& ctx, const uint32_t* src, uint32_t* dst, unsigned log_n, uint32_t w,
                                  uint64_t dst_col_stride, uint32_t src_width) {
     if (w == 0 || !ntt_plan(log_n).fused_first_round) return false;  // no contiguous inverse pass to shorten
-    ctx.ensure_plant_twiddles(log_n);
+    ctx.ensure_plant_twiddles(0, log_n);
     TS_LAUNCH(ctx, k_transpose_bitrev_r16, dim3(1u << (log_n - 6), (w + 63) / 64), dim3(256), 0, src, dst, log_n, w,
               dst_col_stride, src_width ? src_width : w, (const uint2*)ctx.d_plant_inv);
     TS_HIP(hipGetLastError());
@@ -463,14 +479,14 @@ void launch_contig_inverse(Context& ctx, const NttPlan& p, uint32_t* data, uint6
 // one pass); two matrices as coset_lde
 static void launch_lde_mid(Context& ctx, const NttPlan& p, const uint32_t* evals, uint64_t in_col_stride,
                            uint32_t* out, uint64_t out_col_stride, uint32_t ncols, uint32_t beta0, uint32_t n_beta,
-                           const uint32_t* scale, const uint32_t* evals2, const uint32_t* scale2, uint32_t gw,
-                           uint32_t own_a, uint32_t own_b) {
+                           unsigned log_blowup, const uint32_t* scale, const uint32_t* evals2, const uint32_t* scale2,
+                           uint32_t gw, uint32_t own_a, uint32_t own_b) {
     const TwTables W = twiddles_fwd(ctx), Winv = twiddles_inv(ctx);
     const dim3 grid(p.tiles, ncols), b(NT_MID);
     const dim3 grid1(p.tiles * ncols);  // the fixed plan: 1-D, see the kernel
 #define TS_MID_ARGS \
-    evals, in_col_stride, out, out_col_stride, p.log_n, p.log_len, p.log_T, p.row_shift, beta0, n_beta, W, Winv, scale, \
-        evals2, scale2, gw, own_a, own_b
+    evals, in_col_stride, out, out_col_stride, p.log_n, p.log_len, p.log_T, p.row_shift, log_blowup, beta0, n_beta, W, \
+        Winv, scale, evals2, scale2, lde_inv_n_mont(p.log_n), gw, own_a, own_b
 #define TS_MID_K(PLAN, TILE, LM, OWN) \
     (k_lde_mid<PLAN, TILE, NT_MID, LM, OWN, typename MidForm<PLAN, TILE>::Fwd, typename MidForm<PLAN, TILE>::Inv>)
     // (the instantiations that step over a block run under the names of the ones that do not)
@@ -499,7 +515,8 @@ static void launch_lde_mid(Context& ctx, const NttPlan& p, const uint32_t* evals
 }
 
 void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint64_t col_stride, uint32_t ncols,
-                           uint32_t n_blocks, uint32_t gw, uint32_t own_a, uint32_t own_b) {
+                           uint32_t n_blocks, unsigned log_blowup, uint32_t beta0, uint32_t gw, uint32_t own_a,
+                           uint32_t own_b) {
     const TwTables W = twiddles_fwd(ctx);
     with_chunk_log(p.LM, [&](auto lm) {
         constexpr int LM = decltype(lm)::value;
@@ -510,10 +527,10 @@ void launch_contig_forward(Context& ctx, const NttPlan& p, uint32_t* data, uint6
         if (own_a != LDE_NO_OWN)  // one block per column is already there: n_blocks - 1 of them in z
             TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig_own<LM, CPW, TW>),
                             dim3(p.chunks / CPW, ncols, n_blocks - 1), dim3(chunk_threads(LM)), 0, data, col_stride,
-                            p.log_n, W, gw, own_a, own_b);
+                            p.log_n, W, log_blowup, beta0, gw, own_a, own_b);
         else
             TS_LAUNCH_NAMED(ctx, FWD_NAME[LM - 12], (k_lde_fwd_contig<LM, CPW, TW>), dim3(p.chunks / CPW, ncols, n_blocks),
-                            dim3(chunk_threads(LM)), 0, data, col_stride, p.log_n, W);
+                            dim3(chunk_threads(LM)), 0, data, col_stride, p.log_n, W, log_blowup, beta0);
     });
 }
 
@@ -537,15 +554,18 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
     ntt_require_shape(p, ncols, in_col_stride, out_col_stride, true);
     TS_REQUIRE(!first_round_done || p.fused_first_round, TS_ERR_INVARIANT,
                "coset_lde: no contiguous inverse pass at this size");
-    ctx.ensure_twiddles(log_n == 0 ? 1 : log_n);
-    ctx.ensure_plant_twiddles(log_n == 0 ? 1 : log_n);
+    // the forward passes index block beta of the N-point transform: both forward tables reach log_n + log_blowup
+    // (a prover has asked for them already, Context::ensure_lde_twiddles: nothing is rebuilt here inside a proof);
+    // the inverse Plantard table stays at log_n
+    ctx.ensure_lde_twiddles(std::max(1u, log_n + log_blowup));
+    ctx.ensure_plant_twiddles(0, std::max(1u, log_n));
 
-    // per-coset scale table s_beta^k / n (cached per context: the trace's is the same every proof)
+    // scale table shift^k / n (cached per context: the trace's is the same every proof; none for shift 1)
     const uint32_t n_cosets = 1u << log_blowup;
     if (n_beta == 0) n_beta = n_cosets - beta0;
     TS_REQUIRE(beta0 < n_cosets && n_beta <= n_cosets - beta0, TS_ERR_INVALID, "coset_lde: coset range");
-    const uint32_t* scale = coset_scale_table(ctx, log_n, log_blowup, shift);
-    const uint32_t* scale2 = evals2 ? coset_scale_table(ctx, log_n, log_blowup, shift2) : nullptr;
+    const uint32_t* scale = coset_scale_table(ctx, log_n, shift);
+    const uint32_t* scale2 = evals2 ? coset_scale_table(ctx, log_n, shift2) : nullptr;
 
     // A whole LDE whose input lies on one of its cosets (the quotient chunks, the reduced opening): that block is
     // copied -- now, the inverse pass works in place -- and the passes leave it out.  Every matrix of the launch
@@ -570,8 +590,8 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
     }
 
     if (!p.two_pass) {
-        launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2, scale2,
-                       gw, own_a, own_b);
+        launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, log_blowup, scale, evals2,
+                       scale2, gw, own_a, own_b);
     } else {
         // (ctx.lde_pass_mask: measurement only -- ts_bench_stage runs one of the three passes alone, on
         // whatever the buffers hold, to sample its clock and power; every product path leaves it at 7)
@@ -584,9 +604,10 @@ void coset_lde(Context& ctx, uint32_t* evals, uint64_t in_col_stride, uint32_t n
         std::optional<StageTimer> t_rest;
         if (stage_timers) t_rest.emplace(&ctx, "lde: strided pass + forward NTT of the owned cosets");
         if (ctx.lde_pass_mask & 2u)
-            launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, scale, evals2,
-                           scale2, gw, own_a, own_b);
-        if (ctx.lde_pass_mask & 4u) launch_contig_forward(ctx, p, out, out_col_stride, ncols, n_beta, gw, own_a, own_b);
+            launch_lde_mid(ctx, p, evals, in_col_stride, out, out_col_stride, ncols, beta0, n_beta, log_blowup, scale,
+                           evals2, scale2, gw, own_a, own_b);
+        if (ctx.lde_pass_mask & 4u) launch_contig_forward(ctx, p, out, out_col_stride, ncols, n_beta, log_blowup, beta0, gw, own_a,
+                                                          own_b);
     }
     TS_HIP(hipGetLastError());
 }

@@ -329,7 +329,7 @@ static std::vector<uint32_t> prove_multi_versioned(TwoAdicFriPcs& pcs, BfChallen
         st.push_back(check_statement(pcs.fri(), *t.air, t.trace.width, t.trace.height, t.public_values.size()));
         log_max = std::max(log_max, st.back().log_N);
     }
-    ctx.ensure_twiddles(std::max(1u, log_max));
+    ctx.ensure_lde_twiddles(std::max(1u, log_max));
 
     // the statement's shape: a prover must not choose the heights after the fact
     challenger.observe((uint32_t)T);

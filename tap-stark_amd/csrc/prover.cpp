@@ -226,7 +226,7 @@ DevBuf<Ef> TwoAdicFriPcs::open_reduce_slab(const PcsData& trace_data, const PcsD
     const uint32_t qd = (uint32_t)quotient_data.ldes.size();
     for (auto& m : quotient_data.ldes)
         TS_REQUIRE(m.width == 4, TS_ERR_INVALID, "open: quotient chunks must have width 4");
-    ctx_.ensure_twiddles(std::max(1u, log_N));
+    ctx_.ensure_lde_twiddles(std::max(1u, log_N));
     // the matrices opened at both points, in opening order: the leading ones, then the trace.  Raw sums and
     // opened values are laid out in that order, 2 width words each, and the 4 qd of the chunks behind them
     const ColMat* two_point[3];
@@ -559,7 +559,7 @@ std::vector<uint32_t> prove(TwoAdicFriPcs& pcs, const AirProgram& air, BfChallen
         challenger.observe_commitment(preprocessed->root);
         side.push_back(preprocessed);
     }
-    pcs.ctx().ensure_twiddles(std::max(1u, st.log_N));
+    pcs.ctx().ensure_lde_twiddles(std::max(1u, st.log_N));
     const uint64_t n = trace.height;
 
     // :50-53 commit to trace data (natural domain: shift 1)

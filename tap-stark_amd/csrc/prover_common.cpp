@@ -108,7 +108,7 @@ void lde_stage(Context& ctx, const FriConfig& fri, std::vector<DeviceMatrix>& ev
     TS_REQUIRE(same_height || !n_beta, TS_ERR_INVALID, "sharded commit: matrices of one height expected");
     const unsigned log_N = log2_strict(max_n) + fri.log_blowup;
     TS_REQUIRE(log_N <= 27, TS_ERR_INVALID, "commit: LDE larger than the two-adic subgroup");
-    ctx.ensure_twiddles(std::max(1u, log_N));
+    ctx.ensure_lde_twiddles(std::max(1u, log_N));
     // rows held of the LDE of a matrix of height n: all, or the n_beta owned cosets
     auto lde_rows = [&](uint64_t n) { return n_beta ? (uint64_t)n_beta * n : n << fri.log_blowup; };
     data.log_height = log2_strict(lde_rows(max_n));

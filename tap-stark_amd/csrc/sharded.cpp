@@ -221,7 +221,7 @@ std::vector<uint32_t> prove_sharded(TwoAdicFriPcs& pcs, const Comm& comm, const 
     const uint32_t w = stm.w, qd = stm.qd;
     const uint64_t N = 1ull << log_N, n = degree;
     const uint64_t loc0 = N / G;  // slab height
-    ctx.ensure_twiddles(std::max(1u, log_N));
+    ctx.ensure_lde_twiddles(std::max(1u, log_N));
     TwoAdicFriPcs::Slab slab;
     slab.row0 = (uint64_t)sh.rank * loc0;
     slab.rows = loc0;
