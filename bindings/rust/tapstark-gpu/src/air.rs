@@ -435,3 +435,79 @@ impl LogUp {
         (n_missing, first_missing)
     }
 }
+
+// ---- row programs with carried state for the iterate form of `ts_matrix_derive` (include/tapstark.h "iterated
+// columns"): the constants and a mirror of `tap-stark_amd/iterate.py`'s builder.  Source only, never compiled, like
+// the rest of the crate.  The tape goes to `ts_matrix_derive`, `ts_derive_check` and `ts_derive_rows_host` as it is.
+pub const DERIVE_MAGIC: u32 = 0x5245_4454; // "TDER"
+pub const ITERATE_MAGIC: u32 = 0x5254_4954; // "TITR"
+pub const ITERATE_MAX_CARRIES: u32 = 16;
+pub const ITERATE_MAX_WORK: u64 = 1 << 20;
+pub const ITERATE_NO_RESET: u32 = 0xFFFF_FFFF;
+pub const V_CONST: u32 = 0;
+pub const V_COL: u32 = 1;
+pub const V_ROW: u32 = 32;
+pub const V_INV: u32 = 33;
+pub const V_IS_ZERO: u32 = 34;
+pub const V_LT: u32 = 35;
+pub const V_BITS: u32 = 36;
+pub const V_AND: u32 = 37;
+pub const V_XOR: u32 = 38;
+pub const V_CARRY: u32 = 40;
+pub const V_STEP: u32 = 41;
+pub const V_IS_GROUP_FIRST: u32 = 42;
+pub const V_IS_GROUP_LAST: u32 = 43;
+
+/// A node of an [`IterateBuilder`].
+#[derive(Clone, Copy, Debug)]
+pub struct IterNode(pub u32);
+
+/// Collects the nodes, outputs and carries of a TITR program.  Nothing is checked here: `ts_derive_check` is the judge.
+pub struct IterateBuilder {
+    src_width: u32,
+    reset_column: u32,
+    max_group_rows: u32,
+    nodes: Vec<[u32; 3]>,
+    outputs: Vec<[u32; 2]>,
+    carries: Vec<[u32; 2]>, // {node, init}
+}
+
+impl IterateBuilder {
+    pub fn new(src_width: u32, reset_column: Option<u32>, max_group_rows: u32) -> Self {
+        Self { src_width, reset_column: reset_column.unwrap_or(ITERATE_NO_RESET), max_group_rows, nodes: Vec::new(),
+               outputs: Vec::new(), carries: Vec::new() }
+    }
+    pub fn node(&mut self, op: u32, a: u32, b: u32) -> IterNode {
+        self.nodes.push([op, a, b]);
+        IterNode(self.nodes.len() as u32 - 1)
+    }
+    pub fn constant(&mut self, v: u64) -> IterNode { self.node(V_CONST, (v % 0x7800_0001) as u32, 0) }
+    pub fn col(&mut self, c: u32) -> IterNode { self.node(V_COL, 0, c) }
+    pub fn next(&mut self, c: u32) -> IterNode { self.node(V_COL, 1, c) }
+    pub fn prev(&mut self, c: u32) -> IterNode { self.node(V_COL, 2, c) }
+    pub fn add(&mut self, x: IterNode, y: IterNode) -> IterNode { self.node(OP_ADD, x.0, y.0) }
+    pub fn sub(&mut self, x: IterNode, y: IterNode) -> IterNode { self.node(OP_SUB, x.0, y.0) }
+    pub fn mul(&mut self, x: IterNode, y: IterNode) -> IterNode { self.node(OP_MUL, x.0, y.0) }
+    /// A new carry: the node reads its value from BEFORE this row, `init` on a group's first row.
+    pub fn carry(&mut self, init: u64) -> IterNode {
+        self.carries.push([u32::MAX, (init % 0x7800_0001) as u32]);
+        self.node(V_CARRY, self.carries.len() as u32 - 1, 0)
+    }
+    /// After a row the carry (what `carry` returned) holds `x` of that row.
+    pub fn set_carry(&mut self, carry: IterNode, x: IterNode) {
+        let k = self.nodes[carry.0 as usize][1] as usize;
+        self.carries[k][0] = x.0;
+    }
+    pub fn step(&mut self) -> IterNode { self.node(V_STEP, 0, 0) }
+    pub fn is_group_first(&mut self) -> IterNode { self.node(V_IS_GROUP_FIRST, 0, 0) }
+    pub fn is_group_last(&mut self) -> IterNode { self.node(V_IS_GROUP_LAST, 0, 0) }
+    pub fn output(&mut self, x: IterNode, dst_column: u32) { self.outputs.push([x.0, dst_column]); }
+    pub fn tape(&self) -> Vec<u32> {
+        let mut t = vec![ITERATE_MAGIC, 1, self.src_width, self.nodes.len() as u32, self.outputs.len() as u32,
+                         self.carries.len() as u32, self.reset_column, self.max_group_rows];
+        t.extend(self.nodes.iter().flatten());
+        t.extend(self.outputs.iter().flatten());
+        t.extend(self.carries.iter().flatten());
+        t
+    }
+}

@@ -1404,9 +1404,10 @@ ts_status ts_matrix_gather_rows(ts_ctx* ctx, const ts_matrix* src, const ts_matr
  * accesses and interprets the list (scalar instruction fetch, the slot file in LDS).  The call makes no host wait of
  * its own (the arena waits once when it wraps, as for every small upload).  Temporaries come from ctx's pool.
  * The interpreter is the only form: a program is not specialised into a kernel of its own.
- * Out of scope: anything not row-local -- rows that depend on derived values of other rows (chain two calls instead;
- * a first-order recurrence down the rows is ts_matrix_scan below); more than one source matrix; parameters other than
- * constants; extension-field values; use inside batch lanes. */
+ * Out of scope: more than one source matrix; parameters other than constants; extension-field values; use inside batch
+ * lanes.  A TDER program is row-local; rows that depend on derived values of other rows are the other program kind of
+ * these three entry points, "iterated columns" below (a first-order linear recurrence down the rows is cheaper as
+ * ts_matrix_scan further below; or chain two calls). */
 enum { TS_DERIVE_MAX_NODES = 4096, TS_DERIVE_MAX_OUTPUTS = 256, TS_DERIVE_MAX_LIVE = 48 };
 ts_status ts_matrix_derive(ts_ctx* ctx, const uint32_t* program, size_t n_words, const ts_matrix* src, ts_matrix** out);
 /* Host only, no context: every check above that needs no matrix, against a source of src_width columns; the text of a
@@ -1419,6 +1420,65 @@ ts_status ts_derive_check(const uint32_t* program, size_t n_words, uint32_t src_
  * for tests and for callers without a device, not a fast path. */
 ts_status ts_derive_rows_host(const uint32_t* program, size_t n_words, const uint32_t* src_row_major, uint64_t height,
                               uint32_t src_width, uint32_t* out_row_major, size_t out_cap_words);
+
+/* ---- iterated columns: a row program with carried state, per group, in HBM ----
+ * A TDER program is row-local and the scan below runs first-order LINEAR recurrences.  Everything else that is
+ * sequential -- the state column of a hash or sponge chip, the rounds of a block cipher laid out one per row, a
+ * division or square-root loop, a Fibonacci-style pair, a small state machine -- is a row program whose registers are
+ * carried from one row to the next inside a group of rows: one call, one hash invocation, one address.  The recurrence
+ * is sequential inside a group and a trace has thousands of groups, so the device walks the groups side by side.  It
+ * replaces: ts_matrix_download, a host loop down the rows, ts_matrix_upload.
+ * No entry point is added: the iterate form is a SECOND PROGRAM KIND of ts_matrix_derive, ts_derive_check and
+ * ts_derive_rows_host, chosen by the tape's magic.  A "TDER" tape behaves as written above, word for word.
+ * The program, a "TITR" tape of 32-bit words:
+ *   [0]=0x52544954 ("TITR")  [1]=1  [2]=src_width  [3]=n_nodes  [4]=n_outputs
+ *   [5]=n_carries (1 .. TS_ITERATE_MAX_CARRIES)  [6]=reset_column (a column of src, or 0xFFFFFFFF: none)
+ *   [7]=max_group_rows (>= 1)
+ *   n_nodes   x {op, a, b}          as TDER: operands name EARLIER nodes only
+ *   n_outputs x {node, dst_column}  as TDER, the same rules on destination columns
+ *   n_carries x {node, init}        carry k's value after a row is `node` of that row; init < p, canonical
+ * Groups: row 0 starts a group, and so does every row whose reset_column word, reduced mod p, is != 0 -- the rule of the
+ * scan's reset column and of the collect's selectors: 0, p and 2p do not fire, 1 and 0xFFFFFFFF do.  Without a reset
+ * column the whole matrix is one group.  A group ends before the next start or at row h-1; groups are not cyclic.
+ * Ops: every TDER op keeps its meaning, COL with its cyclic neighbour rows of the whole matrix included.  Four more:
+ *   40 CARRY(a = k < n_carries): the value of carry k's node on the previous row of this group, init_k on the group's
+ *      first row.  A CARRY always reads the value from BEFORE this row: a, b <- b, a + b with two carries needs no
+ *      temporary
+ *   41 STEP: the row minus the group's first row
+ *   42 IS_GROUP_FIRST   43 IS_GROUP_LAST (1 when the next row starts a group, or on row h-1)
+ * In a TDER tape 40 .. 43 stay unknown ops.
+ * Output: as for a TDER program -- a NEW row-major matrix of src's height, named columns canonical, the others copied
+ * as stored, all reads see src, src untouched, the result a pure function of src and the same on every run and for
+ * every value of the knob below.
+ * Lowering (ts_derive_check reports it): as above, and carry k owns slot k for the whole walk; a CARRY is an instruction
+ * that copies its carry into a slot of its own; the nodes of the carries are always kept and hold their slots to the end
+ * of the list, where one latch per carry moves the new value into the carry's slot, after every CARRY has been read.
+ * n_live counts the carry slots and the temporaries together, against the same TS_DERIVE_MAX_LIVE; n_instructions is
+ * the nodes kept.
+ * TS_ERR_INVALID, each with a text ("iterate: ...") before any device work, on top of the TDER refusals: n_carries
+ * outside 1 .. 16; a carry node >= n_nodes; init >= p; a CARRY index >= n_carries; reset_column outside src;
+ * max_group_rows = 0; max_group_rows x (the length of the lowered list, stores and latches included) above
+ * TS_ITERATE_MAX_WORK (the text names both factors) -- a condition, not a measurement: it bounds what one lane can be
+ * asked to run on a machine it shares; a word count that does not match the header; TS_ITERATE_BLOCK_ROWS outside its
+ * range.
+ * A group longer than max_group_rows refuses the call after its one host wait, TS_ERR_INVARIANT "iterate: the group
+ * that starts at row R has N rows, max_group_rows is M", R the least such start row; *out stays NULL, every pool block
+ * goes back and the kernel that walks the groups is never launched.  The host evaluator refuses with the same text
+ * before it writes a word.
+ * Launches: FOUR kernels (csrc/iterate.hip), no workgroup waits for another.  (1) count: per block of
+ * TS_ITERATE_BLOCK_ROWS rows the number of group starts and the last of them, from the reset column alone; (2) offsets,
+ * one workgroup: the exclusive scan of the counts and the last start before every block; (3) starts: the row every
+ * group starts at, and -- since a start knows the start before it -- the least over-long group, with its length;
+ * (4) walk: workgroups of one wave, one lane per group; the workgroup copies the untouched columns of its rows with
+ * coalesced accesses, then walks its longest group's rows with the interpreter of a TDER program (scalar instruction
+ * fetch, the slot file in LDS), a lane past its group's end idle.  Every out word is written exactly once.
+ * Waits: exactly ONE, between (3) and (4), for 16 bytes: the number of groups, which sizes (4), and the over-long
+ * group, which refuses the call.  Temporaries come from ctx's pool: 4 bytes per row, 8 per block.
+ * TS_ITERATE_BLOCK_ROWS (1 .. 1024, default 1024, read on every call) is a test knob: the rows of a count block.  No
+ * output word depends on it; a value so small that a grid would pass 2^24 workgroups is TS_ERR_INVALID.
+ * Out of scope: suffix (reverse) walks; extension-field state; more than one source; groups longer than the work
+ * limit allows; use inside batch lanes; a program specialised into its own kernel. */
+enum { TS_ITERATE_MAX_CARRIES = 16, TS_ITERATE_MAX_WORK = 1 << 20 };
 
 /* ---- scanned columns: linear recurrences down the rows, in HBM ----
  * The derive closed the host round trip for columns that are a function of their own row and its neighbours; this closes

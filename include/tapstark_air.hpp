@@ -438,9 +438,44 @@ public:
         return t;
     }
 
-private:
+protected:
     uint32_t src_width_;
     std::vector<uint32_t> nodes_, outputs_;
+};
+
+// ---- row programs with carried state for the iterate form of ts_matrix_derive (include/tapstark.h "iterated
+// columns"): the counterpart of tap-stark_amd/iterate.py, a Derive whose tape is a TITR tape.  carry(init) makes one
+// register and gives the expression that reads it -- its value from BEFORE this row, init on a group's first row;
+// set_carry says what it holds after a row.  A carry that was never set names node 0xFFFFFFFF and is refused.
+class Iterate : public Derive {
+public:
+    enum GroupOp : uint32_t { CARRY = 40, STEP = 41, IS_GROUP_FIRST = 42, IS_GROUP_LAST = 43 };
+    static constexpr uint32_t MAGIC = 0x52544954u;  // "TITR"
+    static constexpr uint32_t NO_RESET = 0xFFFFFFFFu;
+
+    explicit Iterate(uint32_t src_width, uint32_t reset_column = NO_RESET, uint32_t max_group_rows = 1024)
+        : Derive(src_width), reset_column_(reset_column), max_group_rows_(max_group_rows) {}
+    DExpr carry(uint64_t init = 0) {
+        carries_.insert(carries_.end(), {0xFFFFFFFFu, (uint32_t)(init % P)});
+        return node(CARRY, (uint32_t)(carries_.size() / 2 - 1), 0);
+    }
+    // `carry` is what carry() returned
+    void set_carry(DExpr carry, DExpr x) { carries_[2 * nodes_[3 * carry.id() + 1]] = x.id(); }
+    DExpr step() { return node(STEP, 0, 0); }
+    DExpr is_group_first() { return node(IS_GROUP_FIRST, 0, 0); }
+    DExpr is_group_last() { return node(IS_GROUP_LAST, 0, 0); }
+    std::vector<uint32_t> tape() const {
+        std::vector<uint32_t> t = {MAGIC, 1, src_width_, (uint32_t)(nodes_.size() / 3), (uint32_t)(outputs_.size() / 2),
+                                   (uint32_t)(carries_.size() / 2), reset_column_, max_group_rows_};
+        t.insert(t.end(), nodes_.begin(), nodes_.end());
+        t.insert(t.end(), outputs_.begin(), outputs_.end());
+        t.insert(t.end(), carries_.begin(), carries_.end());
+        return t;
+    }
+
+private:
+    uint32_t reset_column_, max_group_rows_;
+    std::vector<uint32_t> carries_;  // {node, init} per carry
 };
 
 inline DExpr DExpr::inv() const { return b_->node(Derive::INV, id_, 0); }

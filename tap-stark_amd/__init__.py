@@ -13,6 +13,7 @@ from .stark import MultiKey, MultiKeyProof, MultiKeyTableOpening, prove_multi_ke
 from .air import BusReport, BusShare, bus_check  # noqa: F401
 from .stark import check_multi  # noqa: F401
 from .derive import DeriveBuilder, derive_check, derive_rows_host  # noqa: F401
+from .iterate import IterateBuilder, iterate_check, iterate_rows_host  # noqa: F401
 from .scan import ScanSpec, carry_last, running_product, running_sum, scan_rows_host  # noqa: F401
 from .collect import CollectSpec, collect_check, collect_rows_host  # noqa: F401
 from .stark import collect_rows  # noqa: F401

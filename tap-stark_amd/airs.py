@@ -1507,3 +1507,169 @@ def fill_span_range_multiplicities(range_trace, chip_table, allow_missing: bool 
     A = SpanChipAir
     return logup_multiplicities_bus(range_trace, [("col", 0)], [(chip_table, [[("col", A.ADDR)]], [("col", A.LIVE)])],
                                     out_column=1, negate=1, allow_missing=allow_missing)
+
+
+# ---------------------------------------------------------------------------------------------- a sponge on the bus
+# A hash call is one row of the machine and ``len`` rows of its chip, where the state after a row is a NONLINEAR function
+# of the state after the row before and the word absorbed: no scan computes it.  The chip's rows are made with
+# ``expand_rows``, its ``acc`` and ``state`` columns with ``DeviceMatrix.iterate`` -- one lane per call, walking its rows
+# -- and each call's digest comes back into the machine's trace with ``join_rows``.
+SPONGE_TAG = 19
+SPONGE_IV = 0x5EED
+
+
+class SpongeCallAir(BaseAir):
+    """The machine's side of the sponge bus: one row per step.  Main columns (id, w0, len, sel, digest, recv): first row
+    ``id = 0``, ``next.id = id + 1``, ``sel`` boolean, ``recv + sel = 0``; the row receives (SPONGE_TAG, id, digest) with
+    multiplicity ``recv``.  A selected call absorbs the ``len`` words w0, w0 + 1, ...; ``sponge_chip_table`` makes the
+    chip's trace from this one in HBM and ``sponge_fetch_digests`` fills ``digest`` from it.  Constraint degree 3."""
+
+    ID, W0, LEN, SEL, DIGEST, RECV = range(6)
+    WIDTH = 6
+    logup = LogUp([(("col", 5), [("const", SPONGE_TAG), ("col", 0), ("col", 4)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return self.WIDTH
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        sel = local[self.SEL]
+        builder.assert_zero(sel * (sel - 1))
+        builder.assert_zero(local[self.RECV] + sel)
+        builder.when_first_row().assert_zero(local[self.ID])
+        builder.when_transition().assert_eq(nxt[self.ID], local[self.ID] + 1)
+        # implied by the first line; constraint degree 3, as every bus AIR (see BusSendAir)
+        builder.assert_zero(local[self.W0] * sel * (sel - 1))
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+class SpongeChipAir(BaseAir):
+    """The chip of the sponge bus: one row per absorbed word.  Main columns (first, last, id, word, acc, state):
+
+    * ``first`` and ``last`` boolean; ``state = acc^7`` (BabyBear's S-box: gcd(7, p - 1) = 1);
+    * first row ``acc = IV + word``; on transitions ``next.acc = next.first IV + (1 - next.first) state + next.word``,
+      a continued call keeps its id, ``(1 - next.first) (next.id - id) = 0``, and nothing continues a finished one,
+      ``last (1 - next.first) = 0``.
+
+    On ``last`` the row sends (SPONGE_TAG, id, state).  A pad row is (1, 0, 0, 0, IV, IV^7): a call of its own that sends
+    nothing.  Constraint degree 7.  It is a demonstrator of the route -- a chip whose state column ``iterate`` fills in
+    HBM -- not a vetted chip."""
+
+    FIRST, LAST, ID, WORD, ACC, STATE = range(6)
+    WIDTH = 6
+    logup = LogUp([(("col", 1), [("const", SPONGE_TAG), ("col", 2), ("col", 5)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return self.WIDTH
+
+    def eval_main(self, builder) -> None:
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        first, last, acc = local[self.FIRST], local[self.LAST], local[self.ACC]
+        for b in (first, last):
+            builder.assert_zero(b * (b - 1))
+        a2 = acc * acc
+        a4 = a2 * a2
+        builder.assert_eq(local[self.STATE], a4 * a2 * acc)
+        builder.when_first_row().assert_eq(acc, local[self.WORD] + SPONGE_IV)
+        t = builder.when_transition()
+        cont = 1 - nxt[self.FIRST]
+        t.assert_eq(nxt[self.ACC], nxt[self.FIRST] * SPONGE_IV + cont * local[self.STATE] + nxt[self.WORD])
+        t.assert_zero(cont * (nxt[self.ID] - local[self.ID]))
+        t.assert_zero(last * cont)
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+def generate_sponge_call_trace(n: int, max_len: int, seed: int = SPLITMIX_SEED, unfilled: bool = False) -> np.ndarray:
+    """(n, 6) canonical u32 satisfying SpongeCallAir, driven by a SplitMix64 stream: about half of the rows selected,
+    1 <= len <= max_len, w0 < p.  ``unfilled``: ``digest`` is 0 everywhere -- what a producer has before the chip ran."""
+    r = splitmix64_stream(seed, 3 * n).reshape(n, 3).astype(np.uint64)
+    A = SpongeCallAir
+    out = np.zeros((n, A.WIDTH), dtype=np.uint32)
+    out[:, A.ID] = np.arange(n)
+    out[:, A.W0] = r[:, 0] % np.uint64(P)
+    out[:, A.LEN] = r[:, 1] % np.uint64(max_len) + np.uint64(1)
+    out[:, A.SEL] = (r[:, 2] >> np.uint64(17)) & np.uint64(1)
+    out[:, A.RECV] = (P - out[:, A.SEL].astype(np.int64)) % P
+    if not unfilled:
+        for row in out:
+            if row[A.SEL]:
+                state = None
+                for j in range(int(row[A.LEN])):
+                    acc = ((SPONGE_IV if state is None else state) + int(row[A.W0]) + j) % P
+                    state = pow(acc, 7, P)
+                row[A.DIGEST] = state
+    return out
+
+
+def sponge_expand_spec(max_len: int):
+    """The word table of a SpongeCallAir trace as a spec for ``expand_rows``: a selected call asks for ``len`` rows
+    (first, last, id, word = w0 + j, 0, 0); the pad row starts a call of its own."""
+    from .expand import FIRST, LAST, ExpandSpec, col, stepped
+    A = SpongeCallAir
+    return ExpandSpec(A.WIDTH, 6, count=col(A.LEN), when=col(A.SEL), max_count=max_len, pad=[1, 0, 0, 0, 0, 0],
+                      terms=[FIRST, LAST, col(A.ID), stepped(A.W0, 1), 0, 0])
+
+
+def sponge_program(max_group_rows: int = 1 << 10):
+    """The TITR program that fills ``acc`` and ``state`` of a SpongeChipAir table with one carry: the state after the
+    previous row of the call, the IV on its first row.  A call starts where ``first`` is set."""
+    from .iterate import IterateBuilder
+    T = SpongeChipAir
+    b = IterateBuilder(T.WIDTH, reset_column=T.FIRST, max_group_rows=max_group_rows)
+    state = b.carry(SPONGE_IV)
+    acc = state + b.col(T.WORD)
+    a2 = acc * acc
+    a4 = a2 * a2
+    new = a4 * a2 * acc
+    b.set_carry(state, new)
+    b.output(acc, T.ACC)
+    b.output(new, T.STATE)
+    return b
+
+
+def sponge_chip_table(ctx, call_trace, out_height: int = 0, max_len: int = 1 << 10):
+    """The SpongeChipAir trace of a resident SpongeCallAir trace, without leaving HBM: the expansion, then one
+    ``iterate``.  Returns (the table, n_live)."""
+    from .stark import expand_rows
+    d_rows, n_live = expand_rows(ctx, sponge_expand_spec(max_len), call_trace, out_height)
+    return d_rows.iterate(sponge_program(max_len)), n_live
+
+
+def sponge_fetch_digests(call_trace, chip_table):
+    """A resident SpongeCallAir trace with ``digest`` filled from a resident chip table: a selected call fetches the
+    ``state`` of the row with its id and ``last`` set (``join_rows``); the others keep their word."""
+    from .join import KEEP, JoinSpec, col
+    A, T = SpongeCallAir, SpongeChipAir
+    spec = JoinSpec(keys=[(col(A.ID), col(T.ID)), (1, col(T.LAST))], when=col(A.SEL), fetch=[(T.STATE, A.DIGEST, 0)],
+                    flags=KEEP)
+    return call_trace.join_rows(chip_table, spec)[0]
+
+
+def generate_sponge_chip_trace(call_trace: np.ndarray, out_height: int = 0) -> np.ndarray:
+    """``sponge_chip_table`` on the host with a plain loop, for the comparison: (height, 6) canonical u32 satisfying
+    SpongeChipAir, padded to ``out_height`` or to the least power of two that holds the words."""
+    A, T = SpongeCallAir, SpongeChipAir
+    rows = []
+    for call in np.asarray(call_trace, dtype=np.uint32).tolist():
+        if call[A.SEL] != 1:
+            continue
+        state = SPONGE_IV
+        for j in range(call[A.LEN]):
+            word = (call[A.W0] + j) % P
+            acc = (state + word) % P
+            state = pow(acc, 7, P)
+            rows.append([int(j == 0), int(j == call[A.LEN] - 1), call[A.ID], word, acc, state])
+    height = out_height or 1 << max(len(rows) - 1, 0).bit_length()
+    assert len(rows) <= height
+    rows += [[1, 0, 0, 0, SPONGE_IV, pow(SPONGE_IV, 7, P)]] * (height - len(rows))
+    return np.array(rows, dtype=np.uint32).reshape(height, T.WIDTH)

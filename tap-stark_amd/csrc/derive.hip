@@ -17,6 +17,7 @@
 #include <string>
 
 #include "derive.hpp"
+#include "iterate.hpp"
 #include "prover_internal.hpp"
 
 namespace ts {
@@ -77,9 +78,11 @@ k_derive(const uint4* __restrict__ code, const uint32_t* __restrict__ named, con
 }
 
 DeviceMatrix derive_matrix(Context& ctx, const uint32_t* program, size_t n_words, const DeviceMatrix& src) {
-    StageTimer timer(&ctx, "derive");
-    require_resident(ctx, src, "derive", "the source");
+    const bool iterate = program && n_words && program[0] == ITERATE_MAGIC;
+    StageTimer timer(&ctx, iterate ? "iterate" : "derive");
+    require_resident(ctx, src, iterate ? "iterate" : "derive", "the source");
     const DeriveProgram prog = derive_lower(program, n_words, src.width);
+    if (prog.iterate) return iterate_matrix(ctx, prog, src);  // the other program kind: iterate.hip
 
     DeviceMatrix out;
     out.buf = DevBuf<uint32_t>(&ctx, (size_t)src.height * prog.out_width);

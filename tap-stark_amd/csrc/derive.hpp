@@ -18,36 +18,52 @@ constexpr uint32_t DERIVE_MAX_OUTPUTS = 256;
 constexpr uint32_t DERIVE_MAX_LIVE = 48;            // 48 slots x 256 lanes x 4 B = 48 KiB of LDS (quotient.hip plan_reg_file)
 constexpr uint32_t DERIVE_MAX_WIDTH = 1u << 16;     // as the sort: height * width stays below 2^43 words
 constexpr uint64_t DERIVE_MAX_HEIGHT = 1ull << 27;
+// The second program kind of the same entry points (include/tapstark.h "iterated columns"): a row program with
+// registers carried down each group of rows.  iterate.hpp has its evaluator, iterate.cpp the host loop, iterate.hip
+// the kernels; the checks and the lowering are derive_lower's.
+constexpr uint32_t ITERATE_MAGIC = 0x52544954u;  // "TITR"
+constexpr uint32_t ITERATE_MAX_CARRIES = 16;
+constexpr uint64_t ITERATE_MAX_WORK = 1ull << 20;   // max_group_rows x instructions: what one lane may be asked to run
+constexpr uint32_t ITERATE_NO_RESET = 0xFFFFFFFFu;  // reset_column: the whole matrix is one group
 
 // The tape's op numbers; an instruction keeps its node's.  V_STORE exists only in the lowered list: one more
-// destination column for the value of the instruction before it.
+// destination column for the value of the instruction before it.  40 to 43 are ops of a TITR tape alone; V_LATCH exists
+// only in its lowered list: carry slot <- the value its node had on this row.
 enum DeriveOp : uint32_t {
     V_CONST = 0, V_COL = 1, V_IS_FIRST = 3, V_IS_LAST = 4, V_IS_TRANSITION = 5, V_ADD = 6, V_SUB = 7, V_NEG = 8, V_MUL = 9,
-    V_ROW = 32, V_INV = 33, V_IS_ZERO = 34, V_LT = 35, V_BITS = 36, V_AND = 37, V_XOR = 38, V_STORE = 63,
+    V_ROW = 32, V_INV = 33, V_IS_ZERO = 34, V_LT = 35, V_BITS = 36, V_AND = 37, V_XOR = 38,
+    V_CARRY = 40, V_STEP = 41, V_IS_GROUP_FIRST = 42, V_IS_GROUP_LAST = 43, V_LATCH = 62, V_STORE = 63,
 };
 
 // One instruction, four words (one scalar 16-byte load on the device):
 //   x = op | slot << 8 | stores << 16   slot: where the value goes (< n_live); stores: 1 = it is also out column w
 //   y, z = the operands: slots for the arithmetic ops (z is BITS's shift | nbits << 8); CONST: y = the value in
-//          Montgomery form; COL: y = row offset, z = column; V_STORE: y = the slot
+//          Montgomery form; COL: y = row offset, z = column; V_STORE: y = the slot; CARRY: y = the carry's slot
+//          (carry k owns slot k for the whole walk); V_LATCH: slot = the carry's, y = the slot of its node
 //   w = the destination column of a store
 // Every value in a slot is a field element in Montgomery form; a store writes its canonical word.
+// A TITR program: the latches stand at the END of the list, after every CARRY has been read, and each reads the slot
+// of a node, never a carry slot (CARRY is an instruction with a slot of its own), so their order does not matter.
 struct DeriveProgram {
     uint32_t src_width = 0, out_width = 0;
     uint32_t n_nodes_kept = 0;             // instructions but for V_STORE: the nodes an output reaches
     uint32_t n_live = 0;                   // slots
     std::vector<uint32_t> code;            // 4 words per instruction
     std::vector<uint32_t> named;           // bit c: out column c is written by a store (else copied from src)
+    bool iterate = false;                  // a TITR program: the fields below, and n_live counts the carry slots
+    uint32_t reset_column = ITERATE_NO_RESET, max_group_rows = 0;
+    std::vector<uint32_t> inits;           // per carry, Montgomery form
     uint32_t n_instr() const { return (uint32_t)(code.size() / 4); }
 };
 
 // Checks the tape against every rule that needs no matrix and lowers it; throws TS_ERR_INVALID with a text.
 DeriveProgram derive_lower(const uint32_t* program, size_t n_words, uint32_t src_width);
-// out (height x out_width, row-major) from src (height x src_width) through the lowered list, on the host.
+// out (height x out_width, row-major) from src (height x src_width) through the lowered list, on the host.  A TITR
+// program goes to iterate_rows_host (iterate.cpp), which refuses a group longer than max_group_rows before it writes.
 void derive_rows_host(const DeriveProgram& prog, const uint32_t* src, uint64_t height, uint32_t* out);
 // A new row-major matrix of src's height and the program's out_width (derive.hip).  `src` is row-major, on ctx, read
 // only.  Throws TS_ERR_INVALID before any device work; one upload of the lowered list through the context's page-locked
-// arena and one launch, no host wait.
+// arena and one launch, no host wait.  A TITR program goes to iterate_matrix (iterate.hip): four launches, one wait.
 struct Context;
 struct DeviceMatrix;
 DeviceMatrix derive_matrix(Context& ctx, const uint32_t* program, size_t n_words, const DeviceMatrix& src);

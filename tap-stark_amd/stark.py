@@ -385,6 +385,11 @@ class DeviceMatrix:
         self.ctx.check(self.ctx._l.ts_matrix_derive(self.ctx.h, _p(t), len(t), self.h, C.byref(h)))
         return DeviceMatrix(self.ctx, h)
 
+    def iterate(self, program) -> "DeviceMatrix":
+        """The same call as ``derive`` for a program with carried state: ``program`` is an ``iterate.IterateBuilder`` or
+        its TITR tape (include/tapstark.h "iterated columns").  One host wait."""
+        return self.derive(program)
+
     def scan(self, spec, finals: bool = False):
         """A new matrix of this height: the columns the scans of ``spec`` (a ``scan.ScanSpec``) name hold linear
         recurrences down the rows of this matrix, the other kept columns are copied (``ts_matrix_scan``); this matrix is
