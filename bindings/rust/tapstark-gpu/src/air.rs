@@ -511,3 +511,67 @@ impl IterateBuilder {
         t
     }
 }
+
+// ---- the group form of the collect's spec (include/tapstark.h "grouped rows"): the counterpart of
+// tap-stark_amd/group.py and of ts::air::Group, word for word.  Like the rest of this crate it has not been compiled.
+pub const GROUP_MAGIC: u32 = 0x5052_4754; // "TGRP"
+pub const G_CONST: u32 = 0;
+pub const G_FIRST: u32 = 1;
+pub const G_LAST: u32 = 2;
+pub const G_FIRST_ROW: u32 = 3;
+pub const G_LAST_ROW: u32 = 4;
+pub const G_COUNT: u32 = 5;
+pub const G_SUM: u32 = 6;
+pub const G_MIN: u32 = 7;
+pub const G_MAX: u32 = 8;
+pub const G_INDEX: u32 = 9;
+
+/// A key, the selector or an output term of a [`GroupSpec`]: `{kind, value}`.
+#[derive(Clone, Copy, Debug)]
+pub struct GroupTerm(pub u32, pub u32);
+
+impl GroupTerm {
+    pub fn constant(v: u64) -> Self { Self(G_CONST, (v % 0x7800_0001) as u32) }
+    /// As a key or the selector: column `c`; as an output term: `first(c)`.
+    pub fn col(c: u32) -> Self { Self(1, c) }
+    pub fn always() -> Self { Self(0, 1) }
+    pub fn first(c: u32) -> Self { Self(G_FIRST, c) }
+    pub fn last(c: u32) -> Self { Self(G_LAST, c) }
+    pub fn first_row() -> Self { Self(G_FIRST_ROW, 0) }
+    pub fn last_row() -> Self { Self(G_LAST_ROW, 0) }
+    pub fn count() -> Self { Self(G_COUNT, 0) }
+    pub fn total(c: u32) -> Self { Self(G_SUM, c) }
+    pub fn least(c: u32) -> Self { Self(G_MIN, c) }
+    pub fn greatest(c: u32) -> Self { Self(G_MAX, c) }
+    pub fn index() -> Self { Self(G_INDEX, 0) }
+}
+
+/// Collects the keys, the selector, the pad row and the terms of a TGRP tape.  Nothing is checked here:
+/// `ts_collect_check` is the judge.
+pub struct GroupSpec {
+    pub src_width: u32,
+    pub out_width: u32,
+    pub keys: Vec<GroupTerm>,
+    pub when: GroupTerm,
+    pub pad: Vec<u32>, // shorter than out_width: filled with zeros
+    pub terms: Vec<GroupTerm>,
+}
+
+impl GroupSpec {
+    pub fn new(src_width: u32, out_width: u32, keys: Vec<GroupTerm>) -> Self {
+        Self { src_width, out_width, keys, when: GroupTerm::always(), pad: Vec::new(), terms: Vec::new() }
+    }
+    pub fn tape(&self) -> Vec<u32> {
+        let mut t = vec![GROUP_MAGIC, 1, self.src_width, self.out_width, self.keys.len() as u32, self.when.0, self.when.1];
+        for k in &self.keys {
+            t.extend([k.0, k.1]);
+        }
+        let mut pad = self.pad.clone();
+        pad.resize(self.out_width as usize, 0);
+        t.extend(pad);
+        for k in &self.terms {
+            t.extend([k.0, k.1]);
+        }
+        t
+    }
+}

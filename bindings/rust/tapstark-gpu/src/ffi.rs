@@ -267,6 +267,10 @@ pub const TS_SCAN_EXCLUSIVE: u32 = 1;
 pub const TS_COLLECT_MAX_SOURCES: usize = 4;
 pub const TS_COLLECT_MAX_EMITTERS: usize = 16;
 pub const TS_COLLECT_MAX_WIDTH: usize = 64;
+/// The limits of the group form ("TGRP") of a `ts_matrix_collect_rows` spec.
+pub const TS_GROUP_MAX_KEYS: usize = 8;
+pub const TS_GROUP_MAX_AGGREGATES: usize = 16;
+pub const TS_GROUP_MAX_WIDTH: usize = 64;
 /// The limits and the flags of a `ts_matrix_join_rows` spec.
 pub const TS_JOIN_MAX_KEYS: usize = 8;
 pub const TS_JOIN_MAX_FETCH: usize = 32;

@@ -1592,8 +1592,8 @@ ts_status ts_scan_rows_host(const ts_scan_spec* spec, const uint32_t* src_row_ma
  * that makes small matrices cross the wave, the workgroup and several trips of launch 2's loop.  No output word depends
  * on it.  A value so small that the job grid would pass 2^24 workgroups is refused.
  * Out of scope: use inside batch lanes; a predicate other than one column (derive it first); any reordering (sort
- * afterwards); removal of duplicates; more than 4 sources, 16 emitters or 64 output columns; extension-field words; a
- * kernel specialised per spec. */
+ * afterwards); more than 4 sources, 16 emitters or 64 output columns; extension-field words; a kernel specialised per
+ * spec.  Removal of duplicates is the group form of this call ("grouped rows" below). */
 enum { TS_COLLECT_MAX_SOURCES = 4, TS_COLLECT_MAX_EMITTERS = 16, TS_COLLECT_MAX_WIDTH = 64 };
 ts_status ts_matrix_collect_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_words,
                                  const ts_matrix* const* sources /* n_sources */, uint64_t out_height,
@@ -1609,6 +1609,71 @@ ts_status ts_collect_check(const uint32_t* spec, size_t n_words, uint32_t* n_sou
 ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint32_t* const* src_row_major,
                                const uint64_t* heights, uint64_t out_height, uint32_t* out_row_major,
                                size_t out_cap_words, uint64_t* out_height_used, uint64_t* n_live);
+
+/* ---- grouped rows: one row per distinct key tuple, in HBM ----
+ * The collect stacks rows; nothing above makes ONE ROW PER DISTINCT KEY: the table of touched addresses of a memory
+ * trace with each address's final value and the clock of its last access (what a continuation hands to the next
+ * segment), the distinct (opcode, a, b) tuples a trace looked up with their multiplicities, per-call totals of a chip
+ * table, per-page access counts.  That is a GROUP BY, and it is a second tape form of the three collect calls above,
+ * told apart by its magic: no entry point of its own.  It replaces: ts_matrix_download, np.unique / np.lexsort and
+ * reduceat on the host, ts_matrix_upload -- or, on sorted input only, sort, derive, scan and collect with four
+ * output-sized matrices and two waits.
+ *   [0]=0x50524754 ("TGRP") [1]=1 [2]=src_width (1..2^16) [3]=out_width (1..64) [4]=n_keys (1..8)
+ *   [5]=sel_kind [6]=sel_value       the expand's rule: 0/1 every row; 1/c column c, the row takes part iff word mod p != 0
+ *   n_keys x {kind, value}           key terms: kind 0 a constant < p, kind 1 a column of the row
+ *   out_width x pad word             each < p
+ *   out_width x {kind, value}        one term per output column
+ * 7 + 2 n_keys + 3 out_width words.  Exactly ONE source: sources[0], or src_row_major[0] and heights[0] on the host;
+ * the check call reports n_sources = 1.
+ * Groups: the rows that take part and carry equal key tuples form a group.  Key words are compared AS STORED, the rule
+ * of the join and of the multiplicity fill: p + 1 does not match 1.  A row that takes no part belongs to no group and
+ * feeds no aggregate.
+ * Order: one output row per group, in ascending order of the group's LEAST source row -- first appearance.  On a
+ * source sorted by its key (the sort is stable) that is key order.
+ * Terms, for the group with least row f, greatest row l and n rows:
+ *   0 CONST      the constant (value < p)          5 COUNT  n (value 0)
+ *   1 FIRST      column `value` of row f, as stored  6 SUM    the sum over the group of (word mod p), mod p, canonical
+ *   2 LAST       column `value` of row l, as stored  7 MIN    the least (word mod p) of the group
+ *   3 FIRST_ROW  f (value 0)                        8 MAX    the greatest (word mod p)
+ *   4 LAST_ROW   l (value 0)                        9 INDEX  the group's own output row index (value 0)
+ * At most 16 terms of kinds 6 to 8.  Sums are exact: integer sums of canonical words, below 2^58 at 2^27 rows, reduced
+ * once.  Every aggregate is order-independent, so the result is the same words on every run and for every value of the
+ * two knobs below.
+ * Height: *n_live is the number of groups; out_height and the pad rows follow the collect's rule; a call where no row
+ * takes part gives n_live = 0 and one pad row.  More groups than a given out_height is refused after the wait with
+ * TS_ERR_INVALID "group: N groups, out_height H": *out is NULL, *n_live is 0 and every pool block the call took is back
+ * in the pool.
+ * TS_ERR_INVALID before any device work, each matrix-free one with a text of its own prefixed "group:" (the check call
+ * makes them, the host loop makes them first): a count outside its range; a word count that does not match the header;
+ * the selector rules; a key or term kind out of range; a column outside the source; a constant or pad word not below
+ * p; a non-zero value word where the table says 0; more than 16 aggregates.  Those that need a matrix are the
+ * collect's: wrong width, not row-major, consumed, another context, height outside [1, 2^27], out_height, a knob
+ * outside its range.
+ * Launches: plain ones, no cooperative launch, no workgroup waits for another, every probe loop bounded by the
+ * capacity of the slot table (the power of two at or above 2 x height).  (1) insert: one lane per row evaluates the
+ * selector, builds the tuple and runs the join's atomicCAS / atomicMin protocol, after which each class owns one slot
+ * that holds its least row; the row keeps its class's slot index, so no later pass probes again; (2) per block of at
+ * most TS_COLLECT_BLOCK_ROWS rows the leaders (rows their class's slot holds) are counted; (3) the collect's scan of
+ * the block counts; then the one wait; (4) the groups' records are filled with their identities; (5) leaders take
+ * index = block offset + rank and write it where the rows of their class find it; (6) every row that takes part adds
+ * into its group's record: COUNT and the sums by 64-bit atomicAdd, LAST_ROW by atomicMax, MIN / MAX by 32-bit atomicMin
+ * / atomicMax -- a wave whose rows all go to one group (a sorted source) combines with shuffles first and issues one
+ * atomic per accumulator; (7) the result is written as one word range with consecutive lanes on consecutive words,
+ * FIRST and LAST words gathered from the source, the pad rows by the workgroups behind the grid.  Every output word is
+ * written exactly once and nothing reads the output; everything a kernel reads was written by a fill or a kernel of
+ * this call.
+ * Waits: exactly ONE, for the copy back of the number of groups (16 bytes), which sizes the result and the records.
+ * Temporaries, all from ctx's pool: the slot table (4 bytes x capacity: 8 to 16 bytes per source row), the class word
+ * (4 bytes per source row), the block counts and offsets (12 bytes per block), and, sized after the wait, the records:
+ * 8 bytes x (3 + aggregates) per GROUP.  No table of capacity x aggregates.
+ * Knobs, both read on every call, no output word depends on either: TS_COLLECT_BLOCK_ROWS (1 .. 1024) caps the rows of
+ * a count block, with the meaning and the refusals it has above; TS_LOGUP_HASH_BITS (0 .. 32) lengthens the probe
+ * chains.
+ * Out of scope: several sources; a group id per SOURCE row (join the source against the result by key with
+ * TS_JOIN_TABLE_ROW, or fetch INDEX); keys compared mod p (derive a canonical column first); products, or aggregates
+ * over extension-field words; more than 8 key words, 16 aggregates or 64 columns; use inside batch lanes; a kernel
+ * specialised per spec. */
+enum { TS_GROUP_MAX_KEYS = 8, TS_GROUP_MAX_AGGREGATES = 16, TS_GROUP_MAX_WIDTH = 64 };
 
 /* ---- joined rows: columns of another table, fetched by key, in HBM ----
  * Every call above reads the rows of its own sources.  A column whose value is DEFINED BY ANOTHER TABLE -- the

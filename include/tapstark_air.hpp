@@ -569,6 +569,57 @@ private:
     std::vector<uint32_t> pad_, records_;
 };
 
+// ---- specs for the group form of ts_matrix_collect_rows (include/tapstark.h "grouped rows"): the counterpart of
+// tap-stark_amd/group.py, word for word.  A key is Group::constant(v) (reduced mod p here) or Group::col(c); the selector
+// Group::always() or Group::col(c); an output term Group::constant(v), Group::first(c), Group::last(c),
+// Group::first_row(), Group::last_row(), Group::count(), Group::total(c), Group::least(c), Group::greatest(c) or
+// Group::index().  tape() is the word tape the three collect calls take.  Nothing is checked here; ts_collect_check is
+// the judge.
+class Group {
+public:
+    struct Term {
+        uint32_t kind, value;
+    };
+    static constexpr uint32_t MAGIC = 0x50524754u;  // "TGRP"
+    static Term constant(uint64_t v) { return Term{0, (uint32_t)(v % P)}; }
+    static Term col(uint32_t c) { return Term{1, c}; }  // as a key or the selector: column c; as an output term: first(c)
+    static Term always() { return Term{0, 1}; }
+    static Term first(uint32_t c) { return Term{1, c}; }
+    static Term last(uint32_t c) { return Term{2, c}; }
+    static Term first_row() { return Term{3, 0}; }
+    static Term last_row() { return Term{4, 0}; }
+    static Term count() { return Term{5, 0}; }
+    static Term total(uint32_t c) { return Term{6, c}; }
+    static Term least(uint32_t c) { return Term{7, c}; }
+    static Term greatest(uint32_t c) { return Term{8, c}; }
+    static Term index() { return Term{9, 0}; }
+
+    // a pad row shorter than out_width is filled with zeros
+    Group(uint32_t src_width, uint32_t out_width, std::vector<Term> keys, Term when = Term{0, 1},
+          std::vector<uint32_t> pad = {})
+        : src_width_(src_width), out_width_(out_width), keys_(std::move(keys)), when_(when), pad_(std::move(pad)) {
+        pad_.resize(out_width_, 0);
+    }
+    Group& terms(const std::vector<Term>& terms) {
+        terms_ = terms;
+        return *this;
+    }
+    std::vector<uint32_t> tape() const {
+        std::vector<uint32_t> t = {MAGIC, 1, src_width_, out_width_, (uint32_t)keys_.size(), when_.kind, when_.value};
+        for (const Term& k : keys_) t.insert(t.end(), {k.kind, k.value});
+        t.insert(t.end(), pad_.begin(), pad_.end());
+        for (const Term& k : terms_) t.insert(t.end(), {k.kind, k.value});
+        return t;
+    }
+
+private:
+    uint32_t src_width_, out_width_;
+    std::vector<Term> keys_;
+    Term when_;
+    std::vector<uint32_t> pad_;
+    std::vector<Term> terms_;
+};
+
 // ---- specs for ts_matrix_expand_rows (include/tapstark.h "expanded rows"): the counterpart of
 // tap-stark_amd/expand.py, word for word.  A term is Expand::constant(v) (reduced mod p here), Expand::col(c),
 // Expand::row(), Expand::inner(), Expand::remaining(), Expand::first(), Expand::last() or Expand::stepped(c, step);

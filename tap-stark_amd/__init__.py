@@ -20,3 +20,5 @@ from .stark import collect_rows  # noqa: F401
 from .join import JoinSpec, join_check, join_rows_host  # noqa: F401
 from .expand import ExpandSpec, expand_check, expand_rows_host  # noqa: F401
 from .stark import expand_rows  # noqa: F401
+from .group import GroupSpec, group_check, group_rows_host  # noqa: F401
+from .stark import group_rows  # noqa: F401

@@ -1306,6 +1306,125 @@ def fill_memory_range_multiplicities(range_trace, memory_table, allow_missing: b
                                     out_column=1, negate=1, allow_missing=allow_missing)
 
 
+# ---------------------------------------------------------------------------------------------- the final state of memory
+# The table a continuation hands to the next segment: one row per touched address with its final value and the clock
+# of its last access.  The sorted memory table marks the last access of every address and sends it; a table of its own
+# -- ONE group call over the sorted table (``group_rows``, include/tapstark.h "grouped rows") -- receives it.
+
+FIN_TAG = 23
+
+
+class MemoryTableFinalAir(MemoryTableAir):
+    """MemoryTableAir with a column ``last`` behind ``start``: boolean, ``last = live (1 - next.cont)`` on transitions
+    (``next.cont = next.live - next.start``: the next row goes on with this address) and ``last = live`` on the last
+    row -- 1 exactly on the last access of every address.  Beside MemoryTableAir's two interactions the row sends
+    (FIN_TAG, addr, clk, value) with multiplicity ``last``.  Constraint degree 3."""
+
+    LAST = 8
+    logup = LogUp(MemoryTableAir.logup.interactions + [(("col", 8), [("const", FIN_TAG), ("col", 0), ("col", 1), ("col", 2)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 9
+
+    def eval_main(self, builder) -> None:
+        super().eval_main(builder)
+        main = builder.main()
+        local, nxt = main.row_slice(0), main.row_slice(1)
+        last, live = local[self.LAST], local[self.LIVE]
+        builder.assert_zero(last * (last - 1))
+        builder.when_transition().assert_zero(last - live * (1 - (nxt[self.LIVE] - nxt[self.START])))
+        builder.when_last_row().assert_zero(last - live)
+
+
+class MemoryFinalAir(BaseAir):
+    """Main columns (addr, clk, value, count, live, recv): one row per touched address -- its final value, the clock of
+    its last access and the number of its accesses -- the live rows first.  ``live`` boolean, ``recv + live = 0``; the
+    row receives (FIN_TAG, addr, clk, value) with multiplicity ``recv``.  That every address appears once follows from
+    the bus: MemoryTableFinalAir sends one tuple per address group.  ``count`` is carried, not constrained.  Constraint
+    degree 3."""
+
+    ADDR, CLK, VALUE, COUNT, LIVE, RECV = range(6)
+    logup = LogUp([(("col", 5), [("const", FIN_TAG), ("col", 0), ("col", 1), ("col", 2)])])
+    aux_width, n_challenges, n_exposed = logup.aux_width, logup.n_challenges, logup.n_exposed
+
+    def width(self) -> int:
+        return 6
+
+    def eval_main(self, builder) -> None:
+        local = builder.main().row_slice(0)
+        live = local[self.LIVE]
+        builder.assert_zero(live * (live - 1))
+        builder.assert_zero(local[self.RECV] + live)
+        # implied by the first line; constraint degree 3, as every bus AIR (see BusSendAir)
+        builder.assert_zero(local[self.ADDR] * live * (live - 1))
+
+    def eval(self, builder) -> None:
+        self.eval_main(builder)
+        self.logup.eval(builder)
+
+
+def memory_last_program():
+    """``last`` as a row program over the sorted (n, 8) MemoryTableAir trace, appended as column 8: ``live (1 - (1 -
+    is_last_row) (next.live - next.start))``, a column of its own row and the row after it."""
+    from .derive import DeriveBuilder
+    A = MemoryTableAir
+    b = DeriveBuilder(8)
+    goes_on = (1 - b.is_last_row()) * (b.next(A.LIVE) - b.next(A.START))
+    b.output(b.col(A.LIVE) * (1 - goes_on), MemoryTableFinalAir.LAST)
+    return b
+
+
+def memory_final_group_spec():
+    """The MemoryFinalAir trace as ONE group call over the sorted (n, 9) table: key ``addr``, the live rows take part;
+    per address its own word, the clock and the value of its last access, the number of its accesses, ``live = 1`` and
+    ``recv = p - 1``.  The pad row is all zero: a dead row."""
+    from .collect import col, const
+    from .group import COUNT, GroupSpec, first, last
+    A = MemoryTableFinalAir
+    return GroupSpec(9, 6, keys=[col(A.ADDR)], when=col(A.LIVE),
+                     terms=[first(A.ADDR), last(A.CLK), last(A.VALUE), COUNT, const(1), const(P - 1)])
+
+
+def generate_memory_table_final(accesses: np.ndarray) -> np.ndarray:
+    """(n, 9) canonical u32 satisfying MemoryTableFinalAir, all on the host: ``generate_memory_table`` and ``last``."""
+    t = generate_memory_table(accesses)
+    A = MemoryTableAir
+    goes_on = np.zeros(t.shape[0], dtype=np.int64)
+    goes_on[:-1] = t[1:, A.LIVE].astype(np.int64) - t[1:, A.START]
+    return np.concatenate([t, (t[:, A.LIVE] * (1 - goes_on)).astype(np.uint32)[:, None]], axis=1)
+
+
+def generate_memory_final(table_final: np.ndarray, out_height: int = 0) -> np.ndarray:
+    """(height, 6) canonical u32 satisfying MemoryFinalAir, on the host, from a MemoryTableFinalAir trace: what the group
+    call of ``memory_final_group_spec`` gives."""
+    A = MemoryTableFinalAir
+    t = np.asarray(table_final, dtype=np.uint32)
+    ends = np.flatnonzero(t[:, A.LAST] == 1)
+    starts = np.flatnonzero(t[:, A.START] == 1)
+    height = out_height or 1 << max(len(ends) - 1, 0).bit_length()
+    out = np.zeros((height, 6), dtype=np.uint32)
+    out[:len(ends), :3] = t[ends][:, [A.ADDR, A.CLK, A.VALUE]]
+    out[:len(ends), 3] = ends - starts + 1
+    out[:len(ends), 4] = 1
+    out[:len(ends), 5] = P - 1
+    return out
+
+
+def memory_final_tables(ctx, accesses, n_live: int, out_height: int = 0):
+    """The MemoryTableFinalAir and MemoryFinalAir traces of a resident (n, 5) access table without leaving HBM: the
+    source columns, the sort, the gaps, ``last`` by one derive over the next row, then ONE group call.  ``n_live``: the
+    selected accesses, which come first.  Returns (the sorted table, the final table, the number of
+    touched addresses)."""
+    from .stark import group_rows
+    T = MemoryTableAir
+    d_sorted = accesses.derive(memory_table_source_program()).sort_rows([T.ADDR, T.CLK], group_keys=1, n_live=n_live,
+                                                                      group_start=True)
+    d_table = d_sorted.derive(memory_gap_program()).derive(memory_last_program())
+    d_final, n_addr = group_rows(ctx, memory_final_group_spec(), d_table, out_height)
+    return d_table, d_final, n_addr
+
+
 # ---------------------------------------------------------------------------------------------- a program ROM on the bus
 # A machine trace whose rows fetch instructions from a fixed program: BusTupleSendAir(ROM_TAG, k, 3) senders of
 # (pc, opcode, arg) against a BusKeyTableAir(ROM_TAG, 3) whose contents are a matrix of the key.  The producer knows

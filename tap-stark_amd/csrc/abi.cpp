@@ -16,6 +16,7 @@
 #include "blake3.hpp"
 #include "collect.hpp"
 #include "expand.hpp"
+#include "group.hpp"
 #include "derive.hpp"
 #include "jit.hpp"
 #include "join.hpp"
@@ -2036,6 +2037,12 @@ ts_status ts_scan_rows_host(const ts_scan_spec* spec, const uint32_t* src_row_ma
 
 // Collected rows: the selected rows of up to four resident matrices as one new matrix (collect.hip), the checks and the
 // sequential loop over host rows (collect.cpp).
+// The three calls take a second tape form, told apart by its magic: grouped rows, one row per distinct key tuple of ONE
+// source (group.hip, group.cpp).  Any other first word is the collect's to judge.
+static bool is_group_tape(const uint32_t* spec, size_t n_words) {
+    return spec && n_words >= 1 && spec[0] == ts::GROUP_MAGIC;
+}
+
 ts_status ts_matrix_collect_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_words, const ts_matrix* const* sources,
                                  uint64_t out_height, ts_matrix** out, uint64_t* n_live) {
     if (out) *out = nullptr;
@@ -2046,6 +2053,14 @@ ts_status ts_matrix_collect_rows(ts_ctx* ctx, const uint32_t* spec, size_t n_wor
     }, false);
     if (refused) return refused;
     return guard(ctx, [&] {
+        if (is_group_tape(spec, n_words)) {
+            const ts::GroupPlan plan = ts::group_check(spec, n_words);
+            TS_REQUIRE(sources[0], ts::TS_ERR_INVALID, "ts_matrix_collect_rows: null argument");
+            uint64_t live = 0;
+            *out = new_matrix(ts::group_matrix(ctx->ctx, plan, sources[0]->m, out_height, &live));
+            *n_live = live;
+            return;
+        }
         const ts::CollectPlan plan = ts::collect_check(spec, n_words);  // (and so how many handles `sources` holds)
         const ts::DeviceMatrix* mats[ts::COLLECT_MAX_SOURCES] = {};
         for (uint32_t s = 0; s < plan.n_sources; s++) {
@@ -2062,6 +2077,12 @@ ts_status ts_collect_check(const uint32_t* spec, size_t n_words, uint32_t* n_sou
     if (n_sources) *n_sources = 0;
     if (out_width) *out_width = 0;
     return guard(nullptr, [&] {
+        if (is_group_tape(spec, n_words)) {
+            const ts::GroupPlan plan = ts::group_check(spec, n_words);
+            if (n_sources) *n_sources = 1;
+            if (out_width) *out_width = plan.out_width;
+            return;
+        }
         const ts::CollectPlan plan = ts::collect_check(spec, n_words);
         if (n_sources) *n_sources = plan.n_sources;
         if (out_width) *out_width = plan.out_width;
@@ -2076,6 +2097,22 @@ ts_status ts_collect_rows_host(const uint32_t* spec, size_t n_words, const uint3
     return guard(nullptr, [&] {
         TS_REQUIRE(spec && src_row_major && heights && out_row_major && out_height_used && n_live, ts::TS_ERR_INVALID,
                    "ts_collect_rows_host: null argument");
+        if (is_group_tape(spec, n_words)) {
+            const ts::GroupPlan plan = ts::group_check(spec, n_words);
+            TS_REQUIRE(src_row_major[0], ts::TS_ERR_INVALID, "ts_collect_rows_host: null argument");
+            TS_REQUIRE(heights[0] >= 1 && heights[0] <= ts::GROUP_MAX_HEIGHT, ts::TS_ERR_INVALID,
+                       "group: the height of source 0 must be in [1, 2^27]");
+            ts::collect_check_out_height(out_height);
+            const std::vector<unsigned long long> records = ts::group_records_host(plan, src_row_major[0], heights[0]);
+            const uint64_t live = records.size() / (ts::GROUP_RECORD_HEAD + plan.n_aggregates);
+            const uint64_t height = ts::group_height(live, out_height);
+            TS_REQUIRE((uint64_t)out_cap_words >= height * plan.out_width, ts::TS_ERR_BUFFER,
+                       "ts_collect_rows_host: the output buffer holds fewer than height * out_width words");
+            ts::group_rows_host(plan, records, src_row_major[0], height, out_row_major);
+            *out_height_used = height;
+            *n_live = live;
+            return;
+        }
         const ts::CollectPlan plan = ts::collect_check(spec, n_words);
         for (uint32_t s = 0; s < plan.n_sources; s++) {
             TS_REQUIRE(src_row_major[s], ts::TS_ERR_INVALID, "ts_collect_rows_host: null argument");

@@ -24,16 +24,12 @@
 #include <string>
 
 #include "collect.hpp"
+#include "collect_dev.hpp"  // the block scan, shared with group.hip
 #include "logup_dev.hpp"  // mult_knob
 #include "prover_internal.hpp"
 
 namespace ts {
 
-constexpr int COLLECT_THREADS = 256;
-constexpr int COLLECT_RPT = 4;  // rows per lane at most: a workgroup owns up to 1024 rows
-constexpr int COLLECT_WAVES = COLLECT_THREADS / 64;
-constexpr uint32_t COLLECT_PAD_TILE_ROWS = 256;
-constexpr uint32_t COLLECT_PAD_BLOCKS = 1024;
 // the image the device reads: selectors, pad row, then out_width terms per emitter (grouped by source)
 constexpr uint32_t COLLECT_IMG_PAD = COLLECT_MAX_EMITTERS;
 constexpr uint32_t COLLECT_IMG_TERMS = COLLECT_IMG_PAD + COLLECT_MAX_WIDTH;
@@ -95,30 +91,6 @@ __device__ __forceinline__ uint64_t collect_lane_mask(const CollectJob& j, const
         }
     }
     return mask;
-}
-
-// Over the workgroup's lanes in lane order: the sum of v over the lanes BEFORE this one; total <- over all lanes.
-// Wave-64 shuffles inside a wave, LDS across the waves.  Every thread calls it.
-__device__ __forceinline__ uint32_t collect_block_scan(uint32_t v, uint32_t (&wave_sums)[COLLECT_WAVES], uint32_t& total) {
-    const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (unsigned d = 1; d < 64; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)inc, d, 64);
-        if (lane >= d) inc += up;
-    }
-    __syncthreads();  // (a second call reuses wave_sums)
-    if (lane == 63) wave_sums[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < COLLECT_WAVES; k++) {
-        const uint32_t w = wave_sums[k];
-        if (k < (int)wv) before += w;
-        all += w;
-    }
-    total = all;
-    return before + inc - v;
 }
 
 __global__ void __launch_bounds__(COLLECT_THREADS)
@@ -191,6 +163,11 @@ k_collect_write(const CollectDev d, const uint32_t* __restrict__ image, const ui
     }
 }
 
+void collect_launch_offsets(Context& ctx, const uint32_t* counts, uint32_t n_blocks, uint64_t* offsets) {
+    TS_LAUNCH(ctx, k_collect_offsets, dim3(1), dim3(COLLECT_THREADS), 0, counts, n_blocks, offsets);
+    TS_HIP(hipGetLastError());
+}
+
 DeviceMatrix collect_matrix(Context& ctx, const CollectPlan& plan, const DeviceMatrix* const* sources,
                             uint64_t out_height, uint64_t* n_live_out) {
     StageTimer timer(&ctx, "collect");
@@ -245,8 +222,7 @@ DeviceMatrix collect_matrix(Context& ctx, const CollectPlan& plan, const DeviceM
     const dim3 block(COLLECT_THREADS);
     TS_LAUNCH(ctx, k_collect_count, dim3(d.n_blocks), block, 0, d, (const uint32_t*)d_image.p, counts.p);
     TS_HIP(hipGetLastError());
-    TS_LAUNCH(ctx, k_collect_offsets, dim3(1), block, 0, (const uint32_t*)counts.p, d.n_blocks, offsets.p);
-    TS_HIP(hipGetLastError());
+    collect_launch_offsets(ctx, counts.p, d.n_blocks, offsets.p);
     uint64_t n_live = 0;
     d2h_sync(ctx, &n_live, offsets.p + d.n_blocks, sizeof(n_live));  // the call's one wait
     const uint64_t height = collect_height(n_live, out_height);  // throws: the buffers above go back to the pool

@@ -446,6 +446,19 @@ def collect_rows(ctx: Context, spec, sources, out_height: int = 0):
     return DeviceMatrix(ctx, h), int(live.value)
 
 
+def group_rows(ctx: Context, spec, src: DeviceMatrix, out_height: int = 0):
+    """The pair (a new matrix, n_groups): one row per distinct key tuple among the rows of the resident matrix ``src``
+    that take part, as ``spec`` (a ``group.GroupSpec`` or its tape) says, in order of first appearance, padded to
+    ``out_height`` rows or to the least power of two that holds them (``ts_matrix_collect_rows`` with a TGRP tape).
+    ``src`` is only read.  One host wait."""
+    from .group import _tape
+    t = _tape(spec)
+    handles = (C.c_void_p * 4)(src.h)
+    h, live = C.c_void_p(), C.c_uint64()
+    ctx.check(ctx._l.ts_matrix_collect_rows(ctx.h, _p(t), len(t), handles, out_height, C.byref(h), C.byref(live)))
+    return DeviceMatrix(ctx, h), int(live.value)
+
+
 def expand_rows(ctx: Context, spec, src: DeviceMatrix, out_height: int = 0):
     """The pair (a new matrix, n_live): every row of the resident matrix ``src`` repeated by the count ``spec`` (an
     ``expand.ExpandSpec`` or its tape) reads from it, in (row, inner index) order, padded to ``out_height`` rows or to
